@@ -1,6 +1,6 @@
 """Headline benchmark: rendered rays/s of the articulated-SDF volume renderer (BASELINE.json).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one ``MetaAvatarRender.forward(inputs, eval=True)`` (per-frame hypernetwork included,
@@ -9,6 +9,9 @@ region) on one synthetic 512x512 frame of the ZJUMOCAP-377-mono configuration wi
 (BASELINE.json configs[1]).  Frames are independent, so N GPUs render disjoint frames (frame
 i -> rank i mod N): no data-path collective, weak scaling, value = all rays of all ranks
 / max-over-ranks time.
+
+--dump-outputs DIR writes what the default path returned for its last timed frame (rank 0) as DIR/<name>.npy: the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 
 Extra objects on the JSON line:
   roofline      largest single launch of the default path: k_canon_wave, loop C (every Broyden iteration of every
@@ -73,6 +76,52 @@ def aggregate(local_rays, local_seconds, dist=None):
     dist.all_reduce(r, op=dist.ReduceOp.SUM)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(r.item()), float(t.item())
+
+
+DUMP_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+DUMP_SEED = 0
+
+
+def host_outputs(out, prefix=""):
+    """The tensors of a forward's output dict (nested dicts / lists included) as host arrays: {name: float32 or float64}.
+    Names join the keys and list positions with '.'; boolean and integer outputs become float32."""
+    import numpy as np
+    arrays = {}
+    if torch.is_tensor(out):
+        a = out.detach().cpu()
+        arrays[prefix] = a.numpy() if a.dtype == torch.float64 else a.float().numpy()
+    elif isinstance(out, dict):
+        for k, v in out.items():
+            arrays.update(host_outputs(v, "%s.%s" % (prefix, k) if prefix else str(k)))
+    elif isinstance(out, (list, tuple)):
+        for i, v in enumerate(out):
+            arrays.update(host_outputs(v, "%s.%d" % (prefix, i) if prefix else str(i)))
+    return {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+
+
+def dump_outputs(arrays, path, budget=DUMP_BYTES):
+    """Write {name: array} as path/<name>.npy.  If they exceed `budget` bytes, the arrays are grouped by the length of their
+    longest axis, and every group above 1 MB is cut to one seeded sample of that axis (the same indices for the whole group,
+    written as path/sample_index_<length>.npy in float64); the other groups are written whole."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    groups = {}
+    for k, a in arrays.items():
+        groups.setdefault(max(a.shape, default=1), []).append(k)
+    total = sum(a.nbytes for a in arrays.values())
+    big = {n: ks for n, ks in groups.items() if sum(arrays[k].nbytes for k in ks) > (1 << 20)}
+    if total > budget and big:
+        big_total = sum(arrays[k].nbytes for ks in big.values() for k in ks)
+        index_total = 8 * sum(big)   # the float64 index files
+        scale = max(budget - (total - big_total) - (1 << 20), 0) / (big_total + index_total)
+        for n, ks in sorted(big.items()):
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, max(1, int(n * scale)), replace=False))
+            for k in ks:
+                arrays[k] = np.take(arrays[k], idx, axis=int(np.argmax(arrays[k].shape)))
+            arrays["sample_index_%d" % n] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return sorted(arrays)
 
 
 def pmc_traffic(kernel, full_shading=False):
@@ -151,6 +200,10 @@ def live_traffic(args, kernels, limit_s=150.0):
                  "--passes default) spawned by this run on this box; FETCH_SIZE x 2 (gfx950), KiB -> bytes")
 
 
+# worker processes of the multi-process CPU baseline: with this process, at most five processes that may open the GPU
+MAX_CPU_WORKERS = 4
+
+
 def _cpu_worker_init(cfg_name, n_steps, near, far, threads):
     # one process of the multi-process CPU baseline: its own model, its own thread pool
     global _CPU_WORKER
@@ -183,18 +236,20 @@ def _cpu_worker_render(job):
     return (lo, hi, ref["rgb_values"].numpy(), ref["network_body_mask"].numpy(), dict(ref["frame"].counters), time.perf_counter() - t0)
 
 
-def cpu_baseline_multiprocess(scene, cfg_name, size, n_steps, near, far, sample_rays, model_gpu, dev, threads_per_worker=4):
+def cpu_baseline_multiprocess(scene, cfg_name, size, n_steps, near, far, sample_rays, model_gpu, dev, threads_per_worker=8):
     """The oracle on ALL host cores: the oracle is a Python loop around torch operators on shrinking active sets and does not
     scale past a handful of threads (round 5: 208 rays/s on 128 threads against the reference's own 348 rays/s on 8), but rays are
     independent -- worker processes render disjoint slices of the same evenly subsampled rays of frame 0.  The split was
     measured on the MI355X box's host (256 logical cores, 16 384 rays, idle OpenMP threads sleeping): 16 x 8 threads 2 226 rays/s,
-    32 x 4 2 661, 64 x 2 1 990, 128 x 1 1 122, 64 x 4 1 709 (and 32 x 8 with spinning OpenMP threads: 912) -- min(32, cores / 8)
-    processes of 4 threads.  Timed: the pool's map over the slices, after every worker has built its model and rendered a
-    warm-up slice."""
+    32 x 4 2 661, 64 x 2 1 990, 128 x 1 1 122, 64 x 4 1 709 (and 32 x 8 with spinning OpenMP threads: 912).  Every worker is a
+    ROCm torch process next to this one, and a shared MI355X node allows at most six processes with the GPU open at a time: at
+    most MAX_CPU_WORKERS processes of 8 threads.  Timed: the pool's map over the slices, after every worker has built its model
+    and rendered a warm-up slice."""
     import multiprocessing as mp
     import numpy as np
     cores = os.cpu_count() or 8
-    workers = int(os.environ.get("ARAH_CPU_BASELINE_WORKERS", "0")) or max(1, min(32, cores // 8))
+    workers = int(os.environ.get("ARAH_CPU_BASELINE_WORKERS", "0")) or max(1, cores // threads_per_worker)
+    workers = min(workers, MAX_CPU_WORKERS)
     os.environ.setdefault("OMP_WAIT_POLICY", "passive")   # inherited by the workers: idle OpenMP threads sleep instead of spinning
     n = int(scene.make_inputs(size, size, frame_idx=0, max_rays=sample_rays)["ray_dirs"].shape[1])
     per = (n + workers - 1) // workers
@@ -329,6 +384,9 @@ def main():
     ap.add_argument("--passes", default="all", choices=["all", "default"],
                     help="'default': only the product's default path (profiling runs); 'all' adds the full-shading, "
                          "exact-engine and strict passes over the same frames")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the output tensors of the default path's last timed frame as "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MB in all; rank 0)")
     args = ap.parse_args()
 
     import torch.distributed as dist
@@ -725,10 +783,13 @@ def run(args, rt):
     phase2_ms = {}
     has_tiers = hasattr(rt, "set_tiering")
 
-    def timed_pass(full_shading, precision="split", n_streams=None, tiering=None):
+    last_out = {}
+
+    def timed_pass(full_shading, precision="split", n_streams=None, tiering=None, keep_last=False):
         """K timed steps (barrier + sync on both sides), then the same K steps again with HIP events
         around the dominant kernel (reading an event needs a sync per step, so it stays outside).
-        tiering: None = the product's setting, False = every sample through loops C and D (the reference's amount of work)."""
+        tiering: None = the product's setting, False = every sample through loops C and D (the reference's amount of work).
+        keep_last: copy the outputs of the last timed frame to the host (last_out["arrays"]) before anything else renders."""
         # ARAH_FULL_SHADING=1 forces the shade-everything path in every pass (the profiler's full-shading PMC passes)
         tracer.full_shading = full_shading or os.environ.get("ARAH_FULL_SHADING") == "1"
         was_tiering = rt.set_tiering(rt.tiered() if tiering is None else tiering) if has_tiers else None
@@ -747,9 +808,11 @@ def run(args, rt):
         rt.reset_counters()
         sync()
         t0 = time.perf_counter()
-        rt.render_many(timed_inputs, n_streams)
+        outs = rt.render_many(timed_inputs, n_streams)
         sync()
         dt = time.perf_counter() - t0
+        if keep_last and outs:
+            last_out["arrays"] = host_outputs(outs[-1])
         ctr = rt.counters()
         rt.set_events(full_shading, True)
         ms, cms, p2 = [], [], []
@@ -771,13 +834,14 @@ def run(args, rt):
 
     default_engine = os.environ.get("ARAH_PRECISION", "split")
     split = rt.split_engine()
+    dump = getattr(args, "dump_outputs", None) is not None and rank == 0
     with torch.no_grad():
         elapsed_one = None
         if args.streams > 1:                                    # the same frames strictly one after the other, FIRST:
             elapsed_one, _, _ = timed_pass(False, default_engine, n_streams=1)   # it is what the watchdog falls back on
         first = elapsed_one
         if first is None:
-            elapsed, counters, dens_ms = timed_pass(False, default_engine)      # the product's default path
+            elapsed, counters, dens_ms = timed_pass(False, default_engine, keep_last=dump)      # the product's default path
             first = elapsed
         if world == 1:   # what the watchdog of main() prints if a LATER pass never returns
             rt.partial_line = {
@@ -789,7 +853,7 @@ def run(args, rt):
                 "note": "PARTIAL LINE: a pass after the first one did not return (watchdog); roofline / cpu_baseline objects "
                         "were not reached" + ("; value = one frame at a time" if elapsed_one else "")}
         if elapsed_one is not None:
-            elapsed, counters, dens_ms = timed_pass(False, default_engine)      # the product's default path: frames in flight
+            elapsed, counters, dens_ms = timed_pass(False, default_engine, keep_last=dump)   # the default path: frames in flight
         elapsed_full = elapsed_exact = elapsed_strict = elapsed_untiered = None
         if args.passes == "all" and has_tiers and rt.tiered():   # every sample through loops C and D, like the reference
             elapsed_untiered, counters_untiered, dens_ms_untiered = timed_pass(False, default_engine, tiering=False)
@@ -799,6 +863,10 @@ def run(args, rt):
             elapsed_exact, _, _ = timed_pass(False, "fp32")
             elapsed_strict, counters_strict, strict_ms = timed_pass(True, "fp32")   # all of the reference's work, fp32 MFMA only
         tracer.full_shading = False
+    if dump:
+        if "arrays" not in last_out:
+            raise RuntimeError("--dump-outputs: the timed pass returned no outputs")
+        dump_outputs(last_out["arrays"], args.dump_outputs)
 
     total_rays, t_max = aggregate(n_rays_local, elapsed, dist)
     t_max_one = aggregate(n_rays_local, elapsed_one, dist)[1] if elapsed_one else None

@@ -98,10 +98,12 @@ class _StubRuntime:
         time.sleep(0.002 * (self.rank + 1))
         self.tracer.ws.n += 1
         self.rendered.append(inputs["frame"])
+        n, f = inputs["ray_dirs"].shape[1], inputs["frame"]
+        return {"rgb_values": torch.full((1, n, 3), float(f)), "network_body_mask": torch.arange(n).reshape(1, n) % 2 == 0,
+                "sdf_params": [torch.full((1, 4), f, dtype=torch.float64)]}
 
     def render_many(self, frames, n_streams):
-        for f in frames:
-            self.render(f)
+        return [self.render(f) for f in frames]
 
     def prepare(self, n_rays, n_steps):
         pass
@@ -234,3 +236,46 @@ def test_pmc_database_reduction(tmp_path):
     assert f["k_canon_wave<true, false>"] == (2000.0 * 1024.0, 2)
     assert f["k_density<true, 8>"] == (10.0 * 1024.0, 1)
     assert bench.pmc_db_per_kernel(path, "WRITE_SIZE") == {"k_density<true, 8>": (7.0 * 1024.0, 1)}
+
+
+def test_dump_outputs_writes_the_last_timed_frame(tmp_path):
+    """--dump-outputs: the outputs of the last timed frame of the default pass, every tensor of the output dict (nested ones
+    by their path) as float32 / float64 .npy files."""
+    import argparse
+    import numpy as np
+    args = argparse.Namespace(gpus=1, steps=3, warmup=1, size=64, n_steps=64, config="zju377_mono", cpu_sample_rays=16,
+                              no_cpu_baseline=True, no_train=True, passes="default", streams=1, beta=None,
+                              dump_outputs=str(tmp_path / "out"))
+    rt = _StubRuntime(1, 0)
+    line = bench.run(args, rt)
+    assert line["steps"] == 3 and rt.rendered[:4] == [0, 1, 2, 3]      # warm-up frame 0, timed frames 1..3
+    files = sorted(p.name for p in (tmp_path / "out").iterdir())
+    assert files == ["network_body_mask.npy", "rgb_values.npy", "sdf_params.0.npy"]
+    rgb = np.load(tmp_path / "out" / "rgb_values.npy")
+    mask = np.load(tmp_path / "out" / "network_body_mask.npy")
+    params = np.load(tmp_path / "out" / "sdf_params.0.npy")
+    assert rgb.dtype == np.float32 and rgb.shape == (1, 1003, 3) and (rgb == 3.0).all()
+    assert mask.dtype == np.float32 and mask.shape == (1, 1003) and mask[0, :4].tolist() == [1.0, 0.0, 1.0, 0.0]
+    assert params.dtype == np.float64 and (params == 3.0).all()
+
+
+def test_dump_outputs_samples_what_exceeds_the_budget(tmp_path):
+    """Above the budget the large arrays are cut to one seeded sample of their longest axis, the same rows for every array
+    of that length, and the rows are written next to them; small arrays stay whole; the same input writes the same files."""
+    import numpy as np
+    n = 200_000
+    arrays = {"rgb_values": np.arange(3 * n, dtype=np.float32).reshape(1, n, 3),
+              "sdf_output": np.arange(n, dtype=np.float32).reshape(1, n), "small": np.ones(10, np.float32)}
+    budget = 3 << 20
+    for d in ("a", "b"):
+        bench.dump_outputs({k: v.copy() for k, v in arrays.items()}, str(tmp_path / d), budget=budget)
+    a = {p.name: np.load(p) for p in sorted((tmp_path / "a").iterdir())}
+    b = {p.name: np.load(p) for p in sorted((tmp_path / "b").iterdir())}
+    assert sorted(a) == ["rgb_values.npy", "sample_index_%d.npy" % n, "sdf_output.npy", "small.npy"]
+    assert sum(v.nbytes for v in a.values()) <= budget
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    idx = a["sample_index_%d.npy" % n].astype(np.int64)
+    assert a["sample_index_%d.npy" % n].dtype == np.float64 and 0 < len(idx) < n and (np.diff(idx) > 0).all()
+    assert np.array_equal(a["sdf_output.npy"][0], arrays["sdf_output"][0, idx])
+    assert np.array_equal(a["rgb_values.npy"][0], arrays["rgb_values"][0, idx])
+    assert np.array_equal(a["small.npy"], arrays["small"])
