@@ -4881,6 +4881,15 @@ static OccBuf carve_occ(void* base) {
     return o;
 }
 
+// L1 distance transform of the bitmap.  It walks lines of the bitmap's box: its dimensions live on the device, the launches cover the
+// largest box the buffer can hold per pair of axes (lines beyond the box return at once)
+static void occ_distance(const OccBuf& o, hipStream_t s) {
+    const int max_lines = kOccMaxVox / 4;   // a box with fewer than 4 voxels along an axis does not occur (>= 0.16 m / voxel)
+    hipLaunchKernelGGL(k_occ_dist_x, dim3((max_lines + 255) / 256), dim3(256), 0, s, (const OccInfo*)o.info, (const unsigned*)o.bits, o.dist);
+    hipLaunchKernelGGL(k_occ_dist_yz<1>, dim3((max_lines + 255) / 256), dim3(256), 0, s, (const OccInfo*)o.info, o.dist);
+    hipLaunchKernelGGL(k_occ_dist_yz<2>, dim3((max_lines + 255) / 256), dim3(256), 0, s, (const OccInfo*)o.info, o.dist);
+}
+
 extern "C" {
 size_t arah_occupancy_bytes(void) { return carve_occ(nullptr).bytes; }
 
@@ -4919,12 +4928,18 @@ int arah_prepare_occupancy(const ArahFrame* f, void* occ_buf, size_t occ_bytes, 
     hipMemsetAsync(o.bits, 0, sizeof(unsigned) * (kOccMaxVox / 32), s);
     hipLaunchKernelGGL(k_occ_mark, dim3((kOccMaxFine + 255) / 256), dim3(256), 0, s, fd, kOccNc, kOccL, o.info,
                        (const float*)o.sel_bar, (const int*)o.sel_idx, (const float*)o.cell_stretch, o.bits);
-    // the distance transform walks lines of the bitmap's box: its dimensions live on the device, the launches cover the
-    // largest box the buffer can hold per pair of axes (lines beyond the box return at once)
-    const int max_lines = kOccMaxVox / 4;   // a box with fewer than 4 voxels along an axis does not occur (>= 0.16 m / voxel)
-    hipLaunchKernelGGL(k_occ_dist_x, dim3((max_lines + 255) / 256), dim3(256), 0, s, (const OccInfo*)o.info, (const unsigned*)o.bits, o.dist);
-    hipLaunchKernelGGL(k_occ_dist_yz<1>, dim3((max_lines + 255) / 256), dim3(256), 0, s, (const OccInfo*)o.info, o.dist);
-    hipLaunchKernelGGL(k_occ_dist_yz<2>, dim3((max_lines + 255) / 256), dim3(256), 0, s, (const OccInfo*)o.info, o.dist);
+    occ_distance(o, s);
+    return check_launch();
+}
+
+int arah_occupancy_clear_box(void* occ_buf, const float* h_lo, const float* h_hi, void* stream) {
+    if (!occ_buf || !h_lo || !h_hi) return ARAH_E_BADARG;
+    OccBuf o = carve_occ(occ_buf);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    constexpr int words = kOccMaxVox / 32;   // the launch covers the largest bitmap; words beyond this one's return at once
+    hipLaunchKernelGGL(k_occ_clear_box, dim3((words + 255) / 256), dim3(256), 0, s, (const OccInfo*)o.info, o.bits, h_lo[0], h_lo[1],
+                       h_lo[2], h_hi[0], h_hi[1], h_hi[2]);
+    occ_distance(o, s);
     return check_launch();
 }
 
@@ -5134,4 +5149,110 @@ int arah_render(const ArahFrame* f, const ArahSampling* cfg, const float* cam_lo
     return check_launch();
 }
 
+}  // extern "C"
+
+// ---- the certificate's audit (tier.hpp, include/arah_hip.h: ArahTierAudit) ------------------------------------------------
+// The audit buffer: the result block, a few private words, the per-sample / per-ray verdicts, and a WORKSPACE of its own -- the
+// production kernels it runs write per-sample scratch (canonical points, T, residuals, lists, counters), and the render's
+// workspace is only read.
+struct AuditBuf {
+    ArahTierAudit* res;
+    int* aux;            // [AX_COUNT]
+    uint8_t* tag;        // [Q]  AT_* of every sample
+    uint8_t* untraced;   // [N]  k_tier_rays of the render, recomputed
+    uint8_t* skip;       // [N]  the audit's trace: every ray but the examined class-C ones
+    uint8_t* ray_tag;    // [N]
+    Workspace w;
+    size_t bytes;
+};
+static AuditBuf carve_audit(void* base, int n_rays, int n_steps) {
+    AuditBuf a;
+    Carver c{reinterpret_cast<char*>(base), 0};
+    const size_t N = (size_t)(n_rays > 0 ? n_rays : 1), Q = N * (size_t)(n_steps > 0 ? n_steps : 1);
+    a.res = c.take<ArahTierAudit>(1);
+    a.aux = c.take<int>(AX_COUNT);
+    a.tag = c.take<uint8_t>(Q);
+    a.untraced = c.take<uint8_t>(N);
+    a.skip = c.take<uint8_t>(N);
+    a.ray_tag = c.take<uint8_t>(N);
+    const size_t off = align_up(c.off, 256);
+    a.w = carve(base ? reinterpret_cast<char*>(base) + off : nullptr, n_rays, n_steps);
+    a.bytes = off + a.w.bytes;
+    return a;
+}
+
+extern "C" {
+size_t arah_tier_audit_bytes(int32_t n_rays, int32_t n_steps) { return carve_audit(nullptr, n_rays, n_steps).bytes; }
+
+int arah_tier_audit(const ArahFrame* f, const ArahSampling* cfg, const float* cam_loc, int32_t rays_per_cam, const float* dirs,
+                    const float* near_far, int32_t n, int32_t rate_log2, uint32_t seed, void* audit_buf, size_t audit_bytes,
+                    void* workspace, size_t wbytes, void* stream) {
+    if (!f || !cfg || n < 0 || !workspace || !audit_buf) return ARAH_E_BADARG;
+    int rc = check_sampling(cfg);
+    if (rc) return rc;
+    if (!cfg->occupancy || cfg->full_shading || rate_log2 < 0 || rate_log2 > 31) return ARAH_E_BADARG;   // a TIERED render only
+    if (n > 0 && (!cam_loc || !dirs || !near_far)) return ARAH_E_BADARG;
+    const int S = cfg->n_steps;
+    Workspace w = carve(workspace, n, S);
+    if (wbytes < w.bytes) return ARAH_E_WORKSPACE;
+    AuditBuf ab = carve_audit(audit_buf, n, S);
+    if (audit_bytes < ab.bytes) return ARAH_E_WORKSPACE;
+    if (int arc = setup_attributes()) return arc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    Workspace& a = ab.w;
+    hipMemsetAsync(a.ctr, 0, sizeof(Counters), s);
+    hipLaunchKernelGGL(k_audit_begin, dim3(1), dim3(256), 0, s, ab.res, ab.aux, a.tcounts, (int)rate_log2, seed);
+    if (n == 0) {
+        hipLaunchKernelGGL(k_audit_finish, dim3(1), dim3(64), 0, s, ab.res, (const int*)ab.aux);
+        return check_launch();
+    }
+    const FrameDev fd = to_dev(*f);
+    const RaySet rs = make_rays(cam_loc, dirs, rays_per_cam);
+    const long long Q = (long long)n * S;
+    int* tc = a.tcounts;   // [0..2] loop C's list {entries, queue head, -}, [3] the density list, [4] its sigma > 0 part, [5] = 0
+    // classes A and B: pick and compact
+    hipMemsetAsync(ab.tag, 0, (size_t)Q, s);
+    hipLaunchKernelGGL(k_audit_witness, dim3(grid_for(Q, 256)), dim3(256), 0, s, (const int*)w.listA, (const int*)w.tcounts, ab.tag);
+    hipLaunchKernelGGL(k_audit_pick, dim3(grid_for(Q, 256)), dim3(256), 0, s, Q, (const uint8_t*)w.q_smask, (const uint8_t*)w.o_mask,
+                       (const float*)w.o_pts, ab.tag, a.o_pts, a.listA, &tc[0], a.listC, &tc[3], ab.res, (int)rate_log2, seed);
+    // class B: what tier_phase runs -- nearest vertex + inverse LBS, loop C, normalisation + convergence; the converged ones join
+    // the density list behind class A
+    launch_nearest<SRC_SAMPLES>(s, fd, Q, (const float*)nullptr, rs, (const float*)w.o_z, S, (const int*)a.listA, (const int*)&tc[0],
+                                0, (int*)nullptr, a.o_pts, a.o_T, 1, &a.ctr->n_knn);
+    rc = run_broyden3(fd, a, nullptr, CanonOut{a.o_pts, a.o_T, a.q_err}, Q, s, cfg->canon_kernel, nullptr, a.listA, &tc[0]);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_tier_finalize, dim3(grid_for(Q, 256)), dim3(256), 0, s, fd, (const int*)a.listA, (const int*)&tc[0],
+                       (const int*)&tc[5], (const float*)a.q_err, a.o_pts, a.o_mask, a.shaded, a.listC, &tc[3]);
+    // density (the lazy-shading pre-pass's kernel) and the SDF value (the certificate's margin) of the listed samples
+    launch_density(fd, a, a.o_pts, Q, (const int*)a.listC, (const int*)&tc[3], a.listB, &tc[4], s);
+    LAUNCH_ENGINE(fd.split, (k_sdf_eval<false, true>), (k_sdf_eval<false, false>), dim3(grid_for(Q, kTile)), dim3(kThreads), kLdsSdfFwd,
+                  s, fd, (const float*)a.o_pts, (const int*)a.listC, (const int*)&tc[3], 0, a.o_z, (float*)nullptr, (float*)nullptr,
+                  (f32x4*)nullptr, &a.ctr->n_sdf_fwd, (unsigned long long*)nullptr, 0);
+    hipLaunchKernelGGL(k_audit_check, dim3(grid_for(Q, 256)), dim3(256), 0, s, fd, (const int*)a.listC, (const int*)&tc[3],
+                       (const f32x4*)a.shaded, (const float*)a.o_z, ab.tag, ab.res, ab.aux);
+    // class C: the render's untraced rays (k_tier_rays is a pure function of the bitmap and the rays), the examined ones traced
+    OccBuf o = carve_occ(const_cast<void*>(cfg->occupancy));
+    const int gb = (n + 255) / 256;
+    hipLaunchKernelGGL(k_tier_rays, dim3(gb), dim3(256), 0, s, n, rs, near_far, (const OccInfo*)o.info, (const uint8_t*)o.dist,
+                       ab.untraced, &a.ctr->tier);
+    hipLaunchKernelGGL(k_audit_rays_pick, dim3(gb), dim3(256), 0, s, n, (const uint8_t*)ab.untraced, ab.skip, ab.ray_tag, ab.res,
+                       (int)rate_log2, seed);
+    rc = trace_impl(f, a, cam_loc, rays_per_cam, dirs, near_far, n, 0, a.o_xnorm, a.o_Tray, a.o_conv, a.o_start, a.o_end, s, ab.skip);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_audit_rays_check, dim3(gb), dim3(256), 0, s, n, (const uint8_t*)a.o_conv, ab.ray_tag, ab.res, ab.aux);
+    hipLaunchKernelGGL(k_audit_finish, dim3(1), dim3(64), 0, s, ab.res, (const int*)ab.aux);
+    return check_launch();
+}
+
+int arah_tier_audit_debug(const void* audit_buf, size_t audit_bytes, int32_t n_rays, int32_t n_steps, uint8_t* sample_tag,
+                          uint8_t* ray_tag, void* stream) {
+    if (!audit_buf || n_rays <= 0 || n_steps <= 0) return ARAH_E_BADARG;
+    AuditBuf ab = carve_audit(const_cast<void*>(audit_buf), n_rays, n_steps);
+    if (audit_bytes < ab.bytes) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    bool ok = true;
+    if (sample_tag) ok = ok && hipMemcpyAsync(sample_tag, ab.tag, (size_t)n_rays * n_steps, hipMemcpyDeviceToDevice, s) == hipSuccess;
+    if (ray_tag) ok = ok && hipMemcpyAsync(ray_tag, ab.ray_tag, (size_t)n_rays, hipMemcpyDeviceToDevice, s) == hipSuccess;
+    return ok ? ARAH_OK : ARAH_E_LAUNCH;
+}
 }  // extern "C"

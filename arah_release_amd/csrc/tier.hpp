@@ -796,3 +796,199 @@ __global__ __launch_bounds__(1024) void k_band_fill(int N, const float* __restri
     __syncthreads();
     if (band) list[block_base + wave_cnt[wave] + __popcll(mk & ((1ull << lane) - 1ull))] = (int)id;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The certificate's audit (arah_tier_audit): a deterministic sample of what a tiered arah_render skipped, through the same kernels
+// ---------------------------------------------------------------------------------------------------------------------
+// Three classes (include/arah_hip.h, ArahTierAudit): A the CERTIFIED samples (phase 1's list head, w.listA[0 .. TC_NWIT), and every
+// phase-2 sample) that converged -- their density is evaluated; B the samples never evaluated (state TS_PENDING: the remaining
+// samples of rays that were not promoted) -- nearest vertex, loop C, normalisation and density like tier_phase; C the rays
+// k_tier_rays kept out of loops A+B -- traced again.  Selection: audit_pick(x, seed, k) with x = ray * S + s (A, B) or the ray
+// index (C); the hash is restated in the header.
+enum { AT_A = 1, AT_B = 2, AT_CLASS = 3, AT_CONV = 4, AT_VIOL = 8, AT_WITNESS = 16 /* between k_audit_witness and k_audit_pick */ };
+static_assert(sizeof(ArahTierAudit) == 176, "ArahTierAudit: the header's layout");
+enum { AX_MIN_KEY = 0, AX_FIRST, AX_COUNT = 8 };   // private words of the audit buffer
+
+__device__ __forceinline__ unsigned audit_hash(unsigned x, unsigned seed) {
+    unsigned h = x * 0x9E3779B1u + seed;
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+    return h;
+}
+__device__ __forceinline__ bool audit_pick(unsigned x, unsigned seed, int k) { return (audit_hash(x, seed) & ((1u << k) - 1u)) == 0u; }
+// floats as ints that order like them (a signed compare of the key is a float compare of the value)
+__device__ __forceinline__ int float_key(float f) {
+    const int b = __float_as_int(f);
+    return b >= 0 ? b : b ^ 0x7fffffff;
+}
+__device__ __forceinline__ float key_float(int k) { return __int_as_float(k >= 0 ? k : k ^ 0x7fffffff); }
+
+__global__ void k_audit_begin(ArahTierAudit* res, int* aux, int* counts, int rate_log2, unsigned seed) {
+    if (blockIdx.x != 0) return;
+    unsigned* r = reinterpret_cast<unsigned*>(res);
+    for (int i = threadIdx.x; i < (int)(sizeof(ArahTierAudit) / 4); i += blockDim.x) r[i] = 0u;
+    for (int i = threadIdx.x; i < TC_COUNT; i += blockDim.x) counts[i] = 0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 0; i < AX_COUNT; ++i) aux[i] = 0;
+        aux[AX_MIN_KEY] = 0x7fffffff;
+        res->rate_log2 = rate_log2;
+        res->seed = seed;
+    }
+}
+
+__device__ __forceinline__ unsigned long long* u64p(uint64_t* p) { return reinterpret_cast<unsigned long long*>(p); }
+
+__device__ __forceinline__ void audit_violation(ArahTierAudit* res, int* aux, long long index, int cls) {
+    const int slot = atomicAdd(&aux[AX_FIRST], 1);
+    if (slot < 8) {
+        res->first_index[slot] = (int64_t)index;
+        res->first_class[slot] = cls;
+    }
+}
+
+// the witnesses of phase 1 are the head of the render's phase-1 list
+__global__ void k_audit_witness(const int* __restrict__ list, const int* __restrict__ tcounts, uint8_t* __restrict__ tag) {
+    const int n = tcounts[TC_NWIT];
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) tag[list[i]] = AT_WITNESS;
+}
+
+// One thread per sample: class, selection, compaction.  One ballot per 64 samples and list; one atomic per wave and list.
+// A -> dens_list (its canonical point copied into the audit's pts), B -> canon_list.
+__global__ void k_audit_pick(long long Q, const uint8_t* __restrict__ state, const uint8_t* __restrict__ mask,
+                             const float* __restrict__ pts_in, uint8_t* __restrict__ tag, float* __restrict__ pts_out,
+                             int* __restrict__ canon_list, int* canon_count, int* __restrict__ dens_list, int* dens_count,
+                             ArahTierAudit* res, int rate_log2, unsigned seed) {
+    const int lane = threadIdx.x & 63;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    unsigned long long na = 0, nb = 0;
+    for (long long q0 = (long long)blockIdx.x * blockDim.x; q0 < Q; q0 += stride) {
+        const long long q = q0 + threadIdx.x;
+        bool a = false, b = false;
+        if (q < Q) {
+            const int st = state[q];
+            const bool sel = audit_pick((unsigned)q, seed, rate_log2);
+            a = sel && (st == TS_PHASE2 || tag[q] == AT_WITNESS) && mask[q] != 0;
+            b = sel && st == TS_PENDING;
+            tag[q] = a ? AT_A : (b ? AT_B : 0);
+            if (a) {
+                pts_out[q * 3] = pts_in[q * 3];
+                pts_out[q * 3 + 1] = pts_in[q * 3 + 1];
+                pts_out[q * 3 + 2] = pts_in[q * 3 + 2];
+            }
+        }
+        const unsigned long long ma = __ballot(a), mb = __ballot(b);
+        int ba = 0, bb = 0;
+        if (lane == 0) {
+            if (ma) ba = atomicAdd(dens_count, __popcll(ma));
+            if (mb) bb = atomicAdd(canon_count, __popcll(mb));
+        }
+        ba = __shfl(ba, 0);
+        bb = __shfl(bb, 0);
+        const unsigned long long below = (1ull << lane) - 1ull;
+        if (a) dens_list[ba + __popcll(ma & below)] = (int)q;
+        if (b) canon_list[bb + __popcll(mb & below)] = (int)q;
+        na += (unsigned long long)__popcll(ma);
+        nb += (unsigned long long)__popcll(mb);
+    }
+    if (lane == 0) {
+        if (na) atomicAdd(u64p(&res->a_examined), na);
+        if (nb) atomicAdd(u64p(&res->b_examined), nb);
+    }
+}
+
+// Check and reduce over the density list (class A and the converged class-B samples): a density other than +0 is a violation;
+// the smallest metric sdf / beta seen is the certificate's margin (it holds while that stays above 17.33).
+__global__ __launch_bounds__(256) void k_audit_check(FrameDev fr, const int* __restrict__ list, const int* count,
+                                                     const f32x4* __restrict__ shaded, const float* __restrict__ sdf_n,
+                                                     uint8_t* __restrict__ tag, ArahTierAudit* res, int* aux) {
+    const int n = *count;
+    const int lane = threadIdx.x & 63;
+    const BodyConst bc = load_bc(fr);
+    const float scale = sdf_scale(bc);
+    const float inv_beta = 1.0f / fminf(fmaxf(fabsf(load_beta(fr)), 1e-6f), 1e6f);
+    unsigned long long va = 0, vb = 0, cb = 0;
+    int key = 0x7fffffff;
+    for (int i0 = blockIdx.x * blockDim.x; i0 < n; i0 += gridDim.x * blockDim.x) {
+        const int i = i0 + threadIdx.x;
+        bool viol = false, isb = false;
+        if (i < n) {
+            const int q = list[i];
+            const int t = tag[q];
+            isb = (t & AT_CLASS) == AT_B;
+            viol = __float_as_uint(shaded[q][3]) != 0u;
+            const float r = sdf_n[q] * scale * inv_beta;
+            if (r == r) key = min(key, float_key(r));
+            tag[q] = (uint8_t)(t | AT_CONV | (viol ? AT_VIOL : 0));
+            if (viol) audit_violation(res, aux, q, isb ? 1 : 0);
+        }
+        va += (unsigned long long)__popcll(__ballot(viol && !isb));
+        vb += (unsigned long long)__popcll(__ballot(viol && isb));
+        cb += (unsigned long long)__popcll(__ballot(i < n && isb));
+    }
+    for (int o = 32; o > 0; o >>= 1) key = min(key, __shfl_xor(key, o));
+    if (lane == 0) {
+        if (va) atomicAdd(u64p(&res->a_violations), va);
+        if (vb) atomicAdd(u64p(&res->b_violations), vb);
+        if (cb) atomicAdd(u64p(&res->b_converged), cb);
+        if (key != 0x7fffffff) atomicMin(&aux[AX_MIN_KEY], key);
+    }
+}
+
+// class C: of the rays k_tier_rays keeps out of loops A+B (untraced[i] = 1), the selected ones are traced again (skip = 0)
+__global__ void k_audit_rays_pick(int n, const uint8_t* __restrict__ untraced, uint8_t* __restrict__ skip, uint8_t* __restrict__ ray_tag,
+                                  ArahTierAudit* res, int rate_log2, unsigned seed) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool c = false;
+    if (i < n) {
+        c = untraced[i] != 0 && audit_pick((unsigned)i, seed, rate_log2);
+        skip[i] = c ? 0 : 1;
+        ray_tag[i] = c ? 1 : 0;
+    }
+    const unsigned long long m = __ballot(c);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(u64p(&res->c_examined), (unsigned long long)__popcll(m));
+}
+
+// ... and a ray of them that converges is a violation
+__global__ void k_audit_rays_check(int n, const uint8_t* __restrict__ conv, uint8_t* __restrict__ ray_tag, ArahTierAudit* res, int* aux) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool v = false;
+    if (i < n && ray_tag[i]) {
+        v = conv[i] != 0;
+        if (v) {
+            ray_tag[i] = 3;
+            audit_violation(res, aux, i, 2);
+        }
+    }
+    const unsigned long long m = __ballot(v);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(u64p(&res->c_violations), (unsigned long long)__popcll(m));
+}
+
+__global__ void k_audit_finish(ArahTierAudit* res, const int* aux) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int key = aux[AX_MIN_KEY];
+    res->min_ratio = key == 0x7fffffff ? __int_as_float(0x7f800000) : key_float(key);
+    res->n_first = (unsigned long long)min(aux[AX_FIRST], 8);
+}
+
+// tests: unmark the voxels whose centres lie in the posed-space box [lo, hi] (one thread per bitmap word); the distance transform
+// is recomputed after it.  A damaged certificate on purpose -- nothing outside the buffer is touched.
+__global__ void k_occ_clear_box(const OccInfo* __restrict__ info, unsigned* __restrict__ bits, float lx, float ly, float lz, float hx,
+                                float hy, float hz) {
+    const int wi = blockIdx.x * blockDim.x + threadIdx.x;
+    const OccInfo oi = *info;
+    if (!oi.valid || wi >= (oi.n_vox + 31) / 32) return;
+    unsigned clear = 0u;
+    for (int k = 0; k < 32; ++k) {
+        const long long b = (long long)wi * 32 + k;
+        if (b >= oi.n_vox) break;
+        const int x = (int)(b % oi.dims[0]), y = (int)((b / oi.dims[0]) % oi.dims[1]), z = (int)(b / ((long long)oi.dims[0] * oi.dims[1]));
+        const float cx = oi.origin[0] + ((float)x + 0.5f) * oi.v, cy = oi.origin[1] + ((float)y + 0.5f) * oi.v,
+                    cz = oi.origin[2] + ((float)z + 0.5f) * oi.v;
+        if (cx >= lx && cx <= hx && cy >= ly && cy <= hy && cz >= lz && cz <= hz) clear |= 1u << k;
+    }
+    if (clear) bits[wi] &= ~clear;
+}

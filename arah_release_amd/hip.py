@@ -111,6 +111,17 @@ class ArahCounters(C.Structure):
 
 COUNTER_BYTES = C.sizeof(ArahCounters)
 
+
+class ArahTierAudit(C.Structure):
+    _fields_ = [("a_examined", C.c_uint64), ("a_violations", C.c_uint64), ("b_examined", C.c_uint64),
+                ("b_converged", C.c_uint64), ("b_violations", C.c_uint64), ("c_examined", C.c_uint64),
+                ("c_violations", C.c_uint64), ("n_first", C.c_uint64), ("first_index", C.c_int64 * 8),
+                ("first_class", C.c_int32 * 8), ("min_ratio", C.c_float), ("rate_log2", C.c_int32), ("seed", C.c_uint32),
+                ("reserved", C.c_int32)]
+
+
+AUDIT_BYTES = C.sizeof(ArahTierAudit)
+
 EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_prepare_body", "arah_workspace_bytes", "arah_counters_reset",
            "arah_counters_read", "arah_sdf_eval", "arah_sdf_grid", "arah_rasterize", "arah_skin_lbs", "arah_skin_jacobian", "arah_color_eval",
            "arah_nearest_inverse_lbs", "arah_broyden3_lbs", "arah_joint_root_find", "arah_trace", "arah_sample_canonicalize",
@@ -118,7 +129,8 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_shade_train_backward", "arah_composite_train_forward", "arah_composite_train_backward", "arah_gram_skinny_blocks", "arah_gram_skinny", "arah_colsum_blocks", "arah_colsum", "arah_inverse3x3", "arah_hsoftmax_train_forward", "arah_hsoftmax_train_backward", "arah_pose_tree_forward", "arah_pose_tree_backward", "arah_gemv_rows", "arah_mesh_query_scratch_bytes", "arah_mesh_query", "arah_dominant_kernel",
            "arah_skin_lbs_counted", "arah_marching_cubes_scratch_bytes", "arah_marching_cubes",
            "arah_occupancy_bytes", "arah_prepare_occupancy", "arah_occupancy_info", "arah_tier_debug", "arah_debug_samples",
-           "arah_sdf_grid_band_scratch_bytes", "arah_sdf_grid_band"]
+           "arah_sdf_grid_band_scratch_bytes", "arah_sdf_grid_band", "arah_tier_audit_bytes", "arah_tier_audit",
+           "arah_tier_audit_debug", "arah_occupancy_clear_box"]
 
 _lib = None
 
@@ -144,6 +156,8 @@ def load_library():
     lib.arah_occupancy_bytes.restype = C.c_size_t
     lib.arah_sdf_grid_band_scratch_bytes.restype = C.c_size_t
     lib.arah_colsum_blocks.argtypes = [C.c_int64]
+    lib.arah_tier_audit_bytes.restype = C.c_size_t
+    lib.arah_tier_audit_bytes.argtypes = [C.c_int32, C.c_int32]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the symbol is missing
     _lib = lib
@@ -249,6 +263,7 @@ class Workspace:
         self.device = device
         self.buf = None
         self.occ = None   # occupancy bitmap of the frame this scratch is rendering (tiered eval forward)
+        self.audit_buf = None   # scratch of arah_tier_audit (allocated by the first audit: about one more workspace)
 
     def occupancy(self, frame):
         """arah_prepare_occupancy for `frame` on the current stream, into this scratch's own buffer (a scratch serves one
@@ -274,6 +289,31 @@ class Workspace:
         return {"origin": f[:3], "voxel": f[3], "dims": i[:3], "n_vox": i[3], "valid": i[4], "n_cells": i[5], "n_fine": i[6],
                 "n_selected": i[7], "overflow": i[8], "band_m": struct.unpack("f", raw[56:60])[0],
                 "lip_pose": struct.unpack("f", raw[60:64])[0]}
+
+    def occupancy_clear_box(self, lo, hi):
+        """Tests only: unmark the voxels of this scratch's occupancy whose centres lie in the posed-space box [lo, hi] (metres) and
+        recompute its distance transform -- a certificate damaged on purpose (arah_occupancy_clear_box)."""
+        lo3, hi3 = (C.c_float * 3)(*[float(v) for v in lo]), (C.c_float * 3)(*[float(v) for v in hi])
+        with torch.cuda.device(self.device):
+            _check(load_library().arah_occupancy_clear_box(_ptr(self.occ), lo3, hi3, _stream(self.device)), "arah_occupancy_clear_box")
+
+    def audit_ensure(self, n_rays, n_steps):
+        need = load_library().arah_tier_audit_bytes(int(n_rays), int(n_steps))
+        if self.audit_buf is None or self.audit_buf.numel() < need:
+            self.audit_buf = None
+            with torch.cuda.device(self.device):
+                self.audit_buf = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self.audit_buf
+
+    def tier_audit_debug(self, n_rays, n_steps):
+        """(sample_tag [N*S], ray_tag [N]) uint8 verdicts of the last arah_tier_audit on this scratch (include/arah_hip.h)."""
+        st = torch.empty(n_rays * n_steps, dtype=torch.uint8, device=self.device)
+        rt = torch.empty(n_rays, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _check(load_library().arah_tier_audit_debug(_ptr(self.audit_buf), C.c_size_t(self.audit_buf.numel()), C.c_int32(n_rays),
+                                                        C.c_int32(n_steps), _ptr(st), _ptr(rt), _stream(self.device)),
+                   "arah_tier_audit_debug")
+        return st, rt
 
     def tier_debug(self, n_rays, n_steps):
         """(ray_tier, ray_sigma_pos) uint8 tensors of the last arah_render on this scratch."""
@@ -1125,3 +1165,36 @@ def render(frame, ws, sampling, cam_loc, dirs, near_far, pose34, tiered=False):
                            _ptr(d), _ptr(nf), _ptr(d_pose), C.c_int32(n), _ptr(rgb), _ptr(pcam), _ptr(vol), _ptr(acc),
                            _ptr(dists), _ptr(conv), _ptr(buf), C.c_size_t(buf.numel()), _stream()), "arah_render")
     return rgb, pcam, vol, acc, dists, conv
+
+
+@_guarded
+def tier_audit(frame, ws, sampling, cam_loc, dirs, near_far, rate_log2=0, seed=0):
+    """Audit of the certificate behind the last TIERED render(frame, ws, sampling, ...) of these rays (arah_tier_audit): enqueued on
+    the current stream, no synchronisation.  Returns the result block, a device uint8 tensor of AUDIT_BYTES (a view into the
+    scratch's audit buffer: the next audit overwrites it) -- audit_result() reads it."""
+    lib = load_library()
+    cam, d, nf = _f32(cam_loc), _f32(dirs), _f32(near_far)
+    n, S = d.shape[0], sampling.n_steps
+    if ws.buf is None or ws.occ is None:
+        raise RuntimeError("tier_audit: no tiered render on this scratch")
+    abuf = ws.audit_ensure(n, S)
+    cfg = ArahSampling.from_buffer_copy(sampling.handle)
+    cfg.occupancy = ws.occ.data_ptr()
+    _check(lib.arah_tier_audit(C.byref(frame.handle), C.byref(cfg), _ptr(cam), C.c_int32(n // cam.shape[0]), _ptr(d), _ptr(nf),
+                               C.c_int32(n), C.c_int32(int(rate_log2)), C.c_uint32(int(seed) & 0xffffffff), _ptr(abuf),
+                               C.c_size_t(abuf.numel()), _ptr(ws.buf), C.c_size_t(ws.buf.numel()), _stream()), "arah_tier_audit")
+    return abuf[:AUDIT_BYTES]
+
+
+def audit_result(block):
+    """ArahTierAudit as a dict, from the result block (a device or host uint8 tensor of AUDIT_BYTES; a device one synchronises)."""
+    raw = bytes(block.cpu().numpy().tobytes()) if isinstance(block, torch.Tensor) else bytes(block)
+    r = ArahTierAudit.from_buffer_copy(raw[:AUDIT_BYTES])
+    k = int(r.n_first)
+    out = {name: int(getattr(r, name)) for name, _ in ArahTierAudit._fields_
+           if name not in ("first_index", "first_class", "min_ratio", "reserved")}
+    out["min_ratio"] = float(r.min_ratio)
+    out["first"] = [("ABC"[int(r.first_class[i])], int(r.first_index[i])) for i in range(k)]
+    out["violations"] = out["a_violations"] + out["b_violations"] + out["c_violations"]
+    return out
+

@@ -366,7 +366,11 @@ class BodyRayTracing(nn.Module):
 
 
 class IDHRNetwork(nn.Module):
-    """Implicit differentiable human renderer (reference implicit_differentiable_renderer.py:15-259)."""
+    """Implicit differentiable human renderer (reference implicit_differentiable_renderer.py:15-259).
+
+    tier_audit ("off" / "sample" / "strict", env ARAH_TIER_AUDIT) audits the tiered forward's sigma = +0 certificate at run time
+    (arah_tier_audit; see __init__).  Both audit modes DETECT violations and neither proves their absence: below rate 1 a violation
+    is caught with a probability set by the rate."""
 
     def __init__(self, deviation_network, rendering_network, skinning_model, ray_tracer, cano_view_dirs=True,
                  train_skinning_net=False, render_last_pt=False, low_vram=False):
@@ -412,6 +416,27 @@ class IDHRNetwork(nn.Module):
         self.tier_share = None
         self._tier_off = False
         self._tier_since_probe = 0
+        # Audit of the certificate (arah_tier_audit, csrc/tier.hpp): the tiers' sigma = +0 certificate rests on Lipschitz
+        # assumptions about the subject's SDF and skinning that only tests check; the audit re-runs a hashed sample of what a tiered
+        # frame skipped through the exact kernels.  ARAH_TIER_AUDIT / .tier_audit:
+        #   "off" (default): no audit, nothing launched;
+        #   "sample": every `tier_audit_every`-th tiered frame is audited at rate 1 / 2^tier_audit_rate_log2 (the seed advances per
+        #     audit); its result is copied to pinned memory behind the frame (no stream drain) and looked at when a later frame
+        #     starts.  A violation warns, adds to `tier_violations`, keeps the result in `tier_audit_last` and sets `tiering` to
+        #     False: every later frame renders untiered until the caller sets `tiering` again.  The audited frame itself and the
+        #     ones already on their way are returned as rendered;
+        #   "strict": every tiered frame is audited and the result read behind it (one synchronisation per frame); a frame with a
+        #     violation is rendered AGAIN untiered before it is returned (and `tiering` goes off as above).
+        # Both DETECT violations; neither proves their absence: at a rate below 1 a violation is caught with a probability set by
+        # the rate and by how many samples break the certificate.
+        self.tier_audit = os.environ.get("ARAH_TIER_AUDIT", "off")
+        self.tier_audit_every = 16
+        self.tier_audit_rate_log2 = 4
+        self.tier_violations = 0
+        self.tier_audit_last = None
+        self._audit = {}          # per scratch: the pinned result block of its last sampled audit and the event behind the copy
+        self._tier_frames = 0     # tiered frames rendered while an audit mode was on
+        self._audits = 0          # audits launched: the seed of the next one
         self.precision = None    # GEMM engine frames are prepared for: None = the process default (ARAH_PRECISION, split),
                                  # hip.PRECISION_FP32 / PRECISION_SPLIT_F16 = this renderer's own choice (bench.py's passes)
         self._precision = None   # becomes hip.PRECISION_FP32 once the range guard has fired: overrides `precision`
@@ -580,6 +605,57 @@ class IDHRNetwork(nn.Module):
         g["host"].copy_(ws.buf[0:hip.COUNTER_BYTES].view(torch.int64), non_blocking=True)
         g["event"].record()
 
+    def _tier_audit_mode(self):
+        mode = self.tier_audit
+        if mode not in ("off", "sample", "strict"):
+            raise ValueError("tier_audit must be 'off', 'sample' or 'strict', not %r" % (mode,))
+        return mode
+
+    def _tier_audit_violated(self, res, where):
+        import warnings
+        self.tier_violations += res["violations"]
+        self.tier_audit_last = res
+        self.tiering = False
+        warnings.warn("tiered forward: the audit of the sigma = +0 certificate found %d violation(s) (classes A/B/C: %d/%d/%d, "
+                      "min sdf / beta %.3g); %s, and the following frames render untiered until `tiering` is set again"
+                      % (res["violations"], res["a_violations"], res["b_violations"], res["c_violations"], res["min_ratio"], where))
+
+    def _tier_audit_collect(self):
+        """"sample": results of earlier audits whose copy has landed (event query, no drain)."""
+        for key, rec in list(self._audit.items()):
+            if rec["pending"] and rec["event"].query():
+                rec["pending"] = False
+                res = hip.audit_result(rec["host"])
+                self.tier_audit_last = res
+                if res["violations"] > 0:
+                    self._tier_audit_violated(res, "a frame already returned may hold wrong pixels")
+
+    def _tier_audit_launch(self, frame, ws, samp, cam, d, nf, dev):
+        """After a tiered frame: the audit, and for "sample" the copy of its result behind it.  -> the result dict ("strict") or None."""
+        self._tier_frames += 1
+        strict = self.tier_audit == "strict"
+        if not strict and (self._tier_frames - 1) % max(1, int(self.tier_audit_every)) != 0:
+            return None
+        key = (dev, id(ws))
+        rec = self._audit.get(key)
+        if not strict and rec is not None and rec["pending"]:
+            return None   # the previous audit of this scratch has not been read yet: its pinned block stays untouched
+        block = hip.tier_audit(frame, ws, samp, cam, d, nf, rate_log2=self.tier_audit_rate_log2, seed=self._audits)
+        self._audits += 1
+        if strict:
+            res = hip.audit_result(block)   # synchronises the stream
+            self.tier_audit_last = res
+            return res
+        if rec is None:
+            if len(self._audit) >= 8:
+                self._audit.pop(next(iter(self._audit)))
+            rec = self._audit[key] = {"host": torch.empty(hip.AUDIT_BYTES, dtype=torch.uint8).pin_memory(),
+                                      "event": torch.cuda.Event(), "pending": False}
+        rec["host"].copy_(block, non_blocking=True)
+        rec["event"].record()
+        rec["pending"] = True
+        return None
+
     def forward(self, input):
         if self.training:
             return self.forward_train(input)
@@ -593,6 +669,9 @@ class IDHRNetwork(nn.Module):
         dev = ray_dirs.device
         ws = self.ray_tracer.workspace(dev)
         guard = self._split_guard(ws, dev) if dev.type == "cuda" else None
+        audit = self._tier_audit_mode() if dev.type == "cuda" else "off"
+        if audit == "sample":
+            self._tier_audit_collect()
         frame = build_frame(input["sdf_network"], self.skinning_model, self.rendering_network,
                             self.deviation_network, input["pose_cond"], input["smpl_verts"],
                             input["skinning_weights"], input["bone_transforms"], input["trans"],
@@ -619,6 +698,14 @@ class IDHRNetwork(nn.Module):
         rgb, pcam, vol, acc, dists, conv = hip.render(frame, ws, samp, cam_loc.reshape(B, 3),
                                                       ray_dirs.reshape(B * N, 3), nf.reshape(B * N, 2), pose34,
                                                       tiered=tiered)
+        if tiered and audit != "off":
+            res = self._tier_audit_launch(frame, ws, samp, cam_loc.reshape(B, 3), ray_dirs.reshape(B * N, 3), nf.reshape(B * N, 2), dev)
+            if res is not None and res["violations"] > 0:   # "strict": this frame again, untiered
+                self._tier_audit_violated(res, "this frame is rendered again untiered")
+                tiered = False
+                rgb, pcam, vol, acc, dists, conv = hip.render(frame, ws, samp, cam_loc.reshape(B, 3),
+                                                              ray_dirs.reshape(B * N, 3), nf.reshape(B * N, 2), pose34,
+                                                              tiered=False)
         if guard is not None and self.guard_mode == "strict" and frame.precision != hip.PRECISION_FP32:
             now = int(ws.buf[64:72].view(torch.int64).item())   # ArahCounters.n_split_nonfinite; synchronises the stream
             grew = now - guard["seen"] if now >= guard["seen"] else now

@@ -477,6 +477,45 @@ int arah_occupancy_info(const void* occ_buf, int32_t* h_out16, void* stream);
 int arah_tier_debug(void* workspace, size_t workspace_bytes, int32_t n_rays, int32_t n_steps, uint8_t* ray_tier,
                     uint8_t* ray_sigma_pos, void* stream);
 
+/* Audit of the certificate (csrc/tier.hpp).  The tiers rest on assumptions the kernels cannot prove (the SDF's and the forward
+ * skinning's Lipschitz constants over a lattice cell, the fat body inside [-1.5, 1.5]^3); arah_tier_audit re-examines, with the
+ * production kernels, a deterministic sample of what the LAST tiered arah_render on `workspace` skipped:
+ *   A  certified samples that converged (phase 1's witnesses, every phase-2 sample): density evaluated; violation: not +0;
+ *   B  samples never evaluated (rays not promoted): nearest vertex, loop C, density; violation: converged with density not +0;
+ *   C  rays kept out of loops A+B (their segment misses the bitmap): traced again; violation: the ray converges.
+ * Ordering rule: enqueue it on the render's stream right behind that arah_render, before anything else uses the workspace or
+ * the occupancy buffer, with the same h_cfg (occupancy included) and ray arguments.  It reads the workspace and never writes
+ * it (outputs, debug arrays and ArahCounters stay as the render left them); all of its own state lives in audit_buf
+ * (arah_tier_audit_bytes(n_rays, n_steps) bytes, 256-byte aligned: about one more workspace), the result at its head.
+ * Selection: sample q = ray * n_steps + s (classes A, B) and ray index (class C) are examined when
+ *   (h(x, seed) & ((1 << rate_log2) - 1)) == 0,   h(x, seed) = fmix32(x * 0x9E3779B1 + seed)   (uint32 arithmetic),
+ *   fmix32(h): h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16  (MurmurHash3's finaliser);
+ * rate_log2 = 0 examines everything skipped.  The audit detects violations; with rate_log2 > 0 it cannot prove their absence. */
+typedef struct ArahTierAudit {
+    uint64_t a_examined, a_violations;
+    uint64_t b_examined, b_converged, b_violations;
+    uint64_t c_examined, c_violations;
+    uint64_t n_first;             /* entries of first_index / first_class written: min(8, all violations), in no particular order */
+    int64_t first_index[8];       /* sample index ray * n_steps + s (classes A, B) or ray index (class C) */
+    int32_t first_class[8];       /* 0 = A, 1 = B, 2 = C */
+    float min_ratio;              /* smallest metric sdf / beta over the examined converged A / B samples (+inf: none); the
+                                     certificate holds with room while this stays above 17.33 */
+    int32_t rate_log2;
+    uint32_t seed;
+    int32_t reserved;
+} ArahTierAudit;
+size_t arah_tier_audit_bytes(int32_t n_rays, int32_t n_steps);
+int arah_tier_audit(const ArahFrame* h_frame, const ArahSampling* h_cfg, const float* cam_loc, int32_t rays_per_cam,
+                    const float* dirs, const float* near_far, int32_t n_rays, int32_t rate_log2, uint32_t seed, void* audit_buf,
+                    size_t audit_bytes, void* workspace, size_t workspace_bytes, void* stream);
+/* tests: per sample [N,S] the audit's verdict (1 class A, 2 class B, | 4 converged, | 8 violation; 0 not examined) and per
+ * ray [N] (1 class C examined, 3 examined and converged); device pointers, either may be NULL */
+int arah_tier_audit_debug(const void* audit_buf, size_t audit_bytes, int32_t n_rays, int32_t n_steps, uint8_t* sample_tag,
+                          uint8_t* ray_tag, void* stream);
+/* tests only: damage a certificate on purpose -- unmark the voxels of an occupancy buffer whose centres lie in the posed-space
+ * box [h_lo, h_hi] (metres, 3 floats each, host) and recompute its distance transform */
+int arah_occupancy_clear_box(void* occ_buf, const float* h_lo, const float* h_hi, void* stream);
+
 /* tests: the per-sample arrays of the workspace's last arah_render, copied device to device (any pointer may be NULL):
  * z [N,S], pts [N,S,3] normalised canonical, T [N,S,16], mask [N,S], shaded [N,S,4] = {rgb, density}, state [N,S] */
 int arah_debug_samples(void* workspace, size_t workspace_bytes, int32_t n_rays, int32_t n_steps, float* z, float* pts,
