@@ -2391,7 +2391,9 @@ __global__ __launch_bounds__(kThreads, 2) void k_sdf_lattice(FrameDev fr, int gr
 // (IDR:291-368), then per-ray compositing (IDR:370-394)
 // ------------------------------------------------------------------------------------------
 // B3 (with SPLIT): the normal sweep and the colour MLP on the bf16 x 3 engine instead of the fp32 MFMA (mlp.hpp)
-template <bool IDR, bool SPLIT, bool B3 = false>
+// MAPS (arah_render_maps): sdfn_out receives the posed unit normal {normalize(T[:3,:3] grad), 0} of every shaded sample instead
+// (the same pointer, so that the instances without maps keep their kernel arguments and their code)
+template <bool IDR, bool SPLIT, bool B3 = false, bool MAPS = false>
 __global__ __launch_bounds__(kThreads) void k_shade(FrameDev fr, int S, int cano_view_dirs, const float* dirs,
                                                      const float* pts, const float* T, const int* list,
                                                      const int* count, int n_direct, f32x4* shaded,
@@ -2455,6 +2457,13 @@ __global__ __launch_bounds__(kThreads) void k_shade(FrameDev fr, int S, int cano
             float vx = 0.f, vy = 0.f, vz = 0.f;
             if (id >= 0) {
                 const float* Tq = T + (size_t)id * 16;
+                if constexpr (MAPS) {   // the posed normal of the maps, whatever frame the colour MLP takes its normal in
+                    const float ax = Tq[0] * nx + Tq[1] * ny + Tq[2] * nz;
+                    const float ay = Tq[4] * nx + Tq[5] * ny + Tq[6] * nz;
+                    const float az = Tq[8] * nx + Tq[9] * ny + Tq[10] * nz;
+                    const float len = fmaxf(sqrtf(ax * ax + ay * ay + az * az), 1e-12f);
+                    sdfn_out[id] = f32x4{ax / len, ay / len, az / len, 0.f};
+                }
                 const int ray = id / S;
                 const float dx = -dirs[(size_t)ray * 3], dy = -dirs[(size_t)ray * 3 + 1], dz = -dirs[(size_t)ray * 3 + 2];
                 if (cano_view_dirs) {                                   // IDR:295-298
@@ -2525,7 +2534,7 @@ __global__ __launch_bounds__(kThreads) void k_shade(FrameDev fr, int S, int cano
         if (tid < kTile && ids[tid] >= 0) {
             const float dens = volsdf_density(outv[tid * 4] * scale, inv_beta);   // IDR:359, 368
             shaded[ids[tid]] = f32x4{rgbv[tid * 4], rgbv[tid * 4 + 1], rgbv[tid * 4 + 2], dens};
-            if (sdfn_out) sdfn_out[ids[tid]] = reinterpret_cast<const f32x4*>(outv)[tid];
+            if (!MAPS && sdfn_out) sdfn_out[ids[tid]] = reinterpret_cast<const f32x4*>(outv)[tid];
         }
         __syncthreads();
         clk.mark(6);
@@ -2661,6 +2670,80 @@ __global__ void k_composite(int n, int S, int render_last_pt, const float* z, co
     rgb[(size_t)i * 3 + 2] = any ? b : 0.f;
     if (acc) acc[i] = any ? fminf(fmaxf(wsum, 0.f), 1.f) : 0.f;
     vol_mask[i] = any ? 1 : 0;
+}
+
+// k_composite plus the maps: the same weights, in the same order, also accumulate the posed unit normals (nrm, written by
+// k_shade<..., MAPS> for the shaded samples) and the depths -- normal [N,3] = sum w n (not renormalised), depth [N] = sum w z.
+// A sample's normal is taken only when its density is > 0: every such sample was shaded, and the others (density +0, weight
+// exactly 0) may hold anything in nrm.  rgb / acc / vol_mask are k_composite's bit for bit.  A body of its own: k_composite's
+// code stays as it is.
+template <bool CHUNK>
+__global__ void k_composite_maps(int n, int S, int render_last_pt, const float* z, const uint8_t* mask,
+                                 const f32x4* shaded, float* rgb, float* acc, uint8_t* vol_mask, const f32x4* nrm,
+                                 float* normal, float* depth) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float inv_steps = 1.0f / (float)S;
+    float r = 0.f, g = 0.f, b = 0.f, wsum = 0.f, trans = 1.0f;
+    float nx = 0.f, ny = 0.f, nz = 0.f, dz = 0.f;
+    int prev = -1;
+    f32x4 ps = {0.f, 0.f, 0.f, 0.f}, pn = {0.f, 0.f, 0.f, 0.f};
+    float pz = 0.f;
+    bool any = false;
+    auto step = [&](int s, float zs, const f32x4 sh, const f32x4 sn) {
+        if (prev >= 0) {
+            float delta;
+            if (s < S) delta = zs - pz;
+            else delta = render_last_pt ? 1e10f : inv_steps;
+            const float alpha = 1.0f - expf(-ps[3] * delta);
+            const float w = alpha * trans;
+            r += ps[0] * w;
+            g += ps[1] * w;
+            b += ps[2] * w;
+            wsum += w;
+            trans *= (1.0f - alpha + 1e-7f);
+            nx += pn[0] * w;
+            ny += pn[1] * w;
+            nz += pn[2] * w;
+            dz += pz * w;
+        }
+        if (s < S) {
+            prev = s;
+            ps = sh;
+            pn = sh[3] > 0.f ? sn : f32x4{0.f, 0.f, 0.f, 0.f};
+            pz = zs;
+            any = true;
+        }
+    };
+    const size_t base = (size_t)i * S;
+    if (CHUNK) {
+        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+        for (int s0 = 0; s0 < S; s0 += 8) {
+            const u32x2 m8 = *reinterpret_cast<const u32x2*>(mask + base + s0);
+            const f32x4 z0 = *reinterpret_cast<const f32x4*>(z + base + s0), z1 = *reinterpret_cast<const f32x4*>(z + base + s0 + 4);
+            f32x4 sh[8], sn[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) sh[u] = shaded[base + s0 + u];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) sn[u] = nrm[base + s0 + u];
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (((u < 4 ? m8[0] : m8[1]) >> (8 * (u & 3))) & 0xffu) step(s0 + u, u < 4 ? z0[u & 3] : z1[u & 3], sh[u], sn[u]);
+        }
+    } else {
+        for (int s = 0; s < S; ++s)
+            if (mask[base + s] != 0) step(s, z[base + s], shaded[base + s], nrm[base + s]);
+    }
+    step(S, 0.f, ps, pn);
+    rgb[(size_t)i * 3] = any ? r : 0.f;
+    rgb[(size_t)i * 3 + 1] = any ? g : 0.f;
+    rgb[(size_t)i * 3 + 2] = any ? b : 0.f;
+    if (acc) acc[i] = any ? fminf(fmaxf(wsum, 0.f), 1.f) : 0.f;
+    vol_mask[i] = any ? 1 : 0;
+    normal[(size_t)i * 3] = any ? nx : 0.f;
+    normal[(size_t)i * 3 + 1] = any ? ny : 0.f;
+    normal[(size_t)i * 3 + 2] = any ? nz : 0.f;
+    depth[i] = any ? dz : 0.f;
 }
 
 // IDR:114-115, 142-143, 251: camera-space surface points, zeroed off-surface
@@ -2955,6 +3038,12 @@ int setup_attributes_once() {
     allow_lds(k_shade<true, true>, lds_shade<true>(), failed);
     allow_lds((k_shade<false, true, true>), lds_shade_b3<false>(), failed);
     allow_lds((k_shade<true, true, true>), lds_shade_b3<true>(), failed);
+    allow_lds((k_shade<false, false, false, true>), lds_shade<false>(), failed);
+    allow_lds((k_shade<false, true, false, true>), lds_shade<false>(), failed);
+    allow_lds((k_shade<true, false, false, true>), lds_shade<true>(), failed);
+    allow_lds((k_shade<true, true, false, true>), lds_shade<true>(), failed);
+    allow_lds((k_shade<false, true, true, true>), lds_shade_b3<false>(), failed);
+    allow_lds((k_shade<true, true, true, true>), lds_shade_b3<true>(), failed);
     allow_lds(k_color_eval<false>, lds_color<false>(), failed);
     allow_lds(k_color_eval<true>, lds_color<true>(), failed);
     allow_lds(k_shade_train<false, false, false>, lds_shade_train<false>(), failed);
@@ -4124,14 +4213,21 @@ static void launch_density(const FrameDev& fd, Workspace& w, const float* pts, l
                       w.shaded, next_list, next_count, &w.ctr->n_sdf_fwd, &w.ctr->n_density);
 }
 
+// the per-sample normal slab of arah_render_maps and the two maps it composites into
+struct MapsOut {
+    f32x4* nrm;      // [N*S] posed unit normal of every shaded sample (k_shade<..., MAPS>)
+    float* normal;   // [N,3]
+    float* depth;    // [N]
+};
+
 static int shade_tail(const ArahFrame* f, const ArahSampling* cfg, Workspace& w, const FrameDev& fd, const float* dirs,
                       const float* z, const float* pts, const float* T, const uint8_t* mask, int32_t n, const int* slist,
-                      const int* scount, float* rgb, float* acc, uint8_t* vol_mask, hipStream_t s);
+                      const int* scount, float* rgb, float* acc, uint8_t* vol_mask, const MapsOut* maps, hipStream_t s);
 
 // ---- loop D -----------------------------------------------------------------------------------
 static int shade_impl(const ArahFrame* f, const ArahSampling* cfg, Workspace& w, const float* dirs, const float* z,
                       const float* pts, const float* T, const uint8_t* mask, int32_t n, float* rgb, float* acc,
-                      uint8_t* vol_mask, hipStream_t s) {
+                      uint8_t* vol_mask, const MapsOut* maps, hipStream_t s) {
     const int S = cfg->n_steps;
     const FrameDev fd = to_dev(*f);
     const long long Q = (long long)n * S;
@@ -4147,41 +4243,57 @@ static int shade_impl(const ArahFrame* f, const ArahSampling* cfg, Workspace& w,
         slist = w.listB;
         scount = &w.counts[1];
     }
-    return shade_tail(f, cfg, w, fd, dirs, z, pts, T, mask, n, slist, scount, rgb, acc, vol_mask, s);
+    return shade_tail(f, cfg, w, fd, dirs, z, pts, T, mask, n, slist, scount, rgb, acc, vol_mask, maps, s);
 }
 
-// normal + colour of the samples in slist[0 .. *scount), then the per-ray compositing
+// k_shade over slist[0 .. *scount) on the frame's engine; MAPS: the posed unit normals -> nrm
+extern "C++" template <bool MAPS>
+static void launch_shade(const ArahFrame* f, const ArahSampling* cfg, Workspace& w, const FrameDev& fd, const float* dirs,
+                         const float* pts, const float* T, const int* slist, const int* scount, int g, f32x4* nrm,
+                         hipStream_t s) {
+    const int S = cfg->n_steps;
+    const B3Nets b3 = b3_of(*f);
+    if (fd.split && shade_b3(cfg->shade_engine)) {
+        if (f->col_mode == ARAH_COLOR_IDR)
+            hipLaunchKernelGGL((k_shade<true, true, true, MAPS>), dim3(g), dim3(kThreads), split_lds(lds_shade_b3<true>()), s, fd,
+                               S, cfg->cano_view_dirs, dirs, pts, T, slist, scount, 0, w.shaded, w.spill, &w.ctr->n_sdf_fwd,
+                               &w.ctr->n_sdf_grad, &w.ctr->n_col, b3, nrm);
+        else
+            hipLaunchKernelGGL((k_shade<false, true, true, MAPS>), dim3(g), dim3(kThreads), split_lds(lds_shade_b3<false>()), s, fd,
+                               S, cfg->cano_view_dirs, dirs, pts, T, slist, scount, 0, w.shaded, w.spill, &w.ctr->n_sdf_fwd,
+                               &w.ctr->n_sdf_grad, &w.ctr->n_col, b3, nrm);
+    } else if (f->col_mode == ARAH_COLOR_IDR)
+        LAUNCH_ENGINE(fd.split, (k_shade<true, true, false, MAPS>), (k_shade<true, false, false, MAPS>), dim3(g), dim3(kThreads),
+                      lds_shade<true>(), s, fd, S, cfg->cano_view_dirs, dirs, pts, T, slist, scount, 0, w.shaded, w.spill,
+                      &w.ctr->n_sdf_fwd, &w.ctr->n_sdf_grad, &w.ctr->n_col, b3, nrm);
+    else
+        LAUNCH_ENGINE(fd.split, (k_shade<false, true, false, MAPS>), (k_shade<false, false, false, MAPS>), dim3(g), dim3(kThreads),
+                      lds_shade<false>(), s, fd, S, cfg->cano_view_dirs, dirs, pts, T, slist, scount, 0, w.shaded, w.spill,
+                      &w.ctr->n_sdf_fwd, &w.ctr->n_sdf_grad, &w.ctr->n_col, b3, nrm);
+}
+
+// normal + colour of the samples in slist[0 .. *scount), then the per-ray compositing (with maps: + normal and depth)
 static int shade_tail(const ArahFrame* f, const ArahSampling* cfg, Workspace& w, const FrameDev& fd, const float* dirs,
                       const float* z, const float* pts, const float* T, const uint8_t* mask, int32_t n, const int* slist,
-                      const int* scount, float* rgb, float* acc, uint8_t* vol_mask, hipStream_t s) {
+                      const int* scount, float* rgb, float* acc, uint8_t* vol_mask, const MapsOut* maps, hipStream_t s) {
     const int S = cfg->n_steps;
     const long long Q = (long long)n * S;
     const int g = grid_for(Q, kTile);
     if (cfg->ev_shade[0] && cfg->ev_shade[1]) hipEventRecord(reinterpret_cast<hipEvent_t>(cfg->ev_shade[0]), s);
-    const B3Nets b3 = b3_of(*f);
-    if (fd.split && shade_b3(cfg->shade_engine)) {
-        if (f->col_mode == ARAH_COLOR_IDR)
-            hipLaunchKernelGGL((k_shade<true, true, true>), dim3(g), dim3(kThreads), split_lds(lds_shade_b3<true>()), s, fd, S,
-                               cfg->cano_view_dirs, dirs, pts, T, slist, scount, 0, w.shaded, w.spill, &w.ctr->n_sdf_fwd,
-                               &w.ctr->n_sdf_grad, &w.ctr->n_col, b3);
-        else
-            hipLaunchKernelGGL((k_shade<false, true, true>), dim3(g), dim3(kThreads), split_lds(lds_shade_b3<false>()), s, fd, S,
-                               cfg->cano_view_dirs, dirs, pts, T, slist, scount, 0, w.shaded, w.spill, &w.ctr->n_sdf_fwd,
-                               &w.ctr->n_sdf_grad, &w.ctr->n_col, b3);
-    } else if (f->col_mode == ARAH_COLOR_IDR)
-        LAUNCH_ENGINE(fd.split, (k_shade<true, true>), (k_shade<true, false>), dim3(g), dim3(kThreads), lds_shade<true>(),
-                      s, fd, S, cfg->cano_view_dirs, dirs, pts, T, slist, scount, 0, w.shaded, w.spill, &w.ctr->n_sdf_fwd,
-                      &w.ctr->n_sdf_grad, &w.ctr->n_col, b3);
-    else
-        LAUNCH_ENGINE(fd.split, (k_shade<false, true>), (k_shade<false, false>), dim3(g), dim3(kThreads),
-                      lds_shade<false>(), s, fd, S, cfg->cano_view_dirs, dirs, pts, T, slist, scount, 0, w.shaded, w.spill,
-                      &w.ctr->n_sdf_fwd, &w.ctr->n_sdf_grad, &w.ctr->n_col, b3);
+    if (maps) launch_shade<true>(f, cfg, w, fd, dirs, pts, T, slist, scount, g, maps->nrm, s);
+    else launch_shade<false>(f, cfg, w, fd, dirs, pts, T, slist, scount, g, nullptr, s);
     if (cfg->ev_shade[0] && cfg->ev_shade[1]) hipEventRecord(reinterpret_cast<hipEvent_t>(cfg->ev_shade[1]), s);
     const bool chunk = S % 8 == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0 && (reinterpret_cast<uintptr_t>(mask) & 7) == 0;
-    if (chunk) hipLaunchKernelGGL(k_composite<true>, dim3((n + 127) / 128), dim3(128), 0, s, n, S, cfg->render_last_pt, z, mask,
-                       (const f32x4*)w.shaded, rgb, acc, vol_mask);
-    else hipLaunchKernelGGL(k_composite<false>, dim3((n + 127) / 128), dim3(128), 0, s, n, S, cfg->render_last_pt, z, mask,
-                       (const f32x4*)w.shaded, rgb, acc, vol_mask);
+    const dim3 gc((n + 127) / 128), bc(128);
+    if (maps) {
+        if (chunk) hipLaunchKernelGGL(k_composite_maps<true>, gc, bc, 0, s, n, S, cfg->render_last_pt, z, mask, (const f32x4*)w.shaded,
+                                      rgb, acc, vol_mask, (const f32x4*)maps->nrm, maps->normal, maps->depth);
+        else hipLaunchKernelGGL(k_composite_maps<false>, gc, bc, 0, s, n, S, cfg->render_last_pt, z, mask, (const f32x4*)w.shaded,
+                                rgb, acc, vol_mask, (const f32x4*)maps->nrm, maps->normal, maps->depth);
+    } else if (chunk) hipLaunchKernelGGL(k_composite<true>, gc, bc, 0, s, n, S, cfg->render_last_pt, z, mask, (const f32x4*)w.shaded,
+                                         rgb, acc, vol_mask);
+    else hipLaunchKernelGGL(k_composite<false>, gc, bc, 0, s, n, S, cfg->render_last_pt, z, mask, (const f32x4*)w.shaded,
+                            rgb, acc, vol_mask);
     return check_launch();
 }
 
@@ -4230,7 +4342,7 @@ int arah_shade_composite(const ArahFrame* f, const ArahSampling* cfg, const floa
     Workspace w = carve(workspace, n, cfg->n_steps);
     if (wbytes < w.bytes) return ARAH_E_WORKSPACE;
     if (int arc = setup_attributes()) return arc;
-    return shade_impl(f, cfg, w, dirs, z, pts, T, mask, n, rgb, acc, vol_mask, reinterpret_cast<hipStream_t>(stream));
+    return shade_impl(f, cfg, w, dirs, z, pts, T, mask, n, rgb, acc, vol_mask, nullptr, reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- loop D with gradients (training) -------------------------------------------------------------
@@ -5068,7 +5180,7 @@ static int tier_phase(const ArahFrame* f, const ArahSampling* cfg, const FrameDe
 
 static int render_tiers(const ArahFrame* f, const ArahSampling* cfg, Workspace& w, const float* cam_loc, int32_t rays_per_cam,
                         const float* dirs, const float* near_far, const uint8_t* conv, const float* start, const float* end,
-                        int32_t n, float* rgb, float* acc, uint8_t* vol_mask, hipStream_t s) {
+                        int32_t n, float* rgb, float* acc, uint8_t* vol_mask, const MapsOut* maps, hipStream_t s) {
     const int S = cfg->n_steps;
     const FrameDev fd = to_dev(*f);
     const RaySet rs = make_rays(cam_loc, dirs, rays_per_cam);
@@ -5101,15 +5213,14 @@ static int render_tiers(const ArahFrame* f, const ArahSampling* cfg, Workspace& 
     if (rc) return rc;
     hipLaunchKernelGGL(k_tier_snap, dim3(1), dim3(64), 0, s, (const unsigned long long*)&w.ctr->n_canon,
                        (const unsigned long long*)&w.ctr->n_density, w.ctr->tier_snap, &w.ctr->n_canon_p2, &w.ctr->n_density_p2, 1);
-    return shade_tail(f, cfg, w, fd, dirs, w.o_z, w.o_pts, w.o_T, w.o_mask, n, w.listB, &tc[TC_NSHADE], rgb, acc, vol_mask, s);
+    return shade_tail(f, cfg, w, fd, dirs, w.o_z, w.o_pts, w.o_T, w.o_mask, n, w.listB, &tc[TC_NSHADE], rgb, acc, vol_mask, maps, s);
 }
 
-extern "C" {
 // ---- whole eval forward -------------------------------------------------------------------------
-int arah_render(const ArahFrame* f, const ArahSampling* cfg, const float* cam_loc, int32_t rays_per_cam,
-                const float* dirs, const float* near_far, const float* d_pose34, int32_t n, float* rgb,
-                float* points_cam, uint8_t* vol_mask, float* acc, float* dists, uint8_t* surface_conv,
-                void* workspace, size_t wbytes, void* stream) {
+static int render_impl(const ArahFrame* f, const ArahSampling* cfg, const float* cam_loc, int32_t rays_per_cam,
+                       const float* dirs, const float* near_far, const float* d_pose34, int32_t n, float* rgb,
+                       float* points_cam, uint8_t* vol_mask, float* acc, float* dists, uint8_t* surface_conv,
+                       void* workspace, size_t wbytes, const MapsOut* maps, void* stream) {
     if (!f || !cfg || n < 0 || !workspace) return ARAH_E_BADARG;
     int rc = check_sampling(cfg);
     if (rc) return rc;
@@ -5133,13 +5244,13 @@ int arah_render(const ArahFrame* f, const ArahSampling* cfg, const float* cam_lo
     if (rc) return rc;
     if (cfg->occupancy && !cfg->full_shading) {
         rc = render_tiers(f, cfg, w, cam_loc, rays_per_cam, dirs, near_far, o_conv, o_start, w.o_end, n, rgb,
-                          acc ? acc : w.o_acc, vol_mask, s);
+                          acc ? acc : w.o_acc, vol_mask, maps, s);
         if (rc) return rc;
     } else {
         rc = sample_impl(f, cfg, w, cam_loc, rays_per_cam, dirs, near_far, o_conv, o_start, w.o_end, n, nullptr, nullptr,
                          nullptr, w.o_z, w.o_pts, w.o_T, w.o_mask, s);
         if (rc) return rc;
-        rc = shade_impl(f, cfg, w, dirs, w.o_z, w.o_pts, w.o_T, w.o_mask, n, rgb, acc ? acc : w.o_acc, vol_mask, s);
+        rc = shade_impl(f, cfg, w, dirs, w.o_z, w.o_pts, w.o_T, w.o_mask, n, rgb, acc ? acc : w.o_acc, vol_mask, maps, s);
         if (rc) return rc;
     }
     if (points_cam)
@@ -5147,6 +5258,40 @@ int arah_render(const ArahFrame* f, const ArahSampling* cfg, const float* cam_lo
                            make_rays(cam_loc, dirs, rays_per_cam), (const float*)o_start, (const uint8_t*)o_conv,
                            (const float*)w.o_xnorm, d_pose34, points_cam);
     return check_launch();
+}
+
+// the caller buffer of arah_render_maps: one f32x4 per sample, the posed unit normal of the samples k_shade shades
+static size_t maps_bytes(int n_rays, int n_steps) {
+    const size_t N = (size_t)(n_rays > 0 ? n_rays : 1), Q = N * (size_t)(n_steps > 0 ? n_steps : 1);
+    return align_up(Q * sizeof(f32x4), 256);
+}
+
+extern "C" {
+int arah_render(const ArahFrame* f, const ArahSampling* cfg, const float* cam_loc, int32_t rays_per_cam,
+                const float* dirs, const float* near_far, const float* d_pose34, int32_t n, float* rgb,
+                float* points_cam, uint8_t* vol_mask, float* acc, float* dists, uint8_t* surface_conv,
+                void* workspace, size_t wbytes, void* stream) {
+    return render_impl(f, cfg, cam_loc, rays_per_cam, dirs, near_far, d_pose34, n, rgb, points_cam, vol_mask, acc, dists,
+                       surface_conv, workspace, wbytes, nullptr, stream);
+}
+
+size_t arah_render_maps_bytes(int32_t n_rays, int32_t n_steps) {
+    if (n_rays < 0 || n_steps < 0) return 0;
+    return maps_bytes(n_rays, n_steps);
+}
+
+int arah_render_maps(const ArahFrame* f, const ArahSampling* cfg, const float* cam_loc, int32_t rays_per_cam,
+                     const float* dirs, const float* near_far, const float* d_pose34, int32_t n, float* rgb,
+                     float* points_cam, uint8_t* vol_mask, float* acc, float* dists, uint8_t* surface_conv,
+                     float* normal_world, float* depth, void* workspace, size_t wbytes, void* maps_buf, size_t maps_buf_bytes,
+                     void* stream) {
+    if (!cfg) return ARAH_E_BADARG;
+    if (int rc = check_sampling(cfg)) return rc;
+    if (n > 0 && (!normal_world || !depth || !maps_buf)) return ARAH_E_BADARG;
+    if (n > 0 && maps_buf_bytes < maps_bytes(n, cfg->n_steps)) return ARAH_E_WORKSPACE;
+    const MapsOut maps{reinterpret_cast<f32x4*>(maps_buf), normal_world, depth};
+    return render_impl(f, cfg, cam_loc, rays_per_cam, dirs, near_far, d_pose34, n, rgb, points_cam, vol_mask, acc, dists,
+                       surface_conv, workspace, wbytes, &maps, stream);
 }
 
 }  // extern "C"

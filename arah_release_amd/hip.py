@@ -130,7 +130,7 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_skin_lbs_counted", "arah_marching_cubes_scratch_bytes", "arah_marching_cubes",
            "arah_occupancy_bytes", "arah_prepare_occupancy", "arah_occupancy_info", "arah_tier_debug", "arah_debug_samples",
            "arah_sdf_grid_band_scratch_bytes", "arah_sdf_grid_band", "arah_tier_audit_bytes", "arah_tier_audit",
-           "arah_tier_audit_debug", "arah_occupancy_clear_box"]
+           "arah_tier_audit_debug", "arah_occupancy_clear_box", "arah_render_maps_bytes", "arah_render_maps"]
 
 _lib = None
 
@@ -158,6 +158,8 @@ def load_library():
     lib.arah_colsum_blocks.argtypes = [C.c_int64]
     lib.arah_tier_audit_bytes.restype = C.c_size_t
     lib.arah_tier_audit_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.arah_render_maps_bytes.restype = C.c_size_t
+    lib.arah_render_maps_bytes.argtypes = [C.c_int32, C.c_int32]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the symbol is missing
     _lib = lib
@@ -264,6 +266,7 @@ class Workspace:
         self.buf = None
         self.occ = None   # occupancy bitmap of the frame this scratch is rendering (tiered eval forward)
         self.audit_buf = None   # scratch of arah_tier_audit (allocated by the first audit: about one more workspace)
+        self.maps_buf = None    # per-sample normals of arah_render_maps (allocated by the first render with maps)
 
     def occupancy(self, frame):
         """arah_prepare_occupancy for `frame` on the current stream, into this scratch's own buffer (a scratch serves one
@@ -304,6 +307,14 @@ class Workspace:
             with torch.cuda.device(self.device):
                 self.audit_buf = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self.audit_buf
+
+    def maps_ensure(self, n_rays, n_steps):
+        need = load_library().arah_render_maps_bytes(int(n_rays), int(n_steps))
+        if self.maps_buf is None or self.maps_buf.numel() < need:
+            self.maps_buf = None
+            with torch.cuda.device(self.device):
+                self.maps_buf = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self.maps_buf
 
     def tier_audit_debug(self, n_rays, n_steps):
         """(sample_tag [N*S], ray_tag [N]) uint8 verdicts of the last arah_tier_audit on this scratch (include/arah_hip.h)."""
@@ -1138,11 +1149,12 @@ def inverse3x3(m, scale=1.0):
 
 
 @_guarded
-def render(frame, ws, sampling, cam_loc, dirs, near_far, pose34, tiered=False):
+def render(frame, ws, sampling, cam_loc, dirs, near_far, pose34, tiered=False, maps=False):
     """Whole eval forward. pose34: DEVICE (3,4) world->camera (no host copy, no stream drain).
     tiered: build the frame's occupancy bitmap first and let arah_render skip the samples it certifies (csrc/tier.hpp;
     lazy shading only -- with full_shading the flag is ignored).
-    Returns rgb, points_cam, vol_mask, acc, dists, conv."""
+    maps: arah_render_maps -- also the composited normal (world frame, not renormalised) and depth maps (include/arah_hip.h).
+    Returns rgb, points_cam, vol_mask, acc, dists, conv (+ normal_world (N,3), depth (N,) with maps)."""
     lib = load_library()
     cam, d, nf = _f32(cam_loc), _f32(dirs), _f32(near_far)
     n, S = d.shape[0], sampling.n_steps
@@ -1161,10 +1173,19 @@ def render(frame, ws, sampling, cam_loc, dirs, near_far, pose34, tiered=False):
     dists = torch.empty(n, device=dev)
     conv = torch.empty(n, dtype=torch.uint8, device=dev)
     d_pose = _f32(pose34).reshape(-1)[:12].contiguous()
-    _check(lib.arah_render(C.byref(frame.handle), C.byref(cfg), _ptr(cam), C.c_int32(n // cam.shape[0]),
-                           _ptr(d), _ptr(nf), _ptr(d_pose), C.c_int32(n), _ptr(rgb), _ptr(pcam), _ptr(vol), _ptr(acc),
-                           _ptr(dists), _ptr(conv), _ptr(buf), C.c_size_t(buf.numel()), _stream()), "arah_render")
-    return rgb, pcam, vol, acc, dists, conv
+    if not maps:
+        _check(lib.arah_render(C.byref(frame.handle), C.byref(cfg), _ptr(cam), C.c_int32(n // cam.shape[0]),
+                               _ptr(d), _ptr(nf), _ptr(d_pose), C.c_int32(n), _ptr(rgb), _ptr(pcam), _ptr(vol), _ptr(acc),
+                               _ptr(dists), _ptr(conv), _ptr(buf), C.c_size_t(buf.numel()), _stream()), "arah_render")
+        return rgb, pcam, vol, acc, dists, conv
+    mbuf = ws.maps_ensure(n, S)
+    normal = torch.empty(n, 3, device=dev)
+    depth = torch.empty(n, device=dev)
+    _check(lib.arah_render_maps(C.byref(frame.handle), C.byref(cfg), _ptr(cam), C.c_int32(n // cam.shape[0]),
+                                _ptr(d), _ptr(nf), _ptr(d_pose), C.c_int32(n), _ptr(rgb), _ptr(pcam), _ptr(vol), _ptr(acc),
+                                _ptr(dists), _ptr(conv), _ptr(normal), _ptr(depth), _ptr(buf), C.c_size_t(buf.numel()),
+                                _ptr(mbuf), C.c_size_t(mbuf.numel()), _stream()), "arah_render_maps")
+    return rgb, pcam, vol, acc, dists, conv, normal, depth
 
 
 @_guarded

@@ -656,8 +656,13 @@ class IDHRNetwork(nn.Module):
         rec["pending"] = True
         return None
 
-    def forward(self, input):
+    def forward(self, input, render_maps=False):
+        """Eval forward (arah_render); training mode: forward_train.  render_maps: also the normal, depth and opacity maps
+        (arah_render_maps) -- normal_values (B,N,3) in each view's camera frame, sum w n, not renormalised; depth_values (B,N),
+        sum w z in the units of the ray parameter; acc_values (B,N), sum w.  Eval only."""
         if self.training:
+            if render_maps:
+                raise ValueError("render_maps is an eval-forward option: the training forward renders no maps")
             return self.forward_train(input)
         ray_dirs = input["ray_dirs"]
         cam_loc = input["cam_loc"]
@@ -695,17 +700,18 @@ class IDHRNetwork(nn.Module):
         if tiered and self.adaptive_shading and self._tier_off and guard is not None and self.guard_mode != "strict":
             self._tier_since_probe += 1
             tiered = self._tier_since_probe % 16 == 0          # every 16th frame tiered: refreshes the measured share
-        rgb, pcam, vol, acc, dists, conv = hip.render(frame, ws, samp, cam_loc.reshape(B, 3),
+        maps_kw = {"maps": True} if render_maps else {}   # (without maps: the call arah_render has always had)
+        rgb, pcam, vol, acc, dists, conv, *maps = hip.render(frame, ws, samp, cam_loc.reshape(B, 3),
                                                       ray_dirs.reshape(B * N, 3), nf.reshape(B * N, 2), pose34,
-                                                      tiered=tiered)
+                                                      tiered=tiered, **maps_kw)
         if tiered and audit != "off":
             res = self._tier_audit_launch(frame, ws, samp, cam_loc.reshape(B, 3), ray_dirs.reshape(B * N, 3), nf.reshape(B * N, 2), dev)
             if res is not None and res["violations"] > 0:   # "strict": this frame again, untiered
                 self._tier_audit_violated(res, "this frame is rendered again untiered")
                 tiered = False
-                rgb, pcam, vol, acc, dists, conv = hip.render(frame, ws, samp, cam_loc.reshape(B, 3),
+                rgb, pcam, vol, acc, dists, conv, *maps = hip.render(frame, ws, samp, cam_loc.reshape(B, 3),
                                                               ray_dirs.reshape(B * N, 3), nf.reshape(B * N, 2), pose34,
-                                                              tiered=False)
+                                                              tiered=False, **maps_kw)
         if guard is not None and self.guard_mode == "strict" and frame.precision != hip.PRECISION_FP32:
             now = int(ws.buf[64:72].view(torch.int64).item())   # ArahCounters.n_split_nonfinite; synchronises the stream
             grew = now - guard["seen"] if now >= guard["seen"] else now
@@ -722,9 +728,9 @@ class IDHRNetwork(nn.Module):
                                     input["coord_min"], input["coord_max"], input["center"],
                                     precision=hip.PRECISION_FP32, body_tables=input.get("_body_tables"))
                 self.last_frame = frame
-                rgb, pcam, vol, acc, dists, conv = hip.render(frame, ws, samp, cam_loc.reshape(B, 3),
+                rgb, pcam, vol, acc, dists, conv, *maps = hip.render(frame, ws, samp, cam_loc.reshape(B, 3),
                                                               ray_dirs.reshape(B * N, 3), nf.reshape(B * N, 2), pose34,
-                                                              tiered=tiered)
+                                                              tiered=tiered, **maps_kw)
         elif guard is not None and self.guard_mode != "strict":
             self._split_guard_arm(guard, ws, full)
         pcam = pcam.reshape(B, N, 3)
@@ -732,7 +738,14 @@ class IDHRNetwork(nn.Module):
             pw = cam_loc.reshape(B, 1, 3) + dists.reshape(B, N, 1) * ray_dirs
             pc = torch.matmul(pw, pose[:, :3, :3].transpose(1, 2)) + pose[:, :3, 3].unsqueeze(1)
             pcam = torch.where((pcam.abs().sum(-1, keepdim=True) > 0), pc, torch.zeros_like(pc))
-        return {"points_cam": pcam, "network_body_mask": vol.bool().reshape(B, N), "rgb_values": rgb.reshape(B, N, 3)}
+        out = {"points_cam": pcam, "network_body_mask": vol.bool().reshape(B, N), "rgb_values": rgb.reshape(B, N, 3)}
+        if render_maps:   # the world-frame normal of view b into that view's camera frame: pose[b, :3, :3] n
+            normal_world, depth = maps
+            rot = pose[:, :3, :3].detach().float()
+            out["normal_values"] = torch.matmul(normal_world.reshape(B, N, 3), rot.transpose(1, 2))
+            out["depth_values"] = depth.reshape(B, N)
+            out["acc_values"] = acc.reshape(B, N)
+        return out
 
 
 class MetaAvatarRender(nn.Module):
@@ -817,6 +830,18 @@ class MetaAvatarRender(nn.Module):
                 yield param
 
     def forward(self, inputs, gen_cano_mesh=False, eval=False):
+        return self._forward(inputs, gen_cano_mesh, eval, False)
+
+    def forward_maps(self, inputs, gen_cano_mesh=False, eval=True):
+        """The eval forward plus the normal, depth and opacity maps: the output also holds normal_values (B,N,3, each view's
+        camera frame), depth_values (B,N) and acc_values (B,N), composited with the weights of the rgb (IDHRNetwork.forward,
+        include/arah_hip.h: arah_render_maps).  `forward` keeps the reference's signature (models/__init__.py:141), hence a
+        method of its own; render_sequence(model, frames, render_maps=True) sends the frames here."""
+        if self.training or not eval:
+            raise ValueError("render_maps needs the eval forward: model.eval() and eval=True")
+        return self._forward(inputs, gen_cano_mesh, True, True)
+
+    def _forward(self, inputs, gen_cano_mesh, eval, render_maps):
         rots, Jtrs = inputs["rots"], inputs["Jtrs"]
         B, dev = rots.size(0), rots.device
         decoder_input = {"coords": torch.zeros(1, 1, 3, dtype=torch.float32, device=dev),
@@ -877,7 +902,7 @@ class MetaAvatarRender(nn.Module):
         if "latent_code_idx" in inputs["pose_cond"]:
             inputs["pose_cond"]["latent_code"] = self.latent(inputs["pose_cond"]["latent_code_idx"])
         try:
-            model_outputs = self.idhr_network(inputs)
+            model_outputs = self.idhr_network(inputs, render_maps=True) if render_maps else self.idhr_network(inputs)
         finally:
             inputs.pop("_body_tables", None)   # they belong to this call's vertices, not to the caller's dict
         model_outputs.update({"sdf_params": out["params"]})
@@ -891,6 +916,15 @@ class MetaAvatarRender(nn.Module):
             maps, _ = meshing.canonical_mesh_outputs(frame, self.idhr_network.ray_tracer.workspace(dev), inputs, want_tri=False)
             model_outputs.update(maps)
         return model_outputs
+
+
+def normal_display(normal_values, mask, background=0.0):
+    """normal_values (..., 3) of a render_maps forward and a mask (...) -> display colours (..., 3) in [0, 1]: ((n + 1) / 2)
+    clipped, the mapping of the reference's normal images (models/__init__.py:265), and `background` (a grey level or an
+    RGB triple) off the mask.  The default, black, is what the reference's background normal -1 maps to."""
+    img = ((normal_values + 1.0) / 2.0).clip(0.0, 1.0)
+    bg = torch.as_tensor(background, dtype=img.dtype, device=img.device).expand(img.shape)
+    return torch.where(mask.unsqueeze(-1).bool(), img, bg)
 
 
 def _walk_tensors(obj):
@@ -919,7 +953,7 @@ def frames_in_flight(n_frames):
     return max(1, min(4, n_frames))
 
 
-def render_sequence(model, frames, n_streams=None, **forward_kwargs):
+def render_sequence(model, frames, n_streams=None, render_maps=False, **forward_kwargs):
     """Render independent frames (a test sequence, reference test.py / lightning_model.py:320) with `n_streams` of them in
     flight: frame k runs on HIP stream k mod n_streams with its own scratch, so that the latency-bound stretches of one
     frame (the tails of sphere tracing and of the joint root find: a few hundred live rays, ~60 us of kernel latency per
@@ -933,7 +967,10 @@ def render_sequence(model, frames, n_streams=None, **forward_kwargs):
     (1600 frames, bit-identical images) came back clean (tools/stress_streams.py, profiles/r03_streams_soak.txt);
     round 4: n_streams=None = frames_in_flight(len(frames)), four or five.
     frames: iterable of input dicts (resident on one GPU); returns the list of output dicts, usable on the caller's
-    current stream.  model(inputs, **forward_kwargs) is called under torch.no_grad()."""
+    current stream.  model(inputs, **forward_kwargs) is called under torch.no_grad(); with render_maps=True,
+    model.forward_maps(inputs, **forward_kwargs) (the maps of each frame in its own scratch)."""
+    if render_maps:
+        return map_in_flight(lambda f: model.forward_maps(f, **forward_kwargs), frames, n_streams=n_streams, owner=model)
     return map_in_flight(lambda f: model(f, **forward_kwargs), frames, n_streams=n_streams, owner=model)
 
 

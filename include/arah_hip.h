@@ -15,6 +15,8 @@
  *   arah_shade_points       its per-sample half (SDF, normal, colour, density) on the shipped engine
  *                           renderer/implicit_differentiable_renderer.py:261-396, :142-148,:225-257
  *   arah_render             IDHRNetwork.forward (eval)  implicit_differentiable_renderer.py:42-259
+ *   arah_render_maps        arah_render + the composited normal and depth maps (no reference counterpart: the VolSDF
+ *                           compositing of the posed SDF normal, implicit_differentiable_renderer.py:338-340, 370-394)
  *   arah_sdf_eval           sdf_network(x) / gradient(sdf, x)   hyperlayers.py:385-415,
  *                           siren_modules.py:35-37, diff_operators.py:39-50
  *   arah_skin_lbs           forward_skinning / query_weights  root_finding_utils.py:54-167,
@@ -458,6 +460,23 @@ int arah_render(const ArahFrame* h_frame, const ArahSampling* h_cfg, const float
                 int32_t n_rays, float* rgb, float* points_cam, uint8_t* vol_mask, float* acc,
                 float* dists, uint8_t* surface_conv, void* workspace, size_t workspace_bytes,
                 void* stream);
+
+/* arah_render plus a normal map and a depth map, composited with the weights w_i of the rgb.  For every valid sample i that
+ * is shaded, n_i = normalize(T_i[:3,:3] . d sdf / d x_norm (x_norm_i)): the posed (world-frame) unit normal, pointing towards
+ * positive sdf (the normal the reference gives the colour network with cano_view_dirs = False, IDR:338-340).  Per ray:
+ *   normal_world [N,3] = sum_i w_i n_i   (not renormalised: |normal_world| <= acc)
+ *   depth [N]          = sum_i w_i z_i   (z: the ray parameter of the samples, the units of `dists`)
+ *   acc [N]            = sum_i w_i       (the existing output)
+ * 0 on rays without valid samples.  Samples that are not shaded have weight exactly 0 and contribute +0; the tiered path
+ * gives the untiered path's maps bit for bit, and rgb, points_cam, vol_mask, acc, dists, surface_conv are arah_render's bit
+ * for bit.  maps_buf: a caller buffer of arah_render_maps_bytes(n_rays, n_steps) bytes (16 bytes per sample: the per-sample
+ * normals), next to the workspace of arah_workspace_bytes. */
+size_t arah_render_maps_bytes(int32_t n_rays, int32_t n_steps);
+int arah_render_maps(const ArahFrame* h_frame, const ArahSampling* h_cfg, const float* cam_loc,
+                     int32_t rays_per_cam, const float* dirs, const float* near_far, const float* pose34,
+                     int32_t n_rays, float* rgb, float* points_cam, uint8_t* vol_mask, float* acc,
+                     float* dists, uint8_t* surface_conv, float* normal_world, float* depth, void* workspace,
+                     size_t workspace_bytes, void* maps_buf, size_t maps_buf_bytes, void* stream);
 
 /* ---- tiered evaluation (csrc/tier.hpp) --------------------------------------------------------- */
 /* The reference evaluates every depth sample of every ray (ray_tracing.py:313-380 -> search_canonical_corr,
