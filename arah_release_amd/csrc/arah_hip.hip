@@ -2765,6 +2765,7 @@ __global__ void k_points_cam(FrameDev fr, int n, RaySet rs, const float* dists, 
 }
 
 #include "tier.hpp"
+#include "posed.hpp"
 }  // namespace
 #include "train.hpp"
 #include "meshquery.hpp"
@@ -2882,6 +2883,8 @@ struct Knobs {
     int canon_wg_per_cu; // ARAH_CANON_WG_PER_CU   resident workgroups of that kernel per CU (grid = this x CUs; 1)
     bool train_b3;       // ARAH_TRAIN_ENGINE!=fp32  bf16 x 3 / f16 split training kernels on split frames
     int canon_tier_wgs;  // ARAH_CANON_TIER_WGS    workgroups of loop C's solver on the tiered forward's lists (0 = one per CU)
+    int posed_canon;     // ARAH_CANON_KERNEL      wave | tile | wave_l2: loop C's solver of arah_query_posed / arah_sdf_grid_posed, whose
+                         //                        signatures carry no ArahSampling (the renderer's calls take it from ArahSampling)
 };
 inline const Knobs& knobs() {
     static const Knobs k = [] {
@@ -2905,6 +2908,9 @@ inline const Knobs& knobs() {
         v.canon_lds_min = max(0, min((int)kLdsCanonWave, env_int("ARAH_CANON_LDS_MIN", 0)));
         v.canon_wg_per_cu = max(1, min(4, env_int("ARAH_CANON_WG_PER_CU", 1)));
         v.canon_tier_wgs = max(0, env_int("ARAH_CANON_TIER_WGS", 0));
+        const char* ck = getenv("ARAH_CANON_KERNEL");
+        v.posed_canon = !ck ? ARAH_CANON_KERNEL_WAVE : strcmp(ck, "tile") == 0 ? ARAH_CANON_KERNEL_TILE
+                        : strcmp(ck, "wave_l2") == 0 ? ARAH_CANON_KERNEL_WAVE_L2 : ARAH_CANON_KERNEL_WAVE;
         const char* e = getenv("ARAH_TRAIN_ENGINE");
         v.train_b3 = !(e && strcmp(e, "fp32") == 0);
         return v;
@@ -5399,5 +5405,133 @@ int arah_tier_audit_debug(const void* audit_buf, size_t audit_bytes, int32_t n_r
     if (sample_tag) ok = ok && hipMemcpyAsync(sample_tag, ab.tag, (size_t)n_rays * n_steps, hipMemcpyDeviceToDevice, s) == hipSuccess;
     if (ray_tag) ok = ok && hipMemcpyAsync(ray_tag, ab.ray_tag, (size_t)n_rays, hipMemcpyDeviceToDevice, s) == hipSuccess;
     return ok ? ARAH_OK : ARAH_E_LAUNCH;
+}
+}  // extern "C"
+
+// ---- posed-space queries (posed.hpp, include/arah_hip.h: arah_query_posed / arah_sdf_grid_posed) ------------------------------
+// The caller buffer: a workspace of (1, 1) rays (counters, the SDF gradient's spill slab), the pass's list counts and the work
+// arrays of one pass of at most kPosedChunk points, indexed by the position in the compacted list.
+struct PosedBuf {
+    Workspace w;
+    int* cnt;        // [4] {entries, head of loop C's queue, -, -}
+    int* bounds;     // [8] voxel bounds of the default lattice box
+    float* cpts;     // [C][3] world points of the list
+    float* zeros;    // [C][3] zero directions and depths: the list rides the sample path as rays of length 0 (cam_loc = point)
+    int* cidx;       // [C] index of the point in the caller's order
+    int* list;       // [C] identity: the list of the production kernels
+    float *xraw, *T, *err, *xn, *sdfn, *grad, *wts;
+    uint8_t* conv;
+    int chunk;
+    size_t bytes;
+};
+static PosedBuf carve_posed(void* base, long long n_pts) {
+    PosedBuf b;
+    const int C = (int)(n_pts < 1 ? 1 : n_pts > kPosedChunk ? kPosedChunk : n_pts);
+    b.chunk = C;
+    b.w = carve(base, 1, 1);
+    Carver c{reinterpret_cast<char*>(base), align_up(b.w.bytes, 256)};
+    b.cnt = c.take<int>(4);
+    b.bounds = c.take<int>(8);
+    b.cpts = c.take<float>((size_t)C * 3);
+    b.zeros = c.take<float>((size_t)C * 3);
+    b.cidx = c.take<int>(C);
+    b.list = c.take<int>(C);
+    b.xraw = c.take<float>((size_t)C * 3);
+    b.T = c.take<float>((size_t)C * 16);
+    b.err = c.take<float>(C);
+    b.xn = c.take<float>((size_t)C * 3);
+    b.sdfn = c.take<float>(C);
+    b.grad = c.take<float>((size_t)C * 3);
+    b.wts = c.take<float>((size_t)C * 24);
+    b.conv = c.take<uint8_t>(C);
+    b.bytes = align_up(c.off, 256);
+    return b;
+}
+
+// every point of `src` (n of them) through pick -> nearest vertex + inverse LBS -> loop C -> normalisation -> SDF trunk
+// (+ gradient, + skinning weights) -> scatter, kPosedChunk points per pass; no host synchronisation
+static int posed_run(const FrameDev& fd, PosedBuf& b, const PosedSrc& src, const void* occ_buf, long long n, const PosedOut& out,
+                     int canon_kernel, hipStream_t s) {
+    const OccBuf o = carve_occ(const_cast<void*>(occ_buf));
+    const OccInfo* info = occ_buf ? (const OccInfo*)o.info : nullptr;
+    Workspace& w = b.w;
+    hipMemsetAsync(w.ctr, 0, sizeof(Counters), s);
+    hipMemsetAsync(b.zeros, 0, sizeof(float) * 3 * (size_t)b.chunk, s);
+    const RaySet rs = make_rays(b.cpts, b.zeros, 1);
+    const int C = b.chunk;
+    for (long long base = 0; base < n; base += C) {
+        const int m = (int)min((long long)C, n - base);
+        hipMemsetAsync(b.cnt, 0, sizeof(int) * 4, s);
+        hipLaunchKernelGGL(k_posed_pick, dim3((m + 255) / 256), dim3(256), 0, s, src, info, (const unsigned*)(occ_buf ? o.bits : nullptr),
+                           (const uint8_t*)(occ_buf ? o.dist : nullptr), base, m, b.cpts, b.cidx, b.list, b.cnt, out.sdf, out.state,
+                           out.counts);
+        launch_nearest<SRC_SAMPLES>(s, fd, m, (const float*)nullptr, rs, (const float*)b.zeros, 1, (const int*)b.list,
+                                    (const int*)&b.cnt[0], 0, (int*)nullptr, b.xraw, b.T, 1, &w.ctr->n_knn);
+        int rc = run_broyden3(fd, w, nullptr, CanonOut{b.xraw, b.T, b.err}, m, s, canon_kernel, nullptr, b.list, b.cnt);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_posed_norm, dim3(grid_for(m, 256)), dim3(256), 0, s, fd, (const int*)b.cnt, (const float*)b.xraw,
+                           (const float*)b.err, b.xn, b.conv);
+        if (out.normal)
+            LAUNCH_ENGINE(fd.split, (k_sdf_eval<true, true>), (k_sdf_eval<true, false>), dim3(grid_for(m, kTile)), dim3(kThreads),
+                          kLdsSdfGrad, s, fd, (const float*)b.xn, (const int*)b.list, (const int*)&b.cnt[0], 0, b.sdfn, (float*)nullptr,
+                          b.grad, w.spill, &w.ctr->n_sdf_fwd, &w.ctr->n_sdf_grad, 0);
+        else
+            LAUNCH_ENGINE(fd.split, (k_sdf_eval<false, true>), (k_sdf_eval<false, false>), dim3(grid_for(m, kTile)), dim3(kThreads),
+                          kLdsSdfFwd, s, fd, (const float*)b.xn, (const int*)b.list, (const int*)&b.cnt[0], 0, b.sdfn, (float*)nullptr,
+                          (float*)nullptr, (f32x4*)nullptr, &w.ctr->n_sdf_fwd, (unsigned long long*)nullptr, 0);
+        if (out.weights)
+            hipLaunchKernelGGL(k_skin_eval, dim3(grid_for(m, kTile)), dim3(kThreads), kLdsSkin, s, fd, (const float*)b.xraw, m, b.wts,
+                               (float*)nullptr, (float*)nullptr, &w.ctr->n_skin_fwd, (const int*)&b.cnt[0], 1);
+        hipLaunchKernelGGL(k_posed_out, dim3(grid_for(m, 256)), dim3(256), 0, s, fd, (const int*)b.cnt, (const int*)b.cidx,
+                           (const float*)b.sdfn, (const uint8_t*)b.conv, (const float*)b.xn, (const float*)b.T, (const float*)b.grad,
+                           (const float*)b.wts, out);
+    }
+    return check_launch();
+}
+
+extern "C" {
+size_t arah_query_posed_bytes(int32_t n_pts) { return carve_posed(nullptr, n_pts).bytes; }
+
+int arah_query_posed(const ArahFrame* f, const void* occ_buf, const float* pts, int32_t n_pts, float* sdf, float* x_hat_norm,
+                     float* T, float* normal, float* weights, uint8_t* state, void* buf, size_t buf_bytes, void* stream) {
+    if (!f || n_pts < 0 || !buf) return ARAH_E_BADARG;
+    if (n_pts == 0) return ARAH_OK;
+    if (!pts || !sdf || !state) return ARAH_E_BADARG;
+    PosedBuf b = carve_posed(buf, n_pts);
+    if (buf_bytes < b.bytes) return ARAH_E_WORKSPACE;
+    if (int arc = setup_attributes()) return arc;
+    const PosedSrc src{pts, nullptr, 0, 0};
+    const PosedOut out{sdf, x_hat_norm, T, normal, weights, state, nullptr};
+    return posed_run(to_dev(*f), b, src, occ_buf, n_pts, out, knobs().posed_canon, reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t arah_sdf_grid_posed_bytes(int32_t n_side) {
+    if (n_side < 2 || n_side > 1024) return 0;
+    return carve_posed(nullptr, (long long)n_side * n_side * n_side).bytes;
+}
+
+int arah_sdf_grid_posed(const ArahFrame* f, const void* occ_buf, const float* box, int32_t n_side, int32_t band, float* sdf,
+                        float* box_out, int32_t* counts, void* buf, size_t buf_bytes, void* stream) {
+    if (!f || !sdf || !box_out || !counts || !buf || n_side < 2 || n_side > 1024) return ARAH_E_BADARG;
+    if (!box && !occ_buf) return ARAH_E_BADARG;   // the default box comes from the bitmap
+    const long long n = (long long)n_side * n_side * n_side;
+    PosedBuf b = carve_posed(buf, n);
+    if (buf_bytes < b.bytes) return ARAH_E_WORKSPACE;
+    if (int arc = setup_attributes()) return arc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipMemsetAsync(counts, 0, sizeof(int32_t) * 3, s);
+    if (box) {
+        if (hipMemcpyAsync(box_out, box, sizeof(float) * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return ARAH_E_LAUNCH;
+    } else {
+        const OccBuf o = carve_occ(const_cast<void*>(occ_buf));
+        constexpr int words = kOccMaxVox / 32;   // the launch covers the largest bitmap; words beyond this one's return at once
+        hipLaunchKernelGGL(k_posed_box_begin, dim3(1), dim3(64), 0, s, b.bounds);
+        hipLaunchKernelGGL(k_posed_box_reduce, dim3((words + 255) / 256), dim3(256), 0, s, (const OccInfo*)o.info, (const unsigned*)o.bits,
+                           b.bounds);
+        hipLaunchKernelGGL(k_posed_box_finish, dim3(1), dim3(64), 0, s, (const OccInfo*)o.info, (const int*)b.bounds, box_out);
+    }
+    const PosedSrc src{nullptr, box_out, (int)n_side, band ? 1 : 0};
+    const PosedOut out{sdf, nullptr, nullptr, nullptr, nullptr, nullptr, counts};
+    return posed_run(to_dev(*f), b, src, occ_buf, n, out, knobs().posed_canon, s);
 }
 }  // extern "C"

@@ -130,7 +130,8 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_skin_lbs_counted", "arah_marching_cubes_scratch_bytes", "arah_marching_cubes",
            "arah_occupancy_bytes", "arah_prepare_occupancy", "arah_occupancy_info", "arah_tier_debug", "arah_debug_samples",
            "arah_sdf_grid_band_scratch_bytes", "arah_sdf_grid_band", "arah_tier_audit_bytes", "arah_tier_audit",
-           "arah_tier_audit_debug", "arah_occupancy_clear_box", "arah_render_maps_bytes", "arah_render_maps"]
+           "arah_tier_audit_debug", "arah_occupancy_clear_box", "arah_render_maps_bytes", "arah_render_maps",
+           "arah_query_posed_bytes", "arah_query_posed", "arah_sdf_grid_posed_bytes", "arah_sdf_grid_posed"]
 
 _lib = None
 
@@ -160,6 +161,10 @@ def load_library():
     lib.arah_tier_audit_bytes.argtypes = [C.c_int32, C.c_int32]
     lib.arah_render_maps_bytes.restype = C.c_size_t
     lib.arah_render_maps_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.arah_query_posed_bytes.restype = C.c_size_t
+    lib.arah_query_posed_bytes.argtypes = [C.c_int32]
+    lib.arah_sdf_grid_posed_bytes.restype = C.c_size_t
+    lib.arah_sdf_grid_posed_bytes.argtypes = [C.c_int32]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the symbol is missing
     _lib = lib
@@ -581,6 +586,100 @@ def sdf_grid_band(frame, ws, n_side=256):
                                   C.c_size_t(scratch.numel()), _ptr(buf), C.c_size_t(buf.numel()), _stream()), "arah_sdf_grid_band")
     n_eval = scratch[0:4].view(torch.int32)
     return out, n_eval
+
+
+POSED_FILL = 1.0   # ARAH_POSED_FILL (include/arah_hip.h), metres
+POSED_WANT = ("sdf", "points_hat", "T", "normal", "weights")
+_posed_scratch = {}
+
+
+def _posed_buf(dev, nbytes):
+    """Per-(device, stream) scratch of the posed queries (grows on demand; one stream's calls are ordered)."""
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+    buf = _posed_scratch.get(key)
+    if buf is None or buf.numel() < nbytes:
+        if buf is None and len(_posed_scratch) >= 8:
+            _posed_scratch.pop(next(iter(_posed_scratch)))
+        buf = _posed_scratch[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    return buf
+
+
+@_guarded
+def query_posed(frame, ws, pts, occ=None, want=POSED_WANT):
+    """The posed SDF at world points pts (P,3) (arah_query_posed): -> dict with `state` (P,) uint8 (0 not converged, 1 converged,
+    2 skipped: certified sigma = +0 by the occupancy buffer `occ`) and the fields of `want` -- sdf (P,) metres, points_hat (P,3)
+    normalised canonical, T (P,4,4), normal (P,3) posed unit normal, weights (P,24).  Skipped points have sdf = POSED_FILL and
+    zeros in the other fields."""
+    lib = load_library()
+    x = _f32(pts).reshape(-1, 3)
+    n, dev = int(x.shape[0]), frame.device
+    bad = set(want) - set(POSED_WANT)
+    if bad:
+        raise ValueError("query_posed: unknown fields %s" % sorted(bad))
+    sdf = torch.empty(n, device=dev)
+    state = torch.empty(n, dtype=torch.uint8, device=dev)
+    z = {"points_hat": 3, "T": 16, "normal": 3, "weights": 24}
+    outs = {k: (torch.zeros(n, c, device=dev) if k in want else None) for k, c in z.items()}
+    buf = _posed_buf(dev, lib.arah_query_posed_bytes(max(n, 1)))
+    _check(lib.arah_query_posed(C.byref(frame.handle), _ptr(occ), _ptr(x), C.c_int32(n), _ptr(sdf), _ptr(outs["points_hat"]),
+                                _ptr(outs["T"]), _ptr(outs["normal"]), _ptr(outs["weights"]), _ptr(state), _ptr(buf),
+                                C.c_size_t(buf.numel()), _stream()), "arah_query_posed")
+    res = {"state": state}
+    if "sdf" in want:
+        res["sdf"] = sdf
+    for k in z:
+        if k in want:
+            res[k] = outs[k].reshape(n, 4, 4) if k == "T" else outs[k]
+    return res
+
+
+@_guarded
+def sdf_grid_posed(frame, ws, n_side=256, occ=None, box=None, band=True):
+    """The posed SDF (metres) on the n_side^3 lattice of a world cube (arah_sdf_grid_posed): converged points take their sdf,
+    unconverged and skipped ones POSED_FILL.  box: (4,) device tensor (origin xyz, side) or None = the cube around the marked voxels
+    of `occ`.  band: evaluate only the points that share a lattice cell with a marked one.  -> (volume (n,n,n) [ix,iy,iz],
+    box (4,), counts (3,) int32 evaluated / converged / skipped), all on the device, no host round trip."""
+    lib = load_library()
+    dev, n_side = frame.device, int(n_side)
+    if box is None and occ is None:
+        raise ValueError("sdf_grid_posed: the default box needs the occupancy bitmap")
+    if band and occ is None:
+        raise ValueError("sdf_grid_posed: band=True needs the occupancy bitmap")
+    out = torch.empty(n_side, n_side, n_side, device=dev)
+    box_out = torch.empty(4, device=dev)
+    counts = torch.empty(3, dtype=torch.int32, device=dev)
+    bx = _f32(box).reshape(4) if box is not None else None
+    buf = _posed_buf(dev, lib.arah_sdf_grid_posed_bytes(n_side))
+    _check(lib.arah_sdf_grid_posed(C.byref(frame.handle), _ptr(occ), _ptr(bx), C.c_int32(n_side), C.c_int32(1 if band else 0), _ptr(out),
+                                   _ptr(box_out), _ptr(counts), _ptr(buf), C.c_size_t(buf.numel()), _stream()), "arah_sdf_grid_posed")
+    return out, box_out, counts
+
+
+def lattice_box(lo, hi, margin=0.0):
+    """The cube (origin xyz, side) around the axis-aligned box [lo, hi] grown by `margin` on every side, centred on it (host
+    helper of posed_mesh's `bounds`; the same rule k_posed_box_finish applies on the device)."""
+    lo = torch.as_tensor(lo, dtype=torch.float32).reshape(3) - margin
+    hi = torch.as_tensor(hi, dtype=torch.float32).reshape(3) + margin
+    side = torch.max(hi - lo)
+    return torch.cat([0.5 * (lo + hi) - 0.5 * side, side.reshape(1)])
+
+
+def posed_band(marked):
+    """Torch restatement of the lattice band of arah_sdf_grid_posed: marked (n,n,n) bool, lattice points in a marked voxel ->
+    the points that share a lattice cell with one of them (their 3x3x3 neighbourhood), the points the band evaluates."""
+    m = marked.float().reshape(1, 1, *marked.shape)
+    return torch.nn.functional.max_pool3d(m, 3, stride=1, padding=1)[0, 0] > 0
+
+
+def posed_value_rule(sdf, state):
+    """The lattice's value rule: converged points (state 1) keep their sdf, unconverged (0) and skipped (2) ones take POSED_FILL."""
+    return torch.where(state == 1, sdf, torch.full_like(sdf, POSED_FILL))
+
+
+def lattice_to_world(x, box):
+    """Coordinates in [-1,1]^3 of a lattice's marching cubes (arah_marching_cubes) -> world metres of the lattice `box`:
+    point i / (n - 1) of the cube's side sits at -1 + 2 i / (n - 1) in the mesh."""
+    return box[:3] + (x + 1.0) * (0.5 * box[3])
 
 
 _mc_tables = {}

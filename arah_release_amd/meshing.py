@@ -249,32 +249,11 @@ def canonical_mesh_outputs(frame, ws, inputs, rasterize_fn=None, n_side=256, ima
     no device -> host round trip at all -- the mesh lives in a fixed-capacity buffer whose tail is degenerate triangles, its
     size stays on the device (hip.marching_cubes, hip.skin_lbs_counted); want_tri=True trims the soup to its size, which
     waits for the GPU."""
-    from . import hip, training
+    from . import hip
     rasterize_fn = rasterize_fn or hip.rasterize
     with torch.no_grad():
-        n_dev = None
-        if tri is None:
-            # the lattice only where the level set can pass (csrc/tier.hpp: same triangles as the full lattice, ~6 % of its
-            # 16.8 M evaluations); ARAH_MESH_BAND=0: every lattice point, like sdf_meshing.py:44-57
-            if n_side >= 33 and os.environ.get("ARAH_MESH_BAND", "1") != "0":
-                sdf, _ = hip.sdf_grid_band(frame, ws, n_side)
-            else:
-                sdf = hip.sdf_grid(frame, ws, n_side)
-            st = _mc_state(sdf.device)
-            _mc_poll(st)
-            tri, n_dev = hip.marching_cubes(sdf, 0.0, st["cap"])                         # (cap,3,3) in [-1,1]^3, zero tail
-            ev, host = st["free"].pop() if st["free"] else (torch.cuda.Event(), torch.empty(1, dtype=torch.int32).pin_memory())
-            host.copy_(n_dev, non_blocking=True)
-            ev.record()
-            st["pending"].append((ev, host, st["cap"]))
+        tri, posed, n_dev = skinned_mesh(frame, ws, inputs, n_side, tri)
         F = tri.shape[0]
-        cmin, cmax, center = inputs["coord_min"][:1], inputs["coord_max"][:1], inputs["center"][:1]
-        x_hat = training.unnormalize_canonical_points(tri.reshape(1, -1, 3), cmin, cmax, center)[0]
-        if n_dev is None:
-            _, x_bar, _ = hip.skin_lbs(frame, ws, x_hat)
-        else:
-            x_bar = hip.skin_lbs_counted(frame, ws, x_hat, n_dev, per_item=3)            # zero beyond the mesh: degenerate
-        posed = (x_bar + inputs["trans"].reshape(1, 3)).reshape(F, 3, 3)
         cam_rot, cam_trans, K = inputs["cam_rot"][0], inputs["cam_trans"][0], inputs["intrinsics"][0]
         p2f = rasterize_fn(project_opencv(posed, cam_rot, cam_trans, K), image_size, image_size)
         n_posed = -face_normals(posed)                                                   # models/__init__.py:243
@@ -288,3 +267,40 @@ def canonical_mesh_outputs(frame, ws, inputs, rasterize_fn=None, n_side=256, ima
         if n_dev is not None:
             tri = tri[:min(int(n_dev.item()), F)]
     return out, tri
+
+
+def skinned_mesh(frame, ws, inputs, n_side=256, tri=None, cap=None):
+    """The canonical level set and its forward-skinned image, the reference's points_bar mesh (models/__init__.py:209-227):
+    -> (tri (F,3,3) in [-1,1]^3 normalised canonical, posed (F,3,3) world metres, n_dev (1,) int32 device count of the level set or
+    None when `tri` was given).  The soup lives in a fixed-capacity buffer whose tail is degenerate triangles (zeros in `tri`,
+    the translation in `posed`); no host round trip.  cap=None: the gen_cano_mesh branch's adaptive capacity (and its overflow
+    bookkeeping); an explicit cap leaves that state alone, the caller compares n_dev with it."""
+    from . import hip, training
+    with torch.no_grad():
+        n_dev = None
+        if tri is None:
+            # the lattice only where the level set can pass (csrc/tier.hpp: same triangles as the full lattice, ~6 % of its
+            # 16.8 M evaluations); ARAH_MESH_BAND=0: every lattice point, like sdf_meshing.py:44-57
+            if n_side >= 33 and os.environ.get("ARAH_MESH_BAND", "1") != "0":
+                sdf, _ = hip.sdf_grid_band(frame, ws, n_side)
+            else:
+                sdf = hip.sdf_grid(frame, ws, n_side)
+            if cap is not None:
+                tri, n_dev = hip.marching_cubes(sdf, 0.0, cap)
+            else:
+                st = _mc_state(sdf.device)
+                _mc_poll(st)
+                tri, n_dev = hip.marching_cubes(sdf, 0.0, st["cap"])                     # (cap,3,3) in [-1,1]^3, zero tail
+                ev, host = st["free"].pop() if st["free"] else (torch.cuda.Event(), torch.empty(1, dtype=torch.int32).pin_memory())
+                host.copy_(n_dev, non_blocking=True)
+                ev.record()
+                st["pending"].append((ev, host, st["cap"]))
+        F = tri.shape[0]
+        cmin, cmax, center = inputs["coord_min"][:1], inputs["coord_max"][:1], inputs["center"][:1]
+        x_hat = training.unnormalize_canonical_points(tri.reshape(1, -1, 3), cmin, cmax, center)[0]
+        if n_dev is None:
+            _, x_bar, _ = hip.skin_lbs(frame, ws, x_hat)
+        else:
+            x_bar = hip.skin_lbs_counted(frame, ws, x_hat, n_dev, per_item=3)            # zero beyond the mesh: degenerate
+        posed = (x_bar + inputs["trans"].reshape(1, 3)).reshape(F, 3, 3)
+    return tri, posed, n_dev

@@ -841,6 +841,100 @@ class MetaAvatarRender(nn.Module):
             raise ValueError("render_maps needs the eval forward: model.eval() and eval=True")
         return self._forward(inputs, gen_cano_mesh, True, True)
 
+    def _eval_decoder(self, decoder_input):
+        """The eval forward's hypernetwork call, through the model's captured graph."""
+        graphed = _GRAPHED.setdefault(self, {}).get("eval")
+        if graphed is None or graphed.decoder is not self.sdf_decoder:
+            graphed = _GRAPHED[self]["eval"] = _GraphedDecoder(self.sdf_decoder)
+        try:
+            return graphed(decoder_input) if not graphed.broken else self.sdf_decoder(decoder_input)
+        except RuntimeError as err:   # a capture the runtime refuses: the same launches, eagerly, from here on
+            import warnings
+            warnings.warn("hypernetwork graph capture failed (%s); this model runs the eager call from now on" % err)
+            graphed.broken = True
+            return self.sdf_decoder(decoder_input)
+
+    def _posed_frame(self, inputs, what):
+        """The packed frame of batch element 0 of `inputs`, emitted the way the eval forward emits it (hypernetwork through the
+        same graph cache, build_frame), without rendering anything: the frame of the posed queries."""
+        if self.training:
+            raise ValueError("%s is eval-only: call model.eval() first" % what)
+        rots, Jtrs = inputs["rots"], inputs["Jtrs"]
+        dev = rots.device
+        if dev.type != "cuda":
+            raise ValueError("%s runs on the HIP kernels: the inputs must live on the GPU" % what)
+        decoder_input = {"coords": torch.zeros(1, 1, 3, dtype=torch.float32, device=dev),
+                         "rots": rots[0].unsqueeze(0), "Jtrs": Jtrs[0].unsqueeze(0)}
+        if "geo_latent_code_idx" in inputs:
+            decoder_input["latent"] = self.latent(inputs["geo_latent_code_idx"])
+        if "latent_code_idx" in inputs["pose_cond"]:   # the colour network's pose vector, as the forward forms it (beta rides along)
+            inputs["pose_cond"]["latent_code"] = self.latent(inputs["pose_cond"]["latent_code_idx"])
+        with torch.no_grad():
+            if "latent" in decoder_input and os.environ.get("ARAH_HYPERNET_GRAPH", "1") != "0":
+                out = self._eval_decoder(decoder_input)
+            else:
+                out = self.sdf_decoder(decoder_input)
+            idhr = self.idhr_network
+            frame = build_frame(out["decoder"], self.skinning_model, idhr.rendering_network, idhr.deviation_network,
+                                inputs["pose_cond"], inputs["smpl_verts"], inputs["skinning_weights"], inputs["bone_transforms"],
+                                inputs["trans"], inputs["coord_min"], inputs["coord_max"], inputs["center"],
+                                precision=idhr._precision if idhr._precision is not None else idhr.precision)
+        return frame, idhr.ray_tracer.workspace(dev)
+
+    def query_posed(self, inputs, points, certify=False):
+        """The posed body of frame `inputs` at world points (P,3) or (B,P,3) (include/arah_hip.h: arah_query_posed): per point what
+        the eval forward computes for a depth sample there.  -> dict of sdf (..., ) metres, normal (..., 3) posed unit normal,
+        points_hat (..., 3) normalised canonical correspondence, weights (..., 24) skinning weights at it, converged (...) bool.
+        certify=True: points the frame's occupancy bitmap certifies outside the posed fat body are not evaluated -- sdf =
+        hip.POSED_FILL, converged False, zeros elsewhere; the evaluated points are bit-equal either way.  Eval only."""
+        frame, ws = self._posed_frame(inputs, "query_posed")
+        shape = points.shape[:-1]
+        if points.shape[-1] != 3:
+            raise ValueError("points must be (P, 3) or (B, P, 3)")
+        with torch.no_grad():
+            occ = ws.occupancy(frame) if certify else None
+            r = hip.query_posed(frame, ws, points.reshape(-1, 3), occ=occ,
+                                want=("sdf", "points_hat", "normal", "weights"))
+        return {"sdf": r["sdf"].reshape(shape), "normal": r["normal"].reshape(*shape, 3),
+                "points_hat": r["points_hat"].reshape(*shape, 3), "weights": r["weights"].reshape(*shape, 24),
+                "converged": (r["state"] == 1).reshape(shape), "state": r["state"].reshape(shape)}
+
+    def posed_mesh(self, inputs, n_side=256, method="lattice", bounds=None):
+        """A triangle soup of the posed body of frame `inputs` in world metres.  method="lattice": the zero level set of the posed
+        SDF (hip.sdf_grid_posed, only the band around the occupancy bitmap's marked voxels unless ARAH_POSED_MESH_BAND=0, then
+        hip.marching_cubes) -- the surface the renderer sees, self-contact included.  method="skinned": the reference's points_bar
+        mesh (models/__init__.py:209-227), the canonical level set skinned forward.  bounds: (lo, hi) world box of the lattice
+        (default: the marked voxels' box plus one voxel).  -> dict of tris (F,3,3) trimmed to the level set's size (the one host
+        synchronisation), n_tris, box (4,) origin xyz + side of the lattice (None for "skinned") and counts (3,) evaluated /
+        converged / skipped lattice points.  The triangle buffer is sized from the device count and the extraction re-run when
+        it was too small: nothing is truncated.  Eval only."""
+        from . import meshing
+        frame, ws = self._posed_frame(inputs, "posed_mesh")
+        with torch.no_grad():
+            if method == "skinned":
+                cap = meshing.MC_DEFAULT_CAP
+                _, posed, n_dev = meshing.skinned_mesh(frame, ws, inputs, n_side, cap=cap)
+                n = int(n_dev.item())
+                if n > cap:   # too small for this level set: the exact size, once more
+                    cap = n
+                    _, posed, n_dev = meshing.skinned_mesh(frame, ws, inputs, n_side, cap=cap)
+                    n = int(n_dev.item())
+                return {"tris": posed[:n], "n_tris": n, "box": None, "counts": None}
+            if method != "lattice":
+                raise ValueError("method must be 'lattice' or 'skinned', got %r" % (method,))
+            occ = ws.occupancy(frame)
+            box = hip.lattice_box(*bounds).to(occ.device) if bounds is not None else None
+            band = os.environ.get("ARAH_POSED_MESH_BAND", "1") != "0"
+            sdf, box, counts = hip.sdf_grid_posed(frame, ws, n_side, occ=occ, box=box, band=band)
+            cap = meshing.MC_DEFAULT_CAP
+            tris, n_dev = hip.marching_cubes(sdf, 0.0, cap)
+            n = int(n_dev.item())
+            if n > cap:   # too small for this level set: the exact size, once more
+                cap = n
+                tris, n_dev = hip.marching_cubes(sdf, 0.0, cap)
+                n = int(n_dev.item())
+            return {"tris": hip.lattice_to_world(tris[:n], box), "n_tris": n, "box": box, "counts": counts}
+
     def _forward(self, inputs, gen_cano_mesh, eval, render_maps):
         rots, Jtrs = inputs["rots"], inputs["Jtrs"]
         B, dev = rots.size(0), rots.device
@@ -870,16 +964,7 @@ class MetaAvatarRender(nn.Module):
                                          % self.nv_noise_type)
         if (eval and dev.type == "cuda" and not torch.is_grad_enabled() and "rots_noise" not in decoder_input
                 and "latent" in decoder_input and os.environ.get("ARAH_HYPERNET_GRAPH", "1") != "0"):
-            graphed = _GRAPHED.setdefault(self, {}).get("eval")
-            if graphed is None or graphed.decoder is not self.sdf_decoder:
-                graphed = _GRAPHED[self]["eval"] = _GraphedDecoder(self.sdf_decoder)
-            try:
-                out = graphed(decoder_input) if not graphed.broken else self.sdf_decoder(decoder_input)
-            except RuntimeError as err:   # a capture the runtime refuses: the same launches, eagerly, from here on
-                import warnings
-                warnings.warn("hypernetwork graph capture failed (%s); this model runs the eager call from now on" % err)
-                graphed.broken = True
-                out = self.sdf_decoder(decoder_input)
+            out = self._eval_decoder(decoder_input)
         elif (not eval and dev.type == "cuda" and torch.is_grad_enabled() and "latent" in decoder_input
               and not rots.requires_grad and not Jtrs.requires_grad and decoder_input["latent"].requires_grad
               and os.environ.get("ARAH_TRAIN_HYPERNET_GRAPH", "0") == "1"):

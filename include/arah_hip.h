@@ -35,6 +35,10 @@
  *                           renderer/implicit_differentiable_renderer.py:291-361, diff_operators.py:39-50
  *   arah_gram_skinny        the matmul backward of autograd for the 1- / 3-row heads and the K = 3 first layer
  *                           (weight gradients summed over ~1e5 samples)
+ *   arah_query_posed        inv_transform_points_opt + the SDF evaluation of the depth samples, on arbitrary posed points
+ *                           ray_tracing.py:403-461, implicit_differentiable_renderer.py:336-359
+ *   arah_sdf_grid_posed     the same on a lattice of posed space (no reference counterpart: the reference meshes the canonical
+ *                           lattice only and skins that mesh forward, models/__init__.py:209-227)
  *   arah_mesh_query         check_mesh_contains + igl.point_mesh_squared_distance + igl.barycentric_coordinates_tri
  *                           im2mesh/utils/libmesh/inside_mesh.py:4-160, im2mesh/data/zju_mocap.py:466-529
  *
@@ -539,6 +543,41 @@ int arah_occupancy_clear_box(void* occ_buf, const float* h_lo, const float* h_hi
  * z [N,S], pts [N,S,3] normalised canonical, T [N,S,16], mask [N,S], shaded [N,S,4] = {rgb, density}, state [N,S] */
 int arah_debug_samples(void* workspace, size_t workspace_bytes, int32_t n_rays, int32_t n_steps, float* z, float* pts,
                        float* T, uint8_t* mask, float* shaded, uint8_t* state, void* stream);
+
+/* ---- posed-space queries (csrc/posed.hpp) ---------------------------------------------------------------------------------- */
+/* The value of the lattice / the sdf of a certified point: any positive value would do (marching cubes at level 0 only reads signs
+ * there); metres. */
+#define ARAH_POSED_FILL 1.0f
+/* Per world-space point, what the eval forward computes for a depth sample at that position: nearest SMPL vertex + inverse LBS
+ * (ray_tracing.py:408-421; exact for every point: outside the nearest-vertex grid's box the search walks every cluster), Broyden
+ * on LBS(x_hat) - (x - trans) with the solver ARAH_CANON_KERNEL selects (wave | tile | wave_l2, read once per process), the SDF
+ * trunk at the normalised solution.  pts [P,3] world metres (finite) ->
+ *   sdf [P]          metres, sdf_norm / 2 * 1.1 * (coord_max - coord_min)   (implicit_differentiable_renderer.py:359)
+ *   x_hat_norm [P,3] the normalised canonical solution (or NULL)
+ *   T [P,16]         the blended forward transform the solver returns (or NULL)
+ *   normal [P,3]     normalize(T[:3,:3] . d sdf / d x_norm), the posed normal of arah_render_maps (or NULL: no gradient sweep)
+ *   weights [P,24]   the skinning MLP's weights at x_hat (or NULL)
+ *   state [P]        0: not converged (values of the solver's best iterate), 1: converged, 2: skipped -- occ_buf (arah_prepare_occupancy
+ *                    of THIS frame, or NULL) certifies that the point is outside the posed fat body (sigma = +0 for a sample there):
+ *                    only sdf is written, +ARAH_POSED_FILL, the other outputs are left untouched.
+ * Every field of an evaluated point is bit-equal whether or not occ_buf is passed, whatever the list's length and the point's
+ * position in it.  buf: arah_query_posed_bytes(n_pts) bytes (256-byte aligned); long lists run in passes of a fixed size, so the
+ * buffer stays below ~130 MB.  No host synchronisation. */
+size_t arah_query_posed_bytes(int32_t n_pts);
+int arah_query_posed(const ArahFrame* h_frame, const void* occ_buf, const float* pts, int32_t n_pts, float* sdf, float* x_hat_norm,
+                     float* T, float* normal, float* weights, uint8_t* state, void* buf, size_t buf_bytes, void* stream);
+/* The posed SDF on the n^3 lattice of a world-space cube: point (ix, iy, iz) at origin + (i / (n - 1)) side, sdf[(ix*n + iy)*n + iz]
+ * in metres (arah_marching_cubes' output maps to world coordinates by x_world = origin + (x + 1) / 2 * side).
+ * box: DEVICE [4] origin xyz, side; NULL = the cube around the bounding box of occ_buf's MARKED voxels plus one voxel (the
+ * whole bitmap box if nothing is marked or the bitmap is invalid).  box_out: DEVICE [4], the cube used.
+ * Value rule: converged points take their sdf, unconverged and skipped points +ARAH_POSED_FILL.
+ * band = 1 (needs occ_buf): a point is evaluated only when it shares a lattice cell with a lattice point in a marked voxel (outside
+ * the bitmap's box counts as marked); the others are skipped.  When the certificate holds, every corner of every cell whose values
+ * change sign is evaluated, so arah_marching_cubes gives band = 0's triangle soup bit for bit.
+ * counts: DEVICE [3] int32 evaluated, converged, skipped.  buf: arah_sdf_grid_posed_bytes(n_side) bytes; 2 <= n_side <= 1024. */
+size_t arah_sdf_grid_posed_bytes(int32_t n_side);
+int arah_sdf_grid_posed(const ArahFrame* h_frame, const void* occ_buf, const float* box, int32_t n_side, int32_t band, float* sdf,
+                        float* box_out, int32_t* counts, void* buf, size_t buf_bytes, void* stream);
 
 /* name of the dominant kernel, for profilers */
 const char* arah_dominant_kernel(void);
