@@ -247,7 +247,7 @@ __global__ void k_fold_film(const float* __restrict__ freq, const float* __restr
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= 6 * 256) return;
     const int k = i >> 8;
-    const double c = kFilmScale;   // revolutions (hardware sine) or half-revolutions (-DARAH_POLY_SINE), see mlp.hpp
+    const double c = kFilmScale;   // revolutions (the hardware sine), see mlp.hpp
     const double f = freq[i];
     fw[i] = (float)(f * c);
     pw[i] = (float)((f * (double)bias[i] + (double)phase[i]) * c);
@@ -1203,8 +1203,6 @@ __global__ __launch_bounds__(kKnnThreads) void k_nearest_invlbs(FrameDev fr, Knn
 // ------------------------------------------------------------------------------------------
 // shared helpers of the MFMA kernels
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ int tile_count(int n) { return (n + kTile - 1) / kTile; }
-
 // wave-0 append of kept ids to a device list
 __device__ __forceinline__ void append_ids(bool keep, int id, int* list, int* count) {
     const unsigned long long m = __ballot(keep);
@@ -2297,9 +2295,6 @@ __global__ __launch_bounds__(kThreads, NT > 4 ? 2 : 4) void k_density(FrameDev f
     int* ids = reinterpret_cast<int*>(outv + TW * 4);    // [TW]
     float* actA = reinterpret_cast<float*>(ids + TW);    // [TW][kSdfLd]
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-#ifdef ARAH_PRIO_WAVES   // A/B (profiles/r05_ab_setprio.txt): static issue priority for one half of the workgroup's waves
-    if ((wave >= kWaves / 2) == (ARAH_PRIO_WAVES == 1)) __builtin_amdgcn_s_setprio(1);
-#endif
     const int n = *count;
     const float scale = sdf_scale(bc);
     const float inv_beta = 1.0f / fminf(fmaxf(fabsf(load_beta(fr)), 1e-6f), 1e6f);
@@ -2313,20 +2308,8 @@ __global__ __launch_bounds__(kThreads, NT > 4 ? 2 : 4) void k_density(FrameDev f
             reinterpret_cast<f32x4*>(xin)[tid] = x;
         }
         __syncthreads();
-        if constexpr (SPLIT && NT == 8) {
-#ifdef ARAH_DENSITY_PP
-            // the two 64-point halves a phase apart (mlp.hpp: sdf_trunk_pp).  Measured on the MI355X, same box, alternating
-            // runs: 12.94-12.98 ms per launch against 12.91-13.08 without -- the pass is not bound by the serialisation of
-            // GEMM and epilogue phases; the plain trunk stays the default, this is the reproducer
-            sdf_trunk_pp<4>(fr.sdf, xin, actA, kSdfLd, wave, lane);
-#else
-            f32x4 dlast[kSdfMT][NT];
-            sdf_trunk<false, NT, SPLIT>(fr.sdf, xin, actA, kSdfLd, nullptr, dlast, wave, lane);
-#endif
-        } else {
-            f32x4 dlast[kSdfMT][NT];
-            sdf_trunk<false, NT, SPLIT>(fr.sdf, xin, actA, kSdfLd, nullptr, dlast, wave, lane);
-        }
+        f32x4 dlast[kSdfMT][NT];
+        sdf_trunk<false, NT, SPLIT>(fr.sdf, xin, actA, kSdfLd, nullptr, dlast, wave, lane);
         sdf_head<SPLIT>(fr.sdf, actA, kSdfLd, outv, 4, tid, TW);
         __syncthreads();
         if (tid == 0) {
@@ -2381,10 +2364,6 @@ __global__ __launch_bounds__(kThreads, 2) void k_sdf_lattice(FrameDev fr, int gr
         __syncthreads();
     }
 }
-
-#ifdef ARAH_REG_TRUNK   // round 5 experiment, not in the shipped library: the density pass on point-owning waves
-#include "regtrunk.hpp"
-#endif
 
 // ------------------------------------------------------------------------------------------
 // loop D: SDF value + normal (reverse sweep) + colour MLP + VolSDF density per valid sample
@@ -2870,17 +2849,11 @@ Workspace carve(void* base, int n_rays, int n_steps) {
 // caller may want to change per call (engines, solver, events, shading mode) travels in ArahSampling / ArahFrame.
 struct Knobs {
     int max_grid;        // ARAH_MAX_GRID          cap of the persistent grids (<= kMaxGrid, the spill slab is sized for it)
-    bool split_solo;     // ARAH_SPLIT_SOLO=1      every split-engine workgroup owns its CU (diagnostic, see split_lds)
     int knn_group;       // ARAH_KNN_GROUP         sixteen-lane search for the ray lists
     int knn_below[3];    // ARAH_KNN_WAVE_{POINTS,RAYS,SAMPLES}  list lengths below which a wave per query is used
     int joint_bulk;      // ARAH_JOINT_BULK_ITERS  loop B iterations launched wide before the finisher
     int trace_bulk;      // ARAH_TRACE_BULK_STEPS  loop A steps launched wide before the finisher
     int trace_small;     // ARAH_TRACE_SMALL       ray lists up to this length go to the finisher at once
-    bool density_wide;   // ARAH_DENSITY_TILE=128  128-point tiles in the density pass
-    bool density_reg;    // ARAH_DENSITY_REG=1     the density pass on the point-owning trunk (regtrunk.hpp)
-    int canon_lds_min;   // ARAH_CANON_LDS_MIN     loop C's point-owning-wave kernel asks for at least this much LDS (bytes): with
-                         //                        more than half of the CU's 160 KB a half-size build (-DCW_WAVES=4) owns one slot per CU
-    int canon_wg_per_cu; // ARAH_CANON_WG_PER_CU   resident workgroups of that kernel per CU (grid = this x CUs; 1)
     bool train_b3;       // ARAH_TRAIN_ENGINE!=fp32  bf16 x 3 / f16 split training kernels on split frames
     int canon_tier_wgs;  // ARAH_CANON_TIER_WGS    workgroups of loop C's solver on the tiered forward's lists (0 = one per CU)
     int posed_canon;     // ARAH_CANON_KERNEL      wave | tile | wave_l2: loop C's solver of arah_query_posed / arah_sdf_grid_posed, whose
@@ -2895,7 +2868,6 @@ inline const Knobs& knobs() {
         Knobs v;
         const int g = env_int("ARAH_MAX_GRID", kMaxGrid);
         v.max_grid = g >= 1 && g <= kMaxGrid ? g : kMaxGrid;
-        v.split_solo = env_int("ARAH_SPLIT_SOLO", 0) == 1;
         v.knn_group = env_int("ARAH_KNN_GROUP", 1);
         v.knn_below[0] = env_int("ARAH_KNN_WAVE_POINTS", 4096);
         v.knn_below[1] = env_int("ARAH_KNN_WAVE_RAYS", v.knn_group ? (1 << 30) : 32768);
@@ -2903,10 +2875,6 @@ inline const Knobs& knobs() {
         v.joint_bulk = max(1, min(kBroydenSteps + 1, env_int("ARAH_JOINT_BULK_ITERS", 3)));
         v.trace_bulk = max(0, min(kSphereIters, env_int("ARAH_TRACE_BULK_STEPS", 24)));
         v.trace_small = env_int("ARAH_TRACE_SMALL", 4096);
-        v.density_wide = env_int("ARAH_DENSITY_TILE", 128) == 128;
-        v.density_reg = env_int("ARAH_DENSITY_REG", 0) == 1;
-        v.canon_lds_min = max(0, min((int)kLdsCanonWave, env_int("ARAH_CANON_LDS_MIN", 0)));
-        v.canon_wg_per_cu = max(1, min(4, env_int("ARAH_CANON_WG_PER_CU", 1)));
         v.canon_tier_wgs = max(0, env_int("ARAH_CANON_TIER_WGS", 0));
         const char* ck = getenv("ARAH_CANON_KERNEL");
         v.posed_canon = !ck ? ARAH_CANON_KERNEL_WAVE : strcmp(ck, "tile") == 0 ? ARAH_CANON_KERNEL_TILE
@@ -2963,17 +2931,9 @@ constexpr size_t lds_color() {
 }
 
 // Launch KS when the frame was prepared for the split engine, KE (exact fp32) otherwise.
-// ARAH_SPLIT_SOLO=1 makes every split-engine workgroup own its CU (asks for more than half of the 160 KB LDS):
-// the workaround that was in place until the irreproducibility of co-resident workgroups was traced to the packed
-// K = 3 input layer (no_pack in mlp.hpp); kept as a diagnostic switch.
-inline size_t split_lds(size_t lds) {
-    constexpr size_t kSolo = 84 * 1024;
-    return knobs().split_solo && lds < kSolo ? kSolo : lds;
-}
-constexpr size_t kLdsSplitSolo = 84 * 1024;
 #define LAUNCH_ENGINE(split, KS, KE, GRID, BLOCK, LDS, ...)                              \
     do {                                                                                 \
-        if (split) hipLaunchKernelGGL(KS, GRID, BLOCK, split_lds(LDS), __VA_ARGS__);     \
+        if (split) hipLaunchKernelGGL(KS, GRID, BLOCK, LDS, __VA_ARGS__);                \
         else hipLaunchKernelGGL(KE, GRID, BLOCK, LDS, __VA_ARGS__);                      \
     } while (0)
 
@@ -3010,30 +2970,27 @@ int setup_attributes_once() {
     allow_lds(k_nearest_invlbs<SRC_RAYS>, kLdsKnn, failed);
     allow_lds(k_nearest_invlbs<SRC_SAMPLES>, kLdsKnn, failed);
     allow_lds(k_sdf_eval<false, false>, kLdsSdfFwd, failed);
-    allow_lds(k_sdf_eval<false, true>, kLdsSplitSolo, failed);
+    allow_lds(k_sdf_eval<false, true>, kLdsSdfFwd, failed);
     allow_lds(k_sdf_eval<true, false>, kLdsSdfGrad, failed);
     allow_lds(k_sdf_eval<true, true>, kLdsSdfGrad, failed);
     allow_lds(k_sdf_march<false>, kLdsSdfFwd, failed);
-    allow_lds(k_sdf_march<true>, kLdsSplitSolo, failed);
+    allow_lds(k_sdf_march<true>, kLdsSdfFwd, failed);
     allow_lds(k_density<false>, kLdsSdfFwd, failed);
-    allow_lds(k_density<true>, kLdsSplitSolo, failed);
+    allow_lds(k_density<true>, kLdsSdfFwd, failed);
     allow_lds(k_density<true, 8>, kLdsDensityWide, failed);
-#ifdef ARAH_REG_TRUNK
-    allow_lds(k_density_reg, kLdsRegTrunk, failed);
-#endif
     allow_lds(k_sdf_lattice, kLdsDensityWide, failed);
     allow_lds(k_skin_eval, kLdsSkin, failed);
     allow_lds(k_skin_jac, kLdsSkin, failed);
     allow_lds(k_canon_solve<false>, kLdsCanonSolve, failed);
-    allow_lds(k_canon_solve<true>, kLdsSplitSolo, failed);
+    allow_lds(k_canon_solve<true>, kLdsCanonSolve, failed);
     allow_lds((k_canon_wave<true, false>), kLdsCanonWave, failed);
     allow_lds((k_canon_wave<true, true>), kLdsCanonWave, failed);
     allow_lds((k_canon_wave<false, false>), kLdsCanonWave, failed);
     allow_lds((k_canon_wave<false, true>), kLdsCanonWave, failed);
     allow_lds(k_joint_iter<true, false>, kLdsJoint, failed);
-    allow_lds(k_joint_iter<true, true>, kLdsSplitSolo, failed);
+    allow_lds(k_joint_iter<true, true>, kLdsJoint, failed);
     allow_lds(k_joint_iter<false, false>, kLdsJoint, failed);
-    allow_lds(k_joint_iter<false, true>, kLdsSplitSolo, failed);
+    allow_lds(k_joint_iter<false, true>, kLdsJoint, failed);
     allow_lds(k_trace_finish<true>, kLdsTraceFinish, failed);
     allow_lds(k_trace_finish<false>, kLdsTraceFinish, failed);
     allow_lds(k_joint_finish<true>, kLdsJointFinish, failed);
@@ -3740,7 +3697,7 @@ int arah_counters_reset(void* workspace, void* stream) {
                                                                                                            : ARAH_E_LAUNCH;
 }
 
-#if defined(ARAH_CLOCKS) || defined(RT_CLOCKS)
+#ifdef ARAH_CLOCKS
 // instrumented builds only (tools/phase_clocks.py): the 2 x 8 x 16 phase clocks (loop C, k_shade) behind the counters;
 // syncs the stream
 int arah_debug_clocks(const void* workspace, unsigned long long* h_out, void* stream) {
@@ -3794,7 +3751,7 @@ int arah_sdf_grid(const ArahFrame* f, int32_t n_side, float* sdf, void* workspac
     const FrameDev fd = to_dev(*f);
     const long long n = (long long)n_side * n_side * n_side;
     if (n > 0x7fffffffLL) return ARAH_E_BADARG;
-    if (fd.split && knobs().density_wide && n >= 128ll * 1024)   // long lattices on the split engine: 128-point tiles, like the density pass
+    if (fd.split && n >= 128ll * 1024)   // long lattices on the split engine: 128-point tiles, like the density pass
         hipLaunchKernelGGL(k_sdf_lattice, dim3(min(num_cus(), grid_for(n, 128))), dim3(kThreads), kLdsDensityWide, s, fd, (int)n_side,
                            (int)n, sdf, &w.ctr->n_sdf_fwd);
     else
@@ -3962,7 +3919,7 @@ static int run_broyden3(const FrameDev& fd, Workspace& w, const float* tgt, Cano
     unsigned long long* const clk_arg = w.ctr->clk;
     if (fd.split && mode != 0) {
         long long gw = (max_pts + kCwWaves * kCwSlots - 1) / (kCwWaves * kCwSlots);
-        int cus = num_cus() * knobs().canon_wg_per_cu;
+        int cus = num_cus();
         if (list_arg && knobs().canon_tier_wgs > 0) cus = min(cus, knobs().canon_tier_wgs);   // the tiers' short lists (see Knobs)
         if (gw > cus) gw = cus;
         if (gw < 1) gw = 1;
@@ -3976,7 +3933,7 @@ static int run_broyden3(const FrameDev& fd, Workspace& w, const float* tgt, Cano
                                (const int*)&cnt[0], &cnt[1], outp, &w.ctr->n_skin_fwd, &w.ctr->n_canon,
                                &w.ctr->n_split_nonfinite, clk_arg);
         } else {
-            const size_t lds_l2 = max(kLdsCanonWave - kCwHiBytes, (size_t)knobs().canon_lds_min);
+            const size_t lds_l2 = kLdsCanonWave - kCwHiBytes;
             hipLaunchKernelGGL((k_canon_wave<false, false>), dim3((int)gw), dim3(kCwThreads), lds_l2, s, fd,
                                list, (const int*)&cnt[0], &cnt[1], outp, &w.ctr->n_skin_fwd,
                                &w.ctr->n_canon, &w.ctr->n_split_nonfinite, clk_arg);
@@ -4187,31 +4144,13 @@ int arah_sample_canonicalize(const ArahFrame* f, const ArahSampling* cfg, const 
                        rand_far, z, pts, T, mask, reinterpret_cast<hipStream_t>(stream));
 }
 
-#ifdef ARAH_REG_TRUNK
-// phase clocks of the point-owning trunk (instrumented builds, -DRT_CLOCKS: tools/probes/density_probe.py clocks)
-static unsigned long long* rt_clk_of(const Workspace& w) {
-#ifdef RT_CLOCKS
-    return w.ctr->clk;
-#else
-    (void)w;
-    return nullptr;
-#endif
-}
-#endif
-
 // the density pre-pass of lazy shading over list[0 .. *count): sigma of every listed sample -> w.shaded, the samples with
 // sigma > 0 appended to next_list
 static void launch_density(const FrameDev& fd, Workspace& w, const float* pts, long long Q, const int* list, const int* count,
                            int* next_list, int* next_count, hipStream_t s) {
     const int g = grid_for(Q, kTile);
-    // long lists on the split engine: 128-point tiles, one workgroup per CU (ARAH_DENSITY_TILE=64 keeps the 64-point kernel)
-#ifdef ARAH_REG_TRUNK
-    if (fd.split && knobs().density_reg && Q >= 128ll * 1024)
-        hipLaunchKernelGGL(k_density_reg, dim3(min(num_cus(), grid_for(Q, kRtTile))), dim3(kRtThreads), kLdsRegTrunk, s, fd,
-                           pts, list, count, w.shaded, next_list, next_count, &w.ctr->n_sdf_fwd, &w.ctr->n_density, rt_clk_of(w));
-    else
-#endif
-    if (fd.split && knobs().density_wide && Q >= 128ll * 1024)
+    // long lists on the split engine: 128-point tiles, one workgroup per CU
+    if (fd.split && Q >= 128ll * 1024)
         hipLaunchKernelGGL((k_density<true, 8>), dim3(min(num_cus(), grid_for(Q, 128))), dim3(kThreads), kLdsDensityWide, s, fd,
                            pts, list, count, w.shaded, next_list, next_count, &w.ctr->n_sdf_fwd, &w.ctr->n_density);
     else
@@ -4261,11 +4200,11 @@ static void launch_shade(const ArahFrame* f, const ArahSampling* cfg, Workspace&
     const B3Nets b3 = b3_of(*f);
     if (fd.split && shade_b3(cfg->shade_engine)) {
         if (f->col_mode == ARAH_COLOR_IDR)
-            hipLaunchKernelGGL((k_shade<true, true, true, MAPS>), dim3(g), dim3(kThreads), split_lds(lds_shade_b3<true>()), s, fd,
+            hipLaunchKernelGGL((k_shade<true, true, true, MAPS>), dim3(g), dim3(kThreads), lds_shade_b3<true>(), s, fd,
                                S, cfg->cano_view_dirs, dirs, pts, T, slist, scount, 0, w.shaded, w.spill, &w.ctr->n_sdf_fwd,
                                &w.ctr->n_sdf_grad, &w.ctr->n_col, b3, nrm);
         else
-            hipLaunchKernelGGL((k_shade<false, true, true, MAPS>), dim3(g), dim3(kThreads), split_lds(lds_shade_b3<false>()), s, fd,
+            hipLaunchKernelGGL((k_shade<false, true, true, MAPS>), dim3(g), dim3(kThreads), lds_shade_b3<false>(), s, fd,
                                S, cfg->cano_view_dirs, dirs, pts, T, slist, scount, 0, w.shaded, w.spill, &w.ctr->n_sdf_fwd,
                                &w.ctr->n_sdf_grad, &w.ctr->n_col, b3, nrm);
     } else if (f->col_mode == ARAH_COLOR_IDR)
@@ -4320,11 +4259,11 @@ int arah_shade_points(const ArahFrame* f, const float* x_norm, const float* T, c
     // the kernels of shade_impl, one sample per "ray" (S = 1: dirs are per point), no list
     if (fd.split && shade_b3(shade_engine)) {
         if (f->col_mode == ARAH_COLOR_IDR)
-            hipLaunchKernelGGL((k_shade<true, true, true>), dim3(g), dim3(kThreads), split_lds(lds_shade_b3<true>()), s, fd, 1,
+            hipLaunchKernelGGL((k_shade<true, true, true>), dim3(g), dim3(kThreads), lds_shade_b3<true>(), s, fd, 1,
                                cano_view_dirs, dirs, x_norm, T, (const int*)nullptr, (const int*)nullptr, n, out, w.spill,
                                &w.ctr->n_sdf_fwd, &w.ctr->n_sdf_grad, &w.ctr->n_col, b3, dbg);
         else
-            hipLaunchKernelGGL((k_shade<false, true, true>), dim3(g), dim3(kThreads), split_lds(lds_shade_b3<false>()), s, fd, 1,
+            hipLaunchKernelGGL((k_shade<false, true, true>), dim3(g), dim3(kThreads), lds_shade_b3<false>(), s, fd, 1,
                                cano_view_dirs, dirs, x_norm, T, (const int*)nullptr, (const int*)nullptr, n, out, w.spill,
                                &w.ctr->n_sdf_fwd, &w.ctr->n_sdf_grad, &w.ctr->n_col, b3, dbg);
     } else if (f->col_mode == ARAH_COLOR_IDR)

@@ -36,15 +36,8 @@
 // by rounding only.
 #pragma once
 
-#ifndef CW_NT
-#define CW_NT 2
-#endif
-constexpr int kCwNT = CW_NT;                    // N-tiles (16 points each) per wave
-static_assert(kCwNT == 2, "the only validated geometry (one N-tile per wave gave wrong roots on the MI355X and was slower)");
-#ifndef CW_WAVES
-#define CW_WAVES 8
-#endif
-constexpr int kCwWaves = CW_WAVES;
+constexpr int kCwNT = 2;   // N-tiles (16 points each) per wave (one N-tile per wave gave wrong roots on the MI355X and was slower)
+constexpr int kCwWaves = 8;
 constexpr int kCwThreads = kCwWaves * 64;
 constexpr int kCwSlots = 16 * kCwNT;            // points per wave
 constexpr int kCwHiBytes = (3 * 32 + 8) * 1024; // hi fragments: 3 x (8 M-tiles x 4 chunks) + 2 x 4, 1 KB each
@@ -86,22 +79,12 @@ __host__ __device__ constexpr CwParts cw_parts(int NT, int L, int kc, int mp) {
     if (n >= 4) return mp == 3 ? CwParts{2 * (n / 4), n - 2 * (n / 4)} : CwParts{(mp - 1) * (n / 4), n / 4};
     return mp == 3 ? CwParts{0, 0} : CwParts{mp - 1, 1};
 }
-#ifndef CW_LO_DIST
-#define CW_LO_DIST 2    // MFMA steps the lo fragments (L2) are requested ahead of their use
-#endif
-#ifndef CW_HI_DIST
-#define CW_HI_DIST 0    // the same for the hi fragments (LDS): requested ahead they cost more in registers than they hide
-#endif
-#ifndef CW_CI_MODE
-#define CW_CI_MODE 0    // bisecting aid: 0 start values LDS -> accumulator, 1 zero start + bias added in the epilogue, 2 as 0, one load per N-tile
-#endif
-#ifndef CW_PIN_MASK
-#define CW_PIN_MASK 0x040f
-#endif
-constexpr int kCwLoDist = CW_LO_DIST, kCwHiDist = CW_HI_DIST;
+constexpr int kCwLoDist = 2;   // MFMA steps the lo fragments (L2) are requested ahead of their use
+constexpr int kCwHiDist = 0;   // the same for the hi fragments (LDS): requested ahead they cost more in registers than they hide
+constexpr int kCwPinMask = 0x040f;
 
 template <bool HI_LDS, bool SCALED>
-__global__ __launch_bounds__(kCwThreads, kCwWaves >= 8 ? kCwWaves / 4 : 2) void k_canon_wave(FrameDev fr, const int* __restrict__ list, const int* count,
+__global__ __launch_bounds__(kCwThreads, 2) void k_canon_wave(FrameDev fr, const int* __restrict__ list, const int* count,
                                                               int* queue_head, CanonOut outp, unsigned long long* ctr,
                                                               unsigned long long* ctr_canon,
                                                               unsigned long long* ctr_bad, unsigned long long* clk_out) {
@@ -117,9 +100,6 @@ __global__ __launch_bounds__(kCwThreads, kCwWaves >= 8 ? kCwWaves / 4 : 2) void 
 #endif
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int j = lane & 15, g = lane >> 4;
-#ifdef ARAH_PRIO_WAVES   // A/B (profiles/r05_ab_setprio.txt): static issue priority for one half of the workgroup's waves
-    if ((wave >= kCwWaves / 2) == (ARAH_PRIO_WAVES == 1)) __builtin_amdgcn_s_setprio(1);
-#endif
     // small operands first: their absolute LDS offsets stay below 64 KB, i.e. inside the offset field of the DS
     // instructions (one address register per lane pattern, not one per constant for the compiler to hoist and spill)
     float* w0c = smem;                   // kCwW0T: the input layer's A operands by row (32 bytes each)
@@ -356,12 +336,9 @@ __global__ __launch_bounds__(kCwThreads, kCwWaves >= 8 ? kCwWaves / 4 : 2) void 
             constexpr int t = p >> 1, h = p & 1;
             constexpr int mt = 2 * q + h;
             float v[4];
-            f32x4 bq = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (CW_CI_MODE == 1) bq = *reinterpret_cast<const f32x4*>(binit + L * 128 + mt * 16 + 4 * g);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float a = acc[L & 1][mt][t][r];
-                if constexpr (CW_CI_MODE == 1) a += bq[r];
                 if constexpr (SCALED && L > 0) a *= L == 1 ? inv1 : (L == 2 ? inv2 : inv3);   // powers of two: exact
                 v[r] = softplus_shift(a, inf);
                 if constexpr (SCALED) v[r] *= L == 0 ? as0 : (L == 1 ? as1 : (L == 2 ? as2 : as3));
@@ -399,17 +376,8 @@ __global__ __launch_bounds__(kCwThreads, kCwWaves >= 8 ? kCwWaves / 4 : 2) void 
 #pragma unroll
                 for (int h = 0; h < 2; ++h)
 #pragma unroll
-                    for (int t = 0; t < NT; ++t) {
-                        if constexpr (CW_CI_MODE == 1 && s.L < 4) {
-                            acc[s.L & 1][2 * s.mp + h][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-                        } else {
-                            acc[s.L & 1][2 * s.mp + h][t] = *reinterpret_cast<const f32x4*>(binit + s.L * 128 + (2 * s.mp + h) * 16 + 4 * g);
-                            if constexpr (CW_CI_MODE == 2) {
-                                f32x4& q = acc[s.L & 1][2 * s.mp + h][t];
-                                asm volatile("" : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3]));
-                            }
-                        }
-                    }
+                    for (int t = 0; t < NT; ++t)
+                        acc[s.L & 1][2 * s.mp + h][t] = *reinterpret_cast<const f32x4*>(binit + s.L * 128 + (2 * s.mp + h) * 16 + 4 * g);
             }
         };
         static_for<0, kCwLoDist>([&](auto Gc) { load_lo(Gc); });
@@ -426,17 +394,8 @@ __global__ __launch_bounds__(kCwThreads, kCwWaves >= 8 ? kCwWaves / 4 : 2) void 
                 a_hi[h] = *reinterpret_cast<const f16x8*>(row);
                 a_lo[h] = *reinterpret_cast<const f16x8*>(row + 4);
 #pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    if constexpr (CW_CI_MODE == 1) {
-                        acc[0][2 * mp + h][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    } else {
-                        acc[0][2 * mp + h][t] = *reinterpret_cast<const f32x4*>(binit + (2 * mp + h) * 16 + 4 * g);
-                        if constexpr (CW_CI_MODE == 2) {
-                            f32x4& q = acc[0][2 * mp + h][t];
-                            asm volatile("" : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3]));
-                        }
-                    }
-                }
+                for (int t = 0; t < NT; ++t)
+                    acc[0][2 * mp + h][t] = *reinterpret_cast<const f32x4*>(binit + (2 * mp + h) * 16 + 4 * g);
             }
 #pragma unroll
             for (int h = 0; h < 2; ++h)
@@ -470,12 +429,10 @@ __global__ __launch_bounds__(kCwThreads, kCwWaves >= 8 ? kCwWaves / 4 : 2) void 
             constexpr int EL = prev ? s.L - 1 : s.L, EQ = prev ? s.kc + 1 : 0;
             constexpr CwParts parts = cw_parts(NT, s.L, s.kc, s.mp);
             constexpr int P0 = parts.first, NP = parts.count;
-#ifndef CW_NO_PIN
             // the requests above stay above: ALU work may cross (mask: ALU | VALU | SALU | MFMA | transcendental), memory
             // operations may not -- under register pressure the scheduler otherwise sinks every request to just ahead of
             // its first use and the wave sits out the L2 / LDS latency fifty times per pass
-            __builtin_amdgcn_sched_barrier(CW_PIN_MASK);
-#endif
+            __builtin_amdgcn_sched_barrier(kCwPinMask);
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -512,7 +469,6 @@ __global__ __launch_bounds__(kCwThreads, kCwWaves >= 8 ? kCwWaves / 4 : 2) void 
         hand_over();     // last pass's requests have landed long ago
         request(cl);     // this pass's claims: a whole pass to land in
         const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-        const float selA = ((j & 3) == g) ? 1.0f : 0.0f, sumA = g < 3 ? 1.0f : 0.0f;
         // What one lane of a point has and the other three need.  Round 4 moved these copies from LDS rows (write, wave barrier,
         // read) to the matrix pipe: v_mfma_f32_16x16x4_f32 with A[i][k] = (i mod 4 == k) hands every lane of point n the four
         // values B[0..3][n] its lane groups supplied, with A[i][k] = (k < 3) their sum over three rows.  Exact, no LDS traffic --
@@ -520,9 +476,7 @@ __global__ __launch_bounds__(kCwThreads, kCwWaves >= 8 ? kCwWaves / 4 : 2) void 
         // is what a pass is made of (vector work hides to 45 % behind MFMAs, matrix work does not hide at
         // all).  Round 5: ds_bpermute_b32 -- the LDS crossbar, no LDS memory, no barrier: lane (j, g) reads the value of lane
         // (j, r) for r = 0..3.  Same bits (a copy is a copy; the three-row sum adds in the MFMA's row order).  Alternating
-        // passes on one box: 14.66 -> 14.24 ms per launch, 38.55 -> 38.2 ms per frame (gpurun_out/r5l).  -DCW_GATHER_MFMA
-        // restores the matrix-pipe form.
-#ifndef CW_GATHER_MFMA
+        // passes on one box: 14.66 -> 14.24 ms per launch, 38.55 -> 38.2 ms per frame.
         const int sh0 = (j) << 2, sh1 = (j + 16) << 2, sh2 = (j + 32) << 2, sh3 = (j + 48) << 2;
         auto bperm = [&](int addr, float v) { return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v))); };
         auto gather = [&](float v) { return f32x4{bperm(sh0, v), bperm(sh1, v), bperm(sh2, v), bperm(sh3, v)}; };
@@ -530,12 +484,6 @@ __global__ __launch_bounds__(kCwThreads, kCwWaves >= 8 ? kCwWaves / 4 : 2) void 
             const float t = (bperm(sh0, v) + bperm(sh1, v)) + bperm(sh2, v);
             return f32x4{t, t, t, t};
         };
-        (void)selA;
-        (void)sumA;
-#else
-        auto gather = [&](float v) { return __builtin_amdgcn_mfma_f32_16x16x4f32(selA, v, zero4, 0, 0, 0); };
-        auto sum3 = [&](float v) { return __builtin_amdgcn_mfma_f32_16x16x4f32(sumA, v, zero4, 0, 0, 0); };
-#endif
         f32x4 p0[NT], p1[NT], s0[NT];
         float tgt[NT];
 #pragma unroll

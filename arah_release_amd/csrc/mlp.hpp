@@ -29,14 +29,6 @@
 
 #include "pointwise.hpp"
 
-#ifndef ARAH_SYNC
-#ifdef ARAH_ABL_NO_BARRIER   // timing ablation: no workgroup barriers inside the MLPs (results are wrong)
-#define ARAH_SYNC() __builtin_amdgcn_wave_barrier()
-#else
-#define ARAH_SYNC() __syncthreads()
-#endif
-#endif
-
 namespace arah {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -54,21 +46,13 @@ __device__ __forceinline__ void zero_acc(f32x4& a) { a = f32x4{0.f, 0.f, 0.f, 0.
 // wrong, run to run) -- tools/ubench/trunk_repro.hip bisects it down to exactly this: the same layer compiled to
 // scalar v_fma_f32 is bit-reproducible.  The empty asm pins each value in its own VGPR, which keeps the SLP
 // vectoriser away from the chain; the arithmetic (an explicit fmaf chain) is unchanged.
-// -DARAH_ALLOW_PACK removes the fence (diagnostic build: the packed listing under profiles/ and trunk_repro come from it).
-__device__ __forceinline__ void no_pack(f32x4& v) {
-#ifndef ARAH_ALLOW_PACK
-    asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
-#endif
-}
+__device__ __forceinline__ void no_pack(f32x4& v) { asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3])); }
 
 // Weight fragments are addressed as (wave-uniform 64-bit base) + (per-lane 32-bit byte offset): the base stays in
 // SGPRs and one offset VGPR serves every layer, instead of one 64-bit VGPR pointer per layer and 4 KB window
 // (global_load_dwordx4 v, v_off, s[base:base+1] offset:imm).
 template <typename Tp>
 __device__ __forceinline__ Tp ld_frag(const void* __restrict__ base, unsigned lane_off, int const_off) {
-#ifdef ARAH_FRAG_FLAT
-    return *reinterpret_cast<const Tp*>(reinterpret_cast<const char*>(base) + const_off + (size_t)lane_off);
-#else
     // a buffer load: the base is four scalar registers, the lane's offset one vector register, the constant part an
     // immediate (+ a scalar for the 4 KB window) -- whatever the unroller and the invariant-code motion make of the loop.
     // (The flat form left 64-bit vector addresses per 4 KB window, hoisted out of the tile loop and spilled: 154 scratch
@@ -78,7 +62,6 @@ __device__ __forceinline__ Tp ld_frag(const void* __restrict__ base, unsigned la
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7fffffff, 0x00020000);
     const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)lane_off + (const_off & 4095), const_off & ~4095, 0);
     return __builtin_bit_cast(Tp, v);
-#endif
 }
 
 constexpr float kActScale = 1024.0f;       // activations are stored as f16 pairs of 1024 h
@@ -267,51 +250,20 @@ __device__ __forceinline__ void gemm_acc_split(const f16x8* __restrict__ wp, int
             ah[m] = lda(((m * KC32) * 2 + 0));
             al[m] = lda(((m * KC32) * 2 + 1));
         }
-#ifdef ARAH_A_AHEAD2   // the A fragments TWO chunks ahead (tuning variant, tools/ablate_trunk.sh)
-        f16x8 ah2[MT], al2[MT];
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            ahn[m] = lda(((m * KC32 + (KC32 > 1 ? 1 : 0)) * 2 + 0));
-            aln[m] = lda(((m * KC32 + (KC32 > 1 ? 1 : 0)) * 2 + 1));
-        }
-#endif
-        // Timing ablations of the forward trunks (tools/ablate_density.sh; results are WRONG with any of them defined):
-        //   ARAH_ABL_A_FIXED  the A fragments of chunk 0 serve every chunk (no L2 fragment stream)
-        //   ARAH_ABL_B_FIXED  the B fragments of chunk 0 serve every chunk (no LDS fragment reads)
-        //   ARAH_ABL_ONE_MFMA only the hi x hi product (a third of the matrix-pipe work)
 #pragma unroll 1
         for (int kc = 0; kc < KC32; ++kc) {
-#ifdef ARAH_ABL_A_FIXED
-            const int kn = 0;
-#else
             const int kn = kc + 1 < KC32 ? kc + 1 : kc;
-#endif
-#ifdef ARAH_A_AHEAD2
-            const int k2 = kc + 2 < KC32 ? kc + 2 : KC32 - 1;
-#pragma unroll
-            for (int m = 0; m < MT; ++m) {
-                ah2[m] = lda(((m * KC32 + k2) * 2 + 0));
-                al2[m] = lda(((m * KC32 + k2) * 2 + 1));
-            }
-#else
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
                 ahn[m] = lda(((m * KC32 + kn) * 2 + 0));
                 aln[m] = lda(((m * KC32 + kn) * 2 + 1));
             }
-#endif
             f16x8 bh[NT], bl[NT];
-#ifdef ARAH_ABL_B_FIXED
-            const int kb = 0;
-#else
-            const int kb = kc;
-#endif
 #pragma unroll
             for (int n = 0; n < NT; ++n) {
-                bh[n] = *reinterpret_cast<const f16x8*>(bptr + n * 16 * ld * 4 + kb * 64);
-                bl[n] = *reinterpret_cast<const f16x8*>(bptr + n * 16 * ld * 4 + lo_off + kb * 64);
+                bh[n] = *reinterpret_cast<const f16x8*>(bptr + n * 16 * ld * 4 + kc * 64);
+                bl[n] = *reinterpret_cast<const f16x8*>(bptr + n * 16 * ld * 4 + lo_off + kc * 64);
             }
-#ifndef ARAH_ABL_ONE_MFMA
 #pragma unroll
             for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -322,7 +274,6 @@ __device__ __forceinline__ void gemm_acc_split(const f16x8* __restrict__ wp, int
 #pragma unroll
                 for (int n = 0; n < NT; ++n)
                     acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[m], bl[n], acc[m][n], 0, 0, 0);
-#endif
 #pragma unroll
             for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -332,10 +283,6 @@ __device__ __forceinline__ void gemm_acc_split(const f16x8* __restrict__ wp, int
             for (int m = 0; m < MT; ++m) {
                 ah[m] = ahn[m];
                 al[m] = aln[m];
-#ifdef ARAH_A_AHEAD2
-                ahn[m] = ah2[m];
-                aln[m] = al2[m];
-#endif
             }
         }
     }
@@ -394,24 +341,15 @@ __device__ __forceinline__ void gemm_acc_split_pipe(const FR* __restrict__ wp, i
     static_for<0, S>([&](auto Sc) {
         constexpr int s = decltype(Sc)::value, kc = s / H, h = s % H, cb = s & 1, ca = kc & 1;
         constexpr bool more_b = s + 1 < S, more_a = h == 0 && kc + 1 < KC32;
-#ifdef ARAH_ABL_A_FIXED   // timing ablations, as in gemm_acc_split (results are wrong with them)
-        constexpr int kA = 0;
-#else
-        constexpr int kA = kc + 1;
-#endif
         if constexpr (more_a) {
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
-                ah[ca ^ 1][m] = lda((m * KC32 + kA) * 2 + 0);
-                al[ca ^ 1][m] = lda((m * KC32 + kA) * 2 + 1);
+                ah[ca ^ 1][m] = lda((m * KC32 + kc + 1) * 2 + 0);
+                al[ca ^ 1][m] = lda((m * KC32 + kc + 1) * 2 + 1);
             }
         }
         if constexpr (more_b) {
-#ifdef ARAH_ABL_B_FIXED
-            constexpr int k1 = 0, h1 = (s + 1) % H;
-#else
             constexpr int k1 = (s + 1) / H, h1 = (s + 1) % H;
-#endif
 #pragma unroll
             for (int n = 0; n < NH; ++n) {
                 bh[cb ^ 1][n] = *reinterpret_cast<const FR*>(bptr + (h1 * NH + n) * 16 * ld * 4 + k1 * 64);
@@ -579,52 +517,7 @@ __device__ __forceinline__ float load_bsplit(const float* act, int ld, int lo_of
 template <int KC32, int MT, int NT = kNT>
 __device__ __forceinline__ void gemm_acc_bsplit(const bf16x8* __restrict__ wp, int mt0, const float* act, int ld, int lo_off,
                                                 f32x4 (&acc)[MT][NT], int lane) {
-#ifndef ARAH_BSPLIT_ROLLED
     gemm_acc_split_pipe<KC32, MT, NT, NT % 2 == 0 ? 2 : 1, bf16x8>(wp, mt0, act, ld, lo_off, acc, lane);
-#else   // round 3's form (A/B reference for the measurement)
-    const int j = lane & 15, g = lane >> 4;
-    const char* bptr = reinterpret_cast<const char*>(act) + j * ld * 4 + split_slot(j, g) * 16;
-    const unsigned aoff = (unsigned)(mt0 * KC32 * 2 * 64 + lane) * 16u;
-    auto lda = [&](int idx) { return ld_frag<bf16x8>(wp, aoff, idx * 1024); };
-    bf16x8 ah[MT], al[MT], ahn[MT], aln[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        ah[m] = lda((m * KC32) * 2 + 0);
-        al[m] = lda((m * KC32) * 2 + 1);
-    }
-#pragma unroll 2
-    for (int kc = 0; kc < KC32; ++kc) {
-        const int kn = kc + 1 < KC32 ? kc + 1 : kc;
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            ahn[m] = lda((m * KC32 + kn) * 2 + 0);
-            aln[m] = lda((m * KC32 + kn) * 2 + 1);
-        }
-        bf16x8 bh[NT], bl[NT];
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-            bh[n] = *reinterpret_cast<const bf16x8*>(bptr + n * 16 * ld * 4 + kc * 64);
-            bl[n] = *reinterpret_cast<const bf16x8*>(bptr + n * 16 * ld * 4 + lo_off + kc * 64);
-        }
-#pragma unroll
-        for (int m = 0; m < MT; ++m)   // small terms first
-#pragma unroll
-            for (int n = 0; n < NT; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[m], bh[n], acc[m][n], 0, 0, 0);
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int n = 0; n < NT; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[m], bl[n], acc[m][n], 0, 0, 0);
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int n = 0; n < NT; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[m], bh[n], acc[m][n], 0, 0, 0);
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            ah[m] = ahn[m];
-            al[m] = aln[m];
-        }
-    }
-#endif
 }
 
 // 4 consecutive channels of one point, already multiplied by kActScale -> hi/lo planes
@@ -669,23 +562,7 @@ __device__ __forceinline__ void store_split4(float* act, int ld, int lo_off, int
     *reinterpret_cast<u32x2*>(row + lo_off) = lo;
 }
 
-// 8 fp32 values -> the hi and lo B fragments of a 16x16x32 step, in registers (same arithmetic as store_split4)
-__device__ __forceinline__ void split8(const float (&v)[8], f16x8& hi, f16x8& lo) {
-    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 h, l;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const f16x2 h2 = __builtin_convertvector(f32x2{v[2 * p], v[2 * p + 1]}, f16x2);
-        h[p] = __builtin_bit_cast(unsigned, h2);
-        l[p] = split_residual2(v[2 * p], v[2 * p + 1], h[p]);
-    }
-    hi = __builtin_bit_cast(f16x8, h);
-    lo = __builtin_bit_cast(f16x8, l);
-}
-
-// 4 fp32 values -> two packed words of hi halves and two of lo halves (half a split8)
+// 4 fp32 values -> two packed words of hi halves and two of lo halves (same arithmetic as store_split4)
 __device__ __forceinline__ void split4(const float (&v)[4], unsigned& h0, unsigned& h1, unsigned& l0, unsigned& l1) {
     typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
     typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -766,9 +643,6 @@ constexpr int kSdfMT = 2;     // 16 M-tiles / 8 waves
 // argument, v_sin_f32(v_fract_f32(w)) = sin(2 pi frac(w)) -- measured on the MI355X against a double-precision sine over
 // 600 half-revolutions (tools/ubench/hw_sin_accuracy.hip, profiles/r02_hw_sin_accuracy.txt): max |error| 1.24e-7, rms
 // 3.46e-8, i.e. the rounding of the fp32 argument and result and nothing else; three VALU operations instead of eleven.
-// -DARAH_POLY_SINE: round 1's branch-free polynomial on HALF-revolutions (q = rint(w), r = w - q in [-1/2, 1/2] exactly,
-// sin(pi w) = (-1)^q r S(r^2), cos(pi w) = (-1)^q C(r^2) with minimax S, C; max |error| 1.71e-7, rms 3.67e-8).
-#ifndef ARAH_POLY_SINE
 constexpr double kFilmScale = 30.0 / 6.28318530717958647692;   // fw = f kFilmScale, pw = (f b + phi) kFilmScale
 __device__ __forceinline__ float sinpi_amp(float w, float amp) {
     return __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(w)) * amp;
@@ -778,38 +652,6 @@ __device__ __forceinline__ void sincospi_amp(float w, float amp, float& s, float
     s = __builtin_amdgcn_sinf(t) * amp;
     c = __builtin_amdgcn_cosf(t);
 }
-#else
-constexpr double kFilmScale = 30.0 / 3.14159265358979323846;
-__device__ __forceinline__ float sinpi_amp(float w, float amp) {
-    const float q = rintf(w);
-    const float r = w - q;
-    const float r2 = r * r;
-    float p = fmaf(r2, 0.0772201280771219f * amp, -0.5980451736306471f * amp);
-    p = fmaf(p, r2, 2.550031377188653f * amp);
-    p = fmaf(p, r2, -5.167706878920042f * amp);
-    p = fmaf(p, r2, 3.1415925800446054f * amp);
-    const unsigned sgn = (unsigned)(int)q << 31;
-    return __uint_as_float(__float_as_uint(p * r) ^ sgn);
-}
-
-__device__ __forceinline__ void sincospi_amp(float w, float amp, float& s, float& c) {
-    const float q = rintf(w);
-    const float r = w - q;
-    const float r2 = r * r;
-    float p = fmaf(r2, 0.0772201280771219f * amp, -0.5980451736306471f * amp);
-    p = fmaf(p, r2, 2.550031377188653f * amp);
-    p = fmaf(p, r2, -5.167706878920042f * amp);
-    p = fmaf(p, r2, 3.1415925800446054f * amp);
-    float pc = fmaf(r2, -0.02439671639064982f, 0.23493755882145678f);
-    pc = fmaf(pc, r2, -1.335212056639698f);
-    pc = fmaf(pc, r2, 4.058709164340391f);
-    pc = fmaf(pc, r2, -4.9348021372282975f);
-    pc = fmaf(pc, r2, 0.9999999997806512f);
-    const unsigned sgn = (unsigned)(int)q << 31;
-    s = __uint_as_float(__float_as_uint(p * r) ^ sgn);
-    c = __uint_as_float(__float_as_uint(pc) ^ sgn);
-}
-#endif
 
 // FiLM-SIREN activation of 4 channels: h = amp sin(z), z = 30 (f (v + b) + phi) = pi (fw v + pw);
 // GRAD: d = dh/dv / amp = 30 f cos(z)
@@ -909,14 +751,12 @@ __device__ __forceinline__ void sdf_trunk(const SdfNet& net, const float* xin, f
                 film_sine<GRAD>(v, fw, pw, f, amp, h, d);
                 if (SPLIT) store_split4(act, ld, 512, n * 16 + j, ch0, h);
                 else *reinterpret_cast<f32x4*>(act + (n * 16 + j) * ld + ch0) = h;
-#ifndef ARAH_ABL_NO_SLAB
                 if (GRAD && KEEP0) spill[((0 * kWaves + wave) * (kSdfMT * NT) + m * NT + n) * 64 + lane] = d;
-#endif
             }
         }
     }
     if constexpr (TAP::on) stream_rows(xin, 4, 4, tap.h[0], tap.row0, tap.rows, wave * 64 + lane);
-    ARAH_SYNC();
+    __syncthreads();
 #pragma unroll 1
     for (int k = 1; k < 6; ++k) {
         f32x4 acc[kSdfMT][NT];
@@ -928,11 +768,9 @@ __device__ __forceinline__ void sdf_trunk(const SdfNet& net, const float* xin, f
             if (SPLIT) stream_rows_split(act, ld, tap.h[k], tap.row0, tap.rows, wave * 64 + lane);
             else stream_rows(act, ld, 256, tap.h[k], tap.row0, tap.rows, wave * 64 + lane);
         }
-#ifndef ARAH_TRUNK_ROLLED   // 128-point tiles (two waves per SIMD): the explicit pipeline, 12.3 vs 13.1 ms for k_density (r3o)
+        // 128-point tiles (two waves per SIMD): the explicit pipeline, 12.3 vs 13.1 ms for k_density (r3o)
         if constexpr (SPLIT && !GRAD && NT == 8) gemm_acc_split_pipe<8, kSdfMT, NT, 2>(net.wps[k - 1], mt0, act, ld, 512, acc, lane);
-        else
-#endif
-        if constexpr (SPLIT && PIPE > 0) gemm_acc_split_pipe<8, kSdfMT, NT, PIPE>(net.wps[k - 1], mt0, act, ld, 512, acc, lane);
+        else if constexpr (SPLIT && PIPE > 0) gemm_acc_split_pipe<8, kSdfMT, NT, PIPE>(net.wps[k - 1], mt0, act, ld, 512, acc, lane);
         else
         if (SPLIT) gemm_acc_split<8, kSdfMT, NT, GRAD>(net.wps[k - 1], mt0, act, ld, 512, acc, lane);   // GRAD kernels: 2 waves/SIMD
         else gemm_acc<16, kSdfMT, NT>(net.wp[k - 1], mt0, act, ld, acc, lane);
@@ -951,7 +789,7 @@ __device__ __forceinline__ void sdf_trunk(const SdfNet& net, const float* xin, f
                 if constexpr (GRAD) fm[m] = *reinterpret_cast<const f32x4*>(net.freq + k * 256 + ch0);
             }
         }
-        ARAH_SYNC();   // everyone is done reading the layer input
+        __syncthreads();   // everyone is done reading the layer input
         ARAH_PC_MARK(9);
 #pragma unroll
         for (int m = 0; m < kSdfMT; ++m) {
@@ -972,204 +810,19 @@ __device__ __forceinline__ void sdf_trunk(const SdfNet& net, const float* xin, f
                 if constexpr (TAP::on)   // the pre-activation v_k itself: the split engine's accumulator carries the operand scales
                     tap.aslab[((k * kWaves + wave) * (kSdfMT * NT) + m * NT + n) * 64 + lane] =
                         SPLIT ? acc[m][n] * net.fws[6 * 256 + k] : acc[m][n];
-#ifdef ARAH_ABL_NO_EPI   //   ARAH_ABL_NO_EPI   no FiLM sine: the accumulators are stored as they are
-                h = acc[m][n] * 1e-6f;
-                d = zero4;
-#else
                 film_sine<GRAD>(acc[m][n], fw, pw, f, amp, h, d);
-#endif
                 if (SPLIT) store_split4(act, ld, 512, n * 16 + j, ch0, h);
                 else *reinterpret_cast<f32x4*>(act + (n * 16 + j) * ld + ch0) = h;
                 if (GRAD) {
-#ifdef ARAH_ABL_NO_SLAB   //   ARAH_ABL_NO_SLAB   timing only: the derivative factors neither leave nor come back
-                    dlast[m][n] = d;
-#else
                     if (k < 5) spill[((k * kWaves + wave) * (kSdfMT * NT) + m * NT + n) * 64 + lane] = d;
                     else dlast[m][n] = d;
-#endif
                 }
             }
         }
         ARAH_PC_MARK(8);
-        ARAH_SYNC();
+        __syncthreads();
         ARAH_PC_MARK(9);
     }
-}
-
-// Forward trunk of a tile of 2 x NTH x 16 points on the split engine with the two halves of the tile a phase apart: while
-// the MFMAs of one half's layer issue, the FiLM-sine epilogue of the other half's previous GEMM rides between them (one
-// 16 x 16 accumulator group per 32-chunk), so that matrix pipe and vector ALU work in the same phase instead of taking
-// turns between workgroup barriers.  One barrier per phase, two phases per layer -- the barrier count of sdf_trunk.
-//   phase (H0, k): GEMM of half 0, layer k   ||  epilogue of half 1, layer k - 1  (writes half 1's rows)
-//   phase (H1, k): GEMM of half 1, layer k   ||  epilogue of half 0, layer k      (writes half 0's rows)
-// A barrier separates a half's GEMM (which reads its rows) from the epilogue that rewrites them in place, and the
-// epilogue from the next GEMM that reads them.  Same MFMA order per accumulator and the same epilogue arithmetic as
-// sdf_trunk: bit-identical results (the density pass and the shading pass must agree on every sample).
-template <typename Tp, Tp V>
-struct PpConst {
-    static constexpr Tp value = V;
-};
-template <int NTH>
-__device__ __forceinline__ void sdf_trunk_pp(const SdfNet& net, const float* xin, float* act, int ld, int wave, int lane) {
-    const int j = lane & 15, g = lane >> 4;
-    const int mt0 = wave * kSdfMT;
-    constexpr float amp = kActScale;
-    constexpr int NT = 2 * NTH;
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    {   // layer 1: K = 3 on the vector ALU, both halves (as sdf_trunk)
-#pragma unroll
-        for (int m = 0; m < kSdfMT; ++m) {
-            const int ch0 = (mt0 + m) * 16 + 4 * g;
-            f32x4 w[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) w[r] = *reinterpret_cast<const f32x4*>(net.w0 + (ch0 + r) * 4);
-            const f32x4 fw = *reinterpret_cast<const f32x4*>(net.fw + ch0);
-            const f32x4 pw = *reinterpret_cast<const f32x4*>(net.pw + ch0);
-#pragma unroll
-            for (int n = 0; n < NT; ++n) {
-                const f32x4 x = *reinterpret_cast<const f32x4*>(xin + (n * 16 + j) * 4);
-                f32x4 v, h, d;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = fmaf(w[r][2], x[2], fmaf(w[r][1], x[1], w[r][0] * x[0]));
-                no_pack(v);
-                film_sine<false>(v, fw, pw, zero4, amp, h, d);
-                store_split4(act, ld, 512, n * 16 + j, ch0, h);
-            }
-        }
-    }
-    ARAH_SYNC();
-    f32x4 acc[2][kSdfMT][NTH];   // [half][m][n]
-    // one phase: acc[hg] = W_k * rows of half hg; EPI: the epilogue of layer ke on acc[he] -> rows of half he
-    auto phase = [&](auto hgc, int k, auto epic, int ke) {
-        constexpr int hg = decltype(hgc)::value, he = 1 - hg;
-        constexpr bool EPI = decltype(epic)::value;
-        const f16x8* wp = net.wps[k - 1];
-        const unsigned aoff = (unsigned)(mt0 * 8 * 2 * 64 + lane) * 16u;
-        auto lda = [&](int idx) { return ld_frag<f16x8>(wp, aoff, idx * 1024); };
-        const char* bptr = reinterpret_cast<const char*>(act) + (hg * NTH * 16 + j) * ld * 4 + split_slot(j, g) * 16;
-        f32x4 fwm[kSdfMT], pwm[kSdfMT];
-        if constexpr (EPI) {
-#pragma unroll
-            for (int m = 0; m < kSdfMT; ++m) {
-                const int ch0 = (mt0 + m) * 16 + 4 * g;
-                fwm[m] = *reinterpret_cast<const f32x4*>(net.fws + ke * 256 + ch0);
-                pwm[m] = *reinterpret_cast<const f32x4*>(net.pw + ke * 256 + ch0);
-            }
-        }
-        // explicit pipeline as in gemm_acc_split_pipe, a stage = half a 32-chunk's N-tiles (3 kSdfMT NTH / 2 MFMAs): the
-        // next stage's B fragments and (first half) the next chunk's A fragments are requested while the stage's MFMAs
-        // run, and the epilogue group of the other half-tile rides between them: FiLM sine in a chunk's first stage,
-        // hi/lo split and the two LDS stores in its second
-        constexpr int NQ = NTH / 2;
-        f16x8 ah[2][kSdfMT], al[2][kSdfMT], bh[2][NQ], bl[2][NQ];
-#pragma unroll
-        for (int m = 0; m < kSdfMT; ++m) {
-            ah[0][m] = lda((m * 8) * 2 + 0);
-            al[0][m] = lda((m * 8) * 2 + 1);
-        }
-#pragma unroll
-        for (int n = 0; n < NQ; ++n) {
-            bh[0][n] = *reinterpret_cast<const f16x8*>(bptr + n * 16 * ld * 4);
-            bl[0][n] = *reinterpret_cast<const f16x8*>(bptr + n * 16 * ld * 4 + 512);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        f32x4 hcur = zero4;
-        static_for<0, 16>([&](auto Sc) {
-            constexpr int st = decltype(Sc)::value, kc = st >> 1, hh = st & 1, cb = st & 1, ca = kc & 1;
-            constexpr bool more_b = st + 1 < 16, more_a = hh == 0 && kc + 1 < 8;
-            if constexpr (more_a) {
-#pragma unroll
-                for (int m = 0; m < kSdfMT; ++m) {
-                    ah[ca ^ 1][m] = lda((m * 8 + kc + 1) * 2 + 0);
-                    al[ca ^ 1][m] = lda((m * 8 + kc + 1) * 2 + 1);
-                }
-            }
-            if constexpr (more_b) {
-                constexpr int k1 = (st + 1) >> 1, h1 = (st + 1) & 1;
-#pragma unroll
-                for (int n = 0; n < NQ; ++n) {
-                    bh[cb ^ 1][n] = *reinterpret_cast<const f16x8*>(bptr + (h1 * NQ + n) * 16 * ld * 4 + k1 * 64);
-                    bl[cb ^ 1][n] = *reinterpret_cast<const f16x8*>(bptr + (h1 * NQ + n) * 16 * ld * 4 + 512 + k1 * 64);
-                }
-            }
-#pragma unroll
-            for (int m = 0; m < kSdfMT; ++m)
-#pragma unroll
-                for (int n = 0; n < NQ; ++n)
-                    acc[hg][m][hh * NQ + n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[ca][m], bh[cb][n], kc == 0 ? zero4 : acc[hg][m][hh * NQ + n], 0, 0, 0);
-#pragma unroll
-            for (int m = 0; m < kSdfMT; ++m)
-#pragma unroll
-                for (int n = 0; n < NQ; ++n)
-                    acc[hg][m][hh * NQ + n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[ca][m], bl[cb][n], acc[hg][m][hh * NQ + n], 0, 0, 0);
-#pragma unroll
-            for (int m = 0; m < kSdfMT; ++m)
-#pragma unroll
-                for (int n = 0; n < NQ; ++n)
-                    acc[hg][m][hh * NQ + n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[ca][m], bh[cb][n], acc[hg][m][hh * NQ + n], 0, 0, 0);
-            if constexpr (EPI) {   // accumulator group kc of the other half: kSdfMT * NTH == 8 groups, one per chunk
-                static_assert(kSdfMT * NTH == 8, "one epilogue group per 32-chunk");
-                constexpr int m = kc / NTH, n = kc % NTH;
-                if constexpr (hh == 0) {
-                    f32x4 d;
-                    film_sine<false>(acc[he][m][n], fwm[m], pwm[m], zero4, amp, hcur, d);
-                } else {
-                    store_split4(act, ld, 512, (he * NTH + n) * 16 + j, (mt0 + m) * 16 + 4 * g, hcur);
-                }
-            }
-            // 0x008 MFMA, 0x002 VALU, 0x020 VMEM read, 0x100 DS read, 0x200 DS write
-            constexpr int n_vm = more_a ? 2 * kSdfMT : 0, n_ds = more_b ? 2 * NQ : 0, n_mf = 3 * kSdfMT * NQ;
-            static_for<0, n_vm>([&](auto) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                if constexpr (EPI) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-            });
-            static_for<0, n_ds>([&](auto) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                if constexpr (EPI) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-            });
-            static_for<0, n_mf - n_vm - n_ds>([&](auto) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                if constexpr (EPI) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-            });
-            if constexpr (EPI) {
-                __builtin_amdgcn_sched_group_barrier(0x002, 16, 0);
-                __builtin_amdgcn_sched_group_barrier(0x200, 4, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        });
-    };
-    typedef PpConst<int, 0> H0_;
-    typedef PpConst<int, 1> H1_;
-    typedef PpConst<bool, true> T_;
-    typedef PpConst<bool, false> F_;
-    phase(H0_{}, 1, F_{}, 0);
-    ARAH_SYNC();
-#pragma unroll 1
-    for (int k = 1; k < 6; ++k) {
-        phase(H1_{}, k, T_{}, k);          // GEMM (H1, k) || epilogue (H0, k)
-        ARAH_SYNC();
-        if (k < 5) {
-            phase(H0_{}, k + 1, T_{}, k);  // GEMM (H0, k + 1) || epilogue (H1, k)
-            ARAH_SYNC();
-        }
-    }
-    {   // epilogue (H1, 5)
-#pragma unroll
-        for (int m = 0; m < kSdfMT; ++m) {
-            const int ch0 = (mt0 + m) * 16 + 4 * g;
-            const f32x4 fw = *reinterpret_cast<const f32x4*>(net.fws + 5 * 256 + ch0);
-            const f32x4 pw = *reinterpret_cast<const f32x4*>(net.pw + 5 * 256 + ch0);
-#pragma unroll
-            for (int n = 0; n < NTH; ++n) {
-                f32x4 h, d;
-                film_sine<false>(acc[1][m][n], fw, pw, zero4, amp, h, d);
-                store_split4(act, ld, 512, (NTH + n) * 16 + j, ch0, h);
-            }
-        }
-    }
-    ARAH_SYNC();
 }
 
 // split planes -> fp32 in place for the first n_pts rows (through registers: the fp32 row overlays both planes)
@@ -1180,7 +833,7 @@ __device__ __forceinline__ void unsplit_rows(float* act, int ld, int tid) {
         const int e = tid + i * kThreads;
         v[i] = load_split(act, ld, 512, e >> 8, e & 255);
     }
-    ARAH_SYNC();
+    __syncthreads();
 #pragma unroll
     for (int i = 0; i < 32; ++i) {
         const int e = tid + i * kThreads;
@@ -1193,35 +846,6 @@ template <bool SPLIT = false>
 __device__ __forceinline__ void sdf_head(const SdfNet& net, const float* act, int ld, float* out, int ostride,
                                          int tid, int n_pts = kTile) {
     const int part = tid & 7;
-#ifdef ARAH_REG_TRUNK   // experiment builds only (regtrunk.hpp, profiles/r05_reg_trunk.txt): the shipped head is the loop below
-    if constexpr (SPLIT) {
-        // The split engine's head sums in the order a POINT-OWNING wave can follow without leaving its registers
-        // (regtrunk.hpp: lane group g of a point holds the units 32 q + 8 g + e): 32 chains (g, e) per point, each over
-        // q = 0 .. 7 with two fmas per unit -- the hi half, then the lo half, against w6 / 1024 (exact) -- then the tree over e
-        // and (t0 + t1) + (t2 + t3) over g.  Every kernel of the engine comes through here, so they all agree bit for bit.
-        for (int pt = tid >> 3; pt < n_pts; pt += kThreads / 8) {   // whole waves drop out: n_pts is a multiple of 8
-            float s[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int q = 0; q < 8; ++q)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int ch = 32 * q + 8 * g + part;
-                    const float w = net.w6[ch] * kInvActScale;
-                    const char* row = reinterpret_cast<const char*>(act) + pt * ld * 4 + split_byte(pt, ch);
-                    s[g] = fmaf(w, (float)*reinterpret_cast<const _Float16*>(row), s[g]);
-                    s[g] = fmaf(w, (float)*reinterpret_cast<const _Float16*>(row + 512), s[g]);
-                }
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                s[g] += __shfl_xor(s[g], 1);
-                s[g] += __shfl_xor(s[g], 2);
-                s[g] += __shfl_xor(s[g], 4);
-            }
-            if (part == 0) out[pt * ostride] = ((s[0] + s[1]) + (s[2] + s[3])) + net.b6[0];
-        }
-        return;
-    }
-#endif
     for (int pt = tid >> 3; pt < n_pts; pt += kThreads / 8) {   // whole waves drop out: n_pts is a multiple of 8
         float s = 0.f;
 #pragma unroll 8
@@ -1251,7 +875,7 @@ __device__ __forceinline__ void sdf_backward(const SdfNet& net, float* bwd, int 
 #pragma unroll
         for (int n = 0; n < kNT; ++n) *reinterpret_cast<f32x4*>(bwd + (n * 16 + j) * ld + ch0) = dlast[m][n] * w;
     }
-    ARAH_SYNC();
+    __syncthreads();
 #pragma unroll 1
     for (int k = 4; k >= 0; --k) {   // g_k+1 (layer index k, 0-based) = W_{k+2}^T u_{k+2}
         f32x4 acc[kSdfMT][kNT];
@@ -1260,7 +884,7 @@ __device__ __forceinline__ void sdf_backward(const SdfNet& net, float* bwd, int 
 #pragma unroll
             for (int n = 0; n < kNT; ++n) zero_acc(acc[m][n]);
         gemm_any<B3, 16, kSdfMT>(net.wpT[k], B3 ? b3->sdf_wpT[k] : nullptr, mt0, bwd, ld, acc, lane);
-        ARAH_SYNC();
+        __syncthreads();
 #pragma unroll
         for (int m = 0; m < kSdfMT; ++m) {
             const int ch0 = (mt0 + m) * 16 + 4 * g;
@@ -1270,7 +894,7 @@ __device__ __forceinline__ void sdf_backward(const SdfNet& net, float* bwd, int 
                 *reinterpret_cast<f32x4*>(bwd + (n * 16 + j) * ld + ch0) = acc[m][n] * d;
             }
         }
-        ARAH_SYNC();
+        __syncthreads();
     }
     // grad_c = sum_ch w0[ch][c] * u1[pt][ch]
     const int pt = tid >> 3, part = tid & 7;
@@ -1352,30 +976,12 @@ enum {
 constexpr float kZUnit = 144.269504088896341f;   // 100 log2(e)
 constexpr float kCwShift = 24.0f;
 
-// Softplus(beta = 100) in z units: S(z) = log2(1 + 2^z) = max(z, 0) + log2(1 + 2^-|z|).  Two transcendentals and
-// three plain operations; the absolute error is that of 1 + e (6e-8 in z, 4e-10 in x).
-__device__ __forceinline__ float softplus_z(float z) {
-    const float e = __builtin_amdgcn_exp2f(-fabsf(z));
-    return fmaxf(z, 0.f) + __builtin_amdgcn_logf(1.0f + e);
-}
-// The shifted form (see above): zs = z - 24 -> S(z) - 24.  `inf` is +infinity in a register the compiler cannot see
-// through: med3(a, b, +inf) = max(a, b) without the canonicalising v_max(a, a) an fmaxf of an MFMA result costs.
-#ifndef CW_SP_FORM
-#define CW_SP_FORM 0
-#endif
+// Softplus(beta = 100) in z units, in the shifted form (see above): zs = z - 24 -> S(z) - 24.  `inf` is +infinity in a
+// register the compiler cannot see through: med3(a, b, +inf) = max(a, b) without the canonicalising v_max(a, a) an fmaxf
+// of an MFMA result costs.
 __device__ __forceinline__ float softplus_shift(float zs, float inf) {
-#if CW_SP_FORM == 3    // bisecting aid: the unshifted form behind two adds
-    return softplus_z(zs + kCwShift) - kCwShift;
-#elif CW_SP_FORM == 1  // v_min instead of the clamp modifier
-    const float e = fminf(__builtin_amdgcn_exp2f(zs), 1.0f);
-    return __builtin_amdgcn_fmed3f(zs, __builtin_amdgcn_logf(e + 0x1p-24f), inf);
-#elif CW_SP_FORM == 2  // canonicalising max instead of med3
-    const float e = __builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(zs), 0.f, 1.f);
-    return fmaxf(zs, __builtin_amdgcn_logf(e + 0x1p-24f));
-#else
     const float e = __builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(zs), 0.f, 1.f);   // v_exp_f32 ... clamp
     return __builtin_amdgcn_fmed3f(zs, __builtin_amdgcn_logf(e + 0x1p-24f), inf);
-#endif
 }
 
 // Softplus(beta=100): log1p(exp(100 x))/100 == max(x,0) + log1p(exp(-|100 x|))/100.  The correction is
@@ -1430,7 +1036,7 @@ __device__ __forceinline__ void skin_mlp(const SkinNet& net, const float* xin, f
             }
         }
     }
-    ARAH_SYNC();
+    __syncthreads();
     clk.mark(2);
     SplitA<4> a_out;
 #pragma unroll 1
@@ -1446,7 +1052,7 @@ __device__ __forceinline__ void skin_mlp(const SkinNet& net, const float* xin, f
         f32x4 b = *reinterpret_cast<const f32x4*>(net.bias + k * 128 + ch0);
         const float S = SPLIT ? net.scales[k] : 1.0f;
         const float inv = SPLIT ? net.scales[4 + k - 1] * S : 1.0f;   // accumulator -> S (W h): S is a power of two
-        ARAH_SYNC();
+        __syncthreads();
         const float c1 = 144.269504088896341f / S, c2 = 6.93147180559945e-3f * S;
         if (SPLIT) b = b * S;
 #pragma unroll
@@ -1464,13 +1070,13 @@ __device__ __forceinline__ void skin_mlp(const SkinNet& net, const float* xin, f
             }
         }
         if (k < 3) {
-            ARAH_SYNC();
+            __syncthreads();
             clk.mark(2 + 2 * k);
         }
     }
     // the output layer's A fragments travel (L2 latency) while the workgroup gathers at the barrier
     if (SPLIT && (wave >> 1) < NT) a_out = load_split_a<4>(net.wps[3], wave & 1, lane);
-    ARAH_SYNC();
+    __syncthreads();
     clk.mark(8);
     {   // output layer 128 -> 25 (padded 32): wave w computes M-tile (w & 1) of N-tile (w >> 1)
         const int mt = wave & 1, nt = wave >> 1;
@@ -1487,7 +1093,7 @@ __device__ __forceinline__ void skin_mlp(const SkinNet& net, const float* xin, f
             for (int r = 0; r < 4; ++r) logits[(nt * 16 + j) * kLogitLd + ch0 + r] = acc[r] + b[r];
         }
     }
-    ARAH_SYNC();
+    __syncthreads();
     clk.mark(9);
 }
 
@@ -1549,7 +1155,7 @@ __device__ __forceinline__ void resplit_rows_bf16(float* act, int ld, int lo_off
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[i][r] = load_split(act, ld, 512, pt, ch0 + r);
     }
-    ARAH_SYNC();
+    __syncthreads();
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int e = tid + i * kThreads;
@@ -1590,7 +1196,7 @@ __device__ __forceinline__ void sdf_backward_bp(const SdfNet& net, const B3Nets&
 #pragma unroll
         for (int n = 0; n < kNT; ++n) store_bsplit4(bwd, ld, 512, n * 16 + j, ch0, dlast[m][n] * w);
     }
-    ARAH_SYNC();
+    __syncthreads();
 #pragma unroll 1
     for (int k = 4; k >= 0; --k) {
         f32x4 acc[kSdfMT][kNT];
@@ -1605,15 +1211,11 @@ __device__ __forceinline__ void sdf_backward_bp(const SdfNet& net, const B3Nets&
         for (int m = 0; m < kSdfMT; ++m)
 #pragma unroll
             for (int n = 0; n < kNT; ++n)
-#ifdef ARAH_ABL_NO_SLAB
-                dk[m][n] = dlast[m][n];
-#else
                 dk[m][n] = k == 0 && xin ? layer0_dfactor(net, xin, mt0, m, n, lane)
                                          : spill[((k * kWaves + wave) * (kSdfMT * kNT) + m * kNT + n) * 64 + lane];
-#endif
         gemm_acc_bsplit<8, kSdfMT>(b3.sdf_wpT[k], mt0, bwd, ld, 512, acc, lane);
         ARAH_PC_MARK(10);
-        ARAH_SYNC();
+        __syncthreads();
         ARAH_PC_MARK(12);
 #pragma unroll
         for (int m = 0; m < kSdfMT; ++m) {
@@ -1622,7 +1224,7 @@ __device__ __forceinline__ void sdf_backward_bp(const SdfNet& net, const B3Nets&
             for (int n = 0; n < kNT; ++n) store_bsplit4(bwd, ld, 512, n * 16 + j, ch0, acc[m][n] * dk[m][n]);
         }
         ARAH_PC_MARK(11);
-        ARAH_SYNC();
+        __syncthreads();
         ARAH_PC_MARK(12);
     }
     const int pt = tid >> 3, part = tid & 7;
@@ -1666,7 +1268,7 @@ __device__ __forceinline__ void color_mlp(const ColNet& net, const float* A, flo
         gemm_any<B3, D::kKC0, 2>(net.w0p, B3 ? b3->col[0] : nullptr, wave * 2, A, D::kLdA, acc, lane);
         relu_store<2>(acc, net.bias, B, ldB, wave * 2, lane);   // B is not read by this GEMM
     }
-    ARAH_SYNC();
+    __syncthreads();
     if (tap) {
         stream_rows(A, D::kLdA, D::kInPad, tap->cin, tap->row0, tap->rows, tid);
         stream_rows(B, ldB, 256, tap->c[0], tap->row0, tap->rows, tid);
@@ -1678,20 +1280,20 @@ __device__ __forceinline__ void color_mlp(const ColNet& net, const float* A, flo
 #pragma unroll
             for (int n = 0; n < kNT; ++n) zero_acc(acc[m][n]);
         gemm_any<B3, 16, 2>(net.w1p, B3 ? b3->col[1] : nullptr, wave * 2, B, ldB, acc, lane);
-        ARAH_SYNC();
+        __syncthreads();
         relu_store<2>(acc, net.bias + 256, B, ldB, wave * 2, lane);
     }
-    ARAH_SYNC();
+    __syncthreads();
     if (tap) stream_rows(B, ldB, 256, tap->c[1], tap->row0, tap->rows, tid);
     {
         f32x4 acc[1][kNT];
 #pragma unroll
         for (int n = 0; n < kNT; ++n) zero_acc(acc[0][n]);
         gemm_any<B3, 16, 1>(net.w2p, B3 ? b3->col[2] : nullptr, wave, B, ldB, acc, lane);
-        ARAH_SYNC();
+        __syncthreads();
         relu_store<1>(acc, net.bias + 512, B, ldB, wave, lane);   // cols 0..127
     }
-    ARAH_SYNC();
+    __syncthreads();
     if (tap) stream_rows(B, ldB, 128, tap->c[2], tap->row0, tap->rows, tid);
     {
         f32x4 acc[2][kNT];
@@ -1701,10 +1303,10 @@ __device__ __forceinline__ void color_mlp(const ColNet& net, const float* A, flo
             for (int n = 0; n < kNT; ++n) zero_acc(acc[m][n]);
         gemm_any<B3, D::kKC0, 2>(net.w3ap, B3 ? b3->col[3] : nullptr, wave * 2, A, D::kLdA, acc, lane);
         gemm_any<B3, 8, 2>(net.w3bp, B3 ? b3->col[4] : nullptr, wave * 2, B, ldB, acc, lane);
-        ARAH_SYNC();
+        __syncthreads();
         relu_store<2>(acc, net.bias + 640, B, ldB, wave * 2, lane);
     }
-    ARAH_SYNC();
+    __syncthreads();
     if (tap) stream_rows(B, ldB, 256, tap->c[3], tap->row0, tap->rows, tid);
     {
         f32x4 acc[2][kNT];
@@ -1713,10 +1315,10 @@ __device__ __forceinline__ void color_mlp(const ColNet& net, const float* A, flo
 #pragma unroll
             for (int n = 0; n < kNT; ++n) zero_acc(acc[m][n]);
         gemm_any<B3, 16, 2>(net.w4p, B3 ? b3->col[5] : nullptr, wave * 2, B, ldB, acc, lane);
-        ARAH_SYNC();
+        __syncthreads();
         relu_store<2>(acc, net.bias + 896, B, ldB, wave * 2, lane);
     }
-    ARAH_SYNC();
+    __syncthreads();
     if (tap) stream_rows(B, ldB, 256, tap->c[4], tap->row0, tap->rows, tid);
     {
         const int pt = tid >> 3, part = tid & 7;
@@ -1787,7 +1389,7 @@ __device__ __forceinline__ void color_mlp_bp(const ColNet& net, const B3Nets& b3
         gemm_acc_bsplit<KCA, 2>(b3.col[0], wave * 2, A, ldA, loA, acc, lane);
         relu_store_bp<2>(acc, bias, B, ldB, wave * 2, lane);   // B is not read by this GEMM
     }
-    ARAH_SYNC();
+    __syncthreads();
     {
         f32x4 acc[2][kNT];
 #pragma unroll
@@ -1797,10 +1399,10 @@ __device__ __forceinline__ void color_mlp_bp(const ColNet& net, const B3Nets& b3
         f32x4 bias[2];
         load_bias<2>(net.bias + 256, wave * 2, lane, bias);
         gemm_acc_bsplit<8, 2>(b3.col[1], wave * 2, B, ldB, 512, acc, lane);
-        ARAH_SYNC();
+        __syncthreads();
         relu_store_bp<2>(acc, bias, B, ldB, wave * 2, lane);
     }
-    ARAH_SYNC();
+    __syncthreads();
     {
         f32x4 acc[1][kNT];
 #pragma unroll
@@ -1808,10 +1410,10 @@ __device__ __forceinline__ void color_mlp_bp(const ColNet& net, const B3Nets& b3
         f32x4 bias[1];
         load_bias<1>(net.bias + 512, wave, lane, bias);
         gemm_acc_bsplit<8, 1>(b3.col[2], wave, B, ldB, 512, acc, lane);
-        ARAH_SYNC();
+        __syncthreads();
         relu_store_bp<1>(acc, bias, B, ldB, wave, lane);   // channels 0..127
     }
-    ARAH_SYNC();
+    __syncthreads();
     {
         f32x4 acc[2][kNT];
 #pragma unroll
@@ -1822,10 +1424,10 @@ __device__ __forceinline__ void color_mlp_bp(const ColNet& net, const B3Nets& b3
         load_bias<2>(net.bias + 640, wave * 2, lane, bias);
         gemm_acc_bsplit<KCA, 2>(b3.col[3], wave * 2, A, ldA, loA, acc, lane);
         gemm_acc_bsplit<4, 2>(b3.col[4], wave * 2, B, ldB, 512, acc, lane);
-        ARAH_SYNC();
+        __syncthreads();
         relu_store_bp<2>(acc, bias, B, ldB, wave * 2, lane);
     }
-    ARAH_SYNC();
+    __syncthreads();
     {
         f32x4 acc[2][kNT];
 #pragma unroll
@@ -1835,10 +1437,10 @@ __device__ __forceinline__ void color_mlp_bp(const ColNet& net, const B3Nets& b3
         f32x4 bias[2];
         load_bias<2>(net.bias + 896, wave * 2, lane, bias);
         gemm_acc_bsplit<8, 2>(b3.col[5], wave * 2, B, ldB, 512, acc, lane);
-        ARAH_SYNC();
+        __syncthreads();
         relu_store_bp<2>(acc, bias, B, ldB, wave * 2, lane);
     }
-    ARAH_SYNC();
+    __syncthreads();
     {
         const int pt = tid >> 3, part = tid & 7;
         float c0 = 0.f, c1 = 0.f, c2 = 0.f;

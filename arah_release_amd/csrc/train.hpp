@@ -136,11 +136,6 @@ __global__ __launch_bounds__(kThreads) void k_shade_train(TrainArgs ka) {
     f32x4* const spill_all = ka.spill_all;
     f32x4* const slab_all = ka.slab_all;
     typedef ColDims<IDR> D;
-#ifdef ARAH_TRAIN_FWD_FP32
-    constexpr bool FWD_B3 = false;            // A/B: the forward's normal sweep and colour MLP on the fp32 MFMA (rounds 3-5)
-#else
-    constexpr bool FWD_B3 = B3;
-#endif
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* xin = smem;                        // [64][4]
     float* outv = xin + 64 * 4;               // [64][4] sdf, normal (canonical)
@@ -226,10 +221,10 @@ __global__ __launch_bounds__(kThreads) void k_shade_train(TrainArgs ka) {
         // runs, 2^-16 per product): a linear sweep, no gates in it; forward kernel 2.28 -> 1.76 ms.  The colour MLP stays on
         // the fp32 MFMA: its results pass ReLU gates and 2^-16 products flip ~1e-5 of them against fp32 arithmetic.  Since the
         // forward hands its activations to the backward (tap_c) the gradient would still be the exact gradient of the function
-        // that was evaluated -- but a flipped gate moves one sample's whole contribution: with -DARAH_TRAIN_FWD_COLOR_B3
+        // that was evaluated -- but a flipped gate moves one sample's whole contribution: with the colour MLP on bf16 x 3 too
         // (forward kernel 1.24 ms) one element of col.lin2.bias' gradient in test_shade_samples_op_against_autograd is 0.47 %
         // of the tensor's scale off the fp32 restatement (bound 0.2 %); the reference-pinned F8 test passes either way.
-        sdf_backward<FWD_B3>(net, B, ldB, spill, dlast, outv, 4, wave, lane, tid, &b3);
+        sdf_backward<B3>(net, B, ldB, spill, dlast, outv, 4, wave, lane, tid, &b3);
         __syncthreads();
         if (geom) {   // regulariser queries: value and normal are the outputs
             if (tid < rows) {
@@ -302,11 +297,7 @@ __global__ __launch_bounds__(kThreads) void k_shade_train(TrainArgs ka) {
             ctap.row0 = row0;
             ctap.rows = rows;
         }
-#ifdef ARAH_TRAIN_FWD_COLOR_B3
-        color_mlp<IDR, FWD_B3>(fr.col, A, B, rgbv, 4, wave, lane, tid, taps ? &ctap : nullptr, &b3);
-#else
         color_mlp<IDR, false>(fr.col, A, B, rgbv, 4, wave, lane, tid, taps ? &ctap : nullptr);
-#endif
         __syncthreads();
         if (tid < rows) {
             const long long p = row0 + tid;

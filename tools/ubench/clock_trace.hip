@@ -1,7 +1,7 @@
 // clock_trace.hip -- the shader clock over time while other kernels run: one wave samples s_memtime (shader cycles) against
 // s_memrealtime (100 MHz) every `period` real-time ticks and logs both.  Built as a shared object and launched from a
-// Python probe on a stream of its own (tools/probes/cosched_probe.py): the chip clocks to its power budget, and what two
-// co-resident kernels draw together comes off the clock of both.
+// Python probe on a stream of its own (round 5's co-scheduling probe, profiles/r05_cosched.txt): the chip clocks to its
+// power budget, and what two co-resident kernels draw together comes off the clock of both.
 //   hipcc --offload-arch=gfx950 -O3 -shared -fPIC tools/ubench/clock_trace.hip -o tools/ubench/bin/libclock_trace.so
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,6 @@
 // coresident.hip -- do workgroups of TWO kernels, launched on two HIP streams, share a CU when their registers and LDS fit
 // side by side?  (Round 5: the half-CU instances of loop C and of the density pass fit on paper -- 4 waves x 248 VGPRs +
-// 84 KB next to 8 waves x 120 VGPRs + 70 KB -- and ran strictly one after the other: tools/probes/cosched_probe.py.)
+// 84 KB next to 8 waves x 120 VGPRs + 70 KB -- and ran strictly one after the other: profiles/r05_cosched.txt.)
 //
 // Kernel A and kernel B spin for a fixed time (s_memrealtime, 100 MHz); every workgroup records where it ran (XCC id, CU
 // id from HW_REG_HW_ID) and when.  Per case the program prints the wall time of {A on stream 1 || B on stream 2} next to
