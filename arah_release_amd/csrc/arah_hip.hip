@@ -3720,8 +3720,9 @@ int arah_counters_read(const void* workspace, ArahCounters* h_out, void* stream)
 // ---- unit seams -----------------------------------------------------------------------------
 int arah_sdf_eval(const ArahFrame* f, const float* x_norm, int32_t n, float* sdf, float* feat, float* grad,
                   void* workspace, size_t wbytes, void* stream) {
-    if (!f || !x_norm || !sdf || n < 0 || !workspace) return ARAH_E_BADARG;
-    if (n == 0) return ARAH_OK;
+    if (!f || n < 0 || !workspace) return ARAH_E_BADARG;
+    if (n == 0) return ARAH_OK;   // an empty point list carries no buffers (a null pointer is what an empty tensor has)
+    if (!x_norm || !sdf) return ARAH_E_BADARG;
     Workspace w = carve(workspace, 1, 1);
     if (wbytes < w.bytes) return ARAH_E_WORKSPACE;
     if (int arc = setup_attributes()) return arc;
@@ -3803,8 +3804,9 @@ int arah_rasterize(const float* tri_uvz, int32_t n_faces, int32_t H, int32_t W, 
 
 int arah_skin_lbs(const ArahFrame* f, const float* x_hat, int32_t n, float* wout, float* x_bar, float* T,
                   void* workspace, size_t wbytes, void* stream) {
-    if (!f || !x_hat || n < 0 || !workspace) return ARAH_E_BADARG;
+    if (!f || n < 0 || !workspace) return ARAH_E_BADARG;
     if (n == 0) return ARAH_OK;
+    if (!x_hat) return ARAH_E_BADARG;
     Workspace w = carve(workspace, 1, 1);
     if (wbytes < w.bytes) return ARAH_E_WORKSPACE;
     if (int arc = setup_attributes()) return arc;
@@ -3853,8 +3855,9 @@ int arah_marching_cubes(const float* sdf, int32_t n_side, float level, const int
 
 int arah_skin_jacobian(const ArahFrame* f, const float* x_hat, int32_t n, float* jac, void* workspace, size_t wbytes,
                        void* stream) {
-    if (!f || !x_hat || !jac || n < 0 || !workspace) return ARAH_E_BADARG;
+    if (!f || n < 0 || !workspace) return ARAH_E_BADARG;
     if (n == 0) return ARAH_OK;
+    if (!x_hat || !jac) return ARAH_E_BADARG;
     Workspace w = carve(workspace, 1, 1);
     if (wbytes < w.bytes) return ARAH_E_WORKSPACE;
     if (int arc = setup_attributes()) return arc;
@@ -3866,9 +3869,10 @@ int arah_skin_jacobian(const ArahFrame* f, const float* x_hat, int32_t n, float*
 
 int arah_color_eval(const ArahFrame* f, const float* x_norm, const float* normal, const float* view,
                     const float* feat, int32_t n, float* rgb, void* workspace, size_t wbytes, void* stream) {
-    if (!f || !x_norm || !normal || !feat || !rgb || n < 0 || !workspace) return ARAH_E_BADARG;
-    if (f->col_mode == ARAH_COLOR_IDR && !view) return ARAH_E_BADARG;
+    if (!f || n < 0 || !workspace) return ARAH_E_BADARG;
     if (n == 0) return ARAH_OK;
+    if (!x_norm || !normal || !feat || !rgb) return ARAH_E_BADARG;
+    if (f->col_mode == ARAH_COLOR_IDR && !view) return ARAH_E_BADARG;
     Workspace w = carve(workspace, 1, 1);
     if (wbytes < w.bytes) return ARAH_E_WORKSPACE;
     if (int arc = setup_attributes()) return arc;
@@ -4245,8 +4249,9 @@ static int shade_tail(const ArahFrame* f, const ArahSampling* cfg, Workspace& w,
 int arah_shade_points(const ArahFrame* f, const float* x_norm, const float* T, const float* dirs, int32_t n,
                       int32_t cano_view_dirs, int32_t shade_engine, float* rgbs, float* sdfn, void* workspace, size_t wbytes,
                       void* stream) {
-    if (!f || !x_norm || !T || !dirs || !rgbs || !sdfn || n < 0 || !workspace) return ARAH_E_BADARG;
+    if (!f || n < 0 || !workspace) return ARAH_E_BADARG;
     if (n == 0) return ARAH_OK;
+    if (!x_norm || !T || !dirs || !rgbs || !sdfn) return ARAH_E_BADARG;
     Workspace w = carve(workspace, n, 1);
     if (wbytes < w.bytes) return ARAH_E_WORKSPACE;
     if (int arc = setup_attributes()) return arc;

@@ -242,6 +242,7 @@ int arah_counters_reset(void* workspace, void* stream);
 int arah_counters_read(const void* workspace, ArahCounters* h_out, void* stream); /* syncs the stream */
 
 /* ---- unit seams (parity tests; also usable on their own) --------------------------------- */
+/* n_pts = 0 is accepted by every seam: nothing is read or written, and the point / output pointers may be null */
 /* x_norm [P,3] -> sdf [P] (normalised units), optional feat [P,256], optional grad [P,3] */
 int arah_sdf_eval(const ArahFrame* h_frame, const float* x_norm, int32_t n_pts, float* sdf, float* feat,
                   float* grad, void* workspace, size_t workspace_bytes, void* stream);

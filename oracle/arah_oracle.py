@@ -18,6 +18,7 @@ root_finding_utils.py (paths relative to the reference root).
 All point sets are flat: (P,3).  The reference's batch dimension is folded into the ray
 dimension (it flattens to (1,-1,3) itself, RT:178-184) with a per-ray camera origin.
 """
+import dataclasses
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
@@ -59,6 +60,21 @@ class Frame:
     def sdf_scale(self):
         # normalised SDF -> metres: sdf / 2 * 1.1 * (max - min)   (RT:528, IDR:359)
         return (self.coord_max - self.coord_min) * 1.1 / 2.0
+
+
+def frame_as(fr, dtype):
+    """A copy of ``fr`` with every floating-point tensor (nested layer tuples included) cast to ``dtype`` and fresh
+    counters; python floats, strings and ints are left alone.  ``frame_as(fr, torch.float64)`` turns every function of
+    this module that takes a Frame into a high-precision reference of the same arithmetic: they follow the dtype of
+    their inputs (tests/test_pointwise_f64.py pins that view against the reference's own fp32 outputs)."""
+    def cast(v):
+        if isinstance(v, torch.Tensor):
+            return v.to(dtype) if v.is_floating_point() else v.clone()
+        if isinstance(v, (list, tuple)):
+            return type(v)(cast(u) for u in v)
+        return v
+    kw = {f.name: cast(getattr(fr, f.name)) for f in dataclasses.fields(fr) if f.name != "counters"}
+    return Frame(**kw)
 
 
 # ----------------------------------------------------------------------------- coordinates
@@ -453,18 +469,18 @@ def shade_composite(fr, pts, z, T, mask, view_dirs, n_steps, cano_view_dirs, ren
     beta = min(max(abs(fr.beta), 1e-6), 1e6)
     inv_beta = 1.0 / beta
     dens = torch.relu(inv_beta * (0.5 + 0.5 * torch.sign(-sdf) * (1 - torch.exp(-sdf.abs() * inv_beta))))
-    rgb_s = torch.zeros(n, S, 3)
-    den_s = torch.zeros(n, S)
-    z_s = torch.full((n, S), 1e10)
+    rgb_s = torch.zeros(n, S, 3, dtype=z.dtype)
+    den_s = torch.zeros(n, S, dtype=z.dtype)
+    z_s = torch.full((n, S), 1e10, dtype=z.dtype)
     rgb_s[packed], den_s[packed], z_s[packed] = rgb, dens, z[mask]
     delta = z_s[:, 1:] - z_s[:, :-1]
     if render_last_pt:
-        delta = torch.cat([delta, torch.full((n, 1), 1e10)], dim=-1)
+        delta = torch.cat([delta, torch.full((n, 1), 1e10, dtype=z.dtype)], dim=-1)
     else:
-        delta = torch.cat([delta, torch.full((n, 1), 1.0 / n_steps)], dim=-1)
+        delta = torch.cat([delta, torch.full((n, 1), 1.0 / n_steps, dtype=z.dtype)], dim=-1)
         delta[torch.arange(n), lengths - 1] = 1.0 / n_steps
     alpha = 1.0 - torch.exp(-den_s * delta)
-    trans = torch.cumprod(torch.cat([torch.ones(n, 1), 1.0 - alpha + 1e-7], dim=-1), dim=-1)[:, :-1]
+    trans = torch.cumprod(torch.cat([torch.ones(n, 1, dtype=z.dtype), 1.0 - alpha + 1e-7], dim=-1), dim=-1)[:, :-1]
     w = alpha * trans
     acc = (w * packed).sum(-1, keepdim=True).clamp(0, 1)
     return (rgb_s * (w * packed)[..., None]).sum(1), acc

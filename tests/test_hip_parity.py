@@ -238,7 +238,7 @@ def ctx_fp32(scene):
 @pytest.mark.parametrize("eng", ENGINES)
 def test_sdf_eval(ctx, ctx_fp32, eng):
     ctx = ctx if eng == "split" else ctx_fp32
-    g = golden("f3_sdf.npz")
+    g = golden("f3_sdf.npz")   # the reference's recorded outputs; precision over the whole domain: tests/test_pointwise_f64.py
     hip = ctx["hip"]
     sdf, feat, grad = hip.sdf_eval(ctx["frame"], ctx["ws"], T(g["x_norm"]), want_feat=True, want_grad=True)
     # SURVEY 8c tolerances for fp32 kernels (rtol 1e-4 / atol 1e-5), on both engines; measured worst absolute errors
@@ -281,7 +281,7 @@ def test_wide_range_skinning_network(scene, eng):
 
 @gpu
 def test_skin_lbs_and_jacobian(ctx):
-    g = golden("f2_pointwise.npz")
+    g = golden("f2_pointwise.npz")   # the reference's recorded outputs; precision over the whole domain: tests/test_pointwise_f64.py
     hip = ctx["hip"]
     w, xb, Tm = hip.skin_lbs(ctx["frame"], ctx["ws"], T(g["x_hat"]))
     np.testing.assert_allclose(w.cpu().numpy(), g["weights"], rtol=1e-4, atol=1e-5)
@@ -296,7 +296,7 @@ def test_skin_lbs_and_jacobian(ctx):
 @pytest.mark.parametrize("name", ["zju377_mono", "zju313"])
 def test_color_eval(scene, name):
     from arah_release_amd import hip, renderer
-    g = golden("f4_color_%s.npz" % name)
+    g = golden("f4_color_%s.npz" % name)   # the reference's recorded outputs; precision over the whole domain: tests/test_pointwise_f64.py
     dev = torch.device("cuda:0")
     model, cfg = get_model(name, dev)
     inputs = scene.make_inputs(64, 64, frame_idx=0, device=dev)
@@ -326,7 +326,7 @@ def test_shade_points_on_the_shipped_engine(scene, name, eng):
     Bounds ("a documented looser bound where fp16/bf16 MFMA is used"): bf16 x 3 carries 16 significant bits per
     operand, 2^-16 per product against 2^-24: gradient entries (|g| up to 1.2 here) within 3e-5 + 1e-4 |g| (measured worst
     1.03e-5; exact engine 2.6e-6), colours within 1e-5 absolute (measured 1.1e-6; exact engine 2.4e-7); the exact engine
-    within the fp32 seams' 1e-4 / 1e-5 and 5e-6."""
+    within the fp32 seams' 1e-4 / 1e-5 and 5e-6.  (Against float64, near the surface and over the whole domain: tests/test_pointwise_f64.py.)"""
     from arah_release_amd import hip, renderer
     from oracle import arah_oracle as O
     dev = torch.device("cuda:0")
