@@ -343,14 +343,26 @@ class LightningModel(nn.Module):
         nrm[nrm.isnan()] = -1
         return ((nrm + 1) / 2.0).clip(0.0, 1.0)
 
-    def validation_step(self, data, data_idx=None, ssim_fn=None, lpips_fn=None):
+    def validation_step(self, data, data_idx=None, ssim_fn=None, lpips_fn=None, metrics=None, data_range=2.0):
         """lightning_model.py:160-230: predicted image, normal map (the canonical-mesh one when the model produced it, else
         finite differences of the surface points), ground-truth image, PSNR (im2mesh/utils/eval.py:6-9).  SSIM and LPIPS
-        come from skimage / lpips in the reference: pass callables (pred HxWx3, gt HxWx3, box mask) to have them filled."""
+        come from skimage / lpips in the reference: pass callables (pred HxWx3, gt HxWx3, box mask) to have them filled.
+
+        metrics="device": 'psnr' and 'ssim' are 0-dimensional float64 tensors ON THE DEVICE (hip.image_metrics: the
+        reference's two formulas in float64, SSIM with data_range R -- 2.0 is scikit-image 0.18.1's choice for float images),
+        with 'metrics_status' (int32, hip.METRICS_STATUS) beside them; this path copies nothing to the host
+        and never waits for the stream, so the step can run under renderer.map_in_flight.  validation_epoch_end reads the
+        values.  lpips_fn still works there and still costs its host copies; ssim_fn belongs to the host route (metrics=None)."""
+        if metrics not in (None, "device"):
+            raise ValueError("metrics must be None or 'device', not %r" % (metrics,))
+        if metrics == "device" and ssim_fn is not None:
+            raise ValueError("metrics='device' computes 'ssim' itself: pass ssim_fn or metrics='device', not both")
         import numpy as np
         out = self.render_image(data, gen_cano_mesh=False)
         mask = data.get("inputs.image_mask")
-        n = int(mask.sum())
+        device_metrics = metrics == "device"
+        # the number of rays IS the number of set mask pixels (the item's rays are the mask's pixels): the shape costs no copy
+        n = int(out["rgb_values"].reshape(-1, 3).shape[0]) if device_metrics else int(mask.sum())
         pred_pixels = out["image"].squeeze(0)
         if "output_normal" in out:
             pred_normals = out["output_normal"].squeeze(0)
@@ -362,17 +374,70 @@ class LightningModel(nn.Module):
         gt_pixels = torch.zeros(*mask.shape, 3, device=mask.device)
         gt_pixels.masked_scatter_(mask.unsqueeze(-1), image.reshape(-1, 3)[:n])
         gt_pixels = gt_pixels.squeeze(0)
-        pred_img = out["rgb_values"].reshape(-1, 3).detach().cpu().numpy()
-        gt_img = image.reshape(-1, 3).detach().cpu().numpy()
-        with np.errstate(divide="ignore"):   # identical images: the reference's formula gives inf (with numpy's warning)
-            res = {"psnr": -10 * np.log(np.mean((pred_img - gt_img) ** 2)) / np.log(10)}
-        box = mask.squeeze(0).detach().cpu().numpy()
+        if device_metrics:
+            from . import hip
+            vals, rect = hip.image_metrics(pred_pixels, gt_pixels, mask.squeeze(0), data_range=data_range)
+            res = {"psnr": vals[0], "ssim": vals[1], "metrics_status": rect[4]}
+        else:
+            pred_img = out["rgb_values"].reshape(-1, 3).detach().cpu().numpy()
+            gt_img = image.reshape(-1, 3).detach().cpu().numpy()
+            with np.errstate(divide="ignore"):   # identical images: the reference's formula gives inf (with numpy's warning)
+                res = {"psnr": -10 * np.log(np.mean((pred_img - gt_img) ** 2)) / np.log(10)}
+        if device_metrics and lpips_fn is None:
+            box = None                           # nothing leaves the device
+        else:
+            box = mask.squeeze(0).detach().cpu().numpy()
         if ssim_fn is not None:
             res["ssim"] = ssim_fn(pred_pixels.detach().cpu().numpy(), gt_pixels.detach().cpu().numpy(), box)
         if lpips_fn is not None:
             res["lpips"] = lpips_fn(pred_pixels.detach().cpu().numpy(), gt_pixels.detach().cpu().numpy(), box)
         res.update({"rgb_pred": pred_pixels.permute(2, 0, 1), "normal_pred": pred_normals.permute(2, 0, 1),
                     "rgb_gt": gt_pixels.permute(2, 0, 1)})
+        return res
+
+    def validation_epoch_end(self, outputs, first_index=0, index_stride=1):
+        """lightning_model.py:232-298 without Lightning: the per-frame metrics of `outputs` (this rank's validation_step
+        results, frames first_index, first_index + index_stride, ...) are read to the host, gathered over the ranks of an
+        initialised torch.distributed group and put in frame order.  Frames are sharded frame i -> rank i mod N WITHOUT
+        padding, so no frame is seen twice and nothing has to be trimmed to val_size (the reference's DistributedSampler pads,
+        hence its trimming).  Rank 0 returns {"psnr", "ssim", ["lpips"], "n", "n_psnr_inf", "frames"}: means over all frames
+        -- a frame whose PSNR is +inf (prediction == ground truth) is counted in n_psnr_inf and left out of the PSNR mean
+        instead of turning it into inf -- and the per-frame values; other ranks return None.  A frame whose device metrics
+        carry a status != 0 (empty ray mask, rectangle smaller than the SSIM window) raises ValueError naming the frame, on
+        every rank.  Images are not gathered: logging them is the caller's (DESIGN.md section 9)."""
+        import math
+        rows = []
+        for k, out in enumerate(outputs):
+            idx = first_index + k * index_stride
+            status = out.get("metrics_status")
+            row = {"frame": idx, "status": int(status) if status is not None else 0}
+            for key in ("psnr", "ssim", "lpips"):
+                if key in out:
+                    row[key] = float(out[key])
+            rows.append(row)
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            gathered = [None] * dist.get_world_size()
+            dist.all_gather_object(gathered, rows)
+            rows = [r for part in gathered for r in part]
+            rank = dist.get_rank()
+        else:
+            rank = 0
+        rows.sort(key=lambda r: r["frame"])
+        from . import hip
+        for r in rows:
+            if r["status"] != 0:
+                raise ValueError("validation frame %d has no SSIM: %s" % (r["frame"], hip.METRICS_STATUS.get(r["status"], r["status"])))
+        if rank != 0:
+            return None
+        res = {"n": len(rows), "frames": rows}
+        finite = [r["psnr"] for r in rows if "psnr" in r and not math.isinf(r["psnr"])]
+        res["n_psnr_inf"] = sum(1 for r in rows if "psnr" in r and math.isinf(r["psnr"]))
+        res["psnr"] = sum(finite) / len(finite) if finite else float("nan")
+        for key in ("ssim", "lpips"):
+            vals = [r[key] for r in rows if key in r]
+            if vals:
+                res[key] = sum(vals) / len(vals)
         return res
 
     def test_step(self, data, data_idx=None):

@@ -2748,6 +2748,7 @@ __global__ void k_points_cam(FrameDev fr, int n, RaySet rs, const float* dists, 
 }  // namespace
 #include "train.hpp"
 #include "meshquery.hpp"
+#include "metrics.hpp"
 namespace {
 
 // ------------------------------------------------------------------------------------------
@@ -4916,6 +4917,31 @@ int arah_mesh_query(const float* verts, int32_t n_verts, const int32_t* faces, i
     else
         hipLaunchKernelGGL(k_mesh_query<float>, dim3(g), dim3(kMeshThreads), 0, s, verts, faces, n_faces, (const MeshBox*)box,
                            reinterpret_cast<const float*>(pts), n_pts, d2, face, closest, bary, inside);
+    return check_launch();
+}
+
+// ---- image metrics of a validation frame (metrics.hpp) --------------------------------------------------------
+size_t arah_image_metrics_bytes(int32_t height, int32_t width) {
+    if (height < 1 || width < 1) return 0;
+    return carve_metrics(nullptr, height, width).bytes;
+}
+
+int arah_image_metrics(const float* pred, const float* gt, const uint8_t* box_mask, int32_t height, int32_t width,
+                       double data_range, double* out, int32_t* rect, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!pred || !gt || !box_mask || !out || !rect || !scratch || height < 1 || width < 1 || !(data_range > 0.0))
+        return ARAH_E_BADARG;
+    if ((long long)height * width > (1ll << 30)) return ARAH_E_BADARG;
+    const MetricsScratch m = carve_metrics(scratch, height, width);
+    if (scratch_bytes < m.bytes) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const double c1 = (0.01 * data_range) * (0.01 * data_range), c2 = (0.03 * data_range) * (0.03 * data_range);
+    hipLaunchKernelGGL(k_metrics_mse, dim3(m.n_mse_blocks), dim3(kMetThreads), 0, s, pred, gt, box_mask, height, width, m.mse_part,
+                       m.cnt_part, m.bnd_part);
+    hipLaunchKernelGGL(k_metrics_rect, dim3(1), dim3(kMetThreads), 0, s, (const int*)m.bnd_part, m.n_mse_blocks, m.bounds);
+    hipLaunchKernelGGL(k_metrics_ssim, dim3(m.tiles_x, m.tiles_y, 3), dim3(kMetThreads), 0, s, pred, gt, height, width,
+                       (const int*)m.bounds, c1, c2, m.ssim_part);
+    hipLaunchKernelGGL(k_metrics_finish, dim3(1), dim3(kMetThreads), 0, s, (const int*)m.bounds, (const double*)m.mse_part,
+                       (const unsigned*)m.cnt_part, m.n_mse_blocks, (const double*)m.ssim_part, m.tiles_x * m.tiles_y, out, rect);
     return check_launch();
 }
 

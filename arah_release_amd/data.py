@@ -353,6 +353,26 @@ def training_item(model, camera, body, faces, image, mask, mask_erode, img_size,
     return item
 
 
+def validation_item(model, camera, body, image, mask_erode, img_size, orig_img_size, box_margin=0.05, device="cuda", **ids):
+    """A validation / test item of a capture (ZJUMOCAPDataset.__getitem__ with mode != 'train', zju_mocap.py:399-433, 603-607)
+    on the device: `frame_item` of the frame -- every pixel of the projected body box whose ray hits the box, in
+    `inputs.image_mask` order -- with `inputs` = the prepared image's colours at those rays, black where mask_erode == 0 (the
+    rim value 100 keeps its colour).  image (H,W,3) in [0,1] and mask_erode (H,W): already undistorted and resized.  The item
+    carries NO 'inputs.novel_seq': the capture datasets never emit it, and its presence makes compose_inputs drop the frame
+    index, i.e. the frame's latent code and its optimised SMPL parameters (lightning_model.py:497-498)."""
+    item = frame_item(model, camera, body, img_size, orig_img_size, box_margin=box_margin, device=device, **ids)
+    item.pop("inputs.novel_seq", None)
+    image = torch.as_tensor(image, dtype=torch.float32, device=device)
+    mask_erode = torch.as_tensor(mask_erode, device=device)
+    image_mask = item["inputs.image_mask"][0]
+    if tuple(image.shape[:2]) != tuple(image_mask.shape) or tuple(mask_erode.shape) != tuple(image_mask.shape):
+        raise ValueError("image %s / mask %s do not have the item's size %s" % (tuple(image.shape), tuple(mask_erode.shape),
+                                                                                tuple(image_mask.shape)))
+    pixels = torch.where((mask_erode == 0).unsqueeze(-1), torch.zeros_like(image), image)
+    item["inputs"] = pixels[image_mask].unsqueeze(0)          # boolean indexing walks the mask row-major, like np.where
+    return item
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the out-of-distribution-pose test dataset (reference ZJUMOCAPODPDataset, data/zju_mocap_odp.py:20-120) and its factory
 # ---------------------------------------------------------------------------------------------------------------------
@@ -496,6 +516,21 @@ class TrainingDataset:
                              frame_idx=d["frame_idx"], data_idx=d["data_idx"], gender=d["gender"])
 
 
+    def validation_item(self, idx, device):
+        """Item `idx` as the reference's dataset returns it in mode 'val' / 'test' (`validation_item` above): the whole
+        projected box with its ground-truth colours, the image pair read and prepared exactly as `item` does."""
+        from PIL import Image
+        d = self.data[idx]
+        cam = self.cameras[d["cam_name"]]
+        image = torch.as_tensor(np.array(Image.open(d["img_file"]).convert("RGB")), device=device).float()
+        mask = torch.as_tensor(np.array(Image.open(d["mask_file"]).convert("L")), device=device)
+        K, D = torch.as_tensor(np.asarray(cam["K"], np.float32)), np.asarray(cam["D"], np.float64).ravel()
+        image, mask, rim, orig = self._prepare(image, mask, self._rim(mask), K, D)
+        return validation_item(load_model_npz(d["model_file"]), cam, self.body, image, rim, self.img_size, orig,
+                               box_margin=self.box_margin, device=device, cam_idx=d["cam_idx"], frame_idx=d["frame_idx"],
+                               data_idx=d["data_idx"], gender=d["gender"])
+
+
 class H36MDataset(TrainingDataset):
     """Human3.6M captures (reference data/h36m.py): the subject's files sit under <subject>/Posing, the image is reduced to
     img_size FIRST (INTER_AREA) and undistorted at that size with intrinsics that already refer to it, the mask rim is left
@@ -545,3 +580,26 @@ class PeopleSnapshotDataset(TrainingDataset):
 
     def _gender(self, subject):
         return "female" if "female" in subject else "male"
+
+
+def get_capture_dataset(mode, cfg, body=None, faces=None, body_models="body_models/misc"):
+    """im2mesh.config.get_dataset for the three capture formats (reference im2mesh/config.py:78-250): split, views, frame range
+    and subsampling rate of `mode` (train / val / test) from cfg['data'], and the reference's image sizes -- ZJU 512 (1024 for
+    high_res training only), People-Snapshot 540 (1080 for high_res training only), H36M 1002 x 1000."""
+    d, t_cfg = cfg["data"], cfg.get("training", {})
+    if mode not in ("train", "val", "test"):
+        raise ValueError("Invalid mode %r" % mode)
+    big = bool(d.get("high_res")) and mode == "train"
+    kinds = {"zju_mocap": (TrainingDataset, (1024, 1024) if big else (512, 512)),
+             "h36m": (H36MDataset, (1002, 1000)),
+             "people_snapshot": (PeopleSnapshotDataset, (1080, 1080) if big else (540, 540))}
+    if d["dataset"] not in kinds:
+        raise ValueError('Invalid dataset "%s"' % d["dataset"])
+    cls, img_size = kinds[d["dataset"]]
+    return cls(d["path"], subjects=d[mode + "_split"], mode=mode, img_size=img_size, num_fg_samples=d["num_fg_samples"],
+               num_bg_samples=d["num_bg_samples"], sampling_rate=d[mode + "_subsampling_rate"],
+               start_frame=d[mode + "_start_frame"], end_frame=d[mode + "_end_frame"], views=d[mode + "_views"],
+               off_surface_thr=d["off_surface_thr"], inside_thr=d["inside_thr"], box_margin=d["box_margin"],
+               sampling=d["sampling"], sample_reg_surface=d["sample_reg_surface"],
+               sample_inside=t_cfg.get("inside_weight", 0) > 0, erode_mask=d["erode_mask"], body=body, faces=faces,
+               body_models=body_models)

@@ -131,7 +131,8 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_occupancy_bytes", "arah_prepare_occupancy", "arah_occupancy_info", "arah_tier_debug", "arah_debug_samples",
            "arah_sdf_grid_band_scratch_bytes", "arah_sdf_grid_band", "arah_tier_audit_bytes", "arah_tier_audit",
            "arah_tier_audit_debug", "arah_occupancy_clear_box", "arah_render_maps_bytes", "arah_render_maps",
-           "arah_query_posed_bytes", "arah_query_posed", "arah_sdf_grid_posed_bytes", "arah_sdf_grid_posed"]
+           "arah_query_posed_bytes", "arah_query_posed", "arah_sdf_grid_posed_bytes", "arah_sdf_grid_posed",
+           "arah_image_metrics_bytes", "arah_image_metrics"]
 
 _lib = None
 
@@ -165,6 +166,8 @@ def load_library():
     lib.arah_query_posed_bytes.argtypes = [C.c_int32]
     lib.arah_sdf_grid_posed_bytes.restype = C.c_size_t
     lib.arah_sdf_grid_posed_bytes.argtypes = [C.c_int32]
+    lib.arah_image_metrics_bytes.restype = C.c_size_t
+    lib.arah_image_metrics_bytes.argtypes = [C.c_int32, C.c_int32]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the symbol is missing
     _lib = lib
@@ -713,6 +716,48 @@ def marching_cubes(sdf, level=0.0, cap=1 << 20):
                                        C.c_int32(int(cap)), _ptr(n_tris), _ptr(scratch), C.c_size_t(scratch.numel()), _stream()),
                "arah_marching_cubes")
     return tris, n_tris
+
+
+METRICS_STATUS = {0: "ok", 1: "the frame's ray mask is empty",
+                  2: "the mask's bounding rectangle is narrower or lower than the 7 x 7 SSIM window"}
+
+
+def image_metrics(pred, gt, box_mask, data_range=2.0):
+    """PSNR and SSIM of a rendered frame against its ground truth (im2mesh/utils/eval.py:6-18) on the device, in float64 and
+    WITHOUT a host round trip (arah_image_metrics): pred / gt (H,W,3) float images, box_mask (H,W) bool / uint8, non-zero = the
+    frame's rays (the reference's `mask_at_box`: PSNR over those pixels, SSIM on their bounding rectangle).  data_range: R of
+    C1 = (0.01 R)^2, C2 = (0.03 R)^2; 2.0 is what scikit-image 0.18.1 takes for float images, pass 1.0 to compare against a
+    call with data_range=1.  -> out (4,) float64 on the device: psnr, ssim, mse, number of masked pixels; rect (5,) int32: x, y,
+    w, h, status (METRICS_STATUS).  Nothing is checked here: `read_image_metrics` raises for a status != 0 when the result is
+    read.  Bit-reproducible: no atomics, fixed summation order."""
+    require_gpu()
+    lib = load_library()
+    dev = _same_device(pred, gt, box_mask)
+    p, g = _f32(pred), _f32(gt)
+    if p.dim() != 3 or p.shape[2] != 3 or g.shape != p.shape or tuple(box_mask.shape) != tuple(p.shape[:2]):
+        raise ValueError("pred, gt must be (H, W, 3) images of one size and box_mask (H, W)")
+    if not float(data_range) > 0.0:
+        raise ValueError("data_range must be positive")
+    m = box_mask.detach().contiguous()
+    m = m.view(torch.uint8) if m.dtype == torch.bool else m.to(torch.uint8)
+    H, W = int(p.shape[0]), int(p.shape[1])
+    with _on_device(dev):
+        out = torch.empty(4, dtype=torch.float64, device=dev)
+        rect = torch.empty(5, dtype=torch.int32, device=dev)
+        scratch = torch.empty(int(lib.arah_image_metrics_bytes(H, W)), dtype=torch.uint8, device=dev)
+        _check(lib.arah_image_metrics(_ptr(p), _ptr(g), _ptr(m), C.c_int32(H), C.c_int32(W), C.c_double(float(data_range)),
+                                      _ptr(out), _ptr(rect), _ptr(scratch), C.c_size_t(scratch.numel()), _stream()),
+               "arah_image_metrics")
+    return out, rect
+
+
+def read_image_metrics(out, rect, what="the frame"):
+    """Host values of an `image_metrics` result (this is where the stream is waited for): {"psnr", "ssim", "mse", "n", "rect"}.
+    Raises ValueError, as scikit-image does for such a crop, when the status says that no SSIM exists."""
+    o, r = out.detach().cpu().tolist(), rect.detach().cpu().tolist()
+    if r[4] != 0:
+        raise ValueError("no SSIM for %s: %s (rectangle x %d y %d w %d h %d)" % (what, METRICS_STATUS.get(r[4], r[4]), *r[:4]))
+    return {"psnr": o[0], "ssim": o[1], "mse": o[2], "n": int(o[3]), "rect": tuple(r[:4])}
 
 
 @_guarded

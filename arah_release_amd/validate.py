@@ -1,0 +1,127 @@
+"""Score rendered frames against the captured images -- the reference's ``validate.py`` (validate.py:1-106) on this build.
+
+    python -m arah_release_amd.validate CONFIG.yaml                      # training views, the config's val frames
+    python -m arah_release_amd.validate CONFIG.yaml --novel-view         # every 30th frame of the val views
+    python -m arah_release_amd.validate CONFIG.yaml --novel-pose [--novel-pose-view 1]
+    python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m arah_release_amd.validate CONFIG.yaml ...
+
+Same arguments and the same overrides of the configuration as validate.py:42-50.  The model is sized from the TRAINING
+dataset (latent codes, optimised cameras and SMPL parameters: validate.py:57,65) and loaded from
+``<out_dir>/checkpoints/last.ckpt``; the frames come from the ``val`` dataset (``test`` with --novel-pose) as validation
+items (data.validation_item), go through ``LightningModel.validation_step(metrics="device")`` with
+renderer.frames_in_flight of them in flight -- PSNR and SSIM are computed on the GPU (hip.image_metrics) and read once per
+chunk -- and are aggregated by ``validation_epoch_end``.  With N processes frame i goes to rank i mod N.  Rank 0 prints one
+JSON line (means, frame count, seconds per frame) and writes the per-frame values to ``<out_dir>/validation.json``.
+LPIPS needs VGG weights that are not part of this build: ``--lpips MODULE:FUNCTION`` names a callable
+(pred HxWx3, gt HxWx3, box mask) -> float to import; without it no LPIPS is reported."""
+import argparse
+import importlib
+import json
+import os
+import time
+
+import torch
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="Validation function on with-distribution poses (ZJU training and testing).")
+    p.add_argument("config", type=str, help="Path to config file.")
+    p.add_argument("--novel-pose", action="store_true", help="Test on novel-poses.")
+    p.add_argument("--novel-pose-view", type=str, default=None,
+                   help="Novel view to use for rendering novel poses. Specify this argument if you only want to render a "
+                        "specific view of novel poses.")
+    p.add_argument("--novel-view", action="store_true", help="Test on novel-views of all training poses.")
+    p.add_argument("--multi-gpu", action="store_true", help="Accepted for compatibility (validate.py:31): frames are sharded "
+                                                            "over the ranks of torch.distributed.run whenever WORLD_SIZE > 1.")
+    p.add_argument("--num-workers", type=int, default=4, help="Accepted for compatibility: items are composed on the GPU.")
+    p.add_argument("--run-name", type=str, default="", help="Accepted for compatibility (the reference's Wandb run name).")
+    p.add_argument("--lpips", type=str, default=None, help="MODULE:FUNCTION of an LPIPS callable (pred, gt, box mask) -> float.")
+    p.add_argument("--data-range", type=float, default=2.0,
+                   help="SSIM data range: 2.0 is what scikit-image 0.18.1 takes for float images, 1.0 the images' own range.")
+    p.add_argument("--default-config", type=str, default="configs/default.yaml")
+    p.add_argument("--body-models", type=str, default="body_models/misc", help="Directory of the SMPL model files.")
+    return p
+
+
+def apply_overrides(cfg, args):
+    """validate.py:42-50."""
+    if args.novel_view and not args.novel_pose:          # novel-view synthesis on training poses: every 30th frame
+        cfg["data"]["val_subsampling_rate"] = 30
+    if args.novel_pose_view is not None:                 # view synthesis (training or testing views) on novel poses
+        assert args.novel_pose
+        cfg["data"]["test_subsampling_rate"] = 1
+        cfg["data"]["test_views"] = [args.novel_pose_view]
+    return cfg
+
+
+def load_callable(spec):
+    module, _, name = spec.partition(":")
+    if not module or not name:
+        raise ValueError("--lpips takes MODULE:FUNCTION, not %r" % spec)
+    return getattr(importlib.import_module(module), name)
+
+
+def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0):
+    """Frames rank, rank + world, ... of the dataset through validation_step with device metrics; -> (what
+    validation_epoch_end returns, frames this rank rendered, seconds it took).  Images are dropped chunk by chunk: only the
+    metric scalars of a frame stay."""
+    from . import renderer
+    lm = lm.to(device).eval()
+    mine = list(range(rank, len(dataset), world))
+    step = lambda item: lm.validation_step(item, lpips_fn=lpips_fn, metrics="device", data_range=data_range)
+    kept = []
+    torch.cuda.synchronize(device)
+    t0 = time.time()
+    for c in range(0, len(mine), 20):   # twenty frames resident at a time, renderer.frames_in_flight of them in flight
+        items = [dataset.validation_item(i, device) for i in mine[c:c + 20]]
+        outs = renderer.map_in_flight(step, items, owner=lm.model)
+        kept += [{k: v for k, v in o.items() if k in ("psnr", "ssim", "lpips", "metrics_status")} for o in outs]
+    torch.cuda.synchronize(device)
+    seconds = time.time() - t0
+    return lm.validation_epoch_end(kept, first_index=rank, index_stride=world), len(mine), seconds
+
+
+def main(argv=None, body=None, faces=None, log=print):
+    from . import config, data
+    args = build_parser().parse_args(argv)
+    cfg = apply_overrides(config.load_config(args.config, args.default_config), args)
+    out_dir = cfg["training"]["out_dir"]
+    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    checkpoint_path = os.path.join(out_dir, "checkpoints/last.ckpt")
+    if not os.path.exists(checkpoint_path):
+        raise FileNotFoundError("No checkpoint is found!")          # validate.py:88-90
+    if not torch.cuda.is_available():
+        raise SystemExit("validate needs a GPU (the renderer has no CPU fallback)")
+    torch.cuda.set_device(local)
+    device = torch.device("cuda", local)
+    train_dataset = data.get_capture_dataset("train", cfg, body=body, faces=faces, body_models=args.body_models)
+    val_dataset = data.get_capture_dataset("test" if args.novel_pose else "val", cfg, body=train_dataset.body,
+                                           faces=train_dataset.faces, body_models=args.body_models)
+    # mode "val": sized from the training dataset like the reference's construction, without reading the MetaAvatar
+    # initialisation files the checkpoint is about to replace
+    lm = config.get_model(cfg, dataset=train_dataset, val_size=len(val_dataset), mode="val", checkpoint_path=checkpoint_path,
+                          body_model=train_dataset.body)
+    dist = None
+    if world > 1:
+        import torch.distributed as dist
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=device)
+    lpips_fn = load_callable(args.lpips) if args.lpips else None
+    res, n_mine, seconds = validate(lm, val_dataset, device, rank, world, lpips_fn, args.data_range)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+    if res is None:
+        return None
+    frames = res.pop("frames")
+    res.update(seconds_per_frame=seconds / max(1, n_mine), world=world, data_range=args.data_range,
+               mode="test" if args.novel_pose else "val")
+    with open(os.path.join(out_dir, "validation.json"), "w") as f:
+        json.dump(dict(res, frames=frames), f, indent=1)
+    log(json.dumps(res))
+    return res
+
+
+if __name__ == "__main__":
+    main()

@@ -39,6 +39,8 @@
  *                           ray_tracing.py:403-461, implicit_differentiable_renderer.py:336-359
  *   arah_sdf_grid_posed     the same on a lattice of posed space (no reference counterpart: the reference meshes the canonical
  *                           lattice only and skins that mesh forward, models/__init__.py:209-227)
+ *   arah_image_metrics      psnr_metric / ssim_metric of a validation frame  im2mesh/utils/eval.py:6-18
+ *                           (skimage.metrics.structural_similarity + cv2.boundingRect; called at lightning_model.py:216-224)
  *   arah_mesh_query         check_mesh_contains + igl.point_mesh_squared_distance + igl.barycentric_coordinates_tri
  *                           im2mesh/utils/libmesh/inside_mesh.py:4-160, im2mesh/data/zju_mocap.py:466-529
  *
@@ -427,6 +429,23 @@ size_t arah_mesh_query_scratch_bytes(void);
 int arah_mesh_query(const float* verts, int32_t n_verts, const int32_t* faces, int32_t n_faces, const void* pts,
                     int32_t pts_are_f64, int32_t n_pts, double* d2, int32_t* face, double* closest, double* bary,
                     uint8_t* inside, void* scratch, void* stream);
+
+/* PSNR and SSIM of a rendered frame against its ground-truth image (im2mesh/utils/eval.py:6-18; csrc/metrics.hpp), without a host
+ * round trip.  pred / gt (H,W,3) fp32 interleaved, box_mask (H,W) uint8, non-zero = the frame's rays.  All arithmetic is float64 on
+ * the fp32 pixels; no atomics: the same inputs give the same bits.
+ *   mse  = mean over the masked pixels' 3 channels of (pred - gt)^2;  psnr = -10 log10(mse), +inf for mse == 0
+ *   rect = bounding rectangle of the non-zero mask bytes (x, y, w, h as cv2.boundingRect), found on the device
+ *   ssim = skimage.metrics.structural_similarity 0.18.1 (multichannel, 7 x 7 uniform window, sample covariance, C1 = (0.01 R)^2,
+ *          C2 = (0.03 R)^2, mean over the window centres >= 3 pixels from every edge, then over the channels) on the crop
+ *          [y:y+h, x:x+w] of both images, R = data_range (skimage's default for float images: 2).  Only windows wholly inside the
+ *          crop are read, nothing outside it.
+ * out [4] DEVICE doubles: psnr, ssim, mse, number of masked pixels.  rect [5] DEVICE: x, y, w, h, status -- 0 ok, 1 empty mask
+ * (psnr, ssim, mse NaN; rect 0), 2 crop narrower or lower than 7 (ssim NaN, psnr / mse valid).  scratch:
+ * arah_image_metrics_bytes(height, width) bytes, 8-byte aligned (the rectangle's bounds and per-workgroup partial sums and rectangles, folded
+ * in index order).  No host synchronisation. */
+size_t arah_image_metrics_bytes(int32_t height, int32_t width);
+int arah_image_metrics(const float* pred, const float* gt, const uint8_t* box_mask, int32_t height, int32_t width,
+                       double data_range, double* out, int32_t* rect, void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---- the hot path ----------------------------------------------------------------------- */
 /* rays: cam_loc [n_cams,3], ray r belongs to camera r / rays_per_cam; dirs [N,3]; near_far [N,2].
