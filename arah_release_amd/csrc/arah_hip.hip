@@ -2749,6 +2749,7 @@ __global__ void k_points_cam(FrameDev fr, int n, RaySet rs, const float* dists, 
 #include "train.hpp"
 #include "meshquery.hpp"
 #include "metrics.hpp"
+#include "meshdist.hpp"
 namespace {
 
 // ------------------------------------------------------------------------------------------
@@ -4942,6 +4943,79 @@ int arah_image_metrics(const float* pred, const float* gt, const uint8_t* box_ma
                        (const int*)m.bounds, c1, c2, m.ssim_part);
     hipLaunchKernelGGL(k_metrics_finish, dim3(1), dim3(kMetThreads), 0, s, (const int*)m.bounds, (const double*)m.mse_part,
                        (const unsigned*)m.cnt_part, m.n_mse_blocks, (const double*)m.ssim_part, m.tiles_x * m.tiles_y, out, rect);
+    return check_launch();
+}
+
+// ---- exact distance to large triangle soups and the geometry scores (meshdist.hpp) ---------------------------
+size_t arah_mesh_index_bytes(int32_t n_faces) {
+    if (n_faces < 1) return 0;
+    return carve_mesh_index(nullptr, n_faces).bytes;
+}
+
+int arah_mesh_index_build(const float* tris, int32_t n_faces, void* index, size_t index_bytes, void* stream) {
+    if (!tris || !index || n_faces < 1 || n_faces > (1 << 26) || (reinterpret_cast<uintptr_t>(index) & 255) != 0) return ARAH_E_BADARG;
+    const MdIndex m = carve_mesh_index(index, n_faces);
+    if (index_bytes < m.bytes) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (hipMemsetAsync(m.cell_count, 0, sizeof(int) * (size_t)m.cap_cells, s) != hipSuccess) return ARAH_E_LAUNCH;
+    const int fg = (n_faces + kMdThreads - 1) / kMdThreads, cg = (m.cap_cells + kMdThreads - 1) / kMdThreads;
+    hipLaunchKernelGGL(k_md_stats, dim3(kMdStatBlocks), dim3(kMdThreads), 0, s, tris, (int)n_faces, m.stat);
+    hipLaunchKernelGGL(k_md_header, dim3(1), dim3(kMdStatBlocks), 0, s, (const double*)m.stat, (int)n_faces, m.cap_cells, m.hdr);
+    hipLaunchKernelGGL(k_md_bin<false>, dim3(fg), dim3(kMdThreads), 0, s, tris, (int)n_faces, m.hdr, m.cell_count,
+                       (const int*)m.cell_base, m.refs, m.big);
+    hipLaunchKernelGGL(k_md_scan, dim3(1), dim3(1024), 0, s, (const int*)m.cell_count, m.hdr, m.cell_base);
+    hipLaunchKernelGGL(k_md_bin<true>, dim3(fg), dim3(kMdThreads), 0, s, tris, (int)n_faces, m.hdr, m.cell_count,
+                       (const int*)m.cell_base, m.refs, m.big);
+    hipLaunchKernelGGL(k_md_dt<0>, dim3(cg), dim3(kMdThreads), 0, s, (const MdHeader*)m.hdr, (const int*)m.cell_base,
+                       (const uint8_t*)nullptr, m.dt[0]);
+    hipLaunchKernelGGL(k_md_dt<1>, dim3(cg), dim3(kMdThreads), 0, s, (const MdHeader*)m.hdr, (const int*)m.cell_base,
+                       (const uint8_t*)m.dt[0], m.dt[1]);
+    hipLaunchKernelGGL(k_md_dt<2>, dim3(cg), dim3(kMdThreads), 0, s, (const MdHeader*)m.hdr, (const int*)m.cell_base,
+                       (const uint8_t*)m.dt[1], m.dt[0]);
+    return check_launch();
+}
+
+int arah_mesh_closest(const void* index, size_t index_bytes, const float* tris, int32_t n_faces, const float* pts,
+                      int32_t n_pts, double* d2, int32_t* face, double* closest, int32_t* tested, void* stream) {
+    if (!index || !tris || n_faces < 1 || n_faces > (1 << 26) || n_pts < 0) return ARAH_E_BADARG;
+    const MdIndex m = carve_mesh_index(const_cast<void*>(index), n_faces);
+    if (index_bytes < m.bytes) return ARAH_E_WORKSPACE;
+    if (n_pts == 0) return ARAH_OK;
+    if (!pts || !d2 || !face) return ARAH_E_BADARG;
+    const int g = (n_pts + kMdQueryThreads - 1) / kMdQueryThreads;
+    hipLaunchKernelGGL(k_md_closest, dim3(g), dim3(kMdQueryThreads), 0, reinterpret_cast<hipStream_t>(stream), tris,
+                       (const MdHeader*)m.hdr, (const int*)m.cell_base, (const uint8_t*)m.dt[0], (const int*)m.refs,
+                       (const int*)m.big, pts, (int)n_pts, d2, (int*)face, closest, (int*)tested);
+    return check_launch();
+}
+
+int arah_face_area_cumsum(const float* tris, int32_t n_faces, double* cum, void* stream) {
+    if (!tris || !cum || n_faces < 1) return ARAH_E_BADARG;
+    hipLaunchKernelGGL(k_md_area_cumsum, dim3(1), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), tris, (int)n_faces, cum);
+    return check_launch();
+}
+
+size_t arah_surface_metrics_bytes(int32_t n_a, int32_t n_b) {
+    if (n_a < 1 || n_b < 1) return 0;
+    const size_t blocks = (size_t)(n_a + kMdThreads - 1) / kMdThreads + (size_t)(n_b + kMdThreads - 1) / kMdThreads;
+    return (blocks * 4 * sizeof(double) + 255) & ~(size_t)255;
+}
+
+int arah_surface_metrics(const float* tris_a, int32_t n_faces_a, const int32_t* sample_face_a, const double* d2_ab,
+                         const int32_t* face_ab, int32_t n_a, const float* tris_b, int32_t n_faces_b,
+                         const int32_t* sample_face_b, const double* d2_ba, const int32_t* face_ba, int32_t n_b, double* out,
+                         void* scratch, size_t scratch_bytes, void* stream) {
+    if (!tris_a || !tris_b || !sample_face_a || !sample_face_b || !d2_ab || !d2_ba || !face_ab || !face_ba || !out || !scratch)
+        return ARAH_E_BADARG;
+    if (n_faces_a < 1 || n_faces_b < 1 || n_a < 1 || n_b < 1) return ARAH_E_BADARG;
+    if (scratch_bytes < arah_surface_metrics_bytes(n_a, n_b)) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int ba = (n_a + kMdThreads - 1) / kMdThreads, bb = (n_b + kMdThreads - 1) / kMdThreads;
+    const MdSide sa = {tris_a, (const int*)sample_face_a, tris_b, d2_ab, (const int*)face_ab, (int)n_a, ba};
+    const MdSide sb = {tris_b, (const int*)sample_face_b, tris_a, d2_ba, (const int*)face_ba, (int)n_b, bb};
+    double* part = reinterpret_cast<double*>(scratch);
+    hipLaunchKernelGGL(k_md_metrics_part, dim3(ba + bb), dim3(kMdThreads), 0, s, sa, sb, part);
+    hipLaunchKernelGGL(k_md_metrics_finish, dim3(1), dim3(kMdThreads), 0, s, (const double*)part, ba, bb, (int)n_a, (int)n_b, out);
     return check_launch();
 }
 

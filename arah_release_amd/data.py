@@ -196,16 +196,18 @@ def _rotvec_to_matrix(rv):
 # training-only samplers (data/zju_mocap.py:455-543) on the device: regularisation points off the canonical
 # SMPL surface, skinning supervision points on it, points inside it
 # ---------------------------------------------------------------------------------------------------------------------
-def sample_surface(verts, faces, count, generator=None):
+def sample_surface(verts, faces, count, generator=None, cum=None):
     """``trimesh.Trimesh.sample(count, return_index=True)`` (trimesh 3.9, not in the reference tree; restated from
     trimesh/sample.py sample_surface): faces drawn proportionally to area by a search in the cumulative areas, the point is
     origin + r1 e1 + r2 e2 with (r1, r2) uniform in the unit square, reflected (|r - 1|) when r1 + r2 > 1.
-    verts (V,3), faces (F,3) integer -> points (count,3), face index (count,)."""
+    verts (V,3), faces (F,3) integer -> points (count,3), face index (count,).  cum: the faces' cumulative areas (F,) when the
+    caller has them (hip.face_area_cumsum: bit-reproducible, which torch.cumsum on the device is not for large F)."""
     dev = verts.device
     tri = verts[faces.long()]
     e1, e2 = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
-    area = torch.linalg.cross(e1, e2).norm(dim=-1) * 0.5
-    cum = torch.cumsum(area, 0)
+    if cum is None:
+        area = torch.linalg.cross(e1, e2).norm(dim=-1) * 0.5
+        cum = torch.cumsum(area, 0)
     pick = torch.rand(count, device=dev, generator=generator) * cum[-1]
     fi = torch.searchsorted(cum, pick).clamp(max=faces.shape[0] - 1)
     r = torch.rand(count, 2, device=dev, generator=generator)

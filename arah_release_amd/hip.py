@@ -132,7 +132,8 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_sdf_grid_band_scratch_bytes", "arah_sdf_grid_band", "arah_tier_audit_bytes", "arah_tier_audit",
            "arah_tier_audit_debug", "arah_occupancy_clear_box", "arah_render_maps_bytes", "arah_render_maps",
            "arah_query_posed_bytes", "arah_query_posed", "arah_sdf_grid_posed_bytes", "arah_sdf_grid_posed",
-           "arah_image_metrics_bytes", "arah_image_metrics"]
+           "arah_image_metrics_bytes", "arah_image_metrics",
+           "arah_mesh_index_bytes", "arah_mesh_index_build", "arah_mesh_closest", "arah_surface_metrics_bytes", "arah_surface_metrics", "arah_face_area_cumsum"]
 
 _lib = None
 
@@ -168,6 +169,10 @@ def load_library():
     lib.arah_sdf_grid_posed_bytes.argtypes = [C.c_int32]
     lib.arah_image_metrics_bytes.restype = C.c_size_t
     lib.arah_image_metrics_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.arah_mesh_index_bytes.restype = C.c_size_t
+    lib.arah_mesh_index_bytes.argtypes = [C.c_int32]
+    lib.arah_surface_metrics_bytes.restype = C.c_size_t
+    lib.arah_surface_metrics_bytes.argtypes = [C.c_int32, C.c_int32]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the symbol is missing
     _lib = lib
@@ -1177,6 +1182,114 @@ def mesh_query(verts, faces, pts):
                                    C.c_int32(1 if pts.dtype == torch.float64 else 0), C.c_int32(P), _ptr(d2), _ptr(face),
                                    _ptr(closest), _ptr(bary), _ptr(inside), _ptr(scratch), _stream()), "arah_mesh_query")
     return d2, face, closest, bary, inside.bool()
+
+
+def _soup(tris, what="tris"):
+    if not torch.is_tensor(tris) or tris.dim() != 3 or tuple(tris.shape[1:]) != (3, 3) or tris.dtype != torch.float32:
+        raise ValueError("%s must be an (F, 3, 3) float32 triangle soup" % what)
+    if tris.shape[0] < 1:
+        raise ValueError("%s holds no triangle" % what)
+    return tris.contiguous()
+
+
+class MeshIndex:
+    """The acceleration structure of `mesh_index`: the device buffer and the triangle soup it was built from."""
+
+    def __init__(self, buf, tris):
+        self.buf, self.tris = buf, tris
+
+    @property
+    def device(self):
+        return self.tris.device
+
+    def header(self):
+        """Host copy of the structure's figures (a synchronisation; for tests and tools): cells per axis, cell side, number
+        of references, triangles on the big list, status."""
+        import struct
+        raw = bytes(self.buf[:96].cpu().numpy())
+        lo_hi_h = struct.unpack("8d", raw[:64])
+        n = struct.unpack("7i", raw[64:92])
+        return {"lo": lo_hi_h[0:3], "hi": lo_hi_h[3:6], "h": lo_hi_h[6], "n": n[0:3], "n_cells": n[3], "n_refs": n[4],
+                "n_big": n[5], "status": n[6]}
+
+
+def mesh_index(tris):
+    """Uniform grid of triangle references over the soup tris (F,3,3) float32 (finite vertices), with a distance transform of
+    its occupied cells (arah_mesh_index_build, csrc/meshdist.hpp) -> MeshIndex for `mesh_closest`.  The buffer's size follows
+    from F alone; no host synchronisation."""
+    require_gpu()
+    lib = load_library()
+    tris = _soup(tris)
+    dev = _same_device(tris)
+    F = int(tris.shape[0])
+    with _on_device(dev):
+        buf = torch.empty(int(lib.arah_mesh_index_bytes(F)), dtype=torch.uint8, device=dev)
+        _check(lib.arah_mesh_index_build(_ptr(tris), C.c_int32(F), _ptr(buf), C.c_size_t(buf.numel()), _stream()),
+               "arah_mesh_index_build")
+    return MeshIndex(buf, tris)
+
+
+def mesh_closest(index, pts, want_closest=True, want_tested=False):
+    """Exact closest triangle of the indexed soup for every point: pts (P,3) float32 -> d2 (P,) float64, face (P,) int32 (the
+    lowest index on ties), closest (P,3) float64 or None, tested (P,) int32 (point-triangle tests made) or None.  d2, face and
+    closest are bit-equal to `mesh_query` on verts = tris.reshape(-1, 3), faces = arange."""
+    lib = load_library()
+    if not isinstance(index, MeshIndex):
+        raise ValueError("index must come from mesh_index")
+    if not torch.is_tensor(pts) or pts.dim() != 2 or pts.shape[1] != 3 or pts.dtype != torch.float32:
+        raise ValueError("pts must be (P, 3) float32")
+    dev = _same_device(index.buf, index.tris, pts)
+    pts = pts.contiguous()
+    P = int(pts.shape[0])
+    d2 = torch.empty(P, dtype=torch.float64, device=dev)
+    face = torch.empty(P, dtype=torch.int32, device=dev)
+    closest = torch.empty(P, 3, dtype=torch.float64, device=dev) if want_closest else None
+    tested = torch.empty(P, dtype=torch.int32, device=dev) if want_tested else None
+    with _on_device(dev):
+        _check(lib.arah_mesh_closest(_ptr(index.buf), C.c_size_t(index.buf.numel()), _ptr(index.tris),
+                                     C.c_int32(index.tris.shape[0]), _ptr(pts), C.c_int32(P), _ptr(d2), _ptr(face),
+                                     _ptr(closest), _ptr(tested), _stream()), "arah_mesh_closest")
+    return d2, face, closest, tested
+
+
+def face_area_cumsum(tris):
+    """Running sum of the areas of the soup's triangles, (F,) float64 on the device (arah_face_area_cumsum): float64 cross
+    products, one fixed summation order -- bit-reproducible, unlike torch.cumsum on the device for arrays of this size."""
+    lib = load_library()
+    tris = _soup(tris)
+    dev = _same_device(tris)
+    with _on_device(dev):
+        cum = torch.empty(tris.shape[0], dtype=torch.float64, device=dev)
+        _check(lib.arah_face_area_cumsum(_ptr(tris), C.c_int32(tris.shape[0]), _ptr(cum), _stream()), "arah_face_area_cumsum")
+    return cum
+
+
+SURFACE_METRICS = ("accuracy", "completeness", "chamfer_l1", "chamfer_l2", "normal_consistency", "hausdorff_ab", "hausdorff_ba",
+                   "n_a", "n_b")
+
+
+def surface_metrics(tris_a, sample_face_a, d2_ab, face_ab, tris_b, sample_face_b, d2_ba, face_ba):
+    """The geometry scores (arah_surface_metrics) from the samples' faces and their query results against the other mesh ->
+    (9,) float64 on the device in the order of SURFACE_METRICS.  No atomics, fixed summation order, no host synchronisation."""
+    lib = load_library()
+    tris_a, tris_b = _soup(tris_a, "tris_a"), _soup(tris_b, "tris_b")
+    dev = _same_device(tris_a, sample_face_a, d2_ab, face_ab, tris_b, sample_face_b, d2_ba, face_ba)
+    n_a, n_b = int(d2_ab.shape[0]), int(d2_ba.shape[0])
+    if n_a < 1 or n_b < 1:
+        raise ValueError("at least one sample per mesh required")
+    for t, n, dt in ((sample_face_a, n_a, torch.int32), (face_ab, n_a, torch.int32), (d2_ab, n_a, torch.float64),
+                     (sample_face_b, n_b, torch.int32), (face_ba, n_b, torch.int32), (d2_ba, n_b, torch.float64)):
+        if t.dtype != dt or tuple(t.shape) != (n,):
+            raise ValueError("faces int32 (n,), d2 float64 (n,) required")
+    args = [t.contiguous() for t in (sample_face_a, d2_ab, face_ab, sample_face_b, d2_ba, face_ba)]
+    with _on_device(dev):
+        out = torch.empty(len(SURFACE_METRICS), dtype=torch.float64, device=dev)
+        scratch = torch.empty(int(lib.arah_surface_metrics_bytes(n_a, n_b)), dtype=torch.uint8, device=dev)
+        _check(lib.arah_surface_metrics(_ptr(tris_a), C.c_int32(tris_a.shape[0]), _ptr(args[0]), _ptr(args[1]), _ptr(args[2]),
+                                        C.c_int32(n_a), _ptr(tris_b), C.c_int32(tris_b.shape[0]), _ptr(args[3]), _ptr(args[4]),
+                                        _ptr(args[5]), C.c_int32(n_b), _ptr(out), _ptr(scratch), C.c_size_t(scratch.numel()),
+                                        _stream()), "arah_surface_metrics")
+    return out
 
 
 def gram_skinny(a, b):

@@ -935,6 +935,23 @@ class MetaAvatarRender(nn.Module):
                 n = int(n_dev.item())
             return {"tris": hip.lattice_to_world(tris[:n], box), "n_tris": n, "box": box, "counts": counts}
 
+    def geometry_metrics(self, inputs, gt, n_side=256, method="lattice", n_samples=100000, seed=0):
+        """Geometry scores of the posed body of frame `inputs` against a ground-truth mesh `gt` in world metres ((F,3,3)
+        triangles or a (verts, faces) pair on the inputs' GPU): `posed_mesh(inputs, n_side, method)` as the prediction, then
+        geometry.mesh_metrics -- accuracy is the mean distance of the posed mesh's samples to the ground truth, completeness
+        the other way round.  -> its dict of 0-dimensional float64 device tensors, plus n_tris of the posed mesh.  Eval only."""
+        from . import geometry
+        if self.training:
+            raise ValueError("geometry_metrics is eval-only: call model.eval() first")
+        if inputs["rots"].device.type != "cuda":
+            raise ValueError("geometry_metrics runs on the HIP kernels: the inputs must live on the GPU")
+        mesh = self.posed_mesh(inputs, n_side=n_side, method=method)
+        if mesh["n_tris"] < 1:
+            raise ValueError("geometry_metrics: the posed level set is empty")
+        res = geometry.mesh_metrics(mesh["tris"], gt, n_samples=n_samples, seed=seed)
+        res["n_tris"] = mesh["n_tris"]
+        return res
+
     def _forward(self, inputs, gen_cano_mesh, eval, render_maps):
         rots, Jtrs = inputs["rots"], inputs["Jtrs"]
         B, dev = rots.size(0), rots.device

@@ -3,6 +3,7 @@
     python -m arah_release_amd.validate CONFIG.yaml                      # training views, the config's val frames
     python -m arah_release_amd.validate CONFIG.yaml --novel-view         # every 30th frame of the val views
     python -m arah_release_amd.validate CONFIG.yaml --novel-pose [--novel-pose-view 1]
+    python -m arah_release_amd.validate CONFIG.yaml --geometry DIR       # + geometry scores against DIR/<frame>.{npz,ply}
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m arah_release_amd.validate CONFIG.yaml ...
 
 Same arguments and the same overrides of the configuration as validate.py:42-50.  The model is sized from the TRAINING
@@ -13,7 +14,12 @@ renderer.frames_in_flight of them in flight -- PSNR and SSIM are computed on the
 chunk -- and are aggregated by ``validation_epoch_end``.  With N processes frame i goes to rank i mod N.  Rank 0 prints one
 JSON line (means, frame count, seconds per frame) and writes the per-frame values to ``<out_dir>/validation.json``.
 LPIPS needs VGG weights that are not part of this build: ``--lpips MODULE:FUNCTION`` names a callable
-(pred HxWx3, gt HxWx3, box mask) -> float to import; without it no LPIPS is reported."""
+(pred HxWx3, gt HxWx3, box mask) -> float to import; without it no LPIPS is reported.
+``--geometry DIR``: every frame whose ground-truth mesh exists as ``DIR/<name of the frame's model file>.npz`` (keys
+``vertices``, ``faces``) or ``.ply`` is also scored against it in world metres (MetaAvatarRender.geometry_metrics: Chamfer
+distance, accuracy / completeness, normal consistency, Hausdorff distances; DESIGN.md "Geometry metrics on the device").  The
+scalars stay on the device until the epoch ends; the JSON line gains their means over the scored frames and ``n_geometry``,
+the number of such frames.  Without the option the output is unchanged."""
 import argparse
 import importlib
 import json
@@ -38,6 +44,12 @@ def build_parser():
     p.add_argument("--lpips", type=str, default=None, help="MODULE:FUNCTION of an LPIPS callable (pred, gt, box mask) -> float.")
     p.add_argument("--data-range", type=float, default=2.0,
                    help="SSIM data range: 2.0 is what scikit-image 0.18.1 takes for float images, 1.0 the images' own range.")
+    p.add_argument("--geometry", type=str, default=None, metavar="DIR",
+                   help="Directory of ground-truth meshes <frame>.npz / <frame>.ply (named like the dataset's model files): "
+                        "adds geometry scores of the posed mesh against them.")
+    p.add_argument("--geometry-n-side", type=int, default=256, help="Lattice resolution of the posed mesh that is scored.")
+    p.add_argument("--geometry-samples", type=int, default=100000, help="Surface samples per mesh of the geometry scores.")
+    p.add_argument("--geometry-seed", type=int, default=0, help="Seed of the geometry scores' surface samples.")
     p.add_argument("--default-config", type=str, default="configs/default.yaml")
     p.add_argument("--body-models", type=str, default="body_models/misc", help="Directory of the SMPL model files.")
     return p
@@ -61,24 +73,70 @@ def load_callable(spec):
     return getattr(importlib.import_module(module), name)
 
 
-def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0):
+def geometry_file(directory, model_file):
+    """The ground-truth mesh of the frame whose SMPL parameters are `model_file`: DIR/<same name>.npz or .ply, else None."""
+    stem = os.path.splitext(os.path.basename(model_file))[0]
+    for ext in (".npz", ".ply"):
+        path = os.path.join(directory, stem + ext)
+        if os.path.exists(path):
+            return path
+    return None
+
+
+def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0, geometry=None):
     """Frames rank, rank + world, ... of the dataset through validation_step with device metrics; -> (what
     validation_epoch_end returns, frames this rank rendered, seconds it took).  Images are dropped chunk by chunk: only the
-    metric scalars of a frame stay."""
-    from . import renderer
+    metric scalars of a frame stay.  geometry: None, or {"dir", "n_side", "n_samples", "seed"} -- frames with a ground-truth
+    mesh in dir are scored by model.geometry_metrics in the same in-flight step, the scalars are read when the epoch ends and
+    the result gains their means, "n_geometry" and the per-frame values."""
+    from . import geometry as geo, renderer
     lm = lm.to(device).eval()
     mine = list(range(rank, len(dataset), world))
-    step = lambda item: lm.validation_step(item, lpips_fn=lpips_fn, metrics="device", data_range=data_range)
+    geo_keys = geo.METRIC_KEYS
+
+    def step(item):
+        gt = item.get("geometry.gt")
+        if gt is None:
+            return lm.validation_step(item, lpips_fn=lpips_fn, metrics="device", data_range=data_range)
+        item = {k: v for k, v in item.items() if k != "geometry.gt"}
+        out = lm.validation_step(item, lpips_fn=lpips_fn, metrics="device", data_range=data_range)
+        scores = lm.model.geometry_metrics(lm.compose_inputs(item, eval=True), gt, n_side=geometry["n_side"],
+                                           n_samples=geometry["n_samples"], seed=geometry["seed"])
+        out["geometry"] = torch.stack([scores[k] for k in geo_keys])
+        return out
+
     kept = []
     torch.cuda.synchronize(device)
     t0 = time.time()
     for c in range(0, len(mine), 20):   # twenty frames resident at a time, renderer.frames_in_flight of them in flight
         items = [dataset.validation_item(i, device) for i in mine[c:c + 20]]
+        if geometry is not None:
+            for i, item in zip(mine[c:c + 20], items):
+                path = geometry_file(geometry["dir"], dataset.data[i]["model_file"])
+                if path is not None:
+                    item["geometry.gt"] = geo.load_mesh(path, device)
         outs = renderer.map_in_flight(step, items, owner=lm.model)
-        kept += [{k: v for k, v in o.items() if k in ("psnr", "ssim", "lpips", "metrics_status")} for o in outs]
+        kept += [{k: v for k, v in o.items() if k in ("psnr", "ssim", "lpips", "metrics_status", "geometry")} for o in outs]
     torch.cuda.synchronize(device)
     seconds = time.time() - t0
-    return lm.validation_epoch_end(kept, first_index=rank, index_stride=world), len(mine), seconds
+    res = lm.validation_epoch_end([{k: v for k, v in o.items() if k != "geometry"} for o in kept], first_index=rank,
+                                  index_stride=world)
+    if geometry is not None:
+        rows = [(rank + k * world, o["geometry"].cpu().tolist()) for k, o in enumerate(kept) if "geometry" in o]
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            gathered = [None] * dist.get_world_size()
+            dist.all_gather_object(gathered, rows)
+            rows = [r for part in gathered for r in part]
+        if res is not None:
+            scored = dict(rows)
+            for frame in res["frames"]:
+                if frame["frame"] in scored:
+                    frame.update(zip(geo_keys, scored[frame["frame"]]))
+            res["n_geometry"] = len(scored)
+            for q, key in enumerate(geo_keys):
+                res[key] = sum(v[q] for v in scored.values()) / len(scored) if scored else None   # null: no frame was scored
+    return res, len(mine), seconds
 
 
 def main(argv=None, body=None, faces=None, log=print):
@@ -108,7 +166,13 @@ def main(argv=None, body=None, faces=None, log=print):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=device)
     lpips_fn = load_callable(args.lpips) if args.lpips else None
-    res, n_mine, seconds = validate(lm, val_dataset, device, rank, world, lpips_fn, args.data_range)
+    geometry = None
+    if args.geometry is not None:
+        if not os.path.isdir(args.geometry):
+            raise FileNotFoundError("--geometry: %s is not a directory" % args.geometry)
+        geometry = {"dir": args.geometry, "n_side": args.geometry_n_side, "n_samples": args.geometry_samples,
+                    "seed": args.geometry_seed}
+    res, n_mine, seconds = validate(lm, val_dataset, device, rank, world, lpips_fn, args.data_range, geometry)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

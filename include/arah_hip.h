@@ -41,6 +41,8 @@
  *                           lattice only and skins that mesh forward, models/__init__.py:209-227)
  *   arah_image_metrics      psnr_metric / ssim_metric of a validation frame  im2mesh/utils/eval.py:6-18
  *                           (skimage.metrics.structural_similarity + cv2.boundingRect; called at lightning_model.py:216-224)
+ *   arah_mesh_closest /     (none: geometry scores of posed meshes against ground-truth meshes; the reference's README points
+ *   arah_surface_metrics    to a script outside its tree)
  *   arah_mesh_query         check_mesh_contains + igl.point_mesh_squared_distance + igl.barycentric_coordinates_tri
  *                           im2mesh/utils/libmesh/inside_mesh.py:4-160, im2mesh/data/zju_mocap.py:466-529
  *
@@ -446,6 +448,36 @@ int arah_mesh_query(const float* verts, int32_t n_verts, const int32_t* faces, i
 size_t arah_image_metrics_bytes(int32_t height, int32_t width);
 int arah_image_metrics(const float* pred, const float* gt, const uint8_t* box_mask, int32_t height, int32_t width,
                        double data_range, double* out, int32_t* rect, void* scratch, size_t scratch_bytes, void* stream);
+
+/* Exact point-to-mesh distance against large triangle soups, and the geometry scores built on it (csrc/meshdist.hpp; no
+ * reference counterpart: the reference's tree computes no geometry score).  tris [F,3,3] f32 with finite vertices.
+ *   arah_mesh_index_build  a uniform grid of triangle references over the soup's bounding box, with a Chebyshev distance
+ *                          transform of its occupied cells, into the caller's `index` buffer (arah_mesh_index_bytes(F) bytes,
+ *                          256-byte aligned).  The buffer's size is fixed by F alone: a triangle is referenced from at most
+ *                          8 cells, one that overlaps more is kept on a list every query walks.  Nothing is truncated.
+ *   arah_mesh_closest      pts [P,3] f32 (finite) -> d2 [P] f64, face [P] i32, closest [P,3] f64 or NULL, tested [P] i32 or
+ *                          NULL (point-triangle tests the query made).  d2 / face / closest are bit-equal to arah_mesh_query's
+ *                          on the same triangles: the same per-triangle arithmetic, the lexicographic minimum of
+ *                          (d2, face index).  A non-finite point or vertex gives d2 NaN, face -1.  `tris` must be the buffer
+ *                          the index was built from.
+ *   arah_surface_metrics   samples of mesh A queried against B and of B against A -> out [9] DEVICE doubles: accuracy,
+ *                          completeness, chamfer_l1, chamfer_l2, normal_consistency, hausdorff_ab, hausdorff_ba, n_a, n_b.
+ *                          sample_face_x [n_x] i32: the face of X each sample was drawn from; d2_xy / face_xy [n_x]: its query
+ *                          result against Y.  Normals are the faces' float64 cross products, normalised; the sums run in
+ *                          index order (no atomics).  scratch: arah_surface_metrics_bytes(n_a, n_b) bytes, 8-byte aligned.
+ *   arah_face_area_cumsum  cum [F] f64: running sum of the triangles' areas (half the norm of the float64 cross product) in a
+ *                          fixed order, for area-weighted sampling that gives the same bits on every run.
+ * No host synchronisation anywhere. */
+size_t arah_mesh_index_bytes(int32_t n_faces);
+int arah_face_area_cumsum(const float* tris, int32_t n_faces, double* cum, void* stream);
+int arah_mesh_index_build(const float* tris, int32_t n_faces, void* index, size_t index_bytes, void* stream);
+int arah_mesh_closest(const void* index, size_t index_bytes, const float* tris, int32_t n_faces, const float* pts,
+                      int32_t n_pts, double* d2, int32_t* face, double* closest, int32_t* tested, void* stream);
+size_t arah_surface_metrics_bytes(int32_t n_a, int32_t n_b);
+int arah_surface_metrics(const float* tris_a, int32_t n_faces_a, const int32_t* sample_face_a, const double* d2_ab,
+                         const int32_t* face_ab, int32_t n_a, const float* tris_b, int32_t n_faces_b,
+                         const int32_t* sample_face_b, const double* d2_ba, const int32_t* face_ba, int32_t n_b, double* out,
+                         void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---- the hot path ----------------------------------------------------------------------- */
 /* rays: cam_loc [n_cams,3], ray r belongs to camera r / rays_per_cam; dirs [N,3]; near_far [N,2].
