@@ -3846,12 +3846,53 @@ int arah_marching_cubes(const float* sdf, int32_t n_side, float level, const int
     int* row_base = row_count + rows;
     const float vs = (float)(2.0 / (n_side - 1));   // sdf_meshing.py:27: voxel_size = 2.0 / (N - 1), rounded to fp32 once
     const signed char* table = reinterpret_cast<const signed char*>(tri_table);
-    hipLaunchKernelGGL(k_mcubes<false>, dim3(rows), dim3(kMcThreads), 0, s, sdf, (int)n_side, level, vs, table, (const int*)n_tri,
-                       row_count, (const int*)nullptr, (float*)nullptr, 0);
+    hipLaunchKernelGGL(k_mcubes<kMcCount>, dim3(rows), dim3(kMcThreads), 0, s, sdf, (int)n_side, level, vs, table, (const int*)n_tri,
+                       row_count, (const int*)nullptr, (float*)nullptr, 0, (const int*)nullptr, (int*)nullptr);
     hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)row_count, rows, row_base, (int*)n_tris);
-    hipLaunchKernelGGL(k_mcubes<true>, dim3(rows), dim3(kMcThreads), 0, s, sdf, (int)n_side, level, vs, table, (const int*)n_tri,
-                       (int*)nullptr, (const int*)row_base, tris, (int)cap);
+    hipLaunchKernelGGL(k_mcubes<kMcSoup>, dim3(rows), dim3(kMcThreads), 0, s, sdf, (int)n_side, level, vs, table, (const int*)n_tri,
+                       (int*)nullptr, (const int*)row_base, tris, (int)cap, (const int*)nullptr, (int*)nullptr);
     hipLaunchKernelGGL(k_mc_pad, dim3(1024), dim3(256), 0, s, tris, (const int*)n_tris, (int)cap);
+    return check_launch();
+}
+
+// the largest lattice whose edge keys ((ix n + iy) n + iz) 3 + a fit int32
+static bool mc_indexed_side_ok(int32_t n_side) { return n_side >= 2 && (int64_t)3 * n_side * n_side * n_side <= (int64_t)INT32_MAX; }
+
+size_t arah_marching_cubes_indexed_scratch_bytes(int32_t n_side) {
+    if (!mc_indexed_side_ok(n_side)) return 0;
+    const size_t n = (size_t)n_side, m = n - 1;
+    return (n * n * n + 2 * n * n + 2 * m * m) * sizeof(int);   // first_vert, vertex rows (count, base), cell rows (count, base)
+}
+
+int arah_marching_cubes_indexed(const float* sdf, int32_t n_side, float level, const int8_t* tri_table, const int32_t* n_tri,
+                                float* verts, int32_t vert_cap, int32_t* vert_edge, int32_t* faces, int32_t face_cap, int32_t* counts,
+                                void* scratch, size_t scratch_bytes, void* stream) {
+    if (!sdf || !tri_table || !n_tri || !verts || !faces || !counts || !scratch || !mc_indexed_side_ok(n_side) || vert_cap <= 0 ||
+        face_cap <= 0)
+        return ARAH_E_BADARG;
+    if (scratch_bytes < arah_marching_cubes_indexed_scratch_bytes(n_side)) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int N = (int)n_side, vrows = N * N, crows = (N - 1) * (N - 1);
+    int* first_vert = reinterpret_cast<int*>(scratch);
+    int* vrow_count = first_vert + (size_t)N * N * N;
+    int* vrow_base = vrow_count + vrows;
+    int* crow_count = vrow_base + vrows;
+    int* crow_base = crow_count + crows;
+    const float vs = (float)(2.0 / (n_side - 1));
+    const signed char* table = reinterpret_cast<const signed char*>(tri_table);
+    hipLaunchKernelGGL(k_mc_verts<false>, dim3(vrows), dim3(kMcThreads), 0, s, sdf, N, level, vs, vrow_count, (const int*)nullptr,
+                       (int*)nullptr, (float*)nullptr, (int*)nullptr, 0);
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)vrow_count, vrows, vrow_base, (int*)counts);
+    hipLaunchKernelGGL(k_mc_verts<true>, dim3(vrows), dim3(kMcThreads), 0, s, sdf, N, level, vs, (int*)nullptr, (const int*)vrow_base,
+                       first_vert, verts, (int*)vert_edge, (int)vert_cap);
+    hipLaunchKernelGGL(k_mcubes<kMcCount>, dim3(crows), dim3(kMcThreads), 0, s, sdf, N, level, vs, table, (const int*)n_tri, crow_count,
+                       (const int*)nullptr, (float*)nullptr, 0, (const int*)nullptr, (int*)nullptr);
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)crow_count, crows, crow_base, (int*)counts + 1);
+    hipLaunchKernelGGL(k_mcubes<kMcFaces>, dim3(crows), dim3(kMcThreads), 0, s, sdf, N, level, vs, table, (const int*)n_tri,
+                       (int*)nullptr, (const int*)crow_base, (float*)nullptr, (int)face_cap, (const int*)first_vert, (int*)faces);
+    hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)verts, (const int*)counts, (int)vert_cap, 3);
+    hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)vert_edge, (const int*)counts, (int)vert_cap, 1);
+    hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)faces, (const int*)counts + 1, (int)face_cap, 3);
     return check_launch();
 }
 

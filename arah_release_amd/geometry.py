@@ -4,7 +4,7 @@ surface samples and their EXACT point-to-surface distances (hip.mesh_index / hip
 
 The reference publishes such numbers but its tree holds no code for them (its README points to a script in its issue
 tracker): PARITY UNPINNED, the definitions are this project's.  Also here: `load_mesh` for the two formats ground-truth meshes
-come in (.npz with `vertices` / `faces`, PLY with triangle faces)."""
+come in (.npz with `vertices` / `faces`, PLY with triangle faces), and `save_mesh`, which writes an indexed mesh in either."""
 import numpy as np
 import torch
 
@@ -260,3 +260,69 @@ def load_mesh(path, device=None):
     v = torch.from_numpy(np.ascontiguousarray(verts, np.float32))
     f = torch.from_numpy(np.ascontiguousarray(faces, np.int64))
     return (v.to(device), f.to(device)) if device is not None else (v, f)
+
+
+def save_mesh(path, verts, faces, normals=None, colors=None):
+    """Write an indexed mesh: verts (V,3) float, faces (F,3) integer vertex ids, optional per-vertex normals (V,3) and colors (V,3)
+    in [0,1].  `.npz`: keys `vertices` (float32), `faces` (int32) and, when given, `normals` / `colors` (float32).  `.ply`: binary
+    little-endian, vertex properties float x y z [, float nx ny nz] [, uchar red green blue: round(255 c), clipped], faces as
+    `list uchar int vertex_indices`.  `load_mesh` reads either back: vertices bit-equal, faces equal.  ValueError for another
+    extension, wrong shapes, attribute lengths that differ from V, or a face index out of range."""
+    path = str(path)
+    low = path.lower()
+    if not low.endswith((".npz", ".ply")):
+        raise ValueError("%s: only .npz and .ply meshes are written" % path)
+
+    def host(a):
+        return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+    v, f = host(verts), host(faces)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError("vertices must be (V, 3), got %s" % (v.shape,))
+    if f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError("faces must be (F, 3) triangles, got %s" % (f.shape,))
+    if not np.issubdtype(f.dtype, np.integer):
+        raise ValueError("faces must hold integer vertex indices")
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError("a face refers to a vertex that does not exist")
+    if v.shape[0] > np.iinfo(np.int32).max:
+        raise ValueError("too many vertices for 32-bit face indices")
+    v, f = np.ascontiguousarray(v, np.float32), np.ascontiguousarray(f, np.int32)
+    extra = {}
+    for name, a in (("normals", normals), ("colors", colors)):
+        if a is not None:
+            a = host(a)
+            if a.ndim != 2 or a.shape != v.shape:
+                raise ValueError("%s must be (V, 3) = %s, got %s" % (name, v.shape, a.shape))
+            extra[name] = np.ascontiguousarray(a, np.float32)
+    if low.endswith(".npz"):
+        with open(path, "wb") as out:
+            np.savez(out, vertices=v, faces=f, **extra)
+        return
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    header = ["ply", "format binary_little_endian 1.0", "element vertex %d" % v.shape[0],
+              "property float x", "property float y", "property float z"]
+    if "normals" in extra:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += ["property float nx", "property float ny", "property float nz"]
+    if "colors" in extra:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        header += ["property uchar red", "property uchar green", "property uchar blue"]
+    header += ["element face %d" % f.shape[0], "property list uchar int vertex_indices", "end_header"]
+    vrec = np.empty(v.shape[0], np.dtype(fields))
+    for i, k in enumerate("xyz"):
+        vrec[k] = v[:, i]
+    if "normals" in extra:
+        for i, k in enumerate(("nx", "ny", "nz")):
+            vrec[k] = extra["normals"][:, i]
+    if "colors" in extra:
+        c8 = np.clip(np.rint(extra["colors"].astype(np.float64) * 255.0), 0, 255).astype(np.uint8)
+        for i, k in enumerate(("red", "green", "blue")):
+            vrec[k] = c8[:, i]
+    frec = np.empty(f.shape[0], np.dtype([("cnt", "u1"), ("idx", "<i4", (3,))]))
+    frec["cnt"] = 3
+    frec["idx"] = f
+    with open(path, "wb") as out:
+        out.write(("\n".join(header) + "\n").encode("ascii"))
+        out.write(vrec.tobytes())
+        out.write(frec.tobytes())

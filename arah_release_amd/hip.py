@@ -128,6 +128,7 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_shade_composite", "arah_shade_points", "arah_render", "arah_shade_train_slab_bytes", "arah_shade_train_forward",
            "arah_shade_train_backward", "arah_composite_train_forward", "arah_composite_train_backward", "arah_gram_skinny_blocks", "arah_gram_skinny", "arah_colsum_blocks", "arah_colsum", "arah_inverse3x3", "arah_hsoftmax_train_forward", "arah_hsoftmax_train_backward", "arah_pose_tree_forward", "arah_pose_tree_backward", "arah_gemv_rows", "arah_mesh_query_scratch_bytes", "arah_mesh_query", "arah_dominant_kernel",
            "arah_skin_lbs_counted", "arah_marching_cubes_scratch_bytes", "arah_marching_cubes",
+           "arah_marching_cubes_indexed_scratch_bytes", "arah_marching_cubes_indexed",
            "arah_occupancy_bytes", "arah_prepare_occupancy", "arah_occupancy_info", "arah_tier_debug", "arah_debug_samples",
            "arah_sdf_grid_band_scratch_bytes", "arah_sdf_grid_band", "arah_tier_audit_bytes", "arah_tier_audit",
            "arah_tier_audit_debug", "arah_occupancy_clear_box", "arah_render_maps_bytes", "arah_render_maps",
@@ -156,6 +157,8 @@ def load_library():
     lib.arah_mesh_query_scratch_bytes.restype = C.c_size_t
     lib.arah_marching_cubes_scratch_bytes.restype = C.c_size_t
     lib.arah_marching_cubes_scratch_bytes.argtypes = [C.c_int32]
+    lib.arah_marching_cubes_indexed_scratch_bytes.restype = C.c_size_t
+    lib.arah_marching_cubes_indexed_scratch_bytes.argtypes = [C.c_int32]
     lib.arah_occupancy_bytes.restype = C.c_size_t
     lib.arah_sdf_grid_band_scratch_bytes.restype = C.c_size_t
     lib.arah_colsum_blocks.argtypes = [C.c_int64]
@@ -693,6 +696,59 @@ def lattice_to_world(x, box):
 _mc_tables = {}
 
 
+def _mc_device_tables(dev):
+    """meshing.case_table() on `dev`, copied once: (tri_table (256,16) int8, n_tri (256,) int32)."""
+    if dev not in _mc_tables:
+        import numpy as np
+        from . import meshing
+        table_np, ntri_np = meshing.case_table()
+        assert table_np.shape[1] <= 16
+        t16 = -np.ones((256, 16), np.int8)
+        t16[:, :table_np.shape[1]] = table_np
+        _mc_tables[dev] = (torch.from_numpy(t16).to(dev), torch.from_numpy(ntri_np.astype(np.int32)).to(dev))
+    return _mc_tables[dev]
+
+
+MC_INDEXED_MAX_SIDE = 894   # the largest lattice whose edge keys (3 n^3 of them) fit int32
+_mc_indexed_scratch = {}
+
+
+def marching_cubes_indexed(sdf, level=0.0, vert_cap=1 << 19, face_cap=1 << 20, want_edge=False):
+    """Level set of the lattice volume sdf (N,N,N) [ix,iy,iz] as an INDEXED mesh, on the device and WITHOUT a host round trip
+    (arah_marching_cubes_indexed): one vertex per crossing lattice edge, in ascending order of the edge key
+    ((ix N + iy) N + iz) 3 + axis.  -> verts (vert_cap,3) coordinates in [-1,1]^3, faces (face_cap,3) int32 vertex ids, counts
+    (2,) int32 on the device (vertices and faces of the level set; either may exceed its capacity, then only the first rows
+    were written), and with want_edge=True vert_edge (vert_cap,) int32, the vertices' keys.  Rows beyond the counts are zero.
+    verts[faces] is `marching_cubes` of the same volume bit for bit; the result is meshing.marching_cubes_indexed(sdf).
+    The scratch (4 N^3 bytes and the row tables) is kept per (device, stream) and grows on demand."""
+    require_gpu()
+    lib = load_library()
+    v = _f32(sdf)
+    if v.dim() != 3 or v.shape[0] != v.shape[1] or v.shape[0] != v.shape[2] or not 2 <= v.shape[0] <= MC_INDEXED_MAX_SIDE:
+        raise ValueError("sdf must be an (N, N, N) lattice volume with 2 <= N <= %d" % MC_INDEXED_MAX_SIDE)
+    if int(vert_cap) < 1 or int(face_cap) < 1:
+        raise ValueError("vert_cap and face_cap must be at least 1")
+    dev, N = v.device, int(v.shape[0])
+    table, ntri = _mc_device_tables(dev)
+    with _on_device(dev):
+        need = int(lib.arah_marching_cubes_indexed_scratch_bytes(N))
+        key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+        scratch = _mc_indexed_scratch.get(key)
+        if scratch is None or scratch.numel() < need:
+            if scratch is None and len(_mc_indexed_scratch) >= 8:
+                _mc_indexed_scratch.pop(next(iter(_mc_indexed_scratch)))
+            scratch = _mc_indexed_scratch[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+        verts = torch.empty(int(vert_cap), 3, device=dev)
+        faces = torch.empty(int(face_cap), 3, dtype=torch.int32, device=dev)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        vert_edge = torch.empty(int(vert_cap), dtype=torch.int32, device=dev) if want_edge else None
+        _check(lib.arah_marching_cubes_indexed(_ptr(v), C.c_int32(N), C.c_float(float(level)), _ptr(table), _ptr(ntri), _ptr(verts),
+                                               C.c_int32(int(vert_cap)), _ptr(vert_edge), _ptr(faces), C.c_int32(int(face_cap)),
+                                               _ptr(counts), _ptr(scratch), C.c_size_t(scratch.numel()), _stream()),
+               "arah_marching_cubes_indexed")
+    return (verts, faces, counts, vert_edge) if want_edge else (verts, faces, counts)
+
+
 def marching_cubes(sdf, level=0.0, cap=1 << 20):
     """Level set of the lattice volume sdf (N,N,N) [ix,iy,iz] as a triangle soup, on the device and WITHOUT a host round
     trip: -> tris (cap,3,3) coordinates in [-1,1]^3 (rows beyond the count are zero: degenerate triangles), n_tris (1,) int32
@@ -704,15 +760,7 @@ def marching_cubes(sdf, level=0.0, cap=1 << 20):
     if v.dim() != 3 or v.shape[0] != v.shape[1] or v.shape[0] != v.shape[2] or v.shape[0] < 2:
         raise ValueError("sdf must be an (N, N, N) lattice volume")
     dev, N = v.device, int(v.shape[0])
-    if dev not in _mc_tables:
-        import numpy as np
-        from . import meshing
-        table_np, ntri_np = meshing.case_table()
-        assert table_np.shape[1] <= 16
-        t16 = -np.ones((256, 16), np.int8)
-        t16[:, :table_np.shape[1]] = table_np
-        _mc_tables[dev] = (torch.from_numpy(t16).to(dev), torch.from_numpy(ntri_np.astype(np.int32)).to(dev))
-    table, ntri = _mc_tables[dev]
+    table, ntri = _mc_device_tables(dev)
     with _on_device(dev):
         tris = torch.empty(int(cap), 3, 3, device=dev)
         n_tris = torch.empty(1, dtype=torch.int32, device=dev)

@@ -92,10 +92,9 @@ def case_table():
     return _TABLE
 
 
-def marching_cubes(sdf, level=0.0):
-    """sdf (N,N,N) tensor indexed [ix,iy,iz] on the lattice of [-1,1]^3 -> triangle soup (F,3,3) of coordinates in
-    [-1,1]^3 (sdf_meshing.py:83-101: vertex = origin + index * voxel_size), right-hand normals towards decreasing
-    values.  Runs on the tensor's device."""
+def _mc_triangles(sdf, level):
+    """The triangles of the level set before the orientation flip: -> (corners (F,3,3) coordinates, flip (F,) bool, pa (F,3,3)
+    lattice index of the lower end of every corner's edge, axis (F,3) of that edge), or None for an empty level set."""
     dev = sdf.device
     N = sdf.shape[0]
     vs = 2.0 / (N - 1)
@@ -110,7 +109,7 @@ def marching_cubes(sdf, level=0.0):
         case += inside[dx:N - 1 + dx, dy:N - 1 + dy, dz:N - 1 + dz].to(torch.int64) << c
     cells = torch.nonzero((case != 0) & (case != 255))                      # (M,3)
     if cells.shape[0] == 0:
-        return torch.zeros(0, 3, 3, device=dev)
+        return None
     ccase = case[cells[:, 0], cells[:, 1], cells[:, 2]]
     cnt = ntri[ccase]
     owner = torch.repeat_interleave(torch.arange(cells.shape[0], device=dev), cnt)           # cell of every triangle
@@ -134,8 +133,74 @@ def marching_cubes(sdf, level=0.0):
     grad = torch.stack([(cv * (2 * cf[:, k] - 1)).sum(1) for k in range(3)], dim=1)
     nrm = torch.cross(verts[:, 1] - verts[:, 0], verts[:, 2] - verts[:, 0], dim=1)
     flip = (nrm * grad).sum(1) > 0
-    verts = torch.where(flip[:, None, None], verts[:, [0, 2, 1]], verts)
-    return verts
+    return verts, flip, pa, (pb - pa).argmax(-1)
+
+
+def marching_cubes(sdf, level=0.0):
+    """sdf (N,N,N) tensor indexed [ix,iy,iz] on the lattice of [-1,1]^3 -> triangle soup (F,3,3) of coordinates in
+    [-1,1]^3 (sdf_meshing.py:83-101: vertex = origin + index * voxel_size), right-hand normals towards decreasing
+    values.  Runs on the tensor's device."""
+    res = _mc_triangles(sdf, level)
+    if res is None:
+        return torch.zeros(0, 3, 3, device=sdf.device)
+    verts, flip = res[:2]
+    return torch.where(flip[:, None, None], verts[:, [0, 2, 1]], verts)
+
+
+def marching_cubes_indexed(sdf, level=0.0):
+    """The level set of `marching_cubes` as an INDEXED mesh, the (verts, faces) pair of sdf_meshing.py:13-114: one vertex per
+    crossing lattice edge.  The edge that leaves lattice point (ix, iy, iz) along axis a (0 x, 1 y, 2 z; a point on the last
+    layer of an axis has no edge along it) has the key ((ix N + iy) N + iz) 3 + a and crosses when (sdf[lo] < level) !=
+    (sdf[hi] < level).  -> verts (V,3): the crossing edges in ascending key order, interpolated with the soup's arithmetic (so
+    verts[faces] IS marching_cubes(sdf), bit for bit); faces (F,3) int64: the soup's triangles in its order, corner for corner;
+    vert_edge (V,) int64: the keys.  Plain tensor operations on the tensor's device: the specification of
+    arah_marching_cubes_indexed (csrc/mcubes.hpp), and what runs for volumes that live on the host."""
+    dev = sdf.device
+    N = sdf.shape[0]
+    vs = 2.0 / (N - 1)
+    inside = sdf < level
+    cross = torch.zeros(N, N, N, 3, dtype=torch.bool, device=dev)
+    cross[:-1, :, :, 0] = inside[:-1] != inside[1:]
+    cross[:, :-1, :, 1] = inside[:, :-1] != inside[:, 1:]
+    cross[:, :, :-1, 2] = inside[:, :, :-1] != inside[:, :, 1:]
+    cross = cross.reshape(-1)
+    vert_edge = torch.nonzero(cross)[:, 0]                                   # ascending keys
+    point, axis = vert_edge // 3, vert_edge % 3
+    pa = torch.stack([point // (N * N), (point // N) % N, point % N], dim=1)
+    pb = pa + torch.nn.functional.one_hot(axis, 3)
+    va = sdf[pa[:, 0], pa[:, 1], pa[:, 2]] - level
+    vb = sdf[pb[:, 0], pb[:, 1], pb[:, 2]] - level
+    t = (va / (va - vb)).clamp(0.0, 1.0).unsqueeze(-1)
+    verts = (pa.float() + t * (pb - pa).float()) * vs - 1.0
+    res = _mc_triangles(sdf, level)
+    if res is None:
+        return verts, torch.zeros(0, 3, dtype=torch.int64, device=dev), vert_edge
+    _, flip, lo, ax = res
+    key = ((lo[..., 0] * N + lo[..., 1]) * N + lo[..., 2]) * 3 + ax           # (F,3)
+    vert_of_key = torch.cumsum(cross.to(torch.int64), 0) - 1
+    faces = vert_of_key[key]
+    faces = torch.where(flip[:, None], faces[:, [0, 2, 1]], faces)
+    return verts, faces, vert_edge
+
+
+MC_DEFAULT_VERT_CAP = 1 << 19
+
+
+def indexed_mesh(sdf, level=0.0):
+    """The indexed mesh of a lattice volume, trimmed to its size: -> (verts (V,3) in [-1,1]^3, faces (F,3)).  On the GPU:
+    hip.marching_cubes_indexed with the default capacities, ONE read of its counts (the host synchronisation) and a second run
+    with the exact sizes when either capacity was too small -- nothing is truncated.  A volume on the host goes through
+    `marching_cubes_indexed`."""
+    if not sdf.is_cuda:
+        verts, faces, _ = marching_cubes_indexed(sdf.float(), level)
+        return verts, faces
+    from . import hip
+    vert_cap, face_cap = MC_DEFAULT_VERT_CAP, MC_DEFAULT_CAP
+    verts, faces, counts = hip.marching_cubes_indexed(sdf, level, vert_cap, face_cap)
+    V, F = counts.tolist()
+    if V > vert_cap or F > face_cap:
+        verts, faces, counts = hip.marching_cubes_indexed(sdf, level, max(V, 1), max(F, 1))
+    return verts[:V], faces[:F]
 
 
 def face_normals(tri):
@@ -279,12 +344,7 @@ def skinned_mesh(frame, ws, inputs, n_side=256, tri=None, cap=None):
     with torch.no_grad():
         n_dev = None
         if tri is None:
-            # the lattice only where the level set can pass (csrc/tier.hpp: same triangles as the full lattice, ~6 % of its
-            # 16.8 M evaluations); ARAH_MESH_BAND=0: every lattice point, like sdf_meshing.py:44-57
-            if n_side >= 33 and os.environ.get("ARAH_MESH_BAND", "1") != "0":
-                sdf, _ = hip.sdf_grid_band(frame, ws, n_side)
-            else:
-                sdf = hip.sdf_grid(frame, ws, n_side)
+            sdf = canonical_lattice(frame, ws, n_side)
             if cap is not None:
                 tri, n_dev = hip.marching_cubes(sdf, 0.0, cap)
             else:
@@ -304,3 +364,28 @@ def skinned_mesh(frame, ws, inputs, n_side=256, tri=None, cap=None):
             x_bar = hip.skin_lbs_counted(frame, ws, x_hat, n_dev, per_item=3)            # zero beyond the mesh: degenerate
         posed = (x_bar + inputs["trans"].reshape(1, 3)).reshape(F, 3, 3)
     return tri, posed, n_dev
+
+
+def canonical_lattice(frame, ws, n_side=256):
+    """The canonical SDF lattice the mesh branch extracts from: only where the level set can pass (csrc/tier.hpp: same
+    triangles as the full lattice, ~6 % of its 16.8 M evaluations); ARAH_MESH_BAND=0 or n_side < 33: every lattice point, like
+    sdf_meshing.py:44-57."""
+    from . import hip
+    if n_side >= 33 and os.environ.get("ARAH_MESH_BAND", "1") != "0":
+        return hip.sdf_grid_band(frame, ws, n_side)[0]
+    return hip.sdf_grid(frame, ws, n_side)
+
+
+def skinned_indexed_mesh(frame, ws, inputs, n_side=256, vert_cap=MC_DEFAULT_VERT_CAP, face_cap=None):
+    """`skinned_mesh` as an indexed mesh: the canonical level set's V vertices are skinned, not its 3 F corners.  -> (verts
+    (vert_cap,3) normalised canonical, posed (vert_cap,3) world metres, faces (face_cap,3) int32, counts (2,) int32 on the
+    device).  Rows beyond the counts: zeros in verts and faces, the translation in posed.  No host round trip."""
+    from . import hip, training
+    with torch.no_grad():
+        sdf = canonical_lattice(frame, ws, n_side)
+        verts, faces, counts = hip.marching_cubes_indexed(sdf, 0.0, vert_cap, MC_DEFAULT_CAP if face_cap is None else face_cap)
+        cmin, cmax, center = inputs["coord_min"][:1], inputs["coord_max"][:1], inputs["center"][:1]
+        x_hat = training.unnormalize_canonical_points(verts.reshape(1, -1, 3), cmin, cmax, center)[0]
+        x_bar = hip.skin_lbs_counted(frame, ws, x_hat, counts[:1], per_item=1)
+        posed = x_bar + inputs["trans"].reshape(1, 3)
+    return verts, posed, faces, counts

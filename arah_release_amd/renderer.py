@@ -899,7 +899,7 @@ class MetaAvatarRender(nn.Module):
                 "points_hat": r["points_hat"].reshape(*shape, 3), "weights": r["weights"].reshape(*shape, 24),
                 "converged": (r["state"] == 1).reshape(shape), "state": r["state"].reshape(shape)}
 
-    def posed_mesh(self, inputs, n_side=256, method="lattice", bounds=None):
+    def posed_mesh(self, inputs, n_side=256, method="lattice", bounds=None, indexed=False):
         """A triangle soup of the posed body of frame `inputs` in world metres.  method="lattice": the zero level set of the posed
         SDF (hip.sdf_grid_posed, only the band around the occupancy bitmap's marked voxels unless ARAH_POSED_MESH_BAND=0, then
         hip.marching_cubes) -- the surface the renderer sees, self-contact included.  method="skinned": the reference's points_bar
@@ -907,10 +907,35 @@ class MetaAvatarRender(nn.Module):
         (default: the marked voxels' box plus one voxel).  -> dict of tris (F,3,3) trimmed to the level set's size (the one host
         synchronisation), n_tris, box (4,) origin xyz + side of the lattice (None for "skinned") and counts (3,) evaluated /
         converged / skipped lattice points.  The triangle buffer is sized from the device count and the extraction re-run when
-        it was too small: nothing is truncated.  Eval only."""
+        it was too small: nothing is truncated.  indexed=True: the same surface as an indexed mesh (hip.marching_cubes_indexed,
+        one vertex per crossing lattice edge) -- verts (V,3) world metres, faces (F,3) int32, n_verts and n_tris take the place of
+        tris, and verts[faces] is the soup of the default call bit for bit; "skinned" then skins V vertices instead of 3 F
+        corners.  Eval only."""
         from . import meshing
         frame, ws = self._posed_frame(inputs, "posed_mesh")
+        if method not in ("lattice", "skinned"):
+            raise ValueError("method must be 'lattice' or 'skinned', got %r" % (method,))
         with torch.no_grad():
+            if indexed:
+                box = counts = None
+                if method == "lattice":
+                    occ = ws.occupancy(frame)
+                    box = hip.lattice_box(*bounds).to(occ.device) if bounds is not None else None
+                    band = os.environ.get("ARAH_POSED_MESH_BAND", "1") != "0"
+                    sdf, box, counts = hip.sdf_grid_posed(frame, ws, n_side, occ=occ, box=box, band=band)
+
+                def extract(vert_cap, face_cap):
+                    if method == "skinned":
+                        _, posed, faces, size = meshing.skinned_indexed_mesh(frame, ws, inputs, n_side, vert_cap, face_cap)
+                        return posed, faces, size
+                    verts, faces, size = hip.marching_cubes_indexed(sdf, 0.0, vert_cap, face_cap)
+                    return hip.lattice_to_world(verts, box), faces, size
+                vert_cap, face_cap = meshing.MC_DEFAULT_VERT_CAP, meshing.MC_DEFAULT_CAP
+                verts, faces, size = extract(vert_cap, face_cap)
+                V, F = size.tolist()
+                if V > vert_cap or F > face_cap:   # too small for this level set: the exact sizes, once more
+                    verts, faces, size = extract(max(V, 1), max(F, 1))
+                return {"verts": verts[:V], "faces": faces[:F], "n_verts": V, "n_tris": F, "box": box, "counts": counts}
             if method == "skinned":
                 cap = meshing.MC_DEFAULT_CAP
                 _, posed, n_dev = meshing.skinned_mesh(frame, ws, inputs, n_side, cap=cap)
@@ -920,8 +945,6 @@ class MetaAvatarRender(nn.Module):
                     _, posed, n_dev = meshing.skinned_mesh(frame, ws, inputs, n_side, cap=cap)
                     n = int(n_dev.item())
                 return {"tris": posed[:n], "n_tris": n, "box": None, "counts": None}
-            if method != "lattice":
-                raise ValueError("method must be 'lattice' or 'skinned', got %r" % (method,))
             occ = ws.occupancy(frame)
             box = hip.lattice_box(*bounds).to(occ.device) if bounds is not None else None
             band = os.environ.get("ARAH_POSED_MESH_BAND", "1") != "0"
@@ -934,6 +957,63 @@ class MetaAvatarRender(nn.Module):
                 tris, n_dev = hip.marching_cubes(sdf, 0.0, cap)
                 n = int(n_dev.item())
             return {"tris": hip.lattice_to_world(tris[:n], box), "n_tris": n, "box": box, "counts": counts}
+
+    def canonical_mesh(self, inputs, n_side=256, attributes=(), view_dirs=None):
+        """The canonical body of frame `inputs` as an indexed mesh, the reference's create_mesh_vertices_and_faces
+        (utils/sdf_meshing.py:13-114): the zero level set of the canonical SDF on the n_side^3 lattice (hip.sdf_grid_band, then
+        hip.marching_cubes_indexed).  -> dict of verts (V,3) normalised canonical coordinates in [-1,1]^3, faces (F,3) int32,
+        n_verts, n_tris, and per vertex whatever `attributes` names:
+
+            "weights"      (V,24) skinning weights at the vertex (hip.skin_lbs)
+            "verts_posed"  (V,3) world metres: the vertex skinned forward plus the translation, the reference's points_bar
+                           (models/__init__.py:211-226)
+            "normal"       (V,3) unit gradient of the canonical SDF (hip.sdf_eval), pointing out of the body
+            "color"        (V,3) the colour network at the vertex with the vertex's own transform (hip.shade_points).  The ray of
+                           every vertex is view_dirs (V,3) or (3,), world-space directions FROM the camera TOWARDS the surface
+                           as in the renderer; default: the ray that meets the posed surface head-on, minus the posed normal
+                           (the vertex's rotation applied to "normal", renormalised)
+
+        Eval only, GPU only; one host synchronisation (the mesh's size)."""
+        from . import meshing
+        names = ("weights", "verts_posed", "normal", "color")
+        bad = set(attributes) - set(names)
+        if bad:
+            raise ValueError("canonical_mesh: unknown attributes %s (known: %s)" % (sorted(bad), ", ".join(names)))
+        frame, ws = self._posed_frame(inputs, "canonical_mesh")
+        with torch.no_grad():
+            verts, faces = meshing.indexed_mesh(meshing.canonical_lattice(frame, ws, n_side), 0.0)
+            V = int(verts.shape[0])
+            res = {"verts": verts, "faces": faces, "n_verts": V, "n_tris": int(faces.shape[0])}
+            if not attributes:
+                return res
+            if V == 0:
+                res.update({k: torch.zeros(0, 24 if k == "weights" else 3, device=verts.device) for k in attributes})
+                return res
+            T = None
+            if set(attributes) & {"weights", "verts_posed", "color"}:
+                cmin, cmax, center = inputs["coord_min"][:1], inputs["coord_max"][:1], inputs["center"][:1]
+                x_hat = training.unnormalize_canonical_points(verts.reshape(1, -1, 3), cmin, cmax, center)[0]
+                w, x_bar, T = hip.skin_lbs(frame, ws, x_hat)
+                if "weights" in attributes:
+                    res["weights"] = w
+                if "verts_posed" in attributes:
+                    res["verts_posed"] = x_bar + inputs["trans"].reshape(1, 3)
+            if set(attributes) & {"normal", "color"}:
+                _, _, grad = hip.sdf_eval(frame, ws, verts, want_grad=True)
+                normal = grad / grad.norm(dim=1, keepdim=True).clamp_min(1e-20)
+                if "normal" in attributes:
+                    res["normal"] = normal
+            if "color" in attributes:
+                if view_dirs is None:
+                    posed_n = torch.einsum("pij,pj->pi", T[:, :3, :3], normal)
+                    dirs = -posed_n / posed_n.norm(dim=1, keepdim=True).clamp_min(1e-20)
+                else:
+                    dirs = torch.as_tensor(view_dirs, dtype=torch.float32, device=verts.device)
+                    if dirs.shape not in ((3,), (V, 3)):
+                        raise ValueError("view_dirs must be (3,) or (V, 3) = (%d, 3), got %s" % (V, tuple(dirs.shape)))
+                    dirs = dirs.expand(V, 3)
+                res["color"] = hip.shade_points(frame, ws, verts, T, dirs.contiguous(), self.idhr_network.cano_view_dirs)[0]
+        return res
 
     def geometry_metrics(self, inputs, gt, n_side=256, method="lattice", n_samples=100000, seed=0):
         """Geometry scores of the posed body of frame `inputs` against a ground-truth mesh `gt` in world metres ((F,3,3)

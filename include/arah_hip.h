@@ -30,6 +30,7 @@
  *   arah_joint_root_find    search_iso_surface_depth on caller-supplied starts  root_finding_utils.py:365-484
  *   arah_sdf_grid           create_mesh_vertices_and_faces' lattice evaluation  utils/sdf_meshing.py:13-70
  *   arah_marching_cubes     skimage.measure.marching_cubes_lewiner as called at utils/sdf_meshing.py:95 (+ :96-101)
+ *   arah_marching_cubes_indexed   the same call's (verts, faces) result, utils/sdf_meshing.py:95-114: shared vertices
  *   arah_rasterize          pytorch3d MeshRasterizer (pix_to_face) as used at metaavatar_render/models/__init__.py:232-276
  *   arah_shade_train_*      get_rbg_value_vol_sdf with self.training: per-sample forward and backward
  *                           renderer/implicit_differentiable_renderer.py:291-361, diff_operators.py:39-50
@@ -284,6 +285,20 @@ int arah_skin_lbs_counted(const ArahFrame* h_frame, const float* x_hat, int32_t 
 size_t arah_marching_cubes_scratch_bytes(int32_t n_side);
 int arah_marching_cubes(const float* sdf, int32_t n_side, float level, const int8_t* tri_table, const int32_t* n_tri,
                         float* tris, int32_t cap, int32_t* n_tris, void* scratch, size_t scratch_bytes, void* stream);
+/* The same level set as an INDEXED mesh (the (verts, faces) pair utils/sdf_meshing.py:13-114 returns): one vertex per
+ * crossing lattice edge.  The edge that leaves point (ix, iy, iz) along axis a (0 x, 1 y, 2 z; a point on the last layer of
+ * an axis has no edge along it) has the key ((ix n + iy) n + iz) 3 + a and crosses when (sdf[lo] < level) != (sdf[hi] < level).
+ * -> verts [vert_cap][3]: the crossing edges in ascending key order, each bit-equal to every corner arah_marching_cubes puts
+ * on that edge; vert_edge [vert_cap] (may be NULL): their keys; faces [face_cap][3]: triangle f of arah_marching_cubes on the
+ * same volume, corner for corner (after its orientation flip), as vertex ids; counts (device int32[2]) = the number of
+ * vertices and of faces of the level set, which may exceed the caps (then only the first vert_cap vertices and the first
+ * face_cap faces were written, and a written face may name a vertex beyond vert_cap).  Rows between a count and its cap are
+ * ZERO.  n_side >= 2 and 3 n^3 <= INT32_MAX (n <= 894); scratch: arah_marching_cubes_indexed_scratch_bytes(n_side) device
+ * bytes (0 for an n_side out of range).  Deterministic: no atomics.  No host synchronisation. */
+size_t arah_marching_cubes_indexed_scratch_bytes(int32_t n_side);
+int arah_marching_cubes_indexed(const float* sdf, int32_t n_side, float level, const int8_t* tri_table, const int32_t* n_tri,
+                                float* verts, int32_t vert_cap, int32_t* vert_edge, int32_t* faces, int32_t face_cap,
+                                int32_t* counts, void* scratch, size_t scratch_bytes, void* stream);
 /* raw canonical x_hat [P,3] -> d x_bar / d x_hat [P,3,3] */
 int arah_skin_jacobian(const ArahFrame* h_frame, const float* x_hat, int32_t n_pts, float* jac,
                        void* workspace, size_t workspace_bytes, void* stream);
