@@ -1863,6 +1863,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_canon_solve(FrameDev fr, const 
 }
 
 #include "mcubes.hpp"
+#include "meshcc.hpp"
 #include "canon_wave.hpp"
 
 // explicit targets (arah_broyden3_lbs): file them where k_canon_solve expects them, in row 3 of the start transform
@@ -3893,6 +3894,102 @@ int arah_marching_cubes_indexed(const float* sdf, int32_t n_side, float level, c
     hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)verts, (const int*)counts, (int)vert_cap, 3);
     hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)vert_edge, (const int*)counts, (int)vert_cap, 1);
     hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)faces, (const int*)counts + 1, (int)face_cap, 3);
+    return check_launch();
+}
+
+// ---- connected components of indexed meshes, selection of some of them (csrc/meshcc.hpp) ----------------------
+static bool cc_sizes_ok(int64_t n_verts, int64_t n_faces) {
+    return n_verts >= 0 && n_faces >= 0 && n_verts <= (int64_t)INT32_MAX && n_faces <= (int64_t)INT32_MAX;
+}
+static size_t cc_blocks(int64_t n) { return (size_t)((n + kCcChunk - 1) / kCcChunk); }
+static int cc_grid(int64_t n) { return (int)min((int64_t)kCcMaxGrid, max((int64_t)1, (n + kCcThreads - 1) / kCcThreads)); }
+
+size_t arah_mesh_components_scratch_bytes(int64_t n_verts, int64_t n_faces) {
+    if (!cc_sizes_ok(n_verts, n_faces)) return 0;
+    // the packed maximum (16 bytes), parent, root, dense, the chunks' counts and bases
+    return 16 + (3 * (size_t)n_verts + 2 * cc_blocks(n_verts)) * sizeof(int);
+}
+
+int arah_mesh_components(const int32_t* faces, int64_t n_faces, int64_t n_verts, int32_t* labels, int32_t* comp_verts,
+                         int32_t* comp_faces, int32_t* counts, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!cc_sizes_ok(n_verts, n_faces) || !counts || !scratch) return ARAH_E_BADARG;
+    if ((n_faces > 0 && !faces) || (n_verts > 0 && (!labels || !comp_verts || !comp_faces))) return ARAH_E_BADARG;
+    if (scratch_bytes < arah_mesh_components_scratch_bytes(n_verts, n_faces)) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (n_verts == 0) {   // no vertex, so no valid face either: nothing indexes an empty array
+        hipLaunchKernelGGL(k_cc_set_counts, dim3(1), dim3(64), 0, s, (int*)counts, 0, 0, -1, 3);
+        return check_launch();
+    }
+    const int V = (int)n_verts, F = (int)n_faces, nb = (int)cc_blocks(n_verts);
+    unsigned long long* best = reinterpret_cast<unsigned long long*>(scratch);
+    int* parent = reinterpret_cast<int*>(scratch) + 4;
+    int* root = parent + (size_t)V;
+    int* dense = root + (size_t)V;
+    int* blk_count = dense + (size_t)V;
+    int* blk_base = blk_count + nb;
+    const int* none = nullptr;
+    hipLaunchKernelGGL(k_cc_init, dim3(cc_grid(V)), dim3(kCcThreads), 0, s, parent, (int*)comp_verts, (int*)comp_faces, V, (int*)counts, best);
+    if (F > 0) hipLaunchKernelGGL(k_cc_hook, dim3(cc_grid(F)), dim3(kCcThreads), 0, s, (const int*)faces, F, V, parent);
+    hipLaunchKernelGGL(k_cc_flatten, dim3(cc_grid(V)), dim3(kCcThreads), 0, s, (const int*)parent, V, root);
+    hipLaunchKernelGGL((k_cc_compact<kCcRoots, false>), dim3(nb), dim3(kCcThreads), 0, s, none, (const int*)root, none, V, V, blk_count,
+                       none, (int*)nullptr, (int*)nullptr);
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)blk_count, nb, blk_base, (int*)counts);
+    hipLaunchKernelGGL((k_cc_compact<kCcRoots, true>), dim3(nb), dim3(kCcThreads), 0, s, none, (const int*)root, none, V, V,
+                       (int*)nullptr, (const int*)blk_base, dense, (int*)nullptr);
+    hipLaunchKernelGGL(k_cc_label, dim3(cc_grid(V)), dim3(kCcThreads), 0, s, (const int*)root, (const int*)dense, V, (int*)labels,
+                       (int*)comp_verts);
+    if (F > 0)
+        hipLaunchKernelGGL(k_cc_faces, dim3(cc_grid(F)), dim3(kCcThreads), 0, s, (const int*)faces, F, V, (const int*)labels,
+                           (int*)comp_faces, (int*)counts);
+    hipLaunchKernelGGL(k_cc_largest, dim3(cc_grid(V)), dim3(kCcThreads), 0, s, (const int*)comp_faces, (const int*)counts, best);
+    hipLaunchKernelGGL(k_cc_finish, dim3(1), dim3(64), 0, s, (const unsigned long long*)best, (int*)counts);
+    return check_launch();
+}
+
+size_t arah_mesh_select_scratch_bytes(int64_t n_verts, int64_t n_faces) {
+    if (!cc_sizes_ok(n_verts, n_faces)) return 0;
+    return 16 + 2 * (cc_blocks(n_verts) + cc_blocks(n_faces)) * sizeof(int);   // the chunks' counts and bases, vertices and faces
+}
+
+int arah_mesh_select(const int32_t* faces, int64_t n_faces, int64_t n_verts, const int32_t* labels, const int32_t* keep,
+                     int32_t* vert_src, int32_t* vert_map, int32_t* faces_out, int32_t* face_src, int32_t* counts, void* scratch,
+                     size_t scratch_bytes, void* stream) {
+    if (!cc_sizes_ok(n_verts, n_faces) || !counts || !scratch) return ARAH_E_BADARG;
+    if ((n_faces > 0 && (!faces || !faces_out || !face_src)) || (n_verts > 0 && (!labels || !keep || !vert_src || !vert_map)))
+        return ARAH_E_BADARG;
+    if (scratch_bytes < arah_mesh_select_scratch_bytes(n_verts, n_faces)) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int V = (int)n_verts, F = (int)n_faces, nbv = (int)cc_blocks(n_verts), nbf = (int)cc_blocks(n_faces);
+    if (V == 0) {   // nothing can be kept; the face outputs are all guard rows
+        hipLaunchKernelGGL(k_cc_set_counts, dim3(1), dim3(64), 0, s, (int*)counts, 0, 0, 0, 2);
+        if (F > 0) {
+            hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)faces_out, (const int*)counts + 1, F, 3);
+            hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)face_src, (const int*)counts + 1, F, 1);
+        }
+        return check_launch();
+    }
+    int* vblk_count = reinterpret_cast<int*>(scratch) + 4;
+    int* vblk_base = vblk_count + nbv;
+    int* fblk_count = vblk_base + nbv;
+    int* fblk_base = fblk_count + nbf;
+    const int* none = nullptr;
+    hipLaunchKernelGGL((k_cc_compact<kCcVerts, false>), dim3(nbv), dim3(kCcThreads), 0, s, none, (const int*)labels, (const int*)keep, V, V,
+                       vblk_count, none, (int*)nullptr, (int*)nullptr);
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)vblk_count, nbv, vblk_base, (int*)counts);
+    hipLaunchKernelGGL((k_cc_compact<kCcVerts, true>), dim3(nbv), dim3(kCcThreads), 0, s, none, (const int*)labels, (const int*)keep, V, V,
+                       (int*)nullptr, (const int*)vblk_base, (int*)vert_map, (int*)vert_src);
+    hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)vert_src, (const int*)counts, V, 1);
+    if (F == 0) {
+        hipLaunchKernelGGL(k_cc_set_counts, dim3(1), dim3(64), 0, s, (int*)counts + 1, 0, 0, 0, 1);
+        return check_launch();
+    }
+    hipLaunchKernelGGL((k_cc_compact<kCcFaces, false>), dim3(nbf), dim3(kCcThreads), 0, s, (const int*)faces, (const int*)vert_map, none, F, V,
+                       fblk_count, none, (int*)nullptr, (int*)nullptr);
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)fblk_count, nbf, fblk_base, (int*)counts + 1);
+    hipLaunchKernelGGL((k_cc_compact<kCcFaces, true>), dim3(nbf), dim3(kCcThreads), 0, s, (const int*)faces, (const int*)vert_map, none, F, V,
+                       (int*)nullptr, (const int*)fblk_base, (int*)faces_out, (int*)face_src);
+    hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)faces_out, (const int*)counts + 1, F, 3);
+    hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)face_src, (const int*)counts + 1, F, 1);
     return check_launch();
 }
 

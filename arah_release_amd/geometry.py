@@ -4,7 +4,9 @@ surface samples and their EXACT point-to-surface distances (hip.mesh_index / hip
 
 The reference publishes such numbers but its tree holds no code for them (its README points to a script in its issue
 tracker): PARITY UNPINNED, the definitions are this project's.  Also here: `load_mesh` for the two formats ground-truth meshes
-come in (.npz with `vertices` / `faces`, PLY with triangle faces), and `save_mesh`, which writes an indexed mesh in either."""
+come in (.npz with `vertices` / `faces`, PLY with triangle faces), and `save_mesh`, which writes an indexed mesh in either;
+`mesh_components` / `clean_mesh`: the connected components of an indexed mesh and the removal of its floaters (DESIGN.md "Mesh
+components on the device")."""
 import numpy as np
 import torch
 
@@ -103,6 +105,147 @@ def mesh_metrics(tris_a, tris_b, n_samples=100000, seed=0, return_samples=False)
     if return_samples:
         res["samples"] = {"tris_a": sa, "n_faces_a": ka, "points_a": pa, "face_a": fa, "d2_ab": d2_ab, "closest_face_ab": g_ab,
                           "tris_b": sb, "n_faces_b": kb, "points_b": pb, "face_b": fb, "d2_ba": d2_ba, "closest_face_ba": g_ba}
+    return res
+
+
+# ---- connected components, floater removal -----------------------------------------------------------------------------------
+def check_keep(keep):
+    """Validate a `keep` / `clean` policy of `clean_mesh` and return it in canonical form: ("largest",), ("referenced",),
+    ("faces", k) or ("share", m, e) with the float share = m / 2^e exactly.  ValueError for anything else."""
+    import math
+    if isinstance(keep, str):
+        if keep in ("largest", "referenced"):
+            return (keep,)
+    elif isinstance(keep, bool):
+        pass
+    elif isinstance(keep, (int, np.integer)):
+        if 0 <= int(keep) <= 2 ** 31 - 1:
+            return ("faces", int(keep))
+    elif isinstance(keep, (float, np.floating)):
+        if math.isfinite(float(keep)) and 0.0 < float(keep) <= 1.0:
+            m, q = float(keep).as_integer_ratio()          # q is a power of two, m < 2^53
+            return ("share", m, q.bit_length() - 1)
+    raise ValueError("keep must be 'largest', 'referenced', an int >= 0 (faces) or a float in (0, 1] (share of the largest "
+                     "component's faces), got %r" % (keep,))
+
+
+def ceil_share(most, m, e):
+    """ceil(most m / 2^e) in int64 tensor operations, exactly: most a 0-dim int64 tensor in [0, 2^31), 0 < m < 2^53, m <= 2^e.
+    most m can need 84 bits, so m is split at bit 26: most m = (most mh) 2^26 + most ml, both products below 2^58."""
+    if e <= 26:                                        # m <= 2^26: the product fits
+        return (most * m + ((1 << e) - 1)) >> e
+    mh, ml = m >> 26, m & ((1 << 26) - 1)
+    low = most * ml
+    high = most * mh + (low >> 26)                     # floor(most m / 2^26)
+    rest = (low & ((1 << 26) - 1)) != 0                # ... and whether bits were dropped
+    s = e - 26
+    if s >= 62:                                        # high < 2^59: the quotient is below 1
+        return ((high != 0) | rest).long()
+    return (high >> s) + (((high & ((1 << s) - 1)) != 0) | rest).long()
+
+
+def keep_components(policy, comp_faces, counts):
+    """The policy of `check_keep` as a few elementwise operations on the device: comp_faces (V,) and counts (3,) of
+    mesh_components -> keep (V,) int32 indexed by component id (entries beyond the component count are never looked at).
+
+        ("largest",)      the component with the most faces (ties: the lowest id)
+        ("faces", k)      every component with at least k faces
+        ("share", m, e)   every component with at least ceil(share largest) faces, share = m / 2^e being the float exactly; the
+                          threshold is computed in integers (ceil_share)
+        ("referenced",)   every component with a face: only the vertices no valid face names go"""
+    V = comp_faces.shape[0]
+    if policy[0] == "largest":
+        keep = torch.arange(V, device=comp_faces.device) == counts[2]
+    elif policy[0] == "faces":
+        keep = comp_faces >= policy[1]
+    elif policy[0] == "share":
+        most = comp_faces.max().long() if V else torch.zeros((), dtype=torch.int64, device=comp_faces.device)
+        keep = comp_faces.long() >= ceil_share(most, policy[1], policy[2])
+    else:
+        keep = comp_faces > 0
+    return keep.to(torch.int32)
+
+
+def _mesh_args(verts_or_n_verts, faces, what):
+    if isinstance(verts_or_n_verts, torch.Tensor) and verts_or_n_verts.dim() > 0:
+        if verts_or_n_verts.dim() != 2 or verts_or_n_verts.shape[1] != 3:
+            raise ValueError("%s: verts must be (V, 3), got %s" % (what, tuple(verts_or_n_verts.shape)))
+        n_verts = int(verts_or_n_verts.shape[0])
+    else:
+        n_verts = verts_or_n_verts
+        if isinstance(n_verts, (bool, float)) or isinstance(n_verts, torch.Tensor) or int(n_verts) != n_verts or int(n_verts) < 0:
+            raise ValueError("%s: the vertex count must be an integer >= 0 or verts (V, 3), got %r" % (what, n_verts))
+        n_verts = int(n_verts)
+    if not isinstance(faces, torch.Tensor):
+        raise ValueError("%s: faces must be an (F, 3) tensor" % what)
+    return n_verts, faces      # shape and dtype of the faces: the backend's own checks
+
+
+def _cc_backend(faces):
+    """The two kernels for a mesh on the GPU, their tensor specification for one on the host."""
+    if faces.is_cuda:
+        from . import hip
+        return hip
+    from . import meshing
+    return meshing
+
+
+def mesh_components(verts_or_n_verts, faces):
+    """Connected components of an indexed mesh by shared vertex ids (hip.mesh_components on the GPU, meshing.mesh_components on the
+    host): faces (F,3) integer ids, and the vertices (V,3) or just their number.  A face with an id out of range is skipped, a
+    vertex no valid face names is a component of its own.  -> dict of labels (V,) int32 component of every vertex, n_components C,
+    comp_verts / comp_faces (C,) int32 sizes, n_valid_faces and largest (the component with the most faces, ties to the lowest id;
+    -1 for an empty mesh).  Components are numbered in ascending order of their smallest vertex id.  One host synchronisation
+    (the counts)."""
+    n_verts, faces = _mesh_args(verts_or_n_verts, faces, "mesh_components")
+    labels, comp_verts, comp_faces, counts = _cc_backend(faces).mesh_components(faces, n_verts)
+    C, n_valid, largest = counts.tolist()
+    return {"labels": labels, "n_components": C, "comp_verts": comp_verts[:C], "comp_faces": comp_faces[:C],
+            "n_valid_faces": n_valid, "largest": largest}
+
+
+def clean_mesh(verts, faces, keep="largest", attributes=None):
+    """Drop floaters: the indexed mesh (verts (V,3), faces (F,3) integer ids) restricted to the connected components `keep` names,
+    vertices and faces in their original order.
+
+        keep = "largest"      the component with the most faces (ties: the lowest-numbered one)
+               int k          every component with at least k faces
+               float in (0,1] every component with at least ceil(share largest) faces, largest being the largest component's
+               "referenced"   every component with a face: only unreferenced vertices go
+
+    Faces with an id out of range are dropped whatever `keep` says.  -> dict of verts (V',3), faces (F',3) in the dtype of
+    `faces`, n_verts, n_tris, vert_src (V',) int64 (the old id of every new vertex: verts_out = verts[vert_src]), removed = dict
+    of the components / vertices / faces dropped, and every tensor of the dict `attributes` (first dimension V) gathered by
+    vert_src.  On the GPU the labelling and the compaction are arah_mesh_components / arah_mesh_select, the policy a few
+    elementwise operations between them, and ONE host synchronisation reads the kept sizes; on the host the same through their
+    tensor specification."""
+    policy = check_keep(keep)
+    n_verts, faces = _mesh_args(verts, faces, "clean_mesh")
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2:
+        raise ValueError("clean_mesh: verts must be a (V, 3) tensor")
+    if verts.device != faces.device:
+        raise ValueError("clean_mesh: verts live on %s, faces on %s" % (verts.device, faces.device))
+    attributes = dict(attributes or {})
+    reserved = ("verts", "faces", "n_verts", "n_tris", "vert_src", "removed")
+    for name, t in attributes.items():
+        if name in reserved:
+            raise ValueError("clean_mesh: an attribute cannot be called %r" % (name,))
+        if not isinstance(t, torch.Tensor) or t.dim() < 1 or t.shape[0] != n_verts or t.device != verts.device:
+            raise ValueError("clean_mesh: attribute %r must be a tensor with %d rows on %s" % (name, n_verts, verts.device))
+    backend = _cc_backend(faces)
+    with torch.no_grad():
+        labels, _, comp_faces, counts = backend.mesh_components(faces, n_verts)
+        keep_c = keep_components(policy, comp_faces, counts)
+        vert_src, _, faces_out, _, kept = backend.mesh_select(faces, n_verts, labels, keep_c)
+        in_use = torch.arange(n_verts, device=faces.device) < counts[0]
+        kept_comps = (keep_c.bool() & in_use).sum().to(torch.int32).reshape(1)
+        nv, nf, C, nc = torch.cat([kept, counts[:1], kept_comps]).tolist()      # the host synchronisation
+        vert_src = vert_src[:nv].long()
+        res = {"verts": verts.index_select(0, vert_src), "faces": faces_out[:nf].to(faces.dtype), "n_verts": nv, "n_tris": nf,
+               "vert_src": vert_src,
+               "removed": {"components": C - nc, "vertices": n_verts - nv, "faces": int(faces.shape[0]) - nf}}
+        for name, t in attributes.items():
+            res[name] = t.index_select(0, vert_src)
     return res
 
 

@@ -134,7 +134,8 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_tier_audit_debug", "arah_occupancy_clear_box", "arah_render_maps_bytes", "arah_render_maps",
            "arah_query_posed_bytes", "arah_query_posed", "arah_sdf_grid_posed_bytes", "arah_sdf_grid_posed",
            "arah_image_metrics_bytes", "arah_image_metrics",
-           "arah_mesh_index_bytes", "arah_mesh_index_build", "arah_mesh_closest", "arah_surface_metrics_bytes", "arah_surface_metrics", "arah_face_area_cumsum"]
+           "arah_mesh_index_bytes", "arah_mesh_index_build", "arah_mesh_closest", "arah_surface_metrics_bytes", "arah_surface_metrics", "arah_face_area_cumsum",
+           "arah_mesh_components_scratch_bytes", "arah_mesh_components", "arah_mesh_select_scratch_bytes", "arah_mesh_select"]
 
 _lib = None
 
@@ -176,6 +177,9 @@ def load_library():
     lib.arah_mesh_index_bytes.argtypes = [C.c_int32]
     lib.arah_surface_metrics_bytes.restype = C.c_size_t
     lib.arah_surface_metrics_bytes.argtypes = [C.c_int32, C.c_int32]
+    for name in ("arah_mesh_components_scratch_bytes", "arah_mesh_select_scratch_bytes"):
+        getattr(lib, name).restype = C.c_size_t
+        getattr(lib, name).argtypes = [C.c_int64, C.c_int64]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the symbol is missing
     _lib = lib
@@ -747,6 +751,89 @@ def marching_cubes_indexed(sdf, level=0.0, vert_cap=1 << 19, face_cap=1 << 20, w
                                                _ptr(counts), _ptr(scratch), C.c_size_t(scratch.numel()), _stream()),
                "arah_marching_cubes_indexed")
     return (verts, faces, counts, vert_edge) if want_edge else (verts, faces, counts)
+
+
+_mesh_cc_scratch = {}
+
+
+def _mesh_cc_buf(dev, nbytes):
+    """Per-(device, stream) scratch of mesh_components / mesh_select (grows on demand; one stream's calls are ordered)."""
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+    buf = _mesh_cc_scratch.get(key)
+    if buf is None or buf.numel() < nbytes:
+        if buf is None and len(_mesh_cc_scratch) >= 8:
+            _mesh_cc_scratch.pop(next(iter(_mesh_cc_scratch)))
+        buf = _mesh_cc_scratch[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    return buf
+
+
+def _mesh_cc_args(faces, n_verts, what):
+    """faces (F,3) integer ids on the GPU and the vertex count of a mesh_components / mesh_select call, checked: -> (faces int32
+    contiguous, V, F)."""
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("%s: faces must be an (F, 3) tensor" % what)
+    if faces.dtype.is_floating_point or faces.dtype.is_complex or faces.dtype == torch.bool:
+        raise ValueError("%s: faces must hold integer vertex ids" % what)
+    if not faces.is_cuda:
+        raise ValueError("%s runs on the HIP kernels: faces must live on the GPU (meshing.%s is the host's)" % (what, what))
+    if isinstance(n_verts, bool) or int(n_verts) != n_verts or not 0 <= int(n_verts) <= 2 ** 31 - 1:
+        raise ValueError("%s: n_verts must be an integer in [0, 2^31), got %r" % (what, n_verts))
+    if faces.dtype != torch.int32:
+        # through int64, which holds every narrower type; ids that do not fit int32 are invalid anyway: they become -1, which the
+        # kernels skip
+        faces = faces.to(torch.int64)
+        faces = torch.where((faces >= 0) & (faces <= 2 ** 31 - 1), faces, torch.full_like(faces, -1)).to(torch.int32)
+    return faces.detach().contiguous(), int(n_verts), int(faces.shape[0])
+
+
+def mesh_components(faces, n_verts):
+    """Connected components of the indexed mesh with faces (F,3) integer vertex ids (on the GPU) over n_verts vertices
+    (arah_mesh_components, csrc/meshcc.hpp): two vertices are connected when a face names both; a face with an id outside [0, n_verts)
+    is skipped; a vertex no valid face names is a component of its own.  -> labels (V,) int32 dense component ids in [0, C),
+    numbered in ascending order of the components' smallest vertex ids; comp_verts, comp_faces (V,) int32 sizes of component c, zero
+    for c >= C; counts (3,) int32 = C, the valid faces, the component with the most faces (ties: the lowest id; -1 when C = 0).
+    All on the device, no host synchronisation.  The result is meshing.mesh_components(faces, n_verts) bit for bit.  The scratch is
+    kept per (device, stream) and grows on demand."""
+    require_gpu()
+    lib = load_library()
+    f, V, F = _mesh_cc_args(faces, n_verts, "mesh_components")
+    dev = f.device
+    with _on_device(dev):
+        scratch = _mesh_cc_buf(dev, int(lib.arah_mesh_components_scratch_bytes(V, F)))
+        labels, comp_verts, comp_faces = (torch.empty(V, dtype=torch.int32, device=dev) for _ in range(3))
+        counts = torch.empty(3, dtype=torch.int32, device=dev)
+        _check(lib.arah_mesh_components(_ptr(f), C.c_int64(F), C.c_int64(V), _ptr(labels), _ptr(comp_verts), _ptr(comp_faces),
+                                        _ptr(counts), _ptr(scratch), C.c_size_t(scratch.numel()), _stream()), "arah_mesh_components")
+    return labels, comp_verts, comp_faces, counts
+
+
+def mesh_select(faces, n_verts, labels, keep):
+    """Order-preserving selection of the components with keep[c] != 0 (arah_mesh_select): labels (V,) from `mesh_components`, keep
+    (V,) integer or bool indexed by component id.  -> vert_src (V,) int32 old id of new vertex j; vert_map (V,) int32 new id of old
+    vertex v or -1; faces_out (F,3) int32 the kept valid faces in their order with the new ids; face_src (F,) int32 their old
+    rows; counts (2,) int32 kept vertices, kept faces.  Rows beyond the counts are zero.  All on the device, no host
+    synchronisation; the result is meshing.mesh_select(...) bit for bit."""
+    require_gpu()
+    lib = load_library()
+    f, V, F = _mesh_cc_args(faces, n_verts, "mesh_select")
+    dev = f.device
+    for name, t in (("labels", labels), ("keep", keep)):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (V,) or t.dtype.is_floating_point or t.dtype.is_complex:
+            raise ValueError("mesh_select: %s must be an integer tensor of shape (%d,)" % (name, V))
+        if t.device != dev:
+            raise ValueError("mesh_select: %s lives on %s, faces on %s" % (name, t.device, dev))
+    lab = labels.detach().to(torch.int32).contiguous()
+    kp = (keep.detach() != 0).to(torch.int32).contiguous()
+    with _on_device(dev):
+        scratch = _mesh_cc_buf(dev, int(lib.arah_mesh_select_scratch_bytes(V, F)))
+        vert_src, vert_map = (torch.empty(V, dtype=torch.int32, device=dev) for _ in range(2))
+        faces_out = torch.empty(F, 3, dtype=torch.int32, device=dev)
+        face_src = torch.empty(F, dtype=torch.int32, device=dev)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        _check(lib.arah_mesh_select(_ptr(f), C.c_int64(F), C.c_int64(V), _ptr(lab), _ptr(kp), _ptr(vert_src), _ptr(vert_map),
+                                    _ptr(faces_out), _ptr(face_src), _ptr(counts), _ptr(scratch), C.c_size_t(scratch.numel()),
+                                    _stream()), "arah_mesh_select")
+    return vert_src, vert_map, faces_out, face_src, counts
 
 
 def marching_cubes(sdf, level=0.0, cap=1 << 20):

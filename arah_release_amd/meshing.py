@@ -203,6 +203,84 @@ def indexed_mesh(sdf, level=0.0):
     return verts[:V], faces[:F]
 
 
+def _cc_faces(faces, n_verts, what):
+    faces = torch.as_tensor(faces)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("%s: faces must be an (F, 3) tensor" % what)
+    if faces.dtype.is_floating_point or faces.dtype.is_complex or faces.dtype == torch.bool:
+        raise ValueError("%s: faces must hold integer vertex ids" % what)
+    if isinstance(n_verts, bool) or int(n_verts) != n_verts or not 0 <= int(n_verts) <= 2 ** 31 - 1:
+        raise ValueError("%s: n_verts must be an integer in [0, 2^31), got %r" % (what, n_verts))
+    faces = faces.long()
+    return faces, int(n_verts), ((faces >= 0) & (faces < int(n_verts))).all(1)
+
+
+def mesh_components(faces, n_verts):
+    """Connected components of an indexed mesh by SHARED VERTEX IDS: faces (F,3) integer ids over n_verts vertices; two vertices
+    are connected when a face names both (positions play no part); a face with an id outside [0, n_verts) is skipped; a vertex
+    no valid face names is a component of its own with 0 faces.  -> labels (V,) int32: dense component ids in [0, C), components
+    numbered in ascending order of their smallest vertex id; comp_verts, comp_faces (V,) int32: the sizes of component c, zero
+    for c >= C; counts (3,) int32: C, the number of valid faces, the component with the most faces (ties: the lowest id; -1
+    when C = 0).  Every vertex takes the smallest label among itself and the vertices it shares a face with, then its label's
+    label, until nothing changes: the fixed point is the smallest vertex id of its component.  Plain tensor operations on the
+    tensor's device: the specification of arah_mesh_components (csrc/meshcc.hpp), and what runs for meshes on the host."""
+    faces, V, valid = _cc_faces(faces, n_verts, "mesh_components")
+    dev = faces.device
+    fv = faces[valid]
+    ids = torch.arange(V, device=dev)
+    low = ids.clone()
+    while fv.shape[0]:
+        new = low.scatter_reduce(0, fv.reshape(-1), low[fv].min(1).values.repeat_interleave(3), "amin")
+        new = new[new]
+        if torch.equal(new, low):
+            break
+        low = new
+    is_root = low == ids
+    labels = (torch.cumsum(is_root.long(), 0) - 1)[low]
+    n_comp = int(is_root.sum())
+    comp_verts = torch.bincount(labels, minlength=V)
+    comp_faces = torch.bincount(labels[fv[:, 0]], minlength=V)
+    if n_comp:
+        most = comp_faces[:n_comp].max()
+        largest = int(torch.nonzero(comp_faces[:n_comp] == most)[0, 0])
+    else:
+        largest = -1
+    counts = torch.tensor([n_comp, int(fv.shape[0]), largest], dtype=torch.int32, device=dev)
+    return labels.to(torch.int32), comp_verts.to(torch.int32), comp_faces.to(torch.int32), counts
+
+
+def mesh_select(faces, n_verts, labels, keep):
+    """Order-preserving selection of the components with keep[c] != 0: labels (V,) of `mesh_components`, keep (V,) integer or
+    bool indexed by component id.  A vertex is kept when its component is (a label outside [0, V) keeps nothing); a face when its
+    ids are valid and its three vertices are kept.  -> vert_src (V,) int32: the old id of new vertex j, in the original order;
+    vert_map (V,) int32: the new id of old vertex v, or -1; faces_out (F,3) int32: the kept faces in their original order with
+    the new ids; face_src (F,) int32: their old rows; counts (2,) int32: kept vertices, kept faces.  Rows beyond a count are
+    zero.  The specification of arah_mesh_select (csrc/meshcc.hpp)."""
+    faces, V, valid = _cc_faces(faces, n_verts, "mesh_select")
+    dev, F = faces.device, faces.shape[0]
+    for name, t in (("labels", labels), ("keep", keep)):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (V,) or t.dtype.is_floating_point or t.dtype.is_complex:
+            raise ValueError("mesh_select: %s must be an integer tensor of shape (%d,)" % (name, V))
+    labels = labels.to(dev).long()
+    in_range = (labels >= 0) & (labels < V)
+    kept_v = in_range & (keep.to(dev)[labels.clamp(0, max(V - 1, 0))] != 0) if V else torch.zeros(0, dtype=torch.bool, device=dev)
+    src_v = torch.nonzero(kept_v)[:, 0]
+    vert_map = torch.full((V,), -1, dtype=torch.int64, device=dev)
+    vert_map[src_v] = torch.arange(src_v.shape[0], device=dev)
+    kept_f = valid.clone()
+    kept_f[valid] = kept_v[faces[valid]].all(1)
+    src_f = torch.nonzero(kept_f)[:, 0]
+    vert_src = torch.zeros(V, dtype=torch.int64, device=dev)
+    vert_src[:src_v.shape[0]] = src_v
+    faces_out = torch.zeros(F, 3, dtype=torch.int64, device=dev)
+    faces_out[:src_f.shape[0]] = vert_map[faces[src_f]]
+    face_src = torch.zeros(F, dtype=torch.int64, device=dev)
+    face_src[:src_f.shape[0]] = src_f
+    counts = torch.tensor([src_v.shape[0], src_f.shape[0]], dtype=torch.int32, device=dev)
+    i32 = torch.int32
+    return vert_src.to(i32), vert_map.to(i32), faces_out.to(i32), face_src.to(i32), counts
+
+
 def face_normals(tri):
     """Unit right-hand normals of a triangle soup (F,3,3) (pytorch3d Meshes.faces_normals_packed)."""
     n = torch.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0], dim=1)

@@ -899,7 +899,7 @@ class MetaAvatarRender(nn.Module):
                 "points_hat": r["points_hat"].reshape(*shape, 3), "weights": r["weights"].reshape(*shape, 24),
                 "converged": (r["state"] == 1).reshape(shape), "state": r["state"].reshape(shape)}
 
-    def posed_mesh(self, inputs, n_side=256, method="lattice", bounds=None, indexed=False):
+    def posed_mesh(self, inputs, n_side=256, method="lattice", bounds=None, indexed=False, clean=None):
         """A triangle soup of the posed body of frame `inputs` in world metres.  method="lattice": the zero level set of the posed
         SDF (hip.sdf_grid_posed, only the band around the occupancy bitmap's marked voxels unless ARAH_POSED_MESH_BAND=0, then
         hip.marching_cubes) -- the surface the renderer sees, self-contact included.  method="skinned": the reference's points_bar
@@ -910,8 +910,14 @@ class MetaAvatarRender(nn.Module):
         it was too small: nothing is truncated.  indexed=True: the same surface as an indexed mesh (hip.marching_cubes_indexed,
         one vertex per crossing lattice edge) -- verts (V,3) world metres, faces (F,3) int32, n_verts and n_tris take the place of
         tris, and verts[faces] is the soup of the default call bit for bit; "skinned" then skins V vertices instead of 3 F
-        corners.  Eval only."""
-        from . import meshing
+        corners.  clean (indexed=True only; None: nothing changes): a `keep` policy of geometry.clean_mesh ("largest", a face
+        count, a share of the largest component's faces, "referenced") -- the mesh is geometry.clean_mesh of the uncleaned call's,
+        floaters dropped on the device, and vert_src and removed come with it.  Eval only."""
+        from . import geometry, meshing
+        if clean is not None:
+            geometry.check_keep(clean)
+            if not indexed:
+                raise ValueError("posed_mesh: clean needs indexed=True (components are defined by shared vertex ids)")
         frame, ws = self._posed_frame(inputs, "posed_mesh")
         if method not in ("lattice", "skinned"):
             raise ValueError("method must be 'lattice' or 'skinned', got %r" % (method,))
@@ -935,7 +941,10 @@ class MetaAvatarRender(nn.Module):
                 V, F = size.tolist()
                 if V > vert_cap or F > face_cap:   # too small for this level set: the exact sizes, once more
                     verts, faces, size = extract(max(V, 1), max(F, 1))
-                return {"verts": verts[:V], "faces": faces[:F], "n_verts": V, "n_tris": F, "box": box, "counts": counts}
+                res = {"verts": verts[:V], "faces": faces[:F], "n_verts": V, "n_tris": F, "box": box, "counts": counts}
+                if clean is not None:
+                    res.update(geometry.clean_mesh(res["verts"], res["faces"], keep=clean))
+                return res
             if method == "skinned":
                 cap = meshing.MC_DEFAULT_CAP
                 _, posed, n_dev = meshing.skinned_mesh(frame, ws, inputs, n_side, cap=cap)
@@ -958,7 +967,7 @@ class MetaAvatarRender(nn.Module):
                 n = int(n_dev.item())
             return {"tris": hip.lattice_to_world(tris[:n], box), "n_tris": n, "box": box, "counts": counts}
 
-    def canonical_mesh(self, inputs, n_side=256, attributes=(), view_dirs=None):
+    def canonical_mesh(self, inputs, n_side=256, attributes=(), view_dirs=None, clean=None):
         """The canonical body of frame `inputs` as an indexed mesh, the reference's create_mesh_vertices_and_faces
         (utils/sdf_meshing.py:13-114): the zero level set of the canonical SDF on the n_side^3 lattice (hip.sdf_grid_band, then
         hip.marching_cubes_indexed).  -> dict of verts (V,3) normalised canonical coordinates in [-1,1]^3, faces (F,3) int32,
@@ -973,17 +982,26 @@ class MetaAvatarRender(nn.Module):
                            as in the renderer; default: the ray that meets the posed surface head-on, minus the posed normal
                            (the vertex's rotation applied to "normal", renormalised)
 
-        Eval only, GPU only; one host synchronisation (the mesh's size)."""
-        from . import meshing
+        clean (None: nothing changes): a `keep` policy of geometry.clean_mesh; the floaters are dropped BEFORE the attributes are
+        evaluated, so a dropped vertex costs no network evaluation, and vert_src (the kept vertices' ids in the uncleaned mesh)
+        and removed come with the result.  With view_dirs (V,3), V is the cleaned mesh's.
+
+        Eval only, GPU only; one host synchronisation (the mesh's size), one more with clean."""
+        from . import geometry, meshing
         names = ("weights", "verts_posed", "normal", "color")
         bad = set(attributes) - set(names)
         if bad:
             raise ValueError("canonical_mesh: unknown attributes %s (known: %s)" % (sorted(bad), ", ".join(names)))
+        if clean is not None:
+            geometry.check_keep(clean)
         frame, ws = self._posed_frame(inputs, "canonical_mesh")
         with torch.no_grad():
             verts, faces = meshing.indexed_mesh(meshing.canonical_lattice(frame, ws, n_side), 0.0)
             V = int(verts.shape[0])
             res = {"verts": verts, "faces": faces, "n_verts": V, "n_tris": int(faces.shape[0])}
+            if clean is not None:
+                res = geometry.clean_mesh(verts, faces, keep=clean)
+                verts, faces, V = res["verts"].contiguous(), res["faces"], res["n_verts"]
             if not attributes:
                 return res
             if V == 0:
@@ -1015,20 +1033,27 @@ class MetaAvatarRender(nn.Module):
                 res["color"] = hip.shade_points(frame, ws, verts, T, dirs.contiguous(), self.idhr_network.cano_view_dirs)[0]
         return res
 
-    def geometry_metrics(self, inputs, gt, n_side=256, method="lattice", n_samples=100000, seed=0):
+    def geometry_metrics(self, inputs, gt, n_side=256, method="lattice", n_samples=100000, seed=0, clean=None):
         """Geometry scores of the posed body of frame `inputs` against a ground-truth mesh `gt` in world metres ((F,3,3)
         triangles or a (verts, faces) pair on the inputs' GPU): `posed_mesh(inputs, n_side, method)` as the prediction, then
         geometry.mesh_metrics -- accuracy is the mean distance of the posed mesh's samples to the ground truth, completeness
-        the other way round.  -> its dict of 0-dimensional float64 device tensors, plus n_tris of the posed mesh.  Eval only."""
+        the other way round.  -> its dict of 0-dimensional float64 device tensors, plus n_tris of the posed mesh.  clean (None:
+        nothing changes): the `clean` of posed_mesh -- the prediction is the indexed posed mesh without its floaters, one of which
+        would otherwise set the Hausdorff distance.  Eval only."""
         from . import geometry
         if self.training:
             raise ValueError("geometry_metrics is eval-only: call model.eval() first")
         if inputs["rots"].device.type != "cuda":
             raise ValueError("geometry_metrics runs on the HIP kernels: the inputs must live on the GPU")
-        mesh = self.posed_mesh(inputs, n_side=n_side, method=method)
+        if clean is not None:
+            mesh = self.posed_mesh(inputs, n_side=n_side, method=method, indexed=True, clean=clean)
+            pred = (mesh["verts"], mesh["faces"])
+        else:
+            mesh = self.posed_mesh(inputs, n_side=n_side, method=method)
+            pred = mesh["tris"]
         if mesh["n_tris"] < 1:
             raise ValueError("geometry_metrics: the posed level set is empty")
-        res = geometry.mesh_metrics(mesh["tris"], gt, n_samples=n_samples, seed=seed)
+        res = geometry.mesh_metrics(pred, gt, n_samples=n_samples, seed=seed)
         res["n_tris"] = mesh["n_tris"]
         return res
 

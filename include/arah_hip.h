@@ -31,6 +31,8 @@
  *   arah_sdf_grid           create_mesh_vertices_and_faces' lattice evaluation  utils/sdf_meshing.py:13-70
  *   arah_marching_cubes     skimage.measure.marching_cubes_lewiner as called at utils/sdf_meshing.py:95 (+ :96-101)
  *   arah_marching_cubes_indexed   the same call's (verts, faces) result, utils/sdf_meshing.py:95-114: shared vertices
+ *   arah_mesh_components /  (none: the reference writes the extracted mesh as it comes; connected components of an indexed mesh
+ *   arah_mesh_select        by shared vertex ids, and the order-preserving selection of some of them: floater removal)
  *   arah_rasterize          pytorch3d MeshRasterizer (pix_to_face) as used at metaavatar_render/models/__init__.py:232-276
  *   arah_shade_train_*      get_rbg_value_vol_sdf with self.training: per-sample forward and backward
  *                           renderer/implicit_differentiable_renderer.py:291-361, diff_operators.py:39-50
@@ -299,6 +301,29 @@ size_t arah_marching_cubes_indexed_scratch_bytes(int32_t n_side);
 int arah_marching_cubes_indexed(const float* sdf, int32_t n_side, float level, const int8_t* tri_table, const int32_t* n_tri,
                                 float* verts, int32_t vert_cap, int32_t* vert_edge, int32_t* faces, int32_t face_cap,
                                 int32_t* counts, void* scratch, size_t scratch_bytes, void* stream);
+/* Connected components of an indexed mesh.  faces [n_faces][3] vertex ids; two vertices are connected when a face names both
+ * (positions play no part).  A face with an id outside [0, n_verts) is SKIPPED (a truncated arah_marching_cubes_indexed may
+ * name a vertex beyond vert_cap); a vertex no valid face names is a component of its own with 0 faces.  -> labels [n_verts]:
+ * the component of every vertex, dense ids in [0, C), components numbered in ascending order of their smallest vertex id;
+ * comp_verts / comp_faces [n_verts]: vertices and valid faces of component c, ZERO for c >= C; counts (device int32[3]) = C,
+ * the number of valid faces, the component with the most faces (ties: the lowest id; -1 when C = 0).  Integer atomics only
+ * (min, add, max): the result is unique.  0 <= n_verts, n_faces <= INT32_MAX, otherwise ARAH_E_BADARG without a launch and
+ * a scratch size of 0; scratch: arah_mesh_components_scratch_bytes(n_verts, n_faces) device bytes, 8-byte aligned.  Empty
+ * inputs still write counts; pointers of empty arrays may be NULL.  No host synchronisation, no allocation. */
+size_t arah_mesh_components_scratch_bytes(int64_t n_verts, int64_t n_faces);
+int arah_mesh_components(const int32_t* faces, int64_t n_faces, int64_t n_verts, int32_t* labels, int32_t* comp_verts,
+                         int32_t* comp_faces, int32_t* counts, void* scratch, size_t scratch_bytes, void* stream);
+/* Order-preserving selection of components.  labels [n_verts] as above, keep [n_verts] int32 indexed by COMPONENT id.  A vertex
+ * is kept when keep[labels[v]] != 0 (a label outside [0, n_verts) keeps nothing); a face is kept when its ids are valid and
+ * its three vertices are kept.  -> vert_src [n_verts]: the old id of new vertex j, kept vertices in their original order;
+ * vert_map [n_verts]: the new id of old vertex v, or -1; faces_out [n_faces][3]: the kept faces in their original order with
+ * the new ids; face_src [n_faces]: their old rows; counts (device int32[2]) = kept vertices, kept faces.  Rows between a count
+ * and the array's length are ZERO (vert_map has none).  The outputs are sized by the inputs: nothing can be truncated.  Sizes,
+ * errors, scratch (arah_mesh_select_scratch_bytes) and empty inputs as for arah_mesh_components. */
+size_t arah_mesh_select_scratch_bytes(int64_t n_verts, int64_t n_faces);
+int arah_mesh_select(const int32_t* faces, int64_t n_faces, int64_t n_verts, const int32_t* labels, const int32_t* keep,
+                     int32_t* vert_src, int32_t* vert_map, int32_t* faces_out, int32_t* face_src, int32_t* counts, void* scratch,
+                     size_t scratch_bytes, void* stream);
 /* raw canonical x_hat [P,3] -> d x_bar / d x_hat [P,3,3] */
 int arah_skin_jacobian(const ArahFrame* h_frame, const float* x_hat, int32_t n_pts, float* jac,
                        void* workspace, size_t workspace_bytes, void* stream);
