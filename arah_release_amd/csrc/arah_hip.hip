@@ -2751,6 +2751,7 @@ __global__ void k_points_cam(FrameDev fr, int n, RaySet rs, const float* dists, 
 #include "meshquery.hpp"
 #include "metrics.hpp"
 #include "meshdist.hpp"
+#include "pointdist.hpp"
 namespace {
 
 // ------------------------------------------------------------------------------------------
@@ -5101,7 +5102,7 @@ int arah_mesh_index_build(const float* tris, int32_t n_faces, void* index, size_
     hipLaunchKernelGGL(k_md_header, dim3(1), dim3(kMdStatBlocks), 0, s, (const double*)m.stat, (int)n_faces, m.cap_cells, m.hdr);
     hipLaunchKernelGGL(k_md_bin<false>, dim3(fg), dim3(kMdThreads), 0, s, tris, (int)n_faces, m.hdr, m.cell_count,
                        (const int*)m.cell_base, m.refs, m.big);
-    hipLaunchKernelGGL(k_md_scan, dim3(1), dim3(1024), 0, s, (const int*)m.cell_count, m.hdr, m.cell_base);
+    hipLaunchKernelGGL(k_md_scan<MdHeader>, dim3(1), dim3(1024), 0, s, (const int*)m.cell_count, m.hdr, m.cell_base);
     hipLaunchKernelGGL(k_md_bin<true>, dim3(fg), dim3(kMdThreads), 0, s, tris, (int)n_faces, m.hdr, m.cell_count,
                        (const int*)m.cell_base, m.refs, m.big);
     hipLaunchKernelGGL(k_md_dt<0>, dim3(cg), dim3(kMdThreads), 0, s, (const MdHeader*)m.hdr, (const int*)m.cell_base,
@@ -5154,6 +5155,78 @@ int arah_surface_metrics(const float* tris_a, int32_t n_faces_a, const int32_t* 
     double* part = reinterpret_cast<double*>(scratch);
     hipLaunchKernelGGL(k_md_metrics_part, dim3(ba + bb), dim3(kMdThreads), 0, s, sa, sb, part);
     hipLaunchKernelGGL(k_md_metrics_finish, dim3(1), dim3(kMdThreads), 0, s, (const double*)part, ba, bb, (int)n_a, (int)n_b, out);
+    return check_launch();
+}
+
+// ---- exact nearest point of large clouds and the per-side scores (pointdist.hpp) ------------------------------
+size_t arah_point_index_bytes(int32_t n_points) {
+    if (n_points < 1) return 0;
+    return carve_point_index(nullptr, n_points).bytes;
+}
+
+int arah_point_index_build(const float* points, int32_t n_points, void* index, size_t index_bytes, void* stream) {
+    if (!points || !index || n_points < 1 || n_points > (1 << 27) || (reinterpret_cast<uintptr_t>(index) & 255) != 0) return ARAH_E_BADARG;
+    const PdIndex m = carve_point_index(index, n_points);
+    if (index_bytes < m.bytes) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (hipMemsetAsync(m.coarse, 0, sizeof(int) * (size_t)kPdCoarseCap, s) != hipSuccess) return ARAH_E_LAUNCH;
+    if (hipMemsetAsync(m.cell_count, 0, sizeof(int) * (size_t)m.cap_cells, s) != hipSuccess) return ARAH_E_LAUNCH;
+    const int pg = (n_points + kPdThreads - 1) / kPdThreads, cg = (m.cap_cells + kMdThreads - 1) / kMdThreads;
+    hipLaunchKernelGGL(k_pd_stats, dim3(kPdStatBlocks), dim3(kPdThreads), 0, s, points, (int)n_points, m.stat);
+    hipLaunchKernelGGL(k_pd_coarse, dim3(1), dim3(kPdStatBlocks), 0, s, (const double*)m.stat, (int)n_points, m.hdr);
+    hipLaunchKernelGGL(k_pd_mark, dim3(pg), dim3(kPdThreads), 0, s, points, (int)n_points, (const PdHeader*)m.hdr, m.coarse);
+    hipLaunchKernelGGL(k_pd_header, dim3(1), dim3(1024), 0, s, (const int*)m.coarse, m.cap_cells, m.hdr);
+    hipLaunchKernelGGL(k_pd_bin<false>, dim3(pg), dim3(kPdThreads), 0, s, points, (int)n_points, (const PdHeader*)m.hdr, m.cell_count,
+                       (const int*)m.cell_base, m.recs);
+    hipLaunchKernelGGL(k_md_scan<PdHeader>, dim3(1), dim3(1024), 0, s, (const int*)m.cell_count, m.hdr, m.cell_base);
+    hipLaunchKernelGGL(k_pd_bin<true>, dim3(pg), dim3(kPdThreads), 0, s, points, (int)n_points, (const PdHeader*)m.hdr, m.cell_count,
+                       (const int*)m.cell_base, m.recs);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_md_dt<0, PdHeader>), dim3(cg), dim3(kMdThreads), 0, s, (const PdHeader*)m.hdr,
+                       (const int*)m.cell_base, (const uint8_t*)nullptr, m.dt[0]);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_md_dt<1, PdHeader>), dim3(cg), dim3(kMdThreads), 0, s, (const PdHeader*)m.hdr,
+                       (const int*)m.cell_base, (const uint8_t*)m.dt[0], m.dt[1]);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_md_dt<2, PdHeader>), dim3(cg), dim3(kMdThreads), 0, s, (const PdHeader*)m.hdr,
+                       (const int*)m.cell_base, (const uint8_t*)m.dt[1], m.dt[0]);
+    return check_launch();
+}
+
+int arah_point_nearest(const void* index, size_t index_bytes, const float* cloud, int32_t n_cloud, const float* queries,
+                       int32_t n_queries, double* d2, int32_t* nearest, int32_t* tested, void* stream) {
+    if (!index || !cloud || n_cloud < 1 || n_cloud > (1 << 27) || n_queries < 0) return ARAH_E_BADARG;
+    const PdIndex m = carve_point_index(const_cast<void*>(index), n_cloud);
+    if (index_bytes < m.bytes) return ARAH_E_WORKSPACE;
+    if (n_queries == 0) return ARAH_OK;
+    if (!queries || !d2 || !nearest) return ARAH_E_BADARG;
+    const int g = (n_queries + kPdQueryThreads - 1) / kPdQueryThreads;
+    hipLaunchKernelGGL(k_pd_nearest, dim3(g), dim3(kPdQueryThreads), 0, reinterpret_cast<hipStream_t>(stream), (const PdHeader*)m.hdr,
+                       (const int*)m.cell_base, (const uint8_t*)m.dt[0], (const PdRecord*)m.recs, queries, (int)n_queries, d2,
+                       (int*)nearest, (int*)tested);
+    return check_launch();
+}
+
+size_t arah_sample_scores_bytes(int32_t n) {
+    if (n < 1) return 0;
+    const size_t blocks = (size_t)(n + kPdThreads - 1) / kPdThreads;
+    return (blocks * (4 * sizeof(double) + kPdMaxThresholds * sizeof(int)) + 255) & ~(size_t)255;
+}
+
+int arah_sample_scores(const double* d2, int32_t n, const double* sample_normals, const double* other_normals, int32_t n_other,
+                       const int32_t* idx, const double* thr2, int32_t n_thresholds, double* sums, int64_t* within, void* scratch,
+                       size_t scratch_bytes, void* stream) {
+    if (!d2 || !sums || !scratch || n < 1 || n_thresholds < 0 || n_thresholds > kPdMaxThresholds) return ARAH_E_BADARG;
+    if (n_thresholds > 0 && (!thr2 || !within)) return ARAH_E_BADARG;
+    const bool normals = sample_normals && other_normals;
+    if (normals && (!idx || n_other < 1)) return ARAH_E_BADARG;
+    if (scratch_bytes < arah_sample_scores_bytes(n)) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int blocks = (n + kPdThreads - 1) / kPdThreads;
+    double* part = reinterpret_cast<double*>(scratch);
+    int* cnt = reinterpret_cast<int*>(part + (size_t)blocks * 4);
+    const PdSide side = {d2, normals ? sample_normals : nullptr, normals ? other_normals : nullptr, (const int*)idx, thr2, (int)n,
+                         (int)n_other, (int)n_thresholds};
+    hipLaunchKernelGGL(k_pd_scores_part, dim3(blocks), dim3(kPdThreads), 0, s, side, part, cnt);
+    hipLaunchKernelGGL(k_pd_scores_finish, dim3(1), dim3(kPdThreads), 0, s, (const double*)part, (const int*)cnt, blocks, (int)n,
+                       normals ? 1 : 0, (int)n_thresholds, sums, reinterpret_cast<long long*>(within));
     return check_launch();
 }
 

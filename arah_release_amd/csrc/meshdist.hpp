@@ -230,8 +230,10 @@ __global__ __launch_bounds__(kMdThreads) void k_md_bin(const float* __restrict__
 
 // base[i] = sum of count[0 .. i) for i <= n_cells (n_cells read from the header), header.n_refs = the total.  One workgroup
 // walks the cells in chunks of 4096 -- four consecutive cells per thread, so a wave reads 1 KB in one piece -- with the
-// in-row prefix of k_mcubes (wave shuffles, then the waves' sums through LDS) and a running carry.
-__global__ __launch_bounds__(1024) void k_md_scan(const int* __restrict__ count, MdHeader* __restrict__ hdr, int* __restrict__ base) {
+// in-row prefix of k_mcubes (wave shuffles, then the waves' sums through LDS) and a running carry.  Header: MdHeader, or the
+// point index's PdHeader (pointdist.hpp) -- anything with n_cells and n_refs.
+template <class Header>
+__global__ __launch_bounds__(1024) void k_md_scan(const int* __restrict__ count, Header* __restrict__ hdr, int* __restrict__ base) {
     __shared__ int wsum[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = hdr->n_cells;
@@ -274,8 +276,9 @@ __global__ __launch_bounds__(1024) void k_md_scan(const int* __restrict__ count,
 
 // One axis of the Chebyshev distance transform: out(c) = min over c' on c's line along AXIS of max(in(c'), |c - c'|), where
 // in = 0 / 255 from the occupancy for AXIS 0.  The walk outwards ends as soon as the offset reaches the best value so far.
-template <int AXIS>
-__global__ __launch_bounds__(kMdThreads) void k_md_dt(const MdHeader* __restrict__ hdr, const int* __restrict__ cell_base,
+// Header: MdHeader or PdHeader (n[3], n_cells).
+template <int AXIS, class Header = MdHeader>
+__global__ __launch_bounds__(kMdThreads) void k_md_dt(const Header* __restrict__ hdr, const int* __restrict__ cell_base,
                                                       const uint8_t* __restrict__ in, uint8_t* __restrict__ out) {
     const int cell = blockIdx.x * kMdThreads + threadIdx.x;
     const int nx = hdr->n[0], ny = hdr->n[1], n_cells = hdr->n_cells;

@@ -6,7 +6,9 @@ The reference publishes such numbers but its tree holds no code for them (its RE
 tracker): PARITY UNPINNED, the definitions are this project's.  Also here: `load_mesh` for the two formats ground-truth meshes
 come in (.npz with `vertices` / `faces`, PLY with triangle faces), and `save_mesh`, which writes an indexed mesh in either;
 `mesh_components` / `clean_mesh`: the connected components of an indexed mesh and the removal of its floaters (DESIGN.md "Mesh
-components on the device")."""
+components on the device").  Ground truth that is a SCAN -- a point cloud, with or without normals -- is scored through the exact
+nearest-point query hip.point_index / hip.point_nearest (DESIGN.md "Scoring against point clouds"): `PointCloud`, `nearest_points`,
+`load_points` / `save_points` / `load_geometry`, and F-scores at distance thresholds (`thresholds=` of `mesh_metrics`)."""
 import numpy as np
 import torch
 
@@ -59,25 +61,165 @@ def drop_degenerate(tris):
     return soup, n_kept, torch.where((idx < n_kept)[:, None], corners, torch.zeros_like(corners))
 
 
-def mesh_metrics(tris_a, tris_b, n_samples=100000, seed=0, return_samples=False):
-    """Scores of mesh A (the prediction) against mesh B (the ground truth), both in world metres, each an (F,3,3) triangle
-    soup or a (verts, faces) pair on one GPU.  n_samples points per mesh are drawn area-weighted (data.sample_surface on
-    hip.face_area_cumsum's cumulative areas) from a torch.Generator seeded with `seed`: A's first, then B's.  -> dict of 0-dimensional float64 DEVICE tensors
+class PointCloud:
+    """A point cloud: points (P,3) float32 and optional unit normals (P,3) float32, tensors on one device.  ValueError for other
+    shapes, an empty cloud, or normals of another length or on another device."""
 
-        accuracy / completeness   mean distance of A's samples to B's surface / of B's samples to A's
+    def __init__(self, points, normals=None):
+        points = torch.as_tensor(points)
+        if points.dim() != 2 or points.shape[1] != 3 or not points.dtype.is_floating_point:
+            raise ValueError("a point cloud is a (P, 3) floating-point tensor, got shape %s" % (tuple(points.shape),))
+        if points.shape[0] < 1:
+            raise ValueError("the point cloud is empty")
+        self.points = points.detach().to(torch.float32).contiguous()
+        self.normals = None
+        if normals is not None:
+            normals = torch.as_tensor(normals)
+            if tuple(normals.shape) != tuple(points.shape) or not normals.dtype.is_floating_point:
+                raise ValueError("normals must be (P, 3) = %s, got %s" % (tuple(points.shape), tuple(normals.shape)))
+            if normals.device != points.device:
+                raise ValueError("points live on %s, normals on %s" % (points.device, normals.device))
+            self.normals = normals.detach().to(torch.float32).contiguous()
+
+    @property
+    def device(self):
+        return self.points.device
+
+    def tensors(self):
+        return (self.points,) if self.normals is None else (self.points, self.normals)
+
+    def to(self, device):
+        return PointCloud(self.points.to(device), None if self.normals is None else self.normals.to(device))
+
+    def __len__(self):
+        return int(self.points.shape[0])
+
+
+def _is_cloud(x):
+    """A PointCloud, or a bare (P,3) tensor / array (a triangle soup is (F,3,3), a mesh pair a tuple)."""
+    if isinstance(x, PointCloud):
+        return True
+    if isinstance(x, (tuple, list)):
+        return False
+    return (torch.is_tensor(x) or isinstance(x, np.ndarray)) and x.ndim == 2 and x.shape[-1] == 3
+
+
+def _as_cloud(x):
+    return x if isinstance(x, PointCloud) else PointCloud(x)
+
+
+def nearest_points(cloud_points, pts):
+    """Nearest point of a cloud for every query: cloud_points (P,3) (or a PointCloud), pts (Q,3), both float32 on one device ->
+    (d2 (Q,) float64 = dx dx + dy dy + dz dz of the float64 differences of the float32 coordinates, index (Q,) int64, the
+    LOWEST index on ties).  On the GPU: hip.point_index / hip.point_nearest.  On the host: the float64 brute force below, which
+    is the specification.  A cloud point with a non-finite coordinate is nobody's neighbour; a query with one answers
+    (NaN, -1); a cloud without a finite point (+inf, -1)."""
+    cloud = _as_cloud(cloud_points).points
+    pts = torch.as_tensor(pts)
+    if pts.dim() != 2 or pts.shape[1] != 3 or not pts.dtype.is_floating_point:
+        raise ValueError("pts must be (Q, 3) floating point, got %s" % (tuple(pts.shape),))
+    pts = pts.detach().to(torch.float32).contiguous()
+    if pts.device != cloud.device:
+        raise ValueError("the cloud lives on %s, pts on %s" % (cloud.device, pts.device))
+    if cloud.is_cuda:
+        from . import hip
+        d2, idx, _ = hip.point_nearest(hip.point_index(cloud), pts)
+        return d2, idx.long()
+    c, q = cloud.double(), pts.double()
+    usable = torch.isfinite(c).all(1)
+    d2 = torch.empty(q.shape[0], dtype=torch.float64)
+    idx = torch.empty(q.shape[0], dtype=torch.int64)
+    order = torch.arange(c.shape[0])
+    for s0 in range(0, q.shape[0], 1024):                         # chunks of queries: the (Q, P) matrix never exists whole
+        d = q[s0:s0 + 1024, None, :] - c[None, :, :]
+        m = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+        m = torch.where(usable[None, :], m, torch.full_like(m, float("inf")))
+        best = m.min(1).values
+        first = torch.where(m == best[:, None], order[None, :], c.shape[0]).min(1).values   # the lowest index at the minimum
+        d2[s0:s0 + 1024], idx[s0:s0 + 1024] = best, first
+    none = ~usable.any()
+    idx = torch.where(none | (idx >= c.shape[0]), torch.full_like(idx, -1), idx)
+    bad = ~torch.isfinite(q).all(1)
+    d2 = torch.where(bad, torch.full_like(d2, float("nan")), d2)
+    idx = torch.where(bad, torch.full_like(idx, -1), idx)
+    return d2, idx
+
+
+def check_thresholds(thresholds):
+    """None, or a sequence of 1 .. 16 positive finite distances in metres -> tuple of floats.  ValueError otherwise."""
+    import math
+    if thresholds is None:
+        return None
+    if isinstance(thresholds, (str, bytes)) or not isinstance(thresholds, (tuple, list, np.ndarray)) or np.ndim(thresholds) != 1:
+        raise ValueError("thresholds must be a sequence of distances, got %r" % (thresholds,))
+    out = []
+    for t in thresholds:
+        if isinstance(t, (bool, str)) or not isinstance(t, (int, float, np.integer, np.floating)):
+            raise ValueError("thresholds must be numbers, got %r" % (t,))
+        t = float(t)
+        if not math.isfinite(t) or t <= 0.0:
+            raise ValueError("thresholds must be positive and finite, got %r" % (t,))
+        out.append(t)
+    if not 1 <= len(out) <= 16:
+        raise ValueError("between 1 and 16 thresholds are taken, got %d" % len(out))
+    return tuple(out)
+
+
+def within_thresholds(d2, thresholds):
+    """The threshold rule on the host, the specification of the device count: for every distance t of `thresholds` the number of
+    entries of d2 (float64 squared distances) with d2 <= t t, the product taken in float64 -- an entry exactly at t t is within,
+    a NaN is not.  -> (T,) int64 tensor."""
+    d2 = torch.as_tensor(d2, dtype=torch.float64)
+    return torch.stack([(d2 <= t * t).sum() for t in check_thresholds(thresholds)]).long()
+
+
+def fscore(precision, recall):
+    """2 P R / (P + R), and 0 where P + R = 0 (elementwise, float64)."""
+    total = precision + recall
+    return torch.where(total > 0, 2.0 * precision * recall / torch.where(total > 0, total, torch.ones_like(total)),
+                       torch.zeros_like(total))
+
+
+def _face_normals(soup):
+    """Unit normals (F,3) float64 of a soup: the float64 cross product on the float32 vertices, normalised (NaN for a face without
+    one)."""
+    t = soup.double()
+    n = torch.linalg.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0])
+    return n / torch.sqrt((n * n).sum(-1))[:, None]
+
+
+def mesh_metrics(tris_a, tris_b, n_samples=100000, seed=0, return_samples=False, thresholds=None):
+    """Scores of A (the prediction) against B (the ground truth), both in world metres on one GPU.  Each is a MESH -- an (F,3,3)
+    triangle soup or a (verts, faces) pair -- or a CLOUD -- a PointCloud or a bare (P,3) tensor.  From a mesh n_samples points
+    are drawn area-weighted (data.sample_surface on hip.face_area_cumsum's cumulative areas) from a torch.Generator seeded with
+    `seed`: A's first, then B's.  A cloud contributes all its points as its samples and draws nothing.  A sample's distance to a
+    mesh is the exact point-to-surface distance (hip.mesh_closest), to a cloud the distance to its nearest point
+    (hip.point_nearest).  -> dict of 0-dimensional float64 DEVICE tensors
+
+        accuracy / completeness   mean distance of A's samples to B / of B's samples to A
         chamfer_l1, chamfer_l2    half the sum of the two mean distances / of the two mean squared distances
-        normal_consistency        half the sum of the two means of |n_sample . n_closest face|
+        normal_consistency        half the sum of the two means of |n_sample . n_nearest|: the sample's normal is its face's (mesh)
+                                  or its own (cloud), the other the closest face's or the nearest point's.  NaN when a cloud
+                                  without normals is involved.
         hausdorff_ab / _ba        the largest of those distances, each way
 
-    plus n_a, n_b (the sample counts, Python ints).  Nothing is copied to the host and the stream is never waited for; the
-    same meshes and seed give the same bits.  A mesh all of whose faces are degenerate, or a (verts, faces) pair with a face index
-    out of range, scores NaN (checked on the device: `load_mesh` raises for such a file).  return_samples=True adds
-    "samples": the points and their faces (indices into the soups "tris_a" / "tris_b" given beside them, degenerate faces
-    dropped), for tests."""
+    plus n_a, n_b (the sample counts, Python ints).  thresholds = (t1, ...), up to 16 positive finite distances in metres, adds
+    (T,) float64 device tensors "precision" (the share of A's samples with d2 <= t t, the product in float64, from an exact
+    integer count), "recall" (the same for B's samples), "fscore" = 2 P R / (P + R) (0 when P + R = 0), and "thresholds" (the
+    tuple of floats); the seven scores above keep their bits.  Nothing is copied to the host and the stream is never waited
+    for; the same inputs and seed give the same bits.  A mesh all of whose faces are degenerate, a (verts, faces) pair with a face
+    index out of range, or a cloud holding a non-finite point scores NaN (checked on the device: `load_mesh` / `load_points` raise
+    for such a file).  return_samples=True adds "samples": the points and their faces (indices into the soups "tris_a" /
+    "tris_b" given beside them, degenerate faces dropped; for a cloud side the points are the cloud's, faces and soup None), for
+    tests."""
     from . import data, hip
     if int(n_samples) != n_samples or n_samples < 1:
         raise ValueError("n_samples must be a positive integer, got %r" % (n_samples,))
     n = int(n_samples)
+    thresholds = check_thresholds(thresholds)
+    cloud_a, cloud_b = _is_cloud(tris_a), _is_cloud(tris_b)
+    if cloud_a or cloud_b:
+        return _mixed_metrics(tris_a, tris_b, cloud_a, cloud_b, n, seed, return_samples, thresholds)
     (a, valid_a), (b, valid_b) = _as_soup(tris_a, "tris_a"), _as_soup(tris_b, "tris_b")
     if not a.is_cuda or not b.is_cuda or a.device != b.device:
         raise ValueError("mesh_metrics runs on the HIP kernels: both meshes must live on one GPU")
@@ -101,10 +243,92 @@ def mesh_metrics(tris_a, tris_b, n_samples=100000, seed=0, return_samples=False)
         nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
         ok = (ka > 0) & (kb > 0) & valid_a & valid_b
         res = {k: torch.where(ok, out[i], nan) for i, k in enumerate(METRIC_KEYS)}
+        if thresholds is not None:
+            thr2 = _thr2(thresholds, dev)
+            _, within_a = hip.sample_scores(d2_ab, thr2=thr2)
+            _, within_b = hip.sample_scores(d2_ba, thr2=thr2)
+            _add_fscores(res, thresholds, within_a, n, within_b, n, ok)
     res["n_a"], res["n_b"] = n, n
     if return_samples:
         res["samples"] = {"tris_a": sa, "n_faces_a": ka, "points_a": pa, "face_a": fa, "d2_ab": d2_ab, "closest_face_ab": g_ab,
                           "tris_b": sb, "n_faces_b": kb, "points_b": pb, "face_b": fb, "d2_ba": d2_ba, "closest_face_ba": g_ba}
+    return res
+
+
+def _thr2(thresholds, dev):
+    """(T,) float64 device tensor of t t, the product in float64 on the host, written by fill kernels (a copy from the host would
+    wait for the stream)."""
+    return torch.cat([torch.full((1,), t * t, dtype=torch.float64, device=dev) for t in thresholds])
+
+
+def _add_fscores(res, thresholds, within_a, n_a, within_b, n_b, ok):
+    nan = torch.full_like(within_a, float("nan"), dtype=torch.float64)
+    # a tensor divisor: count / n correctly rounded (a Python scalar would be turned into a multiplication by 1 / n)
+    p = within_a.double() / torch.full_like(nan, float(n_a))
+    r = within_b.double() / torch.full_like(nan, float(n_b))
+    res["precision"], res["recall"], res["fscore"] = torch.where(ok, p, nan), torch.where(ok, r, nan), torch.where(ok, fscore(p, r), nan)
+    res["thresholds"] = thresholds
+
+
+def _mixed_metrics(in_a, in_b, cloud_a, cloud_b, n, seed, return_samples, thresholds):
+    """mesh_metrics with a cloud on at least one side: hip.sample_scores per direction, the means on the device."""
+    from . import data, hip
+    sides, dev = [], None
+    for x, is_cloud, what in ((in_a, cloud_a, "tris_a"), (in_b, cloud_b, "tris_b")):
+        if is_cloud:
+            cloud = _as_cloud(x)
+            t = cloud.points
+            sides.append({"cloud": cloud})
+        else:
+            t, valid = _as_soup(x, what)
+            sides.append({"soup": t, "valid": valid})
+        if not t.is_cuda or (dev is not None and t.device != dev):
+            raise ValueError("mesh_metrics runs on the HIP kernels: both sides must live on one GPU")
+        dev = t.device
+    gen = torch.Generator(device=dev).manual_seed(int(seed))
+    with torch.no_grad():
+        for s in sides:                                            # A's samples first, then B's; a cloud draws nothing
+            if "cloud" in s:
+                c = s["cloud"]
+                s.update(pts=c.points, normals=None if c.normals is None else c.normals.double(), index=hip.point_index(c.points),
+                         tris=None, n_kept=None, face=None)
+                s["sample_normals"], s["ok"], s["n"] = s["normals"], s["index"].n_bad == 0, len(c)
+            else:
+                soup, n_kept, sample_faces = drop_degenerate(s["soup"])
+                corners = soup.reshape(-1, 3)
+                cum = torch.cummax(hip.face_area_cumsum(corners[sample_faces]), 0).values
+                pts, fi = data.sample_surface(corners, sample_faces, n, generator=gen, cum=cum)
+                normals = _face_normals(soup)
+                s.update(pts=pts.contiguous(), normals=normals, index=hip.mesh_index(soup), tris=soup, n_kept=n_kept,
+                         face=fi.to(torch.int32), sample_normals=normals[fi.long()], ok=(n_kept > 0) & s["valid"], n=n)
+        thr2 = _thr2(thresholds, dev) if thresholds is not None else None
+        sums, within, queried = [], [], []
+        for x, y in ((sides[0], sides[1]), (sides[1], sides[0])):
+            if "cloud" in y:
+                d2, g, _ = hip.point_nearest(y["index"], x["pts"])
+            else:
+                d2, g, _, _ = hip.mesh_closest(y["index"], x["pts"], want_closest=False)
+            if x["sample_normals"] is not None and y["normals"] is not None:
+                su, wi = hip.sample_scores(d2, x["sample_normals"], y["normals"], g, thr2=thr2)
+            else:
+                su, wi = hip.sample_scores(d2, thr2=thr2)
+            sums.append(su), within.append(wi), queried.append((d2, g))
+        (sa, sb), (xa, xb) = sums, sides
+        acc, comp = sa[0] / sa[4], sb[0] / sb[4]
+        out = {"accuracy": acc, "completeness": comp, "chamfer_l1": 0.5 * (acc + comp),
+               "chamfer_l2": 0.5 * (sa[1] / sa[4] + sb[1] / sb[4]), "normal_consistency": 0.5 * (sa[2] / sa[5] + sb[2] / sb[5]),
+               "hausdorff_ab": sa[3], "hausdorff_ba": sb[3]}
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+        ok = xa["ok"] & xb["ok"]
+        res = {k: torch.where(ok, out[k], nan) for k in METRIC_KEYS}
+        if thresholds is not None:
+            _add_fscores(res, thresholds, within[0], xa["n"], within[1], xb["n"], ok)
+    res["n_a"], res["n_b"] = xa["n"], xb["n"]
+    if return_samples:
+        res["samples"] = {"tris_a": xa["tris"], "n_faces_a": xa["n_kept"], "points_a": xa["pts"], "face_a": xa["face"],
+                          "d2_ab": queried[0][0], "closest_face_ab": queried[0][1],
+                          "tris_b": xb["tris"], "n_faces_b": xb["n_kept"], "points_b": xb["pts"], "face_b": xb["face"],
+                          "d2_ba": queried[1][0], "closest_face_ba": queried[1][1]}
     return res
 
 
@@ -256,6 +480,15 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
 
 
 def _load_ply(path):
+    verts, faces, _ = _read_ply(path)
+    if verts is None or faces is None:
+        raise ValueError("%s: a mesh needs a vertex and a face element" % path)
+    return verts, faces
+
+
+def _read_ply(path):
+    """-> (vertices (V,3) float64 or None, faces (F,3) int64 or None: no face element, normals (V,3) float64 or None: the vertex
+    element has no nx, ny, nz)."""
     with open(path, "rb") as f:
         raw = f.read()
     end = raw.find(b"end_header")
@@ -288,7 +521,7 @@ def _load_ply(path):
             for t in p[1:-1]:
                 if t not in _PLY_TYPES:
                     raise ValueError("%s: unknown PLY type %r" % (path, t))
-    verts = faces = None
+    verts = faces = normals = None
     tokens, pos = (body.split(), 0) if fmt == "ascii" else (None, 0)
     for e in elements:
         scalar_only = all(p[0] == "scalar" for p in e["props"])
@@ -297,6 +530,7 @@ def _load_ply(path):
             if not scalar_only or not all(k in names for k in "xyz"):
                 raise ValueError("%s: the vertex element needs scalar properties x, y, z" % path)
             cols = [names.index(k) for k in "xyz"]
+            ncols = [names.index(k) for k in ("nx", "ny", "nz")] if all(k in names for k in ("nx", "ny", "nz")) else None
             if fmt == "ascii":
                 k = len(names)
                 block = np.array(tokens[pos:pos + k * e["count"]], dtype=np.float64)
@@ -304,6 +538,7 @@ def _load_ply(path):
                     raise ValueError("%s: the file ends inside the vertex element" % path)
                 pos += k * e["count"]
                 verts = block.reshape(e["count"], k)[:, cols]
+                normals = block.reshape(e["count"], k)[:, ncols] if ncols else None
             else:
                 dt = np.dtype([(p[2], "<" + _PLY_TYPES[p[1]]) for p in e["props"]])
                 if pos + dt.itemsize * e["count"] > len(body):
@@ -311,6 +546,7 @@ def _load_ply(path):
                 block = np.frombuffer(body, dt, e["count"], pos)
                 pos += dt.itemsize * e["count"]
                 verts = np.stack([block[k].astype(np.float64) for k in "xyz"], 1)
+                normals = np.stack([block[k].astype(np.float64) for k in ("nx", "ny", "nz")], 1).reshape(-1, 3) if ncols else None
         elif e["name"] == "face":
             lists = [p for p in e["props"] if p[0] == "list"]
             if len(lists) != 1 or lists[0][3] not in ("vertex_indices", "vertex_index"):
@@ -370,9 +606,7 @@ def _load_ply(path):
                 pos += len(e["props"]) * e["count"]
             else:
                 pos += sum(np.dtype(_PLY_TYPES[p[1]]).itemsize for p in e["props"]) * e["count"]
-    if verts is None or faces is None:
-        raise ValueError("%s: a mesh needs a vertex and a face element" % path)
-    return verts, faces
+    return verts, faces, normals
 
 
 def load_mesh(path, device=None):
@@ -403,6 +637,112 @@ def load_mesh(path, device=None):
     v = torch.from_numpy(np.ascontiguousarray(verts, np.float32))
     f = torch.from_numpy(np.ascontiguousarray(faces, np.int64))
     return (v.to(device), f.to(device)) if device is not None else (v, f)
+
+
+def _read_geometry(path):
+    """-> (vertices, faces or None, normals or None) as numpy arrays, whatever the file holds; ValueError for another format."""
+    low = path.lower()
+    if low.endswith(".npz"):
+        with np.load(path) as z:
+            if "faces" in z.files:
+                if "vertices" not in z.files:
+                    raise ValueError("%s has no key 'vertices' (keys: %s)" % (path, ", ".join(z.files)))
+                return z["vertices"], z["faces"], z["normals"] if "normals" in z.files else None
+            for key in ("points", "vertices"):
+                if key in z.files:
+                    return z[key], None, z["normals"] if "normals" in z.files else None
+            raise ValueError("%s has neither 'points' nor 'vertices' (keys: %s)" % (path, ", ".join(z.files)))
+    if low.endswith(".ply"):
+        verts, faces, normals = _read_ply(path)
+        if verts is None:
+            raise ValueError("%s: no vertex element" % path)
+        return verts, faces, normals
+    raise ValueError("%s: only .npz and .ply files are read" % path)
+
+
+def _cloud_from(path, points, normals, device):
+    points = np.asarray(points)
+    if points.ndim != 2 or points.shape[1] != 3 or points.shape[0] < 1 or not np.issubdtype(points.dtype, np.number):
+        raise ValueError("%s: points must be (P, 3) with P >= 1, got %s" % (path, points.shape))
+    points = np.ascontiguousarray(points, np.float32)
+    if not np.isfinite(points).all():
+        raise ValueError("%s: a point has a non-finite coordinate" % path)
+    if normals is not None:
+        normals = np.asarray(normals)
+        if normals.shape != points.shape:
+            raise ValueError("%s: normals must be (P, 3) = %s, got %s" % (path, points.shape, normals.shape))
+        normals = torch.from_numpy(np.ascontiguousarray(normals, np.float32))
+    cloud = PointCloud(torch.from_numpy(points), normals)
+    return cloud.to(device) if device is not None else cloud
+
+
+def load_points(path, device=None):
+    """A ground-truth scan from `path`: .npz with `points` (or `vertices` and no `faces`) and optionally `normals`, or a PLY
+    (ASCII or binary little-endian) with a vertex element and no faces -- no face element or one of count zero -- and optionally
+    nx, ny, nz -> PointCloud of float32 tensors on `device` (default: the host).  ValueError for anything else: other formats, a
+    file with faces (`load_mesh` / `load_geometry` read those), non-finite coordinates, wrong shapes, normals of another
+    length."""
+    path = str(path)
+    points, faces, normals = _read_geometry(path)
+    if faces is not None and np.asarray(faces).shape[0] > 0:
+        raise ValueError("%s holds a mesh (it has faces): load_mesh or load_geometry reads it" % path)
+    return _cloud_from(path, points, normals, device)
+
+
+def load_geometry(path, device=None):
+    """Whatever ground truth `path` holds: a (verts, faces) pair (`load_mesh`) when the file has faces, a PointCloud
+    (`load_points`) otherwise."""
+    path = str(path)
+    points, faces, normals = _read_geometry(path)
+    if faces is not None and np.asarray(faces).shape[0] > 0:
+        return load_mesh(path, device)
+    return _cloud_from(path, points, normals, device)
+
+
+def save_points(path, points, normals=None):
+    """Write a point cloud: points (P,3) float, optional normals (P,3).  `.npz`: keys `points` and, when given, `normals`
+    (float32).  `.ply`: binary little-endian, one vertex element with float x y z [, float nx ny nz] and no face element.
+    `load_points` reads either back bit-equal.  ValueError for another extension, wrong shapes, or normals of another length."""
+    path = str(path)
+    low = path.lower()
+    if not low.endswith((".npz", ".ply")):
+        raise ValueError("%s: only .npz and .ply clouds are written" % path)
+
+    def host(a):
+        return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+    if isinstance(points, PointCloud):
+        points, normals = points.points, points.normals if normals is None else normals
+    v = host(points)
+    if v.ndim != 2 or v.shape[1] != 3 or v.shape[0] < 1:
+        raise ValueError("points must be (P, 3) with P >= 1, got %s" % (v.shape,))
+    v = np.ascontiguousarray(v, np.float32)
+    extra = {}
+    if normals is not None:
+        a = host(normals)
+        if a.shape != v.shape:
+            raise ValueError("normals must be (P, 3) = %s, got %s" % (v.shape, a.shape))
+        extra["normals"] = np.ascontiguousarray(a, np.float32)
+    if low.endswith(".npz"):
+        with open(path, "wb") as out:
+            np.savez(out, points=v, **extra)
+        return
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    header = ["ply", "format binary_little_endian 1.0", "element vertex %d" % v.shape[0],
+              "property float x", "property float y", "property float z"]
+    if extra:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += ["property float nx", "property float ny", "property float nz"]
+    header.append("end_header")
+    rec = np.empty(v.shape[0], np.dtype(fields))
+    for i, k in enumerate("xyz"):
+        rec[k] = v[:, i]
+    if extra:
+        for i, k in enumerate(("nx", "ny", "nz")):
+            rec[k] = extra["normals"][:, i]
+    with open(path, "wb") as out:
+        out.write(("\n".join(header) + "\n").encode("ascii"))
+        out.write(rec.tobytes())
 
 
 def save_mesh(path, verts, faces, normals=None, colors=None):

@@ -135,7 +135,8 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_query_posed_bytes", "arah_query_posed", "arah_sdf_grid_posed_bytes", "arah_sdf_grid_posed",
            "arah_image_metrics_bytes", "arah_image_metrics",
            "arah_mesh_index_bytes", "arah_mesh_index_build", "arah_mesh_closest", "arah_surface_metrics_bytes", "arah_surface_metrics", "arah_face_area_cumsum",
-           "arah_mesh_components_scratch_bytes", "arah_mesh_components", "arah_mesh_select_scratch_bytes", "arah_mesh_select"]
+           "arah_mesh_components_scratch_bytes", "arah_mesh_components", "arah_mesh_select_scratch_bytes", "arah_mesh_select",
+           "arah_point_index_bytes", "arah_point_index_build", "arah_point_nearest", "arah_sample_scores_bytes", "arah_sample_scores"]
 
 _lib = None
 
@@ -177,6 +178,9 @@ def load_library():
     lib.arah_mesh_index_bytes.argtypes = [C.c_int32]
     lib.arah_surface_metrics_bytes.restype = C.c_size_t
     lib.arah_surface_metrics_bytes.argtypes = [C.c_int32, C.c_int32]
+    for name in ("arah_point_index_bytes", "arah_sample_scores_bytes"):
+        getattr(lib, name).restype = C.c_size_t
+        getattr(lib, name).argtypes = [C.c_int32]
     for name in ("arah_mesh_components_scratch_bytes", "arah_mesh_select_scratch_bytes"):
         getattr(lib, name).restype = C.c_size_t
         getattr(lib, name).argtypes = [C.c_int64, C.c_int64]
@@ -1425,6 +1429,140 @@ def surface_metrics(tris_a, sample_face_a, d2_ab, face_ab, tris_b, sample_face_b
                                         _ptr(args[5]), C.c_int32(n_b), _ptr(out), _ptr(scratch), C.c_size_t(scratch.numel()),
                                         _stream()), "arah_surface_metrics")
     return out
+
+
+def _cloud(points, what="points"):
+    if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise ValueError("%s must be (P, 3) float32" % what)
+    if points.shape[0] < 1:
+        raise ValueError("%s holds no point" % what)
+    return points.contiguous()
+
+
+class PointIndex:
+    """The acceleration structure of `point_index`: the device buffer and the cloud it was built from."""
+    # the layout of csrc/pointdist.hpp: PdHeader (11 doubles, then n[3], n_cells, n_refs, n_bad, cn[3], c_occ, c_occ2) and the
+    # blocks carve_point_index() hands out before cell_base, each rounded up to 256 bytes
+    _HEADER = "11d11i"
+    _N_BAD = 11 * 8 + 5 * 4                 # byte offset of PdHeader.n_bad
+    _HEADER_BYTES, _STAT_BLOCKS, _COARSE = 256, 256, 64       # kPdHeaderBytes, kPdStatBlocks, kPdCoarse
+
+    @classmethod
+    def _cell_base_offset(cls):
+        up = lambda b: (b + 255) // 256 * 256
+        return up(cls._HEADER_BYTES) + up(8 * 8 * cls._STAT_BLOCKS) + up(4 * (cls._COARSE + 1) ** 3)
+
+    def __init__(self, buf, points):
+        self.buf, self.points = buf, points
+
+    @property
+    def device(self):
+        return self.points.device
+
+    @property
+    def n_bad(self):
+        """0-dim int32 DEVICE tensor: the cloud's points with a non-finite coordinate (skipped by the index).  No
+        synchronisation."""
+        return self.buf[self._N_BAD:self._N_BAD + 4].view(torch.int32)[0]
+
+    def header(self):
+        """Host copy of the structure's figures (a synchronisation; for tests and tools): box, cell side h, coarse cell side g,
+        measured dimension, cells per axis n, n_cells, n_refs (finite points), n_bad, the coarse lattice cn and its occupied
+        cells c_occ / occupied 2x2x2 blocks c_occ2."""
+        import struct
+        d = struct.unpack(self._HEADER, bytes(self.buf[:struct.calcsize(self._HEADER)].cpu().numpy()))
+        return {"lo": d[0:3], "hi": d[3:6], "h": d[6], "g": d[8], "dim": d[10], "n": d[11:14], "n_cells": d[14], "n_refs": d[15],
+                "n_bad": d[16], "cn": d[17:20], "c_occ": d[20], "c_occ2": d[21]}
+
+    def cell_counts(self):
+        """Points per cell, (n_cells,) int32 on the device (a synchronisation: the header is read; for tests and tools)."""
+        n_cells = self.header()["n_cells"]
+        off = self._cell_base_offset()
+        base = self.buf[off:off + 4 * (n_cells + 1)].view(torch.int32)
+        return base[1:] - base[:-1]
+
+
+def point_index(points):
+    """Uniform grid over the cloud points (P,3) float32 with a distance transform of its occupied cells
+    (arah_point_index_build, csrc/pointdist.hpp) -> PointIndex for `point_nearest`.  Points with a non-finite coordinate are
+    skipped.  The buffer's size follows from P alone; no host synchronisation."""
+    points = _cloud(points)
+    require_gpu()
+    lib = load_library()
+    dev = _same_device(points)
+    P = int(points.shape[0])
+    with _on_device(dev):
+        buf = torch.empty(int(lib.arah_point_index_bytes(P)), dtype=torch.uint8, device=dev)
+        _check(lib.arah_point_index_build(_ptr(points), C.c_int32(P), _ptr(buf), C.c_size_t(buf.numel()), _stream()),
+               "arah_point_index_build")
+    return PointIndex(buf, points)
+
+
+def point_nearest(index, pts, want_tested=False):
+    """Exact nearest point of the indexed cloud for every query: pts (Q,3) float32 -> d2 (Q,) float64, nearest (Q,) int32 (the
+    lowest index on ties), tested (Q,) int32 (point tests made) or None.  A non-finite query answers (NaN, -1), a cloud without
+    a finite point (+inf, -1)."""
+    if not isinstance(index, PointIndex):
+        raise ValueError("index must come from point_index")
+    if not torch.is_tensor(pts) or pts.dim() != 2 or pts.shape[1] != 3 or pts.dtype != torch.float32:
+        raise ValueError("pts must be (Q, 3) float32")
+    lib = load_library()
+    dev = _same_device(index.buf, index.points, pts)
+    pts = pts.contiguous()
+    Q = int(pts.shape[0])
+    d2 = torch.empty(Q, dtype=torch.float64, device=dev)
+    nearest = torch.empty(Q, dtype=torch.int32, device=dev)
+    tested = torch.empty(Q, dtype=torch.int32, device=dev) if want_tested else None
+    with _on_device(dev):
+        _check(lib.arah_point_nearest(_ptr(index.buf), C.c_size_t(index.buf.numel()), _ptr(index.points),
+                                      C.c_int32(index.points.shape[0]), _ptr(pts), C.c_int32(Q), _ptr(d2), _ptr(nearest),
+                                      _ptr(tested), _stream()), "arah_point_nearest")
+    return d2, nearest, tested
+
+
+MAX_THRESHOLDS = 16
+SAMPLE_SUMS = ("sum_d", "sum_d2", "sum_c", "max_d", "n", "n_c")
+
+
+def sample_scores(d2, sample_normals=None, other_normals=None, idx=None, thr2=None):
+    """One side of the geometry scores (arah_sample_scores): d2 (n,) float64 of its samples; optionally the samples' unit
+    normals (n,3) float64 with the other side's unit normals (m,3) float64 and idx (n,) int32 into them; thr2 (T,) float64
+    DEVICE tensor of squared thresholds, T <= 16, or None -> (sums (6,) float64 in the order of SAMPLE_SUMS, within (T,) int64:
+    the samples with d2 <= thr2[t]), both on the device.  Fixed summation order, no floating-point atomics, no host
+    synchronisation."""
+    if not torch.is_tensor(d2) or d2.dim() != 1 or d2.dtype != torch.float64 or d2.shape[0] < 1:
+        raise ValueError("d2 must be (n,) float64 with n >= 1")
+    n = int(d2.shape[0])
+    normals = sample_normals is not None or other_normals is not None
+    if normals:
+        if sample_normals is None or other_normals is None or idx is None:
+            raise ValueError("sample_normals, other_normals and idx come together")
+        for t, shape in ((sample_normals, (n, 3)), (other_normals, None)):
+            if not torch.is_tensor(t) or t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3 or t.shape[0] < 1 \
+                    or (shape is not None and tuple(t.shape) != shape):
+                raise ValueError("normals must be (n, 3) / (m, 3) float64")
+        if not torch.is_tensor(idx) or idx.dtype != torch.int32 or tuple(idx.shape) != (n,):
+            raise ValueError("idx must be (n,) int32")
+    T = 0
+    if thr2 is not None:
+        if not torch.is_tensor(thr2) or thr2.dtype != torch.float64 or thr2.dim() != 1 or not 1 <= thr2.shape[0] <= MAX_THRESHOLDS:
+            raise ValueError("thr2 must be (T,) float64 with 1 <= T <= %d" % MAX_THRESHOLDS)
+        T = int(thr2.shape[0])
+    lib = load_library()
+    dev = _same_device(d2, sample_normals, other_normals, idx, thr2)
+    d2 = d2.contiguous()
+    if normals:
+        sample_normals, other_normals, idx = sample_normals.contiguous(), other_normals.contiguous(), idx.contiguous()
+    thr2 = thr2.contiguous() if T else None
+    with _on_device(dev):
+        sums = torch.empty(len(SAMPLE_SUMS), dtype=torch.float64, device=dev)
+        within = torch.empty(T, dtype=torch.int64, device=dev)
+        scratch = torch.empty(int(lib.arah_sample_scores_bytes(n)), dtype=torch.uint8, device=dev)
+        _check(lib.arah_sample_scores(_ptr(d2), C.c_int32(n), _ptr(sample_normals), _ptr(other_normals),
+                                      C.c_int32(other_normals.shape[0] if normals else 0), _ptr(idx), _ptr(thr2), C.c_int32(T),
+                                      _ptr(sums), _ptr(within) if T else None, _ptr(scratch), C.c_size_t(scratch.numel()), _stream()),
+               "arah_sample_scores")
+    return sums, within
 
 
 def gram_skinny(a, b):

@@ -1033,11 +1033,12 @@ class MetaAvatarRender(nn.Module):
                 res["color"] = hip.shade_points(frame, ws, verts, T, dirs.contiguous(), self.idhr_network.cano_view_dirs)[0]
         return res
 
-    def geometry_metrics(self, inputs, gt, n_side=256, method="lattice", n_samples=100000, seed=0, clean=None):
-        """Geometry scores of the posed body of frame `inputs` against a ground-truth mesh `gt` in world metres ((F,3,3)
-        triangles or a (verts, faces) pair on the inputs' GPU): `posed_mesh(inputs, n_side, method)` as the prediction, then
+    def geometry_metrics(self, inputs, gt, n_side=256, method="lattice", n_samples=100000, seed=0, clean=None, thresholds=None):
+        """Geometry scores of the posed body of frame `inputs` against a ground truth `gt` in world metres on the inputs' GPU -- a
+        mesh ((F,3,3) triangles or a (verts, faces) pair) or a scan (a geometry.PointCloud or a (P,3) tensor of points):
+        `posed_mesh(inputs, n_side, method)` as the prediction, then
         geometry.mesh_metrics -- accuracy is the mean distance of the posed mesh's samples to the ground truth, completeness
-        the other way round.  -> its dict of 0-dimensional float64 device tensors, plus n_tris of the posed mesh.  clean (None:
+        the other way round; thresholds: its F-score distances.  -> its dict of device tensors, plus n_tris of the posed mesh.  clean (None:
         nothing changes): the `clean` of posed_mesh -- the prediction is the indexed posed mesh without its floaters, one of which
         would otherwise set the Hausdorff distance.  Eval only."""
         from . import geometry
@@ -1053,7 +1054,7 @@ class MetaAvatarRender(nn.Module):
             pred = mesh["tris"]
         if mesh["n_tris"] < 1:
             raise ValueError("geometry_metrics: the posed level set is empty")
-        res = geometry.mesh_metrics(pred, gt, n_samples=n_samples, seed=seed)
+        res = geometry.mesh_metrics(pred, gt, n_samples=n_samples, seed=seed, thresholds=thresholds)
         res["n_tris"] = mesh["n_tris"]
         return res
 
@@ -1143,6 +1144,10 @@ def _walk_tensors(obj):
     elif isinstance(obj, (list, tuple)):
         for v in obj:
             yield from _walk_tensors(v)
+    else:
+        from .geometry import PointCloud
+        if isinstance(obj, PointCloud):
+            yield from _walk_tensors(obj.tensors())
 
 
 _FREE_STREAMS = {}   # streams of map_in_flight calls without an owner, per (device, count)

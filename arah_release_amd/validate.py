@@ -15,11 +15,16 @@ chunk -- and are aggregated by ``validation_epoch_end``.  With N processes frame
 JSON line (means, frame count, seconds per frame) and writes the per-frame values to ``<out_dir>/validation.json``.
 LPIPS needs VGG weights that are not part of this build: ``--lpips MODULE:FUNCTION`` names a callable
 (pred HxWx3, gt HxWx3, box mask) -> float to import; without it no LPIPS is reported.
-``--geometry DIR``: every frame whose ground-truth mesh exists as ``DIR/<name of the frame's model file>.npz`` (keys
-``vertices``, ``faces``) or ``.ply`` is also scored against it in world metres (MetaAvatarRender.geometry_metrics: Chamfer
-distance, accuracy / completeness, normal consistency, Hausdorff distances; DESIGN.md "Geometry metrics on the device").  The
+``--geometry DIR``: every frame whose ground truth exists as ``DIR/<name of the frame's model file>.npz`` or ``.ply`` is also
+scored against it in world metres (MetaAvatarRender.geometry_metrics: Chamfer distance, accuracy / completeness, normal
+consistency, Hausdorff distances; DESIGN.md "Geometry metrics on the device").  A file with faces is a mesh (keys ``vertices``,
+``faces``), one without is a scan (geometry.load_geometry: ``points`` [, ``normals``], or a vertex-only PLY; DESIGN.md "Scoring
+against point clouds") -- a directory may mix the two; a frame scored against a scan without normals has ``normal_consistency``
+null, and the mean of a score runs over the frames that have it (null when none has).  The
 scalars stay on the device until the epoch ends; the JSON line gains their means over the scored frames and ``n_geometry``,
-the number of such frames.  Without the option the output is unchanged."""
+the number of such frames.  ``--geometry-thresholds 0.005,0.01,0.02`` adds ``precision@T``, ``recall@T`` and ``fscore@T`` for
+every distance T in metres (keys formatted with ``repr(float)``), per frame and as means.  Without the options the output is
+unchanged."""
 import argparse
 import importlib
 import json
@@ -50,6 +55,8 @@ def build_parser():
     p.add_argument("--geometry-n-side", type=int, default=256, help="Lattice resolution of the posed mesh that is scored.")
     p.add_argument("--geometry-samples", type=int, default=100000, help="Surface samples per mesh of the geometry scores.")
     p.add_argument("--geometry-seed", type=int, default=0, help="Seed of the geometry scores' surface samples.")
+    p.add_argument("--geometry-thresholds", type=str, default=None, metavar="T1,T2,...",
+                   help="Distances in metres (up to 16): adds precision@T, recall@T and fscore@T to the geometry scores.")
     p.add_argument("--default-config", type=str, default="configs/default.yaml")
     p.add_argument("--body-models", type=str, default="body_models/misc", help="Directory of the SMPL model files.")
     return p
@@ -87,12 +94,17 @@ def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0
     """Frames rank, rank + world, ... of the dataset through validation_step with device metrics; -> (what
     validation_epoch_end returns, frames this rank rendered, seconds it took).  Images are dropped chunk by chunk: only the
     metric scalars of a frame stay.  geometry: None, or {"dir", "n_side", "n_samples", "seed"} -- frames with a ground-truth
-    mesh in dir are scored by model.geometry_metrics in the same in-flight step, the scalars are read when the epoch ends and
-    the result gains their means, "n_geometry" and the per-frame values."""
+    mesh or scan in dir are scored by model.geometry_metrics in the same in-flight step, the scalars are read when the epoch ends
+    and the result gains their means, "n_geometry" and the per-frame values; an optional "thresholds" (tuple of distances) adds
+    precision@T / recall@T / fscore@T.  normal_consistency of a frame scored against a scan without normals is null; a mean runs over
+    the frames that have the score."""
     from . import geometry as geo, renderer
     lm = lm.to(device).eval()
     mine = list(range(rank, len(dataset), world))
     geo_keys = geo.METRIC_KEYS
+    thresholds = geometry.get("thresholds") if geometry is not None else None
+    if thresholds:
+        geo_keys = geo_keys + tuple("%s@%r" % (name, t) for name in ("precision", "recall", "fscore") for t in thresholds)
 
     def step(item):
         gt = item.get("geometry.gt")
@@ -101,8 +113,11 @@ def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0
         item = {k: v for k, v in item.items() if k != "geometry.gt"}
         out = lm.validation_step(item, lpips_fn=lpips_fn, metrics="device", data_range=data_range)
         scores = lm.model.geometry_metrics(lm.compose_inputs(item, eval=True), gt, n_side=geometry["n_side"],
-                                           n_samples=geometry["n_samples"], seed=geometry["seed"])
-        out["geometry"] = torch.stack([scores[k] for k in geo_keys])
+                                           n_samples=geometry["n_samples"], seed=geometry["seed"], thresholds=thresholds or None)
+        out["geometry"] = torch.stack([scores[k] for k in geo.METRIC_KEYS])
+        if thresholds:
+            out["geometry"] = torch.cat([out["geometry"], scores["precision"], scores["recall"], scores["fscore"]])
+        out["geometry_scan"] = isinstance(gt, geo.PointCloud) and gt.normals is None   # a scan without normals
         return out
 
     kept = []
@@ -114,15 +129,23 @@ def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0
             for i, item in zip(mine[c:c + 20], items):
                 path = geometry_file(geometry["dir"], dataset.data[i]["model_file"])
                 if path is not None:
-                    item["geometry.gt"] = geo.load_mesh(path, device)
+                    item["geometry.gt"] = geo.load_geometry(path, device)
         outs = renderer.map_in_flight(step, items, owner=lm.model)
-        kept += [{k: v for k, v in o.items() if k in ("psnr", "ssim", "lpips", "metrics_status", "geometry")} for o in outs]
+        kept += [{k: v for k, v in o.items() if k in ("psnr", "ssim", "lpips", "metrics_status", "geometry", "geometry_scan")}
+                 for o in outs]
     torch.cuda.synchronize(device)
     seconds = time.time() - t0
-    res = lm.validation_epoch_end([{k: v for k, v in o.items() if k != "geometry"} for o in kept], first_index=rank,
+    res = lm.validation_epoch_end([{k: v for k, v in o.items() if k not in ("geometry", "geometry_scan")} for o in kept], first_index=rank,
                                   index_stride=world)
     if geometry is not None:
-        rows = [(rank + k * world, o["geometry"].cpu().tolist()) for k, o in enumerate(kept) if "geometry" in o]
+        nc = geo.METRIC_KEYS.index("normal_consistency")
+
+        def values(o):   # a scan without normals has no normal consistency: null in the strict JSON.  Any other NaN stays NaN.
+            v = o["geometry"].cpu().tolist()
+            if o["geometry_scan"] and v[nc] != v[nc]:
+                v[nc] = None
+            return v
+        rows = [(rank + k * world, values(o)) for k, o in enumerate(kept) if "geometry" in o]
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             gathered = [None] * dist.get_world_size()
@@ -135,7 +158,8 @@ def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0
                     frame.update(zip(geo_keys, scored[frame["frame"]]))
             res["n_geometry"] = len(scored)
             for q, key in enumerate(geo_keys):
-                res[key] = sum(v[q] for v in scored.values()) / len(scored) if scored else None   # null: no frame was scored
+                col = [v[q] for v in scored.values() if v[q] is not None]   # the frames that have the score
+                res[key] = sum(col) / len(col) if col else None   # null: no frame was scored, or none has this score
     return res, len(mine), seconds
 
 
@@ -172,6 +196,11 @@ def main(argv=None, body=None, faces=None, log=print):
             raise FileNotFoundError("--geometry: %s is not a directory" % args.geometry)
         geometry = {"dir": args.geometry, "n_side": args.geometry_n_side, "n_samples": args.geometry_samples,
                     "seed": args.geometry_seed}
+        if args.geometry_thresholds is not None:
+            from . import geometry as geo
+            geometry["thresholds"] = geo.check_thresholds([float(t) for t in args.geometry_thresholds.split(",")])
+    elif args.geometry_thresholds is not None:
+        raise ValueError("--geometry-thresholds needs --geometry DIR")
     res, n_mine, seconds = validate(lm, val_dataset, device, rank, world, lpips_fn, args.data_range, geometry)
     if world > 1:
         dist.barrier()

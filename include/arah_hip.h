@@ -519,6 +519,35 @@ int arah_surface_metrics(const float* tris_a, int32_t n_faces_a, const int32_t* 
                          const int32_t* sample_face_b, const double* d2_ba, const int32_t* face_ba, int32_t n_b, double* out,
                          void* scratch, size_t scratch_bytes, void* stream);
 
+/* Exact nearest point of a large cloud, and the per-side reduction of the geometry scores over meshes and clouds
+ * (csrc/pointdist.hpp; no reference counterpart).  points [n,3] f32; a point with a non-finite coordinate is skipped by the
+ * build and is never anyone's neighbour.
+ *   arah_point_index_build  a uniform grid over the bounding box of the finite points, each point recorded in its one cell,
+ *                           with the distance transform of the occupied cells, into the caller's `index` buffer
+ *                           (arah_point_index_bytes(n) bytes, 256-byte aligned).  The cell size is derived from the measured
+ *                           occupancy of a coarse lattice at two scales (the cloud's box-counting dimension) under a budget
+ *                           of 8 cells per point; the buffer's size is fixed by n alone.  Nothing is truncated.
+ *   arah_point_nearest      queries [Q,3] f32 -> d2 [Q] f64 (dx dx + dy dy + dz dz of the float64 differences), nearest [Q]
+ *                           i32 (index into the cloud), tested [Q] i32 or NULL (point tests the query made): the
+ *                           lexicographic minimum of (d2, index), whatever the order of the build.  A non-finite query gives
+ *                           d2 NaN, nearest -1; a cloud without a finite point gives d2 +inf, nearest -1.  `cloud` / n_cloud:
+ *                           what the index was built from.
+ *   arah_sample_scores      one side of the scores: d2 [n] f64 of its samples; optionally sample_normals [n,3] f64 with
+ *                           other_normals [n_other,3] f64 and idx [n] i32 into them (both NULL: no normal term; an idx outside
+ *                           [0, n_other) gives a NaN term); thr2 [T] DEVICE f64 squared thresholds, T <= 16 -> sums [6] DEVICE
+ *                           doubles: sum d, sum d^2, sum |n . n'|, max d, samples in the distance sums, samples in the normal
+ *                           sum; within [T] DEVICE i64: samples with d2 <= thr2[t], counted in integers.  Sums run in index
+ *                           order (no floating-point atomics).  scratch: arah_sample_scores_bytes(n) bytes, 8-byte aligned.
+ * No host synchronisation anywhere. */
+size_t arah_point_index_bytes(int32_t n_points);
+int arah_point_index_build(const float* points, int32_t n_points, void* index, size_t index_bytes, void* stream);
+int arah_point_nearest(const void* index, size_t index_bytes, const float* cloud, int32_t n_cloud, const float* queries,
+                       int32_t n_queries, double* d2, int32_t* nearest, int32_t* tested, void* stream);
+size_t arah_sample_scores_bytes(int32_t n);
+int arah_sample_scores(const double* d2, int32_t n, const double* sample_normals, const double* other_normals, int32_t n_other,
+                       const int32_t* idx, const double* thr2, int32_t n_thresholds, double* sums, int64_t* within, void* scratch,
+                       size_t scratch_bytes, void* stream);
+
 /* ---- the hot path ----------------------------------------------------------------------- */
 /* rays: cam_loc [n_cams,3], ray r belongs to camera r / rays_per_cam; dirs [N,3]; near_far [N,2].
  * root_find_all: 0 = joint root find on the non-diverged rays (eval), 1 = on every ray (training, RT:249).

@@ -1,0 +1,726 @@
+"""Scoring meshes against point-cloud scans (DESIGN.md "Scoring against point clouds"): geometry.nearest_points and the cloud
+files on the host; on the GPU the exact nearest-point query (hip.point_index / hip.point_nearest) held to a float64 brute force
+in torch, geometry.mesh_metrics with clouds and thresholds held to a numpy restatement and to closed forms,
+MetaAvatarRender.geometry_metrics against a cloud and `validate --geometry` with a scan and `--geometry-thresholds`."""
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from test_geometry_metrics import (F32, KEYS, _write_ply, brute_closest, face_normals_np, flat_patch, icosphere, posed,  # noqa: F401
+                                   sample_np, sphere_bracket)
+
+gpu = pytest.mark.gpu
+DEV = "cuda:0"
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_EXPORTS = ("arah_point_index_bytes", "arah_point_index_build", "arah_point_nearest", "arah_sample_scores_bytes",
+               "arah_sample_scores")
+
+
+# ------------------------------------------------------------------------------------------------------ restatements
+def nearest_np(cloud, pts):
+    """(d2, index) by a loop over the queries in float64 numpy: the first index of the smallest d2; non-finite cloud points are
+    nobody's neighbour."""
+    c, q = np.asarray(cloud, np.float32).astype(np.float64), np.asarray(pts, np.float32).astype(np.float64)
+    usable = np.isfinite(c).all(1)
+    d2, idx = np.empty(len(q)), np.empty(len(q), np.int64)
+    for i in range(len(q)):
+        d = q[i] - c
+        m = np.where(usable, (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2], np.inf)
+        idx[i] = int(np.argmin(m))       # numpy's argmin returns the first occurrence
+        d2[i] = m[idx[i]]
+    return d2, idx
+
+
+def restate_side(d2, n_sample, n_other, thresholds):
+    d = np.sqrt(d2)
+    c = np.abs((n_sample * n_other).sum(-1)).mean() if n_sample is not None and n_other is not None else float("nan")
+    return {"mean": d.mean(), "mean2": d2.mean(), "c": c, "max": d.max(), "within": [int((d2 <= t * t).sum()) for t in thresholds]}
+
+
+def restate_from_sides(ab, ba):
+    out = {"accuracy": ab["mean"], "completeness": ba["mean"], "chamfer_l1": 0.5 * (ab["mean"] + ba["mean"]),
+           "chamfer_l2": 0.5 * (ab["mean2"] + ba["mean2"]), "normal_consistency": 0.5 * (ab["c"] + ba["c"]),
+           "hausdorff_ab": ab["max"], "hausdorff_ba": ba["max"]}
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------- CPU tests
+def test_nearest_points_on_the_host():
+    from arah_release_amd import geometry
+    cloud = torch.tensor([[0, 0, 0], [1, 0, 0], [0, 2, 0], [1, 0, 0], [0, 0, 0]], dtype=torch.float32)
+    pts = torch.tensor([[0.25, 0, 0], [0.75, 0, 0], [0.5, 0, 0], [0, 1.5, 1], [1, 0, 0]], dtype=torch.float32)
+    d2, idx = geometry.nearest_points(cloud, pts)
+    assert d2.dtype == torch.float64 and idx.dtype == torch.int64
+    assert idx.tolist() == [0, 1, 0, 2, 1] and d2.tolist() == [0.0625, 0.0625, 0.25, 1.25, 0.0]
+    gen = torch.Generator().manual_seed(1)
+    cloud = torch.rand(300, 3, generator=gen)
+    cloud[100:140] = cloud[20:60]                        # duplicates: the lowest index wins
+    pts = torch.cat([torch.rand(150, 3, generator=gen) * 2 - 0.5, cloud[100:140:3]])
+    for c in (cloud, geometry.PointCloud(cloud)):
+        d2, idx = geometry.nearest_points(c, pts)
+        want_d2, want_idx = nearest_np(cloud.numpy(), pts.numpy())
+        np.testing.assert_array_equal(idx.numpy(), want_idx)
+        np.testing.assert_array_equal(d2.numpy(), want_d2)
+    assert int(idx[150:].max()) < 60
+    # non-finite points are nobody's neighbour, non-finite queries answer (NaN, -1), a cloud without a finite point (+inf, -1)
+    holes = cloud.clone()
+    holes[::3, 1] = float("nan")
+    holes[1, 0] = float("inf")
+    q = pts.clone()
+    q[4, 2] = float("nan")
+    q[9, 0] = float("-inf")
+    d2, idx = geometry.nearest_points(holes, q)
+    want_d2, want_idx = nearest_np(holes.numpy(), pts.numpy())
+    ok = np.ones(len(q), bool)
+    ok[[4, 9]] = False
+    np.testing.assert_array_equal(idx.numpy()[ok], want_idx[ok])
+    np.testing.assert_array_equal(d2.numpy()[ok], want_d2[ok])
+    assert idx[[4, 9]].tolist() == [-1, -1] and bool(torch.isnan(d2[[4, 9]]).all())
+    assert bool(torch.isfinite(holes[idx[torch.from_numpy(ok)]]).all())
+    d2, idx = geometry.nearest_points(torch.full((7, 3), float("nan")), pts)
+    assert bool((d2 == float("inf")).all()) and bool((idx == -1).all())
+    for bad_cloud, bad_pts in ((torch.zeros(0, 3), pts), (torch.zeros(4, 2), pts), (cloud, torch.zeros(3, 4)), (cloud, torch.zeros(3))):
+        with pytest.raises(ValueError):
+            geometry.nearest_points(bad_cloud, bad_pts)
+
+
+def _write_cloud_ply(path, points, normals, binary, face_element=False):
+    head = ["ply", "format %s 1.0" % ("binary_little_endian" if binary else "ascii"), "comment written by the test",
+            "element vertex %d" % len(points), "property float x", "property float y", "property float z"]
+    rows = np.asarray(points, np.float32)
+    if normals is not None:
+        head += ["property float nx", "property float ny", "property float nz"]
+        rows = np.concatenate([rows, np.asarray(normals, np.float32)], 1)
+    if face_element:
+        head += ["element face 0", "property list uchar int vertex_indices"]
+    head.append("end_header")
+    with open(path, "wb") as f:
+        f.write(("\n".join(head) + "\n").encode("ascii"))
+        if binary:
+            f.write(np.ascontiguousarray(rows, "<f4").tobytes())
+        else:
+            f.write("".join(" ".join(repr(float(x)) for x in r) + "\n" for r in rows).encode("ascii"))
+
+
+def test_cloud_files_round_trips_and_rejections(tmp_path):
+    from arah_release_amd import geometry
+    rng = np.random.RandomState(2)
+    points = rng.randn(57, 3).astype(np.float32)
+    normals = rng.randn(57, 3).astype(np.float32)
+    normals /= np.linalg.norm(normals, axis=1, keepdims=True)
+    for with_normals in (False, True):
+        nrm = normals if with_normals else None
+        cases = []
+        for ext in (".npz", ".ply"):
+            p = tmp_path / ("saved_%d%s" % (with_normals, ext))
+            geometry.save_points(p, torch.from_numpy(points), None if nrm is None else torch.from_numpy(nrm))
+            cases.append(p)
+        for binary in (False, True):
+            for face_element in (False, True):
+                p = tmp_path / ("hand_%d_%d_%d.ply" % (with_normals, binary, face_element))
+                _write_cloud_ply(p, points, nrm, binary, face_element)
+                cases.append(p)
+        p = tmp_path / ("vertices_%d.npz" % with_normals)
+        np.savez(p, vertices=points, **({"normals": nrm} if with_normals else {}))
+        cases.append(p)
+        for p in cases:
+            for cloud in (geometry.load_points(p), geometry.load_geometry(p)):
+                assert isinstance(cloud, geometry.PointCloud), p
+                assert cloud.points.dtype == torch.float32 and cloud.points.device.type == "cpu"
+                np.testing.assert_array_equal(cloud.points.numpy(), points, err_msg=str(p))
+                if with_normals:
+                    np.testing.assert_array_equal(cloud.normals.numpy(), normals, err_msg=str(p))
+                else:
+                    assert cloud.normals is None
+    # a file with faces is a mesh
+    tris = icosphere(1, 0.5)
+    verts, inv = np.unique(tris.reshape(-1, 3), axis=0, return_inverse=True)
+    faces = inv.reshape(-1, 3)
+    np.savez(tmp_path / "mesh.npz", vertices=verts, faces=faces)
+    _write_ply(tmp_path / "mesh.ply", verts, faces, binary=True)
+    for name in ("mesh.npz", "mesh.ply"):
+        got = geometry.load_geometry(tmp_path / name)
+        assert isinstance(got, tuple) and len(got) == 2
+        np.testing.assert_array_equal(got[0].numpy(), verts)
+        np.testing.assert_array_equal(got[1].numpy(), faces)
+        with pytest.raises(ValueError):
+            geometry.load_points(tmp_path / name)
+    # load_mesh keeps its error on a vertex-only PLY
+    with pytest.raises(ValueError, match="a mesh needs a vertex and a face element"):
+        geometry.load_mesh(tmp_path / "saved_0.ply")
+    with pytest.raises(ValueError):
+        geometry.load_mesh(tmp_path / "saved_0.npz")
+    # rejections of load_points
+    bad = points.copy()
+    bad[5, 1] = np.nan
+    np.savez(tmp_path / "nan.npz", points=bad)
+    _write_cloud_ply(tmp_path / "nan.ply", bad, None, True)
+    np.savez(tmp_path / "shape.npz", points=points[:, :2])
+    np.savez(tmp_path / "flat.npz", points=points.reshape(-1))
+    np.savez(tmp_path / "normals.npz", points=points, normals=normals[:-1])
+    np.savez(tmp_path / "nokey.npz", pts=points)
+    (tmp_path / "cloud.obj").write_text("v 0 0 0\n")
+    for name in ("nan.npz", "nan.ply", "shape.npz", "flat.npz", "normals.npz", "nokey.npz", "cloud.obj"):
+        with pytest.raises(ValueError):
+            geometry.load_points(tmp_path / name)
+        with pytest.raises(ValueError):
+            geometry.load_geometry(tmp_path / name)
+    # ... and of save_points / PointCloud
+    for args in ((tmp_path / "x.obj", points), (tmp_path / "x.ply", points[:, :2]), (tmp_path / "x.npz", points, normals[:-1])):
+        with pytest.raises(ValueError):
+            geometry.save_points(*args)
+    for args in ((torch.zeros(0, 3),), (torch.zeros(4, 2),), (torch.zeros(4, 3), torch.zeros(5, 3))):
+        with pytest.raises(ValueError):
+            geometry.PointCloud(*args)
+
+
+def test_threshold_argument_errors():
+    from arah_release_amd import geometry
+    good = torch.from_numpy(icosphere(0))
+    for bad in ((0.0,), (0.01, -0.5), (float("nan"),), (float("inf"),), tuple([0.01] * 17), (), 0.01, "0.01", ("0.01",)):
+        with pytest.raises(ValueError):
+            geometry.mesh_metrics(good, good, n_samples=10, thresholds=bad)
+        with pytest.raises(ValueError):
+            geometry.check_thresholds(bad)
+    assert geometry.check_thresholds([0.005, 1, np.float32(0.5)]) == (0.005, 1.0, 0.5) and geometry.check_thresholds(None) is None
+    assert len(geometry.check_thresholds([0.01] * 16)) == 16
+    with pytest.raises(ValueError):   # host-resident: the scores run on the HIP kernels
+        geometry.mesh_metrics(good, torch.zeros(5, 3), n_samples=10, thresholds=(0.01,))
+    assert geometry.METRIC_KEYS == KEYS
+
+
+def test_hip_entry_points_refuse_bad_arguments():
+    from arah_release_amd import hip
+    pts = torch.zeros(5, 3)
+    for bad in (pts.double(), pts[:, :2], pts[:0], torch.zeros(5, 3, 3), [[0.0, 0.0, 0.0]]):
+        with pytest.raises(ValueError):
+            hip.point_index(bad)
+    for index in (None, pts, hip.MeshIndex(None, None)):
+        with pytest.raises(ValueError):
+            hip.point_nearest(index, pts)
+    index = hip.PointIndex(None, pts)
+    for bad in (pts.double(), pts[:, :2], torch.zeros(5)):
+        with pytest.raises(ValueError):
+            hip.point_nearest(index, bad)
+    d2 = torch.zeros(4, dtype=torch.float64)
+    nrm = torch.zeros(4, 3, dtype=torch.float64)
+    idx = torch.zeros(4, dtype=torch.int32)
+    for args, kwargs in (((d2.float(),), {}), ((d2[:0],), {}), ((d2.reshape(2, 2),), {}), ((d2, nrm), {}), ((d2, nrm, nrm), {}),
+                         ((d2, nrm[:3], nrm, idx), {}), ((d2, nrm.float(), nrm, idx), {}), ((d2, nrm, nrm, idx.long()), {}),
+                         ((d2,), {"thr2": torch.zeros(17, dtype=torch.float64)}), ((d2,), {"thr2": torch.zeros(2)}),
+                         ((d2,), {"thr2": torch.zeros(0, dtype=torch.float64)}), ((d2,), {"thr2": [0.01]})):
+        with pytest.raises(ValueError):
+            hip.sample_scores(*args, **kwargs)
+
+
+def test_header_and_exports_name_the_new_functions():
+    from arah_release_amd import hip
+    header = open(os.path.join(REPO, "include", "arah_hip.h")).read()
+    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    declared = set(re.findall(r"\b(arah_[a-z0-9_]+)\s*\(", header))
+    for name in NEW_EXPORTS:
+        assert name in declared and name in hip.EXPORTS, name
+
+
+def test_point_index_layout_follows_the_kernel_source():
+    """hip.PointIndex reads the header and the cell table out of the index buffer: its offsets are those of csrc/pointdist.hpp."""
+    import struct
+    from arah_release_amd import hip
+    src = open(os.path.join(REPO, "arah_release_amd", "csrc", "pointdist.hpp")).read()
+    const = {k: int(v) for k, v in re.findall(r"constexpr (?:int|size_t) (kPd\w+) = (\d+);", src)}
+    assert (const["kPdHeaderBytes"], const["kPdStatBlocks"], const["kPdCoarse"]) == (hip.PointIndex._HEADER_BYTES,
+                                                                                    hip.PointIndex._STAT_BLOCKS, hip.PointIndex._COARSE)
+    body = re.search(r"struct PdHeader \{(.*?)\};", src, re.S).group(1)
+    fields = re.findall(r"^\s*(double|int) ([^;]+);", body, re.M)
+    names = [(t, n.strip()) for t, decl in fields for n in decl.split(",")]
+    assert names == [("double", "lo[3]"), ("double", "hi[3]"), ("double", "h"), ("double", "inv_h"), ("double", "g"), ("double", "inv_g"),
+                     ("double", "dim"), ("int", "n[3]"), ("int", "n_cells"), ("int", "n_refs"), ("int", "n_bad"), ("int", "cn[3]"),
+                     ("int", "c_occ"), ("int", "c_occ2")]
+    assert struct.calcsize(hip.PointIndex._HEADER) == 11 * 8 + 11 * 4 <= const["kPdHeaderBytes"]
+    assert hip.PointIndex._N_BAD == struct.calcsize("11d5i")
+    carve = re.search(r"inline PdIndex carve_point_index.*?m\.cell_base", src, re.S).group(0)
+    assert re.findall(r"m\.(\w+) = ", carve) == ["cap_cells", "hdr", "stat", "coarse"]       # what lies before cell_base
+    assert hip.PointIndex._cell_base_offset() == 256 + 8 * 8 * 256 + (4 * 65 ** 3 + 255) // 256 * 256
+
+
+def test_threshold_rule_on_given_distances():
+    from arah_release_amd import geometry
+    rng = np.random.RandomState(3)
+    taus = (0.005, 0.01, 0.02, 0.3)
+    d2 = rng.rand(5000) * 1e-3
+    d2[:4] = [t * t for t in taus]                        # exactly at a threshold: within
+    d2[4:8] = [np.nextafter(t * t, 1.0) for t in taus]    # one ulp above: not
+    d2[8] = np.nan
+    want = [int((d2 <= t * t).sum()) for t in taus]
+    assert geometry.within_thresholds(torch.from_numpy(d2), taus).tolist() == want
+    assert geometry.within_thresholds([4e-4], (0.02,)).tolist() == [int(4e-4 <= 0.02 * 0.02)]
+    assert geometry.within_thresholds([0.02 * 0.02, np.nextafter(0.02 * 0.02, 1.0)], (0.02,)).tolist() == [1]
+    p, r = torch.tensor([0.5, 0.0, 1.0], dtype=torch.float64), torch.tensor([0.25, 0.0, 1.0], dtype=torch.float64)
+    assert geometry.fscore(p, r).tolist() == [2 * 0.5 * 0.25 / 0.75, 0.0, 1.0]
+
+
+# ---------------------------------------------------------------------------------------- GPU: the nearest-point query
+def brute_torch(cloud, pts):
+    """Float64 brute force on the device: the full (Q, P) matrix, the lowest index on ties -> (d2, index, relative gap between
+    the two smallest d2 of every query)."""
+    c, q = cloud.double(), pts.double()
+    d = q[:, None, :] - c[None, :, :]
+    m = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    m = torch.where(torch.isfinite(c).all(1)[None, :], m, torch.full_like(m, float("inf")))
+    best = m.min(1).values
+    order = torch.arange(c.shape[0], device=c.device)
+    idx = torch.where(m == best[:, None], order[None, :], c.shape[0]).min(1).values
+    if c.shape[0] > 1:
+        two = torch.topk(m, 2, dim=1, largest=False).values
+        gap = (two[:, 1] - two[:, 0]) / two[:, 1]
+    else:
+        gap = torch.ones_like(best)
+    return best, idx, gap
+
+
+@pytest.fixture(scope="module")
+def inputs():
+    """The issue's inputs 1-4 (one host generator seeded with 0, draws in the order listed) with their brute-force answers."""
+    gen = torch.Generator().manual_seed(0)
+    c1 = torch.rand(4099, 3, generator=gen) * 2 - 1
+    q1 = torch.rand(2053, 3, generator=gen) * 3 - 1.5
+    c2 = torch.cat([torch.randn(4000, 3, generator=gen) * 1e-3 + 0.25, torch.rand(99, 3, generator=gen) * 2 - 1])
+    q2 = torch.cat([q1[:1000], torch.randn(1053, 3, generator=gen) * 2e-3 + 0.25])
+    c3 = c1.clone()
+    c3[:, 2] = 0.5
+    axis = torch.arange(9, dtype=torch.float32) * 0.25 - 1
+    c4 = torch.stack(torch.meshgrid(axis, axis, axis, indexing="ij"), -1).reshape(-1, 3)[torch.randperm(729, generator=gen)]
+    qa = torch.arange(21, dtype=torch.float32) * 0.125 - 1.25
+    q4 = torch.stack(torch.meshgrid(qa, qa, qa, indexing="ij"), -1).reshape(-1, 3)
+    cases = {"uniform": (c1, q1), "clustered, input 1's queries": (c2, q1), "clustered, own queries": (c2, q2), "planar": (c3, q1),
+             "lattice": (c4, q4)}
+    out = {}
+    for name, (c, q) in cases.items():
+        c, q = c.to(DEV).contiguous(), q.to(DEV).contiguous()
+        out[name] = (c, q) + brute_torch(c, q)
+    return out
+
+
+def _check_query(hip, cloud, pts, want, what, exact=False, allow_close=False):
+    want_d2, want_idx, gap = want
+    index = hip.point_index(cloud)
+    d2, idx, tested = hip.point_nearest(index, pts, want_tested=True)
+    assert d2.dtype == torch.float64 and idx.dtype == torch.int32 and tested.dtype == torch.int32
+    close = gap < 1e-9
+    share = float(close.double().mean())
+    rel = ((d2 - want_d2).abs() / want_d2.clamp(min=1e-300)).max().item() if d2.numel() else 0.0
+    print("%-30s %5d points %5d queries: grid %s, tests per query mean %.1f max %d, d2 rel. error %.3g, left out %.4f"
+          % (what, cloud.shape[0], pts.shape[0], index.header()["n"], tested.float().mean().item(), int(tested.max()), rel, share))
+    if exact:
+        assert torch.equal(d2, want_d2), what
+    else:
+        np.testing.assert_allclose(d2.cpu().numpy(), want_d2.cpu().numpy(), rtol=2.0 ** -48, atol=0.0, err_msg=what)
+    if allow_close:
+        assert torch.equal(idx.long()[~close], want_idx[~close]), what
+    else:
+        assert share == 0.0, what
+        assert torch.equal(idx.long(), want_idx), what
+    return index, d2, idx
+
+
+@gpu
+@pytest.mark.parametrize("name", ["uniform", "clustered, input 1's queries", "clustered, own queries", "planar"])
+def test_point_nearest_equals_the_brute_force(inputs, name):
+    from arah_release_amd import hip
+    cloud, pts, d2, idx, gap = inputs[name]
+    print("smallest relative gap %.3g" % float(gap.min()))
+    _check_query(hip, cloud, pts, (d2, idx, gap), name)
+
+
+@gpu
+def test_point_nearest_on_a_lattice_resolves_every_tie(inputs):
+    from arah_release_amd import hip
+    cloud, pts, d2, idx, gap = inputs["lattice"]
+    assert pts.shape[0] == 9261 and int((gap == 0).sum()) == 7064
+    _, got_d2, got_idx = _check_query(hip, cloud, pts, (d2, idx, torch.ones_like(gap)), "lattice", exact=True)
+    ties = gap == 0
+    assert torch.equal(got_idx.long()[ties], idx[ties])
+
+
+@gpu
+def test_point_nearest_edge_cases():
+    from arah_release_amd import hip
+    dev = torch.device(DEV)
+    gen = torch.Generator().manual_seed(5)
+    box = (torch.rand(200, 3, generator=gen) * 4 - 2).to(dev)
+
+    def check(cloud, pts, what, exact=False):
+        cloud, pts = cloud.to(dev).float().contiguous(), pts.to(dev).float().contiguous()
+        return _check_query(hip, cloud, pts, brute_torch(cloud, pts), what, exact=exact, allow_close=True)
+
+    one = torch.tensor([[0.5, -0.25, 2.0]])
+    _, d2, idx = check(one, box, "one point")
+    assert bool((idx == 0).all())
+    index, d2, idx = check(one.expand(100, 3), torch.cat([box, one.to(dev)]), "100 copies of one point", exact=True)
+    assert bool((idx == 0).all()) and float(d2[-1]) == 0.0 and index.header()["n"] == (1, 1, 1)
+    t = torch.rand(300, 1, generator=gen)
+    line = torch.cat([t * 2 - 1, torch.full_like(t, 0.25), torch.full_like(t, -0.5)], 1)
+    index, _, _ = check(line, box, "collinear")
+    assert index.header()["n"][1:] == (1, 1)
+    ball = torch.randn(1000, 3, generator=gen)
+    ball = ball / ball.norm(dim=1, keepdim=True) * torch.rand(1000, 1, generator=gen) ** (1 / 3)
+    outlier = torch.cat([ball, torch.tensor([[1e4, 0.0, 0.0]])])
+    near_both = torch.cat([box[:100], torch.tensor([1e4, 0.0, 0.0], device=dev) + box[100:]])
+    _, _, idx = check(outlier, near_both, "ball and an outlier")
+    assert int((idx == 1000).sum()) == 100 and bool((idx[:100] < 1000).all())
+    d = torch.randn(100, 3, generator=gen)
+    far = d / d.norm(dim=1, keepdim=True) * 1e3
+    check(ball, far, "queries 1e3 away")
+    # non-finite queries answer (NaN, -1); their neighbours in the wave are answered as ever
+    pts = box[:130].clone()
+    pts[5, 1] = float("nan")
+    pts[70, 0] = float("inf")
+    pts[71, 2] = float("-inf")
+    cloud = ball.to(dev).float().contiguous()
+    d2, idx, tested = hip.point_nearest(hip.point_index(cloud), pts.contiguous(), want_tested=True)
+    want_d2, want_idx, _ = brute_torch(cloud, box[:130])
+    bad = torch.zeros(130, dtype=torch.bool, device=dev)
+    bad[[5, 70, 71]] = True
+    assert bool(torch.isnan(d2[bad]).all()) and bool((idx[bad] == -1).all()) and bool((tested[bad] == 0).all())
+    assert torch.equal(idx.long()[~bad], want_idx[~bad])
+    np.testing.assert_allclose(d2[~bad].cpu().numpy(), want_d2[~bad].cpu().numpy(), rtol=2.0 ** -48, atol=0.0)
+    # non-finite cloud points are never returned
+    holes = ball.clone()
+    holes[::3, 0] = float("nan")
+    holes[1, 2] = float("inf")
+    index, _, idx = check(holes, box, "a cloud with NaN points")
+    assert bool(torch.isfinite(holes.to(dev)[idx.long()]).all()) and index.header()["n_bad"] == 335 and int(index.n_bad) == 335
+    d2, idx, _ = hip.point_nearest(hip.point_index(torch.full((9, 3), float("nan"), device=dev)), box)
+    assert bool((d2 == float("inf")).all()) and bool((idx == -1).all())
+    d2, idx, _ = hip.point_nearest(index, box[:0])
+    assert d2.shape == (0,) and idx.shape == (0,)
+
+
+@gpu
+def test_point_nearest_does_not_depend_on_order_or_build(inputs):
+    from arah_release_amd import hip
+    dev = torch.device(DEV)
+    for name in ("uniform", "clustered, own queries"):
+        cloud, pts, want_d2, want_idx, _ = inputs[name]
+        index = hip.point_index(cloud)
+        first = hip.point_nearest(index, pts, want_tested=True)
+        again = hip.point_nearest(hip.point_index(cloud.clone()), pts, want_tested=True)
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            other = hip.point_nearest(hip.point_index(cloud), pts, want_tested=True)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        for a, b, c in zip(first, again, other):
+            assert torch.equal(a, b) and torch.equal(a, c), name
+        perm = torch.randperm(cloud.shape[0], generator=torch.Generator().manual_seed(6)).to(dev)
+        d2, idx, _ = hip.point_nearest(hip.point_index(cloud[perm].contiguous()), pts)
+        assert torch.equal(d2, first[0]) and torch.equal(perm[idx.long()], first[1].long()), name
+        order = torch.randperm(pts.shape[0], generator=torch.Generator().manual_seed(7)).to(dev)
+        shuffled = hip.point_nearest(index, pts[order].contiguous(), want_tested=True)
+        for a, b in zip(first, shuffled):
+            assert torch.equal(a[order], b), name
+    head = hip.point_index(inputs["uniform"][0]).header()
+    print("uniform:", head)
+    assert head["n_cells"] >= 2 and head["n_cells"] == head["n"][0] * head["n"][1] * head["n"][2] and head["n_refs"] == 4099
+    assert head["n_bad"] == 0 and head["h"] > 0
+    same = hip.point_index(torch.full((100, 3), 0.375, device=dev)).header()
+    assert same["n"] == (1, 1, 1) and same["n_refs"] == 100
+
+
+@gpu
+def test_the_point_index_is_an_index():
+    from arah_release_amd import hip
+    tris = icosphere(5)
+    verts = np.unique(tris.reshape(-1, 3), axis=0)
+    more, _ = sample_np(tris, 20480 - len(verts), np.random.RandomState(8))
+    cloud = torch.from_numpy(np.concatenate([verts, more]).astype(np.float32)).to(DEV)
+    assert cloud.shape[0] == 20480
+    pts = torch.from_numpy(sample_np(icosphere(4, 0.8), 5000, np.random.RandomState(9))[0]).to(DEV)
+    index = hip.point_index(cloud)
+    d2, idx, tested = hip.point_nearest(index, pts, want_tested=True)
+    want_d2, want_idx, gap = brute_torch(cloud, pts)
+    keep = gap >= 1e-9
+    assert torch.equal(idx.long()[keep], want_idx[keep])
+    head = index.header()
+    counts = index.cell_counts()
+    occupied = counts[counts > 0]
+    mean = tested.float().mean().item()
+    print("sheet of %d points: grid %s (measured dimension %.2f), %.1f points per occupied cell (max %d); tests per query mean %.1f "
+          "max %d" % (cloud.shape[0], head["n"], head["dim"], occupied.float().mean().item(), int(occupied.max()), mean,
+                      int(tested.max())))
+    assert int(counts.sum()) == 20480
+    assert mean < cloud.shape[0] / 10
+
+
+# --------------------------------------------------------------------------------------------------- GPU: the scores
+def _sphere_cloud(level, radius):
+    verts = np.unique(icosphere(level, radius).reshape(-1, 3), axis=0)
+    n = verts.astype(np.float64) / np.linalg.norm(verts.astype(np.float64), axis=1, keepdims=True)
+    return verts, n.astype(np.float32)
+
+
+@gpu
+def test_mesh_against_cloud_against_the_restatement():
+    from arah_release_amd import geometry
+    dev = torch.device(DEV)
+    rng = np.random.RandomState(10)
+    mesh = icosphere(2, 0.5, (0.1, -0.2, 0.3))
+    # the cloud lies INSIDE the convex mesh: the closest point of the mesh is then inside a face, not on an edge that two faces
+    # share, where the restatement and the kernel could settle a tie of normals differently by a rounding
+    pts, _ = sample_np(icosphere(3, 0.47, (0.105, -0.2, 0.3)), 1500, rng)
+    nrm = pts.astype(np.float64) - np.array([0.105, -0.2, 0.3])
+    nrm = (nrm / np.linalg.norm(nrm, axis=1, keepdims=True)).astype(np.float32)
+    taus = (0.025, 0.03, 0.05, 0.5)
+    cloud = geometry.PointCloud(torch.from_numpy(pts).to(dev), torch.from_numpy(nrm).to(dev))
+    res = geometry.mesh_metrics(torch.from_numpy(mesh).to(dev), cloud, n_samples=2000, seed=3, return_samples=True, thresholds=taus)
+    assert res["n_a"] == 2000 and res["n_b"] == 1500 and res["thresholds"] == taus
+    s = res["samples"]
+    assert int(s["n_faces_a"]) == len(mesh) and s["tris_b"] is None and torch.equal(s["points_b"], cloud.points)
+    pa, fa = s["points_a"].cpu().numpy(), s["face_a"].cpu().numpy()
+    tris_a = s["tris_a"].cpu().numpy()
+    d2_ab, g_ab = nearest_np(pts, pa)
+    d2_ba, g_ba = brute_closest(tris_a, pts)
+    fn = face_normals_np(tris_a)
+    ab = restate_side(d2_ab, fn[fa], nrm.astype(np.float64)[g_ab], taus)
+    ba = restate_side(d2_ba, nrm.astype(np.float64), fn[g_ba], taus)
+    want = restate_from_sides(ab, ba)
+    np.testing.assert_array_equal(s["closest_face_ab"].cpu().numpy(), g_ab)
+    bound = max(np.abs(tris_a).max(), np.abs(pts).max()) ** 2
+    for k in KEYS:
+        got = float(res[k])
+        tol = 64 * 2.0 ** -53 * (abs(want[k]) + bound)
+        print("%-20s %.17g restated %.17g  |diff| %.3g  tol %.3g" % (k, got, want[k], abs(got - want[k]), tol))
+    for k in KEYS:
+        assert res[k].dim() == 0 and res[k].dtype == torch.float64 and res[k].is_cuda, k
+        assert abs(float(res[k]) - want[k]) <= 64 * 2.0 ** -53 * (abs(want[k]) + bound), k
+    print("within: A", ab["within"], "of 2000, B", ba["within"], "of 1500")
+    assert 0 < ab["within"][0] < 2000 and ab["within"][-1] == 2000
+    for key, side, n in (("precision", ab, 2000), ("recall", ba, 1500)):
+        assert res[key].dtype == torch.float64 and res[key].shape == (4,) and res[key].is_cuda
+        counts = [int(round(float(v) * n)) for v in res[key]]
+        assert counts == side["within"], key
+        assert res[key].tolist() == [w / n for w in side["within"]], key
+    p, r = np.array(ab["within"]) / 2000.0, np.array(ba["within"]) / 1500.0
+    np.testing.assert_allclose(res["fscore"].cpu().numpy(), 2 * p * r / (p + r), rtol=2.0 ** -50)
+    assert 0.9 < want["normal_consistency"] <= 1.0 and 0.01 < want["accuracy"] < 0.05
+    # the other order swaps the roles; a bare tensor is a cloud without normals
+    swapped = geometry.mesh_metrics(cloud, torch.from_numpy(mesh).to(dev), n_samples=2000, seed=3, thresholds=taus)
+    assert swapped["n_a"] == 1500 and swapped["n_b"] == 2000
+    for k, m in (("accuracy", "completeness"), ("completeness", "accuracy"), ("hausdorff_ab", "hausdorff_ba"), ("precision", "recall"),
+                 ("chamfer_l1", "chamfer_l1"), ("fscore", "fscore"), ("normal_consistency", "normal_consistency")):
+        assert torch.equal(swapped[k], res[m]), k
+    bare = geometry.mesh_metrics(torch.from_numpy(mesh).to(dev), cloud.points, n_samples=2000, seed=3, thresholds=taus)
+    for k in KEYS + ("precision", "recall", "fscore"):
+        if k == "normal_consistency":
+            assert bool(torch.isnan(bare[k]))
+        else:
+            assert torch.equal(bare[k], res[k]) and bool(torch.isfinite(bare[k]).all()), k
+
+
+@gpu
+def test_cloud_scores_closed_forms():
+    from arah_release_amd import geometry
+    dev = torch.device(DEV)
+    # a flat patch against the cloud of its own vertices, lifted by delta
+    delta = 2.0 ** -6
+    patch = flat_patch()
+    verts = np.unique(patch.reshape(-1, 3), axis=0)
+    lifted = torch.from_numpy((verts + np.array([0, 0, delta], np.float32)).astype(np.float32)).to(dev)
+    below = float(np.nextafter(delta, 0.0))
+    res = geometry.mesh_metrics(torch.from_numpy(patch).to(dev), lifted, n_samples=3000, seed=0, thresholds=(delta, below, 1.0))
+    print({k: float(res[k]) for k in KEYS}, res["precision"].tolist(), res["recall"].tolist())
+    assert res["n_b"] == len(verts) == 81
+    assert float(res["accuracy"]) >= delta and float(res["hausdorff_ab"]) <= np.sqrt(delta ** 2 + 2 * 0.125 ** 2) + 1e-6
+    assert float(res["completeness"]) == delta and float(res["hausdorff_ba"]) == delta
+    assert res["recall"].tolist() == [1.0, 0.0, 1.0] and float(res["precision"][1]) == 0.0 and float(res["precision"][2]) == 1.0
+    assert float(res["fscore"][1]) == 0.0 and float(res["fscore"][2]) == 1.0 and bool(torch.isnan(res["normal_consistency"]))
+    # concentric icospheres: a mesh of radius 0.8 against the cloud of the unit icosphere's vertices with outward normals
+    r1, r2 = 0.8, 1.0
+    a_np, b_np = icosphere(4, r1), icosphere(4, r2)
+    lo, hi = sphere_bracket(a_np, r1, b_np, r2)
+    spacing = float(np.linalg.norm(b_np[:, 0].astype(np.float64) - b_np[:, 1].astype(np.float64), axis=1).max())
+    verts, normals = _sphere_cloud(4, r2)
+    cloud = geometry.PointCloud(torch.from_numpy(verts).to(dev), torch.from_numpy(normals).to(dev))
+    res = geometry.mesh_metrics(torch.from_numpy(a_np).to(dev), cloud, n_samples=20000, seed=1, return_samples=True)
+    print({k: float(res[k]) for k in KEYS}, "bracket", lo, hi, "spacing", spacing)
+    assert set(res) == set(KEYS) | {"n_a", "n_b", "samples"}
+    d_ab, d_ba = res["samples"]["d2_ab"].sqrt(), res["samples"]["d2_ba"].sqrt()
+    assert lo <= float(d_ab.min()) and float(d_ab.max()) <= hi + spacing
+    assert lo <= float(d_ba.min()) and float(d_ba.max()) <= hi
+    assert lo <= float(res["accuracy"]) <= hi + spacing and lo <= float(res["completeness"]) <= hi
+    assert float(res["hausdorff_ab"]) == float(d_ab.max()) and float(res["hausdorff_ba"]) == float(d_ba.max())
+    assert 0.99 < float(res["normal_consistency"]) <= 1.0
+    # cloud against cloud, both orders, against the numpy loop
+    inner_v, inner_n = _sphere_cloud(3, r1)
+    inner = geometry.PointCloud(torch.from_numpy(inner_v).to(dev), torch.from_numpy(inner_n).to(dev))
+    taus = (0.205, 0.22, 0.25)
+    ab = geometry.mesh_metrics(inner, cloud, thresholds=taus)
+    ba = geometry.mesh_metrics(cloud, inner, thresholds=taus)
+    assert ab["n_a"] == len(inner_v) == ba["n_b"] and ab["n_b"] == len(verts) == ba["n_a"]
+    d2_ab, g_ab = nearest_np(verts, inner_v)
+    d2_ba, g_ba = nearest_np(inner_v, verts)
+    want = restate_from_sides(restate_side(d2_ab, inner_n.astype(np.float64), normals.astype(np.float64)[g_ab], taus),
+                              restate_side(d2_ba, normals.astype(np.float64), inner_n.astype(np.float64)[g_ba], taus))
+    for k in KEYS:
+        assert abs(float(ab[k]) - want[k]) <= 64 * 2.0 ** -53 * (abs(want[k]) + 1.0), k
+    assert ab["precision"].tolist() == [float((d2_ab <= t * t).mean()) for t in taus]
+    assert ab["recall"].tolist() == [float((d2_ba <= t * t).mean()) for t in taus]
+    for k, m in (("accuracy", "completeness"), ("completeness", "accuracy"), ("hausdorff_ab", "hausdorff_ba"), ("precision", "recall"),
+                 ("recall", "precision"), ("fscore", "fscore"), ("chamfer_l2", "chamfer_l2")):
+        assert torch.equal(ab[k], ba[m]), k
+    assert float(ab["accuracy"]) >= r2 - r1 - 1e-6 and float(ab["normal_consistency"]) > 0.99
+
+
+@gpu
+def test_two_meshes_score_as_before():
+    from arah_release_amd import geometry
+    dev = torch.device(DEV)
+    a, b = torch.from_numpy(icosphere(3, 0.8)).to(dev), torch.from_numpy(icosphere(4, 0.81, (0.01, 0, 0))).to(dev)
+    plain = geometry.mesh_metrics(a, b, n_samples=5000, seed=2, return_samples=True)
+    with_t = geometry.mesh_metrics(a, b, n_samples=5000, seed=2, thresholds=(0.01,))
+    assert set(geometry.mesh_metrics(a, b, n_samples=5000, seed=2)) == set(KEYS) | {"n_a", "n_b"}
+    assert set(with_t) == set(KEYS) | {"n_a", "n_b", "precision", "recall", "fscore", "thresholds"}
+    for k in KEYS:
+        assert torch.equal(plain[k], with_t[k]), k
+    s = plain["samples"]
+    for key, d2 in (("precision", s["d2_ab"]), ("recall", s["d2_ba"])):
+        want = int((d2.cpu().numpy() <= 0.01 * 0.01).sum())
+        assert 0 < want < 5000 and with_t[key].tolist() == [want / 5000.0], key
+    p, r = float(with_t["precision"]), float(with_t["recall"])
+    assert float(with_t["fscore"]) == pytest.approx(2 * p * r / (p + r), rel=1e-15)
+
+
+@gpu
+def test_cloud_scores_determinism_no_synchronisation_and_nan_rules():
+    from arah_release_amd import geometry
+    dev = torch.device(DEV)
+    mesh = torch.from_numpy(icosphere(3, 0.8)).to(dev)
+    verts, normals = _sphere_cloud(4, 1.0)
+    cloud = geometry.PointCloud(torch.from_numpy(verts).to(dev), torch.from_numpy(normals).to(dev))
+    taus = (0.19, 0.2, 0.25)
+    first = geometry.mesh_metrics(mesh, cloud, n_samples=10000, seed=0, thresholds=taus)
+    again = geometry.mesh_metrics(mesh, cloud, n_samples=10000, seed=0, thresholds=taus)
+    torch.cuda.synchronize(dev)
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        quiet = geometry.mesh_metrics(mesh, cloud, n_samples=10000, seed=0, thresholds=taus)
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    for k in KEYS + ("precision", "recall", "fscore"):
+        assert torch.equal(first[k], again[k]) and torch.equal(first[k], quiet[k]), k
+        assert bool(torch.isfinite(first[k]).all()), k
+    # a cloud without normals: the normal term alone is NaN
+    bare = geometry.mesh_metrics(mesh, geometry.PointCloud(cloud.points), n_samples=10000, seed=0, thresholds=taus)
+    for k in KEYS + ("precision", "recall", "fscore"):
+        if k == "normal_consistency":
+            assert bool(torch.isnan(bare[k]))
+        else:
+            assert torch.equal(bare[k], first[k]), k
+    # a cloud with one NaN point: every score is NaN
+    holed = cloud.points.clone()
+    holed[17, 1] = float("nan")
+    for pair in ((mesh, geometry.PointCloud(holed, cloud.normals)), (holed, mesh)):
+        bad = geometry.mesh_metrics(*pair, n_samples=1000, seed=0, thresholds=taus)
+        for k in KEYS + ("precision", "recall", "fscore"):
+            assert bool(torch.isnan(bad[k]).all()), k
+    with pytest.raises(ValueError):
+        geometry.mesh_metrics(mesh, cloud.to("cpu"), n_samples=100)
+
+
+@gpu
+def test_geometry_metrics_against_a_cloud_of_the_subject(posed):  # noqa: F811
+    from arah_release_amd import geometry
+    model, inputs, m128 = posed["model"], posed["inputs"], posed["m128"]
+    verts = m128["tris"].reshape(-1, 3).contiguous()
+    cell = float(m128["box"][3]) / 127.0
+    with torch.no_grad():
+        res = model.geometry_metrics(inputs, geometry.PointCloud(verts), n_side=128, n_samples=50000, seed=0, thresholds=(np.sqrt(3) * cell,))
+        bare = model.geometry_metrics(inputs, verts, n_side=128, n_samples=50000, seed=0)
+    tol = np.sqrt(3) * 4 * F32 * float(verts.abs().max())
+    print("own vertices:", {k: float(res[k]) for k in KEYS}, "cell diagonal", np.sqrt(3) * cell, "tolerance", tol)
+    assert res["n_tris"] == m128["n_tris"] and res["n_a"] == 50000 and res["n_b"] == verts.shape[0]
+    assert 0.0 < float(res["accuracy"]) < np.sqrt(3) * cell and float(res["hausdorff_ab"]) < np.sqrt(3) * cell
+    assert 0.0 <= float(res["completeness"]) <= tol and float(res["hausdorff_ba"]) <= tol
+    assert bool(torch.isnan(res["normal_consistency"]))
+    assert res["precision"].tolist() == [1.0] and res["recall"].tolist() == [1.0] and res["fscore"].tolist() == [1.0]
+    assert set(bare) == set(KEYS) | {"n_a", "n_b", "n_tris"}
+    for k in ("accuracy", "completeness", "chamfer_l2", "hausdorff_ab"):
+        assert torch.equal(bare[k], res[k]), k
+
+
+@gpu
+def test_validate_with_a_scan_and_thresholds(tmp_path, scene, monkeypatch):
+    """python -m arah_release_amd.validate --geometry DIR [--geometry-thresholds ...] on the synthetic capture of the validation
+    tests; the ground truth of one frame is the posed mesh as .npz, of another its vertices as a vertex-only binary PLY."""
+    import yaml
+    from test_validation import _capture_cfg, _fake_samples, _write_capture
+    from arah_release_amd import config, data, geometry, smpl, train, validate
+    dev = torch.device(DEV)
+    body = smpl.BodyModel.synthetic(scene)
+    monkeypatch.setattr(data, "training_samples", _fake_samples)
+    n_frames, size = 3, 256
+    faces = np.zeros((1, 3), np.int32)
+    _write_capture(tmp_path / "data", scene, n_frames=n_frames, size=size, focal=300.0, full_masks=True)
+    cfg = _capture_cfg(tmp_path)
+    (tmp_path / "cfg.yaml").write_text(yaml.safe_dump(cfg))
+    argv = [str(tmp_path / "cfg.yaml"), "--default-config", str(tmp_path / "cfg.yaml")]
+    train_ds = data.get_capture_dataset("train", cfg, body=body, faces=faces)
+    val_ds = data.get_capture_dataset("val", cfg, body=body, faces=faces)
+    lm = config.get_model(cfg, dataset=train_ds, mode="val", body_model=body)
+    own = lm.model.state_dict()
+    lm.model.load_state_dict({k: v for k, v in config.synthetic_state_dict(cfg).items()
+                              if k not in own or own[k].shape == v.shape}, strict=False)
+    train.save_checkpoint(str(tmp_path / "out" / "checkpoints" / "last.ckpt"), lm, lm.configure_optimizers(), epoch=1, global_step=n_frames)
+    lm = lm.to(dev).eval()
+    gt_dir = tmp_path / "gt"
+    gt_dir.mkdir()
+    for i in (0, 2):
+        with torch.no_grad():
+            mesh = lm.model.posed_mesh(lm.compose_inputs(val_ds.validation_item(i, dev), eval=True), n_side=128)
+        verts = mesh["tris"].reshape(-1, 3).cpu().numpy()
+        stem = os.path.splitext(os.path.basename(val_ds.data[i]["model_file"]))[0]
+        if i == 0:
+            np.savez(gt_dir / (stem + ".npz"), vertices=verts, faces=np.arange(len(verts)).reshape(-1, 3))
+        else:
+            geometry.save_points(gt_dir / (stem + ".ply"), verts)
+            assert isinstance(geometry.load_geometry(gt_dir / (stem + ".ply")), geometry.PointCloud)
+    plain_keys = {"n", "n_psnr_inf", "psnr", "ssim", "seconds_per_frame", "world", "data_range", "mode"}
+    lines = []
+
+    def no_constant(name):
+        raise AssertionError("%s in the JSON line" % name)
+    common = ["--geometry", str(gt_dir), "--geometry-n-side", "128", "--geometry-samples", "20000"]
+    validate.main(argv + common, body=body, faces=faces, log=lines.append)
+    line = json.loads(lines[-1], parse_constant=no_constant)
+    print("validate --geometry:", lines[-1])
+    assert set(line) == plain_keys | set(KEYS) | {"n_geometry"}
+    assert line["n"] == n_frames and line["n_geometry"] == 2
+    assert line["chamfer_l1"] > 0.0
+    saved = json.load(open(tmp_path / "out" / "validation.json"), parse_constant=no_constant)
+    assert [set(f) for f in saved["frames"]] == [{"frame", "status", "psnr", "ssim"} | set(KEYS), {"frame", "status", "psnr", "ssim"},
+                                                 {"frame", "status", "psnr", "ssim"} | set(KEYS)]
+    # a scan without normals has no normal consistency (null, not NaN); the mean runs over the frames that have the score
+    assert saved["frames"][0]["normal_consistency"] > 0.99 and saved["frames"][2]["normal_consistency"] is None
+    assert line["normal_consistency"] == saved["frames"][0]["normal_consistency"]
+    assert line["chamfer_l1"] == pytest.approx(np.mean([saved["frames"][i]["chamfer_l1"] for i in (0, 2)]), abs=1e-18)
+    validate.main(argv + common + ["--geometry-thresholds", "0.01,0.05"], body=body, faces=faces, log=lines.append)
+    with_t = json.loads(lines[-1], parse_constant=no_constant)
+    print("validate --geometry-thresholds:", lines[-1])
+    extra = {"%s@%s" % (name, t) for name in ("precision", "recall", "fscore") for t in ("0.01", "0.05")}
+    assert set(with_t) == set(line) | extra
+    assert with_t["fscore@0.05"] == 1.0 and with_t["precision@0.05"] == 1.0 and with_t["recall@0.05"] == 1.0
+    assert 0.0 <= with_t["precision@0.01"] <= 1.0 and with_t["recall@0.01"] == 1.0
+    for k in KEYS:
+        assert with_t[k] == line[k], k
+    saved = json.load(open(tmp_path / "out" / "validation.json"), parse_constant=no_constant)
+    scored = [f for f in saved["frames"] if "chamfer_l1" in f]
+    assert [f["frame"] for f in scored] == [0, 2] and all(extra <= set(f) for f in scored) and not extra & set(saved["frames"][1])
+    for k in sorted(extra) + ["chamfer_l1", "accuracy", "hausdorff_ab"]:
+        assert np.mean([f[k] for f in scored]) == pytest.approx(with_t[k], abs=1e-15), k
+    with pytest.raises(ValueError):
+        validate.main(argv + ["--geometry-thresholds", "0.01"], body=body, faces=faces, log=lines.append)
