@@ -385,7 +385,7 @@ __device__ __forceinline__ bool occ_lookup(const OccInfo& oi, const unsigned* bi
 // segment [near, far] walks through no voxel that is marked or shares a face with a marked one (distance byte <= 1: the slack
 // covers a voxel walk that clips a corner differently from floor()) is therefore a certain miss: skip[ray] = 1, loops A and B are
 // not run for it, the tracer reports converged = 0, start = near like the reference does for a ray that left the box (RT:235,
-// 274-277).  Segments that leave the bitmap's box, and every ray of an invalid occupancy, are traced.
+// 274-277).  Segments that leave the bitmap's box, empty intervals (near >= far) and every ray of an invalid occupancy are traced.
 __global__ void k_tier_rays(int n, RaySet rs, const float* __restrict__ near_far, const OccInfo* __restrict__ info,
                             const uint8_t* __restrict__ dist, uint8_t* __restrict__ skip, TierStats* stats) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -393,7 +393,7 @@ __global__ void k_tier_rays(int n, RaySet rs, const float* __restrict__ near_far
     if (i < n) {
         const OccInfo oi = *info;
         const float t0 = near_far[i * 2] - 1e-4f, t1 = near_far[i * 2 + 1] + 1e-4f;
-        if (oi.valid && t0 < t1) {
+        if (oi.valid && near_far[i * 2] < near_far[i * 2 + 1]) {   // an empty interval (near >= far) is traced, not judged by its 2e-4 of slack
             const int cam = i / rs.rays_per_cam;
             const float o[3] = {(rs.cam_loc[cam * 3] - oi.origin[0]) * oi.inv_v, (rs.cam_loc[cam * 3 + 1] - oi.origin[1]) * oi.inv_v,
                                 (rs.cam_loc[cam * 3 + 2] - oi.origin[2]) * oi.inv_v};

@@ -397,6 +397,42 @@ class Workspace:
         return {k: int(getattr(out, k)) for k, _ in ArahCounters._fields_}
 
 
+# The occupancy buffer's layout (csrc/tier.hpp: the constants kOcc*, kTierBand; csrc/arah_hip.hip: carve_occ hands the arrays out in
+# this order, each starting on a 256-byte boundary like Carver::take).  tests/test_occupancy_spec.py reads both out of the source.
+OCC_NC, OCC_F, OCC_L, OCC_MAX_CELLS, OCC_MAX_VOX, OCC_ALIGN, TIER_BAND = 49, 3, 1.5, 12288, 1 << 22, 256, 18.0
+OCC_MAX_FINE = OCC_MAX_CELLS * OCC_F ** 3
+OCC_INFO_WORDS = 16   # OccInfo: origin[3], v, inv_v (float) | dims[3], n_vox, valid, n_cells, n_fine, n_sel, overflow (int) | band_m, lip_pose (float)
+OCC_FIELDS = (("info", torch.int32, (OCC_INFO_WORDS,)), ("bits", torch.int32, (OCC_MAX_VOX // 32,)), ("dist", torch.uint8, (OCC_MAX_VOX,)),
+              ("csdf", torch.float32, (OCC_NC ** 3,)), ("cpts", torch.float32, (OCC_NC ** 3, 3)),
+              ("cell_lip", torch.float32, (OCC_MAX_CELLS,)), ("cell_stretch", torch.float32, (OCC_MAX_CELLS,)),
+              ("fnorm", torch.float32, (OCC_MAX_FINE, 3)), ("fsdf", torch.float32, (OCC_MAX_FINE,)), ("iota", torch.int32, (OCC_MAX_FINE,)),
+              ("sel_raw", torch.float32, (OCC_MAX_FINE, 3)), ("sel_bar", torch.float32, (OCC_MAX_FINE, 3)),
+              ("sel_idx", torch.int32, (OCC_MAX_FINE,)), ("sel_of", torch.int32, (OCC_MAX_FINE,)))
+
+
+def occupancy_layout():
+    """[(name, byte offset, byte length, dtype, shape)] of the occupancy buffer's arrays, and the buffer's size."""
+    out, off = [], 0
+    for name, dt, shape in OCC_FIELDS:
+        off = (off + OCC_ALIGN - 1) // OCC_ALIGN * OCC_ALIGN
+        nbytes = torch.empty(0, dtype=dt).element_size()
+        for s in shape:
+            nbytes *= s
+        out.append((name, off, nbytes, dt, shape))
+        off += nbytes
+    return out, (off + OCC_ALIGN - 1) // OCC_ALIGN * OCC_ALIGN
+
+
+def occupancy_view(occ):
+    """Tests only: the arrays of an occupancy buffer (Workspace.occupancy) as typed views onto it, no copy -- dict name -> tensor in
+    the order of OCC_FIELDS.  `info` is the header's 16 words as int32 (its float fields: .view(torch.float32)); `bits` holds voxel
+    b in bit b & 31 of word b >> 5."""
+    layout, total = occupancy_layout()
+    if occ.dtype != torch.uint8 or occ.dim() != 1 or occ.numel() < total:
+        raise ValueError("occupancy_view: a uint8 buffer of at least %d bytes" % total)
+    return {name: occ[off:off + nbytes].view(dt).reshape(shape) for name, off, nbytes, dt, shape in layout}
+
+
 _side_streams = {}
 
 
