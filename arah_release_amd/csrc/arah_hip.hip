@@ -500,6 +500,14 @@ __device__ __forceinline__ void bitonic_sort_8192(unsigned* keys, unsigned short
     }
 }
 
+// The LDS operations of one wave complete in order; this keeps the compiler from moving them across a hand-over between the
+// lanes of a wave (no workgroup barrier: the other waves are not involved).
+__device__ __forceinline__ void wave_lds_handover() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 __device__ __forceinline__ int float_ordered(float f) {
     const int b = __float_as_int(f);
     return b >= 0 ? b : b ^ 0x7fffffff;
@@ -646,6 +654,38 @@ __global__ void k_cluster_spheres(const float* __restrict__ sorted4, float* __re
     reinterpret_cast<f32x4*>(spheres)[c] = s;
 }
 
+// The geometry of k_cell_clusters' two tests, shared by the serial kernel (the specification) and the wave-per-cell one, so that
+// both round alike: a cell's box, the largest distance from a point of the cell to a sphere's vertices (an upper bound of the
+// cell's nearest-vertex distance), the smallest one (a lower bound for that cluster).
+__device__ __forceinline__ void cell_box(const GridInfo& g, int cell, float (&lo)[3], float (&hi)[3]) {
+    const int cx = cell % g.dims[0], cy = (cell / g.dims[0]) % g.dims[1], cz = cell / (g.dims[0] * g.dims[1]);
+    lo[0] = g.origin[0] + cx * g.h;
+    lo[1] = g.origin[1] + cy * g.h;
+    lo[2] = g.origin[2] + cz * g.h;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) hi[k] = lo[k] + g.h;
+}
+__device__ __forceinline__ float cell_far_bound(const f32x4 s, const float (&lo)[3], const float (&hi)[3]) {
+    float far2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float d = fmaxf(fabsf(s[k] - lo[k]), fabsf(s[k] - hi[k]));
+        far2 += d * d;
+    }
+    return __builtin_amdgcn_sqrtf(far2) + s[3];   // 1 ulp: the slack of cell_upper_slack covers it
+}
+__device__ __forceinline__ float cell_upper_slack(float U) { return U * 1.0001f + 1e-6f; }
+__device__ __forceinline__ float cell_near_bound(const f32x4 s, const float (&lo)[3], const float (&hi)[3]) {
+    float near2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float d = fmaxf(fmaxf(lo[k] - s[k], s[k] - hi[k]), 0.f);
+        near2 += d * d;
+    }
+    return fmaxf(__builtin_amdgcn_sqrtf(near2) - s[3], 0.f);
+}
+
+// THE SPECIFICATION of the cell lists (tests only: arah_cell_clusters_debug, variant 0; the frame runs k_cell_clusters_wave).
 // thread per cell: upper bound U of the NN distance over the cell, then the clusters with lower bound <= U,
 // ordered by lower bound (insertion sort in LDS, <= 63 entries per thread)
 constexpr int kCellThreads = 128;
@@ -660,34 +700,17 @@ __global__ __launch_bounds__(kCellThreads) void k_cell_clusters(const GridInfo* 
     for (int i = t; i < kMaxClusters; i += kCellThreads) sph[i] = reinterpret_cast<const f32x4*>(spheres)[i];
     __syncthreads();
     for (int cell = blockIdx.x * kCellThreads + t; cell < g.n_cells; cell += gridDim.x * kCellThreads) {
-        const int cx = cell % g.dims[0], cy = (cell / g.dims[0]) % g.dims[1], cz = cell / (g.dims[0] * g.dims[1]);
-        const float lo[3] = {g.origin[0] + cx * g.h, g.origin[1] + cy * g.h, g.origin[2] + cz * g.h};
-        const float hi[3] = {lo[0] + g.h, lo[1] + g.h, lo[2] + g.h};
+        float lo[3], hi[3];
+        cell_box(g, cell, lo, hi);
         float U = 3.4e38f;
 #pragma unroll 4
-        for (int c = 0; c < kMaxClusters; ++c) {
-            const f32x4 s = sph[c];
-            float far2 = 0.f;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float d = fmaxf(fabsf(s[k] - lo[k]), fabsf(s[k] - hi[k]));
-                far2 += d * d;
-            }
-            U = fminf(U, __builtin_amdgcn_sqrtf(far2) + s[3]);   // 1 ulp: the slack below covers it
-        }
-        U = U * 1.0001f + 1e-6f;
+        for (int c = 0; c < kMaxClusters; ++c) U = fminf(U, cell_far_bound(sph[c], lo, hi));
+        U = cell_upper_slack(U);
         int cnt = 0;
         bool overflow = false;
 #pragma unroll 1
         for (int c = 0; c < kMaxClusters; ++c) {
-            const f32x4 s = sph[c];
-            float near2 = 0.f;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float d = fmaxf(fmaxf(lo[k] - s[k], s[k] - hi[k]), 0.f);
-                near2 += d * d;
-            }
-            const float lb = fmaxf(__builtin_amdgcn_sqrtf(near2) - s[3], 0.f);
+            const float lb = cell_near_bound(sph[c], lo, hi);
             if (lb <= U) {
                 if (cnt == 63) {
                     overflow = true;
@@ -722,6 +745,69 @@ __global__ __launch_bounds__(kCellThreads) void k_cell_clusters(const GridInfo* 
 #pragma unroll
         for (int q = 0; q < 4; ++q)
             reinterpret_cast<uint4*>(dst)[q] = uint4{w[q * 4], w[q * 4 + 1], w[q * 4 + 2], w[q * 4 + 3]};
+    }
+}
+
+// The frame's kernel: a WAVE per cell, lane l holding clusters l, l + 64, l + 128, l + 192 in registers.  The serial kernel's
+// duration was one thread's dependent chain (512 sphere tests, then an insertion sort through LDS, ~1000 operations) on 44.5 KB
+// of LDS per workgroup; here U is a wave minimum (fminf without NaNs does not depend on the order), the clusters that pass
+// are counted off in cluster order by ballots (the first 63 are kept, like the serial kernel's break), and a kept cluster's
+// slot is its RANK  #{kept j : lb_j < lb_i, or lb_j == lb_i and j before i}  -- where the stable insertion sort puts it.  The
+// record is put together in 64 bytes of LDS per wave and leaves as one 64-byte store.  Same bytes as the specification.
+constexpr int kCellWaves = 4;
+__global__ __launch_bounds__(kCellWaves * 64) void k_cell_clusters_wave(const GridInfo* __restrict__ grid,
+                                                                        const float* __restrict__ spheres,
+                                                                        unsigned char* __restrict__ cells) {
+    static_assert(kMaxClusters == 256 && kCellBytes == 64, "four clusters per lane, a record of 16 words");
+    __shared__ unsigned rec[kCellWaves][kCellBytes / 4];
+    const GridInfo g = *grid;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    f32x4 sp[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) sp[k] = reinterpret_cast<const f32x4*>(spheres)[lane + 64 * k];
+    unsigned char* bytes = reinterpret_cast<unsigned char*>(rec[wave]);
+    for (int cell = blockIdx.x * kCellWaves + wave; cell < g.n_cells; cell += gridDim.x * kCellWaves) {
+        float lo[3], hi[3];
+        cell_box(g, cell, lo, hi);
+        float U = 3.4e38f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) U = fminf(U, cell_far_bound(sp[k], lo, hi));
+        for (int o = 32; o > 0; o >>= 1) U = fminf(U, __shfl_xor(U, o));
+        U = cell_upper_slack(U);
+        float lb[4];
+        unsigned long long kept[4];
+        bool keep[4];
+        int total = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            lb[k] = cell_near_bound(sp[k], lo, hi);
+            const bool pass = lb[k] <= U;
+            const unsigned long long m = __ballot(pass);
+            keep[k] = pass && total + __popcll(m & below) < 63;   // the first 63 in cluster order
+            total += __popcll(m);
+            kept[k] = __ballot(keep[k]);
+        }
+        int rank[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int kj = 0; kj < 4; ++kj) {
+            for (unsigned long long mm = kept[kj]; mm; mm &= mm - 1ull) {
+                const int b = __ffsll((long long)mm) - 1;
+                const float lj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lb[kj]), b));
+                const int cj = b + 64 * kj;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) rank[k] += (lj < lb[k] || (lj == lb[k] && cj < lane + 64 * k)) ? 1 : 0;
+            }
+        }
+        if (lane < kCellBytes / 4) rec[wave][lane] = 0u;
+        wave_lds_handover();
+        if (lane == 0) bytes[0] = (unsigned char)(total > 63 ? 255 : total);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (keep[k]) bytes[1 + rank[k]] = (unsigned char)(lane + 64 * k);
+        wave_lds_handover();
+        if (lane < kCellBytes / 4) reinterpret_cast<unsigned*>(cells + (size_t)cell * kCellBytes)[lane] = rec[wave][lane];
+        wave_lds_handover();   // the next cell zeroes the record after these reads
     }
 }
 
@@ -2143,8 +2229,17 @@ __device__ __forceinline__ float jittered(F val, int i, int m, float t) {
     return lower + (upper - lower) * t;
 }
 
+// The depth expressions of RT:313-350, shared by the thread-per-ray kernel below and the wave-per-ray one of eval mode
+// (tier.hpp: wave_ray_depths): one definition, so that floating-point contraction falls the same way in both.
+__device__ __forceinline__ float depth_uniform(float st, float en, float lin) { return st + (en - st) * lin; }
+__device__ __forceinline__ float depth_surf(float base, float lin) { return base + (kSurfaceRange * 2.0f) * lin; }
+__device__ __forceinline__ float depth_far(float nb, float span, float lin) { return nb + span * lin; }
+__device__ __forceinline__ float depth_surf_base(float st) { return st - kSurfaceRange; }
+__device__ __forceinline__ float depth_far_span(float st, float nb) { return fmaxf(st - kSurfaceRange - nb, 1e-5f); }
+
 // depth samples of one ray (RT:313-350): thread per ray.  lin_* are torch.linspace tables; rand_* are the
-// caller's torch.rand draws of training mode (NULL in eval mode).
+// caller's torch.rand draws of training mode (NULL in eval mode).  Training mode runs this kernel; eval mode runs the
+// wave-per-ray one, whose specification this is (arah_sample_depths_debug compares the two bit for bit).
 __global__ void k_sample_depths(int n, int S, int n_near, int n_far, const float* near_far, const uint8_t* conv,
                                 const float* start, const float* end, const float* lin_s, const float* lin_near,
                                 const float* lin_far, const float* rand_s, const float* rand_near,
@@ -2154,7 +2249,7 @@ __global__ void k_sample_depths(int n, int S, int n_near, int n_far, const float
     const float st = start[i], en = end[i];
     float* zr = z + (size_t)i * S;
     uint8_t* mr = mask + (size_t)i * S;
-    auto uni = [&](int s) { return st + (en - st) * lin_s[s]; };
+    auto uni = [&](int s) { return depth_uniform(st, en, lin_s[s]); };
     auto uni_j = [&](int s) { return rand_s ? jittered(uni, s, S, rand_s[(size_t)i * S + s]) : uni(s); };
     if (!conv[i] || (n_near <= 0 && n_far <= 0)) {
         for (int s = 0; s < S; ++s) {
@@ -2164,11 +2259,11 @@ __global__ void k_sample_depths(int n, int S, int n_near, int n_far, const float
         return;
     }
     const int nc = n_near + 1 + n_far;
-    const float base = st - kSurfaceRange;
+    const float base = depth_surf_base(st);
     const float nb = near_far[i * 2];
-    const float span = fmaxf(st - kSurfaceRange - nb, 1e-5f);
-    auto surf = [&](int a) { return base + (kSurfaceRange * 2.0f) * lin_near[a]; };
-    auto farv = [&](int b) { return nb + span * lin_far[b]; };
+    const float span = depth_far_span(st, nb);
+    auto surf = [&](int a) { return depth_surf(base, lin_near[a]); };
+    auto farv = [&](int b) { return depth_far(nb, span, lin_far[b]); };
     auto surf_j = [&](int a) {   // the surface sample itself (index near/2) is not moved (RT:334, 305-307)
         if (!rand_near) return surf(a);
         return jittered(surf, a, n_near + 1, a == n_near / 2 ? 0.5f : rand_near[(size_t)i * (n_near + 1) + a]);
@@ -3442,6 +3537,8 @@ constexpr size_t kBodyOffSpheres = (size_t)kMaxClusters * kClusterSize * 16;
 constexpr size_t kBodyOffGrid = kBodyOffSpheres + (size_t)kMaxClusters * 16;
 constexpr size_t kBodyOffCells = kBodyOffGrid + ((sizeof(GridInfo) + 255) / 256) * 256;
 constexpr size_t kBodyBytes = kBodyOffCells + (size_t)kMaxCells * kCellBytes;
+static_assert(kBodyOffSpheres == ARAH_BODY_OFF_SPHERES && kBodyOffGrid == ARAH_BODY_OFF_GRID && kBodyOffCells == ARAH_BODY_OFF_CELLS,
+              "the body buffer's layout is part of the test ABI (arah_cell_clusters_debug)");
 
 BodyTables body_tables(void* buf) {
     char* b = reinterpret_cast<char*>(buf);
@@ -3453,11 +3550,18 @@ BodyTables body_tables(void* buf) {
     return t;
 }
 
+// variant 0: the serial specification (tests), variant 1: the wave-per-cell kernel
+void launch_cell_clusters(int variant, const GridInfo* grid, const float* spheres, unsigned char* cells, hipStream_t s) {
+    if (variant == 0)
+        hipLaunchKernelGGL(k_cell_clusters, dim3(kMaxCells / kCellThreads), dim3(kCellThreads), 0, s, grid, spheres, cells);
+    else
+        hipLaunchKernelGGL(k_cell_clusters_wave, dim3(2048), dim3(kCellWaves * 64), 0, s, grid, spheres, cells);
+}
+
 void launch_body_tables(const float* verts, int n_verts, const BodyTables& t, hipStream_t s) {
     hipLaunchKernelGGL(k_sort_verts, dim3(1), dim3(1024), 0, s, verts, n_verts, t.verts4, t.grid);
     hipLaunchKernelGGL(k_cluster_spheres, dim3(1), dim3(256), 0, s, (const float*)t.verts4, t.spheres);
-    hipLaunchKernelGGL(k_cell_clusters, dim3(kMaxCells / kCellThreads), dim3(kCellThreads), 0, s, (const GridInfo*)t.grid,
-                       (const float*)t.spheres, t.cells);
+    launch_cell_clusters(1, t.grid, t.spheres, t.cells, s);
 }
 
 }  // namespace
@@ -3493,6 +3597,14 @@ int arah_prepare_body(const float* verts, int32_t n_verts, void* body_buf, size_
     if (body_bytes < kBodyBytes) return ARAH_E_WORKSPACE;
     if (int arc = setup_attributes()) return arc;
     launch_body_tables(verts, n_verts, body_tables(body_buf), reinterpret_cast<hipStream_t>(stream));
+    return check_launch();
+}
+
+// tests: the per-cell candidate lists of a grid and its cluster spheres (device pointers into a body buffer, or the caller's own)
+// by the serial kernel (variant 0) or the wave-per-cell one (variant 1): n_cells records of 64 bytes -> cells
+int arah_cell_clusters_debug(int32_t variant, const void* grid, const float* spheres, uint8_t* cells, void* stream) {
+    if ((variant != 0 && variant != 1) || !grid || !spheres || !cells) return ARAH_E_BADARG;
+    launch_cell_clusters(variant, reinterpret_cast<const GridInfo*>(grid), spheres, cells, reinterpret_cast<hipStream_t>(stream));
     return check_launch();
 }
 
@@ -4239,6 +4351,22 @@ int arah_joint_root_find(const ArahFrame* f, const float* cam_loc, int32_t rays_
 }
 
 // ---- sampler + loop C -------------------------------------------------------------------------
+static DepthArgs depth_args(const ArahSampling* cfg, const float* near_far, const float* start, const float* end) {
+    return DepthArgs{cfg->n_near, cfg->n_far, near_far, start, end, cfg->lin_steps, cfg->lin_near, cfg->lin_far};
+}
+
+// variant 0: thread per ray (training mode's jitter; the specification), variant 1: wave per ray (eval mode, rand_* all NULL)
+static void launch_sample_depths(int variant, int n, const ArahSampling* cfg, const float* near_far, const uint8_t* conv,
+                                 const float* start, const float* end, const float* rand_s, const float* rand_near,
+                                 const float* rand_far, float* z, uint8_t* mask, hipStream_t s) {
+    if (variant == 0)
+        hipLaunchKernelGGL(k_sample_depths, dim3((n + 127) / 128), dim3(128), 0, s, n, cfg->n_steps, cfg->n_near, cfg->n_far, near_far,
+                           conv, start, end, cfg->lin_steps, cfg->lin_near, cfg->lin_far, rand_s, rand_near, rand_far, z, mask);
+    else
+        hipLaunchKernelGGL(k_sample_depths_wave, dim3(min(2048, (n + kTierWaves - 1) / kTierWaves)), dim3(kTierWaves * 64), 0, s, n,
+                           cfg->n_steps, depth_args(cfg, near_far, start, end), conv, z, mask);
+}
+
 static int sample_impl(const ArahFrame* f, const ArahSampling* cfg, Workspace& w, const float* cam_loc,
                        int32_t rays_per_cam, const float* dirs, const float* near_far, const uint8_t* conv,
                        const float* start, const float* end, int32_t n, const float* rand_s, const float* rand_near,
@@ -4248,8 +4376,8 @@ static int sample_impl(const ArahFrame* f, const ArahSampling* cfg, Workspace& w
     const RaySet rs = make_rays(cam_loc, dirs, rays_per_cam);
     const long long Q = (long long)n * S;
     hipMemsetAsync(w.counts, 0, sizeof(int) * 3 * kNumCounts, s);
-    hipLaunchKernelGGL(k_sample_depths, dim3((n + 127) / 128), dim3(128), 0, s, n, S, cfg->n_near, cfg->n_far, near_far,
-                       conv, start, end, cfg->lin_steps, cfg->lin_near, cfg->lin_far, rand_s, rand_near, rand_far, z, w.q_smask);
+    launch_sample_depths(rand_s || rand_near || rand_far ? 0 : 1, n, cfg, near_far, conv, start, end, rand_s, rand_near, rand_far, z,
+                         w.q_smask, s);
     const int gq = (int)((Q + 255) / 256);
     hipLaunchKernelGGL(k_build_list, dim3((int)((Q + 4095) / 4096)), dim3(1024), 0, s, (const uint8_t*)w.q_smask, (int)Q, w.listA, &w.counts[0]);
     // x0 -> pts (raw canonical, doubles as x_best), T0 -> T (doubles as T_best)
@@ -4287,6 +4415,29 @@ int arah_sample_canonicalize(const ArahFrame* f, const ArahSampling* cfg, const 
         return ARAH_E_BADARG;   // jitter is all or nothing
     return sample_impl(f, cfg, w, cam_loc, rays_per_cam, dirs, near_far, conv, start, end, n, rand_steps, rand_near,
                        rand_far, z, pts, T, mask, reinterpret_cast<hipStream_t>(stream));
+}
+
+// tests: the eval-mode depth samples of n rays by the serial kernel (variant 0) or the wave-per-ray one (variant 1); a pure
+// function of the caller's device buffers
+int arah_sample_depths_debug(int32_t variant, int32_t n, int32_t n_steps, int32_t n_near, int32_t n_far,
+                             const float* near_far, const uint8_t* conv, const float* start, const float* end,
+                             const float* lin_steps, const float* lin_near, const float* lin_far, float* z, uint8_t* mask,
+                             void* stream) {
+    if ((variant != 0 && variant != 1) || n < 0) return ARAH_E_BADARG;
+    ArahSampling cfg;
+    memset(&cfg, 0, sizeof(cfg));
+    cfg.n_steps = n_steps;
+    cfg.n_near = n_near;
+    cfg.n_far = n_far;
+    cfg.lin_steps = lin_steps;
+    cfg.lin_near = lin_near;
+    cfg.lin_far = lin_far;
+    if (int rc = check_sampling(&cfg)) return rc;
+    if (n == 0) return ARAH_OK;
+    if (!near_far || !conv || !start || !end || !z || !mask) return ARAH_E_BADARG;
+    launch_sample_depths(variant, n, &cfg, near_far, conv, start, end, nullptr, nullptr, nullptr, z, mask,
+                         reinterpret_cast<hipStream_t>(stream));
+    return check_launch();
 }
 
 // the density pre-pass of lazy shading over list[0 .. *count): sigma of every listed sample -> w.shaded, the samples with
@@ -5426,7 +5577,7 @@ static int tier_phase(const ArahFrame* f, const ArahSampling* cfg, const FrameDe
                           phase == 1 ? cfg->ev_canon : cfg->ev_canon2, list, cnt);
     if (rc) return rc;
     // phase 1: the witnesses at the head of the list are certified sigma = +0; phase 2: every sample is (tier.hpp)
-    hipLaunchKernelGGL(k_tier_finalize, dim3(grid_for(Q, 256)), dim3(256), 0, s, fd, list, (const int*)&cnt[0],
+    hipLaunchKernelGGL(k_tier_finalize, dim3(grid_for(Q, kTierWaves * 64)), dim3(kTierWaves * 64), 0, s, fd, list, (const int*)&cnt[0],
                        phase == 1 ? (const int*)&w.tcounts[TC_NWIT] : (const int*)&cnt[0], (const float*)w.q_err, w.o_pts, w.o_mask,
                        w.shaded, dens_list, &cnt[2]);
     if (phase == 1) {
@@ -5451,14 +5602,13 @@ static int render_tiers(const ArahFrame* f, const ArahSampling* cfg, Workspace& 
     TierStats* stats = &w.ctr->tier;
     hipMemsetAsync(tc, 0, sizeof(int) * TC_COUNT, s);
     hipMemsetAsync(w.o_mask, 0, (size_t)Q, s);
-    hipLaunchKernelGGL(k_sample_depths, dim3((n + 127) / 128), dim3(128), 0, s, n, S, cfg->n_near, cfg->n_far, near_far, conv,
-                       start, end, cfg->lin_steps, cfg->lin_near, cfg->lin_far, (const float*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr, w.o_z, w.q_smask);
+    // the depth samples are computed by the classifier's first pass (tier.hpp: wave_ray_depths), which writes w.o_z
+    const DepthArgs da = depth_args(cfg, near_far, start, end);
     const dim3 gt(min(2048, (n + kTierWaves - 1) / kTierWaves)), bt(kTierWaves * 64);
-    hipLaunchKernelGGL(k_tier_classify<0>, gt, bt, 0, s, n, S, rs, conv, (const float*)w.o_z, w.q_smask,
+    hipLaunchKernelGGL(k_tier_classify<0>, gt, bt, 0, s, n, S, rs, conv, da, w.o_z, w.q_smask,
                        (const OccInfo*)o.info, (const unsigned*)o.bits, (const uint8_t*)o.dist, w.listA, &tc[TC_N1], stats);
     hipMemcpyAsync(&tc[TC_NWIT], &tc[TC_N1], sizeof(int), hipMemcpyDeviceToDevice, s);   // the witnesses head the list
-    hipLaunchKernelGGL(k_tier_classify<1>, gt, bt, 0, s, n, S, rs, conv, (const float*)w.o_z, w.q_smask,
+    hipLaunchKernelGGL(k_tier_classify<1>, gt, bt, 0, s, n, S, rs, conv, da, w.o_z, w.q_smask,
                        (const OccInfo*)o.info, (const unsigned*)o.bits, (const uint8_t*)o.dist, w.listA, &tc[TC_N1], stats);
     // phase 1: surface rays, marked samples, witnesses
     int rc = tier_phase(f, cfg, fd, w, rs, Q, w.listA, &tc[TC_N1], w.listC, &tc[TC_NSHADE], 1, s);
@@ -5627,7 +5777,7 @@ int arah_tier_audit(const ArahFrame* f, const ArahSampling* cfg, const float* ca
                                 0, (int*)nullptr, a.o_pts, a.o_T, 1, &a.ctr->n_knn);
     rc = run_broyden3(fd, a, nullptr, CanonOut{a.o_pts, a.o_T, a.q_err}, Q, s, cfg->canon_kernel, nullptr, a.listA, &tc[0]);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_tier_finalize, dim3(grid_for(Q, 256)), dim3(256), 0, s, fd, (const int*)a.listA, (const int*)&tc[0],
+    hipLaunchKernelGGL(k_tier_finalize, dim3(grid_for(Q, kTierWaves * 64)), dim3(kTierWaves * 64), 0, s, fd, (const int*)a.listA, (const int*)&tc[0],
                        (const int*)&tc[5], (const float*)a.q_err, a.o_pts, a.o_mask, a.shaded, a.listC, &tc[3]);
     // density (the lazy-shading pre-pass's kernel) and the SDF value (the certificate's margin) of the listed samples
     launch_density(fd, a, a.o_pts, Q, (const int*)a.listC, (const int*)&tc[3], a.listB, &tc[4], s);

@@ -476,18 +476,114 @@ __device__ __forceinline__ void tier_flush_stats(const unsigned (&loc)[NS], unsi
     }
 }
 
+// ---- eval-mode depth samples, one wave per ray ---------------------------------------------------------------------------
+// What k_sample_depths (arah_hip.hip, the specification) computes without jitter, in k_tier_classify's layout: lane l holds
+// samples l and l + 64 of its wave's ray, so a ray's row of z leaves as one or two contiguous 256-byte stores -- the
+// thread-per-ray kernel's lanes write 4 * n_steps bytes apart, 12 times the payload in memory traffic.
+struct DepthArgs {
+    int n_near, n_far;
+    const float* near_far;   // [N][2]
+    const float* start;      // [N]
+    const float* end;        // [N]
+    const float *lin_s, *lin_near, *lin_far;
+};
+
+// zz[it], mk[it]: depth and mask byte of sample lane + 64 * it (undefined for samples >= S).  `surf` is the ray's conv flag
+// (wave-uniform), `row` this wave's own ARAH_MAX_STEPS floats of LDS.
+// A surface ray's first n_near + 1 + n_far samples are the merge of two non-decreasing runs, the far run first on ties
+// (k_sample_depths: vb <= va).  Lane e takes ELEMENT e of their concatenation and finds its place by counting:
+//   place(surf a) = a + #{b : far(b) <= surf(a)},   place(far b) = b + #{a : surf(a) < far(b)}
+// -- the stable merge's positions; the values are the shared depth_* expressions, so the bits are the serial kernel's.  The
+// counted run's table index is the same in every lane (scalar loads).  Places are < n_near + 1 + n_far whatever the tables hold.
+__device__ __forceinline__ void wave_ray_depths(const DepthArgs& d, int S, int ray, bool surf, int lane, float* row, float (&zz)[2],
+                                                uint8_t (&mk)[2]) {
+    const float st = d.start[ray], en = d.end[ray];
+    if (!surf || (d.n_near <= 0 && d.n_far <= 0)) {
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const int s = lane + it * 64;
+            zz[it] = s < S ? depth_uniform(st, en, d.lin_s[s]) : 0.f;
+            mk[it] = 1;
+        }
+        return;
+    }
+    const int nc = d.n_near + 1 + d.n_far;
+    const float base = depth_surf_base(st);
+    const float nb = d.near_far[ray * 2];
+    const float span = depth_far_span(st, nb);
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const int e = lane + it * 64;
+        if (e < nc) {
+            float v;
+            int place;
+            if (e <= d.n_near) {
+                v = depth_surf(base, d.lin_near[e]);
+                int c = 0;
+                for (int b = 0; b < d.n_far; ++b) c += depth_far(nb, span, d.lin_far[b]) <= v ? 1 : 0;
+                place = e + c;
+            } else {
+                const int b = e - d.n_near - 1;
+                v = depth_far(nb, span, d.lin_far[b]);
+                int c = 0;
+                for (int a = 0; a <= d.n_near; ++a) c += depth_surf(base, d.lin_near[a]) < v ? 1 : 0;
+                place = b + c;
+            }
+            row[place] = v;
+        }
+    }
+    wave_lds_handover();
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const int s = lane + it * 64;
+        if (s < nc) {
+            zz[it] = row[s];
+            mk[it] = 1;
+        } else {
+            zz[it] = s < S ? depth_uniform(st, en, d.lin_s[s]) : 0.f;
+            mk[it] = 0;
+        }
+    }
+    wave_lds_handover();   // the next ray's places are written after these reads
+}
+
+// the untiered eval path's sampler (sample_impl) and variant 1 of arah_sample_depths_debug
+__global__ __launch_bounds__(kTierWaves * 64) void k_sample_depths_wave(int n, int S, DepthArgs d, const uint8_t* __restrict__ conv,
+                                                             float* __restrict__ z, uint8_t* __restrict__ mask) {
+    __shared__ float sh_row[kTierWaves][ARAH_MAX_STEPS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int ray = blockIdx.x * kTierWaves + wave; ray < n; ray += gridDim.x * kTierWaves) {
+        float zz[2];
+        uint8_t mk[2];
+        wave_ray_depths(d, S, ray, conv[ray] != 0, lane, sh_row[wave], zz, mk);
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const int s = lane + it * 64;
+            if (s < S) {
+                const size_t q = (size_t)ray * S + s;
+                z[q] = zz[it];
+                mask[q] = mk[it];
+            }
+        }
+    }
+}
+
 // One wave per ray, one lane per depth sample (two for n_steps > 64).  state[q]: TS_* of every sample; phase-1 samples -> list1.
 // Two passes so that the WITNESSES head the list: they are the samples farthest from the body, the slow ones of Broyden's
 // iteration (up to 51 evaluations; near the body two) -- loop C's resident kernel takes the list front to back, and long jobs
 // first is what keeps its tail short.  PASS 0 classifies and appends the witnesses, PASS 1 appends the rest.
+// PASS 0 is also the tiered frame's SAMPLER: the wave computes its ray's depths in registers (wave_ray_depths), classifies from
+// them and writes z and the first state once -- no depth kernel, no mask array written and read back.
+// PASS 1 reads the states PASS 0 left and ignores `da` and `z`; its sh_row is one unused row.
 template <int PASS>
-__global__ __launch_bounds__(kTierWaves * 64) void k_tier_classify(int n, int S, RaySet rs, const uint8_t* __restrict__ conv,
-                                                        const float* __restrict__ z, uint8_t* __restrict__ state,
+__global__ __launch_bounds__(kTierWaves * 64) void k_tier_classify(int n, int S, RaySet rs, const uint8_t* __restrict__ conv, DepthArgs da,
+                                                        float* __restrict__ z, uint8_t* __restrict__ state,
                                                         const OccInfo* __restrict__ info, const unsigned* __restrict__ bits,
                                                         const uint8_t* __restrict__ dist, int* __restrict__ list1, int* count1,
                                                         TierStats* stats) {
     __shared__ int sh_base[kTierWaves + 1];
     __shared__ unsigned sh_stats[kTierWaves * 4];
+    __shared__ float sh_row[PASS == 0 ? kTierWaves : 1][ARAH_MAX_STEPS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const OccInfo oi = *info;
     unsigned loc[4] = {0u, 0u, 0u, 0u};   // rays, surface rays, witnesses, phase-1 samples
@@ -500,13 +596,17 @@ __global__ __launch_bounds__(kTierWaves * 64) void k_tier_classify(int n, int S,
         if (PASS == 0) {
             int dd[2] = {255, 255};
             bool any_marked = false;
+            float zz[2] = {0.f, 0.f};
+            uint8_t valid[2] = {0, 0};
+            if (live) wave_ray_depths(da, S, ray, surf, lane, sh_row[wave], zz, valid);
             for (int it = 0; it < 2; ++it) {
                 const int s = lane + it * 64;
                 if (live && s < S) {
                     const size_t q = (size_t)ray * S + s;
-                    if (state[q]) {
+                    z[q] = zz[it];
+                    if (valid[it]) {
                         int d;
-                        const bool mk = occ_lookup(oi, bits, dist, ray_point(rs, ray, z[q]), d);
+                        const bool mk = occ_lookup(oi, bits, dist, ray_point(rs, ray, zz[it]), d);
                         // a surface ray's samples are all evaluated (its delta chain needs every valid one), but those outside
                         // the fat body -- most of the n_far samples in front of the surface -- are CERTIFIED sigma = +0 like a
                         // witness: convergence only, no density pass (and they head the list with the witnesses)
@@ -582,10 +682,14 @@ __global__ __launch_bounds__(kTierWaves * 64) void k_tier_classify(int n, int S,
 // phase-2 sample lie outside the posed fat body, their density is +0 by the certificate that let their ray's other samples go
 // unevaluated, and only their convergence is asked for (the ray's mask, the delta chain and the (1 - alpha + 1e-7) factors of
 // a promoted ray): sigma = +0 is written, the SDF is not evaluated (29 % of the density pass's samples on the benchmark).
-__global__ __launch_bounds__(256) void k_tier_finalize(FrameDev fr, const int* __restrict__ list, const int* count,
+// The density list is appended per WORKGROUP (tier_block_base: one atomic for the 1024 samples of a batch): with append_ids' atomic
+// per wave the 1.4 M samples of phase 1 were 20 k atomics on one counter, and at ~90 / us those were the kernel's whole duration.
+__global__ __launch_bounds__(kTierWaves * 64) void k_tier_finalize(FrameDev fr, const int* __restrict__ list, const int* count,
                                                         const int* n_certified, const float* __restrict__ err_best,
                                                         float* __restrict__ pts, uint8_t* __restrict__ mask,
                                                         f32x4* __restrict__ shaded, int* __restrict__ dens_list, int* dens_count) {
+    __shared__ int sh_base[kTierWaves + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = *count;
     if ((int)(blockIdx.x * blockDim.x) >= n) return;
     const int n_cert = *n_certified;
@@ -607,7 +711,9 @@ __global__ __launch_bounds__(256) void k_tier_finalize(FrameDev fr, const int* _
                 ok = false;
             }
         }
-        append_ids(ok, q, dens_list, dens_count);
+        const unsigned long long m = __ballot(ok);
+        const int base = tier_block_base(__popcll(m), wave, lane, dens_count, sh_base);
+        if (ok) dens_list[base + __popcll(m & ((1ull << lane) - 1ull))] = q;
     }
 }
 

@@ -130,6 +130,7 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_skin_lbs_counted", "arah_marching_cubes_scratch_bytes", "arah_marching_cubes",
            "arah_marching_cubes_indexed_scratch_bytes", "arah_marching_cubes_indexed",
            "arah_occupancy_bytes", "arah_prepare_occupancy", "arah_occupancy_info", "arah_tier_debug", "arah_debug_samples",
+           "arah_sample_depths_debug", "arah_cell_clusters_debug",
            "arah_sdf_grid_band_scratch_bytes", "arah_sdf_grid_band", "arah_tier_audit_bytes", "arah_tier_audit",
            "arah_tier_audit_debug", "arah_occupancy_clear_box", "arah_render_maps_bytes", "arah_render_maps",
            "arah_query_posed_bytes", "arah_query_posed", "arah_sdf_grid_posed_bytes", "arah_sdf_grid_posed",
@@ -1037,6 +1038,40 @@ def shade_points(frame, ws, x_norm, T, dirs, cano_view_dirs=True, shade_engine=N
     _check(lib.arah_shade_points(C.byref(frame.handle), _ptr(x), _ptr(Tm), _ptr(d), C.c_int32(n), C.c_int32(int(bool(cano_view_dirs))),
                                  C.c_int32(eng), _ptr(rgbs), _ptr(sdfn), _ptr(buf), C.c_size_t(buf.numel()), _stream()), "arah_shade_points")
     return rgbs[:, :3], rgbs[:, 3], sdfn[:, 0], sdfn[:, 1:]
+
+
+def sample_depths_debug(variant, sampling, near_far, conv, start, end):
+    """Tests: (z [N,S] float32, mask [N,S] uint8), the eval-mode depth samples of N rays by the serial kernel (variant 0) or the
+    wave-per-ray one (variant 1); `sampling` is a Sampling (its n_steps / n_near / n_far and linspace tables)."""
+    dev = near_far.device
+    nf, st, en = _f32(near_far), _f32(start), _f32(end)
+    cv = conv.to(torch.uint8).contiguous()
+    n, S = int(st.shape[0]), int(sampling.n_steps)
+    z = torch.empty(n, S, device=dev)
+    mask = torch.empty(n, S, dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        _check(load_library().arah_sample_depths_debug(
+            C.c_int32(int(variant)), C.c_int32(n), C.c_int32(S), C.c_int32(int(sampling.n_near)), C.c_int32(int(sampling.n_far)),
+            _ptr(nf), _ptr(cv), _ptr(st), _ptr(en), _ptr(sampling.lin_steps), _ptr(sampling.lin_near), _ptr(sampling.lin_far),
+            _ptr(z), _ptr(mask), _stream(dev)), "arah_sample_depths_debug")
+    return z, mask
+
+
+# byte offsets of a body buffer's arrays (include/arah_hip.h: ARAH_BODY_OFF_*)
+BODY_OFF_SPHERES, BODY_OFF_GRID, BODY_OFF_CELLS, BODY_CELL_BYTES = 114688, 118784, 119040, 64
+
+
+def cell_clusters_debug(variant, body_buf):
+    """Tests: the candidate lists [n_cells, 64] uint8 of the grid and cluster spheres held in `body_buf` (BodyTables.buf), rebuilt
+    by the serial kernel (variant 0) or the wave-per-cell one (variant 1) into a buffer of their own."""
+    dev = body_buf.device
+    n_cells = int(body_buf[BODY_OFF_GRID:BODY_OFF_GRID + 48].view(torch.int32)[8].item())
+    cells = torch.zeros(n_cells, BODY_CELL_BYTES, dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        _check(load_library().arah_cell_clusters_debug(C.c_int32(int(variant)), _ptr(body_buf[BODY_OFF_GRID:]),
+                                                       _ptr(body_buf[BODY_OFF_SPHERES:]), _ptr(cells), _stream(dev)),
+               "arah_cell_clusters_debug")
+    return cells
 
 
 @_guarded

@@ -665,6 +665,25 @@ int arah_occupancy_clear_box(void* occ_buf, const float* h_lo, const float* h_hi
 int arah_debug_samples(void* workspace, size_t workspace_bytes, int32_t n_rays, int32_t n_steps, float* z, float* pts,
                        float* T, uint8_t* mask, float* shaded, uint8_t* state, void* stream);
 
+/* tests: two helper kernels of the frame exist twice, as a serial specification (variant 0) and as the cooperative kernel the
+ * frame runs (variant 1); both entries are pure functions of the caller's device buffers, and the variants agree bit for bit.
+ *
+ * arah_sample_depths_debug: the eval-mode (no jitter) depth samples of n rays -> z [n, n_steps], mask [n, n_steps];
+ * near_far [n,2], conv [n], start [n], end [n] as the tracer leaves them, lin_* as in ArahSampling.  Variant 1 is the function
+ * the tiered frame's classifier computes its depths with.
+ *
+ * arah_cell_clusters_debug: the per-cell candidate lists of the nearest-vertex search -> cells [n_cells][64] (byte 0: the
+ * count, or 255 when more than 63 clusters qualify; then the cluster ids in the order of their lower bounds).  grid and spheres
+ * are device pointers into a body buffer (arah_prepare_body; byte offsets ARAH_BODY_OFF_*) or buffers of the same layout. */
+#define ARAH_BODY_OFF_SPHERES 114688u /* [256][4] float: centre, radius */
+#define ARAH_BODY_OFF_GRID 118784u    /* origin[3], h, 1/h (float) | dims[3], n_cells, n_clusters, pad[2] (int32) */
+#define ARAH_BODY_OFF_CELLS 119040u   /* [<= 65536][64] uint8 */
+int arah_sample_depths_debug(int32_t variant, int32_t n_rays, int32_t n_steps, int32_t n_near, int32_t n_far,
+                             const float* near_far, const uint8_t* conv, const float* start, const float* end,
+                             const float* lin_steps, const float* lin_near, const float* lin_far, float* z, uint8_t* mask,
+                             void* stream);
+int arah_cell_clusters_debug(int32_t variant, const void* grid, const float* spheres, uint8_t* cells, void* stream);
+
 /* ---- posed-space queries (csrc/posed.hpp) ---------------------------------------------------------------------------------- */
 /* The value of the lattice / the sdf of a certified point: any positive value would do (marching cubes at level 0 only reads signs
  * there); metres. */
