@@ -1950,6 +1950,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_canon_solve(FrameDev fr, const 
 
 #include "mcubes.hpp"
 #include "meshcc.hpp"
+#include "meshsimp.hpp"
 #include "canon_wave.hpp"
 
 // explicit targets (arah_broyden3_lbs): file them where k_canon_solve expects them, in row 3 of the start transform
@@ -4103,6 +4104,132 @@ int arah_mesh_select(const int32_t* faces, int64_t n_faces, int64_t n_verts, con
                        (int*)nullptr, (const int*)fblk_base, (int*)faces_out, (int*)face_src);
     hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)faces_out, (const int*)counts + 1, F, 3);
     hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)face_src, (const int*)counts + 1, F, 1);
+    return check_launch();
+}
+
+// ---- simplification of indexed meshes by vertex clustering (csrc/meshsimp.hpp) ---------------------------------
+struct MsLayout {
+    size_t bitmap, wcount, wbase, vkey, sums, members, best, fslot, tkeys, trows, blk_count, blk_base, bytes;
+    long long n_words, n_slots;
+    int nbf;
+};
+
+static bool ms_sizes_ok(int64_t n_verts, int64_t n_faces, int64_t n_cells) {
+    return n_verts >= 0 && n_faces >= 0 && n_cells >= 1 && n_verts <= ((int64_t)1 << 26) && n_faces <= ((int64_t)1 << 28) &&
+           n_cells <= ((int64_t)1 << 27);
+}
+
+static MsLayout ms_layout(int64_t n_verts, int64_t n_faces, int64_t n_cells) {
+    MsLayout L{};
+    L.n_words = (n_cells + 31) / 32;
+    L.n_slots = 0;
+    if (n_faces > 0) {   // a power of two of at least 2 F slots: the table cannot fill
+        L.n_slots = 64;
+        while (L.n_slots < 2 * n_faces) L.n_slots <<= 1;
+    }
+    L.nbf = (int)((n_faces + kMsChunk - 1) / kMsChunk);
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off = align_up(off + bytes, 256);
+        return at;
+    };
+    L.bitmap = take((size_t)L.n_words * sizeof(unsigned));
+    L.wcount = take((size_t)L.n_words * sizeof(int));
+    L.wbase = take((size_t)L.n_words * sizeof(int));
+    L.vkey = take((size_t)n_verts * sizeof(int));
+    L.sums = take(3 * (size_t)n_verts * sizeof(long long));
+    L.members = take((size_t)n_verts * sizeof(int));
+    L.best = take((size_t)n_verts * sizeof(unsigned long long));
+    L.fslot = take((size_t)n_faces * sizeof(int));
+    L.tkeys = take((size_t)L.n_slots * sizeof(unsigned long long));
+    L.trows = take((size_t)L.n_slots * sizeof(int));
+    L.blk_count = take((size_t)L.nbf * sizeof(int));
+    L.blk_base = take((size_t)L.nbf * sizeof(int));
+    L.bytes = max(off, (size_t)256);
+    return L;
+}
+
+static int ms_grid(int64_t n) { return (int)min((int64_t)kMsMaxGrid, max((int64_t)1, (n + kMsThreads - 1) / kMsThreads)); }
+
+size_t arah_mesh_simplify_scratch_bytes(int64_t n_verts, int64_t n_faces, int64_t n_cells) {
+    if (!ms_sizes_ok(n_verts, n_faces, n_cells)) return 0;
+    return ms_layout(n_verts, n_faces, n_cells).bytes;
+}
+
+int arah_mesh_simplify(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float origin[3], float cell,
+                       const int32_t dims[3], double fix_scale, int32_t position, int32_t dedup, float* verts_out, int32_t* vert_src,
+                       int32_t* vert_map, int32_t* faces_out, int32_t* face_src, int32_t* counts, void* scratch, size_t scratch_bytes,
+                       void* stream) {
+    if (!origin || !dims || !counts || !scratch) return ARAH_E_BADARG;
+    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return ARAH_E_BADARG;
+    // two factors below 2^31 fit int64; once their product is at most 2^27, the third factor fits as well
+    if ((int64_t)dims[0] * dims[1] > ((int64_t)1 << 27)) return ARAH_E_BADARG;
+    const int64_t n_cells = (int64_t)dims[0] * dims[1] * dims[2];
+    if (!ms_sizes_ok(n_verts, n_faces, n_cells)) return ARAH_E_BADARG;
+    const float inv_cell = 1.0f / cell;
+    if (!(cell > 0.0f) || !std::isfinite(cell) || !std::isfinite(inv_cell)) return ARAH_E_BADARG;
+    if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2])) return ARAH_E_BADARG;
+    if (!(fix_scale > 0.0) || !std::isfinite(fix_scale)) return ARAH_E_BADARG;
+    if (position != 0 && position != 1) return ARAH_E_BADARG;
+    if ((n_verts > 0 && (!verts || !verts_out || !vert_src || !vert_map)) || (n_faces > 0 && (!faces || !faces_out || !face_src)))
+        return ARAH_E_BADARG;
+    const MsLayout L = ms_layout(n_verts, n_faces, n_cells);
+    if (scratch_bytes < L.bytes) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int V = (int)n_verts, F = (int)n_faces;
+    if (V == 0) {   // no vertex, so no cluster, and every face names a vertex that is not there
+        hipLaunchKernelGGL(k_ms_set_empty, dim3(1), dim3(64), 0, s, (int*)counts, F);
+        if (F > 0) {
+            hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)faces_out, (const int*)counts + 1, F, 3);
+            hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)face_src, (const int*)counts + 1, F, 1);
+        }
+        return check_launch();
+    }
+    MsGrid g;
+    for (int a = 0; a < 3; ++a) {
+        g.origin[a] = origin[a];
+        g.dims[a] = dims[a];
+    }
+    g.inv_cell = inv_cell;
+    g.scale = fix_scale;
+    char* base = reinterpret_cast<char*>(scratch);
+    unsigned* bitmap = reinterpret_cast<unsigned*>(base + L.bitmap);
+    int* wcount = reinterpret_cast<int*>(base + L.wcount);
+    int* wbase = reinterpret_cast<int*>(base + L.wbase);
+    int* vkey = reinterpret_cast<int*>(base + L.vkey);
+    long long* sums = reinterpret_cast<long long*>(base + L.sums);
+    int* members = reinterpret_cast<int*>(base + L.members);
+    unsigned long long* best = reinterpret_cast<unsigned long long*>(base + L.best);
+    int* fslot = reinterpret_cast<int*>(base + L.fslot);
+    unsigned long long* tkeys = reinterpret_cast<unsigned long long*>(base + L.tkeys);
+    int* trows = reinterpret_cast<int*>(base + L.trows);
+    int* blk_count = reinterpret_cast<int*>(base + L.blk_count);
+    int* blk_base = reinterpret_cast<int*>(base + L.blk_base);
+    const long long n_slots = dedup ? L.n_slots : 0;   // without dedup the table is neither cleared nor touched
+    hipLaunchKernelGGL(k_ms_init, dim3(ms_grid(max(max(L.n_words, (long long)V), n_slots))), dim3(kMsThreads), 0, s, bitmap, L.n_words,
+                       sums, members, best, V, tkeys, trows, n_slots, (int*)counts);
+    hipLaunchKernelGGL(k_ms_mark, dim3(ms_grid(V)), dim3(kMsThreads), 0, s, verts, V, g, vkey, bitmap);
+    hipLaunchKernelGGL(k_ms_popc, dim3(ms_grid(L.n_words)), dim3(kMsThreads), 0, s, (const unsigned*)bitmap, L.n_words, wcount);
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)wcount, (int)L.n_words, wbase, (int*)counts);
+    hipLaunchKernelGGL(k_ms_accum, dim3(ms_grid(V)), dim3(kMsThreads), 0, s, verts, V, g, (const int*)vkey, (const unsigned*)bitmap,
+                       (const int*)wbase, (int*)vert_map, sums, members);
+    hipLaunchKernelGGL(k_ms_pick, dim3(ms_grid(V)), dim3(kMsThreads), 0, s, verts, V, g, (const int*)vert_map, (const long long*)sums,
+                       (const int*)members, best);
+    hipLaunchKernelGGL(k_ms_finish, dim3(ms_grid(V)), dim3(kMsThreads), 0, s, verts, V, g, (int)position, (int)(dedup != 0),
+                       (const long long*)sums, (const int*)members, (const unsigned long long*)best, (int*)counts, verts_out,
+                       (int*)vert_src);
+    if (F == 0) return check_launch();
+    const int dd = dedup != 0;
+    hipLaunchKernelGGL(k_ms_classify, dim3(ms_grid(F)), dim3(kMsThreads), 0, s, (const int*)faces, F, V, (const int*)vert_map, dd, tkeys,
+                       trows, n_slots, fslot, (int*)counts);
+    hipLaunchKernelGGL((k_ms_compact<false>), dim3(L.nbf), dim3(kMsThreads), 0, s, (const int*)faces, F, (const int*)vert_map,
+                       (const int*)fslot, (const int*)trows, dd, blk_count, (const int*)nullptr, (int*)nullptr, (int*)nullptr,
+                       (int*)counts);
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)blk_count, L.nbf, blk_base, (int*)counts + 1);
+    hipLaunchKernelGGL((k_ms_compact<true>), dim3(L.nbf), dim3(kMsThreads), 0, s, (const int*)faces, F, (const int*)vert_map,
+                       (const int*)fslot, (const int*)trows, dd, (int*)nullptr, (const int*)blk_base, (int*)faces_out, (int*)face_src,
+                       (int*)counts);
     return check_launch();
 }
 

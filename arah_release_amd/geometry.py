@@ -6,7 +6,8 @@ The reference publishes such numbers but its tree holds no code for them (its RE
 tracker): PARITY UNPINNED, the definitions are this project's.  Also here: `load_mesh` for the two formats ground-truth meshes
 come in (.npz with `vertices` / `faces`, PLY with triangle faces), and `save_mesh`, which writes an indexed mesh in either;
 `mesh_components` / `clean_mesh`: the connected components of an indexed mesh and the removal of its floaters (DESIGN.md "Mesh
-components on the device").  Ground truth that is a SCAN -- a point cloud, with or without normals -- is scored through the exact
+components on the device"); `simplify_mesh`: fewer vertices and faces by vertex clustering on a grid (DESIGN.md "Simplifying meshes
+on the device").  Ground truth that is a SCAN -- a point cloud, with or without normals -- is scored through the exact
 nearest-point query hip.point_index / hip.point_nearest (DESIGN.md "Scoring against point clouds"): `PointCloud`, `nearest_points`,
 `load_points` / `save_points` / `load_geometry`, and F-scores at distance thresholds (`thresholds=` of `mesh_metrics`)."""
 import numpy as np
@@ -468,6 +469,144 @@ def clean_mesh(verts, faces, keep="largest", attributes=None):
         res = {"verts": verts.index_select(0, vert_src), "faces": faces_out[:nf].to(faces.dtype), "n_verts": nv, "n_tris": nf,
                "vert_src": vert_src,
                "removed": {"components": C - nc, "vertices": n_verts - nv, "faces": int(faces.shape[0]) - nf}}
+        for name, t in attributes.items():
+            res[name] = t.index_select(0, vert_src)
+    return res
+
+
+# ---- simplification by vertex clustering ------------------------------------------------------------------------------------------
+_SIMPLIFY_KEYS = ("cell", "resolution", "bounds", "position", "dedup", "drop_unreferenced")
+
+
+def check_simplify(simplify):
+    """Validate a `simplify` option of the model's mesh entries and return the keywords of `simplify_mesh` it stands for: a cell
+    length (a number > 0), or a dict of cell / resolution / bounds / position / dedup / drop_unreferenced.  ValueError for
+    anything else."""
+    import math
+    if isinstance(simplify, dict):
+        kw = dict(simplify)
+        bad = set(kw) - set(_SIMPLIFY_KEYS)
+        if bad:
+            raise ValueError("simplify: unknown keys %s (known: %s)" % (sorted(bad, key=str), ", ".join(_SIMPLIFY_KEYS)))
+    elif isinstance(simplify, (int, float, np.integer, np.floating)) and not isinstance(simplify, bool):
+        kw = {"cell": float(simplify)}
+    else:
+        raise ValueError("simplify must be a cell length or a dict of simplify_mesh keywords, got %r" % (simplify,))
+    cell, resolution = kw.get("cell"), kw.get("resolution")
+    if (cell is None) == (resolution is None):
+        raise ValueError("simplify: exactly one of cell and resolution is given, got cell=%r resolution=%r" % (cell, resolution))
+    if cell is not None and (isinstance(cell, bool) or not isinstance(cell, (int, float, np.integer, np.floating))
+                             or not math.isfinite(float(cell)) or not float(cell) > 0.0):
+        raise ValueError("simplify: cell must be a finite length > 0, got %r" % (cell,))
+    if resolution is not None and (isinstance(resolution, bool) or not isinstance(resolution, (int, np.integer)) or int(resolution) < 1):
+        raise ValueError("simplify: resolution must be an integer >= 1, got %r" % (resolution,))
+    if kw.get("position", "mean") not in ("mean", "member"):
+        raise ValueError("simplify: position must be 'mean' or 'member', got %r" % (kw["position"],))
+    return kw
+
+
+def simplify_grid_of(lo, hi, cell):
+    """The grid rule of `simplify_mesh`, in float32: origin = floor(lo / cell) cell, dims = floor((hi - origin) / cell) + 1.
+    -> (origin (3,) float32 array, dims list of ints).  ValueError when the quotients are not finite (a cell so small that they
+    overflow float32): such bounds and cell make no grid."""
+    lo, hi, c = np.asarray(lo, np.float32), np.asarray(hi, np.float32), np.float32(cell)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        origin = (np.floor(lo / c) * c).astype(np.float32)
+        dims = np.floor((hi - origin) / c).astype(np.float64) + 1.0
+    if not np.isfinite(origin).all() or not np.isfinite(dims).all():
+        raise ValueError("simplify_mesh: the bounds %r .. %r with cell %r make no grid" % (lo.tolist(), hi.tolist(), float(c)))
+    return origin, [int(x) for x in dims]
+
+
+def simplify_mesh(verts, faces, cell=None, resolution=None, bounds=None, position="mean", dedup=True, attributes=None,
+                  drop_unreferenced=True):
+    """Simplify an indexed mesh (verts (V,3), faces (F,3) integer ids) by vertex clustering: the vertices inside one cell of a
+    regular grid become one vertex, faces are renamed to cells, and the faces that collapse (two corners in one cell) or repeat
+    (dedup: the same three cells as an earlier face, in any orientation) go.  Decimation and welding by position in one step.
+
+        cell          the side of a cell, a length in the units of verts; or
+        resolution    the number of cells along the longest side of the bounds (exactly one of the two is given)
+        bounds        (lo, hi), three numbers each; default: the box of the vertices with finite coordinates
+        position      "mean": a cluster sits at the exact mean of its members; "member": at the member nearest to that mean -- a
+                      subset of the input, still on the extracted level set
+        drop_unreferenced   clusters that lost all their faces are removed (mesh_select with the "referenced" policy of clean_mesh)
+
+    The grid, in float32: origin = floor(lo / cell) cell, dims = floor((hi - origin) / cell) + 1; at most 2^27 cells.  A vertex
+    outside the bounds counts for the nearest cell; a vertex with a non-finite coordinate is invalid and takes its faces along.
+    -> dict of verts (V',3) float32, faces (F',3) in the dtype of `faces`, n_verts, n_tris, vert_src (V',) int64 (the member
+    that represents every new vertex, in the input's ids), removed = dict of vertices / faces_collapsed / faces_duplicate /
+    faces_invalid, cell (float), dims (tuple), and every tensor of the dict `attributes` (first dimension V) gathered by vert_src
+    -- never averaged.  On the GPU the clustering is arah_mesh_simplify and the removal arah_mesh_select; on the host their
+    tensor specifications.  Every decision is an integer's: the result does not depend on the order in which the device's
+    threads arrive, and the host's and the device's are equal bit for bit; the numbering of the vertices matters through the tie
+    rule alone (of members equally near the mean the lowest id represents the cluster, so "member" positions can differ there).  Host synchronisations: ONE (the sizes of the result), and one more
+    when `bounds` is left to the vertices' box.  ValueError when dedup meets more than 2^21 clusters: choose a larger cell, or
+    dedup=False."""
+    check_simplify({"cell": cell, "resolution": resolution, "position": position})
+    n_verts, faces = _mesh_args(verts, faces, "simplify_mesh")
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or not verts.dtype.is_floating_point:
+        raise ValueError("simplify_mesh: verts must be a floating-point (V, 3) tensor")
+    if verts.device != faces.device:
+        raise ValueError("simplify_mesh: verts live on %s, faces on %s" % (verts.device, faces.device))
+    attributes = dict(attributes or {})
+    reserved = ("verts", "faces", "n_verts", "n_tris", "vert_src", "removed", "cell", "dims")
+    for name, t in attributes.items():
+        if name in reserved:
+            raise ValueError("simplify_mesh: an attribute cannot be called %r" % (name,))
+        if not isinstance(t, torch.Tensor) or t.dim() < 1 or t.shape[0] != n_verts or t.device != verts.device:
+            raise ValueError("simplify_mesh: attribute %r must be a tensor with %d rows on %s" % (name, n_verts, verts.device))
+    backend, dev = _cc_backend(faces), verts.device
+    with torch.no_grad():
+        v32 = verts.detach().to(torch.float32).contiguous()
+        if bounds is None:
+            finite = torch.isfinite(v32).all(1, keepdim=True)
+            inf = torch.full_like(v32, float("inf"))
+            box = torch.stack([torch.where(finite, v32, inf).amin(0), torch.where(finite, v32, -inf).amax(0)]) if n_verts else None
+            lo, hi = box.tolist() if n_verts else ([0.0] * 3, [0.0] * 3)      # a host synchronisation
+            if lo[0] > hi[0]:                                                     # no finite vertex
+                lo, hi = [0.0] * 3, [0.0] * 3
+        else:
+            try:
+                lo, hi = ([float(x) for x in (b.tolist() if isinstance(b, torch.Tensor) else b)] for b in bounds)
+            except (TypeError, ValueError):
+                raise ValueError("simplify_mesh: bounds must be (lo, hi), three numbers each, got %r" % (bounds,))
+            if len(lo) != 3 or len(hi) != 3 or not all(np.isfinite(lo + hi)) or any(h < l for l, h in zip(lo, hi)):
+                raise ValueError("simplify_mesh: bounds must be finite with lo <= hi, got %r" % (bounds,))
+        lo, hi = np.asarray(lo, np.float32), np.asarray(hi, np.float32)
+        if cell is None:
+            side = np.float32((hi - lo).max())
+            cell = float(side / np.float32(int(resolution))) if side > 0 else 1.0      # a mesh without extent: one cell
+        cell = float(np.float32(cell))
+        if not np.isfinite(lo).all() or not np.isfinite(hi).all() or not cell > 0.0:
+            raise ValueError("simplify_mesh: the bounds %r .. %r with cell %r make no grid" % (lo.tolist(), hi.tolist(), cell))
+        origin, dims = simplify_grid_of(lo, hi, cell)
+        verts_out, vert_src, _, faces_out, _, counts = backend.mesh_simplify(v32, faces, origin.tolist(), cell, dims,
+                                                                             position=position, dedup=dedup)
+        F = int(faces.shape[0])
+        if drop_unreferenced:
+            # the guard rows of faces_out name vertex 0: they become invalid faces; a vertex is its own component here, kept
+            # when a kept face names it -- so every kept face stays
+            live = torch.arange(F, device=dev)[:, None] < counts[1]
+            named = torch.where(live, faces_out, torch.full_like(faces_out, -1))
+            keep = torch.zeros(n_verts + 1, dtype=torch.int32, device=dev)
+            keep[(named.reshape(-1) + 1).long()] = 1
+            own = torch.arange(n_verts, dtype=torch.int32, device=dev)
+            sel_src, _, faces_out, _, kept = backend.mesh_select(named, n_verts, own, keep[1:].contiguous())
+            sizes = torch.cat([counts, kept]).tolist()                           # the host synchronisation
+            nv, nf = sizes[6:]
+            pick = sel_src[:nv].long()
+            verts_out, vert_src = verts_out.index_select(0, pick), vert_src.long().index_select(0, pick)
+        else:
+            sizes = counts.tolist()                                              # the host synchronisation
+            nv, nf = sizes[:2]
+            verts_out, vert_src = verts_out[:nv], vert_src[:nv].long()
+        if sizes[5]:
+            raise ValueError("simplify_mesh: dedup holds three 21-bit cluster ids in a face's key, and this grid has %d occupied "
+                             "cells; choose a larger cell or dedup=False" % sizes[0])
+        res = {"verts": verts_out, "faces": faces_out[:nf].to(faces.dtype), "n_verts": nv, "n_tris": nf, "vert_src": vert_src,
+               "removed": {"vertices": n_verts - nv, "faces_collapsed": sizes[3], "faces_duplicate": sizes[4],
+                           "faces_invalid": sizes[2]},
+               "cell": cell, "dims": tuple(dims)}
         for name, t in attributes.items():
             res[name] = t.index_select(0, vert_src)
     return res

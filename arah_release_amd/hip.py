@@ -137,6 +137,7 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_image_metrics_bytes", "arah_image_metrics",
            "arah_mesh_index_bytes", "arah_mesh_index_build", "arah_mesh_closest", "arah_surface_metrics_bytes", "arah_surface_metrics", "arah_face_area_cumsum",
            "arah_mesh_components_scratch_bytes", "arah_mesh_components", "arah_mesh_select_scratch_bytes", "arah_mesh_select",
+           "arah_mesh_simplify_scratch_bytes", "arah_mesh_simplify",
            "arah_point_index_bytes", "arah_point_index_build", "arah_point_nearest", "arah_sample_scores_bytes", "arah_sample_scores"]
 
 _lib = None
@@ -185,6 +186,8 @@ def load_library():
     for name in ("arah_mesh_components_scratch_bytes", "arah_mesh_select_scratch_bytes"):
         getattr(lib, name).restype = C.c_size_t
         getattr(lib, name).argtypes = [C.c_int64, C.c_int64]
+    lib.arah_mesh_simplify_scratch_bytes.restype = C.c_size_t
+    lib.arah_mesh_simplify_scratch_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the symbol is missing
     _lib = lib
@@ -875,6 +878,46 @@ def mesh_select(faces, n_verts, labels, keep):
                                     _ptr(faces_out), _ptr(face_src), _ptr(counts), _ptr(scratch), C.c_size_t(scratch.numel()),
                                     _stream()), "arah_mesh_select")
     return vert_src, vert_map, faces_out, face_src, counts
+
+
+def mesh_simplify(verts, faces, origin, cell, dims, position="mean", dedup=True):
+    """Vertex clustering of an indexed mesh on a grid (arah_mesh_simplify, csrc/meshsimp.hpp): verts (V,3) float32 and faces (F,3)
+    integer ids on the GPU; origin (three numbers), cell and dims (three integers, at most 2^27 cells) on the host.  The vertices of
+    every occupied cell become one vertex, at the exact mean of the cell's members (position="mean") or at the member nearest to it
+    (position="member"); faces that name an invalid vertex, collapse or (dedup) repeat an earlier face's three clusters go.  ->
+    verts_out (V,3) float32, vert_src (V,) int32 the representative member of every cluster, vert_map (V,) int32 the cluster of
+    every vertex or -1, faces_out (F,3) int32, face_src (F,) int32, counts (6,) int32 = clusters, kept faces, invalid, collapsed,
+    duplicate faces, status (1: dedup with more than 2^21 clusters, no face kept).  Rows beyond the counts are zero.  All on the
+    device, no host synchronisation; the result is meshing.mesh_simplify(...) bit for bit."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    if position not in ("mean", "member"):
+        raise ValueError("mesh_simplify: position must be 'mean' or 'member', got %r" % (position,))
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise ValueError("mesh_simplify: verts must be a (V, 3) float32 tensor")
+    V = int(verts.shape[0])
+    f, _, F = _mesh_cc_args(faces, V, "mesh_simplify")
+    if verts.device != f.device:
+        raise ValueError("mesh_simplify: verts live on %s, faces on %s" % (verts.device, f.device))
+    if V > meshing.SIMPLIFY_MAX_VERTS or F > meshing.SIMPLIFY_MAX_FACES:
+        raise ValueError("mesh_simplify: at most 2^26 vertices and 2^28 faces, got %d and %d" % (V, F))
+    o, c, _, d, scale = meshing.simplify_grid(origin, cell, dims)
+    dev = f.device
+    v = verts.detach().contiguous()
+    with _on_device(dev):
+        scratch = _mesh_cc_buf(dev, int(lib.arah_mesh_simplify_scratch_bytes(V, F, d[0] * d[1] * d[2])))
+        verts_out = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        vert_src, vert_map = (torch.empty(V, dtype=torch.int32, device=dev) for _ in range(2))
+        faces_out = torch.empty(F, 3, dtype=torch.int32, device=dev)
+        face_src = torch.empty(F, dtype=torch.int32, device=dev)
+        counts = torch.empty(6, dtype=torch.int32, device=dev)
+        _check(lib.arah_mesh_simplify(_ptr(v), C.c_int64(V), _ptr(f), C.c_int64(F), (C.c_float * 3)(*o), C.c_float(c),
+                                      (C.c_int32 * 3)(*d), C.c_double(scale), C.c_int32(int(position == "member")),
+                                      C.c_int32(int(bool(dedup))), _ptr(verts_out), _ptr(vert_src), _ptr(vert_map), _ptr(faces_out),
+                                      _ptr(face_src), _ptr(counts), _ptr(scratch), C.c_size_t(scratch.numel()), _stream()),
+               "arah_mesh_simplify")
+    return verts_out, vert_src, vert_map, faces_out, face_src, counts
 
 
 def marching_cubes(sdf, level=0.0, cap=1 << 20):

@@ -281,6 +281,127 @@ def mesh_select(faces, n_verts, labels, keep):
     return vert_src.to(i32), vert_map.to(i32), faces_out.to(i32), face_src.to(i32), counts
 
 
+SIMPLIFY_MAX_CELLS = 1 << 27            # cells of a clustering grid
+SIMPLIFY_MAX_VERTS = 1 << 26            # vertices: 2^26 fixed-point coordinates below 2^36 sum below 2^62
+SIMPLIFY_MAX_FACES = 1 << 28            # faces: the duplicate table has at least twice as many slots
+SIMPLIFY_MAX_DEDUP_CLUSTERS = 1 << 21   # three sorted 21-bit cluster ids make the 64-bit key of a face
+SIMPLIFY_FIX_BITS = 36                  # fixed-point coordinates inside the grid lie in [0, 2^36]
+
+
+def simplify_grid(origin, cell, dims, what="mesh_simplify"):
+    """A clustering grid, checked: origin three finite numbers, cell a number whose float32 value and float32 reciprocal are
+    positive and finite, dims three integers >= 1 with at most 2^27 cells in all.  -> (origin as three float32 values, cell as a
+    float32 value, the float32 reciprocal, dims as ints, fix_scale = 2^(36 - e) with e = ceil(log2(max(dims) cell)) as a
+    float: a power of two, so that the fixed-point coordinates of a vertex inside the grid lie in [0, 2^36])."""
+    try:
+        o = [float(np.float32(float(x))) for x in (origin.tolist() if isinstance(origin, torch.Tensor) else origin)]
+        d = [int(x) for x in (dims.tolist() if isinstance(dims, torch.Tensor) else dims)]
+        whole = all(float(x) == int(x) for x in (dims.tolist() if isinstance(dims, torch.Tensor) else dims))
+        c = float(np.float32(float(cell)))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("%s: origin must be three numbers, cell a number, dims three integers" % what)
+    if len(o) != 3 or not all(math.isfinite(x) for x in o):
+        raise ValueError("%s: origin must be three finite numbers, got %r" % (what, origin))
+    inv = float(np.float32(1.0) / np.float32(c)) if c > 0.0 and math.isfinite(c) else float("inf")
+    if not math.isfinite(inv):
+        raise ValueError("%s: cell must be a positive float32 length with a finite reciprocal, got %r" % (what, cell))
+    if len(d) != 3 or not whole or min(d) < 1 or d[0] * d[1] * d[2] > SIMPLIFY_MAX_CELLS:
+        raise ValueError("%s: dims must be three integers >= 1 with at most 2^27 cells in all, got %r" % (what, dims))
+    m, e = math.frexp(max(d) * c)                  # max(d) c = m 2^e exactly (the product of two floats below 2^53), 0.5 <= m < 1
+    e = e - 1 if m == 0.5 else e                   # ceil(log2(.))
+    return o, c, inv, d, math.ldexp(1.0, SIMPLIFY_FIX_BITS - e)
+
+
+def mesh_simplify(verts, faces, origin, cell, dims, position="mean", dedup=True):
+    """Vertex clustering of an indexed mesh on a grid: verts (V,3) float32, faces (F,3) integer ids, the grid of `simplify_grid`.
+
+    Cell of a vertex, in float32: c = clamp(floor((v - origin) (1 / cell)), 0, dims - 1) per axis, key = cx + nx (cy + ny cz).  A
+    vertex with a non-finite coordinate is invalid and has no cell.  The clusters are the occupied cells, numbered 0 .. K - 1 in
+    ascending key.  Position of a cluster, exactly: q = llrint(clamp((double(v) - double(origin)) fix_scale, -2^36, 2^36)) per
+    member (the clamp only touches vertices outside the grid), S = sum q and n = the members in integers, mean = float32(
+    double(origin) + (double(S) / double(n)) / fix_scale).  Its representative: the member with the smallest d^2 = float32((dx dx
+    + dy dy) + dz dz), d = double(v) - double(mean), every operation rounded on its own; ties go to the lowest vertex id.
+
+    A face with an id outside [0, V) or an invalid vertex is dropped (n_invalid); the others are renamed to clusters, dropped as
+    collapsed when two of the three are equal, and with `dedup` dropped as duplicates when an earlier surviving face names the
+    same three clusters in any order.  With dedup and K > 2^21 the status is 1 and no face is kept (nor counted as a duplicate).
+
+    -> verts_out (V,3) float32: the clusters' means (position="mean") or representatives (position="member"); vert_src (V,)
+    int32: the representatives' ids; vert_map (V,) int32: the cluster of every vertex or -1; faces_out (F,3) int32: the kept
+    faces in their original order and orientation, as cluster ids; face_src (F,) int32: their old rows; counts (6,) int32: K,
+    kept faces, n_invalid, collapsed, duplicates, status.  Rows beyond K and beyond the kept faces are zero.  Clusters that lose
+    all their faces stay.  Plain tensor operations on the tensors' device: the specification of arah_mesh_simplify
+    (csrc/meshsimp.hpp), and what runs for meshes on the host."""
+    if position not in ("mean", "member"):
+        raise ValueError("mesh_simplify: position must be 'mean' or 'member', got %r" % (position,))
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise ValueError("mesh_simplify: verts must be a (V, 3) float32 tensor")
+    V = int(verts.shape[0])
+    faces, _, in_range = _cc_faces(faces, V, "mesh_simplify")
+    if faces.device != verts.device:
+        raise ValueError("mesh_simplify: verts live on %s, faces on %s" % (verts.device, faces.device))
+    F = int(faces.shape[0])
+    if V > SIMPLIFY_MAX_VERTS or F > SIMPLIFY_MAX_FACES:
+        raise ValueError("mesh_simplify: at most 2^26 vertices and 2^28 faces, got %d and %d" % (V, F))
+    o, c, inv, d, scale = simplify_grid(origin, cell, dims)
+    dev, i32, f64 = verts.device, torch.int32, torch.float64
+    verts = verts.detach()
+    o32 = torch.tensor(o, dtype=torch.float32, device=dev)
+    valid = torch.isfinite(verts).all(1)
+    # cells: one float32 subtraction, one float32 multiplication
+    t = torch.floor((verts - o32) * torch.tensor(inv, dtype=torch.float32, device=dev))
+    ci = torch.where(valid[:, None], t.clamp(0.0, float(SIMPLIFY_MAX_CELLS)), torch.zeros_like(t)).long()
+    ci = torch.minimum(ci, torch.tensor([x - 1 for x in d], device=dev))      # in integers: dims - 1 need not be a float32
+    key = ci[:, 0] + d[0] * (ci[:, 1] + d[1] * ci[:, 2])
+    ids_v = torch.nonzero(valid)[:, 0]
+    _, inverse = torch.unique(key[ids_v], sorted=True, return_inverse=True)
+    K = int(inverse.max()) + 1 if ids_v.shape[0] else 0
+    vert_map = torch.full((V,), -1, dtype=torch.int64, device=dev)
+    vert_map[ids_v] = inverse
+    # exact means
+    o64 = o32.to(f64)
+    q = torch.clamp((verts[ids_v].to(f64) - o64) * scale, -2.0 ** SIMPLIFY_FIX_BITS, 2.0 ** SIMPLIFY_FIX_BITS).round().long()
+    S = torch.zeros(K, 3, dtype=torch.int64, device=dev).index_add_(0, inverse, q)
+    n = torch.bincount(inverse, minlength=K)
+    mean = (o64 + (S.to(f64) / n.to(f64)[:, None]) / scale).float()
+    # representatives: the smallest (bits(d2) << 32) | id per cluster
+    dd = verts[ids_v].to(f64) - mean[inverse].to(f64)
+    d2 = ((dd[:, 0] * dd[:, 0] + dd[:, 1] * dd[:, 1]) + dd[:, 2] * dd[:, 2]).float()
+    packed = (d2.view(i32).long() << 32) | ids_v
+    best = torch.full((K,), 2 ** 63 - 1, dtype=torch.int64, device=dev).scatter_reduce(0, inverse, packed, "amin")
+    src = best & 0xFFFFFFFF
+    vert_src = torch.zeros(V, dtype=torch.int64, device=dev)
+    vert_src[:K] = src
+    verts_out = torch.zeros(V, 3, dtype=torch.float32, device=dev)
+    verts_out[:K] = mean if position == "mean" else verts[src]
+    # faces
+    ok = in_range.clone()
+    ok[in_range] = valid[faces[in_range]].all(1)
+    rows = torch.nonzero(ok)[:, 0]
+    cl = vert_map[faces[rows]]
+    apart = (cl[:, 0] != cl[:, 1]) & (cl[:, 1] != cl[:, 2]) & (cl[:, 0] != cl[:, 2])
+    n_invalid, n_collapsed = F - int(rows.shape[0]), int(rows.shape[0]) - int(apart.sum())
+    rows, cl = rows[apart], cl[apart]
+    status = int(bool(dedup) and K > SIMPLIFY_MAX_DEDUP_CLUSTERS)
+    n_dup = 0
+    if status:
+        rows, cl = rows[:0], cl[:0]
+    elif dedup and rows.shape[0]:
+        s = torch.sort(cl, dim=1).values
+        _, which = torch.unique(s[:, 0] | (s[:, 1] << 21) | (s[:, 2] << 42), return_inverse=True)
+        first = torch.full((int(which.max()) + 1,), F, dtype=torch.int64, device=dev).scatter_reduce(0, which, rows, "amin")
+        first_seen = first[which] == rows
+        n_dup = int(rows.shape[0]) - int(first_seen.sum())
+        rows, cl = rows[first_seen], cl[first_seen]
+    kept = int(rows.shape[0])
+    faces_out = torch.zeros(F, 3, dtype=torch.int64, device=dev)
+    faces_out[:kept] = cl
+    face_src = torch.zeros(F, dtype=torch.int64, device=dev)
+    face_src[:kept] = rows
+    counts = torch.tensor([K, kept, n_invalid, n_collapsed, n_dup, status], dtype=i32, device=dev)
+    return verts_out, vert_src.to(i32), vert_map.to(i32), faces_out.to(i32), face_src.to(i32), counts
+
+
 def face_normals(tri):
     """Unit right-hand normals of a triangle soup (F,3,3) (pytorch3d Meshes.faces_normals_packed)."""
     n = torch.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0], dim=1)

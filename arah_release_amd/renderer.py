@@ -899,7 +899,7 @@ class MetaAvatarRender(nn.Module):
                 "points_hat": r["points_hat"].reshape(*shape, 3), "weights": r["weights"].reshape(*shape, 24),
                 "converged": (r["state"] == 1).reshape(shape), "state": r["state"].reshape(shape)}
 
-    def posed_mesh(self, inputs, n_side=256, method="lattice", bounds=None, indexed=False, clean=None):
+    def posed_mesh(self, inputs, n_side=256, method="lattice", bounds=None, indexed=False, clean=None, simplify=None):
         """A triangle soup of the posed body of frame `inputs` in world metres.  method="lattice": the zero level set of the posed
         SDF (hip.sdf_grid_posed, only the band around the occupancy bitmap's marked voxels unless ARAH_POSED_MESH_BAND=0, then
         hip.marching_cubes) -- the surface the renderer sees, self-contact included.  method="skinned": the reference's points_bar
@@ -912,12 +912,19 @@ class MetaAvatarRender(nn.Module):
         tris, and verts[faces] is the soup of the default call bit for bit; "skinned" then skins V vertices instead of 3 F
         corners.  clean (indexed=True only; None: nothing changes): a `keep` policy of geometry.clean_mesh ("largest", a face
         count, a share of the largest component's faces, "referenced") -- the mesh is geometry.clean_mesh of the uncleaned call's,
-        floaters dropped on the device, and vert_src and removed come with it.  Eval only."""
+        floaters dropped on the device, and vert_src and removed come with it.  simplify (indexed=True only; None: nothing
+        changes): a cell length in metres or a dict of geometry.simplify_mesh keywords -- the mesh is geometry.simplify_mesh of
+        the unsimplified call's (after clean), clustered on the device; vert_src, removed, cell and dims are then simplify_mesh's.
+        Eval only."""
         from . import geometry, meshing
         if clean is not None:
             geometry.check_keep(clean)
             if not indexed:
                 raise ValueError("posed_mesh: clean needs indexed=True (components are defined by shared vertex ids)")
+        if simplify is not None:
+            simplify = geometry.check_simplify(simplify)
+            if not indexed:
+                raise ValueError("posed_mesh: simplify needs indexed=True (clustering renames shared vertex ids)")
         frame, ws = self._posed_frame(inputs, "posed_mesh")
         if method not in ("lattice", "skinned"):
             raise ValueError("method must be 'lattice' or 'skinned', got %r" % (method,))
@@ -944,6 +951,8 @@ class MetaAvatarRender(nn.Module):
                 res = {"verts": verts[:V], "faces": faces[:F], "n_verts": V, "n_tris": F, "box": box, "counts": counts}
                 if clean is not None:
                     res.update(geometry.clean_mesh(res["verts"], res["faces"], keep=clean))
+                if simplify is not None:
+                    res.update(geometry.simplify_mesh(res["verts"], res["faces"], **simplify))
                 return res
             if method == "skinned":
                 cap = meshing.MC_DEFAULT_CAP
@@ -967,7 +976,7 @@ class MetaAvatarRender(nn.Module):
                 n = int(n_dev.item())
             return {"tris": hip.lattice_to_world(tris[:n], box), "n_tris": n, "box": box, "counts": counts}
 
-    def canonical_mesh(self, inputs, n_side=256, attributes=(), view_dirs=None, clean=None):
+    def canonical_mesh(self, inputs, n_side=256, attributes=(), view_dirs=None, clean=None, simplify=None):
         """The canonical body of frame `inputs` as an indexed mesh, the reference's create_mesh_vertices_and_faces
         (utils/sdf_meshing.py:13-114): the zero level set of the canonical SDF on the n_side^3 lattice (hip.sdf_grid_band, then
         hip.marching_cubes_indexed).  -> dict of verts (V,3) normalised canonical coordinates in [-1,1]^3, faces (F,3) int32,
@@ -986,7 +995,12 @@ class MetaAvatarRender(nn.Module):
         evaluated, so a dropped vertex costs no network evaluation, and vert_src (the kept vertices' ids in the uncleaned mesh)
         and removed come with the result.  With view_dirs (V,3), V is the cleaned mesh's.
 
-        Eval only, GPU only; one host synchronisation (the mesh's size), one more with clean."""
+        simplify (None: nothing changes): a cell length in the normalised coordinates or a dict of geometry.simplify_mesh
+        keywords; applied after clean and BEFORE the attributes are evaluated: the networks run on the small mesh, at its new
+        positions, and vert_src, removed, cell and dims are simplify_mesh's (ids into the cleaned mesh).  V is then the simplified
+        mesh's.
+
+        Eval only, GPU only; one host synchronisation (the mesh's size), one more with clean, simplify_mesh's with simplify."""
         from . import geometry, meshing
         names = ("weights", "verts_posed", "normal", "color")
         bad = set(attributes) - set(names)
@@ -994,6 +1008,8 @@ class MetaAvatarRender(nn.Module):
             raise ValueError("canonical_mesh: unknown attributes %s (known: %s)" % (sorted(bad), ", ".join(names)))
         if clean is not None:
             geometry.check_keep(clean)
+        if simplify is not None:
+            simplify = geometry.check_simplify(simplify)
         frame, ws = self._posed_frame(inputs, "canonical_mesh")
         with torch.no_grad():
             verts, faces = meshing.indexed_mesh(meshing.canonical_lattice(frame, ws, n_side), 0.0)
@@ -1001,6 +1017,9 @@ class MetaAvatarRender(nn.Module):
             res = {"verts": verts, "faces": faces, "n_verts": V, "n_tris": int(faces.shape[0])}
             if clean is not None:
                 res = geometry.clean_mesh(verts, faces, keep=clean)
+                verts, faces, V = res["verts"].contiguous(), res["faces"], res["n_verts"]
+            if simplify is not None:
+                res.update(geometry.simplify_mesh(verts, faces, **simplify))
                 verts, faces, V = res["verts"].contiguous(), res["faces"], res["n_verts"]
             if not attributes:
                 return res

@@ -33,6 +33,7 @@
  *   arah_marching_cubes_indexed   the same call's (verts, faces) result, utils/sdf_meshing.py:95-114: shared vertices
  *   arah_mesh_components /  (none: the reference writes the extracted mesh as it comes; connected components of an indexed mesh
  *   arah_mesh_select        by shared vertex ids, and the order-preserving selection of some of them: floater removal)
+ *   arah_mesh_simplify      (none: vertex clustering of an indexed mesh on a grid: decimation and welding by position)
  *   arah_rasterize          pytorch3d MeshRasterizer (pix_to_face) as used at metaavatar_render/models/__init__.py:232-276
  *   arah_shade_train_*      get_rbg_value_vol_sdf with self.training: per-sample forward and backward
  *                           renderer/implicit_differentiable_renderer.py:291-361, diff_operators.py:39-50
@@ -324,6 +325,29 @@ size_t arah_mesh_select_scratch_bytes(int64_t n_verts, int64_t n_faces);
 int arah_mesh_select(const int32_t* faces, int64_t n_faces, int64_t n_verts, const int32_t* labels, const int32_t* keep,
                      int32_t* vert_src, int32_t* vert_map, int32_t* faces_out, int32_t* face_src, int32_t* counts, void* scratch,
                      size_t scratch_bytes, void* stream);
+/* Simplification of an indexed mesh by vertex clustering on a grid (csrc/meshsimp.hpp).  verts [n_verts][3], faces [n_faces][3]
+ * vertex ids; the grid: h_origin (HOST float[3], finite), cell > 0 with a finite float32 reciprocal, h_dims (HOST int32[3], each
+ * >= 1, at most 2^27 cells in all).  Cell of a vertex, in float32: c = clamp(floor((v - origin) (1 / cell)), 0, dims - 1) per
+ * axis, key = cx + nx (cy + ny cz); a vertex with a non-finite coordinate is invalid.  The clusters are the occupied cells in
+ * ascending key.  Mean of a cluster: the exact integer sum of llrint(clamp((double(v) - double(origin)) fix_scale, -2^36, 2^36))
+ * over its members, divided by their number and by fix_scale, plus origin, rounded to float32; fix_scale is a power of two,
+ * 2^(36 - ceil(log2(max(dims) cell))).  Representative: the member with the smallest float32 squared distance to the mean
+ * (evaluated in double, one rounding per operation), ties to the lowest id.  -> verts_out [n_verts][3]: the means (position 0) or
+ * the representatives' coordinates (position 1); vert_src [n_verts]: the representatives; vert_map [n_verts]: the cluster of
+ * every vertex, or -1; faces_out [n_faces][3], face_src [n_faces]: the faces that survive, as cluster ids and old rows, in their
+ * original order and orientation; counts (device int32[6]) = clusters K, kept faces, faces with an id outside [0, n_verts) or an
+ * invalid vertex, faces collapsed (two of the three clusters equal), duplicates (dedup != 0: an earlier surviving face names the
+ * same three clusters in any order), status.  Status 1: dedup with K > 2^21 (the ids do not fit the 64-bit key of a face): no
+ * face is kept and none counted as a duplicate.  Rows between a count and the array's length are ZERO (vert_map has none).
+ * Integer atomics only: the result is unique.  n_verts <= 2^26, n_faces <= 2^28, otherwise ARAH_E_BADARG without a launch, as
+ * for any other argument out of range, and a scratch size of 0; scratch: arah_mesh_simplify_scratch_bytes(n_verts, n_faces,
+ * n_cells) device bytes, 256-byte aligned.  Empty inputs still write counts; pointers of empty arrays may be NULL.  No host
+ * synchronisation, no allocation. */
+size_t arah_mesh_simplify_scratch_bytes(int64_t n_verts, int64_t n_faces, int64_t n_cells);
+int arah_mesh_simplify(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float h_origin[3], float cell,
+                       const int32_t h_dims[3], double fix_scale, int32_t position, int32_t dedup, float* verts_out,
+                       int32_t* vert_src, int32_t* vert_map, int32_t* faces_out, int32_t* face_src, int32_t* counts, void* scratch,
+                       size_t scratch_bytes, void* stream);
 /* raw canonical x_hat [P,3] -> d x_bar / d x_hat [P,3,3] */
 int arah_skin_jacobian(const ArahFrame* h_frame, const float* x_hat, int32_t n_pts, float* jac,
                        void* workspace, size_t workspace_bytes, void* stream);
