@@ -1951,6 +1951,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_canon_solve(FrameDev fr, const 
 #include "mcubes.hpp"
 #include "meshcc.hpp"
 #include "meshsimp.hpp"
+#include "meshadj.hpp"
 #include "canon_wave.hpp"
 
 // explicit targets (arah_broyden3_lbs): file them where k_canon_solve expects them, in row 3 of the start transform
@@ -4230,6 +4231,118 @@ int arah_mesh_simplify(const float* verts, int64_t n_verts, const int32_t* faces
     hipLaunchKernelGGL((k_ms_compact<true>), dim3(L.nbf), dim3(kMsThreads), 0, s, (const int*)faces, F, (const int*)vert_map,
                        (const int*)fslot, (const int*)trows, dd, (int*)nullptr, (const int*)blk_base, (int*)faces_out, (int*)face_src,
                        (int*)counts);
+    return check_launch();
+}
+
+// ---- adjacency of indexed meshes, per-vertex normals, umbrella smoothing (csrc/meshadj.hpp) -----------------------------------
+struct MaLayout {
+    size_t deg, cursor, vf_raw, nb_raw, nb_sorted, bytes;
+};
+
+static bool ma_sizes_ok(int64_t n_verts, int64_t n_faces) {
+    return n_verts >= 0 && n_faces >= 0 && n_verts <= (int64_t)INT32_MAX && n_faces <= ((int64_t)1 << 28);
+}
+
+static MaLayout ma_layout(int64_t n_verts, int64_t n_faces) {
+    MaLayout L{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off = align_up(off + bytes, 256);
+        return at;
+    };
+    L.deg = take((size_t)n_verts * sizeof(int));
+    L.cursor = take((size_t)n_verts * sizeof(int));
+    L.vf_raw = take(3 * (size_t)n_faces * sizeof(unsigned));
+    L.nb_raw = take(6 * (size_t)n_faces * sizeof(unsigned));
+    L.nb_sorted = take(6 * (size_t)n_faces * sizeof(unsigned));
+    L.bytes = off > 256 ? off : (size_t)256;   // in size_t throughout: the largest mesh needs more than 2^32 bytes
+    return L;
+}
+
+static int ma_grid(int64_t n) { return (int)min((int64_t)kMaMaxGrid, max((int64_t)1, (n + kMaThreads - 1) / kMaThreads)); }
+
+size_t arah_mesh_adjacency_scratch_bytes(int64_t n_verts, int64_t n_faces) {
+    if (!ma_sizes_ok(n_verts, n_faces)) return 0;
+    return ma_layout(n_verts, n_faces).bytes;
+}
+
+int arah_mesh_adjacency(const int32_t* faces, int64_t n_faces, int64_t n_verts, int32_t* vf_start, int32_t* vf, int32_t* nbr_start,
+                        int32_t* nbr, int32_t* nbr_out, int32_t* nbr_in, uint8_t* vert_flags, int32_t* counts, void* scratch,
+                        size_t scratch_bytes, void* stream) {
+    if (!ma_sizes_ok(n_verts, n_faces) || !vf_start || !nbr_start || !counts || !scratch) return ARAH_E_BADARG;
+    if ((n_faces > 0 && (!faces || !vf || !nbr || !nbr_out || !nbr_in)) || (n_verts > 0 && !vert_flags)) return ARAH_E_BADARG;
+    const MaLayout L = ma_layout(n_verts, n_faces);
+    if (scratch_bytes < L.bytes) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int V = (int)n_verts, F = (int)n_faces;
+    char* base = reinterpret_cast<char*>(scratch);
+    int* deg = reinterpret_cast<int*>(base + L.deg);
+    int* cursor = reinterpret_cast<int*>(base + L.cursor);
+    unsigned* vf_raw = reinterpret_cast<unsigned*>(base + L.vf_raw);
+    unsigned* nb_raw = reinterpret_cast<unsigned*>(base + L.nb_raw);
+    unsigned* nb_sorted = reinterpret_cast<unsigned*>(base + L.nb_sorted);
+    // an empty mesh runs the same launches over nothing: the scans write vf_start[V] = nbr_start[V] = 0
+    hipLaunchKernelGGL(k_ma_init, dim3(ma_grid(V)), dim3(kMaThreads), 0, s, deg, cursor, V, (int*)counts);
+    if (F > 0 && V > 0)
+        hipLaunchKernelGGL(k_ma_count, dim3(ma_grid(F)), dim3(kMaThreads), 0, s, (const int*)faces, F, V, deg, (int*)counts);
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)deg, V, (int*)vf_start, (int*)vf_start + V);
+    if (F > 0 && V > 0) {
+        hipLaunchKernelGGL(k_ma_fill, dim3(ma_grid(F)), dim3(kMaThreads), 0, s, (const int*)faces, F, V, (const int*)vf_start, cursor,
+                           vf_raw, nb_raw);
+        hipLaunchKernelGGL(k_ma_sort_short, dim3(ma_grid(V)), dim3(kMaThreads), 0, s, (const int*)vf_start, V, (const unsigned*)vf_raw,
+                           (unsigned*)vf, (const unsigned*)nb_raw, nb_sorted);
+        hipLaunchKernelGGL(k_ma_sort_long, dim3(min(V, kMaLongGrid)), dim3(kMaThreads), 0, s, (const int*)vf_start, V,
+                           (const unsigned*)vf_raw, (unsigned*)vf, (const unsigned*)nb_raw, nb_sorted);
+    }
+    if (V > 0)
+        hipLaunchKernelGGL((k_ma_nbr<false>), dim3(ma_grid(V)), dim3(kMaThreads), 0, s, (const int*)vf_start, V, (const unsigned*)nb_sorted,
+                           deg, (const int*)nullptr, (int*)nullptr, (int*)nullptr, (int*)nullptr, (unsigned char*)nullptr,
+                           (int*)counts);
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)deg, V, (int*)nbr_start, (int*)nbr_start + V);
+    if (V > 0)
+        hipLaunchKernelGGL((k_ma_nbr<true>), dim3(ma_grid(V)), dim3(kMaThreads), 0, s, (const int*)vf_start, V, (const unsigned*)nb_sorted,
+                           (int*)nullptr, (const int*)nbr_start, (int*)nbr, (int*)nbr_out, (int*)nbr_in, (unsigned char*)vert_flags,
+                           (int*)counts);
+    if (F > 0) {
+        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)vf, (const int*)vf_start + V, 3 * F, 1);
+        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)nbr, (const int*)nbr_start + V, 6 * F, 1);
+        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)nbr_out, (const int*)nbr_start + V, 6 * F, 1);
+        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)nbr_in, (const int*)nbr_start + V, 6 * F, 1);
+    }
+    hipLaunchKernelGGL(k_ma_finish, dim3(1), dim3(64), 0, s, (int*)counts, V);
+    return check_launch();
+}
+
+int arah_mesh_vertex_normals(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int32_t* vf_start,
+                             const int32_t* vf, double* normal_sum, float* normals, void* stream) {
+    if (!ma_sizes_ok(n_verts, n_faces) || !vf_start) return ARAH_E_BADARG;
+    if ((n_verts > 0 && (!verts || !normal_sum || !normals)) || (n_faces > 0 && (!faces || !vf))) return ARAH_E_BADARG;
+    if (n_verts == 0) return ARAH_OK;
+    hipLaunchKernelGGL(k_ma_normals, dim3(ma_grid(n_verts)), dim3(kMaThreads), 0, reinterpret_cast<hipStream_t>(stream), verts,
+                       (int)n_verts, (const int*)faces, (int)n_faces, (const int*)vf_start, (const int*)vf, normal_sum, normals);
+    return check_launch();
+}
+
+int arah_mesh_smooth(const float* verts, int64_t n_verts, const int32_t* nbr_start, const int32_t* nbr, const uint8_t* vert_flags,
+                     int32_t n_steps, const float factors[2], int32_t pin, float* tmp, float* verts_out, void* stream) {
+    if (n_verts < 0 || n_verts > (int64_t)INT32_MAX || n_steps < 0 || !factors || !nbr_start) return ARAH_E_BADARG;
+    if (!std::isfinite(factors[0]) || !std::isfinite(factors[1])) return ARAH_E_BADARG;
+    if (n_verts > 0 && (!verts || !verts_out || !vert_flags || (n_steps > 1 && !tmp))) return ARAH_E_BADARG;
+    if (n_verts == 0) return ARAH_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int V = (int)n_verts;
+    if (n_steps == 0) {
+        hipLaunchKernelGGL(k_ma_copy, dim3(ma_grid(3 * n_verts)), dim3(kMaThreads), 0, s, verts, 3 * (long long)n_verts, verts_out);
+        return check_launch();
+    }
+    const float* src = verts;
+    for (int32_t i = 0; i < n_steps; ++i) {   // the last step writes verts_out, the one before tmp, and so on back
+        float* dst = ((n_steps - 1 - i) & 1) ? tmp : verts_out;
+        hipLaunchKernelGGL(k_ma_smooth, dim3(ma_grid(V)), dim3(kMaThreads), 0, s, src, V, (const int*)nbr_start, (const int*)nbr,
+                           (const unsigned char*)vert_flags, (double)factors[i & 1], (int)(pin != 0), dst);
+        src = dst;
+    }
     return check_launch();
 }
 

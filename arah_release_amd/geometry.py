@@ -7,9 +7,13 @@ tracker): PARITY UNPINNED, the definitions are this project's.  Also here: `load
 come in (.npz with `vertices` / `faces`, PLY with triangle faces), and `save_mesh`, which writes an indexed mesh in either;
 `mesh_components` / `clean_mesh`: the connected components of an indexed mesh and the removal of its floaters (DESIGN.md "Mesh
 components on the device"); `simplify_mesh`: fewer vertices and faces by vertex clustering on a grid (DESIGN.md "Simplifying meshes
-on the device").  Ground truth that is a SCAN -- a point cloud, with or without normals -- is scored through the exact
+on the device"); `mesh_adjacency` / `mesh_topology` / `vertex_normals` / `smooth_mesh`: who is adjacent to whom, whether a mesh is
+watertight, the mesh's own normals, and Laplacian / Taubin smoothing (DESIGN.md "Adjacency, normals and smoothing on the device").
+Ground truth that is a SCAN -- a point cloud, with or without normals -- is scored through the exact
 nearest-point query hip.point_index / hip.point_nearest (DESIGN.md "Scoring against point clouds"): `PointCloud`, `nearest_points`,
 `load_points` / `save_points` / `load_geometry`, and F-scores at distance thresholds (`thresholds=` of `mesh_metrics`)."""
+import collections
+
 import numpy as np
 import torch
 
@@ -610,6 +614,98 @@ def simplify_mesh(verts, faces, cell=None, resolution=None, bounds=None, positio
         for name, t in attributes.items():
             res[name] = t.index_select(0, vert_src)
     return res
+
+
+# ---- adjacency, topology, per-vertex normals, smoothing -------------------------------------------------------------------------
+MeshAdjacency = collections.namedtuple("MeshAdjacency", ("vf_start", "vf", "nbr_start", "nbr", "nbr_out", "nbr_in", "vert_flags",
+                                                         "counts"))
+MeshAdjacency.__doc__ = """The arrays of `mesh_adjacency`, on the mesh's device: vf_start (V+1,) / vf (3F,) the CSR of the valid
+faces incident to every vertex (ids ascending); nbr_start (V+1,) / nbr (6F,) the CSR of its unique neighbours (ids ascending) with
+nbr_out / nbr_in (6F,) the faces traversing v->n / n->v; vert_flags (V,) uint8 (1 boundary, 2 non-manifold, 4 no neighbour); counts
+(8,) int32 (valid faces, edges, boundary, non-manifold and misoriented edges, the largest valence, isolated vertices, Euler)."""
+
+_SMOOTH_KEYS = ("iterations", "lamb", "mu", "method", "boundary")
+
+
+def mesh_adjacency(verts_or_n_verts, faces):
+    """Who is adjacent to whom in an indexed mesh (hip.mesh_adjacency on the GPU, meshing.mesh_adjacency on the host): faces (F,3)
+    integer ids, and the vertices (V,3) or just their number.  A face with an id out of range or a repeated id is skipped.  -> a
+    MeshAdjacency of arrays that stay on the mesh's device; no host synchronisation on the GPU.  Build it once and hand it to
+    `vertex_normals` and `smooth_mesh` of the same mesh."""
+    n_verts, faces = _mesh_args(verts_or_n_verts, faces, "mesh_adjacency")
+    with torch.no_grad():
+        return MeshAdjacency(*_cc_backend(faces).mesh_adjacency(faces, n_verts))
+
+
+def mesh_topology(verts_or_n_verts, faces):
+    """The topology of an indexed mesh from `mesh_adjacency`, as Python numbers: -> dict of faces (the valid ones), edges,
+    boundary_edges (one face), nonmanifold_edges (three or more), misoriented_edges (two faces that traverse the edge in the same
+    direction), isolated_vertices (no neighbour), max_valence, euler = (V - isolated_vertices) - edges + faces, skipped_faces (an
+    id out of range or repeated), manifold (no non-manifold edge) and watertight (at least one face and no boundary, non-manifold or
+    misoriented edge).  One host synchronisation (the counts)."""
+    adj = mesh_adjacency(verts_or_n_verts, faces)
+    c = adj.counts.tolist()                                                     # the host synchronisation
+    return {"faces": c[0], "edges": c[1], "boundary_edges": c[2], "nonmanifold_edges": c[3], "misoriented_edges": c[4],
+            "isolated_vertices": c[6], "max_valence": c[5], "euler": c[7], "skipped_faces": int(faces.shape[0]) - c[0],
+            "manifold": c[3] == 0, "watertight": c[0] > 0 and c[2] == 0 and c[3] == 0 and c[4] == 0}
+
+
+def _smooth_args(verts, faces, adjacency, what):
+    n_verts, faces = _mesh_args(verts, faces, what)
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or not verts.dtype.is_floating_point:
+        raise ValueError("%s: verts must be a floating-point (V, 3) tensor" % what)
+    if verts.device != faces.device:
+        raise ValueError("%s: verts live on %s, faces on %s" % (what, verts.device, faces.device))
+    return verts.detach().to(torch.float32).contiguous(), faces, (None if adjacency is None else tuple(adjacency))
+
+
+def vertex_normals(verts, faces, adjacency=None):
+    """Unit per-vertex normals (V,3) float32 of an indexed mesh from the mesh itself, pytorch3d's verts_normals_packed: the sum of
+    the incident faces' cross products (area-weighted face normals), normalised; (0, 0, 0) for a vertex without a valid face or
+    with a sum of length 0.  Good for any mesh -- a loaded scan, a simplified or smoothed one --, unlike the SDF gradient
+    canonical_mesh(attributes=("normal",)) gives.  adjacency: a `mesh_adjacency` of the same mesh built earlier, or None.
+    hip.vertex_normals on the GPU, meshing.vertex_normals on the host, equal bit for bit."""
+    v32, faces, adjacency = _smooth_args(verts, faces, adjacency, "vertex_normals")
+    with torch.no_grad():
+        return _cc_backend(faces).vertex_normals(v32, faces, adjacency=adjacency)[1]
+
+
+def smooth_mesh(verts, faces, iterations=10, lamb=0.5, mu=-0.53, method="taubin", boundary="pin", adjacency=None):
+    """Smooth an indexed mesh with the umbrella operator: every step moves a vertex towards (lamb > 0) or away from (mu < 0) the
+    mean of its neighbours, p + f (mean - p), uniform weights.  method="taubin" (Taubin 1995, "A signal processing approach to
+    fair surface design"): an iteration is a lamb step and a mu step, a low-pass filter that does not shrink the mesh the way
+    method="laplacian" (lamb steps only) does.  boundary="pin" keeps the vertices of boundary and non-manifold edges where they
+    are, "free" moves them like the others.  lamb in (0, 1], mu in [-1.1, 0), iterations >= 0.  -> verts (V,3) float32; faces,
+    the vertex count and the order stay, so every per-vertex attribute stays valid.  Vertices with a non-finite coordinate stay
+    and are left out of their neighbours' means.  adjacency: a `mesh_adjacency` of the same mesh built earlier, or None.
+    hip.mesh_smooth on the GPU (no host synchronisation), meshing.mesh_smooth on the host, equal bit for bit."""
+    from . import meshing
+    meshing.check_smooth_args(iterations, lamb, mu, method, boundary, "smooth_mesh")
+    v32, faces, adjacency = _smooth_args(verts, faces, adjacency, "smooth_mesh")
+    with torch.no_grad():
+        return _cc_backend(faces).mesh_smooth(v32, faces, iterations, lamb=lamb, mu=mu, method=method, boundary=boundary,
+                                              adjacency=adjacency)
+
+
+def check_smooth(smooth):
+    """Validate a `smooth` option of the model's mesh entries and return the keywords of `smooth_mesh` it stands for: None
+    (nothing), a number of iterations (an integer >= 0), or a dict of iterations / lamb / mu / method / boundary.  ValueError for
+    anything else."""
+    from . import meshing
+    if smooth is None:
+        return None
+    if isinstance(smooth, dict):
+        kw = dict(smooth)
+        bad = set(kw) - set(_SMOOTH_KEYS)
+        if bad:
+            raise ValueError("smooth: unknown keys %s (known: %s)" % (sorted(bad, key=str), ", ".join(_SMOOTH_KEYS)))
+    elif isinstance(smooth, (int, np.integer)) and not isinstance(smooth, bool):
+        kw = {"iterations": int(smooth)}
+    else:
+        raise ValueError("smooth must be None, a number of iterations or a dict of smooth_mesh keywords, got %r" % (smooth,))
+    meshing.check_smooth_args(kw.get("iterations", 10), kw.get("lamb", 0.5), kw.get("mu", -0.53), kw.get("method", "taubin"),
+                              kw.get("boundary", "pin"), "smooth")
+    return kw
 
 
 # ---- ground-truth files -------------------------------------------------------------------------------------------------

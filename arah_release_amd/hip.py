@@ -138,6 +138,7 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_mesh_index_bytes", "arah_mesh_index_build", "arah_mesh_closest", "arah_surface_metrics_bytes", "arah_surface_metrics", "arah_face_area_cumsum",
            "arah_mesh_components_scratch_bytes", "arah_mesh_components", "arah_mesh_select_scratch_bytes", "arah_mesh_select",
            "arah_mesh_simplify_scratch_bytes", "arah_mesh_simplify",
+           "arah_mesh_adjacency_scratch_bytes", "arah_mesh_adjacency", "arah_mesh_vertex_normals", "arah_mesh_smooth",
            "arah_point_index_bytes", "arah_point_index_build", "arah_point_nearest", "arah_sample_scores_bytes", "arah_sample_scores"]
 
 _lib = None
@@ -183,7 +184,7 @@ def load_library():
     for name in ("arah_point_index_bytes", "arah_sample_scores_bytes"):
         getattr(lib, name).restype = C.c_size_t
         getattr(lib, name).argtypes = [C.c_int32]
-    for name in ("arah_mesh_components_scratch_bytes", "arah_mesh_select_scratch_bytes"):
+    for name in ("arah_mesh_components_scratch_bytes", "arah_mesh_select_scratch_bytes", "arah_mesh_adjacency_scratch_bytes"):
         getattr(lib, name).restype = C.c_size_t
         getattr(lib, name).argtypes = [C.c_int64, C.c_int64]
     lib.arah_mesh_simplify_scratch_bytes.restype = C.c_size_t
@@ -918,6 +919,97 @@ def mesh_simplify(verts, faces, origin, cell, dims, position="mean", dedup=True)
                                       _ptr(face_src), _ptr(counts), _ptr(scratch), C.c_size_t(scratch.numel()), _stream()),
                "arah_mesh_simplify")
     return verts_out, vert_src, vert_map, faces_out, face_src, counts
+
+
+def mesh_adjacency(faces, n_verts):
+    """Adjacency of the indexed mesh with faces (F,3) integer vertex ids (on the GPU) over n_verts vertices (arah_mesh_adjacency,
+    csrc/meshadj.hpp): -> (vf_start (V+1,), vf (3F,), nbr_start (V+1,), nbr (6F,), nbr_out (6F,), nbr_in (6F,)) int32, vert_flags (V,)
+    uint8, counts (8,) int32 as meshing.mesh_adjacency describes them, and equal to it bit for bit.  All on the device, no host
+    synchronisation.  The scratch is kept per (device, stream) and grows on demand."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    f, V, F = _mesh_cc_args(faces, n_verts, "mesh_adjacency")
+    if F > meshing.ADJACENCY_MAX_FACES:
+        raise ValueError("mesh_adjacency: at most 2^28 faces, got %d" % F)
+    dev, i32 = f.device, torch.int32
+    with _on_device(dev):
+        scratch = _mesh_cc_buf(dev, int(lib.arah_mesh_adjacency_scratch_bytes(V, F)))
+        vf_start, nbr_start = (torch.empty(V + 1, dtype=i32, device=dev) for _ in range(2))
+        vf = torch.empty(3 * F, dtype=i32, device=dev)
+        nbr, nbr_out, nbr_in = (torch.empty(6 * F, dtype=i32, device=dev) for _ in range(3))
+        flags = torch.empty(V, dtype=torch.uint8, device=dev)
+        counts = torch.empty(8, dtype=i32, device=dev)
+        _check(lib.arah_mesh_adjacency(_ptr(f), C.c_int64(F), C.c_int64(V), _ptr(vf_start), _ptr(vf), _ptr(nbr_start), _ptr(nbr),
+                                       _ptr(nbr_out), _ptr(nbr_in), _ptr(flags), _ptr(counts), _ptr(scratch),
+                                       C.c_size_t(scratch.numel()), _stream()), "arah_mesh_adjacency")
+    return vf_start, vf, nbr_start, nbr, nbr_out, nbr_in, flags, counts
+
+
+def _mesh_adj_args(verts, faces, adjacency, what):
+    """verts (V,3) float32 and faces on one GPU, and the eight arrays of mesh_adjacency (built here when None): -> (verts
+    contiguous, faces int32 contiguous, V, F, adjacency as contiguous device arrays)."""
+    from . import meshing
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise ValueError("%s: verts must be a (V, 3) float32 tensor" % what)
+    V = int(verts.shape[0])
+    f, _, F = _mesh_cc_args(faces, V, what)
+    if verts.device != f.device:
+        raise ValueError("%s: verts live on %s, faces on %s" % (what, verts.device, f.device))
+    if F > meshing.ADJACENCY_MAX_FACES:
+        raise ValueError("%s: at most 2^28 faces, got %d" % (what, F))
+    if adjacency is None:
+        adjacency = mesh_adjacency(f, V)
+    else:
+        adjacency = tuple(adjacency)
+        shapes = ((V + 1,), (3 * F,), (V + 1,), (6 * F,), (6 * F,), (6 * F,), (V,), (8,))
+        if len(adjacency) != 8 or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != s or t.device != f.device
+                                      or t.dtype != (torch.uint8 if i == 6 else torch.int32)
+                                      for i, (t, s) in enumerate(zip(adjacency, shapes))):
+            raise ValueError("%s: adjacency must be the eight arrays of mesh_adjacency of these faces and vertices, on %s"
+                             % (what, f.device))
+        adjacency = tuple(t.contiguous() for t in adjacency)
+    return verts.detach().contiguous(), f, V, F, adjacency
+
+
+def vertex_normals(verts, faces, adjacency=None):
+    """Per-vertex normals of an indexed mesh from the mesh itself (arah_mesh_vertex_normals): verts (V,3) float32 and faces (F,3)
+    integer ids on the GPU, adjacency: `mesh_adjacency` of them, or None to build it here.  -> normal_sum (V,3) float64 (the
+    incident faces' cross products summed in ascending face id), normals (V,3) float32 (unit, or zero); meshing.vertex_normals bit
+    for bit.  A gather over the sorted CSR: no atomics, no host synchronisation."""
+    require_gpu()
+    lib = load_library()
+    v, f, V, F, adj = _mesh_adj_args(verts, faces, adjacency, "vertex_normals")
+    dev = v.device
+    with _on_device(dev):
+        normal_sum = torch.empty(V, 3, dtype=torch.float64, device=dev)
+        normals = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        _check(lib.arah_mesh_vertex_normals(_ptr(v), C.c_int64(V), _ptr(f), C.c_int64(F), _ptr(adj[0]), _ptr(adj[1]),
+                                            _ptr(normal_sum), _ptr(normals), _stream()), "arah_mesh_vertex_normals")
+    return normal_sum, normals
+
+
+def mesh_smooth(verts, faces, iterations, lamb=0.5, mu=-0.53, method="taubin", boundary="pin", adjacency=None):
+    """Laplacian / Taubin umbrella smoothing of an indexed mesh (arah_mesh_smooth): verts (V,3) float32 and faces (F,3) integer ids
+    on the GPU, the keywords of meshing.mesh_smooth, adjacency: `mesh_adjacency` of them, or None to build it here.  ->
+    verts_out (V,3) float32, meshing.mesh_smooth bit for bit.  All steps inside one C call, between two buffers; no atomics, no
+    host synchronisation."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    factors, pin = meshing.check_smooth_args(iterations, lamb, mu, method, boundary)
+    v, f, V, F, adj = _mesh_adj_args(verts, faces, adjacency, "mesh_smooth")
+    dev = v.device
+    n_steps = int(iterations) * len(factors)
+    if n_steps > 2 ** 31 - 1:
+        raise ValueError("mesh_smooth: too many steps, got %d iterations" % iterations)
+    with _on_device(dev):
+        out = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        tmp = torch.empty(V, 3, dtype=torch.float32, device=dev) if n_steps > 1 else None
+        _check(lib.arah_mesh_smooth(_ptr(v), C.c_int64(V), _ptr(adj[2]), _ptr(adj[3]), _ptr(adj[6]), C.c_int32(n_steps),
+                                    (C.c_float * 2)(factors[0], factors[-1]), C.c_int32(int(pin)), _ptr(tmp), _ptr(out), _stream()),
+               "arah_mesh_smooth")
+    return out
 
 
 def marching_cubes(sdf, level=0.0, cap=1 << 20):

@@ -402,6 +402,194 @@ def mesh_simplify(verts, faces, origin, cell, dims, position="mean", dedup=True)
     return verts_out, vert_src.to(i32), vert_map.to(i32), faces_out.to(i32), face_src.to(i32), counts
 
 
+ADJACENCY_MAX_FACES = 1 << 28           # 6 F neighbour entries fit an int32
+ADJACENCY_FIELDS = ("vf_start", "vf", "nbr_start", "nbr", "nbr_out", "nbr_in", "vert_flags", "counts")
+
+
+def _csr_start(rows, V, dev):
+    """(V+1,) int32 starts of the CSR whose entries lie in the rows `rows` (sorted or not)."""
+    start = torch.zeros(V + 1, dtype=torch.int64, device=dev)
+    start[1:] = torch.cumsum(torch.bincount(rows, minlength=V), 0)
+    return start.to(torch.int32)
+
+
+def mesh_adjacency(faces, n_verts):
+    """Who is adjacent to whom in an indexed mesh: faces (F,3) integer ids over V = n_verts vertices, F <= 2^28.  A face is VALID
+    when its three ids lie in [0, V) and are pairwise different; the others are skipped.  A valid face (a, b, c) traverses the
+    directed edges a->b, b->c, c->a.  -> a tuple of
+
+        vf_start (V+1,), vf (3F,) int32     CSR of the valid faces incident to every vertex, face ids ascending within a vertex;
+                                            rows from vf_start[V] on are zero
+        nbr_start (V+1,), nbr (6F,) int32   CSR of the UNIQUE neighbours of every vertex, ids ascending
+        nbr_out, nbr_in (6F,) int32         for the entry (v, n): the valid faces traversing v->n, and n->v; rows from
+                                            nbr_start[V] on are zero (nbr's too)
+        vert_flags (V,) uint8               bit 0: the vertex has an edge with exactly one face; bit 1: an edge with three or more
+                                            faces; bit 2: no neighbour
+        counts (8,) int32                   valid faces; undirected edges E; edges with one face (boundary); with >= 3 faces (non-
+                                            manifold); with exactly two faces that traverse it in the same direction (misoriented);
+                                            the largest number of neighbours of a vertex; vertices with no neighbour; the Euler
+                                            characteristic (V - counts[6]) - E + counts[0]
+
+    Integers throughout: the result is unique.  Plain tensor operations on the tensor's device: the specification of
+    arah_mesh_adjacency (csrc/meshadj.hpp), and what runs for meshes on the host."""
+    faces, V, in_range = _cc_faces(faces, n_verts, "mesh_adjacency")
+    dev, F, i32 = faces.device, int(faces.shape[0]), torch.int32
+    if F > ADJACENCY_MAX_FACES:
+        raise ValueError("mesh_adjacency: at most 2^28 faces, got %d" % F)
+    valid = in_range & (faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 0] != faces[:, 2])
+    rows = torch.nonzero(valid)[:, 0]
+    fv = faces[rows]                                                            # (Fv,3)
+    n_valid = int(rows.shape[0])
+    # incident faces: the corners sorted by (vertex, face); a valid face names a vertex once, so the keys are unique
+    key = torch.sort(fv.reshape(-1) * max(F, 1) + rows.repeat_interleave(3)).values
+    vf = torch.zeros(3 * F, dtype=torch.int64, device=dev)
+    vf[:3 * n_valid] = key % max(F, 1)
+    vf_start = _csr_start(key // max(F, 1), V, dev)
+    # neighbours: every directed edge s->d is an "out" of the entry (s, d) and an "in" of the entry (d, s)
+    s, d = fv.reshape(-1), fv[:, [1, 2, 0]].reshape(-1)
+    W = max(V, 1)
+    ekey, which = torch.unique(torch.cat([s * W + d, d * W + s]), sorted=True, return_inverse=True)
+    n_ent = int(ekey.shape[0])
+    one, zero = torch.ones_like(s), torch.zeros_like(s)
+    out = torch.zeros(n_ent, dtype=torch.int64, device=dev).index_add_(0, which, torch.cat([one, zero]))
+    inn = torch.zeros(n_ent, dtype=torch.int64, device=dev).index_add_(0, which, torch.cat([zero, one]))
+    ev, en = ekey // W, ekey % W
+    nbr, nbr_out, nbr_in = (torch.zeros(6 * F, dtype=torch.int64, device=dev) for _ in range(3))
+    nbr[:n_ent], nbr_out[:n_ent], nbr_in[:n_ent] = en, out, inn
+    nbr_start = _csr_start(ev, V, dev)
+    tot = out + inn
+    valence = torch.bincount(ev, minlength=V)
+    flags = torch.zeros(V, dtype=torch.int64, device=dev)
+    flags[ev[tot == 1]] |= 1
+    flags[ev[tot >= 3]] |= 2
+    flags[valence == 0] |= 4
+    up = en > ev                                                                # every undirected edge once
+    n_edges, isolated = int(up.sum()), int((valence == 0).sum())
+    counts = torch.tensor([n_valid, n_edges, int((up & (tot == 1)).sum()), int((up & (tot >= 3)).sum()),
+                           int((up & (tot == 2) & (out != 1)).sum()), int(valence.max()) if V else 0, isolated,
+                           (V - isolated) - n_edges + n_valid], dtype=i32, device=dev)
+    return vf_start, vf.to(i32), nbr_start, nbr.to(i32), nbr_out.to(i32), nbr_in.to(i32), flags.to(torch.uint8), counts
+
+
+def _adjacency_of(faces, n_verts, adjacency, what):
+    """The eight arrays of `mesh_adjacency`, built here or taken from the caller (checked for their shapes only)."""
+    if adjacency is None:
+        return mesh_adjacency(faces, n_verts)
+    adjacency = tuple(adjacency)
+    F = int(faces.shape[0])
+    shapes = ((n_verts + 1,), (3 * F,), (n_verts + 1,), (6 * F,), (6 * F,), (6 * F,), (n_verts,), (8,))
+    if len(adjacency) != 8 or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != s for t, s in zip(adjacency, shapes)):
+        raise ValueError("%s: adjacency must be the eight arrays of mesh_adjacency of these faces and vertices" % what)
+    return adjacency
+
+
+def _mesh_verts(verts, faces, what):
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise ValueError("%s: verts must be a (V, 3) float32 tensor" % what)
+    V = int(verts.shape[0])
+    faces, _, in_range = _cc_faces(faces, V, what)
+    if faces.device != verts.device:
+        raise ValueError("%s: verts live on %s, faces on %s" % (what, verts.device, faces.device))
+    if int(faces.shape[0]) > ADJACENCY_MAX_FACES:
+        raise ValueError("%s: at most 2^28 faces, got %d" % (what, int(faces.shape[0])))
+    return verts.detach(), faces, V, in_range
+
+
+def vertex_normals(verts, faces, adjacency=None):
+    """Per-vertex normals of an indexed mesh from the mesh itself, pytorch3d's verts_normals_packed: the area-weighted sum of the
+    incident faces' cross products.  verts (V,3) float32, faces (F,3) integer ids, adjacency: `mesh_adjacency` of them, or None.
+
+    For vertex v its incident valid faces are walked in ascending id.  A face with a non-finite corner contributes nothing; the
+    others n_f = (p1 - p0) x (p2 - p0), corners widened to float64, every subtraction, product and difference rounded on its own.
+    acc starts at 0 and takes acc = acc + n_f in that order.  -> normal_sum (V,3) float64 = acc, normals (V,3) float32 =
+    float32(acc / sqrt((ax ax + ay ay) + az az)), (0, 0, 0) when that length is 0 or not finite.  The ordered sum is a loop over
+    k < the most incident faces of a padded gather (adding 0.0 for the padding is exact).  The specification of
+    arah_mesh_vertex_normals (csrc/meshadj.hpp), and what runs for meshes on the host."""
+    verts, faces, V, _ = _mesh_verts(verts, faces, "vertex_normals")
+    vf_start, vf = _adjacency_of(faces, V, adjacency, "vertex_normals")[:2]
+    dev, f64, F = verts.device, torch.float64, int(faces.shape[0])
+    acc = torch.zeros(V, 3, dtype=f64, device=dev)
+    if V == 0 or F == 0:
+        return acc, acc.float()
+    p = verts.to(f64)[faces.clamp(0, V - 1)]                                    # (F,3,3); rows of skipped faces are never read
+    a, b = p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]
+    nf = torch.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2],
+                      a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], dim=1)
+    nf = torch.where(torch.isfinite(p).all(2).all(1)[:, None], nf, torch.zeros_like(nf))
+    start = vf_start.long()
+    first, deg = start[:-1], start[1:] - start[:-1]
+    vfl = vf.long()
+    for k in range(int(deg.max())):
+        has = k < deg
+        f = vfl[(first + k).clamp(max=3 * F - 1)]
+        acc = acc + torch.where(has[:, None], nf[f], torch.zeros_like(acc))
+    length = torch.sqrt((acc[:, 0] * acc[:, 0] + acc[:, 1] * acc[:, 1]) + acc[:, 2] * acc[:, 2])
+    ok = torch.isfinite(length) & (length > 0)
+    unit = acc / torch.where(ok, length, torch.ones_like(length))[:, None]
+    return acc, torch.where(ok[:, None], unit, torch.zeros_like(unit)).float()
+
+
+def check_smooth_args(iterations, lamb, mu, method, boundary, what="mesh_smooth"):
+    """The arguments of `mesh_smooth`, checked: -> (the steps' factors as float32 values widened to Python floats, one per
+    step of an iteration; pin as a bool)."""
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or int(iterations) < 0:
+        raise ValueError("%s: iterations must be an integer >= 0, got %r" % (what, iterations))
+    for name, x in (("lamb", lamb), ("mu", mu)):
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not math.isfinite(float(x)):
+            raise ValueError("%s: %s must be a finite number, got %r" % (what, name, x))
+    if not 0.0 < float(lamb) <= 1.0:
+        raise ValueError("%s: lamb must lie in (0, 1], got %r" % (what, lamb))
+    if not -1.1 <= float(mu) < 0.0:
+        raise ValueError("%s: mu must lie in [-1.1, 0), got %r" % (what, mu))
+    if method not in ("taubin", "laplacian"):
+        raise ValueError("%s: method must be 'taubin' or 'laplacian', got %r" % (what, method))
+    if boundary not in ("pin", "free"):
+        raise ValueError("%s: boundary must be 'pin' or 'free', got %r" % (what, boundary))
+    lam32, mu32 = float(np.float32(float(lamb))), float(np.float32(float(mu)))
+    return ((lam32, mu32) if method == "taubin" else (lam32,)), boundary == "pin"
+
+
+def mesh_smooth(verts, faces, iterations, lamb=0.5, mu=-0.53, method="taubin", boundary="pin", adjacency=None):
+    """Umbrella smoothing of an indexed mesh: verts (V,3) float32, faces (F,3) integer ids, adjacency: `mesh_adjacency` of them, or
+    None.  One STEP with the factor f (the float32 value of lamb or mu, widened to float64): a vertex moves when it is finite, is
+    not pinned and has a finite neighbour; s = the float64 sum of its finite unique neighbours in ascending id, m their number,
+    new = float32(p + f (s / m - p)) in float64, every operation rounded on its own.  All other vertices are copied bit for
+    bit.  A step reads the previous step's positions only.  method="taubin": an iteration is a lamb step and then a mu step
+    (Taubin 1995: the second, negative step undoes the shrinkage of the first); "laplacian": a lamb step only.  boundary="pin":
+    the vertices with vert_flags bit 0 or 1 (on a boundary or a non-manifold edge) never move; "free": they move like the others.
+    lamb in (0, 1], mu in [-1.1, 0), iterations >= 0.  -> verts_out (V,3) float32; faces, the vertex count and the order stay.
+    The specification of arah_mesh_smooth (csrc/meshadj.hpp), and what runs for meshes on the host."""
+    factors, pin = check_smooth_args(iterations, lamb, mu, method, boundary)
+    verts, faces, V, _ = _mesh_verts(verts, faces, "mesh_smooth")
+    adjacency = _adjacency_of(faces, V, adjacency, "mesh_smooth")
+    nbr_start, nbr, flags = adjacency[2], adjacency[3], adjacency[6]
+    cur = verts.clone()
+    F = int(faces.shape[0])
+    if V == 0 or F == 0 or int(iterations) == 0:
+        return cur
+    f64 = torch.float64
+    start = nbr_start.long()
+    first, deg = start[:-1], start[1:] - start[:-1]
+    width = int(deg.max())
+    free = (flags & 3) == 0 if pin else torch.ones(V, dtype=torch.bool, device=verts.device)
+    nb = nbr.long()
+    for step in range(int(iterations) * len(factors)):
+        f = factors[step % len(factors)]
+        p = cur.to(f64)
+        finite = torch.isfinite(cur).all(1)
+        s = torch.zeros(V, 3, dtype=f64, device=verts.device)
+        m = torch.zeros(V, dtype=f64, device=verts.device)
+        for k in range(width):
+            n = nb[(first + k).clamp(max=6 * F - 1)]
+            has = (k < deg) & finite[n]
+            s = s + torch.where(has[:, None], p[n], torch.zeros_like(s))
+            m = m + has.to(f64)
+        moves = finite & free & (m > 0)
+        new = (p + f * (s / m.clamp_min(1.0)[:, None] - p)).float()
+        cur = torch.where(moves[:, None], new, cur)
+    return cur
+
+
 def face_normals(tri):
     """Unit right-hand normals of a triangle soup (F,3,3) (pytorch3d Meshes.faces_normals_packed)."""
     n = torch.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0], dim=1)

@@ -899,7 +899,7 @@ class MetaAvatarRender(nn.Module):
                 "points_hat": r["points_hat"].reshape(*shape, 3), "weights": r["weights"].reshape(*shape, 24),
                 "converged": (r["state"] == 1).reshape(shape), "state": r["state"].reshape(shape)}
 
-    def posed_mesh(self, inputs, n_side=256, method="lattice", bounds=None, indexed=False, clean=None, simplify=None):
+    def posed_mesh(self, inputs, n_side=256, method="lattice", bounds=None, indexed=False, clean=None, simplify=None, smooth=None):
         """A triangle soup of the posed body of frame `inputs` in world metres.  method="lattice": the zero level set of the posed
         SDF (hip.sdf_grid_posed, only the band around the occupancy bitmap's marked voxels unless ARAH_POSED_MESH_BAND=0, then
         hip.marching_cubes) -- the surface the renderer sees, self-contact included.  method="skinned": the reference's points_bar
@@ -915,6 +915,8 @@ class MetaAvatarRender(nn.Module):
         floaters dropped on the device, and vert_src and removed come with it.  simplify (indexed=True only; None: nothing
         changes): a cell length in metres or a dict of geometry.simplify_mesh keywords -- the mesh is geometry.simplify_mesh of
         the unsimplified call's (after clean), clustered on the device; vert_src, removed, cell and dims are then simplify_mesh's.
+        smooth (indexed=True only; None: nothing changes): a number of Taubin iterations or a dict of geometry.smooth_mesh
+        keywords -- verts are geometry.smooth_mesh of the unsmoothed call's, AFTER clean and simplify; faces, counts and ids stay.
         Eval only."""
         from . import geometry, meshing
         if clean is not None:
@@ -925,6 +927,10 @@ class MetaAvatarRender(nn.Module):
             simplify = geometry.check_simplify(simplify)
             if not indexed:
                 raise ValueError("posed_mesh: simplify needs indexed=True (clustering renames shared vertex ids)")
+        if smooth is not None:
+            smooth = geometry.check_smooth(smooth)
+            if not indexed:
+                raise ValueError("posed_mesh: smooth needs indexed=True (neighbours are defined by shared vertex ids)")
         frame, ws = self._posed_frame(inputs, "posed_mesh")
         if method not in ("lattice", "skinned"):
             raise ValueError("method must be 'lattice' or 'skinned', got %r" % (method,))
@@ -953,6 +959,8 @@ class MetaAvatarRender(nn.Module):
                     res.update(geometry.clean_mesh(res["verts"], res["faces"], keep=clean))
                 if simplify is not None:
                     res.update(geometry.simplify_mesh(res["verts"], res["faces"], **simplify))
+                if smooth is not None:
+                    res["verts"] = geometry.smooth_mesh(res["verts"], res["faces"], **smooth)
                 return res
             if method == "skinned":
                 cap = meshing.MC_DEFAULT_CAP
@@ -976,7 +984,7 @@ class MetaAvatarRender(nn.Module):
                 n = int(n_dev.item())
             return {"tris": hip.lattice_to_world(tris[:n], box), "n_tris": n, "box": box, "counts": counts}
 
-    def canonical_mesh(self, inputs, n_side=256, attributes=(), view_dirs=None, clean=None, simplify=None):
+    def canonical_mesh(self, inputs, n_side=256, attributes=(), view_dirs=None, clean=None, simplify=None, smooth=None):
         """The canonical body of frame `inputs` as an indexed mesh, the reference's create_mesh_vertices_and_faces
         (utils/sdf_meshing.py:13-114): the zero level set of the canonical SDF on the n_side^3 lattice (hip.sdf_grid_band, then
         hip.marching_cubes_indexed).  -> dict of verts (V,3) normalised canonical coordinates in [-1,1]^3, faces (F,3) int32,
@@ -990,6 +998,8 @@ class MetaAvatarRender(nn.Module):
                            every vertex is view_dirs (V,3) or (3,), world-space directions FROM the camera TOWARDS the surface
                            as in the renderer; default: the ray that meets the posed surface head-on, minus the posed normal
                            (the vertex's rotation applied to "normal", renormalised)
+            "vertex_normal" (V,3) the MESH's own unit normals (geometry.vertex_normals: the incident faces' cross products
+                           summed), next to the SDF's "normal": what the triangles say after simplify and smooth moved vertices
 
         clean (None: nothing changes): a `keep` policy of geometry.clean_mesh; the floaters are dropped BEFORE the attributes are
         evaluated, so a dropped vertex costs no network evaluation, and vert_src (the kept vertices' ids in the uncleaned mesh)
@@ -1000,9 +1010,13 @@ class MetaAvatarRender(nn.Module):
         positions, and vert_src, removed, cell and dims are simplify_mesh's (ids into the cleaned mesh).  V is then the simplified
         mesh's.
 
+        smooth (None: nothing changes): a number of Taubin iterations or a dict of geometry.smooth_mesh keywords; applied after
+        clean and simplify and BEFORE the attributes are evaluated, which are then taken at the smoothed positions.  With smooth
+        and "vertex_normal" the adjacency is built once for both.
+
         Eval only, GPU only; one host synchronisation (the mesh's size), one more with clean, simplify_mesh's with simplify."""
         from . import geometry, meshing
-        names = ("weights", "verts_posed", "normal", "color")
+        names = ("weights", "verts_posed", "normal", "color", "vertex_normal")
         bad = set(attributes) - set(names)
         if bad:
             raise ValueError("canonical_mesh: unknown attributes %s (known: %s)" % (sorted(bad), ", ".join(names)))
@@ -1010,6 +1024,7 @@ class MetaAvatarRender(nn.Module):
             geometry.check_keep(clean)
         if simplify is not None:
             simplify = geometry.check_simplify(simplify)
+        smooth = geometry.check_smooth(smooth)
         frame, ws = self._posed_frame(inputs, "canonical_mesh")
         with torch.no_grad():
             verts, faces = meshing.indexed_mesh(meshing.canonical_lattice(frame, ws, n_side), 0.0)
@@ -1021,11 +1036,17 @@ class MetaAvatarRender(nn.Module):
             if simplify is not None:
                 res.update(geometry.simplify_mesh(verts, faces, **simplify))
                 verts, faces, V = res["verts"].contiguous(), res["faces"], res["n_verts"]
+            adjacency = None
+            if smooth is not None:
+                adjacency = geometry.mesh_adjacency(verts, faces)
+                res["verts"] = verts = geometry.smooth_mesh(verts, faces, adjacency=adjacency, **smooth)
             if not attributes:
                 return res
             if V == 0:
                 res.update({k: torch.zeros(0, 24 if k == "weights" else 3, device=verts.device) for k in attributes})
                 return res
+            if "vertex_normal" in attributes:
+                res["vertex_normal"] = geometry.vertex_normals(verts, faces, adjacency=adjacency)
             T = None
             if set(attributes) & {"weights", "verts_posed", "color"}:
                 cmin, cmax, center = inputs["coord_min"][:1], inputs["coord_max"][:1], inputs["center"][:1]

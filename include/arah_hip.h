@@ -34,6 +34,9 @@
  *   arah_mesh_components /  (none: the reference writes the extracted mesh as it comes; connected components of an indexed mesh
  *   arah_mesh_select        by shared vertex ids, and the order-preserving selection of some of them: floater removal)
  *   arah_mesh_simplify      (none: vertex clustering of an indexed mesh on a grid: decimation and welding by position)
+ *   arah_mesh_adjacency /   (none: the reference's users smooth and re-normal with trimesh / open3d / pytorch3d; the incident faces
+ *   arah_mesh_vertex_normals /  and unique neighbours of every vertex with edge statistics, pytorch3d's verts_normals_packed over
+ *   arah_mesh_smooth        them, and Laplacian / Taubin umbrella smoothing)
  *   arah_rasterize          pytorch3d MeshRasterizer (pix_to_face) as used at metaavatar_render/models/__init__.py:232-276
  *   arah_shade_train_*      get_rbg_value_vol_sdf with self.training: per-sample forward and backward
  *                           renderer/implicit_differentiable_renderer.py:291-361, diff_operators.py:39-50
@@ -348,6 +351,45 @@ int arah_mesh_simplify(const float* verts, int64_t n_verts, const int32_t* faces
                        const int32_t h_dims[3], double fix_scale, int32_t position, int32_t dedup, float* verts_out,
                        int32_t* vert_src, int32_t* vert_map, int32_t* faces_out, int32_t* face_src, int32_t* counts, void* scratch,
                        size_t scratch_bytes, void* stream);
+/* Adjacency of an indexed mesh (csrc/meshadj.hpp).  faces [n_faces][3] vertex ids.  A face is VALID when its three ids lie in
+ * [0, n_verts) and are pairwise different; the others are skipped.  A valid face (a, b, c) traverses the directed edges a->b,
+ * b->c, c->a.  -> vf_start [n_verts + 1], vf [3 n_faces]: the CSR of the valid faces incident to every vertex, face ids ASCENDING
+ * within a vertex; nbr_start [n_verts + 1], nbr [6 n_faces]: the CSR of the UNIQUE neighbours of every vertex, ids ascending;
+ * nbr_out, nbr_in [6 n_faces]: for the entry (v, n) the number of valid faces traversing v->n and n->v; vert_flags [n_verts]
+ * uint8: bit 0 the vertex has an edge with exactly one face, bit 1 an edge with three or more, bit 2 no neighbour; counts (device
+ * int32[8]) = valid faces, undirected edges E, edges with one face (boundary), with >= 3 faces (non-manifold), with exactly two
+ * faces that traverse it in the same direction (misoriented), the largest number of neighbours of a vertex, vertices with no
+ * neighbour, the Euler characteristic (n_verts - counts[6]) - E + counts[0].  Rows of vf from vf_start[n_verts] on and of nbr,
+ * nbr_out, nbr_in from nbr_start[n_verts] on are ZERO.  Integer atomics only, and they decide nothing but a layout that is
+ * sorted afterwards: the result is unique.  Segments of any length are sorted (a workgroup per long one).  0 <= n_verts <=
+ * INT32_MAX, 0 <= n_faces <= 2^28 (6 n_faces fits an int32), otherwise ARAH_E_BADARG without a launch and a scratch size of 0;
+ * scratch: arah_mesh_adjacency_scratch_bytes(n_verts, n_faces) device bytes, 256-byte aligned, ARAH_E_WORKSPACE when short.
+ * Empty inputs still write vf_start, nbr_start and counts; pointers of empty arrays may be NULL.  No host synchronisation, no
+ * allocation. */
+size_t arah_mesh_adjacency_scratch_bytes(int64_t n_verts, int64_t n_faces);
+int arah_mesh_adjacency(const int32_t* faces, int64_t n_faces, int64_t n_verts, int32_t* vf_start, int32_t* vf, int32_t* nbr_start,
+                        int32_t* nbr, int32_t* nbr_out, int32_t* nbr_in, uint8_t* vert_flags, int32_t* counts, void* scratch,
+                        size_t scratch_bytes, void* stream);
+/* Per-vertex normals of an indexed mesh from the mesh itself (pytorch3d verts_normals_packed): verts [n_verts][3], faces
+ * [n_faces][3], vf_start / vf of arah_mesh_adjacency on the same mesh.  Vertex v walks its incident faces in the order of vf
+ * (ascending id); a face with a non-finite corner contributes nothing, the others (p1 - p0) x (p2 - p0) with the corners widened to
+ * double, every operation rounded on its own; the sum starts at 0 and is taken in that order.  -> normal_sum [n_verts][3] double:
+ * the sums; normals [n_verts][3] float: float(sum / sqrt((x x + y y) + z z)), (0, 0, 0) when that length is 0 or not finite.  A
+ * gather: no atomics, no scratch.  A row of vf that names no valid face is skipped.  Sizes and errors as for arah_mesh_adjacency;
+ * n_verts = 0 launches nothing. */
+int arah_mesh_vertex_normals(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int32_t* vf_start,
+                             const int32_t* vf, double* normal_sum, float* normals, void* stream);
+/* Umbrella smoothing: n_steps steps over verts [n_verts][3] with nbr_start / nbr / vert_flags of arah_mesh_adjacency, all inside
+ * this call.  Step i has the factor f = double(h_factors[i & 1]) (Taubin: {lambda, mu}; plain Laplacian: {lambda, lambda}).  A
+ * vertex moves when it is finite, is not pinned (pin != 0 pins the vertices with vert_flags bit 0 or 1) and has a finite
+ * neighbour: s = the double sum of its finite neighbours in the order of nbr (ascending id), m their number, new = float(p + f (s /
+ * m - p)) in double, every operation rounded on its own; every other vertex is copied bit for bit.  A step reads the previous
+ * step's positions only: the steps alternate between tmp [n_verts][3] and verts_out so that the LAST one writes verts_out; verts
+ * is never written, tmp may be NULL for n_steps <= 1, and n_steps = 0 copies verts to verts_out.  A gather: no atomics.
+ * ARAH_E_BADARG for n_verts outside [0, INT32_MAX], n_steps < 0, a factor that is not finite or a missing pointer; n_verts = 0
+ * launches nothing. */
+int arah_mesh_smooth(const float* verts, int64_t n_verts, const int32_t* nbr_start, const int32_t* nbr, const uint8_t* vert_flags,
+                     int32_t n_steps, const float h_factors[2], int32_t pin, float* tmp, float* verts_out, void* stream);
 /* raw canonical x_hat [P,3] -> d x_bar / d x_hat [P,3,3] */
 int arah_skin_jacobian(const ArahFrame* h_frame, const float* x_hat, int32_t n_pts, float* jac,
                        void* workspace, size_t workspace_bytes, void* stream);
