@@ -1952,6 +1952,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_canon_solve(FrameDev fr, const 
 #include "meshcc.hpp"
 #include "meshsimp.hpp"
 #include "meshadj.hpp"
+#include "meshraster.hpp"
 #include "canon_wave.hpp"
 
 // explicit targets (arah_broyden3_lbs): file them where k_canon_solve expects them, in row 3 of the start transform
@@ -4343,6 +4344,61 @@ int arah_mesh_smooth(const float* verts, int64_t n_verts, const int32_t* nbr_sta
                            (const unsigned char*)vert_flags, (double)factors[i & 1], (int)(pin != 0), dst);
         src = dst;
     }
+    return check_launch();
+}
+
+// ---- indexed meshes drawn on the device: pix_to_face, depth, barycentrics; attributes (csrc/meshraster.hpp) ------------------------
+static int mr_grid(int64_t n) { return (int)min((int64_t)kMrMaxGrid, max((int64_t)1, (n + kMrThreads - 1) / kMrThreads)); }
+
+static int mr_rasterize(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t H, int32_t W, float z_near,
+                        int32_t cull, int32_t small_area, int32_t wave_area, int32_t huge_area, uint64_t* keys, int32_t* pix_to_face,
+                        float* depth, float* bary, void* stream) {
+    if (n_verts < 0 || n_faces < 0 || n_verts > (int64_t)INT32_MAX || n_faces > (int64_t)INT32_MAX) return ARAH_E_BADARG;
+    if (H <= 0 || W <= 0 || (int64_t)H * W > (int64_t)INT32_MAX || cull < 0 || cull > 2) return ARAH_E_BADARG;
+    if (small_area < 0 || wave_area < small_area || huge_area < wave_area) return ARAH_E_BADARG;
+    if (!keys || !pix_to_face || !depth || !bary || (n_verts > 0 && !verts) || (n_faces > 0 && !faces)) return ARAH_E_BADARG;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int V = (int)n_verts, F = (int)n_faces;
+    const int64_t n_pix = (int64_t)H * W;
+    unsigned long long* k = reinterpret_cast<unsigned long long*>(keys);
+    // the two lists borrow the outputs pass B writes last: H W ids in pix_to_face and in depth, the counters in bary[0], bary[1]
+    int* med_list = pix_to_face;
+    int* huge_list = reinterpret_cast<int*>(depth);
+    unsigned* counters = reinterpret_cast<unsigned*>(bary);
+    hipLaunchKernelGGL(k_mr_init, dim3(mr_grid(n_pix)), dim3(kMrThreads), 0, s, k, (long long)n_pix, counters);
+    if (F > 0 && V > 0) {
+        hipLaunchKernelGGL(k_mr_scatter, dim3(mr_grid(F)), dim3(kMrThreads), 0, s, verts, V, (const int*)faces, F, (int)H, (int)W, z_near,
+                           (int)cull, (int)small_area, (int)wave_area, (int)huge_area, k, med_list, huge_list, (unsigned)n_pix, counters);
+        hipLaunchKernelGGL(k_mr_lists, dim3(kMrListGrid), dim3(kMrThreads), 0, s, verts, V, (const int*)faces, F, (int)H, (int)W, z_near,
+                           (int)cull, k, (const int*)med_list, (const int*)huge_list, (unsigned)n_pix, (const unsigned*)counters);
+    }
+    hipLaunchKernelGGL(k_mr_resolve, dim3(mr_grid(n_pix)), dim3(kMrThreads), 0, s, verts, V, (const int*)faces, F, (int)H, (int)W,
+                       (const unsigned long long*)k, (int*)pix_to_face, depth, bary);
+    return check_launch();
+}
+
+int arah_mesh_rasterize(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t H, int32_t W, float z_near,
+                        int32_t cull, uint64_t* keys, int32_t* pix_to_face, float* depth, float* bary, void* stream) {
+    return mr_rasterize(verts, n_verts, faces, n_faces, H, W, z_near, cull, kMrSmallArea, kMrWaveArea, kMrHugeArea, keys, pix_to_face,
+                        depth, bary, stream);
+}
+
+int arah_mesh_rasterize_debug(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t H, int32_t W,
+                              float z_near, int32_t cull, int32_t small_area, int32_t wave_area, int32_t huge_area, uint64_t* keys,
+                              int32_t* pix_to_face, float* depth, float* bary, void* stream) {
+    return mr_rasterize(verts, n_verts, faces, n_faces, H, W, z_near, cull, small_area, wave_area, huge_area, keys, pix_to_face, depth,
+                        bary, stream);
+}
+
+int arah_mesh_interpolate(const int32_t* pix_to_face, const float* bary, int32_t H, int32_t W, const int32_t* faces, int64_t n_faces,
+                          const float* attr, int64_t n_verts, int32_t n_channels, float background, float* out, void* stream) {
+    if (n_verts < 0 || n_faces < 0 || n_verts > (int64_t)INT32_MAX || n_faces > (int64_t)INT32_MAX) return ARAH_E_BADARG;
+    if (H <= 0 || W <= 0 || (int64_t)H * W > (int64_t)INT32_MAX || n_channels < 1 || n_channels > 32) return ARAH_E_BADARG;
+    if (!pix_to_face || !bary || !out || (n_verts > 0 && !attr) || (n_faces > 0 && !faces)) return ARAH_E_BADARG;
+    const int64_t n_pix = (int64_t)H * W;
+    hipLaunchKernelGGL(k_mr_interpolate, dim3(mr_grid(n_pix * n_channels)), dim3(kMrThreads), 0, reinterpret_cast<hipStream_t>(stream),
+                       (const int*)pix_to_face, bary, (long long)n_pix, (const int*)faces, (int)n_faces, attr, (int)n_verts,
+                       (int)n_channels, background, out);
     return check_launch();
 }
 

@@ -13,6 +13,7 @@ Ground truth that is a SCAN -- a point cloud, with or without normals -- is scor
 nearest-point query hip.point_index / hip.point_nearest (DESIGN.md "Scoring against point clouds"): `PointCloud`, `nearest_points`,
 `load_points` / `save_points` / `load_geometry`, and F-scores at distance thresholds (`thresholds=` of `mesh_metrics`)."""
 import collections
+import math
 
 import numpy as np
 import torch
@@ -706,6 +707,178 @@ def check_smooth(smooth):
     meshing.check_smooth_args(kw.get("iterations", 10), kw.get("lamb", 0.5), kw.get("mu", -0.53), kw.get("method", "taubin"),
                               kw.get("boundary", "pin"), "smooth")
     return kw
+
+
+# ---- drawing indexed meshes ---------------------------------------------------------------------------------------------
+_CAMERA_OPENCV = ("cam_rot", "cam_trans", "K")
+_CAMERA_LOOKAT = ("azim", "dist", "fov", "at")
+_BUILTIN_ATTRIBUTES = ("vertex_normal", "face_normal")
+
+
+def check_camera(camera, what="render_mesh"):
+    """The `camera` of `render_mesh`: -> "opencv" for {"cam_rot" (3,3), "cam_trans" (3,), "K" (3,3)} (all three), "lookat" for
+    {"azim" degrees[, "dist" 2.0, "fov" 60 degrees, "at" the point looked at: three numbers or a tensor of three, default the
+    origin]}.  ValueError for anything else, keys of both kinds included."""
+    if not isinstance(camera, dict) or not camera:
+        raise ValueError("%s: camera must be a dict of cam_rot / cam_trans / K or of azim [/ dist / fov], got %r" % (what, camera))
+    keys = set(camera)
+    if keys == set(_CAMERA_OPENCV):
+        for k, n in (("cam_rot", 9), ("cam_trans", 3), ("K", 9)):
+            t = camera[k]
+            if not isinstance(t, torch.Tensor) or not t.dtype.is_floating_point or t.numel() != n:
+                raise ValueError("%s: camera[%r] must be a floating-point tensor of %d elements" % (what, k, n))
+        return "opencv"
+    if "azim" in keys and keys <= set(_CAMERA_LOOKAT):
+        at = camera.get("at")
+        if at is not None and not (isinstance(at, torch.Tensor) and at.dtype.is_floating_point and at.numel() == 3):
+            if not isinstance(at, (tuple, list)) or len(at) != 3 or any(
+                    isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(float(x)) for x in at):
+                raise ValueError("%s: camera['at'] must be three finite numbers or a floating-point tensor of three, got %r" % (what, at))
+        for k in keys - {"at"}:
+            x = camera[k]
+            if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(float(x)):
+                raise ValueError("%s: camera[%r] must be a finite number, got %r" % (what, k, x))
+        if not float(camera.get("dist", 2.0)) > 0.0 or not 0.0 < float(camera.get("fov", 60.0)) < 180.0:
+            raise ValueError("%s: camera dist must be > 0 and fov in (0, 180) degrees" % what)
+        return "lookat"
+    raise ValueError("%s: camera must hold exactly cam_rot, cam_trans and K, or azim with optional dist, fov and at; got the keys %s"
+                     % (what, sorted(keys, key=str)))
+
+
+def _rows_times(pts, M):
+    """pts (V,3) @ M (3,3) with the sum written out, (x m0 + y m1) + z m2 per column, every operation rounded on its own: the same
+    bits on the host and on the device, which a matrix product does not promise."""
+    x, y, z = pts[:, 0:1], pts[:, 1:2], pts[:, 2:3]
+    return (x * M[0][None, :] + y * M[1][None, :]) + z * M[2][None, :]
+
+
+def project_mesh(verts, camera, height, width):
+    """verts (V,3) float32 through `camera` (check_camera) -> (V,3) (u, v, view depth) in the pixels of a height x width image: the
+    formulas of meshing.project_opencv / project_lookat with the products summed in a fixed order (host and device agree bit for
+    bit).  A look-at view of an image that is not square fits the shorter side, like pytorch3d."""
+    from . import meshing
+    kind = check_camera(camera)
+    dev = verts.device
+    if kind == "opencv":
+        R = camera["cam_rot"].detach().to(dev, torch.float32).reshape(3, 3)
+        t = camera["cam_trans"].detach().to(dev, torch.float32).reshape(3)
+        K = camera["K"].detach().to(dev, torch.float32).reshape(3, 3)
+        xc = _rows_times(verts, R.t()) + t[None, :]
+        z = xc[:, 2]
+        return torch.stack([K[0, 0] * xc[:, 0] / z + K[0, 2], K[1, 1] * xc[:, 1] / z + K[1, 2], z], dim=1)
+    cam, R = meshing._lookat(dev, float(camera["azim"]), float(camera.get("dist", 2.0)))
+    at = camera.get("at")
+    if at is not None:   # the camera keeps its offset and its axes, and moves with the point it looks at
+        at = at.detach().to(dev, torch.float32).reshape(3) if isinstance(at, torch.Tensor) else \
+            torch.tensor([float(x) for x in at], dtype=torch.float32, device=dev)
+        cam = cam + at
+    xv = _rows_times(verts - cam[None, :], R)
+    f = 1.0 / math.tan(math.radians(float(camera.get("fov", 60.0))) / 2.0)
+    z, side = xv[:, 2], min(height, width)
+    u = (1.0 - f * xv[:, 0] / z) * side / 2.0 + (width - side) / 2.0
+    v = (1.0 - f * xv[:, 1] / z) * side / 2.0 + (height - side) / 2.0
+    return torch.stack([u, v, z], dim=1)
+
+
+def face_normals(verts, faces):
+    """Unit right-hand normals (F,3) float32 of the faces of an indexed mesh, (p1 - p0) x (p2 - p0) normalised in float64 with every
+    operation rounded on its own; (0, 0, 0) for a face with an id out of range, a non-finite corner or no area."""
+    V, f64 = int(verts.shape[0]), torch.float64
+    faces = faces.long()
+    if V == 0 or faces.shape[0] == 0:
+        return torch.zeros(faces.shape[0], 3, dtype=torch.float32, device=verts.device)
+    p = verts.to(f64)[faces.clamp(0, V - 1)]
+    a, b = p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]
+    n = torch.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2],
+                     a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], dim=1)
+    length = torch.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])
+    ok = ((faces >= 0) & (faces < V)).all(1) & torch.isfinite(length) & (length > 0)
+    unit = n / torch.where(ok, length, torch.ones_like(length))[:, None]
+    return torch.where(ok[:, None], unit, torch.zeros_like(unit)).float()
+
+
+def surface_centroid(verts, faces):
+    """The centroid (3,) float32 of the SURFACE of an indexed mesh: the faces' centres weighted with their areas, in float64; faces
+    with an id out of range or a non-finite corner are left out, and a mesh without area gives the origin.  Unlike the mean of the
+    vertices it does not depend on how finely a part is tessellated, and unlike the centre of the bounding box it is where the bulk
+    of the surface is.  On the mesh's device, no host synchronisation."""
+    V, f64 = int(verts.shape[0]), torch.float64
+    faces = faces.long()
+    if V == 0 or faces.shape[0] == 0:
+        return torch.zeros(3, dtype=torch.float32, device=verts.device)
+    p = verts.to(f64)[faces.clamp(0, V - 1)]
+    area = torch.linalg.vector_norm(torch.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0], dim=1), dim=1)
+    ok = ((faces >= 0) & (faces < V)).all(1) & torch.isfinite(area)
+    area = torch.where(ok, area, torch.zeros_like(area))
+    centre = torch.where(ok[:, None], p.mean(1), torch.zeros_like(p[:, 0]))
+    c = (area[:, None] * centre).sum(0) / area.sum()
+    return torch.where(torch.isfinite(c), c, torch.zeros_like(c)).float()
+
+
+def render_mesh(verts, faces, height, width, camera=None, attributes=None, cull="none", z_near=1e-4, background=0.0):
+    """Draw an indexed mesh: verts (V,3) world (or canonical) coordinates, faces (F,3) integer ids, through `camera` --
+    {"cam_rot" (3,3), "cam_trans" (3,), "K" (3,3)}, an OpenCV camera as the frames carry it (meshing.project_opencv), or {"azim"
+    degrees[, "dist" 2.0, "fov" 60, "at" the point looked at, default the origin]}, pytorch3d's look-at view of the canonical maps
+    (meshing.project_lookat) -- into a height x
+    width image, one face per pixel, the nearest.  The rule is meshing.mesh_rasterize: watertight along shared edges,
+    perspective-correct depth and barycentrics, faces at or behind z_near dropped whole; cull="back" / "front" drops the faces
+    whose projected area2 is negative / positive.
+
+    attributes: a dict name -> (V,C) float tensor, 1 <= C <= 32, of per-vertex values to interpolate.  The names "vertex_normal"
+    and "face_normal" may be given as True: the mesh's own normals (geometry.vertex_normals, interpolated -- NOT renormalised; and
+    the faces' unit cross products, flat: gathered by pix_to_face).  -> a dict of tensors on the mesh's device: pix_to_face (H,W)
+    int32 (-1: nothing), depth (H,W) float32 view depth (-1), bary (H,W,3) float32 (-1), mask (H,W) bool, and one (H,W,C) float32
+    image per attribute with `background` where nothing is drawn.  hip.mesh_rasterize / hip.mesh_interpolate for a mesh on the GPU
+    (no host synchronisation), their specification in meshing for one on the host, equal bit for bit."""
+    from . import meshing
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or not verts.dtype.is_floating_point:
+        raise ValueError("render_mesh: verts must be a floating-point (V, 3) tensor")
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("render_mesh: faces must be an (F, 3) tensor")
+    if faces.dtype.is_floating_point or faces.dtype.is_complex or faces.dtype == torch.bool:
+        raise ValueError("render_mesh: faces must hold integer vertex ids")
+    if verts.device != faces.device:
+        raise ValueError("render_mesh: verts live on %s, faces on %s" % (verts.device, faces.device))
+    for name, x in (("height", height), ("width", width)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or int(x) < 1:
+            raise ValueError("render_mesh: %s must be an integer >= 1, got %r" % (name, x))
+    if cull not in meshing.RASTER_CULL:
+        raise ValueError("render_mesh: cull must be 'none', 'back' or 'front', got %r" % (cull,))
+    check_camera(camera)
+    V, dev = int(verts.shape[0]), verts.device
+    attributes = dict(attributes or {})
+    for name, a in attributes.items():
+        if a is True and name in _BUILTIN_ATTRIBUTES:
+            continue
+        if name in ("pix_to_face", "depth", "bary", "mask"):
+            raise ValueError("render_mesh: an attribute cannot be called %r" % name)
+        if not isinstance(a, torch.Tensor) or a.dim() != 2 or not a.dtype.is_floating_point or not 1 <= int(a.shape[1]) <= 32:
+            raise ValueError("render_mesh: attribute %r must be a floating-point (V, C) tensor with 1 <= C <= 32%s"
+                             % (name, " (True only for %s)" % " / ".join(_BUILTIN_ATTRIBUTES) if a is True else ""))
+        if int(a.shape[0]) != V:
+            raise ValueError("render_mesh: attribute %r has %d rows, the mesh %d vertices" % (name, int(a.shape[0]), V))
+        if a.device != dev:
+            raise ValueError("render_mesh: attribute %r lives on %s, the mesh on %s" % (name, a.device, dev))
+    height, width = int(height), int(width)
+    backend = _cc_backend(faces)
+    rasterize = backend.mesh_rasterize
+    interpolate = backend.mesh_interpolate if faces.is_cuda else backend.interpolate_attributes
+    with torch.no_grad():
+        v32 = verts.detach().to(torch.float32).contiguous()
+        uvz = project_mesh(v32, camera, height, width)
+        p2f, depth, bary = rasterize(uvz, faces, height, width, z_near=z_near, cull=cull)
+        res = {"pix_to_face": p2f, "depth": depth, "bary": bary, "mask": p2f >= 0}
+        for name, a in attributes.items():
+            if a is True and name == "face_normal":
+                n = face_normals(v32, faces)
+                fill = torch.full((), float(background), dtype=torch.float32, device=dev)
+                res[name] = torch.where(res["mask"][..., None], n[p2f.long().clamp_min(0)], fill) if n.shape[0] else \
+                    fill.expand(height, width, 3).clone()
+                continue
+            if a is True:
+                a = vertex_normals(v32, faces)
+            res[name] = interpolate(p2f, bary, faces, a.detach().to(torch.float32).contiguous(), background=background)
+    return res
 
 
 # ---- ground-truth files -------------------------------------------------------------------------------------------------

@@ -139,6 +139,7 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_mesh_components_scratch_bytes", "arah_mesh_components", "arah_mesh_select_scratch_bytes", "arah_mesh_select",
            "arah_mesh_simplify_scratch_bytes", "arah_mesh_simplify",
            "arah_mesh_adjacency_scratch_bytes", "arah_mesh_adjacency", "arah_mesh_vertex_normals", "arah_mesh_smooth",
+           "arah_mesh_rasterize", "arah_mesh_rasterize_debug", "arah_mesh_interpolate",
            "arah_point_index_bytes", "arah_point_index_build", "arah_point_nearest", "arah_sample_scores_bytes", "arah_sample_scores"]
 
 _lib = None
@@ -1009,6 +1010,62 @@ def mesh_smooth(verts, faces, iterations, lamb=0.5, mu=-0.53, method="taubin", b
         _check(lib.arah_mesh_smooth(_ptr(v), C.c_int64(V), _ptr(adj[2]), _ptr(adj[3]), _ptr(adj[6]), C.c_int32(n_steps),
                                     (C.c_float * 2)(factors[0], factors[-1]), C.c_int32(int(pin)), _ptr(tmp), _ptr(out), _stream()),
                "arah_mesh_smooth")
+    return out
+
+
+def mesh_rasterize(verts_uvz, faces, height, width, z_near=1e-4, cull="none", thresholds=None):
+    """An indexed mesh drawn on the device (arah_mesh_rasterize, csrc/meshraster.hpp): verts_uvz (V,3) float32 (u, v, view depth) and
+    faces (F,3) integer ids on the GPU -> pix_to_face (H,W) int32, depth (H,W) float32, bary (H,W,3) float32, -1 where nothing
+    covers; meshing.mesh_rasterize bit for bit.  The key buffer is allocated here and initialised inside the call; no host
+    synchronisation.  thresholds: (small_area, wave_area, huge_area) of pass A instead of the built-in ones
+    (arah_mesh_rasterize_debug; the image is the same for every choice), for measuring them."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    verts, H, W, cull_code = meshing.check_raster_args(verts_uvz, faces, height, width, cull)
+    V = int(verts.shape[0])
+    f, _, F = _mesh_cc_args(faces, V, "mesh_rasterize")
+    v = verts.contiguous()
+    dev = v.device
+    with _on_device(dev):
+        keys = torch.empty(H * W, dtype=torch.int64, device=dev)
+        pix_to_face = torch.empty(H, W, dtype=torch.int32, device=dev)
+        depth = torch.empty(H, W, dtype=torch.float32, device=dev)
+        bary = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+        head = (_ptr(v) if V else None, C.c_int64(V), _ptr(f) if F else None, C.c_int64(F), C.c_int32(H), C.c_int32(W),
+                C.c_float(float(z_near)), C.c_int32(cull_code))
+        tail = (_ptr(keys), _ptr(pix_to_face), _ptr(depth), _ptr(bary), _stream())
+        if thresholds is None:
+            _check(lib.arah_mesh_rasterize(*head, *tail), "arah_mesh_rasterize")
+        else:
+            _check(lib.arah_mesh_rasterize_debug(*head, *(C.c_int32(int(t)) for t in tuple(thresholds)[:3]), *tail),
+                   "arah_mesh_rasterize_debug")
+    return pix_to_face, depth, bary
+
+
+def mesh_interpolate(pix_to_face, bary, faces, attr, background=0.0):
+    """Per-vertex attributes attr (V,C) float32, 1 <= C <= 32, drawn with the pix_to_face (H,W) and bary (H,W,3) of `mesh_rasterize`
+    (arah_mesh_interpolate), all on the GPU: -> (H,W,C) float32, `background` where no face was drawn;
+    meshing.interpolate_attributes bit for bit.  A gather per pixel and channel; no host synchronisation."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    p2f, b, a = meshing.check_interpolate_args(pix_to_face, bary, faces, attr, "mesh_interpolate")
+    V, Cn = int(a.shape[0]), int(a.shape[1])
+    f, _, F = _mesh_cc_args(faces, V, "mesh_interpolate")
+    H, W = int(p2f.shape[0]), int(p2f.shape[1])
+    if H * W > 2 ** 31 - 1:
+        raise ValueError("mesh_interpolate: at most 2^31 - 1 pixels")
+    dev = a.device
+    if p2f.dtype != torch.int32:   # ids that do not fit int32 name no face: -1
+        p2f = p2f.long()
+        p2f = torch.where((p2f >= 0) & (p2f <= 2 ** 31 - 1), p2f, torch.full_like(p2f, -1)).to(torch.int32)
+    p2f, b, a = p2f.contiguous(), b.contiguous(), a.contiguous()
+    with _on_device(dev):
+        out = torch.empty(H, W, Cn, dtype=torch.float32, device=dev)
+        _check(lib.arah_mesh_interpolate(_ptr(p2f), _ptr(b), C.c_int32(H), C.c_int32(W), _ptr(f) if F else None, C.c_int64(F),
+                                         _ptr(a) if V else None, C.c_int64(V), C.c_int32(Cn), C.c_float(float(background)),
+                                         _ptr(out), _stream()), "arah_mesh_interpolate")
     return out
 
 

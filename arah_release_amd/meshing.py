@@ -590,6 +590,182 @@ def mesh_smooth(verts, faces, iterations, lamb=0.5, mu=-0.53, method="taubin", b
     return cur
 
 
+RASTER_CULL = {"none": 0, "back": 1, "front": 2}
+_RASTER_EMPTY = 2 ** 63 - 1             # a pixel nothing covers; every real key is below it (z > 0: its bits are below 2^31)
+_RASTER_CHUNK = 1 << 22                 # fragments the specification tests at a time
+
+
+def check_raster_args(verts_uvz, faces, height, width, cull, what="mesh_rasterize"):
+    """The arguments of `mesh_rasterize`, checked (nothing is converted or copied): -> (verts (V,3) float32, H, W, the cull code)."""
+    if not isinstance(verts_uvz, torch.Tensor) or verts_uvz.dim() != 2 or verts_uvz.shape[1] != 3 or verts_uvz.dtype != torch.float32:
+        raise ValueError("%s: verts_uvz must be a (V, 3) float32 tensor of (u, v, depth)" % what)
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("%s: faces must be an (F, 3) tensor" % what)
+    if faces.dtype.is_floating_point or faces.dtype.is_complex or faces.dtype == torch.bool:
+        raise ValueError("%s: faces must hold integer vertex ids" % what)
+    if faces.device != verts_uvz.device:
+        raise ValueError("%s: verts live on %s, faces on %s" % (what, verts_uvz.device, faces.device))
+    for name, x in (("height", height), ("width", width)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or int(x) < 1:
+            raise ValueError("%s: %s must be an integer >= 1, got %r" % (what, name, x))
+    if int(height) * int(width) > 2 ** 31 - 1 or int(faces.shape[0]) > 2 ** 31 - 1:
+        raise ValueError("%s: at most 2^31 - 1 pixels and faces" % what)
+    if cull not in RASTER_CULL:
+        raise ValueError("%s: cull must be 'none', 'back' or 'front', got %r" % (what, cull))
+    return verts_uvz.detach(), int(height), int(width), RASTER_CULL[cull]
+
+
+def _raster_edges(p, px, py):
+    """e0 = E(1,2), e1 = E(2,0), e2 = E(0,1) of the corners p (...,3,3) at the pixel centres (px, py), float32, every operation
+    rounded on its own."""
+    dx, dy = p[..., 0] - px[..., None], p[..., 1] - py[..., None]
+    return (dx[..., 1] * dy[..., 2] - dx[..., 2] * dy[..., 1], dx[..., 2] * dy[..., 0] - dx[..., 0] * dy[..., 2],
+            dx[..., 0] * dy[..., 1] - dx[..., 1] * dy[..., 0])
+
+
+def mesh_rasterize(verts_uvz, faces, height, width, z_near=1e-4, cull="none"):
+    """An indexed mesh drawn, one face per pixel: what pytorch3d's MeshRasterizer returns (pix_to_face, zbuf, bary_coords with
+    perspective correction, no blur).  verts_uvz (V,3) float32 = (u, v, z) per vertex, pixel coordinates and view depth, what
+    `project_opencv` / `project_lookat` return; faces (F,3) integer ids.  Pixel (i, j) has its centre at px = j + 0.5, py = i +
+    0.5.  -> pix_to_face (H,W) int32, depth (H,W) float32, bary (H,W,3) float32; -1 in all three where nothing covers.
+
+    All float32 arithmetic has every operation rounded on its own.
+
+      * A face is VALID when its three ids lie in [0, V), all three z are finite and > float32(z_near), and area2 = (x1-x0)*(y2-y0) -
+        (x2-x0)*(y1-y0) is finite and not 0 (a repeated id gives 0).  cull="back" also drops area2 < 0, "front" area2 > 0.  Under
+        `project_opencv` (u to the right, v DOWN, looking along +z) a face seen from the side its right-hand normal (p1 - p0) x
+        (p2 - p0) points to has area2 < 0: that camera frame is right-handed with z away from the viewer, so such a face's
+        normal has a negative z there, and area2 has the sign of that z.
+      * Its pixels are those whose centres lie in the closed bounding box of its three vertices, clipped to the image: columns
+        max(ceil(xmin - 0.5), 0) .. min(floor(xmax - 0.5), W - 1), rows alike, whatever the size of the box.  (A centre inside the
+        triangle lies inside its box; said here so that the kernels and this agree on every sliver as well.)
+      * Edge functions E(a,b) = (xa-px)*(yb-py) - (xb-px)*(ya-py): e0 = E(1,2), e1 = E(2,0), e2 = E(0,1).  The pixel is COVERED when
+        all three are >= 0 (area2 > 0) or all three <= 0 (area2 < 0), and s = (e0+e1)+e2 != 0.  The test is inclusive on purpose:
+        E(a,b) is -E(b,a) bit for bit, so two consistently oriented faces that share an edge leave no pixel centre between them
+        uncovered; the depth key settles who gets a centre both cover.
+      * The fragment's depth, perspective-correct: q = ((e0/z0 + e1/z1) + e2/z2) / s, z = 1/q; a fragment whose z is not finite and
+        > 0 is dropped.
+      * The pixel goes to the smallest 64-bit key (bits(z) << 32) | face id: the nearest face, and the lowest id on an exact tie.
+        depth is the key's z bit for bit.
+      * The winner's barycentrics in float64 from the same float32 e_k: b_k = e_k / ((e0+e1)+e2), p_k = b_k / z_k, bary_k =
+        float32(p_k / ((p0+p1)+p2)).
+
+    Plain tensor operations on the tensors' device (with host synchronisations): the specification of arah_mesh_rasterize
+    (csrc/meshraster.hpp), and what runs for meshes on the host."""
+    verts, H, W, cull = check_raster_args(verts_uvz, faces, height, width, cull)
+    faces = faces.detach().long()
+    dev, V, F, f32 = verts.device, int(verts.shape[0]), int(faces.shape[0]), torch.float32
+    keys = torch.full((H * W,), _RASTER_EMPTY, dtype=torch.int64, device=dev)
+    if V > 0 and F > 0:
+        ok = ((faces >= 0) & (faces < V)).all(1)
+        p = verts[faces.clamp(0, V - 1)]                                        # (F,3,3); rows of invalid faces are never used
+        x, y, z = p[..., 0], p[..., 1], p[..., 2]
+        ok = ok & (z > torch.tensor(float(z_near), dtype=f32, device=dev)).all(1) & torch.isfinite(z).all(1)
+        area2 = (x[:, 1] - x[:, 0]) * (y[:, 2] - y[:, 0]) - (x[:, 2] - x[:, 0]) * (y[:, 1] - y[:, 0])
+        ok = ok & torch.isfinite(area2) & (area2 != 0)
+        if cull == 1:
+            ok = ok & ~(area2 < 0)
+        elif cull == 2:
+            ok = ok & ~(area2 > 0)
+        # the clipped box: in float32, held to [-1, the largest float32 below 2^31], then integers (NaN only in faces already dropped)
+        lim = 2147483520.0
+
+        def to_int(t):
+            return torch.nan_to_num(t, nan=-1.0).clamp(-1.0, lim).long()
+        j0 = to_int(torch.ceil(x.min(1).values - 0.5)).clamp_min(0)
+        j1 = to_int(torch.floor(x.max(1).values - 0.5)).clamp_max(W - 1)
+        i0 = to_int(torch.ceil(y.min(1).values - 0.5)).clamp_min(0)
+        i1 = to_int(torch.floor(y.max(1).values - 0.5)).clamp_max(H - 1)
+        ok = ok & (j0 <= j1) & (i0 <= i1)
+        rows = torch.nonzero(ok)[:, 0]
+        n_box = ((j1 - j0 + 1) * (i1 - i0 + 1))[rows]
+        n_box, order = torch.sort(n_box)
+        rows = rows[order]
+        sizes = n_box.tolist()
+        a = 0
+        while a < len(sizes):                                                   # faces of like size together, <= _RASTER_CHUNK fragments
+            lo, b = a + 1, min(len(sizes), a + max(1, _RASTER_CHUNK // sizes[a]))
+            while lo < b:                                                        # the most faces whose padded boxes fit (sizes ascend)
+                mid = (lo + b + 1) // 2
+                lo, b = (mid, b) if (mid - a) * sizes[mid - 1] <= _RASTER_CHUNK else (lo, mid - 1)
+            r = rows[a:b]
+            k = torch.arange(sizes[b - 1], device=dev)[None, :]                  # (1,n): the box in row-major order
+            w = (j1[r] - j0[r] + 1)[:, None]
+            inside = k < n_box[a:b, None]
+            i, j = i0[r][:, None] + k // w, j0[r][:, None] + k % w
+            pr, pos = p[r][:, None], (area2[r] > 0)[:, None]
+            e0, e1, e2 = _raster_edges(pr, j.to(f32) + 0.5, i.to(f32) + 0.5)
+            cov = torch.where(pos, (e0 >= 0) & (e1 >= 0) & (e2 >= 0), (e0 <= 0) & (e1 <= 0) & (e2 <= 0))
+            s = (e0 + e1) + e2
+            q = ((e0 / pr[..., 0, 2] + e1 / pr[..., 1, 2]) + e2 / pr[..., 2, 2]) / s
+            zf = torch.ones_like(q) / q
+            cov = inside & cov & (s != 0) & torch.isfinite(zf) & (zf > 0)
+            key = (zf.contiguous().view(torch.int32).long() << 32) | r[:, None]
+            pix, key = (i * W + j)[cov], key[cov]
+            # the smallest key per pixel: sorted by key, then stably by pixel, the first of every run
+            key, o = torch.sort(key)
+            pix, o = torch.sort(pix[o], stable=True)
+            key = key[o]
+            first = torch.ones_like(pix, dtype=torch.bool)
+            first[1:] = pix[1:] != pix[:-1]
+            pix, key = pix[first], key[first]
+            keys[pix] = torch.minimum(keys[pix], key)
+            a = b
+    hit = keys != _RASTER_EMPTY
+    face = torch.where(hit, keys & 0xffffffff, torch.zeros_like(keys))
+    depth = torch.where(hit, (keys >> 32).to(torch.int32).view(f32), torch.full((), -1.0, dtype=f32, device=dev))
+    bary = torch.full((H * W, 3), -1.0, dtype=f32, device=dev)
+    if V > 0 and F > 0:
+        pw = verts[faces.clamp(0, V - 1)[face]]                                 # (HW,3,3): the winner's corners
+        pid = torch.arange(H * W, device=dev)
+        e = torch.stack(_raster_edges(pw, (pid % W).to(f32) + 0.5, (pid // W).to(f32) + 0.5), dim=1).to(torch.float64)
+        b = e / ((e[:, 0] + e[:, 1]) + e[:, 2])[:, None]
+        pk = b / pw[..., 2].to(torch.float64)
+        bary = torch.where(hit[:, None], (pk / ((pk[:, 0] + pk[:, 1]) + pk[:, 2])[:, None]).to(f32), bary)
+    pix_to_face = torch.where(hit, face, torch.full_like(face, -1)).to(torch.int32)
+    return pix_to_face.reshape(H, W), depth.reshape(H, W), bary.reshape(H, W, 3)
+
+
+def check_interpolate_args(pix_to_face, bary, faces, attr, what="interpolate_attributes"):
+    """The arguments of `interpolate_attributes`, checked (nothing is converted or copied): -> (pix_to_face (H,W), bary (H,W,3)
+    float32, attr (V,C) float32)."""
+    if not isinstance(pix_to_face, torch.Tensor) or pix_to_face.dim() != 2 or pix_to_face.dtype.is_floating_point \
+            or pix_to_face.dtype == torch.bool or pix_to_face.numel() == 0:
+        raise ValueError("%s: pix_to_face must be an (H, W) integer tensor" % what)
+    if not isinstance(bary, torch.Tensor) or tuple(bary.shape) != (*pix_to_face.shape, 3) or bary.dtype != torch.float32:
+        raise ValueError("%s: bary must be the (H, W, 3) float32 tensor of pix_to_face's rasterisation" % what)
+    if not isinstance(attr, torch.Tensor) or attr.dim() != 2 or attr.dtype != torch.float32 or not 1 <= int(attr.shape[1]) <= 32:
+        raise ValueError("%s: attr must be a (V, C) float32 tensor with 1 <= C <= 32" % what)
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("%s: faces must be an (F, 3) tensor" % what)
+    if faces.dtype.is_floating_point or faces.dtype.is_complex or faces.dtype == torch.bool:
+        raise ValueError("%s: faces must hold integer vertex ids" % what)
+    if len({pix_to_face.device, bary.device, faces.device, attr.device}) != 1:
+        raise ValueError("%s: pix_to_face, bary, faces and attr must live on one device" % what)
+    return pix_to_face.detach(), bary.detach(), attr.detach()
+
+
+def interpolate_attributes(pix_to_face, bary, faces, attr, background=0.0):
+    """Per-vertex attributes attr (V,C) float32, 1 <= C <= 32, drawn with the pix_to_face (H,W) and bary (H,W,3) of
+    `mesh_rasterize` (pytorch3d's interpolate_face_attributes): -> (H,W,C) float32, float32((b0*a0 + b1*a1) + b2*a2) with the
+    products and sums in float64 on the float32 bary and attribute values, every operation rounded on its own.  float32(background)
+    where pix_to_face names no face of this mesh (-1), or a face with an id outside [0, V).  The specification of
+    arah_mesh_interpolate (csrc/meshraster.hpp), and what runs for meshes on the host."""
+    p2f, bary, attr = check_interpolate_args(pix_to_face, bary, faces, attr)
+    p2f, faces = p2f.long(), faces.detach().long()
+    dev, V, F, C, f64 = attr.device, int(attr.shape[0]), int(faces.shape[0]), int(attr.shape[1]), torch.float64
+    out = torch.full((*p2f.shape, C), float(background), dtype=torch.float32, device=dev)
+    if V == 0 or F == 0:
+        return out
+    named = (p2f >= 0) & (p2f < F)
+    ids = faces[p2f.clamp(0, F - 1)]                                            # (H,W,3)
+    named = named & ((ids >= 0) & (ids < V)).all(-1)
+    a = attr.to(f64)[ids.clamp(0, V - 1)]                                       # (H,W,3,C)
+    b = bary.to(f64)[..., None]
+    val = ((b[..., 0, :] * a[..., 0, :] + b[..., 1, :] * a[..., 1, :]) + b[..., 2, :] * a[..., 2, :]).to(torch.float32)
+    return torch.where(named[..., None], val, out)
+
+
 def face_normals(tri):
     """Unit right-hand normals of a triangle soup (F,3,3) (pytorch3d Meshes.faces_normals_packed)."""
     n = torch.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0], dim=1)

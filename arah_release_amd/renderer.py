@@ -1073,6 +1073,53 @@ class MetaAvatarRender(nn.Module):
                 res["color"] = hip.shade_points(frame, ws, verts, T, dirs.contiguous(), self.idhr_network.cano_view_dirs)[0]
         return res
 
+    def render_mesh(self, inputs, height=512, width=512, n_side=256, space="posed", attributes=("color", "vertex_normal"), clean=None,
+                    simplify=None, smooth=None, view=None):
+        """An image of the body of frame `inputs` as an indexed mesh: `canonical_mesh(inputs, n_side, clean=, simplify=, smooth=)`
+        with "verts_posed" and the attributes named, drawn by geometry.render_mesh (hip.mesh_rasterize, hip.mesh_interpolate).
+        space="posed": the skinned vertices through the frame's own camera (cam_rot, cam_trans, intrinsics of batch element 0);
+        space="canonical": the canonical vertices through `view`, a look-at camera {"azim": degrees (0 front, 180 back)[, "dist",
+        "fov", "at"]}, default the front view.  "at", the point looked at, defaults to the centroid of the mesh's surface
+        (geometry.surface_centroid), NOT to the origin the gen_cano_mesh maps look at: a body does not sit in the middle of its
+        normalised cube (the synthetic subject's lies at z in [-0.06, 0.29], most of it near 0.08), a silhouette's area goes with
+        1 / depth^2, and only a camera that turns about the bulk of the body sees it equally large, mirrored, from the front and
+        from the back; "at": (0, 0, 0) gives the other camera.  attributes: per-vertex names of `canonical_mesh` ("color", "normal", "weights",
+        "verts_posed", "vertex_normal") and "face_normal"; each becomes an (H,W,C) image, 0 where nothing is drawn.
+
+        The NORMALS drawn are those of the mesh that is drawn: in posed space "vertex_normal" and "face_normal" are the posed
+        mesh's own (geometry.vertex_normals of the posed vertices, world axes), not the canonical mesh's rotated; in canonical
+        space they are the canonical mesh's.  "normal" stays the canonical SDF's gradient in both.  A "vertex_normal" image is the
+        interpolant, shorter than 1 inside a face: renormalise it for shading.
+
+        -> the dict of geometry.render_mesh (pix_to_face, depth, bary, mask and the images) plus "mesh", the dict of
+        canonical_mesh.  Eval only, GPU only; the host synchronisations are canonical_mesh's."""
+        from . import geometry
+        if space not in ("posed", "canonical"):
+            raise ValueError("render_mesh: space must be 'posed' or 'canonical', got %r" % (space,))
+        names = ("weights", "verts_posed", "normal", "color", "vertex_normal", "face_normal")
+        attributes = tuple(attributes)
+        bad = set(attributes) - set(names)
+        if bad:
+            raise ValueError("render_mesh: unknown attributes %s (known: %s)" % (sorted(bad), ", ".join(names)))
+        if space == "posed":
+            if view is not None:
+                raise ValueError("render_mesh: view is the camera of space='canonical'; the posed body is seen through the frame's")
+            camera = {"cam_rot": inputs["cam_rot"][0], "cam_trans": inputs["cam_trans"][0].reshape(3), "K": inputs["intrinsics"][0]}
+        else:
+            camera = {"azim": 0.0} if view is None else view
+            if geometry.check_camera(camera, "render_mesh: view") != "lookat":
+                raise ValueError("render_mesh: view must be a look-at camera {'azim': degrees[, 'dist', 'fov', 'at']}")
+        own = ("vertex_normal", "face_normal")   # taken from the mesh that is drawn
+        wanted = {a for a in attributes if a not in own} | ({"verts_posed"} if space == "posed" else set())
+        mesh = self.canonical_mesh(inputs, n_side=n_side, attributes=tuple(sorted(wanted)), clean=clean, simplify=simplify, smooth=smooth)
+        verts = mesh["verts_posed"] if space == "posed" else mesh["verts"]
+        draw = {a: (True if a in own else mesh[a]) for a in attributes}
+        if space == "canonical" and "at" not in camera:
+            camera = dict(camera, at=geometry.surface_centroid(verts, mesh["faces"]))
+        res = geometry.render_mesh(verts, mesh["faces"], height, width, camera=camera, attributes=draw)
+        res["mesh"] = mesh
+        return res
+
     def geometry_metrics(self, inputs, gt, n_side=256, method="lattice", n_samples=100000, seed=0, clean=None, thresholds=None):
         """Geometry scores of the posed body of frame `inputs` against a ground truth `gt` in world metres on the inputs' GPU -- a
         mesh ((F,3,3) triangles or a (verts, faces) pair) or a scan (a geometry.PointCloud or a (P,3) tensor of points):

@@ -37,6 +37,9 @@
  *   arah_mesh_adjacency /   (none: the reference's users smooth and re-normal with trimesh / open3d / pytorch3d; the incident faces
  *   arah_mesh_vertex_normals /  and unique neighbours of every vertex with edge statistics, pytorch3d's verts_normals_packed over
  *   arah_mesh_smooth        them, and Laplacian / Taubin umbrella smoothing)
+ *   arah_mesh_rasterize /   pytorch3d MeshRasterizer's three outputs for an INDEXED mesh (pix_to_face, zbuf, bary_coords; one face per
+ *   arah_mesh_interpolate   pixel, no blur, perspective-correct) and interpolate_face_attributes over them; arah_rasterize below
+ *                           stays what the gen_cano_mesh branch draws with
  *   arah_rasterize          pytorch3d MeshRasterizer (pix_to_face) as used at metaavatar_render/models/__init__.py:232-276
  *   arah_shade_train_*      get_rbg_value_vol_sdf with self.training: per-sample forward and backward
  *                           renderer/implicit_differentiable_renderer.py:291-361, diff_operators.py:39-50
@@ -390,6 +393,32 @@ int arah_mesh_vertex_normals(const float* verts, int64_t n_verts, const int32_t*
  * launches nothing. */
 int arah_mesh_smooth(const float* verts, int64_t n_verts, const int32_t* nbr_start, const int32_t* nbr, const uint8_t* vert_flags,
                      int32_t n_steps, const float h_factors[2], int32_t pin, float* tmp, float* verts_out, void* stream);
+/* An indexed mesh drawn (csrc/meshraster.hpp; meshing.mesh_rasterize is the rule, bit for bit): verts [n_verts][3] = (u, v, view
+ * depth) in pixel coordinates (pixel (i, j) has its centre at u = j + 0.5, v = i + 0.5), faces [n_faces][3].  A face is valid when
+ * its ids lie in [0, n_verts), its z are finite and > z_near and area2 = (x1-x0)(y2-y0) - (x2-x0)(y1-y0) is finite and not 0; cull
+ * = 0 none, 1 drops area2 < 0, 2 drops area2 > 0.  With e0 = E(1,2), e1 = E(2,0), e2 = E(0,1), E(a,b) = (xa-px)(yb-py) -
+ * (xb-px)(ya-py), every float operation rounded on its own, a pixel centre inside the closed bounding box is covered when all e_k
+ * >= 0 (area2 > 0) or all <= 0 (area2 < 0) and s = (e0+e1)+e2 != 0: faces that share an edge leave no centre uncovered.  The
+ * fragment's depth is z = 1 / (((e0/z0 + e1/z1) + e2/z2) / s); the smallest key (bits(z) << 32) | face wins the pixel.  ->
+ * pix_to_face [H][W] (-1: nothing), depth [H][W] (the key's z; -1), bary [H][W][3] (perspective-correct, from the same e_k in
+ * double; -1).  keys [H*W] is scratch, initialised inside the call.  Two passes: a scatter with a 64-bit integer atomicMin (the
+ * only atomic that decides anything: the result does not depend on the order of arrival) and a per-pixel resolve.  A face's
+ * clipped bounding box is drawn whatever its size: by its lane, by its wave, by a workgroup or by 64 of them.  pix_to_face, depth
+ * and bary[0..1] hold the lists of the larger faces between the passes.  ARAH_E_BADARG for a negative count or one above INT32_MAX, H or W <= 0,
+ * H W above INT32_MAX, an unknown cull code or a missing pointer; n_faces = 0 or n_verts = 0 writes the background. */
+int arah_mesh_rasterize(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t H, int32_t W, float z_near,
+                        int32_t cull, uint64_t* keys, int32_t* pix_to_face, float* depth, float* bary, void* stream);
+/* The same with the three thresholds of pass A given instead of built in: a face whose clipped bounding box has at most small_area
+ * pixels is drawn by its lane, at most wave_area by its wave, at most huge_area by one workgroup, a larger one by 64 workgroups.
+ * Every choice gives the same image; tools/mesh_render_bench.py measures them.  0 <= small_area <= wave_area <= huge_area. */
+int arah_mesh_rasterize_debug(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t H, int32_t W,
+                              float z_near, int32_t cull, int32_t small_area, int32_t wave_area, int32_t huge_area, uint64_t* keys,
+                              int32_t* pix_to_face, float* depth, float* bary, void* stream);
+/* Per-vertex attributes attr [n_verts][n_channels] drawn with the pix_to_face / bary of arah_mesh_rasterize: out [H][W][n_channels]
+ * = float((b0 a0 + b1 a1) + b2 a2) in double, every operation rounded on its own; `background` where pix_to_face names no face of
+ * this mesh or the face an id out of range.  1 <= n_channels <= 32.  Sizes and errors as for arah_mesh_rasterize. */
+int arah_mesh_interpolate(const int32_t* pix_to_face, const float* bary, int32_t H, int32_t W, const int32_t* faces, int64_t n_faces,
+                          const float* attr, int64_t n_verts, int32_t n_channels, float background, float* out, void* stream);
 /* raw canonical x_hat [P,3] -> d x_bar / d x_hat [P,3,3] */
 int arah_skin_jacobian(const ArahFrame* h_frame, const float* x_hat, int32_t n_pts, float* jac,
                        void* workspace, size_t workspace_bytes, void* stream);
