@@ -2849,6 +2849,7 @@ __global__ void k_points_cam(FrameDev fr, int n, RaySet rs, const float* dists, 
 #include "meshquery.hpp"
 #include "metrics.hpp"
 #include "meshdist.hpp"
+#include "meshray.hpp"
 #include "pointdist.hpp"
 namespace {
 
@@ -5573,6 +5574,37 @@ int arah_mesh_closest(const void* index, size_t index_bytes, const float* tris, 
                        (const MdHeader*)m.hdr, (const int*)m.cell_base, (const uint8_t*)m.dt[0], (const int*)m.refs,
                        (const int*)m.big, pts, (int)n_pts, d2, (int*)face, closest, (int*)tested);
     return check_launch();
+}
+
+int arah_mesh_raycast_debug(const void* index, size_t index_bytes, const float* tris, int32_t n_faces, const float* origins,
+                            const float* dirs, int32_t n_rays, double t_min, double t_max, int32_t cull, int32_t mode,
+                            int32_t workgroup, double* t, int32_t* face, double* bary, uint8_t* hit, int32_t* tested, void* stream) {
+    if (!index || !tris || n_faces < 1 || n_faces > (1 << 26) || n_rays < 0 || n_rays > INT32_MAX - 256 || cull < 0 || cull > 2)
+        return ARAH_E_BADARG;
+    const int kind = mode, wg = workgroup;
+    if (kind < 0 || kind > 1 || (wg != 64 && wg != 128 && wg != 256) || t_min != t_min || t_max != t_max) return ARAH_E_BADARG;
+    const MdIndex m = carve_mesh_index(const_cast<void*>(index), n_faces);
+    if (index_bytes < m.bytes) return ARAH_E_WORKSPACE;
+    if (n_rays == 0) return ARAH_OK;
+    if (!origins || !dirs || (kind == 0 ? (!t || !face || !bary) : !hit)) return ARAH_E_BADARG;
+    const int g = (n_rays + wg - 1) / wg;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (kind == 0)
+        hipLaunchKernelGGL(k_rc_cast<false>, dim3(g), dim3(wg), 0, s, tris, (const MdHeader*)m.hdr, (const int*)m.cell_base,
+                           (const uint8_t*)m.dt[0], (const int*)m.refs, (const int*)m.big, origins, dirs, (int)n_rays, t_min, t_max,
+                           (int)cull, t, (int*)face, bary, hit, (int*)tested);
+    else
+        hipLaunchKernelGGL(k_rc_cast<true>, dim3(g), dim3(wg), 0, s, tris, (const MdHeader*)m.hdr, (const int*)m.cell_base,
+                           (const uint8_t*)m.dt[0], (const int*)m.refs, (const int*)m.big, origins, dirs, (int)n_rays, t_min, t_max,
+                           (int)cull, t, (int*)face, bary, hit, (int*)tested);
+    return check_launch();
+}
+
+int arah_mesh_raycast(const void* index, size_t index_bytes, const float* tris, int32_t n_faces, const float* origins,
+                      const float* dirs, int32_t n_rays, double t_min, double t_max, int32_t cull, int32_t mode, double* t,
+                      int32_t* face, double* bary, uint8_t* hit, int32_t* tested, void* stream) {
+    return arah_mesh_raycast_debug(index, index_bytes, tris, n_faces, origins, dirs, n_rays, t_min, t_max, cull, mode, kRcThreads, t,
+                                   face, bary, hit, tested, stream);
 }
 
 int arah_face_area_cumsum(const float* tris, int32_t n_faces, double* cum, void* stream) {

@@ -11,7 +11,9 @@ on the device"); `mesh_adjacency` / `mesh_topology` / `vertex_normals` / `smooth
 watertight, the mesh's own normals, and Laplacian / Taubin smoothing (DESIGN.md "Adjacency, normals and smoothing on the device").
 Ground truth that is a SCAN -- a point cloud, with or without normals -- is scored through the exact
 nearest-point query hip.point_index / hip.point_nearest (DESIGN.md "Scoring against point clouds"): `PointCloud`, `nearest_points`,
-`load_points` / `save_points` / `load_geometry`, and F-scores at distance thresholds (`thresholds=` of `mesh_metrics`)."""
+`load_points` / `save_points` / `load_geometry`, and F-scores at distance thresholds (`thresholds=` of `mesh_metrics`).
+Rays against a mesh -- `cast_rays`, `occluded`, `vertex_visibility`, `camera_rays`, `ambient_occlusion` -- go through hip.mesh_raycast
+on the same index (DESIGN.md "Casting rays against meshes on the device")."""
 import collections
 import math
 
@@ -879,6 +881,246 @@ def render_mesh(verts, faces, height, width, camera=None, attributes=None, cull=
                 a = vertex_normals(v32, faces)
             res[name] = interpolate(p2f, bary, faces, a.detach().to(torch.float32).contiguous(), background=background)
     return res
+
+
+# ---- casting rays against meshes (DESIGN.md "Casting rays against meshes on the device") ---------------------------------
+def _ray_args(origins, dirs, dev, what):
+    for name, x in (("origins", origins), ("dirs", dirs)):
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] != 3 or not x.dtype.is_floating_point:
+            raise ValueError("%s: %s must be a floating-point (R, 3) tensor" % (what, name))
+        if x.device != dev:
+            raise ValueError("%s: %s live on %s, the mesh on %s" % (what, name, x.device, dev))
+    if origins.shape[0] != dirs.shape[0]:
+        raise ValueError("%s: %d origins but %d directions" % (what, origins.shape[0], dirs.shape[0]))
+    return origins.detach().to(torch.float32).contiguous(), dirs.detach().to(torch.float32).contiguous()
+
+
+def _ray_soup(mesh, what):
+    """The soup rays are cast against: `_as_soup`, with every face of a (verts, faces) pair that names a vertex out of range
+    replaced by three corners at 0 -- a face without area, which no ray hits (its det is exactly 0) --, as mesh_components,
+    face_normals and the interpolation skip such a face.  No host synchronisation."""
+    tris, _ = _as_soup(mesh, what)
+    if isinstance(mesh, (tuple, list)):
+        faces = torch.as_tensor(mesh[1]).to(tris.device).long()
+        ok = ((faces >= 0) & (faces < int(torch.as_tensor(mesh[0]).shape[0]))).all(1)
+        tris = torch.where(ok[:, None, None], tris, torch.zeros_like(tris)).contiguous()
+    return tris
+
+
+def _ray_index(tris, index, what):
+    from . import hip
+    if index is None:
+        return hip.mesh_index(tris)
+    if not isinstance(index, hip.MeshIndex) or index.tris.shape != tris.shape or index.tris.device != tris.device:
+        raise ValueError("%s: index must be the hip.mesh_index of this mesh's soup" % what)
+    return index
+
+
+def cast_rays(mesh, origins, dirs, t_min=0.0, t_max=float("inf"), cull="none", attributes=None, index=None):
+    """What the rays origins + t dirs ((R,3) each; dirs need not be unit, t is in units of |dirs|) see first of a mesh -- an (F,3,3)
+    soup or a (verts, faces) pair as in `mesh_metrics`.  The rule is meshing.mesh_raycast: watertight (a ray through a shared edge
+    or vertex hits one of the faces), float64 on the float32 inputs, the nearest hit with t_min <= t <= t_max, the lowest face id on
+    a tie; cull="back" drops the hits a ray makes running ALONG a face's normal (b-a)x(c-a), "front" those against it.
+    -> a dict of tensors on the mesh's device: hit (R,) bool, t (R,) float64 (+inf on a miss), face (R,) int32 (-1), bary (R,3)
+    float64 (0), points (R,3) float64 the barycentric combination of the face's corners (0), normal (R,3) float32 the face's unit
+    normal (0), and one (R,C) float32 tensor per attribute (0 on a miss).  attributes: as in `render_mesh`, a dict name -> (V,C)
+    per-vertex tensor, "vertex_normal": True for the mesh's own normals; interpolated by the rule of meshing.interpolate_attributes
+    with the rays as a 1 x R image and the barycentrics rounded to float32; they need the (verts, faces) form.  A face that names
+    a vertex out of range is never hit.  index: the
+    hip.mesh_index of the mesh's soup built earlier, or None.  hip.mesh_raycast for a mesh on the GPU (no host synchronisation),
+    the specification for one on the host; equal bit for bit."""
+    from . import meshing
+    tris = _ray_soup(mesh, "cast_rays")
+    dev = tris.device
+    o, d = _ray_args(origins, dirs, dev, "cast_rays")
+    t_min, t_max, _ = meshing.check_raycast_args(tris, o, d, t_min, t_max, cull, "cast_rays")
+    indexed = isinstance(mesh, (tuple, list))
+    attributes = dict(attributes or {})
+    if attributes and not indexed:
+        raise ValueError("cast_rays: attributes are per vertex and need the (verts, faces) form of the mesh")
+    if indexed:
+        verts, faces = torch.as_tensor(mesh[0]).detach().to(torch.float32).contiguous(), torch.as_tensor(mesh[1]).to(dev)
+        V = int(verts.shape[0])
+    for name, a in attributes.items():
+        if a is True and name == "vertex_normal":
+            continue
+        if name in ("hit", "t", "face", "bary", "points", "normal"):
+            raise ValueError("cast_rays: an attribute cannot be called %r" % name)
+        if not isinstance(a, torch.Tensor) or a.dim() != 2 or not a.dtype.is_floating_point or not 1 <= int(a.shape[1]) <= 32:
+            raise ValueError("cast_rays: attribute %r must be a floating-point (V, C) tensor with 1 <= C <= 32%s"
+                             % (name, " (True only for vertex_normal)" if a is True else ""))
+        if int(a.shape[0]) != V or a.device != dev:
+            raise ValueError("cast_rays: attribute %r must have one row per vertex (%d) on the mesh's device" % (name, V))
+    with torch.no_grad():
+        if tris.is_cuda:
+            from . import hip
+            t, face, bary, _ = hip.mesh_raycast(_ray_index(tris, index, "cast_rays"), o, d, t_min, t_max, cull)
+        else:
+            if index is not None:
+                raise ValueError("cast_rays: an index belongs to a mesh on the GPU")
+            t, face, bary = meshing.mesh_raycast(tris, o, d, t_min, t_max, cull)
+        hit = face >= 0
+        corners = tris.double()[face.long().clamp_min(0)]                                        # (R,3,3)
+        points = (bary[:, 0:1] * corners[:, 0] + bary[:, 1:2] * corners[:, 1]) + bary[:, 2:3] * corners[:, 2]
+        points = torch.where(hit[:, None], points, torch.zeros_like(points))
+        soup_faces = torch.arange(3 * tris.shape[0], device=dev).reshape(-1, 3)
+        normal = face_normals(tris.reshape(-1, 3), soup_faces)[face.long().clamp_min(0)]
+        normal = torch.where(hit[:, None], normal, torch.zeros_like(normal))
+        res = {"hit": hit, "t": t, "face": face, "bary": bary, "points": points, "normal": normal}
+        if attributes:
+            interpolate = _cc_backend(faces).mesh_interpolate if tris.is_cuda else meshing.interpolate_attributes
+            R = int(o.shape[0])
+            for name, a in attributes.items():
+                if a is True:
+                    a = vertex_normals(verts, faces)
+                a = a.detach().to(torch.float32).contiguous()
+                if R == 0:
+                    res[name] = torch.zeros(0, a.shape[1], dtype=torch.float32, device=dev)
+                    continue
+                res[name] = interpolate(face.reshape(1, R), bary.to(torch.float32).reshape(1, R, 3), faces, a, background=0.0)[0]
+    return res
+
+
+def occluded(mesh, origins, dirs, t_min, t_max, index=None):
+    """(R,) bool: whether anything of the mesh (as in `cast_rays`) meets the ray origins + t dirs within t_min <= t <= t_max -- for a
+    segment from p to q: origins p, dirs q - p, t in [0, 1].  hip.mesh_raycast(mode="any") on the GPU, which stops at the first
+    accepted face; the specification's face >= 0 on the host; the same answer."""
+    from . import meshing
+    tris = _ray_soup(mesh, "occluded")
+    o, d = _ray_args(origins, dirs, tris.device, "occluded")
+    t_min, t_max, _ = meshing.check_raycast_args(tris, o, d, t_min, t_max, "none", "occluded")
+    with torch.no_grad():
+        if tris.is_cuda:
+            from . import hip
+            return hip.mesh_raycast(_ray_index(tris, index, "occluded"), o, d, t_min, t_max, mode="any")[0]
+        if index is not None:
+            raise ValueError("occluded: an index belongs to a mesh on the GPU")
+        return meshing.mesh_raycast(tris, o, d, t_min, t_max)[1] >= 0
+
+
+def vertex_visibility(verts, faces, eye, eps=1e-4):
+    """(V,) bool: which vertices of the indexed mesh a point `eye` (three numbers or a tensor of three) sees.  A vertex is visible
+    when the segment from the vertex, moved by eps along its own vertex normal (`vertex_normals`) so that its own faces do not
+    hide it, to the eye meets no face.  The normals must point OUT of the body: the level sets of `posed_mesh` / `canonical_mesh` are
+    wound the other way ("Normals") -- pass faces.flip(1) for them."""
+    v32, faces, _ = _smooth_args(verts, faces, None, "vertex_visibility")
+    eye = eye.detach().to(v32.device, torch.float32).reshape(-1) if isinstance(eye, torch.Tensor) else \
+        torch.tensor([float(x) for x in eye], dtype=torch.float32, device=v32.device)
+    if eye.numel() != 3:
+        raise ValueError("vertex_visibility: eye must be a point, three numbers")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not eps >= 0.0:
+        raise ValueError("vertex_visibility: eps must be a number >= 0, got %r" % (eps,))
+    with torch.no_grad():
+        start = v32 + float(eps) * vertex_normals(v32, faces)
+        return ~occluded((v32, faces), start, eye[None, :] - start, 0.0, 1.0)
+
+
+def camera_rays(camera, height, width):
+    """The rays through the pixel centres (j + 0.5, i + 0.5) of a height x width image of `camera` (check_camera), row by row: ->
+    origins, dirs (H W, 3) float32 on the camera tensors' device (the host for a look-at camera of numbers).  A direction has
+    view depth 1 -- it is NOT unit --, so the t of `cast_rays` along it is the view depth `render_mesh` draws, and
+    project_mesh(origin + dir) is the pixel centre."""
+    from . import meshing
+    kind = check_camera(camera, "camera_rays")
+    for name, x in (("height", height), ("width", width)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or int(x) < 1:
+            raise ValueError("camera_rays: %s must be an integer >= 1, got %r" % (name, x))
+    H, W = int(height), int(width)
+    f64 = torch.float64
+    if kind == "opencv":
+        dev = camera["K"].device
+        R = camera["cam_rot"].detach().to(dev, f64).reshape(3, 3)
+        t = camera["cam_trans"].detach().to(dev, f64).reshape(3)
+        K = camera["K"].detach().to(dev, f64).reshape(3, 3)
+    else:
+        at = camera.get("at")
+        dev = at.device if isinstance(at, torch.Tensor) else torch.device("cpu")
+    u = (torch.arange(W, dtype=f64, device=dev) + 0.5)[None, :].expand(H, W).reshape(-1)
+    v = (torch.arange(H, dtype=f64, device=dev) + 0.5)[:, None].expand(H, W).reshape(-1)
+    if kind == "opencv":
+        x_cam = torch.stack([(u - K[0, 2]) / K[0, 0], (v - K[1, 2]) / K[1, 1], torch.ones_like(u)], dim=1)
+        dirs = x_cam @ R                     # R^T x_cam per row
+        origin = -(R.t() @ t)
+    else:
+        cam, R = meshing._lookat(dev, float(camera["azim"]), float(camera.get("dist", 2.0)))
+        cam, R = cam.to(f64), R.to(f64)
+        if at is not None:
+            cam = cam + (at.detach().to(dev, torch.float32).reshape(3) if isinstance(at, torch.Tensor) else
+                         torch.tensor([float(x) for x in at], dtype=torch.float32, device=dev)).to(f64)
+        f = 1.0 / math.tan(math.radians(float(camera.get("fov", 60.0))) / 2.0)
+        side = min(H, W)
+        xv = torch.stack([(1.0 - (u - (W - side) / 2.0) * 2.0 / side) / f, (1.0 - (v - (H - side) / 2.0) * 2.0 / side) / f,
+                          torch.ones_like(u)], dim=1)
+        dirs = xv @ R.t()                    # the columns of R are the view axes
+        origin = cam
+    return origin.to(torch.float32)[None, :].expand(H * W, 3).contiguous(), dirs.to(torch.float32).contiguous()
+
+
+_AO_TABLES = {}
+
+
+def ao_directions(n_rays, seed):
+    """The fixed table of `ambient_occlusion`: (n_rays, 3) float64 on the host, unit directions about +z with a density
+    proportional to the cosine (Malley: a uniform disc lifted onto the hemisphere), from torch's CPU generator seeded with `seed`."""
+    key = (int(n_rays), int(seed))
+    if key not in _AO_TABLES:
+        g = torch.Generator().manual_seed(int(seed))
+        u = torch.rand(int(n_rays), 2, generator=g, dtype=torch.float64)
+        r, phi = torch.sqrt(u[:, 0]), 2.0 * math.pi * u[:, 1]
+        _AO_TABLES[key] = torch.stack([r * torch.cos(phi), r * torch.sin(phi), torch.sqrt(1.0 - u[:, 0])], dim=1)
+    return _AO_TABLES[key]
+
+
+def ambient_occlusion(verts, faces, n_rays=64, seed=0, radius=float("inf"), eps=1e-4, adjacency=None):
+    """(V,) float32 in [0, 1]: the share of n_rays directions about every vertex's normal in which the mesh does not hide the sky
+    within `radius` -- 1 on a convex body, less in folds and armpits.  The directions are those of `ao_directions(n_rays, seed)`
+    turned into the frame of the vertex's normal (`vertex_normals`; adjacency as there), the rays start eps along the normal, and
+    ONE any-hit query (`occluded`) answers all V n_rays of them.  The frame is built in float64 from operations that round the
+    same way on the host and on the device, and the count of open directions is an integer: host and device agree exactly.  A
+    vertex without a normal gets 1.  The normals must point OUT of the body: for the level sets of `posed_mesh` / `canonical_mesh`,
+    which are wound the other way ("Normals"), pass faces.flip(1), as model.render_mesh does."""
+    v32, faces, adjacency = _smooth_args(verts, faces, adjacency, "ambient_occlusion")
+    if isinstance(n_rays, bool) or not isinstance(n_rays, (int, np.integer)) or not 1 <= int(n_rays) <= 4096:
+        raise ValueError("ambient_occlusion: n_rays must be an integer in [1, 4096], got %r" % (n_rays,))
+    if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not radius > 0.0:
+        raise ValueError("ambient_occlusion: radius must be a number > 0, got %r" % (radius,))
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not eps >= 0.0:
+        raise ValueError("ambient_occlusion: eps must be a number >= 0, got %r" % (eps,))
+    V, dev, n_rays = int(v32.shape[0]), v32.device, int(n_rays)
+    if V * n_rays > 2 ** 31 - 1:
+        raise ValueError("ambient_occlusion: at most 2^31 - 1 rays")
+    if V == 0 or faces.shape[0] == 0:
+        return torch.ones(V, dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        start, dirs = ao_rays(v32, faces, n_rays, seed, float(eps), adjacency)
+        hidden = occluded((v32, faces), start, dirs, 0.0, float(radius))
+        open_count = n_rays - hidden.reshape(V, n_rays).sum(1)
+        return open_count.to(torch.float32) / float(n_rays)
+
+
+def ao_rays(v32, faces, n_rays, seed, eps, adjacency=None):
+    """The rays of `ambient_occlusion`: -> origins, dirs (V n_rays, 3) float32, vertex by vertex."""
+    V, dev = int(v32.shape[0]), v32.device
+    n32 = vertex_normals(v32, faces, adjacency=adjacency)
+    n = n32.double()
+    nx, ny, nz = n[:, 0], n[:, 1], n[:, 2]
+    # a tangent: e x n with e the axis the normal is least along, normalised; the other: n x tangent
+    use_x = (nx.abs() <= ny.abs()) & (nx.abs() <= nz.abs())
+    use_y = ~use_x & (ny.abs() <= nz.abs())
+    zero = torch.zeros_like(nx)
+    tx = torch.where(use_x, zero, torch.where(use_y, nz, -ny))
+    ty = torch.where(use_x, -nz, torch.where(use_y, zero, nx))
+    tz = torch.where(use_x, ny, torch.where(use_y, -nx, zero))
+    length = torch.sqrt((tx * tx + ty * ty) + tz * tz)
+    tx, ty, tz = tx / length, ty / length, tz / length
+    bx, by, bz = ny * tz - nz * ty, nz * tx - nx * tz, nx * ty - ny * tx
+    tab = ao_directions(n_rays, seed).to(dev)
+    dx, dy, dz = tab[None, :, 0], tab[None, :, 1], tab[None, :, 2]
+    dirs = torch.stack([(dx * tx[:, None] + dy * bx[:, None]) + dz * nx[:, None],
+                        (dx * ty[:, None] + dy * by[:, None]) + dz * ny[:, None],
+                        (dx * tz[:, None] + dy * bz[:, None]) + dz * nz[:, None]], dim=2).to(torch.float32)   # (V,n,3)
+    start = (v32 + float(eps) * n32)[:, None, :].expand(V, n_rays, 3)
+    return start.reshape(-1, 3), dirs.reshape(-1, 3)
 
 
 # ---- ground-truth files -------------------------------------------------------------------------------------------------

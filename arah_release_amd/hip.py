@@ -139,7 +139,7 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_mesh_components_scratch_bytes", "arah_mesh_components", "arah_mesh_select_scratch_bytes", "arah_mesh_select",
            "arah_mesh_simplify_scratch_bytes", "arah_mesh_simplify",
            "arah_mesh_adjacency_scratch_bytes", "arah_mesh_adjacency", "arah_mesh_vertex_normals", "arah_mesh_smooth",
-           "arah_mesh_rasterize", "arah_mesh_rasterize_debug", "arah_mesh_interpolate",
+           "arah_mesh_rasterize", "arah_mesh_rasterize_debug", "arah_mesh_interpolate", "arah_mesh_raycast", "arah_mesh_raycast_debug",
            "arah_point_index_bytes", "arah_point_index_build", "arah_point_nearest", "arah_sample_scores_bytes", "arah_sample_scores"]
 
 _lib = None
@@ -1652,6 +1652,47 @@ def mesh_closest(index, pts, want_closest=True, want_tested=False):
                                      C.c_int32(index.tris.shape[0]), _ptr(pts), C.c_int32(P), _ptr(d2), _ptr(face),
                                      _ptr(closest), _ptr(tested), _stream()), "arah_mesh_closest")
     return d2, face, closest, tested
+
+
+RAY_MODES = {"first": 0, "any": 1}
+
+
+def mesh_raycast(index, origins, dirs, t_min=0.0, t_max=float("inf"), cull="none", mode="first", want_tested=False, workgroup=None):
+    """Rays against the indexed soup (arah_mesh_raycast, csrc/meshray.hpp): index from `mesh_index`, origins and dirs (R,3) float32 on
+    its device.  mode="first" -> t (R,) float64, face (R,) int32, bary (R,3) float64, tested (R,) int32 (ray-triangle tests made) or
+    None: meshing.mesh_raycast on index.tris bit for bit (a miss: +inf, -1, 0).  mode="any" -> hit (R,) bool, tested: whether any
+    face is accepted in [t_min, t_max]; the walk stops at the first.  cull "none" / "back" / "front" as in the specification.  Every
+    ray of an index built from a soup with a non-finite vertex misses.  workgroup: 64, 128 or 256 threads instead of the built-in
+    size (arah_mesh_raycast_debug; the results are the same for every choice), for measuring it.  No host synchronisation."""
+    from . import meshing
+    lib = load_library()
+    if not isinstance(index, MeshIndex):
+        raise ValueError("index must come from mesh_index")
+    t_min, t_max, cull_code = meshing.check_raycast_args(index.tris, origins, dirs, t_min, t_max, cull, "mesh_raycast")
+    if mode not in RAY_MODES:
+        raise ValueError("mesh_raycast: mode must be 'first' or 'any', got %r" % (mode,))
+    if workgroup is not None and workgroup not in (64, 128, 256):
+        raise ValueError("mesh_raycast: workgroup must be 64, 128 or 256, got %r" % (workgroup,))
+    dev = _same_device(index.buf, index.tris, origins, dirs)
+    origins, dirs = origins.detach().contiguous(), dirs.detach().contiguous()
+    R = int(origins.shape[0])
+    first = mode == "first"
+    t = torch.empty(R, dtype=torch.float64, device=dev) if first else None
+    face = torch.empty(R, dtype=torch.int32, device=dev) if first else None
+    bary = torch.empty(R, 3, dtype=torch.float64, device=dev) if first else None
+    hit = None if first else torch.empty(R, dtype=torch.uint8, device=dev)
+    tested = torch.empty(R, dtype=torch.int32, device=dev) if want_tested else None
+    with _on_device(dev):
+        head = (_ptr(index.buf), C.c_size_t(index.buf.numel()), _ptr(index.tris), C.c_int32(index.tris.shape[0]), _ptr(origins),
+                _ptr(dirs), C.c_int32(R), C.c_double(t_min), C.c_double(t_max), C.c_int32(cull_code), C.c_int32(RAY_MODES[mode]))
+        tail = (_ptr(t), _ptr(face), _ptr(bary), _ptr(hit), _ptr(tested), _stream())
+        if workgroup is None:
+            _check(lib.arah_mesh_raycast(*head, *tail), "arah_mesh_raycast")
+        else:
+            _check(lib.arah_mesh_raycast_debug(*head, C.c_int32(int(workgroup)), *tail), "arah_mesh_raycast_debug")
+    if first:
+        return t, face, bary, tested
+    return hit.bool(), tested
 
 
 def face_area_cumsum(tris):

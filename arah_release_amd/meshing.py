@@ -766,6 +766,118 @@ def interpolate_attributes(pix_to_face, bary, faces, attr, background=0.0):
     return torch.where(named[..., None], val, out)
 
 
+RAY_CULL = {"none": 0, "back": 1, "front": 2}
+
+
+def check_raycast_args(tris, origins, dirs, t_min, t_max, cull, what="mesh_raycast"):
+    """The arguments of `mesh_raycast`, checked (nothing is converted or copied): -> (float(t_min), float(t_max), the cull code)."""
+    if not isinstance(tris, torch.Tensor) or tris.dim() != 3 or tuple(tris.shape[1:]) != (3, 3) or tris.dtype != torch.float32:
+        raise ValueError("%s: tris must be an (F, 3, 3) float32 triangle soup" % what)
+    if tris.shape[0] < 1:
+        raise ValueError("%s: tris holds no triangle" % what)
+    for name, x in (("origins", origins), ("dirs", dirs)):
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] != 3 or x.dtype != torch.float32:
+            raise ValueError("%s: %s must be (R, 3) float32" % (what, name))
+    if origins.shape[0] != dirs.shape[0]:
+        raise ValueError("%s: %d origins but %d directions" % (what, origins.shape[0], dirs.shape[0]))
+    if len({tris.device, origins.device, dirs.device}) != 1:
+        raise ValueError("%s: tris, origins and dirs must live on one device" % what)
+    if int(origins.shape[0]) > 2 ** 31 - 1 - 256 or int(tris.shape[0]) > 2 ** 31 - 1:
+        raise ValueError("%s: at most 2^31 - 257 rays and 2^31 - 1 faces" % what)
+    for name, x in (("t_min", t_min), ("t_max", t_max)):
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or math.isnan(float(x)):
+            raise ValueError("%s: %s must be a number, got %r" % (what, name, x))
+    if cull not in RAY_CULL:
+        raise ValueError("%s: cull must be 'none', 'back' or 'front', got %r" % (what, cull))
+    return float(t_min), float(t_max), RAY_CULL[cull]
+
+
+def mesh_raycast(tris, origins, dirs, t_min=0.0, t_max=float("inf"), cull="none", chunk_bytes=1 << 28):
+    """The first hit of every ray o + t d with the triangle soup tris (F,3,3) float32, origins and dirs (R,3) float32 (dirs need not
+    be unit: t is in units of |d|): -> t (R,) float64, face (R,) int32, bary (R,3) float64; a miss is face -1, t +inf, bary 0.  Brute
+    force over all faces, on the tensors' device; the specification of arah_mesh_raycast (csrc/meshray.hpp).
+
+    The test is Woop, Benthin and Wald's watertight one ("Watertight Ray/Triangle Intersection", JCGT 2013) in float64 on the float32
+    inputs, every operation rounded on its own.  kz = the axis of the largest |d| (the lowest on a tie), kx = (kz+1)%3,
+    ky = (kx+1)%3, swapped when d[kz] < 0; Sx = d[kx]/d[kz], Sy = d[ky]/d[kz], Sz = 1/d[kz].  For a face a, b, c: A = a - o,
+    Ax = A[kx] - Sx A[kz], Ay = A[ky] - Sy A[kz], Az = A[kz] (B, C alike); U = Cx By - Cy Bx, V = Ax Cy - Ay Cx, W = Bx Ay - By Ax.
+    The face is missed when (U<0 or V<0 or W<0) and (U>0 or V>0 or W>0) -- inclusive: a ray through a shared edge or vertex is
+    accepted by at least one of the faces -- or when det = (U+V)+W is 0.  det > 0 is a hit on the FRONT of the face, the side its
+    normal (b-a)x(c-a) points to (the ray runs against the normal); cull="back" drops the hits with det < 0, cull="front" those
+    with det > 0.  t = ((U (Sz Az) + V (Sz Bz)) + W (Sz Cz)) / det is accepted when it is finite, t_min <= t <= t_max, and the
+    hit is ON THE RAY: with bary = (U, V, W) / det and A0 = a - o (B0, C0 alike), |((bary_0 A0 + bary_1 B0) + bary_2 C0) - t d| <=
+    2^-26 m along each of kx, ky, kz, m the largest magnitude among the coordinates of o, a, b, c.  Woop's test leaves this to the
+    conditioning of det: for a ray IN the plane of a face two of U, V, W are exactly 0 and the third is rounding noise, det is
+    not 0, and a "hit" comes out at a corner far beside the ray; such a face is a miss here (a true hit is on the ray to
+    ~2^-50 m).  The answer is the lexicographic minimum of (t, face) over the accepted faces, bary of that face.  A ray whose
+    direction is zero or not finite, or whose origin is not finite, hits nothing; a face with a vertex that is not finite is never
+    hit.  chunk_bytes bounds the (rays x faces) temporaries; the result does not depend on it."""
+    t_min, t_max, cull_code = check_raycast_args(tris, origins, dirs, t_min, t_max, cull)
+    f64, dev = torch.float64, tris.device
+    R, F = int(origins.shape[0]), int(tris.shape[0])
+    t_out = torch.full((R,), float("inf"), dtype=f64, device=dev)
+    face_out = torch.full((R,), -1, dtype=torch.int32, device=dev)
+    bary_out = torch.zeros(R, 3, dtype=f64, device=dev)
+    if R == 0:
+        return t_out, face_out, bary_out
+    T, O, D = tris.detach().to(f64), origins.detach().to(f64), dirs.detach().to(f64)
+    face_ok = torch.isfinite(T).all(-1).all(-1)                                             # (F,)
+    face_max = T.abs().amax((1, 2))
+    ad = D.abs()
+    kz = torch.where((ad[:, 0] >= ad[:, 1]) & (ad[:, 0] >= ad[:, 2]), 0, torch.where(ad[:, 1] >= ad[:, 2], 1, 2))
+    neg = torch.gather(D, 1, kz[:, None])[:, 0] < 0
+    ray_ok = torch.isfinite(D).all(1) & torch.isfinite(O).all(1) & (ad > 0).any(1)
+    ids = torch.arange(F, device=dev)
+    per = max(1, int(chunk_bytes) // (F * 8 * 40))
+    for axis in range(3):
+        for swap in (False, True):
+            kx, ky = (axis + 1) % 3, (axis + 2) % 3
+            if swap:
+                kx, ky = ky, kx
+            rows_all = torch.nonzero(ray_ok & (kz == axis) & (neg == swap))[:, 0]
+            for r0 in range(0, int(rows_all.shape[0]), per):
+                rows = rows_all[r0:r0 + per]
+                o, d = O[rows], D[rows]
+                Sx, Sy, Sz = (d[:, kx] / d[:, axis])[:, None], (d[:, ky] / d[:, axis])[:, None], (1.0 / d[:, axis])[:, None]
+
+                def sheared(corner):
+                    Pz = T[None, :, corner, axis] - o[:, axis, None]
+                    Px0, Py0 = T[None, :, corner, kx] - o[:, kx, None], T[None, :, corner, ky] - o[:, ky, None]
+                    return Px0 - Sx * Pz, Py0 - Sy * Pz, Pz, Px0, Py0
+                Ax, Ay, Az, Ax0, Ay0 = sheared(0)
+                Bx, By, Bz, Bx0, By0 = sheared(1)
+                Cx, Cy, Cz, Cx0, Cy0 = sheared(2)
+                U = Cx * By - Cy * Bx
+                V = Ax * Cy - Ay * Cx
+                W = Bx * Ay - By * Ax
+                miss = ((U < 0) | (V < 0) | (W < 0)) & ((U > 0) | (V > 0) | (W > 0))
+                det = (U + V) + W
+                miss = miss | (det == 0)
+                if cull_code == 1:
+                    miss = miss | (det < 0)
+                elif cull_code == 2:
+                    miss = miss | (det > 0)
+                t = ((U * (Sz * Az) + V * (Sz * Bz)) + W * (Sz * Cz)) / det
+                ok = ~miss & torch.isfinite(t) & (t >= t_min) & (t <= t_max) & face_ok[None, :]
+                bu, bv, bw = U / det, V / det, W / det
+                tol = torch.maximum(o.abs().amax(1)[:, None], face_max[None, :]) * 2.0 ** -26
+                for P0, Q0, R0, k in ((Ax0, Bx0, Cx0, kx), (Ay0, By0, Cy0, ky), (Az, Bz, Cz, axis)):
+                    ok = ok & ((((bu * P0 + bv * Q0) + bw * R0) - t * d[:, k, None]).abs() <= tol)
+                tm = torch.where(ok, t, torch.full_like(t, float("inf")))
+                best = tm.min(dim=1).values
+                first = torch.where(ok & (tm == best[:, None]), ids[None, :], F).min(dim=1).values     # F: nothing accepted
+                hit = first < F
+                g = first.clamp(max=F - 1)[:, None]
+                pick = lambda x: torch.gather(x, 1, g)[:, 0]
+                dg = pick(det)
+                zero = torch.zeros_like(dg)
+                t_out[rows] = torch.where(hit, pick(t), torch.full_like(dg, float("inf")))
+                face_out[rows] = torch.where(hit, first, torch.full_like(first, -1)).to(torch.int32)
+                bary_out[rows] = torch.stack([torch.where(hit, pick(bu), zero), torch.where(hit, pick(bv), zero),
+                                              torch.where(hit, pick(bw), zero)], dim=1)
+    return t_out, face_out, bary_out
+
+
 def face_normals(tri):
     """Unit right-hand normals of a triangle soup (F,3,3) (pytorch3d Meshes.faces_normals_packed)."""
     n = torch.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0], dim=1)

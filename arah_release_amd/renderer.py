@@ -1084,7 +1084,9 @@ class MetaAvatarRender(nn.Module):
         normalised cube (the synthetic subject's lies at z in [-0.06, 0.29], most of it near 0.08), a silhouette's area goes with
         1 / depth^2, and only a camera that turns about the bulk of the body sees it equally large, mirrored, from the front and
         from the back; "at": (0, 0, 0) gives the other camera.  attributes: per-vertex names of `canonical_mesh` ("color", "normal", "weights",
-        "verts_posed", "vertex_normal") and "face_normal"; each becomes an (H,W,C) image, 0 where nothing is drawn.
+        "verts_posed", "vertex_normal"), "face_normal" and "ambient_occlusion" ((H,W,1): geometry.ambient_occlusion of the mesh that is
+        drawn, 64 directions per vertex, 1 = open sky -- a shading for a mesh without colours); each becomes an (H,W,C) image, 0
+        where nothing is drawn.
 
         The NORMALS drawn are those of the mesh that is drawn: in posed space "vertex_normal" and "face_normal" are the posed
         mesh's own (geometry.vertex_normals of the posed vertices, world axes), not the canonical mesh's rotated; in canonical
@@ -1096,7 +1098,7 @@ class MetaAvatarRender(nn.Module):
         from . import geometry
         if space not in ("posed", "canonical"):
             raise ValueError("render_mesh: space must be 'posed' or 'canonical', got %r" % (space,))
-        names = ("weights", "verts_posed", "normal", "color", "vertex_normal", "face_normal")
+        names = ("weights", "verts_posed", "normal", "color", "vertex_normal", "face_normal", "ambient_occlusion")
         attributes = tuple(attributes)
         bad = set(attributes) - set(names)
         if bad:
@@ -1109,14 +1111,52 @@ class MetaAvatarRender(nn.Module):
             camera = {"azim": 0.0} if view is None else view
             if geometry.check_camera(camera, "render_mesh: view") != "lookat":
                 raise ValueError("render_mesh: view must be a look-at camera {'azim': degrees[, 'dist', 'fov', 'at']}")
-        own = ("vertex_normal", "face_normal")   # taken from the mesh that is drawn
+        own = ("vertex_normal", "face_normal", "ambient_occlusion")   # taken from the mesh that is drawn
         wanted = {a for a in attributes if a not in own} | ({"verts_posed"} if space == "posed" else set())
         mesh = self.canonical_mesh(inputs, n_side=n_side, attributes=tuple(sorted(wanted)), clean=clean, simplify=simplify, smooth=smooth)
         verts = mesh["verts_posed"] if space == "posed" else mesh["verts"]
         draw = {a: (True if a in own else mesh[a]) for a in attributes}
+        if "ambient_occlusion" in draw:
+            # the level set's faces are wound with their normals INTO the body ("Normals"): the sky is on the other
+            # side, so the hemispheres are taken about the normals of the reversed faces
+            draw["ambient_occlusion"] = geometry.ambient_occlusion(verts, mesh["faces"].flip(1))[:, None]
         if space == "canonical" and "at" not in camera:
             camera = dict(camera, at=geometry.surface_centroid(verts, mesh["faces"]))
         res = geometry.render_mesh(verts, mesh["faces"], height, width, camera=camera, attributes=draw)
+        res["mesh"] = mesh
+        return res
+
+    def cast_rays(self, inputs, rays=None, n_side=256, clean=None, simplify=None, smooth=None, attributes=()):
+        """What rays see of the posed body of frame `inputs` as an indexed mesh -- the mesh `render_mesh(space="posed")` draws:
+        `canonical_mesh(inputs, n_side, clean=, simplify=, smooth=)` skinned forward ("verts_posed").  rays: (origins, dirs), (R,3)
+        each in world metres, or None for the frame's own rays of batch element 0 (cam_loc and ray_dirs, the masked pixels in eval).
+        attributes: per-vertex names of `canonical_mesh` and "vertex_normal" (the posed mesh's own), interpolated at the hits.
+        -> the dict of geometry.cast_rays (hit, t, face, bary, points, normal and one (R,C) tensor per attribute) plus "mesh",
+        the dict of canonical_mesh.  t is in units of |dirs|: metres along the frame's unit ray_dirs.  Eval only, GPU only; the host
+        synchronisations are canonical_mesh's."""
+        from . import geometry
+        names = ("weights", "verts_posed", "normal", "color", "vertex_normal")
+        attributes = tuple(attributes)
+        bad = set(attributes) - set(names)
+        if bad:
+            raise ValueError("cast_rays: unknown attributes %s (known: %s)" % (sorted(bad), ", ".join(names)))
+        if rays is None:
+            dirs = inputs["ray_dirs"][0].reshape(-1, 3)
+            origins = inputs["cam_loc"][0].reshape(-1, 3).expand(dirs.shape[0], 3)
+        else:
+            if not isinstance(rays, (tuple, list)) or len(rays) != 2:
+                raise ValueError("cast_rays: rays must be (origins, dirs) or None")
+            origins, dirs = rays
+        wanted = {a for a in attributes if a != "vertex_normal"} | {"verts_posed"}
+        mesh = self.canonical_mesh(inputs, n_side=n_side, attributes=tuple(sorted(wanted)), clean=clean, simplify=simplify, smooth=smooth)
+        verts = mesh["verts_posed"]
+        if mesh["faces"].shape[0] < 1:
+            raise ValueError("cast_rays: the level set is empty")
+        for name, x in (("origins", origins), ("dirs", dirs)):
+            if not isinstance(x, torch.Tensor):
+                raise ValueError("cast_rays: %s must be a tensor" % name)
+        take = {a: (True if a == "vertex_normal" else mesh[a]) for a in attributes}
+        res = geometry.cast_rays((verts, mesh["faces"]), origins.to(verts.device), dirs.to(verts.device), attributes=take)
         res["mesh"] = mesh
         return res
 

@@ -614,6 +614,29 @@ int arah_surface_metrics(const float* tris_a, int32_t n_faces_a, const int32_t* 
                          const int32_t* sample_face_b, const double* d2_ba, const int32_t* face_ba, int32_t n_b, double* out,
                          void* scratch, size_t scratch_bytes, void* stream);
 
+/* Rays against the indexed soup (csrc/meshray.hpp; no reference counterpart).  index / tris: as for arah_mesh_closest, the index
+ * is only read.  origins, dirs [R,3] f32 (dirs need not be unit: t is in units of |d|).  The rule per ray and face is Woop, Benthin
+ * and Wald's watertight test in float64 on the float32 inputs, every operation rounded on its own (meshing.mesh_raycast states it
+ * line by line): a hit is accepted when t is finite, t_min <= t <= t_max, and the point bary . corners lies on the ray at t within
+ * 2^-26 of the largest coordinate magnitude of the origin and the face (a ray in a face's plane, whose det is rounding noise, is a
+ * miss); cull 0 none, 1 back (drops det < 0: the ray runs along the face's normal (b-a)x(c-a)), 2 front (drops det > 0).
+ *   mode 0  first hit: t [R] f64, face [R] i32, bary [R,3] f64 = the lexicographic minimum of (t, face) over the accepted faces,
+ *           bit-equal to the brute-force specification whatever the order of the index's references; a miss is t +inf, face -1,
+ *           bary 0.  `hit` is not touched (may be NULL).
+ *   mode 1  any hit: hit [R] u8, 1 when some face is accepted; the walk stops at the first.  t / face / bary are not touched.
+ *   arah_mesh_raycast_debug: the same with the workgroup size given (64, 128 or 256 threads), for measuring it; the results
+ *   do not depend on it.
+ * n_rays <= 2^31 - 1 - 256.
+ * tested [R] i32 or NULL: ray-triangle tests made.  A ray with a zero or non-finite direction or a non-finite origin, and every
+ * ray of an index whose status is 1 (a vertex is not finite), misses.  One thread per ray: the big list, then the cells along
+ * the ray with the distance transform as an empty-space skip.  Nothing is allocated, nothing truncated, no host synchronisation. */
+int arah_mesh_raycast(const void* index, size_t index_bytes, const float* tris, int32_t n_faces, const float* origins,
+                      const float* dirs, int32_t n_rays, double t_min, double t_max, int32_t cull, int32_t mode, double* t,
+                      int32_t* face, double* bary, uint8_t* hit, int32_t* tested, void* stream);
+int arah_mesh_raycast_debug(const void* index, size_t index_bytes, const float* tris, int32_t n_faces, const float* origins,
+                            const float* dirs, int32_t n_rays, double t_min, double t_max, int32_t cull, int32_t mode,
+                            int32_t workgroup, double* t, int32_t* face, double* bary, uint8_t* hit, int32_t* tested, void* stream);
+
 /* Exact nearest point of a large cloud, and the per-side reduction of the geometry scores over meshes and clouds
  * (csrc/pointdist.hpp; no reference counterpart).  points [n,3] f32; a point with a non-finite coordinate is skipped by the
  * build and is never anyone's neighbour.
