@@ -2847,6 +2847,7 @@ __global__ void k_points_cam(FrameDev fr, int n, RaySet rs, const float* dists, 
 }  // namespace
 #include "train.hpp"
 #include "meshquery.hpp"
+#include "meshcontains.hpp"
 #include "metrics.hpp"
 #include "meshdist.hpp"
 #include "meshray.hpp"
@@ -5505,6 +5506,103 @@ int arah_mesh_query(const float* verts, int32_t n_verts, const int32_t* faces, i
     else
         hipLaunchKernelGGL(k_mesh_query<float>, dim3(g), dim3(kMeshThreads), 0, s, verts, faces, n_faces, (const MeshBox*)box,
                            reinterpret_cast<const float*>(pts), n_pts, d2, face, closest, bary, inside);
+    return check_launch();
+}
+
+// ---- containment against large meshes, occupancy grids (meshcontains.hpp) --------------------------------------
+static bool contains_sizes_ok(int32_t n_faces, int32_t resolution) {
+    return n_faces >= 0 && n_faces <= (1 << 28) && resolution >= 2 && resolution <= kCtMaxRes;
+}
+
+size_t arah_contains_index_bytes(int32_t n_faces, int32_t resolution) {
+    if (!contains_sizes_ok(n_faces, resolution)) return 0;
+    return carve_contains(nullptr, n_faces, resolution).bytes;
+}
+
+int arah_contains_index_count(const float* verts, int32_t n_verts, const int32_t* faces, int32_t n_faces, int32_t resolution,
+                              void* index, size_t index_bytes, void* stream) {
+    if (!index || n_verts < 0 || !contains_sizes_ok(n_faces, resolution)) return ARAH_E_BADARG;
+    if (n_faces > 0 && (!verts || !faces || n_verts < 1)) return ARAH_E_BADARG;
+    const CtIndex ix = carve_contains(index, n_faces, resolution);
+    if (index_bytes < ix.bytes) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const long long cells = (long long)resolution * resolution;
+    const int n_blocks = (int)((cells + kCtScanBlock - 1) / kCtScanBlock);
+    if (hipMemsetAsync(ix.cnt, 0, (size_t)cells * sizeof(unsigned), s) != hipSuccess) return ARAH_E_LAUNCH;
+    hipLaunchKernelGGL(k_ct_box, dim3(1), dim3(kCtThreads), 0, s, verts, n_verts, faces, n_faces, resolution, ix.hdr);
+    if (n_faces > 0) {
+        const int g = (n_faces + kCtThreads - 1) / kCtThreads;
+        hipLaunchKernelGGL(k_ct_setup, dim3(g), dim3(kCtThreads), 0, s, verts, faces, n_faces, ix.hdr, ix.rec, ix.rect, ix.med, ix.huge);
+        hipLaunchKernelGGL(k_ct_walk<false>, dim3(mr_grid(n_faces)), dim3(kCtThreads), 0, s, (const int*)ix.rect, n_faces,
+                           resolution, ix.cnt, (int*)nullptr, 0u);
+        hipLaunchKernelGGL(k_ct_walk_lists<false>, dim3(kCtListGrid), dim3(kCtThreads), 0, s, (const CtHeader*)ix.hdr,
+                           (const int*)ix.rect, (const int*)ix.med, (const int*)ix.huge, n_faces, resolution, ix.cnt, (int*)nullptr, 0u);
+    }
+    hipLaunchKernelGGL(k_ct_scan_a, dim3(n_blocks), dim3(kCtThreads), 0, s, (const unsigned*)ix.cnt, cells, ix.sums);
+    hipLaunchKernelGGL(k_ct_scan_b, dim3(1), dim3(kCtThreads), 0, s, ix.sums, n_blocks, ix.hdr);
+    hipLaunchKernelGGL(k_ct_scan_c, dim3(n_blocks), dim3(kCtThreads), 0, s, ix.cnt, cells, (const unsigned long long*)ix.sums, ix.start,
+                       (const CtHeader*)ix.hdr);
+    return check_launch();
+}
+
+int arah_contains_index_fill(void* index, size_t index_bytes, int32_t n_faces, int32_t resolution, int32_t* refs, int64_t n_refs,
+                             void* stream) {
+    if (!index || n_refs < 0 || !contains_sizes_ok(n_faces, resolution)) return ARAH_E_BADARG;
+    if (n_refs > 0x7fffffffll) return ARAH_E_OVERFLOW;
+    const CtIndex ix = carve_contains(index, n_faces, resolution);
+    if (index_bytes < ix.bytes) return ARAH_E_WORKSPACE;
+    if (n_refs == 0 || n_faces == 0) return ARAH_OK;
+    if (!refs) return ARAH_E_BADARG;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const long long cells = (long long)resolution * resolution;
+    const int g = (n_faces + kCtThreads - 1) / kCtThreads;
+    hipLaunchKernelGGL(k_ct_cursor, dim3(mr_grid(cells)),
+                       dim3(kCtThreads), 0, s, (const unsigned*)ix.start, cells, ix.cnt);
+    hipLaunchKernelGGL(k_ct_walk<true>, dim3(mr_grid(n_faces)), dim3(kCtThreads), 0, s, (const int*)ix.rect, n_faces,
+                       resolution, ix.cnt, refs, (unsigned)n_refs);
+    hipLaunchKernelGGL(k_ct_walk_lists<true>, dim3(kCtListGrid), dim3(kCtThreads), 0, s, (const CtHeader*)ix.hdr, (const int*)ix.rect,
+                       (const int*)ix.med, (const int*)ix.huge, n_faces, resolution, ix.cnt, refs, (unsigned)n_refs);
+    return check_launch();
+}
+
+int arah_mesh_contains(const void* index, size_t index_bytes, int32_t n_faces, int32_t resolution, const int32_t* refs, int64_t n_refs,
+                       const void* pts, int32_t pts_are_f64, int32_t n_pts, uint8_t* inside, uint8_t* ambiguous, int32_t* tested,
+                       void* stream) {
+    if (!index || n_pts < 0 || n_refs < 0 || !contains_sizes_ok(n_faces, resolution)) return ARAH_E_BADARG;
+    if (n_refs > 0x7fffffffll) return ARAH_E_OVERFLOW;
+    if (n_refs > 0 && !refs) return ARAH_E_BADARG;
+    const CtIndex ix = carve_contains(const_cast<void*>(index), n_faces, resolution);
+    if (index_bytes < ix.bytes) return ARAH_E_WORKSPACE;
+    if (n_pts == 0) return ARAH_OK;
+    if (!pts || !inside) return ARAH_E_BADARG;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int g = (n_pts + kCtThreads - 1) / kCtThreads;
+    if (pts_are_f64)
+        hipLaunchKernelGGL(k_ct_points<double>, dim3(g), dim3(kCtThreads), 0, s, (const CtHeader*)ix.hdr, (const double*)ix.rec,
+                           (const unsigned*)ix.start, refs, (unsigned)n_refs, n_faces, reinterpret_cast<const double*>(pts), n_pts, inside,
+                           ambiguous, tested);
+    else
+        hipLaunchKernelGGL(k_ct_points<float>, dim3(g), dim3(kCtThreads), 0, s, (const CtHeader*)ix.hdr, (const double*)ix.rec,
+                           (const unsigned*)ix.start, refs, (unsigned)n_refs, n_faces, reinterpret_cast<const float*>(pts), n_pts, inside,
+                           ambiguous, tested);
+    return check_launch();
+}
+
+int arah_mesh_contains_grid(const void* index, size_t index_bytes, int32_t n_faces, int32_t resolution, const int32_t* refs,
+                            int64_t n_refs, const float* xs, int32_t nx, const float* ys, int32_t ny, const float* zs, int32_t nz,
+                            uint8_t* occupancy, uint64_t* ambiguous, void* stream) {
+    if (!index || n_refs < 0 || !contains_sizes_ok(n_faces, resolution)) return ARAH_E_BADARG;
+    if (n_refs > 0x7fffffffll) return ARAH_E_OVERFLOW;
+    if (n_refs > 0 && !refs) return ARAH_E_BADARG;
+    if (!xs || !ys || !zs || !occupancy || nx < 1 || ny < 1 || nz < 1) return ARAH_E_BADARG;
+    if ((long long)nx * ny > 0x7fffffffll || (long long)nx * ny * nz > (1ll << 33)) return ARAH_E_BADARG;
+    const CtIndex ix = carve_contains(const_cast<void*>(index), n_faces, resolution);
+    if (index_bytes < ix.bytes) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (ambiguous && hipMemsetAsync(ambiguous, 0, sizeof(uint64_t), s) != hipSuccess) return ARAH_E_LAUNCH;
+    hipLaunchKernelGGL(k_ct_grid, dim3((unsigned)(nx * ny), (unsigned)((nz + kCtGridZ - 1) / kCtGridZ)), dim3(64), 0, s,
+                       (const CtHeader*)ix.hdr, (const double*)ix.rec, (const unsigned*)ix.start, refs, (unsigned)n_refs, n_faces, xs, ys, ny,
+                       zs, nz, occupancy, reinterpret_cast<unsigned long long*>(ambiguous));
     return check_launch();
 }
 

@@ -13,7 +13,9 @@ Ground truth that is a SCAN -- a point cloud, with or without normals -- is scor
 nearest-point query hip.point_index / hip.point_nearest (DESIGN.md "Scoring against point clouds"): `PointCloud`, `nearest_points`,
 `load_points` / `save_points` / `load_geometry`, and F-scores at distance thresholds (`thresholds=` of `mesh_metrics`).
 Rays against a mesh -- `cast_rays`, `occluded`, `vertex_visibility`, `camera_rays`, `ambient_occlusion` -- go through hip.mesh_raycast
-on the same index (DESIGN.md "Casting rays against meshes on the device")."""
+on the same index (DESIGN.md "Casting rays against meshes on the device").  Whether points lie INSIDE a mesh -- `mesh_contains`,
+`voxelize`, `mesh_iou` -- is the reference's crossing-parity rule over its two-dimensional triangle hash, hip.contains_index /
+hip.mesh_contains / hip.mesh_contains_grid (DESIGN.md "Containment, occupancy grids and IoU on the device")."""
 import collections
 import math
 
@@ -1123,8 +1125,191 @@ def ao_rays(v32, faces, n_rays, seed, eps, adjacency=None):
     return start.reshape(-1, 3), dirs.reshape(-1, 3)
 
 
+# ---- containment, occupancy grids and IoU (DESIGN.md "Containment, occupancy grids and IoU on the device") -----------------
+IOU_KEYS = ("iou", "n_a", "n_b", "n_both", "n_either", "ambiguous_a", "ambiguous_b", "volume_a", "volume_b")
+
+
+def _contains_mesh(mesh, what):
+    """A soup (F,3,3) or a (verts, faces) pair -> (verts (V,3) float32, faces (F,3) int32) on the mesh's device, the soup as three
+    vertices per face.  Face ids are not checked here: a face naming a vertex out of range makes the mesh degenerate for
+    meshing.mesh_contains (every point outside), on the device without a host round trip."""
+    if isinstance(mesh, (tuple, list)):
+        if len(mesh) != 2:
+            raise ValueError("%s: a mesh is an (F, 3, 3) tensor or a (verts, faces) pair" % what)
+        verts, faces = torch.as_tensor(mesh[0]), torch.as_tensor(mesh[1])
+        if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+            raise ValueError("%s: verts must be (V, 3) and faces (F, 3)" % what)
+        if faces.dtype.is_floating_point or faces.dtype == torch.bool:
+            raise ValueError("%s: faces must hold integer vertex indices" % what)
+        V = max(int(verts.shape[0]), 1)
+        faces = faces.to(verts.device).long().clamp(-1, V).to(torch.int32)      # out of range stays out of range in an int32
+        return verts.detach().to(torch.float32).contiguous(), faces.contiguous()
+    tris = torch.as_tensor(mesh)
+    if tris.dim() != 3 or tuple(tris.shape[1:]) != (3, 3):
+        raise ValueError("%s: a mesh is an (F, 3, 3) tensor or a (verts, faces) pair, got shape %s" % (what, tuple(tris.shape)))
+    verts = tris.detach().to(torch.float32).reshape(-1, 3).contiguous()
+    return verts, torch.arange(verts.shape[0], dtype=torch.int32, device=verts.device).reshape(-1, 3)
+
+
+def _contains_index(verts, faces, resolution, index, what):
+    from . import hip
+    if index is None:
+        return hip.contains_index(verts, faces, resolution)
+    if (not isinstance(index, hip.ContainsIndex) or index.n_faces != int(faces.shape[0]) or index.resolution != int(resolution)
+            or index.device != verts.device):
+        raise ValueError("%s: index must be the hip.contains_index of this mesh at this resolution" % what)
+    return index
+
+
+def mesh_contains(mesh, points, resolution=512, index=None, return_ambiguous=False):
+    """(P,) bool: which of the points (P,3) float32 or float64 lie inside the mesh -- an (F,3,3) soup or a (verts, faces) pair as
+    in `mesh_metrics`, on the points' device.  The rule is meshing.mesh_contains, the reference's check_mesh_contains with its
+    triangle hash at `resolution` cells per axis: crossing parities of the z-column through the point, both ways; STRICT -- a
+    column that passes exactly through an edge or a vertex in rescaled coordinates counts no crossing there, and the point may
+    be answered "outside"; return_ambiguous=True -> (inside, ambiguous), ambiguous marking the points whose two parities
+    disagree (the reference prints a warning).  Meant for watertight meshes.  index: the hip.contains_index of the mesh built
+    earlier, or None.  hip.mesh_contains for a mesh on the GPU (one host synchronisation, for the index), the specification for
+    one on the host; equal bit for bit."""
+    from . import meshing
+    verts, faces = _contains_mesh(mesh, "mesh_contains")
+    res = meshing.check_contains_args(verts, faces, points, resolution, "mesh_contains")
+    with torch.no_grad():
+        if verts.is_cuda:
+            from . import hip
+            inside, ambiguous, _ = hip.mesh_contains(_contains_index(verts, faces, res, index, "mesh_contains"), points,
+                                                     want_ambiguous=return_ambiguous)
+        else:
+            if index is not None:
+                raise ValueError("mesh_contains: an index belongs to a mesh on the GPU")
+            inside, ambiguous, _ = meshing.mesh_contains(verts, faces, points, res)
+    return (inside, ambiguous) if return_ambiguous else inside
+
+
+def _used_bounds(verts, faces):
+    """lo, hi (3,) float64 over the vertices some face uses (ids clamped into range), on the device."""
+    used = verts.double()[faces.long().clamp(0, max(int(verts.shape[0]) - 1, 0))].reshape(-1, 3)
+    return used.amin(0), used.amax(0)
+
+
+def _check_bounds(bounds, padding, what):
+    if isinstance(padding, bool) or not isinstance(padding, (int, float, np.integer, np.floating)) or not math.isfinite(float(padding)) \
+            or float(padding) < 0:
+        raise ValueError("%s: padding must be a finite length >= 0, got %r" % (what, padding))
+    if bounds is None:
+        return None
+    lo, hi = (torch.as_tensor(b, dtype=torch.float64).reshape(-1).cpu() for b in bounds)
+    if lo.numel() != 3 or hi.numel() != 3 or not bool(torch.isfinite(lo).all() & torch.isfinite(hi).all() & (hi >= lo).all()):
+        raise ValueError("%s: bounds must be (lo, hi), three finite numbers each with lo <= hi" % what)
+    return lo, hi
+
+
+def voxelize(mesh, dims=None, resolution=None, bounds=None, padding=0.0, hash_resolution=512, index=None):
+    """The mesh (as in `mesh_contains`) on a regular lattice: -> dict with "occupancy" (Nx,Ny,Nz) bool -- whether the CENTRE of the
+    cell lies inside --, "xs", "ys", "zs" the centres' float32 coordinates, "ambiguous" the number of ambiguous centres (0-dim int64
+    tensor) and "bounds" (lo, hi) as tuples of floats.  The lattice spans `bounds` = (lo, hi), default the bounding box of the
+    vertices the faces use (read back: a host synchronisation), widened by the length `padding` on every side; dims = (Nx, Ny, Nz)
+    or one int for all three cuts each axis into that many cells, resolution = N instead makes cubic cells, N along the longest
+    axis and ceil(extent / cell) >= 1 along the others.  Centre i of an axis lies at lo + (i + 0.5) (hi - lo) / N, computed in
+    float64 and rounded to float32.  hip.mesh_contains_grid on the GPU (the 2-D test once per lattice column), the specification
+    on the meshgrid on the host; equal bit for bit."""
+    from . import meshing
+    verts, faces = _contains_mesh(mesh, "voxelize")
+    res = meshing.check_contains_args(verts, faces, None, hash_resolution, "voxelize")
+    given = _check_bounds(bounds, padding, "voxelize")
+    if (dims is None) == (resolution is None):
+        raise ValueError("voxelize: give either dims or resolution")
+    if given is None:
+        if int(faces.shape[0]) < 1 or int(verts.shape[0]) < 1:
+            raise ValueError("voxelize: a mesh without faces has no bounds; give bounds")
+        lo, hi = (b.cpu() for b in _used_bounds(verts, faces))
+        if not bool(torch.isfinite(lo).all() & torch.isfinite(hi).all()):
+            raise ValueError("voxelize: the mesh's bounds are not finite; give bounds")
+    else:
+        lo, hi = given
+    lo, hi = lo - float(padding), hi + float(padding)
+    ext = hi - lo
+    if dims is not None:
+        dims = (dims,) * 3 if isinstance(dims, (int, np.integer)) and not isinstance(dims, bool) else tuple(dims)
+        if len(dims) != 3 or any(isinstance(d, bool) or int(d) != d or int(d) < 1 for d in dims):
+            raise ValueError("voxelize: dims must be one or three positive integers, got %r" % (dims,))
+        dims = tuple(int(d) for d in dims)
+    else:
+        if isinstance(resolution, bool) or int(resolution) != resolution or int(resolution) < 1:
+            raise ValueError("voxelize: resolution must be a positive integer, got %r" % (resolution,))
+        longest = float(ext.max())
+        if not longest > 0:
+            raise ValueError("voxelize: resolution needs bounds with an extent")
+        cell = longest / int(resolution)
+        dims = tuple(max(1, min(int(resolution), int(math.ceil(float(e) / cell - 1e-9)))) for e in ext)
+        hi = lo + torch.tensor(dims, dtype=torch.float64) * cell
+        ext = hi - lo
+    if dims[0] * dims[1] * dims[2] > 2 ** 31 - 1:
+        raise ValueError("voxelize: at most 2^31 - 1 cells")
+    dev = verts.device
+    axes = [(lo[a] + (torch.arange(dims[a], dtype=torch.float64) + 0.5) * (ext[a] / dims[a])).to(torch.float32).to(dev) for a in range(3)]
+    with torch.no_grad():
+        if verts.is_cuda:
+            from . import hip
+            occ, amb = hip.mesh_contains_grid(_contains_index(verts, faces, res, index, "voxelize"), *axes)
+        else:
+            if index is not None:
+                raise ValueError("voxelize: an index belongs to a mesh on the GPU")
+            grid = torch.stack(torch.meshgrid(*axes, indexing="ij"), dim=-1).reshape(-1, 3)
+            inside, ambiguous, _ = meshing.mesh_contains(verts, faces, grid, res)
+            occ, amb = inside.reshape(dims), ambiguous.sum()
+    return {"occupancy": occ, "xs": axes[0], "ys": axes[1], "zs": axes[2], "ambiguous": amb,
+            "bounds": (tuple(lo.tolist()), tuple(hi.tolist()))}
+
+
+def mesh_iou(mesh_a, mesh_b, n_points=100000, seed=0, bounds=None, padding=0.0, resolution=512, return_points=False):
+    """Volumetric intersection over union of two (watertight) meshes, as in `mesh_contains`, on one device -- the third number of
+    the occupancy-network evaluation protocol.  n_points float32 points are drawn uniformly in `bounds` = (lo, hi), default the
+    union of the two meshes' bounding boxes (of the vertices their faces use), widened by the length `padding` on every side,
+    from a torch.Generator on the meshes' device seeded with `seed` (as `mesh_metrics` seeds its samples): lo + u (hi - lo) in
+    float64 with u = rand(n, 3) float64, rounded to float32.  Both meshes answer `mesh_contains` at `resolution` for the same points.
+    -> dict of 0-dim tensors on the device: iou = n_both / n_either in float64 from the integer counts (NaN when n_either = 0),
+    n_a, n_b, n_both, n_either (int64), ambiguous_a, ambiguous_b (int64: points whose parities disagree; they count as outside),
+    volume_a, volume_b (float64: the share of the points inside times the box's volume), plus n_points (Python int).
+    return_points=True adds "points" (n,3) float32, "inside_a", "inside_b" (n,) bool, for tests.  On the GPU the two indices cost one
+    host synchronisation each; nothing else is read back.  The same inputs and seed give the same bits."""
+    from . import meshing
+    if isinstance(n_points, bool) or int(n_points) != n_points or not 1 <= int(n_points) <= 2 ** 31 - 1:
+        raise ValueError("mesh_iou: n_points must be a positive integer, got %r" % (n_points,))
+    n = int(n_points)
+    (va, fa), (vb, fb) = _contains_mesh(mesh_a, "mesh_iou"), _contains_mesh(mesh_b, "mesh_iou")
+    if va.device != vb.device:
+        raise ValueError("mesh_iou: the two meshes must live on one device")
+    res = meshing.check_contains_args(va, fa, None, resolution, "mesh_iou")
+    meshing.check_contains_args(vb, fb, None, resolution, "mesh_iou")
+    given = _check_bounds(bounds, padding, "mesh_iou")
+    dev = va.device
+    with torch.no_grad():
+        if given is None:
+            if min(int(fa.shape[0]), int(fb.shape[0]), int(va.shape[0]), int(vb.shape[0])) < 1:
+                raise ValueError("mesh_iou: a mesh without faces has no bounds; give bounds")
+            (la, ha), (lb, hb) = _used_bounds(va, fa), _used_bounds(vb, fb)
+            lo, hi = torch.minimum(la, lb), torch.maximum(ha, hb)
+        else:
+            lo, hi = given[0].to(dev), given[1].to(dev)
+        lo, hi = lo - float(padding), hi + float(padding)
+        gen = torch.Generator(device=dev).manual_seed(int(seed))
+        u = torch.rand(n, 3, dtype=torch.float64, device=dev, generator=gen)
+        pts = (lo + u * (hi - lo)).to(torch.float32).contiguous()
+        in_a, amb_a = mesh_contains((va, fa), pts, res, return_ambiguous=True)
+        in_b, amb_b = mesh_contains((vb, fb), pts, res, return_ambiguous=True)
+        n_a, n_b = in_a.sum(), in_b.sum()
+        n_both, n_either = (in_a & in_b).sum(), (in_a | in_b).sum()
+        volume = (hi - lo).prod()
+        out = {"iou": n_both.double() / n_either.double(), "n_a": n_a, "n_b": n_b, "n_both": n_both, "n_either": n_either,
+               "ambiguous_a": amb_a.sum(), "ambiguous_b": amb_b.sum(), "volume_a": n_a.double() / n * volume,
+               "volume_b": n_b.double() / n * volume, "n_points": n}
+    if return_points:
+        out.update(points=pts, inside_a=in_a, inside_b=in_b)
+    return out
+
+
 # ---- ground-truth files -------------------------------------------------------------------------------------------------
-_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+_PLY_TYPES ={"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
               "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
               "double": "f8", "float64": "f8"}
 

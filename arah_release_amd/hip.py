@@ -44,7 +44,7 @@ def default_precision():
     raise ValueError("ARAH_PRECISION must be 'split' or 'fp32', got %r" % v)
 
 _ERRORS = {-1: "ARAH_E_BADARG", -2: "ARAH_E_SHAPE", -3: "ARAH_E_WORKSPACE", -4: "ARAH_E_LAUNCH",
-           -5: "ARAH_E_SAMPLING"}
+           -5: "ARAH_E_SAMPLING", -6: "ARAH_E_OVERFLOW"}
 
 _fp = C.c_void_p  # device float*
 
@@ -140,7 +140,9 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_mesh_simplify_scratch_bytes", "arah_mesh_simplify",
            "arah_mesh_adjacency_scratch_bytes", "arah_mesh_adjacency", "arah_mesh_vertex_normals", "arah_mesh_smooth",
            "arah_mesh_rasterize", "arah_mesh_rasterize_debug", "arah_mesh_interpolate", "arah_mesh_raycast", "arah_mesh_raycast_debug",
-           "arah_point_index_bytes", "arah_point_index_build", "arah_point_nearest", "arah_sample_scores_bytes", "arah_sample_scores"]
+           "arah_point_index_bytes", "arah_point_index_build", "arah_point_nearest", "arah_sample_scores_bytes", "arah_sample_scores",
+           "arah_contains_index_bytes", "arah_contains_index_count", "arah_contains_index_fill", "arah_mesh_contains",
+           "arah_mesh_contains_grid"]
 
 _lib = None
 
@@ -190,6 +192,8 @@ def load_library():
         getattr(lib, name).argtypes = [C.c_int64, C.c_int64]
     lib.arah_mesh_simplify_scratch_bytes.restype = C.c_size_t
     lib.arah_mesh_simplify_scratch_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64]
+    lib.arah_contains_index_bytes.restype = C.c_size_t
+    lib.arah_contains_index_bytes.argtypes = [C.c_int32, C.c_int32]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the symbol is missing
     _lib = lib
@@ -1693,6 +1697,109 @@ def mesh_raycast(index, origins, dirs, t_min=0.0, t_max=float("inf"), cull="none
     if first:
         return t, face, bary, tested
     return hit.bool(), tested
+
+
+class ContainsIndex:
+    """The acceleration structure of `contains_index`: libmesh's two-dimensional triangle hash on the device (csrc/meshcontains.hpp).
+    buf holds the bounds, per-triangle records and the cells' starts, refs the triangle ids of every cell."""
+
+    def __init__(self, buf, refs, n_faces, resolution, n_refs, valid):
+        self.buf, self.refs = buf, refs
+        self.n_faces, self.resolution, self.n_refs, self.valid = int(n_faces), int(resolution), int(n_refs), bool(valid)
+
+    @property
+    def device(self):
+        return self.buf.device
+
+    def _head(self):
+        return (_ptr(self.buf), C.c_size_t(self.buf.numel()), C.c_int32(self.n_faces), C.c_int32(self.resolution), _ptr(self.refs),
+                C.c_int64(self.n_refs))
+
+
+def _contains_header(buf):
+    import struct
+    raw = bytes(buf[:88].cpu().numpy())
+    n_refs, = struct.unpack("q", raw[56:64])
+    n_faces, resolution, valid, status = struct.unpack("4i", raw[64:80])
+    return {"scale": struct.unpack("3d", raw[0:24]), "translate": struct.unpack("3d", raw[24:48]), "n_refs": n_refs,
+            "n_faces": n_faces, "resolution": resolution, "valid": valid, "status": status,
+            "n_med": struct.unpack("I", raw[80:84])[0], "n_huge": struct.unpack("I", raw[84:88])[0]}
+
+
+def contains_index(verts, faces, resolution=512):
+    """libmesh's triangle hash of the mesh verts (V,3) float32, faces (F,3) int32 on one GPU, at `resolution` cells per axis of the xy
+    plane (arah_contains_index_count / arah_contains_index_fill) -> ContainsIndex for `mesh_contains` and `mesh_contains_grid`.  The
+    number of references depends on the data: it is read back once, which is the index's one host synchronisation.  F = 0 and the
+    other degenerate meshes of meshing.mesh_contains give an index against which every point is outside."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    res = meshing.check_contains_args(verts, faces, None, resolution, "contains_index")
+    if verts.dtype != torch.float32 or faces.dtype != torch.int32:
+        raise ValueError("contains_index: verts float32 and faces int32 required")
+    dev = _same_device(verts, faces)
+    verts, faces = verts.detach().contiguous(), faces.contiguous()
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    with _on_device(dev):
+        buf = torch.empty(int(lib.arah_contains_index_bytes(F, res)), dtype=torch.uint8, device=dev)
+        _check(lib.arah_contains_index_count(_ptr(verts) if F else None, C.c_int32(V), _ptr(faces) if F else None, C.c_int32(F),
+                                             C.c_int32(res), _ptr(buf), C.c_size_t(buf.numel()), _stream()), "arah_contains_index_count")
+        head = _contains_header(buf)
+        n_refs = int(head["n_refs"])
+        if n_refs > 2 ** 31 - 1 or head["status"] & 1:
+            _check(lib.arah_contains_index_fill(_ptr(buf), C.c_size_t(buf.numel()), C.c_int32(F), C.c_int32(res), None,
+                                                C.c_int64(n_refs), _stream()), "arah_contains_index_fill (%d references)" % n_refs)
+        refs = torch.empty(n_refs, dtype=torch.int32, device=dev) if n_refs else None
+        _check(lib.arah_contains_index_fill(_ptr(buf), C.c_size_t(buf.numel()), C.c_int32(F), C.c_int32(res), _ptr(refs),
+                                            C.c_int64(n_refs), _stream()), "arah_contains_index_fill")
+    return ContainsIndex(buf, refs, F, res, n_refs, head["valid"])
+
+
+def mesh_contains(index, pts, want_ambiguous=False, want_tested=False):
+    """Which points lie inside the indexed mesh (arah_mesh_contains): pts (P,3) float32 or float64 on the index's device -> inside
+    (P,) bool, ambiguous (P,) bool or None, tested (P,) int32 (candidate triangles of the point's cell) or None; equal to
+    meshing.mesh_contains bit for bit.  No host synchronisation."""
+    lib = load_library()
+    if not isinstance(index, ContainsIndex):
+        raise ValueError("index must come from contains_index")
+    if not torch.is_tensor(pts) or pts.dim() != 2 or pts.shape[1] != 3 or pts.dtype not in (torch.float32, torch.float64):
+        raise ValueError("pts must be (P, 3) float32 or float64")
+    dev = _same_device(index.buf, index.refs, pts)
+    pts = pts.detach().contiguous()
+    P = int(pts.shape[0])
+    if P > 2 ** 31 - 1:
+        raise ValueError("at most 2^31 - 1 points")
+    inside = torch.empty(P, dtype=torch.uint8, device=dev)
+    ambiguous = torch.empty(P, dtype=torch.uint8, device=dev) if want_ambiguous else None
+    tested = torch.empty(P, dtype=torch.int32, device=dev) if want_tested else None
+    with _on_device(dev):
+        _check(lib.arah_mesh_contains(*index._head(), _ptr(pts) if P else None, C.c_int32(1 if pts.dtype == torch.float64 else 0),
+                                      C.c_int32(P), _ptr(inside) if P else None, _ptr(ambiguous) if P else None,
+                                      _ptr(tested) if P else None, _stream()), "arah_mesh_contains")
+    return inside.bool(), None if ambiguous is None else ambiguous.bool(), tested
+
+
+def mesh_contains_grid(index, xs, ys, zs):
+    """The lattice xs (Nx,) x ys (Ny,) x zs (Nz,) float32 against the indexed mesh (arah_mesh_contains_grid) -> occupancy (Nx,Ny,Nz)
+    bool, equal to `mesh_contains` on torch.meshgrid(xs, ys, zs, indexing="ij") bit for bit, and the number of ambiguous lattice
+    points, a 0-dim int64 tensor on the device.  The 2-D test runs once per (column, candidate).  No host synchronisation."""
+    lib = load_library()
+    if not isinstance(index, ContainsIndex):
+        raise ValueError("index must come from contains_index")
+    for name, x in (("xs", xs), ("ys", ys), ("zs", zs)):
+        if not torch.is_tensor(x) or x.dim() != 1 or x.dtype != torch.float32 or x.shape[0] < 1:
+            raise ValueError("%s must be a non-empty 1-D float32 tensor" % name)
+    dev = _same_device(index.buf, index.refs, xs, ys, zs)
+    xs, ys, zs = xs.detach().contiguous(), ys.detach().contiguous(), zs.detach().contiguous()
+    nx, ny, nz = int(xs.shape[0]), int(ys.shape[0]), int(zs.shape[0])
+    if nx * ny > 2 ** 31 - 1 or nx * ny * nz > 2 ** 33:
+        raise ValueError("mesh_contains_grid: at most 2^31 - 1 columns and 2^33 lattice points")
+    occ = torch.empty(nx, ny, nz, dtype=torch.uint8, device=dev)
+    amb = torch.empty((), dtype=torch.int64, device=dev)
+    with _on_device(dev):
+        _check(lib.arah_mesh_contains_grid(*index._head(), _ptr(xs), C.c_int32(nx), _ptr(ys), C.c_int32(ny), _ptr(zs), C.c_int32(nz),
+                                           _ptr(occ), _ptr(amb), _stream()), "arah_mesh_contains_grid")
+    return occ.bool(), amb
 
 
 def face_area_cumsum(tris):

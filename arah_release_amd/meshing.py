@@ -878,6 +878,122 @@ def mesh_raycast(tris, origins, dirs, t_min=0.0, t_max=float("inf"), cull="none"
     return t_out, face_out, bary_out
 
 
+CONTAINS_MIN_RESOLUTION, CONTAINS_MAX_RESOLUTION = 2, 4096
+CONTAINS_MAX_FACES = 1 << 28
+
+
+def check_contains_args(verts, faces, points, resolution, what="mesh_contains"):
+    """The arguments of `mesh_contains`, checked (nothing is converted or copied): -> int(resolution).  points may be None."""
+    if isinstance(resolution, bool) or not isinstance(resolution, (int, np.integer)):
+        raise ValueError("%s: resolution must be an integer, got %r" % (what, resolution))
+    if not CONTAINS_MIN_RESOLUTION <= int(resolution) <= CONTAINS_MAX_RESOLUTION:
+        raise ValueError("%s: resolution must lie in [%d, %d], got %d"
+                         % (what, CONTAINS_MIN_RESOLUTION, CONTAINS_MAX_RESOLUTION, int(resolution)))
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or not verts.dtype.is_floating_point:
+        raise ValueError("%s: verts must be a floating-point (V, 3) tensor" % what)
+    if (not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype.is_floating_point
+            or faces.dtype == torch.bool):
+        raise ValueError("%s: faces must be an integer (F, 3) tensor" % what)
+    if int(faces.shape[0]) > CONTAINS_MAX_FACES or int(verts.shape[0]) > 2 ** 31 - 1:
+        raise ValueError("%s: at most 2^28 faces and 2^31 - 1 vertices" % what)
+    if verts.device != faces.device:
+        raise ValueError("%s: verts and faces must live on one device" % what)
+    if points is not None:
+        if (not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3
+                or points.dtype not in (torch.float32, torch.float64)):
+            raise ValueError("%s: points must be (P, 3) float32 or float64" % what)
+        if points.device != verts.device:
+            raise ValueError("%s: points live on %s, the mesh on %s" % (what, points.device, verts.device))
+        if int(points.shape[0]) > 2 ** 31 - 1:
+            raise ValueError("%s: at most 2^31 - 1 points" % what)
+    return int(resolution)
+
+
+def mesh_contains(verts, faces, points, resolution=512, chunk_pairs=1 << 24):
+    """Is a point inside a mesh: verts (V,3) floating point, faces (F,3) integer, points (P,3) float32 or float64 on one device ->
+    inside (P,) bool, ambiguous (P,) bool, tested (P,) int32.  The specification of arah_mesh_contains (csrc/meshcontains.hpp): the
+    reference's `MeshIntersector.query` (im2mesh/utils/libmesh/inside_mesh.py) with its `TriangleHash` (triangle_hash.pyx) restated
+    as a predicate over all (point, triangle) pairs.  float64 throughout, every operation rounded on its own.
+
+    Bounds: lo, hi over the vertices that some face uses; scale = (resolution - 1) / (hi - lo), translate = 0.5 - scale lo, and
+    q = scale x + translate for points and triangle corners alike.  in_box: 0 <= q <= resolution on all three axes (a NaN makes it
+    false).  Candidates: a point reads the one cell ((int)q.x, (int)q.y) of the hash over the xy plane; a cell outside
+    [0, resolution) -- q == resolution, which is in the box -- holds nothing.  Triangle t is a candidate iff the cell lies, on both
+    axes, within [clip((int)min_t), clip((int)max_t)] of its three rescaled corners, clipped to [0, resolution - 1]; `tested`
+    counts the candidates (0 for a point outside the box).  Per candidate, with A = (t1 - t3, t2 - t3) in 2-D, y = q - t3, detA =
+    A00 A11 - A01 A10, s = sign(detA): u = (A11 y0 - A01 y1) s, v = (-A10 y0 + A00 y1) s; the column crosses the triangle when
+    0 < u < |detA|, 0 < v < |detA| and 0 < u + v < |detA|, all STRICT (detA == 0 never passes).  n = (t3 - t1) x (t2 - t1); a
+    vertical triangle (n_z == 0) is skipped; depth = t1_z |n_z| + (n_x (t1_x - q_x) + n_y (t1_y - q_y)) sign(n_z) counts into n0
+    when depth >= q_z |n_z|, else into n1.  inside = in_box & n0 odd & n1 odd; ambiguous = in_box & (n0 odd != n1 odd), for which
+    the reference only prints a warning.
+
+    The rule is the reference's and is deliberately strict: a point whose z-column passes exactly through an edge or a vertex in
+    rescaled coordinates counts no crossing there and may be answered "outside" (or ambiguous) although it lies inside.  The hash
+    is part of the rule: a sliver triangle whose rounded 2-D test passes outside its own bounding box is not a candidate there.
+
+    Degenerate meshes -- no face, a face id outside [0, V), a non-finite vertex that a face uses, an axis with hi == lo (the
+    reference would divide by zero) --: every point is outside, not ambiguous, tested 0.  chunk_pairs bounds the (points x faces)
+    temporaries; the result does not depend on it."""
+    res = check_contains_args(verts, faces, points, resolution)
+    f64, dev = torch.float64, verts.device
+    P, F, V = int(points.shape[0]), int(faces.shape[0]), int(verts.shape[0])
+    n0 = torch.zeros(P, dtype=torch.int64, device=dev)
+    n1 = torch.zeros(P, dtype=torch.int64, device=dev)
+    tested = torch.zeros(P, dtype=torch.int32, device=dev)
+    nothing = torch.zeros(P, dtype=torch.bool, device=dev)
+    if F == 0 or V == 0:
+        return nothing, nothing.clone(), tested
+    fc = faces.detach().long()
+    if not bool(((fc >= 0) & (fc < V)).all()):
+        return nothing, nothing.clone(), tested
+    tri = verts.detach().to(f64)[fc]                                                        # (F,3,3)
+    lo, hi = tri.reshape(-1, 3).amin(0), tri.reshape(-1, 3).amax(0)
+    if not bool(torch.isfinite(tri).all()) or not bool((hi > lo).all()):
+        return nothing, nothing.clone(), tested
+    scale = torch.full_like(lo, float(res - 1)) / (hi - lo)       # a true division (number / tensor would multiply by a reciprocal)
+    translate = 0.5 - scale * lo
+    tri = scale * tri + translate
+    q = scale * points.detach().to(f64) + translate
+    in_box = ((0 <= q) & (q <= res)).all(1)
+    t1, t2, t3 = tri[:, 0], tri[:, 1], tri[:, 2]
+    A00, A01, A10, A11 = t1[:, 0] - t3[:, 0], t2[:, 0] - t3[:, 0], t1[:, 1] - t3[:, 1], t2[:, 1] - t3[:, 1]
+    detA = A00 * A11 - A01 * A10
+    one = torch.ones_like(detA)
+    s_det, a_det = torch.where(detA > 0, one, -one), detA.abs()
+    v1, v2 = t3 - t1, t2 - t1
+    nx = v1[:, 1] * v2[:, 2] - v1[:, 2] * v2[:, 1]
+    ny = v1[:, 2] * v2[:, 0] - v1[:, 0] * v2[:, 2]
+    nz = v1[:, 0] * v2[:, 1] - v1[:, 1] * v2[:, 0]
+    s_n, a_n = torch.where(nz > 0, one, -one), nz.abs()
+    t1z_an = t1[:, 2] * a_n
+    r0 = tri[:, :, :2].amin(1).trunc().long().clamp(0, res - 1)                             # (F,2)
+    r1 = tri[:, :, :2].amax(1).trunc().long().clamp(0, res - 1)
+    cell = torch.nan_to_num(q[:, :2], nan=-1.0).clamp(-1.0, res + 1.0).trunc().long()        # (P,2): (int)q
+    has_cell = ((cell >= 0) & (cell < res)).all(1)
+    per = max(1, int(chunk_pairs) // F)
+    for p0 in range(0, P, per):
+        c = cell[p0:p0 + per]
+        cand = (has_cell[p0:p0 + per, None] & (r0[None, :, 0] <= c[:, None, 0]) & (c[:, None, 0] <= r1[None, :, 0])
+                & (r0[None, :, 1] <= c[:, None, 1]) & (c[:, None, 1] <= r1[None, :, 1]))
+        tested[p0:p0 + per] = cand.sum(1).to(torch.int32)
+        pi, ti = torch.nonzero(cand, as_tuple=True)
+        pi = pi + p0
+        qx, qy, qz = q[pi, 0], q[pi, 1], q[pi, 2]
+        y0, y1 = qx - t3[ti, 0], qy - t3[ti, 1]
+        u = (A11[ti] * y0 - A01[ti] * y1) * s_det[ti]
+        v = (-A10[ti] * y0 + A00[ti] * y1) * s_det[ti]
+        suv = u + v
+        ad, an = a_det[ti], a_n[ti]
+        hit = (ad != 0) & (0 < u) & (u < ad) & (0 < v) & (v < ad) & (0 < suv) & (suv < ad) & (an != 0)
+        alpha = nx[ti] * (t1[ti, 0] - qx) + ny[ti] * (t1[ti, 1] - qy)
+        depth = t1z_an[ti] + alpha * s_n[ti]
+        ge = depth >= qz * an
+        n0.index_add_(0, pi, (hit & ge).long())
+        n1.index_add_(0, pi, (hit & ~ge).long())
+    odd0, odd1 = (n0 & 1).bool(), (n1 & 1).bool()
+    return in_box & odd0 & odd1, in_box & (odd0 != odd1), tested
+
+
 def face_normals(tri):
     """Unit right-hand normals of a triangle soup (F,3,3) (pytorch3d Meshes.faces_normals_packed)."""
     n = torch.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0], dim=1)

@@ -1160,14 +1160,17 @@ class MetaAvatarRender(nn.Module):
         res["mesh"] = mesh
         return res
 
-    def geometry_metrics(self, inputs, gt, n_side=256, method="lattice", n_samples=100000, seed=0, clean=None, thresholds=None):
+    def geometry_metrics(self, inputs, gt, n_side=256, method="lattice", n_samples=100000, seed=0, clean=None, thresholds=None,
+                         iou=None):
         """Geometry scores of the posed body of frame `inputs` against a ground truth `gt` in world metres on the inputs' GPU -- a
         mesh ((F,3,3) triangles or a (verts, faces) pair) or a scan (a geometry.PointCloud or a (P,3) tensor of points):
         `posed_mesh(inputs, n_side, method)` as the prediction, then
         geometry.mesh_metrics -- accuracy is the mean distance of the posed mesh's samples to the ground truth, completeness
         the other way round; thresholds: its F-score distances.  -> its dict of device tensors, plus n_tris of the posed mesh.  clean (None:
         nothing changes): the `clean` of posed_mesh -- the prediction is the indexed posed mesh without its floaters, one of which
-        would otherwise set the Hausdorff distance.  Eval only."""
+        would otherwise set the Hausdorff distance.  iou (None: nothing changes) = N adds the volumetric IoU of the posed mesh and a
+        ground-truth MESH from N uniform points (geometry.mesh_iou with the same seed): "iou" and, under "iou_" + name, its counts
+        n_a (the prediction), n_b, n_both, n_either, ambiguous_a, ambiguous_b, volume_a, volume_b and n_points.  Eval only."""
         from . import geometry
         if self.training:
             raise ValueError("geometry_metrics is eval-only: call model.eval() first")
@@ -1183,6 +1186,12 @@ class MetaAvatarRender(nn.Module):
             raise ValueError("geometry_metrics: the posed level set is empty")
         res = geometry.mesh_metrics(pred, gt, n_samples=n_samples, seed=seed, thresholds=thresholds)
         res["n_tris"] = mesh["n_tris"]
+        if iou is not None:
+            if geometry._is_cloud(gt):
+                raise ValueError("geometry_metrics: iou needs a ground-truth mesh, not a scan")
+            vol = geometry.mesh_iou(pred, gt, n_points=iou, seed=seed)
+            res["iou"] = vol["iou"]
+            res.update(("iou_" + k, vol[k]) for k in geometry.IOU_KEYS[1:] + ("n_points",))
         return res
 
     def _forward(self, inputs, gen_cano_mesh, eval, render_maps):

@@ -23,8 +23,10 @@ against point clouds") -- a directory may mix the two; a frame scored against a 
 null, and the mean of a score runs over the frames that have it (null when none has).  The
 scalars stay on the device until the epoch ends; the JSON line gains their means over the scored frames and ``n_geometry``,
 the number of such frames.  ``--geometry-thresholds 0.005,0.01,0.02`` adds ``precision@T``, ``recall@T`` and ``fscore@T`` for
-every distance T in metres (keys formatted with ``repr(float)``), per frame and as means.  Without the options the output is
-unchanged."""
+every distance T in metres (keys formatted with ``repr(float)``), per frame and as means.  ``--geometry-iou N`` adds ``iou``, the
+volumetric intersection over union of the posed mesh and the ground-truth mesh from N uniform points (geometry.mesh_iou; DESIGN.md
+"Containment, occupancy grids and IoU on the device"), to the frames whose ground truth is a mesh -- a frame scored against a scan
+gets no ``iou`` -- and its mean over those frames to the JSON line.  Without the options the output is unchanged."""
 import argparse
 import importlib
 import json
@@ -57,6 +59,8 @@ def build_parser():
     p.add_argument("--geometry-seed", type=int, default=0, help="Seed of the geometry scores' surface samples.")
     p.add_argument("--geometry-thresholds", type=str, default=None, metavar="T1,T2,...",
                    help="Distances in metres (up to 16): adds precision@T, recall@T and fscore@T to the geometry scores.")
+    p.add_argument("--geometry-iou", type=int, default=None, metavar="N",
+                   help="Uniform points of the volumetric IoU against ground-truth meshes: adds iou to the geometry scores.")
     p.add_argument("--default-config", type=str, default="configs/default.yaml")
     p.add_argument("--body-models", type=str, default="body_models/misc", help="Directory of the SMPL model files.")
     return p
@@ -97,7 +101,7 @@ def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0
     mesh or scan in dir are scored by model.geometry_metrics in the same in-flight step, the scalars are read when the epoch ends
     and the result gains their means, "n_geometry" and the per-frame values; an optional "thresholds" (tuple of distances) adds
     precision@T / recall@T / fscore@T.  normal_consistency of a frame scored against a scan without normals is null; a mean runs over
-    the frames that have the score."""
+    the frames that have the score.  An optional "iou" (a number of points) adds iou for the frames whose ground truth is a mesh."""
     from . import geometry as geo, renderer
     lm = lm.to(device).eval()
     mine = list(range(rank, len(dataset), world))
@@ -105,6 +109,9 @@ def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0
     thresholds = geometry.get("thresholds") if geometry is not None else None
     if thresholds:
         geo_keys = geo_keys + tuple("%s@%r" % (name, t) for name in ("precision", "recall", "fscore") for t in thresholds)
+    n_iou = geometry.get("iou") if geometry is not None else None
+    if n_iou:
+        geo_keys = geo_keys + ("iou",)
 
     def step(item):
         gt = item.get("geometry.gt")
@@ -113,10 +120,15 @@ def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0
         item = {k: v for k, v in item.items() if k != "geometry.gt"}
         out = lm.validation_step(item, lpips_fn=lpips_fn, metrics="device", data_range=data_range)
         scores = lm.model.geometry_metrics(lm.compose_inputs(item, eval=True), gt, n_side=geometry["n_side"],
-                                           n_samples=geometry["n_samples"], seed=geometry["seed"], thresholds=thresholds or None)
+                                           n_samples=geometry["n_samples"], seed=geometry["seed"], thresholds=thresholds or None,
+                                           iou=n_iou if n_iou and not geo._is_cloud(gt) else None)
         out["geometry"] = torch.stack([scores[k] for k in geo.METRIC_KEYS])
         if thresholds:
             out["geometry"] = torch.cat([out["geometry"], scores["precision"], scores["recall"], scores["fscore"]])
+        if n_iou:   # a scan has no volume: its slot stays NaN and the frame gets no iou
+            out["geometry"] = torch.cat([out["geometry"], scores["iou"].reshape(1) if "iou" in scores
+                                         else torch.full((1,), float("nan"), dtype=torch.float64, device=out["geometry"].device)])
+            out["geometry_mesh"] = "iou" in scores
         out["geometry_scan"] = isinstance(gt, geo.PointCloud) and gt.normals is None   # a scan without normals
         return out
 
@@ -131,11 +143,11 @@ def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0
                 if path is not None:
                     item["geometry.gt"] = geo.load_geometry(path, device)
         outs = renderer.map_in_flight(step, items, owner=lm.model)
-        kept += [{k: v for k, v in o.items() if k in ("psnr", "ssim", "lpips", "metrics_status", "geometry", "geometry_scan")}
+        kept += [{k: v for k, v in o.items() if k in ("psnr", "ssim", "lpips", "metrics_status", "geometry", "geometry_scan", "geometry_mesh")}
                  for o in outs]
     torch.cuda.synchronize(device)
     seconds = time.time() - t0
-    res = lm.validation_epoch_end([{k: v for k, v in o.items() if k not in ("geometry", "geometry_scan")} for o in kept], first_index=rank,
+    res = lm.validation_epoch_end([{k: v for k, v in o.items() if k not in ("geometry", "geometry_scan", "geometry_mesh")} for o in kept], first_index=rank,
                                   index_stride=world)
     if geometry is not None:
         nc = geo.METRIC_KEYS.index("normal_consistency")
@@ -144,6 +156,8 @@ def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0
             v = o["geometry"].cpu().tolist()
             if o["geometry_scan"] and v[nc] != v[nc]:
                 v[nc] = None
+            if n_iou and not o["geometry_mesh"]:
+                v[-1] = None
             return v
         rows = [(rank + k * world, values(o)) for k, o in enumerate(kept) if "geometry" in o]
         import torch.distributed as dist
@@ -156,6 +170,8 @@ def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0
             for frame in res["frames"]:
                 if frame["frame"] in scored:
                     frame.update(zip(geo_keys, scored[frame["frame"]]))
+                    if n_iou and frame["iou"] is None:   # scored against a scan
+                        del frame["iou"]
             res["n_geometry"] = len(scored)
             for q, key in enumerate(geo_keys):
                 col = [v[q] for v in scored.values() if v[q] is not None]   # the frames that have the score
@@ -199,8 +215,14 @@ def main(argv=None, body=None, faces=None, log=print):
         if args.geometry_thresholds is not None:
             from . import geometry as geo
             geometry["thresholds"] = geo.check_thresholds([float(t) for t in args.geometry_thresholds.split(",")])
+        if args.geometry_iou is not None:
+            if args.geometry_iou < 1:
+                raise ValueError("--geometry-iou takes a positive number of points")
+            geometry["iou"] = args.geometry_iou
     elif args.geometry_thresholds is not None:
         raise ValueError("--geometry-thresholds needs --geometry DIR")
+    elif args.geometry_iou is not None:
+        raise ValueError("--geometry-iou needs --geometry DIR")
     res, n_mine, seconds = validate(lm, val_dataset, device, rank, world, lpips_fn, args.data_range, geometry)
     if world > 1:
         dist.barrier()

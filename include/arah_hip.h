@@ -80,6 +80,7 @@ extern "C" {
 #define ARAH_E_WORKSPACE (-3)   /* workspace or frame buffer too small */
 #define ARAH_E_LAUNCH (-4)      /* HIP launch error (hipGetLastError) */
 #define ARAH_E_SAMPLING (-5)    /* n_steps < n_near + n_far + 1, or n_steps > ARAH_MAX_STEPS */
+#define ARAH_E_OVERFLOW (-6)    /* a data-dependent count does not fit an int32 */
 
 #define ARAH_MAX_STEPS 128
 #define ARAH_N_JOINTS 24
@@ -836,6 +837,41 @@ int arah_query_posed(const ArahFrame* h_frame, const void* occ_buf, const float*
 size_t arah_sdf_grid_posed_bytes(int32_t n_side);
 int arah_sdf_grid_posed(const ArahFrame* h_frame, const void* occ_buf, const float* box, int32_t n_side, int32_t band, float* sdf,
                         float* box_out, int32_t* counts, void* buf, size_t buf_bytes, void* stream);
+
+/* ---- containment against large meshes, occupancy grids (csrc/meshcontains.hpp) ---------------------------------------------- */
+/* Is a point inside a mesh: libmesh's check_mesh_contains (im2mesh/utils/libmesh/inside_mesh.py) with its TriangleHash restated on
+ * the device; the rule is meshing.mesh_contains and every result equals it bit for bit.  verts [V,3] float, faces [F,3] int32,
+ * 0 <= F <= 2^28, 2 <= resolution <= 4096, otherwise ARAH_E_BADARG without a launch and a size of 0.  A mesh without faces, with
+ * a face id outside [0, V), a non-finite used vertex or no extent on an axis is DEGENERATE: every point is outside.
+ *
+ * The index is built in two calls because its number of references is data-dependent:
+ *   arah_contains_index_count   bounds, per-triangle records and cell rectangles, per-cell counts and their scan into `index`
+ *                               (arah_contains_index_bytes(F, resolution) device bytes, 256-byte aligned).  The first 256 bytes are
+ *                               the header: 7 doubles scale[3], translate[3], resolution | int64 n_refs | int32 n_faces, resolution,
+ *                               valid, status (bit 0: n_refs > INT32_MAX) | uint32 n_med, n_huge.
+ *   the caller reads n_refs from the header (the index's one host synchronisation) and allocates refs [n_refs] int32;
+ *   arah_contains_index_fill    the triangle ids of every cell into refs (cell c: refs[start[c] .. start[c+1])).  ARAH_E_OVERFLOW for
+ *                               n_refs > INT32_MAX; n_refs = 0: nothing to do, refs may be NULL.
+ * The order of the ids inside a cell is unspecified; the answers do not depend on it.
+ *
+ * arah_mesh_contains: pts [P,3] float32 or float64 -> inside [P] u8, ambiguous [P] u8 (or NULL), tested [P] int32 candidates (or
+ * NULL).  One lane per point; rows past P are never written; P = 0 is legal.  An n_refs that is not the header's: every point is
+ * outside.  No host synchronisation.
+ *
+ * arah_mesh_contains_grid: the lattice xs[nx] x ys[ny] x zs[nz] (float32) -> occupancy [nx][ny][nz] u8 in C order, equal to
+ * arah_mesh_contains on the meshgrid(indexing="ij") bit for bit; ambiguous: DEVICE uint64, the number of ambiguous lattice points
+ * (or NULL).  nx, ny, nz >= 1, nx ny <= INT32_MAX, nx ny nz <= 2^33.  No host synchronisation. */
+size_t arah_contains_index_bytes(int32_t n_faces, int32_t resolution);
+int arah_contains_index_count(const float* verts, int32_t n_verts, const int32_t* faces, int32_t n_faces, int32_t resolution,
+                              void* index, size_t index_bytes, void* stream);
+int arah_contains_index_fill(void* index, size_t index_bytes, int32_t n_faces, int32_t resolution, int32_t* refs, int64_t n_refs,
+                             void* stream);
+int arah_mesh_contains(const void* index, size_t index_bytes, int32_t n_faces, int32_t resolution, const int32_t* refs, int64_t n_refs,
+                       const void* pts, int32_t pts_are_f64, int32_t n_pts, uint8_t* inside, uint8_t* ambiguous, int32_t* tested,
+                       void* stream);
+int arah_mesh_contains_grid(const void* index, size_t index_bytes, int32_t n_faces, int32_t resolution, const int32_t* refs,
+                            int64_t n_refs, const float* xs, int32_t nx, const float* ys, int32_t ny, const float* zs, int32_t nz,
+                            uint8_t* occupancy, uint64_t* ambiguous, void* stream);
 
 /* name of the dominant kernel, for profilers */
 const char* arah_dominant_kernel(void);
