@@ -2850,6 +2850,7 @@ __global__ void k_points_cam(FrameDev fr, int n, RaySet rs, const float* dists, 
 #include "meshcontains.hpp"
 #include "metrics.hpp"
 #include "meshdist.hpp"
+#include "meshsdf.hpp"
 #include "meshray.hpp"
 #include "pointdist.hpp"
 namespace {
@@ -5671,6 +5672,55 @@ int arah_mesh_closest(const void* index, size_t index_bytes, const float* tris, 
     hipLaunchKernelGGL(k_md_closest, dim3(g), dim3(kMdQueryThreads), 0, reinterpret_cast<hipStream_t>(stream), tris,
                        (const MdHeader*)m.hdr, (const int*)m.cell_base, (const uint8_t*)m.dt[0], (const int*)m.refs,
                        (const int*)m.big, pts, (int)n_pts, d2, (int*)face, closest, (int*)tested);
+    return check_launch();
+}
+
+// ---- the truncated signed distance field of a soup on a lattice (meshsdf.hpp) -----------------------------------
+static bool sdf_grid_sizes_ok(int64_t n_faces, int64_t nx, int64_t ny, int64_t nz) {
+    return n_faces >= 0 && n_faces <= (1 << 26) && nx >= 1 && ny >= 1 && nz >= 1 && nx <= INT32_MAX && ny <= INT32_MAX && nz <= INT32_MAX;
+}
+
+size_t arah_mesh_sdf_grid_bytes(int64_t n_faces, int64_t nx, int64_t ny, int64_t nz) {
+    if (!sdf_grid_sizes_ok(n_faces, nx, ny, nz) || nx * ny > (int64_t)INT32_MAX || nx * ny * nz > (int64_t)INT32_MAX) return 0;
+    return carve_sdf_grid(nullptr, n_faces).bytes;
+}
+
+int arah_mesh_sdf_grid(const float* tris, int32_t n_faces, const float* xs, int32_t nx, const float* ys, int32_t ny, const float* zs,
+                       int32_t nz, float trunc, const uint8_t* occupancy, double* d2, int32_t* face, float* sdf, int32_t* info,
+                       void* scratch, size_t scratch_bytes, void* stream) {
+    if (!sdf_grid_sizes_ok(n_faces, nx, ny, nz) || !(trunc >= 0.0f)) return ARAH_E_BADARG;   // a NaN trunc fails the comparison
+    if ((int64_t)nx * ny > (int64_t)INT32_MAX || (int64_t)nx * ny * nz > (int64_t)INT32_MAX) return ARAH_E_OVERFLOW;
+    if (!xs || !ys || !zs || !d2 || !info || !scratch || (n_faces > 0 && !tris)) return ARAH_E_BADARG;
+    if ((reinterpret_cast<uintptr_t>(info) & 7) != 0 || (reinterpret_cast<uintptr_t>(d2) & 7) != 0) return ARAH_E_BADARG;   // 64-bit atomics
+    const SgScratch w = carve_sdf_grid(scratch, n_faces);
+    if (scratch_bytes < w.bytes) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const long long n = (long long)nx * ny * nz;
+    const double t = (double)trunc, t2 = t * t;
+    const SgLattice L = {xs, ys, zs, (int)ny, (int)nz};
+    unsigned long long* bits = reinterpret_cast<unsigned long long*>(d2);
+    const int node_grid = (int)min((long long)kSgMaxGrid, (n + kSgThreads - 1) / kSgThreads);
+    if (hipMemsetAsync(info, 0, kSgInfo * sizeof(int32_t), s) != hipSuccess) return ARAH_E_LAUNCH;
+    hipLaunchKernelGGL(k_sg_init, dim3(node_grid), dim3(kSgThreads), 0, s, bits, (int*)face, n);
+    if (n_faces > 0) {
+        const int fg = (n_faces + kSgThreads - 1) / kSgThreads;
+        // k_sg_walk: kSgWaveFaces faces a wave, kSgThreads / 64 waves a workgroup
+        const long long walk_waves = ((long long)n_faces + kSgWaveFaces - 1) / kSgWaveFaces;
+        const int wg = (int)min((long long)kSgMaxGrid, (walk_waves + kSgThreads / 64 - 1) / (kSgThreads / 64));
+        hipLaunchKernelGGL(k_sg_setup, dim3(fg), dim3(kSgThreads), 0, s, tris, (int)n_faces, xs, (int)nx, ys, (int)ny, zs, (int)nz, t,
+                           w.rect, w.med, w.huge, (int*)info);
+        hipLaunchKernelGGL(k_sg_walk<0>, dim3(wg), dim3(kSgThreads), 0, s, tris, (const int*)w.rect, (int)n_faces, L, t2, bits,
+                           (int*)face, (int*)info);
+        hipLaunchKernelGGL(k_sg_walk_lists<0>, dim3(kSgListGrid), dim3(kSgThreads), 0, s, tris, (const int*)w.rect, (const int*)w.med,
+                           (const int*)w.huge, (int)n_faces, L, t2, bits, (int*)face, (int*)info);
+        if (face) {
+            hipLaunchKernelGGL(k_sg_walk<1>, dim3(wg), dim3(kSgThreads), 0, s, tris, (const int*)w.rect, (int)n_faces, L, t2, bits,
+                               (int*)face, (int*)info);
+            hipLaunchKernelGGL(k_sg_walk_lists<1>, dim3(kSgListGrid), dim3(kSgThreads), 0, s, tris, (const int*)w.rect,
+                               (const int*)w.med, (const int*)w.huge, (int)n_faces, L, t2, bits, (int*)face, (int*)info);
+        }
+    }
+    hipLaunchKernelGGL(k_sg_finish, dim3(node_grid), dim3(kSgThreads), 0, s, L, n, t, t2, occupancy, d2, (int*)face, sdf, (int*)info);
     return check_launch();
 }
 

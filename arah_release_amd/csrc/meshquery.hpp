@@ -59,10 +59,16 @@ struct D3 {
     double x, y, z;
 };
 __device__ __forceinline__ D3 dsub(D3 a, D3 b) { return D3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ double ddot(D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+// one rounding per operation, also when inlined into a kernel: a pragma in the caller does not reach into a callee
+__device__ __forceinline__ double ddot(D3 a, D3 b) {
+#pragma clang fp contract(off)
+    return a.x * b.x + a.y * b.y + a.z * b.z;
+}
 
-// closest point of triangle (a, b, c) to p, as barycentric weights (Ericson 5.1.5)
+// closest point of triangle (a, b, c) to p, as barycentric weights (Ericson 5.1.5); one rounding per operation (the rule is
+// meshing.closest_on_triangles)
 __device__ __forceinline__ void closest_on_triangle(D3 p, D3 a, D3 b, D3 c, double& wa, double& wb, double& wc) {
+#pragma clang fp contract(off)
     const D3 ab = dsub(b, a), ac = dsub(c, a), ap = dsub(p, a);
     const double d1 = ddot(ab, ap), d2 = ddot(ac, ap);
     if (d1 <= 0.0 && d2 <= 0.0) { wa = 1.0; wb = 0.0; wc = 0.0; return; }

@@ -1203,6 +1203,54 @@ def _check_bounds(bounds, padding, what):
     return lo, hi
 
 
+def _mesh_bounds(verts, faces, bounds, what):
+    """(lo, hi) float64 (3,) on the host: `bounds` as given and checked, else the bounding box of the vertices the faces use (read
+    back: a host synchronisation)."""
+    given = _check_bounds(bounds, 0.0, what)
+    if given is not None:
+        return given
+    if int(faces.shape[0]) < 1 or int(verts.shape[0]) < 1:
+        raise ValueError("%s: a mesh without faces has no bounds; give bounds" % what)
+    lo, hi = (b.cpu() for b in _used_bounds(verts, faces))
+    if not bool(torch.isfinite(lo).all() & torch.isfinite(hi).all()):
+        raise ValueError("%s: the mesh's bounds are not finite; give bounds" % what)
+    return lo, hi
+
+
+def _lattice_cells(verts, faces, dims, resolution, bounds, padding, what):
+    """The lattice arguments of `voxelize`, shared with `mesh_sdf_grid`: -> lo, hi, ext (3,) float64 on the host and dims, three ints.
+    bounds (default the mesh's), widened by padding; dims cells per axis, or resolution = N cubic cells along the longest axis."""
+    _check_bounds(bounds, padding, what)
+    if (dims is None) == (resolution is None):
+        raise ValueError("%s: give either dims or resolution" % what)
+    lo, hi = _mesh_bounds(verts, faces, bounds, what)
+    lo, hi = lo - float(padding), hi + float(padding)
+    ext = hi - lo
+    if dims is not None:
+        dims = (dims,) * 3 if isinstance(dims, (int, np.integer)) and not isinstance(dims, bool) else tuple(dims)
+        if len(dims) != 3 or any(isinstance(d, bool) or int(d) != d or int(d) < 1 for d in dims):
+            raise ValueError("%s: dims must be one or three positive integers, got %r" % (what, dims))
+        dims = tuple(int(d) for d in dims)
+    else:
+        if isinstance(resolution, bool) or int(resolution) != resolution or int(resolution) < 1:
+            raise ValueError("%s: resolution must be a positive integer, got %r" % (what, resolution))
+        longest = float(ext.max())
+        if not longest > 0:
+            raise ValueError("%s: resolution needs bounds with an extent" % what)
+        cell = longest / int(resolution)
+        dims = tuple(max(1, min(int(resolution), int(math.ceil(float(e) / cell - 1e-9)))) for e in ext)
+        hi = lo + torch.tensor(dims, dtype=torch.float64) * cell
+        ext = hi - lo
+    if dims[0] * dims[1] * dims[2] > 2 ** 31 - 1:
+        raise ValueError("%s: at most 2^31 - 1 cells" % what)
+    return lo, hi, ext, dims
+
+
+def _cell_centres(lo, ext, dims, dev):
+    """Centre i of an axis lies at lo + (i + 0.5) (hi - lo) / N, computed in float64 and rounded to float32."""
+    return [(lo[a] + (torch.arange(dims[a], dtype=torch.float64) + 0.5) * (ext[a] / dims[a])).to(torch.float32).to(dev) for a in range(3)]
+
+
 def voxelize(mesh, dims=None, resolution=None, bounds=None, padding=0.0, hash_resolution=512, index=None):
     """The mesh (as in `mesh_contains`) on a regular lattice: -> dict with "occupancy" (Nx,Ny,Nz) bool -- whether the CENTRE of the
     cell lies inside --, "xs", "ys", "zs" the centres' float32 coordinates, "ambiguous" the number of ambiguous centres (0-dim int64
@@ -1215,38 +1263,9 @@ def voxelize(mesh, dims=None, resolution=None, bounds=None, padding=0.0, hash_re
     from . import meshing
     verts, faces = _contains_mesh(mesh, "voxelize")
     res = meshing.check_contains_args(verts, faces, None, hash_resolution, "voxelize")
-    given = _check_bounds(bounds, padding, "voxelize")
-    if (dims is None) == (resolution is None):
-        raise ValueError("voxelize: give either dims or resolution")
-    if given is None:
-        if int(faces.shape[0]) < 1 or int(verts.shape[0]) < 1:
-            raise ValueError("voxelize: a mesh without faces has no bounds; give bounds")
-        lo, hi = (b.cpu() for b in _used_bounds(verts, faces))
-        if not bool(torch.isfinite(lo).all() & torch.isfinite(hi).all()):
-            raise ValueError("voxelize: the mesh's bounds are not finite; give bounds")
-    else:
-        lo, hi = given
-    lo, hi = lo - float(padding), hi + float(padding)
-    ext = hi - lo
-    if dims is not None:
-        dims = (dims,) * 3 if isinstance(dims, (int, np.integer)) and not isinstance(dims, bool) else tuple(dims)
-        if len(dims) != 3 or any(isinstance(d, bool) or int(d) != d or int(d) < 1 for d in dims):
-            raise ValueError("voxelize: dims must be one or three positive integers, got %r" % (dims,))
-        dims = tuple(int(d) for d in dims)
-    else:
-        if isinstance(resolution, bool) or int(resolution) != resolution or int(resolution) < 1:
-            raise ValueError("voxelize: resolution must be a positive integer, got %r" % (resolution,))
-        longest = float(ext.max())
-        if not longest > 0:
-            raise ValueError("voxelize: resolution needs bounds with an extent")
-        cell = longest / int(resolution)
-        dims = tuple(max(1, min(int(resolution), int(math.ceil(float(e) / cell - 1e-9)))) for e in ext)
-        hi = lo + torch.tensor(dims, dtype=torch.float64) * cell
-        ext = hi - lo
-    if dims[0] * dims[1] * dims[2] > 2 ** 31 - 1:
-        raise ValueError("voxelize: at most 2^31 - 1 cells")
+    lo, hi, ext, dims = _lattice_cells(verts, faces, dims, resolution, bounds, padding, "voxelize")
     dev = verts.device
-    axes = [(lo[a] + (torch.arange(dims[a], dtype=torch.float64) + 0.5) * (ext[a] / dims[a])).to(torch.float32).to(dev) for a in range(3)]
+    axes = _cell_centres(lo, ext, dims, dev)
     with torch.no_grad():
         if verts.is_cuda:
             from . import hip
@@ -1306,6 +1325,180 @@ def mesh_iou(mesh_a, mesh_b, n_points=100000, seed=0, bounds=None, padding=0.0, 
     if return_points:
         out.update(points=pts, inside_a=in_a, inside_b=in_b)
     return out
+
+
+# ---- signed distance to a mesh, remeshing (DESIGN.md "Signed distance to a mesh on the device") ----------------------------
+SDF_KEYS = ("sdf", "d2", "face", "closest", "inside", "ambiguous", "gradient")
+
+
+def _sdf_mesh(mesh, what):
+    """`_contains_mesh`, float32 vertices, and every face id checked (a host synchronisation): a distance needs real triangles.
+    -> verts, faces, tris (F,3,3) float32."""
+    verts, faces = _contains_mesh(mesh, what)
+    V = int(verts.shape[0])
+    if faces.numel() and not bool(((faces >= 0) & (faces < V)).all()):
+        raise ValueError("%s: a face names a vertex outside [0, %d)" % (what, V))
+    tris = verts[faces.long()].contiguous() if faces.numel() else verts.new_zeros((0, 3, 3))
+    return verts, faces, tris
+
+
+def mesh_sdf(mesh, points, trunc=float("inf"), resolution=512, index=None, contains_index=None):
+    """The signed distance of points (P,3) float32 to a mesh -- an (F,3,3) soup or a (verts, faces) pair as in `mesh_contains`, on the
+    points' device -> dict: "sdf" (P,) float32 = meshing.signed_distance(d2, inside, trunc), negative inside; "d2" (P,) float64, "face"
+    (P,) int32 and "closest" (P,3) float64 of the closest triangle (+inf, -1, NaN for a point farther than `trunc`, outside the band);
+    "inside", "ambiguous" (P,) bool, `mesh_contains` at `resolution`, for every point; "gradient" (P,3) float64, the unit vector
+    sign (p - closest) / |p - closest|, NaN where d2 == 0 and outside the band.  The rule is meshing.mesh_sdf.  On the GPU it is
+    hip.mesh_closest plus hip.mesh_contains (index: the hip.mesh_index of the mesh's soup, contains_index: its hip.contains_index,
+    built earlier, or None), on the host the specification.  The sign is the parity rule's: meant for watertight meshes."""
+    from . import meshing
+    t = meshing.check_trunc(trunc, "mesh_sdf")
+    verts, faces, tris = _sdf_mesh(mesh, "mesh_sdf")
+    res = meshing.check_contains_args(verts, faces, points, resolution, "mesh_sdf")
+    if points.dtype != torch.float32:
+        raise ValueError("mesh_sdf: points must be (P, 3) float32")
+    with torch.no_grad():
+        if verts.is_cuda:
+            from . import hip
+            pts = points.detach().contiguous()
+            if int(tris.shape[0]) < 1:
+                d2, face, closest = meshing.soup_closest(tris, pts, t)
+            else:
+                d2, face, closest, _ = hip.mesh_closest(_ray_index(tris, index, "mesh_sdf"), pts)
+                inf = torch.full_like(d2, float("inf"))
+                out = (d2 > t * t) | ((face < 0) & ~torch.isnan(d2))        # beyond the band; or no triangle gave a number
+                d2, face = torch.where(out, inf, d2), torch.where(out, torch.full_like(face, -1), face)
+                closest = torch.where(out[:, None], torch.full_like(closest, float("nan")), closest)
+            inside, ambiguous, _ = hip.mesh_contains(_contains_index(verts, faces, res, contains_index, "mesh_sdf"), pts,
+                                                     want_ambiguous=True)
+        else:
+            if index is not None or contains_index is not None:
+                raise ValueError("mesh_sdf: an index belongs to a mesh on the GPU")
+            d2, face, closest, inside, ambiguous = meshing.mesh_sdf(verts, faces, points, t, res)
+        dv = points.detach().double() - closest
+        norm = torch.sqrt((dv[:, 0] * dv[:, 0] + dv[:, 1] * dv[:, 1]) + dv[:, 2] * dv[:, 2])
+        gradient = torch.where(inside[:, None], -dv, dv) / norm[:, None]        # 0 / 0 on the surface, NaN outside the band
+    return {"sdf": meshing.signed_distance(d2, inside, t), "d2": d2, "face": face, "closest": closest, "inside": inside,
+            "ambiguous": ambiguous, "gradient": gradient}
+
+
+def mesh_sdf_grid(mesh, dims=None, resolution=None, n_side=None, bounds=None, padding=0.0, trunc=None, nodes="centres",
+                  hash_resolution=512, index=None, want_face=False):
+    """The truncated signed distance field of a mesh (as in `mesh_sdf`) on a regular lattice -> dict: "sdf" (Nx,Ny,Nz) float32,
+    meshing.signed_distance; "d2" (Nx,Ny,Nz) float64, +inf outside the band; "face" (Nx,Ny,Nz) int32 with want_face=True, else None;
+    "inside" (Nx,Ny,Nz) bool and "ambiguous" (0-dim int64), `voxelize`'s; "xs", "ys", "zs" the nodes' float32 coordinates; "bounds"
+    (lo, hi); "band", the number of nodes within trunc (0-dim int64 on the device); "trunc" and "step" (floats); "box" and "info".
+    nodes="centres": dims / resolution / bounds / padding mean exactly what they mean in `voxelize`, whose lattice this is.
+    nodes="corners" with n_side=N: the cube lattice of hip.lattice_box(lo, hi, padding) with N nodes per axis, node i at origin +
+    i side / (N - 1) in float64 rounded to float32 -- the lattice hip.marching_cubes_indexed and hip.lattice_to_world assume; "box" is
+    its (origin xyz, side), else None.  trunc: the width of the band, default three lattice steps (the largest of the three).  On the
+    GPU hip.mesh_contains_grid and hip.mesh_sdf_grid (csrc/meshsdf.hpp: the cost follows the band, "info" are its counters), on the
+    host the specification on the meshgrid; d2, face and inside are equal bit for bit."""
+    from . import meshing
+    what = "mesh_sdf_grid"
+    verts, faces, tris = _sdf_mesh(mesh, what)
+    res = meshing.check_contains_args(verts, faces, None, hash_resolution, what)
+    dev = verts.device
+    if nodes not in ("centres", "corners"):
+        raise ValueError("%s: nodes must be 'centres' or 'corners', got %r" % (what, nodes))
+    box = None
+    if nodes == "corners":
+        if dims is not None or resolution is not None or n_side is None:
+            raise ValueError("%s: nodes='corners' takes n_side, the cube lattice's nodes per axis" % what)
+        if isinstance(n_side, bool) or int(n_side) != n_side or not 2 <= int(n_side) <= 1290:
+            raise ValueError("%s: n_side must be an integer in [2, 1290], got %r" % (what, n_side))
+        _check_bounds(None, padding, what)
+        n = int(n_side)
+        lo, hi = _mesh_bounds(verts, faces, bounds, what)
+        lo, hi = lo - float(padding), hi + float(padding)
+        side = float((hi - lo).max())
+        if not side > 0:
+            raise ValueError("%s: the cube lattice needs bounds with an extent" % what)
+        origin = 0.5 * (lo + hi) - 0.5 * side
+        lo, hi = origin, origin + side
+        step = side / (n - 1)
+        axes = [(origin[a] + torch.arange(n, dtype=torch.float64) * step).to(torch.float32).to(dev) for a in range(3)]
+        box = torch.cat([origin, torch.tensor([side], dtype=torch.float64)]).to(torch.float32).to(dev)
+        dims = (n, n, n)
+    else:
+        if n_side is not None:
+            raise ValueError("%s: n_side belongs to nodes='corners'; give dims or resolution" % what)
+        lo, hi, ext, dims = _lattice_cells(verts, faces, dims, resolution, bounds, padding, what)
+        axes = _cell_centres(lo, ext, dims, dev)
+        step = float((ext / torch.tensor(dims, dtype=torch.float64)).max())
+    t = meshing.check_trunc(3.0 * step if trunc is None else trunc, what)
+    meshing.check_lattice_axes(*axes, what=what)     # a lattice finer than float32 resolves is refused here
+    info = None
+    with torch.no_grad():
+        if verts.is_cuda:
+            from . import hip
+            occ, amb = hip.mesh_contains_grid(_contains_index(verts, faces, res, index, what), *axes)
+            d2, face, sdf, info = hip.mesh_sdf_grid(tris, *axes, t, occupancy=occ, want_face=want_face, want_info=True)
+            band = info[0].long()
+        else:
+            if index is not None:
+                raise ValueError("%s: an index belongs to a mesh on the GPU" % what)
+            grid = torch.stack(torch.meshgrid(*axes, indexing="ij"), dim=-1).reshape(-1, 3)
+            inside, ambiguous, _ = meshing.mesh_contains(verts, faces, grid, res)
+            occ, amb = inside.reshape(dims), ambiguous.sum()
+            d2, face = meshing.mesh_sdf_grid(tris, *axes, t)
+            sdf = meshing.signed_distance(d2, occ, t)
+            band = ((d2 <= t * t) & (d2 < float("inf"))).sum()
+            face = face if want_face else None
+    return {"sdf": sdf, "d2": d2, "face": face, "inside": occ, "xs": axes[0], "ys": axes[1], "zs": axes[2], "ambiguous": amb,
+            "bounds": (tuple(lo.tolist()), tuple(hi.tolist())), "band": band, "trunc": t, "step": step, "box": box, "info": info}
+
+
+def remesh(mesh, n_side=256, offset=0.0, trunc=None, padding=None, clean=None, smooth=None):
+    """A watertight, uniform remesh of a (watertight) mesh, or an offset surface of it: the level `offset` (metres; positive grows
+    the body) of its signed distance field on the cube lattice of `mesh_sdf_grid(nodes="corners", n_side=n_side)`, by
+    hip.marching_cubes_indexed and hip.lattice_to_world -> (verts (V,3) float32 in the mesh's own coordinates, faces (F,3) int32).
+    trunc defaults to |offset| plus three lattice steps; |offset| must stay below trunc by at least one step, so that both ends of
+    every edge that crosses the level hold true distances.  padding defaults to max(offset, 0) plus two steps (the step then
+    follows from extent + 2 padding = (n_side - 1) step).  clean / smooth: the policies of geometry.clean_mesh / smooth_mesh
+    (check_keep, check_smooth), applied in that order.  The two capacities are read back once.  GPU only."""
+    from . import meshing
+    what = "remesh"
+    if isinstance(offset, bool) or not isinstance(offset, (int, float, np.integer, np.floating)) or not math.isfinite(float(offset)):
+        raise ValueError("remesh: offset must be a finite length, got %r" % (offset,))
+    offset = float(offset)
+    if isinstance(n_side, bool) or int(n_side) != n_side or not 8 <= int(n_side) <= 894:
+        raise ValueError("remesh: n_side must be an integer in [8, 894], got %r" % (n_side,))
+    n = int(n_side)
+    if clean is not None:
+        check_keep(clean)
+    if smooth is not None:
+        smooth = check_smooth(smooth)
+    verts, faces, _ = _sdf_mesh(mesh, what)
+    lo, hi = _mesh_bounds(verts, faces, None, what)
+    extent = float((hi - lo).max())
+    if padding is None:
+        step = (extent + 2.0 * max(offset, 0.0)) / (n - 5)      # extent + 2 (max(offset, 0) + 2 step) = (n - 1) step
+        padding = max(offset, 0.0) + 2.0 * step
+    else:
+        _check_bounds(None, padding, what)
+        step = (extent + 2.0 * float(padding)) / (n - 1)
+    if not step > 0:
+        raise ValueError("remesh: the mesh has no extent")
+    t = meshing.check_trunc(abs(offset) + 3.0 * step if trunc is None else trunc, what)
+    if not abs(offset) <= t - step:
+        raise ValueError("remesh: |offset| = %g must stay below trunc = %g by at least one lattice step (%g)" % (abs(offset), t, step))
+    if not verts.is_cuda:
+        raise ValueError("remesh runs on the HIP kernels: the mesh must live on the GPU")
+    from . import hip
+    with torch.no_grad():
+        field = mesh_sdf_grid((verts, faces), n_side=n, padding=padding, trunc=t, nodes="corners")
+        vert_cap, face_cap = meshing.MC_DEFAULT_VERT_CAP, meshing.MC_DEFAULT_CAP
+        out_v, out_f, size = hip.marching_cubes_indexed(field["sdf"], offset, vert_cap, face_cap)
+        V, F = size.tolist()
+        if V > vert_cap or F > face_cap:   # too small for this level set: the exact sizes, once more
+            out_v, out_f, size = hip.marching_cubes_indexed(field["sdf"], offset, max(V, 1), max(F, 1))
+        out_v, out_f = hip.lattice_to_world(out_v[:V], field["box"]), out_f[:F]
+        if clean is not None:
+            kept = clean_mesh(out_v, out_f, keep=clean)
+            out_v, out_f = kept["verts"], kept["faces"]
+        if smooth is not None:
+            out_v = smooth_mesh(out_v, out_f, **smooth)
+    return out_v, out_f
 
 
 # ---- ground-truth files -------------------------------------------------------------------------------------------------

@@ -142,7 +142,7 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_mesh_rasterize", "arah_mesh_rasterize_debug", "arah_mesh_interpolate", "arah_mesh_raycast", "arah_mesh_raycast_debug",
            "arah_point_index_bytes", "arah_point_index_build", "arah_point_nearest", "arah_sample_scores_bytes", "arah_sample_scores",
            "arah_contains_index_bytes", "arah_contains_index_count", "arah_contains_index_fill", "arah_mesh_contains",
-           "arah_mesh_contains_grid"]
+           "arah_mesh_contains_grid", "arah_mesh_sdf_grid_bytes", "arah_mesh_sdf_grid"]
 
 _lib = None
 
@@ -194,6 +194,8 @@ def load_library():
     lib.arah_mesh_simplify_scratch_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64]
     lib.arah_contains_index_bytes.restype = C.c_size_t
     lib.arah_contains_index_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.arah_mesh_sdf_grid_bytes.restype = C.c_size_t
+    lib.arah_mesh_sdf_grid_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the symbol is missing
     _lib = lib
@@ -1800,6 +1802,60 @@ def mesh_contains_grid(index, xs, ys, zs):
         _check(lib.arah_mesh_contains_grid(*index._head(), _ptr(xs), C.c_int32(nx), _ptr(ys), C.c_int32(ny), _ptr(zs), C.c_int32(nz),
                                            _ptr(occ), _ptr(amb), _stream()), "arah_mesh_contains_grid")
     return occ.bool(), amb
+
+
+SDF_GRID_INFO = ("band", "status", "tests", "lane", "wave", "group", "huge")
+
+
+def read_sdf_grid_info(info):
+    """Host copy of arah_mesh_sdf_grid's counters (a synchronisation): nodes in the band, status, point-triangle tests made and the
+    triangles of the four size classes."""
+    v = [int(x) for x in info.cpu().tolist()]
+    tests = (v[2] & 0xffffffff) | ((v[3] & 0xffffffff) << 32)
+    return dict(zip(SDF_GRID_INFO, (v[0], v[1], tests, v[4], v[5], v[6], v[7])))
+
+
+def mesh_sdf_grid(tris, xs, ys, zs, trunc, occupancy=None, want_face=False, want_info=False):
+    """The truncated distance field of the soup tris (F,3,3) float32 (F may be 0) on the lattice xs (Nx,) x ys (Ny,) x zs (Nz,)
+    float32, each strictly ascending (arah_mesh_sdf_grid, csrc/meshsdf.hpp) -> d2 (Nx,Ny,Nz) float64 (+inf outside the band of width
+    trunc), face (Nx,Ny,Nz) int32 or None, sdf (Nx,Ny,Nz) float32 by meshing.signed_distance from `occupancy` (bool or uint8, as
+    `mesh_contains_grid` returns it; None: every node outside, the unsigned distance), info (8,) int32 on the device or None (see
+    `read_sdf_grid_info`).  d2 and face equal meshing.mesh_sdf_grid bit for bit.  The axes' order is the caller's to guarantee
+    (geometry.mesh_sdf_grid checks it).  No host synchronisation."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    if not torch.is_tensor(tris) or tris.dim() != 3 or tuple(tris.shape[1:]) != (3, 3) or tris.dtype != torch.float32:
+        raise ValueError("mesh_sdf_grid: tris must be an (F, 3, 3) float32 triangle soup")
+    trunc = meshing.check_trunc(trunc, "mesh_sdf_grid")
+    for name, x in (("xs", xs), ("ys", ys), ("zs", zs)):
+        if not torch.is_tensor(x) or x.dim() != 1 or x.dtype != torch.float32 or x.shape[0] < 1:
+            raise ValueError("mesh_sdf_grid: %s must be a non-empty 1-D float32 tensor" % name)
+    nx, ny, nz = int(xs.shape[0]), int(ys.shape[0]), int(zs.shape[0])
+    if nx * ny * nz > 2 ** 31 - 1:
+        raise ValueError("mesh_sdf_grid: at most 2^31 - 1 lattice nodes, got %d x %d x %d" % (nx, ny, nz))
+    if occupancy is not None:
+        if (not torch.is_tensor(occupancy) or tuple(occupancy.shape) != (nx, ny, nz)
+                or occupancy.dtype not in (torch.bool, torch.uint8)):
+            raise ValueError("mesh_sdf_grid: occupancy must be a (%d, %d, %d) bool or uint8 tensor" % (nx, ny, nz))
+        occupancy = occupancy.contiguous().view(torch.uint8)
+    dev = _same_device(tris, xs, ys, zs, occupancy)
+    tris = tris.detach().contiguous()
+    xs, ys, zs = xs.detach().contiguous(), ys.detach().contiguous(), zs.detach().contiguous()
+    F = int(tris.shape[0])
+    d2 = torch.empty(nx, ny, nz, dtype=torch.float64, device=dev)
+    face = torch.empty(nx, ny, nz, dtype=torch.int32, device=dev) if want_face else None
+    sdf = torch.empty(nx, ny, nz, dtype=torch.float32, device=dev)
+    info = torch.empty(8, dtype=torch.int32, device=dev)
+    with _on_device(dev):
+        nbytes = int(lib.arah_mesh_sdf_grid_bytes(F, nx, ny, nz))
+        if nbytes == 0:
+            raise ValueError("mesh_sdf_grid: %d faces on %d x %d x %d nodes is out of range" % (F, nx, ny, nz))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _check(lib.arah_mesh_sdf_grid(_ptr(tris) if F else None, C.c_int32(F), _ptr(xs), C.c_int32(nx), _ptr(ys), C.c_int32(ny),
+                                      _ptr(zs), C.c_int32(nz), C.c_float(trunc), _ptr(occupancy), _ptr(d2), _ptr(face), _ptr(sdf),
+                                      _ptr(info), _ptr(scratch), C.c_size_t(nbytes), _stream()), "arah_mesh_sdf_grid")
+    return d2, face, sdf, info if want_info else None
 
 
 def face_area_cumsum(tris):

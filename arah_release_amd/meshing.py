@@ -994,6 +994,164 @@ def mesh_contains(verts, faces, points, resolution=512, chunk_pairs=1 << 24):
     return in_box & odd0 & odd1, in_box & (odd0 != odd1), tested
 
 
+# ---- signed distance to a mesh (DESIGN.md "Signed distance to a mesh on the device") ---------------------------------------
+def check_trunc(trunc, what="mesh_sdf"):
+    """The width of the band as the float32 number the kernels take: a number >= 0, +inf for no cut-off -> float."""
+    if isinstance(trunc, bool) or not isinstance(trunc, (int, float, np.integer, np.floating)) or math.isnan(float(trunc)) \
+            or float(trunc) < 0:
+        raise ValueError("%s: trunc must be a number >= 0 (+inf: no cut-off), got %r" % (what, trunc))
+    with np.errstate(over="ignore"):
+        return float(np.float32(trunc))
+
+
+def signed_distance(d2, inside, trunc=float("inf")):
+    """THE rule of the signed value: sdf = (inside ? -1 : +1) * min(sqrt(d2), trunc) in float64, rounded once to float32; negative
+    inside, like the project's own SDF.  d2 = +inf (outside the band) gives +-trunc, a NaN d2 stays NaN."""
+    t = check_trunc(trunc, "signed_distance")
+    r = torch.sqrt(d2.to(torch.float64))
+    m = torch.minimum(r, torch.full_like(r, t))
+    return torch.where(inside.bool(), -m, m).to(torch.float32)
+
+
+def _dot3(u, v):
+    return (u[..., 0] * v[..., 0] + u[..., 1] * v[..., 1]) + u[..., 2] * v[..., 2]
+
+
+def closest_on_triangles(p, a, b, c):
+    """Barycentric weights (wa, wb, wc) of the point of triangle (a, b, c) closest to p, by Voronoi regions (Ericson, Real-Time
+    Collision Detection 5.1.5): float64 (..., 3) tensors that broadcast; every operation rounded on its own, dot products summed
+    from the left.  The specification of closest_on_triangle (csrc/meshquery.hpp), region by region in its order: vertex a, vertex
+    b, edge ab, vertex c, edge ac, edge bc, interior."""
+    ab, ac, ap = b - a, c - a, p - a
+    d1, d2 = _dot3(ab, ap), _dot3(ac, ap)
+    bp = p - b
+    d3, d4 = _dot3(ab, bp), _dot3(ac, bp)
+    cp = p - c
+    d5, d6 = _dot3(ab, cp), _dot3(ac, cp)
+    vc = d1 * d4 - d3 * d2
+    vb = d5 * d2 - d1 * d6
+    va = d3 * d6 - d5 * d4
+    denom = 1.0 / ((va + vb) + vc)
+    wb = vb * denom
+    wc = vc * denom
+    wa = (1.0 - wb) - wc
+    zero, one = torch.zeros_like(wa), torch.ones_like(wa)
+
+    def region(cond, ra, rb, rc):
+        nonlocal wa, wb, wc
+        wa, wb, wc = torch.where(cond, ra, wa), torch.where(cond, rb, wb), torch.where(cond, rc, wc)
+    e43, e56 = d4 - d3, d5 - d6
+    w = e43 / (e43 + e56)
+    region((va <= 0) & (e43 >= 0) & (e56 >= 0), zero, 1.0 - w, w)
+    w = d2 / (d2 - d6)
+    region((vb <= 0) & (d2 >= 0) & (d6 <= 0), 1.0 - w, zero, w)
+    region((d6 >= 0) & (d5 <= d6), zero, zero, one)
+    v = d1 / (d1 - d3)
+    region((vc <= 0) & (d1 >= 0) & (d3 <= 0), 1.0 - v, v, zero)
+    region((d3 >= 0) & (d4 <= d3), zero, one, zero)
+    region((d1 <= 0) & (d2 <= 0), one, zero, zero)
+    return wa, wb, wc
+
+
+def soup_closest(tris, points, trunc=float("inf"), chunk_pairs=1 << 21):
+    """The closest triangle of the soup tris (F,3,3) float32 for every point (P,3) float32: -> d2 (P,) float64, face (P,) int32,
+    closest (P,3) float64.  What hip.mesh_closest and hip.mesh_query compute, brute force: per pair the weights of
+    `closest_on_triangles` in float64 on the float32 data, closest = (wa a + wb b) + wc c, d2 = |p - closest|^2 summed from the left;
+    per point the lexicographic minimum of (d2, face id); a pair whose d2 is NaN (0 / 0 in a triangle without extent) is no
+    candidate.  A soup with a vertex that is not finite, or a point that is not: d2 NaN, face -1, closest NaN.  No candidate at all
+    (F = 0): d2 +inf, face -1, closest NaN.  With a finite trunc >= 0 (rounded to float32 first) a point with d2 > double(trunc)^2
+    is outside the band and reports the same +inf, -1, NaN."""
+    t = check_trunc(trunc, "soup_closest")
+    if not isinstance(tris, torch.Tensor) or tris.dim() != 3 or tuple(tris.shape[1:]) != (3, 3) or tris.dtype != torch.float32:
+        raise ValueError("soup_closest: tris must be an (F, 3, 3) float32 triangle soup")
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise ValueError("soup_closest: points must be (P, 3) float32")
+    if points.device != tris.device:
+        raise ValueError("soup_closest: points live on %s, the mesh on %s" % (points.device, tris.device))
+    f64, dev = torch.float64, tris.device
+    P, F = int(points.shape[0]), int(tris.shape[0])
+    inf, nan = float("inf"), float("nan")
+    d2_out = torch.full((P,), inf, dtype=f64, device=dev)
+    face_out = torch.full((P,), -1, dtype=torch.int32, device=dev)
+    closest_out = torch.full((P, 3), nan, dtype=f64, device=dev)
+    if P == 0 or F == 0:
+        return d2_out, face_out, closest_out
+    T, X = tris.detach().to(f64), points.detach().to(f64)
+    if not bool(torch.isfinite(T).all()):
+        return torch.full_like(d2_out, nan), face_out, closest_out
+    a, b, c = T[None, :, 0], T[None, :, 1], T[None, :, 2]
+    ids = torch.arange(F, device=dev)
+    per = max(1, int(chunk_pairs) // F)
+    for p0 in range(0, P, per):
+        p = X[p0:p0 + per, None, :]
+        wa, wb, wc = closest_on_triangles(p, a, b, c)
+        cp = (wa[..., None] * a + wb[..., None] * b) + wc[..., None] * c
+        dv = p - cp
+        d2 = _dot3(dv, dv)
+        d2 = torch.where(torch.isnan(d2), torch.full_like(d2, inf), d2)
+        best = d2.min(dim=1).values
+        first = torch.where((d2 == best[:, None]) & (d2 < inf), ids[None, :], F).min(dim=1).values      # F: no candidate
+        found = first < F
+        g = first.clamp(max=F - 1)
+        d2_out[p0:p0 + per] = torch.where(found, best, torch.full_like(best, inf))
+        face_out[p0:p0 + per] = torch.where(found, first, torch.full_like(first, -1)).to(torch.int32)
+        picked = torch.gather(cp, 1, g[:, None, None].expand(-1, 1, 3))[:, 0]
+        closest_out[p0:p0 + per] = torch.where(found[:, None], picked, torch.full_like(picked, nan))
+    out = d2_out > t * t
+    d2_out = torch.where(out, torch.full_like(d2_out, inf), d2_out)
+    face_out = torch.where(out, torch.full_like(face_out, -1), face_out)
+    closest_out = torch.where(out[:, None], torch.full_like(closest_out, nan), closest_out)
+    bad = ~torch.isfinite(X).all(1)
+    d2_out = torch.where(bad, torch.full_like(d2_out, nan), d2_out)
+    face_out = torch.where(bad, torch.full_like(face_out, -1), face_out)
+    closest_out = torch.where(bad[:, None], torch.full_like(closest_out, nan), closest_out)
+    return d2_out, face_out, closest_out
+
+
+def mesh_sdf(verts, faces, points, trunc=float("inf"), resolution=512, chunk_pairs=1 << 21):
+    """The signed distance of points (P,3) float32 to the mesh verts (V,3) float32, faces (F,3) integer, as its parts: -> d2 (P,)
+    float64, face (P,) int32, closest (P,3) float64, inside (P,) bool, ambiguous (P,) bool.  d2, face and closest are `soup_closest`
+    of verts[faces] with the band `trunc`; inside and ambiguous are `mesh_contains` at `resolution`, unchanged and reported for every
+    point, in the band or not.  The signed value is signed_distance(d2, inside, trunc).  The sign is the reference's parity rule: it
+    is meant for watertight meshes, and `ambiguous` counts the points it could not decide.  A face id outside [0, V) raises."""
+    check_contains_args(verts, faces, points, resolution, "mesh_sdf")
+    if verts.dtype != torch.float32 or points.dtype != torch.float32:
+        raise ValueError("mesh_sdf: verts and points must be float32")
+    fc = faces.detach().long()
+    if fc.numel() and not bool(((fc >= 0) & (fc < int(verts.shape[0]))).all()):
+        raise ValueError("mesh_sdf: a face names a vertex outside [0, %d)" % int(verts.shape[0]))
+    tris = verts.detach()[fc] if fc.numel() else verts.new_zeros((0, 3, 3))
+    d2, face, closest = soup_closest(tris, points, trunc, chunk_pairs)
+    inside, ambiguous, _ = mesh_contains(verts, faces, points, resolution)
+    return d2, face, closest, inside, ambiguous
+
+
+def check_lattice_axes(xs, ys, zs, what="mesh_sdf_grid"):
+    """The three axes of a lattice: non-empty 1-D float32 tensors on one device, finite and strictly ascending (a host
+    synchronisation) -> (Nx, Ny, Nz)."""
+    for name, x in (("xs", xs), ("ys", ys), ("zs", zs)):
+        if not isinstance(x, torch.Tensor) or x.dim() != 1 or x.dtype != torch.float32 or x.shape[0] < 1:
+            raise ValueError("%s: %s must be a non-empty 1-D float32 tensor" % (what, name))
+        if not bool(torch.isfinite(x).all()) or (x.shape[0] > 1 and not bool((x[1:] > x[:-1]).all())):
+            raise ValueError("%s: %s must be finite and strictly ascending" % (what, name))
+    if len({xs.device, ys.device, zs.device}) != 1:
+        raise ValueError("%s: the axes must live on one device" % what)
+    dims = (int(xs.shape[0]), int(ys.shape[0]), int(zs.shape[0]))
+    if dims[0] * dims[1] * dims[2] > 2 ** 31 - 1:
+        raise ValueError("%s: at most 2^31 - 1 lattice nodes" % what)
+    return dims
+
+
+def mesh_sdf_grid(tris, xs, ys, zs, trunc, chunk_pairs=1 << 21):
+    """`soup_closest` on the nodes of the lattice xs x ys x zs (meshgrid, indexing "ij"): -> d2 (Nx,Ny,Nz) float64, face (Nx,Ny,Nz)
+    int32.  The specification of arah_mesh_sdf_grid (csrc/meshsdf.hpp), which equals it bit for bit; the number of nodes in the band
+    is (d2 <= double(trunc)^2 and d2 < inf).sum()."""
+    dims = check_lattice_axes(xs, ys, zs)
+    grid = torch.stack(torch.meshgrid(xs, ys, zs, indexing="ij"), dim=-1).reshape(-1, 3)
+    d2, face, _ = soup_closest(tris, grid, trunc, chunk_pairs)
+    return d2.reshape(dims), face.reshape(dims)
+
+
 def face_normals(tri):
     """Unit right-hand normals of a triangle soup (F,3,3) (pytorch3d Meshes.faces_normals_packed)."""
     n = torch.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0], dim=1)

@@ -1161,7 +1161,7 @@ class MetaAvatarRender(nn.Module):
         return res
 
     def geometry_metrics(self, inputs, gt, n_side=256, method="lattice", n_samples=100000, seed=0, clean=None, thresholds=None,
-                         iou=None):
+                         iou=None, sdf=None, sdf_band=0.05):
         """Geometry scores of the posed body of frame `inputs` against a ground truth `gt` in world metres on the inputs' GPU -- a
         mesh ((F,3,3) triangles or a (verts, faces) pair) or a scan (a geometry.PointCloud or a (P,3) tensor of points):
         `posed_mesh(inputs, n_side, method)` as the prediction, then
@@ -1170,10 +1170,24 @@ class MetaAvatarRender(nn.Module):
         nothing changes): the `clean` of posed_mesh -- the prediction is the indexed posed mesh without its floaters, one of which
         would otherwise set the Hausdorff distance.  iou (None: nothing changes) = N adds the volumetric IoU of the posed mesh and a
         ground-truth MESH from N uniform points (geometry.mesh_iou with the same seed): "iou" and, under "iou_" + name, its counts
-        n_a (the prediction), n_b, n_both, n_either, ambiguous_a, ambiguous_b, volume_a, volume_b and n_points.  Eval only."""
+        n_a (the prediction), n_b, n_both, n_either, ambiguous_a, ambiguous_b, volume_a, volume_b and n_points.  sdf (None: nothing
+        changes) = N scores the learned posed SDF as a FIELD against the signed distance of a ground-truth MESH: N points are
+        drawn in a band around it -- area-weighted surface samples (data.sample_surface) displaced by a uniform offset in
+        [-sdf_band, sdf_band] metres along a uniform direction, both from a torch.Generator on the device seeded with `seed` --,
+        geometry.mesh_sdf(gt, points, trunc=sdf_band) is compared with query_posed(inputs, points)["sdf"] clamped to the same band
+        at the points where the posed query converged: "sdf_l1" the mean absolute difference (metres), "sdf_sign" the share with
+        equal sign (negative inside), "sdf_n" the points used and "sdf_ambiguous" those among them whose ground-truth sign the
+        parity rule could not decide.  Eval only."""
         from . import geometry
         if self.training:
             raise ValueError("geometry_metrics is eval-only: call model.eval() first")
+        if sdf is not None:
+            if isinstance(sdf, bool) or int(sdf) != sdf or not 1 <= int(sdf) <= 2 ** 31 - 1:
+                raise ValueError("geometry_metrics: sdf must be a positive number of points, got %r" % (sdf,))
+            if isinstance(sdf_band, bool) or not isinstance(sdf_band, (int, float)) or not 0 < float(sdf_band) < float("inf"):
+                raise ValueError("geometry_metrics: sdf_band must be a finite length > 0, got %r" % (sdf_band,))
+            if geometry._is_cloud(gt):
+                raise ValueError("geometry_metrics: sdf needs a ground-truth mesh, not a scan")
         if inputs["rots"].device.type != "cuda":
             raise ValueError("geometry_metrics runs on the HIP kernels: the inputs must live on the GPU")
         if clean is not None:
@@ -1192,7 +1206,35 @@ class MetaAvatarRender(nn.Module):
             vol = geometry.mesh_iou(pred, gt, n_points=iou, seed=seed)
             res["iou"] = vol["iou"]
             res.update(("iou_" + k, vol[k]) for k in geometry.IOU_KEYS[1:] + ("n_points",))
+        if sdf is not None:
+            res.update(self._sdf_scores(inputs, gt, int(sdf), float(sdf_band), seed))
         return res
+
+    def _sdf_scores(self, inputs, gt, n, band, seed):
+        """The sdf= scores of `geometry_metrics`: -> dict of sdf_l1, sdf_sign (float64), sdf_n, sdf_ambiguous (int64), 0-dim tensors."""
+        from . import data, geometry, meshing
+        dev = inputs["rots"].device
+        with torch.no_grad():
+            verts, faces, _ = geometry._sdf_mesh(gt, "geometry_metrics")
+            verts, faces = verts.to(dev), faces.to(dev)
+            if int(faces.shape[0]) < 1:
+                raise ValueError("geometry_metrics: sdf needs a ground-truth mesh with faces")
+            gen = torch.Generator(device=dev).manual_seed(int(seed))
+            base, _ = data.sample_surface(verts, faces, n, generator=gen)
+            d = torch.randn(n, 3, dtype=torch.float64, device=dev, generator=gen)
+            d = d / d.norm(dim=1, keepdim=True).clamp_min(1e-300)
+            u = (2.0 * torch.rand(n, 1, dtype=torch.float64, device=dev, generator=gen) - 1.0) * band
+            pts = (base.double() + u * d).to(torch.float32).contiguous()
+            truth = geometry.mesh_sdf((verts, faces), pts, trunc=band)
+            q = self.query_posed(inputs, pts)
+            band32 = float(meshing.check_trunc(band))
+            ours = q["sdf"].double().clamp(-band32, band32)
+            use = q["converged"] & torch.isfinite(ours) & torch.isfinite(truth["sdf"])
+            k = use.sum()
+            diff = torch.where(use, (ours - truth["sdf"].double()).abs(), torch.zeros_like(ours))
+            same = use & ((ours < 0) == (truth["sdf"] < 0))
+            return {"sdf_l1": diff.sum() / k.double(), "sdf_sign": same.sum().double() / k.double(), "sdf_n": k,
+                    "sdf_ambiguous": (use & truth["ambiguous"]).sum()}
 
     def _forward(self, inputs, gen_cano_mesh, eval, render_maps):
         rots, Jtrs = inputs["rots"], inputs["Jtrs"]

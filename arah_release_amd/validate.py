@@ -26,7 +26,10 @@ the number of such frames.  ``--geometry-thresholds 0.005,0.01,0.02`` adds ``pre
 every distance T in metres (keys formatted with ``repr(float)``), per frame and as means.  ``--geometry-iou N`` adds ``iou``, the
 volumetric intersection over union of the posed mesh and the ground-truth mesh from N uniform points (geometry.mesh_iou; DESIGN.md
 "Containment, occupancy grids and IoU on the device"), to the frames whose ground truth is a mesh -- a frame scored against a scan
-gets no ``iou`` -- and its mean over those frames to the JSON line.  Without the options the output is unchanged."""
+gets no ``iou`` -- and its mean over those frames to the JSON line.  ``--geometry-sdf N`` (with ``--geometry-sdf-band METRES``,
+default 0.05) adds ``sdf_l1`` and ``sdf_sign`` in the same way: the posed SDF against the ground-truth mesh's signed distance at N
+points in a band around it (MetaAvatarRender.geometry_metrics, sdf=; DESIGN.md "Signed distance to a mesh on the device").
+Without the options the output is unchanged."""
 import argparse
 import importlib
 import json
@@ -61,6 +64,10 @@ def build_parser():
                    help="Distances in metres (up to 16): adds precision@T, recall@T and fscore@T to the geometry scores.")
     p.add_argument("--geometry-iou", type=int, default=None, metavar="N",
                    help="Uniform points of the volumetric IoU against ground-truth meshes: adds iou to the geometry scores.")
+    p.add_argument("--geometry-sdf", type=int, default=None, metavar="N",
+                   help="Points in a band around ground-truth meshes at which the posed SDF is compared with the mesh's signed "
+                        "distance: adds sdf_l1 and sdf_sign to the geometry scores.")
+    p.add_argument("--geometry-sdf-band", type=float, default=0.05, metavar="METRES", help="Half width of that band.")
     p.add_argument("--default-config", type=str, default="configs/default.yaml")
     p.add_argument("--body-models", type=str, default="body_models/misc", help="Directory of the SMPL model files.")
     return p
@@ -112,6 +119,10 @@ def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0
     n_iou = geometry.get("iou") if geometry is not None else None
     if n_iou:
         geo_keys = geo_keys + ("iou",)
+    n_sdf = geometry.get("sdf") if geometry is not None else None
+    if n_sdf:
+        geo_keys = geo_keys + ("sdf_l1", "sdf_sign")
+    mesh_only = tuple(q for q, key in enumerate(geo_keys) if key in ("iou", "sdf_l1", "sdf_sign"))   # scores a scan cannot have
 
     def step(item):
         gt = item.get("geometry.gt")
@@ -121,14 +132,20 @@ def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0
         out = lm.validation_step(item, lpips_fn=lpips_fn, metrics="device", data_range=data_range)
         scores = lm.model.geometry_metrics(lm.compose_inputs(item, eval=True), gt, n_side=geometry["n_side"],
                                            n_samples=geometry["n_samples"], seed=geometry["seed"], thresholds=thresholds or None,
-                                           iou=n_iou if n_iou and not geo._is_cloud(gt) else None)
+                                           iou=n_iou if n_iou and not geo._is_cloud(gt) else None,
+                                           **({"sdf": n_sdf, "sdf_band": geometry.get("sdf_band", 0.05)}
+                                              if n_sdf and not geo._is_cloud(gt) else {}))
         out["geometry"] = torch.stack([scores[k] for k in geo.METRIC_KEYS])
         if thresholds:
             out["geometry"] = torch.cat([out["geometry"], scores["precision"], scores["recall"], scores["fscore"]])
         if n_iou:   # a scan has no volume: its slot stays NaN and the frame gets no iou
             out["geometry"] = torch.cat([out["geometry"], scores["iou"].reshape(1) if "iou" in scores
                                          else torch.full((1,), float("nan"), dtype=torch.float64, device=out["geometry"].device)])
-            out["geometry_mesh"] = "iou" in scores
+        if n_sdf:   # ... and no signed distance
+            out["geometry"] = torch.cat([out["geometry"], torch.stack([scores["sdf_l1"], scores["sdf_sign"]]) if "sdf_l1" in scores
+                                         else torch.full((2,), float("nan"), dtype=torch.float64, device=out["geometry"].device)])
+        if n_iou or n_sdf:
+            out["geometry_mesh"] = not geo._is_cloud(gt)
         out["geometry_scan"] = isinstance(gt, geo.PointCloud) and gt.normals is None   # a scan without normals
         return out
 
@@ -156,8 +173,9 @@ def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0
             v = o["geometry"].cpu().tolist()
             if o["geometry_scan"] and v[nc] != v[nc]:
                 v[nc] = None
-            if n_iou and not o["geometry_mesh"]:
-                v[-1] = None
+            if mesh_only and not o["geometry_mesh"]:
+                for q in mesh_only:
+                    v[q] = None
             return v
         rows = [(rank + k * world, values(o)) for k, o in enumerate(kept) if "geometry" in o]
         import torch.distributed as dist
@@ -170,8 +188,9 @@ def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0
             for frame in res["frames"]:
                 if frame["frame"] in scored:
                     frame.update(zip(geo_keys, scored[frame["frame"]]))
-                    if n_iou and frame["iou"] is None:   # scored against a scan
-                        del frame["iou"]
+                    for q in mesh_only:   # scored against a scan
+                        if frame[geo_keys[q]] is None:
+                            del frame[geo_keys[q]]
             res["n_geometry"] = len(scored)
             for q, key in enumerate(geo_keys):
                 col = [v[q] for v in scored.values() if v[q] is not None]   # the frames that have the score
@@ -219,10 +238,16 @@ def main(argv=None, body=None, faces=None, log=print):
             if args.geometry_iou < 1:
                 raise ValueError("--geometry-iou takes a positive number of points")
             geometry["iou"] = args.geometry_iou
+        if args.geometry_sdf is not None:
+            if args.geometry_sdf < 1 or not 0 < args.geometry_sdf_band < float("inf"):
+                raise ValueError("--geometry-sdf takes a positive number of points and --geometry-sdf-band a finite length > 0")
+            geometry["sdf"], geometry["sdf_band"] = args.geometry_sdf, args.geometry_sdf_band
     elif args.geometry_thresholds is not None:
         raise ValueError("--geometry-thresholds needs --geometry DIR")
     elif args.geometry_iou is not None:
         raise ValueError("--geometry-iou needs --geometry DIR")
+    elif args.geometry_sdf is not None:
+        raise ValueError("--geometry-sdf needs --geometry DIR")
     res, n_mine, seconds = validate(lm, val_dataset, device, rank, world, lpips_fn, args.data_range, geometry)
     if world > 1:
         dist.barrier()

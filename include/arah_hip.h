@@ -873,6 +873,30 @@ int arah_mesh_contains_grid(const void* index, size_t index_bytes, int32_t n_fac
                             int64_t n_refs, const float* xs, int32_t nx, const float* ys, int32_t ny, const float* zs, int32_t nz,
                             uint8_t* occupancy, uint64_t* ambiguous, void* stream);
 
+/* ---- the truncated signed distance field of a soup on a lattice (csrc/meshsdf.hpp; no reference counterpart) ------------------- */
+/* The distance of every node of the lattice xs[nx] x ys[ny] x zs[nz] (float32, each axis strictly ascending: the convention of
+ * arah_mesh_contains_grid) to the soup tris [F,3,3] float32, cut off at trunc; the rule is meshing.mesh_sdf_grid, and d2 / face
+ * equal it bit for bit.  All arrays [nx][ny][nz] in C order:
+ *   d2        f64: the squared distance to the closest triangle (arah_mesh_closest's arithmetic), +inf where it exceeds
+ *             (double)trunc^2 -- the node is outside the BAND.  trunc = +inf cuts nothing off; trunc = 0 keeps the nodes on the surface
+ *   face      i32 or NULL: the lowest id among the triangles at that distance, -1 outside the band (asking for it walks the
+ *             band a second time)
+ *   sdf       f32 or NULL: (occupancy ? -1 : +1) * min(sqrt(d2), trunc) in float64, rounded once -- meshing.signed_distance
+ *   occupancy u8 or NULL: as arah_mesh_contains_grid writes it on the same lattice; NULL counts every node as outside
+ *   info      DEVICE int32 [8], 8-byte aligned: [0] nodes in the band, [1] status, [2..3] point-triangle tests made (one uint64), [4..7] triangles
+ *             of the size classes lane / wave / workgroup / several workgroups (a triangle whose dilated box holds no node is in none)
+ * status 1: some vertex is not finite; then d2 is NaN and face -1 everywhere, as arah_mesh_closest answers.  A node with a
+ * coordinate that is not finite gets NaN / -1 too.  F = 0: +inf / -1 everywhere.
+ * The work follows the band: each triangle visits the nodes inside its bounding box dilated by trunc (a conservative superset of
+ * the nodes within trunc of it).  Integer atomics only: the result does not depend on the order of arrival.  Nothing is
+ * truncated.  No host synchronisation.  scratch: arah_mesh_sdf_grid_bytes(F, nx, ny, nz) device bytes, 256-byte aligned; 0 for
+ * a size that is negative or too large.  0 <= F <= 2^26.  ARAH_E_OVERFLOW when nx ny nz does not fit an int32, ARAH_E_BADARG for
+ * a trunc that is negative or NaN. */
+size_t arah_mesh_sdf_grid_bytes(int64_t n_faces, int64_t nx, int64_t ny, int64_t nz);
+int arah_mesh_sdf_grid(const float* tris, int32_t n_faces, const float* xs, int32_t nx, const float* ys, int32_t ny, const float* zs,
+                       int32_t nz, float trunc, const uint8_t* occupancy, double* d2, int32_t* face, float* sdf, int32_t* info,
+                       void* scratch, size_t scratch_bytes, void* stream);
+
 /* name of the dominant kernel, for profilers */
 const char* arah_dominant_kernel(void);
 #ifdef __cplusplus
