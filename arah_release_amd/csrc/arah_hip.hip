@@ -4508,8 +4508,9 @@ static int run_broyden3(const FrameDev& fd, Workspace& w, const float* tgt, Cano
 
 int arah_broyden3_lbs(const ArahFrame* f, const float* tgt, const float* x0, const float* T0, int32_t n, float* x,
                       float* T, float* err, uint8_t* conv, int32_t canon_kernel, void* workspace, size_t wbytes, void* stream) {
-    if (!f || !tgt || !x0 || !T0 || !x || !T || !conv || n < 0 || !workspace) return ARAH_E_BADARG;
-    if (n == 0) return ARAH_OK;
+    if (!f || n < 0 || !workspace) return ARAH_E_BADARG;
+    if (n == 0) return ARAH_OK;   // an empty tensor's pointer is null: checked after n, like the per-point seams
+    if (!tgt || !x0 || !T0 || !x || !T || !conv) return ARAH_E_BADARG;
     Workspace w = carve(workspace, n, 1);
     if (wbytes < w.bytes) return ARAH_E_WORKSPACE;
     if (int arc = setup_attributes()) return arc;

@@ -431,7 +431,9 @@ int arah_color_eval(const ArahFrame* h_frame, const float* x_norm, const float* 
 int arah_nearest_inverse_lbs(const ArahFrame* h_frame, const float* pts, int32_t n_pts, int32_t* idx,
                              float* x_hat0, float* T0, void* workspace, size_t workspace_bytes, void* stream);
 /* Broyden on g(x) = LBS(x) - tgt from caller-supplied x0 [P,3], T0 [P,16];
- * J^-1_0 = (sum_j w_j(x0) A_j)[:3,:3]^-1.  -> x [P,3] raw canonical, T [P,16], err [P], conv [P] */
+ * J^-1_0 = (sum_j w_j(x0) A_j)[:3,:3]^-1.  -> x [P,3] raw canonical, T [P,16], err [P] (optional), conv [P].
+ * A point whose start is never improved keeps T0 -- rows 0..2 and T0[3][3] bit for bit; T0[3][0..2] must be zero (the
+ * bottom row of an affine transform): the solver carries the target there and returns zeros.  n_pts = 0 is a no-op. */
 int arah_broyden3_lbs(const ArahFrame* h_frame, const float* tgt, const float* x0, const float* T0,
                       int32_t n_pts, float* x, float* T, float* err, uint8_t* conv, int32_t canon_kernel /* ARAH_CANON_KERNEL_* */,
                       void* workspace, size_t workspace_bytes, void* stream);

@@ -247,7 +247,7 @@ def nn_inverse_lbs(fr, pts):
     """Inverse LBS with the nearest vertex's weights: returns raw canonical x_hat0 (P,3), T0 (P,4,4)
     (RT:382-400 without the final normalisation; RT:403-422)."""
     T = blend_transforms(fr, fr.vert_weights[nearest_vertex(fr, pts)])
-    ph = torch.cat([pts - fr.trans, torch.ones(pts.shape[0], 1)], dim=-1)
+    ph = torch.cat([pts - fr.trans, torch.ones(pts.shape[0], 1, dtype=pts.dtype)], dim=-1)
     xh = torch.einsum("pij,pj->pi", torch.linalg.inv(T), ph)[:, :3]
     return xh, T
 
@@ -308,8 +308,8 @@ def sphere_trace(fr, o, d, near, far):
     t = near.clone()
     unfinished = near < far
     diverged = near >= far
-    x_cur = torch.zeros(N, 3)
-    T_cur = torch.zeros(N, 4, 4)
+    x_cur = torch.zeros(N, 3, dtype=o.dtype)
+    T_cur = torch.zeros(N, 4, 4, dtype=o.dtype)
     for _ in range(SPHERE_ITERS):
         idx = unfinished.nonzero()[:, 0]
         if idx.numel() == 0:
@@ -337,7 +337,7 @@ def joint_root_find(fr, o, d, sel, x0, z0, T0):
     if ids.numel() == 0:
         return x_opt, z_opt, T_opt, conv
     xs, ds, os_ = x0[ids], d[ids], o[ids]
-    J = torch.zeros(ids.numel(), 4, 4)
+    J = torch.zeros(ids.numel(), 4, 4, dtype=x0.dtype)
     J[:, 1:, :3] = lbs_jacobian(fr, xs)                           # RFU:406
     # d(metric sdf)/d(metric x) == d(normalised sdf)/d(normalised x) up to rounding (RFU:408-413)
     with torch.enable_grad():
@@ -414,13 +414,9 @@ def sample_depths(conv, start, end, near, n_steps, n_near, n_far, jitter=None):
     return z, mask
 
 
-def canonicalize(fr, pts):
-    """Posed points (P,3) -> canonical by 3-D Broyden on forward LBS (RT:403-461, RFU:267-362).
-    Returns x_hat_norm (P,3), T (P,4,4), converged (P,)."""
-    if pts.shape[0] == 0:
-        return torch.zeros(0, 3), torch.zeros(0, 4, 4), torch.zeros(0, dtype=torch.bool)
-    x0, T0 = nn_inverse_lbs(fr, pts)
-    tgt = pts - fr.trans
+def broyden3_lbs(fr, tgt, x0, T0):
+    """3-D Broyden on g(x) = LBS(x) - tgt from the caller's starts (RFU:267-362): what the seam arah_broyden3_lbs
+    computes.  Returns broyden()'s 4-tuple: x_hat (P,3) raw canonical, T (P,4,4), |g| (P,), converged (P,)."""
     # the weights at x0 give both J^-1_0 (RFU:327-328) and, through g(x0), the first residual
     Jinv = torch.linalg.inv(blend_transforms(fr, query_weights(fr, x0))[:, :3, :3])
 
@@ -428,7 +424,16 @@ def canonicalize(fr, pts):
         xb, T = lbs_forward(fr, x)
         return xb - tgt[k], T
 
-    x, T, _, ok = broyden(resid, x0, T0, Jinv)
+    return broyden(resid, x0, T0, Jinv)
+
+
+def canonicalize(fr, pts):
+    """Posed points (P,3) -> canonical by 3-D Broyden on forward LBS (RT:403-461, RFU:267-362).
+    Returns x_hat_norm (P,3), T (P,4,4), converged (P,)."""
+    if pts.shape[0] == 0:
+        return torch.zeros(0, 3, dtype=pts.dtype), torch.zeros(0, 4, 4, dtype=pts.dtype), torch.zeros(0, dtype=torch.bool)
+    x0, T0 = nn_inverse_lbs(fr, pts)
+    x, T, _, ok = broyden3_lbs(fr, pts - fr.trans, x0, T0)
     return normalize_points(fr, x), T, ok
 
 

@@ -261,7 +261,8 @@ def test_wide_range_skinning_network(scene, eng):
     """Fixture F17: the reference on a subject whose skinning MLP has hidden activations up to ~3000 (weight-norm gains x 8)
     -- 4e5 in the z units the split engine's loop C computes in, far outside the f16 range.  The per-frame probe must scale
     the wide layers down (the SCALED instance of k_canon_wave runs), the solver must still find the reference's roots, and the
-    range counter must stay at zero; the exact engine takes the same subject as it is."""
+    range counter must stay at zero; the exact engine takes the same subject as it is.
+    (Float64 residuals, call shapes and refills at this seam: tests/test_root_solvers_f64.py.)"""
     g = golden("f17_wide_skinning.npz")
     assert float(g["hidden_absmax"].max()) > 1000.0
     c = _make_ctx(scene, eng, widen=float(g["scale"]))
@@ -444,6 +445,7 @@ def test_body_tables_built_early_are_the_inline_ones(ctx, scene):
 
 @gpu
 def test_broyden3(ctx):
+    """Loop C against the reference's recorded roots of F1; float64 residuals, call shapes and refills at this seam: tests/test_root_solvers_f64.py."""
     g = golden("f1_broyden3.npz")
     hip = ctx["hip"]
     x, Tm, err, ok = hip.broyden3_lbs(ctx["frame"], ctx["ws"], T(g["tgt"]), T(g["x0"]), T(g["T0"]))
@@ -462,7 +464,8 @@ def test_broyden3_kernels_of_the_call(ctx):
     """The solver is chosen per CALL (the canon_kernel argument / ArahSampling.canon_kernel; round 3 read an environment
     variable into a process-wide static): the point-owning-wave kernel with its hi fragments in LDS (default), the same with
     every fragment from L2, and round 2's tile kernel find the same roots of F1 -- the two wave kernels bit for bit (the same
-    arithmetic on operands delivered differently), the tile kernel within the known-answer tolerances."""
+    arithmetic on operands delivered differently), the tile kernel within the known-answer tolerances.
+    (Float64 residuals, call shapes and refills at this seam: tests/test_root_solvers_f64.py.)"""
     g = golden("f1_broyden3.npz")
     hip = ctx["hip"]
     args = (ctx["frame"], ctx["ws"], T(g["tgt"]), T(g["x0"]), T(g["T0"]))
@@ -481,7 +484,8 @@ def test_broyden3_kernels_of_the_call(ctx):
 @pytest.mark.parametrize("eng", ENGINES)
 def test_joint_root_find(ctx, ctx_fp32, eng):
     """Loop B through its own seam (arah_joint_root_find) against the reference's search_iso_surface_depth
-    (RFU:365-484) on 256 rays with perturbed starts, masked-out rays and a few hopeless starts (f1_broyden4)."""
+    (RFU:365-484) on 256 rays with perturbed starts, masked-out rays and a few hopeless starts (f1_broyden4).
+    (Float64 residuals, call shapes and refills at this seam: tests/test_root_solvers_f64.py.)"""
     ctx = ctx if eng == "split" else ctx_fp32
     g = golden("f1_broyden4.npz")
     hip = ctx["hip"]
