@@ -2851,6 +2851,7 @@ __global__ void k_points_cam(FrameDev fr, int n, RaySet rs, const float* dists, 
 #include "metrics.hpp"
 #include "meshdist.hpp"
 #include "meshsdf.hpp"
+#include "meshwinding.hpp"
 #include "meshray.hpp"
 #include "pointdist.hpp"
 namespace {
@@ -5605,6 +5606,108 @@ int arah_mesh_contains_grid(const void* index, size_t index_bytes, int32_t n_fac
     hipLaunchKernelGGL(k_ct_grid, dim3((unsigned)(nx * ny), (unsigned)((nz + kCtGridZ - 1) / kCtGridZ)), dim3(64), 0, s,
                        (const CtHeader*)ix.hdr, (const double*)ix.rec, (const unsigned*)ix.start, refs, (unsigned)n_refs, n_faces, xs, ys, ny,
                        zs, nz, occupancy, reinterpret_cast<unsigned long long*>(ambiguous));
+    return check_launch();
+}
+
+// ---- generalized winding numbers (meshwinding.hpp) --------------------------------------------------------------
+static bool winding_sizes_ok(int32_t n_faces, int32_t& depth) {
+    if (n_faces < 0 || n_faces > kWnMaxFaces || depth < -1 || depth > kWnMaxDepth) return false;
+    if (depth < 0) depth = wn_auto_depth(n_faces);
+    return true;
+}
+
+static bool winding_accuracy_ok(double accuracy) { return accuracy >= 1.0; }   // false for a NaN
+
+size_t arah_winding_index_bytes(int32_t n_faces, int32_t depth) {
+    if (!winding_sizes_ok(n_faces, depth)) return 0;
+    return carve_winding(nullptr, n_faces, depth).bytes;
+}
+
+int arah_winding_index_count(const float* verts, int32_t n_verts, const int32_t* faces, int32_t n_faces, int32_t depth, void* index,
+                             size_t index_bytes, int32_t* order, float* tris, void* stream) {
+    if (!index || n_verts < 0 || !winding_sizes_ok(n_faces, depth)) return ARAH_E_BADARG;
+    if (n_faces > 0 && (!verts || !faces || !order || !tris || n_verts < 1)) return ARAH_E_BADARG;
+    const WnIndex ix = carve_winding(index, n_faces, depth);
+    if (index_bytes < ix.bytes) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const long long cells = 1ll << (3 * depth);
+    if (hipMemsetAsync(ix.ccnt, 0, (size_t)cells * sizeof(unsigned), s) != hipSuccess) return ARAH_E_LAUNCH;
+    hipLaunchKernelGGL(k_wn_box, dim3(1), dim3(kWnThreads), 0, s, verts, n_verts, faces, n_faces, depth, ix.hdr);
+    if (n_faces > 0) {
+        const int g = (n_faces + kWnThreads - 1) / kWnThreads;
+        if (hipMemsetAsync(ix.tmp, 0xff, (size_t)n_faces * sizeof(int), s) != hipSuccess) return ARAH_E_LAUNCH;
+        hipLaunchKernelGGL(k_wn_keys, dim3(g), dim3(kWnThreads), 0, s, verts, n_verts, faces, n_faces, depth, (const WnHeader*)ix.hdr,
+                           ix.key, ix.ccnt);
+        hipLaunchKernelGGL((k_wn_scan<unsigned, unsigned>), dim3(1), dim3(kWnScanThreads), 0, s, (const unsigned*)ix.ccnt, cells, ix.cstart,
+                           ix.ccnt, (long long*)nullptr);
+        hipLaunchKernelGGL(k_wn_fill, dim3(g), dim3(kWnThreads), 0, s, (const unsigned*)ix.key, n_faces, (unsigned)cells, ix.ccnt, ix.tmp);
+        hipLaunchKernelGGL(k_wn_rank, dim3(g), dim3(kWnThreads), 0, s, verts, n_verts, faces, n_faces, depth, (const unsigned*)ix.key,
+                           (const unsigned*)ix.cstart, (const int*)ix.tmp, order, ix.skey, tris, ix.hdr);
+        hipLaunchKernelGGL(k_wn_heads, dim3(g), dim3(kWnThreads), 0, s, (const unsigned*)ix.skey, n_faces, depth, ix.hlev, ix.cnt64);
+    }
+    hipLaunchKernelGGL((k_wn_scan<long long, long long>), dim3(1), dim3(kWnScanThreads), 0, s, (const long long*)ix.cnt64,
+                       (long long)n_faces, ix.prefix, (long long*)nullptr, &ix.hdr->n_nodes);
+    return check_launch();
+}
+
+int arah_winding_index_fill(const void* index, size_t index_bytes, int32_t n_faces, int32_t depth, const float* tris, int32_t* node_i,
+                            double* node_f, int64_t n_nodes, void* stream) {
+    if (!index || n_nodes < 0 || !winding_sizes_ok(n_faces, depth)) return ARAH_E_BADARG;
+    if (n_nodes > 0x7fffffffll) return ARAH_E_OVERFLOW;
+    const WnIndex ix = carve_winding(const_cast<void*>(index), n_faces, depth);
+    if (index_bytes < ix.bytes) return ARAH_E_WORKSPACE;
+    if (n_nodes == 0 || n_faces == 0) return ARAH_OK;
+    if (!tris || !node_i || !node_f) return ARAH_E_BADARG;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int N = (int)n_nodes, g = (n_faces + kWnThreads - 1) / kWnThreads;
+    const int gn = (int)(((long long)N + kWnThreads - 1) / kWnThreads);           // N may be INT32_MAX
+    if (hipMemsetAsync(node_i, 0, (size_t)N * kWnNodeI * sizeof(int), s) != hipSuccess) return ARAH_E_LAUNCH;
+    if (hipMemsetAsync(node_f, 0, (size_t)N * kWnNodeF * sizeof(double), s) != hipSuccess) return ARAH_E_LAUNCH;
+    hipLaunchKernelGGL(k_wn_nodes, dim3(g), dim3(kWnThreads), 0, s, (const unsigned*)ix.skey, (const int*)ix.hlev,
+                       (const long long*)ix.prefix, n_faces, depth, N, node_i);
+    hipLaunchKernelGGL(k_wn_leaf, dim3(g), dim3(kWnThreads), 0, s, (const int*)ix.hlev, (const long long*)ix.prefix, tris, n_faces, depth, N,
+                       (const int*)node_i, node_f);
+    for (int level = depth - 1; level >= 0; --level)
+        hipLaunchKernelGGL(k_wn_inner, dim3(gn), dim3(kWnThreads), 0, s, level, N, (const int*)node_i, node_f);
+    hipLaunchKernelGGL(k_wn_centroid, dim3(gn), dim3(kWnThreads), 0, s, (const WnHeader*)ix.hdr, (const unsigned*)ix.skey, n_faces, depth, N,
+                       (const int*)node_i, node_f);
+    hipLaunchKernelGGL(k_wn_radius, dim3((unsigned)(((long long)N + kWnThreads / 64 - 1) / (kWnThreads / 64))), dim3(kWnThreads), 0, s, tris, n_faces, N,
+                       (const int*)node_i, node_f);
+    return check_launch();
+}
+
+int arah_mesh_winding(const void* index, size_t index_bytes, int32_t n_faces, int32_t depth, const float* tris, const int32_t* node_i,
+                      const double* node_f, int64_t n_nodes, const float* pts, int32_t n_pts, double accuracy, double* w,
+                      uint8_t* inside, int32_t* n_exact, int32_t* n_far, void* stream) {
+    if (!index || n_pts < 0 || n_nodes < 0 || !winding_sizes_ok(n_faces, depth) || !winding_accuracy_ok(accuracy)) return ARAH_E_BADARG;
+    if (n_nodes > 0x7fffffffll) return ARAH_E_OVERFLOW;
+    if (n_nodes > 0 && (!tris || !node_i || !node_f || n_faces < 1)) return ARAH_E_BADARG;
+    const WnIndex ix = carve_winding(const_cast<void*>(index), n_faces, depth);
+    if (index_bytes < ix.bytes) return ARAH_E_WORKSPACE;
+    if (n_pts == 0) return ARAH_OK;
+    if (!pts || !w) return ARAH_E_BADARG;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_wn_points, dim3((unsigned)(((long long)n_pts + kWnThreads - 1) / kWnThreads)), dim3(kWnThreads), 0, s, (const WnHeader*)ix.hdr, tris,
+                       n_faces, depth, node_i, node_f, (int)n_nodes, accuracy * accuracy, pts, n_pts, w, inside, n_exact, n_far);
+    return check_launch();
+}
+
+int arah_mesh_winding_grid(const void* index, size_t index_bytes, int32_t n_faces, int32_t depth, const float* tris,
+                           const int32_t* node_i, const double* node_f, int64_t n_nodes, const float* xs, int32_t nx, const float* ys,
+                           int32_t ny, const float* zs, int32_t nz, double accuracy, double* w, uint8_t* inside, int32_t* n_exact,
+                           int32_t* n_far, void* stream) {
+    if (!index || n_nodes < 0 || !winding_sizes_ok(n_faces, depth) || !winding_accuracy_ok(accuracy)) return ARAH_E_BADARG;
+    if (n_nodes > 0x7fffffffll) return ARAH_E_OVERFLOW;
+    if (n_nodes > 0 && (!tris || !node_i || !node_f || n_faces < 1)) return ARAH_E_BADARG;
+    if (!xs || !ys || !zs || !w || nx < 1 || ny < 1 || nz < 1) return ARAH_E_BADARG;
+    const long long n_pts = (long long)nx * ny * nz;
+    if (n_pts > 0x7fffffffll) return ARAH_E_OVERFLOW;
+    const WnIndex ix = carve_winding(const_cast<void*>(index), n_faces, depth);
+    if (index_bytes < ix.bytes) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_wn_grid, dim3((unsigned)((n_pts + kWnThreads - 1) / kWnThreads)), dim3(kWnThreads), 0, s, (const WnHeader*)ix.hdr,
+                       tris, n_faces, depth, node_i, node_f, (int)n_nodes, accuracy * accuracy, xs, ys, ny, zs, nz, n_pts, w, inside, n_exact,
+                       n_far);
     return check_launch();
 }
 

@@ -1161,8 +1161,63 @@ def _contains_index(verts, faces, resolution, index, what):
     return index
 
 
-def mesh_contains(mesh, points, resolution=512, index=None, return_ambiguous=False):
-    """(P,) bool: which of the points (P,3) float32 or float64 lie inside the mesh -- an (F,3,3) soup or a (verts, faces) pair as
+def _is_winding_index_of(index, verts, faces, depth):
+    """Whether `index` can be the hip.winding_index of this mesh: its kind, device, numbers of vertices and faces, and its depth where
+    one is asked for.  The coordinates are NOT compared (that would be a host synchronisation per call): an index of another mesh
+    with the same two counts on the same device is accepted and answers for that other mesh."""
+    from . import hip
+    return (isinstance(index, hip.WindingIndex) and index.device == verts.device and index.n_faces == int(faces.shape[0])
+            and index.n_verts == int(verts.shape[0]) and (depth is None or index.depth == depth))
+
+
+def _winding(verts, faces, points, accuracy, what, index=None, depth=None):
+    """The winding number of float32 points against a mesh whose face ids were checked -> w (P,) float64, inside (P,) bool, n_exact,
+    n_far (P,) int32, on the mesh's device: the kernels for a mesh on the GPU, the specification on the host."""
+    from . import meshing
+    acc = meshing.check_accuracy(accuracy, what)
+    if (not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3
+            or points.dtype not in (torch.float32, torch.float64)):
+        raise ValueError("%s: points must be (P, 3) float32 or float64" % what)
+    if points.device != verts.device:
+        raise ValueError("%s: points live on %s, the mesh on %s" % (what, points.device, verts.device))
+    pts = points.detach().to(torch.float32).contiguous()
+    with torch.no_grad():
+        if verts.is_cuda:
+            from . import hip
+            if index is None:
+                index = hip.winding_index(verts, faces, depth)
+            elif not _is_winding_index_of(index, verts, faces, depth):
+                raise ValueError("%s: index must be the hip.winding_index of this mesh%s" % (
+                    what, "" if depth is None else " at depth %r" % (depth,)))
+            return hip.mesh_winding(index, pts, acc, want_counts=True)
+        if index is not None:
+            raise ValueError("%s: an index belongs to a mesh on the GPU" % what)
+        tree = meshing.winding_tree(verts, faces, depth)
+        w, n_exact, n_far = meshing.mesh_winding(tree, pts, acc)
+        return w, meshing.winding_inside(w, tree.orient), n_exact, n_far
+
+
+def winding_number(mesh, points, accuracy=3.0, depth=None, index=None, return_counts=False):
+    """The generalized winding number w (P,) float64 of points (P,3) (rounded to float32) around a mesh -- an (F,3,3) soup or a
+    (verts, faces) pair as in `mesh_contains`, every face id checked as in `mesh_sdf` --, on the mesh's device.  Defined for meshes
+    that are NOT watertight: open sheets, holes, flipped or duplicated patches; |w| is near 1 inside, near 0 outside, and the sign
+    follows the faces' orientation (meshing.winding_orient; `rule="winding"` of `mesh_contains` takes it into account).  The rule is
+    meshing.winding_tree / meshing.mesh_winding: exact solid angles for near triangles, one dipole for a cluster farther than
+    `accuracy` times its radius; accuracy=inf is the exact sum, depth the tree's (None: meshing.winding_depth).  index: the
+    hip.winding_index of the mesh built earlier, or None (then one host synchronisation); an index is checked by its device, its
+    numbers of vertices and faces and, where depth is given, its depth -- not by its coordinates.  return_counts=True -> (w, n_exact, n_far),
+    the triangles summed exactly and the dipoles taken per point.  The kernels for a mesh on the GPU, the specification on the host:
+    equal decisions and dipole terms, exact terms equal up to atan2's last bits."""
+    verts, faces, _ = _sdf_mesh(mesh, "winding_number")
+    w, _, n_exact, n_far = _winding(verts, faces, points, accuracy, "winding_number", index, depth)
+    return (w, n_exact, n_far) if return_counts else w
+
+
+def mesh_contains(mesh, points, resolution=512, index=None, return_ambiguous=False, rule="parity", accuracy=3.0):
+    """rule="winding": inside = orient * winding number >= 0.5 (`winding_number` at `accuracy`; meant for meshes that are NOT
+    watertight; every face id is checked; nothing is ambiguous; index: a hip.winding_index or None).  rule="parity", the default:
+
+    (P,) bool: which of the points (P,3) float32 or float64 lie inside the mesh -- an (F,3,3) soup or a (verts, faces) pair as
     in `mesh_metrics`, on the points' device.  The rule is meshing.mesh_contains, the reference's check_mesh_contains with its
     triangle hash at `resolution` cells per axis: crossing parities of the z-column through the point, both ways; STRICT -- a
     column that passes exactly through an edge or a vertex in rescaled coordinates counts no crossing there, and the point may
@@ -1171,6 +1226,10 @@ def mesh_contains(mesh, points, resolution=512, index=None, return_ambiguous=Fal
     earlier, or None.  hip.mesh_contains for a mesh on the GPU (one host synchronisation, for the index), the specification for
     one on the host; equal bit for bit."""
     from . import meshing
+    if meshing.check_rule(rule, "mesh_contains") == "winding":
+        verts, faces, _ = _sdf_mesh(mesh, "mesh_contains")
+        _, inside, _, _ = _winding(verts, faces, points, accuracy, "mesh_contains", index)
+        return (inside, torch.zeros_like(inside)) if return_ambiguous else inside
     verts, faces = _contains_mesh(mesh, "mesh_contains")
     res = meshing.check_contains_args(verts, faces, points, resolution, "mesh_contains")
     with torch.no_grad():
@@ -1251,8 +1310,32 @@ def _cell_centres(lo, ext, dims, dev):
     return [(lo[a] + (torch.arange(dims[a], dtype=torch.float64) + 0.5) * (ext[a] / dims[a])).to(torch.float32).to(dev) for a in range(3)]
 
 
-def voxelize(mesh, dims=None, resolution=None, bounds=None, padding=0.0, hash_resolution=512, index=None):
-    """The mesh (as in `mesh_contains`) on a regular lattice: -> dict with "occupancy" (Nx,Ny,Nz) bool -- whether the CENTRE of the
+def _winding_lattice(verts, faces, axes, dims, accuracy, index, what):
+    """The winding number on a lattice -> w (Nx,Ny,Nz) float64, occupancy (Nx,Ny,Nz) bool: hip.mesh_winding_grid on the GPU, the
+    specification on the meshgrid on the host."""
+    from . import meshing
+    acc = meshing.check_accuracy(accuracy, what)
+    with torch.no_grad():
+        if verts.is_cuda:
+            from . import hip
+            if index is None:
+                index = hip.winding_index(verts, faces)
+            elif not _is_winding_index_of(index, verts, faces, None):
+                raise ValueError("%s: index must be the hip.winding_index of this mesh" % what)
+            w, occ, _, _ = hip.mesh_winding_grid(index, *axes, acc)
+            return w, occ
+        if index is not None:
+            raise ValueError("%s: an index belongs to a mesh on the GPU" % what)
+        grid = torch.stack(torch.meshgrid(*axes, indexing="ij"), dim=-1).reshape(-1, 3)
+        w, inside, _, _ = _winding(verts, faces, grid, acc, what)
+        return w.reshape(dims), inside.reshape(dims)
+
+
+def voxelize(mesh, dims=None, resolution=None, bounds=None, padding=0.0, hash_resolution=512, index=None, rule="parity", accuracy=3.0):
+    """rule="winding": occupancy = orient * winding number >= 0.5 as in `mesh_contains` (for meshes that are not watertight; face ids
+    checked; "ambiguous" is 0; the dict gains "winding" (Nx,Ny,Nz) float64; index: a hip.winding_index or None).  Default "parity":
+
+    The mesh (as in `mesh_contains`) on a regular lattice: -> dict with "occupancy" (Nx,Ny,Nz) bool -- whether the CENTRE of the
     cell lies inside --, "xs", "ys", "zs" the centres' float32 coordinates, "ambiguous" the number of ambiguous centres (0-dim int64
     tensor) and "bounds" (lo, hi) as tuples of floats.  The lattice spans `bounds` = (lo, hi), default the bounding box of the
     vertices the faces use (read back: a host synchronisation), widened by the length `padding` on every side; dims = (Nx, Ny, Nz)
@@ -1261,11 +1344,19 @@ def voxelize(mesh, dims=None, resolution=None, bounds=None, padding=0.0, hash_re
     float64 and rounded to float32.  hip.mesh_contains_grid on the GPU (the 2-D test once per lattice column), the specification
     on the meshgrid on the host; equal bit for bit."""
     from . import meshing
-    verts, faces = _contains_mesh(mesh, "voxelize")
-    res = meshing.check_contains_args(verts, faces, None, hash_resolution, "voxelize")
+    winding = meshing.check_rule(rule, "voxelize") == "winding"
+    if winding:                                              # no hash: hash_resolution is not read
+        verts, faces = _sdf_mesh(mesh, "voxelize")[:2]
+    else:
+        verts, faces = _contains_mesh(mesh, "voxelize")
+        res = meshing.check_contains_args(verts, faces, None, hash_resolution, "voxelize")
     lo, hi, ext, dims = _lattice_cells(verts, faces, dims, resolution, bounds, padding, "voxelize")
     dev = verts.device
     axes = _cell_centres(lo, ext, dims, dev)
+    if winding:
+        w, occ = _winding_lattice(verts, faces, axes, dims, accuracy, index, "voxelize")
+        return {"occupancy": occ, "xs": axes[0], "ys": axes[1], "zs": axes[2], "ambiguous": torch.zeros((), dtype=torch.int64, device=dev),
+                "bounds": (tuple(lo.tolist()), tuple(hi.tolist())), "winding": w}
     with torch.no_grad():
         if verts.is_cuda:
             from . import hip
@@ -1280,8 +1371,12 @@ def voxelize(mesh, dims=None, resolution=None, bounds=None, padding=0.0, hash_re
             "bounds": (tuple(lo.tolist()), tuple(hi.tolist()))}
 
 
-def mesh_iou(mesh_a, mesh_b, n_points=100000, seed=0, bounds=None, padding=0.0, resolution=512, return_points=False):
-    """Volumetric intersection over union of two (watertight) meshes, as in `mesh_contains`, on one device -- the third number of
+def mesh_iou(mesh_a, mesh_b, n_points=100000, seed=0, bounds=None, padding=0.0, resolution=512, return_points=False, rule="parity",
+             accuracy=3.0):
+    """rule="winding": both meshes answer `mesh_contains(rule="winding", accuracy=accuracy)` -- the IoU of meshes that are not
+    watertight; ambiguous_a and ambiguous_b are 0, and the dict gains "winding" = (w_a, w_b), two (n,) float64.  Default "parity":
+
+    Volumetric intersection over union of two (watertight) meshes, as in `mesh_contains`, on one device -- the third number of
     the occupancy-network evaluation protocol.  n_points float32 points are drawn uniformly in `bounds` = (lo, hi), default the
     union of the two meshes' bounding boxes (of the vertices their faces use), widened by the length `padding` on every side,
     from a torch.Generator on the meshes' device seeded with `seed` (as `mesh_metrics` seeds its samples): lo + u (hi - lo) in
@@ -1292,10 +1387,15 @@ def mesh_iou(mesh_a, mesh_b, n_points=100000, seed=0, bounds=None, padding=0.0, 
     return_points=True adds "points" (n,3) float32, "inside_a", "inside_b" (n,) bool, for tests.  On the GPU the two indices cost one
     host synchronisation each; nothing else is read back.  The same inputs and seed give the same bits."""
     from . import meshing
+    winding = meshing.check_rule(rule, "mesh_iou") == "winding"
     if isinstance(n_points, bool) or int(n_points) != n_points or not 1 <= int(n_points) <= 2 ** 31 - 1:
         raise ValueError("mesh_iou: n_points must be a positive integer, got %r" % (n_points,))
     n = int(n_points)
-    (va, fa), (vb, fb) = _contains_mesh(mesh_a, "mesh_iou"), _contains_mesh(mesh_b, "mesh_iou")
+    if winding:
+        meshing.check_accuracy(accuracy, "mesh_iou")
+        (va, fa), (vb, fb) = _sdf_mesh(mesh_a, "mesh_iou")[:2], _sdf_mesh(mesh_b, "mesh_iou")[:2]
+    else:
+        (va, fa), (vb, fb) = _contains_mesh(mesh_a, "mesh_iou"), _contains_mesh(mesh_b, "mesh_iou")
     if va.device != vb.device:
         raise ValueError("mesh_iou: the two meshes must live on one device")
     res = meshing.check_contains_args(va, fa, None, resolution, "mesh_iou")
@@ -1314,14 +1414,21 @@ def mesh_iou(mesh_a, mesh_b, n_points=100000, seed=0, bounds=None, padding=0.0, 
         gen = torch.Generator(device=dev).manual_seed(int(seed))
         u = torch.rand(n, 3, dtype=torch.float64, device=dev, generator=gen)
         pts = (lo + u * (hi - lo)).to(torch.float32).contiguous()
-        in_a, amb_a = mesh_contains((va, fa), pts, res, return_ambiguous=True)
-        in_b, amb_b = mesh_contains((vb, fb), pts, res, return_ambiguous=True)
+        if winding:
+            w_a, in_a, _, _ = _winding(va, fa, pts, accuracy, "mesh_iou")
+            w_b, in_b, _, _ = _winding(vb, fb, pts, accuracy, "mesh_iou")
+            amb_a, amb_b = torch.zeros_like(in_a), torch.zeros_like(in_b)
+        else:
+            in_a, amb_a = mesh_contains((va, fa), pts, res, return_ambiguous=True)
+            in_b, amb_b = mesh_contains((vb, fb), pts, res, return_ambiguous=True)
         n_a, n_b = in_a.sum(), in_b.sum()
         n_both, n_either = (in_a & in_b).sum(), (in_a | in_b).sum()
         volume = (hi - lo).prod()
         out = {"iou": n_both.double() / n_either.double(), "n_a": n_a, "n_b": n_b, "n_both": n_both, "n_either": n_either,
                "ambiguous_a": amb_a.sum(), "ambiguous_b": amb_b.sum(), "volume_a": n_a.double() / n * volume,
                "volume_b": n_b.double() / n * volume, "n_points": n}
+        if winding:
+            out["winding"] = (w_a, w_b)
     if return_points:
         out.update(points=pts, inside_a=in_a, inside_b=in_b)
     return out
@@ -1342,8 +1449,12 @@ def _sdf_mesh(mesh, what):
     return verts, faces, tris
 
 
-def mesh_sdf(mesh, points, trunc=float("inf"), resolution=512, index=None, contains_index=None):
-    """The signed distance of points (P,3) float32 to a mesh -- an (F,3,3) soup or a (verts, faces) pair as in `mesh_contains`, on the
+def mesh_sdf(mesh, points, trunc=float("inf"), resolution=512, index=None, contains_index=None, rule="parity", accuracy=3.0):
+    """rule="winding": the sign comes from `mesh_contains(rule="winding", accuracy=accuracy)` -- a signed distance to a mesh that is
+    not watertight; "ambiguous" is all False and the dict gains "winding" (P,) float64; contains_index: a hip.winding_index or None.
+    Default "parity":
+
+    The signed distance of points (P,3) float32 to a mesh -- an (F,3,3) soup or a (verts, faces) pair as in `mesh_contains`, on the
     points' device -> dict: "sdf" (P,) float32 = meshing.signed_distance(d2, inside, trunc), negative inside; "d2" (P,) float64, "face"
     (P,) int32 and "closest" (P,3) float64 of the closest triangle (+inf, -1, NaN for a point farther than `trunc`, outside the band);
     "inside", "ambiguous" (P,) bool, `mesh_contains` at `resolution`, for every point; "gradient" (P,3) float64, the unit vector
@@ -1351,6 +1462,9 @@ def mesh_sdf(mesh, points, trunc=float("inf"), resolution=512, index=None, conta
     hip.mesh_closest plus hip.mesh_contains (index: the hip.mesh_index of the mesh's soup, contains_index: its hip.contains_index,
     built earlier, or None), on the host the specification.  The sign is the parity rule's: meant for watertight meshes."""
     from . import meshing
+    winding = meshing.check_rule(rule, "mesh_sdf") == "winding"
+    if winding:
+        meshing.check_accuracy(accuracy, "mesh_sdf")
     t = meshing.check_trunc(trunc, "mesh_sdf")
     verts, faces, tris = _sdf_mesh(mesh, "mesh_sdf")
     res = meshing.check_contains_args(verts, faces, points, resolution, "mesh_sdf")
@@ -1368,22 +1482,36 @@ def mesh_sdf(mesh, points, trunc=float("inf"), resolution=512, index=None, conta
                 out = (d2 > t * t) | ((face < 0) & ~torch.isnan(d2))        # beyond the band; or no triangle gave a number
                 d2, face = torch.where(out, inf, d2), torch.where(out, torch.full_like(face, -1), face)
                 closest = torch.where(out[:, None], torch.full_like(closest, float("nan")), closest)
-            inside, ambiguous, _ = hip.mesh_contains(_contains_index(verts, faces, res, contains_index, "mesh_sdf"), pts,
-                                                     want_ambiguous=True)
+            if not winding:
+                inside, ambiguous, _ = hip.mesh_contains(_contains_index(verts, faces, res, contains_index, "mesh_sdf"), pts,
+                                                         want_ambiguous=True)
         else:
             if index is not None or contains_index is not None:
                 raise ValueError("mesh_sdf: an index belongs to a mesh on the GPU")
-            d2, face, closest, inside, ambiguous = meshing.mesh_sdf(verts, faces, points, t, res)
+            if winding:                                      # the closest triangle alone: the parity pass would be thrown away
+                d2, face, closest = meshing.soup_closest(tris, points, t)
+            else:
+                d2, face, closest, inside, ambiguous = meshing.mesh_sdf(verts, faces, points, t, res)
+        if winding:
+            w, inside, _, _ = _winding(verts, faces, points, accuracy, "mesh_sdf", contains_index)
+            ambiguous = torch.zeros_like(inside)
         dv = points.detach().double() - closest
         norm = torch.sqrt((dv[:, 0] * dv[:, 0] + dv[:, 1] * dv[:, 1]) + dv[:, 2] * dv[:, 2])
         gradient = torch.where(inside[:, None], -dv, dv) / norm[:, None]        # 0 / 0 on the surface, NaN outside the band
-    return {"sdf": meshing.signed_distance(d2, inside, t), "d2": d2, "face": face, "closest": closest, "inside": inside,
-            "ambiguous": ambiguous, "gradient": gradient}
+    out = {"sdf": meshing.signed_distance(d2, inside, t), "d2": d2, "face": face, "closest": closest, "inside": inside,
+           "ambiguous": ambiguous, "gradient": gradient}
+    if winding:
+        out["winding"] = w
+    return out
 
 
 def mesh_sdf_grid(mesh, dims=None, resolution=None, n_side=None, bounds=None, padding=0.0, trunc=None, nodes="centres",
-                  hash_resolution=512, index=None, want_face=False):
-    """The truncated signed distance field of a mesh (as in `mesh_sdf`) on a regular lattice -> dict: "sdf" (Nx,Ny,Nz) float32,
+                  hash_resolution=512, index=None, want_face=False, rule="parity", accuracy=3.0):
+    """rule="winding": "inside" is hip.mesh_winding_grid's occupancy (`voxelize(rule="winding")`), handed to hip.mesh_sdf_grid -- the
+    signed field of a mesh that is not watertight; "ambiguous" is 0 and the dict gains "winding" (Nx,Ny,Nz) float64; index: a
+    hip.winding_index or None.  Default "parity":
+
+    The truncated signed distance field of a mesh (as in `mesh_sdf`) on a regular lattice -> dict: "sdf" (Nx,Ny,Nz) float32,
     meshing.signed_distance; "d2" (Nx,Ny,Nz) float64, +inf outside the band; "face" (Nx,Ny,Nz) int32 with want_face=True, else None;
     "inside" (Nx,Ny,Nz) bool and "ambiguous" (0-dim int64), `voxelize`'s; "xs", "ys", "zs" the nodes' float32 coordinates; "bounds"
     (lo, hi); "band", the number of nodes within trunc (0-dim int64 on the device); "trunc" and "step" (floats); "box" and "info".
@@ -1395,6 +1523,9 @@ def mesh_sdf_grid(mesh, dims=None, resolution=None, n_side=None, bounds=None, pa
     host the specification on the meshgrid; d2, face and inside are equal bit for bit."""
     from . import meshing
     what = "mesh_sdf_grid"
+    winding = meshing.check_rule(rule, what) == "winding"
+    if winding:
+        meshing.check_accuracy(accuracy, what)
     verts, faces, tris = _sdf_mesh(mesh, what)
     res = meshing.check_contains_args(verts, faces, None, hash_resolution, what)
     dev = verts.device
@@ -1429,27 +1560,39 @@ def mesh_sdf_grid(mesh, dims=None, resolution=None, n_side=None, bounds=None, pa
     meshing.check_lattice_axes(*axes, what=what)     # a lattice finer than float32 resolves is refused here
     info = None
     with torch.no_grad():
+        if winding:
+            w, occ = _winding_lattice(verts, faces, axes, dims, accuracy, index, what)
+            amb = torch.zeros((), dtype=torch.int64, device=dev)
         if verts.is_cuda:
             from . import hip
-            occ, amb = hip.mesh_contains_grid(_contains_index(verts, faces, res, index, what), *axes)
+            if not winding:
+                occ, amb = hip.mesh_contains_grid(_contains_index(verts, faces, res, index, what), *axes)
             d2, face, sdf, info = hip.mesh_sdf_grid(tris, *axes, t, occupancy=occ, want_face=want_face, want_info=True)
             band = info[0].long()
         else:
             if index is not None:
                 raise ValueError("%s: an index belongs to a mesh on the GPU" % what)
-            grid = torch.stack(torch.meshgrid(*axes, indexing="ij"), dim=-1).reshape(-1, 3)
-            inside, ambiguous, _ = meshing.mesh_contains(verts, faces, grid, res)
-            occ, amb = inside.reshape(dims), ambiguous.sum()
+            if not winding:
+                grid = torch.stack(torch.meshgrid(*axes, indexing="ij"), dim=-1).reshape(-1, 3)
+                inside, ambiguous, _ = meshing.mesh_contains(verts, faces, grid, res)
+                occ, amb = inside.reshape(dims), ambiguous.sum()
             d2, face = meshing.mesh_sdf_grid(tris, *axes, t)
             sdf = meshing.signed_distance(d2, occ, t)
             band = ((d2 <= t * t) & (d2 < float("inf"))).sum()
             face = face if want_face else None
-    return {"sdf": sdf, "d2": d2, "face": face, "inside": occ, "xs": axes[0], "ys": axes[1], "zs": axes[2], "ambiguous": amb,
-            "bounds": (tuple(lo.tolist()), tuple(hi.tolist())), "band": band, "trunc": t, "step": step, "box": box, "info": info}
+    out = {"sdf": sdf, "d2": d2, "face": face, "inside": occ, "xs": axes[0], "ys": axes[1], "zs": axes[2], "ambiguous": amb,
+           "bounds": (tuple(lo.tolist()), tuple(hi.tolist())), "band": band, "trunc": t, "step": step, "box": box, "info": info}
+    if winding:
+        out["winding"] = w
+    return out
 
 
-def remesh(mesh, n_side=256, offset=0.0, trunc=None, padding=None, clean=None, smooth=None):
-    """A watertight, uniform remesh of a (watertight) mesh, or an offset surface of it: the level `offset` (metres; positive grows
+def remesh(mesh, n_side=256, offset=0.0, trunc=None, padding=None, clean=None, smooth=None, rule="parity", accuracy=3.0):
+    """rule="winding": the field's sign comes from the winding number (`mesh_sdf_grid(rule="winding", accuracy=accuracy)`), so the
+    input need NOT be watertight: remesh(open_mesh, rule="winding") is the REPAIR of a mesh with holes, open sheets or flipped
+    patches into a watertight one -- holes are closed where the winding number crosses 1/2.  Default "parity":
+
+    A watertight, uniform remesh of a (watertight) mesh, or an offset surface of it: the level `offset` (metres; positive grows
     the body) of its signed distance field on the cube lattice of `mesh_sdf_grid(nodes="corners", n_side=n_side)`, by
     hip.marching_cubes_indexed and hip.lattice_to_world -> (verts (V,3) float32 in the mesh's own coordinates, faces (F,3) int32).
     trunc defaults to |offset| plus three lattice steps; |offset| must stay below trunc by at least one step, so that both ends of
@@ -1458,6 +1601,8 @@ def remesh(mesh, n_side=256, offset=0.0, trunc=None, padding=None, clean=None, s
     (check_keep, check_smooth), applied in that order.  The two capacities are read back once.  GPU only."""
     from . import meshing
     what = "remesh"
+    meshing.check_rule(rule, what)
+    meshing.check_accuracy(accuracy, what)
     if isinstance(offset, bool) or not isinstance(offset, (int, float, np.integer, np.floating)) or not math.isfinite(float(offset)):
         raise ValueError("remesh: offset must be a finite length, got %r" % (offset,))
     offset = float(offset)
@@ -1486,7 +1631,7 @@ def remesh(mesh, n_side=256, offset=0.0, trunc=None, padding=None, clean=None, s
         raise ValueError("remesh runs on the HIP kernels: the mesh must live on the GPU")
     from . import hip
     with torch.no_grad():
-        field = mesh_sdf_grid((verts, faces), n_side=n, padding=padding, trunc=t, nodes="corners")
+        field = mesh_sdf_grid((verts, faces), n_side=n, padding=padding, trunc=t, nodes="corners", rule=rule, accuracy=accuracy)
         vert_cap, face_cap = meshing.MC_DEFAULT_VERT_CAP, meshing.MC_DEFAULT_CAP
         out_v, out_f, size = hip.marching_cubes_indexed(field["sdf"], offset, vert_cap, face_cap)
         V, F = size.tolist()

@@ -142,7 +142,9 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_mesh_rasterize", "arah_mesh_rasterize_debug", "arah_mesh_interpolate", "arah_mesh_raycast", "arah_mesh_raycast_debug",
            "arah_point_index_bytes", "arah_point_index_build", "arah_point_nearest", "arah_sample_scores_bytes", "arah_sample_scores",
            "arah_contains_index_bytes", "arah_contains_index_count", "arah_contains_index_fill", "arah_mesh_contains",
-           "arah_mesh_contains_grid", "arah_mesh_sdf_grid_bytes", "arah_mesh_sdf_grid"]
+           "arah_mesh_contains_grid", "arah_mesh_sdf_grid_bytes", "arah_mesh_sdf_grid",
+           "arah_winding_index_bytes", "arah_winding_index_count", "arah_winding_index_fill", "arah_mesh_winding",
+           "arah_mesh_winding_grid"]
 
 _lib = None
 
@@ -196,6 +198,8 @@ def load_library():
     lib.arah_contains_index_bytes.argtypes = [C.c_int32, C.c_int32]
     lib.arah_mesh_sdf_grid_bytes.restype = C.c_size_t
     lib.arah_mesh_sdf_grid_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64]
+    lib.arah_winding_index_bytes.restype = C.c_size_t
+    lib.arah_winding_index_bytes.argtypes = [C.c_int32, C.c_int32]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the symbol is missing
     _lib = lib
@@ -1802,6 +1806,152 @@ def mesh_contains_grid(index, xs, ys, zs):
         _check(lib.arah_mesh_contains_grid(*index._head(), _ptr(xs), C.c_int32(nx), _ptr(ys), C.c_int32(ny), _ptr(zs), C.c_int32(nz),
                                            _ptr(occ), _ptr(amb), _stream()), "arah_mesh_contains_grid")
     return occ.bool(), amb
+
+
+class WindingIndex:
+    """The cluster tree of `winding_index` on the device (csrc/meshwinding.hpp), the tables of meshing.winding_tree: buf (header and
+    build scratch), order (F,) int32, tris (F,3,3) float32 in list order, node_i (N,4) int32 = first, count, level, skip, node_f (N,8)
+    float64 = centroid, radius, area vector, area; orient (+1 / -1), volume, n_faces, n_verts, depth, n_nodes, valid (False: a used vertex is
+    not finite, every winding number is NaN), lo and side of the cube."""
+
+    def __init__(self, buf, order, tris, node_i, node_f, head, n_verts):
+        self.buf, self.order, self.tris, self.node_i, self.node_f = buf, order, tris, node_i, node_f
+        self.n_verts = int(n_verts)
+        self.n_faces, self.depth, self.n_nodes = int(head["n_faces"]), int(head["depth"]), int(head["n_nodes"])
+        self.orient, self.volume, self.valid = int(head["orient"]), float(head["volume"]), bool(head["valid"])
+        self.lo, self.side = tuple(head["lo"]), float(head["side"])
+
+    @property
+    def device(self):
+        return self.buf.device
+
+    def _head(self):
+        return (_ptr(self.buf), C.c_size_t(self.buf.numel()), C.c_int32(self.n_faces), C.c_int32(self.depth),
+                _ptr(self.tris) if self.n_faces else None, _ptr(self.node_i) if self.n_nodes else None,
+                _ptr(self.node_f) if self.n_nodes else None, C.c_int64(self.n_nodes))
+
+    def tree(self):
+        """The tables as a meshing.WindingTree on the host (a synchronisation): what meshing.mesh_winding walks."""
+        from . import meshing
+        ni, nf = self.node_i.cpu(), self.node_f.cpu()
+        return meshing.WindingTree(order=self.order.cpu(), tris=self.tris.cpu(), first=ni[:, 0].contiguous(), count=ni[:, 1].contiguous(),
+                                   level=ni[:, 2].contiguous(), skip=ni[:, 3].contiguous(), nvec=nf[:, 4:7].contiguous(),
+                                   centroid=nf[:, 0:3].contiguous(), radius=nf[:, 3].contiguous(), area=nf[:, 7].contiguous(),
+                                   lo=torch.tensor(self.lo, dtype=torch.float64), side=self.side, depth=self.depth,
+                                   n_faces=self.n_faces, orient=self.orient, volume=self.volume, valid=self.valid)
+
+
+def _winding_header(buf):
+    import struct
+    raw = bytes(buf[:72].cpu().numpy())
+    n_faces, depth, valid, status, orient = struct.unpack("5i", raw[48:68])
+    return {"lo": struct.unpack("3d", raw[0:24]), "side": struct.unpack("d", raw[24:32])[0], "volume": struct.unpack("d", raw[32:40])[0],
+            "n_nodes": struct.unpack("q", raw[40:48])[0], "n_faces": n_faces, "depth": depth, "valid": valid, "status": status,
+            "orient": orient}
+
+
+def winding_index(verts, faces, depth=None):
+    """The cluster tree of the fast winding number of the mesh verts (V,3) float32, faces (F,3) int32 on one GPU
+    (arah_winding_index_count / arah_winding_index_fill) -> WindingIndex for `mesh_winding` and `mesh_winding_grid`; the tables of
+    meshing.winding_tree, the float ones bit for bit.  depth: None for meshing.winding_depth(F), or 0 .. 7.  The number of nodes
+    depends on the data: it is read back once, which is the index's one host synchronisation.  A face id outside [0, V) raises, and
+    so does a mesh that puts more than meshing.WINDING_MAX_LEAF faces into one leaf cell at depth > 0: the ranking of a cell's faces is
+    quadratic in the cell, and the kernel leaves such a cell unranked."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    if (not torch.is_tensor(verts) or verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32
+            or not torch.is_tensor(faces) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32):
+        raise ValueError("winding_index: verts (V, 3) float32 and faces (F, 3) int32 required")
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    if F > meshing.WINDING_MAX_FACES:
+        raise ValueError("winding_index: at most 2^28 faces")
+    depth = meshing.check_winding_depth(depth, F, "winding_index")
+    dev = _same_device(verts, faces)
+    verts, faces = verts.detach().contiguous(), faces.contiguous()
+    if F and V < 1:
+        raise ValueError("winding_index: a face names a vertex outside [0, 0)")
+    with _on_device(dev):
+        buf = torch.empty(int(lib.arah_winding_index_bytes(F, depth)), dtype=torch.uint8, device=dev)
+        order = torch.empty(F, dtype=torch.int32, device=dev)
+        tris = torch.empty(F, 3, 3, dtype=torch.float32, device=dev)
+        _check(lib.arah_winding_index_count(_ptr(verts) if F else None, C.c_int32(V), _ptr(faces) if F else None, C.c_int32(F),
+                                            C.c_int32(depth), _ptr(buf), C.c_size_t(buf.numel()), _ptr(order) if F else None,
+                                            _ptr(tris) if F else None, _stream()), "arah_winding_index_count")
+        head = _winding_header(buf)
+        if head["status"] & 1:
+            raise ValueError("winding_index: a face names a vertex outside [0, %d)" % V)
+        if head["status"] & 2:
+            raise ValueError("winding_index: at depth %d one leaf cell holds more than %d of the %d faces (a small fragment far from "
+                             "the rest stretches the cube); give another depth, or depth=0 for the brute force"
+                             % (depth, meshing.WINDING_MAX_LEAF, F))
+        N = int(head["n_nodes"])
+        if N > 2 ** 31 - 1:
+            _check(lib.arah_winding_index_fill(_ptr(buf), C.c_size_t(buf.numel()), C.c_int32(F), C.c_int32(depth), None, None, None,
+                                               C.c_int64(N), _stream()), "arah_winding_index_fill (%d nodes)" % N)
+        node_i = torch.empty(N, 4, dtype=torch.int32, device=dev)
+        node_f = torch.empty(N, 8, dtype=torch.float64, device=dev)
+        _check(lib.arah_winding_index_fill(_ptr(buf), C.c_size_t(buf.numel()), C.c_int32(F), C.c_int32(depth), _ptr(tris) if F else None,
+                                           _ptr(node_i) if N else None, _ptr(node_f) if N else None, C.c_int64(N), _stream()),
+               "arah_winding_index_fill")
+    return WindingIndex(buf, order, tris, node_i, node_f, head, V)
+
+
+def _winding_outputs(shape, dev, want_counts):
+    w = torch.empty(shape, dtype=torch.float64, device=dev)
+    inside = torch.empty(shape, dtype=torch.uint8, device=dev)
+    n_exact = torch.empty(shape, dtype=torch.int32, device=dev) if want_counts else None
+    n_far = torch.empty(shape, dtype=torch.int32, device=dev) if want_counts else None
+    return w, inside, n_exact, n_far
+
+
+def mesh_winding(index, points, accuracy=3.0, want_counts=False):
+    """The generalized winding number of points (P,3) float32 against the indexed mesh (arah_mesh_winding) -> w (P,) float64, inside
+    (P,) bool = meshing.winding_inside(w, index.orient), n_exact and n_far (P,) int32 or None.  The walk of meshing.mesh_winding:
+    the same near / far decisions, bit-equal dipole terms; accuracy = inf is the exact sum.  No host synchronisation."""
+    from . import meshing
+    lib = load_library()
+    if not isinstance(index, WindingIndex):
+        raise ValueError("index must come from winding_index")
+    acc = meshing.check_accuracy(accuracy, "mesh_winding")
+    if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise ValueError("mesh_winding: points must be (P, 3) float32")
+    dev = _same_device(index.buf, points)
+    pts = points.detach().contiguous()
+    P = int(pts.shape[0])
+    if P > 2 ** 31 - 1:
+        raise ValueError("mesh_winding: at most 2^31 - 1 points")
+    w, inside, n_exact, n_far = _winding_outputs((P,), dev, want_counts)
+    with _on_device(dev):
+        _check(lib.arah_mesh_winding(*index._head(), _ptr(pts) if P else None, C.c_int32(P), C.c_double(acc), _ptr(w) if P else None,
+                                     _ptr(inside) if P else None, _ptr(n_exact) if P and want_counts else None,
+                                     _ptr(n_far) if P and want_counts else None, _stream()), "arah_mesh_winding")
+    return w, inside.bool(), n_exact, n_far
+
+
+def mesh_winding_grid(index, xs, ys, zs, accuracy=3.0, want_counts=False):
+    """The lattice xs (Nx,) x ys (Ny,) x zs (Nz,) float32 against the indexed mesh (arah_mesh_winding_grid) -> w (Nx,Ny,Nz) float64,
+    occupancy (Nx,Ny,Nz) bool, n_exact, n_far (Nx,Ny,Nz) int32 or None; equal to `mesh_winding` on torch.meshgrid(xs, ys, zs,
+    indexing="ij") bit for bit.  The lattice point is made in the kernel.  No host synchronisation."""
+    from . import meshing
+    lib = load_library()
+    if not isinstance(index, WindingIndex):
+        raise ValueError("index must come from winding_index")
+    acc = meshing.check_accuracy(accuracy, "mesh_winding_grid")
+    for name, x in (("xs", xs), ("ys", ys), ("zs", zs)):
+        if not torch.is_tensor(x) or x.dim() != 1 or x.dtype != torch.float32 or x.shape[0] < 1:
+            raise ValueError("mesh_winding_grid: %s must be a non-empty 1-D float32 tensor" % name)
+    dev = _same_device(index.buf, xs, ys, zs)
+    xs, ys, zs = xs.detach().contiguous(), ys.detach().contiguous(), zs.detach().contiguous()
+    nx, ny, nz = int(xs.shape[0]), int(ys.shape[0]), int(zs.shape[0])
+    if nx * ny * nz > 2 ** 31 - 1:
+        raise ValueError("mesh_winding_grid: at most 2^31 - 1 lattice points")
+    w, occ, n_exact, n_far = _winding_outputs((nx, ny, nz), dev, want_counts)
+    with _on_device(dev):
+        _check(lib.arah_mesh_winding_grid(*index._head(), _ptr(xs), C.c_int32(nx), _ptr(ys), C.c_int32(ny), _ptr(zs), C.c_int32(nz),
+                                          C.c_double(acc), _ptr(w), _ptr(occ), _ptr(n_exact), _ptr(n_far), _stream()),
+               "arah_mesh_winding_grid")
+    return w, occ.bool(), n_exact, n_far
 
 
 SDF_GRID_INFO = ("band", "status", "tests", "lane", "wave", "group", "huge")

@@ -1152,6 +1152,309 @@ def mesh_sdf_grid(tris, xs, ys, zs, trunc, chunk_pairs=1 << 21):
     return d2.reshape(dims), face.reshape(dims)
 
 
+# ---- generalized winding numbers (DESIGN.md "Winding numbers on the device") ------------------------------------------------
+WINDING_MAX_DEPTH = 7                   # three times 7 bits: the Morton key of a leaf fits 21 bits
+WINDING_MAX_FACES = 1 << 28
+WINDING_MAX_LEAF = 1 << 15              # faces of one leaf cell the device accepts at depth > 0 (its ranking is quadratic in a cell)
+WINDING_FOUR_PI = 4.0 * math.pi
+WINDING_RULES = ("parity", "winding")
+
+
+def _sqrt_rn(x):
+    """The correctly rounded square root of a float64 tensor on the host, as the device's: torch.sqrt on the CPU is a vectorised
+    approximation that misses the last bit of about one number in a hundred."""
+    return torch.from_numpy(np.sqrt(x.detach().contiguous().numpy()))
+
+
+def check_rule(rule, what="mesh_contains"):
+    if not isinstance(rule, str) or rule not in WINDING_RULES:
+        raise ValueError("%s: rule must be 'parity' or 'winding', got %r" % (what, rule))
+    return rule
+
+
+def check_accuracy(accuracy, what="mesh_winding"):
+    """The opening parameter of the traversal: a number >= 1, +inf for the exact sum -> float."""
+    if isinstance(accuracy, bool) or not isinstance(accuracy, (int, float, np.integer, np.floating)) or math.isnan(float(accuracy)) \
+            or float(accuracy) < 1:
+        raise ValueError("%s: accuracy must be a number >= 1 (+inf: the exact sum), got %r" % (what, accuracy))
+    return float(accuracy)
+
+
+def winding_depth(n_faces):
+    """THE rule of depth=None, shared with the device (wn_auto_depth): the smallest depth with 8 * 4^depth >= n_faces, at most
+    WINDING_MAX_DEPTH -- a surface meets about 4^depth of the 8^depth leaf cells, so a leaf holds about eight triangles.  Chosen from
+    the depth sweep of tools/mesh_winding_bench.py (deeper trees answer faster up to the cap; the build grows with the 8^depth
+    cells); the constant 8 itself and the cap are not measured against alternatives."""
+    d = 0
+    while d < WINDING_MAX_DEPTH and (8 << (2 * d)) < int(n_faces):
+        d += 1
+    return d
+
+
+def check_winding_depth(depth, n_faces, what="winding_tree"):
+    if depth is None:
+        return winding_depth(n_faces)
+    if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or not 0 <= int(depth) <= WINDING_MAX_DEPTH:
+        raise ValueError("%s: depth must be None or an integer in [0, %d], got %r" % (what, WINDING_MAX_DEPTH, depth))
+    return int(depth)
+
+
+def solid_angle_terms(p, a, b, c):
+    """The signed solid angle under which the triangle (a, b, c) is seen from p (Van Oosterom & Strackee 1983): float64 (..., 3)
+    tensors that broadcast.  With a, b, c the corners minus p: num = a . (b x c), the cross product first and the dot product summed
+    from the left; den = (((|a| |b|) |c| + (a.b) |c|) + (b.c) |a|) + (c.a) |b|; the term is 2 atan2(num, den), and 0 where
+    num == 0 -- a point in the plane of the face, on the face or at a corner sees it under no angle.  Every operation is rounded on
+    its own; only atan2 is a library function.  Positive when the corners run counter-clockwise seen from the far side of p."""
+    a, b, c = a - p, b - p, c - p
+    crx = b[..., 1] * c[..., 2] - b[..., 2] * c[..., 1]
+    cry = b[..., 2] * c[..., 0] - b[..., 0] * c[..., 2]
+    crz = b[..., 0] * c[..., 1] - b[..., 1] * c[..., 0]
+    num = (a[..., 0] * crx + a[..., 1] * cry) + a[..., 2] * crz
+    la, lb, lc = _sqrt_rn(_dot3(a, a)), _sqrt_rn(_dot3(b, b)), _sqrt_rn(_dot3(c, c))
+    den = (((la * lb) * lc + _dot3(a, b) * lc) + _dot3(b, c) * la) + _dot3(c, a) * lb
+    term = 2.0 * torch.atan2(num, den)
+    return torch.where(num == 0, torch.zeros_like(term), term)
+
+
+def winding_orient(verts, faces):
+    """+1 or -1: the sign of the mesh's signed volume, sum det(v0, v1, v2) / 6 in float64; +1 where that is 0 or NaN.  det = v0 .
+    (v1 x v2) as in `solid_angle_terms`.  The order of the sum (k_wn_box): 256 partial sums, number t taking the faces t, t + 256,
+    ... in ascending order, then p[t] += p[t + s] for s = 128, 64, ..., 1.  -> (orient int, volume float)."""
+    T = verts.detach().to(torch.float64)[faces.detach().long()].cpu()
+    F = int(T.shape[0])
+    if F == 0:
+        return 1, 0.0
+    v0, v1, v2 = T[:, 0], T[:, 1], T[:, 2]
+    crx = v1[:, 1] * v2[:, 2] - v1[:, 2] * v2[:, 1]
+    cry = v1[:, 2] * v2[:, 0] - v1[:, 0] * v2[:, 2]
+    crz = v1[:, 0] * v2[:, 1] - v1[:, 1] * v2[:, 0]
+    det = ((v0[:, 0] * crx + v0[:, 1] * cry) + v0[:, 2] * crz).numpy()
+    rows = (F + 255) // 256
+    padded = np.zeros(rows * 256, dtype=np.float64)
+    padded[:F] = det
+    p = np.add.accumulate(padded.reshape(rows, 256), axis=0)[-1].copy()      # strictly sequential down every column
+    s = 128
+    while s >= 1:
+        p[:s] = p[:s] + p[s:2 * s]
+        s //= 2
+    volume = float(p[0]) / 6.0
+    return (-1 if volume < 0 else 1), volume
+
+
+def _morton3(ix, iy, iz, depth):
+    """Bit b of ix, iy, iz -> bits 3b + 2, 3b + 1, 3b of the key."""
+    key = np.zeros_like(ix)
+    for b in range(depth):
+        key |= (((ix >> b) & 1) << (3 * b + 2)) | (((iy >> b) & 1) << (3 * b + 1)) | (((iz >> b) & 1) << (3 * b))
+    return key
+
+
+def _unmorton3(key, depth):
+    out = [np.zeros_like(key), np.zeros_like(key), np.zeros_like(key)]
+    for b in range(depth):
+        for a in range(3):
+            out[a] |= ((key >> (3 * b + 2 - a)) & 1) << b
+    return out
+
+
+class WindingTree:
+    """The cluster tree of `winding_tree`, on the host.  order (F,) int32: the triangles' ids in list order; tris (F,3,3) float32:
+    their corners in list order; first, count, level, skip (N,) int32; nvec (N,3), centroid (N,3), radius (N,), area (N,) float64;
+    lo (3,) float64 and side: the cube; depth, n_faces, orient (+1 / -1), volume, valid (False: a used vertex is not finite, every
+    winding number is NaN)."""
+
+    FIELDS = ("order", "tris", "first", "count", "level", "skip", "nvec", "centroid", "radius", "area")
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def n_nodes(self):
+        return int(self.first.shape[0])
+
+
+def winding_tree(verts, faces, depth=None):
+    """The cluster tree of the fast winding number (Barill et al. 2018) of the mesh verts (V,3) floating point, faces (F,3) integer
+    -> WindingTree.  The specification of arah_winding_index_count / _fill (csrc/meshwinding.hpp): the integer tables are equal and
+    the float tables equal bit for bit.  float64 on the vertices as given (the device takes them as float32), every operation rounded
+    on its own.
+
+    The cube: lo = the minimum over the vertices some face uses, side = the largest of the three extents.  Triangle (a, b, c) has
+    the centroid g = ((a + b) + c) / 3 and lies in the leaf cell i = (int) clamp((g - lo) * (2^depth / side), 0, 2^depth - 1) per
+    axis (a NaN counts as 0), whose key interleaves the bits of (ix, iy, iz), x highest.  The list orders the triangles by (key, face
+    id).  Every non-empty cell of every level 0 .. depth -- the key shifted right by 3 (depth - level) -- is a node; the nodes are
+    numbered in depth-first preorder (by first, then level), skip is the number of the next node outside the subtree (N after the
+    last).  depth=None is `winding_depth`; depth=0 makes the root the one leaf, the list the face order.
+
+    Per triangle n = ((b - a) x (c - a)) / 2 -- 0.5 times each component of the cross product --, area = |n| summed from the left,
+    and area * g.  A leaf sums n, area and area * g over its members in list order, starting from 0; an inner node sums its
+    children's sums in child order, starting from 0.  centroid = sum(area g) / sum(area) where the summed area is > 0, else the
+    cell's centre lo + (i + 0.5) * (side / 2^level).  radius = sqrt of the largest |corner - centroid|^2 (summed from the left) over
+    the corners of the member triangles.  A face id outside [0, V) raises.  The device refuses a mesh that puts more than
+    WINDING_MAX_LEAF faces into one leaf cell at depth > 0 (hip.winding_index raises); this specification has no such limit."""
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or not verts.dtype.is_floating_point:
+        raise ValueError("winding_tree: verts must be a floating-point (V, 3) tensor")
+    if (not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype.is_floating_point
+            or faces.dtype == torch.bool):
+        raise ValueError("winding_tree: faces must be an integer (F, 3) tensor")
+    F, V = int(faces.shape[0]), int(verts.shape[0])
+    if F > WINDING_MAX_FACES:
+        raise ValueError("winding_tree: at most 2^28 faces")
+    depth = check_winding_depth(depth, F)
+    fc = faces.detach().long().cpu()
+    if F and not bool(((fc >= 0) & (fc < V)).all()):
+        raise ValueError("winding_tree: a face names a vertex outside [0, %d)" % V)
+    f64, i32 = torch.float64, torch.int32
+    v32 = verts.detach().cpu()
+    T = v32.to(f64)[fc] if F else torch.zeros((0, 3, 3), dtype=f64)
+    orient, volume = winding_orient(v32, fc)
+    empty_i = torch.zeros(0, dtype=i32)
+    if F == 0:
+        return WindingTree(order=empty_i, tris=torch.zeros((0, 3, 3), dtype=torch.float32), first=empty_i, count=empty_i.clone(),
+                           level=empty_i.clone(), skip=empty_i.clone(), nvec=torch.zeros((0, 3), dtype=f64),
+                           centroid=torch.zeros((0, 3), dtype=f64), radius=torch.zeros(0, dtype=f64), area=torch.zeros(0, dtype=f64),
+                           lo=torch.zeros(3, dtype=f64), side=0.0, depth=depth, n_faces=0, orient=1, volume=0.0, valid=True)
+    valid = bool(torch.isfinite(T).all())
+    flat = T.reshape(-1, 3)
+    fin = torch.where(torch.isfinite(flat), flat, torch.full_like(flat, float("nan")))
+    lo = torch.from_numpy(np.fmin.reduce(fin.numpy(), axis=0))
+    hi = torch.from_numpy(np.fmax.reduce(fin.numpy(), axis=0))
+    side = (hi - lo).max()
+    a, b, c = T[:, 0], T[:, 1], T[:, 2]
+    g = ((a + b) + c) / 3.0
+    n_leaf = 1 << depth
+    inv = torch.full((), float(n_leaf), dtype=f64) / side
+    q = torch.nan_to_num((g - lo) * inv, nan=0.0, posinf=float(n_leaf - 1), neginf=0.0).clamp(0.0, float(n_leaf - 1))
+    cell = q.trunc().long().numpy()
+    key = _morton3(cell[:, 0], cell[:, 1], cell[:, 2], depth)
+    order = np.argsort((key << 32) | np.arange(F, dtype=np.int64), kind="stable")
+    sk = key[order]
+    # the level at which a triangle of the list starts a node: 0 for the first, depth + 1 where the key repeats
+    x = sk[1:] ^ sk[:-1]
+    hb = np.where(x > 0, np.floor(np.log2(np.maximum(x, 1))).astype(np.int64), -1)
+    h = np.concatenate([[0], np.where(x > 0, depth - hb // 3, depth + 1)]).astype(np.int64)
+    prefix = np.concatenate([[0], np.cumsum(depth + 1 - h)]).astype(np.int64)
+    N = int(prefix[-1])
+    first, count = np.zeros(N, dtype=np.int64), np.zeros(N, dtype=np.int64)
+    level, skip = np.zeros(N, dtype=np.int64), np.zeros(N, dtype=np.int64)
+    cells = np.zeros((N, 3), dtype=np.int64)
+    for l in range(depth + 1):
+        s = 3 * (depth - l)
+        i = np.flatnonzero(h <= l)
+        node = prefix[i] + l - h[i]
+        end = np.searchsorted(sk, ((sk[i] >> s) + 1) << s, side="left")
+        first[node], count[node], level[node], skip[node] = i, end - i, l, prefix[end]
+        cx, cy, cz = _unmorton3(sk[i] >> s, l)
+        cells[node] = np.stack([cx, cy, cz], axis=1)
+    # per triangle, in list order
+    to = torch.from_numpy(order)
+    a, b, c, g = a[to], b[to], c[to], g[to]
+    e1, e2 = b - a, c - a
+    nv = torch.stack([0.5 * (e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]), 0.5 * (e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]),
+                      0.5 * (e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0])], dim=1)
+    ar = _sqrt_rn(_dot3(nv, nv))
+    val = torch.cat([nv, ar[:, None], ar[:, None] * g], dim=1)                   # (F, 7)
+    sums = torch.zeros((N, 7), dtype=f64)
+    leaves = np.flatnonzero(level == depth)
+    lf, lc = first[leaves], count[leaves]
+    for j in range(int(lc.max())):                                              # list order inside every leaf
+        m = lc > j
+        rows = torch.from_numpy(leaves[m])
+        sums[rows] = sums[rows] + val[torch.from_numpy(lf[m] + j)]
+    for l in range(depth - 1, -1, -1):                                          # child order inside every inner node
+        nodes = np.flatnonzero(level == l)
+        child = nodes + 1
+        for _ in range(8):
+            m = child < skip[nodes]
+            if not m.any():
+                break
+            rows, ch = torch.from_numpy(nodes[m]), torch.from_numpy(child[m])
+            sums[rows] = sums[rows] + sums[ch]
+            child = np.where(m, skip[np.minimum(child, N - 1)], child)
+    lvl = torch.from_numpy(level)
+    width = torch.full((N,), 1.0, dtype=f64) * side / torch.pow(torch.full((N,), 2.0, dtype=f64), lvl.to(f64))
+    centre = lo[None, :] + (torch.from_numpy(cells).to(f64) + 0.5) * width[:, None]
+    area = sums[:, 3]
+    centroid = torch.where((area > 0)[:, None], sums[:, 4:7] / area[:, None], centre)
+    r2 = torch.zeros(N, dtype=f64)
+    corners = torch.stack([a, b, c], dim=1)                                      # (F,3,3) in list order
+    for l in range(depth + 1):
+        nodes = np.flatnonzero(level == l)
+        owner = torch.from_numpy(np.repeat(nodes, count[nodes]))                  # the node of every triangle of the list at level l
+        d = corners - centroid[owner][:, None, :]
+        d2 = _dot3(d, d).amax(1)
+        r2.scatter_reduce_(0, owner, d2, reduce="amax", include_self=True)
+    return WindingTree(order=to.to(i32), tris=v32.to(torch.float32)[fc][to].contiguous(), first=torch.from_numpy(first).to(i32),
+                       count=torch.from_numpy(count).to(i32), level=lvl.to(i32), skip=torch.from_numpy(skip).to(i32),
+                       nvec=sums[:, 0:3].contiguous(), centroid=centroid.contiguous(), radius=_sqrt_rn(r2), area=area.contiguous(),
+                       lo=lo, side=float(side), depth=depth, n_faces=F, orient=orient, volume=volume, valid=valid)
+
+
+def mesh_winding(tree, points, accuracy=3.0, chunk=256):
+    """The generalized winding number of points (P,3) float32 or float64 on the host against a WindingTree -> w (P,) float64,
+    n_exact (P,) int32 (triangles summed exactly), n_far (P,) int32 (clusters taken as dipoles).  The specification of
+    arah_mesh_winding: the same near / far decisions, bit-equal dipole terms, exact terms that differ by atan2's last bits.
+
+    One accumulator per point, in solid angle, starting from 0.  The walk starts at node 0 and ends at node N.  At a node with
+    centroid c, radius r and summed area vector n, d = c - p and d2 = |d|^2 summed from the left: if d2 > accuracy^2 * (r * r) the
+    node adds (d . n) / (d2 * sqrt(d2)) and the walk goes to skip; else a leaf adds `solid_angle_terms` of its triangles one by one
+    in list order and the walk goes to skip; else the walk goes to the next node.  w = accumulator / (4 pi).  accuracy = +inf takes
+    no node as far (inf * 0 is NaN, and no number exceeds a NaN): the exact sum.  A tree that is not valid answers NaN, 0, 0; a NaN
+    in a point takes every node as near and ends as NaN.  `chunk` bounds the temporaries; the result does not depend on it."""
+    acc = check_accuracy(accuracy, "mesh_winding")
+    if not isinstance(tree, WindingTree):
+        raise ValueError("mesh_winding: tree must come from winding_tree")
+    if (not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3
+            or points.dtype not in (torch.float32, torch.float64)):
+        raise ValueError("mesh_winding: points must be (P, 3) float32 or float64")
+    f64 = torch.float64
+    X = points.detach().cpu().to(f64)
+    P, N = int(X.shape[0]), tree.n_nodes
+    total = torch.zeros(P, dtype=f64)
+    n_exact, n_far = torch.zeros(P, dtype=torch.int32), torch.zeros(P, dtype=torch.int32)
+    if not tree.valid:
+        return torch.full((P,), float("nan"), dtype=f64), n_exact, n_far
+    acc2 = acc * acc
+    T = tree.tris.to(f64)
+    first, count, level, skip = (t.tolist() for t in (tree.first, tree.count, tree.level, tree.skip))
+    at = torch.zeros(P, dtype=torch.int64)
+    for n in range(N):
+        here = torch.nonzero(at == n)[:, 0]
+        if here.numel() == 0:
+            continue
+        p = X[here]
+        d = tree.centroid[n][None, :] - p
+        d2 = _dot3(d, d)
+        r = tree.radius[n]
+        far = d2 > acc2 * (r * r)
+        fi = here[far]
+        if fi.numel():
+            df, d2f = d[far], d2[far]
+            total[fi] = total[fi] + _dot3(df, tree.nvec[n][None, :].expand_as(df)) / (d2f * _sqrt_rn(d2f))
+            n_far[fi] += 1
+        if level[n] == tree.depth:
+            ni = here[~far]
+            if ni.numel():
+                pn = X[ni][:, None, :]
+                run = total[ni]
+                for t0 in range(first[n], first[n] + count[n], chunk):
+                    tt = T[t0:min(t0 + chunk, first[n] + count[n])]
+                    terms = solid_angle_terms(pn, tt[None, :, 0], tt[None, :, 1], tt[None, :, 2])
+                    for j in range(int(terms.shape[1])):
+                        run = run + terms[:, j]
+                total[ni] = run
+                n_exact[ni] += count[n]
+            at[here] = skip[n]
+        else:
+            at[here] = torch.where(far, torch.full_like(here, skip[n]), torch.full_like(here, n + 1))
+    return total / WINDING_FOUR_PI, n_exact, n_far
+
+
+def winding_inside(w, orient):
+    """THE rule of the winding number's inside test: orient * w >= 0.5; a NaN is outside."""
+    return (float(orient) * w) >= 0.5
+
+
 def face_normals(tri):
     """Unit right-hand normals of a triangle soup (F,3,3) (pytorch3d Meshes.faces_normals_packed)."""
     n = torch.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0], dim=1)

@@ -1161,7 +1161,7 @@ class MetaAvatarRender(nn.Module):
         return res
 
     def geometry_metrics(self, inputs, gt, n_side=256, method="lattice", n_samples=100000, seed=0, clean=None, thresholds=None,
-                         iou=None, sdf=None, sdf_band=0.05):
+                         iou=None, sdf=None, sdf_band=0.05, inside="parity"):
         """Geometry scores of the posed body of frame `inputs` against a ground truth `gt` in world metres on the inputs' GPU -- a
         mesh ((F,3,3) triangles or a (verts, faces) pair) or a scan (a geometry.PointCloud or a (P,3) tensor of points):
         `posed_mesh(inputs, n_side, method)` as the prediction, then
@@ -1177,10 +1177,13 @@ class MetaAvatarRender(nn.Module):
         geometry.mesh_sdf(gt, points, trunc=sdf_band) is compared with query_posed(inputs, points)["sdf"] clamped to the same band
         at the points where the posed query converged: "sdf_l1" the mean absolute difference (metres), "sdf_sign" the share with
         equal sign (negative inside), "sdf_n" the points used and "sdf_ambiguous" those among them whose ground-truth sign the
-        parity rule could not decide.  Eval only."""
-        from . import geometry
+        parity rule could not decide.  inside="winding" (default "parity": nothing changes): the inside tests of iou= and sdf= are
+        geometry's rule="winding" -- generalized winding numbers, for ground truth that is NOT watertight (scans with holes, open
+        sheets, flipped patches); the ambiguous counts are then 0.  Eval only."""
+        from . import geometry, meshing
         if self.training:
             raise ValueError("geometry_metrics is eval-only: call model.eval() first")
+        meshing.check_rule(inside, "geometry_metrics")
         if sdf is not None:
             if isinstance(sdf, bool) or int(sdf) != sdf or not 1 <= int(sdf) <= 2 ** 31 - 1:
                 raise ValueError("geometry_metrics: sdf must be a positive number of points, got %r" % (sdf,))
@@ -1203,14 +1206,14 @@ class MetaAvatarRender(nn.Module):
         if iou is not None:
             if geometry._is_cloud(gt):
                 raise ValueError("geometry_metrics: iou needs a ground-truth mesh, not a scan")
-            vol = geometry.mesh_iou(pred, gt, n_points=iou, seed=seed)
+            vol = geometry.mesh_iou(pred, gt, n_points=iou, seed=seed, rule=inside)
             res["iou"] = vol["iou"]
             res.update(("iou_" + k, vol[k]) for k in geometry.IOU_KEYS[1:] + ("n_points",))
         if sdf is not None:
-            res.update(self._sdf_scores(inputs, gt, int(sdf), float(sdf_band), seed))
+            res.update(self._sdf_scores(inputs, gt, int(sdf), float(sdf_band), seed, inside))
         return res
 
-    def _sdf_scores(self, inputs, gt, n, band, seed):
+    def _sdf_scores(self, inputs, gt, n, band, seed, inside="parity"):
         """The sdf= scores of `geometry_metrics`: -> dict of sdf_l1, sdf_sign (float64), sdf_n, sdf_ambiguous (int64), 0-dim tensors."""
         from . import data, geometry, meshing
         dev = inputs["rots"].device
@@ -1225,7 +1228,7 @@ class MetaAvatarRender(nn.Module):
             d = d / d.norm(dim=1, keepdim=True).clamp_min(1e-300)
             u = (2.0 * torch.rand(n, 1, dtype=torch.float64, device=dev, generator=gen) - 1.0) * band
             pts = (base.double() + u * d).to(torch.float32).contiguous()
-            truth = geometry.mesh_sdf((verts, faces), pts, trunc=band)
+            truth = geometry.mesh_sdf((verts, faces), pts, trunc=band, rule=inside)
             q = self.query_posed(inputs, pts)
             band32 = float(meshing.check_trunc(band))
             ours = q["sdf"].double().clamp(-band32, band32)

@@ -29,6 +29,9 @@ volumetric intersection over union of the posed mesh and the ground-truth mesh f
 gets no ``iou`` -- and its mean over those frames to the JSON line.  ``--geometry-sdf N`` (with ``--geometry-sdf-band METRES``,
 default 0.05) adds ``sdf_l1`` and ``sdf_sign`` in the same way: the posed SDF against the ground-truth mesh's signed distance at N
 points in a band around it (MetaAvatarRender.geometry_metrics, sdf=; DESIGN.md "Signed distance to a mesh on the device").
+``--geometry-inside winding`` (default ``parity``) answers the inside tests of ``--geometry-iou`` and ``--geometry-sdf`` with
+generalized winding numbers instead of crossing parities (geometry's ``rule="winding"``; DESIGN.md "Winding numbers on the device"):
+for ground truth that is not watertight.  The JSON line then gains ``"geometry_inside": "winding"``.
 Without the options the output is unchanged."""
 import argparse
 import importlib
@@ -68,6 +71,9 @@ def build_parser():
                    help="Points in a band around ground-truth meshes at which the posed SDF is compared with the mesh's signed "
                         "distance: adds sdf_l1 and sdf_sign to the geometry scores.")
     p.add_argument("--geometry-sdf-band", type=float, default=0.05, metavar="METRES", help="Half width of that band.")
+    p.add_argument("--geometry-inside", type=str, default="parity", choices=("parity", "winding"),
+                   help="The inside test of --geometry-iou and --geometry-sdf: crossing parities (watertight ground truth) or "
+                        "generalized winding numbers (ground truth with holes, open sheets, flipped patches).")
     p.add_argument("--default-config", type=str, default="configs/default.yaml")
     p.add_argument("--body-models", type=str, default="body_models/misc", help="Directory of the SMPL model files.")
     return p
@@ -108,7 +114,8 @@ def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0
     mesh or scan in dir are scored by model.geometry_metrics in the same in-flight step, the scalars are read when the epoch ends
     and the result gains their means, "n_geometry" and the per-frame values; an optional "thresholds" (tuple of distances) adds
     precision@T / recall@T / fscore@T.  normal_consistency of a frame scored against a scan without normals is null; a mean runs over
-    the frames that have the score.  An optional "iou" (a number of points) adds iou for the frames whose ground truth is a mesh."""
+    the frames that have the score.  An optional "iou" (a number of points) adds iou for the frames whose ground truth is a mesh; an
+    optional "inside" ("parity" or "winding") is the inside test of iou and sdf."""
     from . import geometry as geo, renderer
     lm = lm.to(device).eval()
     mine = list(range(rank, len(dataset), world))
@@ -122,6 +129,7 @@ def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0
     n_sdf = geometry.get("sdf") if geometry is not None else None
     if n_sdf:
         geo_keys = geo_keys + ("sdf_l1", "sdf_sign")
+    inside = geometry.get("inside", "parity") if geometry is not None else "parity"
     mesh_only = tuple(q for q, key in enumerate(geo_keys) if key in ("iou", "sdf_l1", "sdf_sign"))   # scores a scan cannot have
 
     def step(item):
@@ -133,6 +141,7 @@ def validate(lm, dataset, device, rank=0, world=1, lpips_fn=None, data_range=2.0
         scores = lm.model.geometry_metrics(lm.compose_inputs(item, eval=True), gt, n_side=geometry["n_side"],
                                            n_samples=geometry["n_samples"], seed=geometry["seed"], thresholds=thresholds or None,
                                            iou=n_iou if n_iou and not geo._is_cloud(gt) else None,
+                                           **({"inside": inside} if inside != "parity" else {}),
                                            **({"sdf": n_sdf, "sdf_band": geometry.get("sdf_band", 0.05)}
                                               if n_sdf and not geo._is_cloud(gt) else {}))
         out["geometry"] = torch.stack([scores[k] for k in geo.METRIC_KEYS])
@@ -242,12 +251,16 @@ def main(argv=None, body=None, faces=None, log=print):
             if args.geometry_sdf < 1 or not 0 < args.geometry_sdf_band < float("inf"):
                 raise ValueError("--geometry-sdf takes a positive number of points and --geometry-sdf-band a finite length > 0")
             geometry["sdf"], geometry["sdf_band"] = args.geometry_sdf, args.geometry_sdf_band
+        if args.geometry_inside != "parity":
+            geometry["inside"] = args.geometry_inside
     elif args.geometry_thresholds is not None:
         raise ValueError("--geometry-thresholds needs --geometry DIR")
     elif args.geometry_iou is not None:
         raise ValueError("--geometry-iou needs --geometry DIR")
     elif args.geometry_sdf is not None:
         raise ValueError("--geometry-sdf needs --geometry DIR")
+    elif args.geometry_inside != "parity":
+        raise ValueError("--geometry-inside needs --geometry DIR")
     res, n_mine, seconds = validate(lm, val_dataset, device, rank, world, lpips_fn, args.data_range, geometry)
     if world > 1:
         dist.barrier()
@@ -257,6 +270,8 @@ def main(argv=None, body=None, faces=None, log=print):
     frames = res.pop("frames")
     res.update(seconds_per_frame=seconds / max(1, n_mine), world=world, data_range=args.data_range,
                mode="test" if args.novel_pose else "val")
+    if geometry is not None and geometry.get("inside", "parity") != "parity":
+        res["geometry_inside"] = geometry["inside"]
     with open(os.path.join(out_dir, "validation.json"), "w") as f:
         json.dump(dict(res, frames=frames), f, indent=1)
     log(json.dumps(res))

@@ -899,6 +899,46 @@ int arah_mesh_sdf_grid(const float* tris, int32_t n_faces, const float* xs, int3
                        int32_t nz, float trunc, const uint8_t* occupancy, double* d2, int32_t* face, float* sdf, int32_t* info,
                        void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- generalized winding numbers (csrc/meshwinding.hpp; no reference counterpart) ------------------------------------------------ */
+/* The generalized winding number of points against a triangle mesh, evaluated hierarchically (Barill et al. 2018, first order):
+ * exact solid angles (Van Oosterom & Strackee) for the triangles of near leaves, one dipole for a far cluster.  The rule is
+ * meshing.winding_tree / meshing.mesh_winding; float64 throughout.  Every integer table equals the rule's, every float table, every
+ * near / far decision and every dipole term equal it bit for bit; only atan2 may differ, by its last bits.  verts [V,3] float, faces
+ * [F,3] int32, 0 <= F <= 2^28, depth in [0, 7] or -1 for the rule of meshing.winding_depth; otherwise ARAH_E_BADARG without a launch
+ * and a size of 0.
+ *
+ * The index is built in two calls because its number of nodes is data-dependent:
+ *   arah_winding_index_count   the cube, the leaf keys, the list ordered by (key, face id) -> order [F] int32 and tris [F,3,3] float32
+ *                              (the corners in list order), and the preorder numbering into `index` (arah_winding_index_bytes(F,
+ *                              depth) device bytes, 256-byte aligned).  The first 256 bytes are the header: 5 doubles lo[3], side,
+ *                              volume | int64 n_nodes | int32 n_faces, depth, valid (every used vertex finite), status (bit 0: a face
+ *                              id outside [0, V); bit 1: at depth > 0 a leaf cell holds more than 2^15 faces -- ranking a cell's
+ *                              faces is quadratic in the cell, so that cell is left in the order of arrival, valid is 0 and every
+ *                              winding number NaN), orient (+1 / -1, the sign of the signed volume; +1 for 0).
+ *   the caller reads n_nodes from the header (the index's one host synchronisation) and allocates node_i [n_nodes][4] int32
+ *   (first, count, level, skip) and node_f [n_nodes][8] float64 (centroid xyz, radius, area vector xyz, area);
+ *   arah_winding_index_fill    writes the two tables.  ARAH_E_OVERFLOW for n_nodes > INT32_MAX; n_nodes = 0: nothing to do.
+ *
+ * arah_mesh_winding: pts [P,3] float32 -> w [P] f64, and on request inside [P] u8 (orient * w >= 0.5; a NaN is outside), n_exact [P]
+ * int32 (triangles summed exactly) and n_far [P] int32 (dipoles), each or NULL.  accuracy >= 1, +inf for the exact sum, else
+ * ARAH_E_BADARG.  One lane per point, each point's sum in the rule's order; no atomics.  A mesh with a vertex that is not finite:
+ * w = NaN.  F = 0: w = 0.  P = 0 is legal.  No host synchronisation.
+ *
+ * arah_mesh_winding_grid: the lattice xs[nx] x ys[ny] x zs[nz] (float32), all outputs [nx][ny][nz] in C order, equal to
+ * arah_mesh_winding on the meshgrid(indexing="ij") bit for bit.  ARAH_E_OVERFLOW when nx ny nz does not fit an int32. */
+size_t arah_winding_index_bytes(int32_t n_faces, int32_t depth);
+int arah_winding_index_count(const float* verts, int32_t n_verts, const int32_t* faces, int32_t n_faces, int32_t depth, void* index,
+                             size_t index_bytes, int32_t* order, float* tris, void* stream);
+int arah_winding_index_fill(const void* index, size_t index_bytes, int32_t n_faces, int32_t depth, const float* tris, int32_t* node_i,
+                            double* node_f, int64_t n_nodes, void* stream);
+int arah_mesh_winding(const void* index, size_t index_bytes, int32_t n_faces, int32_t depth, const float* tris, const int32_t* node_i,
+                      const double* node_f, int64_t n_nodes, const float* pts, int32_t n_pts, double accuracy, double* w,
+                      uint8_t* inside, int32_t* n_exact, int32_t* n_far, void* stream);
+int arah_mesh_winding_grid(const void* index, size_t index_bytes, int32_t n_faces, int32_t depth, const float* tris,
+                           const int32_t* node_i, const double* node_f, int64_t n_nodes, const float* xs, int32_t nx, const float* ys,
+                           int32_t ny, const float* zs, int32_t nz, double accuracy, double* w, uint8_t* inside, int32_t* n_exact,
+                           int32_t* n_far, void* stream);
+
 /* name of the dominant kernel, for profilers */
 const char* arah_dominant_kernel(void);
 #ifdef __cplusplus
