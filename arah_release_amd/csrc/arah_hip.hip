@@ -1952,6 +1952,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_canon_solve(FrameDev fr, const 
 #include "meshcc.hpp"
 #include "meshsimp.hpp"
 #include "meshadj.hpp"
+#include "meshorient.hpp"
 #include "meshraster.hpp"
 #include "canon_wave.hpp"
 
@@ -4347,6 +4348,294 @@ int arah_mesh_smooth(const float* verts, int64_t n_verts, const int32_t* nbr_sta
         hipLaunchKernelGGL(k_ma_smooth, dim3(ma_grid(V)), dim3(kMaThreads), 0, s, src, V, (const int*)nbr_start, (const int*)nbr,
                            (const unsigned char*)vert_flags, (double)factors[i & 1], (int)(pin != 0), dst);
         src = dst;
+    }
+    return check_launch();
+}
+
+// ---- orientation, boundary loops and hole filling of indexed meshes (csrc/meshorient.hpp) ---------------------------------------
+struct MoLayout {
+    size_t parent, froot, dense, ones, fstate, blk_count, blk_base, bytes;
+};
+
+static size_t mo_blocks(int64_t n) { return (size_t)((n + kMoChunk - 1) / kMoChunk); }
+static int mo_grid(int64_t n) { return (int)min((int64_t)kMoMaxGrid, max((int64_t)1, (n + kMoThreads - 1) / kMoThreads)); }
+
+static bool mo_quant_ok(const float origin[3], double scale) {
+    return origin && std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]) && scale > 0.0 && std::isfinite(scale);
+}
+
+static MoLayout mo_layout(int64_t n_faces) {
+    MoLayout L{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off = align_up(off + bytes, 256);
+        return at;
+    };
+    L.parent = take(2 * (size_t)n_faces * sizeof(int));
+    L.froot = take((size_t)n_faces * sizeof(int));
+    L.dense = take((size_t)n_faces * sizeof(int));
+    L.ones = take((size_t)n_faces * sizeof(int));
+    L.fstate = take((size_t)n_faces);
+    L.blk_count = take(cc_blocks(n_faces) * sizeof(int));
+    L.blk_base = take(cc_blocks(n_faces) * sizeof(int));
+    L.bytes = off > 256 ? off : (size_t)256;
+    return L;
+}
+
+size_t arah_mesh_orient_scratch_bytes(int64_t n_verts, int64_t n_faces) {
+    if (!ma_sizes_ok(n_verts, n_faces)) return 0;
+    return mo_layout(n_faces).bytes;
+}
+
+int arah_mesh_orient(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int32_t* vf_start, const int32_t* vf,
+                     const int32_t* nbr_start, const int32_t* nbr, const int32_t* nbr_out, const int32_t* nbr_in, int32_t policy,
+                     const float origin[3], double scale, uint8_t* flip, int32_t* face_comp, int32_t* faces_out, int32_t* comp_faces,
+                     int32_t* comp_flags, int64_t* comp_vol_hi, int64_t* comp_vol_lo, int32_t* counts, void* scratch,
+                     size_t scratch_bytes, void* stream) {
+    if (!ma_sizes_ok(n_verts, n_faces) || !vf_start || !nbr_start || !counts || !scratch) return ARAH_E_BADARG;
+    if (policy < kMoSeed || policy > kMoPositive) return ARAH_E_BADARG;
+    const bool by_volume = policy == kMoNegative || policy == kMoPositive;
+    if (by_volume && (!mo_quant_ok(origin, scale) || (n_verts > 0 && !verts))) return ARAH_E_BADARG;
+    if (n_faces > 0 && (!faces || !vf || !nbr || !nbr_out || !nbr_in || !flip || !face_comp || !faces_out || !comp_faces || !comp_flags ||
+                        !comp_vol_hi || !comp_vol_lo))
+        return ARAH_E_BADARG;
+    const MoLayout L = mo_layout(n_faces);
+    if (scratch_bytes < L.bytes) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int V = (int)n_verts, F = (int)n_faces, nb = (int)cc_blocks(n_faces);
+    char* base = reinterpret_cast<char*>(scratch);
+    int* parent = reinterpret_cast<int*>(base + L.parent);
+    int* froot = reinterpret_cast<int*>(base + L.froot);
+    int* dense = reinterpret_cast<int*>(base + L.dense);
+    int* ones = reinterpret_cast<int*>(base + L.ones);
+    unsigned char* fstate = reinterpret_cast<unsigned char*>(base + L.fstate);
+    int* blk_count = reinterpret_cast<int*>(base + L.blk_count);
+    int* blk_base = reinterpret_cast<int*>(base + L.blk_base);
+    const int* none = nullptr;
+    // no face: the init alone, which clears the counts
+    hipLaunchKernelGGL(k_mo_init, dim3(mo_grid(2 * (int64_t)F)), dim3(kMoThreads), 0, s, parent, F, (int*)comp_faces, (int*)comp_flags, ones,
+                       (long long*)comp_vol_hi, (long long*)comp_vol_lo, (int*)counts);
+    if (F == 0) return check_launch();
+    if (V > 0)   // without a vertex no face is valid: nothing indexes the empty CSRs
+        hipLaunchKernelGGL(k_mo_pairs, dim3(mo_grid(3 * (int64_t)F)), dim3(kMoThreads), 0, s, (const int*)faces, F, V, (const int*)vf_start,
+                           (const int*)vf, (const int*)nbr_start, (const int*)nbr, (const int*)nbr_out, (const int*)nbr_in, parent);
+    hipLaunchKernelGGL(k_mo_flatten, dim3(mo_grid(F)), dim3(kMoThreads), 0, s, (const int*)faces, F, V, (const int*)parent, froot, fstate);
+    hipLaunchKernelGGL((k_cc_compact<kCcRoots, false>), dim3(nb), dim3(kCcThreads), 0, s, none, (const int*)froot, none, F, F, blk_count,
+                       none, (int*)nullptr, (int*)nullptr);
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)blk_count, nb, blk_base, (int*)counts + 1);
+    hipLaunchKernelGGL((k_cc_compact<kCcRoots, true>), dim3(nb), dim3(kCcThreads), 0, s, none, (const int*)froot, none, F, F, (int*)nullptr,
+                       (const int*)blk_base, dense, (int*)nullptr);
+    hipLaunchKernelGGL(k_mo_label, dim3(mo_grid(F)), dim3(kMoThreads), 0, s, (const int*)froot, (const unsigned char*)fstate,
+                       (const int*)dense, F, (int*)face_comp, (int*)comp_faces, ones, (int*)comp_flags, (int*)counts);
+    if (by_volume && V > 0) {
+        MoQuant g;
+        for (int a = 0; a < 3; ++a) g.origin[a] = origin[a];
+        g.scale = scale;
+        hipLaunchKernelGGL(k_mo_volume, dim3(mo_grid(F)), dim3(kMoThreads), 0, s, verts, (const int*)faces, F, V, g, (const int*)face_comp,
+                           (const unsigned char*)fstate, (long long*)comp_vol_hi, (long long*)comp_vol_lo);
+    }
+    hipLaunchKernelGGL(k_mo_decide, dim3(mo_grid(F)), dim3(kMoThreads), 0, s, (const int*)comp_faces, (const int*)ones,
+                       (const long long*)comp_vol_hi, (const long long*)comp_vol_lo, (int)policy, (int*)comp_flags, (int*)counts);
+    hipLaunchKernelGGL(k_mo_apply, dim3(mo_grid(F)), dim3(kMoThreads), 0, s, (const int*)faces, F, (const int*)face_comp,
+                       (const unsigned char*)fstate, (const int*)comp_flags, (unsigned char*)flip, (int*)faces_out, (int*)counts);
+    return check_launch();
+}
+
+struct MlLayout {
+    size_t parent, root, dense, vout, vin, bad, eblk_count, eblk_base, vblk_count, vblk_base, bytes;
+};
+
+static MlLayout ml_layout(int64_t n_verts, int64_t n_faces) {
+    MlLayout L{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off = align_up(off + bytes, 256);
+        return at;
+    };
+    const size_t v = (size_t)n_verts * sizeof(int);
+    L.parent = take(v);
+    L.root = take(v);
+    L.dense = take(v);
+    L.vout = take(v);
+    L.vin = take(v);
+    L.bad = take(v);
+    L.eblk_count = take(mo_blocks(3 * n_faces) * sizeof(int));
+    L.eblk_base = take(mo_blocks(3 * n_faces) * sizeof(int));
+    L.vblk_count = take(cc_blocks(n_verts) * sizeof(int));
+    L.vblk_base = take(cc_blocks(n_verts) * sizeof(int));
+    L.bytes = off > 256 ? off : (size_t)256;
+    return L;
+}
+
+size_t arah_mesh_boundary_loops_scratch_bytes(int64_t n_verts, int64_t n_faces) {
+    if (!ma_sizes_ok(n_verts, n_faces)) return 0;
+    return ml_layout(n_verts, n_faces).bytes;
+}
+
+int arah_mesh_boundary_loops(const int32_t* faces, int64_t n_faces, int64_t n_verts, const int32_t* nbr_start, const int32_t* nbr,
+                             const int32_t* nbr_out, const int32_t* nbr_in, int32_t* edges, int32_t* edge_face, int32_t* edge_loop,
+                             int32_t* loop_edges, uint8_t* loop_simple, int32_t* loop_vert, int32_t* counts, void* scratch,
+                             size_t scratch_bytes, void* stream) {
+    if (!ma_sizes_ok(n_verts, n_faces) || !nbr_start || !counts || !scratch) return ARAH_E_BADARG;
+    if ((n_faces > 0 && (!faces || !nbr || !nbr_out || !nbr_in || !edges || !edge_face || !edge_loop)) ||
+        (n_verts > 0 && (!loop_edges || !loop_simple || !loop_vert)))
+        return ARAH_E_BADARG;
+    const MlLayout L = ml_layout(n_verts, n_faces);
+    if (scratch_bytes < L.bytes) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int V = (int)n_verts, F = (int)n_faces, E = 3 * F, nbe = (int)mo_blocks(3 * n_faces), nbv = (int)cc_blocks(n_verts);
+    char* base = reinterpret_cast<char*>(scratch);
+    int* parent = reinterpret_cast<int*>(base + L.parent);
+    int* root = reinterpret_cast<int*>(base + L.root);
+    int* dense = reinterpret_cast<int*>(base + L.dense);
+    int* vout = reinterpret_cast<int*>(base + L.vout);
+    int* vin = reinterpret_cast<int*>(base + L.vin);
+    int* bad = reinterpret_cast<int*>(base + L.bad);
+    int* eblk_count = reinterpret_cast<int*>(base + L.eblk_count);
+    int* eblk_base = reinterpret_cast<int*>(base + L.eblk_base);
+    int* vblk_count = reinterpret_cast<int*>(base + L.vblk_count);
+    int* vblk_base = reinterpret_cast<int*>(base + L.vblk_base);
+    const int* none = nullptr;
+    hipLaunchKernelGGL(k_mo_loop_init, dim3(mo_grid(V)), dim3(kMoThreads), 0, s, parent, vout, vin, bad, V, (int*)loop_edges,
+                       (unsigned char*)loop_simple, (int*)loop_vert, (int*)counts);
+    if (F > 0) {   // the three per-edge arrays are all guard rows until the fill pass writes the first counts[0] of them
+        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)edges, (const int*)counts, E, 2);
+        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)edge_face, (const int*)counts, E, 1);
+        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)edge_loop, (const int*)counts, E, 1);
+    }
+    if (F == 0 || V == 0) return check_launch();
+    MoCompact p{};
+    p.faces = (const int*)faces;
+    p.n_faces = F;
+    p.n_verts = V;
+    p.nbr_start = (const int*)nbr_start;
+    p.nbr = (const int*)nbr;
+    p.nbr_out = (const int*)nbr_out;
+    p.nbr_in = (const int*)nbr_in;
+    p.edges = (int*)edges;
+    p.edge_face = (int*)edge_face;
+    p.vout = vout;
+    p.vin = vin;
+    p.parent = parent;
+    hipLaunchKernelGGL((k_mo_compact<kMoBoundary, false>), dim3(nbe), dim3(kMoThreads), 0, s, p, E, none, eblk_count, none);
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)eblk_count, nbe, eblk_base, (int*)counts);
+    hipLaunchKernelGGL((k_mo_compact<kMoBoundary, true>), dim3(nbe), dim3(kMoThreads), 0, s, p, E, none, (int*)nullptr, (const int*)eblk_base);
+    hipLaunchKernelGGL(k_mo_loop_flatten, dim3(mo_grid(V)), dim3(kMoThreads), 0, s, (const int*)parent, (const int*)vout, (const int*)vin, V,
+                       root);
+    hipLaunchKernelGGL((k_cc_compact<kCcRoots, false>), dim3(nbv), dim3(kCcThreads), 0, s, none, (const int*)root, none, V, V, vblk_count,
+                       none, (int*)nullptr, (int*)nullptr);
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)vblk_count, nbv, vblk_base, (int*)counts + 1);
+    hipLaunchKernelGGL((k_cc_compact<kCcRoots, true>), dim3(nbv), dim3(kCcThreads), 0, s, none, (const int*)root, none, V, V, (int*)nullptr,
+                       (const int*)vblk_base, dense, (int*)nullptr);
+    hipLaunchKernelGGL(k_mo_loop_verts, dim3(mo_grid(V)), dim3(kMoThreads), 0, s, (const int*)root, (const int*)dense, (const int*)vout,
+                       (const int*)vin, V, (int*)loop_vert, bad);
+    hipLaunchKernelGGL(k_mo_loop_edges, dim3(mo_grid(E)), dim3(kMoThreads), 0, s, (const int*)edges, E, (const int*)root, (const int*)dense,
+                       (const int*)counts, (int*)edge_loop, (int*)loop_edges);
+    hipLaunchKernelGGL(k_mo_loop_finish, dim3(mo_grid(V)), dim3(kMoThreads), 0, s, (const int*)bad, V, (unsigned char*)loop_simple,
+                       (int*)counts);
+    return check_launch();
+}
+
+struct MfLayout {
+    size_t sums, nonfinite, lrank, lblk_count, lblk_base, eblk_count, eblk_base, bytes;
+};
+
+static MfLayout mf_layout(int64_t n_verts, int64_t n_faces) {
+    MfLayout L{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off = align_up(off + bytes, 256);
+        return at;
+    };
+    L.sums = take(3 * (size_t)n_verts * sizeof(long long));
+    L.nonfinite = take((size_t)n_verts * sizeof(int));
+    L.lrank = take((size_t)n_verts * sizeof(int));
+    L.lblk_count = take(mo_blocks(n_verts) * sizeof(int));
+    L.lblk_base = take(mo_blocks(n_verts) * sizeof(int));
+    L.eblk_count = take(mo_blocks(3 * n_faces) * sizeof(int));
+    L.eblk_base = take(mo_blocks(3 * n_faces) * sizeof(int));
+    L.bytes = off > 256 ? off : (size_t)256;
+    return L;
+}
+
+size_t arah_mesh_fill_holes_scratch_bytes(int64_t n_verts, int64_t n_faces) {
+    if (!ma_sizes_ok(n_verts, n_faces)) return 0;
+    return mf_layout(n_verts, n_faces).bytes;
+}
+
+int arah_mesh_fill_holes(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int32_t* edges,
+                         const int32_t* edge_loop, const int32_t* loop_edges, const uint8_t* loop_simple, const int32_t* loop_vert,
+                         const int32_t* loop_counts, int32_t max_edges, const float origin[3], double fix_scale, float* verts_out,
+                         int32_t* vert_src, int32_t* faces_out, int32_t* face_loop, int32_t* counts, void* scratch, size_t scratch_bytes,
+                         void* stream) {
+    if (!ma_sizes_ok(n_verts, n_faces) || !loop_counts || !counts || !scratch) return ARAH_E_BADARG;
+    if (max_edges < 0 || max_edges > (1 << 26) || !mo_quant_ok(origin, fix_scale)) return ARAH_E_BADARG;
+    if ((n_verts > 0 && (!verts || !verts_out || !vert_src || !loop_edges || !loop_simple || !loop_vert)) ||
+        (n_faces > 0 && (!faces || !faces_out || !face_loop || !edges || !edge_loop)))
+        return ARAH_E_BADARG;
+    const MfLayout L = mf_layout(n_verts, n_faces);
+    if (scratch_bytes < L.bytes) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int V = (int)n_verts, F = (int)n_faces, E = 3 * F, Lcap = V / 3;
+    const int nbl = (int)mo_blocks(n_verts), nbe = (int)mo_blocks(3 * n_faces);
+    char* base = reinterpret_cast<char*>(scratch);
+    long long* sums = reinterpret_cast<long long*>(base + L.sums);
+    int* nonfinite = reinterpret_cast<int*>(base + L.nonfinite);
+    int* lrank = reinterpret_cast<int*>(base + L.lrank);
+    int* lblk_count = reinterpret_cast<int*>(base + L.lblk_count);
+    int* lblk_base = reinterpret_cast<int*>(base + L.lblk_base);
+    int* eblk_count = reinterpret_cast<int*>(base + L.eblk_count);
+    int* eblk_base = reinterpret_cast<int*>(base + L.eblk_base);
+    hipLaunchKernelGGL(k_mo_fill_init, dim3(mo_grid(V)), dim3(kMoThreads), 0, s, sums, nonfinite, V, (const int*)loop_counts, (int*)counts);
+    if (V > 0 || F > 0)
+        hipLaunchKernelGGL(k_mo_fill_copy, dim3(mo_grid(max(V, F))), dim3(kMoThreads), 0, s, verts, V, (const int*)faces, F, verts_out,
+                           (int*)vert_src, (int*)faces_out, (int*)face_loop);
+    if (V > 0 && F > 0) {
+        MoQuant g;
+        for (int a = 0; a < 3; ++a) g.origin[a] = origin[a];
+        g.scale = fix_scale;
+        hipLaunchKernelGGL(k_mo_fill_accum, dim3(mo_grid(E)), dim3(kMoThreads), 0, s, verts, V, (const int*)edges, (const int*)edge_loop, E,
+                           (const int*)loop_counts, (const int*)loop_edges, (const unsigned char*)loop_simple, (int)max_edges, g, sums,
+                           nonfinite);
+        MoCompact p{};
+        p.n_faces = F;
+        p.n_verts = V;
+        p.loop_edges = (const int*)loop_edges;
+        p.loop_simple = (const unsigned char*)loop_simple;
+        p.loop_vert = (const int*)loop_vert;
+        p.nonfinite = nonfinite;
+        p.sums = sums;
+        p.max_edges = (int)max_edges;
+        p.g = g;
+        p.lrank = lrank;
+        p.verts_out = verts_out;
+        p.vert_src = (int*)vert_src;
+        p.edges_in = (const int*)edges;
+        p.edge_loop = (const int*)edge_loop;
+        p.n_loops_cap = V;
+        p.faces_out = (int*)faces_out;
+        p.face_loop = (int*)face_loop;
+        const int* n_loops = (const int*)loop_counts + 1;
+        const int* n_edges = (const int*)loop_counts;
+        // lrank is written for the loops below *n_loops only, and edge_loop of this call's edges names only those
+        hipLaunchKernelGGL((k_mo_compact<kMoLoops, false>), dim3(nbl), dim3(kMoThreads), 0, s, p, V, n_loops, lblk_count, (const int*)nullptr);
+        hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)lblk_count, nbl, lblk_base, (int*)counts + 3);
+        hipLaunchKernelGGL((k_mo_compact<kMoLoops, true>), dim3(nbl), dim3(kMoThreads), 0, s, p, V, n_loops, (int*)nullptr, (const int*)lblk_base);
+        hipLaunchKernelGGL((k_mo_compact<kMoFilled, false>), dim3(nbe), dim3(kMoThreads), 0, s, p, E, n_edges, eblk_count, (const int*)nullptr);
+        hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)eblk_count, nbe, eblk_base, (int*)counts + 4);
+        hipLaunchKernelGGL((k_mo_compact<kMoFilled, true>), dim3(nbe), dim3(kMoThreads), 0, s, p, E, n_edges, (int*)nullptr, (const int*)eblk_base);
+    }
+    // the rows behind the filled loops and the added faces, up to the arrays' lengths V + V / 3 and 4 F
+    if (Lcap > 0) {
+        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)verts_out + 3 * (size_t)V, (const int*)counts + 3, Lcap, 3);
+        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)vert_src + (size_t)V, (const int*)counts + 3, Lcap, 1);
+    }
+    if (F > 0) {
+        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)faces_out + 3 * (size_t)F, (const int*)counts + 4, E, 3);
+        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)face_loop + (size_t)F, (const int*)counts + 4, E, 1);
     }
     return check_launch();
 }

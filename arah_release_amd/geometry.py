@@ -692,6 +692,117 @@ def smooth_mesh(verts, faces, iterations=10, lamb=0.5, mu=-0.53, method="taubin"
                                               adjacency=adjacency)
 
 
+# ---- orientation, boundary loops, hole filling -----------------------------------------------------------------------------------
+def _repair_attributes(attributes, n_verts, dev, reserved, what):
+    attributes = dict(attributes or {})
+    for name, t in attributes.items():
+        if name in reserved:
+            raise ValueError("%s: an attribute cannot be called %r" % (what, name))
+        if not isinstance(t, torch.Tensor) or t.dim() < 1 or t.shape[0] != n_verts or t.device != dev:
+            raise ValueError("%s: attribute %r must be a tensor with %d rows on %s" % (what, name, n_verts, dev))
+    return attributes
+
+
+def orient_mesh(verts, faces, policy="majority", adjacency=None):
+    """Orient the faces of an indexed mesh consistently (hip.mesh_orient on the GPU, meshing.mesh_orient on the host, equal bit for
+    bit; the rules are stated in meshing.mesh_orient).  Faces that share an edge with exactly one other face are made to traverse
+    it in opposite directions, component by component; edges with one face or with three or more carry no constraint, so a
+    non-manifold edge separates components.  A non-orientable component (a Moebius strip) is left as it is and counted.
+
+        policy = "seed"        the lowest face of every component keeps its orientation
+                 "majority"    the orientation held by more faces of the component wins, ties go to "seed"
+                 "negative" /  the component's signed volume gets that sign -- the project's own meshes are negative
+                 "positive"    (winding_orient gives -1); a zero volume falls back to "majority"
+
+    verts (V,3), or just the vertex count under "seed" and "majority"; adjacency: a `mesh_adjacency` of the same mesh built
+    earlier, or None.  -> dict of faces (F,3) in the dtype of the input: row order and vertices never change, a flipped row (a, b,
+    c) becomes (a, c, b); flip (F,) uint8; face_component (F,) int32, -1 for a skipped face; n_components, n_nonorientable,
+    n_flipped; component_faces (C,) int32; component_nonorientable (C,) bool.  One host synchronisation (the counts), and one more
+    for the vertices' bounds under the two volume policies."""
+    from . import meshing
+    meshing.check_orient_policy(policy, "orient_mesh")
+    n_verts, faces = _mesh_args(verts, faces, "orient_mesh")
+    by_volume = policy in ("negative", "positive")
+    if isinstance(verts, torch.Tensor) and verts.dim() > 0:
+        if not verts.dtype.is_floating_point:
+            raise ValueError("orient_mesh: verts must be a floating-point (V, 3) tensor")
+        if verts.device != faces.device:
+            raise ValueError("orient_mesh: verts live on %s, faces on %s" % (verts.device, faces.device))
+    elif by_volume:
+        raise ValueError("orient_mesh: policy %r needs the vertices, not their number" % (policy,))
+    with torch.no_grad():
+        v = verts.detach().to(torch.float32).contiguous() if by_volume else n_verts
+        flip, face_comp, _, comp_faces, comp_flags, _, _, counts = _cc_backend(faces).mesh_orient(
+            v, faces, policy=policy, adjacency=None if adjacency is None else tuple(adjacency))
+        c = counts.tolist()                                                     # the host synchronisation
+        out = torch.where(flip.bool()[:, None], faces[:, [0, 2, 1]], faces)
+    return {"faces": out, "flip": flip, "face_component": face_comp, "n_components": c[1], "n_nonorientable": c[2],
+            "n_flipped": c[5], "component_faces": comp_faces[:c[1]], "component_nonorientable": (comp_flags[:c[1]] & 1).bool()}
+
+
+def boundary_loops(verts_or_n_verts, faces, adjacency=None):
+    """The boundary of an indexed mesh (hip.mesh_boundary_loops on the GPU, meshing.mesh_boundary_loops on the host): the directed
+    edges a->b of valid faces whose undirected edge carries exactly one face, in ascending (face, corner) order, and their loops:
+    the connected components through shared vertices, numbered in ascending order of their smallest vertex.  A loop is simple when
+    every vertex on it has one outgoing and one incoming boundary edge: one closed polygon.  -> dict of edges (B,2) int32,
+    edge_face (B,) int32, edge_loop (B,) int32, n_edges, n_loops, n_simple, loop_edges (L,) int32, loop_simple (L,) bool, loop_vert
+    (L,) int32 (the loop's smallest vertex).  One host synchronisation (the counts)."""
+    n_verts, faces = _mesh_args(verts_or_n_verts, faces, "boundary_loops")
+    with torch.no_grad():
+        edges, edge_face, edge_loop, loop_edges, loop_simple, loop_vert, counts = _cc_backend(faces).mesh_boundary_loops(
+            faces, n_verts, adjacency=None if adjacency is None else tuple(adjacency))
+        B, L, n_simple = counts.tolist()                                        # the host synchronisation
+    return {"edges": edges[:B], "edge_face": edge_face[:B], "edge_loop": edge_loop[:B], "n_edges": B, "n_loops": L,
+            "n_simple": n_simple, "loop_edges": loop_edges[:L], "loop_simple": loop_simple[:L].bool(), "loop_vert": loop_vert[:L]}
+
+
+def fill_holes(verts, faces, max_edges=64, attributes=None, adjacency=None):
+    """Close the small holes of an indexed mesh (hip.mesh_fill_holes on the GPU, meshing.mesh_fill_holes on the host, equal bit for
+    bit).  A boundary loop is filled when it is simple and has between 3 and max_edges edges: one new vertex at the exact mean of
+    the loop's vertices, appended after the existing ones, and one face (b, a, new) per boundary edge a->b, appended after the
+    existing ones, consistent with the face that owns the edge.  Nothing existing is renumbered.  Larger loops, loops that are not
+    simple (two holes touching at a vertex, a hole in a misoriented neighbourhood: run `orient_mesh` first) and loops with a
+    non-finite vertex are left alone and counted.  -> dict of verts (V',3) float32, faces (F',3) in the dtype of `faces`,
+    n_verts, n_tris, vert_src (V',) int64 (an old vertex: itself; a new one: the smallest vertex of its loop), filled = dict of
+    loops / faces / skipped_loops, and every tensor of the dict `attributes` (first dimension V) gathered by vert_src -- never
+    averaged.  Host synchronisations: the vertices' bounds and the sizes of the result."""
+    from . import meshing
+    meshing.check_max_edges(max_edges, "fill_holes")
+    n_verts, faces = _mesh_args(verts, faces, "fill_holes")
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or not verts.dtype.is_floating_point:
+        raise ValueError("fill_holes: verts must be a floating-point (V, 3) tensor")
+    if verts.device != faces.device:
+        raise ValueError("fill_holes: verts live on %s, faces on %s" % (verts.device, faces.device))
+    attributes = _repair_attributes(attributes, n_verts, verts.device, ("verts", "faces", "n_verts", "n_tris", "vert_src", "filled"),
+                                    "fill_holes")
+    with torch.no_grad():
+        v32 = verts.detach().to(torch.float32).contiguous()
+        verts_out, vert_src, faces_out, _, counts = _cc_backend(faces).mesh_fill_holes(
+            v32, faces, max_edges=max_edges, adjacency=None if adjacency is None else tuple(adjacency))
+        _, L, _, Lf, Bf = counts.tolist()                                       # the host synchronisation
+        F = int(faces.shape[0])
+        vert_src = vert_src[:n_verts + Lf].long()
+        res = {"verts": verts_out[:n_verts + Lf], "faces": torch.cat([faces, faces_out[F:F + Bf].to(faces.dtype)]),
+               "n_verts": n_verts + Lf, "n_tris": F + Bf, "vert_src": vert_src,
+               "filled": {"loops": Lf, "faces": Bf, "skipped_loops": L - Lf}}
+        for name, t in attributes.items():
+            res[name] = t.index_select(0, vert_src)
+    return res
+
+
+def repair_mesh(verts, faces, policy="majority", max_edges=64, attributes=None):
+    """`orient_mesh`, then `fill_holes` of the oriented mesh: -> the dict of `fill_holes` plus topology (`mesh_topology` of the
+    result) and oriented (the report of `orient_mesh` without its faces).  The adjacency is built once for the orientation and
+    once for the filling: the flips change the directions it counts."""
+    if attributes and ("topology" in attributes or "oriented" in attributes):
+        raise ValueError("repair_mesh: an attribute cannot be called 'topology' or 'oriented'")
+    oriented = orient_mesh(verts, faces, policy=policy)
+    res = fill_holes(verts, oriented.pop("faces"), max_edges=max_edges, attributes=attributes)
+    res["topology"] = mesh_topology(res["verts"], res["faces"])
+    res["oriented"] = oriented
+    return res
+
+
 def check_smooth(smooth):
     """Validate a `smooth` option of the model's mesh entries and return the keywords of `smooth_mesh` it stands for: None
     (nothing), a number of iterations (an integer >= 0), or a dict of iterations / lamb / mu / method / boundary.  ValueError for

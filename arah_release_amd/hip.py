@@ -139,6 +139,8 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_mesh_components_scratch_bytes", "arah_mesh_components", "arah_mesh_select_scratch_bytes", "arah_mesh_select",
            "arah_mesh_simplify_scratch_bytes", "arah_mesh_simplify",
            "arah_mesh_adjacency_scratch_bytes", "arah_mesh_adjacency", "arah_mesh_vertex_normals", "arah_mesh_smooth",
+           "arah_mesh_orient_scratch_bytes", "arah_mesh_orient", "arah_mesh_boundary_loops_scratch_bytes",
+           "arah_mesh_boundary_loops", "arah_mesh_fill_holes_scratch_bytes", "arah_mesh_fill_holes",
            "arah_mesh_rasterize", "arah_mesh_rasterize_debug", "arah_mesh_interpolate", "arah_mesh_raycast", "arah_mesh_raycast_debug",
            "arah_point_index_bytes", "arah_point_index_build", "arah_point_nearest", "arah_sample_scores_bytes", "arah_sample_scores",
            "arah_contains_index_bytes", "arah_contains_index_count", "arah_contains_index_fill", "arah_mesh_contains",
@@ -189,7 +191,8 @@ def load_library():
     for name in ("arah_point_index_bytes", "arah_sample_scores_bytes"):
         getattr(lib, name).restype = C.c_size_t
         getattr(lib, name).argtypes = [C.c_int32]
-    for name in ("arah_mesh_components_scratch_bytes", "arah_mesh_select_scratch_bytes", "arah_mesh_adjacency_scratch_bytes"):
+    for name in ("arah_mesh_components_scratch_bytes", "arah_mesh_select_scratch_bytes", "arah_mesh_adjacency_scratch_bytes",
+                 "arah_mesh_orient_scratch_bytes", "arah_mesh_boundary_loops_scratch_bytes", "arah_mesh_fill_holes_scratch_bytes"):
         getattr(lib, name).restype = C.c_size_t
         getattr(lib, name).argtypes = [C.c_int64, C.c_int64]
     lib.arah_mesh_simplify_scratch_bytes.restype = C.c_size_t
@@ -1021,6 +1024,133 @@ def mesh_smooth(verts, faces, iterations, lamb=0.5, mu=-0.53, method="taubin", b
                                     (C.c_float * 2)(factors[0], factors[-1]), C.c_int32(int(pin)), _ptr(tmp), _ptr(out), _stream()),
                "arah_mesh_smooth")
     return out
+
+
+def _mesh_adj_only(faces, n_verts, adjacency, what):
+    """faces on the GPU over n_verts vertices and the eight arrays of mesh_adjacency (built here when None): -> (faces int32
+    contiguous, V, F, adjacency as contiguous device arrays)."""
+    from . import meshing
+    f, V, F = _mesh_cc_args(faces, n_verts, what)
+    if F > meshing.ADJACENCY_MAX_FACES:
+        raise ValueError("%s: at most 2^28 faces, got %d" % (what, F))
+    if adjacency is None:
+        return f, V, F, mesh_adjacency(f, V)
+    adjacency = tuple(adjacency)
+    shapes = ((V + 1,), (3 * F,), (V + 1,), (6 * F,), (6 * F,), (6 * F,), (V,), (8,))
+    if len(adjacency) != 8 or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != s or t.device != f.device
+                                  or t.dtype != (torch.uint8 if i == 6 else torch.int32)
+                                  for i, (t, s) in enumerate(zip(adjacency, shapes))):
+        raise ValueError("%s: adjacency must be the eight arrays of mesh_adjacency of these faces and vertices, on %s" % (what, f.device))
+    return f, V, F, tuple(t.contiguous() for t in adjacency)
+
+
+def mesh_orient(verts, faces, policy="majority", adjacency=None, quant=None):
+    """Consistent orientation of an indexed mesh (arah_mesh_orient, csrc/meshorient.hpp): verts (V,3) float32 on the GPU -- or the
+    vertex count under "seed" and "majority" --, faces (F,3) integer ids on the GPU, adjacency: `mesh_adjacency` of them, or None to
+    build it here.  -> flip (F,) uint8, face_comp (F,) int32, faces_out (F,3) int32, comp_faces, comp_flags (F,) int32,
+    comp_vol_hi, comp_vol_lo (F,) int64, counts (6,) int32 as meshing.mesh_orient describes them, and equal to it bit for bit.  No
+    host synchronisation under "seed" and "majority"; the two volume policies read the vertices' bounds once
+    (meshing.orient_quant) unless `quant` is given."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    pol = meshing.check_orient_policy(policy)
+    if isinstance(verts, torch.Tensor) and verts.dim() > 0:
+        if verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+            raise ValueError("mesh_orient: verts must be a (V, 3) float32 tensor")
+        v, n_verts = verts.detach().contiguous(), int(verts.shape[0])
+    else:
+        v, n_verts = None, verts
+    if pol >= 2 and v is None:
+        raise ValueError("mesh_orient: policy %r needs the vertices, not their number" % (policy,))
+    f, V, F, adj = _mesh_adj_only(faces, n_verts, adjacency, "mesh_orient")
+    if v is not None and v.device != f.device:
+        raise ValueError("mesh_orient: verts live on %s, faces on %s" % (v.device, f.device))
+    origin, scale = ([0.0, 0.0, 0.0], 1.0)
+    if pol >= 2:
+        origin, scale = meshing._check_quant(meshing.orient_quant(v) if quant is None else quant, "mesh_orient")
+    dev, i32, i64 = f.device, torch.int32, torch.int64
+    with _on_device(dev):
+        scratch = _mesh_cc_buf(dev, int(lib.arah_mesh_orient_scratch_bytes(V, F)))
+        flip = torch.empty(F, dtype=torch.uint8, device=dev)
+        face_comp, comp_faces, comp_flags = (torch.empty(F, dtype=i32, device=dev) for _ in range(3))
+        faces_out = torch.empty(F, 3, dtype=i32, device=dev)
+        vol_hi, vol_lo = (torch.empty(F, dtype=i64, device=dev) for _ in range(2))
+        counts = torch.empty(6, dtype=i32, device=dev)
+        _check(lib.arah_mesh_orient(_ptr(v) if pol >= 2 else None, C.c_int64(V), _ptr(f), C.c_int64(F), _ptr(adj[0]), _ptr(adj[1]),
+                                    _ptr(adj[2]), _ptr(adj[3]), _ptr(adj[4]), _ptr(adj[5]), C.c_int32(pol), (C.c_float * 3)(*origin),
+                                    C.c_double(scale), _ptr(flip), _ptr(face_comp), _ptr(faces_out), _ptr(comp_faces),
+                                    _ptr(comp_flags), _ptr(vol_hi), _ptr(vol_lo), _ptr(counts), _ptr(scratch),
+                                    C.c_size_t(scratch.numel()), _stream()), "arah_mesh_orient")
+    return flip, face_comp, faces_out, comp_faces, comp_flags, vol_hi, vol_lo, counts
+
+
+def mesh_boundary_loops(faces, n_verts, adjacency=None):
+    """Boundary half-edges and loops of an indexed mesh (arah_mesh_boundary_loops): faces (F,3) integer ids on the GPU over n_verts
+    vertices, adjacency: `mesh_adjacency` of them, or None to build it here.  -> edges (3F,2), edge_face, edge_loop (3F,) int32,
+    loop_edges (V,) int32, loop_simple (V,) uint8, loop_vert (V,) int32, counts (3,) int32 as meshing.mesh_boundary_loops describes
+    them, and equal to it bit for bit.  All on the device, no host synchronisation."""
+    require_gpu()
+    lib = load_library()
+    f, V, F, adj = _mesh_adj_only(faces, n_verts, adjacency, "mesh_boundary_loops")
+    dev, i32 = f.device, torch.int32
+    with _on_device(dev):
+        scratch = _mesh_cc_buf(dev, int(lib.arah_mesh_boundary_loops_scratch_bytes(V, F)))
+        edges = torch.empty(3 * F, 2, dtype=i32, device=dev)
+        edge_face, edge_loop = (torch.empty(3 * F, dtype=i32, device=dev) for _ in range(2))
+        loop_edges, loop_vert = (torch.empty(V, dtype=i32, device=dev) for _ in range(2))
+        loop_simple = torch.empty(V, dtype=torch.uint8, device=dev)
+        counts = torch.empty(3, dtype=i32, device=dev)
+        _check(lib.arah_mesh_boundary_loops(_ptr(f), C.c_int64(F), C.c_int64(V), _ptr(adj[2]), _ptr(adj[3]), _ptr(adj[4]), _ptr(adj[5]),
+                                            _ptr(edges), _ptr(edge_face), _ptr(edge_loop), _ptr(loop_edges), _ptr(loop_simple),
+                                            _ptr(loop_vert), _ptr(counts), _ptr(scratch), C.c_size_t(scratch.numel()), _stream()),
+               "arah_mesh_boundary_loops")
+    return edges, edge_face, edge_loop, loop_edges, loop_simple, loop_vert, counts
+
+
+def mesh_fill_holes(verts, faces, max_edges=64, adjacency=None, loops=None, quant=None):
+    """Small holes closed by a fan (arah_mesh_fill_holes): verts (V,3) float32 and faces (F,3) integer ids on the GPU, loops: the
+    arrays of `mesh_boundary_loops` of the mesh, or None to build them here (from `adjacency`, itself built when None).  ->
+    verts_out (V + V // 3, 3) float32, vert_src (V + V // 3,) int32, faces_out (4F,3) int32, face_loop (4F,) int32, counts (5,)
+    int32 as meshing.mesh_fill_holes describes them, and equal to it bit for bit.  One host synchronisation: the vertices' bounds
+    (meshing.fill_quant), none when `quant` is given."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    max_edges = meshing.check_max_edges(max_edges)
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise ValueError("mesh_fill_holes: verts must be a (V, 3) float32 tensor")
+    V = int(verts.shape[0])
+    f, _, F = _mesh_cc_args(faces, V, "mesh_fill_holes")
+    if verts.device != f.device:
+        raise ValueError("mesh_fill_holes: verts live on %s, faces on %s" % (verts.device, f.device))
+    if F > meshing.ADJACENCY_MAX_FACES:
+        raise ValueError("mesh_fill_holes: at most 2^28 faces, got %d" % F)
+    v = verts.detach().contiguous()
+    origin, scale = meshing._check_quant(meshing.fill_quant(v) if quant is None else quant, "mesh_fill_holes")
+    if loops is None:
+        loops = mesh_boundary_loops(f, V, adjacency=adjacency)
+    else:
+        loops = tuple(loops)
+        shapes = ((3 * F, 2), (3 * F,), (3 * F,), (V,), (V,), (V,), (3,))
+        if len(loops) != 7 or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != s or t.device != f.device
+                                  or t.dtype != (torch.uint8 if i == 4 else torch.int32)
+                                  for i, (t, s) in enumerate(zip(loops, shapes))):
+            raise ValueError("mesh_fill_holes: loops must be the seven arrays of mesh_boundary_loops of this mesh, on %s" % (f.device,))
+        loops = tuple(t.contiguous() for t in loops)
+    dev, i32 = f.device, torch.int32
+    with _on_device(dev):
+        scratch = _mesh_cc_buf(dev, int(lib.arah_mesh_fill_holes_scratch_bytes(V, F)))
+        verts_out = torch.empty(V + V // 3, 3, dtype=torch.float32, device=dev)
+        vert_src = torch.empty(V + V // 3, dtype=i32, device=dev)
+        faces_out = torch.empty(4 * F, 3, dtype=i32, device=dev)
+        face_loop = torch.empty(4 * F, dtype=i32, device=dev)
+        counts = torch.empty(5, dtype=i32, device=dev)
+        _check(lib.arah_mesh_fill_holes(_ptr(v), C.c_int64(V), _ptr(f), C.c_int64(F), _ptr(loops[0]), _ptr(loops[2]), _ptr(loops[3]),
+                                        _ptr(loops[4]), _ptr(loops[5]), _ptr(loops[6]), C.c_int32(max_edges), (C.c_float * 3)(*origin),
+                                        C.c_double(scale), _ptr(verts_out), _ptr(vert_src), _ptr(faces_out), _ptr(face_loop),
+                                        _ptr(counts), _ptr(scratch), C.c_size_t(scratch.numel()), _stream()), "arah_mesh_fill_holes")
+    return verts_out, vert_src, faces_out, face_loop, counts
 
 
 def mesh_rasterize(verts_uvz, faces, height, width, z_near=1e-4, cull="none", thresholds=None):

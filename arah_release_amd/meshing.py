@@ -590,6 +590,319 @@ def mesh_smooth(verts, faces, iterations, lamb=0.5, mu=-0.53, method="taubin", b
     return cur
 
 
+# ---- orientation, boundary loops, hole filling -----------------------------------------------------------------------------------
+ORIENT_POLICIES = {"seed": 0, "majority": 1, "negative": 2, "positive": 3}
+ORIENT_VOL_BITS = 18                    # quantised coordinates lie in [-2^18, 2^18]: a determinant of three stays below 2^57
+FILL_MAX_EDGES = 1 << 26                # edges of a filled loop: 2^26 fixed-point coordinates below 2^36 sum below 2^62
+
+
+def check_orient_policy(policy, what="mesh_orient"):
+    if not isinstance(policy, str) or policy not in ORIENT_POLICIES:
+        raise ValueError("%s: policy must be one of %s, got %r" % (what, ", ".join(ORIENT_POLICIES), policy))
+    return ORIENT_POLICIES[policy]
+
+
+def check_max_edges(max_edges, what="mesh_fill_holes"):
+    if isinstance(max_edges, bool) or not isinstance(max_edges, (int, np.integer)) or not 0 <= int(max_edges) <= FILL_MAX_EDGES:
+        raise ValueError("%s: max_edges must be an integer in [0, 2^26], got %r" % (what, max_edges))
+    return int(max_edges)
+
+
+def finite_bounds(verts):
+    """(lo, hi), three float32 values each as Python floats: the box of the vertices whose three coordinates are finite, or None
+    when there is none.  One host synchronisation for a tensor on the device."""
+    if int(verts.shape[0]) == 0:
+        return None
+    v = verts.detach().float()
+    finite = torch.isfinite(v).all(1, keepdim=True)
+    inf = torch.full_like(v, float("inf"))
+    lo, hi = torch.stack([torch.where(finite, v, inf).amin(0), torch.where(finite, v, -inf).amax(0)]).tolist()
+    return None if lo[0] > hi[0] else (lo, hi)
+
+
+def _pow2_scale(extent, bits):
+    """2^(bits - e), e = ceil(log2(extent)): a length of at most `extent` times it is at most 2^bits.  1 for no extent."""
+    if not extent > 0.0:
+        return 1.0
+    m, e = math.frexp(extent)
+    e = e - 1 if m == 0.5 else e
+    return math.ldexp(1.0, bits - e)
+
+
+def orient_quant(verts):
+    """The lattice of the exact volumes of `mesh_orient`, shared by the specification and the device: -> (origin, scale); origin =
+    the float32 midpoint float32((lo + hi) / 2) of `finite_bounds`, scale = the power of two 2^(18 - e), e = ceil(log2(the largest
+    distance of a bound from the origin along an axis)).  (0, 0, 0) and 1 without a finite vertex or an extent."""
+    box = finite_bounds(verts)
+    if box is None:
+        return [0.0, 0.0, 0.0], 1.0
+    lo, hi = box
+    origin = [float(np.float32((l + h) / 2.0)) for l, h in zip(lo, hi)]
+    half = max(max(h - o, o - l) for l, h, o in zip(lo, hi, origin))
+    return origin, _pow2_scale(half, ORIENT_VOL_BITS)
+
+
+def fill_quant(verts):
+    """The fixed-point lattice of the new vertices of `mesh_fill_holes`, with the constants of `mesh_simplify`: -> (origin, scale);
+    origin = the lower corner of `finite_bounds`, scale = 2^(36 - e), e = ceil(log2(the longest side)), so that the fixed-point
+    coordinates of a finite vertex lie in [0, 2^36]."""
+    box = finite_bounds(verts)
+    if box is None:
+        return [0.0, 0.0, 0.0], 1.0
+    lo, hi = box
+    return [float(x) for x in lo], _pow2_scale(max(h - l for l, h in zip(lo, hi)), SIMPLIFY_FIX_BITS)
+
+
+def _check_quant(quant, what):
+    try:
+        origin, scale = quant
+        origin, scale = [float(np.float32(float(x))) for x in origin], float(scale)
+    except (TypeError, ValueError):
+        raise ValueError("%s: quant must be (origin of three numbers, scale), got %r" % (what, quant))
+    if len(origin) != 3 or not all(math.isfinite(x) for x in origin) or not (scale > 0.0 and math.isfinite(scale)):
+        raise ValueError("%s: quant must be a finite origin and a finite scale > 0, got %r" % (what, quant))
+    return origin, scale
+
+
+def _min_labels(n, a, b):
+    """The smallest node id of every node's connected component in the graph with n nodes and the edges (a[i], b[i]): every node
+    takes the smallest label among itself and its neighbours, then its label's label, until nothing changes."""
+    low = torch.arange(n, device=a.device)
+    both = torch.cat([a, b])
+    while both.shape[0]:
+        m = torch.minimum(low[a], low[b])
+        new = low.scatter_reduce(0, both, torch.cat([m, m]), "amin")
+        new = new[new]
+        if torch.equal(new, low):
+            break
+        low = new
+    return low
+
+
+def _faces_i32(faces, raw):
+    """The faces as the device sees them: int32, an id that does not fit one replaced by -1 when the input is of another type."""
+    if raw.dtype == torch.int32:
+        return faces.to(torch.int32)
+    return torch.where((faces >= 0) & (faces <= 2 ** 31 - 1), faces, torch.full_like(faces, -1)).to(torch.int32)
+
+
+def _orient_args(verts, faces, what):
+    """verts (V,3) float32 or a vertex count, faces: -> (verts or None, faces as int64, V, the valid rows' mask, the faces as the
+    device sees them)."""
+    raw = torch.as_tensor(faces)
+    if isinstance(verts, torch.Tensor) and verts.dim() > 0:
+        v, f, V, in_range = _mesh_verts(verts, faces, what)
+    else:
+        v = None
+        f, V, in_range = _cc_faces(faces, verts, what)
+        if int(f.shape[0]) > ADJACENCY_MAX_FACES:
+            raise ValueError("%s: at most 2^28 faces, got %d" % (what, int(f.shape[0])))
+    valid = in_range & (f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 0] != f[:, 2])
+    return v, f, V, valid, _faces_i32(f, raw)
+
+
+def _half_edges(f, valid, V):
+    """The directed edges of the valid faces in ascending (face, corner) order: -> (start, end, face, the number of valid faces on
+    the undirected edge of each)."""
+    rows = torch.nonzero(valid)[:, 0]
+    fv = f[rows]
+    s, d, face = fv.reshape(-1), fv[:, [1, 2, 0]].reshape(-1), rows.repeat_interleave(3)
+    W = max(V, 1)
+    _, which, cnt = torch.unique(torch.minimum(s, d) * W + torch.maximum(s, d), return_inverse=True, return_counts=True)
+    return s, d, face, (cnt[which] if s.shape[0] else s)
+
+
+def mesh_orient(verts, faces, policy="majority", adjacency=None, quant=None):
+    """Consistent orientation of an indexed mesh: verts (V,3) float32 -- or just the vertex count under the policies "seed" and
+    "majority" --, faces (F,3) integer ids, F <= 2^28.
+
+    VALIDITY and TRAVERSAL are those of `mesh_adjacency`.  Two valid faces are NEIGHBOURS across an undirected edge when exactly two
+    valid faces lie on it: CONSISTENT (s = 0) when they traverse it in opposite directions, inconsistent (s = 1) otherwise; an edge
+    with one face or with three or more carries no constraint.  ORIENTATION COMPONENTS are the classes of faces connected through
+    such edges, numbered in ascending order of their lowest face id; an invalid face belongs to none (label -1).
+
+    The relative flips come from the DOUBLE COVER: the nodes are 2 f + bit, a pair (f, g, s) joins 2 f with 2 g + s and 2 f + 1
+    with 2 g + (1 - s), and root(x) is the smallest node of x's connected component.  root(2 f) >> 1 is the lowest face of f's
+    component.  The component is NON-ORIENTABLE when root(2 f) == root(2 f + 1) (a Moebius strip): its faces are never flipped
+    and have b = 0.  Otherwise b(f) = root(2 f) & 1 is the flip of f relative to the component's lowest face.
+
+    The POLICY fixes what is left free in an orientable component: "seed" the lowest face keeps its orientation; "majority" the
+    orientation held by more faces wins (the component is reversed when more faces have b = 1 than b = 0; a tie is "seed");
+    "negative" / "positive" the component's signed volume gets that sign (the project's own meshes are negative).  The volume is
+    an exact integer: q = llrint(clamp((double(v) - double(origin)) scale, -2^18, 2^18)) with (origin, scale) = quant, by default
+    `orient_quant(verts)`; det(q0, q1, q2) of a face in int64 (|det| < 2^57), negated for a face with b = 1; a face with a
+    non-finite vertex contributes nothing; the low 32 bits (unsigned) and the arithmetic high part d >> 32 are summed apart per
+    component, the volume is hi 2^32 + lo.  A component whose volume is zero (smaller than a lattice step, an open sheet seen
+    edge-on) falls back to "majority".  Under "seed" and "majority" the two sums stay zero.
+
+    -> flip (F,) uint8: 1 where the face is reversed; face_comp (F,) int32; faces_out (F,3) int32: a flipped row (a, b, c) is
+    (a, c, b), every other row is the input's, row order and vertices never change; comp_faces (F,) int32, comp_flags (F,) int32
+    (bit 0 non-orientable, bit 1 the policy reversed the component), comp_vol_hi, comp_vol_lo (F,) int64, indexed by component
+    and zero from the number of components on; counts (6,) int32: valid faces, components, non-orientable components, faces with
+    b = 1, components reversed by the policy, faces flipped.  Integers throughout: the result is unique.  `adjacency` (the arrays
+    of `mesh_adjacency`) is what the device searches partners in; here it is only checked for its shapes.  Plain tensor operations
+    on the tensor's device: the specification of arah_mesh_orient (csrc/meshorient.hpp), and what runs for meshes on the host."""
+    pol = check_orient_policy(policy)
+    by_volume = pol >= 2
+    v, f, V, valid, f32 = _orient_args(verts, faces, "mesh_orient")
+    if by_volume and v is None:
+        raise ValueError("mesh_orient: policy %r needs the vertices, not their number" % (policy,))
+    dev, F, i32, i64 = f.device, int(f.shape[0]), torch.int32, torch.int64
+    if adjacency is not None:
+        _adjacency_of(f, V, adjacency, "mesh_orient")
+    if by_volume:
+        origin, scale = _check_quant(orient_quant(v) if quant is None else quant, "mesh_orient")
+    # the pairs: the two half-edges of every undirected edge with exactly two faces, adjacent after a sort by edge
+    s, d, face, on_edge = _half_edges(f, valid, V)
+    two = torch.nonzero(on_edge == 2)[:, 0]
+    order = two[torch.sort(torch.minimum(s, d)[two] * max(V, 1) + torch.maximum(s, d)[two], stable=True).indices]
+    first, second = order[0::2], order[1::2]
+    same = ((s[first] < d[first]) == (s[second] < d[second])).long()
+    lo_f, hi_f = torch.minimum(face[first], face[second]), torch.maximum(face[first], face[second])
+    root = _min_labels(2 * F, torch.cat([2 * lo_f, 2 * lo_f + 1]), torch.cat([2 * hi_f + same, 2 * hi_f + (1 - same)]))
+    r0, r1 = root[0::2], root[1::2]
+    ids = torch.arange(F, device=dev)
+    froot = torch.where(valid, r0 >> 1, torch.full_like(r0, -1))
+    b = valid & ((r0 & 1) == 1)
+    is_root = froot == ids
+    dense = torch.cumsum(is_root.long(), 0) - 1
+    face_comp = torch.where(valid, dense[froot.clamp_min(0)], torch.full_like(froot, -1)) if F else froot
+    n_comp = int(is_root.sum())
+    comp_faces = torch.bincount(face_comp[valid], minlength=F)
+    ones = torch.bincount(face_comp[b], minlength=F)
+    nonor = torch.zeros(F, dtype=torch.bool, device=dev)
+    nonor[face_comp[valid & (r0 == r1)]] = True
+    vol_hi, vol_lo = torch.zeros(F, dtype=i64, device=dev), torch.zeros(F, dtype=i64, device=dev)
+    if by_volume and V:
+        rows = torch.nonzero(valid)[:, 0]
+        p = v[f[rows]]                                                          # (Fv,3,3): corner, axis
+        finite = torch.isfinite(p).all(2).all(1)
+        lim = 2.0 ** ORIENT_VOL_BITS
+        x = (p.to(torch.float64) - torch.tensor(origin, dtype=torch.float64, device=dev)) * scale
+        q = torch.where(finite[:, None, None], x, torch.zeros_like(x)).clamp(-lim, lim).round().long()
+        det = (q[:, 0, 0] * (q[:, 1, 1] * q[:, 2, 2] - q[:, 1, 2] * q[:, 2, 1]) - q[:, 0, 1] * (q[:, 1, 0] * q[:, 2, 2] - q[:, 1, 2] * q[:, 2, 0])
+               + q[:, 0, 2] * (q[:, 1, 0] * q[:, 2, 1] - q[:, 1, 1] * q[:, 2, 0]))
+        det = torch.where(b[rows], -det, det)[finite]
+        comp = face_comp[rows][finite]
+        vol_lo.index_add_(0, comp, det & 0xFFFFFFFF)
+        vol_hi.index_add_(0, comp, det >> 32)
+    # the sign of hi 2^32 + lo: the carry of lo goes to hi, what is left of lo is below 2^32 and cannot outweigh it
+    hi2, lo2 = vol_hi + (vol_lo >> 32), vol_lo & 0xFFFFFFFF
+    sign = torch.where(hi2 > 0, 1, torch.where(hi2 < 0, -1, (lo2 > 0).long()))
+    majority = ones > comp_faces - ones
+    if pol == 0:
+        rev = torch.zeros_like(majority)
+    elif pol == 1:
+        rev = majority
+    else:
+        rev = torch.where(sign == 0, majority, sign > 0 if pol == 2 else sign < 0)
+    rev = rev & ~nonor
+    comp_flags = nonor.long() | (rev.long() << 1)
+    fc = face_comp.clamp_min(0)
+    flip = valid & ~nonor[fc] & (b ^ rev[fc]) if F else valid
+    faces_out = torch.where(flip[:, None], f32[:, [0, 2, 1]], f32)
+    counts = torch.tensor([int(valid.sum()), n_comp, int(nonor.sum()), int(b.sum()), int(rev.sum()), int(flip.sum())], dtype=i32, device=dev)
+    return (flip.to(torch.uint8), face_comp.to(i32), faces_out, comp_faces.to(i32), comp_flags.to(i32), vol_hi, vol_lo, counts)
+
+
+def mesh_boundary_loops(faces, n_verts, adjacency=None):
+    """The boundary of an indexed mesh: faces (F,3) integer ids over V = n_verts vertices, validity and traversal as in
+    `mesh_adjacency`.  A BOUNDARY HALF-EDGE is a directed edge a->b of a valid face whose undirected edge carries exactly one valid
+    face; they are numbered in ascending (face, corner) order, corner c of (i0, i1, i2) starting the edge i_c -> i_(c+1).  A LOOP is a
+    connected component of the boundary half-edges through shared vertex ids; loops are numbered in ascending order of their
+    smallest vertex id.  A loop is SIMPLE when every vertex on it has exactly one outgoing and one incoming boundary half-edge: a
+    connected simple loop is one closed polygon; two holes that touch at a vertex, or a hole in a misoriented neighbourhood, are
+    not simple.  -> edges (3F,2) int32, edge_face (3F,) int32, edge_loop (3F,) int32, zero from the number of half-edges B on;
+    loop_edges (V,) int32, loop_simple (V,) uint8, loop_vert (V,) int32 (the loop's smallest vertex), indexed by loop and zero
+    from the number of loops L on; counts (3,) int32: B, L, the simple loops.  `adjacency` is what the device reads the edges'
+    face counts from; here it is only checked for its shapes.  The specification of arah_mesh_boundary_loops."""
+    f, V, in_range = _cc_faces(faces, n_verts, "mesh_boundary_loops")
+    dev, F, i32 = f.device, int(f.shape[0]), torch.int32
+    if F > ADJACENCY_MAX_FACES:
+        raise ValueError("mesh_boundary_loops: at most 2^28 faces, got %d" % F)
+    if adjacency is not None:
+        _adjacency_of(f, V, adjacency, "mesh_boundary_loops")
+    valid = in_range & (f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 0] != f[:, 2])
+    s, d, face, on_edge = _half_edges(f, valid, V)
+    keep = on_edge == 1
+    a, b, face = s[keep], d[keep], face[keep]
+    B = int(a.shape[0])
+    low = _min_labels(V, a, b)
+    vout, vin = torch.bincount(a, minlength=V), torch.bincount(b, minlength=V)
+    on = (vout + vin) > 0
+    is_root = on & (low == torch.arange(V, device=dev))
+    dense = torch.cumsum(is_root.long(), 0) - 1
+    L = int(is_root.sum())
+    loop_of_edge = dense[low[a]]
+    edges = torch.zeros(3 * F, 2, dtype=torch.int64, device=dev)
+    edges[:B] = torch.stack([a, b], 1)
+    edge_face, edge_loop = (torch.zeros(3 * F, dtype=torch.int64, device=dev) for _ in range(2))
+    edge_face[:B], edge_loop[:B] = face, loop_of_edge
+    loop_edges = torch.bincount(loop_of_edge, minlength=V)
+    bad = torch.zeros(V, dtype=torch.bool, device=dev)
+    bad[dense[low[on & ((vout != 1) | (vin != 1))]]] = True
+    loop_simple = ~bad & (torch.arange(V, device=dev) < L)
+    loop_vert = torch.zeros(V, dtype=torch.int64, device=dev)
+    loop_vert[:L] = torch.nonzero(is_root)[:, 0]
+    counts = torch.tensor([B, L, int(loop_simple.sum())], dtype=i32, device=dev)
+    return edges.to(i32), edge_face.to(i32), edge_loop.to(i32), loop_edges.to(i32), loop_simple.to(torch.uint8), loop_vert.to(i32), counts
+
+
+def mesh_fill_holes(verts, faces, max_edges=64, adjacency=None, loops=None, quant=None):
+    """Small holes of an indexed mesh closed by a fan: verts (V,3) float32, faces (F,3) integer ids, loops: the arrays of
+    `mesh_boundary_loops` of the mesh (built here when None).  A loop is FILLED when it is simple, 3 <= loop_edges <= max_edges and
+    none of its vertices has a non-finite coordinate.  The filled loops, in loop order, append one vertex each after the V
+    existing ones; every half-edge a->b of a filled loop appends, in edge order, the face (b, a, new vertex) after the F existing
+    ones: it runs against the half-edge, so it is consistent with the face that owns it.  The new vertex is the mean of the
+    loop's vertices by the fixed-point rule of `mesh_simplify`: q = llrint(clamp((double(v) - double(origin)) scale, -2^36,
+    2^36)), S = sum q over the loop's n vertices in integers, float32(double(origin) + (double(S) / double(n)) / scale), with
+    (origin, scale) = quant, by default `fill_quant(verts)`: the position does not depend on the order of arrival.
+
+    -> verts_out (V + V // 3, 3) float32, vert_src (V + V // 3,) int32: a vertex's own id for the old ones, the loop's smallest
+    vertex id for a new one (attributes are gathered by it, never averaged); faces_out (4F,3) int32, face_loop (4F,) int32: -1
+    for the old faces, the loop of a new one; counts (5,) int32: boundary half-edges, loops, simple loops, filled loops, faces
+    added.  Rows behind the filled loops and the added faces are zero.  The specification of arah_mesh_fill_holes."""
+    max_edges = check_max_edges(max_edges)
+    raw = torch.as_tensor(faces)
+    v, f, V, _ = _mesh_verts(verts, faces, "mesh_fill_holes")
+    dev, F, i32, f64 = f.device, int(f.shape[0]), torch.int32, torch.float64
+    origin, scale = _check_quant(fill_quant(v) if quant is None else quant, "mesh_fill_holes")
+    if loops is None:
+        loops = mesh_boundary_loops(f, V, adjacency=adjacency)
+    edges, _, edge_loop, loop_edges, loop_simple, loop_vert, lcounts = loops
+    B, L, n_simple = lcounts.tolist()
+    a, b, l = edges[:B, 0].long(), edges[:B, 1].long(), edge_loop[:B].long()
+    n = loop_edges.long()
+    cand = (loop_simple != 0) & (n >= 3) & (n <= max_edges) & (torch.arange(V, device=dev) < L)
+    finite = torch.isfinite(v[a]).all(1) if B else torch.zeros(0, dtype=torch.bool, device=dev)
+    nonfinite = torch.zeros(V, dtype=torch.bool, device=dev)
+    nonfinite[l[cand[l] & ~finite]] = True
+    filled = cand & ~nonfinite
+    lrank = torch.where(filled, torch.cumsum(filled.long(), 0) - 1, torch.full((V,), -1, dtype=torch.int64, device=dev))
+    Lf = int(filled.sum())
+    o64 = torch.tensor(origin, dtype=f64, device=dev)
+    use = filled[l] if B else finite
+    lim = 2.0 ** SIMPLIFY_FIX_BITS
+    q = torch.clamp((v[a[use]].to(f64) - o64) * scale, -lim, lim).round().long()
+    S = torch.zeros(V, 3, dtype=torch.int64, device=dev).index_add_(0, l[use], q)
+    which = torch.nonzero(filled)[:, 0]
+    verts_out = torch.zeros(V + V // 3, 3, dtype=torch.float32, device=dev)
+    verts_out[:V] = v
+    verts_out[V:V + Lf] = (o64 + (S[which].to(f64) / n[which].to(f64)[:, None]) / scale).float()
+    vert_src = torch.zeros(V + V // 3, dtype=torch.int64, device=dev)
+    vert_src[:V] = torch.arange(V, device=dev)
+    vert_src[V:V + Lf] = loop_vert.long()[which]
+    Bf = int(use.sum())
+    faces_out = torch.zeros(4 * F, 3, dtype=torch.int64, device=dev)
+    faces_out[:F] = _faces_i32(f, raw).long()
+    faces_out[F:F + Bf] = torch.stack([b[use], a[use], V + lrank[l[use]]], 1)
+    face_loop = torch.zeros(4 * F, dtype=torch.int64, device=dev)
+    face_loop[:F] = -1
+    face_loop[F:F + Bf] = l[use]
+    counts = torch.tensor([B, L, n_simple, Lf, Bf], dtype=i32, device=dev)
+    return verts_out, vert_src.to(i32), faces_out.to(i32), face_loop.to(i32), counts
+
+
 RASTER_CULL = {"none": 0, "back": 1, "front": 2}
 _RASTER_EMPTY = 2 ** 63 - 1             # a pixel nothing covers; every real key is below it (z > 0: its bits are below 2^31)
 _RASTER_CHUNK = 1 << 22                 # fragments the specification tests at a time

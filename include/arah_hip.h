@@ -37,6 +37,9 @@
  *   arah_mesh_adjacency /   (none: the reference's users smooth and re-normal with trimesh / open3d / pytorch3d; the incident faces
  *   arah_mesh_vertex_normals /  and unique neighbours of every vertex with edge statistics, pytorch3d's verts_normals_packed over
  *   arah_mesh_smooth        them, and Laplacian / Taubin umbrella smoothing)
+ *   arah_mesh_orient /      (none: the reference's users repair scans with trimesh's fix_normals / fill_holes; consistent orientation
+ *   arah_mesh_boundary_loops /  by the double cover of the face graph, the boundary loops, and small holes closed by a fan around
+ *   arah_mesh_fill_holes    the loop's exact mean)
  *   arah_mesh_rasterize /   pytorch3d MeshRasterizer's three outputs for an INDEXED mesh (pix_to_face, zbuf, bary_coords; one face per
  *   arah_mesh_interpolate   pixel, no blur, perspective-correct) and interpolate_face_attributes over them; arah_rasterize below
  *                           stays what the gen_cano_mesh branch draws with
@@ -394,6 +397,58 @@ int arah_mesh_vertex_normals(const float* verts, int64_t n_verts, const int32_t*
  * launches nothing. */
 int arah_mesh_smooth(const float* verts, int64_t n_verts, const int32_t* nbr_start, const int32_t* nbr, const uint8_t* vert_flags,
                      int32_t n_steps, const float h_factors[2], int32_t pin, float* tmp, float* verts_out, void* stream);
+/* Consistent orientation of an indexed mesh (csrc/meshorient.hpp; meshing.mesh_orient is the rule, bit for bit).  faces
+ * [n_faces][3], and vf_start / vf / nbr_start / nbr / nbr_out / nbr_in of arah_mesh_adjacency on the same mesh.  Two valid faces are
+ * neighbours across an edge that carries exactly two valid faces, consistent when they traverse it in opposite directions; the
+ * orientation components are the classes of faces connected through such edges, numbered in ascending order of their lowest
+ * face; the double cover (nodes 2 f + bit) gives b(f), the flip of f relative to that lowest face, and marks the non-orientable
+ * components, whose faces are never flipped.  policy: 0 seed (the lowest face keeps its orientation), 1 majority (the orientation
+ * held by more faces wins, ties to seed), 2 negative / 3 positive (the component's integer volume gets that sign; a zero volume
+ * falls back to majority).  The volume: q = llrint(clamp((double(v) - double(h_origin)) scale, -2^18, 2^18)), the sum of
+ * det(q0, q1, q2) in int64 over the faces as the seed orients them, a face with a non-finite vertex contributing nothing; verts
+ * [n_verts][3], h_origin and scale are read under the policies 2 and 3 only (and may be NULL / anything otherwise).  -> flip
+ * [n_faces] uint8; face_comp [n_faces] (-1: an invalid face); faces_out [n_faces][3]: a flipped row (a, b, c) is (a, c, b), every
+ * other row is copied; comp_faces, comp_flags (bit 0 non-orientable, bit 1 reversed by the policy) [n_faces] int32 and comp_vol_hi,
+ * comp_vol_lo [n_faces] int64 (the volume is hi 2^32 + lo; zero under the policies 0 and 1), indexed by component, ZERO from the
+ * number of components on; counts (device int32[6]) = valid faces, components, non-orientable components, faces with b = 1,
+ * components reversed, faces flipped.  Integer atomics only (min, add): the result is unique.  Sizes and errors as for
+ * arah_mesh_adjacency; scratch: arah_mesh_orient_scratch_bytes(n_verts, n_faces) device bytes.  n_faces = 0 still writes counts.
+ * No host synchronisation, no allocation. */
+size_t arah_mesh_orient_scratch_bytes(int64_t n_verts, int64_t n_faces);
+int arah_mesh_orient(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int32_t* vf_start, const int32_t* vf,
+                     const int32_t* nbr_start, const int32_t* nbr, const int32_t* nbr_out, const int32_t* nbr_in, int32_t policy,
+                     const float h_origin[3], double scale, uint8_t* flip, int32_t* face_comp, int32_t* faces_out, int32_t* comp_faces,
+                     int32_t* comp_flags, int64_t* comp_vol_hi, int64_t* comp_vol_lo, int32_t* counts, void* scratch,
+                     size_t scratch_bytes, void* stream);
+/* Boundary loops of an indexed mesh (meshing.mesh_boundary_loops is the rule).  A boundary half-edge is a directed edge a->b of a
+ * valid face whose undirected edge carries exactly one valid face (nbr_start / nbr / nbr_out / nbr_in of arah_mesh_adjacency); they
+ * are numbered in ascending (face, corner) order.  A loop is a connected component of them through shared vertex ids; loops are
+ * numbered in ascending order of their smallest vertex; a loop is simple when every vertex on it has exactly one outgoing and one
+ * incoming boundary half-edge.  -> edges [3 n_faces][2], edge_face, edge_loop [3 n_faces]; loop_edges, loop_vert (the smallest
+ * vertex) [n_verts] int32 and loop_simple [n_verts] uint8, indexed by loop; counts (device int32[3]) = boundary half-edges B,
+ * loops L, simple loops.  Rows from B and from L on are ZERO.  Integer atomics only.  Sizes and errors as for arah_mesh_adjacency;
+ * scratch: arah_mesh_boundary_loops_scratch_bytes(n_verts, n_faces).  Empty inputs still write counts. */
+size_t arah_mesh_boundary_loops_scratch_bytes(int64_t n_verts, int64_t n_faces);
+int arah_mesh_boundary_loops(const int32_t* faces, int64_t n_faces, int64_t n_verts, const int32_t* nbr_start, const int32_t* nbr,
+                             const int32_t* nbr_out, const int32_t* nbr_in, int32_t* edges, int32_t* edge_face, int32_t* edge_loop,
+                             int32_t* loop_edges, uint8_t* loop_simple, int32_t* loop_vert, int32_t* counts, void* scratch,
+                             size_t scratch_bytes, void* stream);
+/* Small holes closed by a fan (meshing.mesh_fill_holes is the rule): edges, edge_loop, loop_edges, loop_simple, loop_vert and
+ * loop_counts are the arrays of arah_mesh_boundary_loops on the same mesh.  A loop is filled when it is simple, 3 <= loop_edges <=
+ * max_edges (0 <= max_edges <= 2^26) and none of its vertices has a non-finite coordinate.  Filled loop number j (in loop order)
+ * adds the vertex n_verts + j at the fixed-point mean of the loop's vertices -- the rule of arah_mesh_simplify: q =
+ * llrint(clamp((double(v) - double(h_origin)) fix_scale, -2^36, 2^36)), float(double(h_origin) + (double(sum q) / double(n)) /
+ * fix_scale) -- and every half-edge a->b of a filled loop adds, in edge order, the face (b, a, new vertex) behind the n_faces old
+ * ones.  -> verts_out [n_verts + n_verts / 3][3], vert_src [n_verts + n_verts / 3] (an old vertex: itself; a new one: its loop's
+ * smallest vertex), faces_out [4 n_faces][3], face_loop [4 n_faces] (-1 for the old faces); counts (device int32[5]) = B, L, simple
+ * loops, filled loops, faces added.  Rows behind the filled loops and the added faces are ZERO.  Integer atomics only.  Sizes
+ * and errors as for arah_mesh_adjacency; scratch: arah_mesh_fill_holes_scratch_bytes(n_verts, n_faces). */
+size_t arah_mesh_fill_holes_scratch_bytes(int64_t n_verts, int64_t n_faces);
+int arah_mesh_fill_holes(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int32_t* edges,
+                         const int32_t* edge_loop, const int32_t* loop_edges, const uint8_t* loop_simple, const int32_t* loop_vert,
+                         const int32_t* loop_counts, int32_t max_edges, const float h_origin[3], double fix_scale, float* verts_out,
+                         int32_t* vert_src, int32_t* faces_out, int32_t* face_loop, int32_t* counts, void* scratch, size_t scratch_bytes,
+                         void* stream);
 /* An indexed mesh drawn (csrc/meshraster.hpp; meshing.mesh_rasterize is the rule, bit for bit): verts [n_verts][3] = (u, v, view
  * depth) in pixel coordinates (pixel (i, j) has its centre at u = j + 0.5, v = i + 0.5), faces [n_faces][3].  A face is valid when
  * its ids lie in [0, n_verts), its z are finite and > z_near and area2 = (x1-x0)(y2-y0) - (x2-x0)(y1-y0) is finite and not 0; cull
