@@ -16,6 +16,7 @@
 
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 
 #include "../../include/arah_hip.h"
 #include "pointwise.hpp"
@@ -1948,6 +1949,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_canon_solve(FrameDev fr, const 
 #endif
 }
 
+#include "meshcommon.hpp"
 #include "mcubes.hpp"
 #include "meshcc.hpp"
 #include "meshsimp.hpp"
@@ -3952,6 +3954,37 @@ int arah_skin_lbs_counted(const ArahFrame* f, const float* x_hat, int32_t n_max,
     return check_launch();
 }
 
+// ---- what the indexed-mesh entries below share (csrc/meshcommon.hpp) -----------------------------------
+static int mesh_grid(int64_t n, int cap = kImeshMaxGrid) {   // workgroups of an element-wise walk
+    return (int)min((int64_t)cap, max((int64_t)1, (n + kImeshThreads - 1) / kImeshThreads));
+}
+static size_t mesh_blocks(int64_t n) { return (size_t)((n + kImeshChunk - 1) / kImeshChunk); }   // workgroups of mesh_compact
+
+static void mesh_scan(hipStream_t s, const int* count, int n, int* base, int* total) {
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, count, n, base, total);
+}
+static void mesh_pad(hipStream_t s, void* buf, const int* total, int cap, int width) {
+    hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, reinterpret_cast<unsigned*>(buf), total, cap, width);
+}
+
+// count, scan, fill: launch(FILL as a std::bool_constant, blk_count, blk_base) issues one pass of a k_*_compact over nb chunks.
+// The count pass gets no bases and the fill pass no counts.
+extern "C++" {   // a template cannot have the C linkage of the entries around it
+template <class Launch>
+static void mesh_compact_passes(hipStream_t s, int nb, int* blk_count, int* blk_base, int* total, Launch launch) {
+    launch(std::false_type{}, blk_count, (const int*)nullptr);
+    mesh_scan(s, blk_count, nb, blk_base, total);
+    launch(std::true_type{}, (int*)nullptr, (const int*)blk_base);
+}
+}
+
+// Scratch of an entry: Carver's blocks (256-byte aligned, typed, null when the base is null: the *_scratch_bytes queries) and the
+// size they add up to, a whole number of 256 bytes and never 0.  Every entry has one carve_* that both it and its query call.
+struct MeshCarver : Carver {
+    explicit MeshCarver(void* scratch) : Carver{reinterpret_cast<char*>(scratch), 0} {}
+    size_t bytes() const { return off > 256 ? align_up(off, 256) : (size_t)256; }   // no max(): the sizes pass 2^32, stay in size_t
+};
+
 // ---- marching cubes (csrc/mcubes.hpp) ------------------------------------------------------------------
 size_t arah_marching_cubes_scratch_bytes(int32_t n_side) {
     if (n_side < 2) return 0;
@@ -3968,10 +4001,10 @@ int arah_marching_cubes(const float* sdf, int32_t n_side, float level, const int
     int* row_base = row_count + rows;
     const float vs = (float)(2.0 / (n_side - 1));   // sdf_meshing.py:27: voxel_size = 2.0 / (N - 1), rounded to fp32 once
     const signed char* table = reinterpret_cast<const signed char*>(tri_table);
-    hipLaunchKernelGGL(k_mcubes<kMcCount>, dim3(rows), dim3(kMcThreads), 0, s, sdf, (int)n_side, level, vs, table, (const int*)n_tri,
+    hipLaunchKernelGGL(k_mcubes<kMcCount>, dim3(rows), dim3(kImeshThreads), 0, s, sdf, (int)n_side, level, vs, table, (const int*)n_tri,
                        row_count, (const int*)nullptr, (float*)nullptr, 0, (const int*)nullptr, (int*)nullptr);
-    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)row_count, rows, row_base, (int*)n_tris);
-    hipLaunchKernelGGL(k_mcubes<kMcSoup>, dim3(rows), dim3(kMcThreads), 0, s, sdf, (int)n_side, level, vs, table, (const int*)n_tri,
+    mesh_scan(s, row_count, rows, row_base, n_tris);
+    hipLaunchKernelGGL(k_mcubes<kMcSoup>, dim3(rows), dim3(kImeshThreads), 0, s, sdf, (int)n_side, level, vs, table, (const int*)n_tri,
                        (int*)nullptr, (const int*)row_base, tris, (int)cap, (const int*)nullptr, (int*)nullptr);
     hipLaunchKernelGGL(k_mc_pad, dim3(1024), dim3(256), 0, s, tris, (const int*)n_tris, (int)cap);
     return check_launch();
@@ -4002,19 +4035,19 @@ int arah_marching_cubes_indexed(const float* sdf, int32_t n_side, float level, c
     int* crow_base = crow_count + crows;
     const float vs = (float)(2.0 / (n_side - 1));
     const signed char* table = reinterpret_cast<const signed char*>(tri_table);
-    hipLaunchKernelGGL(k_mc_verts<false>, dim3(vrows), dim3(kMcThreads), 0, s, sdf, N, level, vs, vrow_count, (const int*)nullptr,
+    hipLaunchKernelGGL(k_mc_verts<false>, dim3(vrows), dim3(kImeshThreads), 0, s, sdf, N, level, vs, vrow_count, (const int*)nullptr,
                        (int*)nullptr, (float*)nullptr, (int*)nullptr, 0);
-    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)vrow_count, vrows, vrow_base, (int*)counts);
-    hipLaunchKernelGGL(k_mc_verts<true>, dim3(vrows), dim3(kMcThreads), 0, s, sdf, N, level, vs, (int*)nullptr, (const int*)vrow_base,
+    mesh_scan(s, vrow_count, vrows, vrow_base, counts);
+    hipLaunchKernelGGL(k_mc_verts<true>, dim3(vrows), dim3(kImeshThreads), 0, s, sdf, N, level, vs, (int*)nullptr, (const int*)vrow_base,
                        first_vert, verts, (int*)vert_edge, (int)vert_cap);
-    hipLaunchKernelGGL(k_mcubes<kMcCount>, dim3(crows), dim3(kMcThreads), 0, s, sdf, N, level, vs, table, (const int*)n_tri, crow_count,
+    hipLaunchKernelGGL(k_mcubes<kMcCount>, dim3(crows), dim3(kImeshThreads), 0, s, sdf, N, level, vs, table, (const int*)n_tri, crow_count,
                        (const int*)nullptr, (float*)nullptr, 0, (const int*)nullptr, (int*)nullptr);
-    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)crow_count, crows, crow_base, (int*)counts + 1);
-    hipLaunchKernelGGL(k_mcubes<kMcFaces>, dim3(crows), dim3(kMcThreads), 0, s, sdf, N, level, vs, table, (const int*)n_tri,
+    mesh_scan(s, crow_count, crows, crow_base, counts + 1);
+    hipLaunchKernelGGL(k_mcubes<kMcFaces>, dim3(crows), dim3(kImeshThreads), 0, s, sdf, N, level, vs, table, (const int*)n_tri,
                        (int*)nullptr, (const int*)crow_base, (float*)nullptr, (int)face_cap, (const int*)first_vert, (int*)faces);
-    hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)verts, (const int*)counts, (int)vert_cap, 3);
-    hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)vert_edge, (const int*)counts, (int)vert_cap, 1);
-    hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)faces, (const int*)counts + 1, (int)face_cap, 3);
+    mesh_pad(s, verts, counts, (int)vert_cap, 3);
+    mesh_pad(s, vert_edge, counts, (int)vert_cap, 1);
+    mesh_pad(s, faces, counts + 1, (int)face_cap, 3);
     return check_launch();
 }
 
@@ -4022,13 +4055,22 @@ int arah_marching_cubes_indexed(const float* sdf, int32_t n_side, float level, c
 static bool cc_sizes_ok(int64_t n_verts, int64_t n_faces) {
     return n_verts >= 0 && n_faces >= 0 && n_verts <= (int64_t)INT32_MAX && n_faces <= (int64_t)INT32_MAX;
 }
-static size_t cc_blocks(int64_t n) { return (size_t)((n + kCcChunk - 1) / kCcChunk); }
-static int cc_grid(int64_t n) { return (int)min((int64_t)kCcMaxGrid, max((int64_t)1, (n + kCcThreads - 1) / kCcThreads)); }
+
+// dense[r] = the number of roots (root[r] == r) below r among n elements, *total = the roots: k_cc_compact<kCcRoots> counts,
+// k_mc_scan, k_cc_compact<kCcRoots> fills
+static void cc_number_roots(hipStream_t s, const int* root, int n, int* blk_count, int* blk_base, int* dense, int* total) {
+    const int nb = (int)mesh_blocks(n);
+    const int* none = nullptr;
+    mesh_compact_passes(s, nb, blk_count, blk_base, total, [&](auto fill, int* count, const int* base) {
+        hipLaunchKernelGGL((k_cc_compact<kCcRoots, decltype(fill)::value>), dim3(nb), dim3(kImeshThreads), 0, s, none, root, none, n, n,
+                           count, base, dense, (int*)nullptr);
+    });
+}
 
 size_t arah_mesh_components_scratch_bytes(int64_t n_verts, int64_t n_faces) {
     if (!cc_sizes_ok(n_verts, n_faces)) return 0;
     // the packed maximum (16 bytes), parent, root, dense, the chunks' counts and bases
-    return 16 + (3 * (size_t)n_verts + 2 * cc_blocks(n_verts)) * sizeof(int);
+    return 16 + (3 * (size_t)n_verts + 2 * mesh_blocks(n_verts)) * sizeof(int);
 }
 
 int arah_mesh_components(const int32_t* faces, int64_t n_faces, int64_t n_verts, int32_t* labels, int32_t* comp_verts,
@@ -4041,35 +4083,30 @@ int arah_mesh_components(const int32_t* faces, int64_t n_faces, int64_t n_verts,
         hipLaunchKernelGGL(k_cc_set_counts, dim3(1), dim3(64), 0, s, (int*)counts, 0, 0, -1, 3);
         return check_launch();
     }
-    const int V = (int)n_verts, F = (int)n_faces, nb = (int)cc_blocks(n_verts);
+    const int V = (int)n_verts, F = (int)n_faces, nb = (int)mesh_blocks(n_verts);
     unsigned long long* best = reinterpret_cast<unsigned long long*>(scratch);
     int* parent = reinterpret_cast<int*>(scratch) + 4;
     int* root = parent + (size_t)V;
     int* dense = root + (size_t)V;
     int* blk_count = dense + (size_t)V;
     int* blk_base = blk_count + nb;
-    const int* none = nullptr;
-    hipLaunchKernelGGL(k_cc_init, dim3(cc_grid(V)), dim3(kCcThreads), 0, s, parent, (int*)comp_verts, (int*)comp_faces, V, (int*)counts, best);
-    if (F > 0) hipLaunchKernelGGL(k_cc_hook, dim3(cc_grid(F)), dim3(kCcThreads), 0, s, (const int*)faces, F, V, parent);
-    hipLaunchKernelGGL(k_cc_flatten, dim3(cc_grid(V)), dim3(kCcThreads), 0, s, (const int*)parent, V, root);
-    hipLaunchKernelGGL((k_cc_compact<kCcRoots, false>), dim3(nb), dim3(kCcThreads), 0, s, none, (const int*)root, none, V, V, blk_count,
-                       none, (int*)nullptr, (int*)nullptr);
-    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)blk_count, nb, blk_base, (int*)counts);
-    hipLaunchKernelGGL((k_cc_compact<kCcRoots, true>), dim3(nb), dim3(kCcThreads), 0, s, none, (const int*)root, none, V, V,
-                       (int*)nullptr, (const int*)blk_base, dense, (int*)nullptr);
-    hipLaunchKernelGGL(k_cc_label, dim3(cc_grid(V)), dim3(kCcThreads), 0, s, (const int*)root, (const int*)dense, V, (int*)labels,
+    hipLaunchKernelGGL(k_cc_init, dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, parent, (int*)comp_verts, (int*)comp_faces, V, (int*)counts, best);
+    if (F > 0) hipLaunchKernelGGL(k_cc_hook, dim3(mesh_grid(F)), dim3(kImeshThreads), 0, s, (const int*)faces, F, V, parent);
+    hipLaunchKernelGGL(k_cc_flatten, dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, (const int*)parent, V, root);
+    cc_number_roots(s, root, V, blk_count, blk_base, dense, counts);
+    hipLaunchKernelGGL(k_cc_label, dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, (const int*)root, (const int*)dense, V, (int*)labels,
                        (int*)comp_verts);
     if (F > 0)
-        hipLaunchKernelGGL(k_cc_faces, dim3(cc_grid(F)), dim3(kCcThreads), 0, s, (const int*)faces, F, V, (const int*)labels,
+        hipLaunchKernelGGL(k_cc_faces, dim3(mesh_grid(F)), dim3(kImeshThreads), 0, s, (const int*)faces, F, V, (const int*)labels,
                            (int*)comp_faces, (int*)counts);
-    hipLaunchKernelGGL(k_cc_largest, dim3(cc_grid(V)), dim3(kCcThreads), 0, s, (const int*)comp_faces, (const int*)counts, best);
+    hipLaunchKernelGGL(k_cc_largest, dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, (const int*)comp_faces, (const int*)counts, best);
     hipLaunchKernelGGL(k_cc_finish, dim3(1), dim3(64), 0, s, (const unsigned long long*)best, (int*)counts);
     return check_launch();
 }
 
 size_t arah_mesh_select_scratch_bytes(int64_t n_verts, int64_t n_faces) {
     if (!cc_sizes_ok(n_verts, n_faces)) return 0;
-    return 16 + 2 * (cc_blocks(n_verts) + cc_blocks(n_faces)) * sizeof(int);   // the chunks' counts and bases, vertices and faces
+    return 16 + 2 * (mesh_blocks(n_verts) + mesh_blocks(n_faces)) * sizeof(int);   // the chunks' counts and bases, vertices and faces
 }
 
 int arah_mesh_select(const int32_t* faces, int64_t n_faces, int64_t n_verts, const int32_t* labels, const int32_t* keep,
@@ -4080,12 +4117,12 @@ int arah_mesh_select(const int32_t* faces, int64_t n_faces, int64_t n_verts, con
         return ARAH_E_BADARG;
     if (scratch_bytes < arah_mesh_select_scratch_bytes(n_verts, n_faces)) return ARAH_E_WORKSPACE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int V = (int)n_verts, F = (int)n_faces, nbv = (int)cc_blocks(n_verts), nbf = (int)cc_blocks(n_faces);
+    const int V = (int)n_verts, F = (int)n_faces, nbv = (int)mesh_blocks(n_verts), nbf = (int)mesh_blocks(n_faces);
     if (V == 0) {   // nothing can be kept; the face outputs are all guard rows
         hipLaunchKernelGGL(k_cc_set_counts, dim3(1), dim3(64), 0, s, (int*)counts, 0, 0, 0, 2);
         if (F > 0) {
-            hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)faces_out, (const int*)counts + 1, F, 3);
-            hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)face_src, (const int*)counts + 1, F, 1);
+            mesh_pad(s, faces_out, counts + 1, F, 3);
+            mesh_pad(s, face_src, counts + 1, F, 1);
         }
         return check_launch();
     }
@@ -4094,29 +4131,35 @@ int arah_mesh_select(const int32_t* faces, int64_t n_faces, int64_t n_verts, con
     int* fblk_count = vblk_base + nbv;
     int* fblk_base = fblk_count + nbf;
     const int* none = nullptr;
-    hipLaunchKernelGGL((k_cc_compact<kCcVerts, false>), dim3(nbv), dim3(kCcThreads), 0, s, none, (const int*)labels, (const int*)keep, V, V,
-                       vblk_count, none, (int*)nullptr, (int*)nullptr);
-    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)vblk_count, nbv, vblk_base, (int*)counts);
-    hipLaunchKernelGGL((k_cc_compact<kCcVerts, true>), dim3(nbv), dim3(kCcThreads), 0, s, none, (const int*)labels, (const int*)keep, V, V,
-                       (int*)nullptr, (const int*)vblk_base, (int*)vert_map, (int*)vert_src);
-    hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)vert_src, (const int*)counts, V, 1);
+    mesh_compact_passes(s, nbv, vblk_count, vblk_base, counts, [&](auto fill, int* count, const int* base) {
+        hipLaunchKernelGGL((k_cc_compact<kCcVerts, decltype(fill)::value>), dim3(nbv), dim3(kImeshThreads), 0, s, none, (const int*)labels,
+                           (const int*)keep, V, V, count, base, (int*)vert_map, (int*)vert_src);
+    });
+    mesh_pad(s, vert_src, counts, V, 1);
     if (F == 0) {
         hipLaunchKernelGGL(k_cc_set_counts, dim3(1), dim3(64), 0, s, (int*)counts + 1, 0, 0, 0, 1);
         return check_launch();
     }
-    hipLaunchKernelGGL((k_cc_compact<kCcFaces, false>), dim3(nbf), dim3(kCcThreads), 0, s, (const int*)faces, (const int*)vert_map, none, F, V,
-                       fblk_count, none, (int*)nullptr, (int*)nullptr);
-    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)fblk_count, nbf, fblk_base, (int*)counts + 1);
-    hipLaunchKernelGGL((k_cc_compact<kCcFaces, true>), dim3(nbf), dim3(kCcThreads), 0, s, (const int*)faces, (const int*)vert_map, none, F, V,
-                       (int*)nullptr, (const int*)fblk_base, (int*)faces_out, (int*)face_src);
-    hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)faces_out, (const int*)counts + 1, F, 3);
-    hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)face_src, (const int*)counts + 1, F, 1);
+    mesh_compact_passes(s, nbf, fblk_count, fblk_base, counts + 1, [&](auto fill, int* count, const int* base) {
+        hipLaunchKernelGGL((k_cc_compact<kCcFaces, decltype(fill)::value>), dim3(nbf), dim3(kImeshThreads), 0, s, (const int*)faces,
+                           (const int*)vert_map, none, F, V, count, base, (int*)faces_out, (int*)face_src);
+    });
+    mesh_pad(s, faces_out, counts + 1, F, 3);
+    mesh_pad(s, face_src, counts + 1, F, 1);
     return check_launch();
 }
 
 // ---- simplification of indexed meshes by vertex clustering (csrc/meshsimp.hpp) ---------------------------------
-struct MsLayout {
-    size_t bitmap, wcount, wbase, vkey, sums, members, best, fslot, tkeys, trows, blk_count, blk_base, bytes;
+struct MsScratch {
+    unsigned* bitmap;
+    int *wcount, *wbase, *vkey;
+    long long* sums;
+    int* members;
+    unsigned long long* best;
+    int* fslot;
+    unsigned long long* tkeys;
+    int *trows, *blk_count, *blk_base;
+    size_t bytes;
     long long n_words, n_slots;
     int nbf;
 };
@@ -4126,42 +4169,35 @@ static bool ms_sizes_ok(int64_t n_verts, int64_t n_faces, int64_t n_cells) {
            n_cells <= ((int64_t)1 << 27);
 }
 
-static MsLayout ms_layout(int64_t n_verts, int64_t n_faces, int64_t n_cells) {
-    MsLayout L{};
+static MsScratch carve_simplify(void* scratch, int64_t n_verts, int64_t n_faces, int64_t n_cells) {
+    MsScratch L{};
     L.n_words = (n_cells + 31) / 32;
     L.n_slots = 0;
     if (n_faces > 0) {   // a power of two of at least 2 F slots: the table cannot fill
         L.n_slots = 64;
         while (L.n_slots < 2 * n_faces) L.n_slots <<= 1;
     }
-    L.nbf = (int)((n_faces + kMsChunk - 1) / kMsChunk);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
-    L.bitmap = take((size_t)L.n_words * sizeof(unsigned));
-    L.wcount = take((size_t)L.n_words * sizeof(int));
-    L.wbase = take((size_t)L.n_words * sizeof(int));
-    L.vkey = take((size_t)n_verts * sizeof(int));
-    L.sums = take(3 * (size_t)n_verts * sizeof(long long));
-    L.members = take((size_t)n_verts * sizeof(int));
-    L.best = take((size_t)n_verts * sizeof(unsigned long long));
-    L.fslot = take((size_t)n_faces * sizeof(int));
-    L.tkeys = take((size_t)L.n_slots * sizeof(unsigned long long));
-    L.trows = take((size_t)L.n_slots * sizeof(int));
-    L.blk_count = take((size_t)L.nbf * sizeof(int));
-    L.blk_base = take((size_t)L.nbf * sizeof(int));
-    L.bytes = max(off, (size_t)256);
+    L.nbf = (int)mesh_blocks(n_faces);
+    MeshCarver c(scratch);
+    L.bitmap = c.take<unsigned>((size_t)L.n_words);
+    L.wcount = c.take<int>((size_t)L.n_words);
+    L.wbase = c.take<int>((size_t)L.n_words);
+    L.vkey = c.take<int>((size_t)n_verts);
+    L.sums = c.take<long long>(3 * (size_t)n_verts);
+    L.members = c.take<int>((size_t)n_verts);
+    L.best = c.take<unsigned long long>((size_t)n_verts);
+    L.fslot = c.take<int>((size_t)n_faces);
+    L.tkeys = c.take<unsigned long long>((size_t)L.n_slots);
+    L.trows = c.take<int>((size_t)L.n_slots);
+    L.blk_count = c.take<int>((size_t)L.nbf);
+    L.blk_base = c.take<int>((size_t)L.nbf);
+    L.bytes = c.bytes();
     return L;
 }
 
-static int ms_grid(int64_t n) { return (int)min((int64_t)kMsMaxGrid, max((int64_t)1, (n + kMsThreads - 1) / kMsThreads)); }
-
 size_t arah_mesh_simplify_scratch_bytes(int64_t n_verts, int64_t n_faces, int64_t n_cells) {
     if (!ms_sizes_ok(n_verts, n_faces, n_cells)) return 0;
-    return ms_layout(n_verts, n_faces, n_cells).bytes;
+    return carve_simplify(nullptr, n_verts, n_faces, n_cells).bytes;
 }
 
 int arah_mesh_simplify(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float origin[3], float cell,
@@ -4181,15 +4217,15 @@ int arah_mesh_simplify(const float* verts, int64_t n_verts, const int32_t* faces
     if (position != 0 && position != 1) return ARAH_E_BADARG;
     if ((n_verts > 0 && (!verts || !verts_out || !vert_src || !vert_map)) || (n_faces > 0 && (!faces || !faces_out || !face_src)))
         return ARAH_E_BADARG;
-    const MsLayout L = ms_layout(n_verts, n_faces, n_cells);
+    const MsScratch L = carve_simplify(scratch, n_verts, n_faces, n_cells);
     if (scratch_bytes < L.bytes) return ARAH_E_WORKSPACE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int V = (int)n_verts, F = (int)n_faces;
     if (V == 0) {   // no vertex, so no cluster, and every face names a vertex that is not there
         hipLaunchKernelGGL(k_ms_set_empty, dim3(1), dim3(64), 0, s, (int*)counts, F);
         if (F > 0) {
-            hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)faces_out, (const int*)counts + 1, F, 3);
-            hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)face_src, (const int*)counts + 1, F, 1);
+            mesh_pad(s, faces_out, counts + 1, F, 3);
+            mesh_pad(s, face_src, counts + 1, F, 1);
         }
         return check_launch();
     }
@@ -4200,77 +4236,57 @@ int arah_mesh_simplify(const float* verts, int64_t n_verts, const int32_t* faces
     }
     g.inv_cell = inv_cell;
     g.scale = fix_scale;
-    char* base = reinterpret_cast<char*>(scratch);
-    unsigned* bitmap = reinterpret_cast<unsigned*>(base + L.bitmap);
-    int* wcount = reinterpret_cast<int*>(base + L.wcount);
-    int* wbase = reinterpret_cast<int*>(base + L.wbase);
-    int* vkey = reinterpret_cast<int*>(base + L.vkey);
-    long long* sums = reinterpret_cast<long long*>(base + L.sums);
-    int* members = reinterpret_cast<int*>(base + L.members);
-    unsigned long long* best = reinterpret_cast<unsigned long long*>(base + L.best);
-    int* fslot = reinterpret_cast<int*>(base + L.fslot);
-    unsigned long long* tkeys = reinterpret_cast<unsigned long long*>(base + L.tkeys);
-    int* trows = reinterpret_cast<int*>(base + L.trows);
-    int* blk_count = reinterpret_cast<int*>(base + L.blk_count);
-    int* blk_base = reinterpret_cast<int*>(base + L.blk_base);
     const long long n_slots = dedup ? L.n_slots : 0;   // without dedup the table is neither cleared nor touched
-    hipLaunchKernelGGL(k_ms_init, dim3(ms_grid(max(max(L.n_words, (long long)V), n_slots))), dim3(kMsThreads), 0, s, bitmap, L.n_words,
-                       sums, members, best, V, tkeys, trows, n_slots, (int*)counts);
-    hipLaunchKernelGGL(k_ms_mark, dim3(ms_grid(V)), dim3(kMsThreads), 0, s, verts, V, g, vkey, bitmap);
-    hipLaunchKernelGGL(k_ms_popc, dim3(ms_grid(L.n_words)), dim3(kMsThreads), 0, s, (const unsigned*)bitmap, L.n_words, wcount);
-    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)wcount, (int)L.n_words, wbase, (int*)counts);
-    hipLaunchKernelGGL(k_ms_accum, dim3(ms_grid(V)), dim3(kMsThreads), 0, s, verts, V, g, (const int*)vkey, (const unsigned*)bitmap,
-                       (const int*)wbase, (int*)vert_map, sums, members);
-    hipLaunchKernelGGL(k_ms_pick, dim3(ms_grid(V)), dim3(kMsThreads), 0, s, verts, V, g, (const int*)vert_map, (const long long*)sums,
-                       (const int*)members, best);
-    hipLaunchKernelGGL(k_ms_finish, dim3(ms_grid(V)), dim3(kMsThreads), 0, s, verts, V, g, (int)position, (int)(dedup != 0),
-                       (const long long*)sums, (const int*)members, (const unsigned long long*)best, (int*)counts, verts_out,
+    hipLaunchKernelGGL(k_ms_init, dim3(mesh_grid(max(max(L.n_words, (long long)V), n_slots))), dim3(kImeshThreads), 0, s, L.bitmap,
+                       L.n_words, L.sums, L.members, L.best, V, L.tkeys, L.trows, n_slots, (int*)counts);
+    hipLaunchKernelGGL(k_ms_mark, dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, verts, V, g, L.vkey, L.bitmap);
+    hipLaunchKernelGGL(k_ms_popc, dim3(mesh_grid(L.n_words)), dim3(kImeshThreads), 0, s, (const unsigned*)L.bitmap, L.n_words, L.wcount);
+    mesh_scan(s, L.wcount, (int)L.n_words, L.wbase, counts);
+    hipLaunchKernelGGL(k_ms_accum, dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, verts, V, g, (const int*)L.vkey, (const unsigned*)L.bitmap,
+                       (const int*)L.wbase, (int*)vert_map, L.sums, L.members);
+    hipLaunchKernelGGL(k_ms_pick, dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, verts, V, g, (const int*)vert_map, (const long long*)L.sums,
+                       (const int*)L.members, L.best);
+    hipLaunchKernelGGL(k_ms_finish, dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, verts, V, g, (int)position, (int)(dedup != 0),
+                       (const long long*)L.sums, (const int*)L.members, (const unsigned long long*)L.best, (int*)counts, verts_out,
                        (int*)vert_src);
     if (F == 0) return check_launch();
     const int dd = dedup != 0;
-    hipLaunchKernelGGL(k_ms_classify, dim3(ms_grid(F)), dim3(kMsThreads), 0, s, (const int*)faces, F, V, (const int*)vert_map, dd, tkeys,
-                       trows, n_slots, fslot, (int*)counts);
-    hipLaunchKernelGGL((k_ms_compact<false>), dim3(L.nbf), dim3(kMsThreads), 0, s, (const int*)faces, F, (const int*)vert_map,
-                       (const int*)fslot, (const int*)trows, dd, blk_count, (const int*)nullptr, (int*)nullptr, (int*)nullptr,
-                       (int*)counts);
-    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)blk_count, L.nbf, blk_base, (int*)counts + 1);
-    hipLaunchKernelGGL((k_ms_compact<true>), dim3(L.nbf), dim3(kMsThreads), 0, s, (const int*)faces, F, (const int*)vert_map,
-                       (const int*)fslot, (const int*)trows, dd, (int*)nullptr, (const int*)blk_base, (int*)faces_out, (int*)face_src,
-                       (int*)counts);
+    hipLaunchKernelGGL(k_ms_classify, dim3(mesh_grid(F)), dim3(kImeshThreads), 0, s, (const int*)faces, F, V, (const int*)vert_map, dd, L.tkeys,
+                       L.trows, n_slots, L.fslot, (int*)counts);
+    mesh_compact_passes(s, L.nbf, L.blk_count, L.blk_base, counts + 1, [&](auto fill, int* count, const int* base) {
+        hipLaunchKernelGGL((k_ms_compact<decltype(fill)::value>), dim3(L.nbf), dim3(kImeshThreads), 0, s, (const int*)faces, F,
+                           (const int*)vert_map, (const int*)L.fslot, (const int*)L.trows, dd, count, base, (int*)faces_out,
+                           (int*)face_src, (int*)counts);
+    });
     return check_launch();
 }
 
 // ---- adjacency of indexed meshes, per-vertex normals, umbrella smoothing (csrc/meshadj.hpp) -----------------------------------
-struct MaLayout {
-    size_t deg, cursor, vf_raw, nb_raw, nb_sorted, bytes;
+struct MaScratch {
+    int *deg, *cursor;
+    unsigned *vf_raw, *nb_raw, *nb_sorted;
+    size_t bytes;   // in size_t throughout: the largest mesh needs more than 2^32 bytes
 };
 
 static bool ma_sizes_ok(int64_t n_verts, int64_t n_faces) {
     return n_verts >= 0 && n_faces >= 0 && n_verts <= (int64_t)INT32_MAX && n_faces <= ((int64_t)1 << 28);
 }
 
-static MaLayout ma_layout(int64_t n_verts, int64_t n_faces) {
-    MaLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
-    L.deg = take((size_t)n_verts * sizeof(int));
-    L.cursor = take((size_t)n_verts * sizeof(int));
-    L.vf_raw = take(3 * (size_t)n_faces * sizeof(unsigned));
-    L.nb_raw = take(6 * (size_t)n_faces * sizeof(unsigned));
-    L.nb_sorted = take(6 * (size_t)n_faces * sizeof(unsigned));
-    L.bytes = off > 256 ? off : (size_t)256;   // in size_t throughout: the largest mesh needs more than 2^32 bytes
-    return L;
+static MaScratch carve_adjacency(void* scratch, int64_t n_verts, int64_t n_faces) {
+    MaScratch w{};
+    MeshCarver c(scratch);
+    w.deg = c.take<int>((size_t)n_verts);
+    w.cursor = c.take<int>((size_t)n_verts);
+    w.vf_raw = c.take<unsigned>(3 * (size_t)n_faces);
+    w.nb_raw = c.take<unsigned>(6 * (size_t)n_faces);
+    w.nb_sorted = c.take<unsigned>(6 * (size_t)n_faces);
+    w.bytes = c.bytes();
+    return w;
 }
-
-static int ma_grid(int64_t n) { return (int)min((int64_t)kMaMaxGrid, max((int64_t)1, (n + kMaThreads - 1) / kMaThreads)); }
 
 size_t arah_mesh_adjacency_scratch_bytes(int64_t n_verts, int64_t n_faces) {
     if (!ma_sizes_ok(n_verts, n_faces)) return 0;
-    return ma_layout(n_verts, n_faces).bytes;
+    return carve_adjacency(nullptr, n_verts, n_faces).bytes;
 }
 
 int arah_mesh_adjacency(const int32_t* faces, int64_t n_faces, int64_t n_verts, int32_t* vf_start, int32_t* vf, int32_t* nbr_start,
@@ -4278,43 +4294,39 @@ int arah_mesh_adjacency(const int32_t* faces, int64_t n_faces, int64_t n_verts, 
                         size_t scratch_bytes, void* stream) {
     if (!ma_sizes_ok(n_verts, n_faces) || !vf_start || !nbr_start || !counts || !scratch) return ARAH_E_BADARG;
     if ((n_faces > 0 && (!faces || !vf || !nbr || !nbr_out || !nbr_in)) || (n_verts > 0 && !vert_flags)) return ARAH_E_BADARG;
-    const MaLayout L = ma_layout(n_verts, n_faces);
-    if (scratch_bytes < L.bytes) return ARAH_E_WORKSPACE;
+    const MaScratch w = carve_adjacency(scratch, n_verts, n_faces);
+    if (scratch_bytes < w.bytes) return ARAH_E_WORKSPACE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int V = (int)n_verts, F = (int)n_faces;
-    char* base = reinterpret_cast<char*>(scratch);
-    int* deg = reinterpret_cast<int*>(base + L.deg);
-    int* cursor = reinterpret_cast<int*>(base + L.cursor);
-    unsigned* vf_raw = reinterpret_cast<unsigned*>(base + L.vf_raw);
-    unsigned* nb_raw = reinterpret_cast<unsigned*>(base + L.nb_raw);
-    unsigned* nb_sorted = reinterpret_cast<unsigned*>(base + L.nb_sorted);
+    int *deg = w.deg, *cursor = w.cursor;
+    unsigned *vf_raw = w.vf_raw, *nb_raw = w.nb_raw, *nb_sorted = w.nb_sorted;
     // an empty mesh runs the same launches over nothing: the scans write vf_start[V] = nbr_start[V] = 0
-    hipLaunchKernelGGL(k_ma_init, dim3(ma_grid(V)), dim3(kMaThreads), 0, s, deg, cursor, V, (int*)counts);
+    hipLaunchKernelGGL(k_ma_init, dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, deg, cursor, V, (int*)counts);
     if (F > 0 && V > 0)
-        hipLaunchKernelGGL(k_ma_count, dim3(ma_grid(F)), dim3(kMaThreads), 0, s, (const int*)faces, F, V, deg, (int*)counts);
-    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)deg, V, (int*)vf_start, (int*)vf_start + V);
+        hipLaunchKernelGGL(k_ma_count, dim3(mesh_grid(F)), dim3(kImeshThreads), 0, s, (const int*)faces, F, V, deg, (int*)counts);
+    mesh_scan(s, deg, V, vf_start, vf_start + V);
     if (F > 0 && V > 0) {
-        hipLaunchKernelGGL(k_ma_fill, dim3(ma_grid(F)), dim3(kMaThreads), 0, s, (const int*)faces, F, V, (const int*)vf_start, cursor,
+        hipLaunchKernelGGL(k_ma_fill, dim3(mesh_grid(F)), dim3(kImeshThreads), 0, s, (const int*)faces, F, V, (const int*)vf_start, cursor,
                            vf_raw, nb_raw);
-        hipLaunchKernelGGL(k_ma_sort_short, dim3(ma_grid(V)), dim3(kMaThreads), 0, s, (const int*)vf_start, V, (const unsigned*)vf_raw,
+        hipLaunchKernelGGL(k_ma_sort_short, dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, (const int*)vf_start, V, (const unsigned*)vf_raw,
                            (unsigned*)vf, (const unsigned*)nb_raw, nb_sorted);
-        hipLaunchKernelGGL(k_ma_sort_long, dim3(min(V, kMaLongGrid)), dim3(kMaThreads), 0, s, (const int*)vf_start, V,
+        hipLaunchKernelGGL(k_ma_sort_long, dim3(min(V, kMaLongGrid)), dim3(kImeshThreads), 0, s, (const int*)vf_start, V,
                            (const unsigned*)vf_raw, (unsigned*)vf, (const unsigned*)nb_raw, nb_sorted);
     }
     if (V > 0)
-        hipLaunchKernelGGL((k_ma_nbr<false>), dim3(ma_grid(V)), dim3(kMaThreads), 0, s, (const int*)vf_start, V, (const unsigned*)nb_sorted,
+        hipLaunchKernelGGL((k_ma_nbr<false>), dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, (const int*)vf_start, V, (const unsigned*)nb_sorted,
                            deg, (const int*)nullptr, (int*)nullptr, (int*)nullptr, (int*)nullptr, (unsigned char*)nullptr,
                            (int*)counts);
-    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)deg, V, (int*)nbr_start, (int*)nbr_start + V);
+    mesh_scan(s, deg, V, nbr_start, nbr_start + V);
     if (V > 0)
-        hipLaunchKernelGGL((k_ma_nbr<true>), dim3(ma_grid(V)), dim3(kMaThreads), 0, s, (const int*)vf_start, V, (const unsigned*)nb_sorted,
+        hipLaunchKernelGGL((k_ma_nbr<true>), dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, (const int*)vf_start, V, (const unsigned*)nb_sorted,
                            (int*)nullptr, (const int*)nbr_start, (int*)nbr, (int*)nbr_out, (int*)nbr_in, (unsigned char*)vert_flags,
                            (int*)counts);
     if (F > 0) {
-        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)vf, (const int*)vf_start + V, 3 * F, 1);
-        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)nbr, (const int*)nbr_start + V, 6 * F, 1);
-        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)nbr_out, (const int*)nbr_start + V, 6 * F, 1);
-        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)nbr_in, (const int*)nbr_start + V, 6 * F, 1);
+        mesh_pad(s, vf, vf_start + V, 3 * F, 1);
+        mesh_pad(s, nbr, nbr_start + V, 6 * F, 1);
+        mesh_pad(s, nbr_out, nbr_start + V, 6 * F, 1);
+        mesh_pad(s, nbr_in, nbr_start + V, 6 * F, 1);
     }
     hipLaunchKernelGGL(k_ma_finish, dim3(1), dim3(64), 0, s, (int*)counts, V);
     return check_launch();
@@ -4325,7 +4337,7 @@ int arah_mesh_vertex_normals(const float* verts, int64_t n_verts, const int32_t*
     if (!ma_sizes_ok(n_verts, n_faces) || !vf_start) return ARAH_E_BADARG;
     if ((n_verts > 0 && (!verts || !normal_sum || !normals)) || (n_faces > 0 && (!faces || !vf))) return ARAH_E_BADARG;
     if (n_verts == 0) return ARAH_OK;
-    hipLaunchKernelGGL(k_ma_normals, dim3(ma_grid(n_verts)), dim3(kMaThreads), 0, reinterpret_cast<hipStream_t>(stream), verts,
+    hipLaunchKernelGGL(k_ma_normals, dim3(mesh_grid(n_verts)), dim3(kImeshThreads), 0, reinterpret_cast<hipStream_t>(stream), verts,
                        (int)n_verts, (const int*)faces, (int)n_faces, (const int*)vf_start, (const int*)vf, normal_sum, normals);
     return check_launch();
 }
@@ -4339,13 +4351,13 @@ int arah_mesh_smooth(const float* verts, int64_t n_verts, const int32_t* nbr_sta
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int V = (int)n_verts;
     if (n_steps == 0) {
-        hipLaunchKernelGGL(k_ma_copy, dim3(ma_grid(3 * n_verts)), dim3(kMaThreads), 0, s, verts, 3 * (long long)n_verts, verts_out);
+        hipLaunchKernelGGL(k_ma_copy, dim3(mesh_grid(3 * n_verts)), dim3(kImeshThreads), 0, s, verts, 3 * (long long)n_verts, verts_out);
         return check_launch();
     }
     const float* src = verts;
     for (int32_t i = 0; i < n_steps; ++i) {   // the last step writes verts_out, the one before tmp, and so on back
         float* dst = ((n_steps - 1 - i) & 1) ? tmp : verts_out;
-        hipLaunchKernelGGL(k_ma_smooth, dim3(ma_grid(V)), dim3(kMaThreads), 0, s, src, V, (const int*)nbr_start, (const int*)nbr,
+        hipLaunchKernelGGL(k_ma_smooth, dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, src, V, (const int*)nbr_start, (const int*)nbr,
                            (const unsigned char*)vert_flags, (double)factors[i & 1], (int)(pin != 0), dst);
         src = dst;
     }
@@ -4353,39 +4365,34 @@ int arah_mesh_smooth(const float* verts, int64_t n_verts, const int32_t* nbr_sta
 }
 
 // ---- orientation, boundary loops and hole filling of indexed meshes (csrc/meshorient.hpp) ---------------------------------------
-struct MoLayout {
-    size_t parent, froot, dense, ones, fstate, blk_count, blk_base, bytes;
+struct MoScratch {
+    int *parent, *froot, *dense, *ones;
+    unsigned char* fstate;
+    int *blk_count, *blk_base;
+    size_t bytes;
 };
-
-static size_t mo_blocks(int64_t n) { return (size_t)((n + kMoChunk - 1) / kMoChunk); }
-static int mo_grid(int64_t n) { return (int)min((int64_t)kMoMaxGrid, max((int64_t)1, (n + kMoThreads - 1) / kMoThreads)); }
 
 static bool mo_quant_ok(const float origin[3], double scale) {
     return origin && std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]) && scale > 0.0 && std::isfinite(scale);
 }
 
-static MoLayout mo_layout(int64_t n_faces) {
-    MoLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
-    L.parent = take(2 * (size_t)n_faces * sizeof(int));
-    L.froot = take((size_t)n_faces * sizeof(int));
-    L.dense = take((size_t)n_faces * sizeof(int));
-    L.ones = take((size_t)n_faces * sizeof(int));
-    L.fstate = take((size_t)n_faces);
-    L.blk_count = take(cc_blocks(n_faces) * sizeof(int));
-    L.blk_base = take(cc_blocks(n_faces) * sizeof(int));
-    L.bytes = off > 256 ? off : (size_t)256;
-    return L;
+static MoScratch carve_orient(void* scratch, int64_t n_faces) {
+    MoScratch w{};
+    MeshCarver c(scratch);
+    w.parent = c.take<int>(2 * (size_t)n_faces);
+    w.froot = c.take<int>((size_t)n_faces);
+    w.dense = c.take<int>((size_t)n_faces);
+    w.ones = c.take<int>((size_t)n_faces);
+    w.fstate = c.take<unsigned char>((size_t)n_faces);
+    w.blk_count = c.take<int>(mesh_blocks(n_faces));
+    w.blk_base = c.take<int>(mesh_blocks(n_faces));
+    w.bytes = c.bytes();
+    return w;
 }
 
 size_t arah_mesh_orient_scratch_bytes(int64_t n_verts, int64_t n_faces) {
     if (!ma_sizes_ok(n_verts, n_faces)) return 0;
-    return mo_layout(n_faces).bytes;
+    return carve_orient(nullptr, n_faces).bytes;
 }
 
 int arah_mesh_orient(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int32_t* vf_start, const int32_t* vf,
@@ -4400,78 +4407,63 @@ int arah_mesh_orient(const float* verts, int64_t n_verts, const int32_t* faces, 
     if (n_faces > 0 && (!faces || !vf || !nbr || !nbr_out || !nbr_in || !flip || !face_comp || !faces_out || !comp_faces || !comp_flags ||
                         !comp_vol_hi || !comp_vol_lo))
         return ARAH_E_BADARG;
-    const MoLayout L = mo_layout(n_faces);
-    if (scratch_bytes < L.bytes) return ARAH_E_WORKSPACE;
+    const MoScratch w = carve_orient(scratch, n_faces);
+    if (scratch_bytes < w.bytes) return ARAH_E_WORKSPACE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int V = (int)n_verts, F = (int)n_faces, nb = (int)cc_blocks(n_faces);
-    char* base = reinterpret_cast<char*>(scratch);
-    int* parent = reinterpret_cast<int*>(base + L.parent);
-    int* froot = reinterpret_cast<int*>(base + L.froot);
-    int* dense = reinterpret_cast<int*>(base + L.dense);
-    int* ones = reinterpret_cast<int*>(base + L.ones);
-    unsigned char* fstate = reinterpret_cast<unsigned char*>(base + L.fstate);
-    int* blk_count = reinterpret_cast<int*>(base + L.blk_count);
-    int* blk_base = reinterpret_cast<int*>(base + L.blk_base);
-    const int* none = nullptr;
+    const int V = (int)n_verts, F = (int)n_faces;
+    int *parent = w.parent, *froot = w.froot, *dense = w.dense, *ones = w.ones;
+    unsigned char* fstate = w.fstate;
     // no face: the init alone, which clears the counts
-    hipLaunchKernelGGL(k_mo_init, dim3(mo_grid(2 * (int64_t)F)), dim3(kMoThreads), 0, s, parent, F, (int*)comp_faces, (int*)comp_flags, ones,
+    hipLaunchKernelGGL(k_mo_init, dim3(mesh_grid(2 * (int64_t)F)), dim3(kImeshThreads), 0, s, parent, F, (int*)comp_faces, (int*)comp_flags, ones,
                        (long long*)comp_vol_hi, (long long*)comp_vol_lo, (int*)counts);
     if (F == 0) return check_launch();
     if (V > 0)   // without a vertex no face is valid: nothing indexes the empty CSRs
-        hipLaunchKernelGGL(k_mo_pairs, dim3(mo_grid(3 * (int64_t)F)), dim3(kMoThreads), 0, s, (const int*)faces, F, V, (const int*)vf_start,
+        hipLaunchKernelGGL(k_mo_pairs, dim3(mesh_grid(3 * (int64_t)F)), dim3(kImeshThreads), 0, s, (const int*)faces, F, V, (const int*)vf_start,
                            (const int*)vf, (const int*)nbr_start, (const int*)nbr, (const int*)nbr_out, (const int*)nbr_in, parent);
-    hipLaunchKernelGGL(k_mo_flatten, dim3(mo_grid(F)), dim3(kMoThreads), 0, s, (const int*)faces, F, V, (const int*)parent, froot, fstate);
-    hipLaunchKernelGGL((k_cc_compact<kCcRoots, false>), dim3(nb), dim3(kCcThreads), 0, s, none, (const int*)froot, none, F, F, blk_count,
-                       none, (int*)nullptr, (int*)nullptr);
-    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)blk_count, nb, blk_base, (int*)counts + 1);
-    hipLaunchKernelGGL((k_cc_compact<kCcRoots, true>), dim3(nb), dim3(kCcThreads), 0, s, none, (const int*)froot, none, F, F, (int*)nullptr,
-                       (const int*)blk_base, dense, (int*)nullptr);
-    hipLaunchKernelGGL(k_mo_label, dim3(mo_grid(F)), dim3(kMoThreads), 0, s, (const int*)froot, (const unsigned char*)fstate,
+    hipLaunchKernelGGL(k_mo_flatten, dim3(mesh_grid(F)), dim3(kImeshThreads), 0, s, (const int*)faces, F, V, (const int*)parent, froot, fstate);
+    cc_number_roots(s, froot, F, w.blk_count, w.blk_base, dense, counts + 1);
+    hipLaunchKernelGGL(k_mo_label, dim3(mesh_grid(F)), dim3(kImeshThreads), 0, s, (const int*)froot, (const unsigned char*)fstate,
                        (const int*)dense, F, (int*)face_comp, (int*)comp_faces, ones, (int*)comp_flags, (int*)counts);
     if (by_volume && V > 0) {
         MoQuant g;
         for (int a = 0; a < 3; ++a) g.origin[a] = origin[a];
         g.scale = scale;
-        hipLaunchKernelGGL(k_mo_volume, dim3(mo_grid(F)), dim3(kMoThreads), 0, s, verts, (const int*)faces, F, V, g, (const int*)face_comp,
+        hipLaunchKernelGGL(k_mo_volume, dim3(mesh_grid(F)), dim3(kImeshThreads), 0, s, verts, (const int*)faces, F, V, g, (const int*)face_comp,
                            (const unsigned char*)fstate, (long long*)comp_vol_hi, (long long*)comp_vol_lo);
     }
-    hipLaunchKernelGGL(k_mo_decide, dim3(mo_grid(F)), dim3(kMoThreads), 0, s, (const int*)comp_faces, (const int*)ones,
+    hipLaunchKernelGGL(k_mo_decide, dim3(mesh_grid(F)), dim3(kImeshThreads), 0, s, (const int*)comp_faces, (const int*)ones,
                        (const long long*)comp_vol_hi, (const long long*)comp_vol_lo, (int)policy, (int*)comp_flags, (int*)counts);
-    hipLaunchKernelGGL(k_mo_apply, dim3(mo_grid(F)), dim3(kMoThreads), 0, s, (const int*)faces, F, (const int*)face_comp,
+    hipLaunchKernelGGL(k_mo_apply, dim3(mesh_grid(F)), dim3(kImeshThreads), 0, s, (const int*)faces, F, (const int*)face_comp,
                        (const unsigned char*)fstate, (const int*)comp_flags, (unsigned char*)flip, (int*)faces_out, (int*)counts);
     return check_launch();
 }
 
-struct MlLayout {
-    size_t parent, root, dense, vout, vin, bad, eblk_count, eblk_base, vblk_count, vblk_base, bytes;
+struct MlScratch {
+    int *parent, *root, *dense, *vout, *vin, *bad, *eblk_count, *eblk_base, *vblk_count, *vblk_base;
+    size_t bytes;
 };
 
-static MlLayout ml_layout(int64_t n_verts, int64_t n_faces) {
-    MlLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
-    const size_t v = (size_t)n_verts * sizeof(int);
-    L.parent = take(v);
-    L.root = take(v);
-    L.dense = take(v);
-    L.vout = take(v);
-    L.vin = take(v);
-    L.bad = take(v);
-    L.eblk_count = take(mo_blocks(3 * n_faces) * sizeof(int));
-    L.eblk_base = take(mo_blocks(3 * n_faces) * sizeof(int));
-    L.vblk_count = take(cc_blocks(n_verts) * sizeof(int));
-    L.vblk_base = take(cc_blocks(n_verts) * sizeof(int));
-    L.bytes = off > 256 ? off : (size_t)256;
-    return L;
+static MlScratch carve_boundary_loops(void* scratch, int64_t n_verts, int64_t n_faces) {
+    MlScratch w{};
+    MeshCarver c(scratch);
+    const size_t v = (size_t)n_verts;
+    w.parent = c.take<int>(v);
+    w.root = c.take<int>(v);
+    w.dense = c.take<int>(v);
+    w.vout = c.take<int>(v);
+    w.vin = c.take<int>(v);
+    w.bad = c.take<int>(v);
+    w.eblk_count = c.take<int>(mesh_blocks(3 * n_faces));
+    w.eblk_base = c.take<int>(mesh_blocks(3 * n_faces));
+    w.vblk_count = c.take<int>(mesh_blocks(n_verts));
+    w.vblk_base = c.take<int>(mesh_blocks(n_verts));
+    w.bytes = c.bytes();
+    return w;
 }
 
 size_t arah_mesh_boundary_loops_scratch_bytes(int64_t n_verts, int64_t n_faces) {
     if (!ma_sizes_ok(n_verts, n_faces)) return 0;
-    return ml_layout(n_verts, n_faces).bytes;
+    return carve_boundary_loops(nullptr, n_verts, n_faces).bytes;
 }
 
 int arah_mesh_boundary_loops(const int32_t* faces, int64_t n_faces, int64_t n_verts, const int32_t* nbr_start, const int32_t* nbr,
@@ -4482,28 +4474,17 @@ int arah_mesh_boundary_loops(const int32_t* faces, int64_t n_faces, int64_t n_ve
     if ((n_faces > 0 && (!faces || !nbr || !nbr_out || !nbr_in || !edges || !edge_face || !edge_loop)) ||
         (n_verts > 0 && (!loop_edges || !loop_simple || !loop_vert)))
         return ARAH_E_BADARG;
-    const MlLayout L = ml_layout(n_verts, n_faces);
-    if (scratch_bytes < L.bytes) return ARAH_E_WORKSPACE;
+    const MlScratch w = carve_boundary_loops(scratch, n_verts, n_faces);
+    if (scratch_bytes < w.bytes) return ARAH_E_WORKSPACE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int V = (int)n_verts, F = (int)n_faces, E = 3 * F, nbe = (int)mo_blocks(3 * n_faces), nbv = (int)cc_blocks(n_verts);
-    char* base = reinterpret_cast<char*>(scratch);
-    int* parent = reinterpret_cast<int*>(base + L.parent);
-    int* root = reinterpret_cast<int*>(base + L.root);
-    int* dense = reinterpret_cast<int*>(base + L.dense);
-    int* vout = reinterpret_cast<int*>(base + L.vout);
-    int* vin = reinterpret_cast<int*>(base + L.vin);
-    int* bad = reinterpret_cast<int*>(base + L.bad);
-    int* eblk_count = reinterpret_cast<int*>(base + L.eblk_count);
-    int* eblk_base = reinterpret_cast<int*>(base + L.eblk_base);
-    int* vblk_count = reinterpret_cast<int*>(base + L.vblk_count);
-    int* vblk_base = reinterpret_cast<int*>(base + L.vblk_base);
-    const int* none = nullptr;
-    hipLaunchKernelGGL(k_mo_loop_init, dim3(mo_grid(V)), dim3(kMoThreads), 0, s, parent, vout, vin, bad, V, (int*)loop_edges,
+    const int V = (int)n_verts, F = (int)n_faces, E = 3 * F, nbe = (int)mesh_blocks(3 * n_faces);
+    int *parent = w.parent, *root = w.root, *dense = w.dense, *vout = w.vout, *vin = w.vin, *bad = w.bad;
+    hipLaunchKernelGGL(k_mo_loop_init, dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, parent, vout, vin, bad, V, (int*)loop_edges,
                        (unsigned char*)loop_simple, (int*)loop_vert, (int*)counts);
     if (F > 0) {   // the three per-edge arrays are all guard rows until the fill pass writes the first counts[0] of them
-        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)edges, (const int*)counts, E, 2);
-        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)edge_face, (const int*)counts, E, 1);
-        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)edge_loop, (const int*)counts, E, 1);
+        mesh_pad(s, edges, counts, E, 2);
+        mesh_pad(s, edge_face, counts, E, 1);
+        mesh_pad(s, edge_loop, counts, E, 1);
     }
     if (F == 0 || V == 0) return check_launch();
     MoCompact p{};
@@ -4519,51 +4500,45 @@ int arah_mesh_boundary_loops(const int32_t* faces, int64_t n_faces, int64_t n_ve
     p.vout = vout;
     p.vin = vin;
     p.parent = parent;
-    hipLaunchKernelGGL((k_mo_compact<kMoBoundary, false>), dim3(nbe), dim3(kMoThreads), 0, s, p, E, none, eblk_count, none);
-    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)eblk_count, nbe, eblk_base, (int*)counts);
-    hipLaunchKernelGGL((k_mo_compact<kMoBoundary, true>), dim3(nbe), dim3(kMoThreads), 0, s, p, E, none, (int*)nullptr, (const int*)eblk_base);
-    hipLaunchKernelGGL(k_mo_loop_flatten, dim3(mo_grid(V)), dim3(kMoThreads), 0, s, (const int*)parent, (const int*)vout, (const int*)vin, V,
+    mesh_compact_passes(s, nbe, w.eblk_count, w.eblk_base, counts, [&](auto fill, int* count, const int* base) {
+        hipLaunchKernelGGL((k_mo_compact<kMoBoundary, decltype(fill)::value>), dim3(nbe), dim3(kImeshThreads), 0, s, p, E,
+                           (const int*)nullptr, count, base);
+    });
+    hipLaunchKernelGGL(k_mo_loop_flatten, dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, (const int*)parent, (const int*)vout, (const int*)vin, V,
                        root);
-    hipLaunchKernelGGL((k_cc_compact<kCcRoots, false>), dim3(nbv), dim3(kCcThreads), 0, s, none, (const int*)root, none, V, V, vblk_count,
-                       none, (int*)nullptr, (int*)nullptr);
-    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)vblk_count, nbv, vblk_base, (int*)counts + 1);
-    hipLaunchKernelGGL((k_cc_compact<kCcRoots, true>), dim3(nbv), dim3(kCcThreads), 0, s, none, (const int*)root, none, V, V, (int*)nullptr,
-                       (const int*)vblk_base, dense, (int*)nullptr);
-    hipLaunchKernelGGL(k_mo_loop_verts, dim3(mo_grid(V)), dim3(kMoThreads), 0, s, (const int*)root, (const int*)dense, (const int*)vout,
+    cc_number_roots(s, root, V, w.vblk_count, w.vblk_base, dense, counts + 1);
+    hipLaunchKernelGGL(k_mo_loop_verts, dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, (const int*)root, (const int*)dense, (const int*)vout,
                        (const int*)vin, V, (int*)loop_vert, bad);
-    hipLaunchKernelGGL(k_mo_loop_edges, dim3(mo_grid(E)), dim3(kMoThreads), 0, s, (const int*)edges, E, (const int*)root, (const int*)dense,
+    hipLaunchKernelGGL(k_mo_loop_edges, dim3(mesh_grid(E)), dim3(kImeshThreads), 0, s, (const int*)edges, E, (const int*)root, (const int*)dense,
                        (const int*)counts, (int*)edge_loop, (int*)loop_edges);
-    hipLaunchKernelGGL(k_mo_loop_finish, dim3(mo_grid(V)), dim3(kMoThreads), 0, s, (const int*)bad, V, (unsigned char*)loop_simple,
+    hipLaunchKernelGGL(k_mo_loop_finish, dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, (const int*)bad, V, (unsigned char*)loop_simple,
                        (int*)counts);
     return check_launch();
 }
 
-struct MfLayout {
-    size_t sums, nonfinite, lrank, lblk_count, lblk_base, eblk_count, eblk_base, bytes;
+struct MfScratch {
+    long long* sums;
+    int *nonfinite, *lrank, *lblk_count, *lblk_base, *eblk_count, *eblk_base;
+    size_t bytes;
 };
 
-static MfLayout mf_layout(int64_t n_verts, int64_t n_faces) {
-    MfLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
-    L.sums = take(3 * (size_t)n_verts * sizeof(long long));
-    L.nonfinite = take((size_t)n_verts * sizeof(int));
-    L.lrank = take((size_t)n_verts * sizeof(int));
-    L.lblk_count = take(mo_blocks(n_verts) * sizeof(int));
-    L.lblk_base = take(mo_blocks(n_verts) * sizeof(int));
-    L.eblk_count = take(mo_blocks(3 * n_faces) * sizeof(int));
-    L.eblk_base = take(mo_blocks(3 * n_faces) * sizeof(int));
-    L.bytes = off > 256 ? off : (size_t)256;
-    return L;
+static MfScratch carve_fill_holes(void* scratch, int64_t n_verts, int64_t n_faces) {
+    MfScratch w{};
+    MeshCarver c(scratch);
+    w.sums = c.take<long long>(3 * (size_t)n_verts);
+    w.nonfinite = c.take<int>((size_t)n_verts);
+    w.lrank = c.take<int>((size_t)n_verts);
+    w.lblk_count = c.take<int>(mesh_blocks(n_verts));
+    w.lblk_base = c.take<int>(mesh_blocks(n_verts));
+    w.eblk_count = c.take<int>(mesh_blocks(3 * n_faces));
+    w.eblk_base = c.take<int>(mesh_blocks(3 * n_faces));
+    w.bytes = c.bytes();
+    return w;
 }
 
 size_t arah_mesh_fill_holes_scratch_bytes(int64_t n_verts, int64_t n_faces) {
     if (!ma_sizes_ok(n_verts, n_faces)) return 0;
-    return mf_layout(n_verts, n_faces).bytes;
+    return carve_fill_holes(nullptr, n_verts, n_faces).bytes;
 }
 
 int arah_mesh_fill_holes(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int32_t* edges,
@@ -4576,28 +4551,22 @@ int arah_mesh_fill_holes(const float* verts, int64_t n_verts, const int32_t* fac
     if ((n_verts > 0 && (!verts || !verts_out || !vert_src || !loop_edges || !loop_simple || !loop_vert)) ||
         (n_faces > 0 && (!faces || !faces_out || !face_loop || !edges || !edge_loop)))
         return ARAH_E_BADARG;
-    const MfLayout L = mf_layout(n_verts, n_faces);
-    if (scratch_bytes < L.bytes) return ARAH_E_WORKSPACE;
+    const MfScratch w = carve_fill_holes(scratch, n_verts, n_faces);
+    if (scratch_bytes < w.bytes) return ARAH_E_WORKSPACE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int V = (int)n_verts, F = (int)n_faces, E = 3 * F, Lcap = V / 3;
-    const int nbl = (int)mo_blocks(n_verts), nbe = (int)mo_blocks(3 * n_faces);
-    char* base = reinterpret_cast<char*>(scratch);
-    long long* sums = reinterpret_cast<long long*>(base + L.sums);
-    int* nonfinite = reinterpret_cast<int*>(base + L.nonfinite);
-    int* lrank = reinterpret_cast<int*>(base + L.lrank);
-    int* lblk_count = reinterpret_cast<int*>(base + L.lblk_count);
-    int* lblk_base = reinterpret_cast<int*>(base + L.lblk_base);
-    int* eblk_count = reinterpret_cast<int*>(base + L.eblk_count);
-    int* eblk_base = reinterpret_cast<int*>(base + L.eblk_base);
-    hipLaunchKernelGGL(k_mo_fill_init, dim3(mo_grid(V)), dim3(kMoThreads), 0, s, sums, nonfinite, V, (const int*)loop_counts, (int*)counts);
+    const int nbl = (int)mesh_blocks(n_verts), nbe = (int)mesh_blocks(3 * n_faces);
+    long long* sums = w.sums;
+    int *nonfinite = w.nonfinite, *lrank = w.lrank;
+    hipLaunchKernelGGL(k_mo_fill_init, dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, sums, nonfinite, V, (const int*)loop_counts, (int*)counts);
     if (V > 0 || F > 0)
-        hipLaunchKernelGGL(k_mo_fill_copy, dim3(mo_grid(max(V, F))), dim3(kMoThreads), 0, s, verts, V, (const int*)faces, F, verts_out,
+        hipLaunchKernelGGL(k_mo_fill_copy, dim3(mesh_grid(max(V, F))), dim3(kImeshThreads), 0, s, verts, V, (const int*)faces, F, verts_out,
                            (int*)vert_src, (int*)faces_out, (int*)face_loop);
     if (V > 0 && F > 0) {
         MoQuant g;
         for (int a = 0; a < 3; ++a) g.origin[a] = origin[a];
         g.scale = fix_scale;
-        hipLaunchKernelGGL(k_mo_fill_accum, dim3(mo_grid(E)), dim3(kMoThreads), 0, s, verts, V, (const int*)edges, (const int*)edge_loop, E,
+        hipLaunchKernelGGL(k_mo_fill_accum, dim3(mesh_grid(E)), dim3(kImeshThreads), 0, s, verts, V, (const int*)edges, (const int*)edge_loop, E,
                            (const int*)loop_counts, (const int*)loop_edges, (const unsigned char*)loop_simple, (int)max_edges, g, sums,
                            nonfinite);
         MoCompact p{};
@@ -4621,27 +4590,27 @@ int arah_mesh_fill_holes(const float* verts, int64_t n_verts, const int32_t* fac
         const int* n_loops = (const int*)loop_counts + 1;
         const int* n_edges = (const int*)loop_counts;
         // lrank is written for the loops below *n_loops only, and edge_loop of this call's edges names only those
-        hipLaunchKernelGGL((k_mo_compact<kMoLoops, false>), dim3(nbl), dim3(kMoThreads), 0, s, p, V, n_loops, lblk_count, (const int*)nullptr);
-        hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)lblk_count, nbl, lblk_base, (int*)counts + 3);
-        hipLaunchKernelGGL((k_mo_compact<kMoLoops, true>), dim3(nbl), dim3(kMoThreads), 0, s, p, V, n_loops, (int*)nullptr, (const int*)lblk_base);
-        hipLaunchKernelGGL((k_mo_compact<kMoFilled, false>), dim3(nbe), dim3(kMoThreads), 0, s, p, E, n_edges, eblk_count, (const int*)nullptr);
-        hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(1024), 0, s, (const int*)eblk_count, nbe, eblk_base, (int*)counts + 4);
-        hipLaunchKernelGGL((k_mo_compact<kMoFilled, true>), dim3(nbe), dim3(kMoThreads), 0, s, p, E, n_edges, (int*)nullptr, (const int*)eblk_base);
+        mesh_compact_passes(s, nbl, w.lblk_count, w.lblk_base, counts + 3, [&](auto fill, int* count, const int* base) {
+            hipLaunchKernelGGL((k_mo_compact<kMoLoops, decltype(fill)::value>), dim3(nbl), dim3(kImeshThreads), 0, s, p, V, n_loops, count, base);
+        });
+        mesh_compact_passes(s, nbe, w.eblk_count, w.eblk_base, counts + 4, [&](auto fill, int* count, const int* base) {
+            hipLaunchKernelGGL((k_mo_compact<kMoFilled, decltype(fill)::value>), dim3(nbe), dim3(kImeshThreads), 0, s, p, E, n_edges, count, base);
+        });
     }
     // the rows behind the filled loops and the added faces, up to the arrays' lengths V + V / 3 and 4 F
     if (Lcap > 0) {
-        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)verts_out + 3 * (size_t)V, (const int*)counts + 3, Lcap, 3);
-        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)vert_src + (size_t)V, (const int*)counts + 3, Lcap, 1);
+        mesh_pad(s, verts_out + 3 * (size_t)V, counts + 3, Lcap, 3);
+        mesh_pad(s, vert_src + (size_t)V, counts + 3, Lcap, 1);
     }
     if (F > 0) {
-        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)faces_out + 3 * (size_t)F, (const int*)counts + 4, E, 3);
-        hipLaunchKernelGGL(k_mc_pad_words, dim3(512), dim3(256), 0, s, (unsigned*)face_loop + (size_t)F, (const int*)counts + 4, E, 1);
+        mesh_pad(s, faces_out + 3 * (size_t)F, counts + 4, E, 3);
+        mesh_pad(s, face_loop + (size_t)F, counts + 4, E, 1);
     }
     return check_launch();
 }
 
 // ---- indexed meshes drawn on the device: pix_to_face, depth, barycentrics; attributes (csrc/meshraster.hpp) ------------------------
-static int mr_grid(int64_t n) { return (int)min((int64_t)kMrMaxGrid, max((int64_t)1, (n + kMrThreads - 1) / kMrThreads)); }
+static int mr_grid(int64_t n) { return mesh_grid(n, kMrMaxGrid); }   // the point-in-mesh entries further down borrow this grid
 
 static int mr_rasterize(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t H, int32_t W, float z_near,
                         int32_t cull, int32_t small_area, int32_t wave_area, int32_t huge_area, uint64_t* keys, int32_t* pix_to_face,
@@ -4658,14 +4627,14 @@ static int mr_rasterize(const float* verts, int64_t n_verts, const int32_t* face
     int* med_list = pix_to_face;
     int* huge_list = reinterpret_cast<int*>(depth);
     unsigned* counters = reinterpret_cast<unsigned*>(bary);
-    hipLaunchKernelGGL(k_mr_init, dim3(mr_grid(n_pix)), dim3(kMrThreads), 0, s, k, (long long)n_pix, counters);
+    hipLaunchKernelGGL(k_mr_init, dim3(mesh_grid(n_pix, kMrMaxGrid)), dim3(kImeshThreads), 0, s, k, (long long)n_pix, counters);
     if (F > 0 && V > 0) {
-        hipLaunchKernelGGL(k_mr_scatter, dim3(mr_grid(F)), dim3(kMrThreads), 0, s, verts, V, (const int*)faces, F, (int)H, (int)W, z_near,
+        hipLaunchKernelGGL(k_mr_scatter, dim3(mesh_grid(F, kMrMaxGrid)), dim3(kImeshThreads), 0, s, verts, V, (const int*)faces, F, (int)H, (int)W, z_near,
                            (int)cull, (int)small_area, (int)wave_area, (int)huge_area, k, med_list, huge_list, (unsigned)n_pix, counters);
-        hipLaunchKernelGGL(k_mr_lists, dim3(kMrListGrid), dim3(kMrThreads), 0, s, verts, V, (const int*)faces, F, (int)H, (int)W, z_near,
+        hipLaunchKernelGGL(k_mr_lists, dim3(kMrListGrid), dim3(kImeshThreads), 0, s, verts, V, (const int*)faces, F, (int)H, (int)W, z_near,
                            (int)cull, k, (const int*)med_list, (const int*)huge_list, (unsigned)n_pix, (const unsigned*)counters);
     }
-    hipLaunchKernelGGL(k_mr_resolve, dim3(mr_grid(n_pix)), dim3(kMrThreads), 0, s, verts, V, (const int*)faces, F, (int)H, (int)W,
+    hipLaunchKernelGGL(k_mr_resolve, dim3(mesh_grid(n_pix, kMrMaxGrid)), dim3(kImeshThreads), 0, s, verts, V, (const int*)faces, F, (int)H, (int)W,
                        (const unsigned long long*)k, (int*)pix_to_face, depth, bary);
     return check_launch();
 }
@@ -4689,7 +4658,7 @@ int arah_mesh_interpolate(const int32_t* pix_to_face, const float* bary, int32_t
     if (H <= 0 || W <= 0 || (int64_t)H * W > (int64_t)INT32_MAX || n_channels < 1 || n_channels > 32) return ARAH_E_BADARG;
     if (!pix_to_face || !bary || !out || (n_verts > 0 && !attr) || (n_faces > 0 && !faces)) return ARAH_E_BADARG;
     const int64_t n_pix = (int64_t)H * W;
-    hipLaunchKernelGGL(k_mr_interpolate, dim3(mr_grid(n_pix * n_channels)), dim3(kMrThreads), 0, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(k_mr_interpolate, dim3(mesh_grid(n_pix * n_channels, kMrMaxGrid)), dim3(kImeshThreads), 0, reinterpret_cast<hipStream_t>(stream),
                        (const int*)pix_to_face, bary, (long long)n_pix, (const int*)faces, (int)n_faces, attr, (int)n_verts,
                        (int)n_channels, background, out);
     return check_launch();

@@ -7,7 +7,7 @@
 //
 //   k_mcubes<kMcCount>  one workgroup per lattice row (ix, iy), one thread per cell iz: the 8 corner values, the inside / outside
 //                    pattern, the triangle count of the case -> triangles per row
-//   k_mc_scan        exclusive scan of the row counts (one workgroup) -> first triangle of every row, the total
+//   k_mc_scan        exclusive scan of the row counts (one workgroup, meshcommon.hpp) -> first triangle of every row, the total
 //   k_mcubes<kMcSoup>  the same walk again; a cell writes its triangles at row base + prefix inside the row
 //   k_mc_pad         zero-fills the unused tail of the caller's buffer: triangles beyond the count are degenerate (all
 //                    three corners equal), which every later stage -- skinning, projection, rasterisation -- ignores
@@ -20,7 +20,6 @@
 // The same level set as an INDEXED mesh (shared vertices, faces of vertex ids): the second half of this file.
 #pragma once
 
-constexpr int kMcThreads = 256;
 constexpr int kMcTableWidth = 16;   // 5 triangles x 3 edge ids, padded
 
 __device__ __constant__ signed char kMcCorner[8][3] = {{0, 0, 0}, {1, 0, 0}, {1, 1, 0}, {0, 1, 0}, {0, 0, 1}, {1, 0, 1}, {1, 1, 1}, {0, 1, 1}};
@@ -81,18 +80,18 @@ enum { kMcCount = 0, kMcSoup = 1, kMcFaces = 2 };
 // MODE kMcCount: triangles per row -> row_count.  kMcSoup: the triangles -> tris [cap][3][3].  kMcFaces: the same triangles as
 // vertex ids of the indexed mesh -> faces [cap][3]; first_vert [N^3] is the id of every lattice point's first vertex.
 template <int MODE>
-__global__ __launch_bounds__(kMcThreads) void k_mcubes(const float* __restrict__ sdf, int N, float level, float vs,
-                                                       const signed char* __restrict__ table, const int* __restrict__ ntri,
-                                                       int* __restrict__ row_count, const int* __restrict__ row_base,
-                                                       float* __restrict__ tris, int cap,
-                                                       const int* __restrict__ first_vert, int* __restrict__ faces) {
+__global__ __launch_bounds__(kImeshThreads) void k_mcubes(const float* __restrict__ sdf, int N, float level, float vs,
+                                                          const signed char* __restrict__ table, const int* __restrict__ ntri,
+                                                          int* __restrict__ row_count, const int* __restrict__ row_base,
+                                                          float* __restrict__ tris, int cap,
+                                                          const int* __restrict__ first_vert, int* __restrict__ faces) {
     constexpr bool EMIT = MODE != kMcCount;
-    __shared__ int wsum[kMcThreads / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ int wsum[kImeshThreads / 64];
+    const int tid = threadIdx.x;
     const int row = blockIdx.x, M = N - 1;
     const int ix = row / M, iy = row - ix * M;
     int done = 0;   // triangles of this row in front of the current chunk of cells
-    for (int z0 = 0; z0 < M; z0 += kMcThreads) {
+    for (int z0 = 0; z0 < M; z0 += kImeshThreads) {
         const int iz = z0 + tid;
         const bool ok = iz < M;
         float cv[8];
@@ -103,24 +102,10 @@ __global__ __launch_bounds__(kMcThreads) void k_mcubes(const float* __restrict__
             cs |= (cv[c] < level ? 1 : 0) << c;
         }
         const int cnt = (ok && cs != 0 && cs != 255) ? ntri[cs] : 0;
-        // exclusive prefix of cnt over the workgroup, in thread order
-        int inc = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(inc, o);
-            if (lane >= o) inc += v;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < kMcThreads / 64; ++w) {
-            if (w < wave) before += wsum[w];
-            total += wsum[w];
-        }
-        __syncthreads();
+        int total;
+        const int before = mesh_prefix(cnt, wsum, total);   // the triangles of the chunk's cells below this one
         if constexpr (EMIT) {
-            const int first = row_base[row] + done + before + inc - cnt;
+            const int first = row_base[row] + done + before;
             for (int s = 0; s < cnt; ++s) {
                 if (first + s >= cap) break;
                 float v[3][3];
@@ -167,30 +152,6 @@ __global__ __launch_bounds__(kMcThreads) void k_mcubes(const float* __restrict__
     if (MODE == kMcCount && tid == 0) row_count[row] = done;
 }
 
-// exclusive scan of n row counts by one workgroup: base[i] = sum of count[0 .. i), *total = the sum
-__global__ __launch_bounds__(1024) void k_mc_scan(const int* __restrict__ count, int n, int* __restrict__ base, int* total) {
-    __shared__ int part[1024];
-    const int tid = threadIdx.x;
-    const int per = (n + 1023) / 1024;
-    const int lo = min(tid * per, n), hi = min(lo + per, n);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += count[i];
-    part[tid] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {   // Hillis-Steele inclusive scan of the 1024 partial sums
-        const int v = tid >= o ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int run = part[tid] - s;
-    for (int i = lo; i < hi; ++i) {
-        base[i] = run;
-        run += count[i];
-    }
-    if (tid == 1023) *total = part[1023];
-}
-
 __global__ void k_mc_pad(float* __restrict__ tris, const int* total, int cap) {
     const size_t first = (size_t)min(max(*total, 0), cap) * 9, end = (size_t)cap * 9;
     for (size_t i = first + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < end; i += (size_t)gridDim.x * blockDim.x) tris[i] = 0.f;
@@ -199,7 +160,7 @@ __global__ void k_mc_pad(float* __restrict__ tris, const int* total, int cap) {
 // ---- indexed mesh: one vertex per crossing lattice edge ------------------------------------------------------------------
 // A marching-cubes vertex lies on a lattice edge, and a lattice edge has an integer name: its lower end (ix, iy, iz) and its
 // axis a, key ((ix N + iy) N + iz) 3 + a.  The vertices are the crossing edges in ascending key order, numbered by the same
-// count / scan / fill as the triangles:
+// count / scan / fill as the triangles (meshcommon.hpp: mesh_prefix inside a row, k_mc_scan over the rows, k_mc_pad_words):
 //
 //   k_mc_verts<false>  one workgroup per lattice row (ix, iy), one thread per POINT iz: its up to three crossing flags
 //                      (mc_point_flags) -> vertices per row
@@ -212,39 +173,26 @@ __global__ void k_mc_pad(float* __restrict__ tris, const int* total, int cap) {
 //
 // No hashing, no sorting, no atomics: the result is deterministic.
 template <bool EMIT>
-__global__ __launch_bounds__(kMcThreads) void k_mc_verts(const float* __restrict__ sdf, int N, float level, float vs,
-                                                         int* __restrict__ row_count, const int* __restrict__ row_base,
-                                                         int* __restrict__ first_vert, float* __restrict__ verts,
-                                                         int* __restrict__ vert_edge, int cap) {
-    __shared__ int wsum[kMcThreads / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+__global__ __launch_bounds__(kImeshThreads) void k_mc_verts(const float* __restrict__ sdf, int N, float level, float vs,
+                                                            int* __restrict__ row_count, const int* __restrict__ row_base,
+                                                            int* __restrict__ first_vert, float* __restrict__ verts,
+                                                            int* __restrict__ vert_edge, int cap) {
+    __shared__ int wsum[kImeshThreads / 64];
+    const int tid = threadIdx.x;
     const int row = blockIdx.x;
     const int ix = row / N, iy = row - ix * N;
     int done = 0;   // vertices of this row in front of the current chunk of points
-    for (int z0 = 0; z0 < N; z0 += kMcThreads) {
+    for (int z0 = 0; z0 < N; z0 += kImeshThreads) {
         const int iz = z0 + tid;
         const bool ok = iz < N;
         const int flags = ok ? mc_point_flags(sdf, N, level, ix, iy, iz, 3) : 0;
         const int cnt = __popc(flags);
-        int inc = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(inc, o);
-            if (lane >= o) inc += v;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < kMcThreads / 64; ++w) {
-            if (w < wave) before += wsum[w];
-            total += wsum[w];
-        }
-        __syncthreads();
+        int total;
+        const int before = mesh_prefix(cnt, wsum, total);   // the vertices of the chunk's points below this one
         if constexpr (EMIT) {
             if (ok) {
                 const size_t p = ((size_t)row * N) + iz;
-                int id = row_base[row] + done + before + inc - cnt;
+                int id = row_base[row] + done + before;
                 first_vert[p] = id;
                 const int pp[3] = {ix, iy, iz};
                 const size_t step[3] = {(size_t)N * N, (size_t)N, 1};
@@ -266,11 +214,4 @@ __global__ __launch_bounds__(kMcThreads) void k_mc_verts(const float* __restrict
         done += total;
     }
     if (!EMIT && tid == 0) row_count[row] = done;
-}
-
-// rows [min(*total, cap), cap) of a buffer of `width` 32-bit words per row are zeroed; buf may be null
-__global__ void k_mc_pad_words(unsigned* __restrict__ buf, const int* total, int cap, int width) {
-    if (!buf) return;
-    const size_t first = (size_t)min(max(*total, 0), cap) * width, end = (size_t)cap * width;
-    for (size_t i = first + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < end; i += (size_t)gridDim.x * blockDim.x) buf[i] = 0u;
 }

@@ -34,10 +34,9 @@
 // Integer atomics only (add, max).  Their order of arrival decides the layout of vf_raw and nb_raw and nothing else, and both
 // are sorted before anything reads them, ties between equal edge keys broken by position -- equal keys are interchangeable.  No
 // thread waits for another: no spin-wait, no grid-wide barrier; every loop ends by an argument of its own, stated at the loop.
+// kImeshThreads, kImeshMaxGrid, k_mc_scan and k_mc_pad_words are meshcommon.hpp's.
 #pragma once
 
-constexpr int kMaThreads = 256;
-constexpr int kMaMaxGrid = 1 << 16;
 constexpr int kMaShort = 32;              // elements of a segment one thread still sorts alone: at most 32^2 comparisons
 constexpr int kMaLongGrid = 1024;         // workgroups that share the long segments
 
@@ -46,8 +45,8 @@ __device__ __forceinline__ bool ma_face_ok(const int* __restrict__ faces, long l
     return cc_face_ok(faces, f, n_verts, id) && id[0] != id[1] && id[1] != id[2] && id[0] != id[2];
 }
 
-__global__ __launch_bounds__(kMaThreads) void k_ma_init(int* __restrict__ deg, int* __restrict__ cursor, int n_verts,
-                                                        int* __restrict__ counts) {
+__global__ __launch_bounds__(kImeshThreads) void k_ma_init(int* __restrict__ deg, int* __restrict__ cursor, int n_verts,
+                                                           int* __restrict__ counts) {
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_verts - v strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < n_verts; v += step) {
@@ -57,7 +56,7 @@ __global__ __launch_bounds__(kMaThreads) void k_ma_init(int* __restrict__ deg, i
     if (blockIdx.x == 0 && threadIdx.x < 8) counts[threadIdx.x] = 0;
 }
 
-__global__ __launch_bounds__(kMaThreads) void k_ma_count(const int* __restrict__ faces, int n_faces, int n_verts, int* deg, int* counts) {
+__global__ __launch_bounds__(kImeshThreads) void k_ma_count(const int* __restrict__ faces, int n_faces, int n_verts, int* deg, int* counts) {
     const long long step = (long long)gridDim.x * blockDim.x, end = ((long long)n_faces + 63) & ~63ll;
     // terminates: end - f strictly decreases (step >= 1) and the loop ends when it reaches 0.  The face count is rounded up to
     // whole waves so that every lane reaches the ballot; lanes beyond the end carry no face
@@ -74,9 +73,9 @@ __global__ __launch_bounds__(kMaThreads) void k_ma_count(const int* __restrict__
     }
 }
 
-__global__ __launch_bounds__(kMaThreads) void k_ma_fill(const int* __restrict__ faces, int n_faces, int n_verts,
-                                                        const int* __restrict__ vf_start, int* cursor, unsigned* __restrict__ vf_raw,
-                                                        unsigned* __restrict__ nb_raw) {
+__global__ __launch_bounds__(kImeshThreads) void k_ma_fill(const int* __restrict__ faces, int n_faces, int n_verts,
+                                                           const int* __restrict__ vf_start, int* cursor, unsigned* __restrict__ vf_raw,
+                                                           unsigned* __restrict__ nb_raw) {
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_faces - f strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x; f < n_faces; f += step) {
@@ -109,9 +108,9 @@ __device__ __forceinline__ void ma_rank_sort(const unsigned* __restrict__ src, u
     }
 }
 
-__global__ __launch_bounds__(kMaThreads) void k_ma_sort_short(const int* __restrict__ vf_start, int n_verts,
-                                                              const unsigned* __restrict__ vf_raw, unsigned* __restrict__ vf,
-                                                              const unsigned* __restrict__ nb_raw, unsigned* __restrict__ nb_sorted) {
+__global__ __launch_bounds__(kImeshThreads) void k_ma_sort_short(const int* __restrict__ vf_start, int n_verts,
+                                                                 const unsigned* __restrict__ vf_raw, unsigned* __restrict__ vf,
+                                                                 const unsigned* __restrict__ nb_raw, unsigned* __restrict__ nb_sorted) {
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_verts - v strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < n_verts; v += step) {
@@ -122,26 +121,26 @@ __global__ __launch_bounds__(kMaThreads) void k_ma_sort_short(const int* __restr
     }
 }
 
-__global__ __launch_bounds__(kMaThreads) void k_ma_sort_long(const int* __restrict__ vf_start, int n_verts,
-                                                             const unsigned* __restrict__ vf_raw, unsigned* __restrict__ vf,
-                                                             const unsigned* __restrict__ nb_raw, unsigned* __restrict__ nb_sorted) {
+__global__ __launch_bounds__(kImeshThreads) void k_ma_sort_long(const int* __restrict__ vf_start, int n_verts,
+                                                                const unsigned* __restrict__ vf_raw, unsigned* __restrict__ vf,
+                                                                const unsigned* __restrict__ nb_raw, unsigned* __restrict__ nb_sorted) {
     // terminates: n_verts - v strictly decreases (gridDim.x >= 1) and the loop ends when it reaches 0.  v and n are the same
     // for every thread of the workgroup; nothing is shared between its threads but the read-only source
     for (long long v = blockIdx.x; v < n_verts; v += gridDim.x) {
         const long long s = vf_start[v];
         const int n = (int)(vf_start[v + 1] - s);
-        if (n > kMaShort) ma_rank_sort(vf_raw + s, vf + s, n, (int)threadIdx.x, kMaThreads);
-        if (2 * n > kMaShort) ma_rank_sort(nb_raw + 2 * s, nb_sorted + 2 * s, 2 * n, (int)threadIdx.x, kMaThreads);
+        if (n > kMaShort) ma_rank_sort(vf_raw + s, vf + s, n, (int)threadIdx.x, kImeshThreads);
+        if (2 * n > kMaShort) ma_rank_sort(nb_raw + 2 * s, nb_sorted + 2 * s, 2 * n, (int)threadIdx.x, kImeshThreads);
     }
 }
 
 // The walk over a vertex's sorted edges: runs of equal neighbour ids.  COUNT: deg[v] = the runs.  FILL: the entries, the flags,
 // the statistics of the edges seen from their lower end.
 template <bool FILL>
-__global__ __launch_bounds__(kMaThreads) void k_ma_nbr(const int* __restrict__ vf_start, int n_verts, const unsigned* __restrict__ nb_sorted,
-                                                       int* __restrict__ deg, const int* __restrict__ nbr_start, int* __restrict__ nbr,
-                                                       int* __restrict__ nbr_out, int* __restrict__ nbr_in,
-                                                       unsigned char* __restrict__ vert_flags, int* counts) {
+__global__ __launch_bounds__(kImeshThreads) void k_ma_nbr(const int* __restrict__ vf_start, int n_verts, const unsigned* __restrict__ nb_sorted,
+                                                          int* __restrict__ deg, const int* __restrict__ nbr_start, int* __restrict__ nbr,
+                                                          int* __restrict__ nbr_out, int* __restrict__ nbr_in,
+                                                          unsigned char* __restrict__ vert_flags, int* counts) {
     const long long step = (long long)gridDim.x * blockDim.x, end = ((long long)n_verts + 63) & ~63ll;
     int n_edges = 0, n_bound = 0, n_nonman = 0, n_misor = 0, n_isol = 0, most = 0;
     // terminates: end - v strictly decreases (step >= 1) and the loop ends when it reaches 0; the vertex count is rounded up to
@@ -211,9 +210,9 @@ __global__ void k_ma_finish(int* __restrict__ counts, int n_verts) {
 }
 
 // ---- per-vertex normals: a gather over vf ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kMaThreads) void k_ma_normals(const float* __restrict__ verts, int n_verts, const int* __restrict__ faces,
-                                                           int n_faces, const int* __restrict__ vf_start, const int* __restrict__ vf,
-                                                           double* __restrict__ normal_sum, float* __restrict__ normals) {
+__global__ __launch_bounds__(kImeshThreads) void k_ma_normals(const float* __restrict__ verts, int n_verts, const int* __restrict__ faces,
+                                                              int n_faces, const int* __restrict__ vf_start, const int* __restrict__ vf,
+                                                              double* __restrict__ normal_sum, float* __restrict__ normals) {
 #pragma clang fp contract(off)
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_verts - v strictly decreases (step >= 1) and the loop ends when it reaches 0
@@ -254,9 +253,9 @@ __global__ __launch_bounds__(kMaThreads) void k_ma_normals(const float* __restri
 }
 
 // ---- one smoothing step: a gather over nbr -----------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kMaThreads) void k_ma_smooth(const float* __restrict__ src, int n_verts, const int* __restrict__ nbr_start,
-                                                          const int* __restrict__ nbr, const unsigned char* __restrict__ vert_flags,
-                                                          double factor, int pin, float* __restrict__ dst) {
+__global__ __launch_bounds__(kImeshThreads) void k_ma_smooth(const float* __restrict__ src, int n_verts, const int* __restrict__ nbr_start,
+                                                             const int* __restrict__ nbr, const unsigned char* __restrict__ vert_flags,
+                                                             double factor, int pin, float* __restrict__ dst) {
 #pragma clang fp contract(off)
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_verts - v strictly decreases (step >= 1) and the loop ends when it reaches 0
@@ -292,7 +291,7 @@ __global__ __launch_bounds__(kMaThreads) void k_ma_smooth(const float* __restric
     }
 }
 
-__global__ __launch_bounds__(kMaThreads) void k_ma_copy(const float* __restrict__ src, long long n, float* __restrict__ dst) {
+__global__ __launch_bounds__(kImeshThreads) void k_ma_copy(const float* __restrict__ src, long long n, float* __restrict__ dst) {
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n - i strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) dst[i] = src[i];

@@ -15,7 +15,7 @@
 //   k_cc_flatten   root[v] = the end of v's parent chain; read-only on parent (the launch boundary made it final), a separate
 //                  array is written.  The root of a component is its smallest vertex id
 //   k_cc_compact<kCcRoots, false>, k_mc_scan, k_cc_compact<kCcRoots, true>
-//                  the count / scan / fill of mcubes.hpp over the marks root[v] == v: dense[r] = the number of roots below r,
+//                  the count / scan / fill of meshcommon.hpp over the marks root[v] == v: dense[r] = the number of roots below r,
 //                  so components are numbered in ascending order of their smallest vertex id; the total is C
 //   k_cc_label     labels[v] = dense[root[v]], comp_verts[label] += 1
 //   k_cc_faces     comp_faces[label of a valid face] += 1, counts[1] += 1
@@ -27,12 +27,9 @@
 //
 // Every atomic is an integer atomicMin / atomicAdd / atomicMax: minima, sums and maxima of integers do not depend on the order
 // of arrival.  No thread ever waits for another lane, wave or workgroup: there is no spin-wait and no grid-wide barrier, every
-// loop ends by an argument local to its own thread (or, for cc_add_one, its own wave in lockstep), stated at the loop.
+// loop ends by an argument local to its own thread (or, for cc_add_one of meshcommon.hpp, its own wave in lockstep), stated at
+// the loop.  The constants, mesh_compact, k_mc_scan, k_mc_pad_words and cc_add_one are meshcommon.hpp's.
 #pragma once
-
-constexpr int kCcThreads = 256;
-constexpr int kCcChunk = 1024;   // elements per workgroup of the count / fill walks: 4 passes of kCcThreads
-constexpr int kCcMaxGrid = 1 << 16;   // workgroups of the element-wise walks (they stride over what is left)
 
 // Why hooking is right.  Let G be the graph of the links in place (x, parent[x]), the pairs (a, b) that threads inside cc_union
 // still have to join, and the edges of the faces not yet visited.  G starts as the mesh's own vertex graph, and no step ever
@@ -85,22 +82,6 @@ __device__ __forceinline__ void cc_union(int* parent, int a, int b) {
     cc_join(parent, b, lo);
 }
 
-// table[key] += 1 for every lane with `active`, one atomicAdd per distinct key of the wave (a body mesh has one component: 64
-// lanes, one key).  Call it from wave-uniform control flow.
-__device__ __forceinline__ void cc_add_one(int* table, int key, bool active) {
-    const int lane = threadIdx.x & 63;
-    unsigned long long pending = __ballot(active);
-    // terminates: every round retires at least its leader, so the number of pending lanes strictly decreases and is bounded
-    // below by 0; the lanes of a wave run this loop in lockstep, nobody waits
-    while (pending) {
-        const int leader = __ffsll((long long)pending) - 1;
-        const int k = __shfl(key, leader);
-        const unsigned long long same = __ballot(active && key == k);
-        if (lane == leader) atomicAdd(&table[k], (int)__popcll(same));
-        pending &= ~same;
-    }
-}
-
 __device__ __forceinline__ bool cc_face_ok(const int* __restrict__ faces, long long f, int n_verts, int id[3]) {
     id[0] = faces[3 * f + 0];
     id[1] = faces[3 * f + 1];
@@ -108,9 +89,9 @@ __device__ __forceinline__ bool cc_face_ok(const int* __restrict__ faces, long l
     return (unsigned)id[0] < (unsigned)n_verts && (unsigned)id[1] < (unsigned)n_verts && (unsigned)id[2] < (unsigned)n_verts;
 }
 
-__global__ __launch_bounds__(kCcThreads) void k_cc_init(int* __restrict__ parent, int* __restrict__ comp_verts,
-                                                        int* __restrict__ comp_faces, int n_verts, int* __restrict__ counts,
-                                                        unsigned long long* __restrict__ best) {
+__global__ __launch_bounds__(kImeshThreads) void k_cc_init(int* __restrict__ parent, int* __restrict__ comp_verts,
+                                                           int* __restrict__ comp_faces, int n_verts, int* __restrict__ counts,
+                                                           unsigned long long* __restrict__ best) {
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_verts - v strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < n_verts; v += step) {
@@ -126,7 +107,7 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_init(int* __restrict__ parent
     }
 }
 
-__global__ __launch_bounds__(kCcThreads) void k_cc_hook(const int* __restrict__ faces, int n_faces, int n_verts, int* parent) {
+__global__ __launch_bounds__(kImeshThreads) void k_cc_hook(const int* __restrict__ faces, int n_faces, int n_verts, int* parent) {
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_faces - f strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x; f < n_faces; f += step) {
@@ -137,7 +118,7 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_hook(const int* __restrict__ 
     }
 }
 
-__global__ __launch_bounds__(kCcThreads) void k_cc_flatten(const int* __restrict__ parent, int n_verts, int* __restrict__ root) {
+__global__ __launch_bounds__(kImeshThreads) void k_cc_flatten(const int* __restrict__ parent, int n_verts, int* __restrict__ root) {
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_verts - v strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < n_verts; v += step) {
@@ -151,11 +132,8 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_flatten(const int* __restrict
     }
 }
 
-// The count / scan / fill idiom of mcubes.hpp over a 0/1 mark per element, kCcChunk elements per workgroup:
-//   FILL = false   blk_count[block] = the marks of the block's chunk
-//   k_mc_scan      blk_base = their exclusive scan, the total
-//   FILL = true    a marked element takes the id blk_base[block] + the marks in front of it inside the chunk: ids ascend with
-//                  the elements, the order is preserved
+// mesh_compact (meshcommon.hpp) over n elements: FILL = false counts the marks of every chunk, k_mc_scan numbers the chunks,
+// FILL = true gives a marked element its id.
 // WHAT                 mark of element i                                              fill
 //   kCcRoots           a[i] == i  (a = root)                                          o0[i] = id  (dense, roots only)
 //   kCcVerts           b[a[i]] != 0  (a = labels, b = keep; a label outside [0, V)    o0[i] = id or -1 (vert_map), o1[id] = i
@@ -164,56 +142,32 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_flatten(const int* __restrict
 //                                                                                     (face_src)
 enum { kCcRoots = 0, kCcVerts = 1, kCcFaces = 2 };
 
+struct CcCorners {
+    int id[3];   // kCcFaces: the new ids of the face's three corners
+};
+
 template <int WHAT, bool FILL>
-__global__ __launch_bounds__(kCcThreads) void k_cc_compact(const int* __restrict__ faces, const int* __restrict__ a,
-                                                           const int* __restrict__ b, int n, int n_verts,
-                                                           int* __restrict__ blk_count, const int* __restrict__ blk_base,
-                                                           int* __restrict__ o0, int* __restrict__ o1) {
-    __shared__ int wsum[kCcThreads / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long first = (long long)blockIdx.x * kCcChunk;
-    int done = 0;   // marks of this chunk in front of the current pass
-#pragma unroll 1
-    for (int z0 = 0; z0 < kCcChunk; z0 += kCcThreads) {   // terminates: kCcChunk - z0 strictly decreases to 0
-        const long long i = first + z0 + tid;
-        const bool ok = i < n;
-        int id[3] = {0, 0, 0};
-        bool mark = false;
-        if (ok) {
-            if constexpr (WHAT == kCcRoots) mark = a[i] == (int)i;
+__global__ __launch_bounds__(kImeshThreads) void k_cc_compact(const int* __restrict__ faces, const int* __restrict__ a,
+                                                              const int* __restrict__ b, int n, int n_verts,
+                                                              int* __restrict__ blk_count, const int* __restrict__ blk_base,
+                                                              int* __restrict__ o0, int* __restrict__ o1) {
+    mesh_compact<FILL, CcCorners>(
+        n, blk_count, blk_base,
+        [&](long long i, CcCorners& c) {
+            if constexpr (WHAT == kCcRoots) return a[i] == (int)i;
             if constexpr (WHAT == kCcVerts) {
-                const int c = a[i];
-                mark = (unsigned)c < (unsigned)n_verts && b[c] != 0;
+                const int l = a[i];
+                return (unsigned)l < (unsigned)n_verts && b[l] != 0;
             }
             if constexpr (WHAT == kCcFaces) {
-                mark = cc_face_ok(faces, i, n_verts, id);
-                if (mark) {
-                    id[0] = a[id[0]];
-                    id[1] = a[id[1]];
-                    id[2] = a[id[2]];
-                    mark = id[0] >= 0 && id[1] >= 0 && id[2] >= 0;
-                }
+                if (!cc_face_ok(faces, i, n_verts, c.id)) return false;
+                c.id[0] = a[c.id[0]];
+                c.id[1] = a[c.id[1]];
+                c.id[2] = a[c.id[2]];
+                return c.id[0] >= 0 && c.id[1] >= 0 && c.id[2] >= 0;
             }
-        }
-        // exclusive prefix of the marks over the workgroup, in thread order
-        const int cnt = mark ? 1 : 0;
-        int inc = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(inc, o);
-            if (lane >= o) inc += v;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < kCcThreads / 64; ++w) {
-            if (w < wave) before += wsum[w];
-            total += wsum[w];
-        }
-        __syncthreads();
-        if constexpr (FILL) {
-            const int at = blk_base[blockIdx.x] + done + before + inc - cnt;
+        },
+        [&](long long i, bool ok, bool mark, int at, const CcCorners& c) {
             if constexpr (WHAT == kCcRoots) {
                 if (mark) o0[i] = at;
             }
@@ -223,22 +177,19 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_compact(const int* __restrict
             }
             if constexpr (WHAT == kCcFaces) {
                 if (mark) {
-                    o0[3 * (long long)at + 0] = id[0];
-                    o0[3 * (long long)at + 1] = id[1];
-                    o0[3 * (long long)at + 2] = id[2];
+                    o0[3 * (long long)at + 0] = c.id[0];
+                    o0[3 * (long long)at + 1] = c.id[1];
+                    o0[3 * (long long)at + 2] = c.id[2];
                     o1[at] = (int)i;
                 }
             }
-        }
-        done += total;
-    }
-    if (!FILL && tid == 0) blk_count[blockIdx.x] = done;
+        });
 }
 
 // The element-wise walks below round the element count up to whole waves, so that every lane of a wave reaches cc_add_one
 // and the shuffles together; lanes beyond the end carry active = false.
-__global__ __launch_bounds__(kCcThreads) void k_cc_label(const int* __restrict__ root, const int* __restrict__ dense, int n_verts,
-                                                         int* __restrict__ labels, int* comp_verts) {
+__global__ __launch_bounds__(kImeshThreads) void k_cc_label(const int* __restrict__ root, const int* __restrict__ dense, int n_verts,
+                                                            int* __restrict__ labels, int* comp_verts) {
     const long long step = (long long)gridDim.x * blockDim.x, end = ((long long)n_verts + 63) & ~63ll;
     // terminates: end - v strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < end; v += step) {
@@ -249,8 +200,8 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_label(const int* __restrict__
     }
 }
 
-__global__ __launch_bounds__(kCcThreads) void k_cc_faces(const int* __restrict__ faces, int n_faces, int n_verts,
-                                                         const int* __restrict__ labels, int* comp_faces, int* counts) {
+__global__ __launch_bounds__(kImeshThreads) void k_cc_faces(const int* __restrict__ faces, int n_faces, int n_verts,
+                                                            const int* __restrict__ labels, int* comp_faces, int* counts) {
     const long long step = (long long)gridDim.x * blockDim.x, end = ((long long)n_faces + 63) & ~63ll;
     const int lane = threadIdx.x & 63;
     // terminates: end - f strictly decreases (step >= 1) and the loop ends when it reaches 0
@@ -264,8 +215,8 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_faces(const int* __restrict__
     }
 }
 
-__global__ __launch_bounds__(kCcThreads) void k_cc_largest(const int* __restrict__ comp_faces, const int* __restrict__ counts,
-                                                           unsigned long long* best) {
+__global__ __launch_bounds__(kImeshThreads) void k_cc_largest(const int* __restrict__ comp_faces, const int* __restrict__ counts,
+                                                              unsigned long long* best) {
     const int n_comp = counts[0];
     const long long step = (long long)gridDim.x * blockDim.x, end = ((long long)n_comp + 63) & ~63ll;
     const int lane = threadIdx.x & 63;

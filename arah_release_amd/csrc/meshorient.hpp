@@ -40,11 +40,9 @@
 // Integer atomics only (min, add, or): minima, sums and disjunctions of integers do not depend on the order of arrival.  No
 // thread waits for another: no spin-wait, no grid-wide barrier; every loop ends by an argument of its own, stated at the loop.
 // The adjacency, the edges and the loop tables are the CALLER's arrays: no value read from them is followed out of bounds.
+// The constants, mesh_compact (the walk of k_mo_compact), k_mc_scan, k_mc_pad_words and cc_add_one are meshcommon.hpp's.
 #pragma once
 
-constexpr int kMoThreads = 256;
-constexpr int kMoChunk = 1024;            // elements per workgroup of the count / fill walks: 4 passes of kMoThreads
-constexpr int kMoMaxGrid = 1 << 16;
 constexpr double kMoVolLimit = 262144.0;  // 2^18: three such factors and six terms stay below 2^57
 enum { kMoSeed = 0, kMoMajority = 1, kMoNegative = 2, kMoPositive = 3 };
 
@@ -73,10 +71,10 @@ __device__ __forceinline__ int mo_edge_faces(const int* __restrict__ nbr_start, 
     return 0;
 }
 
-__global__ __launch_bounds__(kMoThreads) void k_mo_init(int* __restrict__ parent, int n_faces, int* __restrict__ comp_faces,
-                                                        int* __restrict__ comp_flags, int* __restrict__ comp_ones,
-                                                        long long* __restrict__ vol_hi, long long* __restrict__ vol_lo,
-                                                        int* __restrict__ counts) {
+__global__ __launch_bounds__(kImeshThreads) void k_mo_init(int* __restrict__ parent, int n_faces, int* __restrict__ comp_faces,
+                                                           int* __restrict__ comp_flags, int* __restrict__ comp_ones,
+                                                           long long* __restrict__ vol_hi, long long* __restrict__ vol_lo,
+                                                           int* __restrict__ counts) {
     const long long step = (long long)gridDim.x * blockDim.x, n = 2 * (long long)n_faces;
     // terminates: n - i strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
@@ -92,10 +90,10 @@ __global__ __launch_bounds__(kMoThreads) void k_mo_init(int* __restrict__ parent
     if (blockIdx.x == 0 && threadIdx.x < 6) counts[threadIdx.x] = 0;
 }
 
-__global__ __launch_bounds__(kMoThreads) void k_mo_pairs(const int* __restrict__ faces, int n_faces, int n_verts,
-                                                         const int* __restrict__ vf_start, const int* __restrict__ vf,
-                                                         const int* __restrict__ nbr_start, const int* __restrict__ nbr,
-                                                         const int* __restrict__ nbr_out, const int* __restrict__ nbr_in, int* parent) {
+__global__ __launch_bounds__(kImeshThreads) void k_mo_pairs(const int* __restrict__ faces, int n_faces, int n_verts,
+                                                            const int* __restrict__ vf_start, const int* __restrict__ vf,
+                                                            const int* __restrict__ nbr_start, const int* __restrict__ nbr,
+                                                            const int* __restrict__ nbr_out, const int* __restrict__ nbr_in, int* parent) {
     const long long step = (long long)gridDim.x * blockDim.x, n = 3 * (long long)n_faces;
     // terminates: n - i strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
@@ -128,9 +126,9 @@ __global__ __launch_bounds__(kMoThreads) void k_mo_pairs(const int* __restrict__
     }
 }
 
-__global__ __launch_bounds__(kMoThreads) void k_mo_flatten(const int* __restrict__ faces, int n_faces, int n_verts,
-                                                           const int* __restrict__ parent, int* __restrict__ froot,
-                                                           unsigned char* __restrict__ fstate) {
+__global__ __launch_bounds__(kImeshThreads) void k_mo_flatten(const int* __restrict__ faces, int n_faces, int n_verts,
+                                                              const int* __restrict__ parent, int* __restrict__ froot,
+                                                              unsigned char* __restrict__ fstate) {
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_faces - f strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x; f < n_faces; f += step) {
@@ -146,9 +144,9 @@ __global__ __launch_bounds__(kMoThreads) void k_mo_flatten(const int* __restrict
     }
 }
 
-__global__ __launch_bounds__(kMoThreads) void k_mo_label(const int* __restrict__ froot, const unsigned char* __restrict__ fstate,
-                                                         const int* __restrict__ dense, int n_faces, int* __restrict__ face_comp,
-                                                         int* comp_faces, int* comp_ones, int* __restrict__ comp_flags, int* counts) {
+__global__ __launch_bounds__(kImeshThreads) void k_mo_label(const int* __restrict__ froot, const unsigned char* __restrict__ fstate,
+                                                            const int* __restrict__ dense, int n_faces, int* __restrict__ face_comp,
+                                                            int* comp_faces, int* comp_ones, int* __restrict__ comp_flags, int* counts) {
     const long long step = (long long)gridDim.x * blockDim.x, end = ((long long)n_faces + 63) & ~63ll;
     const int lane = threadIdx.x & 63;
     // terminates: end - f strictly decreases (step >= 1) and the loop ends when it reaches 0; the face count is rounded up to
@@ -168,9 +166,9 @@ __global__ __launch_bounds__(kMoThreads) void k_mo_label(const int* __restrict__
     }
 }
 
-__global__ __launch_bounds__(kMoThreads) void k_mo_volume(const float* __restrict__ verts, const int* __restrict__ faces, int n_faces,
-                                                          int n_verts, MoQuant g, const int* __restrict__ face_comp,
-                                                          const unsigned char* __restrict__ fstate, long long* vol_hi, long long* vol_lo) {
+__global__ __launch_bounds__(kImeshThreads) void k_mo_volume(const float* __restrict__ verts, const int* __restrict__ faces, int n_faces,
+                                                             int n_verts, MoQuant g, const int* __restrict__ face_comp,
+                                                             const unsigned char* __restrict__ fstate, long long* vol_hi, long long* vol_lo) {
 #pragma clang fp contract(off)
     const long long step = (long long)gridDim.x * blockDim.x, end = ((long long)n_faces + 63) & ~63ll;
     const int lane = threadIdx.x & 63;
@@ -222,9 +220,9 @@ __global__ __launch_bounds__(kMoThreads) void k_mo_volume(const float* __restric
     }
 }
 
-__global__ __launch_bounds__(kMoThreads) void k_mo_decide(const int* __restrict__ comp_faces, const int* __restrict__ comp_ones,
-                                                          const long long* __restrict__ vol_hi, const long long* __restrict__ vol_lo,
-                                                          int policy, int* __restrict__ comp_flags, int* counts) {
+__global__ __launch_bounds__(kImeshThreads) void k_mo_decide(const int* __restrict__ comp_faces, const int* __restrict__ comp_ones,
+                                                             const long long* __restrict__ vol_hi, const long long* __restrict__ vol_lo,
+                                                             int policy, int* __restrict__ comp_flags, int* counts) {
     const int n_comp = counts[1];
     const long long step = (long long)gridDim.x * blockDim.x, end = ((long long)n_comp + 63) & ~63ll;
     const int lane = threadIdx.x & 63;
@@ -250,9 +248,9 @@ __global__ __launch_bounds__(kMoThreads) void k_mo_decide(const int* __restrict_
     }
 }
 
-__global__ __launch_bounds__(kMoThreads) void k_mo_apply(const int* __restrict__ faces, int n_faces, const int* __restrict__ face_comp,
-                                                         const unsigned char* __restrict__ fstate, const int* __restrict__ comp_flags,
-                                                         unsigned char* __restrict__ flip, int* __restrict__ faces_out, int* counts) {
+__global__ __launch_bounds__(kImeshThreads) void k_mo_apply(const int* __restrict__ faces, int n_faces, const int* __restrict__ face_comp,
+                                                            const unsigned char* __restrict__ fstate, const int* __restrict__ comp_flags,
+                                                            unsigned char* __restrict__ flip, int* __restrict__ faces_out, int* counts) {
     const long long step = (long long)gridDim.x * blockDim.x, end = ((long long)n_faces + 63) & ~63ll;
     // terminates: end - f strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x; f < end; f += step) {
@@ -275,10 +273,10 @@ __global__ __launch_bounds__(kMoThreads) void k_mo_apply(const int* __restrict__
 }
 
 // ---- boundary loops ----------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kMoThreads) void k_mo_loop_init(int* __restrict__ parent, int* __restrict__ vout, int* __restrict__ vin,
-                                                             int* __restrict__ bad, int n_verts, int* __restrict__ loop_edges,
-                                                             unsigned char* __restrict__ loop_simple, int* __restrict__ loop_vert,
-                                                             int* __restrict__ counts) {
+__global__ __launch_bounds__(kImeshThreads) void k_mo_loop_init(int* __restrict__ parent, int* __restrict__ vout, int* __restrict__ vin,
+                                                                int* __restrict__ bad, int n_verts, int* __restrict__ loop_edges,
+                                                                unsigned char* __restrict__ loop_simple, int* __restrict__ loop_vert,
+                                                                int* __restrict__ counts) {
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_verts - v strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < n_verts; v += step) {
@@ -293,8 +291,7 @@ __global__ __launch_bounds__(kMoThreads) void k_mo_loop_init(int* __restrict__ p
     if (blockIdx.x == 0 && threadIdx.x < 3) counts[threadIdx.x] = 0;
 }
 
-// The count / scan / fill idiom of mcubes.hpp over a 0/1 mark per element, kMoChunk elements per workgroup; ids ascend with the
-// elements, so the order is preserved.  The number of elements is n, or *n_dev clamped to n when n_dev is given.
+// mesh_compact (meshcommon.hpp) over n elements, or over *n_dev clamped to [0, n] when n_dev is given.
 //   WHAT          element, mark                                                   fill
 //   kMoBoundary   (face, corner) i: the face is valid and one face lies on its    edges[id] = (a, b), edge_face[id] = face; the
 //                 edge a->b                                                       boundary degrees of a and b; union(a, b)
@@ -314,68 +311,47 @@ struct MoCompact {
     int* faces_out; int* face_loop;
 };
 
+struct MoElement {
+    int a, b;   // kMoBoundary: the half-edge a->b
+    int of;     // kMoBoundary: its face; kMoFilled: its loop
+};
+
 template <int WHAT, bool FILL>
-__global__ __launch_bounds__(kMoThreads) void k_mo_compact(MoCompact p, int n, const int* __restrict__ n_dev, int* __restrict__ blk_count,
-                                                           const int* __restrict__ blk_base) {
-#pragma clang fp contract(off)
-    __shared__ int wsum[kMoThreads / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long first = (long long)blockIdx.x * kMoChunk;
+__global__ __launch_bounds__(kImeshThreads) void k_mo_compact(MoCompact p, int n, const int* __restrict__ n_dev, int* __restrict__ blk_count,
+                                                              const int* __restrict__ blk_base) {
     const long long count = n_dev ? min(max((long long)*n_dev, 0ll), (long long)n) : (long long)n;
-    int done = 0;   // marks of this chunk in front of the current pass
-#pragma unroll 1
-    for (int z0 = 0; z0 < kMoChunk; z0 += kMoThreads) {   // terminates: kMoChunk - z0 strictly decreases to 0
-        const long long i = first + z0 + tid;
-        const bool ok = i < count;
-        bool mark = false;
-        int x = 0, y = 0, z = 0;
-        if (ok) {
+    mesh_compact<FILL, MoElement>(
+        count, blk_count, blk_base,
+        [&](long long i, MoElement& e) {
             if constexpr (WHAT == kMoBoundary) {
                 const int f = (int)(i / 3), c = (int)(i - 3 * (long long)f);
                 int id[3];
-                if (ma_face_ok(p.faces, f, p.n_verts, id)) {
-                    x = id[c];
-                    y = id[(c + 1) % 3];
-                    z = f;
-                    mark = mo_edge_faces(p.nbr_start, p.nbr, p.nbr_out, p.nbr_in, 6 * (long long)p.n_faces, x, y) == 1;
-                }
+                if (!ma_face_ok(p.faces, f, p.n_verts, id)) return false;
+                e.a = id[c];
+                e.b = id[(c + 1) % 3];
+                e.of = f;
+                return mo_edge_faces(p.nbr_start, p.nbr, p.nbr_out, p.nbr_in, 6 * (long long)p.n_faces, e.a, e.b) == 1;
             }
             if constexpr (WHAT == kMoLoops) {
                 const int m = p.loop_edges[i];
-                mark = p.loop_simple[i] != 0 && m >= 3 && m <= p.max_edges && p.nonfinite[i] == 0;
+                return p.loop_simple[i] != 0 && m >= 3 && m <= p.max_edges && p.nonfinite[i] == 0;
             }
             if constexpr (WHAT == kMoFilled) {
-                z = p.edge_loop[i];
-                mark = (unsigned)z < (unsigned)p.n_loops_cap && p.lrank[z] >= 0;
+                e.of = p.edge_loop[i];
+                return (unsigned)e.of < (unsigned)p.n_loops_cap && p.lrank[e.of] >= 0;
             }
-        }
-        // exclusive prefix of the marks over the workgroup, in thread order
-        const int cnt = mark ? 1 : 0;
-        int inc = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(inc, o);
-            if (lane >= o) inc += v;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < kMoThreads / 64; ++w) {
-            if (w < wave) before += wsum[w];
-            total += wsum[w];
-        }
-        __syncthreads();
-        if constexpr (FILL) {
-            const long long at = (long long)blk_base[blockIdx.x] + done + before + inc - cnt;
+        },
+        [&](long long i, bool ok, bool mark, int id, const MoElement& e) {
+#pragma clang fp contract(off)
+            const long long at = id;
             if constexpr (WHAT == kMoBoundary) {
                 if (mark) {   // at < the marks in all <= 3 F: the rows of edges and edge_face
-                    p.edges[2 * at + 0] = x;
-                    p.edges[2 * at + 1] = y;
-                    p.edge_face[at] = z;
-                    atomicAdd(&p.vout[x], 1);
-                    atomicAdd(&p.vin[y], 1);
-                    cc_union(p.parent, x, y);
+                    p.edges[2 * at + 0] = e.a;
+                    p.edges[2 * at + 1] = e.b;
+                    p.edge_face[at] = e.of;
+                    atomicAdd(&p.vout[e.a], 1);
+                    atomicAdd(&p.vin[e.b], 1);
+                    cc_union(p.parent, e.a, e.b);
                 }
             }
             if constexpr (WHAT == kMoLoops) {
@@ -396,29 +372,26 @@ __global__ __launch_bounds__(kMoThreads) void k_mo_compact(MoCompact p, int n, c
                     const long long row = (long long)p.n_faces + at;
                     p.faces_out[3 * row + 0] = p.edges_in[2 * i + 1];
                     p.faces_out[3 * row + 1] = p.edges_in[2 * i + 0];
-                    p.faces_out[3 * row + 2] = p.n_verts + p.lrank[z];
-                    p.face_loop[row] = z;
+                    p.faces_out[3 * row + 2] = p.n_verts + p.lrank[e.of];
+                    p.face_loop[row] = e.of;
                 }
             }
-        }
-        done += total;
-    }
-    if (!FILL && tid == 0) blk_count[blockIdx.x] = done;
+        });
 }
 
 // root[v] = the smallest vertex of v's loop for a vertex on a boundary half-edge, -1 for every other one: the marks root[v] == v
 // of k_cc_compact<kCcRoots> are then the loops' smallest vertices.  Read-only on parent (the launch boundary made it final).
-__global__ __launch_bounds__(kMoThreads) void k_mo_loop_flatten(const int* __restrict__ parent, const int* __restrict__ vout,
-                                                                const int* __restrict__ vin, int n_verts, int* __restrict__ root) {
+__global__ __launch_bounds__(kImeshThreads) void k_mo_loop_flatten(const int* __restrict__ parent, const int* __restrict__ vout,
+                                                                   const int* __restrict__ vin, int n_verts, int* __restrict__ root) {
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_verts - v strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < n_verts; v += step)
         root[v] = vout[v] + vin[v] > 0 ? cc_walk(parent, (int)v) : -1;
 }
 
-__global__ __launch_bounds__(kMoThreads) void k_mo_loop_verts(const int* __restrict__ root, const int* __restrict__ dense,
-                                                              const int* __restrict__ vout, const int* __restrict__ vin, int n_verts,
-                                                              int* __restrict__ loop_vert, int* bad) {
+__global__ __launch_bounds__(kImeshThreads) void k_mo_loop_verts(const int* __restrict__ root, const int* __restrict__ dense,
+                                                                 const int* __restrict__ vout, const int* __restrict__ vin, int n_verts,
+                                                                 int* __restrict__ loop_vert, int* bad) {
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_verts - v strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < n_verts; v += step) {
@@ -430,9 +403,9 @@ __global__ __launch_bounds__(kMoThreads) void k_mo_loop_verts(const int* __restr
     }
 }
 
-__global__ __launch_bounds__(kMoThreads) void k_mo_loop_edges(const int* __restrict__ edges, int cap, const int* __restrict__ root,
-                                                              const int* __restrict__ dense, const int* __restrict__ counts,
-                                                              int* __restrict__ edge_loop, int* loop_edges) {
+__global__ __launch_bounds__(kImeshThreads) void k_mo_loop_edges(const int* __restrict__ edges, int cap, const int* __restrict__ root,
+                                                                 const int* __restrict__ dense, const int* __restrict__ counts,
+                                                                 int* __restrict__ edge_loop, int* loop_edges) {
     const int n_edges = min(max(counts[0], 0), cap);
     const long long step = (long long)gridDim.x * blockDim.x, end = ((long long)n_edges + 63) & ~63ll;
     // terminates: end - e strictly decreases (step >= 1) and the loop ends when it reaches 0
@@ -444,8 +417,8 @@ __global__ __launch_bounds__(kMoThreads) void k_mo_loop_edges(const int* __restr
     }
 }
 
-__global__ __launch_bounds__(kMoThreads) void k_mo_loop_finish(const int* __restrict__ bad, int n_verts, unsigned char* __restrict__ loop_simple,
-                                                               int* counts) {
+__global__ __launch_bounds__(kImeshThreads) void k_mo_loop_finish(const int* __restrict__ bad, int n_verts, unsigned char* __restrict__ loop_simple,
+                                                                  int* counts) {
     const int n_loops = min(max(counts[1], 0), n_verts);
     const long long step = (long long)gridDim.x * blockDim.x, end = ((long long)n_loops + 63) & ~63ll;
     // terminates: end - l strictly decreases (step >= 1) and the loop ends when it reaches 0
@@ -458,8 +431,8 @@ __global__ __launch_bounds__(kMoThreads) void k_mo_loop_finish(const int* __rest
 }
 
 // ---- hole filling --------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kMoThreads) void k_mo_fill_init(long long* __restrict__ sums, int* __restrict__ nonfinite, int n_verts,
-                                                             const int* __restrict__ loop_counts, int* __restrict__ counts) {
+__global__ __launch_bounds__(kImeshThreads) void k_mo_fill_init(long long* __restrict__ sums, int* __restrict__ nonfinite, int n_verts,
+                                                                const int* __restrict__ loop_counts, int* __restrict__ counts) {
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_verts - v strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < n_verts; v += step) {
@@ -471,10 +444,10 @@ __global__ __launch_bounds__(kMoThreads) void k_mo_fill_init(long long* __restri
     if (blockIdx.x == 0 && threadIdx.x < 5) counts[threadIdx.x] = threadIdx.x < 3 ? loop_counts[threadIdx.x] : 0;
 }
 
-__global__ __launch_bounds__(kMoThreads) void k_mo_fill_accum(const float* __restrict__ verts, int n_verts, const int* __restrict__ edges,
-                                                              const int* __restrict__ edge_loop, int cap, const int* __restrict__ loop_counts,
-                                                              const int* __restrict__ loop_edges, const unsigned char* __restrict__ loop_simple,
-                                                              int max_edges, MoQuant g, long long* sums, int* nonfinite) {
+__global__ __launch_bounds__(kImeshThreads) void k_mo_fill_accum(const float* __restrict__ verts, int n_verts, const int* __restrict__ edges,
+                                                                 const int* __restrict__ edge_loop, int cap, const int* __restrict__ loop_counts,
+                                                                 const int* __restrict__ loop_edges, const unsigned char* __restrict__ loop_simple,
+                                                                 int max_edges, MoQuant g, long long* sums, int* nonfinite) {
 #pragma clang fp contract(off)
     const int n_edges = min(max(loop_counts[0], 0), cap);
     const long long step = (long long)gridDim.x * blockDim.x;
@@ -500,9 +473,9 @@ __global__ __launch_bounds__(kMoThreads) void k_mo_fill_accum(const float* __res
     }
 }
 
-__global__ __launch_bounds__(kMoThreads) void k_mo_fill_copy(const float* __restrict__ verts, int n_verts, const int* __restrict__ faces,
-                                                             int n_faces, float* __restrict__ verts_out, int* __restrict__ vert_src,
-                                                             int* __restrict__ faces_out, int* __restrict__ face_loop) {
+__global__ __launch_bounds__(kImeshThreads) void k_mo_fill_copy(const float* __restrict__ verts, int n_verts, const int* __restrict__ faces,
+                                                                int n_faces, float* __restrict__ verts_out, int* __restrict__ vert_src,
+                                                                int* __restrict__ faces_out, int* __restrict__ face_loop) {
     const long long step = (long long)gridDim.x * blockDim.x, n = max((long long)n_verts, (long long)n_faces);
     // terminates: n - i strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {

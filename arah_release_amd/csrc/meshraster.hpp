@@ -39,8 +39,7 @@
 // spin-wait, no grid-wide barrier, nothing persistent; every loop ends by an argument of its own, stated at the loop.
 #pragma once
 
-constexpr int kMrThreads = 256;
-constexpr int kMrMaxGrid = 1 << 14;
+constexpr int kMrMaxGrid = 1 << 14;      // its own cap, a quarter of kImeshMaxGrid; kImeshThreads is meshcommon.hpp's
 // the three thresholds as measured on the 256^3 body and its simplified meshes at 512^2 and 1024^2 (profiles/mesh_render_bench.txt)
 constexpr int kMrSmallArea = 16;         // pixels of a clipped bounding box one lane still walks alone
 constexpr int kMrWaveArea = 64;          // ... the face's wave still walks: one round of its 64 lanes
@@ -118,18 +117,18 @@ __device__ __forceinline__ void mr_draw(const MrFace& t, unsigned face, unsigned
     }
 }
 
-__global__ __launch_bounds__(kMrThreads) void k_mr_init(unsigned long long* __restrict__ keys, long long n_pix, unsigned* __restrict__ counters) {
+__global__ __launch_bounds__(kImeshThreads) void k_mr_init(unsigned long long* __restrict__ keys, long long n_pix, unsigned* __restrict__ counters) {
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_pix - p strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < n_pix; p += step) keys[p] = kMrEmpty;
     if (blockIdx.x == 0 && threadIdx.x < 2) counters[threadIdx.x] = 0u;
 }
 
-__global__ __launch_bounds__(kMrThreads) void k_mr_scatter(const float* __restrict__ verts, int n_verts, const int* __restrict__ faces,
-                                                           int n_faces, int H, int W, float z_near, int cull, int small_area,
-                                                           int wave_area, int huge_area, unsigned long long* __restrict__ keys,
-                                                           int* __restrict__ med_list, int* __restrict__ huge_list, unsigned cap,
-                                                           unsigned* counters) {
+__global__ __launch_bounds__(kImeshThreads) void k_mr_scatter(const float* __restrict__ verts, int n_verts, const int* __restrict__ faces,
+                                                              int n_faces, int H, int W, float z_near, int cull, int small_area,
+                                                              int wave_area, int huge_area, unsigned long long* __restrict__ keys,
+                                                              int* __restrict__ med_list, int* __restrict__ huge_list, unsigned cap,
+                                                              unsigned* counters) {
     const long long step = (long long)gridDim.x * blockDim.x, end = ((long long)n_faces + 63) & ~63ll;
     const unsigned lane = threadIdx.x & 63;
     // terminates: end - f strictly decreases (step >= 1) and the loop ends when it reaches 0.  The face count is rounded up to
@@ -169,18 +168,18 @@ __global__ __launch_bounds__(kMrThreads) void k_mr_scatter(const float* __restri
     }
 }
 
-__global__ __launch_bounds__(kMrThreads) void k_mr_lists(const float* __restrict__ verts, int n_verts, const int* __restrict__ faces,
-                                                         int n_faces, int H, int W, float z_near, int cull,
-                                                         unsigned long long* __restrict__ keys, const int* __restrict__ med_list,
-                                                         const int* __restrict__ huge_list, unsigned cap,
-                                                         const unsigned* __restrict__ counters) {
+__global__ __launch_bounds__(kImeshThreads) void k_mr_lists(const float* __restrict__ verts, int n_verts, const int* __restrict__ faces,
+                                                            int n_faces, int H, int W, float z_near, int cull,
+                                                            unsigned long long* __restrict__ keys, const int* __restrict__ med_list,
+                                                            const int* __restrict__ huge_list, unsigned cap,
+                                                            const unsigned* __restrict__ counters) {
     const unsigned n_med = min(counters[0], cap), n_huge = min(counters[1], cap);
     // terminates: n_med - li strictly decreases (gridDim.x >= 1).  li and the face are the same for every thread of the workgroup
     for (unsigned li = blockIdx.x; li < n_med; li += gridDim.x) {
         const int f = med_list[li];
         MrFace t;
         if ((unsigned)f >= (unsigned)n_faces || !mr_setup(verts, n_verts, faces, f, H, W, z_near, cull, t)) continue;
-        mr_draw(t, (unsigned)f, threadIdx.x, (unsigned)t.n, kMrThreads, W, keys);
+        mr_draw(t, (unsigned)f, threadIdx.x, (unsigned)t.n, kImeshThreads, W, keys);
     }
     const unsigned long long items = (unsigned long long)n_huge * kMrParts;
     // terminates: items - w strictly decreases (gridDim.x >= 1).  Item w is part w % kMrParts of the face huge_list[w / kMrParts]
@@ -191,14 +190,14 @@ __global__ __launch_bounds__(kMrThreads) void k_mr_lists(const float* __restrict
         if ((unsigned)f >= (unsigned)n_faces || !mr_setup(verts, n_verts, faces, f, H, W, z_near, cull, t)) continue;
         const unsigned n = (unsigned)t.n, per = (n + kMrParts - 1) / kMrParts;   // kMrParts * per >= n
         const unsigned lo = min(n, part * per), hi = min(n, lo + per);            // part * per <= n + kMrParts: no wrap
-        mr_draw(t, (unsigned)f, lo + threadIdx.x, hi, kMrThreads, W, keys);
+        mr_draw(t, (unsigned)f, lo + threadIdx.x, hi, kImeshThreads, W, keys);
     }
 }
 
-__global__ __launch_bounds__(kMrThreads) void k_mr_resolve(const float* __restrict__ verts, int n_verts, const int* __restrict__ faces,
-                                                           int n_faces, int H, int W, const unsigned long long* __restrict__ keys,
-                                                           int* __restrict__ pix_to_face, float* __restrict__ depth,
-                                                           float* __restrict__ bary) {
+__global__ __launch_bounds__(kImeshThreads) void k_mr_resolve(const float* __restrict__ verts, int n_verts, const int* __restrict__ faces,
+                                                              int n_faces, int H, int W, const unsigned long long* __restrict__ keys,
+                                                              int* __restrict__ pix_to_face, float* __restrict__ depth,
+                                                              float* __restrict__ bary) {
 #pragma clang fp contract(off)
     const long long step = (long long)gridDim.x * blockDim.x, n_pix = (long long)H * W;
     // terminates: n_pix - p strictly decreases (step >= 1) and the loop ends when it reaches 0
@@ -236,10 +235,10 @@ __global__ __launch_bounds__(kMrThreads) void k_mr_resolve(const float* __restri
 }
 
 // ---- attributes: three rows of attr (V,C) gathered per pixel and mixed with bary, one thread per (pixel, channel) ---------------------
-__global__ __launch_bounds__(kMrThreads) void k_mr_interpolate(const int* __restrict__ pix_to_face, const float* __restrict__ bary,
-                                                               long long n_pix, const int* __restrict__ faces, int n_faces,
-                                                               const float* __restrict__ attr, int n_verts, int C, float background,
-                                                               float* __restrict__ out) {
+__global__ __launch_bounds__(kImeshThreads) void k_mr_interpolate(const int* __restrict__ pix_to_face, const float* __restrict__ bary,
+                                                                  long long n_pix, const int* __restrict__ faces, int n_faces,
+                                                                  const float* __restrict__ attr, int n_verts, int C, float background,
+                                                                  float* __restrict__ out) {
 #pragma clang fp contract(off)
     const long long step = (long long)gridDim.x * blockDim.x, n = n_pix * C;
     // terminates: n - q strictly decreases (step >= 1) and the loop ends when it reaches 0

@@ -31,7 +31,7 @@
 //   k_ms_classify  one thread per face: invalid / collapsed / survivor; a survivor claims the slot of its key (atomicCAS on the
 //                  key, probing linearly) and atomicMin's its row into the slot; fslot[f] = the slot, or -1 for a face that goes
 //   k_ms_compact<false>, k_mc_scan, k_ms_compact<true>
-//                  the count / scan / fill of k_cc_compact over the mark "fslot[f] >= 0 and the slot's row is f": kept faces in
+//                  the count / scan / fill of meshcommon.hpp over the mark "fslot[f] >= 0 and the slot's row is f": kept faces in
 //                  their original order and orientation, face_src; rows from the count on zeroed; counts[4] by subtraction
 //
 // Integer atomics only (or, add, min, compare-and-swap): none of the results depends on the order of arrival -- the table's
@@ -39,9 +39,6 @@
 // grid-wide barrier; every loop ends by an argument of its own, stated at the loop.
 #pragma once
 
-constexpr int kMsThreads = 256;
-constexpr int kMsChunk = 1024;            // faces per workgroup of the count / fill walks: 4 passes of kMsThreads
-constexpr int kMsMaxGrid = 1 << 16;
 constexpr int kMsKeyBits = 21;            // bits of a cluster id inside a face's key
 constexpr double kMsFixLimit = 68719476736.0;   // 2^36
 constexpr unsigned long long kMsEmpty = ~0ull;   // no key: a key has 63 bits
@@ -76,10 +73,10 @@ __device__ __forceinline__ float ms_mean(const MsGrid& g, const long long* __res
     return (float)((double)g.origin[a] + ((double)S[3 * (size_t)k + a] / (double)members[k]) / g.scale);
 }
 
-__global__ __launch_bounds__(kMsThreads) void k_ms_init(unsigned* __restrict__ bitmap, long long n_words, long long* __restrict__ S,
-                                                        int* __restrict__ members, unsigned long long* __restrict__ best, int n_verts,
-                                                        unsigned long long* __restrict__ tkeys, int* __restrict__ trows,
-                                                        long long n_slots, int* __restrict__ counts) {
+__global__ __launch_bounds__(kImeshThreads) void k_ms_init(unsigned* __restrict__ bitmap, long long n_words, long long* __restrict__ S,
+                                                           int* __restrict__ members, unsigned long long* __restrict__ best, int n_verts,
+                                                           unsigned long long* __restrict__ tkeys, int* __restrict__ trows,
+                                                           long long n_slots, int* __restrict__ counts) {
     const long long step = (long long)gridDim.x * blockDim.x;
     const long long end = max(max(n_words, (long long)n_verts), n_slots);
     // terminates: end - i strictly decreases (step >= 1) and the loop ends when it reaches 0
@@ -100,8 +97,8 @@ __global__ __launch_bounds__(kMsThreads) void k_ms_init(unsigned* __restrict__ b
     if (blockIdx.x == 0 && threadIdx.x < 6) counts[threadIdx.x] = 0;
 }
 
-__global__ __launch_bounds__(kMsThreads) void k_ms_mark(const float* __restrict__ verts, int n_verts, MsGrid g, int* __restrict__ vkey,
-                                                        unsigned* bitmap) {
+__global__ __launch_bounds__(kImeshThreads) void k_ms_mark(const float* __restrict__ verts, int n_verts, MsGrid g, int* __restrict__ vkey,
+                                                           unsigned* bitmap) {
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_verts - v strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < n_verts; v += step) {
@@ -112,16 +109,16 @@ __global__ __launch_bounds__(kMsThreads) void k_ms_mark(const float* __restrict_
     }
 }
 
-__global__ __launch_bounds__(kMsThreads) void k_ms_popc(const unsigned* __restrict__ bitmap, long long n_words, int* __restrict__ wcount) {
+__global__ __launch_bounds__(kImeshThreads) void k_ms_popc(const unsigned* __restrict__ bitmap, long long n_words, int* __restrict__ wcount) {
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_words - w strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x; w < n_words; w += step) wcount[w] = __popc(bitmap[w]);
 }
 
-__global__ __launch_bounds__(kMsThreads) void k_ms_accum(const float* __restrict__ verts, int n_verts, MsGrid g,
-                                                         const int* __restrict__ vkey, const unsigned* __restrict__ bitmap,
-                                                         const int* __restrict__ wbase, int* __restrict__ vert_map, long long* S,
-                                                         int* members) {
+__global__ __launch_bounds__(kImeshThreads) void k_ms_accum(const float* __restrict__ verts, int n_verts, MsGrid g,
+                                                            const int* __restrict__ vkey, const unsigned* __restrict__ bitmap,
+                                                            const int* __restrict__ wbase, int* __restrict__ vert_map, long long* S,
+                                                            int* members) {
 #pragma clang fp contract(off)
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_verts - v strictly decreases (step >= 1) and the loop ends when it reaches 0
@@ -144,9 +141,9 @@ __global__ __launch_bounds__(kMsThreads) void k_ms_accum(const float* __restrict
     }
 }
 
-__global__ __launch_bounds__(kMsThreads) void k_ms_pick(const float* __restrict__ verts, int n_verts, MsGrid g,
-                                                        const int* __restrict__ vert_map, const long long* __restrict__ S,
-                                                        const int* __restrict__ members, unsigned long long* best) {
+__global__ __launch_bounds__(kImeshThreads) void k_ms_pick(const float* __restrict__ verts, int n_verts, MsGrid g,
+                                                           const int* __restrict__ vert_map, const long long* __restrict__ S,
+                                                           const int* __restrict__ members, unsigned long long* best) {
 #pragma clang fp contract(off)
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_verts - v strictly decreases (step >= 1) and the loop ends when it reaches 0
@@ -162,10 +159,10 @@ __global__ __launch_bounds__(kMsThreads) void k_ms_pick(const float* __restrict_
     }
 }
 
-__global__ __launch_bounds__(kMsThreads) void k_ms_finish(const float* __restrict__ verts, int n_verts, MsGrid g, int use_member,
-                                                          int dedup, const long long* __restrict__ S, const int* __restrict__ members,
-                                                          const unsigned long long* __restrict__ best, int* counts,
-                                                          float* __restrict__ verts_out, int* __restrict__ vert_src) {
+__global__ __launch_bounds__(kImeshThreads) void k_ms_finish(const float* __restrict__ verts, int n_verts, MsGrid g, int use_member,
+                                                             int dedup, const long long* __restrict__ S, const int* __restrict__ members,
+                                                             const unsigned long long* __restrict__ best, int* counts,
+                                                             float* __restrict__ verts_out, int* __restrict__ vert_src) {
     const int n_clusters = counts[0];
     // the status: three cluster ids of more than kMsKeyBits bits do not fit a face's key
     if (blockIdx.x == 0 && threadIdx.x == 0) counts[5] = dedup && n_clusters > (1 << kMsKeyBits) ? 1 : 0;
@@ -196,10 +193,10 @@ __device__ __forceinline__ unsigned long long ms_hash(unsigned long long x) {
     return x;
 }
 
-__global__ __launch_bounds__(kMsThreads) void k_ms_classify(const int* __restrict__ faces, int n_faces, int n_verts,
-                                                            const int* __restrict__ vert_map, int dedup,
-                                                            unsigned long long* tkeys, int* trows, long long n_slots,
-                                                            int* __restrict__ fslot, int* counts) {
+__global__ __launch_bounds__(kImeshThreads) void k_ms_classify(const int* __restrict__ faces, int n_faces, int n_verts,
+                                                               const int* __restrict__ vert_map, int dedup,
+                                                               unsigned long long* tkeys, int* trows, long long n_slots,
+                                                               int* __restrict__ fslot, int* counts) {
     const long long step = (long long)gridDim.x * blockDim.x, end = ((long long)n_faces + 63) & ~63ll;
     const int lane = threadIdx.x & 63;
     const bool too_many = counts[5] != 0;   // k_ms_finish set it: no face is kept
@@ -248,48 +245,23 @@ __global__ __launch_bounds__(kMsThreads) void k_ms_classify(const int* __restric
     }
 }
 
-// The count / scan / fill of k_cc_compact (meshcc.hpp) over the faces, kMsChunk per workgroup; a face is kept when it claimed a
-// slot and, with dedup, its row is the slot's minimum.  FILL also zeroes the rows from the kept count on (counts[1], final since
-// the scan) and derives the duplicates: what is neither invalid, collapsed nor kept -- nothing when the status is set.
+// mesh_compact (meshcommon.hpp) over the faces; a face is kept when it claimed a slot and, with dedup, its row is the slot's
+// minimum.  FILL also zeroes the rows from the kept count on (counts[1], final since the scan) and derives the duplicates: what is
+// neither invalid, collapsed nor kept -- nothing when the status is set.
 template <bool FILL>
-__global__ __launch_bounds__(kMsThreads) void k_ms_compact(const int* __restrict__ faces, int n_faces, const int* __restrict__ vert_map,
-                                                           const int* __restrict__ fslot, const int* __restrict__ trows, int dedup,
-                                                           int* __restrict__ blk_count, const int* __restrict__ blk_base,
-                                                           int* __restrict__ faces_out, int* __restrict__ face_src, int* counts) {
-    __shared__ int wsum[kMsThreads / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long first = (long long)blockIdx.x * kMsChunk;
+__global__ __launch_bounds__(kImeshThreads) void k_ms_compact(const int* __restrict__ faces, int n_faces, const int* __restrict__ vert_map,
+                                                              const int* __restrict__ fslot, const int* __restrict__ trows, int dedup,
+                                                              int* __restrict__ blk_count, const int* __restrict__ blk_base,
+                                                              int* __restrict__ faces_out, int* __restrict__ face_src, int* counts) {
     const int kept = FILL ? counts[1] : 0;
-    int done = 0;   // kept faces of this chunk in front of the current pass
-#pragma unroll 1
-    for (int z0 = 0; z0 < kMsChunk; z0 += kMsThreads) {   // terminates: kMsChunk - z0 strictly decreases to 0
-        const long long i = first + z0 + tid;
-        const bool ok = i < n_faces;
-        bool mark = false;
-        if (ok) {
+    mesh_compact<FILL, MeshNoState>(
+        n_faces, blk_count, blk_base,
+        [&](long long i, MeshNoState&) {
             const int slot = fslot[i];
-            mark = slot >= 0 && (!dedup || trows[slot] == (int)i);
-        }
-        // exclusive prefix of the marks over the workgroup, in thread order
-        const int cnt = mark ? 1 : 0;
-        int inc = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(inc, o);
-            if (lane >= o) inc += v;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < kMsThreads / 64; ++w) {
-            if (w < wave) before += wsum[w];
-            total += wsum[w];
-        }
-        __syncthreads();
-        if constexpr (FILL) {
+            return slot >= 0 && (!dedup || trows[slot] == (int)i);
+        },
+        [&](long long i, bool ok, bool mark, int at, const MeshNoState&) {
             if (mark) {   // at < kept <= n_faces
-                const int at = blk_base[blockIdx.x] + done + before + inc - cnt;
                 faces_out[3 * (long long)at + 0] = vert_map[faces[3 * i + 0]];
                 faces_out[3 * (long long)at + 1] = vert_map[faces[3 * i + 1]];
                 faces_out[3 * (long long)at + 2] = vert_map[faces[3 * i + 2]];
@@ -301,11 +273,8 @@ __global__ __launch_bounds__(kMsThreads) void k_ms_compact(const int* __restrict
                 faces_out[3 * i + 2] = 0;
                 face_src[i] = 0;
             }
-        }
-        done += total;
-    }
-    if (!FILL && tid == 0) blk_count[blockIdx.x] = done;
-    if (FILL && blockIdx.x == 0 && tid == 0) counts[4] = counts[5] ? 0 : n_faces - counts[2] - counts[3] - kept;
+        });
+    if (FILL && blockIdx.x == 0 && threadIdx.x == 0) counts[4] = counts[5] ? 0 : n_faces - counts[2] - counts[3] - kept;
 }
 
 // a mesh without a vertex: no cluster, every face invalid

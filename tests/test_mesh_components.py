@@ -367,6 +367,44 @@ def test_component_symbols_are_declared_and_exported():
         assert query(-1, 0) == 0 and query(0, -1) == 0 and query(2 ** 31, 0) == 0 and query(0, 2 ** 31) == 0
 
 
+# Every literal below is what the library of commit e16eaee (the last one with a hand-written layout per entry) returned, run on
+# the host: callers size their buffers with these queries, so the shared scratch carver must not move a byte.  0 = a rejected size.
+_BIG = (2 ** 31 - 1, 2 ** 28)
+_VF = ((0, 0), (1, 1), (1024, 1024), (1025, 1025), (1000, 2000), _BIG, (2 ** 31, 0))
+SCRATCH_BYTES = {
+    "mesh_components": (16, 36, 12312, 12332, 12024, 25786580996, 0),
+    "mesh_select": (16, 32, 32, 48, 40, 18874384, 0),
+    "mesh_adjacency": (256, 1280, 69632, 70912, 128512, 33285996544, 0),
+    "mesh_orient": (256, 1792, 22016, 23296, 43264, 5639241728, 0),
+    "mesh_boundary_loops": (256, 2560, 25600, 27136, 25600, 51562676224, 0),
+    "mesh_fill_holes": (256, 1792, 33792, 34560, 33280, 68742545408, 0),
+}
+SIMPLIFY_BYTES = {    # (V, F) -> n_cells = 1, 1000, 2^27; simplification takes at most 2^26 vertices, so _BIG is its rejected size
+    (0, 0): (768, 768, 50331648), (1, 1): (3328, 3328, 50334208), (1024, 1024): (70912, 70912, 50401792),
+    (1025, 1025): (96768, 96768, 50427648), (1000, 2000): (99072, 99072, 50429952), _BIG: (0, 0, 0),
+}
+MCUBES_BYTES = {2: 72, 33: 160652, 894: 2870841416, 895: 0}    # 3 * 895^3 edge keys do not fit int32
+
+
+def test_scratch_sizes_of_the_indexed_mesh_entries_are_those_of_the_hand_written_layouts():
+    from arah_release_amd import hip
+    lib = hip.load_library()
+    for name, want in SCRATCH_BYTES.items():
+        query = getattr(lib, "arah_%s_scratch_bytes" % name)
+        assert tuple(int(query(v, f)) for v, f in _VF) == want, name
+    for (v, f), want in SIMPLIFY_BYTES.items():
+        assert tuple(int(lib.arah_mesh_simplify_scratch_bytes(v, f, c)) for c in (1, 1000, 2 ** 27)) == want, (v, f)
+    assert int(lib.arah_mesh_simplify_scratch_bytes(1, 1, 0)) == 0
+    assert {n: int(lib.arah_marching_cubes_indexed_scratch_bytes(n)) for n in MCUBES_BYTES} == MCUBES_BYTES
+    # The one value that is NOT e16eaee's: its simplify layout took max() of two size_t through a 32-bit overload and returned
+    # 1612710656, this sum modulo 2^32, for the largest mesh it accepts -- and the entry checked the caller's buffer against that.
+    # The blocks add up to: bitmap, wcount, wbase 256 each; vkey 2^28; sums 3 * 2^29; members 2^28; best 2^29; fslot 2^30; 2^29
+    # slots of 8 + 4 bytes; two block arrays of 2^18 ints
+    want = 3 * 256 + 2 ** 28 + 3 * 2 ** 29 + 2 ** 28 + 2 ** 29 + 2 ** 30 + 12 * 2 ** 29 + 2 * 2 ** 20
+    assert want == 10202645248 and want % 2 ** 32 == 1612710656
+    assert int(lib.arah_mesh_simplify_scratch_bytes(2 ** 26, 2 ** 28, 1)) == want
+
+
 # ---- GPU: the kernels against the specification ---------------------------------------------------------------------------------
 def strip(n_faces):
     i = torch.arange(n_faces)

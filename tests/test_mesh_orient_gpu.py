@@ -135,6 +135,44 @@ def test_c_entries_on_the_tests_own_buffers(name):
     assert all(bool((p == SENTINEL).all()) for p in lpads + fpads), name
 
 
+def _open_strip(n_faces):
+    """A consistently oriented open triangle strip: F faces over F + 2 vertices, whose boundary is one simple loop of F + 2 half-edges."""
+    i = torch.arange(n_faces)
+    odd = i % 2 == 1
+    faces = torch.stack([torch.where(odd, i + 1, i), torch.where(odd, i, i + 1), i + 2], 1)
+    k = torch.arange(n_faces + 2)
+    return torch.stack([0.25 * (k // 2), 1.0 * (k % 2), 0.125 * (k % 3)], 1).float(), faces
+
+
+def _disjoint_triangles(n):
+    """n triangles that share nothing: 3 n vertices, n simple loops of 3 half-edges each."""
+    k = torch.arange(n).float()[:, None, None]
+    corner = torch.tensor([[0.0, 0.0, 0.0], [0.5, 0.0, 0.25], [0.0, 0.75, 0.125]])
+    return (corner[None] + k * torch.tensor([1.0, 0.0, 0.0])).reshape(3 * n, 3), torch.arange(3 * n).reshape(n, 3)
+
+
+# The three instances of k_mo_compact on either side of a chunk of 1024 elements, which the named meshes never reach.  Strips: the
+# boundary walk covers 3 F = 1023, 1026, 2049 (face, corner) pairs.  Disjoint triangles: the loop walk covers 3 n slots and is cut
+# at the n loops the device counted, the filled-edge walk covers 3 n boundary edges.
+@pytest.mark.parametrize("family, n, max_edges", [("strip", 341, 4096), ("strip", 342, 4096), ("strip", 683, 4096),
+                                                   ("triangles", 1024, 3), ("triangles", 1025, 3)])
+def test_compaction_walks_on_either_side_of_a_chunk(family, n, max_edges):
+    from arah_release_amd import meshing
+    verts, faces = _open_strip(n) if family == "strip" else _disjoint_triangles(n)
+    V, F = verts.shape[0], faces.shape[0]
+    want_loops = meshing.mesh_boundary_loops(faces, V)
+    want_fill = meshing.mesh_fill_holes(verts, faces, max_edges=max_edges)
+    if family == "strip":                                                          # one loop round the strip, closed by one fan
+        assert want_loops[-1].tolist() == [n + 2, 1, 1] and want_fill[-1].tolist() == [n + 2, 1, 1, 1, n + 2]
+    else:                                                                          # n loops, n added vertices, 3 n added faces
+        assert (V, V // 3) == (3 * n, n) and want_loops[-1].tolist() == [3 * n, n, n] and want_fill[-1].tolist() == [3 * n, n, n, n, 3 * n]
+        assert want_fill[1][V:].tolist() == list(range(0, V, 3)) and bool((want_fill[3][F:] == torch.arange(n).repeat_interleave(3)).all())
+    loops, lpads, fill, fpads = raw_loops_and_fill(verts, faces, max_edges, meshing.fill_quant(verts))
+    _same(loops, want_loops, LOOP_NAMES, (family, n))
+    _same(fill, want_fill, FILL_NAMES, (family, n))
+    assert all(bool((p == SENTINEL).all()) for p in lpads + fpads), (family, n)
+
+
 def test_faces_without_vertices_and_vertices_without_faces():
     from arah_release_amd import hip, meshing
     verts, faces = mesh("sphere17_r")
