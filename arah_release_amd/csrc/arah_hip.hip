@@ -1954,6 +1954,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_canon_solve(FrameDev fr, const 
 #include "meshcc.hpp"
 #include "meshsimp.hpp"
 #include "meshadj.hpp"
+#include "meshquadric.hpp"
 #include "meshorient.hpp"
 #include "meshraster.hpp"
 #include "canon_wave.hpp"
@@ -4258,6 +4259,75 @@ int arah_mesh_simplify(const float* verts, int64_t n_verts, const int32_t* faces
                            (const int*)vert_map, (const int*)L.fslot, (const int*)L.trows, dd, count, base, (int*)faces_out,
                            (int*)face_src, (int*)counts);
     });
+    return check_launch();
+}
+
+// ---- quadric-error placement of the clusters of arah_mesh_simplify (csrc/meshquadric.hpp) -------------------------------------
+struct MqScratch {
+    int *cnt, *start, *cursor;
+    unsigned *raw, *seg;
+    unsigned long long* best;
+    size_t bytes;
+};
+
+static bool mq_sizes_ok(int64_t n_verts, int64_t n_faces) {
+    return n_verts >= 0 && n_faces >= 0 && n_verts <= ((int64_t)1 << 26) && n_faces <= ((int64_t)1 << 28);   // 3 F pairs fit an int32
+}
+
+static MqScratch carve_quadric(void* scratch, int64_t n_verts, int64_t n_faces) {
+    MqScratch w{};
+    MeshCarver c(scratch);
+    w.cnt = c.take<int>((size_t)n_verts);
+    w.start = c.take<int>((size_t)n_verts + 1);
+    w.cursor = c.take<int>((size_t)n_verts);
+    w.raw = c.take<unsigned>(3 * (size_t)n_faces);
+    w.seg = c.take<unsigned>(3 * (size_t)n_faces);
+    w.best = c.take<unsigned long long>((size_t)n_verts);
+    w.bytes = c.bytes();
+    return w;
+}
+
+size_t arah_mesh_quadric_place_scratch_bytes(int64_t n_verts, int64_t n_faces) {
+    if (!mq_sizes_ok(n_verts, n_faces)) return 0;
+    return carve_quadric(nullptr, n_verts, n_faces).bytes;
+}
+
+int arah_mesh_quadric_place(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int32_t* vert_map,
+                            const float* means, const int32_t* counts, float cell, double reg, float* pos_out, int32_t* vert_src_out,
+                            int32_t* qcounts, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!mq_sizes_ok(n_verts, n_faces) || !counts || !qcounts || !scratch) return ARAH_E_BADARG;
+    if (!std::isfinite(cell) || !(cell > 0.0f) || !std::isfinite(reg) || !(reg >= 0.0)) return ARAH_E_BADARG;
+    if ((n_verts > 0 && (!verts || !vert_map || !means || !pos_out || !vert_src_out)) || (n_faces > 0 && !faces)) return ARAH_E_BADARG;
+    const MqScratch w = carve_quadric(scratch, n_verts, n_faces);
+    if (scratch_bytes < w.bytes) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int V = (int)n_verts, F = (int)n_faces;
+    if (V == 0) {   // no vertex, so no cluster and no valid face
+        hipLaunchKernelGGL(k_mq_set_empty, dim3(1), dim3(64), 0, s, (int*)qcounts);
+        return check_launch();
+    }
+    const int* vm = (const int*)vert_map;
+    const int* K = (const int*)counts;
+    const dim3 tb(kImeshThreads), gv(mesh_grid(V)), gl(min(V, kMqLongGrid));
+    hipLaunchKernelGGL(k_mq_init, gv, tb, 0, s, w.cnt, w.cursor, w.best, V, (int*)qcounts);
+    if (F > 0)
+        hipLaunchKernelGGL((k_mq_pairs<false>), dim3(mesh_grid(F)), tb, 0, s, (const int*)faces, F, V, vm, K, w.cnt, (const int*)nullptr,
+                           (unsigned*)nullptr);
+    mesh_scan(s, w.cnt, V, w.start, w.start + V);
+    if (F > 0) {
+        hipLaunchKernelGGL((k_mq_pairs<true>), dim3(mesh_grid(F)), tb, 0, s, (const int*)faces, F, V, vm, K, w.cursor, (const int*)w.start,
+                           w.raw);
+        hipLaunchKernelGGL(k_mq_sort_short, gv, tb, 0, s, (const int*)w.start, (const int*)w.cnt, V, K, (const unsigned*)w.raw, w.seg);
+        hipLaunchKernelGGL(k_mq_sort_long, gl, tb, 0, s, (const int*)w.start, (const int*)w.cnt, V, K, (const unsigned*)w.raw, w.seg);
+    }
+    hipLaunchKernelGGL(k_mq_place_short, gv, tb, 0, s, verts, (const int*)faces, V, K, means, (const int*)w.start, (const int*)w.cnt,
+                       (const unsigned*)w.seg, (double)cell, reg, pos_out, (int*)qcounts);
+    if (F > 0)
+        hipLaunchKernelGGL(k_mq_place_long, gl, tb, 0, s, verts, (const int*)faces, V, K, means, (const int*)w.start, (const int*)w.cnt,
+                           (const unsigned*)w.seg, (double)cell, reg, pos_out, (int*)qcounts);
+    hipLaunchKernelGGL(k_mq_pick, gv, tb, 0, s, verts, V, vm, K, (const float*)pos_out, w.best);
+    hipLaunchKernelGGL(k_mq_finish, gv, tb, 0, s, V, K, (const int*)w.start, (const unsigned long long*)w.best, pos_out, (int*)vert_src_out,
+                       (int*)qcounts);
     return check_launch();
 }
 

@@ -1,5 +1,5 @@
-// meshcommon.hpp -- what the indexed-mesh headers share (mcubes.hpp, meshcc.hpp, meshsimp.hpp, meshadj.hpp, meshorient.hpp,
-// meshraster.hpp): the launch constants, the workgroup prefix, the ordered compaction walk, the one-workgroup scan, the padding of
+// meshcommon.hpp -- what the indexed-mesh headers share (mcubes.hpp, meshcc.hpp, meshsimp.hpp, meshadj.hpp, meshquadric.hpp,
+// meshorient.hpp, meshraster.hpp): the launch constants, the workgroup prefix, the ordered compaction walk, the one-workgroup scan, the padding of
 // the rows between a count and a capacity, and cc_add_one.  DESIGN.md ("Indexed meshes: the shared walk and the scratch carver")
 // tells the same once for the host side.  The query-side headers (meshquery.hpp ... pointdist.hpp, metrics.hpp) share nothing
 // with this file: their prefix sums include a float64 one whose summation order is part of their specification.

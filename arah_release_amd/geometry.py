@@ -484,13 +484,14 @@ def clean_mesh(verts, faces, keep="largest", attributes=None):
 
 
 # ---- simplification by vertex clustering ------------------------------------------------------------------------------------------
-_SIMPLIFY_KEYS = ("cell", "resolution", "bounds", "position", "dedup", "drop_unreferenced")
+_SIMPLIFY_KEYS = ("cell", "resolution", "bounds", "position", "dedup", "drop_unreferenced", "quadric_reg", "target_faces")
+SIMPLIFY_TARGET_MAX_RESOLUTION = 400     # the face-count search ends here: 401^3 cells stay below the grid's 2^27
 
 
 def check_simplify(simplify):
     """Validate a `simplify` option of the model's mesh entries and return the keywords of `simplify_mesh` it stands for: a cell
-    length (a number > 0), or a dict of cell / resolution / bounds / position / dedup / drop_unreferenced.  ValueError for
-    anything else."""
+    length (a number > 0), or a dict of cell / resolution / target_faces (exactly one of the three) / bounds / position /
+    quadric_reg / dedup / drop_unreferenced.  ValueError for anything else."""
     import math
     if isinstance(simplify, dict):
         kw = dict(simplify)
@@ -501,16 +502,23 @@ def check_simplify(simplify):
         kw = {"cell": float(simplify)}
     else:
         raise ValueError("simplify must be a cell length or a dict of simplify_mesh keywords, got %r" % (simplify,))
-    cell, resolution = kw.get("cell"), kw.get("resolution")
-    if (cell is None) == (resolution is None):
-        raise ValueError("simplify: exactly one of cell and resolution is given, got cell=%r resolution=%r" % (cell, resolution))
+    cell, resolution, target = kw.get("cell"), kw.get("resolution"), kw.get("target_faces")
+    if (cell is not None) + (resolution is not None) + (target is not None) != 1:
+        raise ValueError("simplify: exactly one of cell, resolution and target_faces is given, got cell=%r resolution=%r "
+                         "target_faces=%r" % (cell, resolution, target))
     if cell is not None and (isinstance(cell, bool) or not isinstance(cell, (int, float, np.integer, np.floating))
                              or not math.isfinite(float(cell)) or not float(cell) > 0.0):
         raise ValueError("simplify: cell must be a finite length > 0, got %r" % (cell,))
     if resolution is not None and (isinstance(resolution, bool) or not isinstance(resolution, (int, np.integer)) or int(resolution) < 1):
         raise ValueError("simplify: resolution must be an integer >= 1, got %r" % (resolution,))
-    if kw.get("position", "mean") not in ("mean", "member"):
-        raise ValueError("simplify: position must be 'mean' or 'member', got %r" % (kw["position"],))
+    if target is not None and (isinstance(target, bool) or not isinstance(target, (int, np.integer)) or int(target) < 1):
+        raise ValueError("simplify: target_faces must be an integer >= 1, got %r" % (target,))
+    if kw.get("position", "mean") not in ("mean", "member", "quadric"):
+        raise ValueError("simplify: position must be 'mean', 'member' or 'quadric', got %r" % (kw["position"],))
+    reg = kw.get("quadric_reg", 1e-3)
+    if (isinstance(reg, bool) or not isinstance(reg, (int, float, np.integer, np.floating)) or not math.isfinite(float(reg))
+            or float(reg) < 0.0):
+        raise ValueError("simplify: quadric_reg must be a finite number >= 0, got %r" % (reg,))
     return kw
 
 
@@ -528,16 +536,26 @@ def simplify_grid_of(lo, hi, cell):
 
 
 def simplify_mesh(verts, faces, cell=None, resolution=None, bounds=None, position="mean", dedup=True, attributes=None,
-                  drop_unreferenced=True):
+                  drop_unreferenced=True, quadric_reg=1e-3, target_faces=None):
     """Simplify an indexed mesh (verts (V,3), faces (F,3) integer ids) by vertex clustering: the vertices inside one cell of a
     regular grid become one vertex, faces are renamed to cells, and the faces that collapse (two corners in one cell) or repeat
     (dedup: the same three cells as an earlier face, in any orientation) go.  Decimation and welding by position in one step.
 
         cell          the side of a cell, a length in the units of verts; or
-        resolution    the number of cells along the longest side of the bounds (exactly one of the two is given)
+        resolution    the number of cells along the longest side of the bounds; or
+        target_faces  a face count N (exactly one of the three is given): the largest resolution r in [1, 400] that
+                      `search_resolution` finds with at most N kept faces -- up to eleven clusterings, each with one host
+                      synchronisation; the result gains resolution, probes (the (r, faces) asked) and reached (False when even
+                      r = 1 keeps more than N)
         bounds        (lo, hi), three numbers each; default: the box of the vertices with finite coordinates
         position      "mean": a cluster sits at the exact mean of its members; "member": at the member nearest to that mean -- a
-                      subset of the input, still on the extracted level set
+                      subset of the input, still on the extracted level set; "quadric": at the minimiser of the plane quadric
+                      of the faces that touch it (mesh_quadric_place: arah_mesh_quadric_place on the GPU, its specification on
+                      the host), regularised towards the mean by quadric_reg and never further than a cell from it -- a mean of
+                      points on a convex surface lies inside it, the minimiser keeps the volume; the result gains quadric =
+                      dict of fallbacks (clusters left at their mean) and longest (the most faces at one cluster), and
+                      vert_src names the member nearest to the NEW position.  ValueError when a cluster has more than 2^15
+                      faces: choose a smaller cell or position='mean'
         drop_unreferenced   clusters that lost all their faces are removed (mesh_select with the "referenced" policy of clean_mesh)
 
     The grid, in float32: origin = floor(lo / cell) cell, dims = floor((hi - origin) / cell) + 1; at most 2^27 cells.  A vertex
@@ -551,7 +569,8 @@ def simplify_mesh(verts, faces, cell=None, resolution=None, bounds=None, positio
     rule alone (of members equally near the mean the lowest id represents the cluster, so "member" positions can differ there).  Host synchronisations: ONE (the sizes of the result), and one more
     when `bounds` is left to the vertices' box.  ValueError when dedup meets more than 2^21 clusters: choose a larger cell, or
     dedup=False."""
-    check_simplify({"cell": cell, "resolution": resolution, "position": position})
+    check_simplify({"cell": cell, "resolution": resolution, "position": position, "quadric_reg": quadric_reg,
+                    "target_faces": target_faces})
     n_verts, faces = _mesh_args(verts, faces, "simplify_mesh")
     if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or not verts.dtype.is_floating_point:
         raise ValueError("simplify_mesh: verts must be a floating-point (V, 3) tensor")
@@ -559,6 +578,8 @@ def simplify_mesh(verts, faces, cell=None, resolution=None, bounds=None, positio
         raise ValueError("simplify_mesh: verts live on %s, faces on %s" % (verts.device, faces.device))
     attributes = dict(attributes or {})
     reserved = ("verts", "faces", "n_verts", "n_tris", "vert_src", "removed", "cell", "dims")
+    reserved += ("quadric",) if position == "quadric" else ()                  # the keys a mode adds are reserved in that mode
+    reserved += ("resolution", "probes", "reached") if target_faces is not None else ()
     for name, t in attributes.items():
         if name in reserved:
             raise ValueError("simplify_mesh: an attribute cannot be called %r" % (name,))
@@ -582,15 +603,37 @@ def simplify_mesh(verts, faces, cell=None, resolution=None, bounds=None, positio
             if len(lo) != 3 or len(hi) != 3 or not all(np.isfinite(lo + hi)) or any(h < l for l, h in zip(lo, hi)):
                 raise ValueError("simplify_mesh: bounds must be finite with lo <= hi, got %r" % (bounds,))
         lo, hi = np.asarray(lo, np.float32), np.asarray(hi, np.float32)
-        if cell is None:
+
+        def cell_of(resolution):
             side = np.float32((hi - lo).max())
-            cell = float(side / np.float32(int(resolution))) if side > 0 else 1.0      # a mesh without extent: one cell
-        cell = float(np.float32(cell))
-        if not np.isfinite(lo).all() or not np.isfinite(hi).all() or not cell > 0.0:
-            raise ValueError("simplify_mesh: the bounds %r .. %r with cell %r make no grid" % (lo.tolist(), hi.tolist(), cell))
-        origin, dims = simplify_grid_of(lo, hi, cell)
-        verts_out, vert_src, _, faces_out, _, counts = backend.mesh_simplify(v32, faces, origin.tolist(), cell, dims,
-                                                                             position=position, dedup=dedup)
+            return float(side / np.float32(int(resolution))) if side > 0 else 1.0      # a mesh without extent: one cell
+
+        def grid_of(cell):
+            cell = float(np.float32(cell))
+            if not np.isfinite(lo).all() or not np.isfinite(hi).all() or not cell > 0.0:
+                raise ValueError("simplify_mesh: the bounds %r .. %r with cell %r make no grid" % (lo.tolist(), hi.tolist(), cell))
+            origin, dims = simplify_grid_of(lo, hi, cell)
+            return cell, origin, dims
+
+        found = None
+        if target_faces is not None:
+            def kept_faces(r):
+                c, o, d = grid_of(cell_of(r))
+                sizes = backend.mesh_simplify(v32, faces, o.tolist(), c, d, position="mean", dedup=dedup)[5].tolist()   # a host synchronisation
+                return sizes[1], bool(sizes[5])
+            resolution, probes, reached = search_resolution(kept_faces, int(target_faces))
+            found = {"resolution": resolution, "probes": probes, "reached": reached}
+        if cell is None:
+            cell = cell_of(resolution)
+        cell, origin, dims = grid_of(cell)
+        quadric = position == "quadric"
+        verts_out, vert_src, vert_map, faces_out, _, counts = backend.mesh_simplify(v32, faces, origin.tolist(), cell, dims,
+                                                                                    position="mean" if quadric else position,
+                                                                                    dedup=dedup)
+        if quadric:
+            verts_out, vert_src, qcounts = backend.mesh_quadric_place(v32, faces, vert_map, verts_out, counts, cell, float(quadric_reg))
+        else:
+            qcounts = counts[:0]                                                 # its sizes are read with the others
         F = int(faces.shape[0])
         if drop_unreferenced:
             # the guard rows of faces_out name vertex 0: they become invalid faces; a vertex is its own component here, kept
@@ -601,12 +644,12 @@ def simplify_mesh(verts, faces, cell=None, resolution=None, bounds=None, positio
             keep[(named.reshape(-1) + 1).long()] = 1
             own = torch.arange(n_verts, dtype=torch.int32, device=dev)
             sel_src, _, faces_out, _, kept = backend.mesh_select(named, n_verts, own, keep[1:].contiguous())
-            sizes = torch.cat([counts, kept]).tolist()                           # the host synchronisation
-            nv, nf = sizes[6:]
+            sizes = torch.cat([counts, kept, qcounts]).tolist()                  # the host synchronisation
+            nv, nf = sizes[6:8]
             pick = sel_src[:nv].long()
             verts_out, vert_src = verts_out.index_select(0, pick), vert_src.long().index_select(0, pick)
         else:
-            sizes = counts.tolist()                                              # the host synchronisation
+            sizes = torch.cat([counts, counts[:2], qcounts]).tolist()            # the host synchronisation
             nv, nf = sizes[:2]
             verts_out, vert_src = verts_out[:nv], vert_src[:nv].long()
         if sizes[5]:
@@ -616,9 +659,42 @@ def simplify_mesh(verts, faces, cell=None, resolution=None, bounds=None, positio
                "removed": {"vertices": n_verts - nv, "faces_collapsed": sizes[3], "faces_duplicate": sizes[4],
                            "faces_invalid": sizes[2]},
                "cell": cell, "dims": tuple(dims)}
+        if quadric:
+            if sizes[11] == 2:
+                raise ValueError("simplify_mesh: a cell holds more than 2^15 faces (%d), too many to place by their quadric; "
+                                 "choose a smaller cell or position='mean'" % sizes[10])
+            res["quadric"] = {"fallbacks": sizes[8], "longest": sizes[10]}
+        if found is not None:
+            res.update(found)
         for name, t in attributes.items():
             res[name] = t.index_select(0, vert_src)
     return res
+
+
+def search_resolution(kept_faces, target, r_max=SIMPLIFY_TARGET_MAX_RESOLUTION):
+    """The face-count search of `simplify_mesh(target_faces=N)` over the integer resolution r in [1, r_max].  kept_faces(r) ->
+    (the faces the clustering keeps on r's grid, its status); count(r) is that number, and a probe with a status counts as
+    above N.  count(1) > N: r = 1, not reached.  count(r_max) <= N: r = r_max.  Otherwise bisect with count(lo) <= N < count(hi),
+    mid = (lo + hi) // 2, until hi - lo = 1: r = lo.  -> (r, probes = the list of (r, count) in the order asked, reached)."""
+    probes = []
+
+    def above(r):
+        n, status = kept_faces(r)
+        probes.append((r, n))
+        return bool(status) or n > target
+
+    if above(1):
+        return 1, probes, False
+    if not above(r_max):
+        return r_max, probes, True
+    lo, hi = 1, r_max
+    while hi - lo > 1:              # terminates: lo < mid < hi, so hi - lo strictly decreases
+        mid = (lo + hi) // 2
+        if above(mid):
+            hi = mid
+        else:
+            lo = mid
+    return lo, probes, True
 
 
 # ---- adjacency, topology, per-vertex normals, smoothing -------------------------------------------------------------------------

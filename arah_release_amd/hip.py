@@ -138,6 +138,7 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_mesh_index_bytes", "arah_mesh_index_build", "arah_mesh_closest", "arah_surface_metrics_bytes", "arah_surface_metrics", "arah_face_area_cumsum",
            "arah_mesh_components_scratch_bytes", "arah_mesh_components", "arah_mesh_select_scratch_bytes", "arah_mesh_select",
            "arah_mesh_simplify_scratch_bytes", "arah_mesh_simplify",
+           "arah_mesh_quadric_place_scratch_bytes", "arah_mesh_quadric_place",
            "arah_mesh_adjacency_scratch_bytes", "arah_mesh_adjacency", "arah_mesh_vertex_normals", "arah_mesh_smooth",
            "arah_mesh_orient_scratch_bytes", "arah_mesh_orient", "arah_mesh_boundary_loops_scratch_bytes",
            "arah_mesh_boundary_loops", "arah_mesh_fill_holes_scratch_bytes", "arah_mesh_fill_holes",
@@ -192,6 +193,7 @@ def load_library():
         getattr(lib, name).restype = C.c_size_t
         getattr(lib, name).argtypes = [C.c_int32]
     for name in ("arah_mesh_components_scratch_bytes", "arah_mesh_select_scratch_bytes", "arah_mesh_adjacency_scratch_bytes",
+                 "arah_mesh_quadric_place_scratch_bytes",
                  "arah_mesh_orient_scratch_bytes", "arah_mesh_boundary_loops_scratch_bytes", "arah_mesh_fill_holes_scratch_bytes"):
         getattr(lib, name).restype = C.c_size_t
         getattr(lib, name).argtypes = [C.c_int64, C.c_int64]
@@ -933,6 +935,56 @@ def mesh_simplify(verts, faces, origin, cell, dims, position="mean", dedup=True)
                                       _ptr(face_src), _ptr(counts), _ptr(scratch), C.c_size_t(scratch.numel()), _stream()),
                "arah_mesh_simplify")
     return verts_out, vert_src, vert_map, faces_out, face_src, counts
+
+
+def mesh_quadric_place(verts, faces, vert_map, means, n_clusters, cell, reg=1e-3):
+    """Quadric-error placement of the clusters of `mesh_simplify` (arah_mesh_quadric_place, csrc/meshquadric.hpp): verts (V,3)
+    float32, faces (F,3) integer ids, vert_map (V,) and means (V,3) float32 (verts_out at position="mean") of mesh_simplify on the
+    GPU; n_clusters its counts (K is read at [0] ON THE DEVICE) or an integer; cell the cell length, reg >= 0 the share of the
+    quadric's trace that pulls a cluster towards its mean.  -> pos (V,3) float32, vert_src (V,) int32 the member nearest to pos,
+    qcounts (4,) int32 = clusters that fell back to the mean, (face, cluster) pairs, the longest segment, status (2: a cluster
+    with more than 2^15 pairs was not placed).  Rows from K on are zero.  All on the device, no host synchronisation; the result
+    is meshing.mesh_quadric_place(...) bit for bit."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    what = "mesh_quadric_place"
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise ValueError("%s: verts must be a (V, 3) float32 tensor" % what)
+    V = int(verts.shape[0])
+    f, _, F = _mesh_cc_args(faces, V, what)
+    if V > meshing.SIMPLIFY_MAX_VERTS or F > meshing.SIMPLIFY_MAX_FACES:
+        raise ValueError("%s: at most 2^26 vertices and 2^28 faces, got %d and %d" % (what, V, F))
+    if not isinstance(means, torch.Tensor) or tuple(means.shape) != (V, 3) or means.dtype != torch.float32:
+        raise ValueError("%s: means must be a (%d, 3) float32 tensor" % (what, V))
+    if (not isinstance(vert_map, torch.Tensor) or tuple(vert_map.shape) != (V,) or vert_map.dtype.is_floating_point
+            or vert_map.dtype.is_complex or vert_map.dtype == torch.bool):
+        raise ValueError("%s: vert_map must be an integer tensor of shape (%d,)" % (what, V))
+    dev = f.device
+    if verts.device != dev or means.device != dev or vert_map.device != dev:
+        raise ValueError("%s: verts, faces, vert_map and means must live on one device" % what)
+    on_device = isinstance(n_clusters, torch.Tensor) and n_clusters.device == dev
+    K, c, reg = meshing.quadric_args(0 if on_device else n_clusters, cell, reg, V, what)
+    if on_device:                    # the counts of mesh_simplify stay where they are: K is read by the kernels
+        if n_clusters.dtype.is_floating_point or n_clusters.numel() < 1:
+            raise ValueError("%s: n_clusters must be an integer or the counts of mesh_simplify" % what)
+        counts = n_clusters.detach().reshape(-1)[:1].to(torch.int32).contiguous()
+    else:
+        counts = torch.tensor([K], dtype=torch.int32, device=dev)
+    vm = vert_map.detach()
+    if vm.dtype != torch.int32:      # a cluster id that does not fit int32 is no cluster: -1
+        vm = vm.to(torch.int64)
+        vm = torch.where((vm >= 0) & (vm <= 2 ** 31 - 1), vm, torch.full_like(vm, -1)).to(torch.int32)
+    v, mn, vm = verts.detach().contiguous(), means.detach().contiguous(), vm.contiguous()
+    with _on_device(dev):
+        scratch = _mesh_cc_buf(dev, int(lib.arah_mesh_quadric_place_scratch_bytes(V, F)))
+        pos = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        vert_src = torch.empty(V, dtype=torch.int32, device=dev)
+        qcounts = torch.empty(4, dtype=torch.int32, device=dev)
+        _check(lib.arah_mesh_quadric_place(_ptr(v), C.c_int64(V), _ptr(f), C.c_int64(F), _ptr(vm), _ptr(mn), _ptr(counts), C.c_float(c),
+                                           C.c_double(reg), _ptr(pos), _ptr(vert_src), _ptr(qcounts), _ptr(scratch),
+                                           C.c_size_t(scratch.numel()), _stream()), "arah_mesh_quadric_place")
+    return pos, vert_src, qcounts
 
 
 def mesh_adjacency(faces, n_verts):

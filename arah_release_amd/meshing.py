@@ -402,6 +402,156 @@ def mesh_simplify(verts, faces, origin, cell, dims, position="mean", dedup=True)
     return verts_out, vert_src.to(i32), vert_map.to(i32), faces_out.to(i32), face_src.to(i32), counts
 
 
+QUADRIC_MAX_SEGMENT = 1 << 15           # (face, cluster) pairs of one cluster that are still placed: the segment is rank-sorted
+
+
+def quadric_tree_sum(x, start, n):
+    """The fixed in-place tree of `mesh_quadric_place` over the flat rows x (P, C): segment k is x[start[k] : start[k] + n[k]];
+    for stride = 1, 2, 4, ... while stride < n: x[i] += x[i + stride] for every local i that is a multiple of 2 stride with
+    i + stride < n.  -> (K, C): every segment's x[0], zeros for an empty segment.  The shape of the tree depends on n alone."""
+    K, P = int(n.shape[0]), int(x.shape[0])
+    x = x.clone()
+    if P:
+        seg = torch.repeat_interleave(torch.arange(K, device=x.device), n)
+        local = torch.arange(P, device=x.device) - start[seg]
+        length = n[seg]
+        stride, n_max = 1, int(n.max())
+        while stride < n_max:
+            at = torch.nonzero((local % (2 * stride) == 0) & (local + stride < length))[:, 0]
+            x[at] = x[at] + x[at + stride]      # a target is a multiple of 2 stride, a source is not: no row is both
+            stride *= 2
+    out = torch.zeros(K, x.shape[1], dtype=x.dtype, device=x.device)
+    has = torch.nonzero(n > 0)[:, 0]
+    out[has] = x[start[has]]
+    return out
+
+
+def mesh_quadric_place(verts, faces, vert_map, means, n_clusters, cell, reg=1e-3):
+    """Quadric-error placement of the clusters of `mesh_simplify`: verts (V,3) float32, faces (F,3) integer ids, vert_map (V,)
+    integer (the cluster of every vertex or -1), means (V,3) float32 (verts_out at position="mean"), n_clusters = K (an integer,
+    or the counts of mesh_simplify: K at [0]; clamped to [0, V]), cell the float32 cell length (> 0), reg a finite double >= 0.
+
+    A face is VALID when its three ids lie in [0, V) and vert_map lies in [0, K) for all three; a repeated id is fine (the
+    normal is zero).  A valid face contributes once to each of the one, two or three distinct clusters of its corners --
+    collapsed and duplicate faces too: they carry the local shape.  Everything below is float64, every operation rounded on its
+    own, no square root.  Term of face f = (a, b, c) for cluster k, with m = double(means[k]): pa = double(a) - m, pb, pc
+    likewise; e1 = pb - pa, e2 = pc - pa; n = e1 x e2, every component (x y) - (z w); d = -((n0 pa0 + n1 pa1) + n2 pa2); the
+    nine numbers A00 A01 A02 A11 A12 A22 = ni nj and b0 b1 b2 = ni d: Lindstrom's area^2-weighted plane quadric about the mean.
+    The terms of a cluster are listed in ascending face id and summed by the fixed tree of `quadric_tree_sum`.  Solve: t = (A00
+    + A11) + A22; M = A + (reg t) I; the cofactors C00 = M11 M22 - M12 M12, C01 = M02 M12 - M01 M22, C02 = M01 M12 - M02 M11,
+    C11 = M00 M22 - M02 M02, C12 = M01 M02 - M00 M12, C22 = M00 M11 - M01 M01; det = (M00 C00 + M01 C01) + M02 C02; y = -(C b) /
+    det, every row summed left to right and divided once; pos[k] = float32(m + y).  The cluster FALLS BACK to pos[k] = means[k],
+    and is counted, when t or det is not finite or not > 0, or a |y_a| is not finite or > double(cell).  A cluster with more
+    than 2^15 pairs is not placed at all (pos = mean, not counted) and sets the status 2.  Representative: the member with the
+    smallest float32((dx dx + dy dy) + dz dz), d = double(v) - double(pos[k]), ties to the lowest id (0 for a cluster without a
+    member).
+
+    -> pos (V,3) float32, vert_src (V,) int32, qcounts (4,) int32 = clusters that fell back, (face, cluster) pairs, the longest
+    segment, the status.  Rows from K on are zero.  Plain tensor operations on the tensors' device: the specification of
+    arah_mesh_quadric_place (csrc/meshquadric.hpp), and what runs for meshes on the host."""
+    what = "mesh_quadric_place"
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise ValueError("%s: verts must be a (V, 3) float32 tensor" % what)
+    V = int(verts.shape[0])
+    faces, _, in_range = _cc_faces(faces, V, what)
+    F = int(faces.shape[0])
+    if V > SIMPLIFY_MAX_VERTS or F > SIMPLIFY_MAX_FACES:
+        raise ValueError("%s: at most 2^26 vertices and 2^28 faces, got %d and %d" % (what, V, F))
+    if not isinstance(means, torch.Tensor) or tuple(means.shape) != (V, 3) or means.dtype != torch.float32:
+        raise ValueError("%s: means must be a (%d, 3) float32 tensor" % (what, V))
+    if (not isinstance(vert_map, torch.Tensor) or tuple(vert_map.shape) != (V,) or vert_map.dtype.is_floating_point
+            or vert_map.dtype.is_complex or vert_map.dtype == torch.bool):
+        raise ValueError("%s: vert_map must be an integer tensor of shape (%d,)" % (what, V))
+    dev = verts.device
+    if faces.device != dev or means.device != dev or vert_map.device != dev:
+        raise ValueError("%s: verts, faces, vert_map and means must live on one device" % what)
+    K, c, reg = quadric_args(n_clusters, cell, reg, V, what)
+    f64, i32 = torch.float64, torch.int32
+    verts, means, vmap = verts.detach(), means.detach(), vert_map.detach().long()
+    member = (vmap >= 0) & (vmap < K)
+    ok = in_range.clone()
+    ok[in_range] = member[faces[in_range]].all(1)
+    rows = torch.nonzero(ok)[:, 0]
+    cl = vmap[faces[rows]]                                                      # (Fv,3) clusters of the corners
+    first = torch.stack([torch.ones_like(cl[:, 0], dtype=torch.bool), cl[:, 1] != cl[:, 0],
+                         (cl[:, 2] != cl[:, 0]) & (cl[:, 2] != cl[:, 1])], 1)   # a cluster counts at its first corner
+    pf, pk = rows[:, None].expand(-1, 3)[first], cl[first]
+    order = torch.argsort(pk * max(F, 1) + pf)                                  # (cluster, face): unique keys
+    pf, pk = pf[order], pk[order]
+    n = torch.bincount(pk, minlength=K)[:K] if K else torch.zeros(0, dtype=torch.int64, device=dev)
+    start = torch.cumsum(n, 0) - n
+    longest = int(n.max()) if K else 0
+    placed = n <= QUADRIC_MAX_SEGMENT
+    m = means[:K].to(f64)
+    # the terms
+    mk = m[pk]
+    pa, pb, pc = (verts[faces[pf, j]].to(f64) - mk for j in range(3))
+    e1, e2 = pb - pa, pc - pa
+    nx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
+    ny = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
+    nz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+    d = -((nx * pa[:, 0] + ny * pa[:, 1]) + nz * pa[:, 2])
+    terms = torch.stack([nx * nx, nx * ny, nx * nz, ny * ny, ny * nz, nz * nz, nx * d, ny * d, nz * d], 1)
+    keep = placed[pk]                                                           # a skipped segment is not summed
+    n_sum = torch.where(placed, n, torch.zeros_like(n))
+    q = quadric_tree_sum(terms[keep], torch.cumsum(n_sum, 0) - n_sum, n_sum)
+    A00, A01, A02, A11, A12, A22, b0, b1, b2 = (q[:, j] for j in range(9))
+    # the solve
+    t = (A00 + A11) + A22
+    lam = reg * t
+    M00, M11, M22, M01, M02, M12 = A00 + lam, A11 + lam, A22 + lam, A01, A02, A12
+    C00 = M11 * M22 - M12 * M12
+    C01 = M02 * M12 - M01 * M22
+    C02 = M01 * M12 - M02 * M11
+    C11 = M00 * M22 - M02 * M02
+    C12 = M01 * M02 - M00 * M12
+    C22 = M00 * M11 - M01 * M01
+    det = (M00 * C00 + M01 * C01) + M02 * C02
+    y = torch.stack([-((C00 * b0 + C01 * b1) + C02 * b2) / det, -((C01 * b0 + C11 * b1) + C12 * b2) / det,
+                     -((C02 * b0 + C12 * b1) + C22 * b2) / det], 1)
+    good = torch.isfinite(t) & (t > 0) & torch.isfinite(det) & (det > 0) & (torch.isfinite(y) & (y.abs() <= c)).all(1)
+    moved = (m + y).float()
+    pos_k = torch.where((good & placed)[:, None], moved, means[:K])
+    fallbacks = int((placed & ~good).sum())
+    status = 2 if longest > QUADRIC_MAX_SEGMENT else 0
+    # representatives: the smallest (bits(d2) << 32) | id per cluster
+    ids_v = torch.nonzero(member)[:, 0]
+    inv = vmap[ids_v]
+    dd = verts[ids_v].to(f64) - pos_k[inv].to(f64)
+    d2 = ((dd[:, 0] * dd[:, 0] + dd[:, 1] * dd[:, 1]) + dd[:, 2] * dd[:, 2]).float()
+    packed = ((d2.view(i32).long() & 0x7FFFFFFF) << 32) | ids_v
+    best = torch.full((K,), 2 ** 63 - 1, dtype=torch.int64, device=dev).scatter_reduce(0, inv, packed, "amin")
+    src = torch.where(best == 2 ** 63 - 1, torch.zeros_like(best), best & 0xFFFFFFFF)
+    pos = torch.zeros(V, 3, dtype=torch.float32, device=dev)
+    pos[:K] = pos_k
+    vert_src = torch.zeros(V, dtype=torch.int64, device=dev)
+    vert_src[:K] = src
+    qcounts = torch.tensor([fallbacks, int(pf.shape[0]), longest, status], dtype=i32, device=dev)
+    return pos, vert_src.to(i32), qcounts
+
+
+def quadric_args(n_clusters, cell, reg, n_verts, what="mesh_quadric_place"):
+    """The scalars of `mesh_quadric_place`, checked: -> (K clamped to [0, V], cell as a float32 value, reg as a float)."""
+    try:
+        if isinstance(n_clusters, torch.Tensor):
+            if n_clusters.dtype.is_floating_point or n_clusters.numel() < 1:
+                raise TypeError
+            K = int(n_clusters.reshape(-1)[0])
+        else:
+            if isinstance(n_clusters, bool) or int(n_clusters) != n_clusters:
+                raise TypeError
+            K = int(n_clusters)
+        c = float(np.float32(float(cell)))
+        reg = float(reg)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("%s: n_clusters must be an integer (or the counts of mesh_simplify), cell and reg numbers" % what)
+    if not math.isfinite(c) or not c > 0.0:
+        raise ValueError("%s: cell must be a finite float32 length > 0, got %r" % (what, cell))
+    if not math.isfinite(reg) or reg < 0.0:
+        raise ValueError("%s: reg must be a finite number >= 0, got %r" % (what, reg))
+    return min(max(K, 0), n_verts), c, reg
+
+
 ADJACENCY_MAX_FACES = 1 << 28           # 6 F neighbour entries fit an int32
 ADJACENCY_FIELDS = ("vf_start", "vf", "nbr_start", "nbr", "nbr_out", "nbr_in", "vert_flags", "counts")
 

@@ -34,6 +34,7 @@
  *   arah_mesh_components /  (none: the reference writes the extracted mesh as it comes; connected components of an indexed mesh
  *   arah_mesh_select        by shared vertex ids, and the order-preserving selection of some of them: floater removal)
  *   arah_mesh_simplify      (none: vertex clustering of an indexed mesh on a grid: decimation and welding by position)
+ *   arah_mesh_quadric_place (none: the clusters of arah_mesh_simplify moved to the minimisers of their faces' plane quadrics)
  *   arah_mesh_adjacency /   (none: the reference's users smooth and re-normal with trimesh / open3d / pytorch3d; the incident faces
  *   arah_mesh_vertex_normals /  and unique neighbours of every vertex with edge statistics, pytorch3d's verts_normals_packed over
  *   arah_mesh_smooth        them, and Laplacian / Taubin umbrella smoothing)
@@ -358,6 +359,28 @@ int arah_mesh_simplify(const float* verts, int64_t n_verts, const int32_t* faces
                        const int32_t h_dims[3], double fix_scale, int32_t position, int32_t dedup, float* verts_out,
                        int32_t* vert_src, int32_t* vert_map, int32_t* faces_out, int32_t* face_src, int32_t* counts, void* scratch,
                        size_t scratch_bytes, void* stream);
+/* Quadric-error placement of the clusters of arah_mesh_simplify (csrc/meshquadric.hpp).  verts [n_verts][3], faces [n_faces][3]
+ * vertex ids, vert_map [n_verts] and means [n_verts][3] (verts_out at position 0) of arah_mesh_simplify, counts its counts on the
+ * DEVICE: K = counts[0] is read there, clamped to [0, n_verts].  A face is valid when its ids lie in [0, n_verts) and vert_map in
+ * [0, K) for all three (a repeated id is fine); it contributes once to each distinct cluster of its corners, collapsed and
+ * duplicate faces too.  In float64, every operation rounded on its own, no square root: with m = double(means[k]), pa = double(a)
+ * - m (pb, pc likewise), n = (pb - pa) x (pc - pa), d = -((n0 pa0 + n1 pa1) + n2 pa2), the term of the face is A = n n^T (six
+ * numbers) and b = n d.  The terms of a cluster, in ascending face id, are summed by the in-place tree "stride = 1, 2, 4, ... <
+ * n: x[i] += x[i + stride] for i a multiple of 2 stride with i + stride < n".  t = (A00 + A11) + A22, M = A + (reg t) I, C the
+ * cofactors of M, det = (M00 C00 + M01 C01) + M02 C02, y = -(C b) / det row by row; pos_out[k] = float32(m + y).  A cluster
+ * falls back to means[k], bit for bit, when t or det is not finite or not > 0, or a |y_a| is not finite or > cell.  A cluster
+ * with more than 2^15 (face, cluster) pairs is not placed (pos = mean) and sets the status 2.  vert_src_out [n_verts]: the member
+ * with the smallest float32 squared distance to pos_out[k] (evaluated in double), ties to the lowest id.  qcounts (device
+ * int32[4]) = clusters that fell back, pairs, the longest segment, status.  Rows of pos_out and vert_src_out from K on are ZERO.
+ * Integer atomics only: the result is unique, and equal to meshing.mesh_quadric_place bit for bit.  cell finite and > 0, reg
+ * finite and >= 0, n_verts <= 2^26, n_faces <= 2^28, otherwise ARAH_E_BADARG without a launch, and a scratch size of 0 for sizes
+ * out of range; scratch: arah_mesh_quadric_place_scratch_bytes(n_verts, n_faces) device bytes, 256-byte aligned,
+ * ARAH_E_WORKSPACE when short.  Empty inputs still write qcounts; pointers of empty arrays may be NULL.  No host synchronisation,
+ * no allocation. */
+size_t arah_mesh_quadric_place_scratch_bytes(int64_t n_verts, int64_t n_faces);
+int arah_mesh_quadric_place(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int32_t* vert_map,
+                            const float* means, const int32_t* counts, float cell, double reg, float* pos_out,
+                            int32_t* vert_src_out, int32_t* qcounts, void* scratch, size_t scratch_bytes, void* stream);
 /* Adjacency of an indexed mesh (csrc/meshadj.hpp).  faces [n_faces][3] vertex ids.  A face is VALID when its three ids lie in
  * [0, n_verts) and are pairwise different; the others are skipped.  A valid face (a, b, c) traverses the directed edges a->b,
  * b->c, c->a.  -> vf_start [n_verts + 1], vf [3 n_faces]: the CSR of the valid faces incident to every vertex, face ids ASCENDING
