@@ -4680,8 +4680,6 @@ int arah_mesh_fill_holes(const float* verts, int64_t n_verts, const int32_t* fac
 }
 
 // ---- indexed meshes drawn on the device: pix_to_face, depth, barycentrics; attributes (csrc/meshraster.hpp) ------------------------
-static int mr_grid(int64_t n) { return mesh_grid(n, kMrMaxGrid); }   // the point-in-mesh entries further down borrow this grid
-
 static int mr_rasterize(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t H, int32_t W, float z_near,
                         int32_t cull, int32_t small_area, int32_t wave_area, int32_t huge_area, uint64_t* keys, int32_t* pix_to_face,
                         float* depth, float* bary, void* stream) {
@@ -5829,7 +5827,7 @@ int arah_mesh_query(const float* verts, int32_t n_verts, const int32_t* faces, i
     if (!pts || !d2 || !face || !closest || !bary || !inside) return ARAH_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     MeshBox* box = reinterpret_cast<MeshBox*>(scratch);
-    hipLaunchKernelGGL(k_mesh_box, dim3(1), dim3(256), 0, s, verts, faces, n_faces, 512.0, box);
+    hipLaunchKernelGGL(k_mesh_box, dim3(1), dim3(kBoxThreads), 0, s, verts, faces, n_faces, 512.0, box);
     const int g = (n_pts + kMeshThreads - 1) / kMeshThreads;
     if (pts_are_f64)
         hipLaunchKernelGGL(k_mesh_query<double>, dim3(g), dim3(kMeshThreads), 0, s, verts, faces, n_faces, (const MeshBox*)box,
@@ -5843,6 +5841,23 @@ int arah_mesh_query(const float* verts, int32_t n_verts, const int32_t* faces, i
 // ---- containment against large meshes, occupancy grids (meshcontains.hpp) --------------------------------------
 static bool contains_sizes_ok(int32_t n_faces, int32_t resolution) {
     return n_faces >= 0 && n_faces <= (1 << 28) && resolution >= 2 && resolution <= kCtMaxRes;
+}
+
+// The query side's indices and scratch below are carved like the indexed side's: the header first, at offset 0, where Python reads it
+static CtIndex carve_contains(void* index, int n_faces, int res) {
+    const size_t F = (size_t)n_faces, cells = (size_t)res * res;
+    CtIndex ix;
+    MeshCarver c(index);
+    ix.hdr = c.take<CtHeader>(1);
+    ix.rec = c.take<double>(F * kCtRec);
+    ix.rect = c.take<int>(F * 4);
+    ix.med = c.take<int>(F);
+    ix.huge = c.take<int>(F);
+    ix.cnt = c.take<unsigned>(cells);
+    ix.start = c.take<unsigned>(cells + 1);
+    ix.sums = c.take<unsigned long long>((cells + kCtScanBlock - 1) / kCtScanBlock);
+    ix.bytes = c.bytes();
+    return ix;
 }
 
 size_t arah_contains_index_bytes(int32_t n_faces, int32_t resolution) {
@@ -5864,7 +5879,7 @@ int arah_contains_index_count(const float* verts, int32_t n_verts, const int32_t
     if (n_faces > 0) {
         const int g = (n_faces + kCtThreads - 1) / kCtThreads;
         hipLaunchKernelGGL(k_ct_setup, dim3(g), dim3(kCtThreads), 0, s, verts, faces, n_faces, ix.hdr, ix.rec, ix.rect, ix.med, ix.huge);
-        hipLaunchKernelGGL(k_ct_walk<false>, dim3(mr_grid(n_faces)), dim3(kCtThreads), 0, s, (const int*)ix.rect, n_faces,
+        hipLaunchKernelGGL(k_ct_walk<false>, dim3(mesh_grid(n_faces, kMrMaxGrid)), dim3(kCtThreads), 0, s, (const int*)ix.rect, n_faces,
                            resolution, ix.cnt, (int*)nullptr, 0u);
         hipLaunchKernelGGL(k_ct_walk_lists<false>, dim3(kCtListGrid), dim3(kCtThreads), 0, s, (const CtHeader*)ix.hdr,
                            (const int*)ix.rect, (const int*)ix.med, (const int*)ix.huge, n_faces, resolution, ix.cnt, (int*)nullptr, 0u);
@@ -5886,10 +5901,8 @@ int arah_contains_index_fill(void* index, size_t index_bytes, int32_t n_faces, i
     if (!refs) return ARAH_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const long long cells = (long long)resolution * resolution;
-    const int g = (n_faces + kCtThreads - 1) / kCtThreads;
-    hipLaunchKernelGGL(k_ct_cursor, dim3(mr_grid(cells)),
-                       dim3(kCtThreads), 0, s, (const unsigned*)ix.start, cells, ix.cnt);
-    hipLaunchKernelGGL(k_ct_walk<true>, dim3(mr_grid(n_faces)), dim3(kCtThreads), 0, s, (const int*)ix.rect, n_faces,
+    hipLaunchKernelGGL(k_ct_cursor, dim3(mesh_grid(cells, kMrMaxGrid)), dim3(kCtThreads), 0, s, (const unsigned*)ix.start, cells, ix.cnt);
+    hipLaunchKernelGGL(k_ct_walk<true>, dim3(mesh_grid(n_faces, kMrMaxGrid)), dim3(kCtThreads), 0, s, (const int*)ix.rect, n_faces,
                        resolution, ix.cnt, refs, (unsigned)n_refs);
     hipLaunchKernelGGL(k_ct_walk_lists<true>, dim3(kCtListGrid), dim3(kCtThreads), 0, s, (const CtHeader*)ix.hdr, (const int*)ix.rect,
                        (const int*)ix.med, (const int*)ix.huge, n_faces, resolution, ix.cnt, refs, (unsigned)n_refs);
@@ -5945,6 +5958,23 @@ static bool winding_sizes_ok(int32_t n_faces, int32_t& depth) {
 }
 
 static bool winding_accuracy_ok(double accuracy) { return accuracy >= 1.0; }   // false for a NaN
+
+static WnIndex carve_winding(void* index, int n_faces, int depth) {
+    const size_t F = (size_t)n_faces, cells = (size_t)1 << (3 * depth);
+    WnIndex ix;
+    MeshCarver c(index);
+    ix.hdr = c.take<WnHeader>(1);
+    ix.key = c.take<unsigned>(F);
+    ix.skey = c.take<unsigned>(F);
+    ix.tmp = c.take<int>(F);
+    ix.hlev = c.take<int>(F);
+    ix.cnt64 = c.take<long long>(F);
+    ix.prefix = c.take<long long>(F + 1);
+    ix.ccnt = c.take<unsigned>(cells);
+    ix.cstart = c.take<unsigned>(cells + 1);
+    ix.bytes = c.bytes();
+    return ix;
+}
 
 size_t arah_winding_index_bytes(int32_t n_faces, int32_t depth) {
     if (!winding_sizes_ok(n_faces, depth)) return 0;
@@ -6065,6 +6095,23 @@ int arah_image_metrics(const float* pred, const float* gt, const uint8_t* box_ma
 }
 
 // ---- exact distance to large triangle soups and the geometry scores (meshdist.hpp) ---------------------------
+static MdIndex carve_mesh_index(void* index, int n_faces) {
+    MdIndex m;
+    m.cap_cells = md_cap_cells(n_faces);
+    const size_t cap = (size_t)m.cap_cells;
+    MeshCarver c(index);
+    m.hdr = c.take<MdHeader>(1);
+    m.stat = c.take<double>(8 * kMdStatBlocks);
+    m.cell_base = c.take<int>(cap + 1);
+    m.cell_count = c.take<int>(cap);
+    m.dt[0] = c.take<uint8_t>(cap);
+    m.dt[1] = c.take<uint8_t>(cap);
+    m.refs = c.take<int>((size_t)kMdSpan * (size_t)n_faces);
+    m.big = c.take<int>((size_t)n_faces);
+    m.bytes = c.bytes();
+    return m;
+}
+
 size_t arah_mesh_index_bytes(int32_t n_faces) {
     if (n_faces < 1) return 0;
     return carve_mesh_index(nullptr, n_faces).bytes;
@@ -6110,6 +6157,17 @@ int arah_mesh_closest(const void* index, size_t index_bytes, const float* tris, 
 // ---- the truncated signed distance field of a soup on a lattice (meshsdf.hpp) -----------------------------------
 static bool sdf_grid_sizes_ok(int64_t n_faces, int64_t nx, int64_t ny, int64_t nz) {
     return n_faces >= 0 && n_faces <= (1 << 26) && nx >= 1 && ny >= 1 && nz >= 1 && nx <= INT32_MAX && ny <= INT32_MAX && nz <= INT32_MAX;
+}
+
+static SgScratch carve_sdf_grid(void* scratch, int64_t n_faces) {
+    const size_t F = (size_t)n_faces;
+    SgScratch w;
+    MeshCarver c(scratch);
+    w.rect = c.take<int>(64 + F * 6);   // 256 bytes more than the boxes, as the scratch always had
+    w.med = c.take<int>(F);
+    w.huge = c.take<int>(F);
+    w.bytes = c.bytes();
+    return w;
 }
 
 size_t arah_mesh_sdf_grid_bytes(int64_t n_faces, int64_t nx, int64_t ny, int64_t nz) {
@@ -6218,6 +6276,23 @@ int arah_surface_metrics(const float* tris_a, int32_t n_faces_a, const int32_t* 
 }
 
 // ---- exact nearest point of large clouds and the per-side scores (pointdist.hpp) ------------------------------
+static PdIndex carve_point_index(void* index, int n_points) {
+    PdIndex m;
+    m.cap_cells = pd_cap_cells(n_points);
+    const size_t cap = (size_t)m.cap_cells;
+    MeshCarver c(index);
+    m.hdr = c.take<PdHeader>(1);
+    m.stat = c.take<double>(8 * kPdStatBlocks);
+    m.coarse = c.take<int>((size_t)kPdCoarseCap);
+    m.cell_base = c.take<int>(cap + 1);
+    m.cell_count = c.take<int>(cap);
+    m.dt[0] = c.take<uint8_t>(cap);
+    m.dt[1] = c.take<uint8_t>(cap);
+    m.recs = c.take<PdRecord>((size_t)n_points);
+    m.bytes = c.bytes();
+    return m;
+}
+
 size_t arah_point_index_bytes(int32_t n_points) {
     if (n_points < 1) return 0;
     return carve_point_index(nullptr, n_points).bytes;

@@ -1,11 +1,14 @@
-// meshcommon.hpp -- what the indexed-mesh headers share (mcubes.hpp, meshcc.hpp, meshsimp.hpp, meshadj.hpp, meshquadric.hpp,
-// meshorient.hpp, meshraster.hpp): the launch constants, the workgroup prefix, the ordered compaction walk, the one-workgroup scan, the padding of
-// the rows between a count and a capacity, and cc_add_one.  DESIGN.md ("Indexed meshes: the shared walk and the scratch carver")
-// tells the same once for the host side.  The query-side headers (meshquery.hpp ... pointdist.hpp, metrics.hpp) share nothing
-// with this file: their prefix sums include a float64 one whose summation order is part of their specification.
+// meshcommon.hpp -- what the mesh headers share.  The indexed-mesh side (mcubes.hpp, meshcc.hpp, meshsimp.hpp, meshadj.hpp,
+// meshquadric.hpp, meshorient.hpp, meshraster.hpp): the launch constants, the workgroup prefix, the ordered compaction walk, the
+// one-workgroup scan, the padding of the rows between a count and a capacity, and cc_add_one.  The box walkers of both sides
+// (meshraster.hpp, meshcontains.hpp, meshsdf.hpp): the wave's turns and the walk of the two lists, at the end of this file.  The
+// one-workgroup box reduction of the query side (meshquery.hpp, meshcontains.hpp, meshwinding.hpp).  DESIGN.md ("Indexed meshes:
+// the shared walk and the scratch carver") tells the same once, with the host side.  The query side's prefix sums stay out: they
+// include a float64 one whose summation order is part of their specification, and integer scans of three widths whose access
+// patterns were measured where they are.
 //
-// COUNT / SCAN / FILL.  Every variable-length result of these headers is numbered the same way, without atomics, so that it is
-// deterministic and keeps the order of its elements:
+// COUNT / SCAN / FILL.  Every variable-length result of the indexed-mesh headers is numbered the same way, without atomics, so
+// that it is deterministic and keeps the order of its elements:
 //
 //   count   a walk over the elements; every workgroup writes the number of marked elements of its part -> blk_count[block]
 //   scan    k_mc_scan: blk_base = the exclusive scan of blk_count, the total
@@ -118,5 +121,82 @@ __device__ __forceinline__ void cc_add_one(int* table, int key, bool active) {
         const unsigned long long same = __ballot(active && key == k);
         if (lane == leader) atomicAdd(&table[k], (int)__popcll(same));
         pending &= ~same;
+    }
+}
+
+// ---- the box walkers: a face's box of n elements (pixels, cells, nodes) is walked as first, first + stride, ... < last in the
+// box's row-major order by a lane (n small), by the face's wave, by one workgroup (the MEDIUM list) or by PARTS workgroups (the
+// HUGE list).  The thresholds, the way the lists are appended and the per-element walk are each header's own.
+
+// The wave's turns: every lane of the wave takes the lanes with `flagged` one after the other, lowest first; body(src) shuffles
+// the source lane's set-up to itself and strides over that lane's box, first = its own lane, stride 64.
+// CONTRACT: call it from wave-uniform control flow -- all 64 lanes reach the ballot together, lanes without work carry false.
+template <class Body>
+__device__ __forceinline__ void mesh_wave_turns(bool flagged, Body body) {
+    unsigned long long todo = __ballot(flagged);
+    while (todo) {   // terminates: every round clears one of at most 64 bits
+        const int src = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        body(src);
+    }
+}
+
+// The two lists: a one-dimensional grid of THREADS-wide workgroups strides first over the medium list, one workgroup per face,
+// then over the huge list's (face, part) items, PARTS parts per face -- a face that covers everything is spread over PARTS
+// workgroups.  The item and its face are the same for every thread of the workgroup.
+//   size(f, ctx) -> unsigned   the elements of face f's box, 0 to skip it (an id out of range, no box); fills ctx, a Ctx of the
+//                              caller's (the box: registers)
+//   walk(f, ctx, first, last, stride)   the per-element work
+template <int PARTS, int THREADS, class Ctx, class Size, class Walk>
+__device__ __forceinline__ void mesh_list_walk(const int* __restrict__ med, unsigned n_med, const int* __restrict__ huge,
+                                               unsigned n_huge, Size size, Walk walk) {
+    // terminates: n_med - li strictly decreases (gridDim.x >= 1)
+    for (unsigned li = blockIdx.x; li < n_med; li += gridDim.x) {
+        const int f = med[li];
+        Ctx ctx;
+        const unsigned n = size(f, ctx);
+        if (n) walk(f, ctx, threadIdx.x, n, (unsigned)THREADS);
+    }
+    const unsigned long long items = (unsigned long long)n_huge * PARTS;
+    // terminates: items - it strictly decreases.  Item it is part it % PARTS of the face huge[it / PARTS]
+    for (unsigned long long it = blockIdx.x; it < items; it += gridDim.x) {
+        const int f = huge[it / PARTS];
+        const unsigned part = (unsigned)(it % PARTS);
+        Ctx ctx;
+        const unsigned n = size(f, ctx);
+        if (!n) continue;
+        const unsigned per = (n + PARTS - 1) / PARTS;                     // PARTS * per >= n: the parts cover the box
+        const unsigned lo = min(n, part * per), hi = min(n, lo + per);   // n < 2^31, so part * per <= n + PARTS does not wrap
+        walk(f, ctx, lo + threadIdx.x, hi, (unsigned)THREADS);
+    }
+}
+
+// ---- the box reduction of one workgroup of kBoxThreads threads: every thread's lo[3] / hi[3] (and flags, when sflag is not null)
+// are reduced to element 0 of smin / smax / sflag, the caller's __shared__ arrays.  fmin, fmax and |= do not depend on the order.
+// extra(s) is called by the threads tid < s of every round s = 128 .. 1, after the bounds and before the round's barrier: a sum
+// whose order is specified rides along (k_wn_box).  CONTRACT: every thread calls it, from workgroup-uniform control flow; element 0
+// may be read by every thread afterwards.
+constexpr int kBoxThreads = 256;
+
+template <class Extra>
+__device__ __forceinline__ void mesh_box_reduce(const double* lo, const double* hi, int flags, double (*smin)[kBoxThreads],
+                                                double (*smax)[kBoxThreads], int* sflag, Extra extra) {
+    const int tid = threadIdx.x;
+    for (int c = 0; c < 3; ++c) {
+        smin[c][tid] = lo[c];
+        smax[c][tid] = hi[c];
+    }
+    if (sflag) sflag[tid] = flags;
+    __syncthreads();
+    for (int s = kBoxThreads / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            for (int c = 0; c < 3; ++c) {
+                smin[c][tid] = fmin(smin[c][tid], smin[c][tid + s]);
+                smax[c][tid] = fmax(smax[c][tid], smax[c][tid + s]);
+            }
+            if (sflag) sflag[tid] |= sflag[tid + s];
+            extra(s);
+        }
+        __syncthreads();
     }
 }

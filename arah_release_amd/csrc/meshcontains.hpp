@@ -22,8 +22,8 @@
 //                  value by the rule's own operation sequence), the clipped cell rectangle, and the face's class by the cells n
 //                  of its rectangle: lane (n <= kCtLaneCells), wave (<= kCtWaveCells), workgroup (<= kCtGroupCells: the MEDIUM
 //                  list), several workgroups (the HUGE list, kCtParts parts a face)
-//   k_ct_walk      lane and wave classes: +1 per cell of the rectangle (integer atomicAdd)
-//   k_ct_walk_lists  the two lists, as k_mr_lists of meshraster.hpp: one face covering all resolution^2 cells is spread over
+//   k_ct_walk      lane and wave classes: +1 per cell of the rectangle (integer atomicAdd); the wave's turns are mesh_wave_turns
+//   k_ct_walk_lists  the two lists (mesh_list_walk of meshcommon.hpp): one face covering all resolution^2 cells is spread over
 //                  kCtParts workgroups and does not serialise the build
 //   k_ct_scan_a/b/c  exclusive scan of the counts -> start[resolution^2 + 1]; the total (64-bit) goes to the header
 //
@@ -71,30 +71,14 @@ struct CtIndex {
     size_t bytes;
 };
 
-inline CtIndex carve_contains(void* base, int n_faces, int res) {
-    CtIndex ix;
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        char* p = base ? reinterpret_cast<char*>(base) + off : nullptr;
-        off += (n + 255) & ~size_t(255);
-        return p;
-    };
-    const size_t F = (size_t)n_faces, cells = (size_t)res * res;
-    ix.hdr = reinterpret_cast<CtHeader*>(take(256));
-    ix.rec = reinterpret_cast<double*>(take(F * kCtRec * sizeof(double)));
-    ix.rect = reinterpret_cast<int*>(take(F * 4 * sizeof(int)));
-    ix.med = reinterpret_cast<int*>(take(F * sizeof(int)));
-    ix.huge = reinterpret_cast<int*>(take(F * sizeof(int)));
-    ix.cnt = reinterpret_cast<unsigned*>(take(cells * sizeof(unsigned)));
-    ix.start = reinterpret_cast<unsigned*>(take((cells + 1) * sizeof(unsigned)));
-    ix.sums = reinterpret_cast<unsigned long long*>(take(((cells + kCtScanBlock - 1) / kCtScanBlock) * sizeof(unsigned long long)));
-    ix.bytes = off;
-    return ix;
-}
+struct CtRect {   // a face's clipped rectangle as the walks take it: first cell, cells per row
+    int ix0, iy0, h;
+};
 
 // lo / hi over the used vertices, validity, the two list counters
 __global__ __launch_bounds__(kCtThreads) void k_ct_box(const float* __restrict__ verts, int n_verts, const int* __restrict__ faces,
                                                        int n_faces, int res, CtHeader* hdr) {
+    static_assert(kCtThreads == kBoxThreads, "mesh_box_reduce");
     __shared__ double smin[3][kCtThreads], smax[3][kCtThreads];
     __shared__ int sbad[kCtThreads];
     const int tid = threadIdx.x;
@@ -114,22 +98,7 @@ __global__ __launch_bounds__(kCtThreads) void k_ct_box(const float* __restrict__
             hi[c] = fmax(hi[c], x);
         }
     }
-    for (int c = 0; c < 3; ++c) {
-        smin[c][tid] = lo[c];
-        smax[c][tid] = hi[c];
-    }
-    sbad[tid] = bad;
-    __syncthreads();
-    for (int s = kCtThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            for (int c = 0; c < 3; ++c) {
-                smin[c][tid] = fmin(smin[c][tid], smin[c][tid + s]);
-                smax[c][tid] = fmax(smax[c][tid], smax[c][tid + s]);
-            }
-            sbad[tid] |= sbad[tid + s];
-        }
-        __syncthreads();
-    }
+    mesh_box_reduce(lo, hi, bad, smin, smax, sbad, [](int) {});
     if (tid < 3) {
 #pragma clang fp contract(off)
         const double sc = ((double)res - 1.0) / (smax[tid][0] - smin[tid][0]);
@@ -253,14 +222,11 @@ __global__ __launch_bounds__(kCtThreads) void k_ct_walk(const int* __restrict__ 
             if (rc[1] < rc[0] || h < 1) n = 0, h = 1;
         }
         if (n > 0 && n <= kCtLaneCells) ct_walk<FILL>(ix0, iy0, h, (int)f, 0u, (unsigned)n, 1u, res, cnt, refs, n_refs);
-        unsigned long long todo = __ballot(n > kCtLaneCells && n <= kCtWaveCells);
-        while (todo) {   // terminates: every round clears one of at most 64 bits
-            const int src = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
+        mesh_wave_turns(n > kCtLaneCells && n <= kCtWaveCells, [&](int src) {
             const int bx0 = __shfl(ix0, src), by0 = __shfl(iy0, src), bh = __shfl(h, src), bn = __shfl(n, src);
             // the lanes of one wave hold 64 consecutive faces: the source lane's is f - lane + src
             ct_walk<FILL>(bx0, by0, bh, (int)(f - lane + src), lane, (unsigned)bn, 64u, res, cnt, refs, n_refs);
-        }
+        });
     }
 }
 
@@ -269,29 +235,19 @@ __global__ __launch_bounds__(kCtThreads) void k_ct_walk_lists(const CtHeader* __
                                                               const int* __restrict__ med, const int* __restrict__ huge, int n_faces,
                                                               int res, unsigned* __restrict__ cnt, int* __restrict__ refs,
                                                               unsigned n_refs) {
-    const unsigned n_med = min(hdr->n_med, (unsigned)n_faces), n_huge = min(hdr->n_huge, (unsigned)n_faces);
-    // terminates: n_med - li strictly decreases (gridDim.x >= 1).  li and the face are the same for every thread of the workgroup
-    for (unsigned li = blockIdx.x; li < n_med; li += gridDim.x) {
-        const int f = med[li];
-        if ((unsigned)f >= (unsigned)n_faces) continue;
-        const int* rc = rect + 4 * (size_t)f;
-        const int h = rc[3] - rc[2] + 1, w = rc[1] - rc[0] + 1;
-        if (h < 1 || w < 1) continue;
-        ct_walk<FILL>(rc[0], rc[2], h, f, threadIdx.x, (unsigned)(w * h), kCtThreads, res, cnt, refs, n_refs);
-    }
-    const unsigned long long items = (unsigned long long)n_huge * kCtParts;
-    // terminates: items - w strictly decreases.  Item it is part it % kCtParts of the face huge[it / kCtParts]
-    for (unsigned long long it = blockIdx.x; it < items; it += gridDim.x) {
-        const int f = huge[it / kCtParts];
-        const unsigned part = (unsigned)(it % kCtParts);
-        if ((unsigned)f >= (unsigned)n_faces) continue;
-        const int* rc = rect + 4 * (size_t)f;
-        const int h = rc[3] - rc[2] + 1, w = rc[1] - rc[0] + 1;
-        if (h < 1 || w < 1) continue;
-        const unsigned n = (unsigned)(w * h), per = (n + kCtParts - 1) / kCtParts;   // kCtParts * per >= n
-        const unsigned lo = min(n, part * per), hi = min(n, lo + per);                // part * per <= n + kCtParts: no wrap
-        ct_walk<FILL>(rc[0], rc[2], h, f, lo + threadIdx.x, hi, kCtThreads, res, cnt, refs, n_refs);
-    }
+    mesh_list_walk<kCtParts, kCtThreads, CtRect>(
+        med, min(hdr->n_med, (unsigned)n_faces), huge, min(hdr->n_huge, (unsigned)n_faces),
+        [&](int f, CtRect& r) {
+            if ((unsigned)f >= (unsigned)n_faces) return 0u;
+            const int* rc = rect + 4 * (size_t)f;
+            const int h = rc[3] - rc[2] + 1, w = rc[1] - rc[0] + 1;
+            if (h < 1 || w < 1) return 0u;
+            r.ix0 = rc[0], r.iy0 = rc[2], r.h = h;
+            return (unsigned)(w * h);
+        },
+        [&](int f, const CtRect& r, unsigned first, unsigned last, unsigned stride) {
+            ct_walk<FILL>(r.ix0, r.iy0, r.h, f, first, last, stride, res, cnt, refs, n_refs);
+        });
 }
 
 // ---- exclusive scan of the res^2 counts: block sums, their scan, the starts

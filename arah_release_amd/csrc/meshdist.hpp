@@ -66,28 +66,6 @@ inline int md_cap_cells(long long F) {
     return (int)(c < kMdMinCells ? kMdMinCells : c > kMdMaxCells ? kMdMaxCells : c);
 }
 
-inline MdIndex carve_mesh_index(void* base, int n_faces) {
-    MdIndex m;
-    m.cap_cells = md_cap_cells(n_faces);
-    char* p = reinterpret_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* q = p + off;
-        off += (bytes + 255) & ~(size_t)255;
-        return q;
-    };
-    m.hdr = reinterpret_cast<MdHeader*>(take(kMdHeaderBytes));
-    m.stat = reinterpret_cast<double*>(take(sizeof(double) * 8 * kMdStatBlocks));
-    m.cell_base = reinterpret_cast<int*>(take(sizeof(int) * ((size_t)m.cap_cells + 1)));
-    m.cell_count = reinterpret_cast<int*>(take(sizeof(int) * (size_t)m.cap_cells));
-    m.dt[0] = reinterpret_cast<uint8_t*>(take((size_t)m.cap_cells));
-    m.dt[1] = reinterpret_cast<uint8_t*>(take((size_t)m.cap_cells));
-    m.refs = reinterpret_cast<int*>(take(sizeof(int) * (size_t)kMdSpan * (size_t)n_faces));
-    m.big = reinterpret_cast<int*>(take(sizeof(int) * (size_t)n_faces));
-    m.bytes = off;
-    return m;
-}
-
 // cell of coordinate x along axis a: monotone in x, clamped into the grid
 __device__ __forceinline__ int md_cell_of(const MdHeader& H, int a, double x) {
     const double u = floor((x - H.lo[a]) * H.inv_h);

@@ -19,10 +19,10 @@ struct MeshBox {   // libmesh's rescaling to [0.5, resolution - 0.5]^3 (inside_m
     double resolution;
 };
 
-// min / max of the vertices that some face uses -> scale / translate   (one workgroup)
+// min / max of the vertices that some face uses -> scale / translate   (one workgroup of kBoxThreads threads)
 __global__ void k_mesh_box(const float* __restrict__ verts, const int* __restrict__ faces, int n_faces, double resolution,
                            MeshBox* box) {
-    __shared__ double smin[3][256], smax[3][256];
+    __shared__ double smin[3][kBoxThreads], smax[3][kBoxThreads];
     const int tid = threadIdx.x;
     double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
     for (int i = tid; i < n_faces * 3; i += blockDim.x) {
@@ -33,19 +33,7 @@ __global__ void k_mesh_box(const float* __restrict__ verts, const int* __restric
             hi[c] = fmax(hi[c], x);
         }
     }
-    for (int c = 0; c < 3; ++c) {
-        smin[c][tid] = lo[c];
-        smax[c][tid] = hi[c];
-    }
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if (tid < s)
-            for (int c = 0; c < 3; ++c) {
-                smin[c][tid] = fmin(smin[c][tid], smin[c][tid + s]);
-                smax[c][tid] = fmax(smax[c][tid], smax[c][tid + s]);
-            }
-        __syncthreads();
-    }
+    mesh_box_reduce(lo, hi, 0, smin, smax, nullptr, [](int) {});
     if (tid < 3) {
 #pragma clang fp contract(off)
         const double sc = (resolution - 1.0) / (smax[tid][0] - smin[tid][0]);

@@ -21,12 +21,11 @@
 //   k_mr_init      every key = ~0, the two list counters = 0
 //   k_mr_scatter   pass A.  One lane per face sets it up and sorts it by the pixels n of its clipped bounding box:
 //                    n <= small_area   the lane draws it alone (a marching-cubes triangle of the 256^3 body covers 4 at 512^2)
-//                    n <= wave_area    the wave draws it: the large faces of the 64 are taken in turn (ballot), their set-up is
-//                                      broadcast (shuffle) and the 64 lanes stride over the box -- at most wave_area / 64 rounds each
+//                    n <= wave_area    the wave draws it, the large faces of the 64 in turn (mesh_wave_turns of meshcommon.hpp): their
+//                                      set-up is broadcast (shuffle) and the 64 lanes stride over the box, at most wave_area / 64 rounds
 //                    n <= huge_area    the face id is appended to the MEDIUM list
 //                    more              ... to the HUGE list
-//   k_mr_lists     a one-dimensional grid strides first over the medium list, one workgroup per face, then over the huge list's
-//                  (face, part) pairs, kMrParts parts per face: an image-covering face is spread over kMrParts workgroups
+//   k_mr_lists     the two lists (mesh_list_walk of meshcommon.hpp): an image-covering face is spread over kMrParts workgroups
 //   k_mr_resolve   pass B.  One thread per pixel decodes the winner, recomputes its e_k in the same arithmetic and writes the three
 //                  outputs
 //
@@ -39,7 +38,7 @@
 // spin-wait, no grid-wide barrier, nothing persistent; every loop ends by an argument of its own, stated at the loop.
 #pragma once
 
-constexpr int kMrMaxGrid = 1 << 14;      // its own cap, a quarter of kImeshMaxGrid; kImeshThreads is meshcommon.hpp's
+constexpr int kMrMaxGrid = 1 << 14;      // the walkers' cap (meshcontains.hpp's too), a quarter of kImeshMaxGrid
 // the three thresholds as measured on the 256^3 body and its simplified meshes at 512^2 and 1024^2 (profiles/mesh_render_bench.txt)
 constexpr int kMrSmallArea = 16;         // pixels of a clipped bounding box one lane still walks alone
 constexpr int kMrWaveArea = 64;          // ... the face's wave still walks: one round of its 64 lanes
@@ -152,10 +151,7 @@ __global__ __launch_bounds__(kImeshThreads) void k_mr_scatter(const float* __res
                 else large = true;                                       // the list is full: the wave draws it
             }
         }
-        unsigned long long todo = __ballot(large);
-        while (todo) {   // terminates: every round clears one of at most 64 bits
-            const int src = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
+        mesh_wave_turns(large, [&](int src) {
             MrFace b;
             b.x0 = __shfl(t.x0, src), b.y0 = __shfl(t.y0, src), b.z0 = __shfl(t.z0, src);
             b.x1 = __shfl(t.x1, src), b.y1 = __shfl(t.y1, src), b.z1 = __shfl(t.z1, src);
@@ -164,7 +160,7 @@ __global__ __launch_bounds__(kImeshThreads) void k_mr_scatter(const float* __res
             b.pos = __shfl(t.pos, src);
             // the lanes of one wave hold 64 consecutive faces: the source lane's is f - lane + src
             mr_draw(b, (unsigned)(f - lane + src), lane, (unsigned)b.n, 64u, W, keys);
-        }
+        });
     }
 }
 
@@ -173,25 +169,12 @@ __global__ __launch_bounds__(kImeshThreads) void k_mr_lists(const float* __restr
                                                             unsigned long long* __restrict__ keys, const int* __restrict__ med_list,
                                                             const int* __restrict__ huge_list, unsigned cap,
                                                             const unsigned* __restrict__ counters) {
-    const unsigned n_med = min(counters[0], cap), n_huge = min(counters[1], cap);
-    // terminates: n_med - li strictly decreases (gridDim.x >= 1).  li and the face are the same for every thread of the workgroup
-    for (unsigned li = blockIdx.x; li < n_med; li += gridDim.x) {
-        const int f = med_list[li];
-        MrFace t;
-        if ((unsigned)f >= (unsigned)n_faces || !mr_setup(verts, n_verts, faces, f, H, W, z_near, cull, t)) continue;
-        mr_draw(t, (unsigned)f, threadIdx.x, (unsigned)t.n, kImeshThreads, W, keys);
-    }
-    const unsigned long long items = (unsigned long long)n_huge * kMrParts;
-    // terminates: items - w strictly decreases (gridDim.x >= 1).  Item w is part w % kMrParts of the face huge_list[w / kMrParts]
-    for (unsigned long long w = blockIdx.x; w < items; w += gridDim.x) {
-        const int f = huge_list[w / kMrParts];
-        const unsigned part = (unsigned)(w % kMrParts);
-        MrFace t;
-        if ((unsigned)f >= (unsigned)n_faces || !mr_setup(verts, n_verts, faces, f, H, W, z_near, cull, t)) continue;
-        const unsigned n = (unsigned)t.n, per = (n + kMrParts - 1) / kMrParts;   // kMrParts * per >= n
-        const unsigned lo = min(n, part * per), hi = min(n, lo + per);            // part * per <= n + kMrParts: no wrap
-        mr_draw(t, (unsigned)f, lo + threadIdx.x, hi, kImeshThreads, W, keys);
-    }
+    mesh_list_walk<kMrParts, kImeshThreads, MrFace>(
+        med_list, min(counters[0], cap), huge_list, min(counters[1], cap),
+        [&](int f, MrFace& t) {   // the set-up is run again: a list holds ids only
+            return (unsigned)f < (unsigned)n_faces && mr_setup(verts, n_verts, faces, f, H, W, z_near, cull, t) ? (unsigned)t.n : 0u;
+        },
+        [&](int f, const MrFace& t, unsigned first, unsigned last, unsigned stride) { mr_draw(t, (unsigned)f, first, last, stride, W, keys); });
 }
 
 __global__ __launch_bounds__(kImeshThreads) void k_mr_resolve(const float* __restrict__ verts, int n_verts, const int* __restrict__ faces,

@@ -10,7 +10,7 @@
 //   k_sg_setup     one lane per triangle: is it finite (else status 1), the BOX of lattice nodes inside its bounding box dilated by
 //                  trunc (a binary search per axis end), and its class by the nodes n of that box: lane (n <= kSgLaneNodes), wave
 //                  (<= kSgWaveNodes), workgroup (<= kSgGroupNodes: the MEDIUM list), several workgroups (the HUGE list, kSgParts
-//                  parts a triangle) -- the split of meshraster.hpp and meshcontains.hpp
+//                  parts a triangle) -- the box walkers of meshcommon.hpp (mesh_wave_turns, mesh_list_walk)
 //   k_sg_walk<0>, k_sg_walk_lists<0>   every node of every box: d^2; when d^2 <= trunc^2, a 64-bit integer atomicMin on the node's
 //                  d2.  Non-negative doubles order like their bit patterns, so this is the exact minimum whatever the arrival order
 //   k_sg_walk<1>, k_sg_walk_lists<1>   (only when the face is asked for) the same walk again: a triangle that ATTAINS the node's
@@ -46,22 +46,6 @@ struct SgScratch {
     int* huge;    // [F]
     size_t bytes;
 };
-
-inline SgScratch carve_sdf_grid(void* base, long long n_faces) {
-    SgScratch w;
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        char* p = base ? reinterpret_cast<char*>(base) + off : nullptr;
-        off += (n + 255) & ~size_t(255);
-        return p;
-    };
-    const size_t F = (size_t)n_faces;
-    w.rect = reinterpret_cast<int*>(take(256 + F * 6 * sizeof(int)));
-    w.med = reinterpret_cast<int*>(take(F * sizeof(int)));
-    w.huge = reinterpret_cast<int*>(take(F * sizeof(int)));
-    w.bytes = off;
-    return w;
-}
 
 __global__ __launch_bounds__(kSgThreads) void k_sg_init(unsigned long long* __restrict__ d2, int* __restrict__ face, long long n) {
     const long long step = (long long)gridDim.x * blockDim.x;
@@ -154,6 +138,10 @@ struct SgLattice {
     int ny, nz;
 };
 
+struct SgBox {   // a triangle's box as the walks take it: first node, h x d nodes per i-slab
+    int i0, j0, k0, h, d;
+};
+
 // Nodes first, first + stride, ... < last of the box (i0, j0, k0) with h x d nodes per i-slab (k fastest, like the lattice itself)
 // against triangle f.  PASS 0: the minimum of d^2.  PASS 1: the lowest id among the triangles that attain it.  Every node lies
 // inside the lattice: i0 + row <= i1 < nx etc. by sg_axis_range.  Returns the tests made
@@ -222,14 +210,11 @@ __global__ __launch_bounds__(kSgThreads) void k_sg_walk(const float* __restrict_
                 else n = (long long)w * h * d;
             }
             if (n > 0 && n <= kSgLaneNodes) tests += sg_walk<PASS>(tris, (int)f, L, i0, j0, k0, h, d, 0u, (unsigned)n, 1u, trunc2, d2, face);
-            unsigned long long todo = __ballot(n > kSgLaneNodes && n <= kSgWaveNodes);
-            while (todo) {   // terminates: every round clears one of at most 64 bits
-                const int src = __ffsll((long long)todo) - 1;
-                todo &= todo - 1;
+            mesh_wave_turns(n > kSgLaneNodes && n <= kSgWaveNodes, [&](int src) {
                 const int bi0 = __shfl(i0, src), bj0 = __shfl(j0, src), bk0 = __shfl(k0, src), bh = __shfl(h, src), bd = __shfl(d, src);
                 const unsigned bn = (unsigned)__shfl((int)n, src);
                 tests += sg_walk<PASS>(tris, (int)(base + src), L, bi0, bj0, bk0, bh, bd, lane, bn, 64u, trunc2, d2, face);
-            }
+            });
         }
     }
     if (PASS == 0) sg_count(tests, info);
@@ -243,30 +228,19 @@ __global__ __launch_bounds__(kSgThreads) void k_sg_walk_lists(const float* __res
                                                               int* __restrict__ face, int* __restrict__ info) {
     unsigned long long tests = 0ull;
     if (info[1] == 0) {
-        const unsigned n_med = (unsigned)min(max(info[6], 0), n_faces), n_huge = (unsigned)min(max(info[7], 0), n_faces);
-        // terminates: n_med - li strictly decreases (gridDim.x >= 1).  li and the face are the same for every thread of the workgroup
-        for (unsigned li = blockIdx.x; li < n_med; li += gridDim.x) {
-            const int f = med[li];
-            if ((unsigned)f >= (unsigned)n_faces) continue;
-            const int* rc = rect + 6 * (size_t)f;
-            const int w = rc[1] - rc[0] + 1, h = rc[3] - rc[2] + 1, d = rc[5] - rc[4] + 1;
-            if (w < 1 || h < 1 || d < 1) continue;
-            tests += sg_walk<PASS>(tris, f, L, rc[0], rc[2], rc[4], h, d, threadIdx.x, (unsigned)((long long)w * h * d), kSgThreads,
-                                   trunc2, d2, face);
-        }
-        const unsigned long long items = (unsigned long long)n_huge * kSgParts;
-        // terminates: items - it strictly decreases.  Item it is part it % kSgParts of the face huge[it / kSgParts]
-        for (unsigned long long it = blockIdx.x; it < items; it += gridDim.x) {
-            const int f = huge[it / kSgParts];
-            const unsigned part = (unsigned)(it % kSgParts);
-            if ((unsigned)f >= (unsigned)n_faces) continue;
-            const int* rc = rect + 6 * (size_t)f;
-            const int w = rc[1] - rc[0] + 1, h = rc[3] - rc[2] + 1, d = rc[5] - rc[4] + 1;
-            if (w < 1 || h < 1 || d < 1) continue;
-            const unsigned n = (unsigned)((long long)w * h * d), per = (n + kSgParts - 1) / kSgParts;   // kSgParts * per >= n
-            const unsigned lo = min(n, part * per), hi = min(n, lo + per);                             // part * per <= n + kSgParts
-            tests += sg_walk<PASS>(tris, f, L, rc[0], rc[2], rc[4], h, d, lo + threadIdx.x, hi, kSgThreads, trunc2, d2, face);
-        }
+        mesh_list_walk<kSgParts, kSgThreads, SgBox>(
+            med, (unsigned)min(max(info[6], 0), n_faces), huge, (unsigned)min(max(info[7], 0), n_faces),
+            [&](int f, SgBox& b) {
+                if ((unsigned)f >= (unsigned)n_faces) return 0u;
+                const int* rc = rect + 6 * (size_t)f;
+                const int w = rc[1] - rc[0] + 1, h = rc[3] - rc[2] + 1, d = rc[5] - rc[4] + 1;
+                if (w < 1 || h < 1 || d < 1) return 0u;
+                b.i0 = rc[0], b.j0 = rc[2], b.k0 = rc[4], b.h = h, b.d = d;
+                return (unsigned)((long long)w * h * d);   // <= nx ny nz <= INT32_MAX
+            },
+            [&](int f, const SgBox& b, unsigned first, unsigned last, unsigned stride) {
+                tests += sg_walk<PASS>(tris, f, L, b.i0, b.j0, b.k0, b.h, b.d, first, last, stride, trunc2, d2, face);
+            });
     }
     if (PASS == 0) sg_count(tests, info);
 }

@@ -59,28 +59,6 @@ struct WnIndex {
     size_t bytes;
 };
 
-inline WnIndex carve_winding(void* base, int n_faces, int depth) {
-    WnIndex ix;
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        char* p = base ? reinterpret_cast<char*>(base) + off : nullptr;
-        off += (n + 255) & ~size_t(255);
-        return p;
-    };
-    const size_t F = (size_t)n_faces, cells = (size_t)1 << (3 * depth);
-    ix.hdr = reinterpret_cast<WnHeader*>(take(256));
-    ix.key = reinterpret_cast<unsigned*>(take(F * sizeof(unsigned)));
-    ix.skey = reinterpret_cast<unsigned*>(take(F * sizeof(unsigned)));
-    ix.tmp = reinterpret_cast<int*>(take(F * sizeof(int)));
-    ix.hlev = reinterpret_cast<int*>(take(F * sizeof(int)));
-    ix.cnt64 = reinterpret_cast<long long*>(take(F * sizeof(long long)));
-    ix.prefix = reinterpret_cast<long long*>(take((F + 1) * sizeof(long long)));
-    ix.ccnt = reinterpret_cast<unsigned*>(take(cells * sizeof(unsigned)));
-    ix.cstart = reinterpret_cast<unsigned*>(take((cells + 1) * sizeof(unsigned)));
-    ix.bytes = off;
-    return ix;
-}
-
 // THE rule of depth = auto, meshing.winding_depth: the smallest depth with 8 * 4^depth >= n_faces (about eight triangles a leaf of a
 // surface), chosen from the depth sweep of tools/mesh_winding_bench.py
 inline int wn_auto_depth(int n_faces) {
@@ -125,10 +103,11 @@ __device__ __forceinline__ void wn_centroid3(const double* a, const double* b, c
 }
 
 // lo / side, validity, orientation.  The signed volume: partial sum t takes the faces t, t + 256, ... in ascending order, then
-// p[t] += p[t + s] for s = 128 .. 1 -- the order meshing.winding_orient states
+// p[t] += p[t + s] for s = 128 .. 1 -- the order meshing.winding_orient states; it rides along in the rounds of mesh_box_reduce
 __global__ __launch_bounds__(kWnThreads) void k_wn_box(const float* __restrict__ verts, int n_verts, const int* __restrict__ faces,
                                                        int n_faces, int depth, WnHeader* hdr) {
 #pragma clang fp contract(off)
+    static_assert(kWnThreads == kBoxThreads, "mesh_box_reduce");
     __shared__ double smin[3][kWnThreads], smax[3][kWnThreads], svol[kWnThreads];
     __shared__ int sbad[kWnThreads];
     const int tid = threadIdx.x;
@@ -148,24 +127,8 @@ __global__ __launch_bounds__(kWnThreads) void k_wn_box(const float* __restrict__
         }
         vol = vol + wn_det3(p[0], p[1], p[2]);
     }
-    for (int c = 0; c < 3; ++c) {
-        smin[c][tid] = lo[c];
-        smax[c][tid] = hi[c];
-    }
-    svol[tid] = vol;
-    sbad[tid] = bad;
-    __syncthreads();
-    for (int s = kWnThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            for (int c = 0; c < 3; ++c) {
-                smin[c][tid] = fmin(smin[c][tid], smin[c][tid + s]);
-                smax[c][tid] = fmax(smax[c][tid], smax[c][tid + s]);
-            }
-            svol[tid] = svol[tid] + svol[tid + s];
-            sbad[tid] |= sbad[tid + s];
-        }
-        __syncthreads();
-    }
+    svol[tid] = vol;   // visible to the first round through the barrier in front of it
+    mesh_box_reduce(lo, hi, bad, smin, smax, sbad, [&](int s) { svol[tid] = svol[tid] + svol[tid + s]; });
     if (tid == 0) {
         const double ex = smax[0][0] - smin[0][0], ey = smax[1][0] - smin[1][0], ez = smax[2][0] - smin[2][0];
         const double volume = svol[0] / 6.0;

@@ -85,28 +85,6 @@ inline int pd_cap_cells(long long n) {
     return (int)(c < kPdMinCells ? kPdMinCells : c > kPdMaxCells ? kPdMaxCells : c);
 }
 
-inline PdIndex carve_point_index(void* base, int n_points) {
-    PdIndex m;
-    m.cap_cells = pd_cap_cells(n_points);
-    char* p = reinterpret_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* q = p + off;
-        off += (bytes + 255) & ~(size_t)255;
-        return q;
-    };
-    m.hdr = reinterpret_cast<PdHeader*>(take(kPdHeaderBytes));
-    m.stat = reinterpret_cast<double*>(take(sizeof(double) * 8 * kPdStatBlocks));
-    m.coarse = reinterpret_cast<int*>(take(sizeof(int) * (size_t)kPdCoarseCap));
-    m.cell_base = reinterpret_cast<int*>(take(sizeof(int) * ((size_t)m.cap_cells + 1)));
-    m.cell_count = reinterpret_cast<int*>(take(sizeof(int) * (size_t)m.cap_cells));
-    m.dt[0] = reinterpret_cast<uint8_t*>(take((size_t)m.cap_cells));
-    m.dt[1] = reinterpret_cast<uint8_t*>(take((size_t)m.cap_cells));
-    m.recs = reinterpret_cast<PdRecord*>(take(sizeof(PdRecord) * (size_t)n_points));
-    m.bytes = off;
-    return m;
-}
-
 __device__ __forceinline__ bool pd_finite(double x, double y, double z) {
     return fabs(x) <= kMdFltMax && fabs(y) <= kMdFltMax && fabs(z) <= kMdFltMax;   // inf and NaN fail
 }

@@ -242,8 +242,10 @@ def test_point_index_layout_follows_the_kernel_source():
                      ("int", "c_occ"), ("int", "c_occ2")]
     assert struct.calcsize(hip.PointIndex._HEADER) == 11 * 8 + 11 * 4 <= const["kPdHeaderBytes"]
     assert hip.PointIndex._N_BAD == struct.calcsize("11d5i")
-    carve = re.search(r"inline PdIndex carve_point_index.*?m\.cell_base", src, re.S).group(0)
+    host = open(os.path.join(REPO, "arah_release_amd", "csrc", "arah_hip.hip")).read()   # the index is carved beside its entries
+    carve = re.search(r"static PdIndex carve_point_index.*?m\.cell_base", host, re.S).group(0)
     assert re.findall(r"m\.(\w+) = ", carve) == ["cap_cells", "hdr", "stat", "coarse"]       # what lies before cell_base
+    assert re.findall(r"take<(\w+)>\(([^;]*)\);", carve) == [("PdHeader", "1"), ("double", "8 * kPdStatBlocks"), ("int", "(size_t)kPdCoarseCap")]
     assert hip.PointIndex._cell_base_offset() == 256 + 8 * 8 * 256 + (4 * 65 ** 3 + 255) // 256 * 256
 
 

@@ -405,6 +405,34 @@ def test_scratch_sizes_of_the_indexed_mesh_entries_are_those_of_the_hand_written
     assert int(lib.arah_mesh_simplify_scratch_bytes(2 ** 26, 2 ** 28, 1)) == want
 
 
+# The query side.  Every literal below is what the library of commit e191f2c (the last one with a hand-written layout per index)
+# returned, run on the host: from the smallest to the largest size each query accepts, then the sizes it rejects (0).
+_N = (1, 2, 1000, 1024, 1025, 100000, 2 ** 20, 2 ** 26, 2 ** 27, 2 ** 31 - 1, 0, -1)
+INDEX_BYTES = {
+    "contains_index": (((0, 2), (1, 2), (1000, 512), (1025, 513), (2 ** 28, 4096), (0, 4096),
+                        (-1, 512), (2 ** 28 + 1, 512), (5, 1), (5, 4097), (5, 0)),
+                       (1024, 2048, 2251008, 2264064, 40936473088, 134283776, 0, 0, 0, 0, 0)),
+    "winding_index": (((0, 0), (0, -1), (1, -1), (1000, -1), (1025, 3), (2 ** 28, 7), (2 ** 28, -1), (7, 7),     # depth -1: chosen from F
+                       (-1, 0), (2 ** 28 + 1, 0), (5, 8), (5, -2)),
+                      (1024, 1024, 2304, 66048, 38912, 8606712576, 8606712576, 16779264, 0, 0, 0, 0)),
+    "mesh_index": (tuple((n,) for n in _N),
+                   (58368, 58368, 93952, 94720, 96000, 7617280, 79708672, 2457879040, 4873798144, 77351371264, 0, 0)),
+    "point_index": (tuple((n,) for n in _N),
+                    (1156864, 1156864, 1212160, 1213952, 1214976, 10715648, 101778944, 1242629632, 2316371456, 34528626176, 0, 0)),
+    "mesh_sdf_grid": (((0, 1, 1, 1), (1, 1, 1, 1), (1000, 5, 3, 70), (1025, 33, 17, 65), (2 ** 26, 1290, 1290, 1290), (2 ** 26, 2 ** 31 - 1, 1, 1),
+                       (-1, 1, 1, 1), (2 ** 26 + 1, 1, 1, 1), (1, 0, 1, 1), (1, 2 ** 31, 1, 1), (1, 2 ** 16, 2 ** 16, 1), (1, 2048, 1024, 1024)),
+                      (256, 1024, 32512, 33792, 2147483904, 2147483904, 0, 0, 0, 0, 0, 0)),
+}
+
+
+def test_index_sizes_of_the_query_side_are_those_of_the_hand_written_layouts():
+    from arah_release_amd import hip
+    lib = hip.load_library()
+    for name, (sizes, want) in INDEX_BYTES.items():
+        query = getattr(lib, "arah_%s_bytes" % name)
+        assert tuple(int(query(*a)) for a in sizes) == want, name
+
+
 # ---- GPU: the kernels against the specification ---------------------------------------------------------------------------------
 def strip(n_faces):
     i = torch.arange(n_faces)

@@ -59,7 +59,31 @@ def _cases():
     cv = torch.cat([cv, torch.tensor([[1.0, 1.0, 1.0], [2.0, 2.0, 2.0], [1.5, 1.5, 1.5]])])
     cf = torch.cat([cf, torch.tensor([[0, 0, 7], [8, 8, 8], [8, 10, 9], [1, 8, 1]], dtype=torch.int32)])
     out["degenerate_faces"] = (cv, cf, _points_around(cv, 3000, 3), 16, False)
+    # the class edges and the remainder of the parts: six triangles in the unit cube whose rectangles hold exactly EDGE_CELLS cells
+    ev, ef = cube(1.0)
+    for k, (w, h) in enumerate(EDGE_RECTS):           # cell k of an axis has its centre at k / 511: the rectangle starts at cell 7 + k
+        x0, y0, x1, y1 = (7 + k) / 511, (9 + k) / 511, (7 + k + w - 1) / 511, (9 + k + h - 1) / 511
+        n = ev.shape[0]
+        ev = torch.cat([ev, torch.tensor([[x0, y0, 0.25], [x1, y0, 0.5], [x0, y1, 0.75]])])
+        ef = torch.cat([ef, torch.tensor([[n, n + 1, n + 2]], dtype=torch.int32)])
+    assert rect_cells(ev, ef, 512)[12:] == list(EDGE_CELLS)
+    out["class_edges"] = (ev, ef, _points_around(ev, 6000, 4), 512, False)
     return out
+
+
+EDGE_RECTS = ((4, 4), (1, 17), (16, 32), (19, 27), (128, 256), (99, 331))     # 32769 = 99 x 331 is no multiple of the 64 parts
+EDGE_CELLS = (16, 17, 512, 513, 32768, 32769)                                 # lane | wave | wave | medium | medium | huge
+
+
+def rect_cells(verts, faces, res):
+    """The cells of every face's clipped rectangle, by the rule's own rescaling (meshing.mesh_contains), on the host."""
+    tri = verts.double()[faces.long()]
+    lo, hi = tri.reshape(-1, 3).amin(0), tri.reshape(-1, 3).amax(0)
+    scale = torch.full_like(lo, float(res - 1)) / (hi - lo)
+    tri = scale * tri + (0.5 - scale * lo)
+    r0 = tri[:, :, :2].amin(1).trunc().long().clamp(0, res - 1)
+    r1 = tri[:, :, :2].amax(1).trunc().long().clamp(0, res - 1)
+    return ((r1 - r0 + 1).prod(1)).tolist()
 
 
 @pytest.fixture(scope="module")
@@ -82,7 +106,7 @@ def _same(got, want, what):
         assert bad.numel() == 0, "%s: %s differs at %d rows, first %s" % (what, field, bad.numel(), bad[:5].tolist())
 
 
-CASES = ("f10_512", "f10_64", "f10_8", "f10_2", "icosphere", "f10_sheet", "f10_patches", "degenerate_faces")
+CASES = ("f10_512", "f10_64", "f10_8", "f10_2", "icosphere", "f10_sheet", "f10_patches", "degenerate_faces", "class_edges")
 
 
 # ------------------------------------------------------------------------------------------ 7. kernel == specification
@@ -113,6 +137,14 @@ def test_kernel_equals_the_specification(cases, name):
         assert head["n_med"] == 1 and head["n_huge"] == 0
     if name == "f10_2":
         assert head["n_huge"] == 0 and int(got[2].max()) == 1554
+    if name == "class_edges":
+        # the cube's four cap triangles cover all 512 x 512 cells, its eight wall triangles one row of 512; lane and wave classes
+        # have no counter: that every cell of every rectangle was visited once is the reference count
+        cells = rect_cells(c["verts"].cpu(), c["faces"].cpu(), 512)
+        assert cells[:12] == [512 * 512] * 4 + [512] * 8
+        assert head["n_med"] == sum(512 < n <= 1 << 15 for n in cells) == 2
+        assert head["n_huge"] == sum(n > 1 << 15 for n in cells) == 5
+        assert c["index"].n_refs == sum(cells)
     assert int(c["index"].refs.min()) >= 0 and int(c["index"].refs.max()) < c["faces"].shape[0]
 
 

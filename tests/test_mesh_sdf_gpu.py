@@ -134,6 +134,34 @@ def test_every_size_class_was_exercised():
 
 
 @gpu
+def test_class_edges_and_the_remainder_of_the_parts():
+    """Six triangles with corners on the nodes of an integer lattice and trunc = 1 / 4: a box holds the nodes of the triangle's own
+    bounding box, here exactly 32, 33, 2048, 2049, 32768 and 32769 = 33 x 3 x 331 (no multiple of the 64 parts) -- the last of the
+    lane, the first and the last of the wave and of the workgroup class, the first of the several-workgroups class."""
+    from arah_release_amd import hip, meshing
+    dev = torch.device(DEV)
+    dims, trunc = (33, 32, 683), 0.25
+    boxes = ((4, 4, 2), (3, 11, 1), (16, 16, 8), (3, 1, 683), (32, 32, 32), (33, 3, 331))
+    tris = torch.tensor([[[0, 0, 0], [w - 1, 0, d - 1], [0, h - 1, 0]] for w, h, d in boxes], dtype=torch.float32)
+    axes = [torch.arange(n, dtype=torch.float32) for n in dims]
+    nodes = [int(np.prod([int(((x >= t[:, a].min() - trunc) & (x <= t[:, a].max() + trunc)).sum()) for a, x in enumerate(axes)])) for t in tris]
+    assert nodes == [32, 33, 2048, 2049, 32768, 32769]
+    tris, axes = tris.to(dev), [x.to(dev) for x in axes]
+    want_d2, want_face = meshing.mesh_sdf_grid(tris, *axes, trunc)
+    d2, face, _, info = hip.mesh_sdf_grid(tris, *axes, trunc, want_face=True, want_info=True)          # both passes
+    _same_bits(d2, want_d2, "d2")
+    _same_bits(face, want_face, "face")
+    got = hip.read_sdf_grid_info(info)
+    assert [got[c] for c in CLASSES] == [1, 2, 2, 1] and got["status"] == 0, got
+    assert got["tests"] == sum(nodes), got                        # every node of every box once, whatever its class
+    assert got["band"] == int(torch.isfinite(want_d2).sum()) > 0
+    d2_only, no_face, _, info = hip.mesh_sdf_grid(tris, *axes, trunc, want_info=True)                  # the first pass alone
+    assert no_face is None
+    _same_bits(d2_only, want_d2, "d2 without face")
+    assert hip.read_sdf_grid_info(info) == got
+
+
+@gpu
 def test_cut_is_the_specifications_band():
     """The reference the cases share is cut after the fact; the specification with a finite trunc says the same."""
     from arah_release_amd import meshing
