@@ -2858,6 +2858,7 @@ __global__ void k_points_cam(FrameDev fr, int n, RaySet rs, const float* dists, 
 #include "meshwinding.hpp"
 #include "meshray.hpp"
 #include "pointdist.hpp"
+#include "meshintersect.hpp"
 namespace {
 
 // ------------------------------------------------------------------------------------------
@@ -6151,6 +6152,96 @@ int arah_mesh_closest(const void* index, size_t index_bytes, const float* tris, 
     hipLaunchKernelGGL(k_md_closest, dim3(g), dim3(kMdQueryThreads), 0, reinterpret_cast<hipStream_t>(stream), tris,
                        (const MdHeader*)m.hdr, (const int*)m.cell_base, (const uint8_t*)m.dt[0], (const int*)m.refs,
                        (const int*)m.big, pts, (int)n_pts, d2, (int*)face, closest, (int*)tested);
+    return check_launch();
+}
+
+// ---- self-intersections and mesh-mesh intersections (meshintersect.hpp) -----------------------------------------
+struct MiScratch {
+    float* tris;
+    unsigned char* isvoid;
+    int *above, *raw;
+    MiAcc* acc;
+    void* index;
+    size_t index_bytes, bytes;
+};
+
+static bool mi_sizes_ok(int64_t n_verts, int64_t n_faces, int64_t max_pairs) {
+    return n_verts >= 0 && n_verts <= (int64_t)INT32_MAX && n_faces >= 0 && n_faces <= (1 << 26) && max_pairs >= 0 && max_pairs <= (int64_t)INT32_MAX;
+}
+
+static MiScratch carve_intersections(void* scratch, int64_t n_faces, int64_t max_pairs) {
+    MiScratch w{};
+    MeshCarver c(scratch);
+    const size_t F = (size_t)n_faces;
+    w.tris = c.take<float>(9 * F);
+    w.isvoid = c.take<unsigned char>(F);
+    w.above = c.take<int>(F);
+    w.raw = c.take<int>((size_t)max_pairs + F);   // the rows that start below max_pairs, each shorter than F
+    w.acc = c.take<MiAcc>(1);
+    w.index_bytes = n_faces > 0 ? carve_mesh_index(nullptr, (int)n_faces).bytes : 0;
+    w.index = c.take<char>(w.index_bytes);          // 256-byte aligned when the scratch is
+    w.bytes = c.bytes();
+    return w;
+}
+
+size_t arah_mesh_intersections_scratch_bytes(int64_t n_verts, int64_t n_faces, int64_t max_pairs) {
+    if (!mi_sizes_ok(n_verts, n_faces, max_pairs)) return 0;
+    return carve_intersections(nullptr, n_faces, max_pairs).bytes;
+}
+
+int arah_mesh_intersections(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const uint8_t* group,
+                            int32_t between, const float origin[3], double scale, int64_t max_pairs, int32_t* hits, uint8_t* vert_hit,
+                            int32_t* pair_start, int32_t* pairs, int32_t* counts, int64_t* tested, void* scratch, size_t scratch_bytes,
+                            void* stream) {
+    if (!mi_sizes_ok(n_verts, n_faces, max_pairs) || !mo_quant_ok(origin, scale) || !pair_start || !counts || !scratch) return ARAH_E_BADARG;
+    if ((n_verts > 0 && (!verts || !vert_hit)) || (n_faces > 0 && (!faces || !hits)) || (max_pairs > 0 && !pairs) || (between && !group))
+        return ARAH_E_BADARG;
+    if ((reinterpret_cast<uintptr_t>(scratch) & 255) != 0) return ARAH_E_BADARG;   // the index inside it, and the 64-bit atomics
+    const MiScratch w = carve_intersections(scratch, n_faces, max_pairs);
+    if (scratch_bytes < w.bytes) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int V = (int)n_verts, F = (int)n_faces;
+    const long long cap = (long long)max_pairs;
+    if (hipMemsetAsync(w.acc, 0, sizeof(MiAcc), s) != hipSuccess) return ARAH_E_LAUNCH;
+    MoQuant q;
+    for (int a = 0; a < 3; ++a) q.origin[a] = origin[a];
+    q.scale = scale;
+    if (V > 0 || F > 0)
+        hipLaunchKernelGGL(k_mi_quant, dim3(mesh_grid(max(V, F))), dim3(kImeshThreads), 0, s, verts, V, (const int*)faces, F, q, w.tris, w.isvoid,
+                           (unsigned char*)vert_hit, w.acc);
+    if (F > 0) {
+        const int rc = arah_mesh_index_build(w.tris, F, w.index, w.index_bytes, stream);
+        if (rc != ARAH_OK) return rc;
+        const MdIndex ix = carve_mesh_index(w.index, F);
+        const MiMesh m{w.tris, w.isvoid, between ? (const unsigned char*)group : nullptr, (const int*)faces, F, V};
+        const int fg = (F + kImeshThreads - 1) / kImeshThreads, bg = min(F, kMiBigGrid);
+        hipLaunchKernelGGL(k_mi_pairs<false>, dim3(fg), dim3(kImeshThreads), 0, s, m, (const MdHeader*)ix.hdr, (const int*)ix.cell_base,
+                           (const int*)ix.refs, (const int*)ix.big, (int*)hits, w.above, (unsigned char*)vert_hit, (const int*)nullptr,
+                           (int*)nullptr, cap, w.acc, tested ? 1 : 0);
+        hipLaunchKernelGGL(k_mi_big<false>, dim3(bg), dim3(kImeshThreads), 0, s, m, (const MdHeader*)ix.hdr, (const int*)ix.big, (int*)hits,
+                           w.above, (unsigned char*)vert_hit, (const int*)nullptr, (int*)nullptr, cap, w.acc, tested ? 1 : 0);
+        mesh_scan(s, w.above, F, (int*)pair_start, (int*)pair_start + F);
+        hipLaunchKernelGGL(k_mi_tally, dim3(mesh_grid(max(V, F))), dim3(kImeshThreads), 0, s, (const unsigned char*)vert_hit, V,
+                           (const int*)w.above, F, w.acc);
+    } else {
+        if (hipMemsetAsync(pair_start, 0, sizeof(int), s) != hipSuccess) return ARAH_E_LAUNCH;
+    }
+    hipLaunchKernelGGL(k_mi_counts, dim3(1), dim3(1), 0, s, (const MiAcc*)w.acc, cap, (int*)counts, (long long*)tested, (int*)pair_start + F);
+    if (F > 0 && cap > 0) {
+        const MdIndex ix = carve_mesh_index(w.index, F);
+        const MiMesh m{w.tris, w.isvoid, between ? (const unsigned char*)group : nullptr, (const int*)faces, F, V};
+        const int fg = (F + kImeshThreads - 1) / kImeshThreads, bg = min(F, kMiBigGrid);
+        hipLaunchKernelGGL(k_mi_pairs<true>, dim3(fg), dim3(kImeshThreads), 0, s, m, (const MdHeader*)ix.hdr, (const int*)ix.cell_base,
+                           (const int*)ix.refs, (const int*)ix.big, (int*)nullptr, (int*)nullptr, (unsigned char*)nullptr,
+                           (const int*)pair_start, w.raw, cap, w.acc, 0);
+        hipLaunchKernelGGL(k_mi_big<true>, dim3(bg), dim3(kImeshThreads), 0, s, m, (const MdHeader*)ix.hdr, (const int*)ix.big, (int*)nullptr,
+                           (int*)nullptr, (unsigned char*)nullptr, (const int*)pair_start, w.raw, cap, w.acc, 0);
+        hipLaunchKernelGGL(k_mi_sort_short, dim3(mesh_grid(F)), dim3(kImeshThreads), 0, s, (const int*)pair_start, F, (const int*)w.raw,
+                           (int*)pairs, cap, (const MiAcc*)w.acc);
+        hipLaunchKernelGGL(k_mi_sort_long, dim3(bg), dim3(kImeshThreads), 0, s, (const int*)pair_start, F, (const int*)w.raw, (int*)pairs,
+                           cap, (const MiAcc*)w.acc);
+    }
+    if (cap > 0) mesh_pad(s, pairs, counts + 4, (int)cap, 2);   // the rows from the pairs written on are zero
     return check_launch();
 }
 

@@ -1,5 +1,5 @@
 // meshcommon.hpp -- what the mesh headers share.  The indexed-mesh side (mcubes.hpp, meshcc.hpp, meshsimp.hpp, meshadj.hpp,
-// meshquadric.hpp, meshorient.hpp, meshraster.hpp): the launch constants, the workgroup prefix, the ordered compaction walk, the
+// meshquadric.hpp, meshorient.hpp, meshraster.hpp, and meshintersect.hpp on the query side's grid): the launch constants, the workgroup prefix, the ordered compaction walk, the
 // one-workgroup scan, the padding of the rows between a count and a capacity, and cc_add_one.  The box walkers of both sides
 // (meshraster.hpp, meshcontains.hpp, meshsdf.hpp): the wave's turns and the walk of the two lists, at the end of this file.  The
 // one-workgroup box reduction of the query side (meshquery.hpp, meshcontains.hpp, meshwinding.hpp).  DESIGN.md ("Indexed meshes:

@@ -879,6 +879,85 @@ def repair_mesh(verts, faces, policy="majority", max_edges=64, attributes=None):
     return res
 
 
+def _intersections(verts, faces, group, between, max_pairs, what):
+    """The backend's `mesh_intersections` and the counts on the host: -> (hits, vert_hit, pairs (n,2), the five counts)."""
+    from . import meshing
+    meshing.check_max_pairs(max_pairs, what)
+    _mesh_args(verts, faces, what)
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or not verts.dtype.is_floating_point:
+        raise ValueError("%s: verts must be a floating-point (V, 3) tensor" % what)
+    if verts.device != faces.device:
+        raise ValueError("%s: verts live on %s, faces on %s" % (what, verts.device, faces.device))
+    with torch.no_grad():
+        v32 = verts.detach().to(torch.float32).contiguous()
+        if faces.is_cuda:
+            from . import hip
+            hits, vert_hit, _, pairs, counts = hip.mesh_intersections(v32, faces, group=group, between=between, max_pairs=max_pairs, trim=False)
+        else:
+            hits, vert_hit, _, pairs, counts = meshing.mesh_intersections(v32, faces, group=group, between=between, max_pairs=max_pairs)
+        c = counts.tolist()                                                     # the host synchronisation
+        if c[0] < 0:
+            raise ValueError("%s: more than 2^31 - 1 pairs do not fit an int32 count" % what)
+    return hits, vert_hit, pairs[:c[4]], c
+
+
+def self_intersections(verts, faces, max_pairs=1 << 20, return_pairs=True):
+    """Is the indexed mesh EMBEDDED -- or do some of its faces cut through each other?  (hip.mesh_intersections on the GPU,
+    meshing.mesh_intersections on the host, equal bit for bit; the rule is stated in meshing.mesh_intersections.)  Exact in
+    integers on a 2^18 lattice over the vertices' bounds: two faces intersect when an edge of one properly crosses the other.  Faces
+    that share a vertex or an edge are reported only when they fold through each other; duplicates, touching contact and coplanar
+    overlap are not intersections; a degenerate face can cut and cannot be cut; a face with an id out of range or a non-finite
+    vertex is void.  `mesh_topology` says whether a mesh is manifold and watertight; this says whether it bounds a solid without
+    passing through itself, which the parity rule of `mesh_contains`, `voxelize`, `mesh_iou` and `mesh_sdf` assumes -- `remesh`
+    repairs a mesh that is not.  -> dict of count (the pairs), faces_hit, verts_hit, void_faces, hits (F,) int32 (the faces each face
+    intersects), vert_hit (V,) uint8 (1 on the corners of the faces hit: an attribute for `render_mesh`), pairs (n,2) int32 (f < g,
+    ordered by f then g; the first max_pairs of them; None without return_pairs), truncated (count > n) and embedded (count == 0).
+    Host synchronisations: the vertices' bounds and the counts."""
+    if not isinstance(return_pairs, bool):
+        raise ValueError("self_intersections: return_pairs must be True or False, got %r" % (return_pairs,))
+    hits, vert_hit, pairs, c = _intersections(verts, faces, None, False, max_pairs if return_pairs else 0, "self_intersections")
+    return {"count": c[0], "faces_hit": c[1], "verts_hit": c[2], "void_faces": c[3], "hits": hits, "vert_hit": vert_hit,
+            "pairs": pairs if return_pairs else None, "truncated": bool(return_pairs and c[0] > c[4]), "embedded": c[0] == 0}
+
+
+def mesh_intersections(mesh_a, mesh_b, max_pairs=1 << 20, return_pairs=True):
+    """Which faces of mesh_a cut through faces of mesh_b: a posed body against a scan or a prop, frame t against frame t + 1.  Both
+    are (verts (V,3), faces (F,3)) on one device.  The two meshes are concatenated, labelled 0 / 1 and quantised over their joint
+    bounds, and only pairs from different meshes count (the rule of `self_intersections`; a mesh's own folds are not reported).  ->
+    dict of count, faces_hit_a / faces_hit_b, void_faces, hits_a (F_a,) / hits_b (F_b,) int32, vert_hit_a (V_a,) / vert_hit_b (V_b,)
+    uint8, pairs (n,2) int32 (face of a, face of b; ordered by the face of a, then of b; None without return_pairs), truncated and
+    disjoint (count == 0: the SURFACES do not meet; one mesh may still lie inside the other)."""
+    what = "mesh_intersections"
+    if not isinstance(return_pairs, bool):
+        raise ValueError("%s: return_pairs must be True or False, got %r" % (what, return_pairs))
+    for m in (mesh_a, mesh_b):
+        if not isinstance(m, (tuple, list)) or len(m) != 2 or not all(isinstance(t, torch.Tensor) for t in m):
+            raise ValueError("%s: a mesh is (verts (V, 3), faces (F, 3))" % what)
+        _mesh_args(m[0], m[1], what)
+        if m[0].dim() != 2 or not m[0].dtype.is_floating_point:
+            raise ValueError("%s: verts must be a floating-point (V, 3) tensor" % what)
+        if m[1].dim() != 2 or m[1].shape[1] != 3 or m[1].dtype.is_floating_point or m[1].dtype == torch.bool:
+            raise ValueError("%s: faces must be an (F, 3) tensor of integer ids" % what)
+    (va, fa), (vb, fb) = mesh_a, mesh_b
+    if len({va.device, fa.device, vb.device, fb.device}) != 1:
+        raise ValueError("%s: both meshes must live on one device" % what)
+    Va, Fa, Vb = int(va.shape[0]), int(fa.shape[0]), int(vb.shape[0])
+    with torch.no_grad():
+        fa64, fb64 = fa.long(), fb.long()
+        # an id out of its own mesh's range must stay out of range in the joint mesh
+        fb64 = torch.where((fb64 >= 0) & (fb64 < Vb), fb64 + Va, torch.full_like(fb64, -1))
+        fa64 = torch.where((fa64 >= 0) & (fa64 < Va), fa64, torch.full_like(fa64, -1))
+        verts = torch.cat([va.detach().to(torch.float32), vb.detach().to(torch.float32)])
+        faces = torch.cat([fa64, fb64])
+        group = torch.cat([torch.zeros(Fa, dtype=torch.uint8, device=fa.device), torch.ones(int(fb.shape[0]), dtype=torch.uint8, device=fa.device)])
+    hits, vert_hit, pairs, c = _intersections(verts, faces, group, True, max_pairs if return_pairs else 0, what)
+    if return_pairs:
+        pairs = torch.stack([pairs[:, 0], pairs[:, 1] - Fa], 1)                   # f < g and different groups: f in a, g in b
+    return {"count": c[0], "faces_hit_a": int((hits[:Fa] > 0).sum()), "faces_hit_b": int((hits[Fa:] > 0).sum()), "void_faces": c[3],
+            "hits_a": hits[:Fa], "hits_b": hits[Fa:], "vert_hit_a": vert_hit[:Va], "vert_hit_b": vert_hit[Va:],
+            "pairs": pairs if return_pairs else None, "truncated": bool(return_pairs and c[0] > c[4]), "disjoint": c[0] == 0}
+
+
 def check_smooth(smooth):
     """Validate a `smooth` option of the model's mesh entries and return the keywords of `smooth_mesh` it stands for: None
     (nothing), a number of iterations (an integer >= 0), or a dict of iterations / lamb / mu / method / boundary.  ValueError for

@@ -147,7 +147,7 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_contains_index_bytes", "arah_contains_index_count", "arah_contains_index_fill", "arah_mesh_contains",
            "arah_mesh_contains_grid", "arah_mesh_sdf_grid_bytes", "arah_mesh_sdf_grid",
            "arah_winding_index_bytes", "arah_winding_index_count", "arah_winding_index_fill", "arah_mesh_winding",
-           "arah_mesh_winding_grid"]
+           "arah_mesh_winding_grid", "arah_mesh_intersections_scratch_bytes", "arah_mesh_intersections"]
 
 _lib = None
 
@@ -205,6 +205,8 @@ def load_library():
     lib.arah_mesh_sdf_grid_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64]
     lib.arah_winding_index_bytes.restype = C.c_size_t
     lib.arah_winding_index_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.arah_mesh_intersections_scratch_bytes.restype = C.c_size_t
+    lib.arah_mesh_intersections_scratch_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the symbol is missing
     _lib = lib
@@ -1135,6 +1137,52 @@ def mesh_orient(verts, faces, policy="majority", adjacency=None, quant=None):
                                     _ptr(comp_flags), _ptr(vol_hi), _ptr(vol_lo), _ptr(counts), _ptr(scratch),
                                     C.c_size_t(scratch.numel()), _stream()), "arah_mesh_orient")
     return flip, face_comp, faces_out, comp_faces, comp_flags, vol_hi, vol_lo, counts
+
+
+def mesh_intersections(verts, faces, group=None, between=False, quant=None, max_pairs=1 << 20, want_tested=False, trim=True):
+    """Which faces of an indexed mesh cut through each other (arah_mesh_intersections, csrc/meshintersect.hpp): verts (V,3) float32
+    and faces (F,3) integer ids on the GPU, group (F,) uint8 or None, between: only pairs from different groups count.  -> hits (F,)
+    int32, vert_hit (V,) uint8, pair_start (F+1,) int32, pairs (n,2) int32, counts (5,) int32 as meshing.mesh_intersections describes
+    them, and equal to it bit for bit; with want_tested a sixth result, the (1,) int64 number of pairs that reached the six tests.
+    One host read for the vertices' bounds (meshing.orient_quant) unless `quant` is given.  trim=True reads the pair total once
+    more, to return pairs with its n = counts[4] rows and to raise ValueError for more than 2^31 - 1 pairs; trim=False returns the
+    (max_pairs, 2) buffer, zero from row counts[4] on, without that read -- counts[0] == -1 then says that the pairs did not fit."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    what = "mesh_intersections"
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise ValueError("%s: verts must be a (V, 3) float32 tensor" % what)
+    f, V, F = _mesh_cc_args(faces, int(verts.shape[0]), what)
+    v = verts.detach().contiguous()
+    if v.device != f.device:
+        raise ValueError("%s: verts live on %s, faces on %s" % (what, v.device, f.device))
+    if F > meshing.INTERSECT_MAX_FACES:
+        raise ValueError("%s: at most 2^26 faces, got %d" % (what, F))
+    between = meshing.check_between(between, group, what)
+    group = meshing.check_group(group, F, f.device, what)
+    cap = meshing.check_max_pairs(max_pairs, what)
+    origin, scale = meshing._check_quant(meshing.orient_quant(v) if quant is None else quant, what)
+    dev, i32 = f.device, torch.int32
+    with _on_device(dev):
+        scratch = _mesh_cc_buf(dev, int(lib.arah_mesh_intersections_scratch_bytes(V, F, cap)))
+        hits = torch.empty(F, dtype=i32, device=dev)
+        vert_hit = torch.empty(V, dtype=torch.uint8, device=dev)
+        pair_start = torch.empty(F + 1, dtype=i32, device=dev)
+        pairs = torch.empty(cap, 2, dtype=i32, device=dev)
+        counts = torch.empty(5, dtype=i32, device=dev)
+        tested = torch.empty(1, dtype=torch.int64, device=dev) if want_tested else None
+        _check(lib.arah_mesh_intersections(_ptr(v), C.c_int64(V), _ptr(f), C.c_int64(F), _ptr(group.contiguous()) if between else None,
+                                           C.c_int32(1 if between else 0), (C.c_float * 3)(*origin), C.c_double(scale), C.c_int64(cap),
+                                           _ptr(hits), _ptr(vert_hit), _ptr(pair_start), _ptr(pairs) if cap else None, _ptr(counts),
+                                           _ptr(tested), _ptr(scratch), C.c_size_t(scratch.numel()), _stream()),
+               "arah_mesh_intersections")
+    if trim:
+        total, _, _, _, written = counts.tolist()
+        if total < 0:
+            raise ValueError("%s: more than 2^31 - 1 pairs do not fit an int32 count" % what)
+        pairs = pairs[:written]
+    return (hits, vert_hit, pair_start, pairs, counts) + ((tested,) if want_tested else ())
 
 
 def mesh_boundary_loops(faces, n_verts, adjacency=None):

@@ -955,6 +955,150 @@ def mesh_orient(verts, faces, policy="majority", adjacency=None, quant=None):
     return (flip.to(torch.uint8), face_comp.to(i32), faces_out, comp_faces.to(i32), comp_flags.to(i32), vol_hi, vol_lo, counts)
 
 
+# ---- self-intersections and mesh-mesh intersections -------------------------------------------------------------------------------
+INTERSECT_MAX_FACES = 1 << 26            # the faces the uniform grid of the device indexes
+INTERSECT_MAX_PAIRS = 2 ** 31 - 1
+INTERSECT_NAMES = ("hits", "vert_hit", "pair_start", "pairs", "counts")
+
+
+def check_max_pairs(max_pairs, what="mesh_intersections"):
+    if isinstance(max_pairs, bool) or not isinstance(max_pairs, (int, np.integer)) or not 0 <= int(max_pairs) <= INTERSECT_MAX_PAIRS:
+        raise ValueError("%s: max_pairs must be an integer in [0, 2^31 - 1], got %r" % (what, max_pairs))
+    return int(max_pairs)
+
+
+def check_between(between, group, what="mesh_intersections"):
+    if not isinstance(between, (bool, np.bool_)):
+        raise ValueError("%s: between must be True or False, got %r" % (what, between))
+    if bool(between) and group is None:
+        raise ValueError("%s: between=True needs a group label per face" % what)
+    return bool(between)
+
+
+def check_group(group, n_faces, device, what="mesh_intersections"):
+    """group: None, or (F,) uint8 on the faces' device: -> the tensor or None."""
+    if group is None:
+        return None
+    if not isinstance(group, torch.Tensor) or group.dtype != torch.uint8 or tuple(group.shape) != (int(n_faces),):
+        raise ValueError("%s: group must be an (F,) uint8 tensor, F = %d" % (what, int(n_faces)))
+    if group.device != device:
+        raise ValueError("%s: group lives on %s, faces on %s" % (what, group.device, device))
+    return group.detach()
+
+
+def intersect_soup(verts, faces, quant):
+    """The quantised corners of `mesh_intersections`: verts (V,3) float32, faces (F,3) integer ids, quant = (origin, scale) ->
+    q (F,3,3) int64 (face, corner, axis), void (F,) bool.  q = llrint(clamp((double(v) - double(origin)) scale, -2^18, 2^18)); a face
+    with an id outside [0, V) or a non-finite vertex is void and has q = 0.  q.float() is the soup the device indexes."""
+    v, f, V, in_range = _mesh_verts(verts, faces, "mesh_intersections")
+    origin, scale = _check_quant(quant, "mesh_intersections")
+    F, dev = int(f.shape[0]), f.device
+    if V == 0 or F == 0:
+        return torch.zeros(F, 3, 3, dtype=torch.int64, device=dev), torch.ones(F, dtype=torch.bool, device=dev)
+    p = v[f.clamp(0, V - 1)]                                                        # (F,3,3): corner, axis
+    void = ~in_range | ~torch.isfinite(p).all(2).all(1)
+    lim = 2.0 ** ORIENT_VOL_BITS
+    x = (p.to(torch.float64) - torch.tensor(origin, dtype=torch.float64, device=dev)) * scale
+    q = torch.where(void[:, None, None], torch.zeros_like(x), x).clamp(-lim, lim).round().long()
+    return q, void
+
+
+def _orient4(a, b, c, d):
+    """det[b - a; c - a; d - a] of (..., 3) int64 rows.  |q| <= 2^18: every difference is at most 2^19 in magnitude, every triple
+    product at most 2^57, and the six of them add up to less than 6 2^57 < 2^60: exact in int64."""
+    u, v, w = b - a, c - a, d - a
+    return (u[..., 0] * (v[..., 1] * w[..., 2] - v[..., 2] * w[..., 1]) - u[..., 1] * (v[..., 0] * w[..., 2] - v[..., 2] * w[..., 0])
+            + u[..., 2] * (v[..., 0] * w[..., 1] - v[..., 1] * w[..., 0]))
+
+
+def _edges_cross(e, t):
+    """(K,3,3) int64 each: does an edge of triangle e[k] properly cross triangle t[k]? -> (K,) bool."""
+    side = [_orient4(t[:, 0], t[:, 1], t[:, 2], e[:, k]) for k in range(3)]
+    cut = torch.zeros(e.shape[0], dtype=torch.bool, device=e.device)
+    for k in range(3):
+        j = (k + 1) % 3
+        apart = ((side[k] > 0) & (side[j] < 0)) | ((side[k] < 0) & (side[j] > 0))
+        s = [_orient4(e[:, k], e[:, j], t[:, m], t[:, (m + 1) % 3]) for m in range(3)]
+        inside = ((s[0] >= 0) & (s[1] >= 0) & (s[2] >= 0)) | ((s[0] <= 0) & (s[1] <= 0) & (s[2] <= 0))
+        cut = cut | (apart & inside)
+    return cut
+
+
+def mesh_intersections(verts, faces, group=None, between=False, quant=None, max_pairs=1 << 20, chunk_pairs=1 << 22):
+    """Which faces of an indexed mesh cut through each other: verts (V,3) float32, faces (F,3) integer ids, F <= 2^26.  With `group`
+    (F,) uint8 and between=True only pairs of faces from different groups count: the intersections BETWEEN two meshes.
+
+    Integers only, so the answer is unique, symmetric in the two faces, and independent of the order of the faces, of their winding
+    and of the order anything arrives in.
+
+    QUANTISATION.  q = llrint(clamp((double(v) - double(origin)) scale, -2^18, 2^18)) per coordinate, (origin, scale) = quant, by
+    default `orient_quant(verts)` (the lattice of `mesh_orient`'s volume policies).  A face with a vertex id outside [0, V) or a
+    non-finite vertex is VOID: it intersects nothing and is counted.  Vertices that share an id share a q, and vertices of an
+    unwelded soup that coincide still coincide after quantisation.
+
+    ORIENTATION.  orient(a, b, c, d) = det[b - a; c - a; d - a] in int64: every difference is at most 2^19 in magnitude, every
+    triple product at most 2^57, the six-term determinant stays below 2^60.
+
+    PROPER CROSSING.  The segment pq properly crosses the triangle abc when orient(a,b,c,p) and orient(a,b,c,q) are both non-zero
+    and of opposite sign, and orient(p,q,a,b), orient(p,q,b,c), orient(p,q,c,a) are all >= 0 or all <= 0 (the piercing point lies in
+    the closed triangle).
+
+    INTERSECTING FACES.  Two faces f != g intersect when any of the six tests holds: the three edges of one against the other
+    face, both ways.  There is no special case for neighbours: an edge with an endpoint in the other face's plane never crosses it
+    properly, so faces that share a vertex or an edge are reported only when they really fold through each other.  Exact
+    duplicates, touching contact (a vertex or an edge lying in the other face's plane) and coplanar overlap are NOT intersections.
+    A degenerate face (zero area; a repeated id is not void) has orient(a,b,c,.) = 0 everywhere: it can cut with its edges but
+    cannot be cut.
+
+    -> hits (F,) int32: the number of faces each face intersects; vert_hit (V,) uint8: 1 for every corner of a face with hits > 0;
+    pair_start (F+1,) int32 and pairs (n,2) int32: the pairs f < g ordered by f, then g -- pair_start[f] is where f's pairs begin
+    among ALL pairs and is always exact, pairs holds the first n = min(total, max_pairs) of them; counts (5,) int32: pairs, faces
+    hit, vertices hit, void faces, pairs written.  Nothing is silently truncated: counts[0] > counts[4] says so.  More than
+    2^31 - 1 pairs raise ValueError.
+
+    A chunked brute force over all (f, g > f) with the integer box reject, chunk_pairs bounding the temporaries (the result does not
+    depend on it); plain tensor operations on the tensor's device: the specification of arah_mesh_intersections
+    (csrc/meshintersect.hpp), and what runs for meshes on the host."""
+    what = "mesh_intersections"
+    v, f, V, _ = _mesh_verts(verts, faces, what)
+    F, dev, i32 = int(f.shape[0]), f.device, torch.int32
+    if F > INTERSECT_MAX_FACES:
+        raise ValueError("%s: at most 2^26 faces, got %d" % (what, F))
+    between = check_between(between, group, what)
+    group = check_group(group, F, dev, what)
+    cap = check_max_pairs(max_pairs, what)
+    if isinstance(chunk_pairs, bool) or not isinstance(chunk_pairs, (int, np.integer)) or int(chunk_pairs) < 1:
+        raise ValueError("%s: chunk_pairs must be a positive integer, got %r" % (what, chunk_pairs))
+    q, void = intersect_soup(v, f, _check_quant(orient_quant(v) if quant is None else quant, what))
+    lo, hi = q.amin(1), q.amax(1)                                                   # (F,3): the integer boxes
+    ids = torch.arange(F, device=dev)
+    rows = max(1, int(chunk_pairs) // max(F, 1))
+    found = []
+    for f0 in range(0, F, rows):
+        a = slice(f0, min(f0 + rows, F))
+        cand = (ids[a, None] < ids[None, :]) & ~void[a, None] & ~void[None, :]
+        cand = cand & (lo[a, None] <= hi[None, :]).all(2) & (lo[None, :] <= hi[a, None]).all(2)
+        if between:
+            cand = cand & (group[a, None] != group[None, :])
+        i, j = torch.nonzero(cand, as_tuple=True)                                    # row-major: ordered by f, then g
+        i = i + f0
+        hit = _edges_cross(q[j], q[i]) | _edges_cross(q[i], q[j])
+        found.append(torch.stack([i[hit], j[hit]], 1))
+    allp = torch.cat(found) if found else torch.zeros(0, 2, dtype=torch.int64, device=dev)
+    total = int(allp.shape[0])
+    if total > INTERSECT_MAX_PAIRS:
+        raise ValueError("%s: %d pairs do not fit an int32 count" % (what, total))
+    above = torch.bincount(allp[:, 0], minlength=F)
+    hits = above + torch.bincount(allp[:, 1], minlength=F)
+    pair_start = torch.zeros(F + 1, dtype=torch.int64, device=dev)
+    pair_start[1:] = torch.cumsum(above, 0)
+    vert_hit = torch.zeros(V, dtype=torch.uint8, device=dev)
+    vert_hit[f[hits > 0].reshape(-1)] = 1                                           # a face that is hit is not void: ids in range
+    pairs = allp[:cap]
+    counts = torch.tensor([total, int((hits > 0).sum()), int(vert_hit.sum()), int(void.sum()), int(pairs.shape[0])], dtype=i32, device=dev)
+    return hits.to(i32), vert_hit, pair_start.to(i32), pairs.to(i32).contiguous(), counts
+
+
 def mesh_boundary_loops(faces, n_verts, adjacency=None):
     """The boundary of an indexed mesh: faces (F,3) integer ids over V = n_verts vertices, validity and traversal as in
     `mesh_adjacency`.  A BOUNDARY HALF-EDGE is a directed edge a->b of a valid face whose undirected edge carries exactly one valid

@@ -1160,6 +1160,25 @@ class MetaAvatarRender(nn.Module):
         res["mesh"] = mesh
         return res
 
+    def mesh_intersections(self, inputs, n_side=256, space="posed", clean=None, simplify=None, smooth=None, max_pairs=1 << 20):
+        """Where the body of frame `inputs` passes through itself, as an indexed mesh -- the mesh `render_mesh` draws and `cast_rays`
+        sees: `canonical_mesh(inputs, n_side, clean=, simplify=, smooth=)`, skinned forward ("verts_posed") for space="posed", as it is
+        for space="canonical".  Linear blend skinning pushes the surface through itself at bent elbows, armpits and thighs; ray hits,
+        occlusion, parity containment and signed distances are wrong there.  -> the dict of geometry.self_intersections (count,
+        faces_hit, hits, vert_hit, pairs, void_faces, truncated, embedded, ...) plus "mesh", the dict of canonical_mesh.  vert_hit
+        (V,) uint8 can be drawn: geometry.render_mesh(mesh["verts_posed"], mesh["faces"], ..., attributes={"hit":
+        vert_hit.float()[:, None]}).  Eval only, GPU only; the host synchronisations are canonical_mesh's and
+        geometry.self_intersections'."""
+        from . import geometry
+        if space not in ("posed", "canonical"):
+            raise ValueError("mesh_intersections: space must be 'posed' or 'canonical', got %r" % (space,))
+        mesh = self.canonical_mesh(inputs, n_side=n_side, attributes=("verts_posed",) if space == "posed" else (), clean=clean,
+                                   simplify=simplify, smooth=smooth)
+        verts = mesh["verts_posed"] if space == "posed" else mesh["verts"]
+        res = geometry.self_intersections(verts, mesh["faces"], max_pairs=max_pairs)
+        res["mesh"] = mesh
+        return res
+
     def geometry_metrics(self, inputs, gt, n_side=256, method="lattice", n_samples=100000, seed=0, clean=None, thresholds=None,
                          iou=None, sdf=None, sdf_band=0.05, inside="parity"):
         """Geometry scores of the posed body of frame `inputs` against a ground truth `gt` in world metres on the inputs' GPU -- a

@@ -41,6 +41,8 @@
  *   arah_mesh_orient /      (none: the reference's users repair scans with trimesh's fix_normals / fill_holes; consistent orientation
  *   arah_mesh_boundary_loops /  by the double cover of the face graph, the boundary loops, and small holes closed by a fan around
  *   arah_mesh_fill_holes    the loop's exact mean)
+ *   arah_mesh_intersections (none: the pairs of faces that cut through each other, by an exact integer predicate on the lattice of
+ *                           arah_mesh_orient; with a group label, the intersections between two meshes)
  *   arah_mesh_rasterize /   pytorch3d MeshRasterizer's three outputs for an INDEXED mesh (pix_to_face, zbuf, bary_coords; one face per
  *   arah_mesh_interpolate   pixel, no blur, perspective-correct) and interpolate_face_attributes over them; arah_rasterize below
  *                           stays what the gen_cano_mesh branch draws with
@@ -694,6 +696,33 @@ int arah_surface_metrics(const float* tris_a, int32_t n_faces_a, const int32_t* 
                          const int32_t* face_ab, int32_t n_a, const float* tris_b, int32_t n_faces_b,
                          const int32_t* sample_face_b, const double* d2_ba, const int32_t* face_ba, int32_t n_b, double* out,
                          void* scratch, size_t scratch_bytes, void* stream);
+
+/* Which faces of an indexed mesh cut through each other (csrc/meshintersect.hpp; no reference counterpart;
+ * meshing.mesh_intersections is the rule, bit for bit).  verts [n_verts][3], faces [n_faces][3].  q = llrint(clamp((double(v) -
+ * double(h_origin)) scale, -2^18, 2^18)) per coordinate; a face with an id outside [0, n_verts) or a non-finite vertex is VOID and
+ * intersects nothing.  orient(a,b,c,d) = det[b-a; c-a; d-a] in int64 (below 2^60).  A segment pq properly crosses a triangle abc
+ * when orient(a,b,c,p) and orient(a,b,c,q) are non-zero and of opposite sign and orient(p,q,a,b), orient(p,q,b,c), orient(p,q,c,a)
+ * are all >= 0 or all <= 0; two faces f != g intersect when an edge of one properly crosses the other, either way round.  Faces
+ * that share a vertex or an edge are reported only when they fold through each other; duplicates, touching contact and coplanar
+ * overlap are not intersections; a degenerate face can cut and cannot be cut.  between != 0: only pairs with group[f] != group[g]
+ * count (group [n_faces] u8; may be NULL otherwise).  Candidates come from arah_mesh_index_build over the quantised soup, inside
+ * the scratch.
+ *   hits        [n_faces] i32: the faces each face intersects
+ *   vert_hit    [n_verts] u8: 1 for every corner of a face with hits > 0
+ *   pair_start  [n_faces + 1] i32, pairs [max_pairs][2] i32: the pairs f < g ordered by f, then g; pair_start is exact, pairs holds
+ *               the first max_pairs of them and zero rows behind them (may be NULL for max_pairs = 0)
+ *   counts      DEVICE int32 [5]: pairs, faces hit, vertices hit, void faces, pairs written.  More than 2^31 - 1 pairs: counts[0] =
+ *               pair_start[n_faces] = -1, no pair is written and the rest of pair_start means nothing
+ *   tested      DEVICE int64 or NULL: pairs that reached the six tests, both sides counted (a figure for benchmarks)
+ * Integer atomics only, on sums; the result is unique.  0 <= n_faces <= 2^26, 0 <= n_verts, max_pairs <= INT32_MAX, else
+ * ARAH_E_BADARG, as for a missing pointer, a quantisation that is not finite or a scratch that is not 256-byte aligned.  scratch:
+ * arah_mesh_intersections_scratch_bytes(n_verts, n_faces, max_pairs) device bytes (0 for such sizes).  n_faces = 0 still writes
+ * counts and pair_start.  No host synchronisation, no allocation. */
+size_t arah_mesh_intersections_scratch_bytes(int64_t n_verts, int64_t n_faces, int64_t max_pairs);
+int arah_mesh_intersections(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const uint8_t* group,
+                            int32_t between, const float h_origin[3], double scale, int64_t max_pairs, int32_t* hits, uint8_t* vert_hit,
+                            int32_t* pair_start, int32_t* pairs, int32_t* counts, int64_t* tested, void* scratch, size_t scratch_bytes,
+                            void* stream);
 
 /* Rays against the indexed soup (csrc/meshray.hpp; no reference counterpart).  index / tris: as for arah_mesh_closest, the index
  * is only read.  origins, dirs [R,3] f32 (dirs need not be unit: t is in units of |d|).  The rule per ray and face is Woop, Benthin
