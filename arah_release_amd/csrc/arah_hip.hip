@@ -135,11 +135,12 @@ struct Counters {
     // tiered eval forward (tier.hpp): ray / sample bookkeeping, and the share of n_canon / n_density that phase 2 ran
     TierStatsRaw tier;
     unsigned long long n_canon_p2, n_density_p2;
+    unsigned long long n_shade_culled, n_shade_rescued;   // the shading cull (k_shade_split / k_composite_cull)
     unsigned long long tier_snap[2];
     unsigned long long clk[8 * 16];   // instrumented builds (-DARAH_CLOCKS): s_memtime ticks per wave slot and phase
     unsigned long long clk_shade[8 * 16];   // the same for k_shade
 };
-static_assert(offsetof(Counters, tier_snap) == sizeof(ArahCounters), "the head of Counters is the ABI's ArahCounters");
+static_assert(offsetof(Counters, n_shade_culled) == sizeof(ArahCounters), "the head of Counters is the ABI's ArahCounters");
 #ifdef ARAH_CLOCKS
 typedef PhaseClk KernelClk;
 #else
@@ -2828,6 +2829,212 @@ __global__ void k_composite_maps(int n, int S, int render_last_pt, const float* 
     depth[i] = any ? dz : 0.f;
 }
 
+// ------------------------------------------------------------------------------------------
+// loop D, the shading cull (ArahSampling::full_shading == ARAH_SHADING_LAZY): normal and colour only for the sigma > 0 samples whose weight can
+// still change a pixel.  Behind the surface sample of a surface ray every sample multiplies the transmittance by
+// exp(-sigma delta) (2e-3 at beta = 1e-3 and 6.25 mm spacing), and from the third or fourth on w = alpha * trans is below half
+// an ulp of the accumulated colour: r += c * w returns r whatever c is, and the sample's normal and colour are dead values
+// like those of the sigma = +0 samples.  Which samples those are is GUESSED from the densities (k_shade_split: the "tail"
+// samples, not shaded) and VERIFIED by the compositing walk on the very r, g, b it accumulates (k_composite_cull); a ray
+// whose verification fails has its tail shaded after all and is composited again (RESCUE), so the image is the uncut
+// one bit for bit whatever the guess was.  Every decision stays on the device.
+// ------------------------------------------------------------------------------------------
+// rays with a sigma > 0 sample (the shading list holds exactly those samples): the only rays k_shade_split has to walk
+__global__ void k_cull_mark(const int* __restrict__ list, const int* __restrict__ count, int S, uint8_t* __restrict__ ray_pos) {
+    const int n = *count;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) ray_pos[list[i] / S] = 1;
+}
+
+// Appends sample ids base + b for every set bit b of (m0: samples 0..63, m1: samples 64..127) of every lane to list: one
+// atomic per wave.  Every lane of the wave has to call it (lanes with nothing to append pass 0, 0).
+__device__ __forceinline__ void append_sample_bits(unsigned long long m0, unsigned long long m1, int base, int* list, int* count) {
+    const int lane = threadIdx.x & 63;
+    const int cnt = __popcll(m0) + __popcll(m1);
+    int incl = cnt;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(incl, d);
+        if (lane >= d) incl += t;
+    }
+    const int total = __shfl(incl, 63);
+    int o = 0;
+    if (lane == 63 && total) o = atomicAdd(count, total);
+    o = __shfl(o, 63) + incl - cnt;
+    for (; m0; m0 &= m0 - 1) list[o++] = base + __ffsll((long long)m0) - 1;
+    for (; m1; m1 &= m1 - 1) list[o++] = base + 64 + __ffsll((long long)m1) - 1;
+}
+
+// sum of v over the wave, added to *ctr by one lane (every lane of the wave calls it)
+__device__ __forceinline__ void wave_count_add(unsigned long long* ctr, int v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+    if ((threadIdx.x & 63) == 0) count_add(ctr, v);
+}
+
+// The guess.  A thread owns a ray and walks the densities of its valid samples as k_composite does: alpha, w and trans by
+// k_composite's expressions in k_composite's order, and the running weight sum ws.  A sigma > 0 sample is a TAIL sample iff
+// ws + 8 w == ws (its weight is below half an ulp of an eighth of the weight so far, i.e. of every channel's running colour
+// as long as that is at least ws / 8), otherwise a HEAD sample.  Head samples go to `head` (k_shade's list), every sigma > 0
+// sample gets its tag (1 tail, 0 head).  It reads only what the compositing walk reads, so the tiered and the untiered
+// forward decide alike.  Nothing here has to be rigorous: k_composite_cull checks every tail sample.
+template <bool CHUNK>
+__global__ __launch_bounds__(128) void k_shade_split(int n, int S, int render_last_pt, const float* __restrict__ z,
+                                                     const uint8_t* __restrict__ mask, const f32x4* __restrict__ shaded,
+                                                     const uint8_t* __restrict__ ray_pos, uint8_t* __restrict__ tag,
+                                                     int* __restrict__ head, int* head_count) {
+#pragma clang fp contract(off)   // the fused operations are written out below, as in k_composite_cull
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long h0 = 0ull, h1 = 0ull;
+    const size_t base = (size_t)(i < n ? i : 0) * S;
+    if (i < n && ray_pos[i]) {
+        const float inv_steps = 1.0f / (float)S;
+        float ws = 0.f, trans = 1.0f, pd = 0.f, pz = 0.f;
+        int prev = -1;
+        auto step = [&](int s, float zs, float dens) {
+            if (prev >= 0) {
+                float delta;
+                if (s < S) delta = zs - pz;
+                else delta = render_last_pt ? 1e10f : inv_steps;
+                const float alpha = 1.0f - expf(-pd * delta);
+                const float w = alpha * trans;
+                if (pd > 0.f) {
+                    const bool tail = ws + 8.0f * w == ws;
+                    tag[base + prev] = tail ? 1 : 0;
+                    if (!tail) {
+                        if (prev < 64) h0 |= 1ull << prev;
+                        else h1 |= 1ull << (prev - 64);
+                    }
+                }
+                ws = fmaf(alpha, trans, ws);
+                trans *= (1.0f - alpha + 1e-7f);
+            }
+            if (s < S) {
+                prev = s;
+                pd = dens;
+                pz = zs;
+            }
+        };
+        if (CHUNK) {
+            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+            for (int s0 = 0; s0 < S; s0 += 8) {
+                const u32x2 m8 = *reinterpret_cast<const u32x2*>(mask + base + s0);
+                const f32x4 z0 = *reinterpret_cast<const f32x4*>(z + base + s0), z1 = *reinterpret_cast<const f32x4*>(z + base + s0 + 4);
+                float d8[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) d8[u] = shaded[base + s0 + u][3];
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    if (((u < 4 ? m8[0] : m8[1]) >> (8 * (u & 3))) & 0xffu) step(s0 + u, u < 4 ? z0[u & 3] : z1[u & 3], d8[u]);
+            }
+        } else {
+            for (int s = 0; s < S; ++s)
+                if (mask[base + s] != 0) step(s, z[base + s], shaded[base + s][3]);
+        }
+        step(S, 0.f, 0.f);
+    }
+    append_sample_bits(h0, h1, (int)base, head, head_count);
+}
+
+// The check, and the image.  k_composite's arithmetic in k_composite's order (a body of its own: k_composite's code stays as
+// it is); a tail sample still holds {0, 0, 0, density} from the density pass.  Before the walk steps over one it tests
+// r + 2 w == r (and g, b) on the accumulators themselves.  For 0 <= c <= 2 and w >= 0 both fmaf(c, w, r) and r + c * w lie in
+// [r, fl(r + 2 w)] (rounding is monotonic), so a passed test means that the sample's colour, whatever it is, would have left
+// r as it is -- which is what adding 0 * w does.  c <= 2: the colour head (mlp.hpp, color_mlp / color_mlp_bp) returns
+// 1.0f / (1.0f + expf(-x)) with expf(.) >= 0, so the denominator is >= 1 and the quotient <= 1 up to the division's rounding
+// (a few ulp at most), and >= 0.  wsum and trans never depended on colour.  A ray with a failed test is flagged (ray_flag) and
+// its tail samples go to the rescue list; the r that is tested is the r that is written, so no other kernel has to round alike.
+// RESCUE: the flagged rays once more, after k_shade has run on the rescue list -- every sample taken as shaded, i.e.
+// k_composite's walk unchanged.  Without a flagged ray every thread leaves after one byte.
+template <bool CHUNK, bool RESCUE>
+__global__ __launch_bounds__(128) void k_composite_cull(int n, int S, int render_last_pt, const float* __restrict__ z,
+                                                        const uint8_t* __restrict__ mask, const f32x4* __restrict__ shaded,
+                                                        const uint8_t* __restrict__ tag, uint8_t* ray_flag, int* __restrict__ rescue,
+                                                        int* rescue_count, float* __restrict__ rgb, float* __restrict__ acc,
+                                                        uint8_t* __restrict__ vol_mask, unsigned long long* ctr_culled,
+                                                        unsigned long long* ctr_rescued) {
+    // k_composite is compiled with fp contraction, which fuses its `r += ps[0] * w` into fmaf(ps[0], w, r) and its
+    // `wsum += w` into fmaf(alpha, trans, wsum) (w = alpha * trans itself stays a rounded product).  Here the same operations
+    // are written out and contraction is off, so that the further uses of w in this body cannot change what gets fused.
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < n && (!RESCUE || ray_flag[i] != 0);
+    if (RESCUE && !live) return;
+    const size_t base = (size_t)(i < n ? i : 0) * S;
+    unsigned long long t0 = 0ull, t1 = 0ull;   // the ray's tail samples
+    bool bad = false;
+    if (live) {
+        const float inv_steps = 1.0f / (float)S;
+        float r = 0.f, g = 0.f, b = 0.f, wsum = 0.f, trans = 1.0f;
+        int prev = -1;
+        f32x4 ps = {0.f, 0.f, 0.f, 0.f};
+        float pz = 0.f;
+        bool any = false, ptail = false;
+        auto step = [&](int s, float zs, const f32x4 sh, bool tail) {
+            if (prev >= 0) {
+                float delta;
+                if (s < S) delta = zs - pz;
+                else delta = render_last_pt ? 1e10f : inv_steps;
+                const float alpha = 1.0f - expf(-ps[3] * delta);
+                const float w = alpha * trans;
+                if (!RESCUE && ptail) {
+                    const float w2 = 2.0f * w;
+                    bad = bad || !(r + w2 == r && g + w2 == g && b + w2 == b);
+                    if (prev < 64) t0 |= 1ull << prev;
+                    else t1 |= 1ull << (prev - 64);
+                }
+                r = fmaf(ps[0], w, r);
+                g = fmaf(ps[1], w, g);
+                b = fmaf(ps[2], w, b);
+                wsum = fmaf(alpha, trans, wsum);
+                trans *= (1.0f - alpha + 1e-7f);
+            }
+            if (s < S) {
+                prev = s;
+                ps = sh;
+                pz = zs;
+                ptail = tail;
+                any = true;
+            }
+        };
+        if (CHUNK) {
+            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+            for (int s0 = 0; s0 < S; s0 += 8) {
+                const u32x2 m8 = *reinterpret_cast<const u32x2*>(mask + base + s0);
+                const f32x4 z0 = *reinterpret_cast<const f32x4*>(z + base + s0), z1 = *reinterpret_cast<const f32x4*>(z + base + s0 + 4);
+                u32x2 t8 = {0u, 0u};   // tags are written for sigma > 0 samples only: looked at under sh[3] > 0
+                if (!RESCUE) t8 = *reinterpret_cast<const u32x2*>(tag + base + s0);
+                f32x4 sh[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) sh[u] = shaded[base + s0 + u];
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    if (((u < 4 ? m8[0] : m8[1]) >> (8 * (u & 3))) & 0xffu)
+                        step(s0 + u, u < 4 ? z0[u & 3] : z1[u & 3], sh[u],
+                             !RESCUE && sh[u][3] > 0.f && (((u < 4 ? t8[0] : t8[1]) >> (8 * (u & 3))) & 0xffu) != 0u);
+            }
+        } else {
+            for (int s = 0; s < S; ++s)
+                if (mask[base + s] != 0) {
+                    const f32x4 sh = shaded[base + s];
+                    step(s, z[base + s], sh, !RESCUE && sh[3] > 0.f && tag[base + s] != 0);
+                }
+        }
+        step(S, 0.f, ps, false);
+        rgb[(size_t)i * 3] = any ? r : 0.f;
+        rgb[(size_t)i * 3 + 1] = any ? g : 0.f;
+        rgb[(size_t)i * 3 + 2] = any ? b : 0.f;
+        if (acc) acc[i] = any ? fminf(fmaxf(wsum, 0.f), 1.f) : 0.f;
+        vol_mask[i] = any ? 1 : 0;
+        if (!RESCUE) ray_flag[i] = bad ? 1 : 0;
+    }
+    if (!RESCUE) {   // whole waves from here on
+        const int n_tail = __popcll(t0) + __popcll(t1);
+        wave_count_add(ctr_culled, bad ? 0 : n_tail);
+        wave_count_add(ctr_rescued, bad ? n_tail : 0);
+        append_sample_bits(bad ? t0 : 0ull, bad ? t1 : 0ull, (int)base, rescue, rescue_count);
+    }
+}
+
 // IDR:114-115, 142-143, 251: camera-space surface points, zeroed off-surface
 __global__ void k_points_cam(FrameDev fr, int n, RaySet rs, const float* dists, const uint8_t* conv,
                              const float* points_hat_norm, const float* __restrict__ pose, float* points_cam) {
@@ -2904,6 +3111,10 @@ struct Workspace {
     int *listC, *listD;
     int* tcounts;         // [TC_COUNT]
     uint8_t* ray_tier;    // [N] 0 skipped (certified zero), 1 surface ray, 2 promoted
+    // the shading cull: the tag of every sigma > 0 sample (1 tail, 0 head); per ray "has a sigma > 0 sample", later "failed the
+    // check", behind a 256-byte header that holds the device-side counts {head list, rescue list} (one memset clears both)
+    uint8_t* cull_tag;    // [N*S]
+    uint8_t* cull_ray;    // [256 + N]
     size_t bytes;
 };
 
@@ -2951,6 +3162,8 @@ Workspace carve(void* base, int n_rays, int n_steps) {
     w.listD = c.take<int>(Q);
     w.tcounts = c.take<int>(TC_COUNT);
     w.ray_tier = c.take<uint8_t>(N);
+    w.cull_tag = c.take<uint8_t>(Q);
+    w.cull_ray = c.take<uint8_t>(256 + N);
     w.bytes = align_up(c.off, 256);
     return w;
 }
@@ -3842,6 +4055,14 @@ int arah_counters_read(const void* workspace, ArahCounters* h_out, void* stream)
     Workspace w = carve(const_cast<void*>(workspace), 1, 1);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (hipMemcpyAsync(h_out, w.ctr, sizeof(ArahCounters), hipMemcpyDeviceToHost, s) != hipSuccess) return ARAH_E_LAUNCH;
+    return hipStreamSynchronize(s) == hipSuccess ? ARAH_OK : ARAH_E_LAUNCH;
+}
+
+int arah_shade_cull_counters(const void* workspace, uint64_t* h_out2, void* stream) {
+    if (!workspace || !h_out2) return ARAH_E_BADARG;
+    Workspace w = carve(const_cast<void*>(workspace), 1, 1);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (hipMemcpyAsync(h_out2, &w.ctr->n_shade_culled, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s) != hipSuccess) return ARAH_E_LAUNCH;
     return hipStreamSynchronize(s) == hipSuccess ? ARAH_OK : ARAH_E_LAUNCH;
 }
 
@@ -5082,6 +5303,11 @@ static void launch_density(const FrameDev& fd, Workspace& w, const float* pts, l
                       w.shaded, next_list, next_count, &w.ctr->n_sdf_fwd, &w.ctr->n_density);
 }
 
+// ArahSampling.full_shading was a flag before it got a third value: anything but the two lazy modes shades every valid sample
+static bool shade_everything(const ArahSampling* cfg) {
+    return cfg->full_shading != ARAH_SHADING_LAZY && cfg->full_shading != ARAH_SHADING_LAZY_NO_CULL;
+}
+
 // the per-sample normal slab of arah_render_maps and the two maps it composites into
 struct MapsOut {
     f32x4* nrm;      // [N*S] posed unit normal of every shaded sample (k_shade<..., MAPS>)
@@ -5105,7 +5331,7 @@ static int shade_impl(const ArahFrame* f, const ArahSampling* cfg, Workspace& w,
     const int g = grid_for(Q, kTile);
     const int* slist = w.listA;
     const int* scount = &w.counts[0];
-    if (!cfg->full_shading) {   // pass 1: densities; only samples that can receive weight reach k_shade
+    if (!shade_everything(cfg)) {   // pass 1: densities; only samples that can receive weight reach k_shade
         if (cfg->ev_density[0] && cfg->ev_density[1]) hipEventRecord(reinterpret_cast<hipEvent_t>(cfg->ev_density[0]), s);
         launch_density(fd, w, pts, Q, (const int*)w.listA, (const int*)&w.counts[0], w.listB, &w.counts[1], s);
         if (cfg->ev_density[0] && cfg->ev_density[1]) hipEventRecord(reinterpret_cast<hipEvent_t>(cfg->ev_density[1]), s);
@@ -5148,12 +5374,44 @@ static int shade_tail(const ArahFrame* f, const ArahSampling* cfg, Workspace& w,
     const int S = cfg->n_steps;
     const long long Q = (long long)n * S;
     const int g = grid_for(Q, kTile);
+    const bool chunk = S % 8 == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0 && (reinterpret_cast<uintptr_t>(mask) & 7) == 0;
+    const dim3 gc((n + 127) / 128), bc(128);
+    // the shading cull: lazy shading without maps only (full shading shades everything by definition, and k_composite_maps sums
+    // signed normals, for which the check's bound does not hold)
+    if (cfg->full_shading == ARAH_SHADING_LAZY && !maps) {
+        int* ccount = reinterpret_cast<int*>(w.cull_ray);   // {head list, rescue list}
+        uint8_t* ray_flag = w.cull_ray + 256;
+        int *head = w.listC, *rescue = w.listD;             // both free by now on either path (slist is listB)
+        const f32x4* shaded = w.shaded;
+        hipMemsetAsync(w.cull_ray, 0, 256 + (size_t)n, s);
+        hipLaunchKernelGGL(k_cull_mark, dim3(min(1024, grid_for(Q, 256))), dim3(256), 0, s, slist, scount, S, ray_flag);
+        if (chunk) hipLaunchKernelGGL(k_shade_split<true>, gc, bc, 0, s, n, S, cfg->render_last_pt, z, mask, shaded,
+                                      (const uint8_t*)ray_flag, w.cull_tag, head, &ccount[0]);
+        else hipLaunchKernelGGL(k_shade_split<false>, gc, bc, 0, s, n, S, cfg->render_last_pt, z, mask, shaded,
+                                (const uint8_t*)ray_flag, w.cull_tag, head, &ccount[0]);
+        if (cfg->ev_shade[0] && cfg->ev_shade[1]) hipEventRecord(reinterpret_cast<hipEvent_t>(cfg->ev_shade[0]), s);
+        launch_shade<false>(f, cfg, w, fd, dirs, pts, T, head, &ccount[0], g, nullptr, s);
+        if (cfg->ev_shade[0] && cfg->ev_shade[1]) hipEventRecord(reinterpret_cast<hipEvent_t>(cfg->ev_shade[1]), s);
+        if (chunk) hipLaunchKernelGGL((k_composite_cull<true, false>), gc, bc, 0, s, n, S, cfg->render_last_pt, z, mask, shaded,
+                                      (const uint8_t*)w.cull_tag, ray_flag, rescue, &ccount[1], rgb, acc, vol_mask,
+                                      &w.ctr->n_shade_culled, &w.ctr->n_shade_rescued);
+        else hipLaunchKernelGGL((k_composite_cull<false, false>), gc, bc, 0, s, n, S, cfg->render_last_pt, z, mask, shaded,
+                                (const uint8_t*)w.cull_tag, ray_flag, rescue, &ccount[1], rgb, acc, vol_mask,
+                                &w.ctr->n_shade_culled, &w.ctr->n_shade_rescued);
+        // the rescue: both launches return at once while no ray failed its check (the benchmark's frames: none does)
+        launch_shade<false>(f, cfg, w, fd, dirs, pts, T, rescue, &ccount[1], g, nullptr, s);
+        if (chunk) hipLaunchKernelGGL((k_composite_cull<true, true>), gc, bc, 0, s, n, S, cfg->render_last_pt, z, mask, shaded,
+                                      (const uint8_t*)nullptr, ray_flag, (int*)nullptr, (int*)nullptr, rgb, acc, vol_mask,
+                                      (unsigned long long*)nullptr, (unsigned long long*)nullptr);
+        else hipLaunchKernelGGL((k_composite_cull<false, true>), gc, bc, 0, s, n, S, cfg->render_last_pt, z, mask, shaded,
+                                (const uint8_t*)nullptr, ray_flag, (int*)nullptr, (int*)nullptr, rgb, acc, vol_mask,
+                                (unsigned long long*)nullptr, (unsigned long long*)nullptr);
+        return check_launch();
+    }
     if (cfg->ev_shade[0] && cfg->ev_shade[1]) hipEventRecord(reinterpret_cast<hipEvent_t>(cfg->ev_shade[0]), s);
     if (maps) launch_shade<true>(f, cfg, w, fd, dirs, pts, T, slist, scount, g, maps->nrm, s);
     else launch_shade<false>(f, cfg, w, fd, dirs, pts, T, slist, scount, g, nullptr, s);
     if (cfg->ev_shade[0] && cfg->ev_shade[1]) hipEventRecord(reinterpret_cast<hipEvent_t>(cfg->ev_shade[1]), s);
-    const bool chunk = S % 8 == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0 && (reinterpret_cast<uintptr_t>(mask) & 7) == 0;
-    const dim3 gc((n + 127) / 128), bc(128);
     if (maps) {
         if (chunk) hipLaunchKernelGGL(k_composite_maps<true>, gc, bc, 0, s, n, S, cfg->render_last_pt, z, mask, (const f32x4*)w.shaded,
                                       rgb, acc, vol_mask, (const f32x4*)maps->nrm, maps->normal, maps->depth);
@@ -6727,7 +6985,7 @@ static int render_impl(const ArahFrame* f, const ArahSampling* cfg, const float*
     }
     rc = trace_impl(f, w, cam_loc, rays_per_cam, dirs, near_far, n, 0, w.o_xnorm, w.o_Tray, o_conv, o_start, w.o_end, s, skip);
     if (rc) return rc;
-    if (cfg->occupancy && !cfg->full_shading) {
+    if (cfg->occupancy && !shade_everything(cfg)) {
         rc = render_tiers(f, cfg, w, cam_loc, rays_per_cam, dirs, near_far, o_conv, o_start, w.o_end, n, rgb,
                           acc ? acc : w.o_acc, vol_mask, maps, s);
         if (rc) return rc;
@@ -6820,7 +7078,7 @@ int arah_tier_audit(const ArahFrame* f, const ArahSampling* cfg, const float* ca
     if (!f || !cfg || n < 0 || !workspace || !audit_buf) return ARAH_E_BADARG;
     int rc = check_sampling(cfg);
     if (rc) return rc;
-    if (!cfg->occupancy || cfg->full_shading || rate_log2 < 0 || rate_log2 > 31) return ARAH_E_BADARG;   // a TIERED render only
+    if (!cfg->occupancy || shade_everything(cfg) || rate_log2 < 0 || rate_log2 > 31) return ARAH_E_BADARG;   // a TIERED render only
     if (n > 0 && (!cam_loc || !dirs || !near_far)) return ARAH_E_BADARG;
     const int S = cfg->n_steps;
     Workspace w = carve(workspace, n, S);

@@ -110,6 +110,10 @@ class ArahCounters(C.Structure):
 
 
 COUNTER_BYTES = C.sizeof(ArahCounters)
+# the shading cull's two counters (n_shade_culled, n_shade_rescued) sit in the workspace directly behind ArahCounters
+# (include/arah_hip.h: arah_shade_cull_counters)
+CULL_COUNTER_BYTES = 16
+SHADING_LAZY, SHADING_FULL, SHADING_LAZY_NO_CULL = 0, 1, 2   # ArahSampling.full_shading
 
 
 class ArahTierAudit(C.Structure):
@@ -123,7 +127,7 @@ class ArahTierAudit(C.Structure):
 AUDIT_BYTES = C.sizeof(ArahTierAudit)
 
 EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_prepare_body", "arah_workspace_bytes", "arah_counters_reset",
-           "arah_counters_read", "arah_sdf_eval", "arah_sdf_grid", "arah_rasterize", "arah_skin_lbs", "arah_skin_jacobian", "arah_color_eval",
+           "arah_counters_read", "arah_shade_cull_counters", "arah_sdf_eval", "arah_sdf_grid", "arah_rasterize", "arah_skin_lbs", "arah_skin_jacobian", "arah_color_eval",
            "arah_nearest_inverse_lbs", "arah_broyden3_lbs", "arah_joint_root_find", "arah_trace", "arah_sample_canonicalize",
            "arah_shade_composite", "arah_shade_points", "arah_render", "arah_shade_train_slab_bytes", "arah_shade_train_forward",
            "arah_shade_train_backward", "arah_composite_train_forward", "arah_composite_train_backward", "arah_gram_skinny_blocks", "arah_gram_skinny", "arah_colsum_blocks", "arah_colsum", "arah_inverse3x3", "arah_hsoftmax_train_forward", "arah_hsoftmax_train_backward", "arah_pose_tree_forward", "arah_pose_tree_backward", "arah_gemv_rows", "arah_mesh_query_scratch_bytes", "arah_mesh_query", "arah_dominant_kernel",
@@ -405,7 +409,7 @@ class Workspace:
                     _check(load_library().arah_counters_reset(_ptr(self.buf), _stream(self.device)),
                            "arah_counters_reset")
                 else:   # the work counters sit at the head of the workspace: a grown buffer inherits them
-                    self.buf[:COUNTER_BYTES].copy_(old[:COUNTER_BYTES])
+                    self.buf[:COUNTER_BYTES + CULL_COUNTER_BYTES].copy_(old[:COUNTER_BYTES + CULL_COUNTER_BYTES])
         return self.buf
 
     def reset_counters(self):
@@ -417,7 +421,12 @@ class Workspace:
         with torch.cuda.device(self.device):
             _check(load_library().arah_counters_read(_ptr(self.buf), C.byref(out), _stream(self.device)),
                    "arah_counters_read")
-        return {k: int(getattr(out, k)) for k, _ in ArahCounters._fields_}
+            cull = (C.c_uint64 * 2)()
+            _check(load_library().arah_shade_cull_counters(_ptr(self.buf), cull, _stream(self.device)),
+                   "arah_shade_cull_counters")
+        res = {k: int(getattr(out, k)) for k, _ in ArahCounters._fields_}
+        res["n_shade_culled"], res["n_shade_rescued"] = int(cull[0]), int(cull[1])
+        return res
 
 
 # The occupancy buffer's layout (csrc/tier.hpp: the constants kOcc*, kTierBand; csrc/arah_hip.hip: carve_occ hands the arrays out in
@@ -581,7 +590,7 @@ class Sampling:
     """ArahSampling + the device linspace tables (bit-identical to torch.linspace on the CPU)."""
 
     def __init__(self, device, n_steps=64, n_near=16, n_far=16, cano_view_dirs=True, render_last_pt=False,
-                 full_shading=False, shade_engine=None, canon_kernel=None):
+                 full_shading=False, shade_engine=None, canon_kernel=None, shade_cull=True):
         if n_steps < n_near + n_far + 1 or n_steps > ARAH_MAX_STEPS:
             raise ValueError("need n_near + n_far + 1 <= n_steps <= %d (ARAH_E_SAMPLING)" % ARAH_MAX_STEPS)
         self.lin_steps = torch.linspace(0.0, 1.0, n_steps, dtype=torch.float32).to(device)
@@ -590,7 +599,9 @@ class Sampling:
         s = ArahSampling()
         s.n_steps, s.n_near, s.n_far = int(n_steps), int(n_near), int(n_far)
         s.cano_view_dirs, s.render_last_pt = int(bool(cano_view_dirs)), int(bool(render_last_pt))
-        s.full_shading = int(bool(full_shading))
+        # lazy shading also leaves the sigma > 0 samples unshaded whose weight cannot change a pixel (same image, bit for bit)
+        # unless shade_cull is False
+        s.full_shading = SHADING_FULL if full_shading else (SHADING_LAZY if shade_cull else SHADING_LAZY_NO_CULL)
         s.lin_steps, s.lin_near, s.lin_far = _ptr(self.lin_steps), _ptr(self.lin_near), _ptr(self.lin_far)
         # per-call switches of the library (it reads no environment itself): None = this process's default
         s.shade_engine = default_shade_engine() if shade_engine is None else int(shade_engine)
@@ -2537,7 +2548,7 @@ def render(frame, ws, sampling, cam_loc, dirs, near_far, pose34, tiered=False, m
     n, S = d.shape[0], sampling.n_steps
     buf = ws.ensure(n, S)
     cfg = sampling.handle
-    if tiered and not cfg.full_shading:
+    if tiered and cfg.full_shading != SHADING_FULL:
         occ = ws.occupancy(frame)
         buf = ws.buf
         cfg = ArahSampling.from_buffer_copy(sampling.handle)   # the bitmap is this frame's: a private copy of the call's struct

@@ -288,6 +288,8 @@ class BodyRayTracing(nn.Module):
         # per-call engine switches of the C ABI (None: the process default, hip.default_shade_engine / default_canon_kernel)
         self.shade_engine = None
         self.canon_kernel = None
+        # lazy shading: sigma > 0 samples whose weight cannot change a pixel are not shaded (ArahSampling.shade_cull; same image)
+        self.shade_cull = True
         self._events = {}
 
     def workspace(self, device):
@@ -308,10 +310,11 @@ class BodyRayTracing(nn.Module):
 
     def sampling(self, device, cano_view_dirs=True, render_last_pt=False, full_shading=None):
         full = bool(self.full_shading if full_shading is None else full_shading)
-        key = (str(device), bool(cano_view_dirs), bool(render_last_pt), full, self.shade_engine, self.canon_kernel)
+        key = (str(device), bool(cano_view_dirs), bool(render_last_pt), full, self.shade_engine, self.canon_kernel,
+               bool(self.shade_cull))
         if key not in self._sampling:
             sm = hip.Sampling(device, self.n_steps, self.near_surface_vol_samples, self.far_surface_vol_samples,
-                              cano_view_dirs, render_last_pt, full, self.shade_engine, self.canon_kernel)
+                              cano_view_dirs, render_last_pt, full, self.shade_engine, self.canon_kernel, self.shade_cull)
             for which, (a, b) in self._events.items():
                 sm.set_events(which, a, b)
             self._sampling[key] = sm
@@ -569,12 +572,13 @@ class IDHRNetwork(nn.Module):
         key = (dev, id(ws))   # one record per scratch = per stream with a frame in flight: each has its own counter
         g = self._guard.get(key)
         if g is not None and self.guard_mode != "strict" and g["event"].query():   # (strict: read behind the frame itself)
-            ctr = g["host"].tolist()                                 # the nine counters of ArahCounters behind an earlier frame
+            ctr = g["host"].tolist()                                 # the counters of ArahCounters behind an earlier frame
             now = int(ctr[8])
             grew = now - g["seen"] if now >= g["seen"] else now      # the counters may have been reset in between
             g["seen"] = now
-            d_col, d_den = ctr[4] - g["col"], ctr[6] - g["den"]      # n_col, n_density since the last look
-            g["col"], g["den"] = ctr[4], ctr[6]
+            col = ctr[4] + ctr[20]                                   # n_col + n_shade_culled (the first counter behind ArahCounters): the sigma > 0 samples, shaded or not
+            d_col, d_den = col - g["col"], ctr[6] - g["den"]         # ... and n_density since the last look
+            g["col"], g["den"] = col, ctr[6]
             win_full, g["win_full"] = g["win_full"], False
             if d_den > 0 and d_col >= 0 and not win_full:            # lazily shaded frame(s) went by: their share of sigma > 0 samples
                 self.shade_ratio = d_col / d_den
@@ -595,14 +599,14 @@ class IDHRNetwork(nn.Module):
         if g is None:
             if len(self._guard) >= 8:
                 self._guard.pop(next(iter(self._guard)))
-            g = self._guard[key] = {"host": torch.zeros(hip.COUNTER_BYTES // 8, dtype=torch.int64).pin_memory(), "event": torch.cuda.Event(),
+            g = self._guard[key] = {"host": torch.zeros((hip.COUNTER_BYTES + hip.CULL_COUNTER_BYTES) // 8, dtype=torch.int64).pin_memory(), "event": torch.cuda.Event(),
                                     "seen": 0, "col": 0, "den": 0, "win_full": False, "tier": (0, 0, 0)}
         return g
 
     def _split_guard_arm(self, g, ws, full=False):
         g["win_full"] = g["win_full"] or bool(full)   # a frame that shaded everything says nothing about the share
         # n_split_nonfinite is the ninth 64-bit counter at the head of the workspace (include/arah_hip.h: ArahCounters)
-        g["host"].copy_(ws.buf[0:hip.COUNTER_BYTES].view(torch.int64), non_blocking=True)
+        g["host"].copy_(ws.buf[0:hip.COUNTER_BYTES + hip.CULL_COUNTER_BYTES].view(torch.int64), non_blocking=True)
         g["event"].record()
 
     def _tier_audit_mode(self):

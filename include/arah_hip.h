@@ -140,6 +140,13 @@ typedef struct ArahBody {
                                    frame, and order the stream that built it before the frame's stream) */
 } ArahBody;
 
+/* ArahSampling.full_shading.  The shading cull of ARAH_SHADING_LAZY (ignored by arah_render_maps): deep behind the surface
+ * w = alpha * trans falls below half an ulp of the accumulated colour and r += c * w returns r for every c in [0, 1]; such
+ * samples are guessed from the densities, left unshaded, and the guess is verified by the compositing walk on its own
+ * accumulators (a ray that fails has them shaded after all and is composited again, on the device).  The switch is a value of
+ * this field and the cull's two counters have a reader of their own (arah_shade_cull_counters), so that ArahSampling and
+ * ArahCounters keep their sizes. */
+enum { ARAH_SHADING_LAZY = 0, ARAH_SHADING_FULL = 1, ARAH_SHADING_LAZY_NO_CULL = 2 };
 enum { ARAH_SHADE_ENGINE_DEFAULT = 0 /* bf16 x 3 on split frames */, ARAH_SHADE_ENGINE_FP32 = 1 };
 enum { ARAH_CANON_KERNEL_WAVE = 0 /* point-owning waves, hi fragments in LDS */, ARAH_CANON_KERNEL_TILE = 1,
        ARAH_CANON_KERNEL_WAVE_L2 = 2 };
@@ -148,9 +155,11 @@ typedef struct ArahSampling {
     int32_t n_steps, n_near, n_far;   /* configs/default.yaml:49-51 */
     int32_t cano_view_dirs;           /* model.cano_view_dirs */
     int32_t render_last_pt;           /* model.render_last_pt */
-    int32_t full_shading;             /* 0 (default): exact lazy shading -- normal + colour only for samples whose
-                                         density is > 0, the rest provably get weight 0; 1: shade every valid sample
-                                         like the reference does (same image, bit for bit) */
+    int32_t full_shading;             /* ARAH_SHADING_*.  0 (default): exact lazy shading -- normal + colour only for
+                                         samples whose density is > 0 (the rest provably get weight 0), and of those only
+                                         for the ones whose weight can still change a pixel (the shading cull, below);
+                                         1: shade every valid sample like the reference does; 2: lazy shading without
+                                         the cull, every sigma > 0 sample shaded.  Same image bit for bit in all three. */
     /* device copies of torch.linspace(0, 1, k) for k = n_steps, n_near + 1, n_far (RT:317,330,340);
      * the caller builds them once per config so that depth samples are bit-identical to torch's */
     const float* lin_steps;
@@ -261,6 +270,11 @@ size_t arah_workspace_bytes(int32_t n_rays, int32_t n_steps);
 /* zero / read the device-side work counters that live at the head of a workspace */
 int arah_counters_reset(void* workspace, void* stream);
 int arah_counters_read(const void* workspace, ArahCounters* h_out, void* stream); /* syncs the stream */
+/* The shading cull's two counters, which sit in the workspace directly behind ArahCounters (arah_counters_reset zeroes them
+ * too): h_out2[0] = n_shade_culled, sigma > 0 samples never shaded; h_out2[1] = n_shade_rescued, samples set aside first
+ * and shaded after all because their ray failed the check.  n_col keeps counting what was shaded:
+ * n_col + n_shade_culled = sigma > 0 samples.  Syncs the stream. */
+int arah_shade_cull_counters(const void* workspace, uint64_t* h_out2, void* stream);
 
 /* ---- unit seams (parity tests; also usable on their own) --------------------------------- */
 /* n_pts = 0 is accepted by every seam: nothing is read or written, and the point / output pointers may be null */
