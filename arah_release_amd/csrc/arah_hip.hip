@@ -1956,6 +1956,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_canon_solve(FrameDev fr, const 
 #include "meshsimp.hpp"
 #include "meshadj.hpp"
 #include "meshquadric.hpp"
+#include "meshcollapse.hpp"
 #include "meshorient.hpp"
 #include "meshraster.hpp"
 #include "canon_wave.hpp"
@@ -4621,6 +4622,97 @@ int arah_mesh_adjacency(const int32_t* faces, int64_t n_faces, int64_t n_verts, 
         mesh_pad(s, nbr_in, nbr_start + V, 6 * F, 1);
     }
     hipLaunchKernelGGL(k_ma_finish, dim3(1), dim3(64), 0, s, (int*)counts, V);
+    return check_launch();
+}
+
+// ---- one round of edge-collapse decimation (csrc/meshcollapse.hpp) ---------------------------------------------------------------
+struct MxScratch {
+    int *vf_start, *vf, *nbr_start, *nbr, *nbr_out, *nbr_in, *acounts;
+    unsigned char *vert_flags, *pinned;
+    int *owner, *merge_to, *move_edge, *vsrc, *new_id, *blk_count, *blk_base;
+    unsigned long long *m1, *m2;
+    void* adjacency;
+    size_t adjacency_bytes, bytes;
+};
+
+static MxScratch carve_collapse(void* scratch, int64_t n_verts, int64_t n_faces) {
+    MxScratch w{};
+    MeshCarver c(scratch);
+    const size_t V = (size_t)n_verts, F = (size_t)n_faces, nb = mesh_blocks(std::max(6 * n_faces, n_verts));
+    w.vf_start = c.take<int>(V + 1);
+    w.vf = c.take<int>(3 * F);
+    w.nbr_start = c.take<int>(V + 1);
+    w.nbr = c.take<int>(6 * F);
+    w.nbr_out = c.take<int>(6 * F);
+    w.nbr_in = c.take<int>(6 * F);
+    w.acounts = c.take<int>(8);
+    w.vert_flags = c.take<unsigned char>(V);
+    w.pinned = c.take<unsigned char>(V);
+    w.owner = c.take<int>(6 * F);
+    w.merge_to = c.take<int>(V);
+    w.move_edge = c.take<int>(V);
+    w.vsrc = c.take<int>(V);
+    w.new_id = c.take<int>(V);
+    w.blk_count = c.take<int>(nb);
+    w.blk_base = c.take<int>(nb);
+    w.m1 = c.take<unsigned long long>(V);
+    w.m2 = c.take<unsigned long long>(V);
+    w.adjacency_bytes = carve_adjacency(nullptr, n_verts, n_faces).bytes;
+    w.adjacency = c.take<char>(w.adjacency_bytes);
+    w.bytes = c.bytes();
+    return w;
+}
+
+size_t arah_mesh_collapse_round_scratch_bytes(int64_t n_verts, int64_t n_faces) {
+    if (!ma_sizes_ok(n_verts, n_faces)) return 0;
+    return carve_collapse(nullptr, n_verts, n_faces).bytes;
+}
+
+int arah_mesh_collapse_round(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t need, double reg,
+                             float max_cost, float* verts_out, int32_t* faces_out, int32_t* vert_src, int32_t* face_src,
+                             int32_t* counts, float* edge_pos, uint64_t* edge_key, uint8_t* edge_reason, void* scratch,
+                             size_t scratch_bytes, void* stream) {
+    if (!ma_sizes_ok(n_verts, n_faces) || !counts || !scratch || need < 0) return ARAH_E_BADARG;
+    if (!std::isfinite(reg) || !(reg >= 0.0) || !(max_cost >= 0.0f)) return ARAH_E_BADARG;
+    if ((n_verts > 0 && (!verts || !verts_out || !vert_src)) || (n_faces > 0 && (!faces || !faces_out || !face_src || !edge_pos || !edge_key || !edge_reason)))
+        return ARAH_E_BADARG;
+    const MxScratch w = carve_collapse(scratch, n_verts, n_faces);
+    if (scratch_bytes < w.bytes) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int V = (int)n_verts, F = (int)n_faces, cap = 6 * F;
+    const dim3 tb(kImeshThreads), gv(mesh_grid(V));
+    // an empty mesh runs the same launches over nothing (a grid is never empty: the compactions of no element are left out)
+    if (int rc = arah_mesh_adjacency(faces, n_faces, n_verts, w.vf_start, w.vf, w.nbr_start, w.nbr, w.nbr_out, w.nbr_in, w.vert_flags,
+                                     w.acounts, w.adjacency, w.adjacency_bytes, stream))
+        return rc;
+    hipLaunchKernelGGL(k_mx_pin, gv, tb, 0, s, verts, V, (const int*)w.nbr_start, (const int*)w.nbr_out, (const int*)w.nbr_in, w.pinned,
+                       w.owner, w.m1, w.merge_to, w.move_edge, w.vsrc, (int*)counts);
+    if (F > 0)
+        hipLaunchKernelGGL(k_mx_edge, dim3(mesh_grid(cap)), tb, 0, s, verts, (const int*)faces, V, cap, (const int*)w.vf_start,
+                           (const int*)w.vf, (const int*)w.nbr_start, (const int*)w.nbr, (const unsigned char*)w.pinned,
+                           (const int*)w.owner, reg, max_cost, edge_pos, (unsigned long long*)edge_key, (unsigned char*)edge_reason,
+                           w.m1, (int*)counts);
+    hipLaunchKernelGGL(k_mx_m2, gv, tb, 0, s, V, (const int*)w.nbr_start, (const int*)w.nbr, (const unsigned long long*)w.m1, w.m2);
+    if (F > 0)
+        mesh_compact_passes(s, (int)mesh_blocks(cap), w.blk_count, w.blk_base, counts + 2, [&](auto fill, int* count, const int* base) {
+            hipLaunchKernelGGL((k_mx_select<decltype(fill)::value>), dim3(mesh_blocks(cap)), tb, 0, s, verts, V, cap,
+                               (const int*)w.nbr_start, (const int*)w.nbr, (const int*)w.owner, (const float*)edge_pos,
+                               (const unsigned long long*)edge_key, (const unsigned long long*)w.m2, (int)need, count, base,
+                               w.merge_to, w.move_edge, w.vsrc);
+        });
+    if (V > 0)
+        mesh_compact_passes(s, (int)mesh_blocks(V), w.blk_count, w.blk_base, counts, [&](auto fill, int* count, const int* base) {
+            hipLaunchKernelGGL((k_mx_verts<decltype(fill)::value>), dim3(mesh_blocks(V)), tb, 0, s, verts, V, (const int*)w.merge_to,
+                               (const int*)w.move_edge, (const int*)w.vsrc, (const float*)edge_pos, count, base, (const int*)counts,
+                               w.new_id, verts_out, (int*)vert_src);
+        });
+    if (F > 0)
+        mesh_compact_passes(s, (int)mesh_blocks(F), w.blk_count, w.blk_base, counts + 1, [&](auto fill, int* count, const int* base) {
+            hipLaunchKernelGGL((k_mx_faces<decltype(fill)::value>), dim3(mesh_blocks(F)), tb, 0, s, (const int*)faces, F, V,
+                               (const int*)w.merge_to, (const int*)w.new_id, count, base, (const int*)counts, (int*)faces_out,
+                               (int*)face_src);
+        });
+    hipLaunchKernelGGL(k_mx_finish, dim3(1), dim3(64), 0, s, (int*)counts, (int)need);
     return check_launch();
 }
 

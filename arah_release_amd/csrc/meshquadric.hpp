@@ -62,10 +62,13 @@ __device__ __forceinline__ int mq_face_clusters(const int* __restrict__ faces, l
     return n;
 }
 
-// the nine numbers of face f about m: A00 A01 A02 A11 A12 A22 b0 b1 b2.  The face is valid: its ids lie in [0, V)
+// the nine numbers of face f about m: A00 A01 A02 A11 A12 A22 b0 b1 b2; NC = 10 (meshcollapse.hpp): and c = d d, the constant of
+// the quadric, from the same d.  The face is valid: its ids lie in [0, V)
+template <int NC = 9>
 __device__ __forceinline__ void mq_term(const float* __restrict__ verts, const int* __restrict__ faces, long long f, const double m[3],
-                                        double q[9]) {
+                                        double q[NC]) {
 #pragma clang fp contract(off)
+    static_assert(NC == 9 || NC == 10, "nine numbers, or ten with the constant");
     double p[3][3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
@@ -92,46 +95,54 @@ __device__ __forceinline__ void mq_term(const float* __restrict__ verts, const i
     q[6] = nx * d;
     q[7] = ny * d;
     q[8] = nz * d;
+    if constexpr (NC == 10) q[9] = d * d;
 }
 
 // The tree over the n <= kMqShort terms of a segment by one lane: a binary counter of partial sums.  After i + 1 terms level l
 // holds the sum of an aligned block of 2^l terms exactly when bit l of i + 1 is set; a new term climbs while it meets one.
-__device__ __forceinline__ void mq_lane_sum(const float* __restrict__ verts, const int* __restrict__ faces, const unsigned* __restrict__ seg,
-                                            int n, const double m[3], double q[9]) {
+// term(i, x) fills the NC numbers of term i; it is called for i = 0 .. n - 1 in that order, once each.
+template <int NC, class Term>
+__device__ __forceinline__ void mq_lane_tree(int n, Term term, double q[NC]) {
 #pragma clang fp contract(off)
-    double st[kMqLevels][9];
+    double st[kMqLevels][NC];
 #pragma unroll
     for (int l = 0; l < kMqLevels; ++l)
 #pragma unroll
-        for (int c = 0; c < 9; ++c) st[l][c] = 0.0;
+        for (int c = 0; c < NC; ++c) st[l][c] = 0.0;
     // terminates: n - i strictly decreases to 0
     for (int i = 0; i < n; ++i) {
-        double x[9];
-        mq_term(verts, faces, (long long)seg[i], m, x);
+        double x[NC];
+        term(i, x);
         bool put = false;
 #pragma unroll
         for (int l = 0; l < kMqLevels; ++l) {   // i < kMqShort = 2^(kMqLevels - 1): a zero bit of i exists below kMqLevels
             if (put) continue;
             if ((i >> l) & 1) {
 #pragma unroll
-                for (int c = 0; c < 9; ++c) x[c] = st[l][c] + x[c];
+                for (int c = 0; c < NC; ++c) x[c] = st[l][c] + x[c];
             } else {
 #pragma unroll
-                for (int c = 0; c < 9; ++c) st[l][c] = x[c];
+                for (int c = 0; c < NC; ++c) st[l][c] = x[c];
                 put = true;
             }
         }
     }
     bool have = false;
 #pragma unroll
-    for (int c = 0; c < 9; ++c) q[c] = 0.0;
+    for (int c = 0; c < NC; ++c) q[c] = 0.0;
 #pragma unroll
     for (int l = 0; l < kMqLevels; ++l) {   // the blocks of n's binary digits, the shortest (the last) first
         if (!((n >> l) & 1)) continue;
 #pragma unroll
-        for (int c = 0; c < 9; ++c) q[c] = have ? st[l][c] + q[c] : st[l][c];
+        for (int c = 0; c < NC; ++c) q[c] = have ? st[l][c] + q[c] : st[l][c];
         have = true;
     }
+}
+
+// the tree over the faces seg[0 .. n) of a cluster about m
+__device__ __forceinline__ void mq_lane_sum(const float* __restrict__ verts, const int* __restrict__ faces, const unsigned* __restrict__ seg,
+                                            int n, const double m[3], double q[9]) {
+    mq_lane_tree<9>(n, [&](int i, double x[9]) { mq_term(verts, faces, (long long)seg[i], m, x); }, q);
 }
 
 // the tree over x[.][0 .. m) in LDS, m <= kImeshThreads, by the whole workgroup (from uniform control flow); the sum lands in
@@ -150,8 +161,9 @@ __device__ __forceinline__ void mq_group_tree(double (*x)[kImeshThreads], int m)
     __syncthreads();
 }
 
-// pos = float32(m + y), y the minimiser of the regularised quadric; false (and pos untouched) when the cluster falls back
-__device__ __forceinline__ bool mq_solve(const double q[9], const double m[3], double cell, double reg, float pos[3]) {
+// y = the minimiser of the regularised quadric about its own origin; false (and y untouched) when the solve falls back.  q holds
+// at least the nine numbers of mq_term
+__device__ __forceinline__ bool mq_solve_offset(const double* q, double cell, double reg, double y[3]) {
 #pragma clang fp contract(off)
     const double t = (q[0] + q[3]) + q[5];
     if (!isfinite(t) || !(t > 0.0)) return false;
@@ -165,13 +177,23 @@ __device__ __forceinline__ bool mq_solve(const double q[9], const double m[3], d
     const double C22 = M00 * M11 - M01 * M01;
     const double det = (M00 * C00 + M01 * C01) + M02 * C02;
     if (!isfinite(det) || !(det > 0.0)) return false;
-    double y[3];
-    y[0] = -((C00 * q[6] + C01 * q[7]) + C02 * q[8]) / det;
-    y[1] = -((C01 * q[6] + C11 * q[7]) + C12 * q[8]) / det;
-    y[2] = -((C02 * q[6] + C12 * q[7]) + C22 * q[8]) / det;
+    double z[3];
+    z[0] = -((C00 * q[6] + C01 * q[7]) + C02 * q[8]) / det;
+    z[1] = -((C01 * q[6] + C11 * q[7]) + C12 * q[8]) / det;
+    z[2] = -((C02 * q[6] + C12 * q[7]) + C22 * q[8]) / det;
 #pragma unroll
     for (int a = 0; a < 3; ++a)
-        if (!isfinite(y[a]) || fabs(y[a]) > cell) return false;
+        if (!isfinite(z[a]) || fabs(z[a]) > cell) return false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) y[a] = z[a];
+    return true;
+}
+
+// pos = float32(m + y), y the minimiser of the regularised quadric; false (and pos untouched) when the cluster falls back
+__device__ __forceinline__ bool mq_solve(const double q[9], const double m[3], double cell, double reg, float pos[3]) {
+#pragma clang fp contract(off)
+    double y[3];
+    if (!mq_solve_offset(q, cell, reg, y)) return false;
 #pragma unroll
     for (int a = 0; a < 3; ++a) pos[a] = (float)(m[a] + y[a]);
     return true;

@@ -7,7 +7,8 @@ tracker): PARITY UNPINNED, the definitions are this project's.  Also here: `load
 come in (.npz with `vertices` / `faces`, PLY with triangle faces), and `save_mesh`, which writes an indexed mesh in either;
 `mesh_components` / `clean_mesh`: the connected components of an indexed mesh and the removal of its floaters (DESIGN.md "Mesh
 components on the device"); `simplify_mesh`: fewer vertices and faces by vertex clustering on a grid (DESIGN.md "Simplifying meshes
-on the device"); `mesh_adjacency` / `mesh_topology` / `vertex_normals` / `smooth_mesh`: who is adjacent to whom, whether a mesh is
+on the device") and `decimate_mesh`: fewer by edge collapse, which keeps a closed surface closed (DESIGN.md "Edge-collapse
+decimation on the device"); `mesh_adjacency` / `mesh_topology` / `vertex_normals` / `smooth_mesh`: who is adjacent to whom, whether a mesh is
 watertight, the mesh's own normals, and Laplacian / Taubin smoothing (DESIGN.md "Adjacency, normals and smoothing on the device").
 Ground truth that is a SCAN -- a point cloud, with or without normals -- is scored through the exact
 nearest-point query hip.point_index / hip.point_nearest (DESIGN.md "Scoring against point clouds"): `PointCloud`, `nearest_points`,
@@ -491,8 +492,23 @@ SIMPLIFY_TARGET_MAX_RESOLUTION = 400     # the face-count search ends here: 401^
 def check_simplify(simplify):
     """Validate a `simplify` option of the model's mesh entries and return the keywords of `simplify_mesh` it stands for: a cell
     length (a number > 0), or a dict of cell / resolution / target_faces (exactly one of the three) / bounds / position /
-    quadric_reg / dedup / drop_unreferenced.  ValueError for anything else."""
+    quadric_reg / dedup / drop_unreferenced.  A dict with "method": "collapse" stands for `decimate_mesh` instead: target_faces /
+    ratio / max_error / quadric_reg / max_rounds, and comes back with its "method" (`apply_simplify` routes it); "method": "cluster"
+    is the dict without it.  ValueError for anything else."""
     import math
+    if isinstance(simplify, dict) and "method" in simplify:
+        kw = dict(simplify)
+        method = kw.pop("method")
+        if method == "collapse":
+            bad = set(kw) - set(_DECIMATE_KEYS)
+            if bad:
+                raise ValueError("simplify: unknown keys %s for method 'collapse' (known: %s)"
+                                 % (sorted(bad, key=str), ", ".join(_DECIMATE_KEYS)))
+            check_decimate(**kw)
+            return dict(kw, method="collapse")
+        if method != "cluster":
+            raise ValueError("simplify: method must be 'cluster' or 'collapse', got %r" % (method,))
+        return check_simplify(kw)
     if isinstance(simplify, dict):
         kw = dict(simplify)
         bad = set(kw) - set(_SIMPLIFY_KEYS)
@@ -697,8 +713,117 @@ def search_resolution(kept_faces, target, r_max=SIMPLIFY_TARGET_MAX_RESOLUTION):
     return lo, probes, True
 
 
+# ---- decimation by edge collapse ----------------------------------------------------------------------------------------------------
+_DECIMATE_KEYS = ("target_faces", "ratio", "max_error", "quadric_reg", "max_rounds")
+_DECIMATE_SUMS = ("pinned", "link", "long_edges", "nonfinite", "over_error", "flips", "fallbacks")
+
+
+def check_decimate(target_faces=None, ratio=None, max_error=None, quadric_reg=1e-3, max_rounds=200):
+    """Validate the scalars of `decimate_mesh`; ValueError for anything else.  At most one of target_faces (an integer >= 0) and
+    ratio (in [0, 1]) is given, and at least one of them and max_error (a number >= 0)."""
+    import math
+
+    def number(x):
+        return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool) and not math.isnan(float(x))
+    if target_faces is not None and ratio is not None:
+        raise ValueError("decimate_mesh: at most one of target_faces and ratio is given, got %r and %r" % (target_faces, ratio))
+    if target_faces is None and ratio is None and max_error is None:
+        raise ValueError("decimate_mesh: one of target_faces, ratio and max_error is needed")
+    if target_faces is not None and (isinstance(target_faces, bool) or not isinstance(target_faces, (int, np.integer))
+                                     or int(target_faces) < 0):
+        raise ValueError("decimate_mesh: target_faces must be an integer >= 0, got %r" % (target_faces,))
+    if ratio is not None and (not number(ratio) or not 0.0 <= float(ratio) <= 1.0):
+        raise ValueError("decimate_mesh: ratio must lie in [0, 1], got %r" % (ratio,))
+    if max_error is not None and (not number(max_error) or float(max_error) < 0.0):
+        raise ValueError("decimate_mesh: max_error must be a number >= 0, got %r" % (max_error,))
+    if not number(quadric_reg) or not math.isfinite(float(quadric_reg)) or float(quadric_reg) < 0.0:
+        raise ValueError("decimate_mesh: quadric_reg must be a finite number >= 0, got %r" % (quadric_reg,))
+    if isinstance(max_rounds, bool) or not isinstance(max_rounds, (int, np.integer)) or int(max_rounds) < 0:
+        raise ValueError("decimate_mesh: max_rounds must be an integer >= 0, got %r" % (max_rounds,))
+
+
+def decimate_mesh(verts, faces, target_faces=None, ratio=None, max_error=None, quadric_reg=1e-3, max_rounds=200, attributes=None):
+    """Decimate an indexed mesh (verts (V,3), faces (F,3) integer ids) by edge collapse: rounds of `mesh_collapse_round`
+    (arah_mesh_collapse_round on the GPU, meshing.mesh_collapse_round on the host, equal bit for bit).  Unlike `simplify_mesh` the
+    surface stays a surface: an edge collapses only between two vertices interior to a consistently oriented manifold
+    neighbourhood, under the link condition, and when no face around it turns over -- a closed embedded mesh stays manifold and
+    watertight with its Euler characteristic and its components, and faces go where the surface is flat.
+
+        target_faces  the face count to reach; or
+        ratio         the share of the input's faces to reach: target = floor(ratio F)
+        max_error     the largest cost of an edge that may collapse: the quadric's value at the new vertex, the sum over the
+                      faces around the edge of (2 area x distance of the vertex to the face's plane)^2 -- a length to the SIXTH
+                      power, not a distance; alone it decimates as far as that bound allows
+        quadric_reg   the regulariser of the position solve, as in simplify_mesh(position="quadric")
+        max_rounds    the most rounds
+
+    A round collapses at most need = ceil((F - target) / 2) independent edges, two faces each, so the count ends at the target, or
+    one below it when F - target is odd; the last round takes the first `need` selected edges in ascending id, not the cheapest.
+    The loop ends when F <= target, when a round selects no edge (every remaining one is pinned, fails the link or flip test,
+    is surrounded by more than 32 faces or costs more than max_error), or after max_rounds.  Boundary vertices and vertices on
+    non-manifold or misoriented edges never move and never merge.  ONE host synchronisation per round (its counts).
+
+    -> dict of verts (V',3) float32, faces (F',3) in the dtype of `faces`, n_verts, n_tris, vert_src (V',) int64 (the input
+    vertex nearest to every output vertex among those it absorbed in its last collapse), face_src (F',) int64 (every output face
+    is that input face, renamed), every tensor of the dict `attributes` (first dimension V) gathered by vert_src -- never averaged
+    -- and report = dict of target, rounds, reached, faces (the count before every round and at the end) and the rounds' summed
+    counts pinned, link, long_edges, nonfinite, over_error, flips (edges that were no candidates, by their first reason) and
+    fallbacks (position solves that fell back to the midpoint)."""
+    import math
+    check_decimate(target_faces, ratio, max_error, quadric_reg, max_rounds)
+    n_verts, faces = _mesh_args(verts, faces, "decimate_mesh")
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or not verts.dtype.is_floating_point:
+        raise ValueError("decimate_mesh: verts must be a floating-point (V, 3) tensor")
+    if verts.device != faces.device:
+        raise ValueError("decimate_mesh: verts live on %s, faces on %s" % (verts.device, faces.device))
+    attributes = dict(attributes or {})
+    reserved = ("verts", "faces", "n_verts", "n_tris", "vert_src", "face_src", "report")
+    for name, t in attributes.items():
+        if name in reserved:
+            raise ValueError("decimate_mesh: an attribute cannot be called %r" % (name,))
+        if not isinstance(t, torch.Tensor) or t.dim() < 1 or t.shape[0] != n_verts or t.device != verts.device:
+            raise ValueError("decimate_mesh: attribute %r must be a tensor with %d rows on %s" % (name, n_verts, verts.device))
+    backend, dev = _cc_backend(faces), verts.device
+    from . import meshing
+    names = meshing.COLLAPSE_COUNTS
+    n_faces = int(faces.shape[0])
+    target = int(target_faces) if target_faces is not None else int(math.floor(float(ratio) * n_faces)) if ratio is not None else 0
+    max_cost = float("inf") if max_error is None else float(max_error)
+    with torch.no_grad():
+        v, f = verts.detach().to(torch.float32).contiguous(), faces
+        vert_src, face_src = torch.arange(n_verts, device=dev), torch.arange(n_faces, device=dev)
+        history, sums, rounds = [n_faces], dict.fromkeys(_DECIMATE_SUMS, 0), 0
+        while rounds < int(max_rounds) and history[-1] > target:
+            need = (history[-1] - target + 1) // 2
+            out = backend.mesh_collapse_round(v, f, need, float(quadric_reg), max_cost)
+            c = dict(zip(names, out[4].tolist()))                                 # the host synchronisation
+            rounds += 1
+            for k in _DECIMATE_SUMS:
+                sums[k] += c[k]
+            if c["applied"] == 0:
+                break
+            nv, nf = c["n_verts"], c["n_faces"]
+            v, f = out[0][:nv], out[1][:nf]
+            vert_src, face_src = vert_src[out[2][:nv].long()], face_src[out[3][:nf].long()]
+            history.append(nf)
+        res = {"verts": v, "faces": f.to(faces.dtype), "n_verts": int(v.shape[0]), "n_tris": int(f.shape[0]), "vert_src": vert_src,
+               "face_src": face_src,
+               "report": dict(sums, target=target, rounds=rounds, reached=history[-1] <= target, faces=history)}
+        for name, t in attributes.items():
+            res[name] = t.index_select(0, vert_src)
+    return res
+
+
+def apply_simplify(verts, faces, simplify):
+    """The mesh entries' `simplify` option, as `check_simplify` returned it: `decimate_mesh` for method="collapse",
+    `simplify_mesh` otherwise."""
+    if simplify.get("method") == "collapse":
+        return decimate_mesh(verts, faces, **{k: x for k, x in simplify.items() if k != "method"})
+    return simplify_mesh(verts, faces, **simplify)
+
+
 # ---- adjacency, topology, per-vertex normals, smoothing -------------------------------------------------------------------------
-MeshAdjacency = collections.namedtuple("MeshAdjacency", ("vf_start", "vf", "nbr_start", "nbr", "nbr_out", "nbr_in", "vert_flags",
+MeshAdjacency =collections.namedtuple("MeshAdjacency", ("vf_start", "vf", "nbr_start", "nbr", "nbr_out", "nbr_in", "vert_flags",
                                                          "counts"))
 MeshAdjacency.__doc__ = """The arrays of `mesh_adjacency`, on the mesh's device: vf_start (V+1,) / vf (3F,) the CSR of the valid
 faces incident to every vertex (ids ascending); nbr_start (V+1,) / nbr (6F,) the CSR of its unique neighbours (ids ascending) with

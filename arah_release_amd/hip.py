@@ -143,6 +143,7 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_mesh_components_scratch_bytes", "arah_mesh_components", "arah_mesh_select_scratch_bytes", "arah_mesh_select",
            "arah_mesh_simplify_scratch_bytes", "arah_mesh_simplify",
            "arah_mesh_quadric_place_scratch_bytes", "arah_mesh_quadric_place",
+           "arah_mesh_collapse_round_scratch_bytes", "arah_mesh_collapse_round",
            "arah_mesh_adjacency_scratch_bytes", "arah_mesh_adjacency", "arah_mesh_vertex_normals", "arah_mesh_smooth",
            "arah_mesh_orient_scratch_bytes", "arah_mesh_orient", "arah_mesh_boundary_loops_scratch_bytes",
            "arah_mesh_boundary_loops", "arah_mesh_fill_holes_scratch_bytes", "arah_mesh_fill_holes",
@@ -197,7 +198,7 @@ def load_library():
         getattr(lib, name).restype = C.c_size_t
         getattr(lib, name).argtypes = [C.c_int32]
     for name in ("arah_mesh_components_scratch_bytes", "arah_mesh_select_scratch_bytes", "arah_mesh_adjacency_scratch_bytes",
-                 "arah_mesh_quadric_place_scratch_bytes",
+                 "arah_mesh_quadric_place_scratch_bytes", "arah_mesh_collapse_round_scratch_bytes",
                  "arah_mesh_orient_scratch_bytes", "arah_mesh_boundary_loops_scratch_bytes", "arah_mesh_fill_holes_scratch_bytes"):
         getattr(lib, name).restype = C.c_size_t
         getattr(lib, name).argtypes = [C.c_int64, C.c_int64]
@@ -1049,6 +1050,44 @@ def _mesh_adj_args(verts, faces, adjacency, what):
                              % (what, f.device))
         adjacency = tuple(t.contiguous() for t in adjacency)
     return verts.detach().contiguous(), f, V, F, adjacency
+
+
+def mesh_collapse_round(verts, faces, need, reg=1e-3, max_cost=float("inf"), details=False):
+    """One round of edge-collapse decimation (arah_mesh_collapse_round, csrc/meshcollapse.hpp): verts (V,3) float32 and faces (F,3)
+    integer ids on the GPU; need, reg and max_cost on the host, as meshing.mesh_collapse_round describes them.  The adjacency of
+    the mesh is built inside the call.  -> verts_out (V,3) float32, faces_out (F,3) int32, vert_src (V,) int32, face_src (F,) int32,
+    counts (12,) int32 (meshing.COLLAPSE_COUNTS); rows past the counts are zero; details: also edge_pos (6F,3) float32, edge_key
+    (6F,) int64 and edge_reason (6F,) uint8 of every neighbour entry.  All on the device, no host synchronisation; the result is
+    meshing.mesh_collapse_round(...) bit for bit."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    what = "mesh_collapse_round"
+    need, reg, max_cost = meshing.collapse_args(need, reg, max_cost, what)
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise ValueError("%s: verts must be a (V, 3) float32 tensor" % what)
+    V = int(verts.shape[0])
+    f, _, F = _mesh_cc_args(faces, V, what)
+    if verts.device != f.device:
+        raise ValueError("%s: verts live on %s, faces on %s" % (what, verts.device, f.device))
+    if F > meshing.ADJACENCY_MAX_FACES:
+        raise ValueError("%s: at most 2^28 faces, got %d" % (what, F))
+    v, dev, i32 = verts.detach().contiguous(), f.device, torch.int32
+    with _on_device(dev):
+        scratch = _mesh_cc_buf(dev, int(lib.arah_mesh_collapse_round_scratch_bytes(V, F)))
+        verts_out = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        faces_out = torch.empty(F, 3, dtype=i32, device=dev)
+        vert_src, face_src = torch.empty(V, dtype=i32, device=dev), torch.empty(F, dtype=i32, device=dev)
+        counts = torch.empty(len(meshing.COLLAPSE_COUNTS), dtype=i32, device=dev)
+        edge_pos = torch.empty(6 * F, 3, dtype=torch.float32, device=dev)
+        edge_key = torch.empty(6 * F, dtype=torch.int64, device=dev)
+        edge_reason = torch.empty(6 * F, dtype=torch.uint8, device=dev)
+        _check(lib.arah_mesh_collapse_round(_ptr(v), C.c_int64(V), _ptr(f), C.c_int64(F), C.c_int32(need), C.c_double(reg),
+                                            C.c_float(max_cost), _ptr(verts_out), _ptr(faces_out), _ptr(vert_src), _ptr(face_src),
+                                            _ptr(counts), _ptr(edge_pos), _ptr(edge_key), _ptr(edge_reason), _ptr(scratch),
+                                            C.c_size_t(scratch.numel()), _stream()), "arah_mesh_collapse_round")
+    out = (verts_out, faces_out, vert_src, face_src, counts)
+    return out + (edge_pos, edge_key, edge_reason) if details else out
 
 
 def vertex_normals(verts, faces, adjacency=None):

@@ -426,6 +426,41 @@ def quadric_tree_sum(x, start, n):
     return out
 
 
+def quadric_terms(verts, corners, about, with_c=False):
+    """The terms of `mesh_quadric_place`: corners (P,3) vertex ids of P faces, about (P,3) float64 the point each is taken about.
+    -> (P,9) float64 A00 A01 A02 A11 A12 A22 b0 b1 b2; with_c: a tenth column d d, the constant of the quadric."""
+    f64 = torch.float64
+    pa, pb, pc = (verts[corners[:, j]].to(f64) - about for j in range(3))
+    e1, e2 = pb - pa, pc - pa
+    nx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
+    ny = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
+    nz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+    d = -((nx * pa[:, 0] + ny * pa[:, 1]) + nz * pa[:, 2])
+    cols = [nx * nx, nx * ny, nx * nz, ny * ny, ny * nz, nz * nz, nx * d, ny * d, nz * d]
+    return torch.stack(cols + ([d * d] if with_c else []), 1)
+
+
+def quadric_solve(q, reg, bound):
+    """The solve of `mesh_quadric_place` over the rows of q (K, >= 9) float64: -> (y (K,3) float64 the offsets, good (K,) bool:
+    t and det finite and > 0 and every |y_a| finite and <= bound (a number or a (K,) float64 tensor))."""
+    A00, A01, A02, A11, A12, A22, b0, b1, b2 = (q[:, j] for j in range(9))
+    t = (A00 + A11) + A22
+    lam = reg * t
+    M00, M11, M22, M01, M02, M12 = A00 + lam, A11 + lam, A22 + lam, A01, A02, A12
+    C00 = M11 * M22 - M12 * M12
+    C01 = M02 * M12 - M01 * M22
+    C02 = M01 * M12 - M02 * M11
+    C11 = M00 * M22 - M02 * M02
+    C12 = M01 * M02 - M00 * M12
+    C22 = M00 * M11 - M01 * M01
+    det = (M00 * C00 + M01 * C01) + M02 * C02
+    y = torch.stack([-((C00 * b0 + C01 * b1) + C02 * b2) / det, -((C01 * b0 + C11 * b1) + C12 * b2) / det,
+                     -((C02 * b0 + C12 * b1) + C22 * b2) / det], 1)
+    bound = bound[:, None] if isinstance(bound, torch.Tensor) else bound
+    good = torch.isfinite(t) & (t > 0) & torch.isfinite(det) & (det > 0) & (torch.isfinite(y) & (y.abs() <= bound)).all(1)
+    return y, good
+
+
 def mesh_quadric_place(verts, faces, vert_map, means, n_clusters, cell, reg=1e-3):
     """Quadric-error placement of the clusters of `mesh_simplify`: verts (V,3) float32, faces (F,3) integer ids, vert_map (V,)
     integer (the cluster of every vertex or -1), means (V,3) float32 (verts_out at position="mean"), n_clusters = K (an integer,
@@ -484,32 +519,11 @@ def mesh_quadric_place(verts, faces, vert_map, means, n_clusters, cell, reg=1e-3
     placed = n <= QUADRIC_MAX_SEGMENT
     m = means[:K].to(f64)
     # the terms
-    mk = m[pk]
-    pa, pb, pc = (verts[faces[pf, j]].to(f64) - mk for j in range(3))
-    e1, e2 = pb - pa, pc - pa
-    nx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
-    ny = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
-    nz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
-    d = -((nx * pa[:, 0] + ny * pa[:, 1]) + nz * pa[:, 2])
-    terms = torch.stack([nx * nx, nx * ny, nx * nz, ny * ny, ny * nz, nz * nz, nx * d, ny * d, nz * d], 1)
+    terms = quadric_terms(verts, faces[pf], m[pk])
     keep = placed[pk]                                                           # a skipped segment is not summed
     n_sum = torch.where(placed, n, torch.zeros_like(n))
     q = quadric_tree_sum(terms[keep], torch.cumsum(n_sum, 0) - n_sum, n_sum)
-    A00, A01, A02, A11, A12, A22, b0, b1, b2 = (q[:, j] for j in range(9))
-    # the solve
-    t = (A00 + A11) + A22
-    lam = reg * t
-    M00, M11, M22, M01, M02, M12 = A00 + lam, A11 + lam, A22 + lam, A01, A02, A12
-    C00 = M11 * M22 - M12 * M12
-    C01 = M02 * M12 - M01 * M22
-    C02 = M01 * M12 - M02 * M11
-    C11 = M00 * M22 - M02 * M02
-    C12 = M01 * M02 - M00 * M12
-    C22 = M00 * M11 - M01 * M01
-    det = (M00 * C00 + M01 * C01) + M02 * C02
-    y = torch.stack([-((C00 * b0 + C01 * b1) + C02 * b2) / det, -((C01 * b0 + C11 * b1) + C12 * b2) / det,
-                     -((C02 * b0 + C12 * b1) + C22 * b2) / det], 1)
-    good = torch.isfinite(t) & (t > 0) & torch.isfinite(det) & (det > 0) & (torch.isfinite(y) & (y.abs() <= c)).all(1)
+    y, good = quadric_solve(q, reg, c)
     moved = (m + y).float()
     pos_k = torch.where((good & placed)[:, None], moved, means[:K])
     fallbacks = int((placed & ~good).sum())
@@ -740,8 +754,219 @@ def mesh_smooth(verts, faces, iterations, lamb=0.5, mu=-0.53, method="taubin", b
     return cur
 
 
+# ---- edge-collapse decimation: one round ---------------------------------------------------------------------------------------------
+COLLAPSE_MAX_UNION = 32                 # faces around an edge that is still a candidate: kMqShort, one lane's tree
+COLLAPSE_COUNTS = ("n_verts", "n_faces", "selected", "applied", "candidates", "pinned", "link", "long_edges", "nonfinite", "over_error",
+                   "flips", "fallbacks")
+COLLAPSE_REASONS = ("candidate", "pinned", "link", "long_edges", "nonfinite", "over_error", "flips")   # counts[4 + reason]
+COLLAPSE_NO_EDGE = 255                  # edge_reason of a neighbour entry that names no edge (nbr <= owner, or past the entries)
+_COLLAPSE_EMPTY = 2 ** 63 - 1
+
+
+def collapse_args(need, reg, max_cost, what="mesh_collapse_round"):
+    """The scalars of `mesh_collapse_round`, checked: -> (need, reg as a float, max_cost as a float32 value)."""
+    try:
+        if isinstance(need, bool) or int(need) != need:
+            raise TypeError
+        need, reg, max_cost = int(need), float(reg), float(np.float32(float(max_cost)))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("%s: need must be an integer, reg and max_cost numbers" % what)
+    if not 0 <= need <= 2 ** 31 - 1:
+        raise ValueError("%s: need must lie in [0, 2^31), got %r" % (what, need))
+    if not math.isfinite(reg) or reg < 0.0:
+        raise ValueError("%s: reg must be a finite number >= 0, got %r" % (what, reg))
+    if math.isnan(max_cost) or max_cost < 0.0:
+        raise ValueError("%s: max_cost must be a number >= 0 (inf: no bound), got %r" % (what, max_cost))
+    return need, reg, max_cost
+
+
+def _ragged(first, n):
+    """Rows first[k] .. first[k] + n[k] of a flat array for every k: -> (k of every row, the rows), k ascending, rows ascending."""
+    k = torch.repeat_interleave(torch.arange(n.shape[0], device=n.device), n)
+    return k, first[k] + (torch.arange(k.shape[0], device=n.device) - (torch.cumsum(n, 0) - n)[k])
+
+
+def _cross3(p):
+    """(p1 - p0) x (p2 - p0) of corners p (P,3,3) float64, every component (x y) - (z w) as in `quadric_terms`."""
+    e1, e2 = p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]
+    return torch.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
+                        e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], 1)
+
+
+def _d2_f32(p, q):
+    d = p.to(torch.float64) - q.to(torch.float64)
+    return ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]).float()
+
+
+def mesh_collapse_round(verts, faces, need, reg=1e-3, max_cost=float("inf"), adjacency=None, details=False):
+    """One round of edge-collapse decimation: verts (V,3) float32, faces (F,3) integer ids, need >= 0 the most edges to collapse,
+    reg the regulariser of `mesh_quadric_place`'s solve, max_cost a float32 bound on an edge's cost, adjacency `mesh_adjacency`
+    of the mesh or None.  Many independent edges collapse at once; which ones is decided on integers and on the bits of rounded
+    numbers, so the order in which a device's threads arrive does not show.  All floating point is float64 from the float32
+    inputs, every operation rounded on its own; no square root.
+
+    PINNED: a vertex with a non-finite coordinate, or without a neighbour, or with a neighbour entry that is not "one face each
+    way" (nbr_out = nbr_in = 1).  The others are free.
+
+    EDGES: the neighbour entry i = (u, v) with v > u names the edge {u, v}; i is its id.  The first test that fails is the edge's
+    reason (COLLAPSE_REASONS) and is counted:
+      1 pinned      u or v is pinned.
+      2 link        the edge's two faces (the faces of vf[u] that name v, ascending) have the third vertices a and b; a = b, or
+                    nbr[u] and nbr[v] have other than two ids in common (a and b always are), or a or b has fewer than four
+                    neighbours.
+      3 long_edges  n = |vf[u]| + |vf[v]| - 2, the faces that touch u or v each once, is above COLLAPSE_MAX_UNION = 32.
+      4 nonfinite   m = (double(u) + double(v)) 0.5.  The ten numbers of every such face about m (`quadric_terms` and c = d d),
+                    in ascending face id, are summed by `quadric_tree_sum`.  `quadric_solve` with reg and the bound max_a |u_a -
+                    v_a| gives the offset y; a solve that is not good is counted (fallbacks) and y = 0.  pos = float32(m + y),
+                    the midpoint's own float32 bits after a fall-back.  Ay_r = (A_r0 y0 + A_r1 y1) + A_r2 y2 for the rows r of the
+                    symmetric A; raw = (((y0 Ay_0 + y1 Ay_1) + y2 Ay_2) + 2 ((b0 y0 + b1 y1) + b2 y2)) + c; cost32 = float32(raw),
+                    +0 unless raw > 0.  The reason holds when float32(raw) is not finite.
+      5 over_error  cost32 > max_cost.
+      6 flips       for a face of the n that does not name both u and v: N = (p1 - p0) x (p2 - p0) of its corners, N' the same
+                    with the corner that is u or v at double(pos); the reason holds unless (N0 N'0 + N1 N'1) + N2 N'2 > 0 for
+                    every such face.
+    An edge without a reason is a CANDIDATE with key = (bits(cost32) << 32) | i.
+
+    SELECTION: m1[x] = the least key of the candidates at x; m2[x] = the least of m1 over x and its neighbours; a candidate is
+    selected when m2[u] = m2[v] = its key.  Keys are unique, so a selected edge is the least at every vertex of N[u] and N[v]:
+    no end of another selected edge is u, v or a neighbour of either, and the faces two selected edges touch are disjoint.  Of the
+    selected edges the first `need` in ascending id are APPLIED.
+
+    APPLY: v becomes u, u moves to pos; vert_src of u is v when float32(|double(v) - double(pos)|^2) is below u's, else u.  A
+    valid face that names both ends of an applied edge goes; every other face stays in its order, its ids in [0, V) renamed (the
+    others as they are; an id that does not fit int32 is -1).  The merged vertices go, the others keep their order.
+
+    -> verts_out (V,3) float32, faces_out (F,3) int32, vert_src (V,) int32, face_src (F,) int32 (ids of THIS round's input),
+    counts (12,) int32 in the order of COLLAPSE_COUNTS; rows past the counts are zero.  details: also edge_pos (6F,3) float32,
+    edge_key (6F,) int64 (-1: no candidate) and edge_reason (6F,) uint8 (COLLAPSE_NO_EDGE where the entry names no edge, pos
+    zero before reason 4), and selected (6F,) bool.  Plain tensor operations on the tensors' device: the specification of
+    arah_mesh_collapse_round (csrc/meshcollapse.hpp), and what runs for meshes on the host."""
+    what = "mesh_collapse_round"
+    need, reg, max_cost = collapse_args(need, reg, max_cost, what)
+    raw_faces = torch.as_tensor(faces)
+    verts, faces, V, in_range = _mesh_verts(verts, faces, what)
+    if raw_faces.dtype != torch.int32:
+        faces = torch.where((faces >= 0) & (faces <= 2 ** 31 - 1), faces, torch.full_like(faces, -1))
+    F, dev = int(faces.shape[0]), verts.device
+    f64, i32, i64 = torch.float64, torch.int32, torch.int64
+    adjacency = _adjacency_of(faces, V, adjacency, what)
+    vf_start, vf, nbr_start, nbr, nbr_out, nbr_in = (t.long() for t in adjacency[:6])
+    E = int(nbr_start[V])
+    val, nvf = nbr_start[1:] - nbr_start[:-1], vf_start[1:] - vf_start[:-1]
+    ids_v = torch.arange(V, device=dev)
+    ev, en = torch.repeat_interleave(ids_v, val), nbr[:E]
+    pinned = ~torch.isfinite(verts).all(1) | (val == 0)
+    pinned[ev[(nbr_out[:E] != 1) | (nbr_in[:E] != 1)]] = True
+    eid = torch.nonzero(en > ev)[:, 0]
+    u, v = ev[eid], en[eid]
+    n_edges = int(eid.shape[0])
+    reason = torch.zeros(n_edges, dtype=i64, device=dev)
+    pos = torch.zeros(n_edges, 3, dtype=torch.float32, device=dev)
+    cost_bits = torch.zeros(n_edges, dtype=i64, device=dev)
+    fallbacks = 0
+    reason[pinned[u] | pinned[v]] = 1
+    # 2: the link condition
+    at = torch.nonzero(reason == 0)[:, 0]
+    if at.numel():
+        ub, vb = u[at], v[at]
+        k, rows = _ragged(vf_start[ub], nvf[ub])
+        fcs = vf[rows]
+        shared = (faces[fcs] == vb[k][:, None]).any(1)
+        third = faces[fcs[shared]].sum(1) - ub[k[shared]] - vb[k[shared]]          # two per edge: nbr_out = nbr_in = 1
+        a, b = third[0::2], third[1::2]
+        k, rows = _ragged(nbr_start[ub], val[ub])
+        ekey = ev * max(V, 1) + en                                                  # ascending: the entries' own order
+        want = vb[k] * max(V, 1) + nbr[rows]
+        found = ekey[torch.searchsorted(ekey, want).clamp(max=E - 1)] == want
+        common = torch.zeros(at.shape[0], dtype=i64, device=dev).index_add_(0, k, found.long())
+        reason[at[(a == b) | (common != 2) | (val[a] < 4) | (val[b] < 4)]] = 2
+    # 3: the faces around the edge
+    n_union = nvf[u] + nvf[v] - 2
+    reason[(reason == 0) & (n_union > COLLAPSE_MAX_UNION)] = 3
+    # 4 .. 6: position, cost, flips
+    at = torch.nonzero(reason == 0)[:, 0]
+    if at.numel():
+        ub, vb, K = u[at], v[at], int(at.shape[0])
+        ku, ru = _ragged(vf_start[ub], nvf[ub])
+        kv, rv = _ragged(vf_start[vb], nvf[vb])
+        pair = torch.unique(torch.cat([ku * max(F, 1) + vf[ru], kv * max(F, 1) + vf[rv]]), sorted=True)
+        pk, pf = pair // max(F, 1), pair % max(F, 1)
+        n = torch.bincount(pk, minlength=K)
+        pu, pv = verts[ub].to(f64), verts[vb].to(f64)
+        m = (pu + pv) * 0.5
+        q = quadric_tree_sum(quadric_terms(verts, faces[pf], m[pk], with_c=True), torch.cumsum(n, 0) - n, n)
+        y, good = quadric_solve(q, reg, (pu - pv).abs().amax(1))
+        fallbacks = int((~good).sum())
+        y = torch.where(good[:, None], y, torch.zeros_like(y))
+        p_new = torch.where(good[:, None], (m + y).float(), m.float())
+        A00, A01, A02, A11, A12, A22, b0, b1, b2, c = (q[:, j] for j in range(10))
+        y0, y1, y2 = y[:, 0], y[:, 1], y[:, 2]
+        Ay0 = (A00 * y0 + A01 * y1) + A02 * y2
+        Ay1 = (A01 * y0 + A11 * y1) + A12 * y2
+        Ay2 = (A02 * y0 + A12 * y1) + A22 * y2
+        raw = (((y0 * Ay0 + y1 * Ay1) + y2 * Ay2) + 2.0 * ((b0 * y0 + b1 * y1) + b2 * y2)) + c
+        finite = torch.isfinite(raw.float())
+        cost32 = torch.where(raw > 0, raw.float(), torch.zeros_like(raw, dtype=torch.float32))
+        ids = faces[pf]
+        moves = (ids == ub[pk][:, None]) | (ids == vb[pk][:, None])
+        before = verts[ids].to(f64)
+        after = torch.where(moves[:, :, None], p_new[pk].to(f64)[:, None, :], before)
+        N, N2 = _cross3(before), _cross3(after)
+        dot = (N[:, 0] * N2[:, 0] + N[:, 1] * N2[:, 1]) + N[:, 2] * N2[:, 2]
+        flipped = torch.zeros(K, dtype=torch.bool, device=dev)
+        flipped[pk[(moves.sum(1) == 1) & ~(dot > 0)]] = True
+        over = cost32 > max_cost
+        reason[at] = torch.where(~finite, 4, torch.where(over, 5, torch.where(flipped, 6, 0))).to(i64)
+        pos[at] = p_new
+        cost_bits[at] = cost32.view(i32).long()
+    cand = reason == 0
+    key = torch.where(cand, (cost_bits << 32) | eid, torch.full_like(eid, _COLLAPSE_EMPTY))
+    # selection
+    m1 = torch.full((V,), _COLLAPSE_EMPTY, dtype=i64, device=dev)
+    m1 = m1.scatter_reduce(0, torch.cat([u, v]), torch.cat([key, key]), "amin")
+    m2 = m1.scatter_reduce(0, ev, m1[en], "amin")
+    selected = cand & (m2[u] == key) & (m2[v] == key)
+    n_selected = int(selected.sum())
+    applied = torch.nonzero(selected)[:need, 0]
+    # apply
+    ua, va, pa = u[applied], v[applied], pos[applied]
+    merge_to = ids_v.clone()
+    merge_to[va] = ua
+    moved = verts.clone()
+    moved[ua] = pa
+    src = ids_v.clone()
+    src[ua] = torch.where(_d2_f32(verts[va], pa) < _d2_f32(verts[ua], pa), va, ua)
+    keep = merge_to == ids_v
+    new_id = torch.cumsum(keep.long(), 0) - 1
+    nv = int(keep.sum())
+    verts_out = torch.zeros(V, 3, dtype=torch.float32, device=dev)
+    vert_src = torch.zeros(V, dtype=i64, device=dev)
+    verts_out[:nv], vert_src[:nv] = moved[keep], src[keep]
+    named = (faces >= 0) & (faces < V)
+    renamed = torch.where(named, new_id[merge_to[faces.clamp(0, max(V - 1, 0))]] if V else faces, faces)
+    valid = in_range & (faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 0] != faces[:, 2])
+    gone = valid & ((renamed[:, 0] == renamed[:, 1]) | (renamed[:, 1] == renamed[:, 2]) | (renamed[:, 0] == renamed[:, 2]))
+    rows = torch.nonzero(~gone)[:, 0]
+    nf = int(rows.shape[0])
+    faces_out = torch.zeros(F, 3, dtype=i64, device=dev)
+    face_src = torch.zeros(F, dtype=i64, device=dev)
+    faces_out[:nf], face_src[:nf] = renamed[rows], rows
+    counts = torch.tensor([nv, nf, n_selected, int(applied.shape[0])] + [int((reason == r).sum()) for r in range(7)]
+                          + [fallbacks], dtype=i32, device=dev)
+    out = (verts_out, faces_out.to(i32), vert_src.to(i32), face_src.to(i32), counts)
+    if not details:
+        return out
+    edge_pos = torch.zeros(6 * F, 3, dtype=torch.float32, device=dev)
+    edge_key = torch.full((6 * F,), -1, dtype=i64, device=dev)
+    edge_reason = torch.full((6 * F,), COLLAPSE_NO_EDGE, dtype=torch.uint8, device=dev)
+    edge_sel = torch.zeros(6 * F, dtype=torch.bool, device=dev)
+    edge_pos[eid], edge_reason[eid], edge_sel[eid] = pos, reason.to(torch.uint8), selected
+    edge_key[eid] = torch.where(cand, key, torch.full_like(key, -1))
+    return out + (edge_pos, edge_key, edge_reason, edge_sel)
+
+
 # ---- orientation, boundary loops, hole filling -----------------------------------------------------------------------------------
-ORIENT_POLICIES = {"seed": 0, "majority": 1, "negative": 2, "positive": 3}
+ORIENT_POLICIES ={"seed": 0, "majority": 1, "negative": 2, "positive": 3}
 ORIENT_VOL_BITS = 18                    # quantised coordinates lie in [-2^18, 2^18]: a determinant of three stays below 2^57
 FILL_MAX_EDGES = 1 << 26                # edges of a filled loop: 2^26 fixed-point coordinates below 2^36 sum below 2^62
 

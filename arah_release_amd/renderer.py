@@ -919,6 +919,8 @@ class MetaAvatarRender(nn.Module):
         floaters dropped on the device, and vert_src and removed come with it.  simplify (indexed=True only; None: nothing
         changes): a cell length in metres or a dict of geometry.simplify_mesh keywords -- the mesh is geometry.simplify_mesh of
         the unsimplified call's (after clean), clustered on the device; vert_src, removed, cell and dims are then simplify_mesh's.
+        A dict with "method": "collapse" (target_faces or ratio, max_error, quadric_reg, max_rounds) decimates by edge collapse
+        instead, geometry.decimate_mesh: a closed surface stays closed; vert_src, face_src and report are then decimate_mesh's.
         smooth (indexed=True only; None: nothing changes): a number of Taubin iterations or a dict of geometry.smooth_mesh
         keywords -- verts are geometry.smooth_mesh of the unsmoothed call's, AFTER clean and simplify; faces, counts and ids stay.
         Eval only."""
@@ -962,7 +964,7 @@ class MetaAvatarRender(nn.Module):
                 if clean is not None:
                     res.update(geometry.clean_mesh(res["verts"], res["faces"], keep=clean))
                 if simplify is not None:
-                    res.update(geometry.simplify_mesh(res["verts"], res["faces"], **simplify))
+                    res.update(geometry.apply_simplify(res["verts"], res["faces"], simplify))
                 if smooth is not None:
                     res["verts"] = geometry.smooth_mesh(res["verts"], res["faces"], **smooth)
                 return res
@@ -1012,7 +1014,8 @@ class MetaAvatarRender(nn.Module):
         simplify (None: nothing changes): a cell length in the normalised coordinates or a dict of geometry.simplify_mesh
         keywords; applied after clean and BEFORE the attributes are evaluated: the networks run on the small mesh, at its new
         positions, and vert_src, removed, cell and dims are simplify_mesh's (ids into the cleaned mesh).  V is then the simplified
-        mesh's.
+        mesh's.  A dict with "method": "collapse" goes to geometry.decimate_mesh instead (edge collapse: a closed surface stays
+        closed), with its vert_src, face_src and report.
 
         smooth (None: nothing changes): a number of Taubin iterations or a dict of geometry.smooth_mesh keywords; applied after
         clean and simplify and BEFORE the attributes are evaluated, which are then taken at the smoothed positions.  With smooth
@@ -1038,7 +1041,7 @@ class MetaAvatarRender(nn.Module):
                 res = geometry.clean_mesh(verts, faces, keep=clean)
                 verts, faces, V = res["verts"].contiguous(), res["faces"], res["n_verts"]
             if simplify is not None:
-                res.update(geometry.simplify_mesh(verts, faces, **simplify))
+                res.update(geometry.apply_simplify(verts, faces, simplify))
                 verts, faces, V = res["verts"].contiguous(), res["faces"], res["n_verts"]
             adjacency = None
             if smooth is not None:

@@ -35,6 +35,7 @@
  *   arah_mesh_select        by shared vertex ids, and the order-preserving selection of some of them: floater removal)
  *   arah_mesh_simplify      (none: vertex clustering of an indexed mesh on a grid: decimation and welding by position)
  *   arah_mesh_quadric_place (none: the clusters of arah_mesh_simplify moved to the minimisers of their faces' plane quadrics)
+ *   arah_mesh_collapse_round (none: one round of edge-collapse decimation that keeps the surface a surface)
  *   arah_mesh_adjacency /   (none: the reference's users smooth and re-normal with trimesh / open3d / pytorch3d; the incident faces
  *   arah_mesh_vertex_normals /  and unique neighbours of every vertex with edge statistics, pytorch3d's verts_normals_packed over
  *   arah_mesh_smooth        them, and Laplacian / Taubin umbrella smoothing)
@@ -416,6 +417,35 @@ size_t arah_mesh_adjacency_scratch_bytes(int64_t n_verts, int64_t n_faces);
 int arah_mesh_adjacency(const int32_t* faces, int64_t n_faces, int64_t n_verts, int32_t* vf_start, int32_t* vf, int32_t* nbr_start,
                         int32_t* nbr, int32_t* nbr_out, int32_t* nbr_in, uint8_t* vert_flags, int32_t* counts, void* scratch,
                         size_t scratch_bytes, void* stream);
+/* One round of edge-collapse decimation of an indexed mesh (csrc/meshcollapse.hpp).  verts [n_verts][3], faces [n_faces][3]
+ * vertex ids; the adjacency of the mesh is built inside the call (arah_mesh_adjacency's launches, in this call's scratch).  A
+ * vertex is PINNED when a coordinate is not finite, when it has no neighbour, or when one of its neighbour entries is not "one
+ * face each way".  The neighbour entry i = (u, v) with v > u names the edge {u, v}, i is its id.  An edge is a candidate unless,
+ * in this order: (1) an end is pinned; (2) the third vertices a, b of its two faces are equal, or the two neighbour lists have
+ * other than two ids in common, or a or b has fewer than four neighbours; (3) the faces that touch u or v, each once, number
+ * more than 32; (4) with m the midpoint in double, the ten numbers of those faces about m (arah_mesh_quadric_place's nine and c
+ * = d d) summed by its tree in ascending face id, y its solve with reg and the bound max_a |u_a - v_a| (y = 0 after a fall-back,
+ * which is counted), pos = float32(m + y), raw = (y.Ay + 2 b.y) + c with every row and dot product summed left to right: the
+ * float32 of raw is not finite; (5) cost32 = float32(raw), +0 unless raw > 0, exceeds max_cost; (6) a face that names one of u, v
+ * has (N0 N'0 + N1 N'1) + N2 N'2 <= 0 (or not a number), N and N' its cross products before and after that corner moves to
+ * pos.  key = (bits(cost32) << 32) | i; m1[x] = the least key of the candidates at x, m2[x] = the least of m1 over x and its
+ * neighbours; a candidate is selected when m2[u] = m2[v] = key, and the first `need` selected edges in ascending id are applied:
+ * v becomes u, u moves to pos, vert_src of u is the one of u, v with the smaller float32 squared distance to pos (u on a tie),
+ * the valid faces that name both ends go, every other face keeps its row order and orientation with its ids in [0, n_verts)
+ * renamed, the merged vertices go and the others keep their order.  -> verts_out [n_verts][3], vert_src [n_verts], faces_out
+ * [n_faces][3], face_src [n_faces] (rows past the counts ZERO); counts (device int32[12]) = vertices, faces, selected edges,
+ * applied edges, candidates, edges with reason 1 .. 6, fall-backs; edge_pos [6 n_faces][3], edge_key [6 n_faces] (all ones: no
+ * candidate), edge_reason [6 n_faces] (0 candidate, 1 .. 6, 255: the entry names no edge) for every neighbour entry.  Integer
+ * atomics only (min, add): the result is unique, and equal to meshing.mesh_collapse_round bit for bit.  need >= 0, reg finite
+ * and >= 0, max_cost >= 0 (infinity: no bound), sizes as for arah_mesh_adjacency, otherwise ARAH_E_BADARG without a launch and a
+ * scratch size of 0; scratch: arah_mesh_collapse_round_scratch_bytes(n_verts, n_faces) device bytes, 256-byte aligned,
+ * ARAH_E_WORKSPACE when short.  Empty inputs still write counts; pointers of empty arrays may be NULL.  No host synchronisation,
+ * no allocation. */
+size_t arah_mesh_collapse_round_scratch_bytes(int64_t n_verts, int64_t n_faces);
+int arah_mesh_collapse_round(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t need, double reg,
+                             float max_cost, float* verts_out, int32_t* faces_out, int32_t* vert_src, int32_t* face_src,
+                             int32_t* counts, float* edge_pos, uint64_t* edge_key, uint8_t* edge_reason, void* scratch,
+                             size_t scratch_bytes, void* stream);
 /* Per-vertex normals of an indexed mesh from the mesh itself (pytorch3d verts_normals_packed): verts [n_verts][3], faces
  * [n_faces][3], vf_start / vf of arah_mesh_adjacency on the same mesh.  Vertex v walks its incident faces in the order of vf
  * (ascending id); a face with a non-finite corner contributes nothing, the others (p1 - p0) x (p2 - p0) with the corners widened to
