@@ -1957,6 +1957,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_canon_solve(FrameDev fr, const 
 #include "meshadj.hpp"
 #include "meshquadric.hpp"
 #include "meshcollapse.hpp"
+#include "meshsubdiv.hpp"
 #include "meshorient.hpp"
 #include "meshraster.hpp"
 #include "canon_wave.hpp"
@@ -4713,6 +4714,101 @@ int arah_mesh_collapse_round(const float* verts, int64_t n_verts, const int32_t*
                                (int*)face_src);
         });
     hipLaunchKernelGGL(k_mx_finish, dim3(1), dim3(64), 0, s, (int*)counts, (int)need);
+    return check_launch();
+}
+
+// ---- one round of subdivision (csrc/meshsubdiv.hpp) --------------------------------------------------------------------------------
+struct SbScratch {
+    int *vf_start, *vf, *nbr_start, *nbr, *nbr_out, *nbr_in, *acounts;
+    unsigned char* vert_flags;
+    int *owner, *rank, *opp, *fent, *totals, *blk_count, *blk_base, *vert_stat, *mark_stat, *face_stat;
+    void* adjacency;
+    size_t adjacency_bytes, bytes;
+};
+
+// F <= 2^26 and V + 3 F < 2^31: the ids of the output's vertices and the 4 F rows of its faces fit an int32
+static bool sb_sizes_ok(int64_t n_verts, int64_t n_faces) {
+    return n_verts >= 0 && n_faces >= 0 && n_faces <= ((int64_t)1 << 26) && n_verts + 3 * n_faces < ((int64_t)1 << 31);
+}
+
+static SbScratch carve_subdivide(void* scratch, int64_t n_verts, int64_t n_faces) {
+    SbScratch w{};
+    MeshCarver c(scratch);
+    const size_t V = (size_t)n_verts, F = (size_t)n_faces;
+    const size_t nbv = mesh_blocks(n_verts), nbe = mesh_blocks(6 * n_faces), nbf = mesh_blocks(n_faces);
+    w.vf_start = c.take<int>(V + 1);
+    w.vf = c.take<int>(3 * F);
+    w.nbr_start = c.take<int>(V + 1);
+    w.nbr = c.take<int>(6 * F);
+    w.nbr_out = c.take<int>(6 * F);
+    w.nbr_in = c.take<int>(6 * F);
+    w.acounts = c.take<int>(8);
+    w.vert_flags = c.take<unsigned char>(V);
+    w.owner = c.take<int>(6 * F);
+    w.rank = c.take<int>(6 * F);
+    w.opp = c.take<int>(12 * F);
+    w.fent = c.take<int>(3 * F);
+    w.totals = c.take<int>(2);
+    w.blk_count = c.take<int>(std::max(nbv, nbe));
+    w.blk_base = c.take<int>(std::max(nbv, nbe));
+    w.vert_stat = c.take<int>(3 * nbv);
+    w.mark_stat = c.take<int>(3 * nbe);
+    w.face_stat = c.take<int>(3 * nbf);
+    w.adjacency_bytes = carve_adjacency(nullptr, n_verts, n_faces).bytes;
+    w.adjacency = c.take<char>(w.adjacency_bytes);
+    w.bytes = c.bytes();
+    return w;
+}
+
+size_t arah_mesh_subdivide_round_scratch_bytes(int64_t n_verts, int64_t n_faces) {
+    if (!sb_sizes_ok(n_verts, n_faces)) return 0;
+    return carve_subdivide(nullptr, n_verts, n_faces).bytes;
+}
+
+int arah_mesh_subdivide_round(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t method,
+                              int32_t has_threshold, double max_len2, float* verts_out, int32_t* faces_out, int32_t* vert_src,
+                              int32_t* face_src, int32_t* counts, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!sb_sizes_ok(n_verts, n_faces) || !counts || !scratch || (method != 0 && method != kSbLoop)) return ARAH_E_BADARG;
+    if (has_threshold && (method == kSbLoop || std::isnan(max_len2) || max_len2 < 0.0)) return ARAH_E_BADARG;
+    if ((n_verts > 0 && !verts) || (n_faces > 0 && (!faces || !faces_out || !face_src)) || (n_verts + n_faces > 0 && (!verts_out || !vert_src)))
+        return ARAH_E_BADARG;
+    const SbScratch w = carve_subdivide(scratch, n_verts, n_faces);
+    if (scratch_bytes < w.bytes) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int V = (int)n_verts, F = (int)n_faces, cap = 6 * F, loop = method == kSbLoop ? 1 : 0;
+    const int nbv = (int)mesh_blocks(V), nbe = (int)mesh_blocks(cap), nbf = (int)mesh_blocks(F);
+    const dim3 tb(kImeshThreads), gv(mesh_grid(V));
+    // an empty mesh runs the adjacency's launches over nothing (nbr_start[V] = 0); the walks of no element are left out
+    if (int rc = arah_mesh_adjacency(faces, n_faces, n_verts, w.vf_start, w.vf, w.nbr_start, w.nbr, w.nbr_out, w.nbr_in, w.vert_flags,
+                                     w.acounts, w.adjacency, w.adjacency_bytes, stream))
+        return rc;
+    if (V > 0) {
+        hipLaunchKernelGGL(k_sb_owner, gv, tb, 0, s, V, (const int*)w.nbr_start, w.owner);
+        hipLaunchKernelGGL(k_sb_verts, dim3(nbv), tb, 0, s, verts, V, (const int*)w.nbr_start, (const int*)w.nbr, (const int*)w.nbr_out,
+                           (const int*)w.nbr_in, loop, w.blk_count, w.vert_stat, verts_out, (int*)vert_src);
+    }
+    if (F > 0) {
+        hipLaunchKernelGGL(k_sb_face_entries, dim3(mesh_grid(F)), tb, 0, s, (const int*)faces, F, V, (const int*)w.nbr_start,
+                           (const int*)w.nbr, loop, w.fent, w.opp);
+        mesh_compact_passes(s, nbe, w.blk_count, w.blk_base, w.totals, [&](auto fill, int* count, const int* base) {
+            hipLaunchKernelGGL((k_sb_marks<decltype(fill)::value>), dim3(nbe), tb, 0, s, verts, V, cap, (const int*)w.nbr_start,
+                               (const int*)w.nbr, (const int*)w.nbr_out, (const int*)w.nbr_in, (const int*)w.owner, (const int*)w.opp,
+                               loop, (int)(has_threshold != 0), max_len2, count, base, w.mark_stat, w.rank, verts_out, (int*)vert_src);
+        });
+        mesh_compact_passes(s, nbf, w.blk_count, w.blk_base, w.totals + 1, [&](auto fill, int* count, const int* base) {
+            hipLaunchKernelGGL((k_sb_faces<decltype(fill)::value>), dim3(nbf), tb, 0, s, (const int*)faces, F, V, (const int*)w.fent,
+                               (const int*)w.rank, count, base, w.face_stat, (const float*)verts_out, (int*)faces_out, (int*)face_src);
+        });
+    }
+    hipLaunchKernelGGL(k_sb_finish, dim3(1), tb, 0, s, V, F, (const int*)w.acounts, F > 0 ? (const int*)w.totals : (const int*)nullptr,
+                       F > 0 ? (const int*)(w.totals + 1) : (const int*)nullptr, (const int*)w.vert_stat, V > 0 ? nbv : 0,
+                       (const int*)w.mark_stat, F > 0 ? nbe : 0, (const int*)w.face_stat, F > 0 ? nbf : 0, (int*)counts);
+    if (F > 0) {
+        mesh_pad(s, verts_out, counts, V + 3 * F, 3);
+        mesh_pad(s, vert_src, counts, V + 3 * F, 2);
+        mesh_pad(s, faces_out, counts + 1, 4 * F, 3);
+        mesh_pad(s, face_src, counts + 1, 4 * F, 1);
+    }
     return check_launch();
 }
 

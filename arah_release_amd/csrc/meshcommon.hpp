@@ -1,5 +1,5 @@
 // meshcommon.hpp -- what the mesh headers share.  The indexed-mesh side (mcubes.hpp, meshcc.hpp, meshsimp.hpp, meshadj.hpp,
-// meshquadric.hpp, meshorient.hpp, meshraster.hpp, and meshintersect.hpp on the query side's grid): the launch constants, the workgroup prefix, the ordered compaction walk, the
+// meshquadric.hpp, meshcollapse.hpp, meshsubdiv.hpp, meshorient.hpp, meshraster.hpp, and meshintersect.hpp on the query side's grid): the launch constants, the workgroup prefix, the ordered compaction walk, the
 // one-workgroup scan, the padding of the rows between a count and a capacity, and cc_add_one.  The box walkers of both sides
 // (meshraster.hpp, meshcontains.hpp, meshsdf.hpp): the wave's turns and the walk of the two lists, at the end of this file.  The
 // one-workgroup box reduction of the query side (meshquery.hpp, meshcontains.hpp, meshwinding.hpp).  DESIGN.md ("Indexed meshes:
@@ -15,7 +15,8 @@
 //   fill    the same walk again; a marked element takes the id blk_base[block] + the marks in front of it inside the part
 //
 // The part of a workgroup is a lattice row in mcubes.hpp (k_mcubes, k_mc_verts: their own row walks over mesh_prefix) and a chunk
-// of kImeshChunk consecutive elements everywhere else (mesh_compact: k_cc_compact, k_ms_compact, k_mo_compact).
+// of kImeshChunk consecutive elements everywhere else (mesh_compact: k_cc_compact, k_ms_compact, k_mo_compact; meshsubdiv.hpp's
+// sb_walk is the same chunk walk over mesh_prefix with a weight per element instead of a 0/1 mark).
 #pragma once
 
 // "Imesh" = indexed mesh: kMeshThreads = 64 and kMeshChunk = 128 are meshquery.hpp's, the query side's, in the same namespace.

@@ -822,6 +822,144 @@ def apply_simplify(verts, faces, simplify):
     return simplify_mesh(verts, faces, **simplify)
 
 
+# ---- subdivision ----------------------------------------------------------------------------------------------------------------------
+_SUBDIVIDE_KEYS = ("levels", "method", "max_edge", "max_rounds", "max_faces")
+
+
+def check_subdivide(subdivide):
+    """The mesh entries' `subdivide` option, validated: None stays None, an integer is a number of uniform midpoint levels, a dict
+    holds keywords of `subdivide_mesh` (levels, method, max_edge, max_rounds, max_faces).  -> the dict of keywords; ValueError for
+    anything else."""
+    import math
+    if subdivide is None:
+        return None
+    if isinstance(subdivide, (int, np.integer)) and not isinstance(subdivide, bool):
+        subdivide = {"levels": int(subdivide)}
+    if not isinstance(subdivide, dict):
+        raise ValueError("subdivide must be None, a number of levels or a dict of subdivide_mesh keywords, got %r" % (subdivide,))
+    bad = set(subdivide) - set(_SUBDIVIDE_KEYS)
+    if bad:
+        raise ValueError("subdivide: unknown keys %s (known: %s)" % (sorted(bad), ", ".join(_SUBDIVIDE_KEYS)))
+    kw = dict(subdivide)
+    levels, method, max_edge = kw.get("levels", 1), kw.get("method", "midpoint"), kw.get("max_edge")
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or int(levels) < 0:
+        raise ValueError("subdivide_mesh: levels must be an integer >= 0, got %r" % (levels,))
+    if method not in ("midpoint", "loop"):
+        raise ValueError("subdivide_mesh: method must be 'midpoint' or 'loop', got %r" % (method,))
+    if max_edge is not None:
+        if isinstance(max_edge, bool) or not isinstance(max_edge, (int, float, np.integer, np.floating)) \
+                or not math.isfinite(float(max_edge)) or float(max_edge) <= 0.0:
+            raise ValueError("subdivide_mesh: max_edge must be a finite length > 0, got %r" % (max_edge,))
+        if method == "loop":
+            raise ValueError("subdivide_mesh: method='loop' refines every edge: it takes no max_edge")
+    for name in ("max_rounds", "max_faces"):
+        x = kw.get(name, 0)
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or int(x) < 0:
+            raise ValueError("subdivide_mesh: %s must be an integer >= 0, got %r" % (name, x))
+    return kw
+
+
+def _weights_step(rows, cols, vals, n_rows, n_cols, lo, hi):
+    """The (n_rows x n_cols) weights as sorted COO triples with rows lo and hi averaged appended: -> the triples of the taller matrix."""
+    from . import meshing
+    cnt = torch.bincount(rows, minlength=n_rows)
+    start = torch.cumsum(cnt, 0) - cnt
+    parts = [(rows, cols, vals)]
+    for ids in (lo, hi):
+        k, r = meshing._ragged(start[ids], cnt[ids])
+        parts.append((n_rows + k, cols[r], vals[r] * 0.5))
+    idx = torch.stack([torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])])
+    w = torch.sparse_coo_tensor(idx, torch.cat([p[2] for p in parts]), (n_rows + int(lo.shape[0]), n_cols)).coalesce()
+    return w.indices()[0], w.indices()[1], w.values()
+
+
+def subdivide_mesh(verts, faces, levels=1, method="midpoint", max_edge=None, max_rounds=16, max_faces=1 << 24, attributes=None):
+    """Refine an indexed mesh (verts (V,3), faces (F,3) integer ids): rounds of `mesh_subdivide_round` (arah_mesh_subdivide_round on
+    the GPU, meshing.mesh_subdivide_round on the host, equal bit for bit).  Old vertices keep their ids, new ones follow; faces
+    keep their orientation and their order; marks belong to edges, so a closed manifold mesh stays closed and manifold.
+
+        levels      without max_edge: the number of uniform rounds -- every edge is split, every face becomes four
+        method      "midpoint": new vertices at the midpoints, old ones stay -- the surface does not move; "loop": Loop's scheme
+                    with Warren's weights -- old vertices move too, a coarse cage converges to a smooth limit surface; boundary,
+                    non-manifold and misoriented edges and non-finite vertices fall back to the midpoint
+        max_edge    midpoint only, levels is ignored: rounds that split only the edges longer than max_edge (squared length >
+                    float(max_edge)^2) until a round marks nothing (report["reached"]) or max_rounds rounds have run
+        max_faces   a ValueError before a round whose worst case, four times its faces, exceeds it -- for uniform rounds before
+                    the first one runs
+
+    ONE host synchronisation per round (its counts).  -> dict of verts (V',3) float32, faces (F',3) in the dtype of `faces`,
+    n_verts, n_tris, vert_src (V',2) int64 -- (v, v) for an input vertex and (lo, hi), the ends of the edge it split, for a new
+    one, as ids of the OUTPUT (an id below V is an input vertex: following the pairs ends there) --, vert_weights, the same
+    composed down to the input: a sparse COO float64 (V' x V) matrix whose row is the midpoint rule's weights over the input
+    vertices (after two rounds up to four of them; vert_weights @ verts is the midpoint position before rounding), face_src (F',)
+    int64 (the input face every output face lies in), and report = dict of rounds, reached, verts / faces / marked (per round; the
+    first two start with the input's) and counts (the last round's, by meshing.SUBDIVIDE_COUNTS).  attributes = {name: (V, ...)
+    tensor}: pushed through the midpoint rule round by round whatever the method -- a new vertex gets ((A_lo + A_hi) 0.5) in
+    float64 rounded to the attribute's dtype when that is floating, A_lo otherwise; old vertices keep theirs."""
+    from . import meshing
+    kw = check_subdivide({"levels": levels, "method": method, "max_edge": max_edge, "max_rounds": max_rounds, "max_faces": max_faces})
+    n_verts, faces = _mesh_args(verts, faces, "subdivide_mesh")
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or not verts.dtype.is_floating_point:
+        raise ValueError("subdivide_mesh: verts must be a floating-point (V, 3) tensor")
+    if verts.device != faces.device:
+        raise ValueError("subdivide_mesh: verts live on %s, faces on %s" % (verts.device, faces.device))
+    reserved = ("verts", "faces", "n_verts", "n_tris", "vert_src", "vert_weights", "face_src", "report")
+    attributes = _repair_attributes(attributes, n_verts, verts.device, reserved, "subdivide_mesh")
+    backend, dev, names = _cc_backend(faces), verts.device, meshing.SUBDIVIDE_COUNTS
+    n_faces, max_faces = int(faces.shape[0]), int(kw["max_faces"])
+    adaptive = max_edge is not None
+    max_len2 = float(max_edge) ** 2 if adaptive else None
+    n_rounds = int(max_rounds) if adaptive else int(levels)
+    if not adaptive and n_rounds > 0 and n_faces * 4 ** n_rounds > max_faces:
+        raise ValueError("subdivide_mesh: %d levels of %d faces give up to %d faces, more than max_faces = %d"
+                         % (n_rounds, n_faces, n_faces * 4 ** n_rounds, max_faces))
+    with torch.no_grad():
+        v, f = verts.detach().to(torch.float32).contiguous(), faces
+        ids = torch.arange(n_verts, device=dev)
+        vert_src, face_src = torch.stack([ids, ids], 1), torch.arange(n_faces, device=dev)
+        w_rows, w_cols, w_vals = ids, ids, torch.ones(n_verts, dtype=torch.float64, device=dev)
+        attrs = dict(attributes)
+        hist_v, hist_f, hist_m, last, rounds, reached = [n_verts], [n_faces], [], None, 0, not adaptive
+        while rounds < n_rounds:
+            if 4 * hist_f[-1] > max_faces:
+                raise ValueError("subdivide_mesh: a round of %d faces gives up to %d faces, more than max_faces = %d"
+                                 % (hist_f[-1], 4 * hist_f[-1], max_faces))
+            out = backend.mesh_subdivide_round(v, f, method, max_len2)
+            last = dict(zip(names, out[4].tolist()))                              # the host synchronisation
+            rounds += 1
+            hist_m.append(last["marked"])
+            if adaptive and last["marked"] == 0:
+                reached = True
+                break
+            nv, nf, n_old = last["n_verts"], last["n_faces"], hist_v[-1]
+            v, f = out[0][:nv], out[1][:nf]
+            src = out[2][n_old:nv].long()
+            lo, hi = src[:, 0], src[:, 1]
+            vert_src, face_src = torch.cat([vert_src, src]), face_src[out[3][:nf].long()]
+            w_rows, w_cols, w_vals = _weights_step(w_rows, w_cols, w_vals, n_old, n_verts, lo, hi)
+            for name, t in attrs.items():
+                new = ((t[lo].double() + t[hi].double()) * 0.5).to(t.dtype) if t.dtype.is_floating_point else t[lo]
+                attrs[name] = torch.cat([t, new])
+            hist_v.append(nv)
+            hist_f.append(nf)
+        weights = torch.sparse_coo_tensor(torch.stack([w_rows, w_cols]), w_vals, (hist_v[-1], n_verts)).coalesce()
+        res = {"verts": v, "faces": f.to(faces.dtype), "n_verts": int(v.shape[0]), "n_tris": int(f.shape[0]), "vert_src": vert_src,
+               "vert_weights": weights, "face_src": face_src,
+               "report": {"rounds": rounds, "reached": reached, "verts": hist_v, "faces": hist_f, "marked": hist_m, "counts": last}}
+        res.update(attrs)
+    return res
+
+
+def apply_subdivide(verts, faces, subdivide):
+    """The mesh entries' `subdivide` option, as `check_subdivide` returned it: -> the refined verts, faces, n_verts and n_tris of
+    `subdivide_mesh`, and under "subdivide" its vert_src, vert_weights, face_src and report -- the entries' own vert_src and
+    report (clean's, simplify's) stay what they are."""
+    res = subdivide_mesh(verts, faces, **subdivide)
+    out = {k: res[k] for k in ("verts", "faces", "n_verts", "n_tris")}
+    out["subdivide"] = {k: res[k] for k in ("vert_src", "vert_weights", "face_src", "report")}
+    return out
+
+
 # ---- adjacency, topology, per-vertex normals, smoothing -------------------------------------------------------------------------
 MeshAdjacency =collections.namedtuple("MeshAdjacency", ("vf_start", "vf", "nbr_start", "nbr", "nbr_out", "nbr_in", "vert_flags",
                                                          "counts"))

@@ -144,6 +144,7 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_mesh_simplify_scratch_bytes", "arah_mesh_simplify",
            "arah_mesh_quadric_place_scratch_bytes", "arah_mesh_quadric_place",
            "arah_mesh_collapse_round_scratch_bytes", "arah_mesh_collapse_round",
+           "arah_mesh_subdivide_round_scratch_bytes", "arah_mesh_subdivide_round",
            "arah_mesh_adjacency_scratch_bytes", "arah_mesh_adjacency", "arah_mesh_vertex_normals", "arah_mesh_smooth",
            "arah_mesh_orient_scratch_bytes", "arah_mesh_orient", "arah_mesh_boundary_loops_scratch_bytes",
            "arah_mesh_boundary_loops", "arah_mesh_fill_holes_scratch_bytes", "arah_mesh_fill_holes",
@@ -199,6 +200,7 @@ def load_library():
         getattr(lib, name).argtypes = [C.c_int32]
     for name in ("arah_mesh_components_scratch_bytes", "arah_mesh_select_scratch_bytes", "arah_mesh_adjacency_scratch_bytes",
                  "arah_mesh_quadric_place_scratch_bytes", "arah_mesh_collapse_round_scratch_bytes",
+                 "arah_mesh_subdivide_round_scratch_bytes",
                  "arah_mesh_orient_scratch_bytes", "arah_mesh_boundary_loops_scratch_bytes", "arah_mesh_fill_holes_scratch_bytes"):
         getattr(lib, name).restype = C.c_size_t
         getattr(lib, name).argtypes = [C.c_int64, C.c_int64]
@@ -1088,6 +1090,38 @@ def mesh_collapse_round(verts, faces, need, reg=1e-3, max_cost=float("inf"), det
                                             C.c_size_t(scratch.numel()), _stream()), "arah_mesh_collapse_round")
     out = (verts_out, faces_out, vert_src, face_src, counts)
     return out + (edge_pos, edge_key, edge_reason) if details else out
+
+
+def mesh_subdivide_round(verts, faces, method="midpoint", max_len2=None):
+    """One round of subdivision (arah_mesh_subdivide_round, csrc/meshsubdiv.hpp): verts (V,3) float32 and faces (F,3) integer ids on
+    the GPU; method "midpoint" or "loop" and max_len2 (None: every edge; a float: the edges with a squared length above it,
+    midpoint only) on the host, as meshing.mesh_subdivide_round describes them.  The adjacency of the mesh is built inside the
+    call.  -> verts_out (V+3F,3) float32, faces_out (4F,3) int32, vert_src (V+3F,2) int32, face_src (4F,) int32, counts (13,)
+    int32 (meshing.SUBDIVIDE_COUNTS); rows past the counts are zero.  All on the device, no host synchronisation; the result is
+    meshing.mesh_subdivide_round(...) bit for bit."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    what = "mesh_subdivide_round"
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise ValueError("%s: verts must be a (V, 3) float32 tensor" % what)
+    V = int(verts.shape[0])
+    f, _, F = _mesh_cc_args(faces, V, what)
+    if verts.device != f.device:
+        raise ValueError("%s: verts live on %s, faces on %s" % (what, verts.device, f.device))
+    loop, max_len2 = meshing.subdivide_args(method, max_len2, V, F, what)
+    v, dev, i32 = verts.detach().contiguous(), f.device, torch.int32
+    with _on_device(dev):
+        scratch = _mesh_cc_buf(dev, int(lib.arah_mesh_subdivide_round_scratch_bytes(V, F)))
+        verts_out = torch.empty(V + 3 * F, 3, dtype=torch.float32, device=dev)
+        faces_out = torch.empty(4 * F, 3, dtype=i32, device=dev)
+        vert_src, face_src = torch.empty(V + 3 * F, 2, dtype=i32, device=dev), torch.empty(4 * F, dtype=i32, device=dev)
+        counts = torch.empty(len(meshing.SUBDIVIDE_COUNTS), dtype=i32, device=dev)
+        _check(lib.arah_mesh_subdivide_round(_ptr(v), C.c_int64(V), _ptr(f), C.c_int64(F), C.c_int32(loop),
+                                             C.c_int32(0 if max_len2 is None else 1), C.c_double(0.0 if max_len2 is None else max_len2),
+                                             _ptr(verts_out), _ptr(faces_out), _ptr(vert_src), _ptr(face_src), _ptr(counts),
+                                             _ptr(scratch), C.c_size_t(scratch.numel()), _stream()), "arah_mesh_subdivide_round")
+    return verts_out, faces_out, vert_src, face_src, counts
 
 
 def vertex_normals(verts, faces, adjacency=None):

@@ -965,6 +965,197 @@ def mesh_collapse_round(verts, faces, need, reg=1e-3, max_cost=float("inf"), adj
     return out + (edge_pos, edge_key, edge_reason, edge_sel)
 
 
+# ---- subdivision: one round -----------------------------------------------------------------------------------------------------------
+SUBDIVIDE_MAX_FACES = 1 << 26           # 4 F output faces and V + 3 F output vertices fit an int32
+SUBDIVIDE_METHODS = {"midpoint": 0, "loop": 1}
+SUBDIVIDE_COUNTS = ("n_verts", "n_faces", "edges", "marked", "faces_0", "faces_1", "faces_2", "faces_3", "invalid", "marked_nonfinite",
+                    "interior", "rim", "kept")
+
+
+def subdivide_args(method, max_len2, n_verts, n_faces, what="mesh_subdivide_round"):
+    """The scalars of `mesh_subdivide_round`, checked: -> (the method's number, max_len2 as a float or None)."""
+    if method not in SUBDIVIDE_METHODS:
+        raise ValueError("%s: method must be 'midpoint' or 'loop', got %r" % (what, method))
+    if max_len2 is not None:
+        if isinstance(max_len2, bool) or not isinstance(max_len2, (int, float, np.integer, np.floating)):
+            raise ValueError("%s: max_len2 must be a number or None, got %r" % (what, max_len2))
+        max_len2 = float(max_len2)
+        if math.isnan(max_len2) or max_len2 < 0.0:
+            raise ValueError("%s: max_len2 must be a number >= 0 (inf: nothing is marked), got %r" % (what, max_len2))
+        if method == "loop":
+            raise ValueError("%s: method='loop' refines every edge: it takes no threshold" % what)
+    if n_faces > SUBDIVIDE_MAX_FACES or n_verts + 3 * n_faces >= 2 ** 31:
+        raise ValueError("%s: at most 2^26 faces and V + 3 F < 2^31, got V = %d, F = %d" % (what, n_verts, n_faces))
+    return SUBDIVIDE_METHODS[method], max_len2
+
+
+def _d2_f64(p, q):
+    """(dx dx + dy dy) + dz dz of float32 points in float64, every operation rounded on its own."""
+    d = p.to(torch.float64) - q.to(torch.float64)
+    return (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+
+
+def mesh_subdivide_round(verts, faces, method="midpoint", max_len2=None, adjacency=None):
+    """One round of subdivision of an indexed mesh: verts (V,3) float32, faces (F,3) integer ids (F <= 2^26, V + 3 F < 2^31; a face
+    is valid as `mesh_adjacency` defines it), adjacency `mesh_adjacency` of the mesh or None.  Integers decide; all floating point
+    is float64 from the float32 inputs, every operation rounded on its own, and reads the INPUT positions only.  A vertex is
+    finite when its three coordinates are.
+
+    EDGES AND MARKS: the neighbour entry (v, n) with n > v names the edge with the ends lo = v and hi = n, in ascending (v, n)
+    order.  max_len2 = None: every edge is marked.  Otherwise (a Python float >= 0, midpoint only) an edge is marked when both ends
+    are finite and d2 > max_len2, d2 = (dx dx + dy dy) + dz dz.  The k-th marked edge becomes vertex V + k; old vertices keep
+    their ids.
+
+    POSITIONS, "midpoint": old vertices are copied bit for bit; a new vertex is float32((lo + hi) 0.5); when an end is not finite
+    (a uniform round only) it takes the bits of its lowest-id non-finite end, a copy without arithmetic.
+
+    POSITIONS, "loop" (Warren's weights: no cosine).  An entry is REGULAR when nbr_out = nbr_in = 1.  A new vertex on a regular
+    edge with finite lo, hi, c and d -- c the third corner of the face traversing lo->hi, d of the one traversing hi->lo -- is
+    float32((lo + hi) 0.375 + (c + d) 0.125); every other new vertex takes the midpoint rule above.  An old vertex is INTERIOR
+    when it is finite, has k >= 1 edges, all regular, and all its neighbours are finite: it moves to float32(p (1 - k beta) + s
+    beta), s the sum of its neighbours in ascending id starting from 0, beta = 3/16 for k = 3 and 3.0 / (8.0 k) otherwise.  An
+    old vertex is a RIM vertex when it is finite (a non-finite one is never put through arithmetic), exactly two of its edges
+    have one face, every other edge is regular and the neighbours b0 < b1 across the two are finite: it moves to float32(p 0.75
+    + (b0 + b1) 0.125).  Every other old vertex stays bit for bit.
+
+    FACES: a valid face (a, b, c) with m marked edges becomes 1 + m faces in its orientation; x, y, z are the new vertices on ab,
+    bc, ca.  m = 0: (a,b,c).  m = 3: (a,x,z), (x,b,y), (z,y,c), (x,y,z).  m = 1, rotated cyclically so that ab is marked:
+    (a,x,c), (x,b,c).  m = 2, rotated so that ca is unmarked: (x,b,y), then (a,x,y), (a,y,c) when d2(a, y) < d2(x, c) on the
+    OUTPUT float32 positions, else -- ties included -- (a,x,c), (x,y,c).  An invalid face is copied as one face (an id that does
+    not fit int32 is -1).  Faces are ordered by input face, then by template.  Marks belong to edges: no T-junction.
+
+    -> verts_out (V+3F,3) float32, faces_out (4F,3) int32, vert_src (V+3F,2) int32 ((v, v) or (lo, hi)), face_src (4F,) int32,
+    counts (13,) int32 in the order of SUBDIVIDE_COUNTS; rows past the counts are zero.  Plain tensor operations on the tensors'
+    device: the specification of arah_mesh_subdivide_round (csrc/meshsubdiv.hpp), and what runs for meshes on the host."""
+    what = "mesh_subdivide_round"
+    raw_faces = torch.as_tensor(faces)
+    verts, faces, V, in_range = _mesh_verts(verts, faces, what)
+    F, dev = int(faces.shape[0]), verts.device
+    loop, max_len2 = subdivide_args(method, max_len2, V, F, what)
+    if raw_faces.dtype != torch.int32:
+        faces = torch.where((faces >= 0) & (faces <= 2 ** 31 - 1), faces, torch.full_like(faces, -1))
+    f64, i32, i64 = torch.float64, torch.int32, torch.int64
+    adjacency = _adjacency_of(faces, V, adjacency, what)
+    nbr_start, nbr, nbr_out, nbr_in = (t.long() for t in adjacency[2:6])
+    E = int(nbr_start[V])
+    val = nbr_start[1:] - nbr_start[:-1]
+    ids_v = torch.arange(V, device=dev)
+    ev, en, n_out, n_in = torch.repeat_interleave(ids_v, val), nbr[:E], nbr_out[:E], nbr_in[:E]
+    finite = torch.isfinite(verts).all(1)
+    p64 = verts.to(f64)
+    W = max(V, 1)
+    ekey = ev * W + en                                                           # ascending: the entries' own order
+    # marks and ranks
+    is_edge = en > ev
+    both = finite[ev] & finite[en]
+    marked = is_edge & (both & (_d2_f64(verts[ev], verts[en]) > max_len2) if max_len2 is not None else torch.ones_like(is_edge))
+    rank = torch.cumsum(marked.long(), 0) - 1
+    me = torch.nonzero(marked)[:, 0]
+    n_marked = int(me.shape[0])
+    lo, hi = ev[me], en[me]
+    # the entries of the faces' edges; Loop: the opposite corners by traversal direction
+    valid = in_range & (faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 0] != faces[:, 2])
+    rows = torch.nonzero(valid)[:, 0]
+    fv = faces[rows]
+    fs, fd, ft = fv, fv[:, [1, 2, 0]], fv[:, [2, 0, 1]]                          # edge j: source, destination, third corner
+    fent = torch.searchsorted(ekey, torch.minimum(fs, fd) * W + torch.maximum(fs, fd)) if rows.numel() else fs   # (Fv,3), all found
+    # old vertices
+    verts_out = torch.zeros(V + 3 * F, 3, dtype=torch.float32, device=dev)
+    vert_src = torch.zeros(V + 3 * F, 2, dtype=i64, device=dev)
+    moved = verts.clone()
+    n_interior = n_rim = 0
+    regular = (n_out == 1) & (n_in == 1)
+    if loop and E:
+        one = (n_out + n_in) == 1
+        irregular = torch.zeros(V, dtype=i64, device=dev).index_add_(0, ev, (~regular).long())
+        odd = torch.zeros(V, dtype=i64, device=dev).index_add_(0, ev, (~regular & ~one).long())
+        n_one = torch.zeros(V, dtype=i64, device=dev).index_add_(0, ev, one.long())
+        nonfin = torch.zeros(V, dtype=i64, device=dev).index_add_(0, ev, (~finite[en]).long())
+        first = nbr_start[:-1]
+        s = torch.zeros(V, 3, dtype=f64, device=dev)
+        for k in range(int(val.max())):                                          # the ordered sum: a padded gather, + 0.0 is exact
+            has = k < val
+            n = nbr[(first + k).clamp(max=6 * F - 1)]
+            s = s + torch.where(has[:, None], p64[n], torch.zeros_like(s))
+        kf = val.to(f64)
+        beta = torch.where(val == 3, torch.full_like(kf, 0.1875), 3.0 / (8.0 * kf.clamp_min(1.0)))
+        keep = 1.0 - kf * beta
+        interior = finite & (val > 0) & (irregular == 0) & (nonfin == 0)
+        new_int = (p64 * keep[:, None] + s * beta[:, None]).float()
+        # the rim neighbours: the one-face entries of a vertex in ascending order, the first and the second
+        oe = torch.nonzero(one)[:, 0]
+        b0, b1 = torch.zeros(V, dtype=i64, device=dev), torch.zeros(V, dtype=i64, device=dev)
+        if oe.numel():
+            ov = ev[oe]
+            nth = torch.arange(oe.shape[0], device=dev) - (torch.cumsum(n_one, 0) - n_one)[ov]
+            b0[ov[nth == 0]] = en[oe[nth == 0]]
+            b1[ov[nth == 1]] = en[oe[nth == 1]]
+        rim = finite & (n_one == 2) & (odd == 0) & finite[b0] & finite[b1]
+        new_rim = (p64 * 0.75 + (p64[b0] + p64[b1]) * 0.125).float()
+        moved = torch.where(interior[:, None], new_int, torch.where(rim[:, None], new_rim, verts))
+        n_interior, n_rim = int(interior.sum()), int(rim.sum())
+    verts_out[:V] = moved
+    vert_src[:V] = ids_v[:, None]
+    # new vertices
+    n_nonfinite = 0
+    if n_marked:
+        plo, phi = p64[lo], p64[hi]
+        new = ((plo + phi) * 0.5).float()
+        if loop:
+            opp = torch.zeros(E, 2, dtype=i64, device=dev)
+            along = fs < fd
+            opp[fent[along], 0] = ft[along]
+            opp[fent[~along], 1] = ft[~along]
+            c, d = opp[me, 0], opp[me, 1]
+            stencil = regular[me] & finite[c] & finite[d]
+            new = torch.where(stencil[:, None], ((plo + phi) * 0.375 + (p64[c] + p64[d]) * 0.125).float(), new)
+        bad = ~both[me]
+        n_nonfinite = int(bad.sum())
+        copy = torch.where(finite[lo][:, None], verts[hi], verts[lo])
+        verts_out[V:V + n_marked] = torch.where(bad[:, None], copy, new)
+        vert_src[V:V + n_marked] = torch.stack([lo, hi], 1)
+    # faces
+    faces_out = torch.zeros(4 * F, 3, dtype=i64, device=dev)
+    face_src = torch.zeros(4 * F, dtype=i64, device=dev)
+    per = [0, 0, 0, 0]
+    n_faces_out = 0
+    if F:
+        nv = torch.full((F, 3), -1, dtype=i64, device=dev)
+        if rows.numel():
+            nv[rows] = torch.where(marked[fent], V + rank[fent], torch.full_like(fent, -1))
+        has = nv >= 0
+        m = has.sum(1)
+        per = [int((valid & (m == j)).sum()) for j in range(4)]
+        # the rotation: one mark -> the marked edge first; two marks -> the unmarked edge last
+        r = torch.zeros(F, dtype=i64, device=dev)
+        r = torch.where(m == 1, torch.where(has[:, 0], 0, torch.where(has[:, 1], 1, 2)), r)
+        r = torch.where(m == 2, torch.where(~has[:, 2], 0, torch.where(~has[:, 0], 1, 2)), r)
+        turn = (r[:, None] + torch.arange(3, device=dev)[None, :]) % 3
+        a, b, c = (torch.gather(faces, 1, turn)[:, j] for j in range(3))
+        x, y, z = (torch.gather(nv, 1, turn)[:, j] for j in range(3))
+        pos = verts_out
+        safe = lambda t: t.clamp(0, V + 3 * F - 1)                               # rows of other templates are never used
+        ay = (m == 2) & (_d2_f64(pos[safe(a)], pos[safe(y)]) < _d2_f64(pos[safe(x)], pos[safe(c)]))
+        tpl = torch.zeros(F, 4, 3, dtype=i64, device=dev)
+        tri = lambda *t: torch.stack(t, 1)
+        tpl[:, 0] = tri(a, b, c)
+        for sel, rows_t in (((m == 3), (tri(a, x, z), tri(x, b, y), tri(z, y, c), tri(x, y, z))),
+                            ((m == 1), (tri(a, x, c), tri(x, b, c))),
+                            ((m == 2) & ay, (tri(x, b, y), tri(a, x, y), tri(a, y, c))),
+                            ((m == 2) & ~ay, (tri(x, b, y), tri(a, x, c), tri(x, y, c)))):
+            for j, t in enumerate(rows_t):
+                tpl[:, j] = torch.where(sel[:, None], t, tpl[:, j])
+        n_of = 1 + m
+        keep_row = torch.arange(4, device=dev)[None, :] < n_of[:, None]
+        n_faces_out = int(n_of.sum())
+        faces_out[:n_faces_out] = tpl[keep_row]
+        face_src[:n_faces_out] = torch.arange(F, device=dev)[:, None].expand(F, 4)[keep_row]
+    n_edges = int(is_edge.sum())
+    counts = torch.tensor([V + n_marked, n_faces_out, n_edges, n_marked] + per + [F - int(valid.sum()), n_nonfinite, n_interior, n_rim,
+                           V - n_interior - n_rim], dtype=i32, device=dev)
+    return verts_out, faces_out.to(i32), vert_src.to(i32), face_src.to(i32), counts
+
+
 # ---- orientation, boundary loops, hole filling -----------------------------------------------------------------------------------
 ORIENT_POLICIES ={"seed": 0, "majority": 1, "negative": 2, "positive": 3}
 ORIENT_VOL_BITS = 18                    # quantised coordinates lie in [-2^18, 2^18]: a determinant of three stays below 2^57

@@ -903,7 +903,8 @@ class MetaAvatarRender(nn.Module):
                 "points_hat": r["points_hat"].reshape(*shape, 3), "weights": r["weights"].reshape(*shape, 24),
                 "converged": (r["state"] == 1).reshape(shape), "state": r["state"].reshape(shape)}
 
-    def posed_mesh(self, inputs, n_side=256, method="lattice", bounds=None, indexed=False, clean=None, simplify=None, smooth=None):
+    def posed_mesh(self, inputs, n_side=256, method="lattice", bounds=None, indexed=False, clean=None, simplify=None, smooth=None,
+                   subdivide=None):
         """A triangle soup of the posed body of frame `inputs` in world metres.  method="lattice": the zero level set of the posed
         SDF (hip.sdf_grid_posed, only the band around the occupancy bitmap's marked voxels unless ARAH_POSED_MESH_BAND=0, then
         hip.marching_cubes) -- the surface the renderer sees, self-contact included.  method="skinned": the reference's points_bar
@@ -923,6 +924,10 @@ class MetaAvatarRender(nn.Module):
         instead, geometry.decimate_mesh: a closed surface stays closed; vert_src, face_src and report are then decimate_mesh's.
         smooth (indexed=True only; None: nothing changes): a number of Taubin iterations or a dict of geometry.smooth_mesh
         keywords -- verts are geometry.smooth_mesh of the unsmoothed call's, AFTER clean and simplify; faces, counts and ids stay.
+        subdivide (indexed=True only; None: nothing changes): a number of uniform midpoint levels or a dict of
+        geometry.subdivide_mesh keywords (levels, method, max_edge, max_rounds, max_faces) -- the mesh is geometry.subdivide_mesh of
+        the call without it, AFTER clean and simplify and BEFORE smooth; verts, faces, n_verts and n_tris are the refined mesh's
+        and "subdivide" holds its vert_src, vert_weights, face_src and report (ids of the mesh that was refined).
         Eval only."""
         from . import geometry, meshing
         if clean is not None:
@@ -937,6 +942,10 @@ class MetaAvatarRender(nn.Module):
             smooth = geometry.check_smooth(smooth)
             if not indexed:
                 raise ValueError("posed_mesh: smooth needs indexed=True (neighbours are defined by shared vertex ids)")
+        if subdivide is not None:
+            subdivide = geometry.check_subdivide(subdivide)
+            if not indexed:
+                raise ValueError("posed_mesh: subdivide needs indexed=True (edges are defined by shared vertex ids)")
         frame, ws = self._posed_frame(inputs, "posed_mesh")
         if method not in ("lattice", "skinned"):
             raise ValueError("method must be 'lattice' or 'skinned', got %r" % (method,))
@@ -965,6 +974,8 @@ class MetaAvatarRender(nn.Module):
                     res.update(geometry.clean_mesh(res["verts"], res["faces"], keep=clean))
                 if simplify is not None:
                     res.update(geometry.apply_simplify(res["verts"], res["faces"], simplify))
+                if subdivide is not None:
+                    res.update(geometry.apply_subdivide(res["verts"], res["faces"], subdivide))
                 if smooth is not None:
                     res["verts"] = geometry.smooth_mesh(res["verts"], res["faces"], **smooth)
                 return res
@@ -990,7 +1001,7 @@ class MetaAvatarRender(nn.Module):
                 n = int(n_dev.item())
             return {"tris": hip.lattice_to_world(tris[:n], box), "n_tris": n, "box": box, "counts": counts}
 
-    def canonical_mesh(self, inputs, n_side=256, attributes=(), view_dirs=None, clean=None, simplify=None, smooth=None):
+    def canonical_mesh(self, inputs, n_side=256, attributes=(), view_dirs=None, clean=None, simplify=None, smooth=None, subdivide=None):
         """The canonical body of frame `inputs` as an indexed mesh, the reference's create_mesh_vertices_and_faces
         (utils/sdf_meshing.py:13-114): the zero level set of the canonical SDF on the n_side^3 lattice (hip.sdf_grid_band, then
         hip.marching_cubes_indexed).  -> dict of verts (V,3) normalised canonical coordinates in [-1,1]^3, faces (F,3) int32,
@@ -1021,6 +1032,12 @@ class MetaAvatarRender(nn.Module):
         clean and simplify and BEFORE the attributes are evaluated, which are then taken at the smoothed positions.  With smooth
         and "vertex_normal" the adjacency is built once for both.
 
+        subdivide (None: nothing changes): a number of uniform midpoint levels or a dict of geometry.subdivide_mesh keywords;
+        applied after clean and simplify and BEFORE smooth and the attributes, which are evaluated at the refined mesh's
+        vertices: simplify={"method": "collapse", "target_faces": 2000}, subdivide={"max_edge": 0.01} asks the colour and
+        skinning networks inside the large faces.  V is then the refined mesh's, and "subdivide" holds subdivide_mesh's vert_src,
+        vert_weights, face_src and report (ids of the mesh that was refined).
+
         Eval only, GPU only; one host synchronisation (the mesh's size), one more with clean, simplify_mesh's with simplify."""
         from . import geometry, meshing
         names = ("weights", "verts_posed", "normal", "color", "vertex_normal")
@@ -1032,6 +1049,7 @@ class MetaAvatarRender(nn.Module):
         if simplify is not None:
             simplify = geometry.check_simplify(simplify)
         smooth = geometry.check_smooth(smooth)
+        subdivide = geometry.check_subdivide(subdivide)
         frame, ws = self._posed_frame(inputs, "canonical_mesh")
         with torch.no_grad():
             verts, faces = meshing.indexed_mesh(meshing.canonical_lattice(frame, ws, n_side), 0.0)
@@ -1042,6 +1060,9 @@ class MetaAvatarRender(nn.Module):
                 verts, faces, V = res["verts"].contiguous(), res["faces"], res["n_verts"]
             if simplify is not None:
                 res.update(geometry.apply_simplify(verts, faces, simplify))
+                verts, faces, V = res["verts"].contiguous(), res["faces"], res["n_verts"]
+            if subdivide is not None:
+                res.update(geometry.apply_subdivide(verts, faces, subdivide))
                 verts, faces, V = res["verts"].contiguous(), res["faces"], res["n_verts"]
             adjacency = None
             if smooth is not None:
@@ -1081,8 +1102,9 @@ class MetaAvatarRender(nn.Module):
         return res
 
     def render_mesh(self, inputs, height=512, width=512, n_side=256, space="posed", attributes=("color", "vertex_normal"), clean=None,
-                    simplify=None, smooth=None, view=None):
-        """An image of the body of frame `inputs` as an indexed mesh: `canonical_mesh(inputs, n_side, clean=, simplify=, smooth=)`
+                    simplify=None, smooth=None, view=None, subdivide=None):
+        """An image of the body of frame `inputs` as an indexed mesh: `canonical_mesh(inputs, n_side, clean=, simplify=, smooth=,
+        subdivide=)`
         with "verts_posed" and the attributes named, drawn by geometry.render_mesh (hip.mesh_rasterize, hip.mesh_interpolate).
         space="posed": the skinned vertices through the frame's own camera (cam_rot, cam_trans, intrinsics of batch element 0);
         space="canonical": the canonical vertices through `view`, a look-at camera {"azim": degrees (0 front, 180 back)[, "dist",
@@ -1120,7 +1142,8 @@ class MetaAvatarRender(nn.Module):
                 raise ValueError("render_mesh: view must be a look-at camera {'azim': degrees[, 'dist', 'fov', 'at']}")
         own = ("vertex_normal", "face_normal", "ambient_occlusion")   # taken from the mesh that is drawn
         wanted = {a for a in attributes if a not in own} | ({"verts_posed"} if space == "posed" else set())
-        mesh = self.canonical_mesh(inputs, n_side=n_side, attributes=tuple(sorted(wanted)), clean=clean, simplify=simplify, smooth=smooth)
+        mesh = self.canonical_mesh(inputs, n_side=n_side, attributes=tuple(sorted(wanted)), clean=clean, simplify=simplify, smooth=smooth,
+                                   subdivide=subdivide)
         verts = mesh["verts_posed"] if space == "posed" else mesh["verts"]
         draw = {a: (True if a in own else mesh[a]) for a in attributes}
         if "ambient_occlusion" in draw:
@@ -1167,9 +1190,10 @@ class MetaAvatarRender(nn.Module):
         res["mesh"] = mesh
         return res
 
-    def mesh_intersections(self, inputs, n_side=256, space="posed", clean=None, simplify=None, smooth=None, max_pairs=1 << 20):
+    def mesh_intersections(self, inputs, n_side=256, space="posed", clean=None, simplify=None, smooth=None, max_pairs=1 << 20,
+                           subdivide=None):
         """Where the body of frame `inputs` passes through itself, as an indexed mesh -- the mesh `render_mesh` draws and `cast_rays`
-        sees: `canonical_mesh(inputs, n_side, clean=, simplify=, smooth=)`, skinned forward ("verts_posed") for space="posed", as it is
+        sees: `canonical_mesh(inputs, n_side, clean=, simplify=, smooth=, subdivide=)`, skinned forward ("verts_posed") for space="posed", as it is
         for space="canonical".  Linear blend skinning pushes the surface through itself at bent elbows, armpits and thighs; ray hits,
         occlusion, parity containment and signed distances are wrong there.  -> the dict of geometry.self_intersections (count,
         faces_hit, hits, vert_hit, pairs, void_faces, truncated, embedded, ...) plus "mesh", the dict of canonical_mesh.  vert_hit
@@ -1180,7 +1204,7 @@ class MetaAvatarRender(nn.Module):
         if space not in ("posed", "canonical"):
             raise ValueError("mesh_intersections: space must be 'posed' or 'canonical', got %r" % (space,))
         mesh = self.canonical_mesh(inputs, n_side=n_side, attributes=("verts_posed",) if space == "posed" else (), clean=clean,
-                                   simplify=simplify, smooth=smooth)
+                                   simplify=simplify, smooth=smooth, subdivide=subdivide)
         verts = mesh["verts_posed"] if space == "posed" else mesh["verts"]
         res = geometry.self_intersections(verts, mesh["faces"], max_pairs=max_pairs)
         res["mesh"] = mesh

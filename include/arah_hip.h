@@ -36,6 +36,7 @@
  *   arah_mesh_simplify      (none: vertex clustering of an indexed mesh on a grid: decimation and welding by position)
  *   arah_mesh_quadric_place (none: the clusters of arah_mesh_simplify moved to the minimisers of their faces' plane quadrics)
  *   arah_mesh_collapse_round (none: one round of edge-collapse decimation that keeps the surface a surface)
+ *   arah_mesh_subdivide_round (none: one round of midpoint or Loop subdivision, of every edge or of the long ones)
  *   arah_mesh_adjacency /   (none: the reference's users smooth and re-normal with trimesh / open3d / pytorch3d; the incident faces
  *   arah_mesh_vertex_normals /  and unique neighbours of every vertex with edge statistics, pytorch3d's verts_normals_packed over
  *   arah_mesh_smooth        them, and Laplacian / Taubin umbrella smoothing)
@@ -446,6 +447,31 @@ int arah_mesh_collapse_round(const float* verts, int64_t n_verts, const int32_t*
                              float max_cost, float* verts_out, int32_t* faces_out, int32_t* vert_src, int32_t* face_src,
                              int32_t* counts, float* edge_pos, uint64_t* edge_key, uint8_t* edge_reason, void* scratch,
                              size_t scratch_bytes, void* stream);
+/* One round of subdivision of an indexed mesh (csrc/meshsubdiv.hpp).  verts [n_verts][3], faces [n_faces][3] vertex ids; the
+ * adjacency of the mesh is built inside the call (arah_mesh_adjacency's launches, in this call's scratch).  The neighbour entry
+ * (lo, hi) with hi > lo names an edge.  has_threshold = 0: every edge is marked; otherwise an edge is marked when both ends are
+ * finite and (dx dx + dy dy) + dz dz > max_len2 in float64, every operation rounded on its own.  The k-th marked edge in entry
+ * order becomes vertex n_verts + k; old vertices keep their ids.  method 0 (midpoint): old vertices are copied, a new one is
+ * float32((lo + hi) 0.5), or the bits of its lowest non-finite end.  method 1 (Loop, Warren's weights; has_threshold must be 0):
+ * a new vertex on an edge with one face each way and a finite stencil is float32((lo + hi) 0.375 + (c + d) 0.125), c and d the
+ * third corners of the faces traversing lo->hi and hi->lo, every other one the midpoint; a finite old vertex whose k edges all
+ * have one face each way and whose neighbours are finite moves to float32(p (1 - k beta) + s beta), s the sum of the neighbours in
+ * ascending id, beta = 3/16 for k = 3 and 3 / (8 k) otherwise; a finite old vertex with exactly two one-face edges, finite
+ * neighbours b0 < b1 across them and every other edge one face each way moves to float32(p 0.75 + (b0 + b1) 0.125); the others
+ * stay.  A valid face with m marked edges becomes 1 + m faces in its orientation and the input's order (the templates of
+ * meshing.mesh_subdivide_round; the quad of the two-mark template is cut along its shorter diagonal on the output positions,
+ * ties to x-c); an invalid face is copied.  -> verts_out [n_verts + 3 n_faces][3], vert_src [n_verts + 3 n_faces][2] ((v, v) or
+ * (lo, hi)), faces_out [4 n_faces][3], face_src [4 n_faces] (rows past the counts ZERO); counts (device int32[13]) = vertices
+ * out, faces out, edges, marked edges, faces with 0 / 1 / 2 / 3 marks, invalid faces, marked edges with a non-finite end,
+ * interior vertices moved, rim vertices moved, vertices kept.  No atomics besides the adjacency's: the result is unique, and
+ * equal to meshing.mesh_subdivide_round bit for bit.  n_faces <= 2^26 and n_verts + 3 n_faces < 2^31, method 0 or 1, max_len2
+ * >= 0 (infinity: nothing is marked), otherwise ARAH_E_BADARG without a launch and a scratch size of 0; scratch:
+ * arah_mesh_subdivide_round_scratch_bytes(n_verts, n_faces) device bytes, 256-byte aligned, ARAH_E_WORKSPACE when short, without
+ * a launch.  Empty inputs still write counts; pointers of empty arrays may be NULL.  No host synchronisation, no allocation. */
+size_t arah_mesh_subdivide_round_scratch_bytes(int64_t n_verts, int64_t n_faces);
+int arah_mesh_subdivide_round(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t method,
+                              int32_t has_threshold, double max_len2, float* verts_out, int32_t* faces_out, int32_t* vert_src,
+                              int32_t* face_src, int32_t* counts, void* scratch, size_t scratch_bytes, void* stream);
 /* Per-vertex normals of an indexed mesh from the mesh itself (pytorch3d verts_normals_packed): verts [n_verts][3], faces
  * [n_faces][3], vf_start / vf of arah_mesh_adjacency on the same mesh.  Vertex v walks its incident faces in the order of vf
  * (ascending id); a face with a non-finite corner contributes nothing, the others (p1 - p0) x (p2 - p0) with the corners widened to
