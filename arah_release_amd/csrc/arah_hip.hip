@@ -1958,6 +1958,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_canon_solve(FrameDev fr, const 
 #include "meshquadric.hpp"
 #include "meshcollapse.hpp"
 #include "meshsubdiv.hpp"
+#include "meshflip.hpp"
 #include "meshorient.hpp"
 #include "meshraster.hpp"
 #include "canon_wave.hpp"
@@ -4669,12 +4670,14 @@ size_t arah_mesh_collapse_round_scratch_bytes(int64_t n_verts, int64_t n_faces) 
     return carve_collapse(nullptr, n_verts, n_faces).bytes;
 }
 
-int arah_mesh_collapse_round(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t need, double reg,
-                             float max_cost, float* verts_out, int32_t* faces_out, int32_t* vert_src, int32_t* face_src,
-                             int32_t* counts, float* edge_pos, uint64_t* edge_key, uint8_t* edge_reason, void* scratch,
-                             size_t scratch_bytes, void* stream) {
+// both entries: bounded = 0 is arah_mesh_collapse_round, twelve counts; 1 the bounded one, fourteen
+static int collapse_round(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t need, double reg,
+                          float max_cost, int bounded, double short_len2, double long_len2, float* verts_out, int32_t* faces_out,
+                          int32_t* vert_src, int32_t* face_src, int32_t* counts, float* edge_pos, uint64_t* edge_key,
+                          uint8_t* edge_reason, void* scratch, size_t scratch_bytes, void* stream) {
     if (!ma_sizes_ok(n_verts, n_faces) || !counts || !scratch || need < 0) return ARAH_E_BADARG;
     if (!std::isfinite(reg) || !(reg >= 0.0) || !(max_cost >= 0.0f)) return ARAH_E_BADARG;
+    if (bounded && (!(short_len2 >= 0.0) || !(long_len2 >= 0.0))) return ARAH_E_BADARG;
     if ((n_verts > 0 && (!verts || !verts_out || !vert_src)) || (n_faces > 0 && (!faces || !faces_out || !face_src || !edge_pos || !edge_key || !edge_reason)))
         return ARAH_E_BADARG;
     const MxScratch w = carve_collapse(scratch, n_verts, n_faces);
@@ -4687,11 +4690,11 @@ int arah_mesh_collapse_round(const float* verts, int64_t n_verts, const int32_t*
                                      w.acounts, w.adjacency, w.adjacency_bytes, stream))
         return rc;
     hipLaunchKernelGGL(k_mx_pin, gv, tb, 0, s, verts, V, (const int*)w.nbr_start, (const int*)w.nbr_out, (const int*)w.nbr_in, w.pinned,
-                       w.owner, w.m1, w.merge_to, w.move_edge, w.vsrc, (int*)counts);
+                       w.owner, w.m1, w.merge_to, w.move_edge, w.vsrc, (int*)counts, bounded ? kMxBoundedCounts : kMxCounts);
     if (F > 0)
         hipLaunchKernelGGL(k_mx_edge, dim3(mesh_grid(cap)), tb, 0, s, verts, (const int*)faces, V, cap, (const int*)w.vf_start,
                            (const int*)w.vf, (const int*)w.nbr_start, (const int*)w.nbr, (const unsigned char*)w.pinned,
-                           (const int*)w.owner, reg, max_cost, edge_pos, (unsigned long long*)edge_key, (unsigned char*)edge_reason,
+                           (const int*)w.owner, reg, max_cost, bounded, short_len2, long_len2, edge_pos, (unsigned long long*)edge_key, (unsigned char*)edge_reason,
                            w.m1, (int*)counts);
     hipLaunchKernelGGL(k_mx_m2, gv, tb, 0, s, V, (const int*)w.nbr_start, (const int*)w.nbr, (const unsigned long long*)w.m1, w.m2);
     if (F > 0)
@@ -4714,6 +4717,85 @@ int arah_mesh_collapse_round(const float* verts, int64_t n_verts, const int32_t*
                                (int*)face_src);
         });
     hipLaunchKernelGGL(k_mx_finish, dim3(1), dim3(64), 0, s, (int*)counts, (int)need);
+    return check_launch();
+}
+
+int arah_mesh_collapse_round(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t need, double reg,
+                             float max_cost, float* verts_out, int32_t* faces_out, int32_t* vert_src, int32_t* face_src,
+                             int32_t* counts, float* edge_pos, uint64_t* edge_key, uint8_t* edge_reason, void* scratch,
+                             size_t scratch_bytes, void* stream) {
+    return collapse_round(verts, n_verts, faces, n_faces, need, reg, max_cost, 0, 0.0, 0.0, verts_out, faces_out, vert_src, face_src, counts,
+                          edge_pos, edge_key, edge_reason, scratch, scratch_bytes, stream);
+}
+
+int arah_mesh_collapse_round_bounded(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t need, double reg,
+                                     float max_cost, double short_len2, double long_len2, float* verts_out, int32_t* faces_out,
+                                     int32_t* vert_src, int32_t* face_src, int32_t* counts, float* edge_pos, uint64_t* edge_key,
+                                     uint8_t* edge_reason, void* scratch, size_t scratch_bytes, void* stream) {
+    return collapse_round(verts, n_verts, faces, n_faces, need, reg, max_cost, 1, short_len2, long_len2, verts_out, faces_out, vert_src,
+                          face_src, counts, edge_pos, edge_key, edge_reason, scratch, scratch_bytes, stream);
+}
+
+// ---- one round of edge flips (csrc/meshflip.hpp) -------------------------------------------------------------------------------------
+struct MeshFlipScratch {
+    int *vf_start, *vf, *nbr_start, *nbr, *nbr_out, *nbr_in, *acounts;
+    unsigned char* vert_flags;
+    int* owner;
+    unsigned long long* lock;
+    void* adjacency;
+    size_t adjacency_bytes, bytes;
+};
+
+static MeshFlipScratch carve_flip(void* scratch, int64_t n_verts, int64_t n_faces) {
+    MeshFlipScratch w{};
+    MeshCarver c(scratch);
+    const size_t V = (size_t)n_verts, F = (size_t)n_faces;
+    w.vf_start = c.take<int>(V + 1);
+    w.vf = c.take<int>(3 * F);
+    w.nbr_start = c.take<int>(V + 1);
+    w.nbr = c.take<int>(6 * F);
+    w.nbr_out = c.take<int>(6 * F);
+    w.nbr_in = c.take<int>(6 * F);
+    w.acounts = c.take<int>(8);
+    w.vert_flags = c.take<unsigned char>(V);
+    w.owner = c.take<int>(6 * F);
+    w.lock = c.take<unsigned long long>(V);
+    w.adjacency_bytes = carve_adjacency(nullptr, n_verts, n_faces).bytes;
+    w.adjacency = c.take<char>(w.adjacency_bytes);
+    w.bytes = c.bytes();
+    return w;
+}
+
+size_t arah_mesh_flip_round_scratch_bytes(int64_t n_verts, int64_t n_faces) {
+    if (!ma_sizes_ok(n_verts, n_faces)) return 0;
+    return carve_flip(nullptr, n_verts, n_faces).bytes;
+}
+
+int arah_mesh_flip_round(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t criterion, uint32_t salt,
+                         int32_t* faces_out, uint8_t* face_flag, int32_t* counts, uint64_t* edge_key, uint8_t* edge_reason,
+                         void* scratch, size_t scratch_bytes, void* stream) {
+    if (!ma_sizes_ok(n_verts, n_faces) || !counts || !scratch || (criterion != 0 && criterion != kMfValence)) return ARAH_E_BADARG;
+    if ((n_verts > 0 && !verts) || (n_faces > 0 && (!faces || !faces_out || !face_flag || !edge_key || !edge_reason))) return ARAH_E_BADARG;
+    const MeshFlipScratch w = carve_flip(scratch, n_verts, n_faces);
+    if (scratch_bytes < w.bytes) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int V = (int)n_verts, F = (int)n_faces, cap = 6 * F;
+    const dim3 tb(kImeshThreads);
+    // an empty mesh runs the adjacency's launches and k_mf_init over nothing: the counts are cleared, nbr_start[V] = 0
+    if (int rc = arah_mesh_adjacency(faces, n_faces, n_verts, w.vf_start, w.vf, w.nbr_start, w.nbr, w.nbr_out, w.nbr_in, w.vert_flags,
+                                     w.acounts, w.adjacency, w.adjacency_bytes, stream))
+        return rc;
+    hipLaunchKernelGGL(k_mf_init, dim3(mesh_grid(std::max(n_verts, n_faces))), tb, 0, s, (const int*)faces, F, V, (const int*)w.nbr_start,
+                       w.owner, w.lock, (int*)faces_out, (unsigned char*)face_flag, (int*)counts);
+    if (F > 0) {   // without a vertex nbr_start[0] = 0: no entry names an edge, and no vertex is read
+        hipLaunchKernelGGL(k_mf_edge, dim3(mesh_grid(cap)), tb, 0, s, verts, (const int*)faces, V, cap, (const int*)w.vf_start,
+                           (const int*)w.vf, (const int*)w.nbr_start, (const int*)w.nbr, (const int*)w.nbr_out, (const int*)w.nbr_in,
+                           (const unsigned char*)w.vert_flags, (const int*)w.owner, (int)criterion, (unsigned)(salt * 0x9e3779b9u),
+                           (unsigned long long*)edge_key, (unsigned char*)edge_reason, w.lock, (int*)counts);
+        hipLaunchKernelGGL(k_mf_apply, dim3(mesh_grid(cap)), tb, 0, s, (const int*)faces, V, cap, (const int*)w.vf_start, (const int*)w.vf,
+                           (const int*)w.nbr_start, (const int*)w.nbr, (const int*)w.owner, (const unsigned long long*)edge_key,
+                           (const unsigned long long*)w.lock, (int*)faces_out, (unsigned char*)face_flag, (int*)counts);
+    }
     return check_launch();
 }
 
@@ -4841,6 +4923,17 @@ int arah_mesh_smooth(const float* verts, int64_t n_verts, const int32_t* nbr_sta
                            (const unsigned char*)vert_flags, (double)factors[i & 1], (int)(pin != 0), dst);
         src = dst;
     }
+    return check_launch();
+}
+
+int arah_mesh_tangential(const float* verts, int64_t n_verts, const int32_t* nbr_start, const int32_t* nbr, const uint8_t* vert_flags,
+                         const double* normal_sum, float factor, float* verts_out, void* stream) {
+    if (n_verts < 0 || n_verts > (int64_t)INT32_MAX || !nbr_start || !std::isfinite(factor)) return ARAH_E_BADARG;
+    if (n_verts > 0 && (!verts || !verts_out || !vert_flags || !normal_sum)) return ARAH_E_BADARG;
+    if (n_verts == 0) return ARAH_OK;
+    hipLaunchKernelGGL(k_ma_tangential, dim3(mesh_grid(n_verts)), dim3(kImeshThreads), 0, reinterpret_cast<hipStream_t>(stream), verts,
+                       (int)n_verts, (const int*)nbr_start, (const int*)nbr, (const unsigned char*)vert_flags, normal_sum, (double)factor,
+                       verts_out);
     return check_launch();
 }
 

@@ -1,5 +1,5 @@
-// meshadj.hpp -- adjacency of an indexed mesh on the device, and the two gathers that run over it: per-vertex normals and umbrella
-// (Laplacian / Taubin) smoothing.
+// meshadj.hpp -- adjacency of an indexed mesh on the device, and the gathers that run over it: per-vertex normals, umbrella
+// (Laplacian / Taubin) smoothing, and the tangential step of the isotropic remesher (k_ma_tangential, arah_mesh_tangential).
 //
 // Reference: none in its tree.  The reference's users smooth and re-normal their meshes with trimesh / open3d / pytorch3d
 // (Meshes.verts_normals_packed: the area-weighted sum of the incident faces' cross products, the definition taken here); none of
@@ -12,7 +12,9 @@
 //   * nbr: the UNIQUE neighbours of every vertex as a CSR, ids ascending, with the number of faces traversing v->n (nbr_out) and
 //     n->v (nbr_in); an undirected edge is seen once, from its lower end (n > v), with nbr_out + nbr_in faces on it;
 //   * normals: float64 cross products summed per vertex in ascending face id, contraction off -- a gather, no atomics;
-//   * smoothing: float64 sums of the finite neighbours in ascending id, contraction off, two buffers -- a gather, no atomics.
+//   * smoothing: float64 sums of the finite neighbours in ascending id, contraction off, two buffers -- a gather, no atomics;
+//   * the tangential step: the same sums, then the move minus its part along the vertex's normal_sum, by one division and no square
+//     root (meshing.mesh_tangential_step) -- a gather, no atomics.
 //
 // arah_mesh_adjacency, one launch per line:
 //
@@ -283,6 +285,51 @@ __global__ __launch_bounds__(kImeshThreads) void k_ma_smooth(const float* __rest
                     const double pa = (double)p[a];
                     out[a] = (float)(pa + factor * (s[a] / (double)m - pa));
                 }
+            }
+        }
+        dst[3 * v + 0] = out[0];
+        dst[3 * v + 1] = out[1];
+        dst[3 * v + 2] = out[2];
+    }
+}
+
+// ---- one step of tangential relaxation: k_ma_smooth's gather, the move without its part along the vertex normal ----------------
+// A vertex moves when it is finite, not on a boundary or non-manifold edge, has a finite neighbour, and nn = (N0 N0 + N1 N1) +
+// N2 N2 of its normal_sum N (arah_mesh_vertex_normals' double output) is finite and > 0: d = s / m - p as above, t = ((d0 N0 +
+// d1 N1) + d2 N2) / nn, new = float(p + factor (d - t N)).  No square root.  meshing.mesh_tangential_step is the rule.
+__global__ __launch_bounds__(kImeshThreads) void k_ma_tangential(const float* __restrict__ src, int n_verts, const int* __restrict__ nbr_start,
+                                                                 const int* __restrict__ nbr, const unsigned char* __restrict__ vert_flags,
+                                                                 const double* __restrict__ normal_sum, double factor,
+                                                                 float* __restrict__ dst) {
+#pragma clang fp contract(off)
+    const long long step = (long long)gridDim.x * blockDim.x;
+    // terminates: n_verts - v strictly decreases (step >= 1) and the loop ends when it reaches 0
+    for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < n_verts; v += step) {
+        const float p[3] = {src[3 * v + 0], src[3 * v + 1], src[3 * v + 2]};
+        float out[3] = {p[0], p[1], p[2]};
+        const double N[3] = {normal_sum[3 * v + 0], normal_sum[3 * v + 1], normal_sum[3 * v + 2]};
+        const double nn = (N[0] * N[0] + N[1] * N[1]) + N[2] * N[2];
+        if (isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) && !(vert_flags[v] & 3) && isfinite(nn) && nn > 0.0) {
+            double s[3] = {0.0, 0.0, 0.0};
+            int m = 0;
+            const long long last = nbr_start[v + 1];
+            for (long long i = nbr_start[v]; i < last; ++i) {   // terminates: last - i strictly decreases
+                const int n = nbr[i];
+                if ((unsigned)n >= (unsigned)n_verts) continue;   // nbr is the caller's: never followed out of bounds
+                const float q[3] = {src[3 * (size_t)n + 0], src[3 * (size_t)n + 1], src[3 * (size_t)n + 2]};
+                if (!(isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]))) continue;
+                s[0] = s[0] + (double)q[0];
+                s[1] = s[1] + (double)q[1];
+                s[2] = s[2] + (double)q[2];
+                ++m;
+            }
+            if (m > 0) {
+                double d[3];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) d[a] = s[a] / (double)m - (double)p[a];
+                const double t = ((d[0] * N[0] + d[1] * N[1]) + d[2] * N[2]) / nn;
+#pragma unroll
+                for (int a = 0; a < 3; ++a) out[a] = (float)((double)p[a] + factor * (d[a] - t * N[a]));
             }
         }
         dst[3 * v + 0] = out[0];

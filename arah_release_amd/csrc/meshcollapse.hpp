@@ -38,6 +38,13 @@
 // Integer atomics only (min, add).  No thread waits for another: no spin-wait, no grid-wide barrier; every loop ends by an
 // argument of its own, stated at the loop.
 //
+// arah_mesh_collapse_round_bounded runs the same launches with `bounded` set, for the isotropic remesher (meshflip.hpp tells the
+// rest): k_mx_edge then refuses, BEFORE every other test, an edge whose squared length in double is not below short_len2 (reason
+// 7), and, after the flip test and inside its merge, an edge with a ring vertex -- a corner other than u, v of a face that names
+// one of them -- farther than long_len2 (squared) from the new position (reason 8); k_mx_pin clears fourteen counts instead of
+// twelve, and the two reasons are counted at 12 and 13.  Without `bounded` neither test runs and no count beyond the twelfth is
+// touched: arah_mesh_collapse_round is what it was.
+//
 // NOT MEASURED AGAINST AN ALTERNATIVE: one lane per edge (its tree keeps 6 x 10 doubles of partial sums in registers, which
 // bounds the occupancy, and the lanes of a wave diverge on the reason and on the segment lengths; a wave per edge with the ten
 // columns spread over lanes is the alternative); streaming the merge of the two face segments three times from the cache
@@ -49,6 +56,7 @@
 constexpr unsigned long long kMxEmpty = ~0ull;   // no key: a key's upper half is the bits of a non-negative finite float
 constexpr int kMxNoEdge = 255;                   // edge_reason of an entry that names no edge
 constexpr int kMxCounts = 12;                    // n_verts, n_faces, selected, applied, candidates, six reasons, fallbacks
+constexpr int kMxBoundedCounts = 14;             // arah_mesh_collapse_round_bounded: and the reasons 7 (not short) and 8 (too long)
 
 // The merge of two ascending lists without repeats: the values of both, ascending, each once.
 struct MxMerge {
@@ -86,6 +94,15 @@ __device__ __forceinline__ void mx_cross(const double p[3][3], double n[3]) {
     n[2] = e1[0] * e2[1] - e1[1] * e2[0];
 }
 
+// the squared length of the edge {u, v} in double, summed left to right
+__device__ __forceinline__ double mx_len2(const float* __restrict__ verts, int u, int v) {
+#pragma clang fp contract(off)
+    const double dx = (double)verts[3 * (size_t)u + 0] - (double)verts[3 * (size_t)v + 0];
+    const double dy = (double)verts[3 * (size_t)u + 1] - (double)verts[3 * (size_t)v + 1];
+    const double dz = (double)verts[3 * (size_t)u + 2] - (double)verts[3 * (size_t)v + 2];
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
 // float32 of the squared distance of vertex x to pos, evaluated in double
 __device__ __forceinline__ float mx_d2(const float* __restrict__ verts, int x, const float pos[3]) {
 #pragma clang fp contract(off)
@@ -99,8 +116,9 @@ __global__ __launch_bounds__(kImeshThreads) void k_mx_pin(const float* __restric
                                                           const int* __restrict__ nbr_out, const int* __restrict__ nbr_in,
                                                           unsigned char* __restrict__ pinned, int* __restrict__ owner,
                                                           unsigned long long* __restrict__ m1, int* __restrict__ merge_to,
-                                                          int* __restrict__ move_edge, int* __restrict__ vsrc, int* __restrict__ counts) {
-    if (blockIdx.x == 0 && threadIdx.x < kMxCounts) counts[threadIdx.x] = 0;
+                                                          int* __restrict__ move_edge, int* __restrict__ vsrc, int* __restrict__ counts,
+                                                          int n_counts) {
+    if (blockIdx.x == 0 && threadIdx.x < n_counts) counts[threadIdx.x] = 0;
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_verts - v strictly decreases (step >= 1) and the loop ends when it reaches 0
     for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < n_verts; v += step) {
@@ -122,7 +140,8 @@ __global__ __launch_bounds__(kImeshThreads) void k_mx_edge(const float* __restri
                                                            int n_entries_cap, const int* __restrict__ vf_start, const int* __restrict__ vf,
                                                            const int* __restrict__ nbr_start, const int* __restrict__ nbr,
                                                            const unsigned char* __restrict__ pinned, const int* __restrict__ owner,
-                                                           double reg, float max_cost, float* __restrict__ edge_pos,
+                                                           double reg, float max_cost, int bounded, double short_len2,
+                                                           double long_len2, float* __restrict__ edge_pos,
                                                            unsigned long long* __restrict__ edge_key, unsigned char* __restrict__ edge_reason,
                                                            unsigned long long* m1, int* counts) {
 #pragma clang fp contract(off)
@@ -138,7 +157,9 @@ __global__ __launch_bounds__(kImeshThreads) void k_mx_edge(const float* __restri
         unsigned long long key = kMxEmpty;
         if (is_edge) {
             const int u = owner[i], v = nbr[i];
-            if (pinned[u] || pinned[v]) {
+            if (bounded && !(mx_len2(verts, u, v) < short_len2)) {   // the bounded entry's first test; not a number: refused
+                reason = 7;
+            } else if (pinned[u] || pinned[v]) {
                 reason = 1;
             } else {
                 bool both;
@@ -193,7 +214,7 @@ __global__ __launch_bounds__(kImeshThreads) void k_mx_edge(const float* __restri
                         reason = 5;
                     } else {
                         const double pn[3] = {(double)pos[0], (double)pos[1], (double)pos[2]};
-                        bool flipped = false;
+                        bool flipped = false, far = false;
                         w = mx_merge(vf, vf_start, u, v);
                         while (mx_more(w)) {   // terminates: as above
                             const int f = mx_next(w, both);
@@ -206,6 +227,10 @@ __global__ __launch_bounds__(kImeshThreads) void k_mx_edge(const float* __restri
                                 moves = (id == u || id == v) ? c : moves;
 #pragma unroll
                                 for (int x = 0; x < 3; ++x) p[c][x] = (double)verts[3 * (size_t)id + x];
+                                if (bounded && id != u && id != v) {   // a vertex of the ring: how far from the new position
+                                    const double dx = p[c][0] - pn[0], dy = p[c][1] - pn[1], dz = p[c][2] - pn[2];
+                                    far = far || (dx * dx + dy * dy) + dz * dz > long_len2;
+                                }
                             }
                             mx_cross(p, n0);
 #pragma unroll
@@ -218,6 +243,8 @@ __global__ __launch_bounds__(kImeshThreads) void k_mx_edge(const float* __restri
                         }
                         if (flipped) {
                             reason = 6;
+                        } else if (far) {
+                            reason = 8;
                         } else {   // cost32 >= +0 and finite: its bits order like the number
                             key = ((unsigned long long)__float_as_uint(cost32) << 32) | (unsigned long long)i;
                             atomicMin(&m1[u], key);
@@ -234,7 +261,7 @@ __global__ __launch_bounds__(kImeshThreads) void k_mx_edge(const float* __restri
             edge_key[i] = key;
             edge_reason[i] = (unsigned char)(is_edge ? reason : kMxNoEdge);
         }
-        cc_add_one(counts + 4, reason, is_edge);   // reason <= 6: counts[4 .. 10]
+        cc_add_one(counts, reason <= 6 ? 4 + reason : 5 + reason, is_edge);   // reason <= 6: counts[4 .. 10]; 7, 8 (bounded): 12, 13
         cc_add_one(counts + 11, 0, fell);
     }
 }

@@ -960,6 +960,288 @@ def apply_subdivide(verts, faces, subdivide):
     return out
 
 
+# ---- edge flips -------------------------------------------------------------------------------------------------------------------------
+_FLIP_SUMS = ("not_interior", "same_corner", "exists", "nonfinite", "criterion", "normals")
+
+
+def flip_edges(verts, faces, criterion="delaunay", max_rounds=64):
+    """Flip edges of an indexed mesh (verts (V,3), faces (F,3) integer ids) until none asks for it: rounds of `mesh_flip_round`
+    (arah_mesh_flip_round on the GPU, meshing.mesh_flip_round on the host, equal bit for bit).  A flip replaces the edge {u, v}
+    between the faces (u, v, a) and (v, u, b) by {a, b} between (a, u, b) and (b, v, a): vertices, the face count, the faces'
+    order and the topology stay.  Only an edge with one face each way whose flipped edge is not there yet and whose new faces
+    look the way the old ones did can flip, so boundary, non-manifold and misoriented edges and edges at a non-finite vertex
+    never do.
+
+        criterion   "delaunay": an edge flips when the two angles opposite to it sum to more than pi (cot + cot < 0, decided
+                    without a square root) -- on a planar triangulation the loop ends at the Delaunay triangulation;
+                    "valence": when it lowers the sum of |valence - target| over the four vertices around it, target 6, or 4
+                    on a boundary
+        max_rounds  the most rounds
+
+    Round r runs with salt = r: a round flips the candidates that hold the least hashed key at all four of their vertices, and
+    the hash changes with the round.  The loop ends after a round WITHOUT A CANDIDATE (converged), or after max_rounds.  ONE
+    host synchronisation per round (its counts).
+
+    -> dict of faces (F,3) in the dtype of `faces`, rounds (the rounds run, the last, empty one included), converged, flips (the
+    flips applied), candidates (per round) and the rounds' summed counts not_interior, same_corner, exists, nonfinite, criterion
+    and normals (edges that were no candidates, by their first reason)."""
+    from . import meshing
+    meshing.flip_args(criterion, 0, "flip_edges")
+    if isinstance(max_rounds, bool) or not isinstance(max_rounds, (int, np.integer)) or int(max_rounds) < 0:
+        raise ValueError("flip_edges: max_rounds must be an integer >= 0, got %r" % (max_rounds,))
+    n_verts, faces = _mesh_args(verts, faces, "flip_edges")
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or not verts.dtype.is_floating_point:
+        raise ValueError("flip_edges: verts must be a floating-point (V, 3) tensor")
+    if verts.device != faces.device:
+        raise ValueError("flip_edges: verts live on %s, faces on %s" % (verts.device, faces.device))
+    backend, names = _cc_backend(faces), meshing.FLIP_COUNTS
+    with torch.no_grad():
+        v, f = verts.detach().to(torch.float32).contiguous(), faces
+        sums, history, flips, rounds, converged = dict.fromkeys(_FLIP_SUMS, 0), [], 0, 0, False
+        while rounds < int(max_rounds) and not converged:
+            out = backend.mesh_flip_round(v, f, criterion, rounds)
+            c = dict(zip(names, out[2].tolist()))                                 # the host synchronisation
+            rounds += 1
+            history.append(c["candidates"])
+            for k in _FLIP_SUMS:
+                sums[k] += c[k]
+            flips += c["selected"]
+            converged = c["candidates"] == 0
+            if not converged:
+                f = out[0]
+    return dict(sums, faces=f.to(faces.dtype), rounds=rounds, converged=converged, flips=flips, candidates=history)
+
+
+# ---- isotropic remeshing and its yardstick --------------------------------------------------------------------------------------
+_ISOTROPIC_KEYS = ("edge_length", "iterations", "lamb", "project", "max_rounds", "max_faces")
+
+
+def _valid_faces(verts, faces):
+    """The faces with three different ids in [0, V), as int64 on the host, and the vertices as float64 on the host."""
+    f = faces.detach().cpu().long().reshape(-1, 3)
+    V = int(verts.shape[0])
+    ok = ((f >= 0) & (f < V)).all(1) & (f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 0] != f[:, 2])
+    return verts.detach().cpu().double(), f[ok]
+
+
+def _edge_lengths(p, f):
+    """The lengths of the undirected edges of the valid faces f over the float64 positions p, on the host, in ascending (lo, hi)."""
+    V = max(int(p.shape[0]), 1)
+    e = torch.cat([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
+    key = torch.unique(e.min(1).values * V + e.max(1).values)
+    d = p[key // V] - p[key % V]
+    return torch.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+
+
+def mesh_quality(verts, faces, edge_length=None):
+    """How regular the triangles of an indexed mesh are: verts (V,3) floating point, faces (F,3) integer ids, edge_length the
+    target length (None: the mesh's own mean edge length).  Plain float64 tensor code ON THE HOST whatever the mesh's device (one
+    copy; the same mesh gives the same numbers from both), over the faces with three different ids in range and the finite
+    edges.  -> dict of Python numbers: n_verts, n_faces (the valid ones), n_edges, edge_length, edge_min / edge_mean / edge_max,
+    edges_in_range (the share of edges with a length in [4/5, 4/3] of edge_length), min_angle_min / min_angle_mean (degrees, of the
+    smallest angle of every face), small_angle_share (the share of faces with an angle below 30 degrees), valence6_share and
+    valence5to7_share (of the vertices that have a neighbour and lie on no boundary or non-manifold edge)."""
+    import math
+    n_verts, faces = _mesh_args(verts, faces, "mesh_quality")
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or not verts.dtype.is_floating_point:
+        raise ValueError("mesh_quality: verts must be a floating-point (V, 3) tensor")
+    if edge_length is not None and (isinstance(edge_length, bool) or not isinstance(edge_length, (int, float, np.integer, np.floating))
+                                    or not math.isfinite(float(edge_length)) or float(edge_length) <= 0.0):
+        raise ValueError("mesh_quality: edge_length must be a finite length > 0, got %r" % (edge_length,))
+    nan = float("nan")
+    with torch.no_grad():
+        p, f = _valid_faces(verts, faces)
+        length = _edge_lengths(p, f)
+        length = length[torch.isfinite(length)]
+        n_edges = int(length.shape[0])
+        L = float(edge_length) if edge_length is not None else (float(length.mean()) if n_edges else nan)
+        out = {"n_verts": n_verts, "n_faces": int(f.shape[0]), "n_edges": n_edges, "edge_length": L,
+               "edge_min": float(length.min()) if n_edges else nan, "edge_mean": float(length.mean()) if n_edges else nan,
+               "edge_max": float(length.max()) if n_edges else nan,
+               "edges_in_range": float(((length >= 0.8 * L) & (length <= 4.0 / 3.0 * L)).double().mean()) if n_edges else nan}
+        t = p[f]                                                                  # (F,3,3)
+        angles = []
+        for k in range(3):
+            a, b = t[:, (k + 1) % 3] - t[:, k], t[:, (k + 2) % 3] - t[:, k]
+            angles.append(torch.atan2(torch.linalg.cross(a, b).norm(dim=1), (a * b).sum(1)))
+        least = torch.stack(angles, 1).min(1).values * (180.0 / math.pi) if f.shape[0] else torch.zeros(0, dtype=torch.float64)
+        least = least[torch.isfinite(least)]
+        some = int(least.shape[0]) > 0
+        out.update({"min_angle_min": float(least.min()) if some else nan, "min_angle_mean": float(least.mean()) if some else nan,
+                    "small_angle_share": float((least < 30.0).double().mean()) if some else nan})
+        from . import meshing
+        adj = meshing.mesh_adjacency(f, n_verts)
+        deg = (adj[2][1:] - adj[2][:-1]).long()
+        inner = deg[(deg > 0) & ((adj[6] & 3) == 0)]
+        some = int(inner.shape[0]) > 0
+        out.update({"valence6_share": float((inner == 6).double().mean()) if some else nan,
+                    "valence5to7_share": float(((inner >= 5) & (inner <= 7)).double().mean()) if some else nan})
+    return out
+
+
+def check_isotropic(isotropic):
+    """The mesh entries' `isotropic` option, validated: None stays None, a number is the target edge length, a dict holds
+    keywords of `isotropic_remesh` (edge_length, iterations, lamb, project, max_rounds, max_faces).  -> the dict of keywords;
+    ValueError for anything else."""
+    import math
+    from . import meshing
+    if isotropic is None:
+        return None
+    if isinstance(isotropic, (int, float, np.integer, np.floating)) and not isinstance(isotropic, bool):
+        isotropic = {"edge_length": float(isotropic)}
+    if not isinstance(isotropic, dict):
+        raise ValueError("isotropic must be None, an edge length or a dict of isotropic_remesh keywords, got %r" % (isotropic,))
+    bad = set(isotropic) - set(_ISOTROPIC_KEYS)
+    if bad:
+        raise ValueError("isotropic: unknown keys %s (known: %s)" % (sorted(bad), ", ".join(_ISOTROPIC_KEYS)))
+    kw = dict(isotropic)
+    L = kw.get("edge_length")
+    if L is not None and (isinstance(L, bool) or not isinstance(L, (int, float, np.integer, np.floating)) or not math.isfinite(float(L))
+                          or float(L) <= 0.0):
+        raise ValueError("isotropic_remesh: edge_length must be a finite length > 0, got %r" % (L,))
+    for name, least in (("iterations", 0), ("max_rounds", 1), ("max_faces", 0)):
+        x = kw.get(name, least)
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or int(x) < least:
+            raise ValueError("isotropic_remesh: %s must be an integer >= %d, got %r" % (name, least, x))
+    meshing.check_tangential_lamb(kw.get("lamb", 0.5), "isotropic_remesh")
+    if not isinstance(kw.get("project", True), bool):
+        raise ValueError("isotropic_remesh: project must be True or False, got %r" % (kw["project"],))
+    return kw
+
+
+def _closest_on_input(tris, index, pts):
+    """d2, face, closest of the float32 points against the input's soup: hip.mesh_closest on the GPU, its rule on the host."""
+    from . import meshing
+    if tris.is_cuda and int(tris.shape[0]) > 0:
+        from . import hip
+        return hip.mesh_closest(index, pts)[:3]
+    return meshing.soup_closest(tris, pts)
+
+
+def isotropic_remesh(verts, faces, edge_length=None, iterations=5, lamb=0.5, project=True, max_rounds=32, max_faces=1 << 24,
+                     attributes=None):
+    """Remesh an indexed mesh (verts (V,3), faces (F,3) integer ids) towards triangles of one size and vertices of valence six, after
+    Botsch and Kobbelt, "A remeshing approach to multiresolution modeling" (2004).  With L = edge_length (None: the input's mean
+    edge length), every one of the `iterations` does
+
+        1  split     rounds of `mesh_subdivide_round` on the edges longer than 4/3 L until a round marks none
+        2  collapse  rounds of `mesh_collapse_round` on the edges shorter than 4/5 L, refusing a collapse that would leave an edge
+                     longer than 4/3 L at the new vertex, until a round applies none
+        3  flip      `flip_edges(criterion="valence")` until no candidate is left
+        4  relax     one `mesh_tangential_step` with `lamb`, the normals taken from the mesh at hand
+        5  project   (project=True) every vertex moves to the closest point of the INPUT mesh, rounded once to float32; the index
+                     of the input is built once
+
+    each loop also ending after max_rounds rounds; a split round whose worst case, four times its faces, exceeds max_faces
+    raises.  Every step runs its kernels for a mesh on the GPU and its tensor specification for one on the host, equal bit for
+    bit, so the whole call is; one host synchronisation per round.  Boundary, non-manifold and misoriented edges are split but
+    never collapsed or flipped and their vertices are not relaxed: a closed manifold surface stays one.
+
+    -> dict of verts (V',3) float32, faces (F',3) in the dtype of `faces`, n_verts, n_tris, src_face (V',) int64 and src_bary
+    (V',3) float64 -- the closest input face of every output vertex and the barycentric weights of the closest point in it (-1
+    and NaN for a vertex that is not finite) --, every tensor of the dict `attributes` (first dimension V) carried over through
+    them: (w0 A0 + w1 A1) + w2 A2 in float64 rounded to the attribute's dtype when that is floating, the attribute of the corner
+    with the largest weight (the first of them) otherwise; and report = dict of edge_length, iterations (a list of dicts of
+    faces, splits, collapses and flips, one per iteration), and before / after, the `mesh_quality` of the input and of the
+    output against L."""
+    from . import meshing
+    kw = check_isotropic({"edge_length": edge_length, "iterations": iterations, "lamb": lamb, "project": project,
+                          "max_rounds": max_rounds, "max_faces": max_faces})
+    n_verts, faces = _mesh_args(verts, faces, "isotropic_remesh")
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or not verts.dtype.is_floating_point:
+        raise ValueError("isotropic_remesh: verts must be a floating-point (V, 3) tensor")
+    if verts.device != faces.device:
+        raise ValueError("isotropic_remesh: verts live on %s, faces on %s" % (verts.device, faces.device))
+    reserved = ("verts", "faces", "n_verts", "n_tris", "src_face", "src_bary", "report")
+    attributes = _repair_attributes(attributes, n_verts, verts.device, reserved, "isotropic_remesh")
+    backend, dev = _cc_backend(faces), verts.device
+    with torch.no_grad():
+        v0 = verts.detach().to(torch.float32).contiguous()
+        p64, valid = _valid_faces(v0, faces)
+        if edge_length is None:
+            length = _edge_lengths(p64, valid)
+            length = length[torch.isfinite(length)]
+            if int(length.shape[0]) == 0:
+                raise ValueError("isotropic_remesh: the mesh has no finite edge to take the target length from")
+            L = float(length.mean())
+        else:
+            L = float(edge_length)
+        long2, short2 = (4.0 / 3.0 * L) ** 2, (0.8 * L) ** 2
+        corners = valid.to(dev)
+        tris = v0[corners] if int(corners.shape[0]) else v0.new_zeros((0, 3, 3))
+        index = None
+        if tris.is_cuda and int(tris.shape[0]) > 0:
+            from . import hip
+            index = hip.mesh_index(tris)
+        before = mesh_quality(v0, faces, L)
+        v, f, steps = v0, faces, []
+        for _ in range(int(iterations)):
+            splits = collapses = 0
+            for _r in range(int(max_rounds)):
+                if 4 * int(f.shape[0]) > int(max_faces):
+                    raise ValueError("isotropic_remesh: a split round of %d faces gives up to %d faces, more than max_faces = %d"
+                                     % (int(f.shape[0]), 4 * int(f.shape[0]), int(max_faces)))
+                out = backend.mesh_subdivide_round(v, f, "midpoint", long2)
+                c = dict(zip(meshing.SUBDIVIDE_COUNTS, out[4].tolist()))              # the host synchronisation
+                if c["marked"] == 0:
+                    break
+                v, f, splits = out[0][:c["n_verts"]], out[1][:c["n_faces"]], splits + c["marked"]
+            for _r in range(int(max_rounds)):
+                out = backend.mesh_collapse_round(v, f, 2 ** 31 - 1, short_len2=short2, long_len2=long2)
+                c = dict(zip(meshing.COLLAPSE_BOUNDED_COUNTS, out[4].tolist()))       # the host synchronisation
+                if c["applied"] == 0:
+                    break
+                v, f, collapses = out[0][:c["n_verts"]], out[1][:c["n_faces"]], collapses + c["applied"]
+            flipped = flip_edges(v, f, "valence", int(max_rounds))
+            f = flipped["faces"]
+            adj = backend.mesh_adjacency(f, int(v.shape[0]))
+            v = backend.mesh_tangential_step(v, f, backend.vertex_normals(v, f, adjacency=adj)[0], lamb, adjacency=adj)
+            if project:
+                _, face, closest = _closest_on_input(tris, index, v)
+                v = torch.where((face >= 0)[:, None], closest.float(), v)
+            steps.append({"faces": int(f.shape[0]), "splits": splits, "collapses": collapses, "flips": flipped["flips"]})
+        _, face, closest = _closest_on_input(tris, index, v)
+        found = face >= 0
+        at = corners[face.long().clamp(min=0)] if int(corners.shape[0]) else torch.zeros(int(v.shape[0]), 3, dtype=torch.long, device=dev)
+        if int(corners.shape[0]):
+            a, b, c3 = (v0.double()[at[:, k]] for k in range(3))
+            bary = torch.stack(meshing.closest_on_triangles(v.double(), a, b, c3), 1)
+        else:
+            bary = torch.full((int(v.shape[0]), 3), float("nan"), dtype=torch.float64, device=dev)
+        bary = torch.where(found[:, None], bary, torch.full_like(bary, float("nan")))
+        # src_face counts the INPUT's rows, skipped faces included
+        rows = torch.nonzero(_valid_rows(faces, n_verts))[:, 0]
+        src_face = torch.where(found, rows[face.long().clamp(min=0)] if int(rows.shape[0]) else face.long(), torch.full_like(face.long(), -1))
+        res = {"verts": v, "faces": f.to(faces.dtype), "n_verts": int(v.shape[0]), "n_tris": int(f.shape[0]), "src_face": src_face,
+               "src_bary": bary,
+               "report": {"edge_length": L, "iterations": steps, "before": before, "after": mesh_quality(v, f, L)}}
+        for name, t in attributes.items():
+            A = t[at]                                                             # (V',3,...)
+            if t.dtype.is_floating_point:
+                w = bary.reshape(bary.shape + (1,) * (t.dim() - 1))
+                res[name] = ((w[:, 0] * A[:, 0].double() + w[:, 1] * A[:, 1].double()) + w[:, 2] * A[:, 2].double()).to(t.dtype)
+            else:
+                best = torch.where(found[:, None], bary, torch.zeros_like(bary)).argmax(1)
+                res[name] = A[torch.arange(int(v.shape[0]), device=dev), best]
+    return res
+
+
+def _valid_rows(faces, n_verts):
+    """(F,) bool on the faces' device: the rows with three different ids in [0, V)."""
+    f = faces.detach().long().reshape(-1, 3)
+    return ((f >= 0) & (f < n_verts)).all(1) & (f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 0] != f[:, 2])
+
+
+def apply_isotropic(verts, faces, isotropic):
+    """The mesh entries' `isotropic` option, as `check_isotropic` returned it: -> the remeshed verts, faces, n_verts and n_tris of
+    `isotropic_remesh`, and under "isotropic" its src_face, src_bary and report -- the entries' own vert_src and report (clean's,
+    simplify's) stay what they are."""
+    res = isotropic_remesh(verts, faces, **isotropic)
+    out = {k: res[k] for k in ("verts", "faces", "n_verts", "n_tris")}
+    out["isotropic"] = {k: res[k] for k in ("src_face", "src_bary", "report")}
+    return out
+
+
 # ---- adjacency, topology, per-vertex normals, smoothing -------------------------------------------------------------------------
 MeshAdjacency =collections.namedtuple("MeshAdjacency", ("vf_start", "vf", "nbr_start", "nbr", "nbr_out", "nbr_in", "vert_flags",
                                                          "counts"))
@@ -1014,6 +1296,19 @@ def vertex_normals(verts, faces, adjacency=None):
         return _cc_backend(faces).vertex_normals(v32, faces, adjacency=adjacency)[1]
 
 
+def _check_smooth_call(iterations, lamb, mu, method, boundary, what):
+    """meshing.check_smooth_args, and method="tangential": iterations and lamb as for "laplacian"; mu is not used, and boundary
+    must be "pin" (a tangential step never moves a vertex of a boundary or non-manifold edge).  -> True for "tangential"."""
+    from . import meshing
+    if method != "tangential":
+        meshing.check_smooth_args(iterations, lamb, mu, method, boundary, what)
+        return False
+    meshing.check_smooth_args(iterations, lamb, -0.53, "laplacian", "pin", what)
+    if boundary != "pin":
+        raise ValueError("%s: method='tangential' keeps boundary vertices where they are: boundary must be 'pin', got %r" % (what, boundary))
+    return True
+
+
 def smooth_mesh(verts, faces, iterations=10, lamb=0.5, mu=-0.53, method="taubin", boundary="pin", adjacency=None):
     """Smooth an indexed mesh with the umbrella operator: every step moves a vertex towards (lamb > 0) or away from (mu < 0) the
     mean of its neighbours, p + f (mean - p), uniform weights.  method="taubin" (Taubin 1995, "A signal processing approach to
@@ -1022,10 +1317,24 @@ def smooth_mesh(verts, faces, iterations=10, lamb=0.5, mu=-0.53, method="taubin"
     are, "free" moves them like the others.  lamb in (0, 1], mu in [-1.1, 0), iterations >= 0.  -> verts (V,3) float32; faces,
     the vertex count and the order stay, so every per-vertex attribute stays valid.  Vertices with a non-finite coordinate stay
     and are left out of their neighbours' means.  adjacency: a `mesh_adjacency` of the same mesh built earlier, or None.
-    hip.mesh_smooth on the GPU (no host synchronisation), meshing.mesh_smooth on the host, equal bit for bit."""
-    from . import meshing
-    meshing.check_smooth_args(iterations, lamb, mu, method, boundary, "smooth_mesh")
+    hip.mesh_smooth on the GPU (no host synchronisation), meshing.mesh_smooth on the host, equal bit for bit.
+
+    method="tangential": every iteration is one `mesh_tangential_step` with lamb -- the umbrella step without its part along the
+    vertex normal, which is taken from the mesh at hand (`vertex_normals`' unnormalised sum, recomputed every iteration).  Vertices
+    slide along the surface: the triangles even out and the shape neither shrinks nor loses detail the way it does along the
+    normal.  Vertices of boundary and non-manifold edges stay (boundary must be "pin"); mu is not used.  hip.mesh_tangential_step
+    on the GPU, meshing.mesh_tangential_step on the host, equal bit for bit."""
+    tangential = _check_smooth_call(iterations, lamb, mu, method, boundary, "smooth_mesh")
     v32, faces, adjacency = _smooth_args(verts, faces, adjacency, "smooth_mesh")
+    if tangential:
+        backend = _cc_backend(faces)
+        with torch.no_grad():
+            if adjacency is None:
+                adjacency = backend.mesh_adjacency(faces, int(v32.shape[0]))
+            for _ in range(int(iterations)):
+                normal_sum = backend.vertex_normals(v32, faces, adjacency=adjacency)[0]
+                v32 = backend.mesh_tangential_step(v32, faces, normal_sum, lamb, adjacency=adjacency)
+        return v32
     with torch.no_grad():
         return _cc_backend(faces).mesh_smooth(v32, faces, iterations, lamb=lamb, mu=mu, method=method, boundary=boundary,
                                               adjacency=adjacency)
@@ -1237,8 +1546,8 @@ def check_smooth(smooth):
         kw = {"iterations": int(smooth)}
     else:
         raise ValueError("smooth must be None, a number of iterations or a dict of smooth_mesh keywords, got %r" % (smooth,))
-    meshing.check_smooth_args(kw.get("iterations", 10), kw.get("lamb", 0.5), kw.get("mu", -0.53), kw.get("method", "taubin"),
-                              kw.get("boundary", "pin"), "smooth")
+    _check_smooth_call(kw.get("iterations", 10), kw.get("lamb", 0.5), kw.get("mu", -0.53), kw.get("method", "taubin"),
+                       kw.get("boundary", "pin"), "smooth")
     return kw
 
 

@@ -143,9 +143,10 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_mesh_components_scratch_bytes", "arah_mesh_components", "arah_mesh_select_scratch_bytes", "arah_mesh_select",
            "arah_mesh_simplify_scratch_bytes", "arah_mesh_simplify",
            "arah_mesh_quadric_place_scratch_bytes", "arah_mesh_quadric_place",
-           "arah_mesh_collapse_round_scratch_bytes", "arah_mesh_collapse_round",
+           "arah_mesh_collapse_round_scratch_bytes", "arah_mesh_collapse_round", "arah_mesh_collapse_round_bounded",
            "arah_mesh_subdivide_round_scratch_bytes", "arah_mesh_subdivide_round",
-           "arah_mesh_adjacency_scratch_bytes", "arah_mesh_adjacency", "arah_mesh_vertex_normals", "arah_mesh_smooth",
+           "arah_mesh_flip_round_scratch_bytes", "arah_mesh_flip_round",
+           "arah_mesh_adjacency_scratch_bytes", "arah_mesh_adjacency", "arah_mesh_vertex_normals", "arah_mesh_smooth", "arah_mesh_tangential",
            "arah_mesh_orient_scratch_bytes", "arah_mesh_orient", "arah_mesh_boundary_loops_scratch_bytes",
            "arah_mesh_boundary_loops", "arah_mesh_fill_holes_scratch_bytes", "arah_mesh_fill_holes",
            "arah_mesh_rasterize", "arah_mesh_rasterize_debug", "arah_mesh_interpolate", "arah_mesh_raycast", "arah_mesh_raycast_debug",
@@ -200,7 +201,7 @@ def load_library():
         getattr(lib, name).argtypes = [C.c_int32]
     for name in ("arah_mesh_components_scratch_bytes", "arah_mesh_select_scratch_bytes", "arah_mesh_adjacency_scratch_bytes",
                  "arah_mesh_quadric_place_scratch_bytes", "arah_mesh_collapse_round_scratch_bytes",
-                 "arah_mesh_subdivide_round_scratch_bytes",
+                 "arah_mesh_subdivide_round_scratch_bytes", "arah_mesh_flip_round_scratch_bytes",
                  "arah_mesh_orient_scratch_bytes", "arah_mesh_boundary_loops_scratch_bytes", "arah_mesh_fill_holes_scratch_bytes"):
         getattr(lib, name).restype = C.c_size_t
         getattr(lib, name).argtypes = [C.c_int64, C.c_int64]
@@ -1054,18 +1055,20 @@ def _mesh_adj_args(verts, faces, adjacency, what):
     return verts.detach().contiguous(), f, V, F, adjacency
 
 
-def mesh_collapse_round(verts, faces, need, reg=1e-3, max_cost=float("inf"), details=False):
+def mesh_collapse_round(verts, faces, need, reg=1e-3, max_cost=float("inf"), details=False, short_len2=None, long_len2=None):
     """One round of edge-collapse decimation (arah_mesh_collapse_round, csrc/meshcollapse.hpp): verts (V,3) float32 and faces (F,3)
     integer ids on the GPU; need, reg and max_cost on the host, as meshing.mesh_collapse_round describes them.  The adjacency of
     the mesh is built inside the call.  -> verts_out (V,3) float32, faces_out (F,3) int32, vert_src (V,) int32, face_src (F,) int32,
     counts (12,) int32 (meshing.COLLAPSE_COUNTS); rows past the counts are zero; details: also edge_pos (6F,3) float32, edge_key
-    (6F,) int64 and edge_reason (6F,) uint8 of every neighbour entry.  All on the device, no host synchronisation; the result is
-    meshing.mesh_collapse_round(...) bit for bit."""
+    (6F,) int64 and edge_reason (6F,) uint8 of every neighbour entry.  short_len2 / long_len2: the two length bounds
+    (arah_mesh_collapse_round_bounded, the same kernels; counts (14,), meshing.COLLAPSE_BOUNDED_COUNTS).  All on the device, no host
+    synchronisation; the result is meshing.mesh_collapse_round(...) bit for bit."""
     from . import meshing
     require_gpu()
     lib = load_library()
     what = "mesh_collapse_round"
     need, reg, max_cost = meshing.collapse_args(need, reg, max_cost, what)
+    bounds = meshing.collapse_bounds(short_len2, long_len2, what)
     if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
         raise ValueError("%s: verts must be a (V, 3) float32 tensor" % what)
     V = int(verts.shape[0])
@@ -1080,10 +1083,18 @@ def mesh_collapse_round(verts, faces, need, reg=1e-3, max_cost=float("inf"), det
         verts_out = torch.empty(V, 3, dtype=torch.float32, device=dev)
         faces_out = torch.empty(F, 3, dtype=i32, device=dev)
         vert_src, face_src = torch.empty(V, dtype=i32, device=dev), torch.empty(F, dtype=i32, device=dev)
-        counts = torch.empty(len(meshing.COLLAPSE_COUNTS), dtype=i32, device=dev)
+        counts = torch.empty(len(meshing.COLLAPSE_COUNTS if bounds is None else meshing.COLLAPSE_BOUNDED_COUNTS), dtype=i32, device=dev)
         edge_pos = torch.empty(6 * F, 3, dtype=torch.float32, device=dev)
         edge_key = torch.empty(6 * F, dtype=torch.int64, device=dev)
         edge_reason = torch.empty(6 * F, dtype=torch.uint8, device=dev)
+        if bounds is not None:
+            _check(lib.arah_mesh_collapse_round_bounded(_ptr(v), C.c_int64(V), _ptr(f), C.c_int64(F), C.c_int32(need), C.c_double(reg),
+                                                        C.c_float(max_cost), C.c_double(bounds[0]), C.c_double(bounds[1]), _ptr(verts_out),
+                                                        _ptr(faces_out), _ptr(vert_src), _ptr(face_src), _ptr(counts), _ptr(edge_pos),
+                                                        _ptr(edge_key), _ptr(edge_reason), _ptr(scratch), C.c_size_t(scratch.numel()),
+                                                        _stream()), "arah_mesh_collapse_round_bounded")
+            out = (verts_out, faces_out, vert_src, face_src, counts)
+            return out + (edge_pos, edge_key, edge_reason) if details else out
         _check(lib.arah_mesh_collapse_round(_ptr(v), C.c_int64(V), _ptr(f), C.c_int64(F), C.c_int32(need), C.c_double(reg),
                                             C.c_float(max_cost), _ptr(verts_out), _ptr(faces_out), _ptr(vert_src), _ptr(face_src),
                                             _ptr(counts), _ptr(edge_pos), _ptr(edge_key), _ptr(edge_reason), _ptr(scratch),
@@ -1124,6 +1135,40 @@ def mesh_subdivide_round(verts, faces, method="midpoint", max_len2=None):
     return verts_out, faces_out, vert_src, face_src, counts
 
 
+def mesh_flip_round(verts, faces, criterion="delaunay", salt=0, details=False):
+    """One round of edge flips (arah_mesh_flip_round, csrc/meshflip.hpp): verts (V,3) float32 and faces (F,3) integer ids on the
+    GPU; criterion "delaunay" or "valence" and salt (the round number) on the host, as meshing.mesh_flip_round describes them.  The
+    adjacency of the mesh is built inside the call.  -> faces_out (F,3) int32, face_flag (F,) uint8, counts (9,) int32
+    (meshing.FLIP_COUNTS); details: also edge_key (6F,) int64 and edge_reason (6F,) uint8 of every neighbour entry.  All on the
+    device, no host synchronisation; the result is meshing.mesh_flip_round(...) bit for bit."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    what = "mesh_flip_round"
+    crit, salt = meshing.flip_args(criterion, salt, what)
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise ValueError("%s: verts must be a (V, 3) float32 tensor" % what)
+    V = int(verts.shape[0])
+    f, _, F = _mesh_cc_args(faces, V, what)
+    if verts.device != f.device:
+        raise ValueError("%s: verts live on %s, faces on %s" % (what, verts.device, f.device))
+    if F > meshing.ADJACENCY_MAX_FACES:
+        raise ValueError("%s: at most 2^28 faces, got %d" % (what, F))
+    v, dev, i32 = verts.detach().contiguous(), f.device, torch.int32
+    with _on_device(dev):
+        scratch = _mesh_cc_buf(dev, int(lib.arah_mesh_flip_round_scratch_bytes(V, F)))
+        faces_out = torch.empty(F, 3, dtype=i32, device=dev)
+        face_flag = torch.empty(F, dtype=torch.uint8, device=dev)
+        counts = torch.empty(len(meshing.FLIP_COUNTS), dtype=i32, device=dev)
+        edge_key = torch.empty(6 * F, dtype=torch.int64, device=dev)
+        edge_reason = torch.empty(6 * F, dtype=torch.uint8, device=dev)
+        _check(lib.arah_mesh_flip_round(_ptr(v), C.c_int64(V), _ptr(f), C.c_int64(F), C.c_int32(crit), C.c_uint32(salt),
+                                        _ptr(faces_out), _ptr(face_flag), _ptr(counts), _ptr(edge_key), _ptr(edge_reason),
+                                        _ptr(scratch), C.c_size_t(scratch.numel()), _stream()), "arah_mesh_flip_round")
+    out = (faces_out, face_flag, counts)
+    return out + (edge_key, edge_reason) if details else out
+
+
 def vertex_normals(verts, faces, adjacency=None):
     """Per-vertex normals of an indexed mesh from the mesh itself (arah_mesh_vertex_normals): verts (V,3) float32 and faces (F,3)
     integer ids on the GPU, adjacency: `mesh_adjacency` of them, or None to build it here.  -> normal_sum (V,3) float64 (the
@@ -1161,6 +1206,28 @@ def mesh_smooth(verts, faces, iterations, lamb=0.5, mu=-0.53, method="taubin", b
         _check(lib.arah_mesh_smooth(_ptr(v), C.c_int64(V), _ptr(adj[2]), _ptr(adj[3]), _ptr(adj[6]), C.c_int32(n_steps),
                                     (C.c_float * 2)(factors[0], factors[-1]), C.c_int32(int(pin)), _ptr(tmp), _ptr(out), _stream()),
                "arah_mesh_smooth")
+    return out
+
+
+def mesh_tangential_step(verts, faces, normal_sum, lamb=0.5, adjacency=None):
+    """One step of tangential relaxation (arah_mesh_tangential): verts (V,3) float32, faces (F,3) integer ids and normal_sum (V,3)
+    float64 (vertex_normals' first output for the same mesh) on the GPU, lamb as meshing.mesh_tangential_step describes it,
+    adjacency: `mesh_adjacency` of the mesh, or None to build it here.  -> verts_out (V,3) float32, meshing.mesh_tangential_step
+    bit for bit.  A gather: no atomics, no host synchronisation."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    what = "mesh_tangential_step"
+    factor = meshing.check_tangential_lamb(lamb, what)
+    v, f, V, F, adj = _mesh_adj_args(verts, faces, adjacency, what)
+    dev = v.device
+    if not isinstance(normal_sum, torch.Tensor) or tuple(normal_sum.shape) != (V, 3) or normal_sum.dtype != torch.float64 \
+            or normal_sum.device != dev:
+        raise ValueError("%s: normal_sum must be the (V, 3) float64 sum of vertex_normals, on %s" % (what, dev))
+    with _on_device(dev):
+        out = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        _check(lib.arah_mesh_tangential(_ptr(v), C.c_int64(V), _ptr(adj[2]), _ptr(adj[3]), _ptr(adj[6]), _ptr(normal_sum.contiguous()),
+                                        C.c_float(factor), _ptr(out), _stream()), "arah_mesh_tangential")
     return out
 
 

@@ -754,11 +754,60 @@ def mesh_smooth(verts, faces, iterations, lamb=0.5, mu=-0.53, method="taubin", b
     return cur
 
 
+def check_tangential_lamb(lamb, what="mesh_tangential_step"):
+    """lamb of the tangential step, checked: -> its float32 value widened to a Python float."""
+    if isinstance(lamb, bool) or not isinstance(lamb, (int, float, np.integer, np.floating)) or not 0.0 < float(lamb) <= 1.0:
+        raise ValueError("%s: lamb must be a number in (0, 1], got %r" % (what, lamb))
+    return float(np.float32(float(lamb)))
+
+
+def mesh_tangential_step(verts, faces, normal_sum, lamb=0.5, adjacency=None):
+    """One step of tangential relaxation: `mesh_smooth`'s umbrella step with the part along the vertex normal taken out, so that
+    vertices slide along the surface and do not shrink it.  verts (V,3) float32, faces (F,3) integer ids, normal_sum (V,3) float64
+    of `vertex_normals` of the same mesh, lamb in (0, 1] (its float32 value is the factor), adjacency `mesh_adjacency` or None.
+    A vertex moves when it is finite, has neither bit 0 nor bit 1 of vert_flags (is not on a boundary or non-manifold edge), has a
+    finite neighbour, and nn = (N0 N0 + N1 N1) + N2 N2 of its normal_sum N is finite and > 0.  s = the float64 sum of its finite
+    unique neighbours in ascending id, m their number, d = s / m - p, t = ((d0 N0 + d1 N1) + d2 N2) / nn, new = float32(p + lamb
+    (d - t N)), every operation rounded on its own; no square root.  All other vertices are copied bit for bit.  -> verts_out
+    (V,3) float32.  The specification of arah_mesh_tangential (csrc/meshadj.hpp), and what runs for meshes on the host."""
+    what = "mesh_tangential_step"
+    f = check_tangential_lamb(lamb, what)
+    verts, faces, V, _ = _mesh_verts(verts, faces, what)
+    f64 = torch.float64
+    if not isinstance(normal_sum, torch.Tensor) or tuple(normal_sum.shape) != (V, 3) or normal_sum.dtype != f64 \
+            or normal_sum.device != verts.device:
+        raise ValueError("%s: normal_sum must be the (V, 3) float64 sum of vertex_normals, on %s" % (what, verts.device))
+    adjacency = _adjacency_of(faces, V, adjacency, what)
+    nbr_start, nbr, flags = adjacency[2], adjacency[3], adjacency[6]
+    F = int(faces.shape[0])
+    if V == 0 or F == 0:
+        return verts.clone()
+    start = nbr_start.long()
+    first, deg = start[:-1], start[1:] - start[:-1]
+    nb, p, finite = nbr.long(), verts.to(f64), torch.isfinite(verts).all(1)
+    s = torch.zeros(V, 3, dtype=f64, device=verts.device)
+    m = torch.zeros(V, dtype=f64, device=verts.device)
+    for k in range(int(deg.max())):
+        n = nb[(first + k).clamp(max=6 * F - 1)]
+        has = (k < deg) & finite[n]
+        s = s + torch.where(has[:, None], p[n], torch.zeros_like(s))
+        m = m + has.to(f64)
+    N = normal_sum
+    nn = (N[:, 0] * N[:, 0] + N[:, 1] * N[:, 1]) + N[:, 2] * N[:, 2]
+    moves = finite & ((flags & 3) == 0) & (m > 0) & torch.isfinite(nn) & (nn > 0)
+    d = s / m.clamp_min(1.0)[:, None] - p
+    t = ((d[:, 0] * N[:, 0] + d[:, 1] * N[:, 1]) + d[:, 2] * N[:, 2]) / nn
+    new = (p + f * (d - t[:, None] * N)).float()
+    return torch.where(moves[:, None], new, verts)
+
+
 # ---- edge-collapse decimation: one round ---------------------------------------------------------------------------------------------
-COLLAPSE_MAX_UNION = 32                 # faces around an edge that is still a candidate: kMqShort, one lane's tree
+COLLAPSE_MAX_UNION = 32                # faces around an edge that is still a candidate: kMqShort, one lane's tree
 COLLAPSE_COUNTS = ("n_verts", "n_faces", "selected", "applied", "candidates", "pinned", "link", "long_edges", "nonfinite", "over_error",
                    "flips", "fallbacks")
 COLLAPSE_REASONS = ("candidate", "pinned", "link", "long_edges", "nonfinite", "over_error", "flips")   # counts[4 + reason]
+COLLAPSE_BOUNDED_REASONS = COLLAPSE_REASONS + ("not_short", "too_long")   # reasons 7 and 8: counts[12], counts[13]
+COLLAPSE_BOUNDED_COUNTS = COLLAPSE_COUNTS + ("not_short", "too_long")
 COLLAPSE_NO_EDGE = 255                  # edge_reason of a neighbour entry that names no edge (nbr <= owner, or past the entries)
 _COLLAPSE_EMPTY = 2 ** 63 - 1
 
@@ -798,7 +847,23 @@ def _d2_f32(p, q):
     return ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]).float()
 
 
-def mesh_collapse_round(verts, faces, need, reg=1e-3, max_cost=float("inf"), adjacency=None, details=False):
+def collapse_bounds(short_len2, long_len2, what="mesh_collapse_round"):
+    """The two length bounds of `mesh_collapse_round`, checked: -> None without any, else (short_len2, long_len2) as floats >= 0,
+    infinity for the one that is not given."""
+    if short_len2 is None and long_len2 is None:
+        return None
+    out = []
+    for name, x in (("short_len2", short_len2), ("long_len2", long_len2)):
+        if x is None:
+            x = float("inf")
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not float(x) >= 0.0:
+            raise ValueError("%s: %s must be a number >= 0 (inf: no bound), got %r" % (what, name, x))
+        out.append(float(x))
+    return tuple(out)
+
+
+def mesh_collapse_round(verts, faces, need, reg=1e-3, max_cost=float("inf"), adjacency=None, details=False, short_len2=None,
+                        long_len2=None):
     """One round of edge-collapse decimation: verts (V,3) float32, faces (F,3) integer ids, need >= 0 the most edges to collapse,
     reg the regulariser of `mesh_quadric_place`'s solve, max_cost a float32 bound on an edge's cost, adjacency `mesh_adjacency`
     of the mesh or None.  Many independent edges collapse at once; which ones is decided on integers and on the bits of rounded
@@ -827,6 +892,15 @@ def mesh_collapse_round(verts, faces, need, reg=1e-3, max_cost=float("inf"), adj
                     every such face.
     An edge without a reason is a CANDIDATE with key = (bits(cost32) << 32) | i.
 
+    BOUNDED (short_len2 or long_len2 given, the other one infinity; COLLAPSE_BOUNDED_REASONS): two more tests, for a remesher that
+    removes short edges only and must not make long ones.
+      7 not_short   BEFORE every other test: the edge's squared length (dx dx + dy dy) + dz dz in float64 is not below short_len2
+                    (or is not a number).
+      8 too_long    after test 6: a corner other than u and v of a face of the n that does not name both lies farther from pos
+                    than long_len2 -- its squared distance to double(pos), formed the same way, exceeds long_len2.
+    counts then has fourteen entries: the twelve of COLLAPSE_COUNTS, then the edges with reason 7 and with reason 8.  Without
+    bounds nothing changes: twelve counts, the reasons 0 .. 6.
+
     SELECTION: m1[x] = the least key of the candidates at x; m2[x] = the least of m1 over x and its neighbours; a candidate is
     selected when m2[u] = m2[v] = its key.  Keys are unique, so a selected edge is the least at every vertex of N[u] and N[v]:
     no end of another selected edge is u, v or a neighbour of either, and the faces two selected edges touch are disjoint.  Of the
@@ -843,6 +917,7 @@ def mesh_collapse_round(verts, faces, need, reg=1e-3, max_cost=float("inf"), adj
     arah_mesh_collapse_round (csrc/meshcollapse.hpp), and what runs for meshes on the host."""
     what = "mesh_collapse_round"
     need, reg, max_cost = collapse_args(need, reg, max_cost, what)
+    bounds = collapse_bounds(short_len2, long_len2, what)
     raw_faces = torch.as_tensor(faces)
     verts, faces, V, in_range = _mesh_verts(verts, faces, what)
     if raw_faces.dtype != torch.int32:
@@ -865,6 +940,8 @@ def mesh_collapse_round(verts, faces, need, reg=1e-3, max_cost=float("inf"), adj
     cost_bits = torch.zeros(n_edges, dtype=i64, device=dev)
     fallbacks = 0
     reason[pinned[u] | pinned[v]] = 1
+    if bounds is not None:
+        reason[~(_d2_f64(verts[u].to(f64), verts[v].to(f64)) < bounds[0])] = 7
     # 2: the link condition
     at = torch.nonzero(reason == 0)[:, 0]
     if at.numel():
@@ -915,8 +992,13 @@ def mesh_collapse_round(verts, faces, need, reg=1e-3, max_cost=float("inf"), adj
         dot = (N[:, 0] * N2[:, 0] + N[:, 1] * N2[:, 1]) + N[:, 2] * N2[:, 2]
         flipped = torch.zeros(K, dtype=torch.bool, device=dev)
         flipped[pk[(moves.sum(1) == 1) & ~(dot > 0)]] = True
+        far = torch.zeros(K, dtype=torch.bool, device=dev)
+        if bounds is not None:
+            gap = before - p_new[pk].to(f64)[:, None, :]
+            gap2 = (gap[:, :, 0] * gap[:, :, 0] + gap[:, :, 1] * gap[:, :, 1]) + gap[:, :, 2] * gap[:, :, 2]
+            far[pk[(moves.sum(1) == 1) & (~moves & (gap2 > bounds[1])).any(1)]] = True
         over = cost32 > max_cost
-        reason[at] = torch.where(~finite, 4, torch.where(over, 5, torch.where(flipped, 6, 0))).to(i64)
+        reason[at] = torch.where(~finite, 4, torch.where(over, 5, torch.where(flipped, 6, torch.where(far, 8, 0)))).to(i64)
         pos[at] = p_new
         cost_bits[at] = cost32.view(i32).long()
     cand = reason == 0
@@ -952,7 +1034,8 @@ def mesh_collapse_round(verts, faces, need, reg=1e-3, max_cost=float("inf"), adj
     face_src = torch.zeros(F, dtype=i64, device=dev)
     faces_out[:nf], face_src[:nf] = renamed[rows], rows
     counts = torch.tensor([nv, nf, n_selected, int(applied.shape[0])] + [int((reason == r).sum()) for r in range(7)]
-                          + [fallbacks], dtype=i32, device=dev)
+                          + [fallbacks] + ([int((reason == r).sum()) for r in (7, 8)] if bounds is not None else []), dtype=i32,
+                          device=dev)
     out = (verts_out, faces_out.to(i32), vert_src.to(i32), face_src.to(i32), counts)
     if not details:
         return out
@@ -1154,6 +1237,181 @@ def mesh_subdivide_round(verts, faces, method="midpoint", max_len2=None, adjacen
     counts = torch.tensor([V + n_marked, n_faces_out, n_edges, n_marked] + per + [F - int(valid.sum()), n_nonfinite, n_interior, n_rim,
                            V - n_interior - n_rim], dtype=i32, device=dev)
     return verts_out, faces_out.to(i32), vert_src.to(i32), face_src.to(i32), counts
+
+
+# ---- edge flips: one round -----------------------------------------------------------------------------------------------------------
+FLIP_CRITERIA = {"delaunay": 0, "valence": 1}
+FLIP_COUNTS = ("edges", "candidates", "selected", "not_interior", "same_corner", "exists", "nonfinite", "criterion", "normals")
+FLIP_REASONS = ("candidate", "not_interior", "same_corner", "exists", "nonfinite", "criterion", "normals")   # counts[2 + reason], r >= 1
+FLIP_NO_EDGE = 255                      # edge_reason of a neighbour entry that names no edge (nbr <= owner, or past the entries)
+FLIP_SALT_STEP = 0x9e3779b9             # the entry id is xor-ed with salt times this (mod 2^32) before it is hashed
+_M32 = 0xffffffff
+
+
+def flip_args(criterion, salt, what="mesh_flip_round"):
+    """The scalars of `mesh_flip_round`, checked: -> (the criterion's number, salt as an integer in [0, 2^32))."""
+    if criterion not in FLIP_CRITERIA:
+        raise ValueError("%s: criterion must be 'delaunay' or 'valence', got %r" % (what, criterion))
+    if isinstance(salt, bool) or not isinstance(salt, (int, np.integer)) or not 0 <= int(salt) <= _M32:
+        raise ValueError("%s: salt must be an integer in [0, 2^32), got %r" % (what, salt))
+    return FLIP_CRITERIA[criterion], int(salt)
+
+
+def _mul32(x, m):
+    """x m mod 2^32 for an int64 tensor x in [0, 2^32) and a constant m in [0, 2^32): no product leaves the int64 range."""
+    return ((x * (m & 0xffff)) + (((x * (m >> 16)) & 0xffff) << 16)) & _M32
+
+
+def flip_hash32(x):
+    """The integer hash of the flip keys, on int64 tensors holding values in [0, 2^32): x ^= x >> 16, x *= 0x7feb352d, x ^= x >> 15,
+    x *= 0x846ca68b, x ^= x >> 16, all mod 2^32 (a two-round multiply-xorshift finaliser; a bijection of the 32-bit integers)."""
+    x = x ^ (x >> 16)
+    x = _mul32(x, 0x7feb352d)
+    x = x ^ (x >> 15)
+    x = _mul32(x, 0x846ca68b)
+    return x ^ (x >> 16)
+
+
+def mesh_flip_round(verts, faces, criterion="delaunay", salt=0, adjacency=None, details=False):
+    """One round of edge flips: verts (V,3) float32, faces (F,3) integer ids, criterion "delaunay" or "valence", salt the round
+    number (an integer in [0, 2^32)), adjacency `mesh_adjacency` of the mesh or None.  Many independent edges flip at once; which
+    ones is decided on integers, so the order in which a device's threads arrive does not show.  All floating point is float64
+    from the float32 inputs, every operation rounded on its own; no square root, no trigonometry.
+
+    EDGES: the neighbour entry i = (u, v) with v > u names the edge {u, v}; i is its id.  The first test that fails is the edge's
+    reason (FLIP_REASONS) and is counted:
+      1 not_interior  the entry does not carry one face each way (nbr_out = nbr_in = 1): a boundary, non-manifold or misoriented
+                      edge.  Otherwise fa is the valid face that traverses u->v and a its third corner, fb the one that traverses
+                      v->u and b its third corner.
+      2 same_corner   a = b.
+      3 exists        b is a neighbour of a: the flipped edge {a, b} is there already.
+      4 nonfinite     one of u, v, a, b has a non-finite coordinate.
+      5 criterion     Na = (u - a) x (v - a) and Nb = (v - b) x (u - b), the cross products of the corners (a, u, v) and (b, v, u),
+                      N1 = (u - a) x (b - a) and N2 = (v - b) x (a - b) those of the new faces' corners (a, u, b) and (b, v, a),
+                      every component (x y) - (z w).
+                      "delaunay": d_x = ((u - x) . (v - x)) summed left to right for x = a, b; c_a = (Na0 Na0 + Na1 Na1) + Na2 Na2,
+                      c_b the same of Nb.  The edge stays when d_a >= 0 and d_b >= 0; it flips when d_a < 0 and d_b < 0;
+                      otherwise, with n the corner whose d is negative and o the other one, it flips when (d_n d_n) c_o >
+                      (d_o d_o) c_n -- cot(angle at a) + cot(angle at b) < 0, strictly, so that co-circular quads stay.  The
+                      edge flips when this test asks for it AND the same test of the flipped edge {a, b} does not ask to come
+                      back: its corners are u and v, d_x = ((a - x) . (b - x)) for x = u, v, c_u and c_v the squared lengths of
+                      N1 and N2 below.  The four angles of a quad in space sum to at most 2 pi, so in exact arithmetic the
+                      second half never refuses; with rounded numbers a nearly co-circular quad (marching-cubes meshes are
+                      full of them) can ask both ways, and would flip back and forth for ever.
+                      "valence": deg = the number of neighbours, target = 4 for a vertex with vert_flags bit 0 (on a boundary)
+                      and 6 otherwise; the edge flips when the sum of |deg - target| over u, v, a, b is strictly smaller with u
+                      and v one lower and a and b one higher.  Integers only.
+                      The reason holds when the criterion does not ask for the flip.
+      6 normals       the reason holds unless (N 0 M 0 + N 1 M 1) + N 2 M 2 > 0 for every N of N1, N2 and every M of Na, Nb.
+    An edge without a reason is a CANDIDATE with key = (hash32(i ^ (salt 0x9e3779b9 mod 2^32)) << 32) | i (`flip_hash32`), an
+    unsigned 64-bit integer.
+
+    SELECTION: lock[x] = the least key of the candidates that have x among their u, v, a, b; a candidate is selected when the
+    locks of its four vertices all hold its key.  Keys are unique, so two selected flips share no vertex: they rewrite disjoint
+    faces, create different edges, and no test one of them passed reads anything the other changes.
+
+    APPLY: faces_out is a copy of faces (ids that do not fit int32 are -1) in which, for a selected edge, row fa is (a, u, b) and
+    row fb is (b, v, a).  Vertices, the face count and the order stay.
+
+    -> faces_out (F,3) int32, face_flag (F,) uint8 (1: the row was rewritten), counts (9,) int32 in the order of FLIP_COUNTS.
+    details: also edge_key (6F,) int64 (the key's 64 bits, -1: no candidate), edge_reason (6F,) uint8 (FLIP_NO_EDGE where the
+    entry names no edge) and selected (6F,) bool.  Plain tensor operations on the tensors' device: the specification of
+    arah_mesh_flip_round (csrc/meshflip.hpp), and what runs for meshes on the host."""
+    what = "mesh_flip_round"
+    crit, salt = flip_args(criterion, salt, what)
+    raw_faces = torch.as_tensor(faces)
+    verts, faces, V, in_range = _mesh_verts(verts, faces, what)
+    if raw_faces.dtype != torch.int32:
+        faces = torch.where((faces >= 0) & (faces <= 2 ** 31 - 1), faces, torch.full_like(faces, -1))
+    F, dev = int(faces.shape[0]), verts.device
+    f64, i32, i64 = torch.float64, torch.int32, torch.int64
+    adjacency = _adjacency_of(faces, V, adjacency, what)
+    vf_start, vf, nbr_start, nbr, nbr_out, nbr_in = (t.long() for t in adjacency[:6])
+    on_rim = (adjacency[6].long() & 1) != 0
+    E = int(nbr_start[V])
+    val, nvf = nbr_start[1:] - nbr_start[:-1], vf_start[1:] - vf_start[:-1]
+    ev, en = torch.repeat_interleave(torch.arange(V, device=dev), val), nbr[:E]
+    eid = torch.nonzero(en > ev)[:, 0]
+    u, v = ev[eid], en[eid]
+    n_edges = int(eid.shape[0])
+    reason = torch.zeros(n_edges, dtype=i64, device=dev)
+    reason[(nbr_out[eid] != 1) | (nbr_in[eid] != 1)] = 1
+    qa, qb, qfa, qfb = (torch.zeros(n_edges, dtype=i64, device=dev) for _ in range(4))
+    at = torch.nonzero(reason == 0)[:, 0]
+    if at.numel():
+        ub, vb = u[at], v[at]
+        k, rows = _ragged(vf_start[ub], nvf[ub])
+        fcs = vf[rows]
+        shared = (faces[fcs] == vb[k][:, None]).any(1)
+        fs, ks = fcs[shared], k[shared]                                             # two per edge: nbr_out = nbr_in = 1
+        ids, us, vs = faces[fs], ub[k[shared]], vb[k[shared]]
+        fwd = ((ids[:, 0] == us) & (ids[:, 1] == vs)) | ((ids[:, 1] == us) & (ids[:, 2] == vs)) | ((ids[:, 2] == us) & (ids[:, 0] == vs))
+        third = ids.sum(1) - us - vs
+        a, b, fa, fb = (torch.zeros(at.shape[0], dtype=i64, device=dev) for _ in range(4))
+        a[ks[fwd]], fa[ks[fwd]], b[ks[~fwd]], fb[ks[~fwd]] = third[fwd], fs[fwd], third[~fwd], fs[~fwd]
+        ekey = ev * max(V, 1) + en                                                  # ascending: the entries' own order
+        want = a * max(V, 1) + b
+        exists = ekey[torch.searchsorted(ekey, want).clamp(max=E - 1)] == want
+        finite = torch.isfinite(verts).all(1)
+        finite4 = finite[ub] & finite[vb] & finite[a] & finite[b]
+        p = verts.to(f64)
+        pu, pv, pa, pb = p[ub], p[vb], p[a], p[b]
+        Na, Nb = _cross3(torch.stack([pa, pu, pv], 1)), _cross3(torch.stack([pb, pv, pu], 1))
+        N1, N2 = _cross3(torch.stack([pa, pu, pb], 1)), _cross3(torch.stack([pb, pv, pa], 1))
+        if crit == 0:
+            def dot3(x, y):
+                return (x[:, 0] * y[:, 0] + x[:, 1] * y[:, 1]) + x[:, 2] * y[:, 2]
+
+            def wants(da, db, ca, cb):
+                a_neg = (da * da) * cb > (db * db) * ca
+                b_neg = (db * db) * ca > (da * da) * cb
+                return torch.where((da < 0) & (db < 0), torch.ones_like(exists),
+                                   torch.where((da < 0) & (db >= 0), a_neg, torch.where((db < 0) & (da >= 0), b_neg, torch.zeros_like(exists))))
+            asks = wants(dot3(pu - pa, pv - pa), dot3(pu - pb, pv - pb), dot3(Na, Na), dot3(Nb, Nb))
+            back = wants(dot3(pa - pu, pb - pu), dot3(pa - pv, pb - pv), dot3(N1, N1), dot3(N2, N2))
+            asks = asks & ~back
+        else:
+            def off(x, step):
+                return (val[x] + step - torch.where(on_rim[x], 4, 6)).abs()
+            before = off(ub, 0) + off(vb, 0) + off(a, 0) + off(b, 0)
+            after = off(ub, -1) + off(vb, -1) + off(a, 1) + off(b, 1)
+            asks = after < before
+        good = torch.ones_like(exists)
+        for N in (N1, N2):
+            for M in (Na, Nb):
+                good = good & ((N[:, 0] * M[:, 0] + N[:, 1] * M[:, 1]) + N[:, 2] * M[:, 2] > 0)
+        r = torch.where(a == b, 2, torch.where(exists, 3, torch.where(~finite4, 4, torch.where(~asks, 5, torch.where(~good, 6, 0)))))
+        reason[at] = r.to(i64)
+        qa[at], qb[at], qfa[at], qfb[at] = a, b, fa, fb
+    cand = reason == 0
+    # the key with its upper half shifted by 2^31: the signed order of `skey` is the unsigned order of the key
+    h = flip_hash32(eid ^ ((salt * FLIP_SALT_STEP) & _M32))
+    top = torch.iinfo(i64).max
+    skey = torch.where(cand, (h - 2 ** 31) * 2 ** 32 + eid, torch.full_like(eid, top))
+    lock = torch.full((V,), top, dtype=i64, device=dev)
+    ci = torch.nonzero(cand)[:, 0]
+    quad = torch.cat([u[ci], v[ci], qa[ci], qb[ci]])
+    lock = lock.scatter_reduce(0, quad, skey[ci].repeat(4), "amin")
+    selected = cand.clone()
+    selected[ci] = (lock[quad].reshape(4, -1) == skey[ci][None, :]).all(0)
+    si = torch.nonzero(selected)[:, 0]
+    faces_out = faces.clone()
+    face_flag = torch.zeros(F, dtype=torch.uint8, device=dev)
+    faces_out[qfa[si]] = torch.stack([qa[si], u[si], qb[si]], 1)
+    faces_out[qfb[si]] = torch.stack([qb[si], v[si], qa[si]], 1)
+    face_flag[qfa[si]] = 1
+    face_flag[qfb[si]] = 1
+    counts = torch.tensor([n_edges, int(cand.sum()), int(si.shape[0])] + [int((reason == r).sum()) for r in range(1, 7)],
+                          dtype=i32, device=dev)
+    out = (faces_out.to(i32), face_flag, counts)
+    if not details:
+        return out
+    edge_key = torch.full((6 * F,), -1, dtype=i64, device=dev)
+    edge_reason = torch.full((6 * F,), FLIP_NO_EDGE, dtype=torch.uint8, device=dev)
+    edge_sel = torch.zeros(6 * F, dtype=torch.bool, device=dev)
+    edge_reason[eid], edge_sel[eid] = reason.to(torch.uint8), selected
+    edge_key[eid] = torch.where(cand, skey ^ torch.iinfo(i64).min, torch.full_like(skey, -1))
+    return out + (edge_key, edge_reason, edge_sel)
 
 
 # ---- orientation, boundary loops, hole filling -----------------------------------------------------------------------------------

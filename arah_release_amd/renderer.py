@@ -904,7 +904,7 @@ class MetaAvatarRender(nn.Module):
                 "converged": (r["state"] == 1).reshape(shape), "state": r["state"].reshape(shape)}
 
     def posed_mesh(self, inputs, n_side=256, method="lattice", bounds=None, indexed=False, clean=None, simplify=None, smooth=None,
-                   subdivide=None):
+                   subdivide=None, isotropic=None):
         """A triangle soup of the posed body of frame `inputs` in world metres.  method="lattice": the zero level set of the posed
         SDF (hip.sdf_grid_posed, only the band around the occupancy bitmap's marked voxels unless ARAH_POSED_MESH_BAND=0, then
         hip.marching_cubes) -- the surface the renderer sees, self-contact included.  method="skinned": the reference's points_bar
@@ -928,6 +928,9 @@ class MetaAvatarRender(nn.Module):
         geometry.subdivide_mesh keywords (levels, method, max_edge, max_rounds, max_faces) -- the mesh is geometry.subdivide_mesh of
         the call without it, AFTER clean and simplify and BEFORE smooth; verts, faces, n_verts and n_tris are the refined mesh's
         and "subdivide" holds its vert_src, vert_weights, face_src and report (ids of the mesh that was refined).
+        isotropic (indexed=True only; None: nothing changes): a target edge length or a dict of geometry.isotropic_remesh keywords
+        (edge_length, iterations, lamb, project, max_rounds, max_faces) -- after subdivide and before smooth the mesh is remeshed
+        towards triangles of one size; "isotropic" holds src_face, src_bary and report (ids of the mesh that was remeshed).
         Eval only."""
         from . import geometry, meshing
         if clean is not None:
@@ -946,6 +949,10 @@ class MetaAvatarRender(nn.Module):
             subdivide = geometry.check_subdivide(subdivide)
             if not indexed:
                 raise ValueError("posed_mesh: subdivide needs indexed=True (edges are defined by shared vertex ids)")
+        if isotropic is not None:
+            isotropic = geometry.check_isotropic(isotropic)
+            if not indexed:
+                raise ValueError("posed_mesh: isotropic needs indexed=True (edges are defined by shared vertex ids)")
         frame, ws = self._posed_frame(inputs, "posed_mesh")
         if method not in ("lattice", "skinned"):
             raise ValueError("method must be 'lattice' or 'skinned', got %r" % (method,))
@@ -976,6 +983,8 @@ class MetaAvatarRender(nn.Module):
                     res.update(geometry.apply_simplify(res["verts"], res["faces"], simplify))
                 if subdivide is not None:
                     res.update(geometry.apply_subdivide(res["verts"], res["faces"], subdivide))
+                if isotropic is not None:
+                    res.update(geometry.apply_isotropic(res["verts"], res["faces"], isotropic))
                 if smooth is not None:
                     res["verts"] = geometry.smooth_mesh(res["verts"], res["faces"], **smooth)
                 return res
@@ -1001,7 +1010,8 @@ class MetaAvatarRender(nn.Module):
                 n = int(n_dev.item())
             return {"tris": hip.lattice_to_world(tris[:n], box), "n_tris": n, "box": box, "counts": counts}
 
-    def canonical_mesh(self, inputs, n_side=256, attributes=(), view_dirs=None, clean=None, simplify=None, smooth=None, subdivide=None):
+    def canonical_mesh(self, inputs, n_side=256, attributes=(), view_dirs=None, clean=None, simplify=None, smooth=None, subdivide=None,
+                       isotropic=None):
         """The canonical body of frame `inputs` as an indexed mesh, the reference's create_mesh_vertices_and_faces
         (utils/sdf_meshing.py:13-114): the zero level set of the canonical SDF on the n_side^3 lattice (hip.sdf_grid_band, then
         hip.marching_cubes_indexed).  -> dict of verts (V,3) normalised canonical coordinates in [-1,1]^3, faces (F,3) int32,
@@ -1038,6 +1048,10 @@ class MetaAvatarRender(nn.Module):
         skinning networks inside the large faces.  V is then the refined mesh's, and "subdivide" holds subdivide_mesh's vert_src,
         vert_weights, face_src and report (ids of the mesh that was refined).
 
+        isotropic (None: nothing changes): a target edge length or a dict of geometry.isotropic_remesh keywords; applied after
+        subdivide and BEFORE smooth and the attributes, which are evaluated at the remeshed vertices as they are after simplify.
+        "isotropic" holds isotropic_remesh's src_face, src_bary and report (ids of the mesh that was remeshed).
+
         Eval only, GPU only; one host synchronisation (the mesh's size), one more with clean, simplify_mesh's with simplify."""
         from . import geometry, meshing
         names = ("weights", "verts_posed", "normal", "color", "vertex_normal")
@@ -1050,6 +1064,7 @@ class MetaAvatarRender(nn.Module):
             simplify = geometry.check_simplify(simplify)
         smooth = geometry.check_smooth(smooth)
         subdivide = geometry.check_subdivide(subdivide)
+        isotropic = geometry.check_isotropic(isotropic)
         frame, ws = self._posed_frame(inputs, "canonical_mesh")
         with torch.no_grad():
             verts, faces = meshing.indexed_mesh(meshing.canonical_lattice(frame, ws, n_side), 0.0)
@@ -1063,6 +1078,9 @@ class MetaAvatarRender(nn.Module):
                 verts, faces, V = res["verts"].contiguous(), res["faces"], res["n_verts"]
             if subdivide is not None:
                 res.update(geometry.apply_subdivide(verts, faces, subdivide))
+                verts, faces, V = res["verts"].contiguous(), res["faces"], res["n_verts"]
+            if isotropic is not None:
+                res.update(geometry.apply_isotropic(verts, faces, isotropic))
                 verts, faces, V = res["verts"].contiguous(), res["faces"], res["n_verts"]
             adjacency = None
             if smooth is not None:
@@ -1102,9 +1120,9 @@ class MetaAvatarRender(nn.Module):
         return res
 
     def render_mesh(self, inputs, height=512, width=512, n_side=256, space="posed", attributes=("color", "vertex_normal"), clean=None,
-                    simplify=None, smooth=None, view=None, subdivide=None):
+                    simplify=None, smooth=None, view=None, subdivide=None, isotropic=None):
         """An image of the body of frame `inputs` as an indexed mesh: `canonical_mesh(inputs, n_side, clean=, simplify=, smooth=,
-        subdivide=)`
+        subdivide=, isotropic=)`
         with "verts_posed" and the attributes named, drawn by geometry.render_mesh (hip.mesh_rasterize, hip.mesh_interpolate).
         space="posed": the skinned vertices through the frame's own camera (cam_rot, cam_trans, intrinsics of batch element 0);
         space="canonical": the canonical vertices through `view`, a look-at camera {"azim": degrees (0 front, 180 back)[, "dist",
@@ -1143,7 +1161,7 @@ class MetaAvatarRender(nn.Module):
         own = ("vertex_normal", "face_normal", "ambient_occlusion")   # taken from the mesh that is drawn
         wanted = {a for a in attributes if a not in own} | ({"verts_posed"} if space == "posed" else set())
         mesh = self.canonical_mesh(inputs, n_side=n_side, attributes=tuple(sorted(wanted)), clean=clean, simplify=simplify, smooth=smooth,
-                                   subdivide=subdivide)
+                                   subdivide=subdivide, isotropic=isotropic)
         verts = mesh["verts_posed"] if space == "posed" else mesh["verts"]
         draw = {a: (True if a in own else mesh[a]) for a in attributes}
         if "ambient_occlusion" in draw:
@@ -1191,9 +1209,9 @@ class MetaAvatarRender(nn.Module):
         return res
 
     def mesh_intersections(self, inputs, n_side=256, space="posed", clean=None, simplify=None, smooth=None, max_pairs=1 << 20,
-                           subdivide=None):
+                           subdivide=None, isotropic=None):
         """Where the body of frame `inputs` passes through itself, as an indexed mesh -- the mesh `render_mesh` draws and `cast_rays`
-        sees: `canonical_mesh(inputs, n_side, clean=, simplify=, smooth=, subdivide=)`, skinned forward ("verts_posed") for space="posed", as it is
+        sees: `canonical_mesh(inputs, n_side, clean=, simplify=, smooth=, subdivide=, isotropic=)`, skinned forward ("verts_posed") for space="posed", as it is
         for space="canonical".  Linear blend skinning pushes the surface through itself at bent elbows, armpits and thighs; ray hits,
         occlusion, parity containment and signed distances are wrong there.  -> the dict of geometry.self_intersections (count,
         faces_hit, hits, vert_hit, pairs, void_faces, truncated, embedded, ...) plus "mesh", the dict of canonical_mesh.  vert_hit
@@ -1204,7 +1222,7 @@ class MetaAvatarRender(nn.Module):
         if space not in ("posed", "canonical"):
             raise ValueError("mesh_intersections: space must be 'posed' or 'canonical', got %r" % (space,))
         mesh = self.canonical_mesh(inputs, n_side=n_side, attributes=("verts_posed",) if space == "posed" else (), clean=clean,
-                                   simplify=simplify, smooth=smooth, subdivide=subdivide)
+                                   simplify=simplify, smooth=smooth, subdivide=subdivide, isotropic=isotropic)
         verts = mesh["verts_posed"] if space == "posed" else mesh["verts"]
         res = geometry.self_intersections(verts, mesh["faces"], max_pairs=max_pairs)
         res["mesh"] = mesh

@@ -37,6 +37,7 @@
  *   arah_mesh_quadric_place (none: the clusters of arah_mesh_simplify moved to the minimisers of their faces' plane quadrics)
  *   arah_mesh_collapse_round (none: one round of edge-collapse decimation that keeps the surface a surface)
  *   arah_mesh_subdivide_round (none: one round of midpoint or Loop subdivision, of every edge or of the long ones)
+ *   arah_mesh_flip_round    (none: one round of independent edge flips, towards Delaunay or towards valence six)
  *   arah_mesh_adjacency /   (none: the reference's users smooth and re-normal with trimesh / open3d / pytorch3d; the incident faces
  *   arah_mesh_vertex_normals /  and unique neighbours of every vertex with edge statistics, pytorch3d's verts_normals_packed over
  *   arah_mesh_smooth        them, and Laplacian / Taubin umbrella smoothing)
@@ -447,6 +448,16 @@ int arah_mesh_collapse_round(const float* verts, int64_t n_verts, const int32_t*
                              float max_cost, float* verts_out, int32_t* faces_out, int32_t* vert_src, int32_t* face_src,
                              int32_t* counts, float* edge_pos, uint64_t* edge_key, uint8_t* edge_reason, void* scratch,
                              size_t scratch_bytes, void* stream);
+/* arah_mesh_collapse_round with two bounds on lengths, over the same kernels and the same scratch.  Before every other test: (7)
+ * the edge's squared length (dx dx + dy dy) + dz dz in double is not below short_len2 (or not a number).  After test (6): (8) a
+ * corner other than u and v of a face that names one of them lies farther than long_len2 (squared, in double, summed the same
+ * way) from pos.  counts is device int32[14]: the twelve above, then the edges with reason 7 and with reason 8; edge_reason
+ * takes 7 and 8 too.  Equal to meshing.mesh_collapse_round(short_len2=, long_len2=) bit for bit.  short_len2 >= 0 and long_len2
+ * >= 0 (infinity: no bound), otherwise ARAH_E_BADARG; everything else as above. */
+int arah_mesh_collapse_round_bounded(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t need, double reg,
+                                     float max_cost, double short_len2, double long_len2, float* verts_out, int32_t* faces_out,
+                                     int32_t* vert_src, int32_t* face_src, int32_t* counts, float* edge_pos, uint64_t* edge_key,
+                                     uint8_t* edge_reason, void* scratch, size_t scratch_bytes, void* stream);
 /* One round of subdivision of an indexed mesh (csrc/meshsubdiv.hpp).  verts [n_verts][3], faces [n_faces][3] vertex ids; the
  * adjacency of the mesh is built inside the call (arah_mesh_adjacency's launches, in this call's scratch).  The neighbour entry
  * (lo, hi) with hi > lo names an edge.  has_threshold = 0: every edge is marked; otherwise an edge is marked when both ends are
@@ -472,6 +483,33 @@ size_t arah_mesh_subdivide_round_scratch_bytes(int64_t n_verts, int64_t n_faces)
 int arah_mesh_subdivide_round(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t method,
                               int32_t has_threshold, double max_len2, float* verts_out, int32_t* faces_out, int32_t* vert_src,
                               int32_t* face_src, int32_t* counts, void* scratch, size_t scratch_bytes, void* stream);
+/* One round of edge flips of an indexed mesh (csrc/meshflip.hpp).  verts [n_verts][3], faces [n_faces][3] vertex ids; the
+ * adjacency of the mesh is built inside the call (arah_mesh_adjacency's launches, in this call's scratch).  The neighbour entry
+ * i = (u, v) with v > u names the edge {u, v}, i is its id.  An edge is a candidate unless, in this order: (1) the entry does not
+ * carry one face each way; (2) a = b, the third corners of the faces traversing u->v (fa) and v->u (fb); (3) b is a neighbour of
+ * a; (4) one of u, v, a, b has a non-finite coordinate; (5) the criterion does not ask for the flip -- criterion 0 (Delaunay):
+ * with Na = (u - a) x (v - a), Nb = (v - b) x (u - b), d_x = (u - x).(v - x) and c_x = |N_x|^2 in double, every operation rounded
+ * on its own and sums taken left to right, it asks when d_a < 0 and d_b < 0, never when both are >= 0, and otherwise when
+ * (d_n d_n) c_o > (d_o d_o) c_n, n the corner with the negative d and o the other -- and the same test of the flipped edge {a,
+ * b} with the corners u, v and the new faces' cross products must NOT ask (rounding lets a nearly co-circular quad ask both
+ * ways); criterion 1 (valence): with deg the number
+ * of neighbours and the target 4 for a vertex on a boundary (vert_flags bit 0) and 6 otherwise, it asks when the sum of |deg -
+ * target| over u, v, a, b is strictly smaller with u, v one lower and a, b one higher; (6) one of the cross products of the
+ * corners (a, u, b) and (b, v, a) has a dot product <= 0 (or not a number) with Na or Nb.  key = (hash32(i ^ salt 0x9e3779b9) <<
+ * 32) | i with hash32(x): x ^= x >> 16, x *= 0x7feb352d, x ^= x >> 15, x *= 0x846ca68b, x ^= x >> 16 on 32-bit integers.  lock[x] =
+ * the least key of the candidates with x among u, v, a, b; a candidate is selected when its four locks hold its key, so selected
+ * flips share no vertex.  -> faces_out [n_faces][3]: the input's rows, row fa = (a, u, b) and row fb = (b, v, a) for a selected
+ * edge; face_flag [n_faces]: 1 for a rewritten row; counts (device int32[9]) = edges, candidates, selected, edges with reason 1
+ * .. 6; edge_key [6 n_faces] (all ones: no candidate), edge_reason [6 n_faces] (0 candidate, 1 .. 6, 255: the entry names no
+ * edge) for every neighbour entry.  Integer atomics only (min, add): the result is unique, and equal to meshing.mesh_flip_round
+ * bit for bit.  criterion 0 or 1, sizes as for arah_mesh_adjacency, otherwise ARAH_E_BADARG without a launch and a scratch size
+ * of 0; scratch: arah_mesh_flip_round_scratch_bytes(n_verts, n_faces) device bytes, 256-byte aligned, ARAH_E_WORKSPACE when
+ * short, without a launch.  Empty inputs still write counts; pointers of empty arrays may be NULL.  No host synchronisation, no
+ * allocation. */
+size_t arah_mesh_flip_round_scratch_bytes(int64_t n_verts, int64_t n_faces);
+int arah_mesh_flip_round(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t criterion, uint32_t salt,
+                         int32_t* faces_out, uint8_t* face_flag, int32_t* counts, uint64_t* edge_key, uint8_t* edge_reason,
+                         void* scratch, size_t scratch_bytes, void* stream);
 /* Per-vertex normals of an indexed mesh from the mesh itself (pytorch3d verts_normals_packed): verts [n_verts][3], faces
  * [n_faces][3], vf_start / vf of arah_mesh_adjacency on the same mesh.  Vertex v walks its incident faces in the order of vf
  * (ascending id); a face with a non-finite corner contributes nothing, the others (p1 - p0) x (p2 - p0) with the corners widened to
@@ -492,6 +530,16 @@ int arah_mesh_vertex_normals(const float* verts, int64_t n_verts, const int32_t*
  * launches nothing. */
 int arah_mesh_smooth(const float* verts, int64_t n_verts, const int32_t* nbr_start, const int32_t* nbr, const uint8_t* vert_flags,
                      int32_t n_steps, const float h_factors[2], int32_t pin, float* tmp, float* verts_out, void* stream);
+/* One step of tangential relaxation of an indexed mesh: arah_mesh_smooth's gather with the part of the move along the vertex
+ * normal taken out.  nbr_start / nbr / vert_flags of arah_mesh_adjacency and normal_sum [n_verts][3] (double) of
+ * arah_mesh_vertex_normals on the same mesh.  A vertex moves when it is finite, has neither bit 0 nor bit 1 of vert_flags, has a
+ * finite neighbour, and nn = (N0 N0 + N1 N1) + N2 N2 of its normal_sum N is finite and > 0: s = the double sum of its finite
+ * neighbours in ascending id, m their number, d = s / m - p, t = ((d0 N0 + d1 N1) + d2 N2) / nn, new = float32(p + factor (d -
+ * t N)) in double, every operation rounded on its own; no square root.  All other vertices are copied bit for bit.  -> verts_out
+ * [n_verts][3], equal to meshing.mesh_tangential_step bit for bit.  A gather: no atomics, no scratch.  factor finite, n_verts <
+ * 2^31, otherwise ARAH_E_BADARG without a launch.  No host synchronisation, no allocation. */
+int arah_mesh_tangential(const float* verts, int64_t n_verts, const int32_t* nbr_start, const int32_t* nbr, const uint8_t* vert_flags,
+                         const double* normal_sum, float factor, float* verts_out, void* stream);
 /* Consistent orientation of an indexed mesh (csrc/meshorient.hpp; meshing.mesh_orient is the rule, bit for bit).  faces
  * [n_faces][3], and vf_start / vf / nbr_start / nbr / nbr_out / nbr_in of arah_mesh_adjacency on the same mesh.  Two valid faces are
  * neighbours across an edge that carries exactly two valid faces, consistent when they traverse it in opposite directions; the
