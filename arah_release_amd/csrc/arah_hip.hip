@@ -1955,6 +1955,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_canon_solve(FrameDev fr, const 
 #include "meshcc.hpp"
 #include "meshsimp.hpp"
 #include "meshadj.hpp"
+#include "meshlaplace.hpp"
 #include "meshquadric.hpp"
 #include "meshcollapse.hpp"
 #include "meshsubdiv.hpp"
@@ -4934,6 +4935,121 @@ int arah_mesh_tangential(const float* verts, int64_t n_verts, const int32_t* nbr
     hipLaunchKernelGGL(k_ma_tangential, dim3(mesh_grid(n_verts)), dim3(kImeshThreads), 0, reinterpret_cast<hipStream_t>(stream), verts,
                        (int)n_verts, (const int*)nbr_start, (const int*)nbr, (const unsigned char*)vert_flags, normal_sum, (double)factor,
                        verts_out);
+    return check_launch();
+}
+
+// ---- the cotangent Laplacian, curvatures and cotangent smoothing (csrc/meshlaplace.hpp) ----------------------------------------
+extern "C++" {   // a template cannot have the C linkage of the entries around it
+// the two memsets and the two launches of the operator; FULL = false: the weights alone (diag, area, angle_sum may be null)
+template <bool FULL>
+static int ml_launch_cotangent(hipStream_t s, const float* verts, int V, const int32_t* faces, int F, const int32_t* vf_start,
+                               const int32_t* vf, const int32_t* nbr_start, const int32_t* nbr, int mass, double* weight, double* diag,
+                               double* area, double* angle_sum, int32_t* counts) {
+    if (hipMemsetAsync(counts, 0, sizeof(int32_t) * kMlCounts, s) != hipSuccess) return ARAH_E_LAUNCH;
+    if (F > 0 && hipMemsetAsync(weight, 0, sizeof(double) * 6 * (size_t)F, s) != hipSuccess) return ARAH_E_LAUNCH;
+    if (V == 0) return ARAH_OK;
+    hipLaunchKernelGGL((k_ml_cot_short<FULL>), dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, verts, V, (const int*)faces, F,
+                       (const int*)vf_start, (const int*)vf, (const int*)nbr_start, (const int*)nbr, mass, weight, diag, area, angle_sum,
+                       (int*)counts);
+    if (F > kMaShort)   // a vertex with more than kMaShort incident faces needs that many faces
+        hipLaunchKernelGGL((k_ml_cot_long<FULL>), dim3(min(V, kMaLongGrid)), dim3(kImeshThreads), 0, s, verts, V, (const int*)faces, F,
+                           (const int*)vf_start, (const int*)vf, (const int*)nbr_start, (const int*)nbr, mass, weight, diag, area,
+                           angle_sum, (int*)counts);
+    return ARAH_OK;
+}
+}
+
+int arah_mesh_cotangent(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int32_t* vf_start,
+                        const int32_t* vf, const int32_t* nbr_start, const int32_t* nbr, int32_t mass, double* weight, double* diag,
+                        double* area, double* angle_sum, int32_t* counts, void* stream) {
+    if (!ma_sizes_ok(n_verts, n_faces) || !vf_start || !nbr_start || !counts || (mass != 0 && mass != 1)) return ARAH_E_BADARG;
+    if ((n_verts > 0 && (!verts || !diag || !area || !angle_sum)) || (n_faces > 0 && (!faces || !vf || !nbr || !weight))) return ARAH_E_BADARG;
+    if (int rc = ml_launch_cotangent<true>(reinterpret_cast<hipStream_t>(stream), verts, (int)n_verts, faces, (int)n_faces, vf_start, vf,
+                                           nbr_start, nbr, mass, weight, diag, area, angle_sum, counts))
+        return rc;
+    return check_launch();
+}
+
+int arah_mesh_laplacian_apply(const double* weight, const int32_t* nbr_start, const int32_t* nbr, int64_t n_verts, int64_t n_faces,
+                              const void* x, int32_t x_is_f64, int32_t n_channels, double* y, void* stream) {
+    if (!ma_sizes_ok(n_verts, n_faces) || !nbr_start || n_channels < 1 || n_channels > kMlMaxChannels || (x_is_f64 != 0 && x_is_f64 != 1))
+        return ARAH_E_BADARG;
+    if ((n_verts > 0 && (!x || !y)) || (n_faces > 0 && (!weight || !nbr))) return ARAH_E_BADARG;
+    if (n_verts == 0) return ARAH_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int grid = mesh_grid(n_verts * n_channels);
+    if (x_is_f64)
+        hipLaunchKernelGGL((k_ml_apply<double>), dim3(grid), dim3(kImeshThreads), 0, s, weight, (const int*)nbr_start, (const int*)nbr,
+                           (int)n_verts, 6 * (long long)n_faces, (const double*)x, (int)n_channels, y);
+    else
+        hipLaunchKernelGGL((k_ml_apply<float>), dim3(grid), dim3(kImeshThreads), 0, s, weight, (const int*)nbr_start, (const int*)nbr,
+                           (int)n_verts, 6 * (long long)n_faces, (const float*)x, (int)n_channels, y);
+    return check_launch();
+}
+
+int arah_mesh_curvature(const float* verts, int64_t n_verts, int64_t n_faces, const int32_t* nbr_start, const int32_t* nbr,
+                        const uint8_t* vert_flags, const double* weight, const double* area, const double* angle_sum,
+                        const double* normal_sum, double* curv, double* mean_normal, uint8_t* valid, int32_t* counts, void* stream) {
+    if (!ma_sizes_ok(n_verts, n_faces) || !nbr_start || !counts) return ARAH_E_BADARG;
+    if (n_verts > 0 && (!verts || !vert_flags || !area || !angle_sum || !normal_sum || !curv || !mean_normal || !valid)) return ARAH_E_BADARG;
+    if (n_faces > 0 && (!weight || !nbr)) return ARAH_E_BADARG;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (hipMemsetAsync(counts, 0, sizeof(int32_t), s) != hipSuccess) return ARAH_E_LAUNCH;
+    if (n_verts == 0) return ARAH_OK;
+    hipLaunchKernelGGL(k_ml_curvature, dim3(mesh_grid(n_verts)), dim3(kImeshThreads), 0, s, verts, (int)n_verts, (const int*)nbr_start,
+                       (const int*)nbr, 6 * (long long)n_faces, (const unsigned char*)vert_flags, weight, area, angle_sum, normal_sum, curv,
+                       mean_normal, (unsigned char*)valid, (int*)counts);
+    return check_launch();
+}
+
+struct MlapScratch {
+    double* weight;
+    int* counts;
+    size_t bytes;
+};
+
+static MlapScratch carve_smooth_cotangent(void* scratch, int64_t n_faces) {
+    MlapScratch w{};
+    MeshCarver c(scratch);
+    w.weight = c.take<double>(6 * (size_t)n_faces);
+    w.counts = c.take<int>((size_t)kMlCounts);
+    w.bytes = c.bytes();
+    return w;
+}
+
+size_t arah_mesh_smooth_cotangent_scratch_bytes(int64_t n_verts, int64_t n_faces) {
+    if (!ma_sizes_ok(n_verts, n_faces)) return 0;
+    return carve_smooth_cotangent(nullptr, n_faces).bytes;
+}
+
+int arah_mesh_smooth_cotangent(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int32_t* vf_start,
+                               const int32_t* vf, const int32_t* nbr_start, const int32_t* nbr, const uint8_t* vert_flags, int32_t n_steps,
+                               const float factors[2], int32_t pin, float* tmp, float* verts_out, void* scratch, size_t scratch_bytes,
+                               void* stream) {
+    if (!ma_sizes_ok(n_verts, n_faces) || n_steps < 0 || !factors || !vf_start || !nbr_start || !scratch) return ARAH_E_BADARG;
+    if (!std::isfinite(factors[0]) || !std::isfinite(factors[1])) return ARAH_E_BADARG;
+    if (n_verts > 0 && (!verts || !verts_out || !vert_flags || (n_steps > 1 && !tmp))) return ARAH_E_BADARG;
+    if (n_faces > 0 && (!faces || !vf || !nbr)) return ARAH_E_BADARG;
+    const MlapScratch w = carve_smooth_cotangent(scratch, n_faces);
+    if (scratch_bytes < w.bytes) return ARAH_E_WORKSPACE;
+    if (n_verts == 0) return ARAH_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int V = (int)n_verts, F = (int)n_faces;
+    if (n_steps == 0) {
+        hipLaunchKernelGGL(k_ma_copy, dim3(mesh_grid(3 * n_verts)), dim3(kImeshThreads), 0, s, verts, 3 * (long long)n_verts, verts_out);
+        return check_launch();
+    }
+    const float* src = verts;
+    for (int32_t i = 0; i < n_steps; ++i) {   // the last step writes verts_out, the one before tmp, and so on back
+        float* dst = ((n_steps - 1 - i) & 1) ? tmp : verts_out;
+        if (int rc = ml_launch_cotangent<false>(s, src, V, faces, F, vf_start, vf, nbr_start, nbr, 1, w.weight, nullptr, nullptr, nullptr,
+                                                w.counts))
+            return rc;
+        hipLaunchKernelGGL(k_ml_smooth, dim3(mesh_grid(V)), dim3(kImeshThreads), 0, s, src, V, (const int*)nbr_start, (const int*)nbr,
+                           6 * (long long)F, (const unsigned char*)vert_flags, (const double*)w.weight, (double)factors[i & 1],
+                           (int)(pin != 0), dst);
+        src = dst;
+    }
     return check_launch();
 }
 

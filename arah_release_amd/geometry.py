@@ -9,7 +9,9 @@ come in (.npz with `vertices` / `faces`, PLY with triangle faces), and `save_mes
 components on the device"); `simplify_mesh`: fewer vertices and faces by vertex clustering on a grid (DESIGN.md "Simplifying meshes
 on the device") and `decimate_mesh`: fewer by edge collapse, which keeps a closed surface closed (DESIGN.md "Edge-collapse
 decimation on the device"); `mesh_adjacency` / `mesh_topology` / `vertex_normals` / `smooth_mesh`: who is adjacent to whom, whether a mesh is
-watertight, the mesh's own normals, and Laplacian / Taubin smoothing (DESIGN.md "Adjacency, normals and smoothing on the device").
+watertight, the mesh's own normals, and Laplacian / Taubin smoothing (DESIGN.md "Adjacency, normals and smoothing on the device");
+`mesh_laplacian` / `laplacian_matrix` / `apply_laplacian` / `mesh_curvature`: the cotangent Laplacian with its lumped mass, and mean,
+Gaussian and principal curvatures (DESIGN.md "Cotangent operator and curvature on the device").
 Ground truth that is a SCAN -- a point cloud, with or without normals -- is scored through the exact
 nearest-point query hip.point_index / hip.point_nearest (DESIGN.md "Scoring against point clouds"): `PointCloud`, `nearest_points`,
 `load_points` / `save_points` / `load_geometry`, and F-scores at distance thresholds (`thresholds=` of `mesh_metrics`).
@@ -19,6 +21,7 @@ on the same index (DESIGN.md "Casting rays against meshes on the device").  Whet
 hip.mesh_contains / hip.mesh_contains_grid (DESIGN.md "Containment, occupancy grids and IoU on the device")."""
 import collections
 import math
+import warnings
 
 import numpy as np
 import torch
@@ -1250,7 +1253,7 @@ faces incident to every vertex (ids ascending); nbr_start (V+1,) / nbr (6F,) the
 nbr_out / nbr_in (6F,) the faces traversing v->n / n->v; vert_flags (V,) uint8 (1 boundary, 2 non-manifold, 4 no neighbour); counts
 (8,) int32 (valid faces, edges, boundary, non-manifold and misoriented edges, the largest valence, isolated vertices, Euler)."""
 
-_SMOOTH_KEYS = ("iterations", "lamb", "mu", "method", "boundary")
+_SMOOTH_KEYS = ("iterations", "lamb", "mu", "method", "boundary", "weights")
 
 
 def mesh_adjacency(verts_or_n_verts, faces):
@@ -1296,10 +1299,13 @@ def vertex_normals(verts, faces, adjacency=None):
         return _cc_backend(faces).vertex_normals(v32, faces, adjacency=adjacency)[1]
 
 
-def _check_smooth_call(iterations, lamb, mu, method, boundary, what):
+def _check_smooth_call(iterations, lamb, mu, method, boundary, what, weights="uniform"):
     """meshing.check_smooth_args, and method="tangential": iterations and lamb as for "laplacian"; mu is not used, and boundary
     must be "pin" (a tangential step never moves a vertex of a boundary or non-manifold edge).  -> True for "tangential"."""
     from . import meshing
+    meshing.check_smooth_weights(weights, what)
+    if method == "tangential" and weights != "uniform":
+        raise ValueError("%s: method='tangential' has uniform weights only, got weights=%r" % (what, weights))
     if method != "tangential":
         meshing.check_smooth_args(iterations, lamb, mu, method, boundary, what)
         return False
@@ -1309,7 +1315,7 @@ def _check_smooth_call(iterations, lamb, mu, method, boundary, what):
     return True
 
 
-def smooth_mesh(verts, faces, iterations=10, lamb=0.5, mu=-0.53, method="taubin", boundary="pin", adjacency=None):
+def smooth_mesh(verts, faces, iterations=10, lamb=0.5, mu=-0.53, method="taubin", boundary="pin", adjacency=None, weights="uniform"):
     """Smooth an indexed mesh with the umbrella operator: every step moves a vertex towards (lamb > 0) or away from (mu < 0) the
     mean of its neighbours, p + f (mean - p), uniform weights.  method="taubin" (Taubin 1995, "A signal processing approach to
     fair surface design"): an iteration is a lamb step and a mu step, a low-pass filter that does not shrink the mesh the way
@@ -1323,8 +1329,14 @@ def smooth_mesh(verts, faces, iterations=10, lamb=0.5, mu=-0.53, method="taubin"
     vertex normal, which is taken from the mesh at hand (`vertex_normals`' unnormalised sum, recomputed every iteration).  Vertices
     slide along the surface: the triangles even out and the shape neither shrinks nor loses detail the way it does along the
     normal.  Vertices of boundary and non-manifold edges stay (boundary must be "pin"); mu is not used.  hip.mesh_tangential_step
-    on the GPU, meshing.mesh_tangential_step on the host, equal bit for bit."""
-    tangential = _check_smooth_call(iterations, lamb, mu, method, boundary, "smooth_mesh")
+    on the GPU, meshing.mesh_tangential_step on the host, equal bit for bit.
+
+    weights="cotangent" (with "taubin" or "laplacian"): every step takes the cotangent weights of the positions it reads
+    (`mesh_laplacian`) instead of uniform ones: p + f (sum w (q - p)) / (sum |w|), the explicit mean-curvature flow.  On a flat
+    patch it does not move a vertex at all, whatever the sampling, where the uniform mean drags vertices along
+    the surface towards their denser side: the choice for decimated, adaptively subdivided and marching-cubes meshes.  It costs
+    the operator once per step.  hip.mesh_smooth on the GPU, meshing.mesh_smooth on the host, equal bit for bit."""
+    tangential = _check_smooth_call(iterations, lamb, mu, method, boundary, "smooth_mesh", weights)
     v32, faces, adjacency = _smooth_args(verts, faces, adjacency, "smooth_mesh")
     if tangential:
         backend = _cc_backend(faces)
@@ -1336,8 +1348,115 @@ def smooth_mesh(verts, faces, iterations=10, lamb=0.5, mu=-0.53, method="taubin"
                 v32 = backend.mesh_tangential_step(v32, faces, normal_sum, lamb, adjacency=adjacency)
         return v32
     with torch.no_grad():
+        if weights == "uniform":                                                  # the call as it always was
+            return _cc_backend(faces).mesh_smooth(v32, faces, iterations, lamb=lamb, mu=mu, method=method, boundary=boundary,
+                                                  adjacency=adjacency)
         return _cc_backend(faces).mesh_smooth(v32, faces, iterations, lamb=lamb, mu=mu, method=method, boundary=boundary,
-                                              adjacency=adjacency)
+                                              adjacency=adjacency, weights=weights)
+
+
+# ---- the cotangent Laplacian and curvatures ---------------------------------------------------------------------------------------
+def mesh_laplacian(verts, faces, mass="mixed", adjacency=None):
+    """The cotangent Laplacian of an indexed mesh with its lumped mass (hip.mesh_cotangent on the GPU, meshing.mesh_cotangent --
+    which states the rule -- on the host): verts (V,3), faces (F,3) integer ids, mass "mixed" (Meyer et al.'s Voronoi cells, safe
+    with obtuse triangles) or "barycentric" (a third of the incident faces), adjacency a `mesh_adjacency` built earlier or None.
+    -> dict of weight (6F,) float64 -- for the entry (v, n) of adjacency.nbr half the sum of the cotangents opposite to the edge,
+    the same bits from both ends --, diag (V,) the row sums, area (V,) the lumped mass, angle_sum (V,) the sum of the angles at the
+    vertex, adjacency (the MeshAdjacency used) and report: the counts by name (meshing.COTANGENT_COUNTS: faces, degenerate,
+    nonfinite, obtuse, negative_edges, bad_area) as Python numbers, one host synchronisation.  negative_edges are the edges that are
+    not locally Delaunay: `flip_edges`("delaunay") removes them where the surface allows it.  Everything stays on the mesh's
+    device; hand the dict to `laplacian_matrix`, `apply_laplacian` and `mesh_curvature`."""
+    from . import meshing
+    v32, faces, adjacency = _smooth_args(verts, faces, adjacency, "mesh_laplacian")
+    backend = _cc_backend(faces)
+    with torch.no_grad():
+        if adjacency is None:
+            adjacency = backend.mesh_adjacency(faces, int(v32.shape[0]))
+        weight, diag, area, angle_sum, counts = backend.mesh_cotangent(v32, faces, mass, adjacency=adjacency)
+    return {"weight": weight, "diag": diag, "area": area, "angle_sum": angle_sum, "adjacency": MeshAdjacency(*adjacency),
+            "report": dict(zip(meshing.COTANGENT_COUNTS, counts.tolist())), "mass": mass}
+
+
+def _check_laplacian(lap, what):
+    if not isinstance(lap, dict) or any(k not in lap for k in ("weight", "diag", "area", "angle_sum", "adjacency")):
+        raise ValueError("%s: lap must be the dict of mesh_laplacian" % what)
+    return lap
+
+
+def laplacian_matrix(lap, kind="stiffness"):
+    """The operator of `mesh_laplacian` as a torch sparse CSR matrix (V, V) float64 on the mesh's device: off-diagonals weight,
+    diagonal -diag, so that L x = `apply_laplacian`(lap, x) up to the order of the sums; kind="normalized": every row divided by
+    the vertex's area (rows of vertices whose area is not > 0 are not finite).  "stiffness" is symmetric, negative semi-definite,
+    with zero row sums.  Built from the neighbour CSR that is already there -- the diagonal is merged into each sorted row by its
+    position, no sort."""
+    lap = _check_laplacian(lap, "laplacian_matrix")
+    if kind not in ("stiffness", "normalized"):
+        raise ValueError("laplacian_matrix: kind must be 'stiffness' or 'normalized', got %r" % (kind,))
+    adj = lap["adjacency"]
+    start, nbr = adj.nbr_start.long(), adj.nbr.long()
+    V, dev = int(start.shape[0]) - 1, start.device
+    E = int(start[-1]) if V else 0
+    ids = torch.arange(V, device=dev)
+    deg = start[1:] - start[:-1]
+    row = torch.repeat_interleave(ids, deg)
+    col_off, val_off = nbr[:E], lap["weight"][:E]
+    below = torch.zeros(V, dtype=torch.int64, device=dev).index_add_(0, row, (col_off < row).long())   # neighbours in front of v
+    # row v holds deg[v] + 1 entries: its neighbours below v, v itself, the neighbours above
+    crow = torch.zeros(V + 1, dtype=torch.int64, device=dev)
+    crow[1:] = torch.cumsum(deg + 1, 0)
+    k = torch.arange(E, device=dev) - start[:-1][row]                             # position inside the neighbour row
+    at_off = crow[:-1][row] + k + (k >= below[row]).long()
+    at_diag = crow[:-1] + below
+    cols = torch.empty(E + V, dtype=torch.int64, device=dev)
+    vals = torch.empty(E + V, dtype=torch.float64, device=dev)
+    cols[at_off], vals[at_off] = col_off, val_off
+    cols[at_diag], vals[at_diag] = ids, -lap["diag"]
+    if kind == "normalized":
+        vals = vals / lap["area"][torch.repeat_interleave(ids, deg + 1)]
+    with warnings.catch_warnings():                                              # torch announces its CSR support as beta, once
+        warnings.filterwarnings("ignore", message="Sparse CSR tensor support is in beta state")
+        return torch.sparse_csr_tensor(crow, cols, vals, size=(V, V), dtype=torch.float64, device=dev)
+
+
+def apply_laplacian(lap, x):
+    """L x for the dict of `mesh_laplacian`: x (V,) or (V,C) float32 or float64 with C <= 32, on the mesh's device.  -> float64 of
+    the same shape: y[v] = sum over the neighbours in ascending id of weight (x[n] - x[v]); neighbours whose x is not finite are
+    skipped.  Divide by lap["area"] for the pointwise Laplace-Beltrami operator.  hip.laplacian_apply on the GPU,
+    meshing.laplacian_apply on the host, equal bit for bit."""
+    lap = _check_laplacian(lap, "apply_laplacian")
+    if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2):
+        raise ValueError("apply_laplacian: x must be a (V,) or (V, C) tensor")
+    x2 = x.detach()[:, None] if x.dim() == 1 else x.detach()
+    with torch.no_grad():
+        y = _cc_backend(lap["weight"]).laplacian_apply(lap["weight"], tuple(lap["adjacency"]), x2.contiguous())
+    return y[:, 0] if x.dim() == 1 else y
+
+
+def mesh_curvature(verts, faces, mass="mixed", adjacency=None, laplacian=None):
+    """Mean, Gaussian and principal curvatures at the vertices of an indexed mesh (Meyer, Desbrun, Schroeder, Barr 2002, "Discrete
+    differential-geometry operators for triangulated 2-manifolds"; meshing.mesh_curvature states the rule): verts (V,3), faces
+    (F,3) integer ids, mass as in `mesh_laplacian`, adjacency a `mesh_adjacency` built earlier or None, laplacian the dict of
+    `mesh_laplacian` of this mesh or None.  -> dict of mean, mean_abs, gaussian, k1 >= k2 (V,) float64, mean_normal (V,3) float64
+    (the mean-curvature normal, half of the Laplacian of the positions over the area), area (V,), valid (V,) bool and report (the
+    operator's counts and invalid_vertices; one host synchronisation).  mean_abs = |mean_normal| carries no sign; mean takes its sign
+    from the mesh's own orientation: > 0 on a convex part of a mesh with counter-clockwise faces seen from outside, and < 0 THERE
+    ON THE PROJECT'S OWN LEVEL SETS, whose marching-cubes faces are clockwise seen from outside.  gaussian is the angle defect over
+    the area (pi instead of 2 pi on a boundary).  Vertices on non-manifold edges, without a face, with a non-finite coordinate or
+    without area are invalid: NaN, valid False.  hip.mesh_curvature on the GPU, meshing.mesh_curvature on the host: equal bit for
+    bit but for the last bits of the angles' atan2."""
+    v32, faces, adjacency = _smooth_args(verts, faces, adjacency, "mesh_curvature")
+    backend = _cc_backend(faces)
+    with torch.no_grad():
+        if laplacian is None:
+            laplacian = mesh_laplacian(v32, faces, mass, adjacency)
+        lap = _check_laplacian(laplacian, "mesh_curvature")
+        adj = tuple(lap["adjacency"])
+        curv, mean_normal, valid, counts = backend.mesh_curvature(
+            v32, faces, mass, adjacency=adj, laplacian=(lap["weight"], lap["diag"], lap["area"], lap["angle_sum"]))
+    out = {name: curv[:, i].contiguous() for i, name in enumerate(("mean", "mean_abs", "gaussian", "k1", "k2"))}
+    out.update(mean_normal=mean_normal, area=lap["area"], valid=valid.bool(),
+               report=dict(lap["report"], invalid_vertices=int(counts[0])))
+    return out
 
 
 # ---- orientation, boundary loops, hole filling -----------------------------------------------------------------------------------
@@ -1532,7 +1651,7 @@ def mesh_intersections(mesh_a, mesh_b, max_pairs=1 << 20, return_pairs=True):
 
 def check_smooth(smooth):
     """Validate a `smooth` option of the model's mesh entries and return the keywords of `smooth_mesh` it stands for: None
-    (nothing), a number of iterations (an integer >= 0), or a dict of iterations / lamb / mu / method / boundary.  ValueError for
+    (nothing), a number of iterations (an integer >= 0), or a dict of iterations / lamb / mu / method / boundary / weights.  ValueError for
     anything else."""
     from . import meshing
     if smooth is None:
@@ -1547,7 +1666,7 @@ def check_smooth(smooth):
     else:
         raise ValueError("smooth must be None, a number of iterations or a dict of smooth_mesh keywords, got %r" % (smooth,))
     _check_smooth_call(kw.get("iterations", 10), kw.get("lamb", 0.5), kw.get("mu", -0.53), kw.get("method", "taubin"),
-                       kw.get("boundary", "pin"), "smooth")
+                       kw.get("boundary", "pin"), "smooth", kw.get("weights", "uniform"))
     return kw
 
 

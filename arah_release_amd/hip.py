@@ -147,6 +147,8 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_mesh_subdivide_round_scratch_bytes", "arah_mesh_subdivide_round",
            "arah_mesh_flip_round_scratch_bytes", "arah_mesh_flip_round",
            "arah_mesh_adjacency_scratch_bytes", "arah_mesh_adjacency", "arah_mesh_vertex_normals", "arah_mesh_smooth", "arah_mesh_tangential",
+           "arah_mesh_cotangent", "arah_mesh_laplacian_apply", "arah_mesh_curvature", "arah_mesh_smooth_cotangent_scratch_bytes",
+           "arah_mesh_smooth_cotangent",
            "arah_mesh_orient_scratch_bytes", "arah_mesh_orient", "arah_mesh_boundary_loops_scratch_bytes",
            "arah_mesh_boundary_loops", "arah_mesh_fill_holes_scratch_bytes", "arah_mesh_fill_holes",
            "arah_mesh_rasterize", "arah_mesh_rasterize_debug", "arah_mesh_interpolate", "arah_mesh_raycast", "arah_mesh_raycast_debug",
@@ -202,6 +204,7 @@ def load_library():
     for name in ("arah_mesh_components_scratch_bytes", "arah_mesh_select_scratch_bytes", "arah_mesh_adjacency_scratch_bytes",
                  "arah_mesh_quadric_place_scratch_bytes", "arah_mesh_collapse_round_scratch_bytes",
                  "arah_mesh_subdivide_round_scratch_bytes", "arah_mesh_flip_round_scratch_bytes",
+                 "arah_mesh_smooth_cotangent_scratch_bytes",
                  "arah_mesh_orient_scratch_bytes", "arah_mesh_boundary_loops_scratch_bytes", "arah_mesh_fill_holes_scratch_bytes"):
         getattr(lib, name).restype = C.c_size_t
         getattr(lib, name).argtypes = [C.c_int64, C.c_int64]
@@ -1186,15 +1189,16 @@ def vertex_normals(verts, faces, adjacency=None):
     return normal_sum, normals
 
 
-def mesh_smooth(verts, faces, iterations, lamb=0.5, mu=-0.53, method="taubin", boundary="pin", adjacency=None):
+def mesh_smooth(verts, faces, iterations, lamb=0.5, mu=-0.53, method="taubin", boundary="pin", adjacency=None, weights="uniform"):
     """Laplacian / Taubin umbrella smoothing of an indexed mesh (arah_mesh_smooth): verts (V,3) float32 and faces (F,3) integer ids
     on the GPU, the keywords of meshing.mesh_smooth, adjacency: `mesh_adjacency` of them, or None to build it here.  ->
     verts_out (V,3) float32, meshing.mesh_smooth bit for bit.  All steps inside one C call, between two buffers; no atomics, no
-    host synchronisation."""
+    host synchronisation.  weights="cotangent": arah_mesh_smooth_cotangent, the weights of every step in the call's scratch."""
     from . import meshing
     require_gpu()
     lib = load_library()
     factors, pin = meshing.check_smooth_args(iterations, lamb, mu, method, boundary)
+    meshing.check_smooth_weights(weights)
     v, f, V, F, adj = _mesh_adj_args(verts, faces, adjacency, "mesh_smooth")
     dev = v.device
     n_steps = int(iterations) * len(factors)
@@ -1203,6 +1207,13 @@ def mesh_smooth(verts, faces, iterations, lamb=0.5, mu=-0.53, method="taubin", b
     with _on_device(dev):
         out = torch.empty(V, 3, dtype=torch.float32, device=dev)
         tmp = torch.empty(V, 3, dtype=torch.float32, device=dev) if n_steps > 1 else None
+        if weights == "cotangent":
+            scratch = _mesh_cc_buf(dev, int(lib.arah_mesh_smooth_cotangent_scratch_bytes(V, F)))
+            _check(lib.arah_mesh_smooth_cotangent(_ptr(v), C.c_int64(V), _ptr(f), C.c_int64(F), _ptr(adj[0]), _ptr(adj[1]), _ptr(adj[2]),
+                                                  _ptr(adj[3]), _ptr(adj[6]), C.c_int32(n_steps),
+                                                  (C.c_float * 2)(factors[0], factors[-1]), C.c_int32(int(pin)), _ptr(tmp), _ptr(out),
+                                                  _ptr(scratch), C.c_size_t(scratch.numel()), _stream()), "arah_mesh_smooth_cotangent")
+            return out
         _check(lib.arah_mesh_smooth(_ptr(v), C.c_int64(V), _ptr(adj[2]), _ptr(adj[3]), _ptr(adj[6]), C.c_int32(n_steps),
                                     (C.c_float * 2)(factors[0], factors[-1]), C.c_int32(int(pin)), _ptr(tmp), _ptr(out), _stream()),
                "arah_mesh_smooth")
@@ -1229,6 +1240,88 @@ def mesh_tangential_step(verts, faces, normal_sum, lamb=0.5, adjacency=None):
         _check(lib.arah_mesh_tangential(_ptr(v), C.c_int64(V), _ptr(adj[2]), _ptr(adj[3]), _ptr(adj[6]), _ptr(normal_sum.contiguous()),
                                         C.c_float(factor), _ptr(out), _stream()), "arah_mesh_tangential")
     return out
+
+
+def mesh_cotangent(verts, faces, mass="mixed", adjacency=None):
+    """The cotangent Laplacian of an indexed mesh (arah_mesh_cotangent, csrc/meshlaplace.hpp): verts (V,3) float32 and faces (F,3)
+    integer ids on the GPU, mass "barycentric" or "mixed", adjacency: `mesh_adjacency` of them, or None to build it here.  ->
+    weight (6F,), diag, area, angle_sum (V,) float64 and counts (8,) int32 as meshing.mesh_cotangent describes them: bit for bit,
+    except angle_sum by the device's atan2.  A gather: no floating-point atomics, no host synchronisation."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    m = meshing.check_mass(mass)
+    v, f, V, F, adj = _mesh_adj_args(verts, faces, adjacency, "mesh_cotangent")
+    dev, f64 = v.device, torch.float64
+    with _on_device(dev):
+        weight = torch.empty(6 * F, dtype=f64, device=dev)
+        diag, area, angle_sum = (torch.empty(V, dtype=f64, device=dev) for _ in range(3))
+        counts = torch.empty(8, dtype=torch.int32, device=dev)
+        _check(lib.arah_mesh_cotangent(_ptr(v), C.c_int64(V), _ptr(f), C.c_int64(F), _ptr(adj[0]), _ptr(adj[1]), _ptr(adj[2]),
+                                       _ptr(adj[3]), C.c_int32(m), _ptr(weight), _ptr(diag), _ptr(area), _ptr(angle_sum), _ptr(counts),
+                                       _stream()), "arah_mesh_cotangent")
+    return weight, diag, area, angle_sum, counts
+
+
+def _laplacian_args(weight, adjacency, what):
+    adjacency = tuple(adjacency) if adjacency is not None else ()
+    if len(adjacency) != 8 or any(not isinstance(t, torch.Tensor) or not t.is_cuda for t in adjacency):
+        raise ValueError("%s: adjacency must be the eight arrays of mesh_adjacency, on the GPU" % what)
+    nbr_start, nbr = adjacency[2], adjacency[3]
+    if not isinstance(weight, torch.Tensor) or weight.dtype != torch.float64 or weight.shape != nbr.shape or weight.device != nbr.device \
+            or nbr_start.dtype != torch.int32 or nbr.dtype != torch.int32 or nbr_start.dim() != 1 or nbr_start.shape[0] < 1 \
+            or nbr.dim() != 1 or nbr.shape[0] % 6 or nbr_start.device != nbr.device:
+        raise ValueError("%s: weight must be the (6F,) float64 weights of mesh_cotangent, beside nbr" % what)
+    return weight.detach().contiguous(), nbr_start.contiguous(), nbr.contiguous(), int(nbr_start.shape[0]) - 1, int(nbr.shape[0]) // 6
+
+
+def laplacian_apply(weight, adjacency, x):
+    """y = L x (arah_mesh_laplacian_apply): weight of `mesh_cotangent`, adjacency `mesh_adjacency`, x (V,C) float32 or float64 with
+    1 <= C <= 32, all on one GPU.  -> y (V,C) float64, meshing.laplacian_apply bit for bit."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    w, nbr_start, nbr, V, F = _laplacian_args(weight, adjacency, "laplacian_apply")
+    x = meshing._laplacian_x(x, V, w.device, "laplacian_apply").contiguous()
+    dev = w.device
+    with _on_device(dev):
+        y = torch.empty(V, x.shape[1], dtype=torch.float64, device=dev)
+        _check(lib.arah_mesh_laplacian_apply(_ptr(w), _ptr(nbr_start), _ptr(nbr), C.c_int64(V), C.c_int64(F), _ptr(x),
+                                             C.c_int32(int(x.dtype == torch.float64)), C.c_int32(int(x.shape[1])), _ptr(y), _stream()),
+               "arah_mesh_laplacian_apply")
+    return y
+
+
+def mesh_curvature(verts, faces, mass="mixed", adjacency=None, laplacian=None, normal_sum=None):
+    """Mean, Gaussian and principal curvatures at the vertices (arah_mesh_curvature): verts (V,3) float32 and faces (F,3) integer ids
+    on the GPU, and what meshing.mesh_curvature takes; whatever is None is computed here.  -> curv (V,5) float64 (mean, mean_abs,
+    gaussian, k1, k2), mean_normal (V,3) float64, valid (V,) uint8, counts (1,) int32: meshing.mesh_curvature bit for bit given
+    the same angle_sum.  Square roots and divisions happen on the device."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    what = "mesh_curvature"
+    meshing.check_mass(mass, what)
+    v, f, V, F, adj = _mesh_adj_args(verts, faces, adjacency, what)
+    dev, f64 = v.device, torch.float64
+    if laplacian is None:
+        laplacian = mesh_cotangent(v, f, mass, adj)
+    weight, _, area, angle_sum = tuple(laplacian)[:4]
+    if normal_sum is None:
+        normal_sum = vertex_normals(v, f, adj)[0]
+    for t, shape in ((weight, (6 * F,)), (area, (V,)), (angle_sum, (V,)), (normal_sum, (V, 3))):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != f64 or t.device != dev:
+            raise ValueError("%s: laplacian must be the outputs of mesh_cotangent, normal_sum of vertex_normals, on %s" % (what, dev))
+    with _on_device(dev):
+        curv = torch.empty(V, 5, dtype=f64, device=dev)
+        mean_normal = torch.empty(V, 3, dtype=f64, device=dev)
+        valid = torch.empty(V, dtype=torch.uint8, device=dev)
+        counts = torch.empty(1, dtype=torch.int32, device=dev)
+        _check(lib.arah_mesh_curvature(_ptr(v), C.c_int64(V), C.c_int64(F), _ptr(adj[2]), _ptr(adj[3]), _ptr(adj[6]),
+                                       _ptr(weight.contiguous()), _ptr(area.contiguous()), _ptr(angle_sum.contiguous()),
+                                       _ptr(normal_sum.contiguous()), _ptr(curv), _ptr(mean_normal), _ptr(valid), _ptr(counts),
+                                       _stream()), "arah_mesh_curvature")
+    return curv, mean_normal, valid, counts
 
 
 def _mesh_adj_only(faces, n_verts, adjacency, what):

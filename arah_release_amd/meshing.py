@@ -713,7 +713,13 @@ def check_smooth_args(iterations, lamb, mu, method, boundary, what="mesh_smooth"
     return ((lam32, mu32) if method == "taubin" else (lam32,)), boundary == "pin"
 
 
-def mesh_smooth(verts, faces, iterations, lamb=0.5, mu=-0.53, method="taubin", boundary="pin", adjacency=None):
+def check_smooth_weights(weights, what="mesh_smooth"):
+    if not isinstance(weights, str) or weights not in ("uniform", "cotangent"):
+        raise ValueError("%s: weights must be 'uniform' or 'cotangent', got %r" % (what, weights))
+    return weights
+
+
+def mesh_smooth(verts, faces, iterations, lamb=0.5, mu=-0.53, method="taubin", boundary="pin", adjacency=None, weights="uniform"):
     """Umbrella smoothing of an indexed mesh: verts (V,3) float32, faces (F,3) integer ids, adjacency: `mesh_adjacency` of them, or
     None.  One STEP with the factor f (the float32 value of lamb or mu, widened to float64): a vertex moves when it is finite, is
     not pinned and has a finite neighbour; s = the float64 sum of its finite unique neighbours in ascending id, m their number,
@@ -722,10 +728,24 @@ def mesh_smooth(verts, faces, iterations, lamb=0.5, mu=-0.53, method="taubin", b
     (Taubin 1995: the second, negative step undoes the shrinkage of the first); "laplacian": a lamb step only.  boundary="pin":
     the vertices with vert_flags bit 0 or 1 (on a boundary or a non-manifold edge) never move; "free": they move like the others.
     lamb in (0, 1], mu in [-1.1, 0), iterations >= 0.  -> verts_out (V,3) float32; faces, the vertex count and the order stay.
-    The specification of arah_mesh_smooth (csrc/meshadj.hpp), and what runs for meshes on the host."""
+    The specification of arah_mesh_smooth (csrc/meshadj.hpp), and what runs for meshes on the host.
+
+    weights="cotangent" (the default "uniform" is the rule above): every step first takes weight = `mesh_cotangent` (mass
+    "mixed"; the weights do not depend on it) of the positions it reads, and uses the entries (v, n) whose neighbour is finite and
+    whose weight is finite.  A vertex moves when it is finite, is not pinned and s = the sum of |weight| over those entries in
+    ascending neighbour id is finite and > 0: acc = the sum of weight (q - p) over the same entries in the same order, the weights
+    with their own signs, new = float32(p + f (acc / s)).  The step is the explicit mean-curvature flow, normalised by the weights
+    (not by the area) so that lamb keeps its meaning.  On a flat patch acc vanishes, whatever the sampling and whether or not the
+    triangulation is Delaunay; clamping the negative weights at 0 would lose exactly that (one step then moves the interior
+    vertices of a jittered planar grid by 5 % of a cell), so nothing is clamped, and |weight| in the denominator keeps every step
+    inside the vertex's 1-ring: |acc| / s <= max |q - p|.  The specification of arah_mesh_smooth_cotangent
+    (csrc/meshlaplace.hpp)."""
     factors, pin = check_smooth_args(iterations, lamb, mu, method, boundary)
+    check_smooth_weights(weights)
     verts, faces, V, _ = _mesh_verts(verts, faces, "mesh_smooth")
     adjacency = _adjacency_of(faces, V, adjacency, "mesh_smooth")
+    if weights == "cotangent":
+        return _mesh_smooth_cotangent(verts, faces, V, int(iterations), factors, pin, adjacency)
     nbr_start, nbr, flags = adjacency[2], adjacency[3], adjacency[6]
     cur = verts.clone()
     F = int(faces.shape[0])
@@ -799,6 +819,260 @@ def mesh_tangential_step(verts, faces, normal_sum, lamb=0.5, adjacency=None):
     t = ((d[:, 0] * N[:, 0] + d[:, 1] * N[:, 1]) + d[:, 2] * N[:, 2]) / nn
     new = (p + f * (d - t[:, None] * N)).float()
     return torch.where(moves[:, None], new, verts)
+
+
+# ---- the cotangent Laplacian, curvatures, cotangent smoothing ------------------------------------------------------------------------
+TWO_PI = 6.283185307179586             # the doubles nearest to 2 pi and pi: kMlTwoPi, kMlPi
+PI = 3.141592653589793
+COTANGENT_MASSES = ("barycentric", "mixed")                                      # the kernel's mass 0, 1
+COTANGENT_COUNTS = ("faces", "degenerate", "nonfinite", "obtuse", "negative_edges", "bad_area")   # counts[0 .. 5] of 8
+CURVATURE_FIELDS = ("mean", "mean_abs", "gaussian", "k1", "k2")                  # the columns of mesh_curvature's first output
+LAPLACIAN_MAX_CHANNELS = 32
+
+
+def check_mass(mass, what="mesh_cotangent"):
+    if not isinstance(mass, str) or mass not in COTANGENT_MASSES:
+        raise ValueError("%s: mass must be 'barycentric' or 'mixed', got %r" % (what, mass))
+    return COTANGENT_MASSES.index(mass)
+
+
+def _sqrt64(x):
+    """The correctly rounded square root: `_sqrt_rn` on the host, the device's own sqrt on a device."""
+    return torch.sqrt(x) if x.is_cuda else _sqrt_rn(x).to(x.device)
+
+
+def _dot3r(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def _first_true3(m):
+    """The first column of the (N,3) mask that is set, -1 when none."""
+    full = torch.full(m.shape[:1], -1, dtype=torch.int64, device=m.device)
+    return torch.where(m[:, 0], full + 1, torch.where(m[:, 1], full + 2, torch.where(m[:, 2], full + 3, full)))
+
+
+def _cotangent_faces(verts, faces, valid, mass):
+    """Per face (F,...): contributing, degenerate, nonfinite, obtuse masks; cot, angle, share (F,3), all 0 where the face does not
+    contribute."""
+    f64, V = torch.float64, int(verts.shape[0])
+    p = verts.to(f64)[faces.clamp(0, max(V - 1, 0))]                             # (F,3,3); rows of skipped faces are never used
+    finite = torch.isfinite(p).all(2).all(1)
+    N = _cross3(p)
+    A2 = _sqrt64(_dot3r(N, N))
+    area_ok = torch.isfinite(A2) & (A2 > 0)
+    contributing = valid & finite & area_ok
+    dot, l2 = [], []
+    for c in range(3):
+        a, b = (c + 1) % 3, (c + 2) % 3
+        u, w, e = p[:, a] - p[:, c], p[:, b] - p[:, c], p[:, b] - p[:, a]
+        dot.append(_dot3r(u, w))
+        l2.append(_dot3r(e, e))
+    dot, l2 = torch.stack(dot, 1), torch.stack(l2, 1)
+    safe = torch.where(contributing, A2, torch.ones_like(A2))[:, None]
+    cot = dot / safe
+    angle = torch.atan2(safe.expand_as(dot), dot)
+    first_obtuse = _first_true3(dot < 0)
+    if mass == 0:
+        share = safe.expand_as(dot)
+    else:
+        vor = torch.stack([(l2[:, (c + 1) % 3] * cot[:, (c + 1) % 3] + l2[:, (c + 2) % 3] * cot[:, (c + 2) % 3]) * 0.125
+                           for c in range(3)], 1)
+        corner = torch.arange(3, device=verts.device)[None, :]
+        share = torch.where((first_obtuse < 0)[:, None], vor, torch.where(first_obtuse[:, None] == corner, safe * 0.25, safe * 0.125))
+    zero = torch.zeros_like(dot)
+    c3 = contributing[:, None]
+    return (contributing, valid & finite & ~area_ok, valid & ~finite, contributing & (first_obtuse >= 0),
+            torch.where(c3, cot, zero), torch.where(c3, angle, zero), torch.where(c3, share, zero))
+
+
+def mesh_cotangent(verts, faces, mass="mixed", adjacency=None):
+    """The cotangent Laplacian of an indexed mesh with its lumped mass: verts (V,3) float32, faces (F,3) integer ids, mass
+    "barycentric" or "mixed", adjacency `mesh_adjacency` of the mesh or None.  Float64 from the float32 inputs, every operation
+    rounded on its own, square roots correctly rounded; atan2 is the only function that is not.
+
+    PER VALID FACE (ids in range and pairwise different) with corners p0, p1, p2 widened to float64.  The face is NONFINITE when a
+    coordinate is not finite.  Otherwise N = (p1 - p0) x (p2 - p0), each component (x y) - (z w) as in `vertex_normals`, nn = (N0
+    N0 + N1 N1) + N2 N2, A2 = sqrt(nn) (the doubled area), and the face is DEGENERATE when A2 is 0 or not finite.  Nonfinite and
+    degenerate faces contribute nothing anywhere.  For corner c of a contributing face, with a = c + 1 and b = c + 2 (mod 3): u =
+    p_a - p_c, w = p_b - p_c, e = p_b - p_a; dot_c = (u0 w0 + u1 w1) + u2 w2; cot_c = dot_c / A2; angle_c = atan2(A2, dot_c); l2_c
+    = (e0 e0 + e1 e1) + e2 e2, the squared length of the opposite edge.
+
+    PER NEIGHBOUR ENTRY (v, n) of the adjacency's nbr: weight = 0.5 acc, where acc starts at 0 and takes acc = acc + cot_o for every
+    contributing face that holds v and n, o its third corner, in ASCENDING FACE ID (the order of vf[v]).  A boundary edge has one
+    term, a non-manifold edge as many as it has faces.  The sum does not depend on the end it is seen from, so (v, n) and (n, v)
+    carry the same bits.  Nothing is clamped.
+
+    PER VERTEX v: diag = the sum of its entries' weights in ascending neighbour id, from 0.  angle_sum = the sum of angle_c, c the
+    corner of v, over its contributing faces in ascending face id, from 0.  area, by the same loop over the faces: "barycentric":
+    (the sum of A2) / 6.  "mixed" (Meyer, Desbrun, Schroeder, Barr 2002): the sum of the faces' shares; with o the FIRST corner of
+    the face (0, 1, 2) with dot_o < 0: none -- the Voronoi share (l2_a cot_a + l2_b cot_b) 0.125; o = c -- A2 0.25; otherwise A2
+    0.125.  Both partition the area of the contributing faces.
+
+    -> weight (6F,) float64 aligned with nbr (rows from nbr_start[V] on are zero), diag, area, angle_sum (V,) float64, counts (8,)
+    int32: COTANGENT_COUNTS -- contributing, degenerate, nonfinite faces; contributing faces with a corner dot < 0; entries with n >
+    v and weight < 0; vertices whose area is not > 0 -- and two zeros.  The ordered sums are loops over k < the widest segment of a
+    padded gather (adding 0.0 for the padding is exact, and a sum that starts at +0 never becomes -0).  The specification of
+    arah_mesh_cotangent (csrc/meshlaplace.hpp), and what runs for meshes on the host."""
+    m = check_mass(mass)
+    verts, faces, V, in_range = _mesh_verts(verts, faces, "mesh_cotangent")
+    adjacency = _adjacency_of(faces, V, adjacency, "mesh_cotangent")
+    vf_start, vf, nbr_start, nbr = adjacency[:4]
+    dev, f64, F = verts.device, torch.float64, int(faces.shape[0])
+    weight = torch.zeros(6 * F, dtype=f64, device=dev)
+    diag, area, angle_sum = (torch.zeros(V, dtype=f64, device=dev) for _ in range(3))
+    if V == 0 or F == 0:
+        return weight, diag, area, angle_sum, torch.tensor([0, 0, 0, 0, 0, V, 0, 0], dtype=torch.int32, device=dev)
+    valid = in_range & (faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 0] != faces[:, 2])
+    contributing, degenerate, nonfinite, obtuse, cot, angle, share = _cotangent_faces(verts, faces, valid, m)
+    ids = torch.arange(V, device=dev)
+    fstart, vfl = vf_start.long(), vf.long()
+    ffirst, fdeg = fstart[:-1], fstart[1:] - fstart[:-1]
+    zero = torch.zeros(V, dtype=f64, device=dev)
+    for k in range(int(fdeg.max())):
+        has = k < fdeg
+        f = vfl[(ffirst + k).clamp(max=3 * F - 1)]
+        c = _first_true3(faces[f] == ids[:, None]).clamp(min=0)
+        angle_sum = angle_sum + torch.where(has, angle[f, c], zero)
+        area = area + torch.where(has, share[f, c], zero)
+    if m == 0:
+        area = area / 6.0
+    nstart, nb = nbr_start.long(), nbr.long()
+    nfirst, ndeg = nstart[:-1], nstart[1:] - nstart[:-1]
+    E = int(nstart[-1])
+    ev, en = torch.repeat_interleave(ids, ndeg), nb[:E]
+    acc = torch.zeros(E, dtype=f64, device=dev)
+    for k in range(int(fdeg.max())):
+        f = vfl[(ffirst[ev] + k).clamp(max=3 * F - 1)]
+        cv, cn = _first_true3(faces[f] == ev[:, None]), _first_true3(faces[f] == en[:, None])
+        hit = (k < fdeg[ev]) & (cv >= 0) & (cn >= 0)
+        acc = acc + torch.where(hit, cot[f, (3 - cv - cn).clamp(0, 2)], torch.zeros_like(acc))
+    weight[:E] = 0.5 * acc
+    for k in range(int(ndeg.max())):
+        diag = diag + torch.where(k < ndeg, weight[(nfirst + k).clamp(max=6 * F - 1)], zero)
+    counts = torch.tensor([int(contributing.sum()), int(degenerate.sum()), int(nonfinite.sum()), int(obtuse.sum()),
+                           int(((en > ev) & (weight[:E] < 0)).sum()), int((~(area > 0)).sum()), 0, 0], dtype=torch.int32, device=dev)
+    return weight, diag, area, angle_sum, counts
+
+
+def _laplacian_x(x, V, dev, what):
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or int(x.shape[0]) != V or x.dtype not in (torch.float32, torch.float64) \
+            or not 1 <= int(x.shape[1]) <= LAPLACIAN_MAX_CHANNELS or x.device != dev:
+        raise ValueError("%s: x must be a (V, C) float32 or float64 tensor with 1 <= C <= %d, on %s" % (what, LAPLACIAN_MAX_CHANNELS, dev))
+    return x.detach()
+
+
+def _laplacian_weight(weight, adjacency, what):
+    """weight (6F,) float64 beside the eight arrays of `mesh_adjacency` -> (weight, nbr_start, nbr, V)."""
+    adjacency = tuple(adjacency) if adjacency is not None else ()
+    if len(adjacency) != 8 or any(not isinstance(t, torch.Tensor) for t in adjacency):
+        raise ValueError("%s: adjacency must be the eight arrays of mesh_adjacency" % what)
+    nbr_start, nbr = adjacency[2], adjacency[3]
+    if not isinstance(weight, torch.Tensor) or weight.dtype != torch.float64 or weight.shape != nbr.shape or weight.device != nbr.device:
+        raise ValueError("%s: weight must be the (6F,) float64 weights of mesh_cotangent, beside nbr" % what)
+    return weight.detach(), nbr_start, nbr, int(nbr_start.shape[0]) - 1
+
+
+def laplacian_apply(weight, adjacency, x):
+    """y = L x for the weights of `mesh_cotangent`: x (V,C) float32 or float64, 1 <= C <= 32.  y[v] = the sum over v's neighbour
+    entries in ascending neighbour id, from 0, of weight(v, n) (x[n] - x[v]) in float64, every operation rounded on its own, column
+    by column; an entry whose weight or whose x[n] (in that column) is not finite is skipped, and where x[v] itself is not finite y
+    is NaN (the quiet NaN with no payload: the bits of an arithmetic NaN differ between machines).  -> y (V,C) float64.  (L is negative
+    semi-definite: diag is the sum of the weights, the matrix has -diag on its diagonal.)  The specification of
+    arah_mesh_laplacian_apply (csrc/meshlaplace.hpp), and what runs for meshes on the host."""
+    weight, nbr_start, nbr, V = _laplacian_weight(weight, adjacency, "laplacian_apply")
+    x = _laplacian_x(x, V, weight.device, "laplacian_apply")
+    xd = x.to(torch.float64)
+    y = torch.zeros_like(xd)
+    rows = int(nbr.shape[0])
+    if V == 0 or rows == 0:
+        return y
+    start, nb = nbr_start.long(), nbr.long()
+    first, deg = start[:-1], start[1:] - start[:-1]
+    for k in range(int(deg.max())):
+        i = (first + k).clamp(max=rows - 1)
+        n, w = nb[i], weight[i]
+        ok = ((k < deg) & torch.isfinite(w))[:, None] & torch.isfinite(xd[n])
+        y = y + torch.where(ok, w[:, None] * (xd[n] - xd), torch.zeros_like(y))
+    return torch.where(torch.isfinite(xd), y, torch.full_like(y, float("nan")))
+
+
+def mesh_curvature(verts, faces, mass="mixed", adjacency=None, laplacian=None, normal_sum=None):
+    """Mean, Gaussian and principal curvatures at the vertices of an indexed mesh (Meyer, Desbrun, Schroeder, Barr 2002): verts
+    (V,3) float32, faces (F,3) integer ids, mass as in `mesh_cotangent`, adjacency `mesh_adjacency` or None, laplacian the five
+    outputs of `mesh_cotangent` of the mesh or None, normal_sum (V,3) float64 of `vertex_normals` or None.
+
+    L = `laplacian_apply`(weight, verts); K = (-L) / area, Meyer's mean-curvature normal 2 kappa_H n.  N = normal_sum, len =
+    sqrt((N0 N0 + N1 N1) + N2 N2).
+        mean_normal = 0.5 K              mean_abs = 0.5 sqrt((K0 K0 + K1 K1) + K2 K2)
+        mean = 0.5 (((K0 N0 + K1 N1) + K2 N2) / len)
+        gaussian = (TWO_PI - angle_sum) / area, (PI - angle_sum) / area for a vertex with vert_flags bit 0 (on a boundary)
+        r = sqrt(max(mean mean - gaussian, 0)), k1 = mean + r, k2 = mean - r
+    TWO_PI and PI are the nearest doubles.  The sign of mean follows the mesh's own orientation, whatever it is: with counter-
+    clockwise faces seen from outside a convex part has mean > 0.  THE PROJECT'S OWN LEVEL SETS (marching cubes of a signed
+    distance) ARE ORIENTED CLOCKWISE SEEN FROM OUTSIDE, so a convex part of a body has mean < 0 there; mean_abs and gaussian do not
+    depend on the orientation.  A vertex is INVALID when it has vert_flags bit 1 (non-manifold) or bit 2 (isolated), a non-finite
+    coordinate, an area that is not finite and > 0, or a len that is not finite and > 0: NaN in every output, valid = 0.
+
+    -> curv (V,5) float64 with the columns CURVATURE_FIELDS, mean_normal (V,3) float64, valid (V,) uint8, counts (1,) int32 the
+    invalid vertices.  The specification of arah_mesh_curvature (csrc/meshlaplace.hpp), bit for bit given the same angle_sum."""
+    what = "mesh_curvature"
+    check_mass(mass, what)
+    verts, faces, V, _ = _mesh_verts(verts, faces, what)
+    adjacency = _adjacency_of(faces, V, adjacency, what)
+    if laplacian is None:
+        laplacian = mesh_cotangent(verts, faces, mass, adjacency)
+    weight, _, area, angle_sum = tuple(laplacian)[:4]
+    if normal_sum is None:
+        normal_sum = vertex_normals(verts, faces, adjacency)[0]
+    f64, dev = torch.float64, verts.device
+    for t, shape in ((area, (V,)), (angle_sum, (V,)), (normal_sum, (V, 3))):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != f64 or t.device != dev:
+            raise ValueError("%s: laplacian must be the outputs of mesh_cotangent, normal_sum of vertex_normals, on %s" % (what, dev))
+    flags = adjacency[6].long()
+    L = laplacian_apply(weight, adjacency, verts)
+    N = normal_sum
+    length = _sqrt64(_dot3r(N, N))
+    valid = ((flags & 6) == 0) & torch.isfinite(verts).all(1) & torch.isfinite(area) & (area > 0) & torch.isfinite(length) & (length > 0)
+    a = torch.where(valid, area, torch.ones_like(area))
+    K = (-L) / a[:, None]
+    mean = 0.5 * (_dot3r(K, N) / torch.where(valid, length, torch.ones_like(length)))
+    pi = torch.where((flags & 1) != 0, torch.full_like(a, PI), torch.full_like(a, TWO_PI))
+    gauss = (pi - angle_sum) / a
+    disc = mean * mean - gauss
+    root = _sqrt64(torch.where(disc > 0, disc, torch.zeros_like(disc)))
+    curv = torch.stack([mean, 0.5 * _sqrt64(_dot3r(K, K)), gauss, mean + root, mean - root], 1)
+    nan = torch.full_like(curv[:, :1], float("nan"))
+    curv = torch.where(valid[:, None], curv, nan)
+    mean_normal = torch.where(valid[:, None], 0.5 * K, nan)
+    return curv, mean_normal, valid.to(torch.uint8), torch.tensor([V - int(valid.sum())], dtype=torch.int32, device=dev)
+
+
+def _mesh_smooth_cotangent(verts, faces, V, iterations, factors, pin, adjacency):
+    """The steps of `mesh_smooth` with weights="cotangent"."""
+    nbr_start, nbr, flags = adjacency[2], adjacency[3], adjacency[6]
+    cur, F, dev, f64 = verts.clone(), int(faces.shape[0]), verts.device, torch.float64
+    if V == 0 or F == 0 or iterations == 0:
+        return cur
+    start, nb = nbr_start.long(), nbr.long()
+    first, deg = start[:-1], start[1:] - start[:-1]
+    width = int(deg.max())
+    free = (flags & 3) == 0 if pin else torch.ones(V, dtype=torch.bool, device=dev)
+    for step in range(iterations * len(factors)):
+        f = factors[step % len(factors)]
+        weight = mesh_cotangent(cur, faces, "mixed", adjacency)[0]
+        p, finite = cur.to(f64), torch.isfinite(cur).all(1)
+        acc = torch.zeros(V, 3, dtype=f64, device=dev)
+        s = torch.zeros(V, dtype=f64, device=dev)
+        for k in range(width):
+            i = (first + k).clamp(max=6 * F - 1)
+            n, w = nb[i], weight[i]
+            has = (k < deg) & finite[n] & torch.isfinite(w)
+            s = s + torch.where(has, w.abs(), torch.zeros_like(s))
+            acc = acc + torch.where(has[:, None], w[:, None] * (p[n] - p), torch.zeros_like(acc))
+        moves = finite & free & torch.isfinite(s) & (s > 0)
+        new = (p + f * (acc / torch.where(moves, s, torch.ones_like(s))[:, None])).float()
+        cur = torch.where(moves[:, None], new, cur)
+    return cur
 
 
 # ---- edge-collapse decimation: one round ---------------------------------------------------------------------------------------------

@@ -1027,6 +1027,10 @@ class MetaAvatarRender(nn.Module):
                            (the vertex's rotation applied to "normal", renormalised)
             "vertex_normal" (V,3) the MESH's own unit normals (geometry.vertex_normals: the incident faces' cross products
                            summed), next to the SDF's "normal": what the triangles say after simplify and smooth moved vertices
+            "mean_curvature", "gaussian_curvature"  (V,1) float64: "mean" and "gaussian" of geometry.mesh_curvature of the mesh
+                           returned (mixed cells), NaN at its invalid vertices.  The level set's faces are clockwise seen from
+                           outside, so a convex part of the body has mean_curvature < 0.  With "vertex_normal" or smooth the
+                           adjacency is built once for all of them
 
         clean (None: nothing changes): a `keep` policy of geometry.clean_mesh; the floaters are dropped BEFORE the attributes are
         evaluated, so a dropped vertex costs no network evaluation, and vert_src (the kept vertices' ids in the uncleaned mesh)
@@ -1054,7 +1058,7 @@ class MetaAvatarRender(nn.Module):
 
         Eval only, GPU only; one host synchronisation (the mesh's size), one more with clean, simplify_mesh's with simplify."""
         from . import geometry, meshing
-        names = ("weights", "verts_posed", "normal", "color", "vertex_normal")
+        names = ("weights", "verts_posed", "normal", "color", "vertex_normal") + self._CURVATURE_ATTRIBUTES
         bad = set(attributes) - set(names)
         if bad:
             raise ValueError("canonical_mesh: unknown attributes %s (known: %s)" % (sorted(bad), ", ".join(names)))
@@ -1090,9 +1094,14 @@ class MetaAvatarRender(nn.Module):
                 return res
             if V == 0:
                 res.update({k: torch.zeros(0, 24 if k == "weights" else 3, device=verts.device) for k in attributes})
+                res.update({k: torch.zeros(0, 1, dtype=torch.float64, device=verts.device) for k in attributes
+                            if k in self._CURVATURE_ATTRIBUTES})
                 return res
+            if adjacency is None and len(set(attributes) & set(("vertex_normal",) + self._CURVATURE_ATTRIBUTES)) > 1:
+                adjacency = geometry.mesh_adjacency(verts, faces)                # once for the normals and the curvatures
             if "vertex_normal" in attributes:
                 res["vertex_normal"] = geometry.vertex_normals(verts, faces, adjacency=adjacency)
+            res.update(self._curvature_attributes(verts, faces, attributes, adjacency))
             T = None
             if set(attributes) & {"weights", "verts_posed", "color"}:
                 cmin, cmax, center = inputs["coord_min"][:1], inputs["coord_max"][:1], inputs["center"][:1]
@@ -1119,6 +1128,18 @@ class MetaAvatarRender(nn.Module):
                 res["color"] = hip.shade_points(frame, ws, verts, T, dirs.contiguous(), self.idhr_network.cano_view_dirs)[0]
         return res
 
+    _CURVATURE_ATTRIBUTES = ("mean_curvature", "gaussian_curvature")
+
+    @staticmethod
+    def _curvature_attributes(verts, faces, attributes, adjacency=None):
+        """{"mean_curvature" / "gaussian_curvature": (V,1) float64} of the mesh, for the names among `attributes`."""
+        from . import geometry
+        asked = [a for a in attributes if a in MetaAvatarRender._CURVATURE_ATTRIBUTES]
+        if not asked:
+            return {}
+        curv = geometry.mesh_curvature(verts, faces, adjacency=adjacency)
+        return {a: curv["mean" if a == "mean_curvature" else "gaussian"][:, None] for a in asked}
+
     def render_mesh(self, inputs, height=512, width=512, n_side=256, space="posed", attributes=("color", "vertex_normal"), clean=None,
                     simplify=None, smooth=None, view=None, subdivide=None, isotropic=None):
         """An image of the body of frame `inputs` as an indexed mesh: `canonical_mesh(inputs, n_side, clean=, simplify=, smooth=,
@@ -1132,8 +1153,11 @@ class MetaAvatarRender(nn.Module):
         1 / depth^2, and only a camera that turns about the bulk of the body sees it equally large, mirrored, from the front and
         from the back; "at": (0, 0, 0) gives the other camera.  attributes: per-vertex names of `canonical_mesh` ("color", "normal", "weights",
         "verts_posed", "vertex_normal"), "face_normal" and "ambient_occlusion" ((H,W,1): geometry.ambient_occlusion of the mesh that is
-        drawn, 64 directions per vertex, 1 = open sky -- a shading for a mesh without colours); each becomes an (H,W,C) image, 0
-        where nothing is drawn.
+        drawn, 64 directions per vertex, 1 = open sky -- a shading for a mesh without colours), "mean_curvature" and
+        "gaussian_curvature" ((H,W,1): geometry.mesh_curvature of the mesh that is drawn -- the posed one shows the creases at bent
+        joints --, float32, 0 at an invalid vertex; a convex part has mean_curvature < 0, the level set's faces being clockwise seen
+        from outside; a second shading beside the occlusion); each becomes an (H,W,C) image, 0 where nothing is drawn.  When several
+        of "vertex_normal" and the curvatures are asked for, the adjacency of the drawn mesh is built once.
 
         The NORMALS drawn are those of the mesh that is drawn: in posed space "vertex_normal" and "face_normal" are the posed
         mesh's own (geometry.vertex_normals of the posed vertices, world axes), not the canonical mesh's rotated; in canonical
@@ -1145,7 +1169,7 @@ class MetaAvatarRender(nn.Module):
         from . import geometry
         if space not in ("posed", "canonical"):
             raise ValueError("render_mesh: space must be 'posed' or 'canonical', got %r" % (space,))
-        names = ("weights", "verts_posed", "normal", "color", "vertex_normal", "face_normal", "ambient_occlusion")
+        names = ("weights", "verts_posed", "normal", "color", "vertex_normal", "face_normal", "ambient_occlusion") + self._CURVATURE_ATTRIBUTES
         attributes = tuple(attributes)
         bad = set(attributes) - set(names)
         if bad:
@@ -1158,7 +1182,7 @@ class MetaAvatarRender(nn.Module):
             camera = {"azim": 0.0} if view is None else view
             if geometry.check_camera(camera, "render_mesh: view") != "lookat":
                 raise ValueError("render_mesh: view must be a look-at camera {'azim': degrees[, 'dist', 'fov', 'at']}")
-        own = ("vertex_normal", "face_normal", "ambient_occlusion")   # taken from the mesh that is drawn
+        own = ("vertex_normal", "face_normal", "ambient_occlusion") + self._CURVATURE_ATTRIBUTES   # taken from the mesh that is drawn
         wanted = {a for a in attributes if a not in own} | ({"verts_posed"} if space == "posed" else set())
         mesh = self.canonical_mesh(inputs, n_side=n_side, attributes=tuple(sorted(wanted)), clean=clean, simplify=simplify, smooth=smooth,
                                    subdivide=subdivide, isotropic=isotropic)
@@ -1168,22 +1192,38 @@ class MetaAvatarRender(nn.Module):
             # the level set's faces are wound with their normals INTO the body ("Normals"): the sky is on the other
             # side, so the hemispheres are taken about the normals of the reversed faces
             draw["ambient_occlusion"] = geometry.ambient_occlusion(verts, mesh["faces"].flip(1))[:, None]
+        draw.update(self._drawn_mesh_attributes(verts, mesh["faces"], attributes))
         if space == "canonical" and "at" not in camera:
             camera = dict(camera, at=geometry.surface_centroid(verts, mesh["faces"]))
         res = geometry.render_mesh(verts, mesh["faces"], height, width, camera=camera, attributes=draw)
         res["mesh"] = mesh
         return res
 
+    def _drawn_mesh_attributes(self, verts, faces, attributes):
+        """The curvature attributes of the mesh that is drawn or hit as (V,1) float32 (0 at an invalid vertex), and with them
+        "vertex_normal" over the same adjacency, built once."""
+        from . import geometry
+        if not set(attributes) & set(self._CURVATURE_ATTRIBUTES) or int(faces.shape[0]) == 0:
+            return {a: torch.zeros(int(verts.shape[0]), 1, device=verts.device) for a in attributes if a in self._CURVATURE_ATTRIBUTES}
+        with torch.no_grad():
+            adjacency = geometry.mesh_adjacency(verts, faces)
+            out = {a: torch.nan_to_num(x, nan=0.0, posinf=0.0, neginf=0.0).float()
+                   for a, x in self._curvature_attributes(verts, faces, attributes, adjacency).items()}
+            if "vertex_normal" in attributes:
+                out["vertex_normal"] = geometry.vertex_normals(verts, faces, adjacency=adjacency)
+        return out
+
     def cast_rays(self, inputs, rays=None, n_side=256, clean=None, simplify=None, smooth=None, attributes=()):
         """What rays see of the posed body of frame `inputs` as an indexed mesh -- the mesh `render_mesh(space="posed")` draws:
         `canonical_mesh(inputs, n_side, clean=, simplify=, smooth=)` skinned forward ("verts_posed").  rays: (origins, dirs), (R,3)
         each in world metres, or None for the frame's own rays of batch element 0 (cam_loc and ray_dirs, the masked pixels in eval).
-        attributes: per-vertex names of `canonical_mesh` and "vertex_normal" (the posed mesh's own), interpolated at the hits.
+        attributes: per-vertex names of `canonical_mesh` and "vertex_normal", "mean_curvature", "gaussian_curvature" (the posed
+        mesh's own, as `render_mesh` takes them), interpolated at the hits.
         -> the dict of geometry.cast_rays (hit, t, face, bary, points, normal and one (R,C) tensor per attribute) plus "mesh",
         the dict of canonical_mesh.  t is in units of |dirs|: metres along the frame's unit ray_dirs.  Eval only, GPU only; the host
         synchronisations are canonical_mesh's."""
         from . import geometry
-        names = ("weights", "verts_posed", "normal", "color", "vertex_normal")
+        names = ("weights", "verts_posed", "normal", "color", "vertex_normal") + self._CURVATURE_ATTRIBUTES
         attributes = tuple(attributes)
         bad = set(attributes) - set(names)
         if bad:
@@ -1195,7 +1235,7 @@ class MetaAvatarRender(nn.Module):
             if not isinstance(rays, (tuple, list)) or len(rays) != 2:
                 raise ValueError("cast_rays: rays must be (origins, dirs) or None")
             origins, dirs = rays
-        wanted = {a for a in attributes if a != "vertex_normal"} | {"verts_posed"}
+        wanted = {a for a in attributes if a != "vertex_normal" and a not in self._CURVATURE_ATTRIBUTES} | {"verts_posed"}
         mesh = self.canonical_mesh(inputs, n_side=n_side, attributes=tuple(sorted(wanted)), clean=clean, simplify=simplify, smooth=smooth)
         verts = mesh["verts_posed"]
         if mesh["faces"].shape[0] < 1:
@@ -1203,7 +1243,8 @@ class MetaAvatarRender(nn.Module):
         for name, x in (("origins", origins), ("dirs", dirs)):
             if not isinstance(x, torch.Tensor):
                 raise ValueError("cast_rays: %s must be a tensor" % name)
-        take = {a: (True if a == "vertex_normal" else mesh[a]) for a in attributes}
+        take = {a: (True if a == "vertex_normal" else mesh.get(a)) for a in attributes}
+        take.update(self._drawn_mesh_attributes(verts, mesh["faces"], attributes))
         res = geometry.cast_rays((verts, mesh["faces"]), origins.to(verts.device), dirs.to(verts.device), attributes=take)
         res["mesh"] = mesh
         return res

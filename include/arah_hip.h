@@ -41,6 +41,10 @@
  *   arah_mesh_adjacency /   (none: the reference's users smooth and re-normal with trimesh / open3d / pytorch3d; the incident faces
  *   arah_mesh_vertex_normals /  and unique neighbours of every vertex with edge statistics, pytorch3d's verts_normals_packed over
  *   arah_mesh_smooth        them, and Laplacian / Taubin umbrella smoothing)
+ *   arah_mesh_cotangent /   (none: the cotangent Laplacian of an indexed mesh with its lumped mass and angle sums, the operator applied
+ *   arah_mesh_laplacian_apply /  to per-vertex values, mean / Gaussian / principal curvatures after Meyer, Desbrun, Schroeder and Barr
+ *   arah_mesh_curvature /   2002, and umbrella smoothing with cotangent weights: what the reference's users take from trimesh, libigl
+ *   arah_mesh_smooth_cotangent   or pytorch3d)
  *   arah_mesh_orient /      (none: the reference's users repair scans with trimesh's fix_normals / fill_holes; consistent orientation
  *   arah_mesh_boundary_loops /  by the double cover of the face graph, the boundary loops, and small holes closed by a fan around
  *   arah_mesh_fill_holes    the loop's exact mean)
@@ -540,6 +544,45 @@ int arah_mesh_smooth(const float* verts, int64_t n_verts, const int32_t* nbr_sta
  * 2^31, otherwise ARAH_E_BADARG without a launch.  No host synchronisation, no allocation. */
 int arah_mesh_tangential(const float* verts, int64_t n_verts, const int32_t* nbr_start, const int32_t* nbr, const uint8_t* vert_flags,
                          const double* normal_sum, float factor, float* verts_out, void* stream);
+/* The cotangent Laplacian of an indexed mesh (csrc/meshlaplace.hpp; meshing.mesh_cotangent is the rule, bit for bit except
+ * angle_sum, whose atan2 is the only function that is not correctly rounded).  verts [n_verts][3], faces [n_faces][3], vf_start /
+ * vf / nbr_start / nbr of arah_mesh_adjacency on the same mesh, mass 0 (barycentric) or 1 (mixed Voronoi).  -> weight [6 n_faces]
+ * double, aligned with nbr: half the sum of the cotangents opposite to the edge over its faces in ascending face id, rows from
+ * nbr_start[n_verts] on +0; diag, area, angle_sum [n_verts] double: the row sums in ascending neighbour id, the lumped mass, the sum
+ * of the angles at the vertex in ascending face id; counts [8]: contributing, degenerate and nonfinite faces, contributing faces
+ * with an obtuse corner, entries n > v with weight < 0, vertices whose area is not > 0, 0, 0.  A gather: a vertex's own lane or
+ * workgroup writes its rows, integer atomics for the counts only, no scratch.  Rows of the caller's CSRs are clamped to the
+ * arrays and ids tested before they are followed.  Sizes as for arah_mesh_adjacency; a mass other than 0 or 1 or a missing
+ * pointer: ARAH_E_BADARG without a launch.  n_verts = 0 or n_faces = 0 still write counts (and zero rows). */
+int arah_mesh_cotangent(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int32_t* vf_start,
+                        const int32_t* vf, const int32_t* nbr_start, const int32_t* nbr, int32_t mass, double* weight, double* diag,
+                        double* area, double* angle_sum, int32_t* counts, void* stream);
+/* y = L x over the weights of arah_mesh_cotangent: x [n_verts][n_channels] float (x_is_f64 = 0) or double (1), 1 <= n_channels <=
+ * 32; y [n_verts][n_channels] double, y[v][c] = the sum over v's entries in ascending neighbour id, from 0, of weight (x[n][c] -
+ * x[v][c]), every operation rounded on its own; an entry whose weight or x[n][c] is not finite is skipped; the quiet NaN
+ * 0x7ff8000000000000 where x[v][c] is not finite.  n_faces gives the rows
+ * of nbr and weight (6 n_faces).  A gather, one thread per element of y.  ARAH_E_BADARG without a launch otherwise. */
+int arah_mesh_laplacian_apply(const double* weight, const int32_t* nbr_start, const int32_t* nbr, int64_t n_verts, int64_t n_faces,
+                              const void* x, int32_t x_is_f64, int32_t n_channels, double* y, void* stream);
+/* Curvatures from weight / area / angle_sum of arah_mesh_cotangent, normal_sum of arah_mesh_vertex_normals and vert_flags of
+ * arah_mesh_adjacency (meshing.mesh_curvature is the rule, bit for bit given the same angle_sum).  L = arah_mesh_laplacian_apply of
+ * the positions, K = (-L) / area; -> curv [n_verts][5] double: mean = 0.5 ((K.N) / |N|), mean_abs = 0.5 |K|, gaussian = ((2 pi, or
+ * pi with vert_flags bit 0) - angle_sum) / area, k1, k2 = mean +- sqrt(max(mean mean - gaussian, 0)); mean_normal [n_verts][3]
+ * double = 0.5 K; valid [n_verts]; counts [1]: the invalid vertices.  A vertex with vert_flags bit 1 or 2, a non-finite
+ * coordinate, an area or |N| that is not finite and > 0 is invalid: NaN everywhere, valid = 0.  One thread per vertex. */
+int arah_mesh_curvature(const float* verts, int64_t n_verts, int64_t n_faces, const int32_t* nbr_start, const int32_t* nbr,
+                        const uint8_t* vert_flags, const double* weight, const double* area, const double* angle_sum,
+                        const double* normal_sum, double* curv, double* mean_normal, uint8_t* valid, int32_t* counts, void* stream);
+/* arah_mesh_smooth with cotangent weights: every step recomputes the weights from the positions it reads (into the scratch) and
+ * uses the entries with a finite neighbour and a finite weight.  A vertex moves when it is finite, is not pinned and s = the sum
+ * of |w| over those entries in ascending neighbour id is finite and > 0: new = float(p + f ((sum of w (q - p)) / s)) in double.
+ * Factors, pin, tmp and verts_out as for arah_mesh_smooth.  scratch: arah_mesh_smooth_cotangent_scratch_bytes(n_verts, n_faces)
+ * device bytes, ARAH_E_WORKSPACE when short; ARAH_E_BADARG as for arah_mesh_smooth, both without a launch. */
+size_t arah_mesh_smooth_cotangent_scratch_bytes(int64_t n_verts, int64_t n_faces);
+int arah_mesh_smooth_cotangent(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int32_t* vf_start,
+                               const int32_t* vf, const int32_t* nbr_start, const int32_t* nbr, const uint8_t* vert_flags, int32_t n_steps,
+                               const float h_factors[2], int32_t pin, float* tmp, float* verts_out, void* scratch, size_t scratch_bytes,
+                               void* stream);
 /* Consistent orientation of an indexed mesh (csrc/meshorient.hpp; meshing.mesh_orient is the rule, bit for bit).  faces
  * [n_faces][3], and vf_start / vf / nbr_start / nbr / nbr_out / nbr_in of arah_mesh_adjacency on the same mesh.  Two valid faces are
  * neighbours across an edge that carries exactly two valid faces, consistent when they traverse it in opposite directions; the
