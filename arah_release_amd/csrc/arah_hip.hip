@@ -1957,6 +1957,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_canon_solve(FrameDev fr, const 
 #include "meshadj.hpp"
 #include "meshlaplace.hpp"
 #include "meshquadric.hpp"
+#include "meshsolve.hpp"
 #include "meshcollapse.hpp"
 #include "meshsubdiv.hpp"
 #include "meshflip.hpp"
@@ -5050,6 +5051,108 @@ int arah_mesh_smooth_cotangent(const float* verts, int64_t n_verts, const int32_
                            (int)(pin != 0), dst);
         src = dst;
     }
+    return check_launch();
+}
+
+// ---- systems with the cotangent operator: preconditioned conjugate gradients (csrc/meshsolve.hpp) -----------------------------------
+static bool mz_sizes_ok(int64_t n_verts, int64_t n_faces, int64_t n_channels) {
+    return ma_sizes_ok(n_verts, n_faces) && n_verts <= (int64_t)kMzMaxVerts && n_channels >= 1 && n_channels <= kMzMaxChannels;
+}
+
+static int mz_blocks(int64_t n_verts) { return (int)((n_verts + kImeshThreads - 1) / kImeshThreads); }
+
+static size_t carve_solve(void* scratch, int64_t n_verts, int64_t n_channels, MzState& st) {
+    MeshCarver c(scratch);
+    const size_t V = (size_t)n_verts, C = (size_t)n_channels;
+    st.d = c.take<double>(V);
+    st.r = c.take<double>(C * V);
+    st.z = c.take<double>(C * V);
+    st.p = c.take<double>(C * V);
+    st.q = c.take<double>(C * V);
+    st.part = c.take<double>(2 * C * (size_t)mz_blocks(n_verts));
+    st.col = c.take<double>((size_t)kMzColDoubles * kMzMaxChannels);
+    st.icol = c.take<int>((size_t)kMzColInts * kMzMaxChannels);
+    st.counts = c.take<int>((size_t)kMzCounts);
+    st.cls = c.take<unsigned char>(V);
+    st.live = c.take<unsigned char>(V);
+    return c.bytes();
+}
+
+size_t arah_mesh_solve_scratch_bytes(int64_t n_verts, int64_t n_channels) {
+    if (!mz_sizes_ok(n_verts, 0, n_channels)) return 0;
+    MzState st{};
+    return carve_solve(nullptr, n_verts, n_channels, st);
+}
+
+static MzMesh mz_mesh(const double* weight, const double* area, const int32_t* nbr_start, const int32_t* nbr, int64_t n_verts,
+                      int64_t n_faces, int32_t n_channels, double mass_coef, double stiff_coef) {
+    MzMesh m{};
+    m.weight = weight;
+    m.area = area;
+    m.nbr_start = (const int*)nbr_start;
+    m.nbr = (const int*)nbr;
+    m.n_verts = (int)n_verts;
+    m.n_ch = (int)n_channels;
+    m.n_blocks = mz_blocks(n_verts);
+    m.n_rows = 6 * (long long)n_faces;
+    m.mass_coef = mass_coef;
+    m.stiff_coef = stiff_coef;
+    return m;
+}
+
+static bool mz_args_ok(const double* weight, const double* area, const int32_t* nbr_start, const int32_t* nbr, int64_t n_verts,
+                       int64_t n_faces, int32_t n_channels, double mass_coef, double stiff_coef, const double* x, const void* scratch) {
+    if (!mz_sizes_ok(n_verts, n_faces, n_channels) || !nbr_start || !scratch) return false;
+    if (!std::isfinite(mass_coef) || mass_coef < 0.0 || !std::isfinite(stiff_coef) || !(stiff_coef > 0.0)) return false;
+    if ((n_verts > 0 && (!area || !x)) || (n_faces > 0 && (!weight || !nbr))) return false;
+    return true;
+}
+
+static void mz_report(hipStream_t s, int64_t n_verts, int32_t n_channels, const MzState& st, int32_t* iters, int32_t* status, double* rr,
+                      double* r0, int32_t* counts, uint8_t* classes) {
+    hipLaunchKernelGGL(k_mz_report, dim3(mesh_grid(max(n_verts, (int64_t)kMzMaxChannels))), dim3(kImeshThreads), 0, s, (int)n_verts,
+                       (int)n_channels, st, (int*)iters, (int*)status, rr, r0, (int*)counts, (unsigned char*)classes);
+}
+
+int arah_mesh_solve_begin(const double* weight, const double* area, const int32_t* nbr_start, const int32_t* nbr, int64_t n_verts,
+                          int64_t n_faces, const double* rhs, const double* x0, const uint8_t* pinned, int32_t n_channels, double mass_coef,
+                          double stiff_coef, double tol, double* x, int32_t* iters, int32_t* status, double* rr, double* r0,
+                          int32_t* counts, uint8_t* classes, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!mz_args_ok(weight, area, nbr_start, nbr, n_verts, n_faces, n_channels, mass_coef, stiff_coef, x, scratch)) return ARAH_E_BADARG;
+    if (!std::isfinite(tol) || tol < 0.0 || (n_verts > 0 && (!rhs || !x0))) return ARAH_E_BADARG;
+    MzState st{};
+    if (scratch_bytes < carve_solve(scratch, n_verts, n_channels, st)) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const MzMesh m = mz_mesh(weight, area, nbr_start, nbr, n_verts, n_faces, n_channels, mass_coef, stiff_coef);
+    if (hipMemsetAsync(st.counts, 0, sizeof(int) * kMzCounts, s) != hipSuccess) return ARAH_E_LAUNCH;
+    if (n_verts > 0) {
+        hipLaunchKernelGGL(k_mz_live, dim3(mesh_grid(n_verts)), dim3(kImeshThreads), 0, s, x0, m.n_verts, m.n_ch, st.live);
+        hipLaunchKernelGGL(k_mz_class, dim3(mesh_grid(n_verts)), dim3(kImeshThreads), 0, s, m, rhs, (const unsigned char*)pinned, st);
+        hipLaunchKernelGGL(k_mz_start, dim3(m.n_blocks, m.n_ch), dim3(kImeshThreads), 0, s, m, rhs, x0, x, st);
+    }
+    hipLaunchKernelGGL(k_mz_fin_start, dim3(m.n_ch), dim3(kImeshThreads), 0, s, m.n_ch, m.n_blocks, tol, st);
+    mz_report(s, n_verts, n_channels, st, iters, status, rr, r0, counts, classes);
+    return check_launch();
+}
+
+int arah_mesh_solve_steps(const double* weight, const double* area, const int32_t* nbr_start, const int32_t* nbr, int64_t n_verts,
+                          int64_t n_faces, int32_t n_channels, double mass_coef, double stiff_coef, int32_t n_steps, double* x,
+                          int32_t* iters, int32_t* status, double* rr, double* r0, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!mz_args_ok(weight, area, nbr_start, nbr, n_verts, n_faces, n_channels, mass_coef, stiff_coef, x, scratch) || n_steps < 0)
+        return ARAH_E_BADARG;
+    MzState st{};
+    if (scratch_bytes < carve_solve(scratch, n_verts, n_channels, st)) return ARAH_E_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const MzMesh m = mz_mesh(weight, area, nbr_start, nbr, n_verts, n_faces, n_channels, mass_coef, stiff_coef);
+    if (n_verts > 0) {
+        for (int32_t i = 0; i < n_steps; ++i) {   // four launches a step (csrc/meshsolve.hpp)
+            hipLaunchKernelGGL(k_mz_op, dim3(m.n_blocks, m.n_ch), dim3(kImeshThreads), 0, s, m, st);
+            hipLaunchKernelGGL(k_mz_fin_pq, dim3(m.n_ch), dim3(kImeshThreads), 0, s, m.n_ch, m.n_blocks, st);
+            hipLaunchKernelGGL(k_mz_update, dim3(m.n_blocks, m.n_ch), dim3(kImeshThreads), 0, s, m, x, st);
+            hipLaunchKernelGGL(k_mz_fin_rr, dim3(m.n_ch), dim3(kImeshThreads), 0, s, m.n_ch, m.n_blocks, st);
+        }
+    }
+    mz_report(s, n_verts, n_channels, st, iters, status, rr, r0, nullptr, nullptr);
     return check_launch();
 }
 

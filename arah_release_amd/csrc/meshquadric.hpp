@@ -147,6 +147,8 @@ __device__ __forceinline__ void mq_lane_sum(const float* __restrict__ verts, con
 
 // the tree over x[.][0 .. m) in LDS, m <= kImeshThreads, by the whole workgroup (from uniform control flow); the sum lands in
 // x[.][0].  A step's targets are multiples of 2 stride and its sources are not, so no row is read and written in one step.
+// NC: the rows of x that are summed (meshsolve.hpp sums one or two).
+template <int NC = 9>
 __device__ __forceinline__ void mq_group_tree(double (*x)[kImeshThreads], int m) {
 #pragma clang fp contract(off)
     const int tid = (int)threadIdx.x;
@@ -155,7 +157,7 @@ __device__ __forceinline__ void mq_group_tree(double (*x)[kImeshThreads], int m)
         __syncthreads();
         if ((tid & (2 * stride - 1)) == 0 && tid + stride < m) {
 #pragma unroll
-            for (int c = 0; c < 9; ++c) x[c][tid] = x[c][tid] + x[c][tid + stride];
+            for (int c = 0; c < NC; ++c) x[c][tid] = x[c][tid] + x[c][tid + stride];
         }
     }
     __syncthreads();

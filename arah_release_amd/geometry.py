@@ -11,7 +11,9 @@ on the device") and `decimate_mesh`: fewer by edge collapse, which keeps a close
 decimation on the device"); `mesh_adjacency` / `mesh_topology` / `vertex_normals` / `smooth_mesh`: who is adjacent to whom, whether a mesh is
 watertight, the mesh's own normals, and Laplacian / Taubin smoothing (DESIGN.md "Adjacency, normals and smoothing on the device");
 `mesh_laplacian` / `laplacian_matrix` / `apply_laplacian` / `mesh_curvature`: the cotangent Laplacian with its lumped mass, and mean,
-Gaussian and principal curvatures (DESIGN.md "Cotangent operator and curvature on the device").
+Gaussian and principal curvatures (DESIGN.md "Cotangent operator and curvature on the device"); `solve_laplacian` /
+`harmonic_extend` / `smooth_mesh(method="implicit")`: systems solved with that operator (DESIGN.md "Solving with the cotangent
+operator on the device").
 Ground truth that is a SCAN -- a point cloud, with or without normals -- is scored through the exact
 nearest-point query hip.point_index / hip.point_nearest (DESIGN.md "Scoring against point clouds"): `PointCloud`, `nearest_points`,
 `load_points` / `save_points` / `load_geometry`, and F-scores at distance thresholds (`thresholds=` of `mesh_metrics`).
@@ -1253,7 +1255,7 @@ faces incident to every vertex (ids ascending); nbr_start (V+1,) / nbr (6F,) the
 nbr_out / nbr_in (6F,) the faces traversing v->n / n->v; vert_flags (V,) uint8 (1 boundary, 2 non-manifold, 4 no neighbour); counts
 (8,) int32 (valid faces, edges, boundary, non-manifold and misoriented edges, the largest valence, isolated vertices, Euler)."""
 
-_SMOOTH_KEYS = ("iterations", "lamb", "mu", "method", "boundary", "weights")
+_SMOOTH_KEYS = ("iterations", "lamb", "mu", "method", "boundary", "weights", "time")
 
 
 def mesh_adjacency(verts_or_n_verts, faces):
@@ -1299,10 +1301,16 @@ def vertex_normals(verts, faces, adjacency=None):
         return _cc_backend(faces).vertex_normals(v32, faces, adjacency=adjacency)[1]
 
 
-def _check_smooth_call(iterations, lamb, mu, method, boundary, what, weights="uniform"):
+def _check_smooth_call(iterations, lamb, mu, method, boundary, what, weights="uniform", time=None):
     """meshing.check_smooth_args, and method="tangential": iterations and lamb as for "laplacian"; mu is not used, and boundary
-    must be "pin" (a tangential step never moves a vertex of a boundary or non-manifold edge).  -> True for "tangential"."""
+    must be "pin" (a tangential step never moves a vertex of a boundary or non-manifold edge).  -> True for "tangential".
+    method="implicit": iterations, time and boundary (meshing.check_implicit_args); lamb, mu and weights are not used.  -> False."""
     from . import meshing
+    if method == "implicit":
+        meshing.check_implicit_args(iterations, time, boundary, what)
+        return False
+    if time is not None:
+        raise ValueError("%s: time belongs to method='implicit', got it with method=%r" % (what, method))
     meshing.check_smooth_weights(weights, what)
     if method == "tangential" and weights != "uniform":
         raise ValueError("%s: method='tangential' has uniform weights only, got weights=%r" % (what, weights))
@@ -1315,7 +1323,8 @@ def _check_smooth_call(iterations, lamb, mu, method, boundary, what, weights="un
     return True
 
 
-def smooth_mesh(verts, faces, iterations=10, lamb=0.5, mu=-0.53, method="taubin", boundary="pin", adjacency=None, weights="uniform"):
+def smooth_mesh(verts, faces, iterations=10, lamb=0.5, mu=-0.53, method="taubin", boundary="pin", adjacency=None, weights="uniform",
+                time=None):
     """Smooth an indexed mesh with the umbrella operator: every step moves a vertex towards (lamb > 0) or away from (mu < 0) the
     mean of its neighbours, p + f (mean - p), uniform weights.  method="taubin" (Taubin 1995, "A signal processing approach to
     fair surface design"): an iteration is a lamb step and a mu step, a low-pass filter that does not shrink the mesh the way
@@ -1335,9 +1344,26 @@ def smooth_mesh(verts, faces, iterations=10, lamb=0.5, mu=-0.53, method="taubin"
     (`mesh_laplacian`) instead of uniform ones: p + f (sum w (q - p)) / (sum |w|), the explicit mean-curvature flow.  On a flat
     patch it does not move a vertex at all, whatever the sampling, where the uniform mean drags vertices along
     the surface towards their denser side: the choice for decimated, adaptively subdivided and marching-cubes meshes.  It costs
-    the operator once per step.  hip.mesh_smooth on the GPU, meshing.mesh_smooth on the host, equal bit for bit."""
-    tangential = _check_smooth_call(iterations, lamb, mu, method, boundary, "smooth_mesh", weights)
+    the operator once per step.  hip.mesh_smooth on the GPU, meshing.mesh_smooth on the host, equal bit for bit.
+
+    method="implicit", time=t: implicit fairing (Desbrun, Meyer, Schroeder, Barr 1999): every iteration solves (M + t S) p' = M p
+    with the cotangent operator S and the mixed-cell mass M of the positions it reads (`solve_laplacian`, tol 1e-10), and rounds
+    the result once to float32.  time is a length squared, required and > 0: one iteration removes detail below about sqrt(t) for
+    ANY t, where the explicit steps above are stable only for small ones -- a bump ten edges wide goes in one solve instead of
+    hundreds of steps.  boundary="pin" holds the vertices of boundary and non-manifold edges, "free" none; held vertices (and
+    those with a non-finite coordinate or without area) stay bit for bit.  lamb, mu and weights are not used.  A solve that does
+    not converge raises RuntimeError with its status and residual.  meshing.mesh_smooth_implicit is the rule, over
+    hip.laplacian_solve on the GPU and meshing.laplacian_solve on the host, equal bit for bit."""
+    tangential = _check_smooth_call(iterations, lamb, mu, method, boundary, "smooth_mesh", weights, time)
     v32, faces, adjacency = _smooth_args(verts, faces, adjacency, "smooth_mesh")
+    if method == "implicit":
+        from . import meshing
+        backend = _cc_backend(faces)
+        with torch.no_grad():
+            if adjacency is None:
+                adjacency = backend.mesh_adjacency(faces, int(v32.shape[0]))
+            return meshing.mesh_smooth_implicit(v32, faces, iterations, time, boundary, adjacency,
+                                                backend=None if backend is meshing else backend)
     if tangential:
         backend = _cc_backend(faces)
         with torch.no_grad():
@@ -1456,6 +1482,85 @@ def mesh_curvature(verts, faces, mass="mixed", adjacency=None, laplacian=None):
     out = {name: curv[:, i].contiguous() for i, name in enumerate(("mean", "mean_abs", "gaussian", "k1", "k2"))}
     out.update(mean_normal=mean_normal, area=lap["area"], valid=valid.bool(),
                report=dict(lap["report"], invalid_vertices=int(counts[0])))
+    return out
+
+
+# ---- solving with the cotangent operator ------------------------------------------------------------------------------------------
+def solve_laplacian(lap, rhs, mass_coef=0.0, stiff_coef=1.0, pinned=None, x0=None, tol=1e-10, max_iter=10000, check_every=32):
+    """Solve (mass_coef M + stiff_coef S) x = rhs with the dict of `mesh_laplacian` -- M its lumped mass (area), S = -L its
+    stiffness, positive semi-definite -- by Jacobi-preconditioned conjugate gradients in float64 (hip.laplacian_solve on the GPU,
+    meshing.laplacian_solve -- which states the rule -- on the host, equal bit for bit).  rhs (V,) or (V,C) float32 or float64, C <=
+    32 independent columns; mass_coef >= 0, stiff_coef > 0; pinned (V,) bool or None: vertices held at x0; x0 like rhs, zeros when
+    None: the start, and the value of every held vertex.  Besides the pinned, vertices with a non-finite x0 or rhs row, without
+    area (when mass_coef > 0) or without a positive diagonal are held; a held vertex is a Dirichlet value for its neighbours where
+    its x0 is finite and is left out of their sums where it is not.  With mass_coef = 0 every connected component needs a held
+    vertex, or its column of rhs must sum to 0.  tol: the relative residual |r| / |r0| at which a column stops; check_every: steps
+    per batch on the GPU, between two looks at the statuses (the result does not depend on it).
+
+    -> dict of x (float64, of rhs's shape), iterations and status ("converged" | "max_iter" | "breakdown") per column -- numbers
+    and strings for a (V,C) rhs, one of each for a (V,) one --, converged (all of them), residual = sqrt(rr / r0) of the
+    recurrence, true_residual = |rhs - A x| over the solved rows / sqrt(r0) from one more application of the operator (0 where r0
+    is 0), and report: the vertices by class (meshing.SOLVE_COUNTS).  "breakdown": p.Ap was not positive or not finite -- the
+    operator is indefinite (weights spoiled from outside) or the numbers overflowed; x is the last iterate.  Both residuals are
+    relative to the start's: where x0 already solves the system to rounding, r0 is rounding noise and true_residual stays near 1."""
+    from . import meshing
+    what = "solve_laplacian"
+    lap = _check_laplacian(lap, what)
+    if not isinstance(rhs, torch.Tensor) or rhs.dim() not in (1, 2) or rhs.dtype not in (torch.float32, torch.float64):
+        raise ValueError("%s: rhs must be a (V,) or (V, C) float32 or float64 tensor" % what)
+    if x0 is not None and (not isinstance(x0, torch.Tensor) or x0.shape != rhs.shape or x0.dtype not in (torch.float32, torch.float64)):
+        raise ValueError("%s: x0 must be a float32 or float64 tensor of rhs's shape %s, or None" % (what, tuple(rhs.shape)))
+    weight, area, adj = lap["weight"], lap["area"], tuple(lap["adjacency"])
+    one = rhs.dim() == 1
+    b = (rhs.detach()[:, None] if one else rhs.detach()).to(torch.float64).contiguous()
+    start = torch.zeros_like(b) if x0 is None else (x0.detach()[:, None] if one else x0.detach()).to(torch.float64).contiguous()
+    backend = _cc_backend(weight)
+    extra = {"check_every": check_every} if backend is not meshing else {}
+    with torch.no_grad():
+        x, iters, status, rr, r0, counts, classes = backend.laplacian_solve(weight, area, adj, b, start, pinned=pinned, mass_coef=mass_coef,
+                                                                            stiff_coef=stiff_coef, tol=tol, max_iter=max_iter, **extra)
+        # one more application of the operator: rows that are not live are hidden from their neighbours as the solver hides them
+        solved = (classes == 0)[:, None]
+        live = torch.isfinite(start).all(1, keepdim=True)
+        y = backend.laplacian_apply(weight, adj, torch.where(live, x, torch.full_like(x, float("nan"))))
+        ax = -float(stiff_coef) * y if float(mass_coef) == 0.0 else float(mass_coef) * (area[:, None] * x) - float(stiff_coef) * y
+        res = torch.where(solved, b - ax, torch.zeros_like(b))
+        scale = torch.where(r0 > 0, r0, torch.ones_like(r0))
+        true = torch.where(r0 > 0, torch.sqrt((res * res).sum(0) / scale), torch.zeros_like(r0))
+        rel = torch.where(r0 > 0, torch.sqrt(rr / scale), torch.zeros_like(r0))
+        host = torch.stack([rel, true]).cpu()                                      # with the next three: the call's last synchronisations
+    names = [meshing.SOLVE_STATUS[s] for s in status.tolist()]
+    out = {"x": x[:, 0] if one else x, "iterations": iters.tolist(), "status": names, "converged": all(s == "converged" for s in names),
+           "residual": host[0].tolist(), "true_residual": host[1].tolist(), "report": dict(zip(meshing.SOLVE_COUNTS, counts.tolist()))}
+    if one:
+        out.update({k: out[k][0] for k in ("iterations", "status", "residual", "true_residual")})
+    return out
+
+
+def harmonic_extend(verts, faces, known, values, laplacian=None, adjacency=None, tol=1e-10, max_iter=10000):
+    """The harmonic extension of per-vertex values from the vertices where they are known to all others: S x = 0 with x = values at
+    `known` -- the smoothest fill-in (it minimises the Dirichlet energy), for the attributes (skinning weights, colours) of
+    vertices that `fill_holes`, `subdivide_mesh` or a remesh created.  verts (V,3), faces (F,3); known (V,) bool; values (V,) or
+    (V,C) float32 or float64, C <= 32, read at the known vertices only; laplacian: the dict of `mesh_laplacian` of this mesh or
+    None; adjacency as there.  It is `solve_laplacian` with mass_coef 0, rhs 0, pinned = known and x0 = values where known, 0
+    elsewhere.  -> dict of values (float64, of values' shape: the input at the known vertices, the extension elsewhere) and the
+    solver's iterations, status, converged, residual, true_residual and report.  A connected component without a known vertex
+    keeps 0 and converges at once (its right-hand side is 0).  With cotangent weights the extension of a linear function over a
+    planar mesh is that function; negative weights (edges that are not Delaunay) can take it outside the known values' range."""
+    what = "harmonic_extend"
+    if laplacian is None:
+        laplacian = mesh_laplacian(verts, faces, adjacency=adjacency)
+    lap = _check_laplacian(laplacian, what)
+    V, dev = int(lap["area"].shape[0]), lap["area"].device
+    if not isinstance(known, torch.Tensor) or tuple(known.shape) != (V,) or known.dtype != torch.bool or known.device != dev:
+        raise ValueError("%s: known must be a (V,) bool tensor on %s" % (what, dev))
+    if not isinstance(values, torch.Tensor) or values.dim() not in (1, 2) or int(values.shape[0]) != V \
+            or values.dtype not in (torch.float32, torch.float64) or values.device != dev:
+        raise ValueError("%s: values must be a (V,) or (V, C) float32 or float64 tensor on %s" % (what, dev))
+    vals = values.detach().to(torch.float64)
+    x0 = torch.where(known if vals.dim() == 1 else known[:, None], vals, torch.zeros_like(vals))
+    out = solve_laplacian(lap, torch.zeros_like(vals), 0.0, 1.0, pinned=known, x0=x0, tol=tol, max_iter=max_iter)
+    out["values"] = out.pop("x")
     return out
 
 
@@ -1651,8 +1756,8 @@ def mesh_intersections(mesh_a, mesh_b, max_pairs=1 << 20, return_pairs=True):
 
 def check_smooth(smooth):
     """Validate a `smooth` option of the model's mesh entries and return the keywords of `smooth_mesh` it stands for: None
-    (nothing), a number of iterations (an integer >= 0), or a dict of iterations / lamb / mu / method / boundary / weights.  ValueError for
-    anything else."""
+    (nothing), a number of iterations (an integer >= 0), or a dict of iterations / lamb / mu / method / boundary / weights / time
+    ({"method": "implicit", "time": t} is implicit fairing).  ValueError for anything else."""
     from . import meshing
     if smooth is None:
         return None
@@ -1666,7 +1771,7 @@ def check_smooth(smooth):
     else:
         raise ValueError("smooth must be None, a number of iterations or a dict of smooth_mesh keywords, got %r" % (smooth,))
     _check_smooth_call(kw.get("iterations", 10), kw.get("lamb", 0.5), kw.get("mu", -0.53), kw.get("method", "taubin"),
-                       kw.get("boundary", "pin"), "smooth", kw.get("weights", "uniform"))
+                       kw.get("boundary", "pin"), "smooth", kw.get("weights", "uniform"), kw.get("time"))
     return kw
 
 

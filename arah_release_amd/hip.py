@@ -148,7 +148,7 @@ EXPORTS = ["arah_frame_bytes", "arah_prepare_frame", "arah_body_bytes", "arah_pr
            "arah_mesh_flip_round_scratch_bytes", "arah_mesh_flip_round",
            "arah_mesh_adjacency_scratch_bytes", "arah_mesh_adjacency", "arah_mesh_vertex_normals", "arah_mesh_smooth", "arah_mesh_tangential",
            "arah_mesh_cotangent", "arah_mesh_laplacian_apply", "arah_mesh_curvature", "arah_mesh_smooth_cotangent_scratch_bytes",
-           "arah_mesh_smooth_cotangent",
+           "arah_mesh_smooth_cotangent", "arah_mesh_solve_scratch_bytes", "arah_mesh_solve_begin", "arah_mesh_solve_steps",
            "arah_mesh_orient_scratch_bytes", "arah_mesh_orient", "arah_mesh_boundary_loops_scratch_bytes",
            "arah_mesh_boundary_loops", "arah_mesh_fill_holes_scratch_bytes", "arah_mesh_fill_holes",
            "arah_mesh_rasterize", "arah_mesh_rasterize_debug", "arah_mesh_interpolate", "arah_mesh_raycast", "arah_mesh_raycast_debug",
@@ -204,7 +204,7 @@ def load_library():
     for name in ("arah_mesh_components_scratch_bytes", "arah_mesh_select_scratch_bytes", "arah_mesh_adjacency_scratch_bytes",
                  "arah_mesh_quadric_place_scratch_bytes", "arah_mesh_collapse_round_scratch_bytes",
                  "arah_mesh_subdivide_round_scratch_bytes", "arah_mesh_flip_round_scratch_bytes",
-                 "arah_mesh_smooth_cotangent_scratch_bytes",
+                 "arah_mesh_smooth_cotangent_scratch_bytes", "arah_mesh_solve_scratch_bytes",
                  "arah_mesh_orient_scratch_bytes", "arah_mesh_boundary_loops_scratch_bytes", "arah_mesh_fill_holes_scratch_bytes"):
         getattr(lib, name).restype = C.c_size_t
         getattr(lib, name).argtypes = [C.c_int64, C.c_int64]
@@ -1322,6 +1322,48 @@ def mesh_curvature(verts, faces, mass="mixed", adjacency=None, laplacian=None, n
                                        _ptr(normal_sum.contiguous()), _ptr(curv), _ptr(mean_normal), _ptr(valid), _ptr(counts),
                                        _stream()), "arah_mesh_curvature")
     return curv, mean_normal, valid, counts
+
+
+def laplacian_solve(weight, area, adjacency, rhs, x0, pinned=None, mass_coef=0.0, stiff_coef=1.0, tol=1e-10, max_iter=10000,
+                    check_every=32):
+    """Jacobi-preconditioned conjugate gradients with the cotangent operator (arah_mesh_solve_begin / arah_mesh_solve_steps,
+    csrc/meshsolve.hpp): the arguments of meshing.laplacian_solve, everything on one GPU.  -> x (V,C) float64, iters, status (C,)
+    int32, rr, r0 (C,) float64, counts (8,) int32, classes (V,) uint8: meshing.laplacian_solve bit for bit.  The steps are
+    launched in batches of check_every, four launches a step, and the C statuses are read once per batch -- the only host
+    synchronisations; the iterate never goes to the host.  A column that stops inside a batch is left alone by the steps after it,
+    so the batching does not show in the result."""
+    from . import meshing
+    require_gpu()
+    lib = load_library()
+    what = "laplacian_solve"
+    mc, sc, tol, max_iter = meshing.check_solve_args(mass_coef, stiff_coef, tol, max_iter, what)
+    if isinstance(check_every, bool) or not isinstance(check_every, int) or check_every < 1:
+        raise ValueError("%s: check_every must be an integer >= 1, got %r" % (what, check_every))
+    w, nbr_start, nbr, V, F = _laplacian_args(weight, adjacency, what)
+    dev = w.device
+    n_ch = meshing.check_solve_tensors(area, rhs, x0, pinned, V, dev, what)
+    area, rhs, x0 = area.detach().contiguous(), rhs.detach().contiguous(), x0.detach().contiguous()
+    pin = pinned.to(torch.uint8).contiguous() if pinned is not None else None
+    with _on_device(dev):
+        x = torch.empty(V, n_ch, dtype=torch.float64, device=dev)
+        iters, status = (torch.empty(n_ch, dtype=torch.int32, device=dev) for _ in range(2))
+        rr, r0 = (torch.empty(n_ch, dtype=torch.float64, device=dev) for _ in range(2))
+        counts = torch.empty(8, dtype=torch.int32, device=dev)
+        classes = torch.empty(V, dtype=torch.uint8, device=dev)
+        nbytes = int(lib.arah_mesh_solve_scratch_bytes(V, n_ch))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)              # the state of this solve: its own, not the shared buffer
+        op = (_ptr(w), _ptr(area), _ptr(nbr_start), _ptr(nbr), C.c_int64(V), C.c_int64(F))
+        coef = (C.c_double(mc), C.c_double(sc))
+        _check(lib.arah_mesh_solve_begin(*op, _ptr(rhs), _ptr(x0), _ptr(pin), C.c_int32(n_ch), *coef, C.c_double(tol), _ptr(x),
+                                         _ptr(iters), _ptr(status), _ptr(rr), _ptr(r0), _ptr(counts), _ptr(classes), _ptr(scratch),
+                                         C.c_size_t(nbytes), _stream()), "arah_mesh_solve_begin")
+        done = 0
+        while done < max_iter and bool((status == 0).any()):                      # one synchronisation per batch
+            n = min(int(check_every), max_iter - done)
+            _check(lib.arah_mesh_solve_steps(*op, C.c_int32(n_ch), *coef, C.c_int32(n), _ptr(x), _ptr(iters), _ptr(status), _ptr(rr),
+                                             _ptr(r0), _ptr(scratch), C.c_size_t(nbytes), _stream()), "arah_mesh_solve_steps")
+            done += n
+    return x, iters, status, rr, r0, counts, classes
 
 
 def _mesh_adj_only(faces, n_verts, adjacency, what):

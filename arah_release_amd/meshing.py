@@ -1075,8 +1075,232 @@ def _mesh_smooth_cotangent(verts, faces, V, iterations, factors, pin, adjacency)
     return cur
 
 
+# ---- systems with the cotangent operator: preconditioned conjugate gradients -------------------------------------------------------
+SOLVE_MAX_VERTS = 1 << 24               # kMsMaxVerts: blocks of 256, then at most 256 chunks of 256 blocks' sums
+SOLVE_COUNTS = ("solved", "pinned", "not_live", "bad_rhs", "bad_area", "bad_diagonal")   # counts[0 .. 5] of 8; a vertex's class
+SOLVE_STATUS = ("max_iter", "converged", "breakdown")                            # a column's status 0, 1, 2
+
+
+def check_solve_args(mass_coef, stiff_coef, tol, max_iter, what="laplacian_solve"):
+    """The scalars of `laplacian_solve`, checked: -> (mass_coef, stiff_coef, tol) as Python floats and max_iter as an int."""
+    for name, x in (("mass_coef", mass_coef), ("stiff_coef", stiff_coef), ("tol", tol)):
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not math.isfinite(float(x)):
+            raise ValueError("%s: %s must be a finite number, got %r" % (what, name, x))
+    if float(mass_coef) < 0.0:
+        raise ValueError("%s: mass_coef must be >= 0, got %r" % (what, mass_coef))
+    if not float(stiff_coef) > 0.0:
+        raise ValueError("%s: stiff_coef must be > 0, got %r" % (what, stiff_coef))
+    if float(tol) < 0.0:
+        raise ValueError("%s: tol must be >= 0, got %r" % (what, tol))
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or int(max_iter) < 0:
+        raise ValueError("%s: max_iter must be an integer >= 0, got %r" % (what, max_iter))
+    return float(mass_coef), float(stiff_coef), float(tol), int(max_iter)
+
+
+def check_solve_size(n_verts, what="laplacian_solve"):
+    if n_verts > SOLVE_MAX_VERTS:
+        raise ValueError("%s: at most 2^24 vertices (the inner product's tree has three levels of 256), got %d" % (what, n_verts))
+
+
+def check_solve_tensors(area, rhs, x0, pinned, V, dev, what="laplacian_solve"):
+    """area (V,), rhs and x0 (V,C) float64 with 1 <= C <= 32, pinned (V,) bool or None, all on dev: -> C."""
+    check_solve_size(V, what)
+    f64 = torch.float64
+    if not isinstance(area, torch.Tensor) or tuple(area.shape) != (V,) or area.dtype != f64 or area.device != dev:
+        raise ValueError("%s: area must be the (V,) float64 area of mesh_cotangent, on %s" % (what, dev))
+    for name, t in (("rhs", rhs), ("x0", x0)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or int(t.shape[0]) != V or t.dtype != f64 or t.device != dev \
+                or not 1 <= int(t.shape[1]) <= LAPLACIAN_MAX_CHANNELS:
+            raise ValueError("%s: %s must be a (V, C) float64 tensor with 1 <= C <= %d, on %s" % (what, name, LAPLACIAN_MAX_CHANNELS, dev))
+    if rhs.shape != x0.shape:
+        raise ValueError("%s: rhs is %s, x0 is %s" % (what, tuple(rhs.shape), tuple(x0.shape)))
+    if pinned is not None and (not isinstance(pinned, torch.Tensor) or tuple(pinned.shape) != (V,) or pinned.dtype != torch.bool
+                               or pinned.device != dev):
+        raise ValueError("%s: pinned must be a (V,) bool tensor on %s, or None" % (what, dev))
+    return int(rhs.shape[1])
+
+
+def solve_dot(u, v):
+    """<u, v> per column of (V,C) tensors: `quadric_tree_sum` over the V products u_i v_i taken as ONE segment, written as the
+    pairs it consists of -- level by level x[2j] + x[2j + 1], an odd last element carried up unchanged.  The tree over aligned
+    blocks of 256 followed by the same tree over the blocks' sums is this same tree, which is how the device takes it.  -> (C,);
+    zeros for V = 0."""
+    x = u * v
+    if x.shape[0] == 0:
+        return torch.zeros(x.shape[1], dtype=x.dtype, device=x.device)
+    while x.shape[0] > 1:
+        even = x.shape[0] & ~1
+        s = x[0:even:2] + x[1:even:2]
+        x = torch.cat([s, x[even:]]) if even < x.shape[0] else s
+    return x[0]
+
+
+def laplacian_solve(weight, area, adjacency, rhs, x0, pinned=None, mass_coef=0.0, stiff_coef=1.0, tol=1e-10, max_iter=10000):
+    """Solve, for up to 32 independent columns, by Jacobi-preconditioned conjugate gradients in float64,
+
+        mass_coef area_v x_v - stiff_coef sum_n w_vn (x_n - x_v) = rhs_v        at every SOLVED vertex v,
+
+    with x = x0 at every other vertex.  weight (6F,) and area (V,) float64 of `mesh_cotangent`, adjacency `mesh_adjacency`; rhs and
+    x0 (V,C) float64, 1 <= C <= 32; pinned (V,) bool or None; mass_coef >= 0, stiff_coef > 0, tol >= 0 finite Python floats;
+    max_iter >= 0; V <= 2^24.  (mass_coef 0, stiff_coef 1 with pins: a Dirichlet problem, the harmonic extension; mass_coef 1,
+    stiff_coef t, rhs = area p: an implicit smoothing step.)  The cotangent stiffness is positive semi-definite whatever the signs
+    of its weights, so negative weights are allowed.  Every operation is float64 and rounded on its own.
+
+    CLASSES.  live_v: the row x0[v] is finite in every column.  An entry (v, n) of nbr is USABLE when its weight is finite and
+    live_n: decided once, from x0, never from an iterate.  dS_v = the sum of the usable weights of v in ascending neighbour id,
+    from 0.  a_v = area_v, and +0 when mass_coef is 0 (the area is not looked at then).  d_v = mass_coef a_v + stiff_coef dS_v.
+    The class of v is the first that applies: 1 pinned; 2 not live; 3 its rhs row is not finite; 4 mass_coef != 0 and area_v is not
+    finite and > 0; 5 d_v is not finite and > 0; otherwise 0: SOLVED.  Everything else is HELD: a held vertex acts as a Dirichlet
+    value where its x0 is finite and is left out of its neighbours' sums where it is not.
+
+    OPERATOR.  On solved rows Op(y)_v = mass_coef (a_v y_v) - stiff_coef acc, acc = the sum over the usable entries in ascending
+    neighbour id, from 0, of w (y_n - y_v); on held rows +0.  r, z, p, q are +0 on held rows throughout.
+
+    INNER PRODUCT.  <u, v> = `solve_dot`: the tree of `quadric_tree_sum` over the V products as one segment; its shape depends on
+    V alone.
+
+    START, per column.  r = rhs - Op(x0) on solved rows; z = r / d; p = z; rz = <r, z>; rr = <r, r>; r0 = rr; thr = (tol tol) r0.
+    A column whose r0 is not finite has status 2 (breakdown); otherwise one with rr <= thr has status 1 (converged) with 0
+    iterations -- r0 = 0 is such a case.
+
+    STEP, per column with status 0, at most max_iter times.  q = Op(p); pq = <p, q>.  If pq is not finite or not > 0: status 2, and
+    the column stops unchanged.  alpha = rz / pq; x = x + alpha p; r = r - alpha q; z = r / d (solved rows only); rz' = <r, z>; rr =
+    <r, r>; iters += 1.  If rr <= thr: status 1, and the column stops.  Otherwise beta = rz' / rz; p = z + beta p; rz = rz'.  A
+    stopped column's arrays never change again; columns do not wait for each other; after max_iter steps the status stays 0.
+
+    -> x (V,C) float64, iters (C,) int32, status (C,) int32 (SOLVE_STATUS), rr and r0 (C,) float64, counts (8,) int32 (SOLVE_COUNTS
+    by class, and two zeros), classes (V,) uint8.  The specification of arah_mesh_solve_begin / arah_mesh_solve_steps
+    (csrc/meshsolve.hpp), and what runs for meshes on the host."""
+    what = "laplacian_solve"
+    mc, sc, tol, max_iter = check_solve_args(mass_coef, stiff_coef, tol, max_iter, what)
+    weight, nbr_start, nbr, V = _laplacian_weight(weight, adjacency, what)
+    dev, f64, i32 = weight.device, torch.float64, torch.int32
+    C = check_solve_tensors(area, rhs, x0, pinned, V, dev, what)
+    rhs, x0 = rhs.detach(), x0.detach()
+    rows = int(nbr.shape[0])
+    live = torch.isfinite(x0).all(1)
+    start = nbr_start.long()
+    first, deg = start[:-1], (start[1:] - start[:-1]).clamp(min=0)
+    width = int(deg.max()) if V and rows else 0
+    k = torch.arange(width, device=dev)
+    idx = (first[:, None] + k[None, :]).clamp(0, max(rows - 1, 0))                # (V, width): the padded rows of the entries
+    n = nbr.long()[idx] if width else torch.zeros(V, 0, dtype=torch.int64, device=dev)
+    in_range = (n >= 0) & (n < V)
+    n = n.clamp(0, max(V - 1, 0))
+    w = weight[idx] if width else torch.zeros(V, 0, dtype=f64, device=dev)
+    usable = (k[None, :] < deg[:, None]) & in_range & torch.isfinite(w) & live[n]
+    zero_v = torch.zeros(V, dtype=f64, device=dev)
+    dS = zero_v.clone()
+    for j in range(width):
+        dS = dS + torch.where(usable[:, j], w[:, j], zero_v)
+    a = area.detach() if mc != 0.0 else zero_v
+    d = mc * a + sc * dS
+    cls = torch.full((V,), 5, dtype=torch.int64, device=dev)
+    cls[torch.isfinite(d) & (d > 0)] = 0
+    if mc != 0.0:
+        cls[~(torch.isfinite(a) & (a > 0))] = 4
+    cls[~torch.isfinite(rhs).all(1)] = 3
+    cls[~live] = 2
+    if pinned is not None:
+        cls[pinned] = 1
+    solved = (cls == 0)[:, None]
+    counts = torch.cat([torch.bincount(cls, minlength=6), torch.zeros(2, dtype=torch.int64, device=dev)]).to(i32)
+    d1 = torch.where(solved[:, 0], d, torch.ones_like(d))[:, None]
+    zero = torch.zeros(V, C, dtype=f64, device=dev)
+
+    def op(y):
+        acc = zero.clone()
+        for j in range(width):
+            acc = acc + torch.where(usable[:, j, None], w[:, j, None] * (y[n[:, j]] - y), zero)
+        return torch.where(solved, mc * (a[:, None] * y) - sc * acc, zero)
+
+    x = x0.clone()
+    r = torch.where(solved, rhs - op(x0), zero)
+    z = torch.where(solved, r / d1, zero)
+    p = z.clone()
+    rz, rr = solve_dot(r, z), solve_dot(r, r)
+    r0 = rr.clone()
+    thr = (tol * tol) * r0
+    status = torch.where(~torch.isfinite(r0), 2, torch.where(rr <= thr, 1, 0)).to(i32)
+    iters = torch.zeros(C, dtype=i32, device=dev)
+    for _ in range(max_iter):
+        run = status == 0
+        if not bool(run.any()):
+            break
+        q = op(p)
+        pq = solve_dot(p, q)
+        broken = run & ~(torch.isfinite(pq) & (pq > 0))
+        status[broken] = 2
+        run = run & ~broken
+        move = solved & run[None, :]
+        alpha = rz / torch.where(run, pq, torch.ones_like(pq))
+        x = torch.where(move, x + alpha * p, x)
+        r = torch.where(move, r - alpha * q, r)
+        z = torch.where(move, r / d1, z)
+        rz_new, rr_new = solve_dot(r, z), solve_dot(r, r)
+        rr = torch.where(run, rr_new, rr)
+        iters = iters + run.to(i32)
+        done = run & (rr_new <= thr)
+        status[done] = 1
+        go = run & ~done
+        beta = rz_new / torch.where(go, rz, torch.ones_like(rz))
+        p = torch.where(solved & go[None, :], z + beta * p, p)
+        rz = torch.where(go, rz_new, rz)
+    return x, iters, status, rr, r0, counts, cls.to(torch.uint8)
+
+
+def check_implicit_args(iterations, time, boundary, what="mesh_smooth_implicit"):
+    """-> (time as a Python float, pin as a bool)."""
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or int(iterations) < 0:
+        raise ValueError("%s: iterations must be an integer >= 0, got %r" % (what, iterations))
+    if time is None or isinstance(time, bool) or not isinstance(time, (int, float, np.integer, np.floating)) \
+            or not math.isfinite(float(time)) or not float(time) > 0.0:
+        raise ValueError("%s: method='implicit' needs time, a finite length squared > 0, got %r" % (what, time))
+    if boundary not in ("pin", "free"):
+        raise ValueError("%s: boundary must be 'pin' or 'free', got %r" % (what, boundary))
+    return float(time), boundary == "pin"
+
+
+def mesh_smooth_implicit(verts, faces, iterations, time, boundary="pin", adjacency=None, tol=1e-10, max_iter=10000, backend=None):
+    """Implicit fairing (Desbrun, Meyer, Schroeder, Barr 1999, "Implicit fairing of irregular meshes using diffusion and curvature
+    flow"): every iteration takes weight and area = `mesh_cotangent`(cur, faces, "mixed") of the positions it reads and solves
+    (M + time S) p' = M p over the three coordinates with `laplacian_solve`: mass_coef 1, stiff_coef time, rhs = area p (float64,
+    one rounding), x0 = p, pinned = the vertices with vert_flags bit 0 or 1 under boundary="pin", none under "free"; the solved
+    vertices take float32(p'), rounded once, the held ones stay bit for bit.  time is a length squared, > 0: one step removes
+    detail below about sqrt(time), whatever the mesh's resolution, where an explicit step is stable only for time below about an
+    edge length squared.  A column that does not converge raises RuntimeError with its status and residual.  -> verts_out (V,3)
+    float32.  backend: the module whose mesh_cotangent / laplacian_solve run (this one when None; hip for meshes on the GPU)."""
+    what = "mesh_smooth_implicit"
+    time, pin = check_implicit_args(iterations, time, boundary, what)
+    _, _, tol, max_iter = check_solve_args(1.0, time, tol, max_iter, what)
+    if backend is None:
+        verts, faces, V, _ = _mesh_verts(verts, faces, what)
+        adjacency = _adjacency_of(faces, V, adjacency, what)
+        import sys
+        backend = sys.modules[__name__]
+    else:
+        V = int(verts.shape[0])
+    check_solve_size(V, what)
+    cur = verts.clone()
+    if V == 0 or int(faces.shape[0]) == 0 or int(iterations) == 0:
+        return cur
+    pinned = (adjacency[6] & 3) != 0 if pin else None
+    for it in range(int(iterations)):
+        weight, _, area, _, _ = backend.mesh_cotangent(cur, faces, "mixed", adjacency=adjacency)
+        p = cur.to(torch.float64)
+        x, iters, status, rr, r0, _, classes = backend.laplacian_solve(weight, area, adjacency, area[:, None] * p, p, pinned=pinned,
+                                                                       mass_coef=1.0, stiff_coef=time, tol=tol, max_iter=max_iter)
+        status = status.tolist()
+        if any(s != 1 for s in status):
+            res = torch.sqrt(rr / torch.where(r0 > 0, r0, torch.ones_like(r0))).tolist()
+            raise RuntimeError("%s: iteration %d did not converge: status %s, residual %s after %s steps"
+                               % (what, it, [SOLVE_STATUS[s] for s in status], res, iters.tolist()))
+        cur = torch.where((classes == 0)[:, None], x.float(), cur)
+    return cur
+
+
 # ---- edge-collapse decimation: one round ---------------------------------------------------------------------------------------------
-COLLAPSE_MAX_UNION = 32                # faces around an edge that is still a candidate: kMqShort, one lane's tree
+COLLAPSE_MAX_UNION = 32               # faces around an edge that is still a candidate: kMqShort, one lane's tree
 COLLAPSE_COUNTS = ("n_verts", "n_faces", "selected", "applied", "candidates", "pinned", "link", "long_edges", "nonfinite", "over_error",
                    "flips", "fallbacks")
 COLLAPSE_REASONS = ("candidate", "pinned", "link", "long_edges", "nonfinite", "over_error", "flips")   # counts[4 + reason]

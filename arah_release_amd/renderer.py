@@ -923,7 +923,8 @@ class MetaAvatarRender(nn.Module):
         A dict with "method": "collapse" (target_faces or ratio, max_error, quadric_reg, max_rounds) decimates by edge collapse
         instead, geometry.decimate_mesh: a closed surface stays closed; vert_src, face_src and report are then decimate_mesh's.
         smooth (indexed=True only; None: nothing changes): a number of Taubin iterations or a dict of geometry.smooth_mesh
-        keywords -- verts are geometry.smooth_mesh of the unsmoothed call's, AFTER clean and simplify; faces, counts and ids stay.
+        keywords ({"method": "implicit", "time": t} is implicit fairing, t a length squared in metres) -- verts are
+        geometry.smooth_mesh of the unsmoothed call's, AFTER clean and simplify; faces, counts and ids stay.
         subdivide (indexed=True only; None: nothing changes): a number of uniform midpoint levels or a dict of
         geometry.subdivide_mesh keywords (levels, method, max_edge, max_rounds, max_faces) -- the mesh is geometry.subdivide_mesh of
         the call without it, AFTER clean and simplify and BEFORE smooth; verts, faces, n_verts and n_tris are the refined mesh's

@@ -45,6 +45,8 @@
  *   arah_mesh_laplacian_apply /  to per-vertex values, mean / Gaussian / principal curvatures after Meyer, Desbrun, Schroeder and Barr
  *   arah_mesh_curvature /   2002, and umbrella smoothing with cotangent weights: what the reference's users take from trimesh, libigl
  *   arah_mesh_smooth_cotangent   or pytorch3d)
+ *   arah_mesh_solve_begin / (none: systems with that operator by preconditioned conjugate gradients -- implicit smoothing, harmonic
+ *   arah_mesh_solve_steps   extension; what the reference's users take from scipy's or libigl's sparse solvers)
  *   arah_mesh_orient /      (none: the reference's users repair scans with trimesh's fix_normals / fill_holes; consistent orientation
  *   arah_mesh_boundary_loops /  by the double cover of the face graph, the boundary loops, and small holes closed by a fan around
  *   arah_mesh_fill_holes    the loop's exact mean)
@@ -583,6 +585,29 @@ int arah_mesh_smooth_cotangent(const float* verts, int64_t n_verts, const int32_
                                const int32_t* vf, const int32_t* nbr_start, const int32_t* nbr, const uint8_t* vert_flags, int32_t n_steps,
                                const float h_factors[2], int32_t pin, float* tmp, float* verts_out, void* scratch, size_t scratch_bytes,
                                void* stream);
+/* Systems with the cotangent operator, by Jacobi-preconditioned conjugate gradients in double (csrc/meshsolve.hpp;
+ * meshing.laplacian_solve is the rule, bit for bit).  weight / area of arah_mesh_cotangent, nbr_start / nbr of arah_mesh_adjacency;
+ * rhs, x0, x [n_verts][n_channels] double, 1 <= n_channels <= 32; pinned [n_verts] bytes or null; mass_coef >= 0, stiff_coef > 0,
+ * tol >= 0, all finite.  At every SOLVED vertex mass_coef area x - stiff_coef sum w (x_n - x) = rhs over the usable entries (finite
+ * weight, x0 row of the neighbour finite), x = x0 at every other; classes [n_verts]: 0 solved, 1 pinned, 2 x0 row not finite, 3 rhs
+ * row not finite, 4 area not finite and > 0 (mass_coef != 0 only), 5 diagonal not finite and > 0; counts [8]: the vertices by
+ * class, 0, 0.  Per column: iters, status (0 running, 1 converged: rr <= tol^2 r0, 2 breakdown: r0 or p.Ap not finite and > 0), rr
+ * = the squared residual, r0 = its first value.  Inner products are the fixed tree of arah_mesh_quadric_place over the vertices
+ * as one segment: workgroup trees over blocks of 256, then one workgroup per column; no floating-point atomics.
+ * arah_mesh_solve_begin writes x = x0, the classes and the start state into the scratch, and the outputs (a null output is
+ * skipped); arah_mesh_solve_steps takes n_steps steps of four launches each on that scratch with the same operator arguments, a
+ * stopped column is left alone, and iters / status / rr / r0 are written again.  No host synchronisation, no allocation.
+ * scratch: arah_mesh_solve_scratch_bytes(n_verts, n_channels) device bytes (0 for sizes that are refused), ARAH_E_WORKSPACE
+ * when short.  n_verts <= 2^24 (a longer tree needs a level more), sizes otherwise as for arah_mesh_adjacency; a bad size,
+ * coefficient or a missing pointer: ARAH_E_BADARG.  Refused calls launch nothing. */
+size_t arah_mesh_solve_scratch_bytes(int64_t n_verts, int64_t n_channels);
+int arah_mesh_solve_begin(const double* weight, const double* area, const int32_t* nbr_start, const int32_t* nbr, int64_t n_verts,
+                          int64_t n_faces, const double* rhs, const double* x0, const uint8_t* pinned, int32_t n_channels, double mass_coef,
+                          double stiff_coef, double tol, double* x, int32_t* iters, int32_t* status, double* rr, double* r0,
+                          int32_t* counts, uint8_t* classes, void* scratch, size_t scratch_bytes, void* stream);
+int arah_mesh_solve_steps(const double* weight, const double* area, const int32_t* nbr_start, const int32_t* nbr, int64_t n_verts,
+                          int64_t n_faces, int32_t n_channels, double mass_coef, double stiff_coef, int32_t n_steps, double* x,
+                          int32_t* iters, int32_t* status, double* rr, double* r0, void* scratch, size_t scratch_bytes, void* stream);
 /* Consistent orientation of an indexed mesh (csrc/meshorient.hpp; meshing.mesh_orient is the rule, bit for bit).  faces
  * [n_faces][3], and vf_start / vf / nbr_start / nbr / nbr_out / nbr_in of arah_mesh_adjacency on the same mesh.  Two valid faces are
  * neighbours across an edge that carries exactly two valid faces, consistent when they traverse it in opposite directions; the
