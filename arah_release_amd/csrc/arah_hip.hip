@@ -1955,6 +1955,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_canon_solve(FrameDev fr, const 
 #include "meshcc.hpp"
 #include "meshsimp.hpp"
 #include "meshadj.hpp"
+#include "meshedge.hpp"
 #include "meshlaplace.hpp"
 #include "meshquadric.hpp"
 #include "meshsolve.hpp"
@@ -4629,28 +4630,55 @@ int arah_mesh_adjacency(const int32_t* faces, int64_t n_faces, int64_t n_verts, 
     return check_launch();
 }
 
+// The adjacency of a round entry: the eight arrays and the build's scratch, carved from the entry's own scratch, and the read-only
+// view of them that the round's kernels take
+struct MeshAdjScratch {
+    int *vf_start, *vf, *nbr_start, *nbr, *nbr_out, *nbr_in, *counts;
+    unsigned char* vert_flags;
+    int n_verts, n_faces;
+    void* build;
+    size_t build_bytes;
+    MeshAdj view() const { return MeshAdj{vf_start, vf, nbr_start, nbr, nbr_out, nbr_in, vert_flags, counts, n_verts, n_faces}; }
+};
+
+static MeshAdjScratch carve_mesh_adj(MeshCarver& c, int64_t n_verts, int64_t n_faces) {
+    MeshAdjScratch a{};
+    const size_t V = (size_t)n_verts, F = (size_t)n_faces;
+    a.vf_start = c.take<int>(V + 1);
+    a.vf = c.take<int>(3 * F);
+    a.nbr_start = c.take<int>(V + 1);
+    a.nbr = c.take<int>(6 * F);
+    a.nbr_out = c.take<int>(6 * F);
+    a.nbr_in = c.take<int>(6 * F);
+    a.vert_flags = c.take<unsigned char>(V);
+    a.counts = c.take<int>(8);
+    a.n_verts = (int)n_verts;
+    a.n_faces = (int)n_faces;
+    a.build_bytes = carve_adjacency(nullptr, n_verts, n_faces).bytes;
+    a.build = c.take<char>(a.build_bytes);
+    return a;
+}
+
+// the one call of arah_mesh_adjacency that the three round entries make
+static int mesh_adj_build(const MeshAdjScratch& a, const int32_t* faces, void* stream) {
+    return arah_mesh_adjacency(faces, a.n_faces, a.n_verts, a.vf_start, a.vf, a.nbr_start, a.nbr, a.nbr_out, a.nbr_in, a.vert_flags,
+                               a.counts, a.build, a.build_bytes, stream);
+}
+
 // ---- one round of edge-collapse decimation (csrc/meshcollapse.hpp) ---------------------------------------------------------------
 struct MxScratch {
-    int *vf_start, *vf, *nbr_start, *nbr, *nbr_out, *nbr_in, *acounts;
-    unsigned char *vert_flags, *pinned;
+    MeshAdjScratch a;
+    unsigned char* pinned;
     int *owner, *merge_to, *move_edge, *vsrc, *new_id, *blk_count, *blk_base;
     unsigned long long *m1, *m2;
-    void* adjacency;
-    size_t adjacency_bytes, bytes;
+    size_t bytes;
 };
 
 static MxScratch carve_collapse(void* scratch, int64_t n_verts, int64_t n_faces) {
     MxScratch w{};
     MeshCarver c(scratch);
     const size_t V = (size_t)n_verts, F = (size_t)n_faces, nb = mesh_blocks(std::max(6 * n_faces, n_verts));
-    w.vf_start = c.take<int>(V + 1);
-    w.vf = c.take<int>(3 * F);
-    w.nbr_start = c.take<int>(V + 1);
-    w.nbr = c.take<int>(6 * F);
-    w.nbr_out = c.take<int>(6 * F);
-    w.nbr_in = c.take<int>(6 * F);
-    w.acounts = c.take<int>(8);
-    w.vert_flags = c.take<unsigned char>(V);
+    w.a = carve_mesh_adj(c, n_verts, n_faces);
     w.pinned = c.take<unsigned char>(V);
     w.owner = c.take<int>(6 * F);
     w.merge_to = c.take<int>(V);
@@ -4661,8 +4689,6 @@ static MxScratch carve_collapse(void* scratch, int64_t n_verts, int64_t n_faces)
     w.blk_base = c.take<int>(nb);
     w.m1 = c.take<unsigned long long>(V);
     w.m2 = c.take<unsigned long long>(V);
-    w.adjacency_bytes = carve_adjacency(nullptr, n_verts, n_faces).bytes;
-    w.adjacency = c.take<char>(w.adjacency_bytes);
     w.bytes = c.bytes();
     return w;
 }
@@ -4688,21 +4714,19 @@ static int collapse_round(const float* verts, int64_t n_verts, const int32_t* fa
     const int V = (int)n_verts, F = (int)n_faces, cap = 6 * F;
     const dim3 tb(kImeshThreads), gv(mesh_grid(V));
     // an empty mesh runs the same launches over nothing (a grid is never empty: the compactions of no element are left out)
-    if (int rc = arah_mesh_adjacency(faces, n_faces, n_verts, w.vf_start, w.vf, w.nbr_start, w.nbr, w.nbr_out, w.nbr_in, w.vert_flags,
-                                     w.acounts, w.adjacency, w.adjacency_bytes, stream))
-        return rc;
-    hipLaunchKernelGGL(k_mx_pin, gv, tb, 0, s, verts, V, (const int*)w.nbr_start, (const int*)w.nbr_out, (const int*)w.nbr_in, w.pinned,
-                       w.owner, w.m1, w.merge_to, w.move_edge, w.vsrc, (int*)counts, bounded ? kMxBoundedCounts : kMxCounts);
+    if (int rc = mesh_adj_build(w.a, faces, stream)) return rc;
+    const MeshAdj adj = w.a.view();
+    hipLaunchKernelGGL(k_mx_pin, gv, tb, 0, s, verts, adj, w.pinned, w.owner, w.m1, w.merge_to, w.move_edge, w.vsrc, (int*)counts,
+                       bounded ? kMxBoundedCounts : kMxCounts);
     if (F > 0)
-        hipLaunchKernelGGL(k_mx_edge, dim3(mesh_grid(cap)), tb, 0, s, verts, (const int*)faces, V, cap, (const int*)w.vf_start,
-                           (const int*)w.vf, (const int*)w.nbr_start, (const int*)w.nbr, (const unsigned char*)w.pinned,
+        hipLaunchKernelGGL(k_mx_edge, dim3(mesh_grid(cap)), tb, 0, s, verts, (const int*)faces, adj, cap, (const unsigned char*)w.pinned,
                            (const int*)w.owner, reg, max_cost, bounded, short_len2, long_len2, edge_pos, (unsigned long long*)edge_key, (unsigned char*)edge_reason,
                            w.m1, (int*)counts);
-    hipLaunchKernelGGL(k_mx_m2, gv, tb, 0, s, V, (const int*)w.nbr_start, (const int*)w.nbr, (const unsigned long long*)w.m1, w.m2);
+    hipLaunchKernelGGL(k_mx_m2, gv, tb, 0, s, V, adj.nbr_start, adj.nbr, (const unsigned long long*)w.m1, w.m2);
     if (F > 0)
         mesh_compact_passes(s, (int)mesh_blocks(cap), w.blk_count, w.blk_base, counts + 2, [&](auto fill, int* count, const int* base) {
-            hipLaunchKernelGGL((k_mx_select<decltype(fill)::value>), dim3(mesh_blocks(cap)), tb, 0, s, verts, V, cap,
-                               (const int*)w.nbr_start, (const int*)w.nbr, (const int*)w.owner, (const float*)edge_pos,
+            hipLaunchKernelGGL((k_mx_select<decltype(fill)::value>), dim3(mesh_blocks(cap)), tb, 0, s, verts, adj, cap,
+                               (const int*)w.owner, (const float*)edge_pos,
                                (const unsigned long long*)edge_key, (const unsigned long long*)w.m2, (int)need, count, base,
                                w.merge_to, w.move_edge, w.vsrc);
         });
@@ -4740,30 +4764,18 @@ int arah_mesh_collapse_round_bounded(const float* verts, int64_t n_verts, const 
 
 // ---- one round of edge flips (csrc/meshflip.hpp) -------------------------------------------------------------------------------------
 struct MeshFlipScratch {
-    int *vf_start, *vf, *nbr_start, *nbr, *nbr_out, *nbr_in, *acounts;
-    unsigned char* vert_flags;
+    MeshAdjScratch a;
     int* owner;
     unsigned long long* lock;
-    void* adjacency;
-    size_t adjacency_bytes, bytes;
+    size_t bytes;
 };
 
 static MeshFlipScratch carve_flip(void* scratch, int64_t n_verts, int64_t n_faces) {
     MeshFlipScratch w{};
     MeshCarver c(scratch);
-    const size_t V = (size_t)n_verts, F = (size_t)n_faces;
-    w.vf_start = c.take<int>(V + 1);
-    w.vf = c.take<int>(3 * F);
-    w.nbr_start = c.take<int>(V + 1);
-    w.nbr = c.take<int>(6 * F);
-    w.nbr_out = c.take<int>(6 * F);
-    w.nbr_in = c.take<int>(6 * F);
-    w.acounts = c.take<int>(8);
-    w.vert_flags = c.take<unsigned char>(V);
-    w.owner = c.take<int>(6 * F);
-    w.lock = c.take<unsigned long long>(V);
-    w.adjacency_bytes = carve_adjacency(nullptr, n_verts, n_faces).bytes;
-    w.adjacency = c.take<char>(w.adjacency_bytes);
+    w.a = carve_mesh_adj(c, n_verts, n_faces);
+    w.owner = c.take<int>(6 * (size_t)n_faces);
+    w.lock = c.take<unsigned long long>((size_t)n_verts);
     w.bytes = c.bytes();
     return w;
 }
@@ -4784,30 +4796,26 @@ int arah_mesh_flip_round(const float* verts, int64_t n_verts, const int32_t* fac
     const int V = (int)n_verts, F = (int)n_faces, cap = 6 * F;
     const dim3 tb(kImeshThreads);
     // an empty mesh runs the adjacency's launches and k_mf_init over nothing: the counts are cleared, nbr_start[V] = 0
-    if (int rc = arah_mesh_adjacency(faces, n_faces, n_verts, w.vf_start, w.vf, w.nbr_start, w.nbr, w.nbr_out, w.nbr_in, w.vert_flags,
-                                     w.acounts, w.adjacency, w.adjacency_bytes, stream))
-        return rc;
-    hipLaunchKernelGGL(k_mf_init, dim3(mesh_grid(std::max(n_verts, n_faces))), tb, 0, s, (const int*)faces, F, V, (const int*)w.nbr_start,
-                       w.owner, w.lock, (int*)faces_out, (unsigned char*)face_flag, (int*)counts);
+    if (int rc = mesh_adj_build(w.a, faces, stream)) return rc;
+    const MeshAdj adj = w.a.view();
+    hipLaunchKernelGGL(k_mf_init, dim3(mesh_grid(std::max(n_verts, n_faces))), tb, 0, s, (const int*)faces, adj, w.owner, w.lock,
+                       (int*)faces_out, (unsigned char*)face_flag, (int*)counts);
     if (F > 0) {   // without a vertex nbr_start[0] = 0: no entry names an edge, and no vertex is read
-        hipLaunchKernelGGL(k_mf_edge, dim3(mesh_grid(cap)), tb, 0, s, verts, (const int*)faces, V, cap, (const int*)w.vf_start,
-                           (const int*)w.vf, (const int*)w.nbr_start, (const int*)w.nbr, (const int*)w.nbr_out, (const int*)w.nbr_in,
-                           (const unsigned char*)w.vert_flags, (const int*)w.owner, (int)criterion, (unsigned)(salt * 0x9e3779b9u),
-                           (unsigned long long*)edge_key, (unsigned char*)edge_reason, w.lock, (int*)counts);
-        hipLaunchKernelGGL(k_mf_apply, dim3(mesh_grid(cap)), tb, 0, s, (const int*)faces, V, cap, (const int*)w.vf_start, (const int*)w.vf,
-                           (const int*)w.nbr_start, (const int*)w.nbr, (const int*)w.owner, (const unsigned long long*)edge_key,
-                           (const unsigned long long*)w.lock, (int*)faces_out, (unsigned char*)face_flag, (int*)counts);
+        hipLaunchKernelGGL(k_mf_edge, dim3(mesh_grid(cap)), tb, 0, s, verts, (const int*)faces, adj, cap, (const int*)w.owner,
+                           (int)criterion, (unsigned)(salt * 0x9e3779b9u), (unsigned long long*)edge_key, (unsigned char*)edge_reason,
+                           w.lock, (int*)counts);
+        hipLaunchKernelGGL(k_mf_apply, dim3(mesh_grid(cap)), tb, 0, s, (const int*)faces, adj, cap, (const int*)w.owner,
+                           (const unsigned long long*)edge_key, (const unsigned long long*)w.lock, (int*)faces_out,
+                           (unsigned char*)face_flag, (int*)counts);
     }
     return check_launch();
 }
 
 // ---- one round of subdivision (csrc/meshsubdiv.hpp) --------------------------------------------------------------------------------
 struct SbScratch {
-    int *vf_start, *vf, *nbr_start, *nbr, *nbr_out, *nbr_in, *acounts;
-    unsigned char* vert_flags;
+    MeshAdjScratch a;
     int *owner, *rank, *opp, *fent, *totals, *blk_count, *blk_base, *vert_stat, *mark_stat, *face_stat;
-    void* adjacency;
-    size_t adjacency_bytes, bytes;
+    size_t bytes;
 };
 
 // F <= 2^26 and V + 3 F < 2^31: the ids of the output's vertices and the 4 F rows of its faces fit an int32
@@ -4818,16 +4826,9 @@ static bool sb_sizes_ok(int64_t n_verts, int64_t n_faces) {
 static SbScratch carve_subdivide(void* scratch, int64_t n_verts, int64_t n_faces) {
     SbScratch w{};
     MeshCarver c(scratch);
-    const size_t V = (size_t)n_verts, F = (size_t)n_faces;
+    const size_t F = (size_t)n_faces;
     const size_t nbv = mesh_blocks(n_verts), nbe = mesh_blocks(6 * n_faces), nbf = mesh_blocks(n_faces);
-    w.vf_start = c.take<int>(V + 1);
-    w.vf = c.take<int>(3 * F);
-    w.nbr_start = c.take<int>(V + 1);
-    w.nbr = c.take<int>(6 * F);
-    w.nbr_out = c.take<int>(6 * F);
-    w.nbr_in = c.take<int>(6 * F);
-    w.acounts = c.take<int>(8);
-    w.vert_flags = c.take<unsigned char>(V);
+    w.a = carve_mesh_adj(c, n_verts, n_faces);
     w.owner = c.take<int>(6 * F);
     w.rank = c.take<int>(6 * F);
     w.opp = c.take<int>(12 * F);
@@ -4838,8 +4839,6 @@ static SbScratch carve_subdivide(void* scratch, int64_t n_verts, int64_t n_faces
     w.vert_stat = c.take<int>(3 * nbv);
     w.mark_stat = c.take<int>(3 * nbe);
     w.face_stat = c.take<int>(3 * nbf);
-    w.adjacency_bytes = carve_adjacency(nullptr, n_verts, n_faces).bytes;
-    w.adjacency = c.take<char>(w.adjacency_bytes);
     w.bytes = c.bytes();
     return w;
 }
@@ -4863,28 +4862,25 @@ int arah_mesh_subdivide_round(const float* verts, int64_t n_verts, const int32_t
     const int nbv = (int)mesh_blocks(V), nbe = (int)mesh_blocks(cap), nbf = (int)mesh_blocks(F);
     const dim3 tb(kImeshThreads), gv(mesh_grid(V));
     // an empty mesh runs the adjacency's launches over nothing (nbr_start[V] = 0); the walks of no element are left out
-    if (int rc = arah_mesh_adjacency(faces, n_faces, n_verts, w.vf_start, w.vf, w.nbr_start, w.nbr, w.nbr_out, w.nbr_in, w.vert_flags,
-                                     w.acounts, w.adjacency, w.adjacency_bytes, stream))
-        return rc;
+    if (int rc = mesh_adj_build(w.a, faces, stream)) return rc;
+    const MeshAdj adj = w.a.view();
     if (V > 0) {
-        hipLaunchKernelGGL(k_sb_owner, gv, tb, 0, s, V, (const int*)w.nbr_start, w.owner);
-        hipLaunchKernelGGL(k_sb_verts, dim3(nbv), tb, 0, s, verts, V, (const int*)w.nbr_start, (const int*)w.nbr, (const int*)w.nbr_out,
-                           (const int*)w.nbr_in, loop, w.blk_count, w.vert_stat, verts_out, (int*)vert_src);
+        hipLaunchKernelGGL(k_sb_owner, gv, tb, 0, s, adj, w.owner);
+        hipLaunchKernelGGL(k_sb_verts, dim3(nbv), tb, 0, s, verts, adj, loop, w.blk_count, w.vert_stat, verts_out, (int*)vert_src);
     }
     if (F > 0) {
-        hipLaunchKernelGGL(k_sb_face_entries, dim3(mesh_grid(F)), tb, 0, s, (const int*)faces, F, V, (const int*)w.nbr_start,
-                           (const int*)w.nbr, loop, w.fent, w.opp);
+        hipLaunchKernelGGL(k_sb_face_entries, dim3(mesh_grid(F)), tb, 0, s, (const int*)faces, adj, loop, w.fent, w.opp);
         mesh_compact_passes(s, nbe, w.blk_count, w.blk_base, w.totals, [&](auto fill, int* count, const int* base) {
-            hipLaunchKernelGGL((k_sb_marks<decltype(fill)::value>), dim3(nbe), tb, 0, s, verts, V, cap, (const int*)w.nbr_start,
-                               (const int*)w.nbr, (const int*)w.nbr_out, (const int*)w.nbr_in, (const int*)w.owner, (const int*)w.opp,
-                               loop, (int)(has_threshold != 0), max_len2, count, base, w.mark_stat, w.rank, verts_out, (int*)vert_src);
+            hipLaunchKernelGGL((k_sb_marks<decltype(fill)::value>), dim3(nbe), tb, 0, s, verts, adj, cap, (const int*)w.owner,
+                               (const int*)w.opp, loop, (int)(has_threshold != 0), max_len2, count, base, w.mark_stat, w.rank, verts_out,
+                               (int*)vert_src);
         });
         mesh_compact_passes(s, nbf, w.blk_count, w.blk_base, w.totals + 1, [&](auto fill, int* count, const int* base) {
             hipLaunchKernelGGL((k_sb_faces<decltype(fill)::value>), dim3(nbf), tb, 0, s, (const int*)faces, F, V, (const int*)w.fent,
                                (const int*)w.rank, count, base, w.face_stat, (const float*)verts_out, (int*)faces_out, (int*)face_src);
         });
     }
-    hipLaunchKernelGGL(k_sb_finish, dim3(1), tb, 0, s, V, F, (const int*)w.acounts, F > 0 ? (const int*)w.totals : (const int*)nullptr,
+    hipLaunchKernelGGL(k_sb_finish, dim3(1), tb, 0, s, V, F, adj.counts, F > 0 ? (const int*)w.totals : (const int*)nullptr,
                        F > 0 ? (const int*)(w.totals + 1) : (const int*)nullptr, (const int*)w.vert_stat, V > 0 ? nbv : 0,
                        (const int*)w.mark_stat, F > 0 ? nbe : 0, (const int*)w.face_stat, F > 0 ? nbf : 0, (int*)counts);
     if (F > 0) {

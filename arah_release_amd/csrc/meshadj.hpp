@@ -37,10 +37,27 @@
 // are sorted before anything reads them, ties between equal edge keys broken by position -- equal keys are interchangeable.  No
 // thread waits for another: no spin-wait, no grid-wide barrier; every loop ends by an argument of its own, stated at the loop.
 // kImeshThreads, kImeshMaxGrid, k_mc_scan and k_mc_pad_words are meshcommon.hpp's.
+//
+// WHAT THE OTHER HEADERS TAKE FROM HERE: MeshAdj, the device view of the eight arrays, which the kernels of a round (collapse,
+// flip, subdivide) take by value, and ma_face_ok.  The build kernels below keep their own arguments: they write the arrays.  The
+// three gathers at the end of this file and the kernels of meshlaplace.hpp keep theirs too: each runs for 5 to 8 us on 50 k
+// vertices and took 0.5 us longer with the view's larger argument block, its instructions after the argument loads unchanged
+// (profiles/mesh_adj_bench.txt).  What is done WITH the view -- the owner of an entry, the walk over the entries, the bisection
+// of a neighbour segment, the merge of two segments, the float64 helpers -- is meshedge.hpp's, included right after this file.
 #pragma once
 
 constexpr int kMaShort = 32;              // elements of a segment one thread still sorts alone: at most 32^2 comparisons
 constexpr int kMaLongGrid = 1024;         // workgroups that share the long segments
+
+// The adjacency as the kernels of a round see it: the eight arrays of arah_mesh_adjacency and the sizes they were built for.  The
+// round's entry carves the arrays from its own scratch and builds them (the host side: carve_mesh_adj, mesh_adj_build), so they
+// are trusted: segments are not clamped and ids are followed.
+struct MeshAdj {
+    const int *vf_start, *vf, *nbr_start, *nbr, *nbr_out, *nbr_in;
+    const unsigned char* vert_flags;
+    const int* counts;
+    int n_verts, n_faces;
+};
 
 // the three ids of face f when it is valid: in range and pairwise different
 __device__ __forceinline__ bool ma_face_ok(const int* __restrict__ faces, long long f, int n_verts, int id[3]) {

@@ -36,7 +36,8 @@
 //   k_mx_finish        counts[3] = min(selected, need)
 //
 // Integer atomics only (min, add).  No thread waits for another: no spin-wait, no grid-wide barrier; every loop ends by an
-// argument of its own, stated at the loop.
+// argument of its own, stated at the loop.  MeshAdj is meshadj.hpp's; the owner fill, the entry walk, the merge (MaMerge) and the
+// float64 helpers (ma_d2, ma_dot, ma_cross) are meshedge.hpp's.
 //
 // arah_mesh_collapse_round_bounded runs the same launches with `bounded` set, for the isotropic remesher (meshflip.hpp tells the
 // rest): k_mx_edge then refuses, BEFORE every other test, an edge whose squared length in double is not below short_len2 (reason
@@ -48,8 +49,8 @@
 // NOT MEASURED AGAINST AN ALTERNATIVE: one lane per edge (its tree keeps 6 x 10 doubles of partial sums in registers, which
 // bounds the occupancy, and the lanes of a wave diverge on the reason and on the segment lengths; a wave per edge with the ten
 // columns spread over lanes is the alternative); streaming the merge of the two face segments three times from the cache
-// instead of keeping the up to 32 face ids in LDS (32 KiB per workgroup) or in scratch; the owner array instead of a binary
-// search of nbr_start; kMqShort = 32 as the bound on the faces around an edge, which also caps the valence decimation can grow
+// instead of keeping the up to 32 face ids in LDS (32 KiB per workgroup) or in scratch; the owner array (meshedge.hpp tells
+// that one); kMqShort = 32 as the bound on the faces around an edge, which also caps the valence decimation can grow
 // -- a choice.
 #pragma once
 
@@ -58,62 +59,7 @@ constexpr int kMxNoEdge = 255;                   // edge_reason of an entry that
 constexpr int kMxCounts = 12;                    // n_verts, n_faces, selected, applied, candidates, six reasons, fallbacks
 constexpr int kMxBoundedCounts = 14;             // arah_mesh_collapse_round_bounded: and the reasons 7 (not short) and 8 (too long)
 
-// The merge of two ascending lists without repeats: the values of both, ascending, each once.
-struct MxMerge {
-    const int *a, *b;
-    int i, ni, j, nj;
-};
-
-__device__ __forceinline__ MxMerge mx_merge(const int* __restrict__ list, const int* __restrict__ start, int u, int v) {
-    return MxMerge{list + start[u], list + start[v], 0, start[u + 1] - start[u], 0, start[v + 1] - start[v]};
-}
-
-__device__ __forceinline__ bool mx_more(const MxMerge& w) { return w.i < w.ni || w.j < w.nj; }
-
-// the next value (call it while mx_more); both = it stands in both lists.  Every call consumes at least one element.  The ids
-// of faces and vertices lie below INT32_MAX, which stands for an exhausted list
-__device__ __forceinline__ int mx_next(MxMerge& w, bool& both) {
-    const int x = w.i < w.ni ? w.a[w.i] : INT32_MAX, y = w.j < w.nj ? w.b[w.j] : INT32_MAX;
-    both = x == y;
-    if (x <= y) ++w.i;
-    if (y <= x) ++w.j;
-    return min(x, y);
-}
-
-// (p1 - p0) x (p2 - p0), the components as mq_term forms them
-__device__ __forceinline__ void mx_cross(const double p[3][3], double n[3]) {
-#pragma clang fp contract(off)
-    double e1[3], e2[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        e1[a] = p[1][a] - p[0][a];
-        e2[a] = p[2][a] - p[0][a];
-    }
-    n[0] = e1[1] * e2[2] - e1[2] * e2[1];
-    n[1] = e1[2] * e2[0] - e1[0] * e2[2];
-    n[2] = e1[0] * e2[1] - e1[1] * e2[0];
-}
-
-// the squared length of the edge {u, v} in double, summed left to right
-__device__ __forceinline__ double mx_len2(const float* __restrict__ verts, int u, int v) {
-#pragma clang fp contract(off)
-    const double dx = (double)verts[3 * (size_t)u + 0] - (double)verts[3 * (size_t)v + 0];
-    const double dy = (double)verts[3 * (size_t)u + 1] - (double)verts[3 * (size_t)v + 1];
-    const double dz = (double)verts[3 * (size_t)u + 2] - (double)verts[3 * (size_t)v + 2];
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
-// float32 of the squared distance of vertex x to pos, evaluated in double
-__device__ __forceinline__ float mx_d2(const float* __restrict__ verts, int x, const float pos[3]) {
-#pragma clang fp contract(off)
-    const double dx = (double)verts[3 * (size_t)x + 0] - (double)pos[0];
-    const double dy = (double)verts[3 * (size_t)x + 1] - (double)pos[1];
-    const double dz = (double)verts[3 * (size_t)x + 2] - (double)pos[2];
-    return (float)((dx * dx + dy * dy) + dz * dz);
-}
-
-__global__ __launch_bounds__(kImeshThreads) void k_mx_pin(const float* __restrict__ verts, int n_verts, const int* __restrict__ nbr_start,
-                                                          const int* __restrict__ nbr_out, const int* __restrict__ nbr_in,
+__global__ __launch_bounds__(kImeshThreads) void k_mx_pin(const float* __restrict__ verts, MeshAdj adj,
                                                           unsigned char* __restrict__ pinned, int* __restrict__ owner,
                                                           unsigned long long* __restrict__ m1, int* __restrict__ merge_to,
                                                           int* __restrict__ move_edge, int* __restrict__ vsrc, int* __restrict__ counts,
@@ -121,13 +67,11 @@ __global__ __launch_bounds__(kImeshThreads) void k_mx_pin(const float* __restric
     if (blockIdx.x == 0 && threadIdx.x < n_counts) counts[threadIdx.x] = 0;
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_verts - v strictly decreases (step >= 1) and the loop ends when it reaches 0
-    for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < n_verts; v += step) {
-        const int first = nbr_start[v], last = nbr_start[v + 1];
-        bool pin = first == last || !isfinite(verts[3 * v + 0]) || !isfinite(verts[3 * v + 1]) || !isfinite(verts[3 * v + 2]);
-        for (int i = first; i < last; ++i) {   // terminates: last - i strictly decreases.  i < nbr_start[V] <= 6 F
-            owner[i] = (int)v;
-            pin = pin || nbr_out[i] != 1 || nbr_in[i] != 1;
-        }
+    for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < adj.n_verts; v += step) {
+        const int first = adj.nbr_start[v], last = adj.nbr_start[v + 1];
+        bool pin = first == last || !ma_finite(verts, v);
+        ma_fill_owner(adj, v, owner);
+        for (int i = first; i < last; ++i) pin = pin || adj.nbr_out[i] != 1 || adj.nbr_in[i] != 1;   // terminates: last - i decreases
         pinned[v] = pin ? 1 : 0;
         m1[v] = kMxEmpty;
         merge_to[v] = (int)v;
@@ -136,51 +80,47 @@ __global__ __launch_bounds__(kImeshThreads) void k_mx_pin(const float* __restric
     }
 }
 
-__global__ __launch_bounds__(kImeshThreads) void k_mx_edge(const float* __restrict__ verts, const int* __restrict__ faces, int n_verts,
-                                                           int n_entries_cap, const int* __restrict__ vf_start, const int* __restrict__ vf,
-                                                           const int* __restrict__ nbr_start, const int* __restrict__ nbr,
-                                                           const unsigned char* __restrict__ pinned, const int* __restrict__ owner,
+__global__ __launch_bounds__(kImeshThreads) void k_mx_edge(const float* __restrict__ verts, const int* __restrict__ faces, MeshAdj adj,
+                                                           int n_entries_cap, const unsigned char* __restrict__ pinned,
+                                                           const int* __restrict__ owner,
                                                            double reg, float max_cost, int bounded, double short_len2,
                                                            double long_len2, float* __restrict__ edge_pos,
                                                            unsigned long long* __restrict__ edge_key, unsigned char* __restrict__ edge_reason,
                                                            unsigned long long* m1, int* counts) {
 #pragma clang fp contract(off)
-    const int n_entries = nbr_start[n_verts];
-    const long long step = (long long)gridDim.x * blockDim.x, end = ((long long)n_entries_cap + 63) & ~63ll;
-    // terminates: end - i strictly decreases (step >= 1) and the loop ends when it reaches 0.  The entry count is rounded up to
-    // whole waves so that every lane reaches the ballots of cc_add_one; lanes beyond the end carry no entry
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < end; i += step) {
-        const bool is_edge = i < n_entries && nbr[i] > owner[i];
+    ma_entry_walk(adj, owner, n_entries_cap, [&](long long i, bool is_edge, int u, int v) {
+#pragma clang fp contract(off)
         int reason = 0;
         bool fell = false;
         float pos[3] = {0.f, 0.f, 0.f};
         unsigned long long key = kMxEmpty;
         if (is_edge) {
-            const int u = owner[i], v = nbr[i];
-            if (bounded && !(mx_len2(verts, u, v) < short_len2)) {   // the bounded entry's first test; not a number: refused
+            // the bounded entry's first test; not a number: refused
+            if (bounded && !(ma_d2(verts + 3 * (size_t)u, verts + 3 * (size_t)v) < short_len2)) {
                 reason = 7;
             } else if (pinned[u] || pinned[v]) {
                 reason = 1;
             } else {
                 bool both;
                 int common = 0, shared = 0, third[2] = {-1, -1};
-                MxMerge w = mx_merge(nbr, nbr_start, u, v);
-                while (mx_more(w)) {   // terminates: every call consumes an element of the two segments
-                    mx_next(w, both);
+                MaMerge w = ma_merge(adj.nbr, adj.nbr_start, u, v);
+                while (ma_more(w)) {   // terminates: every call consumes an element of the two segments
+                    ma_next(w, both);
                     common += both ? 1 : 0;
                 }
-                w = mx_merge(vf, vf_start, u, v);
-                while (mx_more(w)) {   // terminates: as above
-                    const int f = mx_next(w, both);
+                w = ma_merge(adj.vf, adj.vf_start, u, v);
+                while (ma_more(w)) {   // terminates: as above
+                    const int f = ma_next(w, both);
                     if (both) {   // a valid face of this mesh: its ids lie in [0, V) and two of them are u and v
                         if (shared < 2) third[shared] = faces[3 * (size_t)f + 0] + faces[3 * (size_t)f + 1] + faces[3 * (size_t)f + 2] - u - v;
                         ++shared;
                     }
                 }
                 // the faces around the edge: both ends are free, so exactly two faces name both
-                const int n = (vf_start[u + 1] - vf_start[u]) + (vf_start[v + 1] - vf_start[v]) - 2;
+                const int n = (adj.vf_start[u + 1] - adj.vf_start[u]) + (adj.vf_start[v + 1] - adj.vf_start[v]) - 2;
                 const int a = third[0], b = third[1];
-                if (shared != 2 || a == b || common != 2 || nbr_start[a + 1] - nbr_start[a] < 4 || nbr_start[b + 1] - nbr_start[b] < 4) {
+                if (shared != 2 || a == b || common != 2 || adj.nbr_start[a + 1] - adj.nbr_start[a] < 4 ||
+                    adj.nbr_start[b + 1] - adj.nbr_start[b] < 4) {
                     reason = 2;
                 } else if (n > kMqShort) {
                     reason = 3;
@@ -194,10 +134,10 @@ __global__ __launch_bounds__(kImeshThreads) void k_mx_edge(const float* __restri
                         cell = fmax(cell, fabs(pu[c] - pv[c]));
                     }
                     double q[10];
-                    w = mx_merge(vf, vf_start, u, v);
+                    w = ma_merge(adj.vf, adj.vf_start, u, v);
                     // n calls, each consumes at least one of the n + 2 elements of the two segments and the two shared faces
                     // consume two: the merge holds exactly n values
-                    mq_lane_tree<10>(n, [&](int, double x[10]) { mq_term<10>(verts, faces, (long long)mx_next(w, both), m, x); }, q);
+                    mq_lane_tree<10>(n, [&](int, double x[10]) { mq_term<10>(verts, faces, (long long)ma_next(w, both), m, x); }, q);
                     double y[3] = {0.0, 0.0, 0.0};
                     fell = !mq_solve_offset(q, cell, reg, y);
 #pragma unroll
@@ -215,9 +155,9 @@ __global__ __launch_bounds__(kImeshThreads) void k_mx_edge(const float* __restri
                     } else {
                         const double pn[3] = {(double)pos[0], (double)pos[1], (double)pos[2]};
                         bool flipped = false, far = false;
-                        w = mx_merge(vf, vf_start, u, v);
-                        while (mx_more(w)) {   // terminates: as above
-                            const int f = mx_next(w, both);
+                        w = ma_merge(adj.vf, adj.vf_start, u, v);
+                        while (ma_more(w)) {   // terminates: as above
+                            const int f = ma_next(w, both);
                             if (both) continue;
                             double p[3][3], n0[3], n1[3];
                             int moves = 0;
@@ -232,14 +172,13 @@ __global__ __launch_bounds__(kImeshThreads) void k_mx_edge(const float* __restri
                                     far = far || (dx * dx + dy * dy) + dz * dz > long_len2;
                                 }
                             }
-                            mx_cross(p, n0);
+                            ma_cross(p[0], p[1], p[2], n0);
 #pragma unroll
                             for (int c = 0; c < 3; ++c)
 #pragma unroll
                                 for (int x = 0; x < 3; ++x) p[c][x] = c == moves ? pn[x] : p[c][x];
-                            mx_cross(p, n1);
-                            const double dot = (n0[0] * n1[0] + n0[1] * n1[1]) + n0[2] * n1[2];
-                            flipped = flipped || !(dot > 0.0);
+                            ma_cross(p[0], p[1], p[2], n1);
+                            flipped = flipped || !(ma_dot(n0, n1) > 0.0);
                         }
                         if (flipped) {
                             reason = 6;
@@ -263,7 +202,7 @@ __global__ __launch_bounds__(kImeshThreads) void k_mx_edge(const float* __restri
         }
         cc_add_one(counts, reason <= 6 ? 4 + reason : 5 + reason, is_edge);   // reason <= 6: counts[4 .. 10]; 7, 8 (bounded): 12, 13
         cc_add_one(counts + 11, 0, fell);
-    }
+    });
 }
 
 __global__ __launch_bounds__(kImeshThreads) void k_mx_m2(int n_verts, const int* __restrict__ nbr_start, const int* __restrict__ nbr,
@@ -280,28 +219,28 @@ __global__ __launch_bounds__(kImeshThreads) void k_mx_m2(int n_verts, const int*
 
 // the selected edges in ascending id; FILL: the first `need` of them are applied
 template <bool FILL>
-__global__ __launch_bounds__(kImeshThreads) void k_mx_select(const float* __restrict__ verts, int n_verts, int n_entries_cap,
-                                                             const int* __restrict__ nbr_start, const int* __restrict__ nbr,
+__global__ __launch_bounds__(kImeshThreads) void k_mx_select(const float* __restrict__ verts, MeshAdj adj, int n_entries_cap,
                                                              const int* __restrict__ owner, const float* __restrict__ edge_pos,
                                                              const unsigned long long* __restrict__ edge_key,
                                                              const unsigned long long* __restrict__ m2, int need,
                                                              int* __restrict__ blk_count, const int* __restrict__ blk_base,
                                                              int* __restrict__ merge_to, int* __restrict__ move_edge, int* __restrict__ vsrc) {
-    const int n_entries = nbr_start[n_verts];
+    const int n_entries = adj.nbr_start[adj.n_verts];
     mesh_compact<FILL, MeshNoState>(
         n_entries_cap, blk_count, blk_base,
         [&](long long i, MeshNoState&) {
             if (i >= n_entries) return false;
             const unsigned long long key = edge_key[i];
-            return key != kMxEmpty && m2[owner[i]] == key && m2[nbr[i]] == key;
+            return key != kMxEmpty && m2[owner[i]] == key && m2[adj.nbr[i]] == key;
         },
         [&](long long i, bool ok, bool mark, int at, const MeshNoState&) {
             if (mark && at < need) {   // selected edges share no end: every row below is written by one edge at most
-                const int u = owner[i], v = nbr[i];
+                const int u = owner[i], v = adj.nbr[i];
                 const float pos[3] = {edge_pos[3 * i + 0], edge_pos[3 * i + 1], edge_pos[3 * i + 2]};
                 merge_to[v] = u;
                 move_edge[u] = (int)i;
-                vsrc[u] = mx_d2(verts, v, pos) < mx_d2(verts, u, pos) ? v : u;
+                // the nearer end by float32 of the squared distances, which are evaluated in double
+                vsrc[u] = (float)ma_d2(verts + 3 * (size_t)v, pos) < (float)ma_d2(verts + 3 * (size_t)u, pos) ? v : u;
             }
         });
 }

@@ -5,7 +5,8 @@
 // one-workgroup box reduction of the query side (meshquery.hpp, meshcontains.hpp, meshwinding.hpp).  DESIGN.md ("Indexed meshes:
 // the shared walk and the scratch carver") tells the same once, with the host side.  The query side's prefix sums stay out: they
 // include a float64 one whose summation order is part of their specification, and integer scans of three widths whose access
-// patterns were measured where they are.
+// patterns were measured where they are.  The adjacency as a kernel argument (MeshAdj) is meshadj.hpp's, and what the edge
+// kernels do with it -- owner fill, entry walk, bisection, merge, float64 helpers -- meshedge.hpp's: they need the adjacency's layout.
 //
 // COUNT / SCAN / FILL.  Every variable-length result of the indexed-mesh headers is numbered the same way, without atomics, so
 // that it is deterministic and keeps the order of its elements:

@@ -38,14 +38,15 @@
 //                  once more); the two rows rewritten and flagged -- one writer per row, see above; the selected counted
 //
 // Integer atomics only (min, add).  No thread waits for another: no spin-wait, no grid-wide barrier; every loop ends by an
-// argument of its own, stated at the loop.
+// argument of its own, stated at the loop.  MeshAdj is meshadj.hpp's; the owner fill, the entry walk, the bisection (ma_find),
+// the merge (MaMerge) and the float64 helpers (ma_load, ma_dot, ma_cross) are meshedge.hpp's.
 //
 // NOT MEASURED AGAINST AN ALTERNATIVE (nothing here has been timed against another way of doing it): one lane per entry (half
 // the entries name no edge and their lanes idle; the lanes of a wave diverge on the reason and on the segment lengths -- a
 // compacted list of the edges, or a wave per edge, are the alternatives); the four-vertex lock against meshcollapse.hpp's
 // two-pass minimum over closed neighbourhoods (which selects fewer flips per round but needs no third corners in the second
-// pass); finding the third corners again in k_mf_apply instead of keeping four ids per entry in scratch; the owner array instead
-// of a binary search of nbr_start.
+// pass); finding the third corners again in k_mf_apply instead of keeping four ids per entry in scratch; the owner array
+// (meshedge.hpp tells that one).
 #pragma once
 
 constexpr unsigned long long kMfEmpty = ~0ull;   // no key: an id is below 2^31, so no key is all ones
@@ -66,14 +67,14 @@ __device__ __forceinline__ unsigned mf_hash32(unsigned x) {
 // The faces that name both u and v, by the merge of the two ascending face segments: fa traverses u->v and has the third corner
 // a, fb traverses v->u and has the third corner b.  -> the number of such faces; the four ids are the first of each kind (-1
 // without one).  The callers have nbr_out = nbr_in = 1 for the entry, so there is exactly one of each kind.
-__device__ __forceinline__ int mf_wings(const int* __restrict__ faces, const int* __restrict__ vf_start, const int* __restrict__ vf, int u,
-                                        int v, int& fa, int& a, int& fb, int& b) {
+__device__ __forceinline__ int mf_wings(const int* __restrict__ faces, const MeshAdj& adj, int u, int v, int& fa, int& a, int& fb,
+                                        int& b) {
     fa = a = fb = b = -1;
     int shared = 0;
     bool both;
-    MxMerge w = mx_merge(vf, vf_start, u, v);
-    while (mx_more(w)) {   // terminates: every call consumes an element of the two segments
-        const int f = mx_next(w, both);
+    MaMerge w = ma_merge(adj.vf, adj.vf_start, u, v);
+    while (ma_more(w)) {   // terminates: every call consumes an element of the two segments
+        const int f = ma_next(w, both);
         if (!both) continue;   // a valid face of this mesh: its ids lie in [0, V) and two of them are u and v
         const int i0 = faces[3 * (size_t)f + 0], i1 = faces[3 * (size_t)f + 1], i2 = faces[3 * (size_t)f + 2];
         const bool fwd = (i0 == u && i1 == v) || (i1 == u && i2 == v) || (i2 == u && i0 == v);
@@ -90,32 +91,6 @@ __device__ __forceinline__ int mf_wings(const int* __restrict__ faces, const int
     return shared;
 }
 
-__device__ __forceinline__ void mf_load(const float* __restrict__ verts, int x, double p[3], bool& finite) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float t = verts[3 * (size_t)x + c];
-        finite = finite && isfinite(t);
-        p[c] = (double)t;
-    }
-}
-
-// (p1 - p0) x (p2 - p0) of three corners, as mx_cross forms it
-__device__ __forceinline__ void mf_cross(const double p0[3], const double p1[3], const double p2[3], double n[3]) {
-    double p[3][3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        p[0][c] = p0[c];
-        p[1][c] = p1[c];
-        p[2][c] = p2[c];
-    }
-    mx_cross(p, n);
-}
-
-__device__ __forceinline__ double mf_dot(const double x[3], const double y[3]) {
-#pragma clang fp contract(off)
-    return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2];
-}
-
 // The Delaunay test of the edge {s, t} with the opposite corners x and y, whose faces have the cross products Nx and Ny (any
 // sign): d = (s - c) . (t - c) and c = |N|^2 at each corner c; true when the two opposite angles sum to more than pi --
 // both d negative, or (d_n d_n) c_o > (d_o d_o) c_n with n the corner whose d is negative and o the other.  Not a number: false
@@ -130,8 +105,8 @@ __device__ __forceinline__ bool mf_wants(const double s[3], const double t[3], c
         sy[c] = s[c] - y[c];
         ty[c] = t[c] - y[c];
     }
-    const double dx = mf_dot(sx, tx), dy = mf_dot(sy, ty);
-    const double cx = mf_dot(Nx, Nx), cy = mf_dot(Ny, Ny);
+    const double dx = ma_dot(sx, tx), dy = ma_dot(sy, ty);
+    const double cx = ma_dot(Nx, Nx), cy = ma_dot(Ny, Ny);
     const double lhs = (dx * dx) * cy, rhs = (dy * dy) * cx;
     if (dx < 0.0 && dy < 0.0) return true;
     if (dx < 0.0 && dy >= 0.0) return lhs > rhs;
@@ -139,20 +114,18 @@ __device__ __forceinline__ bool mf_wants(const double s[3], const double t[3], c
     return false;
 }
 
-__global__ __launch_bounds__(kImeshThreads) void k_mf_init(const int* __restrict__ faces, int n_faces, int n_verts,
-                                                           const int* __restrict__ nbr_start, int* __restrict__ owner,
+__global__ __launch_bounds__(kImeshThreads) void k_mf_init(const int* __restrict__ faces, MeshAdj adj, int* __restrict__ owner,
                                                            unsigned long long* __restrict__ lock, int* __restrict__ faces_out,
                                                            unsigned char* __restrict__ face_flag, int* __restrict__ counts) {
     if (blockIdx.x == 0 && threadIdx.x < kMfCounts) counts[threadIdx.x] = 0;
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_verts - v strictly decreases (step >= 1) and the loop ends when it reaches 0
-    for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < n_verts; v += step) {
-        const int last = nbr_start[v + 1];
-        for (int i = nbr_start[v]; i < last; ++i) owner[i] = (int)v;   // terminates: last - i strictly decreases.  i < 6 F
+    for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < adj.n_verts; v += step) {
+        ma_fill_owner(adj, v, owner);
         lock[v] = kMfEmpty;
     }
     // terminates: n_faces - f strictly decreases (step >= 1) and the loop ends when it reaches 0
-    for (long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x; f < n_faces; f += step) {
+    for (long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x; f < adj.n_faces; f += step) {
         faces_out[3 * f + 0] = faces[3 * f + 0];
         faces_out[3 * f + 1] = faces[3 * f + 1];
         faces_out[3 * f + 2] = faces[3 * f + 2];
@@ -160,61 +133,46 @@ __global__ __launch_bounds__(kImeshThreads) void k_mf_init(const int* __restrict
     }
 }
 
-__global__ __launch_bounds__(kImeshThreads) void k_mf_edge(const float* __restrict__ verts, const int* __restrict__ faces, int n_verts,
-                                                           int n_entries_cap, const int* __restrict__ vf_start, const int* __restrict__ vf,
-                                                           const int* __restrict__ nbr_start, const int* __restrict__ nbr,
-                                                           const int* __restrict__ nbr_out, const int* __restrict__ nbr_in,
-                                                           const unsigned char* __restrict__ vert_flags, const int* __restrict__ owner,
-                                                           int criterion, unsigned salt_mix, unsigned long long* __restrict__ edge_key,
-                                                           unsigned char* __restrict__ edge_reason, unsigned long long* lock, int* counts) {
+__global__ __launch_bounds__(kImeshThreads) void k_mf_edge(const float* __restrict__ verts, const int* __restrict__ faces, MeshAdj adj,
+                                                           int n_entries_cap, const int* __restrict__ owner, int criterion, unsigned salt_mix,
+                                                           unsigned long long* __restrict__ edge_key, unsigned char* __restrict__ edge_reason,
+                                                           unsigned long long* lock, int* counts) {
 #pragma clang fp contract(off)
-    const int n_entries = nbr_start[n_verts];
-    const long long step = (long long)gridDim.x * blockDim.x, end = ((long long)n_entries_cap + 63) & ~63ll;
-    // terminates: end - i strictly decreases (step >= 1) and the loop ends when it reaches 0.  The entry count is rounded up to
-    // whole waves so that every lane reaches the ballots of cc_add_one; lanes beyond the end carry no entry
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < end; i += step) {
-        const bool is_edge = i < n_entries && nbr[i] > owner[i];
+    ma_entry_walk(adj, owner, n_entries_cap, [&](long long i, bool is_edge, int u, int v) {
+#pragma clang fp contract(off)
         int reason = 0;
         unsigned long long key = kMfEmpty;
         if (is_edge) {
-            const int u = owner[i], v = nbr[i];
             int fa, a, fb, b;
-            if (nbr_out[i] != 1 || nbr_in[i] != 1) {
+            if (adj.nbr_out[i] != 1 || adj.nbr_in[i] != 1) {
                 reason = 1;
-            } else if (mf_wings(faces, vf_start, vf, u, v, fa, a, fb, b) != 2 || fa < 0 || fb < 0 || a == b) {
+            } else if (mf_wings(faces, adj, u, v, fa, a, fb, b) != 2 || fa < 0 || fb < 0 || a == b) {
                 reason = 2;   // one face each way: two shared faces, one of each kind -- only a = b can hold here
             } else {
-                // b among a's ascending neighbours: lo..hi always brackets the first id >= b
-                int lo = nbr_start[a], hi = nbr_start[a + 1];
-                const int last = hi;
-                while (lo < hi) {   // terminates: hi - lo strictly decreases
-                    const int mid = lo + ((hi - lo) >> 1);
-                    if (nbr[mid] < b) lo = mid + 1;
-                    else hi = mid;
-                }
+                const bool is_edge_ab = ma_find(adj, a, b) >= 0;
                 double pu[3], pv[3], pa[3], pb[3];
                 bool finite = true;
-                mf_load(verts, u, pu, finite);
-                mf_load(verts, v, pv, finite);
-                mf_load(verts, a, pa, finite);
-                mf_load(verts, b, pb, finite);
-                if (lo < last && nbr[lo] == b) {
+                ma_load(verts, u, pu, finite);
+                ma_load(verts, v, pv, finite);
+                ma_load(verts, a, pa, finite);
+                ma_load(verts, b, pb, finite);
+                if (is_edge_ab) {
                     reason = 3;
                 } else if (!finite) {
                     reason = 4;
                 } else {
                     double Na[3], Nb[3], N1[3], N2[3];
-                    mf_cross(pa, pu, pv, Na);
-                    mf_cross(pb, pv, pu, Nb);
-                    mf_cross(pa, pu, pb, N1);
-                    mf_cross(pb, pv, pa, N2);
+                    ma_cross(pa, pu, pv, Na);
+                    ma_cross(pb, pv, pu, Nb);
+                    ma_cross(pa, pu, pb, N1);
+                    ma_cross(pb, pv, pa, N2);
                     bool asks;
                     if (criterion == kMfValence) {
                         const int q[4] = {u, v, a, b};
                         int before = 0, after = 0;
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
-                            const int off = (nbr_start[q[k] + 1] - nbr_start[q[k]]) - ((vert_flags[q[k]] & 1) ? 4 : 6);
+                            const int off = (adj.nbr_start[q[k] + 1] - adj.nbr_start[q[k]]) - ((adj.vert_flags[q[k]] & 1) ? 4 : 6);
                             before += abs(off);
                             after += abs(off + (k < 2 ? -1 : 1));
                         }
@@ -226,7 +184,7 @@ __global__ __launch_bounds__(kImeshThreads) void k_mf_edge(const float* __restri
                     if (!asks) {
                         reason = 5;
                     } else {
-                        const bool good = mf_dot(N1, Na) > 0.0 && mf_dot(N1, Nb) > 0.0 && mf_dot(N2, Na) > 0.0 && mf_dot(N2, Nb) > 0.0;
+                        const bool good = ma_dot(N1, Na) > 0.0 && ma_dot(N1, Nb) > 0.0 && ma_dot(N2, Na) > 0.0 && ma_dot(N2, Nb) > 0.0;
                         if (!good) {
                             reason = 6;
                         } else {   // u, v, a, b are ids of valid faces: all in [0, V)
@@ -246,26 +204,21 @@ __global__ __launch_bounds__(kImeshThreads) void k_mf_edge(const float* __restri
         }
         cc_add_one(counts, 0, is_edge);
         cc_add_one(counts, reason == 0 ? 1 : 2 + reason, is_edge);   // candidates at 1, reason r <= 6 at 2 + r <= 8
-    }
+    });
 }
 
-__global__ __launch_bounds__(kImeshThreads) void k_mf_apply(const int* __restrict__ faces, int n_verts, int n_entries_cap,
-                                                            const int* __restrict__ vf_start, const int* __restrict__ vf,
-                                                            const int* __restrict__ nbr_start, const int* __restrict__ nbr,
+__global__ __launch_bounds__(kImeshThreads) void k_mf_apply(const int* __restrict__ faces, MeshAdj adj, int n_entries_cap,
                                                             const int* __restrict__ owner, const unsigned long long* __restrict__ edge_key,
                                                             const unsigned long long* __restrict__ lock, int* __restrict__ faces_out,
                                                             unsigned char* __restrict__ face_flag, int* counts) {
-    const int n_entries = nbr_start[n_verts];
-    const long long step = (long long)gridDim.x * blockDim.x, end = ((long long)n_entries_cap + 63) & ~63ll;
-    // terminates: end - i strictly decreases (step >= 1) and the loop ends when it reaches 0; whole waves, as in k_mf_edge
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < end; i += step) {
+    ma_walk(adj, n_entries_cap, [&](long long i, bool live) {
         bool selected = false;
-        const unsigned long long key = i < n_entries ? edge_key[i] : kMfEmpty;
+        const unsigned long long key = live ? edge_key[i] : kMfEmpty;
         if (key != kMfEmpty) {   // a candidate: an edge with one face each way and two different third corners
-            const int u = owner[i], v = nbr[i];
+            const int u = owner[i], v = adj.nbr[i];
             if (lock[u] == key && lock[v] == key) {
                 int fa, a, fb, b;
-                mf_wings(faces, vf_start, vf, u, v, fa, a, fb, b);
+                mf_wings(faces, adj, u, v, fa, a, fb, b);
                 if (lock[a] == key && lock[b] == key) {   // selected flips share no vertex: every row has one writer
                     selected = true;
                     faces_out[3 * (size_t)fa + 0] = a;
@@ -280,5 +233,5 @@ __global__ __launch_bounds__(kImeshThreads) void k_mf_apply(const int* __restric
             }
         }
         cc_add_one(counts, 2, selected);
-    }
+    });
 }

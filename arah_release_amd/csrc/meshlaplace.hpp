@@ -34,6 +34,7 @@
 // caller's: rows are clamped to the arrays, ids are tested before they are followed.  No thread waits for another beyond
 // __syncthreads from workgroup-uniform control flow; every loop ends by an argument of its own, stated at the loop.
 // `#pragma clang fp contract(off)` stands in EVERY function that does arithmetic: it does not reach an inlined helper.
+// The clamp of a vertex's rows (ma_segment) and ma_dot are meshedge.hpp's.
 #pragma once
 
 constexpr double kMlTwoPi = 6.283185307179586;    // the doubles nearest to 2 pi and pi: meshing.TWO_PI, meshing.PI
@@ -45,11 +46,6 @@ struct MlFace {
     double A2, dot[3], l2[3];
     int state;   // 0 contributing, 1 degenerate, 2 nonfinite
 };
-
-__device__ __forceinline__ double ml_dot3(const double* a, const double* b) {
-#pragma clang fp contract(off)
-    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
-}
 
 // the face with the valid ids `id` (all < n_verts: ma_face_ok)
 __device__ __forceinline__ void ml_face(const float* __restrict__ verts, const int id[3], MlFace& t) {
@@ -69,7 +65,7 @@ __device__ __forceinline__ void ml_face(const float* __restrict__ verts, const i
     const double ax = p[1][0] - p[0][0], ay = p[1][1] - p[0][1], az = p[1][2] - p[0][2];
     const double bx = p[2][0] - p[0][0], by = p[2][1] - p[0][1], bz = p[2][2] - p[0][2];
     const double N[3] = {ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx};
-    t.A2 = sqrt(ml_dot3(N, N));
+    t.A2 = sqrt(ma_dot(N, N));
     t.state = 1;
     if (!(isfinite(t.A2) && t.A2 > 0.0)) return;
     t.state = 0;
@@ -79,8 +75,8 @@ __device__ __forceinline__ void ml_face(const float* __restrict__ verts, const i
         const double u[3] = {p[a][0] - p[c][0], p[a][1] - p[c][1], p[a][2] - p[c][2]};
         const double w[3] = {p[b][0] - p[c][0], p[b][1] - p[c][1], p[b][2] - p[c][2]};
         const double e[3] = {p[b][0] - p[a][0], p[b][1] - p[a][1], p[b][2] - p[a][2]};
-        t.dot[c] = ml_dot3(u, w);
-        t.l2[c] = ml_dot3(e, e);
+        t.dot[c] = ma_dot(u, w);
+        t.l2[c] = ma_dot(e, e);
     }
 }
 
@@ -100,7 +96,7 @@ __device__ __forceinline__ double ml_share(const MlFace& t, int c, int mass) {
     return (ml_at(t.l2, a) * (ml_at(t.dot, a) / t.A2) + ml_at(t.l2, b) * (ml_at(t.dot, b) / t.A2)) * 0.125;
 }
 
-// the row of `key` in the ascending ids nbr[lo .. hi), or -1
+// the row of `key` in the ascending ids nbr[lo .. hi), or -1; leaves at the first equal row (meshedge.hpp's ma_lower does not)
 __device__ __forceinline__ long long ml_find(const int* __restrict__ nbr, long long lo, long long hi, int key) {
     while (lo < hi) {   // terminates: hi - lo at least halves
         const long long mid = lo + ((hi - lo) >> 1);
@@ -117,10 +113,8 @@ struct MlRows {
 
 __device__ __forceinline__ MlRows ml_rows(const int* __restrict__ vf_start, const int* __restrict__ nbr_start, long long v, int n_faces) {
     MlRows r;
-    r.fs = min(max((long long)vf_start[v], 0ll), 3ll * n_faces);
-    r.fe = min(max((long long)vf_start[v + 1], r.fs), 3ll * n_faces);
-    r.es = min(max((long long)nbr_start[v], 0ll), 6ll * n_faces);
-    r.ee = min(max((long long)nbr_start[v + 1], r.es), 6ll * n_faces);
+    ma_segment(vf_start, v, 3ll * n_faces, r.fs, r.fe);
+    ma_segment(nbr_start, v, 6ll * n_faces, r.es, r.ee);
     return r;
 }
 
@@ -272,7 +266,8 @@ __global__ __launch_bounds__(kImeshThreads) void k_ml_apply(const double* __rest
         const long long v = i / n_ch;
         const int c = (int)(i - v * n_ch);
         const double xv = (double)x[i];
-        const long long es = min(max((long long)nbr_start[v], 0ll), n_rows), ee = min(max((long long)nbr_start[v + 1], es), n_rows);
+        long long es, ee;
+        ma_segment(nbr_start, v, n_rows, es, ee);
         double acc = 0.0;
         for (long long k = es; k < ee; ++k) {   // terminates: ee - k strictly decreases
             const int n = nbr[k];
@@ -306,7 +301,7 @@ __global__ __launch_bounds__(kImeshThreads) void k_ml_curvature(const float* __r
         if (v >= n_verts) continue;
         const float pf[3] = {verts[3 * v + 0], verts[3 * v + 1], verts[3 * v + 2]};
         const double N[3] = {normal_sum[3 * v + 0], normal_sum[3 * v + 1], normal_sum[3 * v + 2]};
-        const double a = area[v], len = sqrt(ml_dot3(N, N));
+        const double a = area[v], len = sqrt(ma_dot(N, N));
         const unsigned flags = vert_flags[v];
         const bool ok = !(flags & 6u) && isfinite(pf[0]) && isfinite(pf[1]) && isfinite(pf[2]) && isfinite(a) && a > 0.0 && isfinite(len) &&
                         len > 0.0;
@@ -315,7 +310,8 @@ __global__ __launch_bounds__(kImeshThreads) void k_ml_curvature(const float* __r
         if (ok) {
             const double p[3] = {(double)pf[0], (double)pf[1], (double)pf[2]};
             double L[3] = {0.0, 0.0, 0.0};
-            const long long es = min(max((long long)nbr_start[v], 0ll), n_rows), ee = min(max((long long)nbr_start[v + 1], es), n_rows);
+            long long es, ee;
+            ma_segment(nbr_start, v, n_rows, es, ee);
             for (long long k = es; k < ee; ++k) {   // terminates: ee - k strictly decreases
                 const int n = nbr[k];
                 if ((unsigned)n >= (unsigned)n_verts) continue;   // nbr is the caller's: never followed out of bounds
@@ -327,12 +323,12 @@ __global__ __launch_bounds__(kImeshThreads) void k_ml_curvature(const float* __r
                 }
             }
             const double K[3] = {(-L[0]) / a, (-L[1]) / a, (-L[2]) / a};
-            const double mean = 0.5 * (ml_dot3(K, N) / len);
+            const double mean = 0.5 * (ma_dot(K, N) / len);
             const double gauss = (((flags & 1u) ? kMlPi : kMlTwoPi) - angle_sum[v]) / a;
             const double disc = mean * mean - gauss;
             const double root = sqrt(disc > 0.0 ? disc : 0.0);
             out[0] = mean;
-            out[1] = 0.5 * sqrt(ml_dot3(K, K));
+            out[1] = 0.5 * sqrt(ma_dot(K, K));
             out[2] = gauss;
             out[3] = mean + root;
             out[4] = mean - root;
@@ -367,7 +363,8 @@ __global__ __launch_bounds__(kImeshThreads) void k_ml_smooth(const float* __rest
         float out[3] = {p[0], p[1], p[2]};
         if (isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) && !(pin && (vert_flags[v] & 3))) {
             double acc[3] = {0.0, 0.0, 0.0}, s = 0.0;
-            const long long es = min(max((long long)nbr_start[v], 0ll), n_rows), ee = min(max((long long)nbr_start[v + 1], es), n_rows);
+            long long es, ee;
+            ma_segment(nbr_start, v, n_rows, es, ee);
             for (long long i = es; i < ee; ++i) {   // terminates: ee - i strictly decreases
                 const int n = nbr[i];
                 if ((unsigned)n >= (unsigned)n_verts) continue;   // nbr is the caller's: never followed out of bounds

@@ -40,7 +40,8 @@
 // Integer atomics only (min, add, or): minima, sums and disjunctions of integers do not depend on the order of arrival.  No
 // thread waits for another: no spin-wait, no grid-wide barrier; every loop ends by an argument of its own, stated at the loop.
 // The adjacency, the edges and the loop tables are the CALLER's arrays: no value read from them is followed out of bounds.
-// The constants, mesh_compact (the walk of k_mo_compact), k_mc_scan, k_mc_pad_words and cc_add_one are meshcommon.hpp's.
+// The constants, mesh_compact (the walk of k_mo_compact), k_mc_scan, k_mc_pad_words and cc_add_one are meshcommon.hpp's; the
+// clamped segment (ma_segment) is meshedge.hpp's.
 #pragma once
 
 constexpr double kMoVolLimit = 262144.0;  // 2^18: three such factors and six terms stay below 2^57
@@ -51,17 +52,13 @@ struct MoQuant {
     double scale;
 };
 
-// the caller's CSR starts, clamped to the rows the array has
-__device__ __forceinline__ void mo_segment(const int* __restrict__ start, int v, long long rows, long long& lo, long long& hi) {
-    lo = min(max((long long)start[v], 0ll), rows);
-    hi = min(max((long long)start[v + 1], lo), rows);
-}
-
-// number of valid faces on the undirected edge {a, b}: the entry (a, b) of the sorted neighbour CSR by bisection, 0 when absent
+// number of valid faces on the undirected edge {a, b}: the entry (a, b) of the sorted neighbour CSR by bisection, 0 when absent.
+// The adjacency is the caller's: ma_find's unclamped segment is not for it, the rows are clamped first (ma_segment); the loop
+// leaves at the first equal row, which ma_find's lower bound does not
 __device__ __forceinline__ int mo_edge_faces(const int* __restrict__ nbr_start, const int* __restrict__ nbr,
                                              const int* __restrict__ nbr_out, const int* __restrict__ nbr_in, long long rows, int a, int b) {
     long long lo, hi;
-    mo_segment(nbr_start, a, rows, lo, hi);
+    ma_segment(nbr_start, a, rows, lo, hi);
     while (lo < hi) {   // terminates: hi - lo strictly decreases (lo < mid + 1 <= hi or hi = mid < hi)
         const long long mid = lo + ((hi - lo) >> 1);
         const int n = nbr[mid];
@@ -103,8 +100,8 @@ __global__ __launch_bounds__(kImeshThreads) void k_mo_pairs(const int* __restric
         const int a = id[c], b = id[(c + 1) % 3];
         if (mo_edge_faces(nbr_start, nbr, nbr_out, nbr_in, 6 * (long long)n_faces, a, b) != 2) continue;
         long long alo, ahi, blo, bhi;
-        mo_segment(vf_start, a, 3 * (long long)n_faces, alo, ahi);
-        mo_segment(vf_start, b, 3 * (long long)n_faces, blo, bhi);
+        ma_segment(vf_start, a, 3 * (long long)n_faces, alo, ahi);
+        ma_segment(vf_start, b, 3 * (long long)n_faces, blo, bhi);
         const bool by_a = ahi - alo <= bhi - blo;
         const long long last = by_a ? ahi : bhi;
         const int other = by_a ? b : a;

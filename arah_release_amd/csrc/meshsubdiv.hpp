@@ -27,27 +27,17 @@
 //
 // NO ATOMICS of its own (the adjacency build's integer ones are the only ones): ranks come from mesh_prefix and k_mc_scan, the
 // statistics from per-workgroup sums that one workgroup adds up.  No thread waits for another: no spin-wait, no grid-wide
-// barrier; every loop ends by an argument of its own, stated at the loop.
+// barrier; every loop ends by an argument of its own, stated at the loop.  MeshAdj is meshadj.hpp's; the owner fill, the entry's
+// ends (ma_entry), the bisection (ma_find) and ma_finite / ma_d2 are meshedge.hpp's.
 //
 // NOT MEASURED AGAINST AN ALTERNATIVE: one lane per old vertex under Loop -- a fan's apex with n neighbours is summed by one
 // lane, n additions in ascending id, where meshadj.hpp spreads a long segment over a workgroup; keeping the three entries of
-// a face (12 bytes per face of scratch) instead of searching them again in each of the two face passes; the owner array instead
-// of a binary search of nbr_start.
+// a face (12 bytes per face of scratch) instead of searching them again in each of the two face passes; the owner array
+// (meshedge.hpp tells that one).
 #pragma once
 
 constexpr int kSbCounts = 13;   // meshing.SUBDIVIDE_COUNTS
 constexpr int kSbLoop = 1;      // method: 0 midpoint, 1 Loop
-
-__device__ __forceinline__ bool sb_finite(const float* __restrict__ verts, long long v) {
-    return isfinite(verts[3 * v + 0]) && isfinite(verts[3 * v + 1]) && isfinite(verts[3 * v + 2]);
-}
-
-// the squared distance of two float32 points in double: (dx dx + dy dy) + dz dz, every operation rounded on its own
-__device__ __forceinline__ double sb_d2(const float* __restrict__ p, const float* __restrict__ q) {
-#pragma clang fp contract(off)
-    const double dx = (double)p[0] - (double)q[0], dy = (double)p[1] - (double)q[1], dz = (double)p[2] - (double)q[2];
-    return (dx * dx + dy * dy) + dz * dz;
-}
 
 __device__ __forceinline__ float sb_mid(float lo, float hi) {
 #pragma clang fp contract(off)
@@ -84,18 +74,6 @@ __device__ __forceinline__ float sb_loop_rim(float p, float b0, float b1) {
     const double own = (double)p * 0.75;
     const double ring = ((double)b0 + (double)b1) * 0.125;
     return (float)(own + ring);
-}
-
-// the entry (lo, hi) of the neighbour CSR, hi in lo's ascending segment; -1 when it is not there (never, for an edge of a valid
-// face of the mesh the adjacency was built from)
-__device__ __forceinline__ int sb_find(const int* __restrict__ nbr_start, const int* __restrict__ nbr, int lo, int hi) {
-    int first = nbr_start[lo], last = nbr_start[lo + 1];
-    const int end = last;
-    while (first < last) {   // terminates: last - first at least halves
-        const int mid = first + ((last - first) >> 1);
-        if (nbr[mid] < hi) first = mid + 1; else last = mid;
-    }
-    return first < end && nbr[first] == hi ? first : -1;
 }
 
 // The count (FILL = false) or fill (FILL = true) walk of a workgroup over its chunk of the n elements, mesh_compact with a WEIGHT
@@ -139,29 +117,25 @@ __device__ __forceinline__ void sb_walk(long long n, int* __restrict__ blk_count
     }
 }
 
-__global__ __launch_bounds__(kImeshThreads) void k_sb_owner(int n_verts, const int* __restrict__ nbr_start, int* __restrict__ owner) {
+__global__ __launch_bounds__(kImeshThreads) void k_sb_owner(MeshAdj adj, int* __restrict__ owner) {
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_verts - v strictly decreases (step >= 1) and the loop ends when it reaches 0
-    for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < n_verts; v += step) {
-        const int last = nbr_start[v + 1];
-        for (int i = nbr_start[v]; i < last; ++i) owner[i] = (int)v;   // terminates: last - i strictly decreases.  i < 6 F
-    }
+    for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < adj.n_verts; v += step) ma_fill_owner(adj, v, owner);
 }
 
-__global__ __launch_bounds__(kImeshThreads) void k_sb_face_entries(const int* __restrict__ faces, int n_faces, int n_verts,
-                                                                   const int* __restrict__ nbr_start, const int* __restrict__ nbr,
-                                                                   int loop, int* __restrict__ fent, int* __restrict__ opp) {
+__global__ __launch_bounds__(kImeshThreads) void k_sb_face_entries(const int* __restrict__ faces, MeshAdj adj, int loop,
+                                                                   int* __restrict__ fent, int* __restrict__ opp) {
     const long long step = (long long)gridDim.x * blockDim.x;
     // terminates: n_faces - f strictly decreases (step >= 1) and the loop ends when it reaches 0
-    for (long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x; f < n_faces; f += step) {
+    for (long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x; f < adj.n_faces; f += step) {
         int id[3];
-        const bool ok = ma_face_ok(faces, f, n_verts, id);
+        const bool ok = ma_face_ok(faces, f, adj.n_verts, id);
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             int e = -1;
             if (ok) {
                 const int s = id[j], d = id[(j + 1) % 3];
-                e = sb_find(nbr_start, nbr, min(s, d), max(s, d));
+                e = ma_find(adj, min(s, d), max(s, d));
                 if (loop && e >= 0) opp[2 * (size_t)e + (s < d ? 0 : 1)] = id[(j + 2) % 3];   // e < nbr_start[V] <= 6 F
             }
             fent[3 * f + j] = ok && e >= 0 ? e : -1;
@@ -171,23 +145,21 @@ __global__ __launch_bounds__(kImeshThreads) void k_sb_face_entries(const int* __
 
 // the old vertices.  The walk is sb_walk's COUNT pass with the weight 0: nothing is numbered, the positions are written on the
 // way and the statistics (interior, rim) come out per workgroup
-__global__ __launch_bounds__(kImeshThreads) void k_sb_verts(const float* __restrict__ verts, int n_verts, const int* __restrict__ nbr_start,
-                                                            const int* __restrict__ nbr, const int* __restrict__ nbr_out,
-                                                            const int* __restrict__ nbr_in, int loop, int* __restrict__ blk_count,
-                                                            int* __restrict__ blk_stat, float* __restrict__ verts_out,
-                                                            int* __restrict__ vert_src) {
+__global__ __launch_bounds__(kImeshThreads) void k_sb_verts(const float* __restrict__ verts, MeshAdj adj, int loop,
+                             int* __restrict__ blk_count, int* __restrict__ blk_stat, float* __restrict__ verts_out,
+                             int* __restrict__ vert_src) {
     sb_walk<false, MeshNoState>(
-        n_verts, blk_count, (const int*)nullptr, blk_stat,
+        adj.n_verts, blk_count, (const int*)nullptr, blk_stat,
         [&](long long v, MeshNoState&, int& stat) {
             const float p[3] = {verts[3 * v + 0], verts[3 * v + 1], verts[3 * v + 2]};
             float out[3] = {p[0], p[1], p[2]};
-            if (loop && sb_finite(verts, v)) {
-                const int first = nbr_start[v], last = nbr_start[v + 1], k = last - first;
+            if (loop && ma_finite(verts, v)) {
+                const int first = adj.nbr_start[v], last = adj.nbr_start[v + 1], k = last - first;
                 bool all_regular = true, others_regular = true, all_finite = true;
                 int n_one = 0, rim[2] = {-1, -1};
                 double s[3] = {0.0, 0.0, 0.0};
                 for (int i = first; i < last; ++i) {   // terminates: last - i strictly decreases
-                    const int n = nbr[i], n_out = nbr_out[i], n_in = nbr_in[i];
+                    const int n = adj.nbr[i], n_out = adj.nbr_out[i], n_in = adj.nbr_in[i];
                     const bool regular = n_out == 1 && n_in == 1, one = n_out + n_in == 1;
                     all_regular = all_regular && regular;
                     others_regular = others_regular && (regular || one);
@@ -195,7 +167,7 @@ __global__ __launch_bounds__(kImeshThreads) void k_sb_verts(const float* __restr
                         if (n_one < 2) rim[n_one] = n;
                         ++n_one;
                     }
-                    all_finite = all_finite && sb_finite(verts, n);   // n is a vertex of a valid face: in [0, V)
+                    all_finite = all_finite && ma_finite(verts, n);   // n is a vertex of a valid face: in [0, V)
                     s[0] = s[0] + (double)verts[3 * (size_t)n + 0];
                     s[1] = s[1] + (double)verts[3 * (size_t)n + 1];
                     s[2] = s[2] + (double)verts[3 * (size_t)n + 2];
@@ -206,7 +178,7 @@ __global__ __launch_bounds__(kImeshThreads) void k_sb_verts(const float* __restr
 #pragma unroll
                     for (int a = 0; a < 3; ++a) out[a] = sb_loop_interior(p[a], s[a], keep, beta);
                     stat = 1;
-                } else if (n_one == 2 && others_regular && sb_finite(verts, rim[0]) && sb_finite(verts, rim[1])) {
+                } else if (n_one == 2 && others_regular && ma_finite(verts, rim[0]) && ma_finite(verts, rim[1])) {
 #pragma unroll
                     for (int a = 0; a < 3; ++a)
                         out[a] = sb_loop_rim(p[a], verts[3 * (size_t)rim[0] + a], verts[3 * (size_t)rim[1] + a]);
@@ -229,23 +201,20 @@ struct SbMark {
 
 // the marked edges in entry order; FILL: their ranks, positions and sources
 template <bool FILL>
-__global__ __launch_bounds__(kImeshThreads) void k_sb_marks(const float* __restrict__ verts, int n_verts, int n_entries_cap,
-                                                            const int* __restrict__ nbr_start, const int* __restrict__ nbr,
-                                                            const int* __restrict__ nbr_out, const int* __restrict__ nbr_in,
+__global__ __launch_bounds__(kImeshThreads) void k_sb_marks(const float* __restrict__ verts, MeshAdj adj, int n_entries_cap,
                                                             const int* __restrict__ owner, const int* __restrict__ opp, int loop,
                                                             int has_threshold, double max_len2, int* __restrict__ blk_count,
                                                             const int* __restrict__ blk_base, int* __restrict__ blk_stat,
                                                             int* __restrict__ rank, float* __restrict__ verts_out,
                                                             int* __restrict__ vert_src) {
-    const int n_entries = nbr_start[n_verts];
+    const int n_verts = adj.n_verts, n_entries = adj.nbr_start[n_verts];
     sb_walk<FILL, SbMark>(
         n_entries_cap, blk_count, blk_base, blk_stat,
         [&](long long i, SbMark& st, int& stat) {
-            if (i >= n_entries) return 0;
-            const int u = owner[i], v = nbr[i];
-            if (v <= u) return 0;
-            st.finite = sb_finite(verts, u) && sb_finite(verts, v);
-            const bool marked = has_threshold ? st.finite && sb_d2(verts + 3 * (size_t)u, verts + 3 * (size_t)v) > max_len2 : true;
+            int u, v;
+            if (i >= n_entries || !ma_entry(adj, owner, i, u, v)) return 0;
+            st.finite = ma_finite(verts, u) && ma_finite(verts, v);
+            const bool marked = has_threshold ? st.finite && ma_d2(verts + 3 * (size_t)u, verts + 3 * (size_t)v) > max_len2 : true;
             stat = marked && !st.finite ? 1 : 0;
             return marked ? 1 : 0;
         },
@@ -254,19 +223,20 @@ __global__ __launch_bounds__(kImeshThreads) void k_sb_marks(const float* __restr
             rank[i] = weight ? at : -1;
             if (!weight) return;
             // at < the marked edges <= the edges <= 3 F: the row lies below V + 3 F
-            const int u = owner[i], v = nbr[i];
+            const int u = owner[i], v = adj.nbr[i];
             const size_t row = (size_t)n_verts + (size_t)at;
             const float *lo = verts + 3 * (size_t)u, *hi = verts + 3 * (size_t)v;
             float out[3];
             if (!st.finite) {   // a copy of the lowest non-finite end: no arithmetic touches a NaN's payload
-                const float* src = sb_finite(verts, u) ? hi : lo;
+                const float* src = ma_finite(verts, u) ? hi : lo;
                 out[0] = src[0], out[1] = src[1], out[2] = src[2];
             } else {
                 bool stencil = false;
                 int c = 0, d = 0;
-                if (loop && nbr_out[i] == 1 && nbr_in[i] == 1) {   // a regular edge: each slot was written by its one face
+                if (loop && adj.nbr_out[i] == 1 && adj.nbr_in[i] == 1) {   // a regular edge: each slot was written by its one face
                     c = opp[2 * (size_t)i + 0], d = opp[2 * (size_t)i + 1];
-                    stencil = (unsigned)c < (unsigned)n_verts && (unsigned)d < (unsigned)n_verts && sb_finite(verts, c) && sb_finite(verts, d);
+                    stencil = (unsigned)c < (unsigned)n_verts && (unsigned)d < (unsigned)n_verts && ma_finite(verts, c) && ma_finite(verts,
+                               d);
                 }
 #pragma unroll
                 for (int a = 0; a < 3; ++a)
@@ -347,7 +317,7 @@ __global__ __launch_bounds__(kImeshThreads) void k_sb_faces(const int* __restric
             }
             sb_put_face(faces_out, face_src, row + 0, x, b, y, f);
             // the quad a, x, y, c along its shorter diagonal, ties to x-c; all four are vertices of the output
-            const bool ay = sb_d2(pos + 3 * (size_t)a, pos + 3 * (size_t)y) < sb_d2(pos + 3 * (size_t)x, pos + 3 * (size_t)c);
+            const bool ay = ma_d2(pos + 3 * (size_t)a, pos + 3 * (size_t)y) < ma_d2(pos + 3 * (size_t)x, pos + 3 * (size_t)c);
             if (ay) {
                 sb_put_face(faces_out, face_src, row + 1, a, x, y, f);
                 sb_put_face(faces_out, face_src, row + 2, a, y, c, f);

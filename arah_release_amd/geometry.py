@@ -421,6 +421,14 @@ def _mesh_args(verts_or_n_verts, faces, what):
     return n_verts, faces      # shape and dtype of the faces: the backend's own checks
 
 
+def _check_mesh_verts(verts, faces, what):
+    """The vertices of a mesh whose faces _mesh_args has checked: a floating-point (V, 3) tensor on the faces' device."""
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or not verts.dtype.is_floating_point:
+        raise ValueError("%s: verts must be a floating-point (V, 3) tensor" % what)
+    if verts.device != faces.device:
+        raise ValueError("%s: verts live on %s, faces on %s" % (what, verts.device, faces.device))
+
+
 def _cc_backend(faces):
     """The two kernels for a mesh on the GPU, their tensor specification for one on the host."""
     if faces.is_cuda:
@@ -593,10 +601,7 @@ def simplify_mesh(verts, faces, cell=None, resolution=None, bounds=None, positio
     check_simplify({"cell": cell, "resolution": resolution, "position": position, "quadric_reg": quadric_reg,
                     "target_faces": target_faces})
     n_verts, faces = _mesh_args(verts, faces, "simplify_mesh")
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or not verts.dtype.is_floating_point:
-        raise ValueError("simplify_mesh: verts must be a floating-point (V, 3) tensor")
-    if verts.device != faces.device:
-        raise ValueError("simplify_mesh: verts live on %s, faces on %s" % (verts.device, faces.device))
+    _check_mesh_verts(verts, faces, "simplify_mesh")
     attributes = dict(attributes or {})
     reserved = ("verts", "faces", "n_verts", "n_tris", "vert_src", "removed", "cell", "dims")
     reserved += ("quadric",) if position == "quadric" else ()                  # the keys a mode adds are reserved in that mode
@@ -777,10 +782,7 @@ def decimate_mesh(verts, faces, target_faces=None, ratio=None, max_error=None, q
     import math
     check_decimate(target_faces, ratio, max_error, quadric_reg, max_rounds)
     n_verts, faces = _mesh_args(verts, faces, "decimate_mesh")
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or not verts.dtype.is_floating_point:
-        raise ValueError("decimate_mesh: verts must be a floating-point (V, 3) tensor")
-    if verts.device != faces.device:
-        raise ValueError("decimate_mesh: verts live on %s, faces on %s" % (verts.device, faces.device))
+    _check_mesh_verts(verts, faces, "decimate_mesh")
     attributes = dict(attributes or {})
     reserved = ("verts", "faces", "n_verts", "n_tris", "vert_src", "face_src", "report")
     for name, t in attributes.items():
@@ -904,10 +906,7 @@ def subdivide_mesh(verts, faces, levels=1, method="midpoint", max_edge=None, max
     from . import meshing
     kw = check_subdivide({"levels": levels, "method": method, "max_edge": max_edge, "max_rounds": max_rounds, "max_faces": max_faces})
     n_verts, faces = _mesh_args(verts, faces, "subdivide_mesh")
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or not verts.dtype.is_floating_point:
-        raise ValueError("subdivide_mesh: verts must be a floating-point (V, 3) tensor")
-    if verts.device != faces.device:
-        raise ValueError("subdivide_mesh: verts live on %s, faces on %s" % (verts.device, faces.device))
+    _check_mesh_verts(verts, faces, "subdivide_mesh")
     reserved = ("verts", "faces", "n_verts", "n_tris", "vert_src", "vert_weights", "face_src", "report")
     attributes = _repair_attributes(attributes, n_verts, verts.device, reserved, "subdivide_mesh")
     backend, dev, names = _cc_backend(faces), verts.device, meshing.SUBDIVIDE_COUNTS
@@ -995,10 +994,7 @@ def flip_edges(verts, faces, criterion="delaunay", max_rounds=64):
     if isinstance(max_rounds, bool) or not isinstance(max_rounds, (int, np.integer)) or int(max_rounds) < 0:
         raise ValueError("flip_edges: max_rounds must be an integer >= 0, got %r" % (max_rounds,))
     n_verts, faces = _mesh_args(verts, faces, "flip_edges")
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or not verts.dtype.is_floating_point:
-        raise ValueError("flip_edges: verts must be a floating-point (V, 3) tensor")
-    if verts.device != faces.device:
-        raise ValueError("flip_edges: verts live on %s, faces on %s" % (verts.device, faces.device))
+    _check_mesh_verts(verts, faces, "flip_edges")
     backend, names = _cc_backend(faces), meshing.FLIP_COUNTS
     with torch.no_grad():
         v, f = verts.detach().to(torch.float32).contiguous(), faces
@@ -1153,10 +1149,7 @@ def isotropic_remesh(verts, faces, edge_length=None, iterations=5, lamb=0.5, pro
     kw = check_isotropic({"edge_length": edge_length, "iterations": iterations, "lamb": lamb, "project": project,
                           "max_rounds": max_rounds, "max_faces": max_faces})
     n_verts, faces = _mesh_args(verts, faces, "isotropic_remesh")
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or not verts.dtype.is_floating_point:
-        raise ValueError("isotropic_remesh: verts must be a floating-point (V, 3) tensor")
-    if verts.device != faces.device:
-        raise ValueError("isotropic_remesh: verts live on %s, faces on %s" % (verts.device, faces.device))
+    _check_mesh_verts(verts, faces, "isotropic_remesh")
     reserved = ("verts", "faces", "n_verts", "n_tris", "src_face", "src_bary", "report")
     attributes = _repair_attributes(attributes, n_verts, verts.device, reserved, "isotropic_remesh")
     backend, dev = _cc_backend(faces), verts.device
@@ -1283,10 +1276,7 @@ def mesh_topology(verts_or_n_verts, faces):
 
 def _smooth_args(verts, faces, adjacency, what):
     n_verts, faces = _mesh_args(verts, faces, what)
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or not verts.dtype.is_floating_point:
-        raise ValueError("%s: verts must be a floating-point (V, 3) tensor" % what)
-    if verts.device != faces.device:
-        raise ValueError("%s: verts live on %s, faces on %s" % (what, verts.device, faces.device))
+    _check_mesh_verts(verts, faces, what)
     return verts.detach().to(torch.float32).contiguous(), faces, (None if adjacency is None else tuple(adjacency))
 
 
@@ -1641,10 +1631,7 @@ def fill_holes(verts, faces, max_edges=64, attributes=None, adjacency=None):
     from . import meshing
     meshing.check_max_edges(max_edges, "fill_holes")
     n_verts, faces = _mesh_args(verts, faces, "fill_holes")
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or not verts.dtype.is_floating_point:
-        raise ValueError("fill_holes: verts must be a floating-point (V, 3) tensor")
-    if verts.device != faces.device:
-        raise ValueError("fill_holes: verts live on %s, faces on %s" % (verts.device, faces.device))
+    _check_mesh_verts(verts, faces, "fill_holes")
     attributes = _repair_attributes(attributes, n_verts, verts.device, ("verts", "faces", "n_verts", "n_tris", "vert_src", "filled"),
                                     "fill_holes")
     with torch.no_grad():
@@ -1680,10 +1667,7 @@ def _intersections(verts, faces, group, between, max_pairs, what):
     from . import meshing
     meshing.check_max_pairs(max_pairs, what)
     _mesh_args(verts, faces, what)
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or not verts.dtype.is_floating_point:
-        raise ValueError("%s: verts must be a floating-point (V, 3) tensor" % what)
-    if verts.device != faces.device:
-        raise ValueError("%s: verts live on %s, faces on %s" % (what, verts.device, faces.device))
+    _check_mesh_verts(verts, faces, what)
     with torch.no_grad():
         v32 = verts.detach().to(torch.float32).contiguous()
         if faces.is_cuda:

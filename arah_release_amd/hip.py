@@ -1032,9 +1032,9 @@ def mesh_adjacency(faces, n_verts):
     return vf_start, vf, nbr_start, nbr, nbr_out, nbr_in, flags, counts
 
 
-def _mesh_adj_args(verts, faces, adjacency, what):
-    """verts (V,3) float32 and faces on one GPU, and the eight arrays of mesh_adjacency (built here when None): -> (verts
-    contiguous, faces int32 contiguous, V, F, adjacency as contiguous device arrays)."""
+def _mesh_verts_faces(verts, faces, what, bounded=True):
+    """verts (V,3) float32 and faces (F,3) integer ids on one GPU, at most meshing.ADJACENCY_MAX_FACES faces (bounded=False: the
+    caller has a bound of its own): -> (verts contiguous, faces int32 contiguous, V, F)."""
     from . import meshing
     if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
         raise ValueError("%s: verts must be a (V, 3) float32 tensor" % what)
@@ -1042,20 +1042,39 @@ def _mesh_adj_args(verts, faces, adjacency, what):
     f, _, F = _mesh_cc_args(faces, V, what)
     if verts.device != f.device:
         raise ValueError("%s: verts live on %s, faces on %s" % (what, verts.device, f.device))
+    if bounded and F > meshing.ADJACENCY_MAX_FACES:
+        raise ValueError("%s: at most 2^28 faces, got %d" % (what, F))
+    return verts.detach().contiguous(), f, V, F
+
+
+def _mesh_adj_args(verts, faces, adjacency, what):
+    """verts (V,3) float32 and faces on one GPU, and the eight arrays of mesh_adjacency (built here when None): -> (verts
+    contiguous, faces int32 contiguous, V, F, adjacency as contiguous device arrays)."""
+    v, f, V, F = _mesh_verts_faces(verts, faces, what)
+    return v, f, V, F, _mesh_adj_arrays(f, V, F, adjacency, what)
+
+
+def _mesh_adj_only(faces, n_verts, adjacency, what):
+    """faces on the GPU over n_verts vertices and the eight arrays of mesh_adjacency (built here when None): -> (faces int32
+    contiguous, V, F, adjacency as contiguous device arrays)."""
+    from . import meshing
+    f, V, F = _mesh_cc_args(faces, n_verts, what)
     if F > meshing.ADJACENCY_MAX_FACES:
         raise ValueError("%s: at most 2^28 faces, got %d" % (what, F))
+    return f, V, F, _mesh_adj_arrays(f, V, F, adjacency, what)
+
+
+def _mesh_adj_arrays(f, V, F, adjacency, what):
+    """The eight arrays of mesh_adjacency of the checked faces f (built here when None), checked: -> contiguous device arrays."""
     if adjacency is None:
-        adjacency = mesh_adjacency(f, V)
-    else:
-        adjacency = tuple(adjacency)
-        shapes = ((V + 1,), (3 * F,), (V + 1,), (6 * F,), (6 * F,), (6 * F,), (V,), (8,))
-        if len(adjacency) != 8 or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != s or t.device != f.device
-                                      or t.dtype != (torch.uint8 if i == 6 else torch.int32)
-                                      for i, (t, s) in enumerate(zip(adjacency, shapes))):
-            raise ValueError("%s: adjacency must be the eight arrays of mesh_adjacency of these faces and vertices, on %s"
-                             % (what, f.device))
-        adjacency = tuple(t.contiguous() for t in adjacency)
-    return verts.detach().contiguous(), f, V, F, adjacency
+        return mesh_adjacency(f, V)
+    adjacency = tuple(adjacency)
+    shapes = ((V + 1,), (3 * F,), (V + 1,), (6 * F,), (6 * F,), (6 * F,), (V,), (8,))
+    if len(adjacency) != 8 or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != s or t.device != f.device
+                                  or t.dtype != (torch.uint8 if i == 6 else torch.int32)
+                                  for i, (t, s) in enumerate(zip(adjacency, shapes))):
+        raise ValueError("%s: adjacency must be the eight arrays of mesh_adjacency of these faces and vertices, on %s" % (what, f.device))
+    return tuple(t.contiguous() for t in adjacency)
 
 
 def mesh_collapse_round(verts, faces, need, reg=1e-3, max_cost=float("inf"), details=False, short_len2=None, long_len2=None):
@@ -1072,15 +1091,8 @@ def mesh_collapse_round(verts, faces, need, reg=1e-3, max_cost=float("inf"), det
     what = "mesh_collapse_round"
     need, reg, max_cost = meshing.collapse_args(need, reg, max_cost, what)
     bounds = meshing.collapse_bounds(short_len2, long_len2, what)
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
-        raise ValueError("%s: verts must be a (V, 3) float32 tensor" % what)
-    V = int(verts.shape[0])
-    f, _, F = _mesh_cc_args(faces, V, what)
-    if verts.device != f.device:
-        raise ValueError("%s: verts live on %s, faces on %s" % (what, verts.device, f.device))
-    if F > meshing.ADJACENCY_MAX_FACES:
-        raise ValueError("%s: at most 2^28 faces, got %d" % (what, F))
-    v, dev, i32 = verts.detach().contiguous(), f.device, torch.int32
+    v, f, V, F = _mesh_verts_faces(verts, faces, what)
+    dev, i32 = f.device, torch.int32
     with _on_device(dev):
         scratch = _mesh_cc_buf(dev, int(lib.arah_mesh_collapse_round_scratch_bytes(V, F)))
         verts_out = torch.empty(V, 3, dtype=torch.float32, device=dev)
@@ -1090,18 +1102,13 @@ def mesh_collapse_round(verts, faces, need, reg=1e-3, max_cost=float("inf"), det
         edge_pos = torch.empty(6 * F, 3, dtype=torch.float32, device=dev)
         edge_key = torch.empty(6 * F, dtype=torch.int64, device=dev)
         edge_reason = torch.empty(6 * F, dtype=torch.uint8, device=dev)
-        if bounds is not None:
-            _check(lib.arah_mesh_collapse_round_bounded(_ptr(v), C.c_int64(V), _ptr(f), C.c_int64(F), C.c_int32(need), C.c_double(reg),
-                                                        C.c_float(max_cost), C.c_double(bounds[0]), C.c_double(bounds[1]), _ptr(verts_out),
-                                                        _ptr(faces_out), _ptr(vert_src), _ptr(face_src), _ptr(counts), _ptr(edge_pos),
-                                                        _ptr(edge_key), _ptr(edge_reason), _ptr(scratch), C.c_size_t(scratch.numel()),
-                                                        _stream()), "arah_mesh_collapse_round_bounded")
-            out = (verts_out, faces_out, vert_src, face_src, counts)
-            return out + (edge_pos, edge_key, edge_reason) if details else out
-        _check(lib.arah_mesh_collapse_round(_ptr(v), C.c_int64(V), _ptr(f), C.c_int64(F), C.c_int32(need), C.c_double(reg),
-                                            C.c_float(max_cost), _ptr(verts_out), _ptr(faces_out), _ptr(vert_src), _ptr(face_src),
-                                            _ptr(counts), _ptr(edge_pos), _ptr(edge_key), _ptr(edge_reason), _ptr(scratch),
-                                            C.c_size_t(scratch.numel()), _stream()), "arah_mesh_collapse_round")
+        # the two entries differ by the two bounds, which the bounded one takes after max_cost
+        name = "arah_mesh_collapse_round" if bounds is None else "arah_mesh_collapse_round_bounded"
+        lens = () if bounds is None else (C.c_double(bounds[0]), C.c_double(bounds[1]))
+        _check(getattr(lib, name)(_ptr(v), C.c_int64(V), _ptr(f), C.c_int64(F), C.c_int32(need), C.c_double(reg), C.c_float(max_cost),
+                                  *lens, _ptr(verts_out), _ptr(faces_out), _ptr(vert_src), _ptr(face_src), _ptr(counts),
+                                  _ptr(edge_pos), _ptr(edge_key), _ptr(edge_reason), _ptr(scratch), C.c_size_t(scratch.numel()),
+                                  _stream()), name)
     out = (verts_out, faces_out, vert_src, face_src, counts)
     return out + (edge_pos, edge_key, edge_reason) if details else out
 
@@ -1117,14 +1124,9 @@ def mesh_subdivide_round(verts, faces, method="midpoint", max_len2=None):
     require_gpu()
     lib = load_library()
     what = "mesh_subdivide_round"
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
-        raise ValueError("%s: verts must be a (V, 3) float32 tensor" % what)
-    V = int(verts.shape[0])
-    f, _, F = _mesh_cc_args(faces, V, what)
-    if verts.device != f.device:
-        raise ValueError("%s: verts live on %s, faces on %s" % (what, verts.device, f.device))
+    v, f, V, F = _mesh_verts_faces(verts, faces, what, bounded=False)   # subdivide_args holds the bound on F, with V
     loop, max_len2 = meshing.subdivide_args(method, max_len2, V, F, what)
-    v, dev, i32 = verts.detach().contiguous(), f.device, torch.int32
+    dev, i32 = f.device, torch.int32
     with _on_device(dev):
         scratch = _mesh_cc_buf(dev, int(lib.arah_mesh_subdivide_round_scratch_bytes(V, F)))
         verts_out = torch.empty(V + 3 * F, 3, dtype=torch.float32, device=dev)
@@ -1149,15 +1151,8 @@ def mesh_flip_round(verts, faces, criterion="delaunay", salt=0, details=False):
     lib = load_library()
     what = "mesh_flip_round"
     crit, salt = meshing.flip_args(criterion, salt, what)
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
-        raise ValueError("%s: verts must be a (V, 3) float32 tensor" % what)
-    V = int(verts.shape[0])
-    f, _, F = _mesh_cc_args(faces, V, what)
-    if verts.device != f.device:
-        raise ValueError("%s: verts live on %s, faces on %s" % (what, verts.device, f.device))
-    if F > meshing.ADJACENCY_MAX_FACES:
-        raise ValueError("%s: at most 2^28 faces, got %d" % (what, F))
-    v, dev, i32 = verts.detach().contiguous(), f.device, torch.int32
+    v, f, V, F = _mesh_verts_faces(verts, faces, what)
+    dev, i32 = f.device, torch.int32
     with _on_device(dev):
         scratch = _mesh_cc_buf(dev, int(lib.arah_mesh_flip_round_scratch_bytes(V, F)))
         faces_out = torch.empty(F, 3, dtype=i32, device=dev)
@@ -1364,24 +1359,6 @@ def laplacian_solve(weight, area, adjacency, rhs, x0, pinned=None, mass_coef=0.0
                                              _ptr(r0), _ptr(scratch), C.c_size_t(nbytes), _stream()), "arah_mesh_solve_steps")
             done += n
     return x, iters, status, rr, r0, counts, classes
-
-
-def _mesh_adj_only(faces, n_verts, adjacency, what):
-    """faces on the GPU over n_verts vertices and the eight arrays of mesh_adjacency (built here when None): -> (faces int32
-    contiguous, V, F, adjacency as contiguous device arrays)."""
-    from . import meshing
-    f, V, F = _mesh_cc_args(faces, n_verts, what)
-    if F > meshing.ADJACENCY_MAX_FACES:
-        raise ValueError("%s: at most 2^28 faces, got %d" % (what, F))
-    if adjacency is None:
-        return f, V, F, mesh_adjacency(f, V)
-    adjacency = tuple(adjacency)
-    shapes = ((V + 1,), (3 * F,), (V + 1,), (6 * F,), (6 * F,), (6 * F,), (V,), (8,))
-    if len(adjacency) != 8 or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != s or t.device != f.device
-                                  or t.dtype != (torch.uint8 if i == 6 else torch.int32)
-                                  for i, (t, s) in enumerate(zip(adjacency, shapes))):
-        raise ValueError("%s: adjacency must be the eight arrays of mesh_adjacency of these faces and vertices, on %s" % (what, f.device))
-    return f, V, F, tuple(t.contiguous() for t in adjacency)
 
 
 def mesh_orient(verts, faces, policy="majority", adjacency=None, quant=None):

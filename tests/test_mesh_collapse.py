@@ -110,6 +110,15 @@ def mesh(name):
     return _MESH[name]
 
 
+def shaped(kind):
+    """Two shapes for the round tests on the device.  whole_waves: grid10, 640 = 10 x 64 neighbour entries (every other case leaves
+    a part of a wave).  isolated: grid8 between two vertices that no face names, the first id and the last."""
+    verts, faces = mesh("grid10" if kind == "whole_waves" else "grid8")
+    if kind == "isolated":
+        verts, faces = torch.cat([verts[:1] + 0.25, verts, verts[-1:] + 0.25]), faces + 1
+    return verts, faces
+
+
 def spec(name, need=10 ** 6, reg=1e-3, max_cost=float("inf")):
     """meshing.mesh_collapse_round of a case on the host with its details, computed once and shared; never modified."""
     from arah_release_amd import meshing

@@ -7,7 +7,7 @@ import ctypes as C
 import pytest
 import torch
 
-from test_mesh_collapse import NAMES, counts_of, mesh, same_bits, spec
+from test_mesh_collapse import NAMES, counts_of, mesh, same_bits, shaped, spec
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -42,6 +42,17 @@ def test_kernels_are_the_specification(name):
         assert c["applied"] > 0 and mesh(name)[1].shape[0] % 256 != 0
     # again, from faces of another integer type: the order of arrival does not show
     same_bits(run(name, faces_dtype=torch.int64), first, (name, "again"), n=8)
+
+
+@pytest.mark.parametrize("kind", ["whole_waves", "isolated"])
+def test_whole_waves_of_entries_and_isolated_vertices(kind):
+    from arah_release_amd import hip, meshing
+    verts, faces = shaped(kind)
+    adj = meshing.mesh_adjacency(faces, verts.shape[0])
+    assert (int(adj[2][-1]) % 64 == 0) == (kind == "whole_waves") and (int(adj[7][6]) == 2) == (kind == "isolated")
+    for bounds in ({}, {"short_len2": 1.5, "long_len2": 9.0}):
+        want = meshing.mesh_collapse_round(verts, faces, 10 ** 6, details=True, **bounds)
+        same_bits(hip.mesh_collapse_round(verts.to(DEV), faces.to(DEV), 10 ** 6, details=True, **bounds), want, (kind, bounds), n=8)
 
 
 @pytest.mark.parametrize("need", [0, 1, 7, 10 ** 6])

@@ -7,7 +7,7 @@ import ctypes as C
 import pytest
 import torch
 
-from test_mesh_collapse import mesh
+from test_mesh_collapse import mesh, shaped
 from test_mesh_subdivide import CASES, counts_of, modes, same_bits, spec, thresholds
 
 pytestmark = pytest.mark.gpu
@@ -37,6 +37,17 @@ def test_kernels_are_the_specification(name):
         c = counts_of(spec(name, "midpoint", thresholds(name)[0]))
         assert min(c["faces_%d" % m] for m in range(4)) > 0 and c["marked"] > 1024
         assert counts_of(spec(name, "loop"))["interior"] == mesh(name)[0].shape[0] > 1024
+
+
+@pytest.mark.parametrize("kind", ["whole_waves", "isolated"])
+def test_whole_waves_of_entries_and_isolated_vertices(kind):
+    from arah_release_amd import hip, meshing
+    verts, faces = shaped(kind)
+    adj = meshing.mesh_adjacency(faces, verts.shape[0])
+    assert (int(adj[2][-1]) % 64 == 0) == (kind == "whole_waves") and (int(adj[7][6]) == 2) == (kind == "isolated")
+    for method, max_len2 in (("midpoint", None), ("midpoint", 1.5), ("loop", None)):
+        want = meshing.mesh_subdivide_round(verts, faces, method, max_len2)
+        same_bits(hip.mesh_subdivide_round(verts.to(DEV), faces.to(DEV), method, max_len2), want, (kind, method, max_len2))
 
 
 def test_empty_meshes_write_their_counts():
